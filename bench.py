@@ -11,7 +11,13 @@ One "step" = one pass of the hot path over one batch of synthetic clean raw alre
   all-reduce] -> Adam.  Workload = BASELINE.json configs[1]: 4x1424x2128 packed raw per image, fp32; 8 frames per GPU
   (weak scaling: the per-GPU batch is fixed as N grows, so N=8 is configs[3]: 8xMI355X data parallel, global batch 64).
 Prints ONE JSON line (rank 0).  value = total raw pixels of all ranks / wall time of the timed K steps
-(barrier + device sync on both sides, MAX over ranks).
+(barrier + device sync on both sides, MAX over ranks); ms_per_step = that wall time / K.
+
+A plain run does only what that line needs: set-up, W warm-up steps, the K timed steps, the line.  --full adds, measured after the
+timed steps: per-rank step times and the exposed all-reduce cost (N > 1), the U-Net and sampler rooflines, the alt_* legs (fp16x2
+products, bf16, 'Pg', eval sweep) and the CPU baseline (--no-alt / --no-cpu-baseline trim them).
+--dump-outputs DIR writes what the last timed step computed (loss, output, noisy input, parameters, gradients) as DIR/<name>.npy;
+the inputs depend only on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -68,6 +74,27 @@ def load_traffic():
                 t.pop('sampler_bytes_per_pixel', None)
                 t.pop('sampler_valu_lane_ops_per_pixel', None)
     return t
+
+
+DUMP_SAMPLE = 1 << 20          # elements kept of each large array: a fixed, seeded choice (4.2 MB each; params are written whole, 31.0 MB)
+
+
+def dump_outputs(model, loss, out_dir):
+    """What the last timed step handed its caller: the loss, the network output, the noisy input the sampler made, the updated flat
+    parameters and the flat gradient, as float32 / float64 .npy files (43.6 MB at the default size).  A large array is sampled at sorted
+    indices drawn with replacement from a fixed seed, so an element may appear twice; the same arguments give the same indices."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(t, seed):
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(seed).integers(0, flat.numel(), DUMP_SAMPLE))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        return flat.float().cpu().numpy()
+    arrays = {'loss': np.array([loss], dtype=np.float64), 'output': sample(model.output, 1), 'input': sample(model.input, 2),
+              'params': model.netG.flat_params.detach().float().cpu().numpy(), 'grads': sample(model.optimizer_G.grads, 3)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
 
 
 def timed_events(fn, reps):
@@ -291,7 +318,12 @@ def main():
     ap.add_argument('--no-alt', action='store_true', help='skip the alt_fp16x2_products leg (profiling runs: only the default kernels in the trace)')
     ap.add_argument('--prefetch', type=int, default=1, help='1: synthesise batch i+1 on the side stream during step i (Engine.train default); 0: serial')
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'bf16'], help="U-Net precision; the contract's metric is quoted on fp32 (BASELINE configs[1]); bf16 = configs[2]")
+    ap.add_argument('--full', action='store_true', help='after the timed steps, also measure everything beside the headline (per-rank times, all-reduce '
+                    'cost, rooflines, alt_* legs, eval sweep, CPU baseline) and put it on the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step computed as DIR/<name>.npy (float32 / float64)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     from eld_amd import dist as D
     world, rank, local = D.init()
@@ -353,11 +385,14 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
-    per_rank, exchange = None, None
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, loss, args.dump_outputs)
+    per_rank, exchange = None, None
+    if world > 1 and args.full:
         allr = [torch.zeros(1, dtype=torch.float64, device=dev) for _ in range(world)]
         torch.distributed.all_gather(allr, torch.tensor([dt_local / args.steps * 1e3], dtype=torch.float64, device=dev))
         per_rank = [round(float(v.item()), 3) for v in allr]
@@ -396,7 +431,7 @@ def main():
     if per_rank is not None:
         res['per_rank_ms_per_step'] = per_rank
         res['allreduce'] = exchange
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernels, measured live with HIP events on the launch stream ----------------------
         traffic = load_traffic()
         res['roofline'], peak, x3 = unet_roofline(model, B, Hh, Ww, args.precision, dev, traffic)
@@ -582,6 +617,7 @@ def main():
         del yb, zb
         if world == 1 and not args.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(Hh, Ww)
+    if rank == 0:
         print(json.dumps(res))
     if world > 1:
         torch.distributed.barrier()

@@ -2,7 +2,8 @@
 187-190).  One process per GPU, torch.distributed backend "nccl" (= RCCL over xGMI on ROCm).  Needs >= 2 GPUs: on a 1-GPU box
 every test here skips (the same logic runs on gloo in tests/test_dist_cpu.py and tests/test_model_gpu.py).
 
-Checked for world = 2 and, when the node has them, 4 and 8 ranks:
+Checked for world = 2 and, when the node has them, 4 ranks (not 8: beside the test's own process, eight ranks are nine processes
+holding devices at once, and the GPU suite keeps that number at six or fewer; world 8 runs on gloo in tests/test_dist_cpu.py):
   * replicas are identical after the rank-0 broadcast and stay identical after training steps;
   * N ranks x (B/N images each) with the bucketed all-reduce overlapped with the backward == one process stepping on the
     B-image global batch (loss and weights);
@@ -56,7 +57,7 @@ def _worker(rank, world, port, tmp, q, steps, gbatch):
     T.distributed.destroy_process_group()
 
 
-@pytest.mark.parametrize('world', [2, 4, 8])
+@pytest.mark.parametrize('world', [2, 4])
 def test_rccl_data_parallel_equals_global_batch(eld_lib, tmp_path, world):
     if _ngpu() < world:
         pytest.skip('needs %d GPUs, this box has %d' % (world, _ngpu()))
@@ -100,7 +101,7 @@ def test_rccl_data_parallel_equals_global_batch(eld_lib, tmp_path, world):
 
 
 def test_bench_multi_gpu_line(eld_lib, tmp_path):
-    """bench.py under torchrun with the nccl backend prints one JSON line with per-rank timings."""
+    """bench.py --full under torchrun with the nccl backend prints one JSON line with per-rank timings."""
     if _ngpu() < 2:
         pytest.skip('needs 2 GPUs, this box has %d' % _ngpu())
     import json
@@ -110,7 +111,7 @@ def test_bench_multi_gpu_line(eld_lib, tmp_path):
     s = socket.socket(); s.bind(('127.0.0.1', 0)); port = s.getsockname()[1]; s.close()
     r = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                         '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '1',
-                        '--height', '256', '--width', '256', '--no-cpu-baseline'], capture_output=True, text=True, timeout=900)
+                        '--height', '256', '--width', '256', '--full', '--no-cpu-baseline'], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
     assert line['n_gpus'] == 2 and len(line['per_rank_ms_per_step']) == 2 and line['allreduce']['bytes'] == 4 * 7760484

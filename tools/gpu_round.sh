@@ -19,7 +19,7 @@ T=$1; STEP=$2; shift 2
 O=gpurun_out/$T; mkdir -p $O
 case $STEP in
   tests) ( time timeout 2400 python -m pytest ${@:-tests} -m gpu -q -x ) > $O/pytest.log 2>&1; grep -n "passed\|failed\|error" $O/pytest.log | tail -3 ;;
-  bench) timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; python -c "
+  bench) timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; python -c "
 import json; r = json.load(open('$O/bench.json')); print(r['value'], r['ms_per_step'], r['roofline']['frac'], r['alt_bf16']['ms_per_step'], r['alt_bf16']['roofline']['frac'])" ;;
   trace) p=${1:-fp32}; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$p -o t -- python bench.py --precision $p --no-cpu-baseline --no-alt --steps 5 --warmup 1 > $O/bench_$p.json 2> $O/err_$p.txt
          f=$(find $O/prof_$p -name 't_kernel_trace.csv' | head -1); python tools/step_trace.py $f 3 $O/step_trace_$p.md > /dev/null; python tools/step_breakdown.py $f 3 $O/kernel_stats_$p.md | head -30; rm -rf $O/prof_$p ;;
