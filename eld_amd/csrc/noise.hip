@@ -816,6 +816,42 @@ extern "C" int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int
 }
 
 // ---------------------------------------------------------------------------------------------
+// X-Trans sensor mosaic -> packed, normalised raw (the X-Trans branch of the dataset pack, dataset/sid_dataset.py:199-239), one pass:
+//   out[c][i][j] = clip((float(im[row][col]) - black) / (white - black), 0, 1),  (row, col) = xtrans_kernel's index map of (c, i, j)
+// float32 as NumPy evaluates it (uint16 -> float32 exact, one rounding per op, true division): bit-exact.  One thread per packed element.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pack_raw_xtrans_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, int Hm, int Wm,
+                                                              float black, float denom) {
+    const int n = blockIdx.y;
+    const size_t hw = (size_t)h * w, total = 9 * hw;
+    const uint16_t* s = im + (size_t)n * Hm * Wm;
+    float* d = out + (size_t)n * total;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const int c = (int)(e / hw);
+        const int r = (int)(e - (size_t)c * hw);
+        const int i = r / w, j = r - i * w;
+        int row, col;
+        if (c < 5) { row = 6 * (i >> 1) + XT_RC[c][i & 1][j & 1][0]; col = 6 * (j >> 1) + XT_RC[c][i & 1][j & 1][1]; }
+        else { row = 3 * i + XT_RC3[c - 5][0]; col = 3 * j + XT_RC3[c - 5][1]; }
+        const float v = ((float)s[(size_t)row * Wm + col] - black) / denom;
+        d[e] = fminf(fmaxf(v, 0.f), 1.f);
+    }
+}
+
+// uint16 mosaic [N, Hm, Wm] -> packed float32 [N, 9, 2*(Hm/6), 2*(Wm/6)] (sides truncated to whole 6x6 cells, as eld_pack_xtrans)
+extern "C" int eld_pack_raw_xtrans_u16(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point, void* stream) {
+    if (N < 0 || Hm < 0 || Wm < 0 || !(white_point > black_level)) return ELD_EINVAL;
+    const int h = 2 * (Hm / 6), w = 2 * (Wm / 6);
+    const size_t total = (size_t)9 * h * w;
+    if (N == 0 || total == 0) return 0;
+    if (!mosaic || !packed) return ELD_EINVAL;
+    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
+    ELD_LAUNCH(pack_raw_xtrans_kernel, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Augmentation (sid_dataset.py:344-352): out = transpose?(flipW?(flipH?(x))) per image, optional clip (:354).
 //   no transpose: out[c][i][j] = x[c][fh(i)][fw(j)]      transpose: out[c][i][j] = x[c][fh(j)][fw(i)]
 // ---------------------------------------------------------------------------------------------

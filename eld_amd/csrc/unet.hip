@@ -217,7 +217,7 @@ struct Plan {
 
 int make_plan(Plan& P, int N, int H, int W, int in_ch, int out_ch) {
     if (N < 1 || H < 16 || W < 16 || (H % 16) || (W % 16)) return ELD_EINVAL;     // 4 pool levels (Unet.py:51-63)
-    if (in_ch < 1 || in_ch > 16 || out_ch < 1 || out_ch > 4) return ELD_ENOTSUP;
+    if (in_ch < 1 || in_ch > 16 || out_ch < 1 || out_ch > 16) return ELD_ENOTSUP;
     P.N = N; P.H = H; P.W = W; P.in_ch = in_ch; P.out_ch = out_ch;
     P.nparams = build_layers(in_ch, out_ch, P.L);
     for (int l = 0; l < NLEV; ++l) { P.Hl[l] = H >> l; P.Wl[l] = W >> l; }
@@ -248,8 +248,8 @@ int make_plan(Plan& P, int N, int H, int W, int in_ch, int out_ch) {
     }
     P.gA = take(act(0, 32));
     P.gB = take(act(0, 32));
-    P.head_part = take(head_train_ws_floats());
-    size_t pmax = head_bwd_ws_floats();
+    P.head_part = take(head_train_ws_floats(out_ch));       // out_ch <= 4: the sizes of the quad-lane head (unet_misc.hip), unchanged
+    size_t pmax = head_bwd_ws_floats(out_ch);
     pmax = pmax > conv_first_wgrad_ws_floats() ? pmax : conv_first_wgrad_ws_floats();
     pmax = pmax > colsum_ws_floats(256) ? pmax : colsum_ws_floats(256);
     for (int i = 0; i < NLAYERS; ++i) {
@@ -318,7 +318,13 @@ int pack_weights(const Plan& P, const float* params, float* ws, int dir, hipStre
         J.src_off = d.w_off; J.Cout = d.cout; J.Cin = d.cin; J.Cinp = d.cin;
         if (d.kind == 0) {
             J.T = 9;
-            if (!for_backward) { J.kind = PACK_CONV_FWD; J.Cinp = (d.cin + 15) / 16 * 16; J.dst_off = P.wp_fwd[i]; if (bf16 && i == L_E0A) continue; }
+            if (!for_backward) {
+                J.kind = PACK_CONV_FWD; J.Cinp = (d.cin + 15) / 16 * 16; J.dst_off = P.wp_fwd[i];
+                if (bf16 && i == L_E0A) {
+                    if (d.cin <= 4) continue;        // conv_first.hip reads the fp32 weights directly
+                    J.Cinp = 32;                     // more planes: the generic bf16 conv on the zero-padded NHWC32 input (bf16 K granule: 32 channels)
+                }
+            }
             else if (i != L_E0A) { J.kind = PACK_CONV_BWD; J.dst_off = P.wp_bwd[i]; }
             else continue;
         } else if (d.kind == 1) {
@@ -459,9 +465,11 @@ int conv_fwd_bf16(const bf16_t* in0, int C0, const bf16_t* in1, int C1, const bf
 int unet_forward_bf16(const Plan& P, const float* x, const float* prm, float* out, float* ws, hipStream_t st, const HeadLoss* hl = nullptr, unsigned* have_out = nullptr,
                       bool infer = false) {
     const int N = P.N;
-    if (P.in_ch > 4) return ELD_ENOTSUP;
+    const bool first_direct = P.in_ch <= 4;       // conv1_1 straight from the NCHW planes (conv_first.hip); more planes: NHWC32 bf16 in ws + P.x16
     RC(pack_weights(P, prm, ws, hl ? PACK_BOTH : PACK_FWD, st, true));
-    if (!hl && !infer) {   // keep the fp32 input for the first layer's weight gradient (the fused training forward leaves it with the caller: see FusedFwd)
+    if (!first_direct) {   // (64 B per pixel: the size of the fp32 plan's NHWC16 region; the backward's weight gradient reads it there)
+        RC(launch_nchw_to_nhwc32_bf16(x, reinterpret_cast<bf16_t*>(ws + P.x16), N, P.in_ch, P.H, P.W, st));
+    } else if (!hl && !infer) {   // keep the fp32 input for the first layer's weight gradient (the fused training forward leaves it with the caller: see FusedFwd)
         hipError_t e = hipMemcpyAsync(ws + P.x16, x, (size_t)N * P.in_ch * P.H * P.W * sizeof(float), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) return (int)e;
     }
@@ -470,13 +478,15 @@ int unet_forward_bf16(const Plan& P, const float* x, const float* prm, float* ou
     // launches that would otherwise re-read the saved 32-channel tensor): written by conv1_1's and conv9_1's epilogues where those kernels are the
     // ones that run (conv_first's MFMA kernel; conv_bfs for the 64 -> 32 layer) -- 8 bytes per pixel instead of 64 in the backward
     const bool bfs0 = !infer && bfs_takes(32, 32, N, P.H, P.W) && !(debug_kernel_mask(-1) & 128);
-    const bool c_ea0 = bfs0 && conv_first_writes_codes(P.in_ch), c_da0 = bfs0 && bfs_takes(32, 64, N, P.H, P.W);
+    const bool c_ea0 = bfs0 && first_direct && conv_first_writes_codes(P.in_ch), c_da0 = bfs0 && bfs_takes(32, 64, N, P.H, P.W);
     if (have_out) *have_out = (c_ea0 ? CODES_EA0 : 0u) | (c_da0 ? CODES_DA0 : 0u);
     for (int l = 0; l < NLEV; ++l) {
         const LayerDef& A = P.L[2 * l]; const LayerDef& Bd = P.L[2 * l + 1];
-        if (l == 0)
+        if (l == 0 && first_direct)
             RC(launch_conv_first_fwd_bf16(x, prm + A.w_off, prm + A.b_off, B(P.ea[0]), N, P.in_ch, P.H, P.W, 1, st,
                                           c_ea0 ? reinterpret_cast<unsigned*>(ws + P.cd_ea[0]) : nullptr));
+        else if (l == 0)
+            RC(conv_fwd_bf16(B(P.x16), 32, nullptr, 0, B(P.wp_fwd[0]), prm + A.b_off, B(P.ea[0]), N, P.H, P.W, chan(0), 1, st));
         else
             RC(conv_fwd_bf16(B(P.pool[l - 1]), chan(l - 1), nullptr, 0, B(P.wp_fwd[2 * l]), prm + A.b_off, B(P.ea[l]), N, P.Hl[l], P.Wl[l], chan(l), 1, st));
         // layers on the DMA kernel (conv_bfd.hip) write the pooled tensor from their epilogue
@@ -603,20 +613,20 @@ int conv_bwd_data_bf16(const bf16_t* g, const bf16_t* wb, bf16_t* out0, bf16_t* 
     return launch_conv(a, CONV_3X3, st);
 }
 
+// Cin_real > 0: the weight tensor's input channels when x0 is zero padded beyond them (conv1_1 with more than 4 planes)
 int conv_wgrad_bf16(const bf16_t* g, int Cout, const bf16_t* x0, int C0, const bf16_t* x1, int C1, float* dw, float* db, float* part,
-                    int N, int H, int W, hipStream_t st) {
+                    int N, int H, int W, hipStream_t st, int Cin_real = 0) {
     const WgradGeom q = wgrad_geom(CONV_3X3, Cout, C0 + C1, N, H, W, (C0 % 32 || C1 % 32) ? 0 : 3);
     WgradArgs a = {};
     a.g = g; a.CA = Cout; a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.N = N; a.H = H; a.W = W; a.dtype = DT_BF16;
     a.part = part; a.bpart = db ? part + (size_t)q.psplit * q.T * q.CA * q.CBp : nullptr; a.CBp = q.CBp; a.psplit = q.psplit;
     a.wgrad8 = q.w8;
     RC(launch_wgrad(a, CONV_3X3, st));
-    return launch_wgrad_reduce(part, a.bpart, dw, db, q.psplit, q.T, q.CA, q.CBp, C0 + C1, st);
+    return launch_wgrad_reduce(part, a.bpart, dw, db, q.psplit, q.T, q.CA, q.CBp, Cin_real > 0 ? Cin_real : C0 + C1, st);
 }
 
 int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float* grd, float* ws, hipStream_t st, BucketMarks& marks, const FusedFwd& fused) {
     const int N = P.N;
-    if (P.in_ch > 4) return ELD_ENOTSUP;
     if (!fused.packed) RC(pack_weights(P, prm, ws, PACK_BWD, st, true));
     auto B = [&](size_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
     bf16_t* cur = B(P.gA); bf16_t* oth = B(P.gB); float* part = ws + P.part;
@@ -664,7 +674,10 @@ int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float
                               l == 0 && (fused.codes & CODES_EA0) ? reinterpret_cast<const unsigned*>(ws + P.cd_ea[0]) : nullptr));
         swap();
         if (l == 0) {
-            RC(launch_conv_first_wgrad_bf16(cur, fused.x ? fused.x : ws + P.x16, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, P.in_ch, H, W, st));
+            if (P.in_ch <= 4)
+                RC(launch_conv_first_wgrad_bf16(cur, fused.x ? fused.x : ws + P.x16, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, P.in_ch, H, W, st));
+            else      // the zero-padded NHWC32 bf16 input the forward left in ws + P.x16; only the in_ch real channels are written to dw
+                RC(conv_wgrad_bf16(cur, C, B(P.x16), 32, nullptr, 0, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, H, W, st, P.in_ch));
             RC(marks.done(P, ia, st));
             break;
         }
@@ -685,7 +698,7 @@ int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float
 // C ABI
 // ====================================================================================================
 extern "C" int eld_unet_param_offsets(int in_ch, int out_ch, int64_t* offsets) {
-    if (!offsets || in_ch < 1 || in_ch > 16 || out_ch < 1 || out_ch > 4) return ELD_EINVAL;
+    if (!offsets || in_ch < 1 || in_ch > 16 || out_ch < 1 || out_ch > 16) return ELD_EINVAL;
     LayerDef L[NLAYERS];
     const size_t n = build_layers(in_ch, out_ch, L);
     for (int i = 0; i < NLAYERS; ++i) { offsets[2 * i] = (int64_t)L[i].w_off; offsets[2 * i + 1] = (int64_t)L[i].b_off; }

@@ -10,11 +10,11 @@ int launch_maxpool_bwd(const float* act, const float* dp, const float* skip, flo
 int launch_maxpool_bwd_codes(const unsigned* pool_codes, const unsigned* slope_codes, const float* dp, const float* skip, float* g, int N, int Ho, int Wo, int C,
                              hipStream_t st);
 int launch_head_fwd(const float* in, const float* w, const float* b, float* out, int N, int H, int W, int OC, hipStream_t st);
-size_t head_bwd_ws_floats();
+size_t head_bwd_ws_floats(int OC);
 int launch_head_bwd(const float* dout, const float* act, const float* w, float* g, float* dw, float* db, float* part,
                     int N, int H, int W, int OC, hipStream_t st);
 // fused training head (forward + loss + backward in one pass over conv9_2's output): see unet_misc.hip
-size_t head_train_ws_floats();
+size_t head_train_ws_floats(int OC);
 int launch_head_train(const void* act, int bf16, const float* w, const float* b, const float* tgt, float* out, void* g, float* part, float* loss,
                       int N, int H, int W, int OC, int mse, float grad_scale, hipStream_t st);
 int launch_head_train_reduce(const float* part, float* dw, float* db, int N, int H, int W, int OC, int bf16, hipStream_t st);
@@ -47,3 +47,15 @@ int launch_head_bwd_bf16(const float* dout, const bf16_t* act, const float* w, b
                          int N, int H, int W, int OC, hipStream_t st);
 int launch_colsum_bf16(const bf16_t* x, float* out, float* part, size_t P, int C, hipStream_t st);
 int launch_conv_first_wgrad_bf16(const bf16_t* g, const float* x, float* dw, float* db, float* part, int N, int Cin, int H, int W, hipStream_t st);
+
+// the U-Net's ends for more than 4 planes (unet_wide.hip): the head for 5 <= OC <= 16 (the OC <= 4 launchers above hand such calls over) and the
+// bf16 network's conv1_1 operand for 5 <= Cin <= 16 (NHWC 32-channel bf16, zero padded)
+size_t head_wide_bwd_ws_floats(int OC);
+size_t head_wide_train_ws_floats(int OC);
+int launch_head_wide_fwd(const void* act, int bf16, const float* w, const float* b, float* out, int N, int H, int W, int OC, hipStream_t st);
+int launch_head_wide_bwd(const float* dout, const void* act, int bf16, const float* w, void* g, float* dw, float* db, float* part,
+                         int N, int H, int W, int OC, hipStream_t st);
+int launch_head_wide_train(const void* act, int bf16, const float* w, const float* b, const float* tgt, float* out, void* g, float* part, float* loss,
+                           int N, int H, int W, int OC, int mse, float grad_scale, hipStream_t st);
+int launch_head_wide_train_reduce(const float* part, float* dw, float* db, int N, int H, int W, int OC, hipStream_t st);
+int launch_nchw_to_nhwc32_bf16(const float* x, bf16_t* y, int N, int C, int H, int W, hipStream_t st);

@@ -163,7 +163,7 @@ int launch_maxpool_bwd(const float* act, const float* dp, const float* skip, flo
 }
 
 // ------------------------------------------------------------------------------------------------
-// conv10_1: 1x1, 32 -> OC (<= 4), no activation; NHWC in, NCHW out (Unet.py:46,88)
+// conv10_1: 1x1, 32 -> OC (<= 4; 5..16: unet_wide.hip), no activation; NHWC in, NCHW out (Unet.py:46,88)
 // ------------------------------------------------------------------------------------------------
 // LPP lanes per pixel (8 x 4 fp32 channels / 4 x 8 bf16 channels: a wave reads whole pixels, 1 KiB contiguous per instruction); the 32-channel sum
 // is formed as per-lane fma chains + a butterfly over the pixel's lanes -- the SAME order as the fused training head (head_train_kernel), so the
@@ -226,6 +226,7 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ in,
 }
 
 int launch_head_fwd(const float* in, const float* w, const float* b, float* out, int N, int H, int W, int OC, hipStream_t st) {
+    if (OC > 4) return launch_head_wide_fwd(in, 0, w, b, out, N, H, W, OC, st);
     const size_t total = (size_t)N * H * W;
     if (!total) return 0;
     ELD_LAUNCH(head_fwd_kernel<float>, dim3((unsigned)min((total + 31) / 32, (size_t)16384)), dim3(256), 0, st, in, w, b, out, N, (size_t)H * W, OC);
@@ -328,10 +329,11 @@ __global__ __launch_bounds__(256) void head_bwd_reduce_kernel(const float* __res
     if (t < 128) { if (t / 32 < OC) dw[t] = s; } else if (t - 128 < OC) db[t - 128] = s;
 }
 
-size_t head_bwd_ws_floats() { return (size_t)HEAD_BLOCKS * 132; }
+size_t head_bwd_ws_floats(int OC) { return OC > 4 ? head_wide_bwd_ws_floats(OC) : (size_t)HEAD_BLOCKS * 132; }
 
 int launch_head_bwd(const float* dout, const float* act, const float* w, float* g, float* dw, float* db, float* part,
                     int N, int H, int W, int OC, hipStream_t st) {
+    if (OC > 4) return launch_head_wide_bwd(dout, act, 0, w, g, dw, db, part, N, H, W, OC, st);
     const size_t total = (size_t)N * H * W;
     if (!total) return 0;
     const int nb = (int)min((total + 31) / 32, (size_t)HEAD_BLOCKS);
@@ -765,6 +767,7 @@ int launch_maxpool_fwd_bf16(const bf16_t* in, bf16_t* out, int N, int Ho, int Wo
 }
 
 int launch_head_fwd_bf16(const bf16_t* in, const float* w, const float* b, float* out, int N, int H, int W, int OC, hipStream_t st) {
+    if (OC > 4) return launch_head_wide_fwd(in, 1, w, b, out, N, H, W, OC, st);
     const size_t total = (size_t)N * H * W;
     if (!total) return 0;
     ELD_LAUNCH(head_fwd_kernel<bf16_t>, dim3((unsigned)min((total + 63) / 64, (size_t)16384)), dim3(256), 0, st, in, w, b, out, N, (size_t)H * W, OC);
@@ -879,6 +882,7 @@ __global__ __launch_bounds__(256) void head_bwd_bf16_kernel(const float* __restr
 
 int launch_head_bwd_bf16(const float* dout, const bf16_t* act, const float* w, bf16_t* g, float* dw, float* db, float* part,
                          int N, int H, int W, int OC, hipStream_t st) {
+    if (OC > 4) return launch_head_wide_bwd(dout, act, 1, w, g, dw, db, part, N, H, W, OC, st);
     const size_t total = (size_t)N * H * W;
     if (!total) return 0;
     const int nb = (int)min((total + 63) / 64, (size_t)HEAD_BLOCKS);
@@ -1026,12 +1030,13 @@ __global__ __launch_bounds__(256) void head_train_kernel(const T* __restrict__ a
     if (tid == 132) lpart[blockIdx.x] = red[0][132] + red[1][132] + red[2][132] + red[3][132];
 }
 
-size_t head_train_ws_floats() { return (size_t)HEAD_BLOCKS * 133; }
+size_t head_train_ws_floats(int OC) { return OC > 4 ? head_wide_train_ws_floats(OC) : (size_t)HEAD_BLOCKS * 133; }
 static int head_train_blocks(size_t total, int bf16) { return (int)min((total + (bf16 ? 63 : 31)) / (bf16 ? 64 : 32), (size_t)HEAD_BLOCKS); }
 
-// part: head_train_ws_floats() floats that must survive until launch_head_train_reduce (the backward) has run
+// part: head_train_ws_floats(OC) floats that must survive until launch_head_train_reduce (the backward) has run
 int launch_head_train(const void* act, int bf16, const float* w, const float* b, const float* tgt, float* out, void* g, float* part, float* loss,
                       int N, int H, int W, int OC, int mse, float grad_scale, hipStream_t st) {
+    if (OC > 4) return launch_head_wide_train(act, bf16, w, b, tgt, out, g, part, loss, N, H, W, OC, mse, grad_scale, st);
     const size_t total = (size_t)N * H * W;
     if (!total) return ELD_EINVAL;
     const int nb = head_train_blocks(total, bf16);
@@ -1054,6 +1059,7 @@ int launch_head_train(const void* act, int bf16, const float* w, const float* b,
 
 // the head's dW / db from the partials launch_head_train left in `part`
 int launch_head_train_reduce(const float* part, float* dw, float* db, int N, int H, int W, int OC, int bf16, hipStream_t st) {
+    if (OC > 4) return launch_head_wide_train_reduce(part, dw, db, N, H, W, OC, st);
     const size_t total = (size_t)N * H * W;
     if (!total) return 0;
     ELD_LAUNCH(head_bwd_reduce_kernel, dim3((132 + 15) / 16), dim3(256), 0, st, part, dw, db, head_train_blocks(total, bf16), OC);

@@ -18,7 +18,7 @@ def quality_assess(X, Y, data_range=255.0):
     dev = torch.device('cuda', torch.cuda.current_device())
     X = torch.as_tensor(np.ascontiguousarray(X) if isinstance(X, np.ndarray) else X).to(dev)
     Y = torch.as_tensor(np.ascontiguousarray(Y) if isinstance(Y, np.ndarray) else Y).to(dev)
-    if X.dim() == 3 and X.shape[-1] <= 4 < X.shape[0]:        # HWC (tensor2im's layout) -> CHW
+    if X.dim() == 3 and X.shape[-1] <= 16 < X.shape[0]:       # HWC (tensor2im's layout, up to 16 planes: X-Trans has 9) -> CHW
         X, Y = X.permute(2, 0, 1), Y.permute(2, 0, 1)
     q = quality_assess_frames(X.float()[None], Y.float()[None], data_range, scale=1.0)[0].tolist()
     return {'PSNR': q[0], 'SSIM': q[1]}

@@ -128,8 +128,9 @@ class ELDModel:
             raise RuntimeError('--crf: no CRF tables reached the model: pass them as opt.crf_tables = (E, fs) or through ISPDataset(CRF=...) as '
                                'train_syn.py:42-58 does; refusing to render the input with gamma 2.2 against a CRF-rendered target')
         prec = getattr(opt, 'precision', os.environ.get('ELD_AMD_PRECISION', 'fp32'))      # 'bf16' = BASELINE config 3
-        if prec == 'bf16' and cin > 4:
-            raise NotImplementedError('precision=bf16 supports up to 4 input planes (got %d: burst inputs run in fp32)' % cin)
+        for what, n in (('input', cin), ('output', cout)):     # the engine's range in both precisions (include/eld_amd.h): 4 Bayer, 9 X-Trans, bursts
+            if not 1 <= n <= 16:
+                raise ValueError('eld_amd U-Net supports 1..16 %s planes, got %d (opt.channels=%r, precision=%s)' % (what, n, ch, prec))
         self.netG = ARCH[getattr(opt, 'netG', 'unet')](cin, cout).to(self.device)
         self.netG.train_precision = self.netG.inference_precision = prec
         self.world, self.rank = D.world_size(), D.rank()

@@ -297,6 +297,27 @@ def pack_raw_bayer(raw_image_visible, raw_pattern, black_level_per_channel, whit
     return out.cpu().numpy() if as_np else out
 
 
+def pack_raw_xtrans(raw_image_visible, black_level=1024, white_point=16383):
+    """The X-Trans branch of the dataset pack (dataset/sid_dataset.py:199-239) on the device: uint16 sensor mosaic (Hm,Wm) or
+    (N,Hm,Wm) [ndarray or CUDA int16/uint16 tensor] -> packed, black-level-normalised float32 (9,2*(Hm//6),2*(Wm//6)) /
+    (N,9,...) in RawPacker.pack_raw_xtrans's plane order (sides truncated to whole 6x6 cells).  One black level for all planes,
+    as the reference's X-Trans path uses (1024 / 16383 for the Fuji sensors)."""
+    import torch
+    as_np = isinstance(raw_image_visible, np.ndarray)
+    t = torch.from_numpy(np.ascontiguousarray(raw_image_visible, dtype=np.uint16).view(np.int16)).cuda() if as_np else raw_image_visible.contiguous()
+    assert t.is_cuda and is_u16_codes(t)
+    single = t.dim() == 2
+    if single:
+        t = t.unsqueeze(0)
+    N, Hm, Wm = t.shape
+    out = torch.empty((N, 9, 2 * (Hm // 6), 2 * (Wm // 6)), dtype=torch.float32, device=t.device)
+    L.check(L.lib().eld_pack_raw_xtrans_u16(L.dptr(t), L.dptr(out), N, Hm, Wm, float(np.float32(black_level)), float(np.float32(white_point)),
+                                            L.cur_stream()), 'eld_pack_raw_xtrans_u16')
+    if single:
+        out = out[0]
+    return out.cpu().numpy() if as_np else out
+
+
 class NoiseModelBase:  # same name / role as noise.py:148
     seed = int(os.environ.get('ELD_AMD_SEED', '2018'))      # Philox key (reference --seed default, base_option.py:22)
     sample_base = 0                                         # first global sample index handed out by this instance

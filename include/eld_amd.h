@@ -128,6 +128,11 @@ int eld_unpack_xtrans(const float* packed, float* mosaic, int N, int h, int w, v
  * (black_level: HOST array of 4 floats = raw.black_level_per_channel; white_point 16383 in the reference).  Bit-exact. */
 int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern,
                            const float* black_level, float white_point, void* stream);
+/* The X-Trans branch of the same dataset pack (dataset/sid_dataset.py:199-239): uint16 sensor mosaic [N,Hm,Wm] -> packed float32
+ * [N,9,2*(Hm/6),2*(Wm/6)] (eld_pack_xtrans's index map; sides truncated to whole 6x6 cells) of
+ * clip((x - black_level) / (white_point - black_level), 0, 1), float32 arithmetic as NumPy's (one black level for all planes;
+ * 1024 / 16383 in the reference).  white_point must exceed black_level.  Bit-exact. */
+int eld_pack_raw_xtrans_u16(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point, void* stream);
 
 
 /* Training-pair augmentation of ELDTrainDataset.__getitem__ (dataset/sid_dataset.py:344-352), batched on device:
@@ -150,6 +155,8 @@ int eld_augment_u16(const uint16_t* in, float* out, const int32_t* aug, int N, i
  * maps onto it by plain views (models/ELD_model.py:516-523) and a data-parallel gradient all-reduce is
  * one contiguous buffer.  Activations are kept NHWC float32 in the caller-provided workspace.
  * x / out / dout are NCHW float32 like the reference's tensors.  H and W must be multiples of 16.
+ * Channels: 1 <= in_ch <= 16 and 1 <= out_ch <= 16 in both precisions (4 -> 4 Bayer; 9 -> 9 X-Trans, ELD_model.py:377-391;
+ * num_burst x 4 burst inputs); outside that range eld_unet_param_offsets returns ELD_EINVAL and eld_unet_workspace_bytes 0.
  * ==================================================================================================== */
 #define ELD_UNET_NTENSORS 46
 
