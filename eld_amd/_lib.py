@@ -41,6 +41,13 @@ SIGNATURES = {
     'eld_pack_raw_bayer_u16': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp]),
     'eld_pack_raw_xtrans_u16': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp]),
     'eld_augment': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _u32, _vp]),
+    'eld_calib_bias_stats_workspace_bytes': (_sz, [_i, _i]),
+    'eld_calib_bias_stats': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), _vp, _vp, _vp, _sz, _vp]),
+    'eld_calib_bias_residual': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
+    'eld_calib_flat_stats_workspace_bytes': (_sz, [_i, _i]),
+    'eld_calib_flat_stats': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), _i, _vp, _vp, _sz, _vp]),
+    'eld_calib_ppcc_workspace_bytes': (_sz, [_i, _sz, _i]),
+    'eld_calib_ppcc': (_i, [_vp, _i, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     'eld_unet_param_offsets': (_i, [_i, _i, _vp]),
     'eld_unet_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'eld_unet_forward': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),

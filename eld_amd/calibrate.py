@@ -1,0 +1,361 @@
+"""Noise-parameter calibration: bias frames and flat-field pairs -> a camera table in the release schema.
+
+The reference ships the calibrated tables of five cameras (camera_params/release/*_params.npy, restated in camera_params.json) but
+not the calibration method (README.md: "we are unable to provide the noise model as well as the calibration method").  This module
+estimates the same table for any Bayer sensor, in DN (raw digital numbers, the sampler's ADU), so that NoiseModel(cameras=[name])
+can synthesise its noise.  The estimators are the contract of DESIGN.md, "Calibration"; the pixel passes run in HIP
+(eld_amd/csrc/calib.hip: exact integer sums, the float64 residual, the Tukey-lambda PPCC), the rest is float64 NumPy on the host.
+
+    sessions = [{'iso': 100, 'bias': (F,Hm,Wm) uint16, 'flats': (P,2,Hm,Wm) uint16}, ...]
+    params, diag = calibrate_camera(sessions, raw_pattern, black_level, white_level)
+    save_camera_params(params, 'MyCam', 'camera_params/release')
+
+Command line: python -m eld_amd.calibrate manifest.json --camera NAME --out DIR (the manifest format is in INTEGRATION.md).
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+
+from . import _lib as L
+
+DEFAULT_LAMBDAS = np.linspace(-1.0, 1.0, 141)     # scipy.stats.ppcc_plot(x, -1, 1, N=141): every shipped G_shape lies on it
+PROFILE = 'Profile-1'
+SIGMA_KEYS = ('G_scale', 'R_scale', 'g_scale')
+
+
+# ---- argument checks (host only: they run before any device work) ---------------------------------------------------------------
+def _pattern(raw_pattern):
+    p = np.asarray(raw_pattern).reshape(-1)
+    if p.size != 4 or sorted(int(v) for v in p) != [0, 1, 2, 3] or not np.all(p == np.round(p)):
+        raise ValueError('raw_pattern must be a 2x2 permutation of 0..3, got %r' % (np.asarray(raw_pattern).tolist(),))
+    return p.astype(np.int64).reshape(2, 2)
+
+
+def _black(black_level):
+    b = np.asarray(black_level, dtype=np.float64).reshape(-1)
+    if b.size != 4:
+        raise ValueError('black_level must hold 4 values (black_level_per_channel), got %d' % b.size)
+    return b
+
+
+def _shape(x):
+    return tuple(int(s) for s in x.shape)
+
+
+def _check_mosaics(x, ndim, what):
+    s = _shape(x)
+    if len(s) != ndim:
+        raise ValueError('%s: expected %d dimensions, got shape %s' % (what, ndim, s))
+    if ndim == 4 and s[1] != 2:
+        raise ValueError('%s: flat pairs must have shape (P, 2, Hm, Wm), got %s' % (what, s))
+    Hm, Wm = s[-2:]
+    if Hm % 2 or Wm % 2 or Hm == 0 or Wm == 0:
+        raise ValueError('%s: mosaic sides must be even and non-zero, got %dx%d' % (what, Hm, Wm))
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.uint16:
+            raise ValueError('%s: uint16 mosaics expected, got %s' % (what, x.dtype))
+    else:
+        import torch
+        if not (x.is_cuda and x.dtype in (torch.int16, torch.uint16)):
+            raise ValueError('%s: a tensor must be CUDA int16/uint16 codes, got %s on %s' % (what, x.dtype, x.device))
+    return s
+
+
+def _device_u16(x):
+    """ndarray uint16 or CUDA int16/uint16 tensor -> contiguous CUDA tensor of the same bits, 4-byte aligned (the kernels read a row
+    as 32-bit words: a view starting at an odd element is copied)."""
+    import torch
+    if isinstance(x, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(x).view(np.int16)).cuda()
+    x = x.contiguous()
+    return x.clone() if x.data_ptr() % 4 else x
+
+
+def _ws(nbytes, device):
+    import torch
+    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _c_pattern(p):
+    return (ctypes.c_int * 4)(*[int(v) for v in p.reshape(-1)])
+
+
+# ---- host derivations from the exact sums ------------------------------------------------------------------------------------
+def bias_stats_from_sums(chan_sums, row_sums, raw_pattern, black_level, Hm, Wm):
+    """Host half of bias_frame_stats: per frame colour bias cb_c (F,4), row offsets rho_y (F,Hm), the g_scale and R_scale samples (F,)
+    (DESIGN.md "Calibration"), float64, from chan_sums int64 (F,4,2) = (sum u, sum u^2) and row_sums int64 (F,Hm,2) = sum u over the
+    even / odd columns."""
+    pat, black = _pattern(raw_pattern), _black(black_level)
+    chan_sums, row_sums = np.asarray(chan_sums), np.asarray(row_sums)
+    F = chan_sums.shape[0]
+    n, nc = Hm * Wm, Hm * Wm // 4
+    mean_u = chan_sums[:, :, 0].astype(np.float64) / nc                  # black_c + cb_c
+    cb = mean_u - black[None, :]
+    se2 = np.zeros(F)                                                     # sum of e^2 = sum_c (Q_c - S_c^2 / n_c), exact numerator
+    for f in range(F):
+        se2[f] = sum(float(nc * int(chan_sums[f, c, 1]) - int(chan_sums[f, c, 0]) ** 2) / nc for c in range(4))
+    par = np.arange(Hm) & 1                                               # channels of row y: pat[y&1][0], pat[y&1][1]
+    mrow = 0.5 * (mean_u[:, pat[par, 0]] + mean_u[:, pat[par, 1]])        # (F,Hm)
+    rho = (row_sums[:, :, 0] + row_sums[:, :, 1]).astype(np.float64) / Wm - mrow
+    st2 = se2 - Wm * np.sum(rho * rho, axis=1)                            # sum t^2, t = e - rho_y
+    g_scale = np.sqrt(se2 / n)
+    R_scale = np.sqrt(np.maximum(0.0, np.mean(rho * rho, axis=1) - (st2 / n) / Wm))
+    return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
+
+
+def flat_stats_from_sums(sums, black_level, white_level, color_bias, Hm, Wm):
+    """Host half of flat_pair_stats: sums int64 (P,4,4) -> mu, var (P,4) float64 and usable (P,4) bool."""
+    black = _black(black_level)
+    sums = np.asarray(sums)
+    P = sums.shape[0]
+    cbm = np.asarray(color_bias, np.float64).reshape(4)
+    nc = Hm * Wm // 4
+    mu = sums[:, :, 0].astype(np.float64) / (2 * nc) - black[None, :] - cbm[None, :]
+    var = np.array([[float(nc * int(sums[p, c, 2]) - int(sums[p, c, 1]) ** 2) / (nc * nc) / 2.0 for c in range(4)] for p in range(P)])
+    usable = (sums[:, :, 3] == 0) & (mu > 0) & (mu <= 0.8 * (float(white_level) - black[None, :]))
+    return {'mu': mu, 'var': var.reshape(P, 4), 'usable': usable}
+
+
+def ptc_gain(mu, var, usable, what='session'):
+    """K = the OLS slope of var on mu over the usable photon-transfer points."""
+    mu, var = np.asarray(mu)[np.asarray(usable)], np.asarray(var)[np.asarray(usable)]
+    if mu.size < 2 or np.ptp(mu) <= 0:
+        raise ValueError('%s: fewer than two usable flat points (%d): flats saturated, too dark or all alike' % (what, mu.size))
+    K = _ols(mu, var)[0]
+    if not K > 0:
+        raise ValueError('%s: the photon-transfer slope is %r, not a positive gain' % (what, K))
+    return K
+
+
+def params_from_samples(frames, Ks):
+    """Per-frame samples (dicts with K, lambda, G_scale, R_scale, g_scale, color_bias) and the session gains -> the release-schema
+    table."""
+    if len(frames) < 3:
+        raise ValueError('at least 3 bias frames are needed for the log-linear fits, got %d' % len(frames))
+    for j, fr in enumerate(frames):
+        if not fr['R_scale'] > 0:
+            raise ValueError('bias frame %d (iso %s): the row-noise sample is 0 (no log): the row offsets do not exceed the read noise '
+                             'averaged into them' % (j, fr.get('iso')))
+    if len(set(float(k) for k in Ks)) < 2:
+        raise ValueError('the sessions give fewer than 2 distinct K: the log-linear fits need a range of gains')
+    Kf = np.array([fr['K'] for fr in frames], np.float64)
+    return {'Kmin': np.float64(min(Ks)), 'Kmax': np.float64(max(Ks)),
+            'G_shape': np.array([fr['lambda'] for fr in frames], dtype=np.float64),
+            'color_bias': np.array([fr['color_bias'] for fr in frames], dtype=np.float32).reshape(len(frames), 4),
+            PROFILE: {k: fit_log_linear(Kf, [fr[k] for fr in frames]) for k in SIGMA_KEYS}}
+
+
+def _ols(x, y):
+    x, y = np.asarray(x, np.float64), np.asarray(y, np.float64)
+    dx = x - x.mean()
+    sxx = float(np.sum(dx * dx))
+    if sxx <= 0:
+        raise ValueError('least squares needs at least two distinct abscissae')
+    slope = float(np.sum(dx * (y - y.mean())) / sxx)
+    return slope, float(y.mean() - slope * x.mean())
+
+
+# ---- public steps -----------------------------------------------------------------------------------------------------------
+def bias_frame_stats(bias, raw_pattern, black_level, residual=False):
+    """Bias frames (F,Hm,Wm) uint16 [ndarray or CUDA int16/uint16 tensor] -> dict of host arrays:
+    chan_sums int64 (F,4,2) (sum u, sum u^2 per channel), row_sums int64 (F,Hm,2) (sum u over even / odd columns), color_bias (F,4),
+    row_offset (F,Hm), g_scale (F,), R_scale (F,) float64; with residual=True also 't', the CUDA float32 (F,Hm*Wm) residuals
+    float32(((u - black_c) - cb_c) - rho_y)."""
+    import torch
+    pat, black = _pattern(raw_pattern), _black(black_level)
+    F, Hm, Wm = _check_mosaics(bias, 3, 'bias')
+    u = _device_u16(bias)
+    dev = u.device
+    cs = torch.empty((F, 4, 2), dtype=torch.int64, device=dev)
+    rs = torch.empty((F, Hm, 2), dtype=torch.int64, device=dev)
+    cp = _c_pattern(pat)
+    ws = _ws(L.lib().eld_calib_bias_stats_workspace_bytes(F, Hm), dev)
+    L.check(L.lib().eld_calib_bias_stats(L.dptr(u), F, Hm, Wm, cp, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), L.cur_stream()),
+            'eld_calib_bias_stats')
+    out = {'chan_sums': cs.cpu().numpy(), 'row_sums': rs.cpu().numpy()}
+    out.update(bias_stats_from_sums(out['chan_sums'], out['row_sums'], pat, black, Hm, Wm))
+    if residual:
+        t = torch.empty((F, Hm * Wm), dtype=torch.float32, device=dev)
+        cbd = torch.from_numpy(np.ascontiguousarray(out['color_bias'])).to(dev)
+        rhod = torch.from_numpy(np.ascontiguousarray(out['row_offset'])).to(dev)
+        L.check(L.lib().eld_calib_bias_residual(L.dptr(u), F, Hm, Wm, cp, (ctypes.c_double * 4)(*black.tolist()), L.dptr(cbd), L.dptr(rhod),
+                                                L.dptr(t), L.cur_stream()), 'eld_calib_bias_residual')
+        out['t'] = t
+    return out
+
+
+def tukey_lambda_ppcc(t, lambdas=None, presorted=False):
+    """Tukey-lambda probability-plot correlation of the samples t ((n,) or (F,n); ndarray or CUDA tensor; n >= 3) over the shape
+    grid (default DEFAULT_LAMBDAS), as scipy.stats.ppcc_plot / probplot(fit=True) define it with Filliben's medians.
+    Returns {'lambdas' (L,), 'r' (F,L), 'slope' (F,L), 'lam_hat' (F,), 'scale' (F,), 'index' (F,)} (float64 host arrays; the F axis
+    is dropped for 1-D input).  lam_hat = the arg-max of r (lowest index on a tie), scale = the probplot slope there."""
+    import torch
+    lam = np.asarray(DEFAULT_LAMBDAS if lambdas is None else lambdas, dtype=np.float64).reshape(-1)
+    if lam.size == 0:
+        raise ValueError('empty lambda grid')
+    one = len(_shape(t)) == 1
+    if len(_shape(t)) not in (1, 2):
+        raise ValueError('t must have shape (n,) or (F,n), got %s' % (_shape(t),))
+    n = _shape(t)[-1]
+    if n < 3:
+        raise ValueError('PPCC needs n >= 3 samples, got %d' % n)
+    if not isinstance(t, np.ndarray) and not t.is_cuda:
+        raise ValueError('t: a tensor must live on the GPU (CUDA), got one on %s; pass an ndarray to have it uploaded' % (t.device,))
+    x = torch.from_numpy(np.ascontiguousarray(t, dtype=np.float32)).cuda() if isinstance(t, np.ndarray) else t.float()
+    x = x.reshape(-1, n)
+    if not presorted:
+        x = torch.sort(x, dim=1).values
+    x = x.contiguous()
+    F, dev = x.shape[0], x.device
+    lamd = torch.from_numpy(lam.astype(np.float32)).to(dev)
+    sums = torch.empty((F, lam.size, 2), dtype=torch.float64, device=dev)
+    tsums = torch.empty((F, 2), dtype=torch.float64, device=dev)
+    ws = _ws(L.lib().eld_calib_ppcc_workspace_bytes(F, n, lam.size), dev)
+    L.check(L.lib().eld_calib_ppcc(L.dptr(x), F, n, L.dptr(lamd), lam.size, L.dptr(sums), L.dptr(tsums), L.dptr(ws), ws.numel(),
+                                   L.cur_stream()), 'eld_calib_ppcc')
+    s, ts = sums.cpu().numpy(), tsums.cpu().numpy()
+    stm, smm = s[:, :, 0], s[:, :, 1]
+    stt = ts[:, 1] - ts[:, 0] * ts[:, 0] / n                                # centred sum of squares of t
+    with np.errstate(invalid='ignore', divide='ignore'):
+        r = stm / np.sqrt(smm * stt[:, None])
+    slope = stm / smm
+    idx = np.argmax(np.where(np.isnan(r), -np.inf, r), axis=1)
+    out = {'lambdas': lam, 'r': r, 'slope': slope, 'index': idx, 'lam_hat': lam[idx], 'scale': slope[np.arange(F), idx]}
+    if one:
+        out = {k: (v if k == 'lambdas' else v[0]) for k, v in out.items()}
+    return out
+
+
+def flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias):
+    """Flat pairs (P,2,Hm,Wm) uint16 -> dict: sums int64 (P,4,4) = per channel (sum(a+b), sum(a-b), sum((a-b)^2), saturated pixels),
+    mu (P,4) = mean((a+b)/2) - black_c - color_bias_c, var (P,4) = var(a-b)/2, usable (P,4) bool (no saturated pixel and
+    0 < mu <= 0.8 (white - black_c)).  color_bias: the session's mean colour bias (4,)."""
+    import torch
+    pat, black = _pattern(raw_pattern), _black(black_level)
+    P, _, Hm, Wm = _check_mosaics(flats, 4, 'flats')
+    cbm = np.asarray(color_bias, np.float64).reshape(4)
+    ab = _device_u16(flats)
+    out = torch.empty((P, 4, 4), dtype=torch.int64, device=ab.device)
+    ws = _ws(L.lib().eld_calib_flat_stats_workspace_bytes(P, Hm), ab.device)
+    L.check(L.lib().eld_calib_flat_stats(L.dptr(ab), P, Hm, Wm, _c_pattern(pat), int(white_level), L.dptr(out), L.dptr(ws), ws.numel(),
+                                         L.cur_stream()), 'eld_calib_flat_stats')
+    res = {'sums': out.cpu().numpy()}
+    res.update(flat_stats_from_sums(res['sums'], black, white_level, cbm, Hm, Wm))
+    return res
+
+
+def fit_log_linear(K, sigma):
+    """log sigma_j = slope * log K_j + bias by ordinary least squares; sigma = sqrt(SSR / (m - 2)).  The release tables' regression
+    records ({'slope', 'bias', 'sigma'}, float64) that NoiseModel._sample_params draws from."""
+    x, y = np.log(np.asarray(K, np.float64)), np.log(np.asarray(sigma, np.float64))
+    if x.size != y.size or x.size < 3:
+        raise ValueError('fit_log_linear needs m >= 3 matching samples, got %d and %d' % (x.size, y.size))
+    if not np.all(np.isfinite(x)) or not np.all(np.isfinite(y)):
+        raise ValueError('fit_log_linear: K and sigma must be positive and finite')
+    slope, bias = _ols(x, y)
+    res = y - (slope * x + bias)
+    return {'slope': np.float64(slope), 'bias': np.float64(bias), 'sigma': np.float64(np.sqrt(np.sum(res * res) / (x.size - 2)))}
+
+
+def _check_sessions(sessions):
+    if not isinstance(sessions, (list, tuple)) or len(sessions) == 0:
+        raise ValueError('sessions must be a non-empty list of {"iso", "bias", "flats"}')
+    shape, nbias = None, 0
+    for i, s in enumerate(sessions):
+        for k in ('bias', 'flats'):
+            if k not in s:
+                raise ValueError('session %d has no %r' % (i, k))
+        F, Hm, Wm = _check_mosaics(s['bias'], 3, 'session %d bias' % i)
+        P = _check_mosaics(s['flats'], 4, 'session %d flats' % i)[0]
+        if shape is None:
+            shape = (Hm, Wm)
+        if (Hm, Wm) != shape or _shape(s['flats'])[-2:] != shape:
+            raise ValueError('session %d: mosaic shapes differ (%s vs %s / %s)' % (i, shape, (Hm, Wm), _shape(s['flats'])[-2:]))
+        if F == 0 or P == 0:
+            raise ValueError('session %d: needs at least one bias frame and one flat pair' % i)
+        nbias += F
+    if nbias < 3:
+        raise ValueError('at least 3 bias frames are needed for the log-linear fits, got %d' % nbias)
+    if len(sessions) < 2:
+        raise ValueError('at least 2 sessions (2 distinct K) are needed, got %d' % len(sessions))
+
+
+def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None):
+    """Sessions of bias frames and flat pairs -> (params, diagnostics).  params has exactly the release schema
+    (Kmin, Kmax, G_shape (m,), color_bias (m,4) float32, 'Profile-1': {G_scale, R_scale, g_scale: {slope, bias, sigma}}), one G_shape /
+    color_bias row per bias frame; diagnostics holds the per-frame samples, r(lambda) and the photon-transfer points."""
+    _pattern(raw_pattern)
+    _black(black_level)
+    _check_sessions(sessions)
+    frames, r_all, ptc, Ks = [], [], [], []
+    lam = None
+    for i, s in enumerate(sessions):
+        st = bias_frame_stats(s['bias'], raw_pattern, black_level, residual=True)
+        pp = tukey_lambda_ppcc(st.pop('t'), lambdas)
+        lam = pp['lambdas']
+        fl = flat_pair_stats(s['flats'], raw_pattern, black_level, white_level, st['color_bias'].mean(axis=0))
+        what = 'session %d (iso %s)' % (i, s.get('iso'))
+        K = ptc_gain(fl['mu'], fl['var'], fl['usable'], what)
+        Ks.append(K)
+        ptc.append({'iso': s.get('iso'), 'mu': fl['mu'], 'var': fl['var'], 'usable': fl['usable'], 'K': K})
+        for f in range(st['color_bias'].shape[0]):
+            frames.append({'session': i, 'iso': s.get('iso'), 'K': K, 'lambda': float(pp['lam_hat'][f]), 'G_scale': float(pp['scale'][f]),
+                           'R_scale': float(st['R_scale'][f]), 'g_scale': float(st['g_scale'][f]), 'color_bias': st['color_bias'][f]})
+            r_all.append(pp['r'][f])
+    params = params_from_samples(frames, Ks)
+    diag = {'frames': frames, 'lambdas': lam, 'r': np.array(r_all), 'K': np.array(Ks), 'ptc': ptc}
+    return params, diag
+
+
+def save_camera_params(params, camera, out_dir):
+    """Write <out_dir>/<camera>_params.npy (a pickled dict, as the release tables): load_camera_params(camera, out_dir) and the
+    reference's np.load(...).item() read it; NoiseModel(cameras=[camera]) finds it under camera_params/release/ of the CWD."""
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, camera + '_params.npy')
+    np.save(path, np.array(params, dtype=object), allow_pickle=True)
+    return path
+
+
+# ---- command line -------------------------------------------------------------------------------------------------------------
+def load_manifest(path):
+    """Manifest JSON -> (sessions, raw_pattern, black_level, white_level).  Paths are relative to the manifest's directory."""
+    with open(path) as f:
+        m = json.load(f)
+    base = os.path.dirname(os.path.abspath(path))
+
+    def load(p):
+        return np.load(os.path.join(base, p))
+    sessions = []
+    for s in m['sessions']:
+        bias = np.stack([load(p) for p in s['bias']])
+        flats = np.stack([np.stack([load(a), load(b)]) for a, b in s['flats']])
+        sessions.append({'iso': s.get('iso'), 'bias': bias, 'flats': flats})
+    return sessions, m['raw_pattern'], m['black_level'], m['white_level']
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog='python -m eld_amd.calibrate', description=__doc__.split('\n')[0])
+    ap.add_argument('manifest', help='JSON: raw_pattern, black_level, white_level, sessions [{iso, bias: [.npy], flats: [[a.npy, b.npy]]}]')
+    ap.add_argument('--camera', required=True, help='camera name: writes <out>/<camera>_params.npy')
+    ap.add_argument('--out', default=os.path.join('camera_params', 'release'))
+    a = ap.parse_args(argv)
+    sessions, pattern, black, white = load_manifest(a.manifest)
+    params, diag = calibrate_camera(sessions, pattern, black, white)
+    path = save_camera_params(params, a.camera, a.out)
+    for fr in diag['frames']:
+        print('iso %-6s K %.5g  lambda %+.4f  G_scale %.4g  R_scale %.4g  g_scale %.4g' % (fr['iso'], fr['K'], fr['lambda'], fr['G_scale'],
+                                                                                          fr['R_scale'], fr['g_scale']))
+    print('Kmin %.5g Kmax %.5g' % (params['Kmin'], params['Kmax']))
+    for k in SIGMA_KEYS:
+        r = params[PROFILE][k]
+        print('%-8s slope %.5f bias %.5f sigma %.5f' % (k, r['slope'], r['bias'], r['sigma']))
+    print('wrote', path)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -1,0 +1,397 @@
+// calib.hip -- noise-parameter calibration from bias frames and flat-field pairs (eld_amd/calibrate.py, DESIGN.md "Calibration").
+//
+// Four passes; everything else is derived on the host in float64 from their outputs:
+//   bias statistics   uint16 mosaics -> per row: sums over the even / odd columns; per frame and channel: sum u, sum u^2 (uint64, exact)
+//   bias residual     t = float32(((u - black_c) - cb_c) - rho_y), float64 arithmetic, one rounding (NumPy's, bit for bit)
+//   flat statistics   uint16 pairs (a, b) -> per pair and channel: sum(a+b), sum(a-b), sum((a-b)^2), saturated pixels (int64, exact)
+//   PPCC              sorted residuals -> per Tukey-lambda shape: sum t*M, sum M^2 (and sum t, sum t^2), float64, fixed order
+// Packed channel of mosaic pixel (y, x): raw_pattern[y&1][x&1] (R, G1, B, G2 = 0..3), as eld_pack_raw_bayer_u16.
+// No atomics anywhere: every sum is reduced in an order fixed by the shape alone, so two launches give identical bits.
+#include "common.h"
+
+namespace {
+
+constexpr int CB_THREADS = 256;
+constexpr int CB_WAVES = CB_THREADS / ELD_WAVE;
+
+// channel of each (row parity, column parity): pat[2*py + px]
+struct Pattern {
+    int c[4];
+};
+
+__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// Sum NV uint64 values over the block (256 threads); the block's totals land in tot[] (LDS, valid after the call).  Integer sums:
+// exact, order-independent.
+template <int NV>
+__device__ __forceinline__ void block_sum_u64(uint64_t (&v)[NV], uint64_t* red /* LDS [CB_WAVES][NV] */, uint64_t* tot /* LDS [NV] */) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = wave_sum_u64(v[k]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < NV; ++k) red[wv * NV + k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        uint64_t s = 0;
+        for (int w = 0; w < CB_WAVES; ++w) s += red[w * NV + threadIdx.x];
+        tot[threadIdx.x] = s;
+    }
+    __syncthreads();
+}
+
+// One 32-bit word of a row holds the pixels of one even column (low half) and the odd column after it: Wm is even, rows start
+// 4-byte aligned.  VEC: 16-byte loads (4 words) when Wm % 8 == 0 and the base is 16-byte aligned.
+template <bool VEC>
+__device__ __forceinline__ int row_words(const uint32_t* __restrict__ row, int k, uint32_t (&w)[4]) {
+    if (VEC) {
+        const uint4 q = reinterpret_cast<const uint4*>(row)[k];
+        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+        return 4;
+    }
+    w[0] = row[k];
+    return 1;
+}
+
+// ---- bias statistics, pass 1: one block per (row, frame).  rows[(f*Hm + y)*2 + p] = sum of u over the columns of parity p;
+// part[((f*Hm + y)*2 + p)*2 + {0, 1}] = sum of u, sum of u^2 there (workspace, pass 2's input). ----
+template <bool VEC>
+__global__ __launch_bounds__(CB_THREADS) void bias_row_kernel(const uint16_t* __restrict__ u, int Hm, int Wm, uint64_t* __restrict__ rows,
+                                                               uint64_t* __restrict__ part) {
+    __shared__ uint64_t red[CB_WAVES * 4], tot[4];
+    const int y = blockIdx.x, f = blockIdx.y;
+    const size_t ro = ((size_t)f * Hm + y);
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(u + ro * Wm);
+    const int nw = Wm / 2, nk = VEC ? nw / 4 : nw;
+    uint64_t v[4] = {0, 0, 0, 0};                              // sum even, sum odd, sum^2 even, sum^2 odd
+    for (int k = threadIdx.x; k < nk; k += CB_THREADS) {
+        uint32_t w[4];
+        const int m = row_words<VEC>(row, k, w);
+        for (int j = 0; j < m; ++j) {
+            const uint32_t e = w[j] & 0xFFFFu, o = w[j] >> 16;
+            v[0] += e; v[1] += o;
+            v[2] += (uint64_t)(e * e); v[3] += (uint64_t)(o * o);   // < 2^32: exact in uint32
+        }
+    }
+    block_sum_u64<4>(v, red, tot);
+    if (threadIdx.x < 2) rows[ro * 2 + threadIdx.x] = tot[threadIdx.x];
+    if (threadIdx.x < 4) part[ro * 4 + threadIdx.x] = tot[(threadIdx.x & 1) * 2 + (threadIdx.x >> 1)];   // [px][s] <- tot[s*2 + px]
+}
+
+// ---- pass 2 (bias and flat): one block per frame / pair sums the per-row partials of the rows of each parity into the channels.
+// part: [F][Hm][2 column parities][NS] uint64 (two's-complement sums stay exact); out: [F][4 channels][NS]. ----
+template <int NS>
+__global__ __launch_bounds__(CB_THREADS) void chan_reduce_kernel(const uint64_t* __restrict__ part, int Hm, Pattern pat, uint64_t* __restrict__ out) {
+    __shared__ uint64_t red[CB_WAVES * 4 * NS], tot[4 * NS];
+    const int f = blockIdx.x;
+    const uint64_t* p = part + (size_t)f * Hm * 2 * NS;
+    uint64_t v[4 * NS];                                        // [2*py + px][s]
+#pragma unroll
+    for (int k = 0; k < 4 * NS; ++k) v[k] = 0;
+    for (int y = threadIdx.x; y < Hm; y += CB_THREADS) {
+        const int py = y & 1;
+#pragma unroll
+        for (int px = 0; px < 2; ++px)
+#pragma unroll
+            for (int s = 0; s < NS; ++s) {
+                const uint64_t a = p[((size_t)y * 2 + px) * NS + s];
+                v[(2 * 0 + px) * NS + s] += py ? 0 : a;
+                v[(2 * 1 + px) * NS + s] += py ? a : 0;
+            }
+    }
+    block_sum_u64<4 * NS>(v, red, tot);
+    if (threadIdx.x < 4 * NS) {
+        const int q = threadIdx.x / NS, s = threadIdx.x % NS;
+        out[((size_t)f * 4 + pat.c[q]) * NS + s] = tot[threadIdx.x];
+    }
+}
+
+// ---- flat statistics, pass 1: one block per (row, pair).  part[(p*Hm + y)*2 + px][4] = sum(a+b), sum(a-b), sum((a-b)^2), #(a or b >= white)
+template <bool VEC>
+__global__ __launch_bounds__(CB_THREADS) void flat_row_kernel(const uint16_t* __restrict__ ab, int Hm, int Wm, uint32_t white,
+                                                               uint64_t* __restrict__ part) {
+    __shared__ uint64_t red[CB_WAVES * 8], tot[8];
+    const int y = blockIdx.x, pr = blockIdx.y;
+    const size_t frame = (size_t)Hm * Wm;
+    const uint16_t* a = ab + (size_t)pr * 2 * frame + (size_t)y * Wm;
+    const uint32_t* ra = reinterpret_cast<const uint32_t*>(a);
+    const uint32_t* rb = reinterpret_cast<const uint32_t*>(a + frame);
+    const int nw = Wm / 2, nk = VEC ? nw / 4 : nw;
+    uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // [px][s]
+    for (int k = threadIdx.x; k < nk; k += CB_THREADS) {
+        uint32_t wa[4], wb[4];
+        const int m = row_words<VEC>(ra, k, wa);
+        row_words<VEC>(rb, k, wb);
+        for (int j = 0; j < m; ++j)
+#pragma unroll
+            for (int px = 0; px < 2; ++px) {
+                const uint32_t x = (wa[j] >> (16 * px)) & 0xFFFFu, z = (wb[j] >> (16 * px)) & 0xFFFFu;
+                const int32_t d = (int32_t)x - (int32_t)z;
+                v[px * 4 + 0] += x + z;
+                v[px * 4 + 1] += (uint64_t)(int64_t)d;
+                v[px * 4 + 2] += (uint64_t)((uint32_t)d * (uint32_t)d);   // d^2 < 2^32: exact modulo 2^32
+                v[px * 4 + 3] += (x >= white || z >= white) ? 1u : 0u;
+            }
+    }
+    block_sum_u64<8>(v, red, tot);
+    if (threadIdx.x < 8) part[((size_t)pr * Hm + y) * 8 + threadIdx.x] = tot[threadIdx.x];
+}
+
+// ---- bias residual: t = float32(((u - black_c) - cb[f][c]) - rho[f][y]) in float64.  One block per (row, frame). ----
+struct Black {
+    double b[4];
+};
+
+__global__ __launch_bounds__(CB_THREADS) void bias_residual_kernel(const uint16_t* __restrict__ u, int Hm, int Wm, Pattern pat, Black blk,
+                                                                   const double* __restrict__ cb, const double* __restrict__ rho,
+                                                                   float* __restrict__ t) {
+    const int y = blockIdx.x, f = blockIdx.y;
+    const size_t ro = (size_t)f * Hm + y;
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(u + ro * Wm);
+    float2* out = reinterpret_cast<float2*>(t + ro * Wm);
+    const int c0 = pat.c[2 * (y & 1)], c1 = pat.c[2 * (y & 1) + 1];
+    const double b0 = blk.b[c0], b1 = blk.b[c1], cb0 = cb[f * 4 + c0], cb1 = cb[f * 4 + c1], r = rho[ro];
+    for (int k = threadIdx.x; k < Wm / 2; k += CB_THREADS) {
+        const uint32_t w = row[k];
+        const double e = (((double)(w & 0xFFFFu) - b0) - cb0) - r;
+        const double o = (((double)(w >> 16) - b1) - cb1) - r;
+        out[k] = make_float2((float)e, (float)o);
+    }
+}
+
+// ---- PPCC over a Tukey-lambda grid -----------------------------------------------------------------------------------------
+// Sorted t_0 <= ... <= t_{n-1}; Filliben's medians m_i (i = 1..n) with m_{n+1-i} = 1 - m_i, so pair i (0-based, i < n/2) with
+// j = n-1-i: M(m_j) = -M(m_i), sum M = 0 exactly, and the pair contributes M_j (t_j - t_i) to sum t*M and 2 M_j^2 to sum M^2.
+// With a = log2 m_i, b = log2(1 - m_i), h = (a+b)/2, g = (b-a) ln2/2 >= 0:
+//   M_j = (2^(lam b) - 2^(lam a)) / lam = 2^(lam h + 1) g shc(lam g),  shc(x) = sinh(x)/x  (= 2g at lam = 0: the logistic quantile)
+// shc is even and >= 1: below |x| = 1 a Taylor polynomial (no cancellation at small |lam|); at |x| >= 1 the first form, whose two
+// powers then differ by more than a factor e^2.  Each lane evaluates only its own form.
+constexpr int PP_THREADS = 256;
+constexpr int PP_PAIRS = 8;                      // pairs per thread per block: a block covers PP_THREADS * PP_PAIRS pairs
+constexpr int PP_BLOCK_PAIRS = PP_THREADS * PP_PAIRS;
+constexpr int PP_LG = 16;                        // lambdas per block (grid.y covers the grid in groups of PP_LG)
+
+__host__ __device__ inline size_t pp_blocks(size_t n) { return (n / 2 + PP_BLOCK_PAIRS - 1) / PP_BLOCK_PAIRS; }
+
+// partial layout: [F][nb][L][2] (sum t*M, sum M^2) then [F][nb][2] (sum t, sum t^2)
+__global__ __launch_bounds__(PP_THREADS) void ppcc_partial_kernel(const float* __restrict__ ts, size_t n, const float* __restrict__ lam, int L,
+                                                                  double* __restrict__ part, double* __restrict__ tpart) {
+    __shared__ double red[PP_THREADS / ELD_WAVE][2 * PP_LG];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const size_t nb = gridDim.x, blk = blockIdx.x, np = n / 2;
+    const int l0 = blockIdx.y * PP_LG, f = blockIdx.z;
+    const float* t = ts + (size_t)f * n;
+    const double rdn = 1.0 / ((double)n + 0.365);
+    const double mn = exp2(-1.0 / (double)n), m1 = 1.0 - mn;  // m_n = 0.5^(1/n), m_1 = 1 - m_n
+
+    float lm[PP_LG];
+#pragma unroll
+    for (int q = 0; q < PP_LG; ++q) lm[q] = (l0 + q < L) ? lam[l0 + q] : 0.0f;
+    float il[PP_LG];                                           // 1/lam (used only where |lam g| >= 1, so never at lam = 0)
+#pragma unroll
+    for (int q = 0; q < PP_LG; ++q) il[q] = lm[q] != 0.0f ? 1.0f / lm[q] : 0.0f;
+    double stm[PP_LG], smm[PP_LG];
+#pragma unroll
+    for (int q = 0; q < PP_LG; ++q) { stm[q] = 0.0; smm[q] = 0.0; }
+    double st = 0.0, stt = 0.0;
+
+    for (int k = 0; k < PP_PAIRS; ++k) {
+        const size_t i = blk * PP_BLOCK_PAIRS + (size_t)k * PP_THREADS + threadIdx.x;
+        if (i >= np) break;
+        // m_i and 1 - m_i, each without cancellation (1-based index i+1); rounded to float32 below, so 1/(n + 0.365) once suffices
+        const double mi = i == 0 ? m1 : ((double)(i + 1) - 0.3175) * rdn;
+        const double mj = i == 0 ? mn : ((double)n + 0.6825 - (double)(i + 1)) * rdn;
+        const float a = __builtin_amdgcn_logf((float)mi), b = __builtin_amdgcn_logf((float)mj);
+        const float h = 0.5f * (a + b), g = (b - a) * 0.34657359027997264f;
+        const float ti = t[i], tj = t[n - 1 - i];
+        const double dt = (double)tj - (double)ti;
+        if (blockIdx.y == 0) {
+            st += (double)ti + (double)tj;
+            stt += (double)ti * (double)ti + (double)tj * (double)tj;
+        }
+#pragma unroll
+        for (int q = 0; q < PP_LG; ++q) {
+            const float x = lm[q] * g;
+            float M;
+            if (fabsf(x) < 1.0f) {                             // one form per lane: a wave of adjacent pairs nearly always takes one
+                const float x2 = x * x;
+                float poly = __builtin_fmaf(x2, 1.0f / 39916800.0f, 1.0f / 362880.0f);
+                poly = __builtin_fmaf(poly, x2, 1.0f / 5040.0f);
+                poly = __builtin_fmaf(poly, x2, 1.0f / 120.0f);
+                poly = __builtin_fmaf(poly, x2, 1.0f / 6.0f);
+                poly = __builtin_fmaf(poly, x2, 1.0f);
+                M = __builtin_amdgcn_exp2f(__builtin_fmaf(lm[q], h, 1.0f)) * g * poly;
+            } else {                                           // |lam (b-a)| >= 2/ln2: the two powers differ by > 7x, no cancellation
+                M = (__builtin_amdgcn_exp2f(lm[q] * b) - __builtin_amdgcn_exp2f(lm[q] * a)) * il[q];
+            }
+            const double Md = (double)M;
+            stm[q] = __builtin_fma(Md, dt, stm[q]);
+            smm[q] = __builtin_fma(Md, Md, smm[q]);
+        }
+    }
+    // block reduction in a fixed order: wave butterflies, then waves 0..3 in order
+#pragma unroll
+    for (int q = 0; q < PP_LG; ++q) {
+        const double s1 = wave_sum_f64(stm[q]), s2 = wave_sum_f64(smm[q]);
+        if (lane == 0) { red[wv][2 * q] = s1; red[wv][2 * q + 1] = 2.0 * s2; }
+    }
+    const double a1 = wave_sum_f64(st), a2 = wave_sum_f64(stt);
+    __syncthreads();
+    if (threadIdx.x < 2 * PP_LG) {
+        double s = 0.0;
+        for (int w = 0; w < PP_THREADS / ELD_WAVE; ++w) s += red[w][threadIdx.x];
+        const int l = l0 + threadIdx.x / 2;
+        if (l < L) part[(((size_t)f * nb + blk) * L + l) * 2 + (threadIdx.x & 1)] = s;
+    }
+    __syncthreads();
+    if (blockIdx.y == 0) {
+        if (lane == 0) { red[wv][0] = a1; red[wv][1] = a2; }
+        __syncthreads();
+        if (threadIdx.x < 2) {
+            double s = 0.0;
+            for (int w = 0; w < PP_THREADS / ELD_WAVE; ++w) s += red[w][threadIdx.x];
+            tpart[((size_t)f * nb + blk) * 2 + threadIdx.x] = s;
+        }
+    }
+}
+
+// one block per (frame, lambda) and one per frame for the t sums: thread k sums blocks k, k+256, ... in order, then the fixed
+// block reduction
+__global__ __launch_bounds__(256) void ppcc_final_kernel(const float* __restrict__ ts, size_t n, int L, size_t nb,
+                                                         const double* __restrict__ part, const double* __restrict__ tpart,
+                                                         double* __restrict__ sums, double* __restrict__ tsums) {
+    __shared__ double red[256 / ELD_WAVE][2];
+    const int f = blockIdx.y, l = blockIdx.x;                  // l == L: the t sums
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    double s1 = 0.0, s2 = 0.0;
+    for (size_t b = threadIdx.x; b < nb; b += 256) {
+        const double* p = l < L ? part + (((size_t)f * nb + b) * L + l) * 2 : tpart + ((size_t)f * nb + b) * 2;
+        s1 += p[0];
+        s2 += p[1];
+    }
+    s1 = wave_sum_f64(s1);
+    s2 = wave_sum_f64(s2);
+    if (lane == 0) { red[wv][0] = s1; red[wv][1] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        s1 = 0.0; s2 = 0.0;
+        for (int w = 0; w < 256 / ELD_WAVE; ++w) { s1 += red[w][0]; s2 += red[w][1]; }
+        if (l < L) {
+            sums[((size_t)f * L + l) * 2] = s1;
+            sums[((size_t)f * L + l) * 2 + 1] = s2;
+        } else {
+            if (n & 1) {                                       // the median element: M = 0, it enters the t sums only
+                const double tm = ts[(size_t)f * n + n / 2];
+                s1 += tm;
+                s2 += tm * tm;
+            }
+            tsums[(size_t)f * 2] = s1;
+            tsums[(size_t)f * 2 + 1] = s2;
+        }
+    }
+}
+
+int parse_pattern(const int* raw_pattern, Pattern& p) {
+    if (!raw_pattern) return ELD_EINVAL;
+    bool seen[4] = {false, false, false, false};
+    for (int i = 0; i < 4; ++i) {
+        const int k = raw_pattern[i];
+        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
+        seen[k] = true;
+        p.c[i] = k;
+    }
+    return 0;
+}
+
+bool mosaic_ok(int F, int Hm, int Wm) { return F >= 0 && Hm >= 0 && Wm >= 0 && Hm % 2 == 0 && Wm % 2 == 0 && F <= 65535; }
+bool vec_ok(const void* p, int Wm) { return Wm % 8 == 0 && ((uintptr_t)p & 15u) == 0; }
+bool word_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }   // rows are read as 32-bit words (two pixels)
+
+}  // namespace
+
+extern "C" size_t eld_calib_bias_stats_workspace_bytes(int F, int Hm) {
+    return F <= 0 || Hm <= 0 ? 0 : (size_t)F * Hm * 4 * sizeof(uint64_t);
+}
+
+extern "C" int eld_calib_bias_stats(const uint16_t* u, int F, int Hm, int Wm, const int* raw_pattern, uint64_t* chan_sums, uint64_t* row_sums,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    Pattern pat;
+    if (!mosaic_ok(F, Hm, Wm) || parse_pattern(raw_pattern, pat)) return ELD_EINVAL;
+    if (F == 0 || Hm == 0 || Wm == 0) return 0;
+    if (!u || !chan_sums || !row_sums || !ws || !word_aligned(u)) return ELD_EINVAL;
+    if (ws_bytes < eld_calib_bias_stats_workspace_bytes(F, Hm)) return ELD_EWS;
+    uint64_t* part = static_cast<uint64_t*>(ws);
+    hipStream_t s = as_stream(stream);
+    if (vec_ok(u, Wm)) ELD_LAUNCH(bias_row_kernel<true>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, row_sums, part);
+    else ELD_LAUNCH(bias_row_kernel<false>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, row_sums, part);
+    ELD_LAUNCH_CHECK();
+    ELD_LAUNCH(chan_reduce_kernel<2>, dim3(F), dim3(CB_THREADS), 0, s, part, Hm, pat, chan_sums);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int eld_calib_bias_residual(const uint16_t* u, int F, int Hm, int Wm, const int* raw_pattern, const double* black_level,
+                                       const double* color_bias, const double* row_offset, float* t, void* stream) {
+    Pattern pat;
+    if (!mosaic_ok(F, Hm, Wm) || parse_pattern(raw_pattern, pat) || !black_level) return ELD_EINVAL;
+    if (F == 0 || Hm == 0 || Wm == 0) return 0;
+    if (!u || !color_bias || !row_offset || !t || !word_aligned(u) || ((uintptr_t)t & 7u)) return ELD_EINVAL;
+    Black blk;
+    for (int k = 0; k < 4; ++k) blk.b[k] = black_level[k];
+    ELD_LAUNCH(bias_residual_kernel, dim3(Hm, F), dim3(CB_THREADS), 0, as_stream(stream), u, Hm, Wm, pat, blk, color_bias, row_offset, t);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t eld_calib_flat_stats_workspace_bytes(int P, int Hm) {
+    return P <= 0 || Hm <= 0 ? 0 : (size_t)P * Hm * 8 * sizeof(uint64_t);
+}
+
+extern "C" int eld_calib_flat_stats(const uint16_t* ab, int P, int Hm, int Wm, const int* raw_pattern, int white_level, int64_t* out,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    Pattern pat;
+    if (!mosaic_ok(P, Hm, Wm) || parse_pattern(raw_pattern, pat) || white_level < 0) return ELD_EINVAL;
+    if (P == 0 || Hm == 0 || Wm == 0) return 0;
+    if (!ab || !out || !ws || !word_aligned(ab)) return ELD_EINVAL;
+    if (ws_bytes < eld_calib_flat_stats_workspace_bytes(P, Hm)) return ELD_EWS;
+    uint64_t* part = static_cast<uint64_t*>(ws);
+    hipStream_t s = as_stream(stream);
+    if (vec_ok(ab, Wm)) ELD_LAUNCH(flat_row_kernel<true>, dim3(Hm, P), dim3(CB_THREADS), 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
+    else ELD_LAUNCH(flat_row_kernel<false>, dim3(Hm, P), dim3(CB_THREADS), 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
+    ELD_LAUNCH_CHECK();
+    ELD_LAUNCH(chan_reduce_kernel<4>, dim3(P), dim3(CB_THREADS), 0, s, part, Hm, pat, reinterpret_cast<uint64_t*>(out));
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t eld_calib_ppcc_workspace_bytes(int F, size_t n, int L) {
+    if (F <= 0 || n < 3 || L <= 0) return 0;
+    const size_t nb = pp_blocks(n);
+    return (size_t)F * nb * ((size_t)L + 1) * 2 * sizeof(double);
+}
+
+extern "C" int eld_calib_ppcc(const float* t_sorted, int F, size_t n, const float* lambdas, int L, double* sums, double* tsums,
+                              void* ws, size_t ws_bytes, void* stream) {
+    if (F < 0 || L < 0 || F > 65535 || (n < 3 && F > 0) || n > ((size_t)1 << 40)) return ELD_EINVAL;
+    if (F == 0 || L == 0) return 0;
+    if (!t_sorted || !lambdas || !sums || !tsums || !ws) return ELD_EINVAL;
+    if (ws_bytes < eld_calib_ppcc_workspace_bytes(F, n, L)) return ELD_EWS;
+    const size_t nb = pp_blocks(n);
+    if (nb > 0x7FFFFFFFu) return ELD_EINVAL;
+    double* part = static_cast<double*>(ws);
+    double* tpart = part + (size_t)F * nb * L * 2;
+    hipStream_t s = as_stream(stream);
+    ELD_LAUNCH(ppcc_partial_kernel, dim3((unsigned)nb, (L + PP_LG - 1) / PP_LG, F), dim3(PP_THREADS), 0, s, t_sorted, n, lambdas, L, part, tpart);
+    ELD_LAUNCH_CHECK();
+    ELD_LAUNCH(ppcc_final_kernel, dim3(L + 1, F), dim3(256), 0, s, t_sorted, n, L, nb, part, tpart, sums, tsums);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}

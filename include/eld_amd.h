@@ -134,6 +134,31 @@ int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int N, int h, 
  * 1024 / 16383 in the reference).  white_point must exceed black_level.  Bit-exact. */
 int eld_pack_raw_xtrans_u16(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point, void* stream);
 
+/* ---- noise-parameter calibration (eld_amd/calibrate.py; estimators: DESIGN.md "Calibration") ------------------------------
+ * Inputs are uint16 Bayer sensor mosaics [F,Hm,Wm] with even sides; packed channel of pixel (y,x) = raw_pattern[y&1][x&1] (HOST
+ * array of 4 ints, a permutation of 0..3: R, G1, B, G2), as eld_pack_raw_bayer_u16.  Integer sums are exact (uint64 / int64, equal
+ * to NumPy int64 bit for bit); float64 sums are reduced in an order fixed by the shape, without atomics: two calls give identical bits.
+ * The mosaics are read as 32-bit words (two pixels): `u` and `ab` must be 4-byte aligned (ELD_EINVAL otherwise), the residual `t` 8-byte
+ * aligned; PyTorch allocations are, a view that starts at an odd element is not.
+ *
+ * Bias statistics: chan_sums[F][4][2] = (sum u, sum u^2) per frame and channel; row_sums[F][Hm][2] = sum u over the even / odd
+ * columns of each mosaic row.  Workspace: eld_calib_bias_stats_workspace_bytes(F, Hm). */
+size_t eld_calib_bias_stats_workspace_bytes(int F, int Hm);
+int eld_calib_bias_stats(const uint16_t* u, int F, int Hm, int Wm, const int* raw_pattern, uint64_t* chan_sums, uint64_t* row_sums, void* ws, size_t ws_bytes, void* stream);
+/* Bias residual: t[f][y][x] = float32(((u - black_level[c]) - color_bias[f][c]) - row_offset[f][y]), float64 arithmetic rounded once
+ * (black_level: HOST array of 4 doubles; color_bias: device double[F][4]; row_offset: device double[F][Hm]; t: float32 [F,Hm,Wm]). */
+int eld_calib_bias_residual(const uint16_t* u, int F, int Hm, int Wm, const int* raw_pattern, const double* black_level, const double* color_bias, const double* row_offset, float* t, void* stream);
+/* Flat pairs ab [P][2][Hm][Wm] (a = ab[p][0], b = ab[p][1]): out[P][4][4] = per channel (sum(a+b), sum(a-b), sum((a-b)^2),
+ * #pixels with a >= white_level or b >= white_level).  Workspace: eld_calib_flat_stats_workspace_bytes(P, Hm). */
+size_t eld_calib_flat_stats_workspace_bytes(int P, int Hm);
+int eld_calib_flat_stats(const uint16_t* ab, int P, int Hm, int Wm, const int* raw_pattern, int white_level, int64_t* out, void* ws, size_t ws_bytes, void* stream);
+/* Tukey-lambda probability-plot sums of F sorted rows t_sorted[F][n] (n >= 3) against the quantiles M_lam(m_i) at Filliben's medians
+ * m_i, for the L shapes lambdas[L] (device float32): sums[F][L][2] = (sum t*M, sum M^2), tsums[F][2] = (sum t, sum t^2); sum M = 0
+ * exactly (the quantiles are built antisymmetric).  PPCC r = sum tM / sqrt(sum M^2 (sum t^2 - (sum t)^2/n)); probplot slope =
+ * sum tM / sum M^2.  Workspace: eld_calib_ppcc_workspace_bytes(F, n, L). */
+size_t eld_calib_ppcc_workspace_bytes(int F, size_t n, int L);
+int eld_calib_ppcc(const float* t_sorted, int F, size_t n, const float* lambdas, int L, double* sums, double* tsums, void* ws, size_t ws_bytes, void* stream);
+
 
 /* Training-pair augmentation of ELDTrainDataset.__getitem__ (dataset/sid_dataset.py:344-352), batched on device:
  * per image n, bits of aug[n]: 1 = flip H (axis 1), 2 = flip W (axis 2), 4 = transpose (0,2,1), applied in that order;

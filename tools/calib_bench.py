@@ -1,0 +1,162 @@
+"""Stage timings of the calibration pipeline (eld_amd/calibrate.py) on synthetic frames: 9 ISOs x (2 bias frames + 8 flat pairs) of
+4256 x 2848 mosaics, plus one 8288 x 5520 bias stack (Nikon D850 size).  Reports per stage the device time (hip events, median of
+--reps), the stats kernels' GB/s against the measured 6.3 TB/s HBM ceiling, the PPCC's element*lambda/s against its VALU throughput
+bound (ppcc_bound) and torch.sort's time.  One JSON line at the end (profiles/calib_bench.json is one such run).
+
+    python tools/calib_bench.py [--reps 5] [--isos 9] [--out FILE]
+"""
+import argparse
+import ctypes
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from eld_amd import _lib as L  # noqa: E402
+from eld_amd import calibrate as CAL  # noqa: E402
+
+HBM_BPS = 6.3e12                 # measured HBM ceiling of the MI355X (float4 copy)
+CUS, SIMDS, CLOCK = 256, 4, 2.4e9   # 2.4 GHz: the peak shader clock, so the bound below is an upper bound
+
+# PPCC VALU bound, a throughput model of ppcc_partial_kernel's inner loop (gfx950 ISA, 124 VGPRs: 4 waves per SIMD, enough to keep the
+# vector unit issuing).  Cycles per wave64 instruction at throughput: fp32 2 (32 lanes per cycle), float64 FMA / add / mul / conversion
+# 4 (half rate: 78.6 of 157.3 TF/s), transcendental 8 (quarter rate).  Per (wave, lambda):
+CYC_HEAD = 2 * 2                 # x = lam g, the |x| < 1 test
+CYC_DIRECT = 4 * 2 + 2 * 8       # |x| >= 1 in some lane: 2 mul, sub, mul by 1/lam; 2 exp2
+CYC_POLY = 9 * 2 + 1 * 8         # |x| < 1 in some lane: x^2, 5-term Horner, lam h + 1, 2 mul; 1 exp2
+CYC_ACC = 1 * 4 + 2 * 4          # M -> float64, 2 float64 FMAs
+CYC_PAIR = 120                   # per wave and pair, shared by the block's 16 lambdas: the Filliben medians (float64), 2 log2, h, g,
+                                 # the two loads -> dt, the t sums (~30 float64 / fp32 ops)
+PP_LG = 16
+
+
+def ppcc_bound(n, lambdas):
+    """element*lambda/s the kernel could reach at these prices: every wave of 64 adjacent pairs runs the polynomial and / or the direct
+    form for each lambda as its lanes need (a wave whose lanes disagree runs both)."""
+    npairs = n // 2
+    i = np.arange(npairs, dtype=np.float64)
+    m = (i + 1 - 0.3175) / (n + 0.365)
+    m[0] = 1 - 0.5 ** (1.0 / n)
+    g = (np.log2(1 - m) - np.log2(m)) * (np.log(2) / 2)
+    pad = (-npairs) % 64
+    g = np.concatenate([g, np.full(pad, g[-1])]).reshape(-1, 64)
+    gmin, gmax = g.min(axis=1), g.max(axis=1)
+    cyc = 0.0
+    for lam in np.abs(np.asarray(lambdas, np.float64)):
+        poly = np.count_nonzero(lam * gmin < 1)
+        direct = np.count_nonzero(lam * gmax >= 1)
+        cyc += g.shape[0] * (CYC_HEAD + CYC_ACC + CYC_PAIR / PP_LG) + poly * CYC_POLY + direct * CYC_DIRECT
+    return float(n) * len(lambdas) * CUS * SIMDS * CLOCK / cyc      # cyc: SIMD cycles of the whole launch, spread over every SIMD
+
+
+def timed(fn, reps):
+    ts = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b) * 1e-3)
+    return float(np.median(ts))
+
+
+def frames(F, Hm, Wm, seed):
+    g = torch.Generator(device='cuda').manual_seed(seed)
+    x = torch.randint(480, 560, (F, Hm, Wm), generator=g, device='cuda', dtype=torch.int32)
+    return x.to(torch.int16)
+
+
+def bench_stack(u, reps, lam):
+    F, Hm, Wm = u.shape
+    n = Hm * Wm
+    lib = L.lib()
+    pat = (ctypes.c_int * 4)(0, 1, 3, 2)
+    cs = torch.empty((F, 4, 2), dtype=torch.int64, device='cuda')
+    rs = torch.empty((F, Hm, 2), dtype=torch.int64, device='cuda')
+    ws = torch.empty(lib.eld_calib_bias_stats_workspace_bytes(F, Hm), dtype=torch.uint8, device='cuda')
+    t_stats = timed(lambda: L.check(lib.eld_calib_bias_stats(L.dptr(u), F, Hm, Wm, pat, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(),
+                                                             L.cur_stream())), reps)
+    st = CAL.bias_stats_from_sums(cs.cpu().numpy(), rs.cpu().numpy(), [[0, 1], [3, 2]], [512.0] * 4, Hm, Wm)
+    cb = torch.from_numpy(st['color_bias']).cuda()
+    rho = torch.from_numpy(st['row_offset']).cuda()
+    t = torch.empty((F, n), dtype=torch.float32, device='cuda')
+    blk = (ctypes.c_double * 4)(512.0, 512.0, 512.0, 512.0)
+    t_res = timed(lambda: L.check(lib.eld_calib_bias_residual(L.dptr(u), F, Hm, Wm, pat, blk, L.dptr(cb), L.dptr(rho), L.dptr(t),
+                                                              L.cur_stream())), reps)
+    ts = {}
+    t_sort = timed(lambda: ts.__setitem__('v', torch.sort(t, dim=1).values), reps)
+    x = ts['v'].contiguous()
+    lamd = torch.from_numpy(lam.astype(np.float32)).cuda()
+    sums = torch.empty((F, lam.size, 2), dtype=torch.float64, device='cuda')
+    tsums = torch.empty((F, 2), dtype=torch.float64, device='cuda')
+    pws = torch.empty(lib.eld_calib_ppcc_workspace_bytes(F, n, lam.size), dtype=torch.uint8, device='cuda')
+    t_ppcc = timed(lambda: L.check(lib.eld_calib_ppcc(L.dptr(x), F, n, L.dptr(lamd), lam.size, L.dptr(sums), L.dptr(tsums), L.dptr(pws),
+                                                      pws.numel(), L.cur_stream())), reps)
+    return {'frames': F, 'Hm': Hm, 'Wm': Wm,
+            'bias_stats_s': t_stats, 'bias_stats_GBps': F * n * 2 / t_stats / 1e9,
+            'residual_s': t_res, 'residual_GBps': F * n * 6 / t_res / 1e9,
+            'sort_s': t_sort, 'ppcc_s': t_ppcc, 'ppcc_elem_lambda_per_s': F * n * lam.size / t_ppcc}
+
+
+def bench_flats(ab, reps):
+    P, _, Hm, Wm = ab.shape
+    lib = L.lib()
+    pat = (ctypes.c_int * 4)(0, 1, 3, 2)
+    out = torch.empty((P, 4, 4), dtype=torch.int64, device='cuda')
+    ws = torch.empty(lib.eld_calib_flat_stats_workspace_bytes(P, Hm), dtype=torch.uint8, device='cuda')
+    t = timed(lambda: L.check(lib.eld_calib_flat_stats(L.dptr(ab), P, Hm, Wm, pat, 16383, L.dptr(out), L.dptr(ws), ws.numel(),
+                                                       L.cur_stream())), reps)
+    return {'pairs': P, 'flat_stats_s': t, 'flat_stats_GBps': P * 2 * Hm * Wm * 2 / t / 1e9}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--isos', type=int, default=9)
+    ap.add_argument('--out', help='also write the JSON result here')
+    a = ap.parse_args()
+    L.load_library()
+    lam = CAL.DEFAULT_LAMBDAS
+    iso_rows = []
+    for i in range(a.isos):
+        bias = frames(2, 2848, 4256, 10 * i)
+        flats = frames(16, 2848, 4256, 10 * i + 1).view(8, 2, 2848, 4256)
+        r = bench_stack(bias, a.reps, lam)
+        r.update(bench_flats(flats, a.reps))
+        iso_rows.append(r)
+        del bias, flats
+    big = bench_stack(frames(2, 5520, 8288, 99), a.reps, lam)
+    torch.cuda.synchronize()
+    keys = ('bias_stats_s', 'residual_s', 'sort_s', 'ppcc_s', 'flat_stats_s')
+    per_iso = {k: float(np.median([r[k] for r in iso_rows])) for k in keys}
+    total = sum(sum(r[k] for k in keys) for r in iso_rows)
+    res = {'isos': a.isos, 'per_iso_median_s': per_iso, 'session_total_s': total,
+           'bias_stats_GBps': float(np.median([r['bias_stats_GBps'] for r in iso_rows])),
+           'residual_GBps': float(np.median([r['residual_GBps'] for r in iso_rows])),
+           'flat_stats_GBps': float(np.median([r['flat_stats_GBps'] for r in iso_rows])),
+           'ppcc_elem_lambda_per_s': float(np.median([r['ppcc_elem_lambda_per_s'] for r in iso_rows])),
+           'nikon_d850': big}
+    res['frac_hbm'] = {k: res[k] * 1e9 / HBM_BPS for k in ('bias_stats_GBps', 'residual_GBps', 'flat_stats_GBps')}
+    res['ppcc_valu_bound_elem_lambda_per_s'] = ppcc_bound(2848 * 4256, lam)
+    res['ppcc_frac_valu'] = res['ppcc_elem_lambda_per_s'] / res['ppcc_valu_bound_elem_lambda_per_s']
+    big['ppcc_valu_bound_elem_lambda_per_s'] = ppcc_bound(5520 * 8288, lam)
+    big['ppcc_frac_valu'] = big['ppcc_elem_lambda_per_s'] / big['ppcc_valu_bound_elem_lambda_per_s']
+    res['device'] = torch.cuda.get_device_name()
+    res['library_src'] = L.build_src_hash()
+    for r in iso_rows[:1] + [big]:
+        print('%dx%dx%d: bias stats %.3f ms (%.0f GB/s)  residual %.3f ms (%.0f GB/s)  sort %.3f ms  ppcc %.3f ms (%.3g elem*lambda/s)'
+              % (r['frames'], r['Hm'], r['Wm'], 1e3 * r['bias_stats_s'], r['bias_stats_GBps'], 1e3 * r['residual_s'], r['residual_GBps'],
+                 1e3 * r['sort_s'], 1e3 * r['ppcc_s'], r['ppcc_elem_lambda_per_s']))
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, 'w') as f:
+            json.dump(res, f, indent=1)
+            f.write('\n')
+
+
+if __name__ == '__main__':
+    main()
