@@ -82,6 +82,16 @@ SIGNATURES = {
     'eld_convt2x2_backward_weight': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     'eld_maxpool2x2_forward': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'eld_maxpool2x2_backward': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'eld_conv3x3_forward_bf16': (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'eld_conv3x3_backward_data_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'eld_conv3x3_backward_weight_bf16': (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'eld_convt2x2_forward_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'eld_convt2x2_backward_data_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'eld_convt2x2_backward_weight_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'eld_maxpool2x2_forward_bf16': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    'eld_maxpool2x2_backward_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'eld_debug_last_conv_kernel': (C.c_char_p, []),
+    'eld_debug_unet_region': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i)]),
 }
 
 

@@ -51,6 +51,10 @@ __device__ __forceinline__ uint32_t fdiv_u32(uint32_t n, FastDiv f) {
 
 static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 
+// Test hook behind eld_debug_last_conv_kernel: the launcher that picks a convolution or weight-gradient kernel family records its name (a
+// string literal) right before the launch.  Host-side only: one relaxed atomic store per launch, no device work.
+void eld_note_conv_kernel(const char* family);
+
 // compute units of the CURRENT device (persistent-grid sizing); read once per device, immutable afterwards
 static inline int eld_num_cus() {
     static int cus[64] = {0};

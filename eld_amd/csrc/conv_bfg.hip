@@ -265,8 +265,10 @@ int launch_conv_bfg(const ConvArgs& a, int mode, hipStream_t st) {
     if (!bn || a.C1 != 0) return ELD_ENOTSUP;
     if (!gather) {
         if (a.epi != EPI_CONVT_FWD || bn != 128) return ELD_ENOTSUP;
+        eld_note_conv_kernel("conv_bfg<128>");
         return launch_bfg<128, false>(a, st);
     }
     if (a.epi != EPI_GRAD || a.split != a.Nout || a.out1 != nullptr) return ELD_ENOTSUP;
+    eld_note_conv_kernel(bn == 128 ? "conv_bfg<128,gather>" : "conv_bfg<64,gather>");
     return bn == 128 ? launch_bfg<128, true>(a, st) : launch_bfg<64, true>(a, st);
 }

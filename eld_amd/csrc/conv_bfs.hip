@@ -355,6 +355,7 @@ int launch_conv_bfs(const ConvArgs& a, hipStream_t st) {
     if (a.pool_out && (a.epi != EPI_FWD || (a.H & 1) || (a.W & 1))) return ELD_EINVAL;
     if (a.epi == EPI_GRAD && (a.split != 32 || a.out1 != nullptr)) return ELD_ENOTSUP;
     if (a.epi != EPI_FWD && a.epi != EPI_GRAD) return ELD_ENOTSUP;
+    eld_note_conv_kernel("conv_bfs");
     if (a.epi == EPI_GRAD && a.act0 != nullptr) {
         if (a.C0 + a.C1 != 32) return ELD_ENOTSUP;      // the slope variant assumes one chunk per tile (the U-Net's two such launches have K = 32)
         return a.codes0 ? launch_bfs<2, 8, 2>(a, st) : launch_bfs<2, 8, 1>(a, st);

@@ -376,6 +376,7 @@ bool bfw_takes(const ConvArgs& a) {
 int launch_conv_bfw(const ConvArgs& a, hipStream_t st) {
     if ((size_t)a.H * a.W * a.C0 * 2 >= 0xFFFFFFF0ull) return ELD_ENOTSUP;
     if (a.pool_out && (a.epi != EPI_FWD || (a.H & 1) || (a.W & 1))) return ELD_EINVAL;
+    eld_note_conv_kernel("conv_bfw");
     if (a.epi == EPI_GRAD && (a.act0 != nullptr || a.act1 != nullptr)) return launch_bfw<true>(a, st);
     return launch_bfw<false>(a, st);
 }

@@ -508,6 +508,10 @@ long long conv_tile_count(int N, int H, int W, int TH, bool pooled) {
     return tile_count(N, H, W, th, tw);
 }
 
+static std::atomic<const char*> g_last_conv_kernel{""};
+void eld_note_conv_kernel(const char* family) { g_last_conv_kernel.store(family, std::memory_order_relaxed); }
+extern "C" const char* eld_debug_last_conv_kernel(void) { return g_last_conv_kernel.load(std::memory_order_relaxed); }
+
 int launch_conv(const ConvArgs& a_in, int mode, hipStream_t st) {
     ConvArgs a = a_in;
     a.dbg = 0;
@@ -523,17 +527,21 @@ int launch_conv(const ConvArgs& a_in, int mode, hipStream_t st) {
     if (a.dtype == DT_BF16) {
         if (mode == CONV_3X3 && a.epi != EPI_CONVT_FWD && bfd_slab_bn(a.Nout, Cin, a.N, a.H, a.W)) return launch_conv_bfd(a, st);      // weights in slab layout
         if (mode != CONV_3X3 && !a.pool_out && bfg_slab_bn(mode == CONV_GATHER2X2, a.Nout, a.C0, a.Cout_t, a.N, a.H, a.W)) return launch_conv_bfg(a, mode, st);      // weights in bfg slab layout
-        return a.pool_out ? ELD_ENOTSUP : launch_dt<bf16_t>(a, mode, st);
+        if (a.pool_out) return ELD_ENOTSUP;
+        eld_note_conv_kernel(mode == CONV_3X3 ? "conv_igemm<bf16>" : (mode == CONV_1X1 ? "conv_igemm<bf16,1x1>" : "conv_igemm<bf16,gather>"));
+        return launch_dt<bf16_t>(a, mode, st);
     }
     const int algo = resolve_algo(a.algo);
     if (a.pool_out && !(mode == CONV_3X3 && a.epi == EPI_FWD && algo == 1 && a.dtype == DT_F32)) return ELD_ENOTSUP;     // fused pooling: conv_x3.hip only
-    if (mode == CONV_3X3 && a.epi != EPI_CONVT_FWD && algo == 1) return launch_conv_x3(a, st);
+    if (mode == CONV_3X3 && a.epi != EPI_CONVT_FWD && algo == 1) { eld_note_conv_kernel("conv_x3"); return launch_conv_x3(a, st); }
     if (mode != CONV_3X3 && algo == 1) {
+        eld_note_conv_kernel("conv_x3_gemm");
         const int rc = launch_conv_x3_gemm(a, mode, st);
         if (rc != ELD_ENOTSUP) return rc;
     }
     if (algo == 2) {                    // two fp16 pieces per operand, three products; needs the operand bounds
         if (!a.amax_in0 || !a.amax_w) return ELD_EINVAL;
+        eld_note_conv_kernel("conv_igemm<f32,h2>");
         const bool n64 = a.Nout % 64 == 0;
         switch (mode) {
             case CONV_3X3: return n64 ? launch_t<float, CONV_3X3, 64, 2, true>(a, st) : launch_t<float, CONV_3X3, 32, 4, true>(a, st);
@@ -542,5 +550,6 @@ int launch_conv(const ConvArgs& a_in, int mode, hipStream_t st) {
         }
         return ELD_EINVAL;
     }
+    eld_note_conv_kernel("conv_igemm<f32>");
     return launch_dt<float>(a, mode, st);
 }

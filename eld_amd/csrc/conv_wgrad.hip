@@ -1149,6 +1149,7 @@ bool wgradt8_takes(int CA, int CB) {
 int wgradt8_ntiles(int N, int H, int W) { return ((W + 7) / 8) * ((H + 7) / 8) * N; }
 
 static int launch_wt8(WgradArgs a, hipStream_t st) {
+    eld_note_conv_kernel("wgradt8");
     a.xcd = eld_xcd_mask() & XCD_WGRAD8;
     a.band = eld_tile_band();
     a.tiles_x = (a.W + 7) / 8;
@@ -1191,6 +1192,7 @@ int wgrad8_ntiles(int CA, int CBp, int N, int H, int W, bool bf16) {
 
 template <typename T, int WCO, int WCI, int WPIX, int TH, int TWT, int STREAM = 0>
 static int launch_w8(WgradArgs a, hipStream_t st) {
+    eld_note_conv_kernel(sizeof(T) == 2 ? "wgrad8<bf16>" : "wgrad8<f32>");
     a.xcd = eld_xcd_mask() & XCD_WGRAD8;
     a.band = eld_tile_band();
     constexpr int COB = 32 * WCO, JBK = 32 * WCI;
@@ -1212,6 +1214,7 @@ static int launch_w8(WgradArgs a, hipStream_t st) {
 
 template <int WCO, int WCI, int WPIX, int TH, int TWT>
 static int launch_w8d(WgradArgs a, hipStream_t st) {
+    eld_note_conv_kernel("wgrad8d");
     a.xcd = eld_xcd_mask() & XCD_WGRAD8;
     a.band = eld_tile_band();
     constexpr int COB = 32 * WCO, JBK = 32 * WCI;
@@ -1276,6 +1279,7 @@ static int launch_wgrad8(const WgradArgs& a, hipStream_t st) {
 
 template <typename T, int MODE, int WCO, int TH, int ALG = ALG_F32>
 static int launch_w(WgradArgs a, hipStream_t st) {
+    eld_note_conv_kernel(sizeof(T) == 2 ? (MODE == CONV_3X3 ? "wgrad<bf16>" : "wgrad<bf16,gather>") : (MODE == CONV_3X3 ? "wgrad<f32>" : "wgrad<f32,gather>"));
     a.xcd = eld_xcd_mask() & XCD_WGRAD;
     constexpr int COB = 32 * WCO;
     constexpr int X_PIX = MODE == CONV_3X3 ? (TH + 2) * (TW + 2) : 4 * TH * TW;

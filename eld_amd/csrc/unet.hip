@@ -918,7 +918,8 @@ extern "C" size_t eld_layer_workspace_bytes(int N, int H, int W, int Cin, int Co
     const int cinp = (Cin + 15) / 16 * 16;
     size_t f = (size_t)9 * Cout * cinp * 2 + 64;                            // one packed weight set (fp32 or pre-split slabs)
     size_t p = 0, q;
-    if (Cout % 32 == 0) { q = wgrad_geom(CONV_3X3, Cout, Cin, N, H, W, 0).floats; p = q > p ? q : p; q = wgrad_geom(CONV_3X3, Cout, Cin, N, H, W, 1).floats; p = q > p ? q : p; }
+    if (Cout % 32 == 0) { q = wgrad_geom(CONV_3X3, Cout, Cin, N, H, W, 0).floats; p = q > p ? q : p; q = wgrad_geom(CONV_3X3, Cout, Cin, N, H, W, 1).floats; p = q > p ? q : p;
+                          q = wgrad_geom(CONV_3X3, Cout, Cin, N, H, W, 3).floats; p = q > p ? q : p; }      // (3: the bf16 entry points below)
     if (Cin % 32 == 0) { q = wgrad_geom(CONV_GATHER2X2, Cin, Cout, N, H, W, 0).floats; p = q > p ? q : p; q = wgrad_geom(CONV_GATHER2X2, Cin, Cout, N, H, W, 1).floats; p = q > p ? q : p; }
     q = colsum_ws_floats(Cout > Cin ? Cout : Cin); p = q > p ? q : p;
     return (align_up(f, 64) + align_up(p, 64) + 64) * sizeof(float);      // + 64 operand-bound slots (conv_fp32_algo 2)
@@ -1043,4 +1044,142 @@ extern "C" int eld_maxpool2x2_backward(const float* act, const float* dp, const 
     if (N == 0) return 0;
     if (!act || !dp || !g || C % 4) return ELD_EINVAL;
     return launch_maxpool_bwd(act, dp, skip, g, N, Ho, Wo, C, as_stream(stream));
+}
+
+// ---- single layers on NHWC bf16 tensors (test hooks of the bf16 network's dispatchers) -------------------------------------------------
+// Each call packs the reference-layout fp32 weights as pack_weights does for the same launch (bf16, round to nearest even; the DMA kernels' slab
+// width from bfd_slab_bn / bfg_slab_bn) and calls the dispatcher the bf16 U-Net calls, so the launch runs on the kernel family the network would use.
+static int pack_one_bf16(const float* w, float* pack, int kind, int Cout, int Cin, int T, int bfdbn, int bfgbn, hipStream_t st) {
+    PackJobs jobs;
+    jobs.n = 1;
+    PackJob J = {};
+    J.kind = kind; J.Cout = Cout; J.Cin = Cin; J.Cinp = Cin; J.T = T; J.bf16 = 1; J.bfdbn = bfdbn; J.bfgbn = bfgbn;
+    jobs.job[0] = J;
+    return launch_pack_all(jobs, w, pack, st);
+}
+
+extern "C" int eld_conv3x3_forward_bf16(const uint16_t* in0, int C0, const uint16_t* in1, int C1, const float* w, const float* bias, uint16_t* out,
+                                        uint16_t* pool_out, int N, int H, int W, int Cout, int lrelu, void* ws, size_t ws_bytes, void* stream) {
+    if (N == 0) return 0;
+    if (!in0 || !w || !bias || !out || C0 % 32 || C1 % 32 || (C1 && !in1) || Cout % 32) return ELD_EINVAL;
+    float *pack, *part;
+    RC(layer_ws(ws, ws_bytes, N, H, W, C0 + C1, Cout, &pack, &part));
+    hipStream_t st = as_stream(stream);
+    RC(pack_one_bf16(w, pack, PACK_CONV_FWD, Cout, C0 + C1, 9, bfd_slab_bn(Cout, C0 + C1, N, H, W), 0, st));
+    return conv_fwd_bf16(in0, C0, in1, C1, reinterpret_cast<const bf16_t*>(pack), bias, out, N, H, W, Cout, lrelu, st, pool_out);
+}
+
+extern "C" int eld_conv3x3_backward_data_bf16(const uint16_t* g, const float* w, uint16_t* din0, uint16_t* din1, int split, const uint16_t* act0,
+                                              const uint16_t* act1, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream) {
+    if (N == 0) return 0;
+    if (!g || !w || !din0 || Cin % 32 || Cout % 32 || split < 32 || split % 32 || split > Cin || (split < Cin && !din1)) return ELD_EINVAL;
+    float *pack, *part;
+    RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
+    hipStream_t st = as_stream(stream);
+    RC(pack_one_bf16(w, pack, PACK_CONV_BWD, Cout, Cin, 9, bfd_slab_bn(Cin, Cout, N, H, W), 0, st));
+    return conv_bwd_data_bf16(g, reinterpret_cast<const bf16_t*>(pack), din0, din1, split, act0, act1, N, H, W, Cin, Cout, st);
+}
+
+extern "C" int eld_conv3x3_backward_weight_bf16(const uint16_t* g, const uint16_t* x0, int C0, const uint16_t* x1, int C1, float* dw, float* db, int N,
+                                                int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream) {
+    if (N == 0) return 0;
+    if (!g || !x0 || !dw || Cout % 32 || C0 % 8 || C1 % 8 || (C1 && (!x1 || C0 % 32))) return ELD_EINVAL;
+    float *pack, *part;
+    RC(layer_ws(ws, ws_bytes, N, H, W, C0 + C1, Cout, &pack, &part));
+    return conv_wgrad_bf16(g, Cout, x0, C0, x1, C1, dw, db, part, N, H, W, as_stream(stream));
+}
+
+extern "C" int eld_convt2x2_forward_bf16(const uint16_t* in, const float* w, const float* bias, uint16_t* out, int N, int H, int W, int Cin, int Cout,
+                                         void* ws, size_t ws_bytes, void* stream) {
+    if (N == 0) return 0;
+    if (!in || !w || !bias || !out || Cin % 32 || Cout % 8) return ELD_EINVAL;
+    float *pack, *part;
+    RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
+    hipStream_t st = as_stream(stream);
+    RC(pack_one_bf16(w, pack, PACK_CONVT_FWD, Cout, Cin, 4, 0, bfg_slab_bn(false, 4 * Cout, Cin, Cout, N, H, W), st));
+    ConvArgs a = {};      // as unet_forward_bf16
+    a.in0 = in; a.C0 = Cin; a.wp = pack; a.N = N; a.H = H; a.W = W; a.Nout = 4 * Cout;
+    a.epi = EPI_CONVT_FWD; a.bias = bias; a.out0 = out; a.Cout_t = Cout; a.dtype = DT_BF16;
+    return launch_conv(a, CONV_1X1, st);
+}
+
+extern "C" int eld_convt2x2_backward_data_bf16(const uint16_t* dout, const float* w, const uint16_t* act, uint16_t* din, int N, int H, int W, int Cin,
+                                               int Cout, void* ws, size_t ws_bytes, void* stream) {
+    if (N == 0) return 0;
+    if (!dout || !w || !din || Cin % 32 || Cout % 32) return ELD_EINVAL;
+    float *pack, *part;
+    RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
+    hipStream_t st = as_stream(stream);
+    RC(pack_one_bf16(w, pack, PACK_CONVT_BWD, Cout, Cin, 4, 0, bfg_slab_bn(true, Cin, Cout, 0, N, H, W), st));
+    ConvArgs c = {};      // as unet_backward_bf16
+    c.in0 = dout; c.C0 = Cout; c.wp = pack; c.N = N; c.H = H; c.W = W; c.Nout = Cin;
+    c.epi = EPI_GRAD; c.out0 = din; c.split = Cin; c.act0 = act; c.dtype = DT_BF16;
+    return launch_conv(c, CONV_GATHER2X2, st);
+}
+
+extern "C" int eld_convt2x2_backward_weight_bf16(const uint16_t* in, const uint16_t* dout, float* dw, float* db, int N, int H, int W, int Cin, int Cout,
+                                                 void* ws, size_t ws_bytes, void* stream) {
+    if (N == 0) return 0;
+    if (!in || !dout || !dw || Cin % 32 || Cout % 8) return ELD_EINVAL;
+    float *pack, *part;
+    RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
+    hipStream_t st = as_stream(stream);
+    const WgradGeom q = wgrad_geom(CONV_GATHER2X2, Cin, Cout, N, H, W, 0);      // as unet_backward_bf16
+    WgradArgs a = {};
+    a.g = in; a.CA = Cin; a.x0 = dout; a.C0 = Cout; a.N = N; a.H = H; a.W = W; a.dtype = DT_BF16;
+    a.part = part; a.bpart = nullptr; a.CBp = q.CBp; a.psplit = q.psplit;
+    const bool fused_bias = db != nullptr && q.CBp <= q.CA && Cout == q.CBp;
+    a.xbpart = fused_bias ? part + (size_t)q.psplit * q.T * q.CA * q.CBp : nullptr;
+    RC(launch_wgrad(a, CONV_GATHER2X2, st));
+    RC(launch_wgrad_reduce(part, a.xbpart, dw, fused_bias ? db : nullptr, q.psplit, q.T, q.CA, q.CBp, Cout, st, q.CBp));
+    if (!db || fused_bias) return 0;
+    return launch_colsum_bf16(dout, db, part, (size_t)N * 4 * H * W, Cout, st);
+}
+
+extern "C" int eld_maxpool2x2_forward_bf16(const uint16_t* in, uint16_t* out, int N, int Ho, int Wo, int C, void* stream) {
+    if (N == 0) return 0;
+    if (!in || !out || C % 4) return ELD_EINVAL;
+    return launch_maxpool_fwd_bf16(in, out, N, Ho, Wo, C, as_stream(stream));
+}
+
+extern "C" int eld_maxpool2x2_backward_bf16(const uint16_t* act, const uint16_t* dp, const uint16_t* skip, uint16_t* g, int N, int Ho, int Wo, int C,
+                                            void* stream) {
+    if (N == 0) return 0;
+    if (!act || !dp || !g || C % 4) return ELD_EINVAL;
+    return launch_maxpool_bwd_bf16(act, dp, skip, g, N, Ho, Wo, C, as_stream(stream));
+}
+
+// The gradient buffer conv1_1's weight gradient reads in unet_backward_bf16: the head writes gA, every later stage writes the other buffer and
+// swaps -- three swaps per decoder level and per encoder level 4 .. 1 (24, even), one more after conv1_2's backward-data: gB.
+extern "C" int eld_debug_unet_region(int N, int H, int W, int in_ch, int out_ch, int precision, int region, int level, size_t* offset, int* channels,
+                                     int* dtype) {
+    if (!offset || !channels || !dtype || (precision != 0 && precision != 1)) return ELD_EINVAL;
+    Plan P;
+    RC(make_plan(P, N, H, W, in_ch, out_ch));
+    const bool full = region == ELD_REGION_EA || region == ELD_REGION_EB;
+    if (level < 0 || level >= (full ? NLEV : NLEV - 1) || (region >= ELD_REGION_X16 && level != 0)) return ELD_EINVAL;
+    size_t off;
+    int ch = chan(level), dt = precision;
+    switch (region) {
+        case ELD_REGION_EA: off = P.ea[level]; break;
+        case ELD_REGION_EB: off = P.eb[level]; break;
+        case ELD_REGION_POOL: off = P.pool[level]; break;
+        case ELD_REGION_UP: off = P.up[level]; break;
+        case ELD_REGION_DA: off = P.da[level]; break;
+        case ELD_REGION_DB: off = P.db[level]; break;
+        case ELD_REGION_X16:
+            off = P.x16;
+            if (in_ch <= 4) { ch = in_ch; dt = 2; }          // the fp32 NCHW copy of the input (forwards other than eld_unet_forward_loss_ex)
+            else ch = precision ? 32 : 16;
+            break;
+        case ELD_REGION_GRAD_CONV1_1:
+            if (precision != 1) return ELD_ENOTSUP;
+            off = P.gB; ch = 32;
+            break;
+        default: return ELD_EINVAL;
+    }
+    *offset = off * sizeof(float);
+    *channels = ch;
+    *dtype = dt;
+    return 0;
 }

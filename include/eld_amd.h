@@ -330,6 +330,41 @@ int eld_convt2x2_backward_weight(const float* in, const float* dout, float* dw, 
 int eld_maxpool2x2_forward(const float* in, float* out, int N, int Ho, int Wo, int C, void* stream);
 int eld_maxpool2x2_backward(const float* act, const float* dp, const float* skip, float* g, int N, int Ho, int Wo, int C, void* stream);
 
+/* ---- the same single layers with bf16 activations (test hooks of the bf16 network) ----
+ * Activations and gradients are NHWC bf16 device buffers (uint16_t bit patterns); weights come in the reference fp32 layout, bias is fp32,
+ * dw / db are fp32.  Each call packs the weights to bf16 (round to nearest even) in the layout the U-Net's packer would choose for the same
+ * launch and runs the dispatcher the bf16 U-Net runs, so the launch lands on the kernel family the network would use for that shape
+ * (eld_debug_last_conv_kernel names it).  Workspace: eld_layer_workspace_bytes.  Channel counts: multiples of 32 (weight gradients: C0, C1
+ * multiples of 8, C0 of 32 when C1 > 0; transposed convs: Cout a multiple of 8 forward and for the weight gradient). */
+int eld_conv3x3_forward_bf16(const uint16_t* in0, int C0, const uint16_t* in1, int C1, const float* w_oihw, const float* bias, uint16_t* out,
+                             uint16_t* pool_out, int N, int H, int W, int Cout, int lrelu, void* ws, size_t ws_bytes, void* stream);
+/* pool_out (optional): also the 2x2 max-pool of out, fused into the epilogue; ELD_ENOTSUP where the dispatcher would not fuse it (conv_igemm). */
+int eld_conv3x3_backward_data_bf16(const uint16_t* g, const float* w_oihw, uint16_t* din0, uint16_t* din1, int split, const uint16_t* act0,
+                                   const uint16_t* act1, int N, int H, int W, int Cin, int Cout, void* ws, size_t ws_bytes, void* stream);
+int eld_conv3x3_backward_weight_bf16(const uint16_t* g, const uint16_t* x0, int C0, const uint16_t* x1, int C1, float* dw, float* db,
+                                     int N, int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream);
+int eld_convt2x2_forward_bf16(const uint16_t* in, const float* w, const float* bias, uint16_t* out, int N, int H, int W, int Cin, int Cout,
+                              void* ws, size_t ws_bytes, void* stream);
+int eld_convt2x2_backward_data_bf16(const uint16_t* dout, const float* w, const uint16_t* act, uint16_t* din, int N, int H, int W, int Cin,
+                                    int Cout, void* ws, size_t ws_bytes, void* stream);
+int eld_convt2x2_backward_weight_bf16(const uint16_t* in, const uint16_t* dout, float* dw, float* db, int N, int H, int W, int Cin, int Cout,
+                                      void* ws, size_t ws_bytes, void* stream);
+int eld_maxpool2x2_forward_bf16(const uint16_t* in, uint16_t* out, int N, int Ho, int Wo, int C, void* stream);
+int eld_maxpool2x2_backward_bf16(const uint16_t* act, const uint16_t* dp, const uint16_t* skip, uint16_t* g, int N, int Ho, int Wo, int C, void* stream);
+
+/* Test hook: the family name of the most recent convolution or weight-gradient launch of this process ("conv_bfs", "conv_bfw", "conv_bfd<128>",
+ * "conv_bfg<64,gather>", "conv_igemm<bf16>", "wgrad8d", "wgrad8<bf16>", "wgrad<bf16,gather>", ...), recorded by the launcher that chose it;
+ * host-side only, "" before the first launch. */
+const char* eld_debug_last_conv_kernel(void);
+/* Test hook: where the U-Net workspace of problem (N, H, W, in_ch, out_ch, precision) holds a region after a forward (eld_unet_forward_ex /
+ * eld_unet_forward_bf16) or, for ELD_REGION_GRAD_CONV1_1, after a bf16 backward: *offset in bytes, *channels, *dtype = 0 fp32 NHWC, 1 bf16 NHWC,
+ * 2 fp32 NCHW.  level: the U-Net level (pool: the level of the tensor it pools), 0 for X16 and GRAD_CONV1_1.  X16 = the first layer's input as the
+ * forward kept it; GRAD_CONV1_1 = the gradient of conv1_1's output that its weight gradient consumed (bf16 only). */
+enum { ELD_REGION_EA = 0, ELD_REGION_EB = 1, ELD_REGION_POOL = 2, ELD_REGION_UP = 3, ELD_REGION_DA = 4, ELD_REGION_DB = 5, ELD_REGION_X16 = 6,
+       ELD_REGION_GRAD_CONV1_1 = 7 };
+int eld_debug_unet_region(int N, int H, int W, int in_ch, int out_ch, int precision, int region, int level, size_t* offset, int* channels,
+                          int* dtype);
+
 #ifdef __cplusplus
 }
 #endif
