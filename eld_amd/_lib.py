@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get('ELD_AMD_LIB') or os.path.join(_HERE, 'libeld_amd.so')
 # flags / enums of include/eld_amd.h
 SHOT_POISSON, SHOT_GAUSS, READ_GAUSS, READ_TL, ROW, QUANT, CBIAS, CLIP = 1, 2, 4, 8, 16, 32, 64, 128
 AUG_NOTRANSPOSE = 256
+CFA_XTRANS = 512
 IN_F32, IN_U16 = 0, 1
 NPLANES = 6
 PLANE = {'counts': 0, 'n_shot': 1, 'n_read': 2, 't_tl': 3, 'n_row': 4, 'u_q': 5}
@@ -48,6 +49,11 @@ SIGNATURES = {
     'eld_calib_flat_stats': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), _i, _vp, _vp, _sz, _vp]),
     'eld_calib_ppcc_workspace_bytes': (_sz, [_i, _sz, _i]),
     'eld_calib_ppcc': (_i, [_vp, _i, _sz, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    'eld_calib_cell_stats_workspace_bytes': (_sz, [_i, _i, _i]),
+    'eld_calib_cell_stats': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'eld_calib_cell_residual': (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_double), _vp, _vp, _vp, _vp]),
+    'eld_calib_cell_flat_stats_workspace_bytes': (_sz, [_i, _i, _i]),
+    'eld_calib_cell_flat_stats': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     'eld_unet_param_offsets': (_i, [_i, _i, _vp]),
     'eld_unet_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'eld_unet_forward': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _vp]),
@@ -95,7 +101,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 2         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
+ABI_VERSION = 3         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
 PHILOX_ROUNDS = 7      # the sampler's generator: Philox4x32-7 (csrc/philox.h); checked against the library at load
 
 

@@ -2,13 +2,16 @@
 
 The reference ships the calibrated tables of five cameras (camera_params/release/*_params.npy, restated in camera_params.json) but
 not the calibration method (README.md: "we are unable to provide the noise model as well as the calibration method").  This module
-estimates the same table for any Bayer sensor, in DN (raw digital numbers, the sampler's ADU), so that NoiseModel(cameras=[name])
+estimates the same table for any Bayer or X-Trans sensor, in DN (raw digital numbers, the sampler's ADU), so that NoiseModel(cameras=[name])
 can synthesise its noise.  The estimators are the contract of DESIGN.md, "Calibration"; the pixel passes run in HIP
 (eld_amd/csrc/calib.hip: exact integer sums, the float64 residual, the Tukey-lambda PPCC), the rest is float64 NumPy on the host.
 
     sessions = [{'iso': 100, 'bias': (F,Hm,Wm) uint16, 'flats': (P,2,Hm,Wm) uint16}, ...]
     params, diag = calibrate_camera(sessions, raw_pattern, black_level, white_level)
     save_camera_params(params, 'MyCam', 'camera_params/release')
+
+X-Trans (cfa='xtrans'): raw_pattern is rawpy's 6x6 raw_pattern, the pixel passes return per-cell sums (eld_calib_cell_*) that the host
+folds into the colours R, G, B; the table gains 'cfa': 'xtrans' and a (m, 3) color_bias in (R, G, B) order.
 
 Command line: python -m eld_amd.calibrate manifest.json --camera NAME --out DIR (the manifest format is in INTEGRATION.md).
 """
@@ -42,18 +45,50 @@ def _black(black_level):
     return b
 
 
+XT_PERIOD = 6
+CODE_COLOUR = np.array([0, 1, 2, 1])               # rawpy colour code (R, G, B, G2) -> colour class R 0, G 1, B 2
+
+
+def _xpattern(raw_pattern):
+    """rawpy's 6x6 X-Trans raw_pattern (0 = R, 2 = B, 1 and 3 = G) with 8 R, 20 G and 8 B -> int64 (6,6)."""
+    p = np.asarray(raw_pattern)
+    if p.shape != (XT_PERIOD, XT_PERIOD) or not np.all(np.isin(p, [0, 1, 2, 3])):
+        raise ValueError('raw_pattern must be a 6x6 array of colour codes 0..3 for X-Trans, got %r' % (p.tolist(),))
+    p = p.astype(np.int64)
+    n = np.bincount(CODE_COLOUR[p].reshape(-1), minlength=3)
+    if tuple(int(v) for v in n) != (8, 20, 8):
+        raise ValueError('an X-Trans raw_pattern holds 8 R, 20 G and 8 B, got %d, %d, %d' % tuple(int(v) for v in n))
+    return p
+
+
+def _cfa(cfa):
+    if cfa not in ('bayer', 'xtrans'):
+        raise ValueError("cfa must be 'bayer' or 'xtrans', got %r" % (cfa,))
+    return cfa
+
+
+def cell_counts(Hm, Wm, p=XT_PERIOD):
+    """(p,p) int64: pixels of an Hm x Wm mosaic in cell (r, c) = {(y, x): y % p == r, x % p == c}."""
+    nr = np.array([(Hm - r + p - 1) // p for r in range(p)], np.int64)
+    nc = np.array([(Wm - c + p - 1) // p for c in range(p)], np.int64)
+    return np.outer(nr, nc)
+
+
 def _shape(x):
     return tuple(int(s) for s in x.shape)
 
 
-def _check_mosaics(x, ndim, what):
+def _check_mosaics(x, ndim, what, cfa='bayer'):
     s = _shape(x)
     if len(s) != ndim:
         raise ValueError('%s: expected %d dimensions, got shape %s' % (what, ndim, s))
     if ndim == 4 and s[1] != 2:
         raise ValueError('%s: flat pairs must have shape (P, 2, Hm, Wm), got %s' % (what, s))
     Hm, Wm = s[-2:]
-    if Hm % 2 or Wm % 2 or Hm == 0 or Wm == 0:
+    if cfa == 'xtrans':
+        if Wm % 2 or Hm < XT_PERIOD or Wm < XT_PERIOD:
+            raise ValueError('%s: X-Trans mosaics need an even width and both sides >= 6, got %dx%d' % (what, Hm, Wm))
+    elif Hm % 2 or Wm % 2 or Hm == 0 or Wm == 0:
         raise ValueError('%s: mosaic sides must be even and non-zero, got %dx%d' % (what, Hm, Wm))
     if isinstance(x, np.ndarray):
         if x.dtype != np.uint16:
@@ -107,6 +142,55 @@ def bias_stats_from_sums(chan_sums, row_sums, raw_pattern, black_level, Hm, Wm):
     return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
 
 
+def xtrans_bias_stats_from_cell_sums(cell_sums, row_sums, raw_pattern, black_level, Hm, Wm):
+    """X-Trans host half of bias_frame_stats, from the exact cell sums: cell_sums int64 (F,6,6,2) = (sum u, sum u^2) per cell, row_sums
+    int64 (F,Hm,6) = sum u per row and column class.  Returns color_bias (F,3) (R, G, B: the mean of u - black_code over the colour's
+    pixels), row_offset (F,Hm) (the row means of e = u - black_code - color_bias), g_scale and R_scale (F,), as the Bayer estimators."""
+    pat, black = _xpattern(raw_pattern), _black(black_level)
+    cs, rs = np.asarray(cell_sums).reshape(-1, XT_PERIOD, XT_PERIOD, 2), np.asarray(row_sums)
+    F = cs.shape[0]
+    ncell = cell_counts(Hm, Wm)
+    bcell, col = black[pat], CODE_COLOUR[pat]                             # (6,6) black level and colour of each cell
+    n = Hm * Wm
+    S = cs[..., 0].astype(np.float64)                                     # < 2^53: exact
+    cb = np.stack([np.sum((S - ncell * bcell)[:, col == k], axis=1) / ncell[col == k].sum() for k in range(3)], axis=1)
+    se2 = np.zeros(F)                     # sum e^2 = sum over cells of (Q - S^2/n) [exact numerator] + n (S/n - black - cb)^2
+    for f in range(F):
+        for r in range(XT_PERIOD):
+            for c in range(XT_PERIOD):
+                m, s1, q = int(ncell[r, c]), int(cs[f, r, c, 0]), int(cs[f, r, c, 1])
+                se2[f] += float(m * q - s1 * s1) / m + m * (s1 / m - bcell[r, c] - cb[f, col[r, c]]) ** 2
+    ncol = cell_counts(1, Wm)[0]                                          # pixels per column class in one row
+    off = (bcell[None, :, :] + cb[:, col]) * ncol[None, None, :]          # (F,6,6): sum over a row of class r of black + cb, per column class
+    rho = (rs.sum(axis=2).astype(np.float64) - off.sum(axis=2)[:, np.arange(Hm) % XT_PERIOD]) / Wm
+    st2 = se2 - Wm * np.sum(rho * rho, axis=1)
+    g_scale = np.sqrt(se2 / n)
+    R_scale = np.sqrt(np.maximum(0.0, np.mean(rho * rho, axis=1) - (st2 / n) / Wm))
+    return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
+
+
+def xtrans_flat_stats_from_cell_sums(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm):
+    """X-Trans host half of flat_pair_stats: sums int64 (P,6,6,4) per cell -> mu, var (P,3) float64 and usable (P,3) bool, one
+    photon-transfer point per colour and pair (black = the mean black level of the colour's pixels)."""
+    pat, black = _xpattern(raw_pattern), _black(black_level)
+    sums = np.asarray(sums).reshape(-1, XT_PERIOD, XT_PERIOD, 4)
+    P = sums.shape[0]
+    cbm = np.asarray(color_bias, np.float64).reshape(3)
+    ncell = cell_counts(Hm, Wm)
+    bcell, col = black[pat], CODE_COLOUR[pat]
+    mu, var, usable = np.zeros((P, 3)), np.zeros((P, 3)), np.zeros((P, 3), bool)
+    for k in range(3):
+        m = col == k
+        nk = int(ncell[m].sum())
+        bbar = float(np.sum(ncell[m] * bcell[m])) / nk
+        for p in range(P):
+            sab, d1, d2 = (sum(int(v) for v in sums[p][m][:, j]) for j in range(3))
+            mu[p, k] = sab / (2 * nk) - bbar - cbm[k]
+            var[p, k] = float(nk * d2 - d1 * d1) / (nk * nk) / 2.0
+            usable[p, k] = int(sums[p][m][:, 3].sum()) == 0 and mu[p, k] > 0 and mu[p, k] <= 0.8 * (float(white_level) - bbar)
+    return {'mu': mu, 'var': var, 'usable': usable}
+
+
 def flat_stats_from_sums(sums, black_level, white_level, color_bias, Hm, Wm):
     """Host half of flat_pair_stats: sums int64 (P,4,4) -> mu, var (P,4) float64 and usable (P,4) bool."""
     black = _black(black_level)
@@ -145,7 +229,7 @@ def params_from_samples(frames, Ks):
     Kf = np.array([fr['K'] for fr in frames], np.float64)
     return {'Kmin': np.float64(min(Ks)), 'Kmax': np.float64(max(Ks)),
             'G_shape': np.array([fr['lambda'] for fr in frames], dtype=np.float64),
-            'color_bias': np.array([fr['color_bias'] for fr in frames], dtype=np.float32).reshape(len(frames), 4),
+            'color_bias': np.array([fr['color_bias'] for fr in frames], dtype=np.float32).reshape(len(frames), -1),
             PROFILE: {k: fit_log_linear(Kf, [fr[k] for fr in frames]) for k in SIGMA_KEYS}}
 
 
@@ -248,6 +332,50 @@ def flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias):
     return res
 
 
+def xtrans_bias_frame_stats(bias, raw_pattern, black_level, residual=False):
+    """X-Trans bias frames (F,Hm,Wm) uint16 -> dict: cell_sums int64 (F,6,6,2), row_sums int64 (F,Hm,6), color_bias (F,3), row_offset
+    (F,Hm), g_scale, R_scale (F,); with residual=True also 't' (CUDA float32 (F,Hm*Wm)) = float32(((u - black_code) - cb) - rho_y)."""
+    import torch
+    pat, black = _xpattern(raw_pattern), _black(black_level)
+    F, Hm, Wm = _check_mosaics(bias, 3, 'bias', 'xtrans')
+    u = _device_u16(bias)
+    dev = u.device
+    p = XT_PERIOD
+    cs = torch.empty((F, p, p, 2), dtype=torch.int64, device=dev)
+    rs = torch.empty((F, Hm, p), dtype=torch.int64, device=dev)
+    ws = _ws(L.lib().eld_calib_cell_stats_workspace_bytes(F, Hm, p), dev)
+    L.check(L.lib().eld_calib_cell_stats(L.dptr(u), F, Hm, Wm, p, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), L.cur_stream()),
+            'eld_calib_cell_stats')
+    out = {'cell_sums': cs.cpu().numpy(), 'row_sums': rs.cpu().numpy()}
+    out.update(xtrans_bias_stats_from_cell_sums(out['cell_sums'], out['row_sums'], pat, black, Hm, Wm))
+    if residual:
+        t = torch.empty((F, Hm * Wm), dtype=torch.float32, device=dev)
+        cbc = np.ascontiguousarray(out['color_bias'][:, CODE_COLOUR[pat].reshape(-1)])          # (F,36) bias of each cell's colour
+        cbd = torch.from_numpy(cbc).to(dev)
+        rhod = torch.from_numpy(np.ascontiguousarray(out['row_offset'])).to(dev)
+        L.check(L.lib().eld_calib_cell_residual(L.dptr(u), F, Hm, Wm, p, (ctypes.c_double * (p * p))(*black[pat].reshape(-1).tolist()),
+                                                L.dptr(cbd), L.dptr(rhod), L.dptr(t), L.cur_stream()), 'eld_calib_cell_residual')
+        out['t'] = t
+    return out
+
+
+def xtrans_flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias):
+    """X-Trans flat pairs (P,2,Hm,Wm) uint16 -> dict: sums int64 (P,6,6,4) per cell, mu, var (P,3), usable (P,3) per colour.
+    color_bias: the session's mean (R, G, B) bias."""
+    import torch
+    pat, black = _xpattern(raw_pattern), _black(black_level)
+    P, _, Hm, Wm = _check_mosaics(flats, 4, 'flats', 'xtrans')
+    ab = _device_u16(flats)
+    p = XT_PERIOD
+    out = torch.empty((P, p, p, 4), dtype=torch.int64, device=ab.device)
+    ws = _ws(L.lib().eld_calib_cell_flat_stats_workspace_bytes(P, Hm, p), ab.device)
+    L.check(L.lib().eld_calib_cell_flat_stats(L.dptr(ab), P, Hm, Wm, p, int(white_level), L.dptr(out), L.dptr(ws), ws.numel(),
+                                              L.cur_stream()), 'eld_calib_cell_flat_stats')
+    res = {'sums': out.cpu().numpy()}
+    res.update(xtrans_flat_stats_from_cell_sums(res['sums'], pat, black, white_level, color_bias, Hm, Wm))
+    return res
+
+
 def fit_log_linear(K, sigma):
     """log sigma_j = slope * log K_j + bias by ordinary least squares; sigma = sqrt(SSR / (m - 2)).  The release tables' regression
     records ({'slope', 'bias', 'sigma'}, float64) that NoiseModel._sample_params draws from."""
@@ -261,7 +389,7 @@ def fit_log_linear(K, sigma):
     return {'slope': np.float64(slope), 'bias': np.float64(bias), 'sigma': np.float64(np.sqrt(np.sum(res * res) / (x.size - 2)))}
 
 
-def _check_sessions(sessions):
+def _check_sessions(sessions, cfa='bayer'):
     if not isinstance(sessions, (list, tuple)) or len(sessions) == 0:
         raise ValueError('sessions must be a non-empty list of {"iso", "bias", "flats"}')
     shape, nbias = None, 0
@@ -269,8 +397,8 @@ def _check_sessions(sessions):
         for k in ('bias', 'flats'):
             if k not in s:
                 raise ValueError('session %d has no %r' % (i, k))
-        F, Hm, Wm = _check_mosaics(s['bias'], 3, 'session %d bias' % i)
-        P = _check_mosaics(s['flats'], 4, 'session %d flats' % i)[0]
+        F, Hm, Wm = _check_mosaics(s['bias'], 3, 'session %d bias' % i, cfa)
+        P = _check_mosaics(s['flats'], 4, 'session %d flats' % i, cfa)[0]
         if shape is None:
             shape = (Hm, Wm)
         if (Hm, Wm) != shape or _shape(s['flats'])[-2:] != shape:
@@ -284,20 +412,25 @@ def _check_sessions(sessions):
         raise ValueError('at least 2 sessions (2 distinct K) are needed, got %d' % len(sessions))
 
 
-def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None):
+def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None, cfa='bayer'):
     """Sessions of bias frames and flat pairs -> (params, diagnostics).  params has exactly the release schema
     (Kmin, Kmax, G_shape (m,), color_bias (m,4) float32, 'Profile-1': {G_scale, R_scale, g_scale: {slope, bias, sigma}}), one G_shape /
-    color_bias row per bias frame; diagnostics holds the per-frame samples, r(lambda) and the photon-transfer points."""
-    _pattern(raw_pattern)
+    color_bias row per bias frame; diagnostics holds the per-frame samples, r(lambda) and the photon-transfer points.
+    cfa='xtrans': raw_pattern is the 6x6 X-Trans pattern and black_level rawpy's 4 values by colour code; the table's color_bias is
+    (m,3) in (R, G, B) order and it carries 'cfa': 'xtrans'."""
+    xt = _cfa(cfa) == 'xtrans'
+    _xpattern(raw_pattern) if xt else _pattern(raw_pattern)
     _black(black_level)
-    _check_sessions(sessions)
+    _check_sessions(sessions, cfa)
+    bias_stats = xtrans_bias_frame_stats if xt else bias_frame_stats
+    flat_stats = xtrans_flat_pair_stats if xt else flat_pair_stats
     frames, r_all, ptc, Ks = [], [], [], []
     lam = None
     for i, s in enumerate(sessions):
-        st = bias_frame_stats(s['bias'], raw_pattern, black_level, residual=True)
+        st = bias_stats(s['bias'], raw_pattern, black_level, residual=True)
         pp = tukey_lambda_ppcc(st.pop('t'), lambdas)
         lam = pp['lambdas']
-        fl = flat_pair_stats(s['flats'], raw_pattern, black_level, white_level, st['color_bias'].mean(axis=0))
+        fl = flat_stats(s['flats'], raw_pattern, black_level, white_level, st['color_bias'].mean(axis=0))
         what = 'session %d (iso %s)' % (i, s.get('iso'))
         K = ptc_gain(fl['mu'], fl['var'], fl['usable'], what)
         Ks.append(K)
@@ -307,6 +440,8 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
                            'R_scale': float(st['R_scale'][f]), 'g_scale': float(st['g_scale'][f]), 'color_bias': st['color_bias'][f]})
             r_all.append(pp['r'][f])
     params = params_from_samples(frames, Ks)
+    if xt:
+        params['cfa'] = 'xtrans'
     diag = {'frames': frames, 'lambdas': lam, 'r': np.array(r_all), 'K': np.array(Ks), 'ptc': ptc}
     return params, diag
 
@@ -321,8 +456,9 @@ def save_camera_params(params, camera, out_dir):
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
-def load_manifest(path):
-    """Manifest JSON -> (sessions, raw_pattern, black_level, white_level).  Paths are relative to the manifest's directory."""
+def load_manifest(path, with_cfa=False):
+    """Manifest JSON -> (sessions, raw_pattern, black_level, white_level), and the manifest's "cfa" ('bayer' when absent) as a fifth
+    item with with_cfa=True.  Paths are relative to the manifest's directory."""
     with open(path) as f:
         m = json.load(f)
     base = os.path.dirname(os.path.abspath(path))
@@ -334,17 +470,18 @@ def load_manifest(path):
         bias = np.stack([load(p) for p in s['bias']])
         flats = np.stack([np.stack([load(a), load(b)]) for a, b in s['flats']])
         sessions.append({'iso': s.get('iso'), 'bias': bias, 'flats': flats})
-    return sessions, m['raw_pattern'], m['black_level'], m['white_level']
+    out = (sessions, m['raw_pattern'], m['black_level'], m['white_level'])
+    return out + (_cfa(m.get('cfa', 'bayer')),) if with_cfa else out
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m eld_amd.calibrate', description=__doc__.split('\n')[0])
-    ap.add_argument('manifest', help='JSON: raw_pattern, black_level, white_level, sessions [{iso, bias: [.npy], flats: [[a.npy, b.npy]]}]')
+    ap.add_argument('manifest', help='JSON: raw_pattern, black_level, white_level, [cfa,] sessions [{iso, bias: [.npy], flats: [[a.npy, b.npy]]}]')
     ap.add_argument('--camera', required=True, help='camera name: writes <out>/<camera>_params.npy')
     ap.add_argument('--out', default=os.path.join('camera_params', 'release'))
     a = ap.parse_args(argv)
-    sessions, pattern, black, white = load_manifest(a.manifest)
-    params, diag = calibrate_camera(sessions, pattern, black, white)
+    sessions, pattern, black, white, cfa = load_manifest(a.manifest, with_cfa=True)
+    params, diag = calibrate_camera(sessions, pattern, black, white, cfa=cfa)
     path = save_camera_params(params, a.camera, a.out)
     for fr in diag['frames']:
         print('iso %-6s K %.5g  lambda %+.4f  G_scale %.4g  R_scale %.4g  g_scale %.4g' % (fr['iso'], fr['K'], fr['lambda'], fr['G_scale'],

@@ -1,4 +1,6 @@
 // calib.hip -- noise-parameter calibration from bias frames and flat-field pairs (eld_amd/calibrate.py, DESIGN.md "Calibration").
+// The Bayer passes below take a 2x2 raw_pattern; the cell passes (eld_calib_cell_*) return per-cell sums of a period-2 or -6 mosaic
+// (X-Trans) and leave the colours to the host.
 //
 // Four passes; everything else is derived on the host in float64 from their outputs:
 //   bias statistics   uint16 mosaics -> per row: sums over the even / odd columns; per frame and channel: sum u, sum u^2 (uint64, exact)
@@ -299,6 +301,155 @@ __global__ __launch_bounds__(256) void ppcc_final_kernel(const float* __restrict
     }
 }
 
+// ---- cell statistics of a pattern of period PP = 2 * P2 (2: Bayer, 6: X-Trans) ----------------------------------------------
+// Word k of a row holds columns 2k, 2k+1: column classes 2 (k % P2) and 2 (k % P2) + 1.  A lane takes G consecutive words per step (G a
+// multiple of P2, starting at a multiple of G), so word j of the step has class j % P2 at compile time; the last nw % G words of the row
+// (fewer than G, starting at a multiple of P2) go to lanes 0.. one word each.  fn(q, k, w, take) adds word k to class q where `take`.
+// Accumulators v[(q*2 + px)*NS + s]: word class q, column parity px (column class 2q + px), statistic s.
+template <int P2, bool VEC>
+struct CellWalk {
+    static constexpr int G = VEC ? 4 * P2 : P2;
+    template <typename Fn>
+    __device__ __forceinline__ static void run(const uint32_t* __restrict__ row, int nw, Fn fn) {
+        const int ng = nw / G;
+        for (int kk = threadIdx.x; kk < ng; kk += CB_THREADS) {
+            uint32_t w[G];
+            if (VEC) {
+#pragma unroll
+                for (int i = 0; i < G / 4; ++i) {
+                    const uint4 q = reinterpret_cast<const uint4*>(row)[kk * (G / 4) + i];
+                    w[4 * i] = q.x; w[4 * i + 1] = q.y; w[4 * i + 2] = q.z; w[4 * i + 3] = q.w;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < G; ++j) w[j] = row[kk * G + j];
+            }
+#pragma unroll
+            for (int j = 0; j < G; ++j) fn(j % P2, (size_t)kk * G + j, w[j], true);
+        }
+        const int tail = nw - ng * G;
+        if ((int)threadIdx.x < tail) {
+            const int k = ng * G + threadIdx.x;
+            const uint32_t wt = row[k];
+#pragma unroll
+            for (int q = 0; q < P2; ++q) fn(q, (size_t)k, wt, (int)threadIdx.x % P2 == q);   // every class, masked: no indexed registers
+        }
+    }
+};
+
+// bias pass 1: one block per (row, frame).  rows[(f*Hm + y)*PP + c] = sum of u over the columns of class c;
+// part[((f*Hm + y)*PP + c)*2 + {0, 1}] = sum u, sum u^2 there.
+template <int P2, bool VEC>
+__global__ __launch_bounds__(CB_THREADS) void cell_row_kernel(const uint16_t* __restrict__ u, int Hm, int Wm, uint64_t* __restrict__ rows,
+                                                               uint64_t* __restrict__ part) {
+    constexpr int PP = 2 * P2, NV = PP * 2;
+    __shared__ uint64_t red[CB_WAVES * NV], tot[NV];
+    const int y = blockIdx.x, f = blockIdx.y;
+    const size_t ro = (size_t)f * Hm + y;
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(u + ro * Wm);
+    uint64_t v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = 0;
+    CellWalk<P2, VEC>::run(row, Wm / 2, [&](int q, size_t, uint32_t w, bool take) __attribute__((always_inline)) {
+        const uint32_t e = take ? w & 0xFFFFu : 0u, o = take ? w >> 16 : 0u;
+        v[(2 * q) * 2] += e; v[(2 * q + 1) * 2] += o;
+        v[(2 * q) * 2 + 1] += (uint64_t)(e * e); v[(2 * q + 1) * 2 + 1] += (uint64_t)(o * o);   // < 2^32: exact in uint32
+    });
+    block_sum_u64<NV>(v, red, tot);
+    if (threadIdx.x < PP) rows[ro * PP + threadIdx.x] = tot[threadIdx.x * 2];
+    if (threadIdx.x < NV) part[ro * NV + threadIdx.x] = tot[threadIdx.x];
+}
+
+// flat pass 1: one block per (row, pair).  part[((p*Hm + y)*PP + c)*4 + s] = sum(a+b), sum(a-b), sum((a-b)^2), #(a or b >= white)
+template <int P2, bool VEC>
+__global__ __launch_bounds__(CB_THREADS) void cell_flat_row_kernel(const uint16_t* __restrict__ ab, int Hm, int Wm, uint32_t white,
+                                                                    uint64_t* __restrict__ part) {
+    constexpr int PP = 2 * P2, NV = PP * 4;
+    __shared__ uint64_t red[CB_WAVES * NV], tot[NV];
+    const int y = blockIdx.x, pr = blockIdx.y;
+    const size_t frame = (size_t)Hm * Wm;
+    const uint16_t* a = ab + (size_t)pr * 2 * frame + (size_t)y * Wm;
+    const uint32_t* rb = reinterpret_cast<const uint32_t*>(a + frame);
+    uint64_t v[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = 0;
+    // the b row is read word for word at the a row's word index (same alignment: the frame size is a multiple of 2 words when VEC)
+    CellWalk<P2, VEC>::run(reinterpret_cast<const uint32_t*>(a), Wm / 2, [&](int q, size_t k, uint32_t wa, bool take) __attribute__((always_inline)) {
+        const uint32_t wb = rb[k];
+#pragma unroll
+        for (int px = 0; px < 2; ++px) {
+            const uint32_t x = take ? (wa >> (16 * px)) & 0xFFFFu : 0u, z = take ? (wb >> (16 * px)) & 0xFFFFu : 0u;
+            const int32_t d = (int32_t)x - (int32_t)z;
+            uint64_t* vv = v + (2 * q + px) * 4;
+            vv[0] += x + z;
+            vv[1] += (uint64_t)(int64_t)d;
+            vv[2] += (uint64_t)((uint32_t)d * (uint32_t)d);          // d^2 < 2^32: exact modulo 2^32
+            vv[3] += (take && (x >= white || z >= white)) ? 1u : 0u;
+        }
+    });
+    block_sum_u64<NV>(v, red, tot);
+    if (threadIdx.x < NV) part[((size_t)pr * Hm + y) * NV + threadIdx.x] = tot[threadIdx.x];
+}
+
+// pass 2 (bias and flat): one block per frame / pair folds the per-row partials part[F][Hm][PP][NS] into out[F][PP][PP][NS] (row class
+// y % PP).  Lanes take rows y = tid, tid + RS, ... with RS a multiple of PP, so a lane's rows share one class; the lanes of one class
+// are then summed in lane order.
+template <int PP, int NS>
+__global__ __launch_bounds__(CB_THREADS) void cell_reduce_kernel(const uint64_t* __restrict__ part, int Hm, uint64_t* __restrict__ out) {
+    constexpr int RS = CB_THREADS - CB_THREADS % PP, NV = PP * NS;
+    __shared__ uint64_t red[RS * NV];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const uint64_t* p = part + (size_t)f * Hm * NV;
+    if (tid < RS) {
+        uint64_t v[NV];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = 0;
+        for (int y = tid; y < Hm; y += RS)
+#pragma unroll
+            for (int k = 0; k < NV; ++k) v[k] += p[(size_t)y * NV + k];
+#pragma unroll
+        for (int k = 0; k < NV; ++k) red[tid * NV + k] = v[k];
+    }
+    __syncthreads();
+    for (int o = tid; o < PP * NV; o += CB_THREADS) {             // o = rc * NV + (c * NS + s)
+        const int rc = o / NV, k = o - rc * NV;
+        uint64_t s = 0;
+        for (int l = rc; l < RS; l += PP) s += red[l * NV + k];
+        out[(size_t)f * PP * NV + o] = s;
+    }
+}
+
+// residual: t = float32(((u - black[k]) - cb[f][k]) - rho[f][y]), k = (y % PP) * PP + x % PP, in float64.  One block per (row, frame).
+struct CellBlack {
+    double b[36];
+};
+
+template <int P2>
+__global__ __launch_bounds__(CB_THREADS) void cell_residual_kernel(const uint16_t* __restrict__ u, int Hm, int Wm, CellBlack blk,
+                                                                   const double* __restrict__ cb, const double* __restrict__ rho,
+                                                                   float* __restrict__ t) {
+    constexpr int PP = 2 * P2;
+    __shared__ double s_b[PP], s_cb[PP];
+    const int y = blockIdx.x, f = blockIdx.y;
+    const size_t ro = (size_t)f * Hm + y;
+    const int rc = y % PP;
+    if (threadIdx.x < PP) {
+        s_b[threadIdx.x] = blk.b[rc * PP + threadIdx.x];
+        s_cb[threadIdx.x] = cb[(size_t)f * PP * PP + rc * PP + threadIdx.x];
+    }
+    __syncthreads();
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(u + ro * Wm);
+    float2* out = reinterpret_cast<float2*>(t + ro * Wm);
+    const double r = rho[ro];
+    for (int k = threadIdx.x; k < Wm / 2; k += CB_THREADS) {
+        const uint32_t w = row[k];
+        const int c0 = 2 * (k % P2);
+        const double e = (((double)(w & 0xFFFFu) - s_b[c0]) - s_cb[c0]) - r;
+        const double o = (((double)(w >> 16) - s_b[c0 + 1]) - s_cb[c0 + 1]) - r;
+        out[k] = make_float2((float)e, (float)o);
+    }
+}
+
 int parse_pattern(const int* raw_pattern, Pattern& p) {
     if (!raw_pattern) return ELD_EINVAL;
     bool seen[4] = {false, false, false, false};
@@ -392,6 +543,84 @@ extern "C" int eld_calib_ppcc(const float* t_sorted, int F, size_t n, const floa
     ELD_LAUNCH(ppcc_partial_kernel, dim3((unsigned)nb, (L + PP_LG - 1) / PP_LG, F), dim3(PP_THREADS), 0, s, t_sorted, n, lambdas, L, part, tpart);
     ELD_LAUNCH_CHECK();
     ELD_LAUNCH(ppcc_final_kernel, dim3(L + 1, F), dim3(256), 0, s, t_sorted, n, L, nb, part, tpart, sums, tsums);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+// ---- cell statistics (any CFA of period 2 or 6) ----------------------------------------------------------------------------------
+namespace {
+bool cell_ok(int F, int Hm, int Wm, int p) { return (p == 2 || p == 6) && F >= 0 && Hm >= 0 && Wm >= 0 && Wm % 2 == 0 && F <= 65535; }
+}  // namespace
+
+extern "C" size_t eld_calib_cell_stats_workspace_bytes(int F, int Hm, int p) {
+    return F <= 0 || Hm <= 0 || (p != 2 && p != 6) ? 0 : (size_t)F * Hm * p * 2 * sizeof(uint64_t);
+}
+
+extern "C" int eld_calib_cell_stats(const uint16_t* u, int F, int Hm, int Wm, int p, uint64_t* cell_sums, uint64_t* row_sums,
+                                    void* ws, size_t ws_bytes, void* stream) {
+    if (!cell_ok(F, Hm, Wm, p)) return ELD_EINVAL;
+    if (F == 0 || Hm == 0 || Wm == 0) return 0;
+    if (!u || !cell_sums || !row_sums || !ws || !word_aligned(u)) return ELD_EINVAL;
+    if (ws_bytes < eld_calib_cell_stats_workspace_bytes(F, Hm, p)) return ELD_EWS;
+    uint64_t* part = static_cast<uint64_t*>(ws);
+    hipStream_t s = as_stream(stream);
+    const dim3 g(Hm, F), b(CB_THREADS);
+    const bool v = vec_ok(u, Wm);
+    if (p == 2) {
+        if (v) ELD_LAUNCH((cell_row_kernel<1, true>), g, b, 0, s, u, Hm, Wm, row_sums, part);
+        else ELD_LAUNCH((cell_row_kernel<1, false>), g, b, 0, s, u, Hm, Wm, row_sums, part);
+        ELD_LAUNCH_CHECK();
+        ELD_LAUNCH((cell_reduce_kernel<2, 2>), dim3(F), b, 0, s, part, Hm, cell_sums);
+    } else {
+        if (v) ELD_LAUNCH((cell_row_kernel<3, true>), g, b, 0, s, u, Hm, Wm, row_sums, part);
+        else ELD_LAUNCH((cell_row_kernel<3, false>), g, b, 0, s, u, Hm, Wm, row_sums, part);
+        ELD_LAUNCH_CHECK();
+        ELD_LAUNCH((cell_reduce_kernel<6, 2>), dim3(F), b, 0, s, part, Hm, cell_sums);
+    }
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int eld_calib_cell_residual(const uint16_t* u, int F, int Hm, int Wm, int p, const double* black, const double* cell_bias,
+                                       const double* row_offset, float* t, void* stream) {
+    if (!cell_ok(F, Hm, Wm, p) || !black) return ELD_EINVAL;
+    if (F == 0 || Hm == 0 || Wm == 0) return 0;
+    if (!u || !cell_bias || !row_offset || !t || !word_aligned(u) || ((uintptr_t)t & 7u)) return ELD_EINVAL;
+    CellBlack blk;
+    for (int k = 0; k < 36; ++k) blk.b[k] = k < p * p ? black[k] : 0.0;
+    hipStream_t s = as_stream(stream);
+    if (p == 2) ELD_LAUNCH(cell_residual_kernel<1>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, blk, cell_bias, row_offset, t);
+    else ELD_LAUNCH(cell_residual_kernel<3>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, blk, cell_bias, row_offset, t);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t eld_calib_cell_flat_stats_workspace_bytes(int P, int Hm, int p) {
+    return P <= 0 || Hm <= 0 || (p != 2 && p != 6) ? 0 : (size_t)P * Hm * p * 4 * sizeof(uint64_t);
+}
+
+extern "C" int eld_calib_cell_flat_stats(const uint16_t* ab, int P, int Hm, int Wm, int p, int white_level, int64_t* out,
+                                         void* ws, size_t ws_bytes, void* stream) {
+    if (!cell_ok(P, Hm, Wm, p) || white_level < 0) return ELD_EINVAL;
+    if (P == 0 || Hm == 0 || Wm == 0) return 0;
+    if (!ab || !out || !ws || !word_aligned(ab)) return ELD_EINVAL;
+    if (ws_bytes < eld_calib_cell_flat_stats_workspace_bytes(P, Hm, p)) return ELD_EWS;
+    uint64_t* part = static_cast<uint64_t*>(ws);
+    uint64_t* o = reinterpret_cast<uint64_t*>(out);
+    hipStream_t s = as_stream(stream);
+    const dim3 g(Hm, P), b(CB_THREADS);
+    const bool v = vec_ok(ab, Wm);
+    if (p == 2) {
+        if (v) ELD_LAUNCH((cell_flat_row_kernel<1, true>), g, b, 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
+        else ELD_LAUNCH((cell_flat_row_kernel<1, false>), g, b, 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
+        ELD_LAUNCH_CHECK();
+        ELD_LAUNCH((cell_reduce_kernel<2, 4>), dim3(P), b, 0, s, part, Hm, o);
+    } else {
+        if (v) ELD_LAUNCH((cell_flat_row_kernel<3, true>), g, b, 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
+        else ELD_LAUNCH((cell_flat_row_kernel<3, false>), g, b, 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
+        ELD_LAUNCH_CHECK();
+        ELD_LAUNCH((cell_reduce_kernel<6, 4>), dim3(P), b, 0, s, part, Hm, o);
+    }
     ELD_LAUNCH_CHECK();
     return 0;
 }

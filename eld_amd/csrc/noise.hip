@@ -1,4 +1,4 @@
-// noise.hip -- fused per-pixel physics-based noise sampler for packed-raw Bayer tensors (gfx950).
+// noise.hip -- fused per-pixel physics-based noise sampler for packed-raw Bayer and X-Trans tensors (gfx950).
 //
 // Replaces NoiseModelBase.__call__ (reference noise.py:149-170), batched over images, plus the
 // withheld ELD terms (Tukey-lambda read, row, quantisation, colour bias).
@@ -189,6 +189,13 @@ __device__ __forceinline__ float div_rn(float a, float b, float rb) {
 
 __device__ __forceinline__ uint32_t pick(const uint4& w, int j) { return j == 0 ? w.x : j == 1 ? w.y : j == 2 ? w.z : w.w; }
 
+// X-Trans (ELD_CFA_XTRANS, C == 9, RawPacker.pack_raw_xtrans's planes): packed row i holds sensor rows 3i..3i+2.  Element (c, i, j)
+// reads sensor row 3i + d(c, (i ^ j) & 1), d = 2 bits at 4c + 2((i ^ j) & 1) of XT_DROW (planes 0-2: 0; 3: 1,2; 4: 2,1; 5-6: 1;
+// 7-8: 2 -- eld_pack_xtrans's XT_RC rows minus 3 (i & 1)); plane c has CFA colour (XT_COLOUR >> 2c) & 3 (R 0, G 1, B 2).
+constexpr uint64_t XT_DROW = 0xaa5569000ull;
+constexpr uint32_t XT_COLOUR = 0x15624u;
+__device__ __forceinline__ uint32_t xt_drow(uint32_t c, uint32_t parity) { return (uint32_t)(XT_DROW >> (4u * c + 2u * parity)) & 3u; }
+
 __device__ __forceinline__ float row_normal(uint32_t srow, const SamplerRng& rng) {
     const uint4 w = rng.words(srow, STREAM_ROW);
     return box_muller(w.x, w.y).x;
@@ -222,6 +229,7 @@ __device__ __forceinline__ void load_y4(const NoiseArgs& a, size_t img_off /* n 
 template <bool VEC, uint32_t TFLAGS, bool DEBUG>
 __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a) {
     constexpr bool MAYBE_P = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_SHOT_POISSON);
+    constexpr bool MAYBE_X = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_CFA_XTRANS);
     __shared__ float s_row[MAX_LDS_ROWS];
     __shared__ uint32_t s_cnt[MAYBE_P ? ELEMS_PER_BLOCK : 1];     // (count << 9) | low 9 bits of the pixel's POIS_V word (free: u01 takes w >> 9)
     __shared__ uint4 s_qp[MAYBE_P ? QP_CAP : 1];
@@ -242,6 +250,8 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
     const size_t in_off = (size_t)n * a.in_stride, out_off = (size_t)n * a.out_stride;
     const bool inject = DEBUG && a.inject != nullptr;
     const bool do_pois = MAYBE_P && (flags & ELD_SHOT_POISSON) && !inject;
+    const bool xt = MAYBE_X && (flags & ELD_CFA_XTRANS);            // X-Trans row map / colour bias (Bayer kernels: false at compile time)
+    const uint32_t rows_per = xt ? 3u : 1u;                          // staged row normals per packed row
     const float S = P.saturation, ratio = P.ratio, K = P.K;
 
     const uint32_t wave = tid >> 6;
@@ -259,12 +269,13 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
         r_first = VEC ? fdiv_u32(g_begin, a.divW) : fdiv_u32(e_first, a.divW);
         const uint32_t r_last = VEC ? fdiv_u32(g_end - 1u, a.divW) : fdiv_u32(e_last, a.divW);
         const uint32_t nrows = r_last - r_first + 1u;
-        lds_rows = nrows <= MAX_LDS_ROWS;
+        lds_rows = nrows * rows_per <= MAX_LDS_ROWS;
         if (lds_rows) {
-            for (uint32_t t = tid; t < nrows; t += NOISE_THREADS) {
-                const uint32_t r = r_first + t;
+            for (uint32_t t = tid; t < nrows * rows_per; t += NOISE_THREADS) {
+                const uint32_t q = xt ? t / 3u : t;                  // X-Trans: entry 3q + k = sensor row 3h + k of packed row r_first + q
+                const uint32_t r = r_first + q;
                 const uint32_t c = fdiv_u32(r, a.divH), h = r - c * a.H;
-                s_row[t] = row_normal(2u * h + (c >> 1), rng);
+                s_row[t] = row_normal(xt ? 3u * h + (t - 3u * q) : 2u * h + (c >> 1), rng);
             }
         }
     }
@@ -478,6 +489,12 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
             if (flags & ELD_ROW) {
                 if (inject) {
                     v_nrow = a.inject[ELD_PLANE_NROW * a.total + ge];
+                } else if (xt) {
+                    // column parity: VEC groups start at a multiple of 4 within the row, so it is j's; scalar: from the element
+                    const uint32_t c = fdiv_u32(r, a.divH), h = r - c * a.H;
+                    const uint32_t jpar = VEC ? (uint32_t)j & 1u : (e - r * a.W) & 1u;
+                    const uint32_t d = xt_drow(c, (h ^ jpar) & 1u);
+                    v_nrow = lds_rows ? s_row[3u * (r - r_first) + d] : row_normal(3u * h + d, rng);
                 } else if (lds_rows) {
                     v_nrow = s_row[r - r_first];
                 } else {
@@ -494,7 +511,7 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
             }
             if (flags & ELD_CBIAS) {
                 const uint32_t c = fdiv_u32(r, a.divH);
-                zz = zz + P.color_bias[c & 3u];
+                zz = zz + P.color_bias[xt ? (XT_COLOUR >> (2u * c)) & 3u : c & 3u];
             }
             zz = zz * ratio;                      // noise.py:168
             zz = div_rn(zz, S, r_S);              // noise.py:169  (zz / S, correctly rounded)
@@ -584,7 +601,9 @@ extern "C" int eld_noise_forward_strided(const void* in, int in_dtype, size_t in
     if (N < 0 || C < 0 || H < 0 || W < 0) return ELD_EINVAL;
     if (in_dtype != ELD_IN_F32 && in_dtype != ELD_IN_U16) return ELD_EINVAL;
     if ((flags & ELD_SHOT_POISSON) && (flags & ELD_SHOT_GAUSS)) return ELD_EINVAL;   // 'P' wins in the parser (noise.py:158-160)
-    if ((flags & (ELD_ROW | ELD_CBIAS)) && C != 4) return ELD_EINVAL;
+    if ((flags & ELD_CFA_XTRANS) && C != 9) return ELD_EINVAL;
+    if ((flags & (ELD_ROW | ELD_CBIAS)) && !(C == 4 || ((flags & ELD_CFA_XTRANS) && C == 9))) return ELD_EINVAL;
+    if (!(flags & (ELD_ROW | ELD_CBIAS))) flags &= ~ELD_CFA_XTRANS;   // the per-pixel terms do not depend on the layout: same kernels as without
     const size_t chw = (size_t)C * H * W;
     if (N == 0 || chw == 0) return 0;               // empty input: nothing to do (reference returns an empty array)
     if (!in || !out || !params) return ELD_EINVAL;
@@ -619,6 +638,8 @@ extern "C" int eld_noise_forward_strided(const void* in, int in_dtype, size_t in
     switch (flags) {
         case FULL: return launch_noise<true, FULL, false>(a, N, st);
         case FULL | ELD_CLIP: return launch_noise<true, FULL | ELD_CLIP, false>(a, N, st);
+        case FULL | ELD_CFA_XTRANS: return launch_noise<true, FULL | ELD_CFA_XTRANS, false>(a, N, st);                          // 'PGRU' on X-Trans
+        case FULL | ELD_CFA_XTRANS | ELD_CLIP: return launch_noise<true, FULL | ELD_CFA_XTRANS | ELD_CLIP, false>(a, N, st);
         case PG: return launch_noise<true, PG, false>(a, N, st);
         case PG | ELD_CLIP: return launch_noise<true, PG | ELD_CLIP, false>(a, N, st);
         case ELD_READ_GAUSS: return launch_noise<true, ELD_READ_GAUSS, false>(a, N, st);

@@ -24,7 +24,7 @@ from . import _lib as L
 from . import dist as D
 from . import unet as arch_unet
 from .data import records_from_batch
-from .noise import (NoiseModel, augment, decode_augment_u16, is_u16_codes, make_records, model_flags, sample_noise_records, set_sample_ids)
+from .noise import (NoiseModel, augment, decode_augment_u16, is_u16_codes, make_records, noise_model_flags, sample_noise_records, set_sample_ids)
 
 ARCH = {'unet': arch_unet.unet}          # the `arch.__dict__[opt.netG]` registry (ELD_model.py:391)
 
@@ -274,7 +274,7 @@ class ELDModel:
             raise ValueError('need %d sample ids (N x burst), got %d' % (N * burst, len(sample_ids)))
         in_u16 = is_u16_codes(clean)
         clean = clean.contiguous() if in_u16 else clean.contiguous().float()
-        flags = model_flags(nm.model) | L.CLIP
+        flags = noise_model_flags(nm) | L.CLIP
         out = None
         for k in range(burst):                   # frame k of image i carries id sample_ids[i*burst + k]
             out = sample_noise_records(clean, set_sample_ids(recs, sample_ids[k::burst]), flags, self.seed, in_u16=in_u16, out=out,

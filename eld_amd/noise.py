@@ -27,9 +27,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ALL_CAMERAS = ['CanonEOS5D4', 'CanonEOS70D', 'CanonEOS700D', 'NikonD850', 'SonyA7S2']   # noise.py:179
 
 
-def model_flags(model):
-    """Letter-containment parse, as noise.py:158-166 ('P' shadows 'p')."""
-    f = 0
+def model_flags(model, cfa='bayer'):
+    """Letter-containment parse, as noise.py:158-166 ('P' shadows 'p'); cfa='xtrans' adds L.CFA_XTRANS (9-plane X-Trans input)."""
+    f = L.CFA_XTRANS if cfa == 'xtrans' else 0
     if 'P' in model:
         f |= L.SHOT_POISSON
     elif 'p' in model:
@@ -45,6 +45,16 @@ def model_flags(model):
     if 'B' in model:
         f |= L.CBIAS
     return f
+
+
+def noise_model_flags(nm):
+    """Launch flags of a noise-model instance: its model letters and the CFA of its raw_packer (noise.py:199)."""
+    return model_flags(nm.model, getattr(getattr(nm, 'raw_packer', None), 'cfa', 'bayer'))
+
+
+def table_cfa(camera_params):
+    """CFA a camera table describes: 'xtrans' when it says so, else 'bayer' (every release table)."""
+    return camera_params.get('cfa', 'bayer')
 
 
 class NoiseParams(tuple):
@@ -328,6 +338,9 @@ class NoiseModelBase:  # same name / role as noise.py:148
         self._counter += n
         return ids
 
+    def flags(self):
+        return noise_model_flags(self)
+
     def __call__(self, y, params=None):
         import torch
         if not hasattr(self, '_counter'):
@@ -355,7 +368,7 @@ class NoiseModelBase:  # same name / role as noise.py:148
             plist = params
         else:
             plist = [params] * N
-        out = sample_noise(t, plist, model_flags(self.model), self.seed, self._next_ids(N))
+        out = sample_noise(t, plist, self.flags(), self.seed, self._next_ids(N))
         if single:
             out = out[0]
         return out.cpu().numpy() if as_np else out
@@ -383,6 +396,11 @@ class NoiseModel(NoiseModelBase):
             self.camera_params[camera] = load_camera_params(camera, self.param_dir)
         self.model = model
         self.raw_packer = RawPacker(cfa)                    # noise.py:199
+        if 'B' in model:          # the colour bias is laid out by CFA (Bayer: 4 packed channels, X-Trans: R, G, B): no mapping between them
+            for camera in self.cameras:
+                if table_cfa(self.camera_params[camera]) != cfa:
+                    raise ValueError("NoiseModel(model=%r, cfa=%r): camera %s has a %s table; its colour bias does not apply to %s input"
+                                     % (model, cfa, camera, table_cfa(self.camera_params[camera]), cfa))
         self._counter = 0
         # noise.py:209-210 reads the calibrated Kmin/Kmax and then samples log K from the hard-coded [0.1, 30] (:215); the
         # calibrated range is the paper's.  Default = the reference's behaviour; ELD_AMD_CALIBRATED_K=1 or this attribute opts in.
@@ -416,6 +434,7 @@ class NoiseModel(NoiseModelBase):
             return float(np.exp(np.random.standard_normal() * r['sigma'] + r['slope'] * log_K + r['bias']))
         tl_scale, row_scale = reg('G_scale'), reg('R_scale')
         i = np.random.randint(len(camera_params['G_shape']))
+        cb = [float(b) for b in np.asarray(camera_params['color_bias'])[i]]
         return NoiseParams(K, g_scale, saturation_level, ratio, tl_lambda=float(camera_params['G_shape'][i]),
                            tl_scale=tl_scale, row_scale=row_scale, q_step=1.0,
-                           color_bias=tuple(float(b) for b in np.asarray(camera_params['color_bias'])[i]))
+                           color_bias=tuple(cb + [0.0] * (4 - len(cb))))      # X-Trans tables: (R, G, B) -> (R, G, B, 0)

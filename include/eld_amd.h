@@ -29,8 +29,10 @@ extern "C" {
 
 /* 2 (round 6): eld_unet_infer_ex and eld_debug_ws_state_entries exist; the U-Net workspace grew (slope-code regions) -- size it with
  * eld_unet_workspace_bytes of the SAME library; eld_unet_backward_ex accepts an explicit dout after eld_unet_forward_loss_ex and refuses a backward
- * after eld_unet_infer_ex.  A binding must compare eld_abi_version() with the ELD_ABI_VERSION it was written against. */
-#define ELD_ABI_VERSION 2
+ * after eld_unet_infer_ex.  A binding must compare eld_abi_version() with the ELD_ABI_VERSION it was written against.
+ * 3: ELD_CFA_XTRANS (row noise and colour bias on 9-plane X-Trans inputs) and the cell-statistics calibration entry points
+ * (eld_calib_cell_*) exist; every version-2 call behaves as before. */
+#define ELD_ABI_VERSION 3
 
 /* negative = argument errors (hipError_t values are >= 0) */
 #define ELD_EINVAL   (-1)   /* bad shape / flag combination / null pointer                   */
@@ -47,6 +49,8 @@ extern "C" {
 #define ELD_CBIAS        64u   /* 'B'  per-channel colour bias     camera_params/release/ npy tables] */
 #define ELD_CLIP        128u   /* fuse the caller's clip to [0,1]       dataset/sid_dataset.py:277 */
 #define ELD_AUG_NOTRANSPOSE 256u /* eld_augment only: no image of the batch has its transpose bit set (then H != W is fine) */
+#define ELD_CFA_XTRANS  512u   /* the C == 9 input is in RawPacker.pack_raw_xtrans's plane layout (noise.py:22-64): ELD_ROW and
+                                  ELD_CBIAS follow the X-Trans mosaic; without ELD_ROW / ELD_CBIAS it changes nothing */
 
 /* input element types */
 #define ELD_IN_F32  0   /* float32 in [0,1]                                                      */
@@ -63,7 +67,7 @@ typedef struct EldNoiseParams {
     float q_step;       /* quantisation step (ADU), 1                                         */
     float saturation;   /* 16383-800                                   noise.py:205           */
     float ratio;        /* exposure ratio                              noise.py:223           */
-    float color_bias[4];/* per packed channel (ADU)  ('color_bias')                           */
+    float color_bias[4];/* per packed channel (ADU)  ('color_bias'); ELD_CFA_XTRANS: (R, G, B) per CFA colour, [3] unused */
     uint32_t sample_id_lo, sample_id_hi;  /* GLOBAL sample index -> Philox counter words 1,2  */
     uint32_t reserved[2];
 } EldNoiseParams;
@@ -90,7 +94,11 @@ const char* eld_error_string(int code);
  *   inject optional float[ELD_NPLANES][numel]: take the variates from here instead of Philox
  *          (deterministic-arithmetic parity against the reference's own draws)
  *   dump   optional float[ELD_NPLANES][numel]: also write the variates that were used
- * ELD_ROW requires C == 4 (Bayer packing: channels 0,1 <- sensor row 2h, 2,3 <- 2h+1; noise.py:16-19). */
+ * ELD_ROW and ELD_CBIAS require C == 4 (Bayer packing: channels 0,1 <- sensor row 2h, 2,3 <- 2h+1; noise.py:16-19), or C == 9 with
+ * ELD_CFA_XTRANS.  X-Trans: packed row i holds sensor rows 3i..3i+2; element (c, i, j) reads sensor row 3i + d, d = 0 for planes
+ * 0-2, 1 for 5-6, 2 for 7-8, and for planes 3 / 4 d = 1 / 2 where i + j is even, 2 / 1 where it is odd.  Its row normal is
+ * the one of that sensor row (same Philox counter layout as Bayer's, indexed by the sensor row).  The colour bias of plane c
+ * is color_bias[colour of c]: planes 0, 3 R; 2, 4 B; 1, 5-8 G.  ELD_CFA_XTRANS with C != 9 is ELD_EINVAL. */
 int eld_noise_forward(const void* in, int in_dtype, float* out, const EldNoiseParams* params,
                       int N, int C, int H, int W, uint32_t flags, uint64_t seed,
                       const float* inject, float* dump, void* stream);
@@ -158,6 +166,22 @@ int eld_calib_flat_stats(const uint16_t* ab, int P, int Hm, int Wm, const int* r
  * sum tM / sum M^2.  Workspace: eld_calib_ppcc_workspace_bytes(F, n, L). */
 size_t eld_calib_ppcc_workspace_bytes(int F, size_t n, int L);
 int eld_calib_ppcc(const float* t_sorted, int F, size_t n, const float* lambdas, int L, double* sums, double* tsums, void* ws, size_t ws_bytes, void* stream);
+/* Cell statistics of a mosaic pattern of period p (2 or 6; anything else is ELD_EINVAL), for any CFA (X-Trans: p = 6).  They know
+ * nothing about colours: cell (r, c) is the set of pixels (y, x) with y % p == r, x % p == c, and the host folds cells into colours.
+ * Same rules as the Bayer passes above: exact integer sums, fixed reduction order, 4-byte aligned `u` / `ab`, Wm even; Hm and Wm
+ * need not be multiples of p.
+ *
+ * cell_sums[F][p][p][2] = (sum u, sum u^2) per frame and cell; row_sums[F][Hm][p] = sum u over the columns x % p == c of each row.
+ * Workspace: eld_calib_cell_stats_workspace_bytes(F, Hm, p). */
+size_t eld_calib_cell_stats_workspace_bytes(int F, int Hm, int p);
+int eld_calib_cell_stats(const uint16_t* u, int F, int Hm, int Wm, int p, uint64_t* cell_sums, uint64_t* row_sums, void* ws, size_t ws_bytes, void* stream);
+/* Cell residual: t[f][y][x] = float32(((u - black[k]) - cell_bias[f][k]) - row_offset[f][y]), k = (y % p) * p + x % p, float64
+ * arithmetic rounded once (black: HOST array of p*p doubles; cell_bias: device double[F][p*p]; row_offset: device double[F][Hm]). */
+int eld_calib_cell_residual(const uint16_t* u, int F, int Hm, int Wm, int p, const double* black, const double* cell_bias, const double* row_offset, float* t, void* stream);
+/* Flat pairs ab [P][2][Hm][Wm]: out[P][p][p][4] = per cell (sum(a+b), sum(a-b), sum((a-b)^2), #pixels with a or b >= white_level).
+ * Workspace: eld_calib_cell_flat_stats_workspace_bytes(P, Hm, p). */
+size_t eld_calib_cell_flat_stats_workspace_bytes(int P, int Hm, int p);
+int eld_calib_cell_flat_stats(const uint16_t* ab, int P, int Hm, int Wm, int p, int white_level, int64_t* out, void* ws, size_t ws_bytes, void* stream);
 
 
 /* Training-pair augmentation of ELDTrainDataset.__getitem__ (dataset/sid_dataset.py:344-352), batched on device:

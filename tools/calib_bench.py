@@ -113,12 +113,48 @@ def bench_flats(ab, reps):
     return {'pairs': P, 'flat_stats_s': t, 'flat_stats_GBps': P * 2 * Hm * Wm * 2 / t / 1e9}
 
 
+def bench_cells(F, Hm, Wm, reps):
+    """--cfa xtrans: the X-Trans cell statistics (p = 6) against the Bayer bias statistics on the same mosaics, and the flat pass."""
+    lib = L.lib()
+    u = frames(F, Hm, Wm, 7)
+    pat = (ctypes.c_int * 4)(0, 1, 3, 2)
+    cs = torch.empty((F, 4, 2), dtype=torch.int64, device='cuda')
+    rs = torch.empty((F, Hm, 2), dtype=torch.int64, device='cuda')
+    ws = torch.empty(lib.eld_calib_bias_stats_workspace_bytes(F, Hm), dtype=torch.uint8, device='cuda')
+    xcs = torch.empty((F, 6, 6, 2), dtype=torch.int64, device='cuda')
+    xrs = torch.empty((F, Hm, 6), dtype=torch.int64, device='cuda')
+    xws = torch.empty(lib.eld_calib_cell_stats_workspace_bytes(F, Hm, 6), dtype=torch.uint8, device='cuda')
+    bayer, xtrans = [], []
+    for _ in range(3):                                   # interleaved A/B
+        bayer.append(timed(lambda: L.check(lib.eld_calib_bias_stats(L.dptr(u), F, Hm, Wm, pat, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(),
+                                                                     L.cur_stream())), reps))
+        xtrans.append(timed(lambda: L.check(lib.eld_calib_cell_stats(L.dptr(u), F, Hm, Wm, 6, L.dptr(xcs), L.dptr(xrs), L.dptr(xws),
+                                                                      xws.numel(), L.cur_stream())), reps))
+    tb, tx = float(np.median(bayer)), float(np.median(xtrans))
+    ab = frames(4, Hm, Wm, 8).view(2, 2, Hm, Wm)
+    out = torch.empty((2, 6, 6, 4), dtype=torch.int64, device='cuda')
+    fws = torch.empty(lib.eld_calib_cell_flat_stats_workspace_bytes(2, Hm, 6), dtype=torch.uint8, device='cuda')
+    tf = timed(lambda: L.check(lib.eld_calib_cell_flat_stats(L.dptr(ab), 2, Hm, Wm, 6, 16383, L.dptr(out), L.dptr(fws), fws.numel(),
+                                                             L.cur_stream())), reps)
+    byt = 2.0 * F * Hm * Wm
+    res = {'mosaic': [F, Hm, Wm], 'bayer_bias_stats_ms': tb * 1e3, 'xtrans_cell_stats_ms': tx * 1e3, 'ratio': tx / tb,
+           'bayer_GBps': byt / tb / 1e9, 'cell_stats_GBps': byt / tx / 1e9, 'cell_flat_stats_ms_2_pairs': tf * 1e3,
+           'cell_flat_GBps': 2 * 2.0 * 2 * Hm * Wm / tf / 1e9}
+    print(json.dumps(res))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument('--cfa', choices=['bayer', 'xtrans'], default='bayer',
+                    help='xtrans: time the cell statistics (p = 6) against the Bayer bias statistics on 4 frames of 4158 x 6240')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--isos', type=int, default=9)
     ap.add_argument('--out', help='also write the JSON result here')
     a = ap.parse_args()
+    if a.cfa == 'xtrans':
+        bench_cells(4, 4158, 6240, a.reps)
+        return
     L.load_library()
     lam = CAL.DEFAULT_LAMBDAS
     iso_rows = []

@@ -7,7 +7,33 @@ if os.environ.get('ELD_DEV_LIB'):          # tools/build_dev.sh: library with th
     L.LIB_PATH = os.environ['ELD_DEV_LIB']
 from eld_amd.noise import NoiseParams, sample_noise, model_flags
 
+def cfa_ab(N, reps=20, rounds=5):
+    """--cfa: 'PGRU' (+ clip) per element, Bayer 8 x 4 x 1424 x 2128 against X-Trans 8 x 9 x 1386 x 2080, interleaved A/B."""
+    g = torch.Generator(device='cuda').manual_seed(0)
+    p = NoiseParams(2.288, 6.451, 15583, 208.98, tl_lambda=-0.14285714, tl_scale=3.3, row_scale=0.9)
+    cases = []
+    for cfa, C, H, W in (('bayer', 4, 1424, 2128), ('xtrans', 9, 1386, 2080)):
+        y = (torch.rand(N, C, H, W, device='cuda', generator=g) ** 2.2 * 65535).floor() / 65535
+        cases.append((cfa, y, torch.empty_like(y), model_flags('PGRU', cfa) | L.CLIP))
+    times = {c[0]: [] for c in cases}
+    for _ in range(rounds):
+        for cfa, y, out, fl in cases:
+            for _ in range(3):
+                sample_noise(y, [p] * N, fl, 2018, list(range(N)), out=out)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                sample_noise(y, [p] * N, fl, 2018, list(range(N)), out=out)
+            e1.record(); torch.cuda.synchronize()
+            times[cfa].append(e0.elapsed_time(e1) / reps / y.numel() * 1e6)      # ns per element
+    for cfa, y, _, _ in cases:
+        print('PGRU %-6s %s  %.4f ns/element (median of %d)' % (cfa, tuple(y.shape), float(np.median(times[cfa])), rounds))
+    print('xtrans / bayer per element: %.3f' % (np.median(times['xtrans']) / np.median(times['bayer'])))
+
+
 def main():
+    if '--cfa' in sys.argv:
+        return cfa_ab(8)
     N = int(sys.argv[1]) if len(sys.argv) > 1 else 8
     H, W = 1424, 2128
     g = torch.Generator(device='cuda').manual_seed(0)
