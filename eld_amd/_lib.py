@@ -13,6 +13,7 @@ SHOT_POISSON, SHOT_GAUSS, READ_GAUSS, READ_TL, ROW, QUANT, CBIAS, CLIP = 1, 2, 4
 AUG_NOTRANSPOSE = 256
 CFA_XTRANS = 512
 IN_F32, IN_U16 = 0, 1
+ROUND_TRUNC, ROUND_NEAREST, ROUND_TRUNC_F32 = 0, 1, 2      # write-back rounding (eld_unpack_raw_*_u16)
 NPLANES = 6
 PLANE = {'counts': 0, 'n_shot': 1, 'n_read': 2, 't_tl': 3, 'n_row': 4, 'u_q': 5}
 
@@ -41,6 +42,10 @@ SIGNATURES = {
     'eld_unpack_xtrans': (_i, [_vp, _vp, _i, _i, _i, _vp]),
     'eld_pack_raw_bayer_u16': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp]),
     'eld_pack_raw_xtrans_u16': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp]),
+    'eld_pack_raw_bayer_u16_gain': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp, _vp]),
+    'eld_pack_raw_xtrans_u16_gain': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
+    'eld_unpack_raw_bayer_u16': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _i, _vp]),
+    'eld_unpack_raw_xtrans_u16': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
     'eld_augment': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _u32, _vp]),
     'eld_calib_bias_stats_workspace_bytes': (_sz, [_i, _i]),
     'eld_calib_bias_stats': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), _vp, _vp, _vp, _sz, _vp]),
@@ -70,6 +75,7 @@ SIGNATURES = {
     'eld_debug_kernel_mask': (_i, [_i]),
     'eld_debug_ws_state_entries': (_i, []),
     'eld_isp_process': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    'eld_isp_process_xtrans': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     'eld_quality_assess_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'eld_quality_assess': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
     'eld_quality_assess_images': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
@@ -101,7 +107,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 3         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
+ABI_VERSION = 4         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
 PHILOX_ROUNDS = 7      # the sampler's generator: Philox4x32-7 (csrc/philox.h); checked against the library at load
 
 

@@ -7,6 +7,7 @@
 //     to [0,1], one scale per image.
 // Sums are accumulated in double and reduced in a fixed order (run-to-run bit-stable, no atomics).
 #include "common.h"
+#include "xtrans.h"
 
 int debug_kernel_mask(int set);      // conv_bfs.hip (eld_debug_kernel_mask): set < 0 only queries
 
@@ -334,6 +335,40 @@ __device__ __forceinline__ float isp_quant(float v) {
     return (float)q / 255.0f;
 }
 
+// the tail both ISP kernels share: linear RGB of one pixel -> CCM -> clamp -> gamma / CRF -> 8-bit code / 255 into dst[c * hw + i]
+__device__ __forceinline__ void isp_rgb_out(float r, float g, float b, const float (&m)[9], float* __restrict__ dst, size_t i, size_t hw,
+                                            float inv_gamma, double ig, const float* __restrict__ crf_E, const float* __restrict__ crf_f,
+                                            int crf_n, int gtab, const unsigned* s_t) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float v = r * m[3 * c];
+        v = v + g * m[3 * c + 1];
+        v = v + b * m[3 * c + 2];
+        v = fminf(fmaxf(v, 0.f), 1.f);
+        float o;
+        if (crf_n > 0) {
+            int lo = 0, hi = crf_n;                              // searchsorted(E, v, 'left') - 1, clamped to [0, n-2]
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (crf_E[mid] < v) lo = mid + 1; else hi = mid; }
+            int ind = lo - 1;
+            ind = ind < 0 ? 0 : (ind > crf_n - 2 ? crf_n - 2 : ind);
+            const float slope = (crf_f[ind + 1] - crf_f[ind]) / (crf_E[ind + 1] - crf_E[ind]);
+            o = crf_f[ind] + slope * (v - crf_E[ind]);
+        } else if (gtab) {                                      // exact: code = #{c : bits(max(v,1e-8)) >= T[c]}, found from a hardware-pow guess
+            const float vm = fmaxf(v, 1e-8f);
+            const unsigned vb = __float_as_uint(vm);
+            int q = (int)(__builtin_amdgcn_exp2f(__builtin_amdgcn_logf(vm) * inv_gamma) * 255.0f);
+            q = q < 0 ? 0 : (q > 255 ? 255 : q);
+            while (q < 255 && vb >= s_t[q + 1]) ++q;
+            while (q > 0 && vb < s_t[q]) --q;
+            dst[c * hw + i] = (float)q / 255.0f;
+            continue;
+        } else {
+            o = (float)pow((double)fmaxf(v, 1e-8f), ig);
+        }
+        dst[c * hw + i] = isp_quant(o);
+    }
+}
+
 __global__ __launch_bounds__(256) void isp_kernel(const float* __restrict__ bayer, const float* __restrict__ wbs, const float* __restrict__ ccms,
                                                   float* __restrict__ out, size_t hw, float inv_gamma, const float* __restrict__ crf_E,
                                                   const float* __restrict__ crf_f, int crf_n, int gtab) {
@@ -354,34 +389,41 @@ __global__ __launch_bounds__(256) void isp_kernel(const float* __restrict__ baye
         const float c0 = fminf(fmaxf(src[i] * w0, 0.f), 1.f), c1 = fminf(fmaxf(src[hw + i] * w1, 0.f), 1.f);
         const float c2 = fminf(fmaxf(src[2 * hw + i] * w2, 0.f), 1.f), c3 = fminf(fmaxf(src[3 * hw + i] * w3, 0.f), 1.f);
         const float r = c0, g = (c1 + c3) / 2.0f, b = c2;
+        isp_rgb_out(r, g, b, m, dst, i, hw, inv_gamma, ig, crf_E, crf_f, crf_n, gtab, s_t);
+    }
+}
+
+// X-Trans (eld_isp_process_xtrans): one packed pixel = one 3x3 mosaic block, nine planes.  Gains by plane colour (xtrans.h xt_colour)
+// -> clamp -> per colour its planes summed in ascending plane order in float32 (R = p0 + p3, G = (((p1 + p5) + p6) + p7) + p8,
+// B = p2 + p4) and divided by the plane count (2 / 5 / 2) -> the shared tail.  36 B read + 12 B written per packed pixel.
+// planes of colour col among planes 0 .. k-1 (k = 9: the plane count of the colour)
+__host__ __device__ constexpr int xt_planes_before(int k, uint32_t col) { return k == 0 ? 0 : xt_planes_before(k - 1, col) + (xt_colour(k - 1) == col ? 1 : 0); }
+
+__global__ __launch_bounds__(256) void isp_xtrans_kernel(const float* __restrict__ packed, const float* __restrict__ wbs, const float* __restrict__ ccms,
+                                                         float* __restrict__ out, size_t hw, float inv_gamma, const float* __restrict__ crf_E,
+                                                         const float* __restrict__ crf_f, int crf_n, int gtab) {
+    __shared__ unsigned s_t[256];
+    if (gtab) s_t[threadIdx.x] = ELD_GAMMA22_T[threadIdx.x];
+    __syncthreads();
+    const int n = blockIdx.y;
+    const float wc[3] = {wbs[3 * n], wbs[3 * n + 1], wbs[3 * n + 2]};
+    const float* cm = ccms + 9 * n;
+    float m[9];
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            float v = r * m[3 * c];
-            v = v + g * m[3 * c + 1];
-            v = v + b * m[3 * c + 2];
-            v = fminf(fmaxf(v, 0.f), 1.f);
-            float o;
-            if (crf_n > 0) {
-                int lo = 0, hi = crf_n;                              // searchsorted(E, v, 'left') - 1, clamped to [0, n-2]
-                while (lo < hi) { const int mid = (lo + hi) >> 1; if (crf_E[mid] < v) lo = mid + 1; else hi = mid; }
-                int ind = lo - 1;
-                ind = ind < 0 ? 0 : (ind > crf_n - 2 ? crf_n - 2 : ind);
-                const float slope = (crf_f[ind + 1] - crf_f[ind]) / (crf_E[ind + 1] - crf_E[ind]);
-                o = crf_f[ind] + slope * (v - crf_E[ind]);
-            } else if (gtab) {                                      // exact: code = #{c : bits(max(v,1e-8)) >= T[c]}, found from a hardware-pow guess
-                const float vm = fmaxf(v, 1e-8f);
-                const unsigned vb = __float_as_uint(vm);
-                int q = (int)(__builtin_amdgcn_exp2f(__builtin_amdgcn_logf(vm) * inv_gamma) * 255.0f);
-                q = q < 0 ? 0 : (q > 255 ? 255 : q);
-                while (q < 255 && vb >= s_t[q + 1]) ++q;
-                while (q > 0 && vb < s_t[q]) --q;
-                dst[c * hw + i] = (float)q / 255.0f;
-                continue;
-            } else {
-                o = (float)pow((double)fmaxf(v, 1e-8f), ig);
-            }
-            dst[c * hw + i] = isp_quant(o);
+    for (int i = 0; i < 9; ++i) m[i] = cm[i];
+    const float* src = packed + (size_t)n * 9 * hw;
+    float* dst = out + (size_t)n * 3 * hw;
+    const double ig = (double)inv_gamma;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < hw; i += (size_t)gridDim.x * 256) {
+        float sum[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {
+            const uint32_t col = xt_colour(k);
+            const float v = fminf(fmaxf(src[k * hw + i] * wc[col], 0.f), 1.f);
+            sum[col] = xt_planes_before(k, col) == 0 ? v : sum[col] + v;
         }
+        const float r = sum[0] / (float)xt_planes_before(9, 0), g = sum[1] / (float)xt_planes_before(9, 1), b = sum[2] / (float)xt_planes_before(9, 2);
+        isp_rgb_out(r, g, b, m, dst, i, hw, inv_gamma, ig, crf_E, crf_f, crf_n, gtab, s_t);
     }
 }
 
@@ -477,6 +519,20 @@ extern "C" int eld_isp_process(const float* bayer, const float* wbs, const float
     const unsigned bx = (unsigned)((hw + 255) / 256 < 2048 ? (hw + 255) / 256 : 2048);
     const int gtab = (crf_n == 0 && gamma == 2.2f) ? 1 : 0;
     ELD_LAUNCH(isp_kernel, dim3(bx, N), dim3(256), 0, as_stream(stream), bayer, wbs, ccms, out, hw, (float)(1.0 / (double)gamma), crf_E, crf_f, crf_n, gtab);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int eld_isp_process_xtrans(const float* packed, const float* wbs, const float* ccms, float* out, int N, int H, int W, float gamma,
+                                      const float* crf_E, const float* crf_f, int crf_n, void* stream) {
+    if (N == 0) return 0;
+    if (!packed || !wbs || !ccms || !out || N < 0 || H < 1 || W < 1 || !(gamma > 0.f)) return ELD_EINVAL;
+    if (crf_n != 0 && (crf_n < 2 || !crf_E || !crf_f)) return ELD_EINVAL;
+    const size_t hw = (size_t)H * W;
+    const unsigned bx = (unsigned)((hw + 255) / 256 < 2048 ? (hw + 255) / 256 : 2048);
+    const int gtab = (crf_n == 0 && gamma == 2.2f) ? 1 : 0;
+    ELD_LAUNCH(isp_xtrans_kernel, dim3(bx, N), dim3(256), 0, as_stream(stream), packed, wbs, ccms, out, hw, (float)(1.0 / (double)gamma), crf_E, crf_f, crf_n,
+               gtab);
     ELD_LAUNCH_CHECK();
     return 0;
 }

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include "philox.h"
 #include "poisson_alias_table.h"
+#include "xtrans.h"
 
 #pragma clang fp contract(off)
 
@@ -191,9 +192,8 @@ __device__ __forceinline__ uint32_t pick(const uint4& w, int j) { return j == 0 
 
 // X-Trans (ELD_CFA_XTRANS, C == 9, RawPacker.pack_raw_xtrans's planes): packed row i holds sensor rows 3i..3i+2.  Element (c, i, j)
 // reads sensor row 3i + d(c, (i ^ j) & 1), d = 2 bits at 4c + 2((i ^ j) & 1) of XT_DROW (planes 0-2: 0; 3: 1,2; 4: 2,1; 5-6: 1;
-// 7-8: 2 -- eld_pack_xtrans's XT_RC rows minus 3 (i & 1)); plane c has CFA colour (XT_COLOUR >> 2c) & 3 (R 0, G 1, B 2).
+// 7-8: 2 -- eld_pack_xtrans's XT_RC rows minus 3 (i & 1)); plane c has CFA colour (XT_COLOUR >> 2c) & 3 (R 0, G 1, B 2, xtrans.h).
 constexpr uint64_t XT_DROW = 0xaa5569000ull;
-constexpr uint32_t XT_COLOUR = 0x15624u;
 __device__ __forceinline__ uint32_t xt_drow(uint32_t c, uint32_t parity) { return (uint32_t)(XT_DROW >> (4u * c + 2u * parity)) & 3u; }
 
 __device__ __forceinline__ float row_normal(uint32_t srow, const SamplerRng& rng) {
@@ -722,17 +722,9 @@ extern "C" int eld_unpack_bayer(const float* packed, float* mosaic, int N, int h
 // ---------------------------------------------------------------------------------------------
 // X-Trans pack / unpack (RawPacker.pack_raw_xtrans / unpack_raw_xtrans, noise.py:22-64, 83-127).  Pure index maps, bit-exact:
 // the 6x6 colour cell <-> 9 planes at 1/3 resolution.  Planes 0..4: packed (2a + pi, 2b + pj) <-> cell (a, b), position
-// XT_RC[c][pi][pj]; planes 5..8: packed (i, j) <-> 3x3 block (i, j), position XT_RC3[c - 5].  One thread per packed element
+// XT_RC[c][pi][pj]; planes 5..8: packed (i, j) <-> 3x3 block (i, j), position XT_RC3[c - 5] (xtrans.h).  One thread per packed element
 // (the packed side is the coalesced one: 4 B per lane, consecutive j); the 36 positions of a cell are covered exactly once.
 // ---------------------------------------------------------------------------------------------
-__constant__ unsigned char XT_RC[5][2][2][2] = {
-    {{{0, 0}, {0, 4}}, {{3, 1}, {3, 3}}},
-    {{{0, 2}, {0, 5}}, {{3, 2}, {3, 5}}},
-    {{{0, 1}, {0, 3}}, {{3, 0}, {3, 4}}},
-    {{{1, 2}, {2, 5}}, {{5, 2}, {4, 5}}},
-    {{{2, 2}, {1, 5}}, {{4, 2}, {5, 5}}},
-};
-__constant__ unsigned char XT_RC3[4][2] = {{1, 0}, {1, 1}, {2, 0}, {2, 1}};
 
 template <bool PACK>
 __global__ __launch_bounds__(256) void xtrans_kernel(const float* __restrict__ src, float* __restrict__ dst, int h, int w, int Hm, int Wm) {
@@ -784,10 +776,17 @@ extern "C" int eld_unpack_xtrans(const float* packed, float* mosaic, int N, int 
 // float32 throughout as NumPy evaluates it (uint16 -> float32 exact, one rounding per op, true division).  2 B read + 4 B written
 // per sensor pixel.  A lane handles two horizontally adjacent packed positions of all four channels: one 8-byte read per mosaic row.
 // ---------------------------------------------------------------------------------------------
+// GAIN (eld_pack_raw_bayer_u16_gain, the evaluation input stage of dataset/sid_dataset.py:398-409): then min(max(v * ratio[n], 0), 1)
+// -- NumPy's np.maximum(np.minimum(v * np.float32(ratio), 1), 0), one float32 rounding for the product.
 struct PackRawArgs { int oy[4], ox[4]; float black[4], denom[4]; };
 
-__global__ __launch_bounds__(256) void pack_raw_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, PackRawArgs p) {
+__device__ __forceinline__ float apply_gain(float v, float ratio) { return fmaxf(fminf(v * ratio, 1.f), 0.f); }
+
+template <bool GAIN>
+__global__ __launch_bounds__(256) void pack_raw_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, PackRawArgs p,
+                                                       const float* __restrict__ ratios) {
     const int n = blockIdx.y;
+    const float ratio = GAIN ? ratios[n] : 1.f;
     const size_t hw = (size_t)h * w, W2 = 2 * (size_t)w;
     const uint16_t* src = im + (size_t)n * 4 * hw;
     float* dst = out + (size_t)n * 4 * hw;
@@ -810,14 +809,16 @@ __global__ __launch_bounds__(256) void pack_raw_kernel(const uint16_t* __restric
             const float v0 = ((float)q[p.oy[k]][p.ox[k]] - p.black[k]) / p.denom[k];
             const float v1 = ((float)q[p.oy[k]][2 + p.ox[k]] - p.black[k]) / p.denom[k];
             float* o = dst + (size_t)k * hw + (size_t)y * w + x;
-            o[0] = fminf(fmaxf(v0, 0.f), 1.f);
-            if (two) o[1] = fminf(fmaxf(v1, 0.f), 1.f);
+            float o0 = fminf(fmaxf(v0, 0.f), 1.f), o1 = fminf(fmaxf(v1, 0.f), 1.f);
+            if (GAIN) { o0 = apply_gain(o0, ratio); o1 = apply_gain(o1, ratio); }
+            o[0] = o0;
+            if (two) o[1] = o1;
         }
     }
 }
 
-extern "C" int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
-                                      float white_point, void* stream) {
+static int pack_raw_bayer_launch(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
+                                 float white_point, const float* ratios, void* stream) {
     if (N < 0 || h < 0 || w < 0 || !raw_pattern || !black_level) return ELD_EINVAL;
     if (N == 0 || h == 0 || w == 0) return 0;
     if (!mosaic || !packed) return ELD_EINVAL;
@@ -831,9 +832,21 @@ extern "C" int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int
     for (int k = 0; k < 4; ++k) { p.black[k] = black_level[k]; p.denom[k] = white_point - black_level[k]; }
     const size_t total = (size_t)h * ((w + 1) / 2);
     dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
-    ELD_LAUNCH(pack_raw_kernel, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, p);
+    if (ratios) ELD_LAUNCH(pack_raw_kernel<true>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, p, ratios);
+    else ELD_LAUNCH(pack_raw_kernel<false>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, p, ratios);
     ELD_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
+                                      float white_point, void* stream) {
+    return pack_raw_bayer_launch(mosaic, packed, N, h, w, raw_pattern, black_level, white_point, nullptr, stream);
+}
+
+extern "C" int eld_pack_raw_bayer_u16_gain(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
+                                           float white_point, const float* ratios, void* stream) {
+    if (N > 0 && h > 0 && w > 0 && !ratios) return ELD_EINVAL;
+    return pack_raw_bayer_launch(mosaic, packed, N, h, w, raw_pattern, black_level, white_point, ratios, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -841,9 +854,11 @@ extern "C" int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int
 //   out[c][i][j] = clip((float(im[row][col]) - black) / (white - black), 0, 1),  (row, col) = xtrans_kernel's index map of (c, i, j)
 // float32 as NumPy evaluates it (uint16 -> float32 exact, one rounding per op, true division): bit-exact.  One thread per packed element.
 // ---------------------------------------------------------------------------------------------
+template <bool GAIN>
 __global__ __launch_bounds__(256) void pack_raw_xtrans_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, int Hm, int Wm,
-                                                              float black, float denom) {
+                                                              float black, float denom, const float* __restrict__ ratios) {
     const int n = blockIdx.y;
+    const float ratio = GAIN ? ratios[n] : 1.f;
     const size_t hw = (size_t)h * w, total = 9 * hw;
     const uint16_t* s = im + (size_t)n * Hm * Wm;
     float* d = out + (size_t)n * total;
@@ -855,19 +870,203 @@ __global__ __launch_bounds__(256) void pack_raw_xtrans_kernel(const uint16_t* __
         if (c < 5) { row = 6 * (i >> 1) + XT_RC[c][i & 1][j & 1][0]; col = 6 * (j >> 1) + XT_RC[c][i & 1][j & 1][1]; }
         else { row = 3 * i + XT_RC3[c - 5][0]; col = 3 * j + XT_RC3[c - 5][1]; }
         const float v = ((float)s[(size_t)row * Wm + col] - black) / denom;
-        d[e] = fminf(fmaxf(v, 0.f), 1.f);
+        const float o = fminf(fmaxf(v, 0.f), 1.f);
+        d[e] = GAIN ? apply_gain(o, ratio) : o;
     }
 }
 
-// uint16 mosaic [N, Hm, Wm] -> packed float32 [N, 9, 2*(Hm/6), 2*(Wm/6)] (sides truncated to whole 6x6 cells, as eld_pack_xtrans)
-extern "C" int eld_pack_raw_xtrans_u16(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point, void* stream) {
+static int pack_raw_xtrans_launch(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
+                                  const float* ratios, void* stream) {
     if (N < 0 || Hm < 0 || Wm < 0 || !(white_point > black_level)) return ELD_EINVAL;
     const int h = 2 * (Hm / 6), w = 2 * (Wm / 6);
     const size_t total = (size_t)9 * h * w;
     if (N == 0 || total == 0) return 0;
     if (!mosaic || !packed) return ELD_EINVAL;
     dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
-    ELD_LAUNCH(pack_raw_xtrans_kernel, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level);
+    if (ratios) ELD_LAUNCH(pack_raw_xtrans_kernel<true>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level, ratios);
+    else ELD_LAUNCH(pack_raw_xtrans_kernel<false>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level, ratios);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+// uint16 mosaic [N, Hm, Wm] -> packed float32 [N, 9, 2*(Hm/6), 2*(Wm/6)] (sides truncated to whole 6x6 cells, as eld_pack_xtrans)
+extern "C" int eld_pack_raw_xtrans_u16(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point, void* stream) {
+    return pack_raw_xtrans_launch(mosaic, packed, N, Hm, Wm, black_level, white_point, nullptr, stream);
+}
+
+extern "C" int eld_pack_raw_xtrans_u16_gain(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
+                                            const float* ratios, void* stream) {
+    if (N > 0 && Hm >= 6 && Wm >= 6 && !ratios) return ELD_EINVAL;
+    return pack_raw_xtrans_launch(mosaic, packed, N, Hm, Wm, black_level, white_point, ratios, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Write-back: packed network output -> uint16 sensor codes (the mosaic half of postprocess_bayer / postprocess_xtrans,
+// models/ELD_model.py:41-129), per element with the black level b of its channel and the white point w:
+//   v = double(clip(x, 0, 1)) * (w - b) + b      exact in double for integer b, w <= 65535: a 24-bit mantissa times a 16-bit integer
+//                                                 is <= 40 bits, and adding an integer below 2^16 stays within 53
+//   ELD_ROUND_TRUNC     uint16(v) truncated toward zero: NumPy's float64 -> uint16 assignment into raw_image_visible (the reference's
+//                       Bayer path: black_level_per_channel is an int64 array, so the product is float64)
+//   ELD_ROUND_NEAREST   v rounded to the nearest integer, ties to even
+//   ELD_ROUND_TRUNC_F32 float32 evaluation fl(fl(x * (w - b)) + b) truncated: the reference's X-Trans path, whose black / white are
+//                       Python ints that leave the float32 array float32
+// A NaN in the output writes b (fmaxf drops it).  HBM-bound: 4 B read + 2 B written per pixel, no reuse.
+// ---------------------------------------------------------------------------------------------
+template <int MODE>
+__device__ __forceinline__ uint32_t wb_code(float x, double scale, double black, float scale_f, float black_f) {
+    const float c = fminf(fmaxf(x, 0.f), 1.f);
+    if (MODE == ELD_ROUND_TRUNC_F32) return (uint32_t)__fadd_rn(__fmul_rn(c, scale_f), black_f);
+    const double v = __dadd_rn(__dmul_rn((double)c, scale), black);
+    return MODE == ELD_ROUND_NEAREST ? (uint32_t)__builtin_rint(v) : (uint32_t)v;
+}
+
+// per 2x2 cell position (row-major; the X-Trans kernel uses entry 0): the plane it reads and the constants of that plane's channel
+struct WriteBackArgs { double scale[4], black[4]; float scale_f[4], black_f[4]; int plane[4]; };
+
+// Bayer: packed [N,4,h,w] -> mosaic [N,2h,2w]; mosaic (2y + oy, 2x + ox) <- plane raw_pattern[oy][ox].
+// VEC (w % 4 == 0, 16-byte aligned buffers): a lane takes four packed columns: four 16-byte plane reads, two 16-byte row writes.
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(256) void unpack_raw_kernel(const float* __restrict__ packed, uint16_t* __restrict__ mosaic, int h, int w, WriteBackArgs a) {
+    const int n = blockIdx.y;
+    const size_t hw = (size_t)h * w, W2 = 2 * (size_t)w;
+    const float* src = packed + (size_t)n * 4 * hw;
+    uint16_t* dst = mosaic + (size_t)n * 4 * hw;
+    constexpr int XS = VEC ? 4 : 1;
+    const int wq = w / XS;
+    const size_t total = (size_t)h * wq;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int y = (int)(i / wq), x = XS * (int)(i - (size_t)y * wq);
+        const size_t q = (size_t)y * w + x;
+#pragma unroll
+        for (int oy = 0; oy < 2; ++oy) {
+            uint16_t* row = dst + (size_t)(2 * y + oy) * W2 + 2 * x;
+            const int k0 = 2 * oy, k1 = 2 * oy + 1;                     // cell positions (compile time after unrolling)
+            const float* s0 = src + (size_t)a.plane[k0] * hw + q;
+            const float* s1 = src + (size_t)a.plane[k1] * hw + q;
+            if (VEC) {
+                const float4 p0 = *reinterpret_cast<const float4*>(s0);
+                const float4 p1 = *reinterpret_cast<const float4*>(s1);
+                const float e0[4] = {p0.x, p0.y, p0.z, p0.w}, e1[4] = {p1.x, p1.y, p1.z, p1.w};
+                uint32_t wv[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    wv[j] = wb_code<MODE>(e0[j], a.scale[k0], a.black[k0], a.scale_f[k0], a.black_f[k0]) |
+                            (wb_code<MODE>(e1[j], a.scale[k1], a.black[k1], a.scale_f[k1], a.black_f[k1]) << 16);
+                *reinterpret_cast<uint4*>(row) = make_uint4(wv[0], wv[1], wv[2], wv[3]);
+            } else {
+                row[0] = (uint16_t)wb_code<MODE>(*s0, a.scale[k0], a.black[k0], a.scale_f[k0], a.black_f[k0]);
+                row[1] = (uint16_t)wb_code<MODE>(*s1, a.scale[k1], a.black[k1], a.scale_f[k1], a.black_f[k1]);
+            }
+        }
+    }
+}
+
+// plane[i]: the packed plane of cell position i (Bayer: raw_pattern; X-Trans: {0, 0, 0, 0} with one black level)
+static bool writeback_args(WriteBackArgs& a, const float* black_level, const int* plane, float white_point, int rounding) {
+    if (rounding < ELD_ROUND_TRUNC || rounding > ELD_ROUND_TRUNC_F32 || !(white_point <= 65535.f)) return false;
+    for (int k = 0; k < 4; ++k) {
+        const float b = black_level[plane[k]];
+        a.plane[k] = plane[k];
+        if (!(b >= 0.f) || !(white_point > b)) return false;
+        a.scale[k] = (double)white_point - (double)b; a.black[k] = (double)b;
+        a.scale_f[k] = white_point - b; a.black_f[k] = b;
+    }
+    return true;
+}
+
+template <int MODE>
+static void unpack_raw_bayer_dispatch(bool vec, dim3 grid, hipStream_t st, const float* packed, uint16_t* mosaic, int h, int w, const WriteBackArgs& a) {
+    if (vec) ELD_LAUNCH((unpack_raw_kernel<MODE, true>), grid, dim3(256), 0, st, packed, mosaic, h, w, a);
+    else ELD_LAUNCH((unpack_raw_kernel<MODE, false>), grid, dim3(256), 0, st, packed, mosaic, h, w, a);
+}
+
+extern "C" int eld_unpack_raw_bayer_u16(const float* packed, uint16_t* mosaic, int N, int h, int w, const int* raw_pattern, const float* black_level,
+                                        float white_point, int rounding, void* stream) {
+    if (N < 0 || h < 0 || w < 0 || !raw_pattern || !black_level) return ELD_EINVAL;
+    bool seen[4] = {false, false, false, false};
+    for (int i = 0; i < 4; ++i) {                                    // a permutation of 0..3, as eld_pack_raw_bayer_u16
+        const int k = raw_pattern[i];
+        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
+        seen[k] = true;
+    }
+    WriteBackArgs a;
+    if (!writeback_args(a, black_level, raw_pattern, white_point, rounding)) return ELD_EINVAL;
+    if (N == 0 || h == 0 || w == 0) return 0;
+    if (!packed || !mosaic) return ELD_EINVAL;
+    const bool vec = w % 4 == 0 && (((uintptr_t)packed | (uintptr_t)mosaic) & 15) == 0;
+    const size_t total = (size_t)h * (vec ? w / 4 : w);
+    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
+    hipStream_t st = as_stream(stream);
+    if (rounding == ELD_ROUND_TRUNC) unpack_raw_bayer_dispatch<ELD_ROUND_TRUNC>(vec, grid, st, packed, mosaic, h, w, a);
+    else if (rounding == ELD_ROUND_NEAREST) unpack_raw_bayer_dispatch<ELD_ROUND_NEAREST>(vec, grid, st, packed, mosaic, h, w, a);
+    else unpack_raw_bayer_dispatch<ELD_ROUND_TRUNC_F32>(vec, grid, st, packed, mosaic, h, w, a);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+// X-Trans: packed [N,9,2*(Hm/6),2*(Wm/6)] -> the whole 6x6 cells of mosaic [N,Hm,Wm]; rows / columns beyond the last whole cell are not
+// written (the caller's mosaic keeps its codes there).  A lane owns one cell (a, b): its 36 codes come from packed rows 2a, 2a + 1 and
+// columns 2b, 2b + 1 of the nine planes (one 8-byte read per plane and row; consecutive lanes read consecutive 8 bytes), the index map
+// of xtrans.h unrolled into immediates, and leave as six 12-byte row segments (PAIRS: three 4-byte stores when Wm is even).
+template <int MODE, bool PAIRS>
+__global__ __launch_bounds__(256) void unpack_raw_xtrans_kernel(const float* __restrict__ packed, uint16_t* __restrict__ mosaic, int Hm, int Wm,
+                                                                double scale, double black, float scale_f, float black_f) {
+    const int n = blockIdx.y;
+    const int ca = Hm / 6, cb = Wm / 6, w = 2 * cb;
+    const size_t hw = (size_t)(2 * ca) * w, cells = (size_t)ca * cb;
+    const float* src = packed + (size_t)n * 9 * hw;
+    uint16_t* dst = mosaic + (size_t)n * Hm * Wm;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < cells; e += (size_t)gridDim.x * 256) {
+        const int a = (int)(e / cb), b = (int)(e - (size_t)a * cb);
+        uint32_t code[6][6];
+#pragma unroll
+        for (int c = 0; c < 9; ++c)
+#pragma unroll
+            for (int pi = 0; pi < 2; ++pi) {
+                const float2 v = *reinterpret_cast<const float2*>(src + (size_t)c * hw + (size_t)(2 * a + pi) * w + 2 * b);
+#pragma unroll
+                for (int pj = 0; pj < 2; ++pj) {
+                    const int r = c < 5 ? XT_RC[c][pi][pj][0] : 3 * pi + XT_RC3[c - 5][0];
+                    const int q = c < 5 ? XT_RC[c][pi][pj][1] : 3 * pj + XT_RC3[c - 5][1];
+                    code[r][q] = wb_code<MODE>(pj ? v.y : v.x, scale, black, scale_f, black_f);
+                }
+            }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            uint16_t* row = dst + (size_t)(6 * a + r) * Wm + 6 * b;
+            if (PAIRS) {
+#pragma unroll
+                for (int q = 0; q < 3; ++q) reinterpret_cast<uint32_t*>(row)[q] = code[r][2 * q] | (code[r][2 * q + 1] << 16);
+            } else {
+#pragma unroll
+                for (int q = 0; q < 6; ++q) row[q] = (uint16_t)code[r][q];
+            }
+        }
+    }
+}
+
+template <int MODE>
+static void unpack_raw_xtrans_dispatch(bool pairs, dim3 grid, hipStream_t st, const float* packed, uint16_t* mosaic, int Hm, int Wm, const WriteBackArgs& a) {
+    if (pairs) ELD_LAUNCH((unpack_raw_xtrans_kernel<MODE, true>), grid, dim3(256), 0, st, packed, mosaic, Hm, Wm, a.scale[0], a.black[0], a.scale_f[0], a.black_f[0]);
+    else ELD_LAUNCH((unpack_raw_xtrans_kernel<MODE, false>), grid, dim3(256), 0, st, packed, mosaic, Hm, Wm, a.scale[0], a.black[0], a.scale_f[0], a.black_f[0]);
+}
+
+extern "C" int eld_unpack_raw_xtrans_u16(const float* packed, uint16_t* mosaic, int N, int Hm, int Wm, float black_level, float white_point, int rounding,
+                                         void* stream) {
+    if (N < 0 || Hm < 0 || Wm < 0) return ELD_EINVAL;
+    WriteBackArgs a;
+    const int plane0[4] = {0, 0, 0, 0};
+    if (!writeback_args(a, &black_level, plane0, white_point, rounding)) return ELD_EINVAL;
+    const size_t cells = (size_t)(Hm / 6) * (Wm / 6);
+    if (N == 0 || cells == 0) return 0;
+    if (!packed || !mosaic) return ELD_EINVAL;
+    if (((uintptr_t)packed & 7) != 0) return ELD_EINVAL;                    // 8-byte plane reads (every plane row is 8-byte aligned then)
+    const bool pairs = Wm % 2 == 0 && ((uintptr_t)mosaic & 3) == 0;
+    dim3 grid((unsigned)min((cells + 255) / 256, (size_t)4096), N);
+    hipStream_t st = as_stream(stream);
+    if (rounding == ELD_ROUND_TRUNC) unpack_raw_xtrans_dispatch<ELD_ROUND_TRUNC>(pairs, grid, st, packed, mosaic, Hm, Wm, a);
+    else if (rounding == ELD_ROUND_NEAREST) unpack_raw_xtrans_dispatch<ELD_ROUND_NEAREST>(pairs, grid, st, packed, mosaic, Hm, Wm, a);
+    else unpack_raw_xtrans_dispatch<ELD_ROUND_TRUNC_F32>(pairs, grid, st, packed, mosaic, Hm, Wm, a);
     ELD_LAUNCH_CHECK();
     return 0;
 }

@@ -1,0 +1,415 @@
+"""Denoise raw frames end to end: a trained U-Net on a sensor's own uint16 mosaics, back to a uint16 mosaic (and, with a white
+balance and a colour matrix, an 8-bit sRGB rendering).  The third step after calibrating a sensor (eld_amd.calibrate) and training a
+denoiser for it (train_syn.py through the plugins).  Every device stage is a HIP kernel of libeld_amd:
+
+    input stage   pack -> x ratio -> clip in one pass (eld_pack_raw_*_u16_gain; dataset/sid_dataset.py:398-409)
+    network       the U-Net, whole frame when the packed sides are multiples of 16, else the reference's forward_chop tiles
+    write-back    the packed output -> uint16 codes (eld_unpack_raw_*_u16; the mosaic half of postprocess_bayer / postprocess_xtrans,
+                  models/ELD_model.py:41-129)
+    sRGB          util/process.py `process` (eld_isp_process; X-Trans: eld_isp_process_xtrans, the same pipeline on X-Trans binning)
+
+Write-back rounding.  Per element v = float64(clip(x, 0, 1)) * (white - black) + black (exact).  rounding='reference' truncates as the
+reference's assignment into the uint16 raw_image_visible does (Bayer: the float64 expression; X-Trans: the reference evaluates it in
+float32, and so does this mode).  Under that truncation pack followed by write-back is NOT the identity on Bayer: of the 15872 codes in
+[512, 16383], 7893 come back one DN low (7676 of 15360 for black 1024).  rounding='nearest' (the default) rounds half to even, and then
+every code in [black, white] round-trips, for (black, white) = (512, 16383), (1024, 16383), (2048, 16383) and (0, 65535).
+
+Raw files are not decoded here (no rawpy): mosaics arrive as arrays (`raw.raw_image_visible`), and the values rawpy reports
+(raw_pattern, black_level_per_channel, camera_whitebalance, rgb_camera_matrix[:3, :3]) as arguments or a JSON sidecar.
+LibRaw's demosaic and rendering are out of scope: the sRGB output is the reference's `process` at packed resolution.
+
+    python -m eld_amd.denoise --ckpt model.pt --cfa xtrans --black 1024 --white 16383 --ratio 100 [--wb R G B] [--ccm 9 values] [--bf16] \\
+        in.npy [more.npy] -o outdir
+"""
+import argparse
+import ctypes
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+from . import _lib as L
+
+PLANES = {'bayer': 4, 'xtrans': 9}
+ROUNDING = ('nearest', 'reference')
+DEFAULT_BLACK = {'bayer': 512, 'xtrans': 1024}      # SID Sony (rawpy black_level_per_channel) / the reference's X-Trans constant
+DEFAULT_PATTERN = ((0, 1), (3, 2))                   # RGGB as rawpy codes (R 0, G1 1, B 2, G2 3)
+
+
+# ---- the denoiser ---------------------------------------------------------------------------------------------------------------
+class Denoiser:
+    """A U-Net ready for inference: `net` (eld_amd.unet.UNetSeeInDark), the CFA it was trained for and its precision."""
+    def __init__(self, net, cfa, precision):
+        self.net, self.cfa, self.precision = net, cfa, precision
+
+    @property
+    def in_channels(self):
+        return self.net.in_channels
+
+    @property
+    def out_channels(self):
+        return self.net.out_channels
+
+
+def _check_cfa(cfa):
+    if cfa not in PLANES:
+        raise ValueError("cfa must be 'bayer' or 'xtrans', got %r" % (cfa,))
+
+
+def load_denoiser(ckpt_or_model, cfa='bayer', precision='fp32', device=None):
+    """ckpt_or_model: a checkpoint path, the reference's checkpoint dict ({'netG': state_dict, ...}, what ELDModel.save writes and
+    ELDModel.load reads), a bare U-Net state_dict, an ELDModel or a U-Net instance.  Returns a Denoiser whose network runs in
+    `precision` ('fp32' or 'bf16') on `device` (default: the current CUDA device)."""
+    import torch
+    from .unet import UNetSeeInDark
+    _check_cfa(cfa)
+    if precision not in ('fp32', 'bf16'):
+        raise ValueError("precision must be 'fp32' or 'bf16', got %r" % (precision,))
+    if isinstance(ckpt_or_model, (str, os.PathLike)):
+        ckpt_or_model = torch.load(ckpt_or_model, map_location='cpu')
+    if isinstance(ckpt_or_model, UNetSeeInDark):
+        net = ckpt_or_model
+    elif hasattr(ckpt_or_model, 'netG'):
+        net = ckpt_or_model.netG
+    elif isinstance(ckpt_or_model, dict):
+        sd = ckpt_or_model.get('netG', ckpt_or_model)
+        if 'conv1_1.weight' not in sd or 'conv10_1.weight' not in sd:
+            raise ValueError('not a U-Net checkpoint: expected the reference dict {"netG": state_dict, ...} or a UNetSeeInDark state_dict')
+        net = UNetSeeInDark(int(sd['conv1_1.weight'].shape[1]), int(sd['conv10_1.weight'].shape[0]))
+        net.load_state_dict(sd)
+    else:
+        raise ValueError('cannot load a denoiser from %r' % (type(ckpt_or_model).__name__,))
+    if device is None:
+        device = torch.device('cuda', torch.cuda.current_device()) if torch.cuda.is_available() else torch.device('cpu')
+    net = net.to(device)
+    net.requires_grad_(False)
+    net.inference_precision = precision
+    return Denoiser(net, cfa, precision)
+
+
+# ---- argument checks (all before any device work) ---------------------------------------------------------------------------------
+def _as_u16(mosaic):
+    """-> (kind, array-or-tensor, batched).  kind: 'numpy' or 'torch'.  Refuses anything that is not uint16 codes."""
+    if isinstance(mosaic, np.ndarray):
+        if mosaic.dtype != np.uint16:
+            raise ValueError('mosaic must be a uint16 array, got %s' % mosaic.dtype)
+        kind = 'numpy'
+    else:
+        try:
+            import torch
+        except ImportError:                                     # pragma: no cover
+            torch = None
+        if torch is None or not isinstance(mosaic, torch.Tensor):
+            raise ValueError('mosaic must be a NumPy uint16 array or a CUDA uint16 / int16 tensor, got %r' % (type(mosaic).__name__,))
+        if mosaic.dtype not in (torch.uint16, torch.int16):
+            raise ValueError('mosaic must hold uint16 codes (torch.uint16, or its int16 view), got %s' % mosaic.dtype)
+        if not mosaic.is_cuda:
+            raise ValueError('a mosaic tensor must be on a CUDA device (NumPy arrays are uploaded)')
+        kind = 'torch'
+    if mosaic.ndim not in (2, 3):
+        raise ValueError('mosaic must be (Hm, Wm) or (N, Hm, Wm), got shape %s' % (tuple(mosaic.shape),))
+    return kind, mosaic.ndim == 3
+
+
+def _check_sides(Hm, Wm, cfa):
+    if Hm % 2 or Wm % 2:
+        raise ValueError('mosaic sides must be even, got %d x %d' % (Hm, Wm))
+    if cfa == 'xtrans' and (Hm < 6 or Wm < 6):
+        raise ValueError('an X-Trans mosaic needs sides of at least 6 (one 6x6 cell), got %d x %d' % (Hm, Wm))
+    if Hm < 2 or Wm < 2:
+        raise ValueError('empty mosaic: %d x %d' % (Hm, Wm))
+
+
+def _levels(cfa, raw_pattern, black_level, white_point):
+    """-> (pattern as 4 ints or None, black levels: 4 float32 for Bayer / one for X-Trans, white)"""
+    white = float(white_point)
+    if not (0 < white <= 65535) or white != math.floor(white):
+        raise ValueError('white_point must be an integer in (0, 65535], got %r' % (white_point,))
+    if black_level is None:
+        black_level = DEFAULT_BLACK[cfa]
+    blk = np.asarray(black_level, dtype=np.float64).reshape(-1)
+    if cfa == 'bayer':
+        pat = np.asarray(DEFAULT_PATTERN if raw_pattern is None else raw_pattern).reshape(-1)
+        if pat.size != 4 or sorted(int(v) for v in pat) != [0, 1, 2, 3]:
+            raise ValueError('raw_pattern must be a 2x2 permutation of the codes 0..3, got %r' % (raw_pattern,))
+        pat = [int(v) for v in pat]
+        if blk.size == 1:
+            blk = np.repeat(blk, 4)
+        if blk.size != 4:
+            raise ValueError('Bayer black_level takes 1 or 4 values (black_level_per_channel), got %d' % blk.size)
+    else:
+        pat = None
+        if blk.size > 1:
+            if not np.all(blk == blk[0]):
+                raise ValueError('X-Trans takes one black level for all planes (as the reference), got %r' % (blk.tolist(),))
+            blk = blk[:1]
+    if np.any(blk < 0) or np.any(blk != np.floor(blk)):
+        raise ValueError('black levels must be non-negative integers, got %r' % (blk.tolist(),))
+    if np.any(white <= blk):
+        raise ValueError('white_point (%g) must exceed every black level %r' % (white, blk.tolist()))
+    return pat, [float(v) for v in blk], white
+
+
+def _ratios(ratio, N):
+    r = np.asarray(ratio, dtype=np.float64).reshape(-1)
+    if r.size == 1:
+        r = np.repeat(r, N)
+    if r.size != N:
+        raise ValueError('ratio takes one value or one per frame (%d), got %d' % (N, r.size))
+    if not np.all(np.isfinite(r)) or np.any(r <= 0):
+        raise ValueError('ratio must be finite and > 0, got %r' % (r.tolist(),))
+    return r.astype(np.float32)
+
+
+def _colour(cfa, wb, ccm, N):
+    """-> (wbs float32 (N,4) Bayer RGBG / (N,3) X-Trans RGB, ccms float32 (N,3,3)) or (None, None)"""
+    if wb is None and ccm is None:
+        return None, None
+    if wb is None or ccm is None:
+        raise ValueError('the sRGB output needs both wb and ccm')
+    w = np.asarray(wb, dtype=np.float64)
+    if w.ndim == 1:
+        w = np.broadcast_to(w, (N, w.size))
+    if w.ndim != 2 or w.shape[0] != N or w.shape[1] not in (3, 4):
+        raise ValueError('wb must hold 3 (R, G, B) or 4 (rawpy camera_whitebalance) values, per frame or for all, got shape %s'
+                         % (np.shape(wb),))
+    if w.shape[1] == 4:                       # raw2rgb_postprocess (util/process.py:111-121): wb /= wb[1]
+        if np.any(w[:, 1] == 0):
+            raise ValueError('camera_whitebalance with a zero green gain')
+        w = w / w[:, 1:2]
+    if cfa == 'bayer' and w.shape[1] == 3:
+        w = np.concatenate([w, w[:, 1:2]], axis=1)          # R, G, B -> R, G1, B, G2
+    if cfa == 'xtrans':
+        w = w[:, :3]
+    m = np.asarray(ccm, dtype=np.float64)
+    if m.shape == (9,) or m.shape == (3, 3):
+        m = np.broadcast_to(m.reshape(3, 3), (N, 3, 3))
+    if m.shape != (N, 3, 3):
+        raise ValueError('ccm must be 3x3 (9 values), per frame or for all, got shape %s' % (np.shape(ccm),))
+    if not (np.all(np.isfinite(w)) and np.all(np.isfinite(m))):
+        raise ValueError('wb and ccm must be finite')
+    return np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(m, dtype=np.float32)
+
+
+# ---- the device stages ------------------------------------------------------------------------------------------------------------
+def pack_input(t, cfa, raw_pattern, black_level, white_point, ratios):
+    """CUDA int16-view codes (N,Hm,Wm) -> the network input (N,C,h,w) float32: pack, x ratio[n], clip -- one kernel."""
+    import torch
+    N, Hm, Wm = t.shape
+    r = torch.as_tensor(np.asarray(ratios, np.float32), device=t.device)
+    if cfa == 'bayer':
+        out = torch.empty((N, 4, Hm // 2, Wm // 2), dtype=torch.float32, device=t.device)
+        pat = (ctypes.c_int * 4)(*raw_pattern)
+        blk = (ctypes.c_float * 4)(*black_level)
+        L.check(L.lib().eld_pack_raw_bayer_u16_gain(L.dptr(t), L.dptr(out), N, Hm // 2, Wm // 2, pat, blk, float(white_point), L.dptr(r),
+                                                    L.cur_stream()), 'eld_pack_raw_bayer_u16_gain')
+    else:
+        out = torch.empty((N, 9, 2 * (Hm // 6), 2 * (Wm // 6)), dtype=torch.float32, device=t.device)
+        L.check(L.lib().eld_pack_raw_xtrans_u16_gain(L.dptr(t), L.dptr(out), N, Hm, Wm, float(black_level[0]), float(white_point), L.dptr(r),
+                                                     L.cur_stream()), 'eld_pack_raw_xtrans_u16_gain')
+    return out
+
+
+def write_back(packed, mosaic, cfa, raw_pattern, black_level, white_point, rounding='nearest'):
+    """Packed output (N,C,h,w) float32 -> uint16 codes written INTO `mosaic` (CUDA int16/uint16 (N,Hm,Wm)).  Bayer writes every pixel;
+    X-Trans writes the whole 6x6 cells and leaves the borders beyond them as they are."""
+    packed = packed.contiguous().float()
+    N = packed.shape[0]
+    mode = {'nearest': L.ROUND_NEAREST, 'reference': L.ROUND_TRUNC if cfa == 'bayer' else L.ROUND_TRUNC_F32}[rounding]
+    if cfa == 'bayer':
+        pat = (ctypes.c_int * 4)(*raw_pattern)
+        blk = (ctypes.c_float * 4)(*black_level)
+        L.check(L.lib().eld_unpack_raw_bayer_u16(L.dptr(packed), L.dptr(mosaic), N, packed.shape[2], packed.shape[3], pat, blk, float(white_point),
+                                                 mode, L.cur_stream()), 'eld_unpack_raw_bayer_u16')
+    else:
+        L.check(L.lib().eld_unpack_raw_xtrans_u16(L.dptr(packed), L.dptr(mosaic), N, mosaic.shape[1], mosaic.shape[2], float(black_level[0]),
+                                                  float(white_point), mode, L.cur_stream()), 'eld_unpack_raw_xtrans_u16')
+    return mosaic
+
+
+def run_network(denoiser, x, chop=None):
+    """x (N,C,h,w) CUDA float32 -> the network output.  chop None: whole frame when h and w are multiples of 16, else forward_chop."""
+    import torch
+    from .model import forward_chop
+    h, w = x.shape[2:]
+    if chop is None:
+        chop = bool(h % 16 or w % 16)
+    with torch.no_grad():
+        return forward_chop(denoiser.net, x) if chop else denoiser.net(x)
+
+
+def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
+                chop=None, rounding='nearest'):
+    """Denoise uint16 sensor mosaics with a trained U-Net.
+
+    mosaic_u16  NumPy uint16 array or CUDA uint16 / int16-view tensor, (Hm, Wm) or (N, Hm, Wm) -- rawpy's raw_image_visible.
+    cfa         'bayer' (4 planes; raw_pattern: rawpy's 2x2 raw_pattern, default RGGB; black_level: 1 or 4 values, default 512) or
+                'xtrans' (9 planes, RawPacker.pack_raw_xtrans's layout; one black level, default 1024).
+    ratio       exposure ratio, one value or one per frame: the input is clip(pack(raw) * ratio, 0, 1) (dataset/sid_dataset.py:398-409).
+    wb, ccm     with both, an sRGB rendering at packed resolution (util/process.py `process`): wb R, G, B, or rawpy's 4-value
+                camera_whitebalance (divided by its green); ccm rawpy's rgb_camera_matrix[:3, :3].  CRF: None (gamma 2.2) or (E, fs).
+    chop        None: whole frame when the packed sides are multiples of 16, else the reference's forward_chop; True / False force it.
+    rounding    'nearest' (default: every code in [black, white] round-trips) or 'reference' (the reference's truncation, bit for bit).
+
+    Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
+    uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
+    _check_cfa(cfa)
+    if getattr(denoiser, 'cfa', cfa) != cfa:
+        raise ValueError('the denoiser was loaded for cfa=%r, called with %r' % (denoiser.cfa, cfa))
+    if rounding not in ROUNDING:
+        raise ValueError('rounding must be one of %r, got %r' % (ROUNDING, rounding))
+    if chop not in (None, True, False):
+        raise ValueError('chop must be None, True or False, got %r' % (chop,))
+    kind, batched = _as_u16(mosaic_u16)
+    shape = tuple(mosaic_u16.shape)
+    N = shape[0] if batched else 1
+    Hm, Wm = shape[-2:]
+    if N < 1:
+        raise ValueError('empty batch')
+    _check_sides(Hm, Wm, cfa)
+    pat, blk, white = _levels(cfa, raw_pattern, black_level, white_point)
+    ratios = _ratios(ratio, N)
+    if denoiser.in_channels != PLANES[cfa]:
+        raise ValueError('the network takes %d input planes, a %s frame packs to %d' % (denoiser.in_channels, cfa, PLANES[cfa]))
+    if denoiser.out_channels != PLANES[cfa]:
+        raise ValueError('the network writes %d planes, the %s write-back needs %d' % (denoiser.out_channels, cfa, PLANES[cfa]))
+    wbs, ccms = _colour(cfa, wb, ccm, N)
+
+    import torch
+    dev = next(denoiser.net.parameters()).device
+    if dev.type != 'cuda':
+        raise ValueError('the denoiser must live on a CUDA device (load_denoiser(..., device=...)), it is on %s' % dev)
+    if kind == 'numpy':
+        t = torch.from_numpy(np.ascontiguousarray(mosaic_u16).view(np.int16)).to(dev)
+    else:
+        t = mosaic_u16.contiguous()
+        if t.device != dev:
+            raise ValueError('the mosaic is on %s, the denoiser on %s' % (t.device, dev))
+    t3 = t if batched else t.unsqueeze(0)
+    x = pack_input(t3, cfa, pat, blk, white, ratios)
+    out = run_network(denoiser, x, chop)
+    mosaic = t3.clone()                   # X-Trans: the borders outside whole cells keep the input's codes
+    write_back(out, mosaic, cfa, pat, blk, white, rounding)
+    srgb = None
+    if wbs is not None:
+        from .isp import process, process_xtrans
+        fn = process if cfa == 'bayer' else process_xtrans
+        rgb = fn(out, torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev), CRF=CRF)
+        srgb = torch.round(rgb * 255.0).to(torch.uint8)          # k/255 -> k exactly
+    if not batched:
+        mosaic = mosaic[0]
+    if kind == 'numpy':
+        return {'packed': out.cpu().numpy(), 'mosaic': mosaic.cpu().numpy().view(np.uint16),
+                'srgb': None if srgb is None else srgb.cpu().numpy()}
+    return {'packed': out, 'mosaic': mosaic, 'srgb': srgb}
+
+
+# ---- command line -------------------------------------------------------------------------------------------------------------
+SIDECAR_ALIASES = {'black_level_per_channel': 'black_level', 'white_level': 'white_point', 'camera_whitebalance': 'wb',
+                   'rgb_camera_matrix': 'ccm', 'black': 'black_level', 'white': 'white_point'}
+SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop')
+
+
+def read_sidecar(path):
+    """JSON with denoise_raw's keys, or the names rawpy reports (raw_pattern, black_level_per_channel, white_level, camera_whitebalance,
+    rgb_camera_matrix -- a 3x4 / 4x4 matrix is cut to [:3, :3])."""
+    with open(path) as fh:
+        d = json.load(fh)
+    if not isinstance(d, dict):
+        raise ValueError('%s: the sidecar must be a JSON object' % path)
+    out = {}
+    for k, v in d.items():
+        k = SIDECAR_ALIASES.get(k, k)
+        if k not in SIDECAR_KEYS:
+            raise ValueError('%s: unknown key %r (known: %s)' % (path, k, ', '.join(SIDECAR_KEYS + tuple(SIDECAR_ALIASES))))
+        if k == 'ccm':
+            m = np.asarray(v, dtype=np.float64)
+            if m.ndim == 2 and m.shape[0] >= 3 and m.shape[1] >= 3:
+                m = m[:3, :3]
+            v = m.reshape(-1).tolist()
+        out[k] = v
+    return out
+
+
+def build_parser():
+    p = argparse.ArgumentParser(prog='python -m eld_amd.denoise', description='Denoise uint16 raw mosaics (.npy) with a trained ELD U-Net.')
+    p.add_argument('inputs', nargs='+', help='uint16 mosaics (.npy, raw_image_visible)')
+    p.add_argument('-o', '--out', required=True, help='output directory')
+    p.add_argument('--ckpt', required=True, help='checkpoint (.pt): the reference dict {"netG": ...} or a U-Net state_dict')
+    p.add_argument('--meta', help='JSON sidecar: cfa, raw_pattern, black_level, white_point, ratio, wb, ccm (or rawpy names)')
+    p.add_argument('--cfa', choices=sorted(PLANES))
+    p.add_argument('--raw-pattern', type=int, nargs=4, metavar='CODE', help='Bayer 2x2 raw_pattern, row-major')
+    p.add_argument('--black', type=float, nargs='+', help='black level(s): 1 or 4 (Bayer), 1 (X-Trans)')
+    p.add_argument('--white', type=float, help='white point (default 16383)')
+    p.add_argument('--ratio', type=float, help='exposure ratio (default 1)')
+    p.add_argument('--wb', type=float, nargs='+', help='white balance: R G B, or the 4 camera_whitebalance values')
+    p.add_argument('--ccm', type=float, nargs=9, help='3x3 camera -> sRGB matrix, row-major')
+    p.add_argument('--bf16', action='store_true', help='run the network in bf16')
+    p.add_argument('--chop', choices=('auto', 'on', 'off'), help='forward_chop tiles (default auto)')
+    p.add_argument('--rounding', choices=ROUNDING, help="write-back rounding (default 'nearest')")
+    return p
+
+
+def parse_args(argv):
+    """-> (inputs, outdir, ckpt, options for load_denoiser / denoise_raw).  Command-line values override the sidecar's."""
+    a = build_parser().parse_args(argv)
+    o = read_sidecar(a.meta) if a.meta else {}
+    cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
+           'ccm': a.ccm, 'rounding': a.rounding, 'precision': 'bf16' if a.bf16 else None,
+           'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
+    o.update({k: v for k, v in cli.items() if v is not None})
+    o.setdefault('cfa', 'bayer')
+    o.setdefault('white_point', 16383)
+    o.setdefault('ratio', 1.0)
+    o.setdefault('precision', 'fp32')
+    o.setdefault('rounding', 'nearest')
+    if o.get('chop') == 'auto':
+        o['chop'] = None
+    _check_cfa(o['cfa'])
+    if o.get('raw_pattern') is not None:
+        o['raw_pattern'] = np.asarray(o['raw_pattern']).reshape(2, 2).tolist()
+    if o.get('black_level') is not None:
+        b = np.asarray(o['black_level'], dtype=np.float64).reshape(-1)
+        o['black_level'] = b.tolist() if b.size > 1 else float(b[0])
+    if o.get('ccm') is not None:
+        o['ccm'] = np.asarray(o['ccm'], dtype=np.float64).reshape(3, 3).tolist()
+    if (o.get('wb') is None) != (o.get('ccm') is None):
+        raise ValueError('the sRGB output needs both --wb and --ccm')
+    return a.inputs, a.out, a.ckpt, o
+
+
+def _save_png(path, hwc):
+    try:
+        from PIL import Image
+    except ImportError:
+        return False
+    Image.fromarray(hwc).save(path)
+    return True
+
+
+def main(argv=None):
+    inputs, outdir, ckpt, o = parse_args(sys.argv[1:] if argv is None else argv)
+    den = load_denoiser(ckpt, cfa=o['cfa'], precision=o['precision'])
+    os.makedirs(outdir, exist_ok=True)
+    kw = {k: o.get(k) for k in ('raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'chop', 'rounding')}
+    for path in inputs:
+        raw = np.load(path)
+        res = denoise_raw(den, raw, o['cfa'], **kw)
+        name = os.path.splitext(os.path.basename(path))[0]
+        np.save(os.path.join(outdir, name + '_denoised.npy'), res['mosaic'])
+        line = '%s -> %s_denoised.npy' % (path, name)
+        if res['srgb'] is not None:
+            hwc = np.ascontiguousarray(np.moveaxis(res['srgb'], 1, -1))          # (N,h,w,3); one frame: (h,w,3)
+            hwc = hwc if raw.ndim == 3 else hwc[0]
+            np.save(os.path.join(outdir, name + '_srgb.npy'), hwc)
+            line += ', %s_srgb.npy' % name
+            if hwc.ndim == 3 and _save_png(os.path.join(outdir, name + '_srgb.png'), hwc):
+                line += ', %s_srgb.png' % name
+        print(line)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

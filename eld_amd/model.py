@@ -289,24 +289,8 @@ class ELDModel:
             self.output = self.netG(self.input)
         return self.output
 
-    def forward_chop(self, x, base=16):              # ELD_model.py:434-467, same tile arithmetic
-        b, c, h, w = x.size()
-        h_half, w_half = h // 2, w // 2
-        shave_h = np.ceil(h_half / base) * base - h_half
-        shave_w = np.ceil(w_half / base) * base - w_half
-        shave_h = shave_h if shave_h >= 10 else shave_h + base
-        shave_w = shave_w if shave_w >= 10 else shave_w + base
-        h_size, w_size = int(h_half + shave_h), int(w_half + shave_w)
-        tiles = [x[:, :, 0:h_size, 0:w_size], x[:, :, 0:h_size, (w - w_size):w],
-                 x[:, :, (h - h_size):h, 0:w_size], x[:, :, (h - h_size):h, (w - w_size):w]]
-        with torch.no_grad():
-            outs = [self.netG(t.contiguous()) for t in tiles]
-        out = x.new_empty(b, outs[0].shape[1], h, w)
-        out[:, :, 0:h_half, 0:w_half] = outs[0][:, :, 0:h_half, 0:w_half]
-        out[:, :, 0:h_half, w_half:w] = outs[1][:, :, 0:h_half, (w_size - w + w_half):w_size]
-        out[:, :, h_half:h, 0:w_half] = outs[2][:, :, (h_size - h + h_half):h_size, 0:w_half]
-        out[:, :, h_half:h, w_half:w] = outs[3][:, :, (h_size - h + h_half):h_size, (w_size - w + w_half):w_size]
-        return out
+    def forward_chop(self, x, base=16):              # ELD_model.py:434-467
+        return forward_chop(self.netG, x, base)
 
     # ---- ELD_model.py:469-475: the training iteration -------------------------------------------------------
     def optimize_parameters(self, **kwargs):
@@ -447,6 +431,28 @@ def illuminance_correct(predict, source):
     """ELD_model.py:138-169: alpha = <p,s>/<p,p> over source != 1 on the [0,1]-clamped prediction, per image (csrc/eval.hip)."""
     from .metrics import illuminance_correct as _ic
     return _ic(predict, source)
+
+
+def forward_chop(net, x, base=16):
+    """ELD_model.py:434-467 with the network as an argument: four overlapping tiles whose sides are multiples of `base`, run without
+    autograd, stitched by the same tile arithmetic (ELDModel.forward_chop; eld_amd.denoise for frames the U-Net cannot take whole)."""
+    b, c, h, w = x.size()
+    h_half, w_half = h // 2, w // 2
+    shave_h = np.ceil(h_half / base) * base - h_half
+    shave_w = np.ceil(w_half / base) * base - w_half
+    shave_h = shave_h if shave_h >= 10 else shave_h + base
+    shave_w = shave_w if shave_w >= 10 else shave_w + base
+    h_size, w_size = int(h_half + shave_h), int(w_half + shave_w)
+    tiles = [x[:, :, 0:h_size, 0:w_size], x[:, :, 0:h_size, (w - w_size):w],
+             x[:, :, (h - h_size):h, 0:w_size], x[:, :, (h - h_size):h, (w - w_size):w]]
+    with torch.no_grad():
+        outs = [net(t.contiguous()) for t in tiles]
+    out = x.new_empty(b, outs[0].shape[1], h, w)
+    out[:, :, 0:h_half, 0:w_half] = outs[0][:, :, 0:h_half, 0:w_half]
+    out[:, :, 0:h_half, w_half:w] = outs[1][:, :, 0:h_half, (w_size - w + w_half):w_size]
+    out[:, :, h_half:h, 0:w_half] = outs[2][:, :, (h_size - h + h_half):h_size, 0:w_half]
+    out[:, :, h_half:h, w_half:w] = outs[3][:, :, (h_size - h + h_half):h_size, (w_size - w + w_half):w_size]
+    return out
 
 
 def eld_model():                                     # models/__init__.py:3-4

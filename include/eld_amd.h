@@ -31,8 +31,10 @@ extern "C" {
  * eld_unet_workspace_bytes of the SAME library; eld_unet_backward_ex accepts an explicit dout after eld_unet_forward_loss_ex and refuses a backward
  * after eld_unet_infer_ex.  A binding must compare eld_abi_version() with the ELD_ABI_VERSION it was written against.
  * 3: ELD_CFA_XTRANS (row noise and colour bias on 9-plane X-Trans inputs) and the cell-statistics calibration entry points
- * (eld_calib_cell_*) exist; every version-2 call behaves as before. */
-#define ELD_ABI_VERSION 3
+ * (eld_calib_cell_*) exist; every version-2 call behaves as before.
+ * 4: the write-back entry points (eld_unpack_raw_bayer_u16 / eld_unpack_raw_xtrans_u16, ELD_ROUND_*), the fused evaluation input stage
+ * (eld_pack_raw_*_u16_gain) and the X-Trans ISP (eld_isp_process_xtrans) exist; every version-3 call behaves as before. */
+#define ELD_ABI_VERSION 4
 
 /* negative = argument errors (hipError_t values are >= 0) */
 #define ELD_EINVAL   (-1)   /* bad shape / flag combination / null pointer                   */
@@ -141,6 +143,40 @@ int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int N, int h, 
  * clip((x - black_level) / (white_point - black_level), 0, 1), float32 arithmetic as NumPy's (one black level for all planes;
  * 1024 / 16383 in the reference).  white_point must exceed black_level.  Bit-exact. */
 int eld_pack_raw_xtrans_u16(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point, void* stream);
+/* The evaluation input stage of dataset/sid_dataset.py:398-409 in one pass: the pack above, then min(max(p * ratios[n], 0), 1) in float32
+ * (bit-identical to NumPy's np.maximum(np.minimum(pack * np.float32(ratio), 1), 0)).  ratios: DEVICE array of N float32 exposure
+ * ratios, one per image. */
+int eld_pack_raw_bayer_u16_gain(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern,
+                                const float* black_level, float white_point, const float* ratios, void* stream);
+int eld_pack_raw_xtrans_u16_gain(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
+                                 const float* ratios, void* stream);
+
+/* Write-back: a packed network output in [0, 1] -> uint16 sensor codes, the inverse of the two packs above (the mosaic half of the
+ * reference's postprocess_bayer / postprocess_xtrans, models/ELD_model.py:41-129).  Per element, with the black level b of the element's
+ * channel and the white point w (integers, 0 <= b < w <= 65535):
+ *     v = double(clip(x, 0, 1)) * (w - b) + b          (exact in double: a 24-bit mantissa times w - b < 2^16, plus b)
+ * then, by `rounding`:
+ *     ELD_ROUND_TRUNC      truncation toward zero -- the reference's assignment of its float64 Bayer expression into the uint16
+ *                          raw_image_visible, bit for bit;
+ *     ELD_ROUND_NEAREST    round half to even;
+ *     ELD_ROUND_TRUNC_F32  fl32(fl32(x * (w - b)) + b) truncated -- the reference's X-Trans expression (its black / white are Python
+ *                          ints, which leave the float32 array float32), bit for bit.
+ * Measured (NumPy, exhaustive over the codes): pack followed by a truncating float64 write-back is NOT the identity -- of the 15872
+ * codes in [512, 16383], 7893 come back one DN low (7676 of 15360 for black 1024); with ELD_ROUND_NEAREST every code in [b, w]
+ * round-trips, for (b, w) = (512, 16383), (1024, 16383), (2048, 16383) and (0, 65535); the float32 X-Trans expression round-trips
+ * those codes too.  A NaN writes b.
+ * Bayer: packed [N,4,h,w] -> mosaic [N,2h,2w], every pixel written; raw_pattern (HOST, 4 ints, a permutation of 0..3) and black_level
+ * (HOST, 4 floats, per channel) as eld_pack_raw_bayer_u16.
+ * X-Trans: packed [N,9,2*(Hm/6),2*(Wm/6)] -> the pixels of the whole 6x6 cells of mosaic [N,Hm,Wm] (eld_pack_xtrans's index map); the
+ * rows / columns beyond the last whole cell are not written, so a mosaic that already holds the input frame keeps its codes there, as
+ * the reference's in-place write into raw_image_visible does.  packed must be 8-byte aligned. */
+#define ELD_ROUND_TRUNC      0
+#define ELD_ROUND_NEAREST    1
+#define ELD_ROUND_TRUNC_F32  2
+int eld_unpack_raw_bayer_u16(const float* packed, uint16_t* mosaic, int N, int h, int w, const int* raw_pattern,
+                             const float* black_level, float white_point, int rounding, void* stream);
+int eld_unpack_raw_xtrans_u16(const float* packed, uint16_t* mosaic, int N, int Hm, int Wm, float black_level, float white_point,
+                              int rounding, void* stream);
 
 /* ---- noise-parameter calibration (eld_amd/calibrate.py; estimators: DESIGN.md "Calibration") ------------------------------
  * Inputs are uint16 Bayer sensor mosaics [F,Hm,Wm] with even sides; packed channel of pixel (y,x) = raw_pattern[y&1][x&1] (HOST
@@ -316,6 +352,13 @@ int eld_illuminance_correct(const float* predict, const float* source, float* ou
  * camera response by piecewise-linear interpolation of (crf_E, crf_f), ascending crf_E (torchinterp1d's rule). */
 int eld_isp_process(const float* bayer, const float* wbs, const float* ccms, float* out, int N, int H, int W, float gamma,
                     const float* crf_E, const float* crf_f, int crf_n, void* stream);
+/* The same pipeline on X-Trans: packed (N,9,H,W) in RawPacker.pack_raw_xtrans's planes (one packed pixel = one 3x3 mosaic block) ->
+ * out (N,3,H,W), k/255.  wbs (N,3) R, G, B gains, applied by plane colour (R: planes 0, 3; G: 1, 5, 6, 7, 8; B: 2, 4 -- xtrans.h
+ * XT_COLOUR), clamp, then per colour the mean of its planes summed in ascending plane order in float32 and divided by 2 / 5 / 2:
+ * R = (p0 + p3) / 2, G = ((((p1 + p5) + p6) + p7) + p8) / 5, B = (p2 + p4) / 2; then the CCM, clamp and gamma / CRF quantiser
+ * of eld_isp_process.  This is the reference's `process` applied to X-Trans binning, not LibRaw's demosaic. */
+int eld_isp_process_xtrans(const float* packed, const float* wbs, const float* ccms, float* out, int N, int H, int W, float gamma,
+                           const float* crf_E, const float* crf_f, int crf_n, void* stream);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
