@@ -23,6 +23,10 @@ NOISE_PARAMS_DTYPE = np.dtype([
     ('q_step', '<f4'), ('saturation', '<f4'), ('ratio', '<f4'), ('color_bias', '<f4', (4,)),
     ('sample_id_lo', '<u4'), ('sample_id_hi', '<u4'), ('reserved', '<u4', (2,))])
 assert NOISE_PARAMS_DTYPE.itemsize == 64
+# numpy mirrors of struct EldPoolFrame and struct EldCropRecord (16 bytes each)
+POOL_FRAME_DTYPE = np.dtype([('offset', '<u8'), ('Hm', '<i4'), ('Wm', '<i4')])
+CROP_RECORD_DTYPE = np.dtype([('frame', '<i4'), ('y0', '<i4'), ('x0', '<i4'), ('ratio', '<f4')])
+assert POOL_FRAME_DTYPE.itemsize == 16 and CROP_RECORD_DTYPE.itemsize == 16
 
 _vp, _i, _u32, _u64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 
@@ -46,6 +50,8 @@ SIGNATURES = {
     'eld_pack_raw_xtrans_u16_gain': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
     'eld_unpack_raw_bayer_u16': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _i, _vp]),
     'eld_unpack_raw_xtrans_u16': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _i, _vp]),
+    'eld_crop_pack_raw_bayer_u16': (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp, _vp]),
+    'eld_crop_pack_raw_xtrans_u16': (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _i, _i, _i, _f, _f, _vp, _vp]),
     'eld_augment': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _u32, _vp]),
     'eld_calib_bias_stats_workspace_bytes': (_sz, [_i, _i]),
     'eld_calib_bias_stats': (_i, [_vp, _i, _i, _i, C.POINTER(C.c_int), _vp, _vp, _vp, _sz, _vp]),
@@ -107,7 +113,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 4         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
+ABI_VERSION = 5         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
 PHILOX_ROUNDS = 7      # the sampler's generator: Philox4x32-7 (csrc/philox.h); checked against the library at load
 
 

@@ -377,7 +377,7 @@ class NoiseModelBase:  # same name / role as noise.py:148
 class NoiseModel(NoiseModelBase):
     last_instance = None
 
-    def __init__(self, model='g', cameras=None, include=None, exclude=None, cfa='bayer'):
+    def __init__(self, model='g', cameras=None, include=None, exclude=None, cfa='bayer', param_dir=None):
         super().__init__()
         assert cfa in ['bayer', 'xtrans']                   # noise.py:177
         assert include is None or exclude is None           # noise.py:178
@@ -387,7 +387,7 @@ class NoiseModel(NoiseModelBase):
         if exclude is not None:                             # noise.py:183-185
             exclude_camera = set([self.cameras[exclude]])
             self.cameras = list(set(self.cameras) - exclude_camera)
-        self.param_dir = join('camera_params', 'release')   # noise.py:187
+        self.param_dir = param_dir or join('camera_params', 'release')   # noise.py:187 (param_dir: where eld_amd.calibrate wrote <camera>_params.npy)
         print('[i] NoiseModel with {}'.format(self.param_dir))        # noise.py:189-191
         print('[i] cameras: {}'.format(self.cameras))
         print('[i] using noise model {}'.format(model))

@@ -33,8 +33,10 @@ extern "C" {
  * 3: ELD_CFA_XTRANS (row noise and colour bias on 9-plane X-Trans inputs) and the cell-statistics calibration entry points
  * (eld_calib_cell_*) exist; every version-2 call behaves as before.
  * 4: the write-back entry points (eld_unpack_raw_bayer_u16 / eld_unpack_raw_xtrans_u16, ELD_ROUND_*), the fused evaluation input stage
- * (eld_pack_raw_*_u16_gain) and the X-Trans ISP (eld_isp_process_xtrans) exist; every version-3 call behaves as before. */
-#define ELD_ABI_VERSION 4
+ * (eld_pack_raw_*_u16_gain) and the X-Trans ISP (eld_isp_process_xtrans) exist; every version-3 call behaves as before.
+ * 5: the frame-pool crop entry points (eld_crop_pack_raw_bayer_u16 / eld_crop_pack_raw_xtrans_u16, EldPoolFrame, EldCropRecord) exist; every
+ * version-4 call behaves as before. */
+#define ELD_ABI_VERSION 5
 
 /* negative = argument errors (hipError_t values are >= 0) */
 #define ELD_EINVAL   (-1)   /* bad shape / flag combination / null pointer                   */
@@ -177,6 +179,35 @@ int eld_unpack_raw_bayer_u16(const float* packed, uint16_t* mosaic, int N, int h
                              const float* black_level, float white_point, int rounding, void* stream);
 int eld_unpack_raw_xtrans_u16(const float* packed, uint16_t* mosaic, int N, int Hm, int Wm, float black_level, float white_point,
                               int rounding, void* stream);
+
+/* ---- frame pool: training patches cut from device-resident mosaics (eld_amd/framepool.py) ----------------------
+ * What util/lmdb_data.py::create_lmdb_train stores in its patch databases, made on the device from the sensor's own uint16 mosaics:
+ * pack (:24-98), x ratio, clip, x 65535, astype(uint16) (:201-210), bit for bit.  The dtypes are the reference's and differ by CFA:
+ *   Bayer    float32 throughout: p = clip((float32(u) - b_k) / (white - b_k), 0, 1); p = clip(fl32(p * ratio), 0, 1);
+ *            code = trunc(fl32(p * 65535))
+ *   X-Trans  p is the same float32 value (one black level); the reference packs it into a float64 array (:62), so
+ *            code = trunc(clip(double(p) * double(ratio), 0, 1) * 65535.0), both products in float64
+ * ratio 1 gives the codes of the chain without the ratio multiply (x * 1 is exact).
+ *   pool     one flat DEVICE uint16 buffer of pool_elems codes, 16-byte aligned, holding F mosaics
+ *   frames   DEVICE table of F entries: element offset of the mosaic in the pool (even), its sides Hm x Wm (Wm even).  The packed extent of
+ *            a frame is (Hm/2) x (Wm/2) for Bayer and 2*(Hm/6) x 2*(Wm/6) for X-Trans (whole 6x6 cells only, eld_pack_xtrans's index map)
+ *   max_h, max_w   HOST: the largest packed extent over the frames (what the entry can check a patch size against)
+ *   recs     DEVICE array of B records (B <= 65535): frame index, y0, x0 in PACKED coordinates -- any values, odd ones included -- and the ratio
+ *   out      DEVICE uint16 [B, C, ph, pw], C = 4 (R, G1, B, G2 by raw_pattern, as eld_pack_raw_bayer_u16) or 9; 16-byte aligned
+ * ELD_EINVAL before any launch for what the host can see: zero or negative sizes, ph > max_h or pw > max_w, a raw_pattern that is not a
+ * permutation of 0..3, white_point <= a black level or > 65535, null or misaligned pointers.  The records and the frame table are device
+ * memory: a record that does not describe a patch inside its frame, or a frame entry that does not lie inside the pool, makes the kernel
+ * SKIP that patch (its slice of `out` is not written); nothing outside the pool is ever read.
+ * pw % 8 == 0 takes the 16-byte-store kernel; per patch it reads 16 bytes per load when (offset + 2 x0) % 8 == 0 (X-Trans: offset + 3 x0)
+ * and Wm % 8 == 0, and 4 bytes per load otherwise.  Any other pw takes a one-code-per-lane kernel. */
+typedef struct EldPoolFrame { uint64_t offset; int32_t Hm, Wm; } EldPoolFrame;                 /* 16 bytes */
+typedef struct EldCropRecord { int32_t frame, y0, x0; float ratio; } EldCropRecord;            /* 16 bytes */
+int eld_crop_pack_raw_bayer_u16(const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int max_h, int max_w,
+                                const EldCropRecord* recs, int B, int ph, int pw, const int* raw_pattern, const float* black_level,
+                                float white_point, uint16_t* out, void* stream);
+int eld_crop_pack_raw_xtrans_u16(const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int max_h, int max_w,
+                                 const EldCropRecord* recs, int B, int ph, int pw, float black_level, float white_point, uint16_t* out,
+                                 void* stream);
 
 /* ---- noise-parameter calibration (eld_amd/calibrate.py; estimators: DESIGN.md "Calibration") ------------------------------
  * Inputs are uint16 Bayer sensor mosaics [F,Hm,Wm] with even sides; packed channel of pixel (y,x) = raw_pattern[y&1][x&1] (HOST
