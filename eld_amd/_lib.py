@@ -14,6 +14,7 @@ AUG_NOTRANSPOSE = 256
 CFA_XTRANS = 512
 IN_F32, IN_U16 = 0, 1
 ROUND_TRUNC, ROUND_NEAREST, ROUND_TRUNC_F32 = 0, 1, 2      # write-back rounding (eld_unpack_raw_*_u16)
+RENDER_SRGB8, RENDER_LINEAR_F32 = 0, 1                      # out_mode of eld_render_bayer / eld_render_xtrans
 NPLANES = 6
 PLANE = {'counts': 0, 'n_shot': 1, 'n_read': 2, 't_tl': 3, 'n_row': 4, 'u_q': 5}
 
@@ -82,6 +83,9 @@ SIGNATURES = {
     'eld_debug_ws_state_entries': (_i, []),
     'eld_isp_process': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     'eld_isp_process_xtrans': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    'eld_render_bayer': (_i, [_vp, C.POINTER(C.c_int), _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    'eld_render_xtrans': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    'eld_debug_xtrans_demosaic_tables': (_i, [C.POINTER(C.c_int), _i]),
     'eld_quality_assess_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'eld_quality_assess': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
     'eld_quality_assess_images': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
@@ -113,7 +117,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 5         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
+ABI_VERSION = 6         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
 PHILOX_ROUNDS = 7      # the sampler's generator: Philox4x32-7 (csrc/philox.h); checked against the library at load
 
 

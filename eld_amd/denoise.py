@@ -6,7 +6,9 @@ denoiser for it (train_syn.py through the plugins).  Every device stage is a HIP
     network       the U-Net, whole frame when the packed sides are multiples of 16, else the reference's forward_chop tiles
     write-back    the packed output -> uint16 codes (eld_unpack_raw_*_u16; the mosaic half of postprocess_bayer / postprocess_xtrans,
                   models/ELD_model.py:41-129)
-    sRGB          util/process.py `process` (eld_isp_process; X-Trans: eld_isp_process_xtrans, the same pipeline on X-Trans binning)
+    sRGB          util/process.py `process` (eld_isp_process; X-Trans: eld_isp_process_xtrans, the same pipeline on X-Trans binning) at
+                  packed resolution, or with srgb_size='full' the same pipeline behind a demosaic at mosaic resolution
+                  (eld_render_bayer: Malvar-He-Cutler; eld_render_xtrans: normalised convolution on colour differences)
 
 Write-back rounding.  Per element v = float64(clip(x, 0, 1)) * (white - black) + black (exact).  rounding='reference' truncates as the
 reference's assignment into the uint16 raw_image_visible does (Bayer: the float64 expression; X-Trans: the reference evaluates it in
@@ -16,10 +18,10 @@ every code in [black, white] round-trips, for (black, white) = (512, 16383), (10
 
 Raw files are not decoded here (no rawpy): mosaics arrive as arrays (`raw.raw_image_visible`), and the values rawpy reports
 (raw_pattern, black_level_per_channel, camera_whitebalance, rgb_camera_matrix[:3, :3]) as arguments or a JSON sidecar.
-LibRaw's demosaic and rendering are out of scope: the sRGB output is the reference's `process` at packed resolution.
+The sRGB output is the reference's `process`: at packed resolution by default, at mosaic resolution with --srgb-size full.
 
     python -m eld_amd.denoise --ckpt model.pt --cfa xtrans --black 1024 --white 16383 --ratio 100 [--wb R G B] [--ccm 9 values] [--bf16] \\
-        in.npy [more.npy] -o outdir
+        [--srgb-size full] in.npy [more.npy] -o outdir
 """
 import argparse
 import ctypes
@@ -34,6 +36,7 @@ from . import _lib as L
 
 PLANES = {'bayer': 4, 'xtrans': 9}
 ROUNDING = ('nearest', 'reference')
+SRGB_SIZES = ('packed', 'full')
 DEFAULT_BLACK = {'bayer': 512, 'xtrans': 1024}      # SID Sony (rawpy black_level_per_channel) / the reference's X-Trans constant
 DEFAULT_PATTERN = ((0, 1), (3, 2))                   # RGGB as rawpy codes (R 0, G1 1, B 2, G2 3)
 
@@ -241,7 +244,7 @@ def run_network(denoiser, x, chop=None):
 
 
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
-                chop=None, rounding='nearest'):
+                chop=None, rounding='nearest', srgb_size='packed', linear=False):
     """Denoise uint16 sensor mosaics with a trained U-Net.
 
     mosaic_u16  NumPy uint16 array or CUDA uint16 / int16-view tensor, (Hm, Wm) or (N, Hm, Wm) -- rawpy's raw_image_visible.
@@ -252,6 +255,9 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                 camera_whitebalance (divided by its green); ccm rawpy's rgb_camera_matrix[:3, :3].  CRF: None (gamma 2.2) or (E, fs).
     chop        None: whole frame when the packed sides are multiples of 16, else the reference's forward_chop; True / False force it.
     rounding    'nearest' (default: every code in [black, white] round-trips) or 'reference' (the reference's truncation, bit for bit).
+    srgb_size   'packed' (default): the rendering above.  'full': the same gains, matrix and tone curve behind a demosaic, at mosaic
+                resolution (N,3,Hm,Wm) -- X-Trans: the whole 6x6 cells, as the write-back; needs wb and ccm.
+    linear      with srgb_size='full', also 'linear': float32 (N,3,Hm,Wm) linear RGB after the colour matrix (no clamp, no tone curve).
 
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
@@ -262,6 +268,12 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         raise ValueError('rounding must be one of %r, got %r' % (ROUNDING, rounding))
     if chop not in (None, True, False):
         raise ValueError('chop must be None, True or False, got %r' % (chop,))
+    if not isinstance(srgb_size, str) or srgb_size not in SRGB_SIZES:
+        raise ValueError('srgb_size must be one of %r, got %r' % (SRGB_SIZES, srgb_size))
+    if srgb_size == 'full' and (wb is None or ccm is None):
+        raise ValueError("srgb_size='full' renders sRGB: it needs both wb and ccm")
+    if linear and srgb_size != 'full':
+        raise ValueError("linear=True needs srgb_size='full'")
     kind, batched = _as_u16(mosaic_u16)
     shape = tuple(mosaic_u16.shape)
     N = shape[0] if batched else 1
@@ -276,6 +288,8 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     if denoiser.out_channels != PLANES[cfa]:
         raise ValueError('the network writes %d planes, the %s write-back needs %d' % (denoiser.out_channels, cfa, PLANES[cfa]))
     wbs, ccms = _colour(cfa, wb, ccm, N)
+    if srgb_size == 'full' and cfa == 'bayer' and (pat[0] & 1) != (pat[3] & 1):
+        raise ValueError('the full-size render needs a Bayer raw_pattern with its greens on a diagonal, got %r' % (raw_pattern,))
 
     import torch
     dev = next(denoiser.net.parameters()).device
@@ -292,8 +306,17 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     out = run_network(denoiser, x, chop)
     mosaic = t3.clone()                   # X-Trans: the borders outside whole cells keep the input's codes
     write_back(out, mosaic, cfa, pat, blk, white, rounding)
-    srgb = None
-    if wbs is not None:
+    srgb = lin = None
+    if wbs is not None and srgb_size == 'full':
+        from .isp import render_bayer, render_xtrans
+        wt, ct = torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev)
+        if cfa == 'bayer':
+            srgb = render_bayer(out, pat, wt, ct, CRF=CRF)
+            lin = render_bayer(out, pat, wt, ct, linear=True) if linear else None
+        else:
+            srgb = render_xtrans(out, wt, ct, CRF=CRF)
+            lin = render_xtrans(out, wt, ct, linear=True) if linear else None
+    elif wbs is not None:
         from .isp import process, process_xtrans
         fn = process if cfa == 'bayer' else process_xtrans
         rgb = fn(out, torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev), CRF=CRF)
@@ -301,15 +324,21 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     if not batched:
         mosaic = mosaic[0]
     if kind == 'numpy':
-        return {'packed': out.cpu().numpy(), 'mosaic': mosaic.cpu().numpy().view(np.uint16),
-                'srgb': None if srgb is None else srgb.cpu().numpy()}
-    return {'packed': out, 'mosaic': mosaic, 'srgb': srgb}
+        res = {'packed': out.cpu().numpy(), 'mosaic': mosaic.cpu().numpy().view(np.uint16),
+               'srgb': None if srgb is None else srgb.cpu().numpy()}
+        if lin is not None:
+            res['linear'] = lin.cpu().numpy()
+        return res
+    res = {'packed': out, 'mosaic': mosaic, 'srgb': srgb}
+    if lin is not None:
+        res['linear'] = lin
+    return res
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
 SIDECAR_ALIASES = {'black_level_per_channel': 'black_level', 'white_level': 'white_point', 'camera_whitebalance': 'wb',
                    'rgb_camera_matrix': 'ccm', 'black': 'black_level', 'white': 'white_point'}
-SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop')
+SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size')
 
 
 def read_sidecar(path):
@@ -349,6 +378,7 @@ def build_parser():
     p.add_argument('--bf16', action='store_true', help='run the network in bf16')
     p.add_argument('--chop', choices=('auto', 'on', 'off'), help='forward_chop tiles (default auto)')
     p.add_argument('--rounding', choices=ROUNDING, help="write-back rounding (default 'nearest')")
+    p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
     return p
 
 
@@ -357,7 +387,7 @@ def parse_args(argv):
     a = build_parser().parse_args(argv)
     o = read_sidecar(a.meta) if a.meta else {}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
-           'ccm': a.ccm, 'rounding': a.rounding, 'precision': 'bf16' if a.bf16 else None,
+           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'precision': 'bf16' if a.bf16 else None,
            'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
     o.update({k: v for k, v in cli.items() if v is not None})
     o.setdefault('cfa', 'bayer')
@@ -365,6 +395,9 @@ def parse_args(argv):
     o.setdefault('ratio', 1.0)
     o.setdefault('precision', 'fp32')
     o.setdefault('rounding', 'nearest')
+    o.setdefault('srgb_size', 'packed')
+    if o['srgb_size'] not in SRGB_SIZES:
+        raise ValueError('srgb_size must be one of %r, got %r' % (SRGB_SIZES, o['srgb_size']))
     if o.get('chop') == 'auto':
         o['chop'] = None
     _check_cfa(o['cfa'])
@@ -377,6 +410,8 @@ def parse_args(argv):
         o['ccm'] = np.asarray(o['ccm'], dtype=np.float64).reshape(3, 3).tolist()
     if (o.get('wb') is None) != (o.get('ccm') is None):
         raise ValueError('the sRGB output needs both --wb and --ccm')
+    if o['srgb_size'] == 'full' and o.get('wb') is None:
+        raise ValueError('--srgb-size full needs --wb and --ccm')
     return a.inputs, a.out, a.ckpt, o
 
 
@@ -393,7 +428,7 @@ def main(argv=None):
     inputs, outdir, ckpt, o = parse_args(sys.argv[1:] if argv is None else argv)
     den = load_denoiser(ckpt, cfa=o['cfa'], precision=o['precision'])
     os.makedirs(outdir, exist_ok=True)
-    kw = {k: o.get(k) for k in ('raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'chop', 'rounding')}
+    kw = {k: o.get(k) for k in ('raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'chop', 'rounding', 'srgb_size')}
     for path in inputs:
         raw = np.load(path)
         res = denoise_raw(den, raw, o['cfa'], **kw)

@@ -1,6 +1,9 @@
 """Raw -> sRGB ISP on the device: the reference's util/process.py:52-68 `process` (gains, binning, CCM, gamma / camera
 response, 8-bit quantisation) as one HBM-bound HIP kernel (csrc/eval.hip eld_isp_process).  Used by the sRGB training /
-evaluation stages (train_syn.py:55-58, models/ELD_model.py:230-233), and its X-Trans counterpart (process_xtrans) for eld_amd.denoise."""
+evaluation stages (train_syn.py:55-58, models/ELD_model.py:230-233), and its X-Trans counterpart (process_xtrans) for eld_amd.denoise.
+render_bayer / render_xtrans are the same pipeline at MOSAIC resolution: a demosaic (csrc/demosaic.hip) in place of the binning."""
+import ctypes
+
 import numpy as np
 
 from . import _lib as L
@@ -50,4 +53,49 @@ def process_xtrans(packed, wbs, cam2rgbs, gamma=2.2, CRF=None):
     E, fs, n = _crf(CRF, dev)
     L.check(L.lib().eld_isp_process_xtrans(L.dptr(x), L.dptr(wbs), L.dptr(ccm), L.dptr(out), N, H, W, float(gamma), L.dptr(E), L.dptr(fs), n,
                                            L.cur_stream()), 'eld_isp_process_xtrans')
+    return out
+
+
+def _render_out(x, planes, wbs, cam2rgbs, linear, gains):
+    import torch
+    if not (x.is_cuda and x.dim() == 4 and x.shape[1] == planes):
+        raise ValueError('packed must be a CUDA (N,%d,h,w) tensor, got %s on %s' % (planes, tuple(x.shape), x.device))
+    dev = x.device
+    x = x.contiguous().float()
+    N, _, h, w = x.shape
+    wbs = torch.as_tensor(wbs, dtype=torch.float32, device=dev).reshape(N, gains).contiguous()
+    ccm = None if cam2rgbs is None else torch.as_tensor(cam2rgbs, dtype=torch.float32, device=dev).reshape(N, 9).contiguous()
+    if ccm is None and not linear:
+        raise ValueError('the sRGB render needs cam2rgbs (only linear=True renders camera RGB)')
+    f = planes // 4 + 1                                      # mosaic sites per packed pixel and side: Bayer 2, X-Trans 3
+    out = torch.empty((N, 3, f * h, f * w), dtype=torch.float32 if linear else torch.uint8, device=dev)
+    return x, wbs, ccm, out, L.RENDER_LINEAR_F32 if linear else L.RENDER_SRGB8
+
+
+def render_bayer(bayer_images, raw_pattern, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False):
+    """`process` at mosaic resolution (csrc/demosaic.hip eld_render_bayer): gains and clamp, Malvar-He-Cutler demosaic with mirrored
+    borders, then the CCM / gamma or CRF / quantiser of `process`.  bayer_images CUDA (N,4,h,w) float32 in the planes of raw_pattern (2x2
+    rawpy codes, R 0, G1 1, B 2, G2 3, as the write-back takes it); wbs (N,4) by plane; cam2rgbs (N,3,3), or None with linear=True.
+    Returns CUDA (N,3,2h,2w): uint8 codes, or with linear=True float32 linear RGB after the CCM (no clamp, no gamma)."""
+    x, wbs, ccm, out, mode = _render_out(bayer_images, 4, wbs, cam2rgbs, linear, 4)
+    pat = [int(v) for v in np.asarray(raw_pattern).reshape(-1)]
+    if len(pat) != 4:
+        raise ValueError('raw_pattern must hold 2x2 codes, got %r' % (raw_pattern,))
+    E, fs, n = _crf(CRF, x.device)
+    N, _, h, w = x.shape
+    L.check(L.lib().eld_render_bayer(L.dptr(x), (ctypes.c_int * 4)(*pat), L.dptr(wbs), L.dptr(ccm), L.dptr(out), mode, N, h, w, float(gamma),
+                                     L.dptr(E), L.dptr(fs), n, L.cur_stream()), 'eld_render_bayer')
+    return out
+
+
+def render_xtrans(packed, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False):
+    """`process_xtrans` at mosaic resolution (csrc/demosaic.hip eld_render_xtrans): gains by plane colour and clamp, a two-stage normalised
+    convolution on colour differences (G from the 3x3, R - G and B - G from the 5x5 neighbourhood, windows clipped to the image), then
+    the tail of `process`.  packed CUDA (N,9,h,w) float32 with even h and w (whole 6x6 cells); wbs (N,3); cam2rgbs (N,3,3), or None with
+    linear=True.  Returns CUDA (N,3,3h,3w): uint8 codes, or with linear=True float32 linear RGB after the CCM."""
+    x, wbs, ccm, out, mode = _render_out(packed, 9, wbs, cam2rgbs, linear, 3)
+    E, fs, n = _crf(CRF, x.device)
+    N, _, h, w = x.shape
+    L.check(L.lib().eld_render_xtrans(L.dptr(x), L.dptr(wbs), L.dptr(ccm), L.dptr(out), mode, N, h, w, float(gamma), L.dptr(E), L.dptr(fs), n,
+                                      L.cur_stream()), 'eld_render_xtrans')
     return out

@@ -35,8 +35,10 @@ extern "C" {
  * 4: the write-back entry points (eld_unpack_raw_bayer_u16 / eld_unpack_raw_xtrans_u16, ELD_ROUND_*), the fused evaluation input stage
  * (eld_pack_raw_*_u16_gain) and the X-Trans ISP (eld_isp_process_xtrans) exist; every version-3 call behaves as before.
  * 5: the frame-pool crop entry points (eld_crop_pack_raw_bayer_u16 / eld_crop_pack_raw_xtrans_u16, EldPoolFrame, EldCropRecord) exist; every
- * version-4 call behaves as before. */
-#define ELD_ABI_VERSION 5
+ * version-4 call behaves as before.
+ * 6: the full-resolution renders (eld_render_bayer / eld_render_xtrans, ELD_RENDER_*) and eld_debug_xtrans_demosaic_tables exist; every
+ * version-5 call behaves as before. */
+#define ELD_ABI_VERSION 6
 
 /* negative = argument errors (hipError_t values are >= 0) */
 #define ELD_EINVAL   (-1)   /* bad shape / flag combination / null pointer                   */
@@ -390,6 +392,44 @@ int eld_isp_process(const float* bayer, const float* wbs, const float* ccms, flo
  * of eld_isp_process.  This is the reference's `process` applied to X-Trans binning, not LibRaw's demosaic. */
 int eld_isp_process_xtrans(const float* packed, const float* wbs, const float* ccms, float* out, int N, int H, int W, float gamma,
                            const float* crf_E, const float* crf_f, int crf_n, void* stream);
+
+/* ---- full-resolution renders (csrc/demosaic.hip) ------------------------------------------------------------------
+ * The packed network output -> planar RGB (N,3,Hm,Wm) at MOSAIC resolution.  Bayer: packed (N,4,h,w), Hm = 2h, Wm = 2w, raw_pattern
+ * (HOST, 4 ints, a permutation of 0..3 with the greens on a diagonal) as eld_unpack_raw_bayer_u16 takes it, wbs (N,4) by plane.
+ * X-Trans: packed (N,9,h,w), h and w even (whole 6x6 cells, as the write-back), Hm = 3h, Wm = 3w, wbs (N,3) R, G, B by plane colour.
+ * ccms (N,3,3) row-major or NULL.  out_mode:
+ *     ELD_RENDER_SRGB8        uint8 codes k of the quantiser of eld_isp_process (which writes k / 255); ccms NULL = the identity;
+ *     ELD_RENDER_LINEAR_F32   float32 after the CCM (after the demosaic when ccms is NULL): no second clamp, no gamma, no quantiser.
+ * Per mosaic site, float32, one rounding per operation:
+ *   1. v = min(max(p * gain, 0), 1), as eld_isp_process / eld_isp_process_xtrans.
+ *   2. demosaic -> camera RGB at every site; the colour sampled at a site passes through unchanged.
+ *      Bayer, Malvar-He-Cutler (2004), coefficients in eighths; borders mirrored without repeating the edge (index -1 -> 1, -2 -> 2,
+ *      H -> H - 2), which preserves CFA parity; with c the site's own value and N, S, W, E / NN, SS, WW, EE / NW, NE, SW, SE its neighbours
+ *      at distance 1 / 2 / diagonal:
+ *          S1 = (N+S)+(W+E)    S2 = (NN+SS)+(WW+EE)    D = (NW+NE)+(SW+SE)
+ *          G at R/B site            : ((4c + 2*S1) - S2) * 0.125
+ *          R at G site, R left/right: (((5c + 4*(W+E)) + 0.5*(NN+SS)) - (D + (WW+EE))) * 0.125     (B likewise; up/down case transposed)
+ *          R at B site, B at R site : ((6c + 2*D) - 1.5*S2) * 0.125
+ *      X-Trans, normalised convolution on colour differences, windows clipped to the image; sums start at 0 and add w * value tap by
+ *      tap in raster order (dy outer, dx inner), the weight sums are exact integers, the division is correctly rounded:
+ *          stage 1  G^ = v at G sites, else (sum w*v over the G sites of the clipped 3x3) / (sum w),  w = [1 2 1] x [1 2 1]
+ *          stage 2  for c in {R, B}, at sites not of colour c:
+ *                   c^ = G^ + (sum w*(v - G^) over the c sites of the clipped 5x5) / (sum w),         w = [1 2 3 2 1] x [1 2 3 2 1]
+ *   3. out[c] = ((r*m[c][0]) + g*m[c][1]) + b*m[c][2]; ELD_RENDER_SRGB8 then clamps to [0,1], applies the gamma table / pow / CRF and
+ *      quantises exactly as eld_isp_process does (the same device function).
+ * ELD_EINVAL before any launch: a null packed / wbs / out / raw_pattern, packed or out not 16-byte aligned, wbs / ccms / crf_E / crf_f
+ * not 4-byte aligned, N < 1 or N > 65535, h < 2 or w < 2 (mosaic sides below 4), an odd X-Trans h or w, a raw_pattern that is not such a
+ * permutation, an unknown out_mode, gamma <= 0, crf_n < 0 or crf_n == 1, crf_n >= 2 without crf_E / crf_f. */
+#define ELD_RENDER_SRGB8       0
+#define ELD_RENDER_LINEAR_F32  1
+int eld_render_bayer(const float* packed, const int* raw_pattern, const float* wbs, const float* ccms, void* out, int out_mode,
+                     int N, int h, int w, float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream);
+int eld_render_xtrans(const float* packed, const float* wbs, const float* ccms, void* out, int out_mode,
+                      int N, int h, int w, float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream);
+/* Test hook (HOST, no device work): the per-phase tables the X-Trans render is compiled with, 36 rows (phase = 6 * row + col of the cell)
+ * of 8 ints: colour (R 0, G 1, B 2), packed plane, then for G (3x3 window) and for R and B (5x5 window) the bit mask of the window taps that
+ * hold the colour (bit = raster index of the tap) and the sum of their weights.  n = ints available in out (>= 288). */
+int eld_debug_xtrans_demosaic_tables(int* out, int n);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
