@@ -204,6 +204,161 @@ def flat_stats_from_sums(sums, black_level, white_level, color_bias, Hm, Wm):
     return {'mu': mu, 'var': var.reshape(P, 4), 'usable': usable}
 
 
+# ---- the same derivations over the unflagged sites of a defect map (count-aware) -------------------------------------------------------
+def _masked_tail(se2, n_row, dev_row, n):
+    """rho, g_scale, R_scale from sum e^2 (F,), per-row counts (Hm,), per-row sums of e (F,Hm) and the site count: the row offset is the
+    mean of e over the row's unflagged sites, and the read noise averaged into it is (sum t^2 / n) / n_y, row by row."""
+    if np.any(n_row == 0):
+        raise ValueError('row %d has no unflagged site: the defect map flags a whole row' % int(np.flatnonzero(n_row == 0)[0]))
+    rho = dev_row / n_row[None, :]
+    st2 = se2 - np.sum(n_row[None, :] * rho * rho, axis=1)
+    g_scale = np.sqrt(se2 / n)
+    R_scale = np.sqrt(np.maximum(0.0, np.mean(rho * rho, axis=1) - (st2 / n) * np.mean(1.0 / n_row)))
+    return rho, g_scale, R_scale
+
+
+def bias_stats_from_sums_masked(chan_sums, row_sums, raw_pattern, black_level, Hm, Wm, chan_counts=None, row_counts=None):
+    """bias_stats_from_sums over the unflagged sites only: chan_sums / row_sums are the sums over those sites, chan_counts (4,) and
+    row_counts (Hm,2) (even / odd columns) their numbers.  Without counts (or with every site counted) it IS bias_stats_from_sums: the
+    same call, hence the same bits."""
+    pat, black = _pattern(raw_pattern), _black(black_level)
+    if chan_counts is None or (np.all(np.asarray(chan_counts) == Hm * Wm // 4) and np.all(np.asarray(row_counts) == Wm // 2)):
+        return bias_stats_from_sums(chan_sums, row_sums, pat, black, Hm, Wm)
+    chan_sums, row_sums = np.asarray(chan_sums), np.asarray(row_sums)
+    nc, nr = np.asarray(chan_counts, np.int64).reshape(4), np.asarray(row_counts, np.int64).reshape(Hm, 2)
+    if np.any(nc == 0):
+        raise ValueError('channel %d has no unflagged site' % int(np.flatnonzero(nc == 0)[0]))
+    F = chan_sums.shape[0]
+    mean_u = chan_sums[:, :, 0].astype(np.float64) / nc[None, :]
+    cb = mean_u - black[None, :]
+    se2 = np.zeros(F)
+    for f in range(F):
+        se2[f] = sum(float(int(nc[c]) * int(chan_sums[f, c, 1]) - int(chan_sums[f, c, 0]) ** 2) / int(nc[c]) for c in range(4))
+    par = np.arange(Hm) & 1
+    dev_row = (row_sums[:, :, 0] - nr[None, :, 0] * mean_u[:, pat[par, 0]]) + (row_sums[:, :, 1] - nr[None, :, 1] * mean_u[:, pat[par, 1]])
+    rho, g_scale, R_scale = _masked_tail(se2, nr.sum(axis=1), dev_row, int(nc.sum()))
+    return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
+
+
+def xtrans_bias_stats_from_cell_sums_masked(cell_sums, row_sums, raw_pattern, black_level, Hm, Wm, cell_n=None, row_n=None):
+    """xtrans_bias_stats_from_cell_sums over the unflagged sites only: cell_n (6,6) and row_n (Hm,6) count them per cell and per row and
+    column class.  Without counts (or with every site counted) it IS xtrans_bias_stats_from_cell_sums."""
+    pat, black = _xpattern(raw_pattern), _black(black_level)
+    if cell_n is None or (np.array_equal(cell_n, cell_counts(Hm, Wm)) and np.array_equal(row_n, np.broadcast_to(cell_counts(1, Wm)[0], (Hm, XT_PERIOD)))):
+        return xtrans_bias_stats_from_cell_sums(cell_sums, row_sums, pat, black, Hm, Wm)
+    cs, rs = np.asarray(cell_sums).reshape(-1, XT_PERIOD, XT_PERIOD, 2), np.asarray(row_sums)
+    ncell, nrow = np.asarray(cell_n, np.int64).reshape(XT_PERIOD, XT_PERIOD), np.asarray(row_n, np.int64).reshape(Hm, XT_PERIOD)
+    F = cs.shape[0]
+    bcell, col = black[pat], CODE_COLOUR[pat]
+    for k in range(3):
+        if ncell[col == k].sum() == 0:
+            raise ValueError('colour %d has no unflagged site' % k)
+    S = cs[..., 0].astype(np.float64)
+    cb = np.stack([np.sum((S - ncell * bcell)[:, col == k], axis=1) / ncell[col == k].sum() for k in range(3)], axis=1)
+    se2 = np.zeros(F)
+    for f in range(F):
+        for r in range(XT_PERIOD):
+            for c in range(XT_PERIOD):
+                m, s1, q = int(ncell[r, c]), int(cs[f, r, c, 0]), int(cs[f, r, c, 1])
+                if m:
+                    se2[f] += float(m * q - s1 * s1) / m + m * (s1 / m - bcell[r, c] - cb[f, col[r, c]]) ** 2
+    ry = np.arange(Hm) % XT_PERIOD
+    level = bcell[None, :, :] + cb[:, col]                                # (F,6,6): black + cb of each cell
+    dev_row = (rs.astype(np.float64) - nrow[None, :, :] * level[:, ry, :]).sum(axis=2)
+    rho, g_scale, R_scale = _masked_tail(se2, nrow.sum(axis=1), dev_row, int(ncell.sum()))
+    return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
+
+
+def flat_stats_from_sums_masked(sums, black_level, white_level, color_bias, Hm, Wm, chan_counts=None):
+    """flat_stats_from_sums over the unflagged sites only (chan_counts (4,) of them per channel); without counts it IS flat_stats_from_sums."""
+    if chan_counts is None or np.all(np.asarray(chan_counts) == Hm * Wm // 4):
+        return flat_stats_from_sums(sums, black_level, white_level, color_bias, Hm, Wm)
+    black, sums = _black(black_level), np.asarray(sums)
+    nc = np.asarray(chan_counts, np.int64).reshape(4)
+    if np.any(nc == 0):
+        raise ValueError('channel %d has no unflagged site' % int(np.flatnonzero(nc == 0)[0]))
+    P = sums.shape[0]
+    cbm = np.asarray(color_bias, np.float64).reshape(4)
+    mu = sums[:, :, 0].astype(np.float64) / (2 * nc[None, :]) - black[None, :] - cbm[None, :]
+    var = np.array([[float(int(nc[c]) * int(sums[p, c, 2]) - int(sums[p, c, 1]) ** 2) / (int(nc[c]) ** 2) / 2.0 for c in range(4)] for p in range(P)])
+    usable = (sums[:, :, 3] == 0) & (mu > 0) & (mu <= 0.8 * (float(white_level) - black[None, :]))
+    return {'mu': mu, 'var': var.reshape(P, 4), 'usable': usable}
+
+
+def xtrans_flat_stats_from_cell_sums_masked(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm, cell_n=None):
+    """xtrans_flat_stats_from_cell_sums over the unflagged sites only (cell_n (6,6) of them per cell); without counts it IS that function."""
+    if cell_n is None or np.array_equal(cell_n, cell_counts(Hm, Wm)):
+        return xtrans_flat_stats_from_cell_sums(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm)
+    pat, black = _xpattern(raw_pattern), _black(black_level)
+    sums = np.asarray(sums).reshape(-1, XT_PERIOD, XT_PERIOD, 4)
+    P = sums.shape[0]
+    cbm = np.asarray(color_bias, np.float64).reshape(3)
+    ncell = np.asarray(cell_n, np.int64).reshape(XT_PERIOD, XT_PERIOD)
+    bcell, col = black[pat], CODE_COLOUR[pat]
+    mu, var, usable = np.zeros((P, 3)), np.zeros((P, 3)), np.zeros((P, 3), bool)
+    for k in range(3):
+        m = col == k
+        nk = int(ncell[m].sum())
+        if nk == 0:
+            raise ValueError('colour %d has no unflagged site' % k)
+        bbar = float(np.sum(ncell[m] * bcell[m])) / nk
+        for p in range(P):
+            sab, d1, d2 = (sum(int(v) for v in sums[p][m][:, j]) for j in range(3))
+            mu[p, k] = sab / (2 * nk) - bbar - cbm[k]
+            var[p, k] = float(nk * d2 - d1 * d1) / (nk * nk) / 2.0
+            usable[p, k] = int(sums[p][m][:, 3].sum()) == 0 and mu[p, k] > 0 and mu[p, k] <= 0.8 * (float(white_level) - bbar)
+    return {'mu': mu, 'var': var, 'usable': usable}
+
+
+def _site_counts(dmap, Hm, Wm, p):
+    """Unflagged sites per cell (p,p) and per row and column class (Hm,p)."""
+    keep = ~dmap.mask
+    cell_n = np.array([[int(keep[r::p, c::p].sum()) for c in range(p)] for r in range(p)], np.int64)
+    row_n = np.stack([keep[:, c::p].sum(axis=1) for c in range(p)], axis=1).astype(np.int64)
+    return cell_n, row_n
+
+
+def _gather_sites(u, dmap):
+    """CUDA codes (..., Hm, Wm) -> host int64 (..., K): the codes at the map's sites."""
+    import torch
+    ys = torch.from_numpy(dmap.sites[:, 0].astype(np.int64)).to(u.device)
+    xs = torch.from_numpy(dmap.sites[:, 1].astype(np.int64)).to(u.device)
+    v = u.view(torch.int16) if u.dtype == torch.uint16 else u            # the same bits: indexing is defined for int16
+    return (v[..., ys, xs].to(torch.int32) & 0xffff).cpu().numpy().astype(np.int64)
+
+
+def _flat_terms(a, b, white):
+    """host int64 codes (P,k) of the two flats at k sites -> (P,4): sum(a+b), sum(a-b), sum((a-b)^2), #sites with a or b >= white."""
+    return np.stack([(a + b).sum(axis=1), (a - b).sum(axis=1), ((a - b) ** 2).sum(axis=1), ((a >= white) | (b >= white)).sum(axis=1)], axis=1)
+
+
+def _drop_flagged(t, defects):
+    """Residuals (F, Hm*Wm) -> (F, Hm*Wm - K): the flagged sites' entries removed (row-major order kept)."""
+    if defects is None or not defects.count:
+        return t
+    import torch
+    keep = torch.from_numpy(~defects.mask.reshape(-1)).to(t.device)
+    return t[:, keep].contiguous()
+
+
+def _check_defects(defects, cfa, shape=None, raw_pattern=None):
+    """The map must be for this CFA, these sides and -- X-Trans -- this pattern: its neighbourhoods are those of the colours of the 6x6
+    cell it was built for.  A Bayer map's neighbourhoods are the sites at offsets of +-2 whatever the 2x2 permutation, so a Bayer map
+    made under another raw_pattern flags and repairs the same sites: its raw_pattern is not compared."""
+    if defects is None or (isinstance(defects, str) and defects == 'auto'):
+        return defects
+    from .defects import DefectMap
+    if not isinstance(defects, DefectMap):
+        raise ValueError("defects must be a DefectMap, 'auto' or None, got %r" % (type(defects).__name__,))
+    if cfa == 'xtrans' and defects.cfa == 'xtrans' and raw_pattern is not None and not np.array_equal(CODE_COLOUR[_xpattern(raw_pattern)], defects.classes):
+        raise ValueError('calibration: the defect map was built for another X-Trans raw_pattern (the colours of its 6x6 cell differ)')
+    if shape is not None:
+        defects.check_frames(shape, cfa, 'calibration')
+    elif defects.cfa != cfa:
+        raise ValueError('calibration: the defect map is for cfa=%r, the frames are %r' % (defects.cfa, cfa))
+    return defects
+
+
 def ptc_gain(mu, var, usable, what='session'):
     """K = the OLS slope of var on mu over the usable photon-transfer points."""
     mu, var = np.asarray(mu)[np.asarray(usable)], np.asarray(var)[np.asarray(usable)]
@@ -244,14 +399,18 @@ def _ols(x, y):
 
 
 # ---- public steps -----------------------------------------------------------------------------------------------------------
-def bias_frame_stats(bias, raw_pattern, black_level, residual=False):
+def bias_frame_stats(bias, raw_pattern, black_level, residual=False, defects=None):
     """Bias frames (F,Hm,Wm) uint16 [ndarray or CUDA int16/uint16 tensor] -> dict of host arrays:
     chan_sums int64 (F,4,2) (sum u, sum u^2 per channel), row_sums int64 (F,Hm,2) (sum u over even / odd columns), color_bias (F,4),
     row_offset (F,Hm), g_scale (F,), R_scale (F,) float64; with residual=True also 't', the CUDA float32 (F,Hm*Wm) residuals
-    float32(((u - black_c) - cb_c) - rho_y)."""
+    float32(((u - black_c) - cb_c) - rho_y).
+    defects (a DefectMap): every statistic is over its unflagged sites only -- the sums have the flagged sites' contributions taken out
+    (exactly, on the host), 'chan_counts' (4,) and 'row_counts' (Hm,2) count what is left, and 't' is (F, Hm*Wm - K): the flagged
+    entries are dropped."""
     import torch
     pat, black = _pattern(raw_pattern), _black(black_level)
     F, Hm, Wm = _check_mosaics(bias, 3, 'bias')
+    defects = _check_defects(defects, 'bayer', (Hm, Wm))
     u = _device_u16(bias)
     dev = u.device
     cs = torch.empty((F, 4, 2), dtype=torch.int64, device=dev)
@@ -261,14 +420,24 @@ def bias_frame_stats(bias, raw_pattern, black_level, residual=False):
     L.check(L.lib().eld_calib_bias_stats(L.dptr(u), F, Hm, Wm, cp, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), L.cur_stream()),
             'eld_calib_bias_stats')
     out = {'chan_sums': cs.cpu().numpy(), 'row_sums': rs.cpu().numpy()}
-    out.update(bias_stats_from_sums(out['chan_sums'], out['row_sums'], pat, black, Hm, Wm))
+    if defects is not None and defects.count:
+        g, ys, xs = _gather_sites(u, defects), defects.sites[:, 0], defects.sites[:, 1]
+        ch = pat[ys & 1, xs & 1]
+        for c in range(4):
+            out['chan_sums'][:, c, 0] -= g[:, ch == c].sum(axis=1)
+            out['chan_sums'][:, c, 1] -= (g[:, ch == c] ** 2).sum(axis=1)
+        for f in range(F):
+            np.subtract.at(out['row_sums'][f], (ys, xs & 1), g[f])
+        cell_n, out['row_counts'] = _site_counts(defects, Hm, Wm, 2)
+        out['chan_counts'] = np.array([cell_n[pat == c][0] for c in range(4)], np.int64)
+    out.update(bias_stats_from_sums_masked(out['chan_sums'], out['row_sums'], pat, black, Hm, Wm, out.get('chan_counts'), out.get('row_counts')))
     if residual:
         t = torch.empty((F, Hm * Wm), dtype=torch.float32, device=dev)
         cbd = torch.from_numpy(np.ascontiguousarray(out['color_bias'])).to(dev)
         rhod = torch.from_numpy(np.ascontiguousarray(out['row_offset'])).to(dev)
         L.check(L.lib().eld_calib_bias_residual(L.dptr(u), F, Hm, Wm, cp, (ctypes.c_double * 4)(*black.tolist()), L.dptr(cbd), L.dptr(rhod),
                                                 L.dptr(t), L.cur_stream()), 'eld_calib_bias_residual')
-        out['t'] = t
+        out['t'] = _drop_flagged(t, defects)
     return out
 
 
@@ -314,13 +483,14 @@ def tukey_lambda_ppcc(t, lambdas=None, presorted=False):
     return out
 
 
-def flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias):
+def flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias, defects=None):
     """Flat pairs (P,2,Hm,Wm) uint16 -> dict: sums int64 (P,4,4) = per channel (sum(a+b), sum(a-b), sum((a-b)^2), saturated pixels),
     mu (P,4) = mean((a+b)/2) - black_c - color_bias_c, var (P,4) = var(a-b)/2, usable (P,4) bool (no saturated pixel and
     0 < mu <= 0.8 (white - black_c)).  color_bias: the session's mean colour bias (4,)."""
     import torch
     pat, black = _pattern(raw_pattern), _black(black_level)
     P, _, Hm, Wm = _check_mosaics(flats, 4, 'flats')
+    defects = _check_defects(defects, 'bayer', (Hm, Wm))
     cbm = np.asarray(color_bias, np.float64).reshape(4)
     ab = _device_u16(flats)
     out = torch.empty((P, 4, 4), dtype=torch.int64, device=ab.device)
@@ -328,16 +498,23 @@ def flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias):
     L.check(L.lib().eld_calib_flat_stats(L.dptr(ab), P, Hm, Wm, _c_pattern(pat), int(white_level), L.dptr(out), L.dptr(ws), ws.numel(),
                                          L.cur_stream()), 'eld_calib_flat_stats')
     res = {'sums': out.cpu().numpy()}
-    res.update(flat_stats_from_sums(res['sums'], black, white_level, cbm, Hm, Wm))
+    if defects is not None and defects.count:                 # the sums (and the saturation count) over the unflagged sites only
+        g, ch = _gather_sites(ab, defects), pat[defects.sites[:, 0] & 1, defects.sites[:, 1] & 1]
+        for c in range(4):
+            res['sums'][:, c] -= _flat_terms(g[:, 0][:, ch == c], g[:, 1][:, ch == c], int(white_level))
+        cell_n = _site_counts(defects, Hm, Wm, 2)[0]
+        res['chan_counts'] = np.array([cell_n[pat == c][0] for c in range(4)], np.int64)
+    res.update(flat_stats_from_sums_masked(res['sums'], black, white_level, cbm, Hm, Wm, res.get('chan_counts')))
     return res
 
 
-def xtrans_bias_frame_stats(bias, raw_pattern, black_level, residual=False):
+def xtrans_bias_frame_stats(bias, raw_pattern, black_level, residual=False, defects=None):
     """X-Trans bias frames (F,Hm,Wm) uint16 -> dict: cell_sums int64 (F,6,6,2), row_sums int64 (F,Hm,6), color_bias (F,3), row_offset
     (F,Hm), g_scale, R_scale (F,); with residual=True also 't' (CUDA float32 (F,Hm*Wm)) = float32(((u - black_code) - cb) - rho_y)."""
     import torch
     pat, black = _xpattern(raw_pattern), _black(black_level)
     F, Hm, Wm = _check_mosaics(bias, 3, 'bias', 'xtrans')
+    defects = _check_defects(defects, 'xtrans', (Hm, Wm), raw_pattern)
     u = _device_u16(bias)
     dev = u.device
     p = XT_PERIOD
@@ -347,7 +524,15 @@ def xtrans_bias_frame_stats(bias, raw_pattern, black_level, residual=False):
     L.check(L.lib().eld_calib_cell_stats(L.dptr(u), F, Hm, Wm, p, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), L.cur_stream()),
             'eld_calib_cell_stats')
     out = {'cell_sums': cs.cpu().numpy(), 'row_sums': rs.cpu().numpy()}
-    out.update(xtrans_bias_stats_from_cell_sums(out['cell_sums'], out['row_sums'], pat, black, Hm, Wm))
+    if defects is not None and defects.count:                 # as bias_frame_stats: the flagged sites leave the sums, exactly
+        g, ys, xs = _gather_sites(u, defects), defects.sites[:, 0], defects.sites[:, 1]
+        for f in range(F):
+            np.subtract.at(out['cell_sums'][f, :, :, 0], (ys % p, xs % p), g[f])
+            np.subtract.at(out['cell_sums'][f, :, :, 1], (ys % p, xs % p), g[f] ** 2)
+            np.subtract.at(out['row_sums'][f], (ys, xs % p), g[f])
+        out['cell_counts'], out['row_counts'] = _site_counts(defects, Hm, Wm, p)
+    out.update(xtrans_bias_stats_from_cell_sums_masked(out['cell_sums'], out['row_sums'], pat, black, Hm, Wm, out.get('cell_counts'),
+                                                       out.get('row_counts')))
     if residual:
         t = torch.empty((F, Hm * Wm), dtype=torch.float32, device=dev)
         cbc = np.ascontiguousarray(out['color_bias'][:, CODE_COLOUR[pat].reshape(-1)])          # (F,36) bias of each cell's colour
@@ -355,16 +540,17 @@ def xtrans_bias_frame_stats(bias, raw_pattern, black_level, residual=False):
         rhod = torch.from_numpy(np.ascontiguousarray(out['row_offset'])).to(dev)
         L.check(L.lib().eld_calib_cell_residual(L.dptr(u), F, Hm, Wm, p, (ctypes.c_double * (p * p))(*black[pat].reshape(-1).tolist()),
                                                 L.dptr(cbd), L.dptr(rhod), L.dptr(t), L.cur_stream()), 'eld_calib_cell_residual')
-        out['t'] = t
+        out['t'] = _drop_flagged(t, defects)
     return out
 
 
-def xtrans_flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias):
+def xtrans_flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias, defects=None):
     """X-Trans flat pairs (P,2,Hm,Wm) uint16 -> dict: sums int64 (P,6,6,4) per cell, mu, var (P,3), usable (P,3) per colour.
     color_bias: the session's mean (R, G, B) bias."""
     import torch
     pat, black = _xpattern(raw_pattern), _black(black_level)
     P, _, Hm, Wm = _check_mosaics(flats, 4, 'flats', 'xtrans')
+    defects = _check_defects(defects, 'xtrans', (Hm, Wm), raw_pattern)
     ab = _device_u16(flats)
     p = XT_PERIOD
     out = torch.empty((P, p, p, 4), dtype=torch.int64, device=ab.device)
@@ -372,7 +558,14 @@ def xtrans_flat_pair_stats(flats, raw_pattern, black_level, white_level, color_b
     L.check(L.lib().eld_calib_cell_flat_stats(L.dptr(ab), P, Hm, Wm, p, int(white_level), L.dptr(out), L.dptr(ws), ws.numel(),
                                               L.cur_stream()), 'eld_calib_cell_flat_stats')
     res = {'sums': out.cpu().numpy()}
-    res.update(xtrans_flat_stats_from_cell_sums(res['sums'], pat, black, white_level, color_bias, Hm, Wm))
+    if defects is not None and defects.count:
+        g, ys, xs = _gather_sites(ab, defects), defects.sites[:, 0], defects.sites[:, 1]
+        for r in range(p):
+            for c in range(p):
+                m = (ys % p == r) & (xs % p == c)
+                res['sums'][:, r, c] -= _flat_terms(g[:, 0][:, m], g[:, 1][:, m], int(white_level))
+        res['cell_counts'] = _site_counts(defects, Hm, Wm, p)[0]
+    res.update(xtrans_flat_stats_from_cell_sums_masked(res['sums'], pat, black, white_level, color_bias, Hm, Wm, res.get('cell_counts')))
     return res
 
 
@@ -412,25 +605,38 @@ def _check_sessions(sessions, cfa='bayer'):
         raise ValueError('at least 2 sessions (2 distinct K) are needed, got %d' % len(sessions))
 
 
-def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None, cfa='bayer'):
+def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None, cfa='bayer', defects=None):
     """Sessions of bias frames and flat pairs -> (params, diagnostics).  params has exactly the release schema
     (Kmin, Kmax, G_shape (m,), color_bias (m,4) float32, 'Profile-1': {G_scale, R_scale, g_scale: {slope, bias, sigma}}), one G_shape /
     color_bias row per bias frame; diagnostics holds the per-frame samples, r(lambda) and the photon-transfer points.
     cfa='xtrans': raw_pattern is the 6x6 X-Trans pattern and black_level rawpy's 4 values by colour code; the table's color_bias is
-    (m,3) in (R, G, B) order and it carries 'cfa': 'xtrans'."""
+    (m,3) in (R, G, B) order and it carries 'cfa': 'xtrans'.
+    defects: a DefectMap (eld_amd.defects) of the sensor -- every statistic is then taken over its unflagged sites only (colour bias, row
+    offsets, g_scale, R_scale, the residuals of the PPCC, the flat-pair sums and their saturation count); 'auto' finds the map first from
+    the bias frames of the lowest-ISO session (find_defects with its defaults) and returns it as diag['defects'].  X-Trans maps exist for
+    the pattern phase the library packs only (row 0 = R B G B R G): another 6x6 raw_pattern with defects set is a ValueError.  None (default): every
+    site counts, as before."""
     xt = _cfa(cfa) == 'xtrans'
     _xpattern(raw_pattern) if xt else _pattern(raw_pattern)
     _black(black_level)
+    _check_defects(defects, cfa, raw_pattern=raw_pattern)
     _check_sessions(sessions, cfa)
+    if defects is not None and not isinstance(defects, str):
+        defects.check_frames(_shape(sessions[0]['bias']), cfa, 'calibration')
+    elif defects == 'auto':
+        from .defects import find_defects
+        isos = [s.get('iso') for s in sessions]
+        low = int(np.argmin([float(v) for v in isos])) if all(isinstance(v, (int, float)) for v in isos) else 0
+        defects = find_defects(sessions[low]['bias'], cfa, raw_pattern)[0]
     bias_stats = xtrans_bias_frame_stats if xt else bias_frame_stats
     flat_stats = xtrans_flat_pair_stats if xt else flat_pair_stats
     frames, r_all, ptc, Ks = [], [], [], []
     lam = None
     for i, s in enumerate(sessions):
-        st = bias_stats(s['bias'], raw_pattern, black_level, residual=True)
+        st = bias_stats(s['bias'], raw_pattern, black_level, residual=True, defects=defects)
         pp = tukey_lambda_ppcc(st.pop('t'), lambdas)
         lam = pp['lambdas']
-        fl = flat_stats(s['flats'], raw_pattern, black_level, white_level, st['color_bias'].mean(axis=0))
+        fl = flat_stats(s['flats'], raw_pattern, black_level, white_level, st['color_bias'].mean(axis=0), defects=defects)
         what = 'session %d (iso %s)' % (i, s.get('iso'))
         K = ptc_gain(fl['mu'], fl['var'], fl['usable'], what)
         Ks.append(K)
@@ -443,6 +649,8 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
     if xt:
         params['cfa'] = 'xtrans'
     diag = {'frames': frames, 'lambdas': lam, 'r': np.array(r_all), 'K': np.array(Ks), 'ptc': ptc}
+    if defects is not None:
+        diag['defects'] = defects
     return params, diag
 
 
@@ -456,9 +664,18 @@ def save_camera_params(params, camera, out_dir):
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
+def manifest_defects(path):
+    """The manifest's "defects" entry: None, 'auto', or the path of a saved map (relative to the manifest's directory)."""
+    with open(path) as f:
+        d = json.load(f).get('defects')
+    if d is None or d == 'auto':
+        return d
+    return os.path.join(os.path.dirname(os.path.abspath(path)), d)
+
+
 def load_manifest(path, with_cfa=False):
     """Manifest JSON -> (sessions, raw_pattern, black_level, white_level), and the manifest's "cfa" ('bayer' when absent) as a fifth
-    item with with_cfa=True.  Paths are relative to the manifest's directory."""
+    item with with_cfa=True.  Paths are relative to the manifest's directory.  The optional "defects" entry is read by manifest_defects."""
     with open(path) as f:
         m = json.load(f)
     base = os.path.dirname(os.path.abspath(path))
@@ -479,10 +696,20 @@ def main(argv=None):
     ap.add_argument('manifest', help='JSON: raw_pattern, black_level, white_level, [cfa,] sessions [{iso, bias: [.npy], flats: [[a.npy, b.npy]]}]')
     ap.add_argument('--camera', required=True, help='camera name: writes <out>/<camera>_params.npy')
     ap.add_argument('--out', default=os.path.join('camera_params', 'release'))
+    ap.add_argument('--defects', help="a defect map written by eld_amd.defects (.npz), or 'auto' to find one from the bias frames of the lowest-ISO "
+                                      "session and write <out>/<camera>_defects.npz; overrides the manifest's \"defects\"")
     a = ap.parse_args(argv)
     sessions, pattern, black, white, cfa = load_manifest(a.manifest, with_cfa=True)
-    params, diag = calibrate_camera(sessions, pattern, black, white, cfa=cfa)
+    defects = a.defects if a.defects is not None else manifest_defects(a.manifest)
+    if defects is not None and defects != 'auto':
+        from .defects import as_defect_map
+        defects = as_defect_map(defects, '--defects')
+    params, diag = calibrate_camera(sessions, pattern, black, white, cfa=cfa, defects=defects)
     path = save_camera_params(params, a.camera, a.out)
+    if defects is not None:
+        print('%d defective sites kept out of every statistic' % diag['defects'].count)
+        if defects == 'auto':
+            print('wrote', diag['defects'].save(os.path.join(a.out, a.camera + '_defects.npz')))
     for fr in diag['frames']:
         print('iso %-6s K %.5g  lambda %+.4f  G_scale %.4g  R_scale %.4g  g_scale %.4g' % (fr['iso'], fr['K'], fr['lambda'], fr['G_scale'],
                                                                                           fr['R_scale'], fr['g_scale']))

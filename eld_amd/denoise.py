@@ -244,7 +244,7 @@ def run_network(denoiser, x, chop=None):
 
 
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
-                chop=None, rounding='nearest', srgb_size='packed', linear=False):
+                chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None):
     """Denoise uint16 sensor mosaics with a trained U-Net.
 
     mosaic_u16  NumPy uint16 array or CUDA uint16 / int16-view tensor, (Hm, Wm) or (N, Hm, Wm) -- rawpy's raw_image_visible.
@@ -258,6 +258,10 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     srgb_size   'packed' (default): the rendering above.  'full': the same gains, matrix and tone curve behind a demosaic, at mosaic
                 resolution (N,3,Hm,Wm) -- X-Trans: the whole 6x6 cells, as the write-back; needs wb and ccm.
     linear      with srgb_size='full', also 'linear': float32 (N,3,Hm,Wm) linear RGB after the colour matrix (no clamp, no tone curve).
+    defects     a DefectMap (eld_amd.defects) or the path of a saved one: the flagged sites of the input codes are repaired (the lower
+                median of their unflagged same-colour neighbours) in one pass before the input stage -- the ratio would turn a warm pixel
+                into a saturated dot.  X-Trans: the borders outside whole cells, which pass through to the output mosaic, are repaired
+                too.  None (default): the codes are used as they are.
 
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
@@ -288,6 +292,10 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     if denoiser.out_channels != PLANES[cfa]:
         raise ValueError('the network writes %d planes, the %s write-back needs %d' % (denoiser.out_channels, cfa, PLANES[cfa]))
     wbs, ccms = _colour(cfa, wb, ccm, N)
+    if defects is not None:
+        from .defects import as_defect_map, repair_device
+        defects = as_defect_map(defects)
+        defects.check_frames((Hm, Wm), cfa, 'denoise_raw')
     if srgb_size == 'full' and cfa == 'bayer' and (pat[0] & 1) != (pat[3] & 1):
         raise ValueError('the full-size render needs a Bayer raw_pattern with its greens on a diagonal, got %r' % (raw_pattern,))
 
@@ -302,6 +310,8 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         if t.device != dev:
             raise ValueError('the mosaic is on %s, the denoiser on %s' % (t.device, dev))
     t3 = t if batched else t.unsqueeze(0)
+    if defects is not None:
+        t3 = repair_device(t3, defects)
     x = pack_input(t3, cfa, pat, blk, white, ratios)
     out = run_network(denoiser, x, chop)
     mosaic = t3.clone()                   # X-Trans: the borders outside whole cells keep the input's codes
@@ -338,7 +348,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
 # ---- command line -------------------------------------------------------------------------------------------------------------
 SIDECAR_ALIASES = {'black_level_per_channel': 'black_level', 'white_level': 'white_point', 'camera_whitebalance': 'wb',
                    'rgb_camera_matrix': 'ccm', 'black': 'black_level', 'white': 'white_point'}
-SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size')
+SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size', 'defects')
 
 
 def read_sidecar(path):
@@ -351,6 +361,8 @@ def read_sidecar(path):
     out = {}
     for k, v in d.items():
         k = SIDECAR_ALIASES.get(k, k)
+        if k == 'defects' and isinstance(v, str):             # a saved defect map, relative to the sidecar
+            v = os.path.join(os.path.dirname(os.path.abspath(path)), v)
         if k not in SIDECAR_KEYS:
             raise ValueError('%s: unknown key %r (known: %s)' % (path, k, ', '.join(SIDECAR_KEYS + tuple(SIDECAR_ALIASES))))
         if k == 'ccm':
@@ -378,6 +390,7 @@ def build_parser():
     p.add_argument('--bf16', action='store_true', help='run the network in bf16')
     p.add_argument('--chop', choices=('auto', 'on', 'off'), help='forward_chop tiles (default auto)')
     p.add_argument('--rounding', choices=ROUNDING, help="write-back rounding (default 'nearest')")
+    p.add_argument('--defects', metavar='PATH', help='a defect map written by eld_amd.defects (.npz): its sites are repaired before the network')
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
     return p
 
@@ -387,7 +400,7 @@ def parse_args(argv):
     a = build_parser().parse_args(argv)
     o = read_sidecar(a.meta) if a.meta else {}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
-           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'precision': 'bf16' if a.bf16 else None,
+           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'precision': 'bf16' if a.bf16 else None,
            'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
     o.update({k: v for k, v in cli.items() if v is not None})
     o.setdefault('cfa', 'bayer')
@@ -429,6 +442,9 @@ def main(argv=None):
     den = load_denoiser(ckpt, cfa=o['cfa'], precision=o['precision'])
     os.makedirs(outdir, exist_ok=True)
     kw = {k: o.get(k) for k in ('raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'chop', 'rounding', 'srgb_size')}
+    if o.get('defects') is not None:
+        from .defects import as_defect_map
+        kw['defects'] = as_defect_map(o['defects'], '--defects')
     for path in inputs:
         raw = np.load(path)
         res = denoise_raw(den, raw, o['cfa'], **kw)

@@ -55,11 +55,13 @@ class FramePool:
 
     mosaics      NumPy uint16 arrays or CUDA uint16 / int16-view tensors, each (Hm, Wm) (a (N, Hm, Wm) stack counts as N frames); uploaded once.
     cfa, raw_pattern, black_level, white_point   as eld_amd.denoise.denoise_raw (same checks, same defaults).
+    defects      a DefectMap (eld_amd.defects) or the path of a saved one: every frame is repaired once, at upload (no per-step cost);
+                 every frame must then have the map's shape.  Paired mode takes the same map for both pools.
     device       the CUDA device of the pool (default: the current one).  Without a GPU the pool keeps its geometry only: grid() and the
                  loader's draws work, patches() does not.
     Bad arguments raise ValueError before any device work; a missing libeld_amd raises LibraryMissing."""
 
-    def __init__(self, mosaics, cfa='bayer', raw_pattern=None, black_level=None, white_point=16383, device=None):
+    def __init__(self, mosaics, cfa='bayer', raw_pattern=None, black_level=None, white_point=16383, device=None, defects=None):
         _check_cfa(cfa)
         if isinstance(mosaics, np.ndarray) or hasattr(mosaics, 'is_cuda'):
             mosaics = [mosaics]
@@ -71,6 +73,12 @@ class FramePool:
             raise ValueError('FramePool needs at least one mosaic')
         for m in frames:
             _check_sides(int(m.shape[0]), int(m.shape[1]), cfa)
+        if defects is not None:
+            from .defects import as_defect_map
+            defects = as_defect_map(defects)
+            for i, m in enumerate(frames):
+                defects.check_frames(m.shape, cfa, 'frame %d' % i)
+        self.defects = defects
         self.cfa, self.C = cfa, PLANES[cfa]
         self.raw_pattern, self.black_level, self.white_point = _levels(cfa, raw_pattern, black_level, white_point)
         table = np.zeros(len(frames), L.POOL_FRAME_DTYPE)
@@ -99,6 +107,11 @@ class FramePool:
             n = int(f['Hm']) * int(f['Wm'])
             src = torch.from_numpy(np.ascontiguousarray(m).view(np.int16)) if isinstance(m, np.ndarray) else m.contiguous().view(torch.int16)
             buf[int(f['offset']):int(f['offset']) + n].copy_(src.reshape(-1))
+        if self.defects is not None and self.defects.count:
+            from .defects import repair_device
+            for f in self.frames:                             # in place, frame by frame (the frames start 16-byte aligned, not back to back)
+                v = buf[int(f['offset']):int(f['offset']) + int(f['Hm']) * int(f['Wm'])].view(1, int(f['Hm']), int(f['Wm']))
+                repair_device(v, self.defects, v)
         self.buffer, self.device = buf, dev
         self._table_dev = torch.from_numpy(self.frames.view(np.uint8).copy()).to(dev)
 

@@ -27,6 +27,7 @@ def build_parser():
     p.add_argument('--raw-pattern', type=int, nargs=4, metavar='CODE', help='Bayer 2x2 raw_pattern, row-major')
     p.add_argument('--black', type=float, nargs='+', help='black level(s): 1 or 4 (Bayer), 1 (X-Trans)')
     p.add_argument('--white', type=float, help='white point (default 16383)')
+    p.add_argument('--defects', metavar='PATH', help='a defect map written by eld_amd.defects (.npz): the frames are repaired once, at upload')
     p.add_argument('--camera', default='SonyA7S2', help='a table written by eld_amd.calibrate (<dir>/<name>_params.npy) or a release camera name')
     p.add_argument('--noise', default='PGRU', help="noise model letters of NoiseModel(model=...) (default 'PGRU')")
     p.add_argument('--patch', type=int, default=512, help='packed patch side (default 512)')
@@ -52,7 +53,8 @@ def noise_model(camera, letters, cfa):
 def main(argv=None):
     from .denoise import read_sidecar
     a = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
-    o = {k: v for k, v in (read_sidecar(a.meta) if a.meta else {}).items() if k in ('cfa', 'raw_pattern', 'black_level', 'white_point')}
+    side = read_sidecar(a.meta) if a.meta else {}
+    o = {k: v for k, v in side.items() if k in ('cfa', 'raw_pattern', 'black_level', 'white_point')}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white}
     o.update({k: v for k, v in cli.items() if v is not None})
     cfa = o.pop('cfa', 'bayer')
@@ -65,7 +67,7 @@ def main(argv=None):
     from .framepool import FramePool, FramePoolLoader
     np.random.seed(a.seed)
     torch.manual_seed(a.seed)
-    pool = FramePool(mosaics, cfa=cfa, **o)
+    pool = FramePool(mosaics, cfa=cfa, defects=a.defects if a.defects is not None else side.get('defects'), **o)
     if pool.buffer is None:
         raise RuntimeError('eld_amd.train_frames needs a GPU: there is no CPU fallback')
     nm = noise_model(a.camera, a.noise, cfa)

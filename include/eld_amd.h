@@ -37,8 +37,10 @@ extern "C" {
  * 5: the frame-pool crop entry points (eld_crop_pack_raw_bayer_u16 / eld_crop_pack_raw_xtrans_u16, EldPoolFrame, EldCropRecord) exist; every
  * version-4 call behaves as before.
  * 6: the full-resolution renders (eld_render_bayer / eld_render_xtrans, ELD_RENDER_*) and eld_debug_xtrans_demosaic_tables exist; every
- * version-5 call behaves as before. */
-#define ELD_ABI_VERSION 6
+ * version-5 call behaves as before.
+ * 7: the defective-pixel entry points (eld_defect_deviation / eld_defect_flags / eld_defect_repair_u16, eld_debug_xtrans_defect_tables) exist;
+ * every version-6 call behaves as before. */
+#define ELD_ABI_VERSION 7
 
 /* negative = argument errors (hipError_t values are >= 0) */
 #define ELD_EINVAL   (-1)   /* bad shape / flag combination / null pointer                   */
@@ -430,6 +432,37 @@ int eld_render_xtrans(const float* packed, const float* wbs, const float* ccms, 
  * of 8 ints: colour (R 0, G 1, B 2), packed plane, then for G (3x3 window) and for R and B (5x5 window) the bit mask of the window taps that
  * hold the colour (bit = raster index of the tap) and the sum of their weights.  n = ints available in out (>= 288). */
 int eld_debug_xtrans_demosaic_tables(int* out, int n);
+
+/* ---- defective-pixel maps (csrc/defect.hip, eld_amd/defects.py) ----------------------------------------------------
+ * All integer, so every result is defined bit for bit:
+ *   class of site (y, x) = pattern[(y % period) * period + x % period] (HOST array of period^2 ints).  period 2: a permutation of 0..3, as
+ *       eld_pack_raw_bayer_u16's raw_pattern (the two greens are classes of their own); period 6: rawpy's X-Trans colour codes (0 R, 2 B,
+ *       1 and 3 both G) of the 6x6 cell this library packs (xtrans.h: row 0 = R B G B R G) -- any other cell is ELD_EINVAL, because the
+ *       tap lists and the window radius are compiled for that cell.
+ *   N(y, x) = the sites other than (y, x) inside the image with |dy| <= R, |dx| <= R and the class of (y, x).  Bayer: R = 2 (the 8 sites at
+ *       offsets of +-2; 3 in a corner).  X-Trans: R = the smallest radius that leaves every site of every phase at least 3 neighbours in
+ *       every image-clipped window of a mosaic with sides >= 6, derived at compile time (eld_debug_xtrans_defect_tables reports it).
+ *   lower median of m >= 1 integers = the element of rank (m - 1) / 2 in ascending order.
+ * Deviation: stack [F,Hm,Wm] uint16, 1 <= F <= 4096; S = sum over f (exact in uint32); D[y][x] = int32(S - lower median of S over N).
+ *   Two passes: S goes through the workspace (eld_defect_deviation_workspace_bytes(Hm, Wm) = 4 Hm Wm bytes, 8-byte aligned).
+ *   ELD_EINVAL: a null pointer, F outside [1, 4096], period not 2 or 6, a bad pattern, Hm or Wm < 1 (X-Trans: < 6), an odd Wm (the stack
+ *   is read as 32-bit words), Hm * Wm >= 2^31, stack or D not 4-byte aligned; ELD_EWS: the workspace is too small.
+ * Flags: site is hot when D > T_hi, cold when -D > T_lo; bitmap[y][x >> 5] bit x & 31, ceil(Wm / 32) uint32 words per row, every word
+ *   written, unused bits zero.
+ * Repair: out[n][y][x] = in[n][y][x] where the bit is clear, else the lower median of in[n] over the UNFLAGGED sites of N(y, x); a flagged
+ *   site with no unflagged neighbour keeps its code.  One bitmap serves the N frames.  in == out is allowed and gives the same bits as
+ *   out of place (only unflagged sites are read, and they are written back unchanged); any other overlap is ELD_EINVAL.  Per row, 16-byte
+ *   loads and stores when both row pointers are 16-byte aligned, 4-byte ones when 4-byte aligned, 2-byte ones otherwise. */
+size_t eld_defect_deviation_workspace_bytes(int Hm, int Wm);
+int eld_defect_deviation(const uint16_t* stack, int F, int Hm, int Wm, int period, const int* pattern, int32_t* D, void* ws, size_t ws_bytes,
+                         void* stream);
+int eld_defect_flags(const int32_t* D, int Hm, int Wm, int32_t T_hi, int32_t T_lo, uint32_t* bitmap, void* stream);
+int eld_defect_repair_u16(const uint16_t* in, uint16_t* out, int N, int Hm, int Wm, int period, const int* pattern, const uint32_t* bitmap,
+                          void* stream);
+/* Test hook (HOST, no device work): out[0] = the X-Trans window radius R, then 36 rows (phase = 6 * row + col of the cell) of 4 ints: colour
+ * (R 0, G 1, B 2), number of same-colour taps in the (2R + 1)^2 window, and the low / high 32 bits of their mask (bit = raster index
+ * (dy + R) * (2R + 1) + dx + R; the centre is never set).  n = ints available in out (>= 145). */
+int eld_debug_xtrans_defect_tables(int* out, int n);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
