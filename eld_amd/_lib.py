@@ -91,6 +91,8 @@ SIGNATURES = {
     'eld_defect_flags': (_i, [_vp, _i, _i, C.c_int32, C.c_int32, _vp, _vp]),
     'eld_defect_repair_u16': (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int), _vp, _vp]),
     'eld_debug_xtrans_defect_tables': (_i, [C.POINTER(C.c_int), _i]),
+    'eld_hist_u16': (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _vp, _vp]),
+    'eld_hist_f32': (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int), _i, _vp, _i, _vp, _vp]),
     'eld_quality_assess_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'eld_quality_assess': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
     'eld_quality_assess_images': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
@@ -122,7 +124,7 @@ SIGNATURES = {
 }
 
 
-ABI_VERSION = 7         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
+ABI_VERSION = 8         # ELD_ABI_VERSION of include/eld_amd.h this binding was written against
 PHILOX_ROUNDS = 7      # the sampler's generator: Philox4x32-7 (csrc/philox.h); checked against the library at load
 
 

@@ -1,0 +1,503 @@
+"""Validate a calibrated noise table against the sensor's own frames: does noise synthesised from the table look like the sensor's?
+
+The check of the ELD paper's Table 1, per colour group: the discrete KL divergence between the histogram of real bias frames (and of
+the difference of real flat pairs) and the histogram of the sampler's synthesis under each noise model named, next to the divergence of
+two synthetic draws from each other (the sampling floor).  It is a test of MARGINAL distributions: the spatial structure of row noise is
+seen only through its effect on the marginal.
+
+    report = validate_camera(sessions, raw_pattern, black_level, white_level, models=('Pg', 'PG', 'PGR', 'PGRB'))
+    report['best']                                  # the model with the lowest mean bias-frame kl
+    report['sessions'][0]['frames'][0]['models']['PG']   # {'kl', 'floor', 'kl_groups', 'floor_groups'}
+
+The histograms are exact integer counts built on the device (eld_amd/csrc/hist.hip: eld_hist_u16 for sensor codes, eld_hist_f32 for
+sampler output); the binning contract is DESIGN.md sec. 15.  kl_divergence runs in float64 on the host.
+
+Command line: python -m eld_amd.validate manifest.json [--camera TABLE.npy] [--models Pg,PG,PGR,PGRB] [--source frames|table]
+[--defects PATH|auto] [--radius N] [--seed S] [--out report.json] [--hist hist.npz] (the manifest is calibrate's).
+"""
+import argparse
+import ctypes
+import json
+import sys
+
+import numpy as np
+
+from . import _lib as L
+from . import calibrate as CAL
+from .noise import NoiseParams, model_flags, table_cfa
+
+MODEL_LETTERS = 'PpgGRUB'
+MAX_RADIUS = 32767
+XT_PLANE_COLOUR = (0, 1, 2, 0, 2, 1, 1, 1, 1)     # packed X-Trans plane -> colour (R 0, G 1, B 2): planes 0, 3 R; 1, 5-8 G; 2, 4 B
+ID_BASE = 1 << 62                                 # validation streams lie far from the sample ids a training run counts up from 0
+
+
+# ---- argument checks (host only) -------------------------------------------------------------------------------------------------------
+def _radius(radius, what='radius'):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or radius < 1 or radius > MAX_RADIUS:
+        raise ValueError('%s must be an integer in [1, %d], got %r' % (what, MAX_RADIUS, radius))
+    return int(radius)
+
+
+def _models(models):
+    if isinstance(models, str):
+        models = [m for m in models.split(',') if m]
+    models = list(models)
+    if not models:
+        raise ValueError('no noise model named')
+    for m in models:
+        if not isinstance(m, str) or not m or any(ch not in MODEL_LETTERS for ch in m):
+            raise ValueError('unknown noise model %r: the letters are %s' % (m, ', '.join(MODEL_LETTERS)))
+    if len(set(models)) != len(models):
+        raise ValueError('a noise model is named twice: %r' % (models,))
+    return models
+
+
+def group_map_u16(cfa, raw_pattern):
+    """-> (period, groups: p*p ints, G).  Bayer: cell (r, c) -> the packed channel raw_pattern[r][c] (R, G1, B, G2), G = 4;
+    X-Trans: cell -> the colour (R 0, G 1, B 2) of its colour code, G = 3."""
+    if CAL._cfa(cfa) == 'xtrans':
+        return CAL.XT_PERIOD, [int(v) for v in CAL.CODE_COLOUR[CAL._xpattern(raw_pattern)].reshape(-1)], 3
+    return 2, [int(v) for v in CAL._pattern(raw_pattern).reshape(-1)], 4
+
+
+def group_map_f32(cfa):
+    """-> (C, groups: C ints, G).  Bayer: plane c -> group c; X-Trans: planes 0, 3 -> R, 1, 5-8 -> G, 2, 4 -> B."""
+    if CAL._cfa(cfa) == 'xtrans':
+        return 9, list(XT_PLANE_COLOUR), 3
+    return 4, [0, 1, 2, 3], 4
+
+
+def group_black(cfa, black_level):
+    """The integer centre of each histogram group: rint(black) of the packed channel (Bayer) or of the colour (X-Trans, whose two green
+    codes must share one rounded black level: a group has one centre)."""
+    b = np.rint(CAL._black(black_level)).astype(np.int64)
+    if cfa == 'xtrans':
+        if b[1] != b[3]:
+            raise ValueError('X-Trans: the two green colour codes have black levels %d and %d; a histogram group has one centre' % (b[1], b[3]))
+        return b[:3]
+    return b
+
+
+def sample_id(session, frame, model_index, draw):
+    """The sampler stream of one synthetic frame: 2^62 + session * 2^40 + frame * 2^8 + model_index * 2 + draw.
+    session < 2^20, frame < 2^32 (bias frames count from 0, flat pairs follow them), model_index < 128, draw 0 or 1."""
+    session, frame, model_index, draw = int(session), int(frame), int(model_index), int(draw)
+    if not (0 <= session < 1 << 20 and 0 <= frame < 1 << 32 and 0 <= model_index < 128 and draw in (0, 1)):
+        raise ValueError('sample_id(%d, %d, %d, %d): out of range' % (session, frame, model_index, draw))
+    return ID_BASE + (session << 40) + (frame << 8) + (model_index << 1) + draw
+
+
+# ---- KL divergence (host, float64) -----------------------------------------------------------------------------------------------------
+def kl_divergence(p_counts, q_counts, alpha=1.0):
+    """Discrete KL(p || q) over the last axis, float64: p = (n + alpha) / (sum n + alpha B), q likewise, sum p log(p / q).
+    alpha (additive smoothing) is an interface default that nothing pins: 1.0 is add-one smoothing; report the value with the numbers.
+    alpha = 0 uses the raw frequencies (0 log 0 = 0).  ValueError when alpha < 0, when a histogram is empty at alpha = 0, or when
+    alpha <= 0 and some q bin is empty where the p bin is not (the divergence is infinite)."""
+    p = np.asarray(p_counts, dtype=np.float64)
+    q = np.asarray(q_counts, dtype=np.float64)
+    if p.shape[-1:] != q.shape[-1:] or p.ndim == 0:
+        raise ValueError('histograms must share their last axis, got %s and %s' % (p.shape, q.shape))
+    if not (alpha >= 0):
+        raise ValueError('alpha must be >= 0, got %r' % (alpha,))
+    if np.any(p < 0) or np.any(q < 0):
+        raise ValueError('negative counts')
+    p, q = np.broadcast_arrays(p, q)
+    if alpha <= 0:
+        if np.any((q == 0) & (p > 0)):
+            raise ValueError('alpha <= 0 and a q bin is empty where the p bin is not: the divergence is infinite')
+        if np.any(p.sum(axis=-1) == 0) or np.any(q.sum(axis=-1) == 0):
+            raise ValueError('alpha <= 0 and an empty histogram')
+    B = p.shape[-1]
+    pp = (p + alpha) / (p.sum(axis=-1, keepdims=True) + alpha * B)
+    qq = (q + alpha) / (q.sum(axis=-1, keepdims=True) + alpha * B)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        t = np.where(pp > 0, pp * np.log(pp / qq), 0.0)
+    return t.sum(axis=-1)
+
+
+# ---- histograms (device) ---------------------------------------------------------------------------------------------------------------
+def _check_frames(x, what):
+    s = CAL._shape(x)
+    if len(s) != 3:
+        raise ValueError('%s: expected (F, Hm, Wm), got shape %s' % (what, s))
+    if s[2] % 2:
+        raise ValueError('%s: the mosaic width must be even (rows are read as 32-bit words), got %d' % (what, s[2]))
+    if s[1] * s[2] >= 1 << 31:
+        raise ValueError('%s: a frame of %d x %d has 2^31 pixels or more' % (what, s[1], s[2]))
+    if isinstance(x, np.ndarray):
+        if x.dtype != np.uint16:
+            raise ValueError('%s: uint16 mosaics expected, got %s' % (what, x.dtype))
+    else:
+        import torch
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.int16, torch.uint16)):
+            raise ValueError('%s: a tensor must be CUDA int16/uint16 codes' % what)
+    return s
+
+
+def histogram_u16(frames, cfa, raw_pattern, centre, radius, subtract=None, defects=None):
+    """Exact histograms of sensor codes.  frames (F,Hm,Wm) uint16 [ndarray or CUDA int16/uint16 tensor] -> int64 ndarray (F, G, 2R+1):
+    per colour group (group_map_u16) the counts of clamp(u - centre[g] + R, 0, 2R), or of clamp(u - v + R, 0, 2R) with subtract=v (same
+    shape; centre is then ignored and may be None).  defects: a DefectMap whose flagged sites are not counted."""
+    R = _radius(radius)
+    p, groups, G = group_map_u16(cfa, raw_pattern)
+    F, Hm, Wm = _check_frames(frames, 'frames')
+    if subtract is not None:
+        if _check_frames(subtract, 'subtract') != (F, Hm, Wm):
+            raise ValueError('subtract has shape %s, the frames %s' % (CAL._shape(subtract), (F, Hm, Wm)))
+        cen = None
+    else:
+        c = np.asarray(centre if centre is not None else [], dtype=np.float64).reshape(-1)
+        if c.size != G or not np.all(c == np.rint(c)) or np.any(np.abs(c) > 1 << 30):
+            raise ValueError('centre must hold %d integers (one per group), got %r' % (G, centre))
+        cen = (ctypes.c_int32 * G)(*[int(v) for v in c])
+    if defects is not None:
+        defects = CAL._check_defects(defects, cfa, (Hm, Wm), raw_pattern if cfa == 'xtrans' else None)
+        if isinstance(defects, str):
+            raise ValueError("histogram_u16 takes a DefectMap, not 'auto'")
+    import torch
+    u = CAL._device_u16(frames)
+    v = None if subtract is None else CAL._device_u16(subtract)
+    counts = torch.empty((F, G, 2 * R + 1), dtype=torch.int64, device=u.device)
+    bm = None if defects is None else defects.bitmap_on(u.device)
+    L.check(L.lib().eld_hist_u16(L.dptr(u), L.dptr(v), F, Hm, Wm, p, (ctypes.c_int * (p * p))(*groups), G, cen, R, L.dptr(bm), L.dptr(counts),
+                                 L.cur_stream()), 'eld_hist_u16')
+    return counts.cpu().numpy()
+
+
+def histogram_f32(x, scale, radius, cfa, subtract=None):
+    """Exact histograms of sampler output.  x: CUDA float32 (N,C,H,W) (C = 4 Bayer, 9 X-Trans); scale: N floats (or one for all);
+    -> int64 ndarray (N, G, 2R+1): per colour group (group_map_f32) the counts of clamp(q(x) + R, 0, 2R), q(t) = rint(float32(t * scale[n]))
+    saturated at +-2^29, or of clamp(q(x) - q(x2) + R, 0, 2R) with subtract=x2.  An element whose product is NaN is not counted."""
+    R = _radius(radius)
+    C, groups, G = group_map_f32(cfa)
+    import torch
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 4:
+        raise ValueError('x must be a CUDA float32 tensor (N, C, H, W)')
+    if x.shape[1] != C:
+        raise ValueError('cfa=%r input has %d planes, got %d' % (cfa, C, x.shape[1]))
+    if subtract is not None and (not isinstance(subtract, torch.Tensor) or not subtract.is_cuda or subtract.dtype != torch.float32
+                                 or subtract.shape != x.shape):
+        raise ValueError('subtract must be a CUDA float32 tensor of the shape of x')
+    N, _, H, W = (int(v) for v in x.shape)
+    sc = np.asarray(scale, dtype=np.float32).reshape(-1)
+    if sc.size == 1:
+        sc = np.repeat(sc, N)
+    if sc.size != N:
+        raise ValueError('scale must hold one value per image (%d), got %d' % (N, sc.size))
+    x = x.contiguous()
+    x2 = None if subtract is None else subtract.contiguous()
+    scd = torch.from_numpy(np.ascontiguousarray(sc)).to(x.device)
+    counts = torch.empty((N, G, 2 * R + 1), dtype=torch.int64, device=x.device)
+    L.check(L.lib().eld_hist_f32(L.dptr(x), L.dptr(x2), N, C, H, W, (ctypes.c_int * C)(*groups), G, L.dptr(scd), R, L.dptr(counts),
+                                 L.cur_stream()), 'eld_hist_f32')
+    return counts.cpu().numpy()
+
+
+# ---- synthesis -------------------------------------------------------------------------------------------------------------------------
+def _noise_params(p, sat):
+    """Any parameter record -> the one validation samples with: ratio = 1, saturation = sat, q_step = 1."""
+    if isinstance(p, dict):
+        p = NoiseParams(p.get('K', 1.0), p.get('g_scale', 0.0), sat, 1.0, p.get('tl_lambda', 0.0), p.get('tl_scale', 0.0), p.get('row_scale', 0.0),
+                        1.0, tuple(p.get('color_bias', (0.0,) * 4)))
+    p = NoiseParams.coerce(p)
+    cb = tuple(float(v) for v in p.color_bias) + (0.0,) * (4 - len(p.color_bias))
+    return NoiseParams(float(p[0]), float(p[1]), float(sat), 1.0, float(p.tl_lambda), float(p.tl_scale), float(p.row_scale), 1.0, cb)
+
+
+def _sample(clean, params, model, cfa, seed, ids):
+    """The sampler on clean (N,C,h,w) float32 CUDA with one parameter record and N sample ids -> float32 (N,C,h,w)."""
+    from .noise import make_records, sample_noise_records
+    return sample_noise_records(clean, make_records([params] * len(ids), ids), model_flags(model, cfa), seed)
+
+
+def synthesize_codes(clean, params, model, cfa, seed, sample_id, white, black, shape=None):
+    """What a sensor would have stored for one frame: the sampler's output x on `clean` under `model`, as a uint16 mosaic
+    clip(rint(x * sat) + rint(black_c), 0, 65535), unpacked (CUDA uint16 (Hm, Wm); Bayer planes land in the layout [[0, 1], [3, 2]] of
+    RawPacker.unpack_raw_bayer).  x * sat is one float32 multiply and rint rounds half to even: eld_hist_f32's q.
+    clean: packed float32 (C,h,w) [ndarray or CUDA tensor], or None for a dark frame -- zeros of the packed `shape` (C,h,w).
+    params: a NoiseParams / dict (K, g_scale, tl_lambda, tl_scale, row_scale, color_bias, in DN); the sampler runs with ratio = 1,
+    saturation = white - max(black) and q_step = 1.  black: per packed channel (Bayer) or per colour code (X-Trans)."""
+    import torch
+    from .noise import RawPacker
+    CAL._cfa(cfa)
+    _models([model])
+    b = np.rint(CAL._black(black))
+    sat = float(white) - float(np.max(CAL._black(black)))
+    if not sat > 0:
+        raise ValueError('white level %r does not exceed the black level' % (white,))
+    C = group_map_f32(cfa)[0]
+    if clean is None:
+        if shape is None or len(shape) != 3 or int(shape[0]) != C:
+            raise ValueError('a dark frame needs shape=(%d, h, w), got %r' % (C, shape))
+        y = torch.zeros((1,) + tuple(int(v) for v in shape), dtype=torch.float32, device='cuda')
+    else:
+        y = (torch.from_numpy(np.ascontiguousarray(clean, dtype=np.float32)).cuda() if isinstance(clean, np.ndarray) else clean.float()).contiguous()
+        if y.dim() != 3 or y.shape[0] != C:
+            raise ValueError('clean must be packed (%d, h, w), got %s' % (C, tuple(y.shape)))
+        y = y.unsqueeze(0)
+    x = _sample(y, _noise_params(params, sat), model, cfa, seed, [int(sample_id)])
+    plane_black = b[list(XT_PLANE_COLOUR)] if cfa == 'xtrans' else b
+    codes = torch.round(x * np.float32(sat)) + torch.from_numpy(plane_black.astype(np.float32)).to(x.device).view(1, C, 1, 1)
+    mos = RawPacker(cfa).unpack_raw(torch.clamp(codes, 0, 65535))
+    return mos[0].to(torch.int32).to(torch.uint16)
+
+
+def clean_from_flat_pair(a, b, cfa, raw_pattern, black_level, color_bias, sat):
+    """The clean image a flat pair stands for, packed float32 (C,h,w) on the device:
+        y = clip((((a + b) * 0.5 - black_c) - color_bias_c) / sat, 0, 1)
+    every operation in float32 ((a + b) * 0.5 is exact), black_c / color_bias_c those of the plane's packed channel (Bayer) or colour
+    (X-Trans: black of the colour code R 0, G 1, B 2); a, b: CUDA int16/uint16 (Hm,Wm)."""
+    import torch
+    from .noise import RawPacker
+    m = ((a.to(torch.int32) & 0xffff).float() + (b.to(torch.int32) & 0xffff).float()) * 0.5
+    blk = CAL._black(black_level)
+    if cfa == 'xtrans':
+        planes = RawPacker('xtrans').pack_raw_xtrans(m)
+        col = list(XT_PLANE_COLOUR)
+        bl, cb = blk[col], np.asarray(color_bias, np.float64).reshape(-1)[:3][col]
+    else:
+        pat = CAL._pattern(raw_pattern)
+        pos = [np.argwhere(pat == c)[0] for c in range(4)]
+        planes = torch.stack([m[int(r)::2, int(q)::2] for r, q in pos]).contiguous()
+        bl, cb = blk, np.asarray(color_bias, np.float64).reshape(-1)[:4]
+    C = planes.shape[0]
+    dev = planes.device
+    t = (planes - torch.from_numpy(bl.astype(np.float32)).to(dev).view(C, 1, 1)) - torch.from_numpy(cb.astype(np.float32)).to(dev).view(C, 1, 1)
+    return torch.clamp(t / np.float32(sat), 0.0, 1.0).contiguous()
+
+
+# ---- the validation --------------------------------------------------------------------------------------------------------------------
+def _table_params(table, K, ncb):
+    """source='table': the regression means at log K (no sigma scatter), the median G_shape, the mean colour-bias row."""
+    prof = table[CAL.PROFILE]
+    lk = float(np.log(K))
+    reg = {k: float(np.exp(float(prof[k]['slope']) * lk + float(prof[k]['bias']))) for k in CAL.SIGMA_KEYS}
+    cb = np.asarray(table['color_bias'], np.float64).reshape(len(table['G_shape']), -1).mean(axis=0)
+    return {'K': float(K), 'g_scale': reg['g_scale'], 'tl_scale': reg['G_scale'], 'row_scale': reg['R_scale'],
+            'tl_lambda': float(np.median(np.asarray(table['G_shape'], np.float64))), 'color_bias': [float(v) for v in cb[:ncb]]}
+
+
+def _frame_params(fr, ncb):
+    return {'K': float(fr['K']), 'g_scale': float(fr['g_scale']), 'tl_scale': float(fr['G_scale']), 'row_scale': float(fr['R_scale']),
+            'tl_lambda': float(fr['lambda']), 'color_bias': [float(v) for v in np.asarray(fr['color_bias']).reshape(-1)[:ncb]]}
+
+
+def _mean_params(ps):
+    out = {k: float(np.mean([p[k] for p in ps])) for k in ('K', 'g_scale', 'tl_scale', 'row_scale')}
+    out['tl_lambda'] = float(np.median([p['tl_lambda'] for p in ps]))
+    out['color_bias'] = [float(v) for v in np.mean([p['color_bias'] for p in ps], axis=0)]
+    return out
+
+
+def _check_session_shapes(sessions, cfa):
+    """calibrate's per-session checks without the counts its log-linear fits need: with a diag given nothing is fitted here."""
+    if not isinstance(sessions, (list, tuple)) or len(sessions) == 0:
+        raise ValueError('sessions must be a non-empty list of {"iso", "bias", "flats"}')
+    shape = None
+    for i, s in enumerate(sessions):
+        for k in ('bias', 'flats'):
+            if k not in s:
+                raise ValueError('session %d has no %r' % (i, k))
+        F, Hm, Wm = CAL._check_mosaics(s['bias'], 3, 'session %d bias' % i, cfa)
+        P = CAL._check_mosaics(s['flats'], 4, 'session %d flats' % i, cfa)[0]
+        shape = shape or (Hm, Wm)
+        if (Hm, Wm) != shape or CAL._shape(s['flats'])[-2:] != shape:
+            raise ValueError('session %d: mosaic shapes differ' % i)
+        if F == 0 or P == 0:
+            raise ValueError('session %d: needs at least one bias frame and one flat pair' % i)
+
+
+def validate_camera(sessions, raw_pattern, black_level, white_level, table=None, diag=None, models=('Pg', 'PG', 'PGR', 'PGRB'), source='frames',
+                    cfa='bayer', defects=None, radius=256, flat_radius=1024, seed=2018, alpha=1.0, keep_hist=False):
+    """Sessions (calibrate_camera's) -> a report dict: how far the sampler's synthesis under each model lies from the real frames.
+
+    Parameters of a bias frame: source='frames' -- that frame's own estimates, diag['frames'] of calibrate_camera (run here when neither
+    table nor diag is given); source='table' -- the table's regression means at log K of the session (diag['K']), without sigma scatter,
+    the median G_shape and the mean colour-bias row.  Flat pairs use the session's mean parameters.
+    Bias frame f of session s, model m (index i): real = histogram of u - rint(black_g); syn_d = histogram of q(x_d), x_d the sampler's dark
+    frame at sample_id(s, f, i, d); kl = KL(real || syn_0), floor = KL(syn_0 || syn_1), each the mean over the colour groups ('kl_groups',
+    'floor_groups' hold the G values).  Flat pair j: real = histogram of a - b; syn = histogram of q(x_0) - q(x_1) on the clean image
+    clean_from_flat_pair, ids sample_id(s, F + j, i, d); kl_flat = KL(real || syn).  A defects map masks the real side only (synthetic
+    frames have no defects; probabilities are normalised).  best = the model of lowest mean bias-frame kl, lowest index on a tie.
+    This is a check of marginal distributions per colour group: it does not test the spatial structure of row noise."""
+    cfa = CAL._cfa(cfa)
+    models = _models(models)
+    R, RF = _radius(radius), _radius(flat_radius, 'flat_radius')
+    if source not in ('frames', 'table'):
+        raise ValueError("source must be 'frames' or 'table', got %r" % (source,))
+    if not (alpha >= 0):
+        raise ValueError('alpha must be >= 0, got %r' % (alpha,))
+    if table is not None and any('B' in m for m in models) and table_cfa(table) != cfa:
+        raise ValueError('the table is for cfa=%r, the frames are %r: its colour bias does not apply (model with B)' % (table_cfa(table), cfa))
+    CAL._xpattern(raw_pattern) if cfa == 'xtrans' else CAL._pattern(raw_pattern)
+    black = CAL._black(black_level)
+    CAL._check_defects(defects, cfa, raw_pattern=raw_pattern)
+    if diag is None:
+        CAL._check_sessions(sessions, cfa)                 # a calibration runs here: its session and frame counts apply
+    else:
+        _check_session_shapes(sessions, cfa)
+    if len(sessions) >= 1 << 20:
+        raise ValueError('too many sessions')
+    centre = group_black(cfa, black)
+    sat = float(white_level) - float(black.max())
+    if not sat > 0:
+        raise ValueError('white level %r does not exceed the black level' % (white_level,))
+    if defects is not None and not isinstance(defects, str):
+        defects.check_frames(CAL._shape(sessions[0]['bias']), cfa, 'validation')
+
+    import torch
+    if diag is None:
+        table_c, diag = CAL.calibrate_camera(sessions, raw_pattern, black_level, white_level, cfa=cfa, defects=defects)
+        if table is None:
+            table = table_c
+    if defects == 'auto':
+        defects = diag.get('defects')
+        if defects is None:
+            from .defects import find_defects
+            defects = find_defects(sessions[0]['bias'], cfa, raw_pattern)[0]
+    C, _, G = group_map_f32(cfa)
+    ncb = 3 if cfa == 'xtrans' else 4
+    if source == 'table':
+        if table is None or 'K' not in diag:
+            raise ValueError("source='table' needs a table and the session gains diag['K']")
+        if len(diag['K']) != len(sessions):
+            raise ValueError("diag['K'] holds %d gains for %d sessions" % (len(diag['K']), len(sessions)))
+    else:
+        nb = sum(CAL._shape(s['bias'])[0] for s in sessions)
+        if 'frames' not in diag or len(diag['frames']) != nb:
+            raise ValueError("source='frames' needs diag['frames'] with one record per bias frame (%d)" % nb)
+
+    report = {'models': models, 'source': source, 'cfa': cfa, 'groups': G, 'radius': R, 'flat_radius': RF, 'alpha': float(alpha), 'seed': int(seed),
+              'sessions': []}
+    hists = {}
+    j0 = 0
+    for si, s in enumerate(sessions):
+        bias = CAL._device_u16(s['bias'])
+        flats = CAL._device_u16(s['flats'])
+        F, Hm, Wm = CAL._shape(bias)
+        P = CAL._shape(flats)[0]
+        h, w = (2 * (Hm // 6), 2 * (Wm // 6)) if cfa == 'xtrans' else (Hm // 2, Wm // 2)
+        if source == 'table':
+            fparams = [_table_params(table, float(diag['K'][si]), ncb)] * F
+        else:
+            fparams = [_frame_params(fr, ncb) for fr in diag['frames'][j0:j0 + F]]
+        j0 += F
+        sparams = _mean_params(fparams)
+        real = histogram_u16(bias, cfa, raw_pattern, centre, R, defects=defects)
+        dark = torch.zeros((2, C, h, w), dtype=torch.float32, device=bias.device)
+        srep = {'iso': s.get('iso'), 'K': sparams['K'], 'params': sparams, 'frames': [], 'flats': []}
+        for f in range(F):
+            frep = {'params': fparams[f], 'models': {}}
+            prm = _noise_params(fparams[f], sat)
+            for mi, m in enumerate(models):
+                x = _sample(dark, prm, m, cfa, seed, [sample_id(si, f, mi, 0), sample_id(si, f, mi, 1)])
+                syn = histogram_f32(x, sat, R, cfa)
+                klg, flg = kl_divergence(real[f], syn[0], alpha), kl_divergence(syn[0], syn[1], alpha)
+                frep['models'][m] = {'kl': float(klg.mean()), 'floor': float(flg.mean()), 'kl_groups': klg.tolist(), 'floor_groups': flg.tolist()}
+                if keep_hist:
+                    hists['s%d_f%d_%s' % (si, f, m)] = syn
+            srep['frames'].append(frep)
+        if keep_hist:
+            hists['s%d_real' % si] = real
+        a, b = flats[:, 0].contiguous(), flats[:, 1].contiguous()
+        realf = histogram_u16(a, cfa, raw_pattern, None, RF, subtract=b, defects=defects)
+        prm = _noise_params(sparams, sat)
+        for j in range(P):
+            y = clean_from_flat_pair(a[j], b[j], cfa, raw_pattern, black, sparams['color_bias'], sat)
+            y2 = torch.stack([y, y])
+            prep = {'models': {}}
+            for mi, m in enumerate(models):
+                x = _sample(y2, prm, m, cfa, seed, [sample_id(si, F + j, mi, 0), sample_id(si, F + j, mi, 1)])
+                syn = histogram_f32(x[:1], sat, RF, cfa, subtract=x[1:])
+                klg = kl_divergence(realf[j], syn[0], alpha)
+                prep['models'][m] = {'kl_flat': float(klg.mean()), 'kl_flat_groups': klg.tolist()}
+                if keep_hist:
+                    hists['s%d_p%d_%s' % (si, j, m)] = syn[0]
+            srep['flats'].append(prep)
+        if keep_hist:
+            hists['s%d_real_flats' % si] = realf
+        srep['means'] = {m: {'kl': float(np.mean([fr['models'][m]['kl'] for fr in srep['frames']])),
+                             'floor': float(np.mean([fr['models'][m]['floor'] for fr in srep['frames']])),
+                             'kl_flat': float(np.mean([pr['models'][m]['kl_flat'] for pr in srep['flats']]))} for m in models}
+        report['sessions'].append(srep)
+    report['means'] = {m: {k: float(np.mean([fr['models'][m][k] for s in report['sessions'] for fr in s['frames']])) for k in ('kl', 'floor')}
+                       for m in models}
+    for m in models:
+        report['means'][m]['kl_flat'] = float(np.mean([pr['models'][m]['kl_flat'] for s in report['sessions'] for pr in s['flats']]))
+    report['best'] = models[int(np.argmin([report['means'][m]['kl'] for m in models]))]      # argmin: the lowest index on a tie
+    if keep_hist:
+        report['hist'] = hists
+    return report
+
+
+# ---- command line ----------------------------------------------------------------------------------------------------------------------
+def to_jsonable(x):
+    """NumPy scalars and arrays -> Python numbers and lists, recursively (the report as JSON: no pickle)."""
+    if isinstance(x, dict):
+        return {str(k): to_jsonable(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [to_jsonable(v) for v in x]
+    if isinstance(x, np.ndarray):
+        return x.tolist()
+    if isinstance(x, np.generic):
+        return x.item()
+    return x
+
+
+def parser():
+    ap = argparse.ArgumentParser(prog='python -m eld_amd.validate', description=__doc__.split('\n')[0])
+    ap.add_argument('manifest', help="calibrate's manifest JSON")
+    ap.add_argument('--camera', help='a table written by eld_amd.calibrate (<camera>_params.npy); default: calibrate here')
+    ap.add_argument('--models', default='Pg,PG,PGR,PGRB', type=_models_arg)
+    ap.add_argument('--source', default='frames', choices=('frames', 'table'))
+    ap.add_argument('--defects', help="a defect map (.npz) or 'auto'; overrides the manifest's \"defects\"")
+    ap.add_argument('--radius', type=_radius_arg, default=256)
+    ap.add_argument('--seed', type=int, default=2018)
+    ap.add_argument('--out', help='write the report here as JSON')
+    ap.add_argument('--hist', help='write the histograms here (.npz)')
+    return ap
+
+
+def _models_arg(s):
+    try:
+        return _models(s)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _radius_arg(s):
+    try:
+        return _radius(int(s))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def main(argv=None):
+    a = parser().parse_args(argv)
+    sessions, pattern, black, white, cfa = CAL.load_manifest(a.manifest, with_cfa=True)
+    defects = a.defects if a.defects is not None else CAL.manifest_defects(a.manifest)
+    if defects is not None and defects != 'auto':
+        from .defects import as_defect_map
+        defects = as_defect_map(defects, '--defects')
+    table = None if a.camera is None else np.load(a.camera, allow_pickle=True).item()
+    rep = validate_camera(sessions, pattern, black, white, table=table, models=a.models, source=a.source, cfa=cfa, defects=defects,
+                          radius=a.radius, seed=a.seed, keep_hist=a.hist is not None)
+    hists = rep.pop('hist', None)
+    for si, s in enumerate(rep['sessions']):
+        for m in rep['models']:
+            mm = s['means'][m]
+            print('session %d iso %-6s %-6s kl %.5f  floor %.5f  kl_flat %.5f' % (si, s['iso'], m, mm['kl'], mm['floor'], mm['kl_flat']))
+    print('best model: %s (alpha %g, radius %d, seed %d)' % (rep['best'], rep['alpha'], rep['radius'], rep['seed']))
+    if a.out:
+        with open(a.out, 'w') as f:
+            json.dump(to_jsonable(rep), f, indent=1)
+        print('wrote', a.out)
+    if a.hist:
+        np.savez(a.hist, **hists)
+        print('wrote', a.hist)
+    return 0
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -39,8 +39,9 @@ extern "C" {
  * 6: the full-resolution renders (eld_render_bayer / eld_render_xtrans, ELD_RENDER_*) and eld_debug_xtrans_demosaic_tables exist; every
  * version-5 call behaves as before.
  * 7: the defective-pixel entry points (eld_defect_deviation / eld_defect_flags / eld_defect_repair_u16, eld_debug_xtrans_defect_tables) exist;
- * every version-6 call behaves as before. */
-#define ELD_ABI_VERSION 7
+ * every version-6 call behaves as before.
+ * 8: the histogram entry points (eld_hist_u16 / eld_hist_f32) exist; every version-7 call behaves as before. */
+#define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
 #define ELD_EINVAL   (-1)   /* bad shape / flag combination / null pointer                   */
@@ -463,6 +464,26 @@ int eld_defect_repair_u16(const uint16_t* in, uint16_t* out, int N, int Hm, int 
  * (R 0, G 1, B 2), number of same-colour taps in the (2R + 1)^2 window, and the low / high 32 bits of their mask (bit = raster index
  * (dy + R) * (2R + 1) + dx + R; the centre is never set).  n = ints available in out (>= 145). */
 int eld_debug_xtrans_defect_tables(int* out, int n);
+
+/* ---- exact histograms (csrc/hist.hip, eld_amd/validate.py) --------------------------------------------------------------
+ * counts[.][G][B], B = 2R + 1, uint64, fully written by the call (zeros included); integer adds only, so the result is defined bit for bit
+ * (it equals np.bincount).  1 <= G <= 4, 1 <= R <= 32767 (every R works: a table too large for the LDS is counted in global memory).  No
+ * workspace.  bin = clamp(d + R, 0, 2R): the end bins absorb the overflow.
+ *
+ * eld_hist_u16: u [F,Hm,Wm] uint16 codes, F <= 65535, Wm even, Hm * Wm < 2^31; p = the pattern period (2 or 6); group: HOST array of p*p ints
+ *   in [-1, G), cell (y % p, x % p) -> histogram group, -1 = not counted; d = int(u) - centre[g] (centre: HOST int32[G], |centre| <= 2^30), or
+ *   int(u) - int(v) when v (optional, same shape) is given (centre is then ignored and may be NULL); bitmap (optional): the defect bitmap of
+ *   eld_defect_flags, ceil(Wm / 32) uint32 words per row, one map for all F frames -- a flagged site is not counted.  counts[F][G][B].
+ *   u, v and bitmap 4-byte aligned, counts 8-byte aligned.  16-byte loads when Wm % 8 == 0 and u (and v) are 16-byte aligned.
+ * eld_hist_f32: x [N,C,H,W] float32, N <= 65535, C <= 64, H * W < 2^31; group: HOST array of C ints in [-1, G), plane c -> group; scale: DEVICE
+ *   float32[N]; q(t) = (int)clamp(rintf(t * scale[n]), -2^29, 2^29) -- one float32 multiply, round half to even; d = q(x), or q(x) - q(x2)
+ *   when x2 (optional, same shape) is given.  +-inf and values beyond the clamp land in the end bins; an element whose product x * scale[n]
+ *   (or x2 * scale[n]) is NaN -- every NaN x -- is not counted.  counts[N][G][B].
+ * ELD_EINVAL before any launch for everything the host can see: sizes, p, G, R, a group entry outside [-1, G), null or misaligned pointers. */
+int eld_hist_u16(const uint16_t* u, const uint16_t* v, int F, int Hm, int Wm, int p, const int* group, int G, const int32_t* centre, int R,
+                 const uint32_t* bitmap, uint64_t* counts, void* stream);
+int eld_hist_f32(const float* x, const float* x2, int N, int C, int H, int W, const int* group, int G, const float* scale, int R,
+                 uint64_t* counts, void* stream);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
