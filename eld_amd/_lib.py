@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get('ELD_AMD_LIB') or os.path.join(_HERE, 'libeld_amd.so')
 SHOT_POISSON, SHOT_GAUSS, READ_GAUSS, READ_TL, ROW, QUANT, CBIAS, CLIP = 1, 2, 4, 8, 16, 32, 64, 128
 AUG_NOTRANSPOSE = 256
 CFA_XTRANS = 512
+DARK = 1024             # 'D': signal-independent noise read from a pool of dark frames (eld_noise_forward_dark only)
 IN_F32, IN_U16 = 0, 1
 ROUND_TRUNC, ROUND_NEAREST, ROUND_TRUNC_F32 = 0, 1, 2      # write-back rounding (eld_unpack_raw_*_u16)
 RENDER_SRGB8, RENDER_LINEAR_F32 = 0, 1                      # out_mode of eld_render_bayer / eld_render_xtrans
@@ -38,6 +39,8 @@ SIGNATURES = {
     'eld_error_string': (C.c_char_p, [_i]),
     'eld_noise_forward': (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _u32, _u64, _vp, _vp, _vp]),
     'eld_noise_forward_strided': (_i, [_vp, _i, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _u32, _u64, _vp, _vp, _vp]),
+    'eld_noise_forward_dark': (_i, [_vp, _i, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _u32, _u64, _vp, _vp,
+                                    _vp, _sz, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _vp]),
     'eld_augment_u16': (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _u32, _vp]),
     'eld_philox_rounds': (_i, []),
     'eld_philox_words': (_i, [_vp, _u32, _u32, _u64, _u32, _u32, _u64, _vp]),
@@ -158,7 +161,10 @@ def load_library(path=None):
     for name, (res, args) in SIGNATURES.items():
         if name == 'eld_philox_rounds' and any_philox and not hasattr(lib_, name):
             continue                      # dev A/B runs against a library older than the symbol (tools/build_variant.sh <old rev>)
-        fn = getattr(lib_, name)          # AttributeError if the symbol is not exported
+        try:
+            fn = getattr(lib_, name)
+        except AttributeError:            # same ABI number, older build (eld_noise_forward_dark came without a new number)
+            raise RuntimeError('%s does not export %s: it was built from older sources; rebuild with `python __graft_entry__.py`' % (p, name))
         fn.restype = res
         fn.argtypes = args
     if not any_philox and lib_.eld_philox_rounds() != PHILOX_ROUNDS:

@@ -14,6 +14,14 @@
 //   * the float32 op sequence is exactly the reference's (one rounding per op, FMA contraction
 //     OFF for this translation unit), so with injected variates the output is bit-identical to
 //     the reference's NumPy evaluation.
+//
+// ELD_DARK (eld_noise_forward_dark, model letter 'D'): the signal-independent noise is not drawn but READ -- a crop of a real dark frame of
+// the sensor, held in a frame pool (framepool.hip), enters the op chain between the shot term and the quantisation dither.  The crop
+// (frame, y0, x0) is a function of (seed, sample id): one Philox call per wave, on uniform operands.  10 B of algorithmic traffic per
+// packed element (the 2 B code on top of the 8 B).  VEC + Bayer: the four elements of a lane are the even or the odd codes of eight
+// consecutive codes of one mosaic row -- one 16-byte load where the crop's alignment allows it, four 4-byte loads otherwise (the predicate
+// of framepool.hip, uniform over the image).  An image whose record or frame entry does not describe a patch inside a frame inside the pool
+// is SKIPPED as a whole (its output is left as it was); nothing outside the pool is read.
 #include <stdlib.h>
 #include "philox.h"
 #include "poisson_alias_table.h"
@@ -48,7 +56,17 @@ struct NoiseArgs {
     uint32_t flags, in_dtype;
     PhiloxKey key;
     uint32_t dbg;          // ablation switches (dev builds, env ELD_NOISE_DBG): 1 skip the queue drain, 4 PTRS draws always take the queue route, 8 skip phase 3 RNG
+    // ELD_DARK only (appended: kernels that do not name ELD_DARK read none of it and keep their argument offsets)
+    const uint16_t* pool;
+    size_t pool_elems;
+    const EldPoolFrame* frames;
+    int F;
+    uint32_t dark_pos;     // Bayer: 2 bits per packed plane c at 2c: the 2x2 cell position (2 * row + col) that raw_pattern maps to plane c
+    float dark_black[4];   // nominal black level per packed plane (X-Trans: [0])
 };
+
+// the image's crop of a dark frame (ELD_DARK): uniform over the block
+struct DarkCrop { const uint16_t* src; uint32_t Wm, y0, x0; bool ok, wide; };
 
 // ---------------------------------------------------------------------------------------------
 // Poisson(lam), exact, float32 (replaces the internals of np.random.poisson that noise.py:159 calls; the CPU statement of
@@ -201,6 +219,87 @@ __device__ __forceinline__ float row_normal(uint32_t srow, const SamplerRng& rng
     return box_muller(w.x, w.y).x;
 }
 
+// ---- ELD_DARK ---------------------------------------------------------------------------------------------------------------------------
+// The crop of image n: w = Philox(index 0, sample id, STREAM_DARK); frame = first + umulhi(w.x, count) of the record's range; offsets uniform
+// over the valid ones (X-Trans: the even ones).  Every operand is uniform over the block; readfirstlane tells the compiler so (the table
+// entry becomes a scalar load).  The checks are load_patch's (framepool.hip): ok == false -> the image is skipped.
+__device__ __forceinline__ DarkCrop dark_select(const NoiseArgs& a, const EldNoiseParams& P, const SamplerRng& rng, bool xt) {
+    DarkCrop d;
+    d.src = a.pool; d.Wm = d.y0 = d.x0 = 0; d.ok = d.wide = false;
+    const uint32_t first = P.reserved[0], count = P.reserved[1], F = (uint32_t)a.F;
+    if (count == 0u || first >= F || count > F - first) return d;
+    const uint4 w = rng.words(0u, STREAM_DARK);
+    const uint32_t fi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(first + __umulhi(w.x, count)));
+    const EldPoolFrame f = a.frames[fi];
+    if (f.Hm < 2 || f.Wm < 2 || (f.Wm & 1) || (f.offset & 1)) return d;          // 4-byte loads: even row pitch and frame start
+    const uint64_t area = (uint64_t)f.Hm * (uint64_t)f.Wm;
+    if (f.offset > a.pool_elems || area > a.pool_elems - f.offset) return d;
+    const uint32_t hp = xt ? 2u * ((uint32_t)f.Hm / 6u) : (uint32_t)f.Hm / 2u, wp = xt ? 2u * ((uint32_t)f.Wm / 6u) : (uint32_t)f.Wm / 2u;
+    if (a.H > hp || a.W > wp) return d;
+    const uint32_t y0 = xt ? 2u * __umulhi(w.y, (hp - a.H) / 2u + 1u) : __umulhi(w.y, hp - a.H + 1u);
+    const uint32_t x0 = xt ? 2u * __umulhi(w.z, (wp - a.W) / 2u + 1u) : __umulhi(w.z, wp - a.W + 1u);
+    d.y0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)y0);
+    d.x0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)x0);
+    d.src = a.pool + f.offset; d.Wm = (uint32_t)f.Wm;
+    // 16-byte loads (Bayer, VEC): every row segment a lane reads starts on a 16-byte boundary (the pool base is 16-byte aligned: checked by the entry)
+    d.wide = !xt && ((f.offset + (uint64_t)(2u * d.x0)) & 7) == 0 && (f.Wm & 7) == 0;
+    d.ok = true;
+    return d;
+}
+
+// mosaic site of packed X-Trans element (c, i, j): eld_pack_xtrans's index map (xtrans.h)
+__device__ __forceinline__ size_t xt_site(uint32_t c, uint32_t i, uint32_t j, uint32_t Wm) {
+    uint32_t row, col;
+    if (c < 5u) { row = 6u * (i >> 1) + XT_RC[c][i & 1u][j & 1u][0]; col = 6u * (j >> 1) + XT_RC[c][i & 1u][j & 1u][1]; }
+    else { row = 3u * i + XT_RC3[c - 5u][0]; col = 3u * j + XT_RC3[c - 5u][1]; }
+    return (size_t)row * Wm + col;
+}
+
+__device__ __forceinline__ float dark_black(const NoiseArgs& a, uint32_t c) {
+    return c == 0u ? a.dark_black[0] : c == 1u ? a.dark_black[1] : c == 2u ? a.dark_black[2] : a.dark_black[3];
+}
+
+// float(code) - black_c of the group's elements e0 .. e0 + 3 (VEC: one row segment of one plane; r_vec = its flattened row c * H + h)
+template <bool VEC>
+__device__ __forceinline__ void dark_load(const NoiseArgs& a, const DarkCrop& dk, bool xt, uint32_t e0, uint32_t nvalid, uint32_t g, uint32_t r_vec,
+                                          float (&v)[4]) {
+    if (VEC) {
+        const uint32_t c = fdiv_u32(r_vec, a.divH), h = r_vec - c * a.H, w0 = 4u * (g - r_vec * a.divW.d);
+        if (xt) {
+            const float black = a.dark_black[0];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (float)dk.src[xt_site(c, dk.y0 + h, dk.x0 + w0 + (uint32_t)j, dk.Wm)] - black;
+        } else {
+            // plane c sits at cell position (pr, pc): packed columns x0 + w0 .. + 3 are the codes at 2 (x0 + w0) + pc, + 2, + 4, + 6 of mosaic row 2 (y0 + h) + pr
+            const uint32_t pos = (a.dark_pos >> (2u * c)) & 3u, pr = pos >> 1, pc = pos & 1u;
+            const uint16_t* s = dk.src + (size_t)(2u * (dk.y0 + h) + pr) * dk.Wm + 2u * (dk.x0 + w0);
+            uint32_t w[4];
+            if (dk.wide) {
+                const uint4 q = *reinterpret_cast<const uint4*>(s);
+                w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) w[j] = reinterpret_cast<const uint32_t*>(s)[j];
+            }
+            const float black = dark_black(a, c);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = (float)(pc ? w[j] >> 16 : w[j] & 0xffffu) - black;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if ((uint32_t)j >= nvalid) continue;
+            const uint32_t e = e0 + (uint32_t)j, r = fdiv_u32(e, a.divW), c = fdiv_u32(r, a.divH), h = r - c * a.H, x = e - r * a.W;
+            if (xt) {
+                v[j] = (float)dk.src[xt_site(c, dk.y0 + h, dk.x0 + x, dk.Wm)] - a.dark_black[0];
+            } else {
+                const uint32_t pos = (a.dark_pos >> (2u * c)) & 3u;
+                v[j] = (float)dk.src[(size_t)(2u * (dk.y0 + h) + (pos >> 1)) * dk.Wm + 2u * (dk.x0 + x) + (pos & 1u)] - dark_black(a, c);
+            }
+        }
+    }
+}
+
 template <bool VEC>
 __device__ __forceinline__ void load_y4(const NoiseArgs& a, size_t img_off /* n * in_stride */, uint32_t e0, uint32_t nvalid, float (&y)[4]) {
     if (VEC) {
@@ -230,6 +329,7 @@ template <bool VEC, uint32_t TFLAGS, bool DEBUG>
 __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a) {
     constexpr bool MAYBE_P = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_SHOT_POISSON);
     constexpr bool MAYBE_X = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_CFA_XTRANS);
+    constexpr bool MAYBE_D = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_DARK);
     __shared__ float s_row[MAX_LDS_ROWS];
     __shared__ uint32_t s_cnt[MAYBE_P ? ELEMS_PER_BLOCK : 1];     // (count << 9) | low 9 bits of the pixel's POIS_V word (free: u01 takes w >> 9)
     __shared__ uint4 s_qp[MAYBE_P ? QP_CAP : 1];
@@ -253,6 +353,15 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
     const bool xt = MAYBE_X && (flags & ELD_CFA_XTRANS);            // X-Trans row map / colour bias (Bayer kernels: false at compile time)
     const uint32_t rows_per = xt ? 3u : 1u;                          // staged row normals per packed row
     const float S = P.saturation, ratio = P.ratio, K = P.K;
+
+    // ---- ELD_DARK: which frame, where (before any barrier: a skipped image leaves as a whole block) ----------------------------
+    const bool do_dark = MAYBE_D && (flags & ELD_DARK);
+    DarkCrop dk;
+    dk.src = nullptr; dk.Wm = dk.y0 = dk.x0 = 0; dk.ok = dk.wide = false;
+    if (do_dark) {
+        dk = dark_select(a, P, rng, xt);
+        if (!dk.ok) return;
+    }
 
     const uint32_t wave = tid >> 6;
     if (do_pois) {
@@ -452,7 +561,10 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
         }
 
         uint32_t r_vec = 0;
-        if (VEC && (flags & (ELD_ROW | ELD_CBIAS))) r_vec = fdiv_u32(g, a.divW);
+        if (VEC && ((flags & (ELD_ROW | ELD_CBIAS)) || do_dark)) r_vec = fdiv_u32(g, a.divW);
+
+        float v_dark[4] = {0.f, 0.f, 0.f, 0.f};     // float(code) - black_c of the lane's four elements
+        if (do_dark) dark_load<VEC>(a, dk, xt, e0, nvalid, g, r_vec, v_dark);
 
         float z[4];
 #pragma unroll
@@ -503,6 +615,7 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
                 }
                 zz = zz + v_nrow * P.row_scale;
             }
+            if (do_dark) zz = zz + v_dark[j];
             if (flags & ELD_QUANT) {
                 if (inject) v_uq = a.inject[ELD_PLANE_UQ * a.total + ge];
                 else if (uq_borrow) v_uq = (float)(((pick(w_tl, j) & 511u) << 9) | (pick(cw, j) & 511u)) * 0x1p-18f;
@@ -595,21 +708,51 @@ extern "C" int eld_noise_forward(const void* in, int in_dtype, float* out, const
     return eld_noise_forward_strided(in, in_dtype, chw, out, chw, params, N, C, H, W, flags, seed, inject, dump, stream);
 }
 
-extern "C" int eld_noise_forward_strided(const void* in, int in_dtype, size_t in_image_stride, float* out, size_t out_image_stride,
-                                         const EldNoiseParams* params, int N, int C, int H, int W, uint32_t flags, uint64_t seed,
-                                         const float* inject, float* dump, void* stream) {
+// the pool side of eld_noise_forward_dark as the host hands it over
+struct DarkPoolArgs { const uint16_t* pool; size_t pool_elems; const EldPoolFrame* frames; int F, min_h, min_w; const int* raw_pattern; const float* black_level; };
+
+static int noise_forward(const void* in, int in_dtype, size_t in_image_stride, float* out, size_t out_image_stride,
+                         const EldNoiseParams* params, int N, int C, int H, int W, uint32_t flags, uint64_t seed,
+                         const float* inject, float* dump, const DarkPoolArgs* dark, void* stream) {
     if (N < 0 || C < 0 || H < 0 || W < 0) return ELD_EINVAL;
     if (in_dtype != ELD_IN_F32 && in_dtype != ELD_IN_U16) return ELD_EINVAL;
     if ((flags & ELD_SHOT_POISSON) && (flags & ELD_SHOT_GAUSS)) return ELD_EINVAL;   // 'P' wins in the parser (noise.py:158-160)
     if ((flags & ELD_CFA_XTRANS) && C != 9) return ELD_EINVAL;
     if ((flags & (ELD_ROW | ELD_CBIAS)) && !(C == 4 || ((flags & ELD_CFA_XTRANS) && C == 9))) return ELD_EINVAL;
-    if (!(flags & (ELD_ROW | ELD_CBIAS))) flags &= ~ELD_CFA_XTRANS;   // the per-pixel terms do not depend on the layout: same kernels as without
+    NoiseArgs a;
+    a.pool = nullptr; a.pool_elems = 0; a.frames = nullptr; a.F = 0; a.dark_pos = 0;
+    for (int k = 0; k < 4; ++k) a.dark_black[k] = 0.f;
+    if (flags & ELD_DARK) {                                  // what the host can see of the pool (the table and the records are device memory)
+        if (!dark) return ELD_EINVAL;                        // the entries without a pool
+        if (flags & (ELD_READ_GAUSS | ELD_READ_TL | ELD_ROW | ELD_CBIAS)) return ELD_EINVAL;      // the dark frame holds these terms already
+        const bool x = (flags & ELD_CFA_XTRANS) != 0;
+        if (C != (x ? 9 : 4)) return ELD_EINVAL;
+        if (!dark->pool || !dark->frames || ((uintptr_t)dark->pool & 15) || ((uintptr_t)dark->frames & 7)) return ELD_EINVAL;
+        if (dark->F <= 0 || dark->pool_elems == 0 || dark->min_h <= 0 || dark->min_w <= 0 || H > dark->min_h || W > dark->min_w) return ELD_EINVAL;
+        if (!dark->black_level) return ELD_EINVAL;
+        if (x) {
+            if (!(dark->black_level[0] >= 0.f)) return ELD_EINVAL;
+            a.dark_black[0] = dark->black_level[0];
+        } else {
+            if (!dark->raw_pattern) return ELD_EINVAL;
+            bool seen[4] = {false, false, false, false};
+            for (int i = 0; i < 4; ++i) {                    // a permutation of 0..3, as eld_pack_raw_bayer_u16: cell position i holds plane k
+                const int k = dark->raw_pattern[i];
+                if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
+                seen[k] = true;
+                if (!(dark->black_level[k] >= 0.f)) return ELD_EINVAL;
+                a.dark_pos |= (uint32_t)i << (2 * k);
+                a.dark_black[k] = dark->black_level[k];
+            }
+        }
+        a.pool = dark->pool; a.pool_elems = dark->pool_elems; a.frames = dark->frames; a.F = dark->F;
+    }
+    if (!(flags & (ELD_ROW | ELD_CBIAS | ELD_DARK))) flags &= ~ELD_CFA_XTRANS;   // the per-pixel terms do not depend on the layout: same kernels as without
     const size_t chw = (size_t)C * H * W;
     if (N == 0 || chw == 0) return 0;               // empty input: nothing to do (reference returns an empty array)
     if (!in || !out || !params) return ELD_EINVAL;
     if (chw >= (1ull << 32) - 4) return ELD_ENOTSUP;
 
-    NoiseArgs a;
     a.in = in; a.out = out; a.params = params; a.inject = inject; a.dump = dump;
     a.total = (size_t)N * chw;
     if (out_image_stride < chw && N > 1) return ELD_EINVAL;          // outputs must not overlap (inputs may: stride 0 = one clean image)
@@ -635,7 +778,12 @@ extern "C" int eld_noise_forward_strided(const void* in, int in_dtype, size_t in
     // compile-time specialisations of the hot model strings (dead terms and their registers vanish)
     constexpr uint32_t FULL = ELD_SHOT_POISSON | ELD_READ_TL | ELD_ROW | ELD_QUANT;   // 'PGRU' -- BASELINE.json config 2
     constexpr uint32_t PG = ELD_SHOT_POISSON | ELD_READ_GAUSS;                        // 'Pg'   -- config 1
+    constexpr uint32_t PDU = ELD_SHOT_POISSON | ELD_DARK | ELD_QUANT;                 // 'PDU'  -- shot noise + the sensor's own dark frames
     switch (flags) {
+        case PDU: return launch_noise<true, PDU, false>(a, N, st);
+        case PDU | ELD_CLIP: return launch_noise<true, PDU | ELD_CLIP, false>(a, N, st);
+        case PDU | ELD_CFA_XTRANS: return launch_noise<true, PDU | ELD_CFA_XTRANS, false>(a, N, st);
+        case PDU | ELD_CFA_XTRANS | ELD_CLIP: return launch_noise<true, PDU | ELD_CFA_XTRANS | ELD_CLIP, false>(a, N, st);
         case FULL: return launch_noise<true, FULL, false>(a, N, st);
         case FULL | ELD_CLIP: return launch_noise<true, FULL | ELD_CLIP, false>(a, N, st);
         case FULL | ELD_CFA_XTRANS: return launch_noise<true, FULL | ELD_CFA_XTRANS, false>(a, N, st);                          // 'PGRU' on X-Trans
@@ -650,6 +798,21 @@ extern "C" int eld_noise_forward_strided(const void* in, int in_dtype, size_t in
         case ELD_CLIP: return launch_noise<true, ELD_CLIP, false>(a, N, st);
         default: return launch_noise<true, RUNTIME_FLAGS, false>(a, N, st);
     }
+}
+
+extern "C" int eld_noise_forward_strided(const void* in, int in_dtype, size_t in_image_stride, float* out, size_t out_image_stride,
+                                         const EldNoiseParams* params, int N, int C, int H, int W, uint32_t flags, uint64_t seed,
+                                         const float* inject, float* dump, void* stream) {
+    return noise_forward(in, in_dtype, in_image_stride, out, out_image_stride, params, N, C, H, W, flags, seed, inject, dump, nullptr, stream);
+}
+
+extern "C" int eld_noise_forward_dark(const void* in, int in_dtype, size_t in_image_stride, float* out, size_t out_image_stride,
+                                      const EldNoiseParams* params, int N, int C, int H, int W, uint32_t flags, uint64_t seed,
+                                      const float* inject, float* dump,
+                                      const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int min_h, int min_w,
+                                      const int* raw_pattern, const float* black_level, void* stream) {
+    const DarkPoolArgs d = {pool, pool_elems, frames, F, min_h, min_w, raw_pattern, black_level};
+    return noise_forward(in, in_dtype, in_image_stride, out, out_image_stride, params, N, C, H, W, flags, seed, inject, dump, &d, stream);
 }
 
 // ---------------------------------------------------------------------------------------------

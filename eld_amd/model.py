@@ -278,7 +278,7 @@ class ELDModel:
         out = None
         for k in range(burst):                   # frame k of image i carries id sample_ids[i*burst + k]
             out = sample_noise_records(clean, set_sample_ids(recs, sample_ids[k::burst]), flags, self.seed, in_u16=in_u16, out=out,
-                                       burst_index=k, burst=burst)
+                                       burst_index=k, burst=burst, dark=getattr(nm, 'dark', None))
         return out
 
     # ---- ELD_model.py:422-432 -------------------------------------------------------------------------------

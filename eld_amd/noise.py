@@ -12,7 +12,9 @@ Differences a user can observe, all documented in DESIGN.md:
   * besides ndarray (C,H,W) in / ndarray out, `__call__` accepts a CUDA tensor (C,H,W) or
     (N,C,H,W) and then returns a CUDA tensor without touching the host;
   * model letters G / R / U / B select the withheld ELD terms (Tukey-lambda read, row,
-    quantisation, colour bias) -- the reference ignores unknown letters (noise.py:158-166).
+    quantisation, colour bias) -- the reference ignores unknown letters (noise.py:158-166);
+  * model letter D takes every signal-independent term from the sensor's own dark frames instead
+    (NoiseModel(model='PDU', dark=DarkPool(...)), eld_amd/darkpool.py): it excludes g / G / R / B.
 There is no CPU path: calling the plugin without a GPU / built library raises.
 """
 import json
@@ -44,6 +46,8 @@ def model_flags(model, cfa='bayer'):
         f |= L.QUANT
     if 'B' in model:
         f |= L.CBIAS
+    if 'D' in model:
+        f |= L.DARK
     return f
 
 
@@ -61,10 +65,11 @@ class NoiseParams(tuple):
     """(K, g_scale, saturation_level, ratio) exactly as noise.py:225 returns it; the withheld-model
     terms ride along as attributes so burst call sites (sid_dataset.py:269-272) keep working."""
     def __new__(cls, K, g_scale, saturation_level, ratio, tl_lambda=0.0, tl_scale=0.0, row_scale=0.0,
-                q_step=1.0, color_bias=(0.0, 0.0, 0.0, 0.0)):
+                q_step=1.0, color_bias=(0.0, 0.0, 0.0, 0.0), dark=None):
         self = super().__new__(cls, (K, g_scale, saturation_level, ratio))
         self.tl_lambda, self.tl_scale, self.row_scale, self.q_step = tl_lambda, tl_scale, row_scale, q_step
         self.color_bias = tuple(color_bias)
+        self.dark = None if dark is None else (int(dark[0]), int(dark[1]))      # model 'D': (first, count) of the session's frames in the DarkPool's table
         return self
 
     @classmethod
@@ -74,7 +79,7 @@ class NoiseParams(tuple):
         if isinstance(p, dict):
             return cls(p['K'], p['g_scale'], p.get('saturation', 16383 - 800), p['ratio'], p.get('tl_lambda', 0.0),
                        p.get('tl_scale', 0.0), p.get('row_scale', 0.0), p.get('q_step', 1.0),
-                       p.get('color_bias', (0.0,) * 4))
+                       p.get('color_bias', (0.0,) * 4), p.get('dark'))
         K, g, s, r = p
         return cls(K, g, s, r)
 
@@ -85,6 +90,7 @@ class NoiseParams(tuple):
             self.tl_lambda, self.tl_scale, self.row_scale, self.q_step
         rec['color_bias'] = self.color_bias
         rec['sample_id_lo'], rec['sample_id_hi'] = sample_id & 0xFFFFFFFF, (sample_id >> 32) & 0xFFFFFFFF
+        rec['reserved'] = self.dark if self.dark is not None else (0, 0)
         return rec
 
 
@@ -158,10 +164,11 @@ def is_u16_codes(t):
     return t is not None and t.dtype in (torch.int16, torch.uint16)
 
 
-def sample_noise_records(y, recs, flags, seed, in_u16=False, inject=None, dump=None, out=None, burst_index=0, burst=1):
+def sample_noise_records(y, recs, flags, seed, in_u16=False, inject=None, dump=None, out=None, burst_index=0, burst=1, dark=None, dark_table=None):
     """The C-ABI sampler call.  y: CUDA (N,C,H,W) float32, or int16/uint16 LMDB codes when in_u16; recs: N structured records
     (host); out: CUDA float32 (N, burst*C, H, W) -- this call fills channels [burst_index*C, (burst_index+1)*C) of every image
-    (burst == 1: the whole tensor)."""
+    (burst == 1: the whole tensor).  flags with DARK: `dark` is the DarkPool the records' ranges refer to (eld_noise_forward_dark);
+    dark_table = (device table, F) replaces the pool's own frame table (DarkPool.launch_args)."""
     import torch
     assert y.is_cuda and y.is_contiguous() and y.dim() == 4
     N, C, H, W = y.shape
@@ -170,15 +177,25 @@ def sample_noise_records(y, recs, flags, seed, in_u16=False, inject=None, dump=N
         assert is_u16_codes(y), 'in_u16 needs int16/uint16 codes, got %s' % (y.dtype,)
     else:
         assert y.dtype == torch.float32
+    if int(flags) & L.DARK:
+        if dark is None:
+            raise ValueError("model letter 'D' (flag DARK) needs a DarkPool: NoiseModel(model=..., dark=pool)")
+        if (dark.cfa == 'xtrans') != bool(int(flags) & L.CFA_XTRANS):
+            raise ValueError('the DarkPool holds %s frames, the flags say %s' % (dark.cfa, 'xtrans' if int(flags) & L.CFA_XTRANS else 'bayer'))
+        dark.check_patch(H, W)
+        dark_args = dark.launch_args(dark_table)
     prm = _upload(np.ascontiguousarray(recs).view(np.uint8).reshape(-1), y.device)
     if out is None:
         out = torch.empty((N, burst * C, H, W), dtype=torch.float32, device=y.device)
     assert out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (N, burst * C, H, W)
     chw = C * H * W
     optr = None if out.numel() == 0 else C_void(out.data_ptr() + 4 * burst_index * chw)
-    rc = L.lib().eld_noise_forward_strided(L.dptr(y), L.IN_U16 if in_u16 else L.IN_F32, chw, optr, burst * chw, L.dptr(prm),
-                                           N, C, H, W, int(flags), int(seed) & (2 ** 64 - 1), L.dptr(inject), L.dptr(dump), L.cur_stream())
-    L.check(rc, 'eld_noise_forward_strided')
+    head = (L.dptr(y), L.IN_U16 if in_u16 else L.IN_F32, chw, optr, burst * chw, L.dptr(prm), N, C, H, W, int(flags), int(seed) & (2 ** 64 - 1),
+            L.dptr(inject), L.dptr(dump))
+    if int(flags) & L.DARK:
+        L.check(L.lib().eld_noise_forward_dark(*head, *dark_args, L.cur_stream()), 'eld_noise_forward_dark')
+    else:
+        L.check(L.lib().eld_noise_forward_strided(*head, L.cur_stream()), 'eld_noise_forward_strided')
     return out
 
 
@@ -187,10 +204,10 @@ def C_void(addr):
     return ctypes.c_void_p(addr)
 
 
-def sample_noise(y, params, flags, seed, sample_ids, in_u16=False, inject=None, dump=None, out=None):
+def sample_noise(y, params, flags, seed, sample_ids, in_u16=False, inject=None, dump=None, out=None, dark=None):
     """Device-side batched sampler call.  y: CUDA tensor (N,C,H,W) float32 (or uint16 codes viewed as
-    int16 when in_u16); params: list of N NoiseParams; returns CUDA float32 tensor (N,C,H,W)."""
-    return sample_noise_records(y, make_records(params, sample_ids), flags, seed, in_u16=in_u16, inject=inject, dump=dump, out=out)
+    int16 when in_u16); params: list of N NoiseParams; returns CUDA float32 tensor (N,C,H,W).  dark: the DarkPool of flag DARK."""
+    return sample_noise_records(y, make_records(params, sample_ids), flags, seed, in_u16=in_u16, inject=inject, dump=dump, out=out, dark=dark)
 
 
 def decode_augment_u16(codes, bits=None):
@@ -368,7 +385,7 @@ class NoiseModelBase:  # same name / role as noise.py:148
             plist = params
         else:
             plist = [params] * N
-        out = sample_noise(t, plist, self.flags(), self.seed, self._next_ids(N))
+        out = sample_noise(t, plist, self.flags(), self.seed, self._next_ids(N), dark=getattr(self, 'dark', None))
         if single:
             out = out[0]
         return out.cpu().numpy() if as_np else out
@@ -377,10 +394,18 @@ class NoiseModelBase:  # same name / role as noise.py:148
 class NoiseModel(NoiseModelBase):
     last_instance = None
 
-    def __init__(self, model='g', cameras=None, include=None, exclude=None, cfa='bayer', param_dir=None):
+    def __init__(self, model='g', cameras=None, include=None, exclude=None, cfa='bayer', param_dir=None, dark=None):
         super().__init__()
         assert cfa in ['bayer', 'xtrans']                   # noise.py:177
         assert include is None or exclude is None           # noise.py:178
+        if 'D' in model:          # the dark frames hold every signal-independent term of the sensor: a parametric one next to them counts it twice
+            if dark is None:
+                raise ValueError("NoiseModel(model=%r): 'D' samples the sensor's dark frames and needs dark=DarkPool(...)" % (model,))
+            if any(ch in model for ch in 'gGRB'):
+                raise ValueError("NoiseModel(model=%r): 'D' excludes g, G, R and B (the dark frames contain those terms)" % (model,))
+            if dark.cfa != cfa:
+                raise ValueError('NoiseModel(model=%r, cfa=%r): the DarkPool holds %s frames' % (model, cfa, dark.cfa))
+        self.dark = dark
         self.cameras = cameras or list(ALL_CAMERAS)
         if include is not None:                             # noise.py:181-182
             self.cameras = [self.cameras[include]]
@@ -426,6 +451,11 @@ class NoiseModel(NoiseModelBase):
         K = np.exp(log_K)
         g_scale = np.exp(log_g_scale)
         ratio = np.random.uniform(low=100, high=300)
+        if 'D' in self.model:     # after the reference's five draws: one session of the pool.  Its K, the pool's saturation; the kernel draws frame and crop
+            if self.dark.K is None:
+                raise ValueError("the DarkPool has no session gains: DarkPool(..., K=diag['K'])")
+            si = int(np.random.randint(self.dark.sessions))
+            return NoiseParams(float(self.dark.K[si]), g_scale, self.dark.saturation, ratio, q_step=1.0, dark=self.dark.ranges[si])
         if not any(ch in self.model for ch in 'GRUB'):
             return NoiseParams(K, g_scale, saturation_level, ratio)
 

@@ -8,7 +8,11 @@ The frames are uint16 mosaics (.npy, rawpy's raw_image_visible of clean long exp
 (eld_amd.framepool) and every batch is cut, synthesised and trained on the device.  --meta is the JSON sidecar eld_amd.denoise reads (cfa,
 raw_pattern, black_level, white_point, or rawpy's names).  --camera is a table eld_amd.calibrate wrote (<dir>/<name>_params.npy) or the
 name of a release camera.  The checkpoint is the reference's dict ({'netG': ..., 'opt_g': ..., ...}), what eld_amd.denoise.load_denoiser
-reads."""
+reads.
+
+--noise PDU --dark manifest.json takes the signal-independent noise from the sensor's own dark frames instead of a fitted law: the bias
+frames of calibrate's manifest are uploaded as a DarkPool (eld_amd.darkpool) and the sampler adds a random crop of one of them to every
+patch.  The session gains come from a calibration of that manifest; --camera still names the table NoiseModel reads."""
 import argparse
 import glob
 import os
@@ -30,6 +34,7 @@ def build_parser():
     p.add_argument('--defects', metavar='PATH', help='a defect map written by eld_amd.defects (.npz): the frames are repaired once, at upload')
     p.add_argument('--camera', default='SonyA7S2', help='a table written by eld_amd.calibrate (<dir>/<name>_params.npy) or a release camera name')
     p.add_argument('--noise', default='PGRU', help="noise model letters of NoiseModel(model=...) (default 'PGRU')")
+    p.add_argument('--dark', metavar='MANIFEST', help="calibrate's manifest JSON: its bias frames become the dark-frame pool of noise letter D (--noise PDU)")
     p.add_argument('--patch', type=int, default=512, help='packed patch side (default 512)')
     p.add_argument('--batch', type=int, default=1, help='patches per step (default 1)')
     p.add_argument('--epochs', type=int, default=1)
@@ -40,14 +45,30 @@ def build_parser():
     return p
 
 
-def noise_model(camera, letters, cfa):
+def noise_model(camera, letters, cfa, dark=None):
     from .noise import NoiseModel
     if camera.endswith('.npy') or os.path.exists(camera):
         name = os.path.basename(camera)
         if not name.endswith('_params.npy') or not os.path.exists(camera):
             raise ValueError('--camera: %s is not a <name>_params.npy table written by eld_amd.calibrate' % camera)
-        return NoiseModel(model=letters, cameras=[name[:-len('_params.npy')]], cfa=cfa, param_dir=os.path.dirname(camera) or '.')
-    return NoiseModel(model=letters, cameras=[camera], cfa=cfa)
+        return NoiseModel(model=letters, cameras=[name[:-len('_params.npy')]], cfa=cfa, param_dir=os.path.dirname(camera) or '.', dark=dark)
+    return NoiseModel(model=letters, cameras=[camera], cfa=cfa, dark=dark)
+
+
+def dark_pool(manifest, camera, letters, patch, device=None):
+    """--dark: the manifest's bias frames as a DarkPool (None without the letter D; the letter without --dark is an error, and so is --dark
+    without the letter).  A --camera that is a table file is handed on, so that a manifest which does not belong to it is refused; the patch
+    must fit the smallest dark frame."""
+    if 'D' not in letters:
+        if manifest is not None:
+            raise ValueError('--dark needs the noise letter D (--noise PDU), got --noise %s' % letters)
+        return None
+    if manifest is None:
+        raise ValueError("--noise %s: the letter D samples the sensor's dark frames and needs --dark manifest.json" % letters)
+    from .darkpool import DarkPool
+    pool = DarkPool.from_manifest(manifest, K=camera if camera.endswith('.npy') else None, device=device)
+    pool.check_patch(patch, patch)
+    return pool
 
 
 def main(argv=None):
@@ -70,7 +91,10 @@ def main(argv=None):
     pool = FramePool(mosaics, cfa=cfa, defects=a.defects if a.defects is not None else side.get('defects'), **o)
     if pool.buffer is None:
         raise RuntimeError('eld_amd.train_frames needs a GPU: there is no CPU fallback')
-    nm = noise_model(a.camera, a.noise, cfa)
+    dark = dark_pool(a.dark, a.camera, a.noise, a.patch, device=pool.device)
+    if dark is not None and dark.cfa != cfa:
+        raise ValueError('--dark: the manifest holds %s frames, the clean frames are %s' % (dark.cfa, cfa))
+    nm = noise_model(a.camera, a.noise, cfa, dark=dark)
     loader = FramePoolLoader(pool, nm, a.batch, patch=a.patch, steps_per_epoch=a.steps)
     out = os.path.abspath(a.out)
     opt = types.SimpleNamespace(gpu_ids=[pool.device.index], isTrain=True, checkpoints_dir=os.path.dirname(out), name='.',

@@ -26,7 +26,8 @@ from . import _lib as L
 from . import calibrate as CAL
 from .noise import NoiseParams, model_flags, table_cfa
 
-MODEL_LETTERS = 'PpgGRUB'
+MODEL_LETTERS = 'PpgGRUBD'
+DARK_EXCLUDES = 'gGRB'                            # the terms a dark frame already holds: not next to D
 MAX_RADIUS = 32767
 XT_PLANE_COLOUR = (0, 1, 2, 0, 2, 1, 1, 1, 1)     # packed X-Trans plane -> colour (R 0, G 1, B 2): planes 0, 3 R; 1, 5-8 G; 2, 4 B
 ID_BASE = 1 << 62                                 # validation streams lie far from the sample ids a training run counts up from 0
@@ -48,6 +49,9 @@ def _models(models):
     for m in models:
         if not isinstance(m, str) or not m or any(ch not in MODEL_LETTERS for ch in m):
             raise ValueError('unknown noise model %r: the letters are %s' % (m, ', '.join(MODEL_LETTERS)))
+        if 'D' in m and any(ch in m for ch in DARK_EXCLUDES):
+            raise ValueError("noise model %r: D takes the signal-independent noise from the sensor's dark frames and excludes %s"
+                             % (m, ', '.join(DARK_EXCLUDES)))
     if len(set(models)) != len(models):
         raise ValueError('a noise model is named twice: %r' % (models,))
     return models
@@ -205,10 +209,19 @@ def _noise_params(p, sat):
     return NoiseParams(float(p[0]), float(p[1]), float(sat), 1.0, float(p.tl_lambda), float(p.tl_scale), float(p.row_scale), 1.0, cb)
 
 
-def _sample(clean, params, model, cfa, seed, ids):
-    """The sampler on clean (N,C,h,w) float32 CUDA with one parameter record and N sample ids -> float32 (N,C,h,w)."""
+def _sample(clean, params, model, cfa, seed, ids, dark=None, dark_table=None):
+    """The sampler on clean (N,C,h,w) float32 CUDA with one parameter record and N sample ids -> float32 (N,C,h,w).  dark, dark_table:
+    the DarkPool and the frame table of a model with D (sample_noise_records)."""
     from .noise import make_records, sample_noise_records
-    return sample_noise_records(clean, make_records([params] * len(ids), ids), model_flags(model, cfa), seed)
+    return sample_noise_records(clean, make_records([params] * len(ids), ids), model_flags(model, cfa), seed, dark=dark, dark_table=dark_table)
+
+
+def _leave_one_out(pool, first, count, omit):
+    """The frame table of one session without its frame `omit`, on the pool's device -> ((tensor, count - 1), (0, count - 1)): the table
+    argument of the sampler and the range a record names in it."""
+    import torch
+    rows = np.delete(pool.pool.frames[first:first + count], omit)
+    return (torch.from_numpy(rows.view(np.uint8).copy()).to(pool.pool.device), len(rows)), (0, len(rows))
 
 
 def synthesize_codes(clean, params, model, cfa, seed, sample_id, white, black, shape=None):
@@ -319,7 +332,12 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     frame at sample_id(s, f, i, d); kl = KL(real || syn_0), floor = KL(syn_0 || syn_1), each the mean over the colour groups ('kl_groups',
     'floor_groups' hold the G values).  Flat pair j: real = histogram of a - b; syn = histogram of q(x_0) - q(x_1) on the clean image
     clean_from_flat_pair, ids sample_id(s, F + j, i, d); kl_flat = KL(real || syn).  A defects map masks the real side only (synthetic
-    frames have no defects; probabilities are normalised).  best = the model of lowest mean bias-frame kl, lowest index on a tie.
+    frames have no defects; probabilities are normalised).
+    A model with the letter D (e.g. 'PD', 'PDU') takes its signal-independent noise from the sensor's own frames: for bias frame f the draws
+    read the session's OTHER bias frames (leave-one-out: the frame table handed to the sampler omits f; with defects the pooled frames are
+    repaired), the clean image is zero and K the frame's.  Such rows carry 'dark': 'leave-one-out'; they apply to bias frames only (kl_flat
+    is None) and every session needs at least two bias frames (ValueError).  kl of 'PD' against its floor is how close two real frames of
+    the sensor are to each other: the yardstick the parametric rows are read against.  best = the model of lowest mean bias-frame kl, lowest index on a tie.
     This is a check of marginal distributions per colour group: it does not test the spatial structure of row noise."""
     cfa = CAL._cfa(cfa)
     models = _models(models)
@@ -339,6 +357,11 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         _check_session_shapes(sessions, cfa)
     if len(sessions) >= 1 << 20:
         raise ValueError('too many sessions')
+    with_dark = any('D' in m for m in models)
+    if with_dark:
+        for i, s in enumerate(sessions):
+            if CAL._shape(s['bias'])[0] < 2:
+                raise ValueError('session %d has a single bias frame: a model with D draws from the OTHER bias frames of the session' % i)
     centre = group_black(cfa, black)
     sat = float(white_level) - float(black.max())
     if not sat > 0:
@@ -368,6 +391,11 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         if 'frames' not in diag or len(diag['frames']) != nb:
             raise ValueError("source='frames' needs diag['frames'] with one record per bias frame (%d)" % nb)
 
+    dpool = None
+    if with_dark:
+        from .darkpool import DarkPool
+        dpool = DarkPool([{'bias': s['bias']} for s in sessions], cfa=cfa, raw_pattern=None if cfa == 'xtrans' else raw_pattern, black_level=black,
+                         white_level=white_level, defects=defects)
     report = {'models': models, 'source': source, 'cfa': cfa, 'groups': G, 'radius': R, 'flat_radius': RF, 'alpha': float(alpha), 'seed': int(seed),
               'sessions': []}
     hists = {}
@@ -390,11 +418,20 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         for f in range(F):
             frep = {'params': fparams[f], 'models': {}}
             prm = _noise_params(fparams[f], sat)
+            if dpool is not None:
+                loo_table, loo_range = _leave_one_out(dpool, dpool.ranges[si][0], F, f)
+                dprm = NoiseParams(prm[0], prm[1], prm[2], prm[3], q_step=1.0, dark=loo_range)
             for mi, m in enumerate(models):
-                x = _sample(dark, prm, m, cfa, seed, [sample_id(si, f, mi, 0), sample_id(si, f, mi, 1)])
+                ids = [sample_id(si, f, mi, 0), sample_id(si, f, mi, 1)]
+                if 'D' in m:
+                    x = _sample(dark, dprm, m, cfa, seed, ids, dark=dpool, dark_table=loo_table)
+                else:
+                    x = _sample(dark, prm, m, cfa, seed, ids)
                 syn = histogram_f32(x, sat, R, cfa)
                 klg, flg = kl_divergence(real[f], syn[0], alpha), kl_divergence(syn[0], syn[1], alpha)
                 frep['models'][m] = {'kl': float(klg.mean()), 'floor': float(flg.mean()), 'kl_groups': klg.tolist(), 'floor_groups': flg.tolist()}
+                if 'D' in m:
+                    frep['models'][m]['dark'] = 'leave-one-out'
                 if keep_hist:
                     hists['s%d_f%d_%s' % (si, f, m)] = syn
             srep['frames'].append(frep)
@@ -408,6 +445,9 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
             y2 = torch.stack([y, y])
             prep = {'models': {}}
             for mi, m in enumerate(models):
+                if 'D' in m:                                   # dark frames stand for the noise of bias frames only
+                    prep['models'][m] = {'kl_flat': None, 'kl_flat_groups': None, 'dark': 'leave-one-out'}
+                    continue
                 x = _sample(y2, prm, m, cfa, seed, [sample_id(si, F + j, mi, 0), sample_id(si, F + j, mi, 1)])
                 syn = histogram_f32(x[:1], sat, RF, cfa, subtract=x[1:])
                 klg = kl_divergence(realf[j], syn[0], alpha)
@@ -419,12 +459,14 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
             hists['s%d_real_flats' % si] = realf
         srep['means'] = {m: {'kl': float(np.mean([fr['models'][m]['kl'] for fr in srep['frames']])),
                              'floor': float(np.mean([fr['models'][m]['floor'] for fr in srep['frames']])),
-                             'kl_flat': float(np.mean([pr['models'][m]['kl_flat'] for pr in srep['flats']]))} for m in models}
+                             'kl_flat': None if 'D' in m else float(np.mean([pr['models'][m]['kl_flat'] for pr in srep['flats']]))} for m in models}
         report['sessions'].append(srep)
     report['means'] = {m: {k: float(np.mean([fr['models'][m][k] for s in report['sessions'] for fr in s['frames']])) for k in ('kl', 'floor')}
                        for m in models}
     for m in models:
-        report['means'][m]['kl_flat'] = float(np.mean([pr['models'][m]['kl_flat'] for s in report['sessions'] for pr in s['flats']]))
+        report['means'][m]['kl_flat'] = None if 'D' in m else float(np.mean([pr['models'][m]['kl_flat'] for s in report['sessions'] for pr in s['flats']]))
+        if 'D' in m:
+            report['means'][m]['dark'] = 'leave-one-out'
     report['best'] = models[int(np.argmin([report['means'][m]['kl'] for m in models]))]      # argmin: the lowest index on a tie
     if keep_hist:
         report['hist'] = hists
@@ -487,7 +529,8 @@ def main(argv=None):
     for si, s in enumerate(rep['sessions']):
         for m in rep['models']:
             mm = s['means'][m]
-            print('session %d iso %-6s %-6s kl %.5f  floor %.5f  kl_flat %.5f' % (si, s['iso'], m, mm['kl'], mm['floor'], mm['kl_flat']))
+            flat = 'kl_flat %.5f' % mm['kl_flat'] if mm['kl_flat'] is not None else 'dark frames, leave-one-out'
+            print('session %d iso %-6s %-6s kl %.5f  floor %.5f  %s' % (si, s['iso'], m, mm['kl'], mm['floor'], flat))
     print('best model: %s (alpha %g, radius %d, seed %d)' % (rep['best'], rep['alpha'], rep['radius'], rep['seed']))
     if a.out:
         with open(a.out, 'w') as f:

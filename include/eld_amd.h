@@ -40,7 +40,11 @@ extern "C" {
  * version-5 call behaves as before.
  * 7: the defective-pixel entry points (eld_defect_deviation / eld_defect_flags / eld_defect_repair_u16, eld_debug_xtrans_defect_tables) exist;
  * every version-6 call behaves as before.
- * 8: the histogram entry points (eld_hist_u16 / eld_hist_f32) exist; every version-7 call behaves as before. */
+ * 8: the histogram entry points (eld_hist_u16 / eld_hist_f32) exist; every version-7 call behaves as before.
+ * Still 8: eld_noise_forward_dark and ELD_DARK were added (signal-independent noise read from a pool of dark frames; EldNoiseParams.reserved
+ * names the frame range) without a new number, because no existing call changed its signature, its record layout or its result: the one
+ * difference is that ELD_DARK in the flags of the two older sampler entries is now ELD_EINVAL instead of an ignored bit.  A binding that needs
+ * the new entry looks for its symbol (eld_amd/_lib.py binds every prototype at load and names the missing one with a rebuild hint). */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -59,7 +63,9 @@ extern "C" {
 #define ELD_CLIP        128u   /* fuse the caller's clip to [0,1]       dataset/sid_dataset.py:277 */
 #define ELD_AUG_NOTRANSPOSE 256u /* eld_augment only: no image of the batch has its transpose bit set (then H != W is fine) */
 #define ELD_CFA_XTRANS  512u   /* the C == 9 input is in RawPacker.pack_raw_xtrans's plane layout (noise.py:22-64): ELD_ROW and
-                                  ELD_CBIAS follow the X-Trans mosaic; without ELD_ROW / ELD_CBIAS it changes nothing */
+                                  ELD_CBIAS follow the X-Trans mosaic; without ELD_ROW / ELD_CBIAS / ELD_DARK it changes nothing */
+#define ELD_DARK       1024u   /* 'D'  z += code - black: the signal-independent noise is a random crop of a real dark frame
+                                  (eld_noise_forward_dark only; SFRN, Zhang et al., ICCV 2021) */
 
 /* input element types */
 #define ELD_IN_F32  0   /* float32 in [0,1]                                                      */
@@ -78,7 +84,7 @@ typedef struct EldNoiseParams {
     float ratio;        /* exposure ratio                              noise.py:223           */
     float color_bias[4];/* per packed channel (ADU)  ('color_bias'); ELD_CFA_XTRANS: (R, G, B) per CFA colour, [3] unused */
     uint32_t sample_id_lo, sample_id_hi;  /* GLOBAL sample index -> Philox counter words 1,2  */
-    uint32_t reserved[2];
+    uint32_t reserved[2];                 /* ELD_DARK: first index and count of the frame-table range this image draws from; else 0 */
 } EldNoiseParams;
 
 /* Variate planes of the debug/inject buffers: float[ELD_NPLANES][N*C*H*W]. */
@@ -213,6 +219,36 @@ int eld_crop_pack_raw_bayer_u16(const uint16_t* pool, size_t pool_elems, const E
 int eld_crop_pack_raw_xtrans_u16(const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int max_h, int max_w,
                                  const EldCropRecord* recs, int B, int ph, int pw, float black_level, float white_point, uint16_t* out,
                                  void* stream);
+
+/* ---- the sampler with the sensor's own dark frames (ELD_DARK, model letter 'D') -------------------------------------
+ * eld_noise_forward_strided plus one term: every signal-independent component (read noise, banding, fixed pattern, colour bias) is taken
+ * from a random crop of a real dark frame held in a frame pool, in the same pass:
+ *     zz = shot term;  zz = zz + (float(code) - black_c);  [ELD_QUANT: zz = zz + (u - 0.5) * q_step];  zz = zz * ratio;  zz = zz / S;  [clip]
+ * float32, one rounding per operation.  black_c is the NOMINAL black level of the plane (black_level[c]; X-Trans: black_level[0]), so the
+ * sensor's colour bias stays in the sample.  ELD_QUANT here is the dither that undoes the dark frame's own quantisation.  `inject` does
+ * not reach this term (the code is data, not a variate).
+ *   pool, pool_elems, frames, F   the frame pool's buffer and table, as eld_crop_pack_raw_*_u16 (same alignment rules)
+ *   min_h, min_w   HOST: the smallest packed extent over the frames; H > min_h or W > min_w is ELD_EINVAL
+ *   raw_pattern, black_level   as eld_pack_raw_bayer_u16 (HOST arrays of 4); ELD_CFA_XTRANS: raw_pattern is ignored (may be null)
+ *   params[n].reserved[0], [1]   first index and count of the contiguous range of `frames` image n may draw from (its session)
+ * The crop is chosen by the kernel, uniformly over the block, from w = Philox(index 0, sample id, stream 8):
+ *     f = first + umulhi(w.x, count);  (hp, wp) = packed extent of frame f
+ *     Bayer    y0 = umulhi(w.y, hp - H + 1),            x0 = umulhi(w.z, wp - W + 1)             (odd offsets included)
+ *     X-Trans  y0 = 2 umulhi(w.y, (hp - H) / 2 + 1),    x0 = 2 umulhi(w.z, (wp - W) / 2 + 1)     (a patch starts on a 6x6 cell)
+ * and element (c, h, w) reads the mosaic site that packed element (c, y0 + h, x0 + w) of frame f packs from (eld_pack_raw_bayer_u16's map by
+ * raw_pattern; eld_pack_xtrans's index map).  The choice is a function of (seed, sample id) alone.
+ * ELD_EINVAL before any launch: ELD_DARK with ELD_READ_GAUSS, ELD_READ_TL, ELD_ROW or ELD_CBIAS (those terms would be counted twice); C other
+ * than 4, or other than 9 with ELD_CFA_XTRANS; a null or misaligned pool or table; F <= 0; H > min_h or W > min_w; a raw_pattern that is not a
+ * permutation of 0..3; a null or negative black level.  On the device: a record whose range is empty or leaves the table, a frame smaller
+ * than the patch, and a frame entry that leaves the pool (or has an odd offset / row pitch) make the kernel SKIP that image: its slice
+ * of `out` is not written, and nothing outside the pool is read.
+ * W % 4 == 0 (Bayer): a lane's four packed elements are eight consecutive codes of one mosaic row, read as one 16-byte load when
+ * (offset + 2 x0) % 8 == 0 and Wm % 8 == 0, and as four 4-byte loads otherwise.  Without ELD_DARK in `flags` the pool arguments are ignored. */
+int eld_noise_forward_dark(const void* in, int in_dtype, size_t in_image_stride, float* out, size_t out_image_stride,
+                           const EldNoiseParams* params, int N, int C, int H, int W, uint32_t flags, uint64_t seed,
+                           const float* inject, float* dump,
+                           const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int min_h, int min_w,
+                           const int* raw_pattern, const float* black_level, void* stream);
 
 /* ---- noise-parameter calibration (eld_amd/calibrate.py; estimators: DESIGN.md "Calibration") ------------------------------
  * Inputs are uint16 Bayer sensor mosaics [F,Hm,Wm] with even sides; packed channel of pixel (y,x) = raw_pattern[y&1][x&1] (HOST
