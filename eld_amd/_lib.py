@@ -96,6 +96,8 @@ SIGNATURES = {
     'eld_debug_xtrans_defect_tables': (_i, [C.POINTER(C.c_int), _i]),
     'eld_hist_u16': (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _vp, _vp]),
     'eld_hist_f32': (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int), _i, _vp, _i, _vp, _vp]),
+    'eld_struct_sums_u16': (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp]),
+    'eld_struct_cross_u16': (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32), _i, _vp, _vp]),
     'eld_quality_assess_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'eld_quality_assess': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
     'eld_quality_assess_images': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),

@@ -3,7 +3,8 @@
 The check of the ELD paper's Table 1, per colour group: the discrete KL divergence between the histogram of real bias frames (and of
 the difference of real flat pairs) and the histogram of the sampler's synthesis under each noise model named, next to the divergence of
 two synthetic draws from each other (the sampling floor).  It is a test of MARGINAL distributions: the spatial structure of row noise is
-seen only through its effect on the marginal.
+seen only through its effect on the marginal.  structure=True (--structure) adds the report of that structure: row, column and
+fixed-pattern variance components of the real frames next to those of each model's synthesis (eld_amd/structure.py).
 
     report = validate_camera(sessions, raw_pattern, black_level, white_level, models=('Pg', 'PG', 'PGR', 'PGRB'))
     report['best']                                  # the model with the lowest mean bias-frame kl
@@ -13,7 +14,7 @@ The histograms are exact integer counts built on the device (eld_amd/csrc/hist.h
 sampler output); the binning contract is DESIGN.md sec. 15.  kl_divergence runs in float64 on the host.
 
 Command line: python -m eld_amd.validate manifest.json [--camera TABLE.npy] [--models Pg,PG,PGR,PGRB] [--source frames|table]
-[--defects PATH|auto] [--radius N] [--seed S] [--out report.json] [--hist hist.npz] (the manifest is calibrate's).
+[--defects PATH|auto] [--radius N] [--seed S] [--out report.json] [--hist hist.npz] [--structure [--lags L]] (the manifest is calibrate's).
 """
 import argparse
 import ctypes
@@ -224,6 +225,17 @@ def _leave_one_out(pool, first, count, omit):
     return (torch.from_numpy(rows.view(np.uint8).copy()).to(pool.pool.device), len(rows)), (0, len(rows))
 
 
+def _disjoint_halves(pool, first, count, omit):
+    """The leave-one-out frames of one session in two disjoint tables (every other frame each), as _leave_one_out returns them: two draws
+    that read one table each never read the same dark frame, whatever the seed.  Needs count >= 3."""
+    import torch
+    rows = np.delete(pool.pool.frames[first:first + count], omit)
+    out = []
+    for half in (rows[0::2], rows[1::2]):
+        out.append(((torch.from_numpy(half.view(np.uint8).copy()).to(pool.pool.device), len(half)), (0, len(half))))
+    return out
+
+
 def synthesize_codes(clean, params, model, cfa, seed, sample_id, white, black, shape=None):
     """What a sensor would have stored for one frame: the sampler's output x on `clean` under `model`, as a uint16 mosaic
     clip(rint(x * sat) + rint(black_c), 0, 65535), unpacked (CUDA uint16 (Hm, Wm); Bayer planes land in the layout [[0, 1], [3, 2]] of
@@ -232,7 +244,6 @@ def synthesize_codes(clean, params, model, cfa, seed, sample_id, white, black, s
     params: a NoiseParams / dict (K, g_scale, tl_lambda, tl_scale, row_scale, color_bias, in DN); the sampler runs with ratio = 1,
     saturation = white - max(black) and q_step = 1.  black: per packed channel (Bayer) or per colour code (X-Trans)."""
     import torch
-    from .noise import RawPacker
     CAL._cfa(cfa)
     _models([model])
     b = np.rint(CAL._black(black))
@@ -250,10 +261,18 @@ def synthesize_codes(clean, params, model, cfa, seed, sample_id, white, black, s
             raise ValueError('clean must be packed (%d, h, w), got %s' % (C, tuple(y.shape)))
         y = y.unsqueeze(0)
     x = _sample(y, _noise_params(params, sat), model, cfa, seed, [int(sample_id)])
+    return _stored_codes(x, cfa, b, sat)[0]
+
+
+def _stored_codes(x, cfa, b, sat):
+    """Sampler output x (N,C,h,w) -> the stored codes (N,Hm,Wm) uint16 of synthesize_codes; b = rint(black) per packed channel / colour code."""
+    import torch
+    from .noise import RawPacker
+    C = x.shape[1]
     plane_black = b[list(XT_PLANE_COLOUR)] if cfa == 'xtrans' else b
     codes = torch.round(x * np.float32(sat)) + torch.from_numpy(plane_black.astype(np.float32)).to(x.device).view(1, C, 1, 1)
     mos = RawPacker(cfa).unpack_raw(torch.clamp(codes, 0, 65535))
-    return mos[0].to(torch.int32).to(torch.uint16)
+    return mos.to(torch.int32).to(torch.uint16)
 
 
 def clean_from_flat_pair(a, b, cfa, raw_pattern, black_level, color_bias, sat):
@@ -322,7 +341,7 @@ def _check_session_shapes(sessions, cfa):
 
 
 def validate_camera(sessions, raw_pattern, black_level, white_level, table=None, diag=None, models=('Pg', 'PG', 'PGR', 'PGRB'), source='frames',
-                    cfa='bayer', defects=None, radius=256, flat_radius=1024, seed=2018, alpha=1.0, keep_hist=False):
+                    cfa='bayer', defects=None, radius=256, flat_radius=1024, seed=2018, alpha=1.0, keep_hist=False, structure=False, lags=8):
     """Sessions (calibrate_camera's) -> a report dict: how far the sampler's synthesis under each model lies from the real frames.
 
     Parameters of a bias frame: source='frames' -- that frame's own estimates, diag['frames'] of calibrate_camera (run here when neither
@@ -338,7 +357,16 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     repaired), the clean image is zero and K the frame's.  Such rows carry 'dark': 'leave-one-out'; they apply to bias frames only (kl_flat
     is None) and every session needs at least two bias frames (ValueError).  kl of 'PD' against its floor is how close two real frames of
     the sensor are to each other: the yardstick the parametric rows are read against.  best = the model of lowest mean bias-frame kl, lowest index on a tie.
-    This is a check of marginal distributions per colour group: it does not test the spatial structure of row noise."""
+    This is a check of marginal distributions per colour group; the spatial structure of the noise is a separate report:
+    structure=True adds report['structure'] (eld_amd/structure.py).  Per session: 'real' -- the components of the bias
+    frames (pairs = all frame pairs of the session; the defects map applies); per model 'synthetic' -- the same components of two synthetic
+    dark frames per real frame, stored as codes the way synthesize_codes stores them, drawn with the sample ids of the histogram pass
+    (pair = the two draws; for a model with D the two draws are repeated for this report with the leave-one-out frames dealt into two
+    disjoint tables, so that they never read the same dark frame), averaged over the frames -- and 'log_ratio' = log(synthetic / real)
+    where both are positive.  Each component is
+    the mean over frames (pairs) and colour groups; row_acf1 / col_acf1 are the lag-1 autocorrelations.  A model with D in a session of
+    fewer than 3 bias frames draws both frames from the same real frame: its fixed / temporal split is None and 'split' says why.  No
+    best model is chosen from these numbers.  Without structure=True the report is what it was."""
     cfa = CAL._cfa(cfa)
     models = _models(models)
     R, RF = _radius(radius), _radius(flat_radius, 'flat_radius')
@@ -346,6 +374,9 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         raise ValueError("source must be 'frames' or 'table', got %r" % (source,))
     if not (alpha >= 0):
         raise ValueError('alpha must be >= 0, got %r' % (alpha,))
+    if structure:
+        from . import structure as ST
+        lags = ST._lags(lags)
     if table is not None and any('B' in m for m in models) and table_cfa(table) != cfa:
         raise ValueError('the table is for cfa=%r, the frames are %r: its colour bias does not apply (model with B)' % (table_cfa(table), cfa))
     CAL._xpattern(raw_pattern) if cfa == 'xtrans' else CAL._pattern(raw_pattern)
@@ -399,6 +430,10 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     report = {'models': models, 'source': source, 'cfa': cfa, 'groups': G, 'radius': R, 'flat_radius': RF, 'alpha': float(alpha), 'seed': int(seed),
               'sessions': []}
     hists = {}
+    if structure:
+        report['structure'] = {'lags': lags, 'sessions': []}
+        cells = ST.cell_centres(cfa, raw_pattern, black)
+        bl = np.rint(black)
     j0 = 0
     for si, s in enumerate(sessions):
         bias = CAL._device_u16(s['bias'])
@@ -415,12 +450,18 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         real = histogram_u16(bias, cfa, raw_pattern, centre, R, defects=defects)
         dark = torch.zeros((2, C, h, w), dtype=torch.float32, device=bias.device)
         srep = {'iso': s.get('iso'), 'K': sparams['K'], 'params': sparams, 'frames': [], 'flats': []}
+        if structure:
+            rst = ST.structure_stats(ST.structure_sums(bias, cfa, raw_pattern, cells, defects=defects,
+                                                       pairs=[(a, b) for a in range(F) for b in range(a + 1, F)]), cfa, raw_pattern, lags)
+            syn_parts = {m: [] for m in models}
         for f in range(F):
             frep = {'params': fparams[f], 'models': {}}
             prm = _noise_params(fparams[f], sat)
             if dpool is not None:
                 loo_table, loo_range = _leave_one_out(dpool, dpool.ranges[si][0], F, f)
                 dprm = NoiseParams(prm[0], prm[1], prm[2], prm[3], q_step=1.0, dark=loo_range)
+                if structure and F >= 3:
+                    halves = _disjoint_halves(dpool, dpool.ranges[si][0], F, f)
             for mi, m in enumerate(models):
                 ids = [sample_id(si, f, mi, 0), sample_id(si, f, mi, 1)]
                 if 'D' in m:
@@ -428,6 +469,13 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
                 else:
                     x = _sample(dark, prm, m, cfa, seed, ids)
                 syn = histogram_f32(x, sat, R, cfa)
+                if structure:
+                    if 'D' in m and F >= 3:                    # the two draws of the histogram pass may have read the same dark frame
+                        x = torch.cat([_sample(dark[d:d + 1], NoiseParams(prm[0], prm[1], prm[2], prm[3], q_step=1.0, dark=rng_), m, cfa, seed,
+                                               ids[d:d + 1], dark=dpool, dark_table=tab) for d, (tab, rng_) in enumerate(halves)])
+                    sst = ST.structure_stats(ST.structure_sums(_stored_codes(x, cfa, bl, sat), cfa, raw_pattern, cells, pairs=[(0, 1)]),
+                                             cfa, raw_pattern, lags)
+                    syn_parts[m].append(ST.summarise(sst, with_pairs=not ('D' in m and F < 3)))
                 klg, flg = kl_divergence(real[f], syn[0], alpha), kl_divergence(syn[0], syn[1], alpha)
                 frep['models'][m] = {'kl': float(klg.mean()), 'floor': float(flg.mean()), 'kl_groups': klg.tolist(), 'floor_groups': flg.tolist()}
                 if 'D' in m:
@@ -461,6 +509,20 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
                              'floor': float(np.mean([fr['models'][m]['floor'] for fr in srep['frames']])),
                              'kl_flat': None if 'D' in m else float(np.mean([pr['models'][m]['kl_flat'] for pr in srep['flats']]))} for m in models}
         report['sessions'].append(srep)
+        if structure:
+            real = ST.summarise(rst)
+            strep = {'iso': s.get('iso'), 'real': real, 'real_frames': _finite(rst['frames']), 'real_pairs': _finite(rst['pairs']), 'models': {}}
+            for m in models:
+                synm = {}
+                for k in ST.COMPONENTS:
+                    vals = [q[k] for q in syn_parts[m] if q[k] is not None]
+                    synm[k] = float(np.mean(vals)) if vals else None
+                strep['models'][m] = {'synthetic': synm, 'log_ratio': ST.log_ratio(real, synm)}
+                if 'D' in m:
+                    strep['models'][m]['dark'] = 'leave-one-out'
+                    if F < 3:
+                        strep['models'][m]['split'] = 'fewer than 3 bias frames: both draws read the same dark frame, no fixed / temporal split'
+            report['structure']['sessions'].append(strep)
     report['means'] = {m: {k: float(np.mean([fr['models'][m][k] for s in report['sessions'] for fr in s['frames']])) for k in ('kl', 'floor')}
                        for m in models}
     for m in models:
@@ -471,6 +533,37 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     if keep_hist:
         report['hist'] = hists
     return report
+
+
+def _finite(x):
+    """Nested lists / dicts of floats with nan (a moment without data) -> the same with None."""
+    if isinstance(x, dict):
+        return {k: _finite(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return [_finite(v) for v in x]
+    if isinstance(x, float) and not np.isfinite(x):
+        return None
+    return x
+
+
+def _sigma(v):
+    """A variance component as a signed sigma for the table: sign(v) sqrt(|v|); '-' where undefined."""
+    return '      -' if v is None else '%7.3f' % (np.sign(v) * np.sqrt(abs(v)))
+
+
+def structure_lines(rep):
+    """The printed structure table: one line per session and model, real | synthetic."""
+    out = ['structure (sigma in DN, negative = none detected): sigma_row (sensor), sigma_col, sigma_pix fixed, row_acf[1]; real | synthetic']
+    for si, s in enumerate(rep['structure']['sessions']):
+        for m in rep['models']:
+            r, y = s['real'], s['models'][m]['synthetic']
+
+            def acf(v):
+                return '      -' if v is None else '%7.3f' % v
+            out.append('session %d iso %-6s %-6s row %s | %s  col %s | %s  fixed %s | %s  acf1 %s | %s'
+                       % (si, s['iso'], m, _sigma(r['row_var_sensor']), _sigma(y['row_var_sensor']), _sigma(r['col_var_sensor']),
+                          _sigma(y['col_var_sensor']), _sigma(r['pix_fixed_var']), _sigma(y['pix_fixed_var']), acf(r['row_acf1']), acf(y['row_acf1'])))
+    return out
 
 
 # ---- command line ----------------------------------------------------------------------------------------------------------------------
@@ -498,7 +591,17 @@ def parser():
     ap.add_argument('--seed', type=int, default=2018)
     ap.add_argument('--out', help='write the report here as JSON')
     ap.add_argument('--hist', help='write the histograms here (.npz)')
+    ap.add_argument('--structure', action='store_true', help='add the spatial-structure report: row, column and fixed-pattern components')
+    ap.add_argument('--lags', type=_lags_arg, default=8, help='autocorrelation lags of the structure report')
     return ap
+
+
+def _lags_arg(s):
+    from .structure import _lags
+    try:
+        return _lags(int(s))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
 
 
 def _models_arg(s):
@@ -524,7 +627,7 @@ def main(argv=None):
         defects = as_defect_map(defects, '--defects')
     table = None if a.camera is None else np.load(a.camera, allow_pickle=True).item()
     rep = validate_camera(sessions, pattern, black, white, table=table, models=a.models, source=a.source, cfa=cfa, defects=defects,
-                          radius=a.radius, seed=a.seed, keep_hist=a.hist is not None)
+                          radius=a.radius, seed=a.seed, keep_hist=a.hist is not None, structure=a.structure, lags=a.lags)
     hists = rep.pop('hist', None)
     for si, s in enumerate(rep['sessions']):
         for m in rep['models']:
@@ -532,6 +635,8 @@ def main(argv=None):
             flat = 'kl_flat %.5f' % mm['kl_flat'] if mm['kl_flat'] is not None else 'dark frames, leave-one-out'
             print('session %d iso %-6s %-6s kl %.5f  floor %.5f  %s' % (si, s['iso'], m, mm['kl'], mm['floor'], flat))
     print('best model: %s (alpha %g, radius %d, seed %d)' % (rep['best'], rep['alpha'], rep['radius'], rep['seed']))
+    if a.structure:
+        print('\n'.join(structure_lines(rep)))
     if a.out:
         with open(a.out, 'w') as f:
             json.dump(to_jsonable(rep), f, indent=1)

@@ -44,7 +44,9 @@ extern "C" {
  * Still 8: eld_noise_forward_dark and ELD_DARK were added (signal-independent noise read from a pool of dark frames; EldNoiseParams.reserved
  * names the frame range) without a new number, because no existing call changed its signature, its record layout or its result: the one
  * difference is that ELD_DARK in the flags of the two older sampler entries is now ELD_EINVAL instead of an ignored bit.  A binding that needs
- * the new entry looks for its symbol (eld_amd/_lib.py binds every prototype at load and names the missing one with a rebuild hint). */
+ * the new entry looks for its symbol (eld_amd/_lib.py binds every prototype at load and names the missing one with a rebuild hint).
+ * Still 8: eld_struct_sums_u16 and eld_struct_cross_u16 were added (exact row, column, cell and frame-pair sums for the spatial structure of
+ * noise) without a new number: two new symbols, no existing call changed in any way.  A binding finds them by symbol, as above. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -520,6 +522,27 @@ int eld_hist_u16(const uint16_t* u, const uint16_t* v, int F, int Hm, int Wm, in
                  const uint32_t* bitmap, uint64_t* counts, void* stream);
 int eld_hist_f32(const float* x, const float* x2, int N, int C, int H, int W, const int* group, int G, const float* scale, int R,
                  uint64_t* counts, void* stream);
+
+/* ---- exact sums for the spatial structure of noise (csrc/structure.hip, eld_amd/structure.py) ----------------------------
+ * u [F,Hm,Wm] uint16 codes, F <= 65535, Wm even, Hm * Wm < 2^31; p = the pattern period (2 or 6); centre: HOST int32[p*p], one value in
+ * [0, 65535] per cell (y % p, x % p); d = int(u) - centre[cell], so |d| <= 65535.  bitmap (optional): the defect bitmap of eld_defect_flags,
+ * ceil(Wm / 32) uint32 words per row, one map for all frames -- a flagged site contributes nothing anywhere.  Every output is int64 and
+ * fully written by the call (zeroed first); integer adds only, so the result is defined bit for bit.  sum d^2 <= 65535^2 Hm Wm
+ * < 2^32 * 2^31 = 2^63 fits int64, and so does every other sum.  No workspace.
+ *
+ * eld_struct_sums_u16: row[F][Hm][p][2] = (n, sum d) over the unflagged columns x of row y with x % p == c; col[F][Wm][p][2] = (n, sum d)
+ *   over the unflagged rows y of column x with y % p == r; cell[F][p*p][3] = (n, sum d, sum d^2) of cell r * p + c.  An entry with n == 0
+ *   is (0, 0).
+ * eld_struct_cross_u16: pairs: HOST int32[Q][2], frame indices (a, b) in [0, F), Q <= 2^24; cross[Q][p*p] = sum d_a d_b over the unflagged
+ *   sites of the cell.  (a, a) gives that frame's sum d^2.  For two independent frames of one sensor cov(d_a, d_b) per site is the variance
+ *   of what does not change between frames: the fixed pattern.
+ * u and bitmap 4-byte aligned, outputs 8-byte aligned.  16-byte loads when Wm % 8 == 0 and u is 16-byte aligned, 32-bit words otherwise.
+ * ELD_EINVAL before any launch for everything the host can see: p, sizes, an odd Wm, a centre outside [0, 65535], a pair outside [0, F),
+ * null or misaligned pointers (an output without elements may be NULL).  F == 0 (Q == 0) or an empty frame: 0 after zeroing the outputs. */
+int eld_struct_sums_u16(const uint16_t* u, int F, int Hm, int Wm, int p, const int32_t* centre, const uint32_t* bitmap, int64_t* row,
+                        int64_t* col, int64_t* cell, void* stream);
+int eld_struct_cross_u16(const uint16_t* u, int F, int Hm, int Wm, int p, const int32_t* centre, const uint32_t* bitmap, const int32_t* pairs,
+                         int Q, int64_t* cross, void* stream);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
