@@ -125,6 +125,7 @@ SIGNATURES = {
     'eld_maxpool2x2_forward_bf16': (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
     'eld_maxpool2x2_backward_bf16': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'eld_debug_last_conv_kernel': (C.c_char_p, []),
+    'eld_debug_conv_kernel_count': (C.c_uint, [C.c_char_p]),
     'eld_debug_unet_region': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i)]),
 }
 

@@ -26,6 +26,7 @@
 // MFMA-bound and a plain stage -> barrier -> compute -> barrier loop with >= 2 workgroups per CU
 // (LDS <= 80 KB each) keeps the matrix pipe busy while the other workgroup stages.
 #include <stdlib.h>
+#include <string.h>
 #include <atomic>
 #include "conv.h"
 
@@ -509,7 +510,31 @@ long long conv_tile_count(int N, int H, int W, int TH, bool pooled) {
 }
 
 static std::atomic<const char*> g_last_conv_kernel{""};
-void eld_note_conv_kernel(const char* family) { g_last_conv_kernel.store(family, std::memory_order_relaxed); }
+// launches per family name since the process started (eld_debug_conv_kernel_count): a fixed table, first come first served; names are string literals
+static std::atomic<const char*> g_seen_name[64];
+static std::atomic<unsigned> g_seen_count[64];
+static std::atomic<bool> g_seen_overflow{false};          // a 65th name arrived: counts of names outside the table are unknown, not 0
+void eld_note_conv_kernel(const char* family) {
+    g_last_conv_kernel.store(family, std::memory_order_relaxed);
+    for (int i = 0; i < 64; ++i) {
+        const char* p = g_seen_name[i].load(std::memory_order_acquire);
+        if (p == nullptr) {
+            const char* expect = nullptr;
+            if (g_seen_name[i].compare_exchange_strong(expect, family, std::memory_order_acq_rel)) p = family; else p = expect;
+        }
+        if (p == family || strcmp(p, family) == 0) { g_seen_count[i].fetch_add(1, std::memory_order_relaxed); return; }
+    }
+    g_seen_overflow.store(true, std::memory_order_relaxed);
+}
+extern "C" unsigned eld_debug_conv_kernel_count(const char* family) {
+    if (!family) return 0;
+    for (int i = 0; i < 64; ++i) {
+        const char* p = g_seen_name[i].load(std::memory_order_acquire);
+        if (p == nullptr) return 0;
+        if (strcmp(p, family) == 0) return g_seen_count[i].load(std::memory_order_relaxed);
+    }
+    return g_seen_overflow.load(std::memory_order_relaxed) ? ELD_CONV_KERNEL_COUNT_UNKNOWN : 0;
+}
 extern "C" const char* eld_debug_last_conv_kernel(void) { return g_last_conv_kernel.load(std::memory_order_relaxed); }
 
 int launch_conv(const ConvArgs& a_in, int mode, hipStream_t st) {
@@ -533,10 +558,9 @@ int launch_conv(const ConvArgs& a_in, int mode, hipStream_t st) {
     }
     const int algo = resolve_algo(a.algo);
     if (a.pool_out && !(mode == CONV_3X3 && a.epi == EPI_FWD && algo == 1 && a.dtype == DT_F32)) return ELD_ENOTSUP;     // fused pooling: conv_x3.hip only
-    if (mode == CONV_3X3 && a.epi != EPI_CONVT_FWD && algo == 1) { eld_note_conv_kernel("conv_x3"); return launch_conv_x3(a, st); }
+    if (mode == CONV_3X3 && a.epi != EPI_CONVT_FWD && algo == 1) return launch_conv_x3(a, st);      // (names its kernel itself: eld_note_conv_kernel)
     if (mode != CONV_3X3 && algo == 1) {
-        eld_note_conv_kernel("conv_x3_gemm");
-        const int rc = launch_conv_x3_gemm(a, mode, st);
+        const int rc = launch_conv_x3_gemm(a, mode, st);                                          // (as above, only when it takes the call)
         if (rc != ELD_ENOTSUP) return rc;
     }
     if (algo == 2) {                    // two fp16 pieces per operand, three products; needs the operand bounds

@@ -1192,10 +1192,12 @@ int wgrad8_ntiles(int CA, int CBp, int N, int H, int W, bool bf16) {
 
 template <typename T, int WCO, int WCI, int WPIX, int TH, int TWT, int STREAM = 0>
 static int launch_w8(WgradArgs a, hipStream_t st) {
-    eld_note_conv_kernel(sizeof(T) == 2 ? "wgrad8<bf16>" : "wgrad8<f32>");
     a.xcd = eld_xcd_mask() & XCD_WGRAD8;
     a.band = eld_tile_band();
     constexpr int COB = 32 * WCO, JBK = 32 * WCI;
+    // fp32: the block shape (output x input channels) is part of the name -- five instantiations with their own staging and MFMA loops
+    eld_note_conv_kernel(sizeof(T) == 2 ? "wgrad8<bf16>" : (COB == 128 ? "wgrad8<f32,128x64>" : (COB == 64 ? (JBK == 64 ? "wgrad8<f32,64x64>" : "wgrad8<f32,64x32>")
+                                                                                                    : (JBK == 64 ? "wgrad8<f32,32x64>" : "wgrad8<f32,32x32>"))));
     a.vp = vrow_pitch(a.N, a.H, TH);
     a.tiles_x = (a.W + TWT - 1) / TWT;
     a.tiles_y = (vrow_extent(a.N, a.H, a.vp) + TH - 1) / TH;

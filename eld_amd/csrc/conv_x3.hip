@@ -992,6 +992,7 @@ int launch_x3(ConvArgs a, hipStream_t st) {
     const long long tiles = (long long)a.tiles_x * a.tiles_y * a.N * (a.Nout / BN);
     if (tiles <= 0) return 0;
     if (tiles > 0x7fffffffLL) return ELD_ENOTSUP;
+    eld_note_conv_kernel("conv_x3<32>");                      // (every instantiation has BN == 32)
     auto kern = conv_x3_kernel<BN, RPW, DB, BFIRST, BSLAB, STREAM>;
     static EldAttrOnce once;
     { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
@@ -1030,6 +1031,7 @@ int launch_x3d(ConvArgs a, hipStream_t st) {
         if (ks >= 2) { a.ksplit = ks; tiles *= ks; }
     }
     if (tiles > 0x7fffffffLL) return ELD_ENOTSUP;
+    eld_note_conv_kernel(BN == 128 ? "conv_x3d<128,8>" : (BN == 32 ? "conv_x3d<32,8>" : (WAVES == 8 ? "conv_x3d<64,8>" : (a.ksplit > 1 ? "conv_x3d<64,4,splitk>" : "conv_x3d<64,4>"))));
     auto kern = conv_x3d_kernel<BN, RPW, WAVES, DB, STREAM>;
     static EldAttrOnce once;
     { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
@@ -1063,6 +1065,7 @@ int launch_x3_gemm(ConvArgs a, hipStream_t st) {
     if (grid > tiles) grid = tiles;
     // (round 6: a software-pipelined variant -- 16-k stages, doubled stage buffer, the cut of stage s + 1 between the MFMAs of stage s -- measured +26 % per launch:
     // these launches are bound by the bytes a workgroup keeps in flight, not by the cut; commit 7f24c6e, profiles/r06_ab_notes.md section 9)
+    eld_note_conv_kernel(MODE == CONV_1X1 ? "conv_x3_gemm<1x1>" : "conv_x3_gemm<gather>");
     auto kern = conv_x3_gemm_kernel<MODE, BN, WAVES>;
     static EldAttrOnce once;
     { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
@@ -1166,6 +1169,9 @@ int launch_conv_x3_gemm(const ConvArgs& a, int mode, hipStream_t st) {
     if (a.Nout % 64 || a.C0 % 32 || a.C1 != 0 || src_img >= 0xFFFFFFF0ull) return ELD_ENOTSUP;
     // (an 8-wave 16 x 32 x 128 tile, <.., 128, 8>, was measured at the same speed as the 4-wave 8 x 32 x 64 one: these launches are not bound by
     // the operand cuts; the small tile wastes less on the 89 x 133 / 178 x 266 levels)
+    // the transposed-conv epilogue places one whole 32-channel block of GEMM N at ONE tap (tap = n / Cout_t per block): Cout_t must be a multiple of 32
+    // (Cout_t = 16 wrote every second block's upper half to the wrong tap; the U-Net's own layers have Cout_t >= 32)
+    if (mode == CONV_1X1 && a.epi == EPI_CONVT_FWD && a.Cout_t % 32) return ELD_ENOTSUP;
     if (mode == CONV_1X1 && a.epi == EPI_CONVT_FWD) return launch_x3_gemm<CONV_1X1, 64, 4>(a, st);
     if (mode == CONV_GATHER2X2 && a.epi == EPI_GRAD && a.split == a.Nout) return launch_x3_gemm<CONV_GATHER2X2, 64, 4>(a, st);
     return ELD_ENOTSUP;

@@ -401,6 +401,7 @@ int launch_conv_x3w(const ConvArgs& a_in, hipStream_t st) {
     const long long tiles = (long long)a.tiles_x * a.tiles_y * a.N;
     if (tiles <= 0) return 0;
     if (tiles > 0x3fffffffLL) return ELD_ENOTSUP;
+    eld_note_conv_kernel("conv_x3w");
     constexpr size_t lds_bytes = (size_t)(2 * W_BWORDS + 2 * W_AWORDS) * sizeof(float);
     long long grid = (long long)eld_num_cus();
     if (grid > tiles) grid = tiles;

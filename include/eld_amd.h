@@ -603,10 +603,23 @@ int eld_convt2x2_backward_weight_bf16(const uint16_t* in, const uint16_t* dout, 
 int eld_maxpool2x2_forward_bf16(const uint16_t* in, uint16_t* out, int N, int Ho, int Wo, int C, void* stream);
 int eld_maxpool2x2_backward_bf16(const uint16_t* act, const uint16_t* dp, const uint16_t* skip, uint16_t* g, int N, int Ho, int Wo, int C, void* stream);
 
-/* Test hook: the family name of the most recent convolution or weight-gradient launch of this process ("conv_bfs", "conv_bfw", "conv_bfd<128>",
- * "conv_bfg<64,gather>", "conv_igemm<bf16>", "wgrad8d", "wgrad8<bf16>", "wgrad<bf16,gather>", ...), recorded by the launcher that chose it;
- * host-side only, "" before the first launch. */
+/* Test hook: the family name of the most recent convolution or weight-gradient launch of this process, recorded by the launcher that chose it
+ * (a dispatcher that falls through to another family records nothing itself); host-side only, "" before the first launch.
+ *   bf16: "conv_bfs", "conv_bfw", "conv_bfd<128>", "conv_bfd<64>", "conv_bfg<128>", "conv_bfg<64,gather>", "conv_bfg<128,gather>", "conv_igemm<bf16>",
+ *         "conv_igemm<bf16,1x1>", "conv_igemm<bf16,gather>", "wgrad8d", "wgrad8<bf16>", "wgrad<bf16>", "wgrad<bf16,gather>";
+ *   fp32, three-piece scheme (tile width in output channels, waves per workgroup): "conv_x3w", "conv_x3<32>", "conv_x3d<128,8>", "conv_x3d<64,8>",
+ *         "conv_x3d<64,4>", "conv_x3d<64,4,splitk>" (K split over workgroups, inside a U-Net entry point only), "conv_x3d<32,8>" (opt-in),
+ *         "conv_x3_gemm<1x1>", "conv_x3_gemm<gather>" (transposed convs), "wgrad8<f32,128x64>", "wgrad8<f32,64x64>", "wgrad8<f32,64x32>",
+ *         "wgrad8<f32,32x64>", "wgrad8<f32,32x32>" (block = output x input channels), "wgradt8";
+ *   fp32, other schemes and shapes: "conv_igemm<f32>", "conv_igemm<f32,h2>", "wgrad<f32>", "wgrad<f32,gather>". */
 const char* eld_debug_last_conv_kernel(void);
+/* Test hook: how many launches this process has recorded under a family name (0 for a name never seen): what a test of a whole-network entry
+ * point compares before and after the call to see which families the dispatcher chose inside it.  The table holds 64 names; once a 65th has
+ * been launched, a name outside the table answers ELD_CONV_KERNEL_COUNT_UNKNOWN instead of 0.
+ * Added without a change of ELD_ABI_VERSION (no existing signature changed), so the Python binding, which binds every symbol, needs a library
+ * built from this header or a later one: an older ABI-8 library fails at bind with this symbol missing, not with the version message. */
+#define ELD_CONV_KERNEL_COUNT_UNKNOWN 0xFFFFFFFFu
+unsigned eld_debug_conv_kernel_count(const char* family);
 /* Test hook: where the U-Net workspace of problem (N, H, W, in_ch, out_ch, precision) holds a region after a forward (eld_unet_forward_ex /
  * eld_unet_forward_bf16) or, for ELD_REGION_GRAD_CONV1_1, after a bf16 backward: *offset in bytes, *channels, *dtype = 0 fp32 NHWC, 1 bf16 NHWC,
  * 2 fp32 NCHW.  level: the U-Net level (pool: the level of the tensor it pools), 0 for X16 and GRAD_CONV1_1.  X16 = the first layer's input as the
