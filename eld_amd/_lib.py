@@ -98,6 +98,11 @@ SIGNATURES = {
     'eld_hist_f32': (_i, [_vp, _vp, _i, _i, _i, _i, C.POINTER(C.c_int), _i, _vp, _i, _vp, _vp]),
     'eld_struct_sums_u16': (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, _vp, _vp, _vp, _vp]),
     'eld_struct_cross_u16': (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int32), _vp, C.POINTER(C.c_int32), _i, _vp, _vp]),
+    'eld_shading_fit_u16': (_i, [_vp, _sz, _vp, _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                 C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _vp]),
+    'eld_shading_apply_u16': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
+    'eld_pack_raw_bayer_u16_shaded': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp, _vp, _vp, _f, _vp]),
+    'eld_pack_raw_xtrans_u16_shaded': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _vp]),
     'eld_quality_assess_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'eld_quality_assess': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
     'eld_quality_assess_images': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),

@@ -33,9 +33,12 @@ class DarkPool:
                  sampler calls with explicit parameters -- _sample_params() raises without gains.
     defects      a DefectMap or its path: the frames are repaired once, at upload, as FramePool does (a hot pixel would otherwise be stamped
                  into training patches at a moving position).
+    shading      a DarkShading (eld_amd.shading) or its path: after the repair, each session's frames are corrected in place at that
+                 session's ISO (eld_shading_apply_u16), so the sampler draws temporal noise only.  Every session then needs an 'iso' inside
+                 the map's range and every frame the map's shape.  The sampler and its kernels are untouched.
     Bad arguments raise ValueError before any device work."""
 
-    def __init__(self, sessions, cfa='bayer', raw_pattern=None, black_level=None, white_level=16383, K=None, defects=None, device=None):
+    def __init__(self, sessions, cfa='bayer', raw_pattern=None, black_level=None, white_level=16383, K=None, defects=None, device=None, shading=None):
         _check_cfa(cfa)
         if not isinstance(sessions, (list, tuple)) or len(sessions) == 0:
             raise ValueError('sessions must be a non-empty list of {"bias": frames[, "iso"]}')
@@ -58,12 +61,30 @@ class DarkPool:
             K = np.asarray(K, dtype=np.float64).reshape(-1)
             if K.size != len(sessions) or not np.all(np.isfinite(K)) or np.any(K <= 0):
                 raise ValueError('K holds one finite gain > 0 per session (%d), got %r' % (len(sessions), K.tolist()))
+        tvals = None
+        if shading is not None:
+            from .shading import as_dark_shading
+            shading = as_dark_shading(shading)
+            for i, m in enumerate(frames):
+                shading.check_frames(m.shape, cfa, 'frame %d' % i)
+            shading.check_pattern(raw_pattern if cfa == 'bayer' else None, 'DarkPool')
+            for i, iso in enumerate(isos):
+                if iso is None:
+                    raise ValueError("session %d has no 'iso': the dark-shading map is subtracted at the session's ISO" % i)
+            tvals = [shading.t(iso) for iso in isos]
         pool = FramePool(frames, cfa=cfa, raw_pattern=raw_pattern, black_level=black_level, white_point=white_level, device=device, defects=defects)
         self.pool, self.cfa, self.C = pool, cfa, pool.C
         self.raw_pattern, self.black_level, self.white_level = pool.raw_pattern, pool.black_level, pool.white_point
         self.saturation = float(pool.white_point) - float(max(pool.black_level))
         self.ranges, self.isos, self.K = ranges, isos, K
         self.min_extent = (int(pool.extent[:, 0].min()), int(pool.extent[:, 1].min()))
+        self.shading = shading
+        if shading is not None and pool.buffer is not None:
+            Hm, Wm = shading.shape
+            for (first, count), tv in zip(ranges, tvals):
+                for f in pool.frames[first:first + count]:       # in place, frame by frame (the frames start 16-byte aligned, not back to back)
+                    v = pool.buffer[int(f['offset']):int(f['offset']) + Hm * Wm].view(1, Hm, Wm)
+                    shading.apply_device(v, tv, pool.defects, v)
 
     def __len__(self):
         return len(self.pool)
@@ -73,7 +94,7 @@ class DarkPool:
         return len(self.ranges)
 
     @classmethod
-    def from_manifest(cls, path, K=None, defects=None, device=None):
+    def from_manifest(cls, path, K=None, defects=None, device=None, shading=None):
         """calibrate's manifest -> a DarkPool.  K: None -- calibrate_camera runs here for the session gains (diag['K']); a sequence of
         gains, one per session; or the path of a table eld_amd.calibrate wrote.  A table keeps only the range [Kmin, Kmax] of the gains, not
         the gain of each session, so with a path the calibration runs as well and the gains it finds must lie in the table's range
@@ -97,8 +118,8 @@ class DarkPool:
             defects = find_defects(sessions[0]['bias'], cfa, pattern)[0]
         if cfa == 'xtrans':
             b = np.asarray(black, dtype=np.float64).reshape(-1)
-            return cls(sessions, cfa=cfa, black_level=b, white_level=white, K=K, defects=defects, device=device)
-        return cls(sessions, cfa=cfa, raw_pattern=pattern, black_level=black, white_level=white, K=K, defects=defects, device=device)
+            return cls(sessions, cfa=cfa, black_level=b, white_level=white, K=K, defects=defects, device=device, shading=shading)
+        return cls(sessions, cfa=cfa, raw_pattern=pattern, black_level=black, white_level=white, K=K, defects=defects, device=device, shading=shading)
 
     def check_patch(self, H, W):
         """ValueError when a (H, W) packed patch does not fit the smallest dark frame (the entry's check, stated before upload)."""

@@ -197,11 +197,25 @@ def _colour(cfa, wb, ccm, N):
 
 
 # ---- the device stages ------------------------------------------------------------------------------------------------------------
-def pack_input(t, cfa, raw_pattern, black_level, white_point, ratios):
-    """CUDA int16-view codes (N,Hm,Wm) -> the network input (N,C,h,w) float32: pack, x ratio[n], clip -- one kernel."""
+def pack_input(t, cfa, raw_pattern, black_level, white_point, ratios, shading=None, tval=None):
+    """CUDA int16-view codes (N,Hm,Wm) -> the network input (N,C,h,w) float32: pack, x ratio[n], clip -- one kernel.  shading (a
+    DarkShading) with tval = shading.t(iso): the same kernel shape with the map a + b * tval subtracted in float32 between the black level
+    and the division (eld_pack_raw_*_u16_shaded)."""
     import torch
     N, Hm, Wm = t.shape
     r = torch.as_tensor(np.asarray(ratios, np.float32), device=t.device)
+    if shading is not None:
+        ma, mb = shading.on(t.device)
+        if cfa == 'bayer':
+            out = torch.empty((N, 4, Hm // 2, Wm // 2), dtype=torch.float32, device=t.device)
+            L.check(L.lib().eld_pack_raw_bayer_u16_shaded(L.dptr(t), L.dptr(out), N, Hm // 2, Wm // 2, (ctypes.c_int * 4)(*raw_pattern),
+                                                          (ctypes.c_float * 4)(*black_level), float(white_point), L.dptr(r), L.dptr(ma), L.dptr(mb),
+                                                          float(tval), L.cur_stream()), 'eld_pack_raw_bayer_u16_shaded')
+        else:
+            out = torch.empty((N, 9, 2 * (Hm // 6), 2 * (Wm // 6)), dtype=torch.float32, device=t.device)
+            L.check(L.lib().eld_pack_raw_xtrans_u16_shaded(L.dptr(t), L.dptr(out), N, Hm, Wm, float(black_level[0]), float(white_point), L.dptr(r),
+                                                           L.dptr(ma), L.dptr(mb), float(tval), L.cur_stream()), 'eld_pack_raw_xtrans_u16_shaded')
+        return out
     if cfa == 'bayer':
         out = torch.empty((N, 4, Hm // 2, Wm // 2), dtype=torch.float32, device=t.device)
         pat = (ctypes.c_int * 4)(*raw_pattern)
@@ -244,7 +258,7 @@ def run_network(denoiser, x, chop=None):
 
 
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
-                chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None):
+                chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None, shading=None, iso=None):
     """Denoise uint16 sensor mosaics with a trained U-Net.
 
     mosaic_u16  NumPy uint16 array or CUDA uint16 / int16-view tensor, (Hm, Wm) or (N, Hm, Wm) -- rawpy's raw_image_visible.
@@ -262,6 +276,11 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                 median of their unflagged same-colour neighbours) in one pass before the input stage -- the ratio would turn a warm pixel
                 into a saturated dot.  X-Trans: the borders outside whole cells, which pass through to the output mosaic, are repaired
                 too.  None (default): the codes are used as they are.
+    shading, iso  a DarkShading (eld_amd.shading) or the path of a saved one, and the ISO the frames were shot at: after the defect
+                repair the input stage subtracts the sensor's fixed pattern a + b * (iso - x0) in float32, fused into the pack
+                (eld_pack_raw_*_u16_shaded) -- the ratio would otherwise multiply it into visible columns and blotches.  The write-back is
+                unchanged: the network's output estimates the clean signal above the nominal black level.  shading without iso, a map
+                of another shape, CFA or Bayer pattern, or an ISO outside the map's range is a ValueError.
 
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
@@ -296,6 +315,17 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         from .defects import as_defect_map, repair_device
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'denoise_raw')
+    tval = None
+    if shading is not None:
+        from .shading import as_dark_shading
+        shading = as_dark_shading(shading)
+        if iso is None:
+            raise ValueError('shading needs iso: the ISO the frames were shot at')
+        shading.check_frames((Hm, Wm), cfa, 'denoise_raw')
+        shading.check_pattern(None if cfa == 'xtrans' else np.asarray(pat).reshape(2, 2), 'denoise_raw')
+        tval = shading.t(iso)
+    elif iso is not None:
+        raise ValueError('iso is the abscissa of a dark-shading map: pass shading= with it')
     if srgb_size == 'full' and cfa == 'bayer' and (pat[0] & 1) != (pat[3] & 1):
         raise ValueError('the full-size render needs a Bayer raw_pattern with its greens on a diagonal, got %r' % (raw_pattern,))
 
@@ -312,7 +342,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     t3 = t if batched else t.unsqueeze(0)
     if defects is not None:
         t3 = repair_device(t3, defects)
-    x = pack_input(t3, cfa, pat, blk, white, ratios)
+    x = pack_input(t3, cfa, pat, blk, white, ratios, shading, tval)
     out = run_network(denoiser, x, chop)
     mosaic = t3.clone()                   # X-Trans: the borders outside whole cells keep the input's codes
     write_back(out, mosaic, cfa, pat, blk, white, rounding)
@@ -348,7 +378,8 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
 # ---- command line -------------------------------------------------------------------------------------------------------------
 SIDECAR_ALIASES = {'black_level_per_channel': 'black_level', 'white_level': 'white_point', 'camera_whitebalance': 'wb',
                    'rgb_camera_matrix': 'ccm', 'black': 'black_level', 'white': 'white_point'}
-SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size', 'defects')
+SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size', 'defects',
+                'shading', 'iso')
 
 
 def read_sidecar(path):
@@ -361,7 +392,7 @@ def read_sidecar(path):
     out = {}
     for k, v in d.items():
         k = SIDECAR_ALIASES.get(k, k)
-        if k == 'defects' and isinstance(v, str):             # a saved defect map, relative to the sidecar
+        if k in ('defects', 'shading') and isinstance(v, str):             # a saved defect / dark-shading map, relative to the sidecar
             v = os.path.join(os.path.dirname(os.path.abspath(path)), v)
         if k not in SIDECAR_KEYS:
             raise ValueError('%s: unknown key %r (known: %s)' % (path, k, ', '.join(SIDECAR_KEYS + tuple(SIDECAR_ALIASES))))
@@ -391,6 +422,8 @@ def build_parser():
     p.add_argument('--chop', choices=('auto', 'on', 'off'), help='forward_chop tiles (default auto)')
     p.add_argument('--rounding', choices=ROUNDING, help="write-back rounding (default 'nearest')")
     p.add_argument('--defects', metavar='PATH', help='a defect map written by eld_amd.defects (.npz): its sites are repaired before the network')
+    p.add_argument('--shading', metavar='FILE', help='a dark-shading map written by eld_amd.shading (.npz): subtracted in the input stage; needs --iso')
+    p.add_argument('--iso', type=float, help='the ISO the frames were shot at (the abscissa of --shading)')
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
     return p
 
@@ -400,7 +433,7 @@ def parse_args(argv):
     a = build_parser().parse_args(argv)
     o = read_sidecar(a.meta) if a.meta else {}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
-           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'precision': 'bf16' if a.bf16 else None,
+           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'precision': 'bf16' if a.bf16 else None,
            'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
     o.update({k: v for k, v in cli.items() if v is not None})
     o.setdefault('cfa', 'bayer')
@@ -425,6 +458,8 @@ def parse_args(argv):
         raise ValueError('the sRGB output needs both --wb and --ccm')
     if o['srgb_size'] == 'full' and o.get('wb') is None:
         raise ValueError('--srgb-size full needs --wb and --ccm')
+    if o.get('shading') is not None and o.get('iso') is None:
+        raise ValueError('--shading needs --iso')
     return a.inputs, a.out, a.ckpt, o
 
 
@@ -445,6 +480,9 @@ def main(argv=None):
     if o.get('defects') is not None:
         from .defects import as_defect_map
         kw['defects'] = as_defect_map(o['defects'], '--defects')
+    if o.get('shading') is not None:
+        from .shading import as_dark_shading
+        kw['shading'], kw['iso'] = as_dark_shading(o['shading'], '--shading'), o['iso']
     for path in inputs:
         raw = np.load(path)
         res = denoise_raw(den, raw, o['cfa'], **kw)

@@ -35,6 +35,8 @@ def build_parser():
     p.add_argument('--camera', default='SonyA7S2', help='a table written by eld_amd.calibrate (<dir>/<name>_params.npy) or a release camera name')
     p.add_argument('--noise', default='PGRU', help="noise model letters of NoiseModel(model=...) (default 'PGRU')")
     p.add_argument('--dark', metavar='MANIFEST', help="calibrate's manifest JSON: its bias frames become the dark-frame pool of noise letter D (--noise PDU)")
+    p.add_argument('--dark-shading', metavar='FILE', help='a dark-shading map written by eld_amd.shading (.npz): subtracted from the --dark frames at '
+                                                          "upload, at each session's ISO")
     p.add_argument('--patch', type=int, default=512, help='packed patch side (default 512)')
     p.add_argument('--batch', type=int, default=1, help='patches per step (default 1)')
     p.add_argument('--epochs', type=int, default=1)
@@ -55,10 +57,12 @@ def noise_model(camera, letters, cfa, dark=None):
     return NoiseModel(model=letters, cameras=[camera], cfa=cfa, dark=dark)
 
 
-def dark_pool(manifest, camera, letters, patch, device=None):
+def dark_pool(manifest, camera, letters, patch, device=None, shading=None):
     """--dark: the manifest's bias frames as a DarkPool (None without the letter D; the letter without --dark is an error, and so is --dark
     without the letter).  A --camera that is a table file is handed on, so that a manifest which does not belong to it is refused; the patch
     must fit the smallest dark frame."""
+    if shading is not None and manifest is None:
+        raise ValueError('--dark-shading corrects the frames of --dark: it needs --dark manifest.json')
     if 'D' not in letters:
         if manifest is not None:
             raise ValueError('--dark needs the noise letter D (--noise PDU), got --noise %s' % letters)
@@ -66,7 +70,7 @@ def dark_pool(manifest, camera, letters, patch, device=None):
     if manifest is None:
         raise ValueError("--noise %s: the letter D samples the sensor's dark frames and needs --dark manifest.json" % letters)
     from .darkpool import DarkPool
-    pool = DarkPool.from_manifest(manifest, K=camera if camera.endswith('.npy') else None, device=device)
+    pool = DarkPool.from_manifest(manifest, K=camera if camera.endswith('.npy') else None, device=device, shading=shading)
     pool.check_patch(patch, patch)
     return pool
 
@@ -91,7 +95,7 @@ def main(argv=None):
     pool = FramePool(mosaics, cfa=cfa, defects=a.defects if a.defects is not None else side.get('defects'), **o)
     if pool.buffer is None:
         raise RuntimeError('eld_amd.train_frames needs a GPU: there is no CPU fallback')
-    dark = dark_pool(a.dark, a.camera, a.noise, a.patch, device=pool.device)
+    dark = dark_pool(a.dark, a.camera, a.noise, a.patch, device=pool.device, shading=a.dark_shading)
     if dark is not None and dark.cfa != cfa:
         raise ValueError('--dark: the manifest holds %s frames, the clean frames are %s' % (dark.cfa, cfa))
     nm = noise_model(a.camera, a.noise, cfa, dark=dark)

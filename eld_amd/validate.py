@@ -341,7 +341,7 @@ def _check_session_shapes(sessions, cfa):
 
 
 def validate_camera(sessions, raw_pattern, black_level, white_level, table=None, diag=None, models=('Pg', 'PG', 'PGR', 'PGRB'), source='frames',
-                    cfa='bayer', defects=None, radius=256, flat_radius=1024, seed=2018, alpha=1.0, keep_hist=False, structure=False, lags=8):
+                    cfa='bayer', defects=None, radius=256, flat_radius=1024, seed=2018, alpha=1.0, keep_hist=False, structure=False, lags=8, shading=None):
     """Sessions (calibrate_camera's) -> a report dict: how far the sampler's synthesis under each model lies from the real frames.
 
     Parameters of a bias frame: source='frames' -- that frame's own estimates, diag['frames'] of calibrate_camera (run here when neither
@@ -366,7 +366,12 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     where both are positive.  Each component is
     the mean over frames (pairs) and colour groups; row_acf1 / col_acf1 are the lag-1 autocorrelations.  A model with D in a session of
     fewer than 3 bias frames draws both frames from the same real frame: its fixed / temporal split is None and 'split' says why.  No
-    best model is chosen from these numbers.  Without structure=True the report is what it was."""
+    best model is chosen from these numbers.  Without structure=True the report is what it was.
+    shading: a DarkShading (eld_amd.shading) or its path: the REAL bias frames are corrected at their session's ISO (the integer path,
+    eld_shading_apply_u16; flagged sites pass through) before the histograms and the structure sums, and the dark frames a model with D
+    draws from are corrected the same way, so the report shows the fixed components with the correction applied, next to the models.  The
+    flats, and the calibration that runs here without a diag, see the frames as they are.  Every session then needs an 'iso' inside the
+    map's range (ValueError).  report['shading'] records x0 and the ISO range."""
     cfa = CAL._cfa(cfa)
     models = _models(models)
     R, RF = _radius(radius), _radius(flat_radius, 'flat_radius')
@@ -399,6 +404,15 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         raise ValueError('white level %r does not exceed the black level' % (white_level,))
     if defects is not None and not isinstance(defects, str):
         defects.check_frames(CAL._shape(sessions[0]['bias']), cfa, 'validation')
+    if shading is not None:
+        from .shading import as_dark_shading
+        shading = as_dark_shading(shading)
+        shading.check_pattern(None if cfa == 'xtrans' else raw_pattern, 'validation')
+        for i, s in enumerate(sessions):
+            shading.check_frames(CAL._shape(s['bias']), cfa, 'session %d bias' % i)
+            if s.get('iso') is None:
+                raise ValueError("session %d has no 'iso': the dark-shading map is subtracted at the session's ISO" % i)
+            shading.t(s['iso'])
 
     import torch
     if diag is None:
@@ -425,11 +439,13 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     dpool = None
     if with_dark:
         from .darkpool import DarkPool
-        dpool = DarkPool([{'bias': s['bias']} for s in sessions], cfa=cfa, raw_pattern=None if cfa == 'xtrans' else raw_pattern, black_level=black,
-                         white_level=white_level, defects=defects)
+        dpool = DarkPool([{'bias': s['bias'], 'iso': s.get('iso')} for s in sessions], cfa=cfa, raw_pattern=None if cfa == 'xtrans' else raw_pattern,
+                         black_level=black, white_level=white_level, defects=defects, shading=shading)
     report = {'models': models, 'source': source, 'cfa': cfa, 'groups': G, 'radius': R, 'flat_radius': RF, 'alpha': float(alpha), 'seed': int(seed),
               'sessions': []}
     hists = {}
+    if shading is not None:
+        report['shading'] = {'x0': shading.x0, 'iso_min': shading.iso_min, 'iso_max': shading.iso_max, 'centred': shading.centred}
     if structure:
         report['structure'] = {'lags': lags, 'sessions': []}
         cells = ST.cell_centres(cfa, raw_pattern, black)
@@ -437,6 +453,8 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     j0 = 0
     for si, s in enumerate(sessions):
         bias = CAL._device_u16(s['bias'])
+        if shading is not None:
+            bias = shading.apply_device(bias, shading.t(s['iso']), None if isinstance(defects, str) else defects)
         flats = CAL._device_u16(s['flats'])
         F, Hm, Wm = CAL._shape(bias)
         P = CAL._shape(flats)[0]
@@ -592,6 +610,7 @@ def parser():
     ap.add_argument('--out', help='write the report here as JSON')
     ap.add_argument('--hist', help='write the histograms here (.npz)')
     ap.add_argument('--structure', action='store_true', help='add the spatial-structure report: row, column and fixed-pattern components')
+    ap.add_argument('--shading', metavar='FILE', help='a dark-shading map written by eld_amd.shading (.npz): the real bias frames are corrected first')
     ap.add_argument('--lags', type=_lags_arg, default=8, help='autocorrelation lags of the structure report')
     return ap
 
@@ -627,7 +646,8 @@ def main(argv=None):
         defects = as_defect_map(defects, '--defects')
     table = None if a.camera is None else np.load(a.camera, allow_pickle=True).item()
     rep = validate_camera(sessions, pattern, black, white, table=table, models=a.models, source=a.source, cfa=cfa, defects=defects,
-                          radius=a.radius, seed=a.seed, keep_hist=a.hist is not None, structure=a.structure, lags=a.lags)
+                          radius=a.radius, seed=a.seed, keep_hist=a.hist is not None, structure=a.structure, lags=a.lags,
+                          shading=a.shading)
     hists = rep.pop('hist', None)
     for si, s in enumerate(rep['sessions']):
         for m in rep['models']:

@@ -46,7 +46,10 @@ extern "C" {
  * difference is that ELD_DARK in the flags of the two older sampler entries is now ELD_EINVAL instead of an ignored bit.  A binding that needs
  * the new entry looks for its symbol (eld_amd/_lib.py binds every prototype at load and names the missing one with a rebuild hint).
  * Still 8: eld_struct_sums_u16 and eld_struct_cross_u16 were added (exact row, column, cell and frame-pair sums for the spatial structure of
- * noise) without a new number: two new symbols, no existing call changed in any way.  A binding finds them by symbol, as above. */
+ * noise) without a new number: two new symbols, no existing call changed in any way.  A binding finds them by symbol, as above.
+ * Still 8: the dark-shading entry points (eld_shading_fit_u16, eld_shading_apply_u16, eld_pack_raw_bayer_u16_shaded,
+ * eld_pack_raw_xtrans_u16_shaded) were added the same way: four new symbols, no existing call changed, so the Python binding, which binds
+ * every symbol, needs a library built from this header or a later one (an older ABI-8 library fails at bind with the symbol's name). */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -543,6 +546,47 @@ int eld_struct_sums_u16(const uint16_t* u, int F, int Hm, int Wm, int p, const i
                         int64_t* col, int64_t* cell, void* stream);
 int eld_struct_cross_u16(const uint16_t* u, int F, int Hm, int Wm, int p, const int32_t* centre, const uint32_t* bitmap, const int32_t* pairs,
                          int Q, int64_t* cross, void* stream);
+
+/* ---- dark shading: per-site offset maps over ISO (csrc/shading.hip, eld_amd/shading.py) ---------------------------------
+ * The mean of a sensor's dark frames is, per site, close to linear in ISO: offset(y, x, iso) = a(y, x) + b(y, x) * t, t = iso - x0.  The fit
+ * pools the bias frames of all sessions; the other three entries subtract the map.  Every output depends on its own site only: no atomics,
+ * no cross-lane sums, and every floating-point operation below is rounded once, in the order written, without FMA contraction -- two calls
+ * give the same bits, and the results are defined bit for bit (tests/shading_ref.py restates them in NumPy).
+ * Common rules: Wm even, Hm * Wm < 2^31; bitmap (optional) = the defect bitmap of eld_defect_flags, ceil(Wm / 32) uint32 words per row;
+ * code, pool, map and bitmap pointers 4-byte aligned.  ELD_EINVAL before any launch for what the host can see: null pointers, an odd Wm, a
+ * period other than 2 or 6, a misaligned pointer, S < 1, S > 16, a session with count < 1, count > 65536 or a range outside [0, F), a centre
+ * outside [0, 65535].  A zero-sized problem returns 0.
+ *
+ * eld_shading_fit_u16: pool, pool_elems, frames, F = a frame pool's buffer and DEVICE table, as eld_crop_pack_raw_*_u16; all frames Hm x Wm.
+ *   sessions: HOST int32[S][2], (first, count) ranges of the table; alpha, beta: HOST float64[S], the regression weights of the session means
+ *   (eld_amd.shading.fit_coefficients); centre: HOST int32[period^2], the nominal black level of cell (y % period, x % period).  Per site,
+ *   for s = 0 .. S-1 in order:
+ *       T_s = sum over the session's frames of int(u)                               exact (uint32: 65536 * 65535 < 2^32)
+ *       y_s = (double(T_s) - double(count_s) * double(centre)) / double(count_s)    product and difference exact: one rounding
+ *       A = A + alpha_s * y_s;  B = B + beta_s * y_s                                float64 from +0.0
+ *   out_a = float(A), out_b = float(B) (float32 [Hm,Wm]); a site flagged in the bitmap writes +0.0 to both.  A table entry that is not an
+ *   Hm x Wm frame at an even offset inside the pool contributes no codes (nothing outside the pool is read; the host wrapper checks its
+ *   table before the call).  One pass: 2 bytes read per site and frame, 8 written per site.  A lane owns 8 consecutive columns: 16-byte
+ *   loads where Wm % 8 == 0, the pool is 16-byte aligned and the frame's offset is a multiple of 8 elements; 32-bit words otherwise.
+ * eld_shading_apply_u16: in, out uint16 [N,Hm,Wm] (out == in is allowed), a, b float32 [Hm,Wm], one map for all frames:
+ *       ds = a + b * t;  r = rintf(ds) (ties to even);  out = clamp(int(u) - int(r), 0, 65535)
+ *   float32; r is limited to [-65536, 65536] before the conversion, which changes no result.  A flagged site passes through unchanged.
+ *   |ds - r| <= 0.5 DN stays in the frame as a fixed remainder (variance 1/12 for a spread-out ds).  16-byte accesses when Wm % 8 == 0 and
+ *   all four pointers are 16-byte aligned, 32-bit words otherwise.
+ * eld_pack_raw_bayer_u16_shaded / eld_pack_raw_xtrans_u16_shaded: eld_pack_raw_*_u16_gain with the map of the mosaic site (row, col) an element
+ *   packs from subtracted in float32 before the division -- nothing is rounded to codes:
+ *       ds = a[row][col] + b[row][col] * t;  v = ((float(u) - black_k) - ds) / denom_k;  out = min(max(min(max(v, 0), 1) * ratios[n], 0), 1)
+ *   a, b: float32 [2h,2w] (Bayer) / [Hm,Wm] (X-Trans), one map for all N frames.  With a = b = +0.0 the result is eld_pack_raw_*_u16_gain's,
+ *   bit for bit.  Bayer reads the map 16 bytes at a time when w is even and a, b are 16-byte aligned. */
+int eld_shading_fit_u16(const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int Hm, int Wm, const int32_t* sessions,
+                        int S, const double* alpha, const double* beta, const int32_t* centre, int period, const uint32_t* bitmap,
+                        float* out_a, float* out_b, void* stream);
+int eld_shading_apply_u16(const uint16_t* in, uint16_t* out, int N, int Hm, int Wm, const float* a, const float* b, float t,
+                          const uint32_t* bitmap, void* stream);
+int eld_pack_raw_bayer_u16_shaded(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
+                                  float white_point, const float* ratios, const float* a, const float* b, float t, void* stream);
+int eld_pack_raw_xtrans_u16_shaded(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
+                                   const float* ratios, const float* a, const float* b, float t, void* stream);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
