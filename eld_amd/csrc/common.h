@@ -54,6 +54,11 @@ static inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 // Test hook behind eld_debug_last_conv_kernel: the launcher that picks a convolution or weight-gradient kernel family records its name (a
 // string literal) right before the launch.  Host-side only: one relaxed atomic store per launch, no device work.
 void eld_note_conv_kernel(const char* family);
+// A launcher that runs a NON-default variant of its family (an ELD_* switch of this process chose another instantiation or another tile shape) records
+// "family/v1[,v2[,v3]]" instead: v1..v3 are string literals naming what differs from the default (nullptr or "": nothing), so a switch that is no
+// longer read or no longer reaches its kernel shows in the name.  With every part empty this is eld_note_conv_kernel(family): default runs keep
+// their names.  The joined names are interned once per distinct name (a mutex, non-default runs only).
+void eld_note_conv_variant(const char* family, const char* v1, const char* v2 = nullptr, const char* v3 = nullptr);
 
 // compute units of the CURRENT device (persistent-grid sizing); read once per device, immutable afterwards
 static inline int eld_num_cus() {

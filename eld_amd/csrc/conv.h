@@ -317,6 +317,8 @@ __host__ __device__ inline int conv_slot_of_lane(int m, bool grouped) {
 }
 __host__ __device__ inline bool conv_slots_grouped(int th, int tw, int TH) { return !(th == TH && tw == 32); }
 long long conv_tile_count(int N, int H, int W, int TH, bool pooled);
+// name of a non-default ELD_CONV_TILES mode of this process ("tiles-f", "tiles-p", "tiles-m", "tiles-q", "tiles-t") for eld_note_conv_variant; nullptr: the default choice
+const char* conv_tile_variant();
 
 // f32_line_store for pixel slots whose pixels are per-lane: p0 / p1 = channel 0 of the 32-channel block in the pixels of slot lane & 15 and slot
 // (lane & 15) + 16 of the MFMA column (nullptr: nothing to store).  EVERY lane must take part in the exchange.

@@ -436,8 +436,9 @@ int launch_conv_bfd(const ConvArgs& a, hipStream_t st) {
     if (a.pool_out && (a.epi != EPI_FWD || (a.H & 1) || (a.W & 1))) return ELD_EINVAL;
     const int bn = bfd_slab_bn(a.Nout, a.C0 + a.C1, a.N, a.H, a.W);
     if (bn == 32) return launch_conv_bfs(a, st);
-    if (bn == 128) { eld_note_conv_kernel("conv_bfd<128>"); return launch_bfd<128, 2, 8>(a, st); }
+    const char* tiles = a.pool_out ? nullptr : conv_tile_variant();      // (launches that fuse the pool keep 16 x 32 tiles whatever ELD_CONV_TILES says)
+    if (bn == 128) { eld_note_conv_variant("conv_bfd<128>", tiles); return launch_bfd<128, 2, 8>(a, st); }
     if (bn == 64 && bfw_takes(a)) return launch_conv_bfw(a, st);
-    if (bn == 64) { eld_note_conv_kernel("conv_bfd<64>"); return launch_bfd<64, 2, 8>(a, st); }
+    if (bn == 64) { eld_note_conv_variant("conv_bfd<64>", tiles); return launch_bfd<64, 2, 8>(a, st); }
     return ELD_ENOTSUP;
 }

@@ -281,6 +281,7 @@ static int launch_first_t(const float* x, const float* w, const float* bias, TO*
         ELD_LAUNCH_CHECK();
         return 0;
     }
+    if (Cin == 4) eld_note_conv_kernel("conv_first/mma0");      // ELD_FIRST_MMA=0 only: the default launches of this file record no name
     switch (Cin) {
         case 1: ELD_LAUNCH((conv_first_fwd_kernel<1, TO>), dim3(grid), dim3(256), 0, st, x, w, bias, out, N, H, W, lrelu); break;
         case 2: ELD_LAUNCH((conv_first_fwd_kernel<2, TO>), dim3(grid), dim3(256), 0, st, x, w, bias, out, N, H, W, lrelu); break;

@@ -28,6 +28,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <mutex>
+#include <set>
+#include <string>
 #include "conv.h"
 
 #define ELD_FP32_CONV_DEFAULT 1
@@ -457,12 +460,11 @@ static float tile_conflict_factor(int th, int tw, int TH) {
         }
     return (float)cyc / (float)n;
 }
-void conv_tile_shape(int N, int H, int W, int TH, bool pooled, int& th, int& tw) {
-    th = TH; tw = 32;
-    // ELD_CONV_TILES (A/B runs of the tile choice; virtual rows stay): f = TH x 32 everywhere, p = widths 8/16/32/64 only, m<k> = widths >= k,
-    // q<k> = widths that are multiples of k, t = fewest tiles (no conflict term)
-    // (function-local statics with initialisers: C++11 guarantees one thread-safe initialisation -- the entry points may be called from several host threads)
-    struct TileMode { int mode, marg; };
+// ELD_CONV_TILES (A/B runs of the tile choice; virtual rows stay): f = TH x 32 everywhere, p = widths 8/16/32/64 only, m<k> = widths >= k,
+// q<k> = widths that are multiples of k, t = fewest tiles (no conflict term)
+// (function-local statics with initialisers: C++11 guarantees one thread-safe initialisation -- the entry points may be called from several host threads)
+struct TileMode { int mode, marg; };
+static const TileMode& tile_mode() {
     static const TileMode tm = [] {
         TileMode t = {0, 0};
         const char* e = getenv("ELD_CONV_TILES");
@@ -473,6 +475,15 @@ void conv_tile_shape(int N, int H, int W, int TH, bool pooled, int& th, int& tw)
         if (e && e[0] == 't') t.mode = 5;
         return t;
     }();
+    return tm;
+}
+const char* conv_tile_variant() {
+    static const char* const names[6] = {nullptr, "tiles-f", "tiles-p", "tiles-m", "tiles-q", "tiles-t"};
+    return names[tile_mode().mode];
+}
+void conv_tile_shape(int N, int H, int W, int TH, bool pooled, int& th, int& tw) {
+    th = TH; tw = 32;
+    const TileMode& tm = tile_mode();
     const int mode = tm.mode, marg = tm.marg;
     if (pooled || mode == 1 || N <= 0 || H <= 0 || W <= 0 || (TH != 8 && TH != 16 && TH != 32)) return;
     const int ti = TH == 8 ? 0 : (TH == 16 ? 1 : 2);
@@ -525,6 +536,19 @@ void eld_note_conv_kernel(const char* family) {
         if (p == family || strcmp(p, family) == 0) { g_seen_count[i].fetch_add(1, std::memory_order_relaxed); return; }
     }
     g_seen_overflow.store(true, std::memory_order_relaxed);
+}
+void eld_note_conv_variant(const char* family, const char* v1, const char* v2, const char* v3) {
+    const char* v[3] = {v1, v2, v3};
+    std::string name;
+    for (int i = 0; i < 3; ++i)
+        if (v[i] && v[i][0]) { name += name.empty() ? '/' : ','; name += v[i]; }
+    if (name.empty()) { eld_note_conv_kernel(family); return; }
+    name.insert(0, family);
+    static std::mutex mu;
+    static std::set<std::string> names;              // node-based: c_str() of an element stays valid (the tables above keep the pointers)
+    const char* p;
+    { std::lock_guard<std::mutex> lk(mu); p = names.insert(name).first->c_str(); }
+    eld_note_conv_kernel(p);
 }
 extern "C" unsigned eld_debug_conv_kernel_count(const char* family) {
     if (!family) return 0;

@@ -1196,8 +1196,9 @@ static int launch_w8(WgradArgs a, hipStream_t st) {
     a.band = eld_tile_band();
     constexpr int COB = 32 * WCO, JBK = 32 * WCI;
     // fp32: the block shape (output x input channels) is part of the name -- five instantiations with their own staging and MFMA loops
-    eld_note_conv_kernel(sizeof(T) == 2 ? "wgrad8<bf16>" : (COB == 128 ? "wgrad8<f32,128x64>" : (COB == 64 ? (JBK == 64 ? "wgrad8<f32,64x64>" : "wgrad8<f32,64x32>")
-                                                                                                    : (JBK == 64 ? "wgrad8<f32,32x64>" : "wgrad8<f32,32x32>"))));
+    eld_note_conv_variant(sizeof(T) == 2 ? "wgrad8<bf16>" : (COB == 128 ? "wgrad8<f32,128x64>" : (COB == 64 ? (JBK == 64 ? "wgrad8<f32,64x64>" : "wgrad8<f32,64x32>")
+                                                                                                     : (JBK == 64 ? "wgrad8<f32,32x64>" : "wgrad8<f32,32x32>"))),
+                          STREAM == 1 ? "stream" : (STREAM == 2 ? "rowshare" : nullptr));      // the opt-in main loops (ELD_WG8_STREAM, ELD_WG8_ROWSHARE)
     a.vp = vrow_pitch(a.N, a.H, TH);
     a.tiles_x = (a.W + TWT - 1) / TWT;
     a.tiles_y = (vrow_extent(a.N, a.H, a.vp) + TH - 1) / TH;
@@ -1281,7 +1282,8 @@ static int launch_wgrad8(const WgradArgs& a, hipStream_t st) {
 
 template <typename T, int MODE, int WCO, int TH, int ALG = ALG_F32>
 static int launch_w(WgradArgs a, hipStream_t st) {
-    eld_note_conv_kernel(sizeof(T) == 2 ? (MODE == CONV_3X3 ? "wgrad<bf16>" : "wgrad<bf16,gather>") : (MODE == CONV_3X3 ? "wgrad<f32>" : "wgrad<f32,gather>"));
+    eld_note_conv_variant(sizeof(T) == 2 ? (MODE == CONV_3X3 ? "wgrad<bf16>" : "wgrad<bf16,gather>") : (MODE == CONV_3X3 ? "wgrad<f32>" : "wgrad<f32,gather>"),
+                          (sizeof(T) == 2 && ALG == ALG_F32) ? "f32mma" : nullptr);      // bf16 tensors widened onto the fp32 MFMA: ELD_WGRAD_BF16_MMA=0
     a.xcd = eld_xcd_mask() & XCD_WGRAD;
     constexpr int COB = 32 * WCO;
     constexpr int X_PIX = MODE == CONV_3X3 ? (TH + 2) * (TW + 2) : 4 * TH * TW;

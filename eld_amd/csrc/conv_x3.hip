@@ -992,7 +992,9 @@ int launch_x3(ConvArgs a, hipStream_t st) {
     const long long tiles = (long long)a.tiles_x * a.tiles_y * a.N * (a.Nout / BN);
     if (tiles <= 0) return 0;
     if (tiles > 0x7fffffffLL) return ELD_ENOTSUP;
-    eld_note_conv_kernel("conv_x3<32>");                      // (every instantiation has BN == 32)
+    // (every instantiation has BN == 32)  The default is the round-6 loop: BFIRST, BSLAB, STREAM; what an instantiation lacks is in its name
+    // (cut = fp32 packed weights cut per stage instead of pre-split slabs: ELD_X3W=0 without ELD_X3_BSLAB=1)
+    eld_note_conv_variant("conv_x3<32>", BSLAB ? nullptr : "cut", BFIRST ? nullptr : "bfirst0", STREAM ? nullptr : "stream0");
     auto kern = conv_x3_kernel<BN, RPW, DB, BFIRST, BSLAB, STREAM>;
     static EldAttrOnce once;
     { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
@@ -1031,7 +1033,10 @@ int launch_x3d(ConvArgs a, hipStream_t st) {
         if (ks >= 2) { a.ksplit = ks; tiles *= ks; }
     }
     if (tiles > 0x7fffffffLL) return ELD_ENOTSUP;
-    eld_note_conv_kernel(BN == 128 ? "conv_x3d<128,8>" : (BN == 32 ? "conv_x3d<32,8>" : (WAVES == 8 ? "conv_x3d<64,8>" : (a.ksplit > 1 ? "conv_x3d<64,4,splitk>" : "conv_x3d<64,4>"))));
+    // the 8-wave kernels of 64 / 128 channels default to the streamed weight-reuse loop (STREAM == 2); the others have the one loop (STREAM == 0)
+    eld_note_conv_variant(BN == 128 ? "conv_x3d<128,8>" : (BN == 32 ? "conv_x3d<32,8>" : (WAVES == 8 ? "conv_x3d<64,8>" : (a.ksplit > 1 ? "conv_x3d<64,4,splitk>" : "conv_x3d<64,4>"))),
+                          (WAVES == 8 && BN >= 64) ? (STREAM == 0 ? "stream0" : (STREAM == 1 ? "wreuse0" : nullptr)) : nullptr,
+                          a.pool_out ? nullptr : conv_tile_variant());
     auto kern = conv_x3d_kernel<BN, RPW, WAVES, DB, STREAM>;
     static EldAttrOnce once;
     { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }

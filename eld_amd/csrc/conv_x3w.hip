@@ -401,11 +401,11 @@ int launch_conv_x3w(const ConvArgs& a_in, hipStream_t st) {
     const long long tiles = (long long)a.tiles_x * a.tiles_y * a.N;
     if (tiles <= 0) return 0;
     if (tiles > 0x3fffffffLL) return ELD_ENOTSUP;
-    eld_note_conv_kernel("conv_x3w");
     constexpr size_t lds_bytes = (size_t)(2 * W_BWORDS + 2 * W_AWORDS) * sizeof(float);
     long long grid = (long long)eld_num_cus();
     if (grid > tiles) grid = tiles;
     const int mode = x3w_mode();
+    eld_note_conv_variant("conv_x3w", mode == 5 ? nullptr : (mode == 7 ? "m7" : (mode == 4 ? "m4" : (mode == 1 ? "m1" : (mode == 3 ? "m3" : "m2")))));      // (any other value runs mode 2)
     if (mode == 7) {
         static EldAttrOnce once;
         { const int rc = once.ensure(conv_x3w_kernel<8, 2, true, false, 8, true>, lds_bytes); if (rc) return rc; }

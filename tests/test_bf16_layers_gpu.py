@@ -252,7 +252,7 @@ CT = [  # forward family, backward-data family, N, H, W (input resolution), Cin,
 
 
 @pytest.mark.parametrize('ffam,bfam,N,H,W,Cin,Cout', CT)
-def test_convt2x2_bf16(lib, ffam, bfam, N, H, W, Cin, Cout):
+def test_convt2x2_bf16(lib, ffam, bfam, N, H, W, Cin, Cout, wfam='wgrad<bf16,gather>'):      # wfam: tests/variant_child.py passes a variant's name
     g = torch.Generator().manual_seed(7 * N * H * W + Cin)
     x = rand_bf16((N, H, W, Cin), g)
     w = (torch.randn(Cin, Cout, 2, 2, generator=g) / np.sqrt(Cin)).cuda()
@@ -278,7 +278,7 @@ def test_convt2x2_bf16(lib, ffam, bfam, N, H, W, Cin, Cout):
     dbias = torch.full((Cout,), float('nan'), device='cuda')
     Lb().check(lib.eld_convt2x2_backward_weight_bf16(dp(xb), dp(db16), dp(dw), dp(dbias), N, H, W, Cin, Cout, dp(ws), ws.numel(), st))
     torch.cuda.synchronize()
-    assert family(lib) == 'wgrad<bf16,gather>'
+    assert family(lib) == wfam
     f32_check(dw, R.convt_wgrad(x, d), R.f32_bound(R.convt_wgrad(x * x, d * d), N * H * W, R.convt_wgrad(x.abs(), d.abs())), 'convT dW')
     yb, bb = colsum_ref(d)
     f32_check(dbias, yb, bb, 'convT db')

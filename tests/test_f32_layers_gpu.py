@@ -10,9 +10,10 @@ proof in tests/test_f32_ref_cpu.py), both with exact +0 / -0 sprinkled into the 
 bit for bit.  The whole fp32 forward is checked teacher-forced: each of the 23 layers against the reference applied to the kernel's own
 saved input (eld_debug_unet_region), pools bit for bit, and the families chosen inside it (split-K among them) by launch counts.
 
-Out of scope: the opt-in modes read once per process from the environment (ELD_X3W other than the default, ELD_X3D_32 -> "conv_x3d<32,8>",
-ELD_X3_BSLAB, ELD_WG8_*), the other fp32 schemes (tests/test_unet_gpu.py runs them), and the backward's call-site variants (slope and
-pool codes: bit-for-bit tests in tests/test_unet_gpu.py; the region hook exposes no fp32 gradient regions).
+The modes read once per process from the environment (ELD_X3W other than the default, ELD_X3D_32 -> "conv_x3d<32,8>", ELD_X3_BSLAB, ELD_WG8_*, ...)
+run these same checks in one fresh interpreter per setting: tests/test_env_variants_gpu.py.  Out of scope: the other fp32 schemes
+(tests/test_unet_gpu.py runs them), and the backward's call-site variants (slope and pool codes: bit-for-bit tests in tests/test_unet_gpu.py; the
+region hook exposes no fp32 gradient regions).
 
 F32_MEASURED: worst error as a fraction of its bound per family, one MI355X (this file)."""
 import ctypes as C
