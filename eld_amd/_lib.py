@@ -17,6 +17,7 @@ IN_F32, IN_U16 = 0, 1
 ROUND_TRUNC, ROUND_NEAREST, ROUND_TRUNC_F32 = 0, 1, 2      # write-back rounding (eld_unpack_raw_*_u16)
 RENDER_SRGB8, RENDER_LINEAR_F32 = 0, 1                      # out_mode of eld_render_bayer / eld_render_xtrans
 NPLANES = 6
+PAIRSTATS_BINS = 61                                           # ELD_PAIRSTATS_BINS
 PLANE = {'counts': 0, 'n_shot': 1, 'n_read': 2, 't_tl': 3, 'n_row': 4, 'u_q': 5}
 
 # numpy mirror of struct EldNoiseParams (64 bytes)
@@ -103,6 +104,8 @@ SIGNATURES = {
     'eld_shading_apply_u16': (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _f, _vp, _vp]),
     'eld_pack_raw_bayer_u16_shaded': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp, _vp, _vp, _f, _vp]),
     'eld_pack_raw_xtrans_u16_shaded': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _vp]),
+    'eld_pair_level_stats_workspace_bytes': (_sz, [_i, _i, _i]),
+    'eld_pair_level_stats_u16': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _sz, _vp]),
     'eld_quality_assess_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'eld_quality_assess': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
     'eld_quality_assess_images': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),

@@ -387,6 +387,11 @@ def read_sidecar(path):
     rgb_camera_matrix -- a 3x4 / 4x4 matrix is cut to [:3, :3])."""
     with open(path) as fh:
         d = json.load(fh)
+    return sidecar_from_dict(d, path)
+
+
+def sidecar_from_dict(d, path):
+    """read_sidecar on an object already parsed from `path` (eld_amd.evaluate's manifest carries the same fields beside its pairs)."""
     if not isinstance(d, dict):
         raise ValueError('%s: the sidecar must be a JSON object' % path)
     out = {}

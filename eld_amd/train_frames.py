@@ -44,6 +44,8 @@ def build_parser():
     p.add_argument('--lr', type=float, default=1e-4)
     p.add_argument('--bf16', action='store_true', help='train the U-Net in bf16')
     p.add_argument('--seed', type=int, default=2018, help='np.random / torch / Philox seed')
+    p.add_argument('--val', metavar='PAIRS', help="held-out short/long pairs (eld_amd.evaluate's pairs.json): after every epoch print their mean PSNR / SSIM "
+                                                  'under the model being trained')
     return p
 
 
@@ -75,9 +77,31 @@ def dark_pool(manifest, camera, letters, patch, device=None, shading=None):
     return pool
 
 
+def val_pairs(path):
+    """--val: the manifest's pairs with their mosaics loaded, or None without the flag.  A missing file or a bad manifest is a ValueError before
+    anything is uploaded."""
+    if path is None:
+        return None
+    from .evaluate import load_pairs, read_manifest
+    return load_pairs(read_manifest(path)[1])
+
+
+def validate_epoch(engine, pairs, cfa, o, precision):
+    """Mean PSNR / SSIM of the held-out pairs under the network as it stands: evaluate_pairs(levels=False), which draws no random number and
+    runs the network's inference entry point (its own workspace: nothing of the training state is touched)."""
+    from .denoise import Denoiser
+    from .evaluate import evaluate_pairs
+    rep = evaluate_pairs(Denoiser(engine.model.netG, cfa, precision), pairs, cfa, raw_pattern=o.get('raw_pattern'), black_level=o.get('black_level'),
+                         white_point=o['white_point'], levels=False)
+    print('epoch %d  val PSNR %.3f  SSIM %.4f  (input %.3f %.4f, %d pairs)' % (engine.epoch, rep['mean']['psnr'], rep['mean']['ssim'],
+                                                                               rep['mean']['psnr_in'], rep['mean']['ssim_in'], len(pairs)))
+    return rep['mean']
+
+
 def main(argv=None):
     from .denoise import read_sidecar
     a = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    val = val_pairs(a.val)
     side = read_sidecar(a.meta) if a.meta else {}
     o = {k: v for k, v in side.items() if k in ('cfa', 'raw_pattern', 'black_level', 'white_point')}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white}
@@ -111,6 +135,8 @@ def main(argv=None):
                                                                                  pool.C, a.patch, a.patch))
     while engine.epoch < a.epochs:
         engine.train(loader)
+        if val is not None:
+            validate_epoch(engine, val, cfa, o, 'bf16' if a.bf16 else 'fp32')
     torch.save(engine.model.state_dict(), out)
     print('wrote %s' % out)
     return 0

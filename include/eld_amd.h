@@ -49,7 +49,9 @@ extern "C" {
  * noise) without a new number: two new symbols, no existing call changed in any way.  A binding finds them by symbol, as above.
  * Still 8: the dark-shading entry points (eld_shading_fit_u16, eld_shading_apply_u16, eld_pack_raw_bayer_u16_shaded,
  * eld_pack_raw_xtrans_u16_shaded) were added the same way: four new symbols, no existing call changed, so the Python binding, which binds
- * every symbol, needs a library built from this header or a later one (an older ABI-8 library fails at bind with the symbol's name). */
+ * every symbol, needs a library built from this header or a later one (an older ABI-8 library fails at bind with the symbol's name).
+ * Still 8: eld_pair_level_stats_u16 and eld_pair_level_stats_workspace_bytes were added the same way (exact error-versus-signal sums of an
+ * estimate against a reference frame): two new symbols, no existing call changed. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -587,6 +589,30 @@ int eld_pack_raw_bayer_u16_shaded(const uint16_t* mosaic, float* packed, int N, 
                                   float white_point, const float* ratios, const float* a, const float* b, float t, void* stream);
 int eld_pack_raw_xtrans_u16_shaded(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
                                    const float* ratios, const float* a, const float* b, float t, void* stream);
+
+/* ---- error versus signal level of an estimate against a reference (csrc/pairstats.hip, eld_amd/evaluate.py) ---------------
+ * est, ref [F,Hm,Wm] uint16 codes (any width, odd ones included), F <= 65535, Hm * Wm < 2^31; p = the pattern period (2 or 6); group: HOST
+ * array of p*p ints in [-1, G), cell (y % p, x % p) -> colour group, -1 = not counted, 1 <= G <= 4; black: HOST int32[p*p] in [0, 65535], the
+ * black level of each cell; white in [1, 65536]; bitmap (optional): the defect bitmap of eld_defect_flags, ceil(Wm / 32) uint32 words per row,
+ * one map for all frames.  A site (y, x) counts when y < Hc, x < Wc (0 <= Hc <= Hm, 0 <= Wc <= Wm: X-Trans passes the whole 6x6 cells, whose
+ * borders the write-back leaves untouched), its bit is clear and its group is not -1.  With c = (y % p) * p + x % p, g = group[c]:
+ *     s = int(ref) - black[c]        e = int(est) - int(ref)
+ *     bin = NB - 1                                     when ref >= white   (the saturated bin)
+ *           0                                          when s <= 0
+ *           s                                          when s < 8
+ *           8 + 4 * (o - 3) + ((s >> (o - 2)) & 3)     otherwise, o = floor(log2 s): quarter octaves
+ *   NB = ELD_PAIRSTATS_BINS = 61 (s <= 65535 ends in bin 59).  out[f][g][bin][0..3] += (1, s, e, e^2): int64, fully written by the call
+ *   (zeroed first).  e^2 < 2^32 and fewer than 2^31 sites: every sum fits.  Integer adds only, so the result is defined bit for bit whatever
+ *   the launch geometry (tests/pairstats_ref.py restates it in NumPy).
+ * One pass, 4 bytes read per site: 16-byte loads when est and ref are 16-byte aligned (any width: a frame is read as a flat array, the few
+ * sites around its aligned body one by one), 2-byte loads otherwise.  est and ref 2-byte aligned, bitmap 4-byte, out 8-byte.
+ * Workspace: eld_pair_level_stats_workspace_bytes(F, Hm, Wm) bytes (0 in this implementation: ws may then be NULL); ELD_EWS when ws_bytes
+ * is smaller.  ELD_EINVAL before any launch for everything the host can see: p, G, sizes, Hc > Hm, Wc > Wm, a group outside [-1, G), a black
+ * level outside [0, 65535], white outside [1, 65536], null or misaligned pointers.  F == 0: 0; an empty frame or crop: 0 after zeroing out. */
+#define ELD_PAIRSTATS_BINS 61
+size_t eld_pair_level_stats_workspace_bytes(int F, int Hm, int Wm);
+int eld_pair_level_stats_u16(const uint16_t* est, const uint16_t* ref, int F, int Hm, int Wm, int Hc, int Wc, int p, const int* group, int G,
+                             const int32_t* black, int white, const uint32_t* bitmap, int64_t* out, void* ws, size_t ws_bytes, void* stream);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
