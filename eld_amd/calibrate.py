@@ -7,6 +7,7 @@ can synthesise its noise.  The estimators are the contract of DESIGN.md, "Calibr
 (eld_amd/csrc/calib.hip: exact integer sums, the float64 residual, the Tukey-lambda PPCC), the rest is float64 NumPy on the host.
 
     sessions = [{'iso': 100, 'bias': (F,Hm,Wm) uint16, 'flats': (P,2,Hm,Wm) uint16}, ...]
+    sessions = [{'iso': 100, 'bias': (F,Hm,Wm) uint16, 'bursts': [(N,Hm,Wm) uint16, ...]}, ...]      # no flat field: bursts of a static scene
     params, diag = calibrate_camera(sessions, raw_pattern, black_level, white_level)
     save_camera_params(params, 'MyCam', 'camera_params/release')
 
@@ -584,20 +585,33 @@ def fit_log_linear(K, sigma):
 
 def _check_sessions(sessions, cfa='bayer'):
     if not isinstance(sessions, (list, tuple)) or len(sessions) == 0:
-        raise ValueError('sessions must be a non-empty list of {"iso", "bias", "flats"}')
+        raise ValueError('sessions must be a non-empty list of {"iso", "bias", "flats" or "bursts"}')
     shape, nbias = None, 0
     for i, s in enumerate(sessions):
-        for k in ('bias', 'flats'):
-            if k not in s:
-                raise ValueError('session %d has no %r' % (i, k))
+        if 'bias' not in s:
+            raise ValueError('session %d has no %r' % (i, 'bias'))
+        if 'flats' not in s and 'bursts' not in s:
+            raise ValueError("session %d has neither 'flats' (flat-field pairs) nor 'bursts' (stacks of a static scene): the gain needs one of them" % i)
         F, Hm, Wm = _check_mosaics(s['bias'], 3, 'session %d bias' % i, cfa)
-        P = _check_mosaics(s['flats'], 4, 'session %d flats' % i, cfa)[0]
         if shape is None:
             shape = (Hm, Wm)
-        if (Hm, Wm) != shape or _shape(s['flats'])[-2:] != shape:
-            raise ValueError('session %d: mosaic shapes differ (%s vs %s / %s)' % (i, shape, (Hm, Wm), _shape(s['flats'])[-2:]))
-        if F == 0 or P == 0:
-            raise ValueError('session %d: needs at least one bias frame and one flat pair' % i)
+        if 'flats' in s:
+            P = _check_mosaics(s['flats'], 4, 'session %d flats' % i, cfa)[0]
+            if (Hm, Wm) != shape or _shape(s['flats'])[-2:] != shape:
+                raise ValueError('session %d: mosaic shapes differ (%s vs %s / %s)' % (i, shape, (Hm, Wm), _shape(s['flats'])[-2:]))
+            if F == 0 or P == 0:
+                raise ValueError('session %d: needs at least one bias frame and one flat pair' % i)
+        elif (Hm, Wm) != shape or F == 0:
+            raise ValueError('session %d: needs at least one bias frame of %s, got %s' % (i, shape, (F, Hm, Wm)))
+        if 'bursts' in s:
+            if not isinstance(s['bursts'], (list, tuple)) or len(s['bursts']) == 0:
+                raise ValueError("session %d: 'bursts' is a non-empty list of stacks (N, Hm, Wm)" % i)
+            for j, b in enumerate(s['bursts']):
+                bs = _check_mosaics(b, 3, 'session %d burst %d' % (i, j), cfa)
+                if bs[-2:] != shape:
+                    raise ValueError('session %d burst %d: mosaic shapes differ (%s vs %s)' % (i, j, shape, bs[-2:]))
+                if bs[0] < 2 or bs[0] > 256:
+                    raise ValueError('session %d burst %d: a burst holds 2 to 256 frames, got %d' % (i, j, bs[0]))
         nbias += F
     if nbias < 3:
         raise ValueError('at least 3 bias frames are needed for the log-linear fits, got %d' % nbias)
@@ -606,7 +620,8 @@ def _check_sessions(sessions, cfa='bayer'):
 
 
 def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None, cfa='bayer', defects=None):
-    """Sessions of bias frames and flat pairs -> (params, diagnostics).  params has exactly the release schema
+    """Sessions of bias frames and flat pairs (or, in a session without 'flats', 'bursts': stacks (N,Hm,Wm) of a static scene whose gain is
+    eld_amd.burst.burst_gain over the session's bursts; bursts next to flats are reported as diag['ptc'][i]['burst']) -> (params, diagnostics).  params has exactly the release schema
     (Kmin, Kmax, G_shape (m,), color_bias (m,4) float32, 'Profile-1': {G_scale, R_scale, g_scale: {slope, bias, sigma}}), one G_shape /
     color_bias row per bias frame; diagnostics holds the per-frame samples, r(lambda) and the photon-transfer points.
     cfa='xtrans': raw_pattern is the 6x6 X-Trans pattern and black_level rawpy's 4 values by colour code; the table's color_bias is
@@ -636,11 +651,24 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
         st = bias_stats(s['bias'], raw_pattern, black_level, residual=True, defects=defects)
         pp = tukey_lambda_ppcc(st.pop('t'), lambdas)
         lam = pp['lambdas']
-        fl = flat_stats(s['flats'], raw_pattern, black_level, white_level, st['color_bias'].mean(axis=0), defects=defects)
         what = 'session %d (iso %s)' % (i, s.get('iso'))
-        K = ptc_gain(fl['mu'], fl['var'], fl['usable'], what)
+        burst = None
+        if 'bursts' in s:
+            from .burst import burst_gain, stack_burst
+            burst = burst_gain([stack_burst(b, cfa, raw_pattern, np.rint(_black(black_level)), white_level, defects=defects) for b in s['bursts']],
+                               what=what)
+        if 'flats' in s:                                           # a session with flat pairs behaves as it always did; its bursts are reported beside
+            fl = flat_stats(s['flats'], raw_pattern, black_level, white_level, st['color_bias'].mean(axis=0), defects=defects)
+            K = ptc_gain(fl['mu'], fl['var'], fl['usable'], what)
+            point = {'iso': s.get('iso'), 'mu': fl['mu'], 'var': fl['var'], 'usable': fl['usable'], 'K': K}
+            if burst is not None:
+                point['burst'] = burst
+        else:
+            K = burst['K']
+            point = {'iso': s.get('iso'), 'mu': burst['mu'], 'var': burst['var'], 'usable': np.ones(burst['mu'].shape, bool), 'K': K,
+                     'n': burst['n'], 'sigma0_sq': burst['sigma0_sq'], 'source': 'bursts'}
         Ks.append(K)
-        ptc.append({'iso': s.get('iso'), 'mu': fl['mu'], 'var': fl['var'], 'usable': fl['usable'], 'K': K})
+        ptc.append(point)
         for f in range(st['color_bias'].shape[0]):
             frames.append({'session': i, 'iso': s.get('iso'), 'K': K, 'lambda': float(pp['lam_hat'][f]), 'G_scale': float(pp['scale'][f]),
                            'R_scale': float(st['R_scale'][f]), 'g_scale': float(st['g_scale'][f]), 'color_bias': st['color_bias'][f]})
@@ -685,15 +713,21 @@ def load_manifest(path, with_cfa=False):
     sessions = []
     for s in m['sessions']:
         bias = np.stack([load(p) for p in s['bias']])
-        flats = np.stack([np.stack([load(a), load(b)]) for a, b in s['flats']])
-        sessions.append({'iso': s.get('iso'), 'bias': bias, 'flats': flats})
+        if 'flats' not in s and 'bursts' not in s:
+            raise ValueError("%s: a session needs 'flats' ([[a.npy, b.npy], ...]) or 'bursts' ([[a0.npy, a1.npy, ...], ...])" % path)
+        session = {'iso': s.get('iso'), 'bias': bias}
+        if 'flats' in s:
+            session['flats'] = np.stack([np.stack([load(a), load(b)]) for a, b in s['flats']])
+        if 'bursts' in s:
+            session['bursts'] = [np.stack([load(p) for p in b]) for b in s['bursts']]
+        sessions.append(session)
     out = (sessions, m['raw_pattern'], m['black_level'], m['white_level'])
     return out + (_cfa(m.get('cfa', 'bayer')),) if with_cfa else out
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m eld_amd.calibrate', description=__doc__.split('\n')[0])
-    ap.add_argument('manifest', help='JSON: raw_pattern, black_level, white_level, [cfa,] sessions [{iso, bias: [.npy], flats: [[a.npy, b.npy]]}]')
+    ap.add_argument('manifest', help='JSON: raw_pattern, black_level, white_level, [cfa,] sessions [{iso, bias: [.npy], flats: [[a.npy, b.npy]] or bursts: [[a0.npy, a1.npy, ...]]}]')
     ap.add_argument('--camera', required=True, help='camera name: writes <out>/<camera>_params.npy')
     ap.add_argument('--out', default=os.path.join('camera_params', 'release'))
     ap.add_argument('--defects', help="a defect map written by eld_amd.defects (.npz), or 'auto' to find one from the bias frames of the lowest-ISO "

@@ -1,7 +1,7 @@
 // pairstats.hip -- exact integer error-versus-signal sums of an estimate against a reference frame (eld_amd/evaluate.py).
 //
 //   eld_pair_level_stats_u16   est, ref uint16 mosaics [F,Hm,Wm] -> out[F][G][NB][4] = (n, sum s, sum e, sum e^2) per colour group and signal bin
-// s = int(ref) - black[cell], e = int(est) - int(ref), bin = a pure integer function of ref (bin_of below; NB = 61).  Sites outside
+// s = int(ref) - black[cell], e = int(est) - int(ref), bin = a pure integer function of ref (bin_of in levelbins.h; NB = 61).  Sites outside
 // [0, Hc) x [0, Wc), sites flagged in the defect bitmap and cells of group -1 contribute nothing.  Integer adds only: any arrival order, any
 // launch geometry gives the same bits.  e^2 <= 65535^2 < 2^32 and Hm Wm < 2^31, so sum e^2 < 2^63: every output fits int64.
 //
@@ -24,11 +24,11 @@
 // At its end a workgroup folds the copies and adds every non-zero sum to out[] with a 64-bit global integer atomic (at most 976 per 32768
 // sites); out[] is zeroed by a kernel of this call first.  No floating point anywhere, no environment switch, no workspace.
 #include "common.h"
+#include "levelbins.h"
 
 namespace {
 
 constexpr int PT = 512;                          // threads per workgroup
-constexpr int PS_NB = 61;                        // bins: 0, 1..7, quarter octaves 8..59, saturated 60
 constexpr int PS_TW = 4 * PS_NB;                 // table entries (G <= 4)
 constexpr int PS_COPIES = 16;
 constexpr int PS_QOFF = 3 * PS_TW;               // words n[TW], s[TW], e[TW], then TW double words of e^2 (732 is even: 8-byte aligned)
@@ -58,16 +58,6 @@ __global__ __launch_bounds__(256) void pairstats_zero_kernel(long long* __restri
 }
 
 extern __shared__ unsigned long long ps_lds[];
-
-__device__ __forceinline__ int bin_of(int ref, int s, int white) {
-    if (ref >= white) return PS_NB - 1;
-    if (s <= 0) return 0;
-    if (s < 8) return s;
-    const int o = 31 - __clz(s);
-    return 8 + 4 * (o - 3) + ((s >> (o - 2)) & 3);
-}
-
-__device__ __forceinline__ uint32_t mod6(uint32_t v) { return v - 6u * (__umulhi(v, 0xAAAAAAABu) >> 2); }
 
 // the pending run of one column parity
 struct Run {

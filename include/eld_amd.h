@@ -51,7 +51,9 @@ extern "C" {
  * eld_pack_raw_xtrans_u16_shaded) were added the same way: four new symbols, no existing call changed, so the Python binding, which binds
  * every symbol, needs a library built from this header or a later one (an older ABI-8 library fails at bind with the symbol's name).
  * Still 8: eld_pair_level_stats_u16 and eld_pair_level_stats_workspace_bytes were added the same way (exact error-versus-signal sums of an
- * estimate against a reference frame): two new symbols, no existing call changed. */
+ * estimate against a reference frame): two new symbols, no existing call changed.
+ * Still 8: eld_burst_stack_u16 and eld_burst_stack_workspace_bytes were added the same way (robust mean and photon-transfer sums of a burst of
+ * a static scene): two new symbols, no existing call changed. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -613,6 +615,32 @@ int eld_pack_raw_xtrans_u16_shaded(const uint16_t* mosaic, float* packed, int N,
 size_t eld_pair_level_stats_workspace_bytes(int F, int Hm, int Wm);
 int eld_pair_level_stats_u16(const uint16_t* est, const uint16_t* ref, int F, int Hm, int Wm, int Hc, int Wc, int p, const int* group, int G,
                              const int32_t* black, int white, const uint32_t* bitmap, int64_t* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- a burst of a static scene: robust mean and photon-transfer sums (csrc/burst.hip, eld_amd/burst.py) --------------------
+ * frames [N,Hm,Wm] uint16 codes of one scene shot N times from a tripod, 2 <= N <= 256, Hm * Wm < 2^31, any width; p, group, G, black, white
+ * and bitmap as eld_pair_level_stats_u16 (group and black: HOST arrays of p*p values per cell (y % p, x % p)).  All arithmetic is integer.
+ * Per site, with samples x_0 .. x_{N-1}:  S1 = sum x (< 2^24),  S2 = sum x^2 (< 2^40).
+ *   Leave-one-out rejection, active when N >= 4 and k2q > 0: d = N x - S1 ((N - 1) times the deviation of x from the mean of the others),
+ *   V1 = (N - 1)(S2 - x^2) - (S1 - x)^2 ((N - 1)^2 times the others' population variance); x is rejected iff
+ *       |d| > (N - 1) min_dev   and   4 d^2 (N - 2) > k2q (N - 1) V1
+ *   that is, iff x lies further than k sample deviations of the other N - 1 samples from their mean, k2q = round(4 k^2), and further than
+ *   min_dev DN.  0 <= k2q <= 256, 0 <= min_dev <= 65535: both sides then fit unsigned 64 bits (d^2 < 2^48, V1 < 2^46).
+ *   With n kept samples of sum S:  mean = (2 S + n) / (2 n) (rounds half up; n == 0, possible for k2q <= 5 only, gives 0);  kept = n as uint8,
+ *   256 written as 0 (kept may be NULL).  A site flagged in bitmap still gets mean and kept: repair is eld_defect_repair_u16's.
+ *   ptc (may be NULL) [G][ELD_PAIRSTATS_BINS][4] int64, fully written (zeroed first): over the ELIGIBLE sites -- group >= 0, not flagged,
+ *   n == N, max x < white, min x > 0 -- ptc[g][bin] += (1, S1, V mod 2^32, V >> 32) with V = N S2 - S1^2 (< 2^46) and bin = the bin of
+ *   eld_pair_level_stats_u16 for ref = mean, s = mean - black[cell].  The host recombines sum V = ptc[..][2] + 2^32 ptc[..][3].  Integer adds
+ *   only: the result is defined bit for bit whatever the launch geometry (tests/burst_ref.py restates it in NumPy).
+ * One pass, 2 N bytes read per site; 16-byte loads when frames and mean are 16-byte aligned, kept 8-byte aligned and Wm % 8 == 0, 32-bit
+ * words when frames and mean are 4-byte aligned, kept 2-byte aligned and Wm is even, 2-byte loads otherwise.  frames and mean 2-byte
+ * aligned, bitmap 4-byte, ptc 8-byte.  Workspace: eld_burst_stack_workspace_bytes(N, Hm, Wm) bytes (0 in this implementation: ws may then be
+ * NULL); ELD_EWS when ws_bytes is smaller.  ELD_EINVAL before any launch for everything the host can see: p, G, sizes, N outside [2, 256],
+ * k2q outside [0, 256], min_dev outside [0, 65535], a group outside [-1, G), a black level outside [0, 65535], white outside [1, 65536],
+ * null or misaligned pointers.  An empty frame: 0 after zeroing ptc. */
+size_t eld_burst_stack_workspace_bytes(int N, int Hm, int Wm);
+int eld_burst_stack_u16(const uint16_t* frames, int N, int Hm, int Wm, int p, const int* group, int G, const int32_t* black, int white,
+                        const uint32_t* bitmap, int k2q, int min_dev, uint16_t* mean, uint8_t* kept, int64_t* ptc, void* ws, size_t ws_bytes,
+                        void* stream);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
