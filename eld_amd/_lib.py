@@ -108,6 +108,13 @@ SIGNATURES = {
     'eld_pair_level_stats_u16': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _sz, _vp]),
     'eld_burst_stack_workspace_bytes': (_sz, [_i, _i, _i]),
     'eld_burst_stack_u16': (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'eld_burst_luma_pyramid_elems': (_sz, [_i, _i, _i, _i, _i]),
+    'eld_burst_luma_pyramid_u16': (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    'eld_burst_align_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'eld_burst_align_u16': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'eld_burst_stack_aligned_workspace_bytes': (_sz, [_i, _i, _i]),
+    'eld_burst_stack_aligned_u16': (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp,
+                                         _vp, _vp, _sz, _vp]),
     'eld_quality_assess_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'eld_quality_assess': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),
     'eld_quality_assess_images': (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _f, _vp]),

@@ -9,12 +9,23 @@ The mean of N short frames is the clean frame a tripod gives: where a long expos
 it; a sample that lies further than k deviations of the OTHER N - 1 samples from their mean (a cosmic-ray hit, a passing object) is left
 out.  The same pass sums, per colour group and signal bin, the temporal mean and variance of the sites nothing was rejected at: one
 scene covers every signal level, so a burst stands in for the flat-field pairs of eld_amd.calibrate (a session may give 'bursts').
-There is NO registration: a burst is a tripod burst.  What moves shows up as kept < N and is averaged over the frames it is absent from.
-The kernel is csrc/burst.hip (eld_burst_stack_u16: integer arithmetic only, defined bit for bit); the rule, the eligibility conditions
-and their selection bias are DESIGN.md sec. 20.
+Without align= there is no registration: a burst is a tripod burst.  What moves shows up as kept < N and is averaged over the frames it is
+absent from.  The kernel is csrc/burst.hip (eld_burst_stack_u16: integer arithmetic only, defined bit for bit); the rule, the eligibility
+conditions and their selection bias are DESIGN.md sec. 20.
+
+A hand-held burst is registered first:
+
+    stack = stack_burst(frames, 'bayer', raw_pattern, black_level, white_level, align=True)      # every frame aligned to frame 0
+    al = align_burst(frames, 'bayer', ref=2); al.shift_px(); al.outlier_share()                  # or the field on its own
+    stack = stack_burst(frames, ..., align=al); stack.present                                    # samples found inside the frame, per site
+
+align_burst is a coarse-to-fine search over 16 x 16 tiles of a luma pyramid (one luma pixel per CFA cell); displacements are whole CFA
+periods, so every sample stays a raw code of its site's colour and nothing is resampled.  The stack then gathers each site's samples
+through the field and the rule above rejects what alignment could not fix (csrc/align.hip).  The gain still wants a
+tripod: misalignment below one CFA period adds variance wherever the scene has gradients and biases K upward.
 
 Command line: python -m eld_amd.burst 'burst/*.npy' --meta sensor.json -o clean.npy [--kept kept.npy] [--ptc ptc.json] [--defects map.npz]
-[--k 5] [--min-dev 2]
+[--k 5] [--min-dev 2] [--align [--ref N] [--disp field.npy]]
 """
 import argparse
 import ctypes
@@ -31,6 +42,10 @@ MAX_FRAMES = 256
 TILE_UNITS = 2048               # csrc/burst.hip BS_UNITS: units (8, 2 or 1 adjacent sites of a row) per workgroup; the tests size a frame by it
 TILE_SITES = TILE_UNITS * 8     # sites per workgroup on the 16-byte path
 FLICKER_FACTOR = 3.0            # warn when the frame means spread more than this times what the sites' own temporal noise explains
+ALIGN_TILE = 16                 # csrc/align.hip AL_T: tile side in luma pixels (CFA cells)
+ALIGN_RADIUS = 4                # AL_R: search radius per pyramid level
+ALIGN_MAX_LEVELS = 4
+ALIGN_MAX_DISP = ALIGN_RADIUS * (1 + 2 + 4 + 8)     # 60 luma pixels: what four levels can reach
 
 
 class BurstStack:
@@ -42,10 +57,14 @@ class BurstStack:
     N        frames in the burst
     period, group, G, black    the layout the sums were taken with: cell (y % p) * p + x % p -> colour group and black level
     group_black   the black level of each group (the mean over its cells)
-    cfa, white, k2q, min_dev   as given"""
+    cfa, white, k2q, min_dev   as given
+    present  None, or for an aligned stack a uint8 CUDA tensor (Hm,Wm): the frames whose sample lay inside the frame (0 stands for 256);
+             kept counts out of present, and only sites with present == N enter ptc
+    align    None, or the BurstAlignment the samples were gathered through"""
 
-    def __init__(self, mean, kept, ptc, N, cfa, period, group, G, black, white, k2q, min_dev):
+    def __init__(self, mean, kept, ptc, N, cfa, period, group, G, black, white, k2q, min_dev, present=None, align=None):
         self.mean, self.kept, self.ptc, self.N = mean, kept, ptc, N
+        self.present, self.align = present, align
         self.cfa, self.period, self.group, self.G, self.black, self.white = cfa, period, list(group), G, list(black), white
         self.k2q, self.min_dev = k2q, min_dev
         g, b = np.asarray(self.group), np.asarray(self.black, np.float64)
@@ -54,8 +73,59 @@ class BurstStack:
     def rejected_share(self):
         """The share of sites that lost at least one sample."""
         k = self.kept.to('cpu').numpy().astype(np.int64)
-        k[k == 0] = 256
-        return float(np.mean(k != self.N))
+        if self.present is None:
+            k[k == 0] = 256
+            return float(np.mean(k != self.N))
+        m = self.present.to('cpu').numpy().astype(np.int64)
+        if self.N == 256:
+            m[m == 0] = 256                                        # frame ref is always present: 0 can only stand for 256
+            k[(k == 0) & (m == 256)] = 256                         # k2q >= 6 keeps at least one sample
+        return float(np.mean(k != m))
+
+    def absent_share(self):
+        """The share of sites that some frame's sample fell outside the frame for (aligned stacks; 0.0 otherwise)."""
+        if self.present is None:
+            return 0.0
+        m = self.present.to('cpu').numpy().astype(np.int64)
+        return float(np.mean(m != self.N % 256))
+
+
+class BurstAlignment:
+    """What align_burst returns, and what stack_burst(align=...) takes.
+
+    disp     host int16 (N, TY, TX, 2): (dy, dx) of every 16 x 16-cell tile of every frame, in luma pixels = CFA periods; zero for frame ref
+    cost     host uint32 (N, TY, TX): the winning candidate's sum of absolute luma differences over the tile (None when built by hand)
+    period   the CFA period the field counts in (2 Bayer, 6 X-Trans);  tile = 16;  levels: pyramid levels searched;  ref: the reference frame"""
+
+    def __init__(self, disp, cost=None, period=2, tile=ALIGN_TILE, levels=1, ref=0):
+        disp = np.asarray(disp)
+        if disp.dtype.kind not in 'iu' or disp.ndim != 4 or disp.shape[3] != 2:
+            raise ValueError('disp must be an integer array (N, TY, TX, 2), got %s %s' % (disp.dtype, disp.shape))
+        if disp.size and np.abs(disp.astype(np.int64)).max() > ALIGN_MAX_DISP:
+            raise ValueError('a displacement beyond +-%d luma pixels' % ALIGN_MAX_DISP)
+        if cost is not None:
+            cost = np.asarray(cost)
+            if cost.shape != disp.shape[:3]:
+                raise ValueError('cost must have shape %s, got %s' % (disp.shape[:3], cost.shape))
+            cost = cost.astype(np.uint32)
+        if period not in (2, 6) or tile != ALIGN_TILE:
+            raise ValueError('period must be 2 or 6 and tile %d, got %r and %r' % (ALIGN_TILE, period, tile))
+        self.disp, self.cost = np.ascontiguousarray(disp.astype(np.int16)), cost
+        self.period, self.tile, self.levels, self.ref = int(period), int(tile), int(levels), int(ref)
+
+    def _median(self):
+        N = self.disp.shape[0]
+        return np.median(self.disp.reshape(N, -1, 2).astype(np.float64), axis=1)
+
+    def shift_px(self):
+        """float64 (N, 2): every frame's median displacement (dy, dx) in mosaic pixels."""
+        return self._median() * self.period
+
+    def outlier_share(self):
+        """float64 (N,): per frame, the share of tiles more than 1 luma pixel (in either axis) from the frame's median displacement."""
+        N = self.disp.shape[0]
+        d = np.abs(self.disp.reshape(N, -1, 2).astype(np.float64) - self._median()[:, None, :])
+        return np.mean(d.max(axis=2) > 1.0, axis=1)
 
 
 # ---- argument checks (host only: they run before any device work) ----------------------------------------------------------------------
@@ -91,13 +161,87 @@ def _check_burst(frames, cfa, what='frames'):
     return N, Hm, Wm
 
 
-# ---- the kernel's wrapper ----------------------------------------------------------------------------------------------------------------
-def stack_burst(frames, cfa='bayer', raw_pattern=None, black_level=None, white_level=16383, k=5.0, min_dev=2, defects=None):
+def _period(cfa):
+    if cfa not in ('bayer', 'xtrans'):
+        raise ValueError("cfa must be 'bayer' or 'xtrans', got %r" % (cfa,))
+    return 2 if cfa == 'bayer' else 6
+
+
+def align_levels(Hm, Wm, p, levels=None):
+    """The pyramid levels of a frame: the largest count (1..4) whose every level keeps both sides >= ALIGN_TILE luma pixels when levels is
+    None, else `levels` checked against that.  ValueError when the frame is below one tile or the count does not fit."""
+    h, w = Hm // p, Wm // p
+    if h < ALIGN_TILE or w < ALIGN_TILE:
+        raise ValueError('a frame of %d x %d has a luma plane of %d x %d, below one %d x %d tile: too small to align'
+                         % (Hm, Wm, h, w, ALIGN_TILE, ALIGN_TILE))
+    most = 1
+    while most < ALIGN_MAX_LEVELS and (h + 1) // 2 >= ALIGN_TILE and (w + 1) // 2 >= ALIGN_TILE:
+        h, w, most = (h + 1) // 2, (w + 1) // 2, most + 1
+    if levels is None:
+        return most
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1 or levels > ALIGN_MAX_LEVELS:
+        raise ValueError('levels must be an integer in [1, %d], got %r' % (ALIGN_MAX_LEVELS, levels))
+    if levels > most:
+        raise ValueError('levels = %d: level %d of a %d x %d frame has a side below %d (at most %d levels)'
+                         % (levels, levels - 1, Hm, Wm, ALIGN_TILE, most))
+    return int(levels)
+
+
+def _tile_grid(Hm, Wm, p):
+    return -(-(Hm // p) // ALIGN_TILE), -(-(Wm // p) // ALIGN_TILE)
+
+
+def _check_ref(ref, N):
+    if isinstance(ref, bool) or not isinstance(ref, (int, np.integer)) or ref < 0 or ref >= N:
+        raise ValueError('ref must be a frame of the burst (0..%d), got %r' % (N - 1, ref))
+    return int(ref)
+
+
+# ---- the kernels' wrappers ---------------------------------------------------------------------------------------------------------------
+def align_burst(frames, cfa='bayer', ref=0, levels=None):
+    """Register every frame of a burst to frame `ref`: a coarse-to-fine search of 16 x 16-cell tiles over a luma pyramid of `levels` levels
+    (default: as many as the frame allows, at most 4; each level doubles the reach: 4, 12, 28, 60 CFA periods).  -> BurstAlignment.
+    Translation per tile in whole CFA periods; no rotation model, no exposure compensation.  Bad arguments raise ValueError before any
+    device work."""
+    from . import calibrate as CAL
+    p = _period(cfa)
+    N, Hm, Wm = _check_burst(frames, cfa)
+    ref = _check_ref(ref, N)
+    levels = align_levels(Hm, Wm, p, levels)
+    TY, TX = _tile_grid(Hm, Wm, p)
+    import torch
+    lib = L.lib()
+    u = CAL._device_u16(frames)
+    with torch.cuda.device(u.device):
+        disp = torch.empty((N, TY, TX, 2), dtype=torch.int16, device=u.device)
+        cost = torch.empty((N, TY, TX), dtype=torch.int32, device=u.device)
+        need = lib.eld_burst_align_workspace_bytes(N, Hm, Wm, p, levels)
+        ws = torch.empty(max(need, 4), dtype=torch.uint8, device=u.device)
+        L.check(lib.eld_burst_align_u16(L.dptr(u), N, Hm, Wm, p, ref, levels, L.dptr(disp), L.dptr(cost), L.dptr(ws), need, L.cur_stream()),
+                'eld_burst_align_u16')
+    return BurstAlignment(disp.cpu().numpy(), cost.cpu().numpy().view(np.uint32), p, ALIGN_TILE, levels, ref)
+
+
+def _check_alignment(align, N, Hm, Wm, p):
+    if not isinstance(align, BurstAlignment):
+        raise ValueError('align must be None, True or a BurstAlignment, got %r' % (type(align).__name__,))
+    if align.period != p:
+        raise ValueError('the alignment counts in CFA periods of %d, the burst has %d' % (align.period, p))
+    want = (N,) + _tile_grid(Hm, Wm, p) + (2,)
+    if align.disp.shape != want:
+        raise ValueError('the alignment field has shape %s, a burst of %d frames of %d x %d takes %s' % (align.disp.shape, N, Hm, Wm, want))
+    return align
+
+
+def stack_burst(frames, cfa='bayer', raw_pattern=None, black_level=None, white_level=16383, k=5.0, min_dev=2, defects=None, align=None):
     """Stack N frames of one static scene.  frames: uint16 (N,Hm,Wm), 2 <= N <= 256, a NumPy array or a CUDA uint16 / int16-view tensor.
     raw_pattern, black_level: as eld_amd.evaluate.pair_level_stats (Bayer: 4 colour groups by CFA position; X-Trans: 3 by colour);
     white_level: codes >= it are saturated.  k: a sample further than k sample deviations of the other N - 1 from their mean is rejected
     (N >= 4; k = 0 switches the rule off; k <= 8), but never one within min_dev DN of that mean.  defects: a DefectMap (or its path) whose
     sites are kept out of the photon-transfer sums; they still get a mean (repair them downstream, as every frame).  -> BurstStack.
+    align: None stacks the frames as they lie (a tripod burst); True registers them to frame 0 first (align_burst), a BurstAlignment is used
+    as given.  An aligned stack takes each site's samples through the field, reports in `present` how many lay inside the frame, applies
+    the rule over those, and counts only sites with all N present in the photon-transfer sums.
     Bad arguments raise ValueError before any device work."""
     from . import calibrate as CAL
     from .evaluate import _cells, _white
@@ -109,9 +253,31 @@ def stack_burst(frames, cfa='bayer', raw_pattern=None, black_level=None, white_l
         from .defects import as_defect_map
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'stack_burst')
+    if align is not None and align is not False and align is not True:
+        _check_alignment(align, N, Hm, Wm, p)
+    if align is True:
+        align_levels(Hm, Wm, p)
     import torch
-    u = CAL._device_u16(frames)
     lib = L.lib()
+    u = CAL._device_u16(frames)
+    if align is not None and align is not False:
+        if align is True:
+            align = align_burst(u, cfa, 0)
+        TY, TX = align.disp.shape[1:3]
+        with torch.cuda.device(u.device):
+            mean = torch.empty((Hm, Wm), dtype=torch.int16, device=u.device)
+            kept = torch.empty((Hm, Wm), dtype=torch.uint8, device=u.device)
+            present = torch.empty((Hm, Wm), dtype=torch.uint8, device=u.device)
+            ptc = torch.empty((G, NB, 4), dtype=torch.int64, device=u.device)
+            disp = torch.from_numpy(align.disp).to(u.device)
+            need = lib.eld_burst_stack_aligned_workspace_bytes(N, Hm, Wm)
+            ws = torch.empty(max(need, 4), dtype=torch.uint8, device=u.device)
+            bm = None if defects is None else defects.bitmap_on(u.device)
+            L.check(lib.eld_burst_stack_aligned_u16(L.dptr(u), N, Hm, Wm, p, (ctypes.c_int * (p * p))(*group), G, (ctypes.c_int32 * (p * p))(*black),
+                                                    white, L.dptr(bm), k2q, min_dev, L.dptr(disp), TY, TX, L.dptr(mean), L.dptr(kept),
+                                                    L.dptr(present), L.dptr(ptc), L.dptr(ws), need, L.cur_stream()),
+                    'eld_burst_stack_aligned_u16')
+        return BurstStack(mean.view(torch.uint16), kept, ptc.cpu().numpy(), N, cfa, p, group, G, black, white, k2q, min_dev, present, align)
     with torch.cuda.device(u.device):
         mean = torch.empty((Hm, Wm), dtype=torch.int16, device=u.device)
         kept = torch.empty((Hm, Wm), dtype=torch.uint8, device=u.device)
@@ -241,6 +407,9 @@ def build_parser():
     p.add_argument('--defects', metavar='F', help='a defect map written by eld_amd.defects (.npz)')
     p.add_argument('--k', type=float, default=5.0, help='reject a sample beyond k deviations of the other frames (default 5; 0: off)')
     p.add_argument('--min-dev', type=int, default=2, help='never reject a sample within this many DN of the mean of the others (default 2)')
+    p.add_argument('--align', action='store_true', help='a hand-held burst: register every frame to the reference frame before stacking')
+    p.add_argument('--ref', type=int, default=0, metavar='N', help='the reference frame of --align (default 0)')
+    p.add_argument('--disp', metavar='OUT', help='with --align: write the displacement field (.npy, int16 (N, TY, TX, 2), CFA periods)')
     return p
 
 
@@ -263,18 +432,23 @@ def load_burst(patterns):
     return np.stack(frames)
 
 
-def run(frames, o, k=5.0, min_dev=2):
-    """The command line's work on loaded frames and sidecar options -> (BurstStack, result dict)."""
+def run(frames, o, k=5.0, min_dev=2, align=False, ref=0):
+    """The command line's work on loaded frames and sidecar options -> (BurstStack, result dict).  align: register the frames to frame
+    `ref` first; the result then carries 'shift_px', 'outlier_share' and 'absent_share'."""
     kw = dict(cfa=o.get('cfa', 'bayer'), raw_pattern=o.get('raw_pattern'), black_level=o.get('black_level'))
     defects = o.get('defects')
     if defects is not None:
         from .defects import as_defect_map
         defects = as_defect_map(defects)
-    stack = stack_burst(frames, white_level=o.get('white_point', 16383), k=k, min_dev=min_dev, defects=defects, **kw)
+    field = align_burst(frames, kw['cfa'], ref) if align else None
+    stack = stack_burst(frames, white_level=o.get('white_point', 16383), k=k, min_dev=min_dev, defects=defects, align=field, **kw)
     levels, sites = frame_levels(frames, defects=defects, **kw)
     res = {'N': stack.N, 'rejected_share': stack.rejected_share(), 'flicker': flicker_check(levels, sites, stack), 'K': None, 'sigma0': None,
            'frame_levels': levels.tolist()}
     res['warning'] = res['flicker']['warning']
+    if field is not None:
+        res.update(ref=field.ref, levels=field.levels, shift_px=field.shift_px().tolist(), outlier_share=field.outlier_share().tolist(),
+                   absent_share=stack.absent_share())
     try:
         fit = burst_gain([stack])
         res['K'], res['sigma0_sq'] = fit['K'], fit['sigma0_sq']
@@ -290,18 +464,30 @@ def main(argv=None):
     o = read_sidecar(a.meta) if a.meta else {}
     if a.defects is not None:
         o['defects'] = a.defects
-    stack, res = run(load_burst(a.inputs), o, a.k, a.min_dev)
+    if (a.disp or a.ref) and not a.align:
+        raise SystemExit('--ref and --disp go with --align')
+    stack, res = run(load_burst(a.inputs), o, a.k, a.min_dev, a.align, a.ref)
     np.save(a.out, stack.mean.cpu().numpy())
     print('stacked %d frames -> %s' % (res['N'], a.out))
     print('sites with a rejected sample: %.4f %%' % (100.0 * res['rejected_share']))
+    if a.align:
+        print('aligned to frame %d over %d pyramid levels' % (res['ref'], res['levels']))
+        for i, (sh, out) in enumerate(zip(res['shift_px'], res['outlier_share'])):
+            print('frame %d: shift %+.0f %+.0f px (dy dx), outlier tiles %.2f %%' % (i, sh[0], sh[1], 100.0 * out))
+        print('sites with a sample outside the frame: %.4f %%' % (100.0 * res['absent_share']))
     if res['K'] is not None:
         print('K %.5g DN/e-  sigma0 %.4g DN' % (res['K'], res['sigma0']))
+        if a.align:
+            print('  (a hand-held burst: misalignment below one CFA period adds variance where the scene has gradients and biases K '
+                  'upward; take the gain from a tripod burst)')
     else:
         print('no gain: %s' % res['gain_error'])
     if res['warning']:
         print('WARNING: %s' % res['warning'])
     if a.kept:
         np.save(a.kept, stack.kept.cpu().numpy())
+    if a.disp:
+        np.save(a.disp, stack.align.disp)
     if a.ptc:
         with open(a.ptc, 'w') as fh:
             json.dump(dict(res, ptc=stack.ptc.tolist(), group_black=stack.group_black.tolist(), k2q=stack.k2q, min_dev=stack.min_dev), fh, indent=1)

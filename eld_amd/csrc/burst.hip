@@ -36,27 +36,14 @@
 // the table in LDS with a copy stride of 2 modulo 32 words, then at most G * 61 * 4 64-bit global integer atomics per workgroup of
 // BS_UNITS * CW <= 16384 sites into ptc[], which a kernel of this call zeroes first.  Integer adds only: any arrival order gives the same
 // bits.  No floating point, no environment switch, no workspace.
-#include "common.h"
-#include "levelbins.h"
+#include "burst_dev.h"
 
 namespace {
 
-constexpr int BT = 256;                          // threads per workgroup
 constexpr int BS_TURNS = 8;                      // units per lane
 constexpr int BS_UNITS = BT * BS_TURNS;          // 2048 units per workgroup (eld_amd/burst.py TILE_UNITS mirrors it for the tests)
 constexpr int BS_DEPTH = 4;                      // frames whose loads are in flight
-constexpr int BS_TW = 4 * PS_NB;                 // table entries (G <= 4)
-constexpr int BS_COPIES = 4;                     // 23.6 KB of LDS: six workgroups fit a CU, the registers allow four
-constexpr int BS_OFF_V = 2 * BS_TW;              // words: TW double words of sum S1, TW double words of sum Vlo, TW words n, TW words sum Vhi
-constexpr int BS_OFF_N = 4 * BS_TW;
-constexpr int BS_OFF_H = 5 * BS_TW;
-constexpr int BS_STRIDE = 1474;                  // >= 6 * TW = 1464, even, and 2 modulo 32
-static_assert(BS_STRIDE >= 6 * BS_TW && BS_STRIDE % 32 == 2, "LDS layout");
-static_assert(BS_COPIES * BS_STRIDE * 4 <= 65536, "static LDS");
 static_assert((long long)BS_UNITS * 8 * (1 << 14) < (1ll << 32), "32-bit partial sums of V >> 32 (V < 2^46) and of the site count");
-static_assert(256ll * 65535 < (1ll << 24) && 256ll * 65535 * 65535 < (1ll << 40), "S1, |d| < 2^24 and S2 < 2^40");
-static_assert(255ull * 255 * 65535 * 65535 / 4 < (1ull << 46) && 256ull * 256 * 65535 * 65535 / 4 < (1ull << 46), "V1, V < 2^46");
-static_assert(4ull * 254 * (255ull * 65535) * (255ull * 65535) < (1ull << 58), "4 (N - 2) d^2 < 2^58");
 
 struct BurstArgs {
     const uint16_t* frames;
@@ -70,26 +57,6 @@ struct BurstArgs {
     FastDiv dupr;
     int32_t tab[36];                             // cell -> black | (group + 1) << 16
 };
-
-__global__ __launch_bounds__(256) void burst_zero_kernel(unsigned long long* __restrict__ p, int n) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) p[i] = 0;
-}
-
-// the pending run of one column parity
-struct Run {
-    int key;
-    uint32_t n, vhi;
-    unsigned long long s1, vlo;
-};
-
-__device__ __forceinline__ void run_flush(uint32_t* __restrict__ tab, const Run& r) {
-    if (r.key >= 0) {
-        atomicAdd(reinterpret_cast<unsigned long long*>(tab) + r.key, r.s1);
-        atomicAdd(reinterpret_cast<unsigned long long*>(tab + BS_OFF_V) + r.key, r.vlo);
-        atomicAdd(tab + BS_OFF_N + r.key, r.n);
-        atomicAdd(tab + BS_OFF_H + r.key, r.vhi);
-    }
-}
 
 template <int CW>
 __device__ __forceinline__ void load_codes(const uint16_t* __restrict__ p, uint32_t (&w)[(CW + 1) / 2]) {
@@ -119,22 +86,11 @@ __global__ __launch_bounds__(BT) void burst_stack_kernel(BurstArgs a) {
     uint32_t* tab = lds + (threadIdx.x & (BS_COPIES - 1)) * BS_STRIDE;
     const int N = a.N, white = a.white;
     const bool rej_on = N >= 4 && a.k2q > 0;
-    const uint32_t dev_floor = (uint32_t)(N - 1) * (uint32_t)a.min_dev;      // < 2^24
-    const uint32_t c_left = 4u * (uint32_t)(N - 2), c_right = (uint32_t)a.k2q * (uint32_t)(N - 1);   // < 2^10, <= 2^16
+    const BurstRule rule(N, a.k2q, a.min_dev);
+    const uint32_t dev_floor = rule.dev_floor;                   // < 2^24
     Run run[2];
-    run[0].key = run[1].key = -1;
-    run[0].n = run[1].n = 0; run[0].vhi = run[1].vhi = 0; run[0].s1 = run[1].s1 = 0; run[0].vlo = run[1].vlo = 0;
-
-    // the rule for one sample of a site with sums s1, s2
-    auto rejected = [&](uint32_t x, uint32_t s1, unsigned long long s2) __attribute__((always_inline)) -> bool {
-        const int32_t d = (int32_t)((uint32_t)N * x) - (int32_t)s1;
-        const uint32_t ad = d < 0 ? (uint32_t)-d : (uint32_t)d;
-        if (ad <= dev_floor) return false;
-        const unsigned long long d2 = (unsigned long long)ad * ad;                                 // < 2^48
-        const uint32_t r1 = s1 - x;
-        const unsigned long long v1 = (unsigned long long)(uint32_t)(N - 1) * (s2 - (unsigned long long)(x * x)) - (unsigned long long)r1 * r1;   // < 2^46
-        return d2 * c_left > v1 * c_right;                                                         // < 2^58, < 2^62
-    };
+    run_clear(run[0]);
+    run_clear(run[1]);
 
     const uint32_t u0 = blockIdx.x * (uint32_t)BS_UNITS;
     const uint32_t u1 = min(u0 + (uint32_t)BS_UNITS, a.units);
@@ -190,7 +146,7 @@ __global__ __launch_bounds__(BT) void burst_stack_kernel(BurstArgs a) {
                 for (int j = 0; j < CW; ++j)
                     if ((need >> j) & 1u) {
                         const uint32_t x = code_of(w, j);
-                        if (!rejected(x, S1[j], S2[j])) { Sk[j] += x; nk[j] += 1; }
+                        if (!rule.rejected(x, S1[j], S2[j])) { Sk[j] += x; nk[j] += 1; }
                     }
             };
             int f2 = 0;
@@ -225,12 +181,7 @@ __global__ __launch_bounds__(BT) void burst_stack_kernel(BurstArgs a) {
                     const int key = g * PS_NB + bin_of((int)m[j], (int)m[j] - (t & 0xFFFF), white);
                     const unsigned long long v = V[j];
                     Run& r = run[CW % 2 == 0 ? (j & 1) : 0];     // x0 is even when CW is; CW = 1 keeps one run (a static index: registers)
-                    if (key == r.key) {
-                        r.n += 1; r.vhi += (uint32_t)(v >> 32); r.s1 += S1[j]; r.vlo += (uint32_t)v;
-                    } else {
-                        run_flush(tab, r);
-                        r.key = key; r.n = 1; r.vhi = (uint32_t)(v >> 32); r.s1 = S1[j]; r.vlo = (uint32_t)v;
-                    }
+                    run_add(tab, r, key, S1[j], v);
                 }
             }
         }
@@ -252,25 +203,7 @@ __global__ __launch_bounds__(BT) void burst_stack_kernel(BurstArgs a) {
     run_flush(tab, run[1]);
 
     __syncthreads();
-    const int tw = a.G * PS_NB;
-    for (int k = threadIdx.x; k < tw; k += BT) {
-        uint32_t n = 0, vhi = 0;
-        unsigned long long s1 = 0, vlo = 0;
-        for (int c = 0; c < BS_COPIES; ++c) {
-            const uint32_t* t = lds + c * BS_STRIDE;
-            s1 += reinterpret_cast<const unsigned long long*>(t)[k];
-            vlo += reinterpret_cast<const unsigned long long*>(t + BS_OFF_V)[k];
-            n += t[BS_OFF_N + k];
-            vhi += t[BS_OFF_H + k];
-        }
-        unsigned long long* o = a.ptc + 4 * k;
-        if (n) {                                                 // an entry without sites has all four sums zero
-            atomicAdd(o, (unsigned long long)n);
-            atomicAdd(o + 1, s1);
-            if (vlo) atomicAdd(o + 2, vlo);
-            if (vhi) atomicAdd(o + 3, (unsigned long long)vhi);
-        }
-    }
+    ptc_merge(lds, a.ptc, a.G);
 }
 
 template <int P, int CW>

@@ -53,7 +53,10 @@ extern "C" {
  * Still 8: eld_pair_level_stats_u16 and eld_pair_level_stats_workspace_bytes were added the same way (exact error-versus-signal sums of an
  * estimate against a reference frame): two new symbols, no existing call changed.
  * Still 8: eld_burst_stack_u16 and eld_burst_stack_workspace_bytes were added the same way (robust mean and photon-transfer sums of a burst of
- * a static scene): two new symbols, no existing call changed. */
+ * a static scene): two new symbols, no existing call changed.
+ * Still 8: eld_burst_luma_pyramid_elems, eld_burst_luma_pyramid_u16, eld_burst_align_workspace_bytes, eld_burst_align_u16,
+ * eld_burst_stack_aligned_workspace_bytes and eld_burst_stack_aligned_u16 were added the same way (registration of a hand-held burst and the
+ * stack through its displacement field): six new symbols, no existing call changed. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -641,6 +644,47 @@ size_t eld_burst_stack_workspace_bytes(int N, int Hm, int Wm);
 int eld_burst_stack_u16(const uint16_t* frames, int N, int Hm, int Wm, int p, const int* group, int G, const int32_t* black, int white,
                         const uint32_t* bitmap, int k2q, int min_dev, uint16_t* mean, uint8_t* kept, int64_t* ptc, void* ws, size_t ws_bytes,
                         void* stream);
+
+/* ---- aligning a hand-held burst: tile motion search, then the stack through the field (csrc/align.hip, eld_amd/burst.py) ------
+ * frames [N,Hm,Wm] uint16, 2 <= N <= 256, Hm * Wm < 2^31; p the CFA period (2 or 6); frame `ref` is the reference.  All arithmetic is integer;
+ * tests/align_ref.py restates every line below in NumPy.  T = 16 (tile side), R = 4 (search radius per level).
+ *   luma      Hl = Hm / p, Wl = Wm / p (floor; rows and columns beyond p Hl, p Wl do not enter);
+ *             L0[i][Y][X] = (sum of the p p codes of cell (Y, X) of frame i + p p / 2) / (p p), uint16.  Black levels are not subtracted.
+ *   pyramid   level l + 1 has sides (h + 1) / 2, (w + 1) / 2 and L[l+1][Y][X] = (a + b + c + d + 2) >> 2 over the 2 x 2 block at (2Y, 2X) of
+ *             level l, coordinates clamped to that level's last row and column.  `levels` counts the levels, the finest included: 1..4, and
+ *             every level has both sides >= T (so Hl, Wl >= T), else ELD_EINVAL.
+ *   tiles     a level with sides (h, w) has TY = ceil(h / T) by TX = ceil(w / T) tiles; tile (ty, tx) has origin y0 = min(ty T, h - T),
+ *             x0 = min(tx T, w - T): the last tile of a row or column is a whole tile shifted back.
+ *   search    coarsest level first.  The start (sy, sx) is (0, 0) at the coarsest level and otherwise twice the displacement of the parent tile
+ *             (min(((y0 + T / 2) >> 1) / T, TY' - 1), the same in x) one level up.  The 81 candidates (sy + v, sx + u), v, u in [-R, R], are
+ *             ranked 0..80 by ascending (|v| + |u|, v, u).  cost = sum over the tile's 256 pixels of |L[ref][y][x] - L[i][cl(y + dy)][cl(x + dx)]|
+ *             with cl clamping to the level (cost < 2^24).  The winner minimises (cost << 7) | rank (< 2^31): ties fall to the smallest move.
+ *   outputs   disp [N][TY0][TX0][2] int16, (dy, dx) at level 0 in luma units (CFA periods), |dy|, |dx| <= 60; cost (may be NULL) [N][TY0][TX0]
+ *             uint32, the winner's cost.  Both are zero for frame ref.
+ * eld_burst_luma_pyramid_u16 writes the pyramid alone: out holds eld_burst_luma_pyramid_elems(...) uint16 (0: bad arguments), level by level
+ * from the finest, each level [N][h][w].  eld_burst_align_u16 runs the pyramid into its workspace and then one search launch per level.
+ * Workspace: eld_burst_align_workspace_bytes(...) bytes (0: bad arguments), 4-byte aligned; ELD_EWS when ws_bytes is smaller.  frames, out and disp
+ * 2-byte aligned, cost 4-byte. */
+size_t eld_burst_luma_pyramid_elems(int N, int Hm, int Wm, int p, int levels);
+int eld_burst_luma_pyramid_u16(const uint16_t* frames, int N, int Hm, int Wm, int p, int levels, uint16_t* out, void* stream);
+size_t eld_burst_align_workspace_bytes(int N, int Hm, int Wm, int p, int levels);
+int eld_burst_align_u16(const uint16_t* frames, int N, int Hm, int Wm, int p, int ref, int levels, int16_t* disp, uint32_t* cost, void* ws,
+                        size_t ws_bytes, void* stream);
+
+/* eld_burst_stack_u16 over the samples a displacement field points at.  disp [N][TY0][TX0][2] int16 as eld_burst_align_u16 writes it, TY0 =
+ * ceil((Hm / p) / T), TX0 = ceil((Wm / p) / T) (anything else: ELD_EINVAL; Hm / p, Wm / p >= T).  Site (y, x) belongs to tile
+ * (min((y / p) / T, TY0 - 1), min((x / p) / T, TX0 - 1)); its sample from frame i is frames[i][y + p dy][x + p dx], PRESENT iff that lies inside
+ * the frame.  Displacements are whole CFA periods: every sample is a raw code of the site's own colour, nothing is resampled.  With M present
+ * samples the rule, mean and kept of eld_burst_stack_u16 apply as written with N replaced by M (rejection needs M >= 4; M = 0 writes mean 0,
+ * kept 0).  present (may be NULL) [Hm][Wm] uint8 = M (256 as 0).  ptc: the eligible sites are those of eld_burst_stack_u16 with M == N besides.
+ * With an all-zero field mean, kept and ptc equal eld_burst_stack_u16's bit for bit.  A displacement outside [-60, 60] is ELD_EINVAL: the call
+ * checks the field on the device and waits for that one flag before the stack is launched (it synchronises the stream once).
+ * 32-bit loads when frames and mean are 4-byte aligned, kept and present 2-byte aligned and Wm is even (a shifted row is only 2 p bytes
+ * aligned: there is no 16-byte path), 2-byte loads otherwise.  Workspace: eld_burst_stack_aligned_workspace_bytes bytes, 4-byte aligned. */
+size_t eld_burst_stack_aligned_workspace_bytes(int N, int Hm, int Wm);
+int eld_burst_stack_aligned_u16(const uint16_t* frames, int N, int Hm, int Wm, int p, const int* group, int G, const int32_t* black, int white,
+                                const uint32_t* bitmap, int k2q, int min_dev, const int16_t* disp, int TY0, int TX0, uint16_t* mean, uint8_t* kept,
+                                uint8_t* present, int64_t* ptc, void* ws, size_t ws_bytes, void* stream);
 
 /* Dev tool (tools/conv_phase_profile.py; a no-op unless built with -DELD_DEV_TOOLS=1): device buffer of 8 x 4 x 128 x 6 uint64 that conv_x3_kernel fills with s_memtime
  * stamps of its stage phases (first 8 workgroups, first 128 stages); NULL switches it off (default). */
