@@ -36,6 +36,7 @@ import sys
 import numpy as np
 
 from . import _lib as L
+from . import mosaic as M
 
 NB = L.PAIRSTATS_BINS
 MAX_FRAMES = 256
@@ -203,7 +204,6 @@ def align_burst(frames, cfa='bayer', ref=0, levels=None):
     (default: as many as the frame allows, at most 4; each level doubles the reach: 4, 12, 28, 60 CFA periods).  -> BurstAlignment.
     Translation per tile in whole CFA periods; no rotation model, no exposure compensation.  Bad arguments raise ValueError before any
     device work."""
-    from . import calibrate as CAL
     p = _period(cfa)
     N, Hm, Wm = _check_burst(frames, cfa)
     ref = _check_ref(ref, N)
@@ -211,7 +211,7 @@ def align_burst(frames, cfa='bayer', ref=0, levels=None):
     TY, TX = _tile_grid(Hm, Wm, p)
     import torch
     lib = L.lib()
-    u = CAL._device_u16(frames)
+    u = M.device_u16(frames)
     with torch.cuda.device(u.device):
         disp = torch.empty((N, TY, TX, 2), dtype=torch.int16, device=u.device)
         cost = torch.empty((N, TY, TX), dtype=torch.int32, device=u.device)
@@ -243,7 +243,6 @@ def stack_burst(frames, cfa='bayer', raw_pattern=None, black_level=None, white_l
     as given.  An aligned stack takes each site's samples through the field, reports in `present` how many lay inside the frame, applies
     the rule over those, and counts only sites with all N present in the photon-transfer sums.
     Bad arguments raise ValueError before any device work."""
-    from . import calibrate as CAL
     from .evaluate import _cells, _white
     p, group, G, black = _cells(cfa, raw_pattern, black_level)
     white = _white(white_level)
@@ -259,7 +258,7 @@ def stack_burst(frames, cfa='bayer', raw_pattern=None, black_level=None, white_l
         align_levels(Hm, Wm, p)
     import torch
     lib = L.lib()
-    u = CAL._device_u16(frames)
+    u = M.device_u16(frames)
     if align is not None and align is not False:
         if align is True:
             align = align_burst(u, cfa, 0)

@@ -25,187 +25,26 @@ import sys
 import numpy as np
 
 from . import _lib as L
+from .defects import as_defect_map, check_defects, find_defects
+from .mosaic import (CODE_COLOUR, XT_PERIOD, bayer_pattern, black_levels, cell_counts, check_cfa, check_mosaics,  # noqa: F401 (re-exported)
+                     check_sessions as _check_sessions, device_u16, shape_of, workspace, xtrans_pattern)
 
 DEFAULT_LAMBDAS = np.linspace(-1.0, 1.0, 141)     # scipy.stats.ppcc_plot(x, -1, 1, N=141): every shipped G_shape lies on it
 PROFILE = 'Profile-1'
 SIGMA_KEYS = ('G_scale', 'R_scale', 'g_scale')
 
 
-# ---- argument checks (host only: they run before any device work) ---------------------------------------------------------------
-def _pattern(raw_pattern):
-    p = np.asarray(raw_pattern).reshape(-1)
-    if p.size != 4 or sorted(int(v) for v in p) != [0, 1, 2, 3] or not np.all(p == np.round(p)):
-        raise ValueError('raw_pattern must be a 2x2 permutation of 0..3, got %r' % (np.asarray(raw_pattern).tolist(),))
-    return p.astype(np.int64).reshape(2, 2)
-
-
-def _black(black_level):
-    b = np.asarray(black_level, dtype=np.float64).reshape(-1)
-    if b.size != 4:
-        raise ValueError('black_level must hold 4 values (black_level_per_channel), got %d' % b.size)
-    return b
-
-
-XT_PERIOD = 6
-CODE_COLOUR = np.array([0, 1, 2, 1])               # rawpy colour code (R, G, B, G2) -> colour class R 0, G 1, B 2
-
-
-def _xpattern(raw_pattern):
-    """rawpy's 6x6 X-Trans raw_pattern (0 = R, 2 = B, 1 and 3 = G) with 8 R, 20 G and 8 B -> int64 (6,6)."""
-    p = np.asarray(raw_pattern)
-    if p.shape != (XT_PERIOD, XT_PERIOD) or not np.all(np.isin(p, [0, 1, 2, 3])):
-        raise ValueError('raw_pattern must be a 6x6 array of colour codes 0..3 for X-Trans, got %r' % (p.tolist(),))
-    p = p.astype(np.int64)
-    n = np.bincount(CODE_COLOUR[p].reshape(-1), minlength=3)
-    if tuple(int(v) for v in n) != (8, 20, 8):
-        raise ValueError('an X-Trans raw_pattern holds 8 R, 20 G and 8 B, got %d, %d, %d' % tuple(int(v) for v in n))
-    return p
-
-
-def _cfa(cfa):
-    if cfa not in ('bayer', 'xtrans'):
-        raise ValueError("cfa must be 'bayer' or 'xtrans', got %r" % (cfa,))
-    return cfa
-
-
-def cell_counts(Hm, Wm, p=XT_PERIOD):
-    """(p,p) int64: pixels of an Hm x Wm mosaic in cell (r, c) = {(y, x): y % p == r, x % p == c}."""
-    nr = np.array([(Hm - r + p - 1) // p for r in range(p)], np.int64)
-    nc = np.array([(Wm - c + p - 1) // p for c in range(p)], np.int64)
-    return np.outer(nr, nc)
-
-
-def _shape(x):
-    return tuple(int(s) for s in x.shape)
-
-
-def _check_mosaics(x, ndim, what, cfa='bayer'):
-    s = _shape(x)
-    if len(s) != ndim:
-        raise ValueError('%s: expected %d dimensions, got shape %s' % (what, ndim, s))
-    if ndim == 4 and s[1] != 2:
-        raise ValueError('%s: flat pairs must have shape (P, 2, Hm, Wm), got %s' % (what, s))
-    Hm, Wm = s[-2:]
-    if cfa == 'xtrans':
-        if Wm % 2 or Hm < XT_PERIOD or Wm < XT_PERIOD:
-            raise ValueError('%s: X-Trans mosaics need an even width and both sides >= 6, got %dx%d' % (what, Hm, Wm))
-    elif Hm % 2 or Wm % 2 or Hm == 0 or Wm == 0:
-        raise ValueError('%s: mosaic sides must be even and non-zero, got %dx%d' % (what, Hm, Wm))
-    if isinstance(x, np.ndarray):
-        if x.dtype != np.uint16:
-            raise ValueError('%s: uint16 mosaics expected, got %s' % (what, x.dtype))
-    else:
-        import torch
-        if not (x.is_cuda and x.dtype in (torch.int16, torch.uint16)):
-            raise ValueError('%s: a tensor must be CUDA int16/uint16 codes, got %s on %s' % (what, x.dtype, x.device))
-    return s
-
-
-def _device_u16(x):
-    """ndarray uint16 or CUDA int16/uint16 tensor -> contiguous CUDA tensor of the same bits, 4-byte aligned (the kernels read a row
-    as 32-bit words: a view starting at an odd element is copied)."""
-    import torch
-    if isinstance(x, np.ndarray):
-        return torch.from_numpy(np.ascontiguousarray(x).view(np.int16)).cuda()
-    x = x.contiguous()
-    return x.clone() if x.data_ptr() % 4 else x
-
-
-def _ws(nbytes, device):
-    import torch
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-
-
-def _c_pattern(p):
-    return (ctypes.c_int * 4)(*[int(v) for v in p.reshape(-1)])
-
-
 # ---- host derivations from the exact sums ------------------------------------------------------------------------------------
-def bias_stats_from_sums(chan_sums, row_sums, raw_pattern, black_level, Hm, Wm):
-    """Host half of bias_frame_stats: per frame colour bias cb_c (F,4), row offsets rho_y (F,Hm), the g_scale and R_scale samples (F,)
-    (DESIGN.md "Calibration"), float64, from chan_sums int64 (F,4,2) = (sum u, sum u^2) and row_sums int64 (F,Hm,2) = sum u over the
-    even / odd columns."""
-    pat, black = _pattern(raw_pattern), _black(black_level)
-    chan_sums, row_sums = np.asarray(chan_sums), np.asarray(row_sums)
-    F = chan_sums.shape[0]
-    n, nc = Hm * Wm, Hm * Wm // 4
-    mean_u = chan_sums[:, :, 0].astype(np.float64) / nc                  # black_c + cb_c
-    cb = mean_u - black[None, :]
-    se2 = np.zeros(F)                                                     # sum of e^2 = sum_c (Q_c - S_c^2 / n_c), exact numerator
-    for f in range(F):
-        se2[f] = sum(float(nc * int(chan_sums[f, c, 1]) - int(chan_sums[f, c, 0]) ** 2) / nc for c in range(4))
-    par = np.arange(Hm) & 1                                               # channels of row y: pat[y&1][0], pat[y&1][1]
-    mrow = 0.5 * (mean_u[:, pat[par, 0]] + mean_u[:, pat[par, 1]])        # (F,Hm)
-    rho = (row_sums[:, :, 0] + row_sums[:, :, 1]).astype(np.float64) / Wm - mrow
+# Each takes the counts of the unflagged sites of a defect map (the *_masked names) or counts every site (the plain names: the same call
+# without counts).  The flat derivations are one expression either way.  The bias derivations share the colour bias and sum e^2 but end in
+# two tails, because the row offset of a full row, (sum over the row) / Wm - mean level, and of a masked one, sum of deviations / n_y, are
+# different float64 expressions: with every site counted the plain tail runs, whatever the caller passed.
+def _plain_tail(se2, rho, n, Wm):
+    """g_scale, R_scale from sum e^2 (F,) and the row offsets (F,Hm) of full rows: the read noise averaged into a row is (sum t^2 / n) / Wm."""
     st2 = se2 - Wm * np.sum(rho * rho, axis=1)                            # sum t^2, t = e - rho_y
-    g_scale = np.sqrt(se2 / n)
-    R_scale = np.sqrt(np.maximum(0.0, np.mean(rho * rho, axis=1) - (st2 / n) / Wm))
-    return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
+    return np.sqrt(se2 / n), np.sqrt(np.maximum(0.0, np.mean(rho * rho, axis=1) - (st2 / n) / Wm))
 
 
-def xtrans_bias_stats_from_cell_sums(cell_sums, row_sums, raw_pattern, black_level, Hm, Wm):
-    """X-Trans host half of bias_frame_stats, from the exact cell sums: cell_sums int64 (F,6,6,2) = (sum u, sum u^2) per cell, row_sums
-    int64 (F,Hm,6) = sum u per row and column class.  Returns color_bias (F,3) (R, G, B: the mean of u - black_code over the colour's
-    pixels), row_offset (F,Hm) (the row means of e = u - black_code - color_bias), g_scale and R_scale (F,), as the Bayer estimators."""
-    pat, black = _xpattern(raw_pattern), _black(black_level)
-    cs, rs = np.asarray(cell_sums).reshape(-1, XT_PERIOD, XT_PERIOD, 2), np.asarray(row_sums)
-    F = cs.shape[0]
-    ncell = cell_counts(Hm, Wm)
-    bcell, col = black[pat], CODE_COLOUR[pat]                             # (6,6) black level and colour of each cell
-    n = Hm * Wm
-    S = cs[..., 0].astype(np.float64)                                     # < 2^53: exact
-    cb = np.stack([np.sum((S - ncell * bcell)[:, col == k], axis=1) / ncell[col == k].sum() for k in range(3)], axis=1)
-    se2 = np.zeros(F)                     # sum e^2 = sum over cells of (Q - S^2/n) [exact numerator] + n (S/n - black - cb)^2
-    for f in range(F):
-        for r in range(XT_PERIOD):
-            for c in range(XT_PERIOD):
-                m, s1, q = int(ncell[r, c]), int(cs[f, r, c, 0]), int(cs[f, r, c, 1])
-                se2[f] += float(m * q - s1 * s1) / m + m * (s1 / m - bcell[r, c] - cb[f, col[r, c]]) ** 2
-    ncol = cell_counts(1, Wm)[0]                                          # pixels per column class in one row
-    off = (bcell[None, :, :] + cb[:, col]) * ncol[None, None, :]          # (F,6,6): sum over a row of class r of black + cb, per column class
-    rho = (rs.sum(axis=2).astype(np.float64) - off.sum(axis=2)[:, np.arange(Hm) % XT_PERIOD]) / Wm
-    st2 = se2 - Wm * np.sum(rho * rho, axis=1)
-    g_scale = np.sqrt(se2 / n)
-    R_scale = np.sqrt(np.maximum(0.0, np.mean(rho * rho, axis=1) - (st2 / n) / Wm))
-    return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
-
-
-def xtrans_flat_stats_from_cell_sums(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm):
-    """X-Trans host half of flat_pair_stats: sums int64 (P,6,6,4) per cell -> mu, var (P,3) float64 and usable (P,3) bool, one
-    photon-transfer point per colour and pair (black = the mean black level of the colour's pixels)."""
-    pat, black = _xpattern(raw_pattern), _black(black_level)
-    sums = np.asarray(sums).reshape(-1, XT_PERIOD, XT_PERIOD, 4)
-    P = sums.shape[0]
-    cbm = np.asarray(color_bias, np.float64).reshape(3)
-    ncell = cell_counts(Hm, Wm)
-    bcell, col = black[pat], CODE_COLOUR[pat]
-    mu, var, usable = np.zeros((P, 3)), np.zeros((P, 3)), np.zeros((P, 3), bool)
-    for k in range(3):
-        m = col == k
-        nk = int(ncell[m].sum())
-        bbar = float(np.sum(ncell[m] * bcell[m])) / nk
-        for p in range(P):
-            sab, d1, d2 = (sum(int(v) for v in sums[p][m][:, j]) for j in range(3))
-            mu[p, k] = sab / (2 * nk) - bbar - cbm[k]
-            var[p, k] = float(nk * d2 - d1 * d1) / (nk * nk) / 2.0
-            usable[p, k] = int(sums[p][m][:, 3].sum()) == 0 and mu[p, k] > 0 and mu[p, k] <= 0.8 * (float(white_level) - bbar)
-    return {'mu': mu, 'var': var, 'usable': usable}
-
-
-def flat_stats_from_sums(sums, black_level, white_level, color_bias, Hm, Wm):
-    """Host half of flat_pair_stats: sums int64 (P,4,4) -> mu, var (P,4) float64 and usable (P,4) bool."""
-    black = _black(black_level)
-    sums = np.asarray(sums)
-    P = sums.shape[0]
-    cbm = np.asarray(color_bias, np.float64).reshape(4)
-    nc = Hm * Wm // 4
-    mu = sums[:, :, 0].astype(np.float64) / (2 * nc) - black[None, :] - cbm[None, :]
-    var = np.array([[float(nc * int(sums[p, c, 2]) - int(sums[p, c, 1]) ** 2) / (nc * nc) / 2.0 for c in range(4)] for p in range(P)])
-    usable = (sums[:, :, 3] == 0) & (mu > 0) & (mu <= 0.8 * (float(white_level) - black[None, :]))
-    return {'mu': mu, 'var': var.reshape(P, 4), 'usable': usable}
-
-
-# ---- the same derivations over the unflagged sites of a defect map (count-aware) -------------------------------------------------------
 def _masked_tail(se2, n_row, dev_row, n):
     """rho, g_scale, R_scale from sum e^2 (F,), per-row counts (Hm,), per-row sums of e (F,Hm) and the site count: the row offset is the
     mean of e over the row's unflagged sites, and the read noise averaged into it is (sum t^2 / n) / n_y, row by row."""
@@ -218,45 +57,64 @@ def _masked_tail(se2, n_row, dev_row, n):
     return rho, g_scale, R_scale
 
 
+def bias_stats_from_sums(chan_sums, row_sums, raw_pattern, black_level, Hm, Wm):
+    """Host half of bias_frame_stats: per frame colour bias cb_c (F,4), row offsets rho_y (F,Hm), the g_scale and R_scale samples (F,)
+    (DESIGN.md "Calibration"), float64, from chan_sums int64 (F,4,2) = (sum u, sum u^2) and row_sums int64 (F,Hm,2) = sum u over the
+    even / odd columns."""
+    return bias_stats_from_sums_masked(chan_sums, row_sums, raw_pattern, black_level, Hm, Wm)
+
+
 def bias_stats_from_sums_masked(chan_sums, row_sums, raw_pattern, black_level, Hm, Wm, chan_counts=None, row_counts=None):
     """bias_stats_from_sums over the unflagged sites only: chan_sums / row_sums are the sums over those sites, chan_counts (4,) and
     row_counts (Hm,2) (even / odd columns) their numbers.  Without counts (or with every site counted) it IS bias_stats_from_sums: the
-    same call, hence the same bits."""
-    pat, black = _pattern(raw_pattern), _black(black_level)
-    if chan_counts is None or (np.all(np.asarray(chan_counts) == Hm * Wm // 4) and np.all(np.asarray(row_counts) == Wm // 2)):
-        return bias_stats_from_sums(chan_sums, row_sums, pat, black, Hm, Wm)
+    same expressions, hence the same bits."""
+    pat, black = bayer_pattern(raw_pattern), black_levels(black_level)
+    full = chan_counts is None or (np.all(np.asarray(chan_counts) == Hm * Wm // 4) and np.all(np.asarray(row_counts) == Wm // 2))
     chan_sums, row_sums = np.asarray(chan_sums), np.asarray(row_sums)
-    nc, nr = np.asarray(chan_counts, np.int64).reshape(4), np.asarray(row_counts, np.int64).reshape(Hm, 2)
+    nc = np.full(4, Hm * Wm // 4, np.int64) if full else np.asarray(chan_counts, np.int64).reshape(4)
     if np.any(nc == 0):
         raise ValueError('channel %d has no unflagged site' % int(np.flatnonzero(nc == 0)[0]))
     F = chan_sums.shape[0]
-    mean_u = chan_sums[:, :, 0].astype(np.float64) / nc[None, :]
+    mean_u = chan_sums[:, :, 0].astype(np.float64) / nc[None, :]          # black_c + cb_c
     cb = mean_u - black[None, :]
-    se2 = np.zeros(F)
+    se2 = np.zeros(F)                                                     # sum of e^2 = sum_c (Q_c - S_c^2 / n_c), exact numerator
     for f in range(F):
         se2[f] = sum(float(int(nc[c]) * int(chan_sums[f, c, 1]) - int(chan_sums[f, c, 0]) ** 2) / int(nc[c]) for c in range(4))
-    par = np.arange(Hm) & 1
-    dev_row = (row_sums[:, :, 0] - nr[None, :, 0] * mean_u[:, pat[par, 0]]) + (row_sums[:, :, 1] - nr[None, :, 1] * mean_u[:, pat[par, 1]])
-    rho, g_scale, R_scale = _masked_tail(se2, nr.sum(axis=1), dev_row, int(nc.sum()))
+    par = np.arange(Hm) & 1                                               # channels of row y: pat[y&1][0], pat[y&1][1]
+    if full:
+        mrow = 0.5 * (mean_u[:, pat[par, 0]] + mean_u[:, pat[par, 1]])    # (F,Hm)
+        rho = (row_sums[:, :, 0] + row_sums[:, :, 1]).astype(np.float64) / Wm - mrow
+        g_scale, R_scale = _plain_tail(se2, rho, Hm * Wm, Wm)
+    else:
+        nr = np.asarray(row_counts, np.int64).reshape(Hm, 2)
+        dev_row = (row_sums[:, :, 0] - nr[None, :, 0] * mean_u[:, pat[par, 0]]) + (row_sums[:, :, 1] - nr[None, :, 1] * mean_u[:, pat[par, 1]])
+        rho, g_scale, R_scale = _masked_tail(se2, nr.sum(axis=1), dev_row, int(nc.sum()))
     return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
+
+
+def xtrans_bias_stats_from_cell_sums(cell_sums, row_sums, raw_pattern, black_level, Hm, Wm):
+    """X-Trans host half of bias_frame_stats, from the exact cell sums: cell_sums int64 (F,6,6,2) = (sum u, sum u^2) per cell, row_sums
+    int64 (F,Hm,6) = sum u per row and column class.  Returns color_bias (F,3) (R, G, B: the mean of u - black_code over the colour's
+    pixels), row_offset (F,Hm) (the row means of e = u - black_code - color_bias), g_scale and R_scale (F,), as the Bayer estimators."""
+    return xtrans_bias_stats_from_cell_sums_masked(cell_sums, row_sums, raw_pattern, black_level, Hm, Wm)
 
 
 def xtrans_bias_stats_from_cell_sums_masked(cell_sums, row_sums, raw_pattern, black_level, Hm, Wm, cell_n=None, row_n=None):
     """xtrans_bias_stats_from_cell_sums over the unflagged sites only: cell_n (6,6) and row_n (Hm,6) count them per cell and per row and
     column class.  Without counts (or with every site counted) it IS xtrans_bias_stats_from_cell_sums."""
-    pat, black = _xpattern(raw_pattern), _black(black_level)
-    if cell_n is None or (np.array_equal(cell_n, cell_counts(Hm, Wm)) and np.array_equal(row_n, np.broadcast_to(cell_counts(1, Wm)[0], (Hm, XT_PERIOD)))):
-        return xtrans_bias_stats_from_cell_sums(cell_sums, row_sums, pat, black, Hm, Wm)
+    pat, black = xtrans_pattern(raw_pattern), black_levels(black_level)
+    ncol = cell_counts(1, Wm)[0]                                          # pixels per column class in one row
+    full = cell_n is None or (np.array_equal(cell_n, cell_counts(Hm, Wm)) and np.array_equal(row_n, np.broadcast_to(ncol, (Hm, XT_PERIOD))))
     cs, rs = np.asarray(cell_sums).reshape(-1, XT_PERIOD, XT_PERIOD, 2), np.asarray(row_sums)
-    ncell, nrow = np.asarray(cell_n, np.int64).reshape(XT_PERIOD, XT_PERIOD), np.asarray(row_n, np.int64).reshape(Hm, XT_PERIOD)
+    ncell = cell_counts(Hm, Wm) if full else np.asarray(cell_n, np.int64).reshape(XT_PERIOD, XT_PERIOD)
     F = cs.shape[0]
-    bcell, col = black[pat], CODE_COLOUR[pat]
+    bcell, col = black[pat], CODE_COLOUR[pat]                             # (6,6) black level and colour of each cell
     for k in range(3):
         if ncell[col == k].sum() == 0:
             raise ValueError('colour %d has no unflagged site' % k)
-    S = cs[..., 0].astype(np.float64)
+    S = cs[..., 0].astype(np.float64)                                     # < 2^53: exact
     cb = np.stack([np.sum((S - ncell * bcell)[:, col == k], axis=1) / ncell[col == k].sum() for k in range(3)], axis=1)
-    se2 = np.zeros(F)
+    se2 = np.zeros(F)                     # sum e^2 = sum over cells of (Q - S^2/n) [exact numerator] + n (S/n - black - cb)^2
     for f in range(F):
         for r in range(XT_PERIOD):
             for c in range(XT_PERIOD):
@@ -265,17 +123,26 @@ def xtrans_bias_stats_from_cell_sums_masked(cell_sums, row_sums, raw_pattern, bl
                     se2[f] += float(m * q - s1 * s1) / m + m * (s1 / m - bcell[r, c] - cb[f, col[r, c]]) ** 2
     ry = np.arange(Hm) % XT_PERIOD
     level = bcell[None, :, :] + cb[:, col]                                # (F,6,6): black + cb of each cell
-    dev_row = (rs.astype(np.float64) - nrow[None, :, :] * level[:, ry, :]).sum(axis=2)
-    rho, g_scale, R_scale = _masked_tail(se2, nrow.sum(axis=1), dev_row, int(ncell.sum()))
+    if full:
+        off = level * ncol[None, None, :]                                 # sum over a row of class r of black + cb, per column class
+        rho = (rs.sum(axis=2).astype(np.float64) - off.sum(axis=2)[:, ry]) / Wm
+        g_scale, R_scale = _plain_tail(se2, rho, Hm * Wm, Wm)
+    else:
+        nrow = np.asarray(row_n, np.int64).reshape(Hm, XT_PERIOD)
+        dev_row = (rs.astype(np.float64) - nrow[None, :, :] * level[:, ry, :]).sum(axis=2)
+        rho, g_scale, R_scale = _masked_tail(se2, nrow.sum(axis=1), dev_row, int(ncell.sum()))
     return {'color_bias': cb, 'row_offset': rho, 'g_scale': g_scale, 'R_scale': R_scale}
 
 
+def flat_stats_from_sums(sums, black_level, white_level, color_bias, Hm, Wm):
+    """Host half of flat_pair_stats: sums int64 (P,4,4) -> mu, var (P,4) float64 and usable (P,4) bool."""
+    return flat_stats_from_sums_masked(sums, black_level, white_level, color_bias, Hm, Wm)
+
+
 def flat_stats_from_sums_masked(sums, black_level, white_level, color_bias, Hm, Wm, chan_counts=None):
-    """flat_stats_from_sums over the unflagged sites only (chan_counts (4,) of them per channel); without counts it IS flat_stats_from_sums."""
-    if chan_counts is None or np.all(np.asarray(chan_counts) == Hm * Wm // 4):
-        return flat_stats_from_sums(sums, black_level, white_level, color_bias, Hm, Wm)
-    black, sums = _black(black_level), np.asarray(sums)
-    nc = np.asarray(chan_counts, np.int64).reshape(4)
+    """flat_stats_from_sums over the unflagged sites only (chan_counts (4,) of them per channel; default: every site)."""
+    black, sums = black_levels(black_level), np.asarray(sums)
+    nc = np.full(4, Hm * Wm // 4, np.int64) if chan_counts is None else np.asarray(chan_counts, np.int64).reshape(4)
     if np.any(nc == 0):
         raise ValueError('channel %d has no unflagged site' % int(np.flatnonzero(nc == 0)[0]))
     P = sums.shape[0]
@@ -286,15 +153,19 @@ def flat_stats_from_sums_masked(sums, black_level, white_level, color_bias, Hm, 
     return {'mu': mu, 'var': var.reshape(P, 4), 'usable': usable}
 
 
+def xtrans_flat_stats_from_cell_sums(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm):
+    """X-Trans host half of flat_pair_stats: sums int64 (P,6,6,4) per cell -> mu, var (P,3) float64 and usable (P,3) bool, one
+    photon-transfer point per colour and pair (black = the mean black level of the colour's pixels)."""
+    return xtrans_flat_stats_from_cell_sums_masked(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm)
+
+
 def xtrans_flat_stats_from_cell_sums_masked(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm, cell_n=None):
-    """xtrans_flat_stats_from_cell_sums over the unflagged sites only (cell_n (6,6) of them per cell); without counts it IS that function."""
-    if cell_n is None or np.array_equal(cell_n, cell_counts(Hm, Wm)):
-        return xtrans_flat_stats_from_cell_sums(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm)
-    pat, black = _xpattern(raw_pattern), _black(black_level)
+    """xtrans_flat_stats_from_cell_sums over the unflagged sites only (cell_n (6,6) of them per cell; default: every site)."""
+    pat, black = xtrans_pattern(raw_pattern), black_levels(black_level)
     sums = np.asarray(sums).reshape(-1, XT_PERIOD, XT_PERIOD, 4)
     P = sums.shape[0]
     cbm = np.asarray(color_bias, np.float64).reshape(3)
-    ncell = np.asarray(cell_n, np.int64).reshape(XT_PERIOD, XT_PERIOD)
+    ncell = cell_counts(Hm, Wm) if cell_n is None else np.asarray(cell_n, np.int64).reshape(XT_PERIOD, XT_PERIOD)
     bcell, col = black[pat], CODE_COLOUR[pat]
     mu, var, usable = np.zeros((P, 3)), np.zeros((P, 3)), np.zeros((P, 3), bool)
     for k in range(3):
@@ -333,6 +204,68 @@ def _flat_terms(a, b, white):
     return np.stack([(a + b).sum(axis=1), (a - b).sum(axis=1), ((a - b) ** 2).sum(axis=1), ((a >= white) | (b >= white)).sum(axis=1)], axis=1)
 
 
+# ---- the device passes, for a pattern of period p (2: Bayer, 6: X-Trans) -------------------------------------------------------------
+def _cell_sums(u, p, defects):
+    """CUDA codes (F,Hm,Wm) -> host int64 cell_sums (F,p,p,2) = (sum u, sum u^2) per cell and row_sums (F,Hm,p) = sum u per row and column
+    class; with a defect map the flagged sites' contributions are taken out (exactly, on the host) and (cell_n, row_n), the numbers of
+    unflagged sites, follow -- (None, None) otherwise."""
+    import torch
+    F, Hm, Wm = shape_of(u)
+    cs = torch.empty((F, p, p, 2), dtype=torch.int64, device=u.device)
+    rs = torch.empty((F, Hm, p), dtype=torch.int64, device=u.device)
+    ws = workspace(L.lib().eld_calib_cell_stats_workspace_bytes(F, Hm, p), u.device)
+    L.check(L.lib().eld_calib_cell_stats(L.dptr(u), F, Hm, Wm, p, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), L.cur_stream()),
+            'eld_calib_cell_stats')
+    cs, rs = cs.cpu().numpy(), rs.cpu().numpy()
+    if defects is None or not defects.count:
+        return cs, rs, None, None
+    g, ys, xs = _gather_sites(u, defects), defects.sites[:, 0], defects.sites[:, 1]
+    for f in range(F):
+        np.subtract.at(cs[f, :, :, 0], (ys % p, xs % p), g[f])
+        np.subtract.at(cs[f, :, :, 1], (ys % p, xs % p), g[f] ** 2)
+        np.subtract.at(rs[f], (ys, xs % p), g[f])
+    return (cs, rs) + _site_counts(defects, Hm, Wm, p)
+
+
+def _cell_flat_sums(ab, p, white_level, defects):
+    """CUDA flat pairs (P,2,Hm,Wm) -> host int64 sums (P,p,p,4) per cell (sum(a+b), sum(a-b), sum((a-b)^2), saturated pixels) and cell_n
+    (p,p), the unflagged sites of the defect map that were counted (None without one)."""
+    import torch
+    P, _, Hm, Wm = shape_of(ab)
+    out = torch.empty((P, p, p, 4), dtype=torch.int64, device=ab.device)
+    ws = workspace(L.lib().eld_calib_cell_flat_stats_workspace_bytes(P, Hm, p), ab.device)
+    L.check(L.lib().eld_calib_cell_flat_stats(L.dptr(ab), P, Hm, Wm, p, int(white_level), L.dptr(out), L.dptr(ws), ws.numel(),
+                                              L.cur_stream()), 'eld_calib_cell_flat_stats')
+    sums = out.cpu().numpy()
+    if defects is None or not defects.count:
+        return sums, None
+    g, ys, xs = _gather_sites(ab, defects), defects.sites[:, 0], defects.sites[:, 1]
+    for r in range(p):
+        for c in range(p):
+            m = (ys % p == r) & (xs % p == c)
+            sums[:, r, c] -= _flat_terms(g[:, 0][:, m], g[:, 1][:, m], int(white_level))
+    return sums, _site_counts(defects, Hm, Wm, p)[0]
+
+
+def _cell_residual(u, p, black_cell, bias_cell, row_offset, defects):
+    """CUDA float32 (F, Hm*Wm - K) = float32(((u - black_cell[k]) - bias_cell[f][k]) - row_offset[f][y]) at every unflagged site, k the
+    site's cell: black_cell (p,p) and bias_cell (F,p*p) are host float64 arrays."""
+    import torch
+    F, Hm, Wm = shape_of(u)
+    t = torch.empty((F, Hm * Wm), dtype=torch.float32, device=u.device)
+    cbd = torch.from_numpy(np.ascontiguousarray(bias_cell)).to(u.device)
+    rhod = torch.from_numpy(np.ascontiguousarray(row_offset)).to(u.device)
+    L.check(L.lib().eld_calib_cell_residual(L.dptr(u), F, Hm, Wm, p, (ctypes.c_double * (p * p))(*black_cell.reshape(-1).tolist()),
+                                            L.dptr(cbd), L.dptr(rhod), L.dptr(t), L.cur_stream()), 'eld_calib_cell_residual')
+    return _drop_flagged(t, defects)
+
+
+def _to_channels(cells, pat, axis=1):
+    """Per-cell values of a period-2 mosaic, (..., 2, 2, ...) from `axis`, in Bayer channel order (..., 4, ...): channel pat[r][c] is cell (r, c)."""
+    s = cells.shape
+    return np.take(cells.reshape(s[:axis] + (4,) + s[axis + 2:]), np.argsort(pat.reshape(-1)), axis=axis)
+
+
 def _drop_flagged(t, defects):
     """Residuals (F, Hm*Wm) -> (F, Hm*Wm - K): the flagged sites' entries removed (row-major order kept)."""
     if defects is None or not defects.count:
@@ -340,24 +273,6 @@ def _drop_flagged(t, defects):
     import torch
     keep = torch.from_numpy(~defects.mask.reshape(-1)).to(t.device)
     return t[:, keep].contiguous()
-
-
-def _check_defects(defects, cfa, shape=None, raw_pattern=None):
-    """The map must be for this CFA, these sides and -- X-Trans -- this pattern: its neighbourhoods are those of the colours of the 6x6
-    cell it was built for.  A Bayer map's neighbourhoods are the sites at offsets of +-2 whatever the 2x2 permutation, so a Bayer map
-    made under another raw_pattern flags and repairs the same sites: its raw_pattern is not compared."""
-    if defects is None or (isinstance(defects, str) and defects == 'auto'):
-        return defects
-    from .defects import DefectMap
-    if not isinstance(defects, DefectMap):
-        raise ValueError("defects must be a DefectMap, 'auto' or None, got %r" % (type(defects).__name__,))
-    if cfa == 'xtrans' and defects.cfa == 'xtrans' and raw_pattern is not None and not np.array_equal(CODE_COLOUR[_xpattern(raw_pattern)], defects.classes):
-        raise ValueError('calibration: the defect map was built for another X-Trans raw_pattern (the colours of its 6x6 cell differ)')
-    if shape is not None:
-        defects.check_frames(shape, cfa, 'calibration')
-    elif defects.cfa != cfa:
-        raise ValueError('calibration: the defect map is for cfa=%r, the frames are %r' % (defects.cfa, cfa))
-    return defects
 
 
 def ptc_gain(mu, var, usable, what='session'):
@@ -408,37 +323,17 @@ def bias_frame_stats(bias, raw_pattern, black_level, residual=False, defects=Non
     defects (a DefectMap): every statistic is over its unflagged sites only -- the sums have the flagged sites' contributions taken out
     (exactly, on the host), 'chan_counts' (4,) and 'row_counts' (Hm,2) count what is left, and 't' is (F, Hm*Wm - K): the flagged
     entries are dropped."""
-    import torch
-    pat, black = _pattern(raw_pattern), _black(black_level)
-    F, Hm, Wm = _check_mosaics(bias, 3, 'bias')
-    defects = _check_defects(defects, 'bayer', (Hm, Wm))
-    u = _device_u16(bias)
-    dev = u.device
-    cs = torch.empty((F, 4, 2), dtype=torch.int64, device=dev)
-    rs = torch.empty((F, Hm, 2), dtype=torch.int64, device=dev)
-    cp = _c_pattern(pat)
-    ws = _ws(L.lib().eld_calib_bias_stats_workspace_bytes(F, Hm), dev)
-    L.check(L.lib().eld_calib_bias_stats(L.dptr(u), F, Hm, Wm, cp, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), L.cur_stream()),
-            'eld_calib_bias_stats')
-    out = {'chan_sums': cs.cpu().numpy(), 'row_sums': rs.cpu().numpy()}
-    if defects is not None and defects.count:
-        g, ys, xs = _gather_sites(u, defects), defects.sites[:, 0], defects.sites[:, 1]
-        ch = pat[ys & 1, xs & 1]
-        for c in range(4):
-            out['chan_sums'][:, c, 0] -= g[:, ch == c].sum(axis=1)
-            out['chan_sums'][:, c, 1] -= (g[:, ch == c] ** 2).sum(axis=1)
-        for f in range(F):
-            np.subtract.at(out['row_sums'][f], (ys, xs & 1), g[f])
-        cell_n, out['row_counts'] = _site_counts(defects, Hm, Wm, 2)
-        out['chan_counts'] = np.array([cell_n[pat == c][0] for c in range(4)], np.int64)
-    out.update(bias_stats_from_sums_masked(out['chan_sums'], out['row_sums'], pat, black, Hm, Wm, out.get('chan_counts'), out.get('row_counts')))
+    pat, black = bayer_pattern(raw_pattern), black_levels(black_level)
+    F, Hm, Wm = check_mosaics(bias, 3, 'bias')
+    defects = check_defects(defects, 'bayer', (Hm, Wm))
+    u = device_u16(bias)
+    cs, rs, cell_n, row_n = _cell_sums(u, 2, defects)
+    out = {'chan_sums': _to_channels(cs, pat), 'row_sums': rs}
+    if cell_n is not None:
+        out['row_counts'], out['chan_counts'] = row_n, _to_channels(cell_n, pat, axis=0)
+    out.update(bias_stats_from_sums_masked(out['chan_sums'], rs, pat, black, Hm, Wm, out.get('chan_counts'), row_n))
     if residual:
-        t = torch.empty((F, Hm * Wm), dtype=torch.float32, device=dev)
-        cbd = torch.from_numpy(np.ascontiguousarray(out['color_bias'])).to(dev)
-        rhod = torch.from_numpy(np.ascontiguousarray(out['row_offset'])).to(dev)
-        L.check(L.lib().eld_calib_bias_residual(L.dptr(u), F, Hm, Wm, cp, (ctypes.c_double * 4)(*black.tolist()), L.dptr(cbd), L.dptr(rhod),
-                                                L.dptr(t), L.cur_stream()), 'eld_calib_bias_residual')
-        out['t'] = _drop_flagged(t, defects)
+        out['t'] = _cell_residual(u, 2, black[pat], out['color_bias'][:, pat.reshape(-1)], out['row_offset'], defects)
     return out
 
 
@@ -451,10 +346,10 @@ def tukey_lambda_ppcc(t, lambdas=None, presorted=False):
     lam = np.asarray(DEFAULT_LAMBDAS if lambdas is None else lambdas, dtype=np.float64).reshape(-1)
     if lam.size == 0:
         raise ValueError('empty lambda grid')
-    one = len(_shape(t)) == 1
-    if len(_shape(t)) not in (1, 2):
-        raise ValueError('t must have shape (n,) or (F,n), got %s' % (_shape(t),))
-    n = _shape(t)[-1]
+    one = len(shape_of(t)) == 1
+    if len(shape_of(t)) not in (1, 2):
+        raise ValueError('t must have shape (n,) or (F,n), got %s' % (shape_of(t),))
+    n = shape_of(t)[-1]
     if n < 3:
         raise ValueError('PPCC needs n >= 3 samples, got %d' % n)
     if not isinstance(t, np.ndarray) and not t.is_cuda:
@@ -468,7 +363,7 @@ def tukey_lambda_ppcc(t, lambdas=None, presorted=False):
     lamd = torch.from_numpy(lam.astype(np.float32)).to(dev)
     sums = torch.empty((F, lam.size, 2), dtype=torch.float64, device=dev)
     tsums = torch.empty((F, 2), dtype=torch.float64, device=dev)
-    ws = _ws(L.lib().eld_calib_ppcc_workspace_bytes(F, n, lam.size), dev)
+    ws = workspace(L.lib().eld_calib_ppcc_workspace_bytes(F, n, lam.size), dev)
     L.check(L.lib().eld_calib_ppcc(L.dptr(x), F, n, L.dptr(lamd), lam.size, L.dptr(sums), L.dptr(tsums), L.dptr(ws), ws.numel(),
                                    L.cur_stream()), 'eld_calib_ppcc')
     s, ts = sums.cpu().numpy(), tsums.cpu().numpy()
@@ -488,84 +383,46 @@ def flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias, de
     """Flat pairs (P,2,Hm,Wm) uint16 -> dict: sums int64 (P,4,4) = per channel (sum(a+b), sum(a-b), sum((a-b)^2), saturated pixels),
     mu (P,4) = mean((a+b)/2) - black_c - color_bias_c, var (P,4) = var(a-b)/2, usable (P,4) bool (no saturated pixel and
     0 < mu <= 0.8 (white - black_c)).  color_bias: the session's mean colour bias (4,)."""
-    import torch
-    pat, black = _pattern(raw_pattern), _black(black_level)
-    P, _, Hm, Wm = _check_mosaics(flats, 4, 'flats')
-    defects = _check_defects(defects, 'bayer', (Hm, Wm))
+    pat, black = bayer_pattern(raw_pattern), black_levels(black_level)
+    P, _, Hm, Wm = check_mosaics(flats, 4, 'flats')
+    defects = check_defects(defects, 'bayer', (Hm, Wm))
     cbm = np.asarray(color_bias, np.float64).reshape(4)
-    ab = _device_u16(flats)
-    out = torch.empty((P, 4, 4), dtype=torch.int64, device=ab.device)
-    ws = _ws(L.lib().eld_calib_flat_stats_workspace_bytes(P, Hm), ab.device)
-    L.check(L.lib().eld_calib_flat_stats(L.dptr(ab), P, Hm, Wm, _c_pattern(pat), int(white_level), L.dptr(out), L.dptr(ws), ws.numel(),
-                                         L.cur_stream()), 'eld_calib_flat_stats')
-    res = {'sums': out.cpu().numpy()}
-    if defects is not None and defects.count:                 # the sums (and the saturation count) over the unflagged sites only
-        g, ch = _gather_sites(ab, defects), pat[defects.sites[:, 0] & 1, defects.sites[:, 1] & 1]
-        for c in range(4):
-            res['sums'][:, c] -= _flat_terms(g[:, 0][:, ch == c], g[:, 1][:, ch == c], int(white_level))
-        cell_n = _site_counts(defects, Hm, Wm, 2)[0]
-        res['chan_counts'] = np.array([cell_n[pat == c][0] for c in range(4)], np.int64)
+    sums, cell_n = _cell_flat_sums(device_u16(flats), 2, white_level, defects)   # the sums (and the saturation count) over the unflagged sites only
+    res = {'sums': _to_channels(sums, pat)}
+    if cell_n is not None:
+        res['chan_counts'] = _to_channels(cell_n, pat, axis=0)
     res.update(flat_stats_from_sums_masked(res['sums'], black, white_level, cbm, Hm, Wm, res.get('chan_counts')))
     return res
 
 
 def xtrans_bias_frame_stats(bias, raw_pattern, black_level, residual=False, defects=None):
     """X-Trans bias frames (F,Hm,Wm) uint16 -> dict: cell_sums int64 (F,6,6,2), row_sums int64 (F,Hm,6), color_bias (F,3), row_offset
-    (F,Hm), g_scale, R_scale (F,); with residual=True also 't' (CUDA float32 (F,Hm*Wm)) = float32(((u - black_code) - cb) - rho_y)."""
-    import torch
-    pat, black = _xpattern(raw_pattern), _black(black_level)
-    F, Hm, Wm = _check_mosaics(bias, 3, 'bias', 'xtrans')
-    defects = _check_defects(defects, 'xtrans', (Hm, Wm), raw_pattern)
-    u = _device_u16(bias)
-    dev = u.device
-    p = XT_PERIOD
-    cs = torch.empty((F, p, p, 2), dtype=torch.int64, device=dev)
-    rs = torch.empty((F, Hm, p), dtype=torch.int64, device=dev)
-    ws = _ws(L.lib().eld_calib_cell_stats_workspace_bytes(F, Hm, p), dev)
-    L.check(L.lib().eld_calib_cell_stats(L.dptr(u), F, Hm, Wm, p, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), L.cur_stream()),
-            'eld_calib_cell_stats')
-    out = {'cell_sums': cs.cpu().numpy(), 'row_sums': rs.cpu().numpy()}
-    if defects is not None and defects.count:                 # as bias_frame_stats: the flagged sites leave the sums, exactly
-        g, ys, xs = _gather_sites(u, defects), defects.sites[:, 0], defects.sites[:, 1]
-        for f in range(F):
-            np.subtract.at(out['cell_sums'][f, :, :, 0], (ys % p, xs % p), g[f])
-            np.subtract.at(out['cell_sums'][f, :, :, 1], (ys % p, xs % p), g[f] ** 2)
-            np.subtract.at(out['row_sums'][f], (ys, xs % p), g[f])
-        out['cell_counts'], out['row_counts'] = _site_counts(defects, Hm, Wm, p)
-    out.update(xtrans_bias_stats_from_cell_sums_masked(out['cell_sums'], out['row_sums'], pat, black, Hm, Wm, out.get('cell_counts'),
-                                                       out.get('row_counts')))
-    if residual:
-        t = torch.empty((F, Hm * Wm), dtype=torch.float32, device=dev)
-        cbc = np.ascontiguousarray(out['color_bias'][:, CODE_COLOUR[pat].reshape(-1)])          # (F,36) bias of each cell's colour
-        cbd = torch.from_numpy(cbc).to(dev)
-        rhod = torch.from_numpy(np.ascontiguousarray(out['row_offset'])).to(dev)
-        L.check(L.lib().eld_calib_cell_residual(L.dptr(u), F, Hm, Wm, p, (ctypes.c_double * (p * p))(*black[pat].reshape(-1).tolist()),
-                                                L.dptr(cbd), L.dptr(rhod), L.dptr(t), L.cur_stream()), 'eld_calib_cell_residual')
-        out['t'] = _drop_flagged(t, defects)
+    (F,Hm), g_scale, R_scale (F,); with residual=True also 't' (CUDA float32 (F,Hm*Wm)) = float32(((u - black_code) - cb) - rho_y).
+    defects: as bias_frame_stats, with 'cell_counts' (6,6) and 'row_counts' (Hm,6)."""
+    pat, black = xtrans_pattern(raw_pattern), black_levels(black_level)
+    F, Hm, Wm = check_mosaics(bias, 3, 'bias', 'xtrans')
+    defects = check_defects(defects, 'xtrans', (Hm, Wm), raw_pattern)
+    u = device_u16(bias)
+    cs, rs, cell_n, row_n = _cell_sums(u, XT_PERIOD, defects)
+    out = {'cell_sums': cs, 'row_sums': rs}
+    if cell_n is not None:
+        out['cell_counts'], out['row_counts'] = cell_n, row_n
+    out.update(xtrans_bias_stats_from_cell_sums_masked(cs, rs, pat, black, Hm, Wm, cell_n, row_n))
+    if residual:                                              # the colour bias of each cell's colour, (F,36)
+        out['t'] = _cell_residual(u, XT_PERIOD, black[pat], out['color_bias'][:, CODE_COLOUR[pat].reshape(-1)], out['row_offset'], defects)
     return out
 
 
 def xtrans_flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias, defects=None):
     """X-Trans flat pairs (P,2,Hm,Wm) uint16 -> dict: sums int64 (P,6,6,4) per cell, mu, var (P,3), usable (P,3) per colour.
     color_bias: the session's mean (R, G, B) bias."""
-    import torch
-    pat, black = _xpattern(raw_pattern), _black(black_level)
-    P, _, Hm, Wm = _check_mosaics(flats, 4, 'flats', 'xtrans')
-    defects = _check_defects(defects, 'xtrans', (Hm, Wm), raw_pattern)
-    ab = _device_u16(flats)
-    p = XT_PERIOD
-    out = torch.empty((P, p, p, 4), dtype=torch.int64, device=ab.device)
-    ws = _ws(L.lib().eld_calib_cell_flat_stats_workspace_bytes(P, Hm, p), ab.device)
-    L.check(L.lib().eld_calib_cell_flat_stats(L.dptr(ab), P, Hm, Wm, p, int(white_level), L.dptr(out), L.dptr(ws), ws.numel(),
-                                              L.cur_stream()), 'eld_calib_cell_flat_stats')
-    res = {'sums': out.cpu().numpy()}
-    if defects is not None and defects.count:
-        g, ys, xs = _gather_sites(ab, defects), defects.sites[:, 0], defects.sites[:, 1]
-        for r in range(p):
-            for c in range(p):
-                m = (ys % p == r) & (xs % p == c)
-                res['sums'][:, r, c] -= _flat_terms(g[:, 0][:, m], g[:, 1][:, m], int(white_level))
-        res['cell_counts'] = _site_counts(defects, Hm, Wm, p)[0]
+    pat, black = xtrans_pattern(raw_pattern), black_levels(black_level)
+    P, _, Hm, Wm = check_mosaics(flats, 4, 'flats', 'xtrans')
+    defects = check_defects(defects, 'xtrans', (Hm, Wm), raw_pattern)
+    sums, cell_n = _cell_flat_sums(device_u16(flats), XT_PERIOD, white_level, defects)
+    res = {'sums': sums}
+    if cell_n is not None:
+        res['cell_counts'] = cell_n
     res.update(xtrans_flat_stats_from_cell_sums_masked(res['sums'], pat, black, white_level, color_bias, Hm, Wm, res.get('cell_counts')))
     return res
 
@@ -583,42 +440,6 @@ def fit_log_linear(K, sigma):
     return {'slope': np.float64(slope), 'bias': np.float64(bias), 'sigma': np.float64(np.sqrt(np.sum(res * res) / (x.size - 2)))}
 
 
-def _check_sessions(sessions, cfa='bayer'):
-    if not isinstance(sessions, (list, tuple)) or len(sessions) == 0:
-        raise ValueError('sessions must be a non-empty list of {"iso", "bias", "flats" or "bursts"}')
-    shape, nbias = None, 0
-    for i, s in enumerate(sessions):
-        if 'bias' not in s:
-            raise ValueError('session %d has no %r' % (i, 'bias'))
-        if 'flats' not in s and 'bursts' not in s:
-            raise ValueError("session %d has neither 'flats' (flat-field pairs) nor 'bursts' (stacks of a static scene): the gain needs one of them" % i)
-        F, Hm, Wm = _check_mosaics(s['bias'], 3, 'session %d bias' % i, cfa)
-        if shape is None:
-            shape = (Hm, Wm)
-        if 'flats' in s:
-            P = _check_mosaics(s['flats'], 4, 'session %d flats' % i, cfa)[0]
-            if (Hm, Wm) != shape or _shape(s['flats'])[-2:] != shape:
-                raise ValueError('session %d: mosaic shapes differ (%s vs %s / %s)' % (i, shape, (Hm, Wm), _shape(s['flats'])[-2:]))
-            if F == 0 or P == 0:
-                raise ValueError('session %d: needs at least one bias frame and one flat pair' % i)
-        elif (Hm, Wm) != shape or F == 0:
-            raise ValueError('session %d: needs at least one bias frame of %s, got %s' % (i, shape, (F, Hm, Wm)))
-        if 'bursts' in s:
-            if not isinstance(s['bursts'], (list, tuple)) or len(s['bursts']) == 0:
-                raise ValueError("session %d: 'bursts' is a non-empty list of stacks (N, Hm, Wm)" % i)
-            for j, b in enumerate(s['bursts']):
-                bs = _check_mosaics(b, 3, 'session %d burst %d' % (i, j), cfa)
-                if bs[-2:] != shape:
-                    raise ValueError('session %d burst %d: mosaic shapes differ (%s vs %s)' % (i, j, shape, bs[-2:]))
-                if bs[0] < 2 or bs[0] > 256:
-                    raise ValueError('session %d burst %d: a burst holds 2 to 256 frames, got %d' % (i, j, bs[0]))
-        nbias += F
-    if nbias < 3:
-        raise ValueError('at least 3 bias frames are needed for the log-linear fits, got %d' % nbias)
-    if len(sessions) < 2:
-        raise ValueError('at least 2 sessions (2 distinct K) are needed, got %d' % len(sessions))
-
-
 def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None, cfa='bayer', defects=None):
     """Sessions of bias frames and flat pairs (or, in a session without 'flats', 'bursts': stacks (N,Hm,Wm) of a static scene whose gain is
     eld_amd.burst.burst_gain over the session's bursts; bursts next to flats are reported as diag['ptc'][i]['burst']) -> (params, diagnostics).  params has exactly the release schema
@@ -631,15 +452,14 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
     the bias frames of the lowest-ISO session (find_defects with its defaults) and returns it as diag['defects'].  X-Trans maps exist for
     the pattern phase the library packs only (row 0 = R B G B R G): another 6x6 raw_pattern with defects set is a ValueError.  None (default): every
     site counts, as before."""
-    xt = _cfa(cfa) == 'xtrans'
-    _xpattern(raw_pattern) if xt else _pattern(raw_pattern)
-    _black(black_level)
-    _check_defects(defects, cfa, raw_pattern=raw_pattern)
+    xt = check_cfa(cfa) == 'xtrans'
+    xtrans_pattern(raw_pattern) if xt else bayer_pattern(raw_pattern)
+    black_levels(black_level)
+    check_defects(defects, cfa, raw_pattern=raw_pattern)
     _check_sessions(sessions, cfa)
     if defects is not None and not isinstance(defects, str):
-        defects.check_frames(_shape(sessions[0]['bias']), cfa, 'calibration')
+        defects.check_frames(shape_of(sessions[0]['bias']), cfa, 'calibration')
     elif defects == 'auto':
-        from .defects import find_defects
         isos = [s.get('iso') for s in sessions]
         low = int(np.argmin([float(v) for v in isos])) if all(isinstance(v, (int, float)) for v in isos) else 0
         defects = find_defects(sessions[low]['bias'], cfa, raw_pattern)[0]
@@ -655,7 +475,7 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
         burst = None
         if 'bursts' in s:
             from .burst import burst_gain, stack_burst
-            burst = burst_gain([stack_burst(b, cfa, raw_pattern, np.rint(_black(black_level)), white_level, defects=defects) for b in s['bursts']],
+            burst = burst_gain([stack_burst(b, cfa, raw_pattern, np.rint(black_levels(black_level)), white_level, defects=defects) for b in s['bursts']],
                                what=what)
         if 'flats' in s:                                           # a session with flat pairs behaves as it always did; its bursts are reported beside
             fl = flat_stats(s['flats'], raw_pattern, black_level, white_level, st['color_bias'].mean(axis=0), defects=defects)
@@ -722,7 +542,7 @@ def load_manifest(path, with_cfa=False):
             session['bursts'] = [np.stack([load(p) for p in b]) for b in s['bursts']]
         sessions.append(session)
     out = (sessions, m['raw_pattern'], m['black_level'], m['white_level'])
-    return out + (_cfa(m.get('cfa', 'bayer')),) if with_cfa else out
+    return out + (check_cfa(m.get('cfa', 'bayer')),) if with_cfa else out
 
 
 def main(argv=None):
@@ -736,7 +556,6 @@ def main(argv=None):
     sessions, pattern, black, white, cfa = load_manifest(a.manifest, with_cfa=True)
     defects = a.defects if a.defects is not None else manifest_defects(a.manifest)
     if defects is not None and defects != 'auto':
-        from .defects import as_defect_map
         defects = as_defect_map(defects, '--defects')
     params, diag = calibrate_camera(sessions, pattern, black, white, cfa=cfa, defects=defects)
     path = save_camera_params(params, a.camera, a.out)

@@ -1,13 +1,14 @@
 // calib.hip -- noise-parameter calibration from bias frames and flat-field pairs (eld_amd/calibrate.py, DESIGN.md "Calibration").
-// The Bayer passes below take a 2x2 raw_pattern; the cell passes (eld_calib_cell_*) return per-cell sums of a period-2 or -6 mosaic
-// (X-Trans) and leave the colours to the host.
+// One set of pixel passes serves every CFA: they return per-cell sums of a mosaic of period 2 (Bayer) or 6 (X-Trans) and leave the
+// colours to the host.  The Bayer entry points (eld_calib_bias_stats, _bias_residual, _flat_stats) are the period-2 case with the cells
+// stored in the channel order of a 2x2 raw_pattern.
 //
 // Four passes; everything else is derived on the host in float64 from their outputs:
-//   bias statistics   uint16 mosaics -> per row: sums over the even / odd columns; per frame and channel: sum u, sum u^2 (uint64, exact)
-//   bias residual     t = float32(((u - black_c) - cb_c) - rho_y), float64 arithmetic, one rounding (NumPy's, bit for bit)
-//   flat statistics   uint16 pairs (a, b) -> per pair and channel: sum(a+b), sum(a-b), sum((a-b)^2), saturated pixels (int64, exact)
+//   bias statistics   uint16 mosaics -> per row: sums over each column class; per frame and cell: sum u, sum u^2 (uint64, exact)
+//   bias residual     t = float32(((u - black_k) - cb_k) - rho_y), float64 arithmetic, one rounding (NumPy's, bit for bit)
+//   flat statistics   uint16 pairs (a, b) -> per pair and cell: sum(a+b), sum(a-b), sum((a-b)^2), saturated pixels (int64, exact)
 //   PPCC              sorted residuals -> per Tukey-lambda shape: sum t*M, sum M^2 (and sum t, sum t^2), float64, fixed order
-// Packed channel of mosaic pixel (y, x): raw_pattern[y&1][x&1] (R, G1, B, G2 = 0..3), as eld_pack_raw_bayer_u16.
+// Cell of mosaic pixel (y, x): (y % p, x % p); its Bayer channel is raw_pattern[y&1][x&1] (R, G1, B, G2 = 0..3), as eld_pack_raw_bayer_u16.
 // No atomics anywhere: every sum is reduced in an order fixed by the shape alone, so two launches give identical bits.
 #include "common.h"
 
@@ -16,9 +17,10 @@ namespace {
 constexpr int CB_THREADS = 256;
 constexpr int CB_WAVES = CB_THREADS / ELD_WAVE;
 
-// channel of each (row parity, column parity): pat[2*py + px]
-struct Pattern {
-    int c[4];
+// Where cell k = r*p + c of the pattern lives in the caller's per-cell arrays (the sums written, the colour bias read): slot s[k].  The
+// cell entry points store cells in order (identity); the Bayer ones in channel order, s = the 2x2 raw_pattern.
+struct CellSlots {
+    unsigned char s[36];
 };
 
 __device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
@@ -48,125 +50,6 @@ __device__ __forceinline__ void block_sum_u64(uint64_t (&v)[NV], uint64_t* red /
         tot[threadIdx.x] = s;
     }
     __syncthreads();
-}
-
-// One 32-bit word of a row holds the pixels of one even column (low half) and the odd column after it: Wm is even, rows start
-// 4-byte aligned.  VEC: 16-byte loads (4 words) when Wm % 8 == 0 and the base is 16-byte aligned.
-template <bool VEC>
-__device__ __forceinline__ int row_words(const uint32_t* __restrict__ row, int k, uint32_t (&w)[4]) {
-    if (VEC) {
-        const uint4 q = reinterpret_cast<const uint4*>(row)[k];
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-        return 4;
-    }
-    w[0] = row[k];
-    return 1;
-}
-
-// ---- bias statistics, pass 1: one block per (row, frame).  rows[(f*Hm + y)*2 + p] = sum of u over the columns of parity p;
-// part[((f*Hm + y)*2 + p)*2 + {0, 1}] = sum of u, sum of u^2 there (workspace, pass 2's input). ----
-template <bool VEC>
-__global__ __launch_bounds__(CB_THREADS) void bias_row_kernel(const uint16_t* __restrict__ u, int Hm, int Wm, uint64_t* __restrict__ rows,
-                                                               uint64_t* __restrict__ part) {
-    __shared__ uint64_t red[CB_WAVES * 4], tot[4];
-    const int y = blockIdx.x, f = blockIdx.y;
-    const size_t ro = ((size_t)f * Hm + y);
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(u + ro * Wm);
-    const int nw = Wm / 2, nk = VEC ? nw / 4 : nw;
-    uint64_t v[4] = {0, 0, 0, 0};                              // sum even, sum odd, sum^2 even, sum^2 odd
-    for (int k = threadIdx.x; k < nk; k += CB_THREADS) {
-        uint32_t w[4];
-        const int m = row_words<VEC>(row, k, w);
-        for (int j = 0; j < m; ++j) {
-            const uint32_t e = w[j] & 0xFFFFu, o = w[j] >> 16;
-            v[0] += e; v[1] += o;
-            v[2] += (uint64_t)(e * e); v[3] += (uint64_t)(o * o);   // < 2^32: exact in uint32
-        }
-    }
-    block_sum_u64<4>(v, red, tot);
-    if (threadIdx.x < 2) rows[ro * 2 + threadIdx.x] = tot[threadIdx.x];
-    if (threadIdx.x < 4) part[ro * 4 + threadIdx.x] = tot[(threadIdx.x & 1) * 2 + (threadIdx.x >> 1)];   // [px][s] <- tot[s*2 + px]
-}
-
-// ---- pass 2 (bias and flat): one block per frame / pair sums the per-row partials of the rows of each parity into the channels.
-// part: [F][Hm][2 column parities][NS] uint64 (two's-complement sums stay exact); out: [F][4 channels][NS]. ----
-template <int NS>
-__global__ __launch_bounds__(CB_THREADS) void chan_reduce_kernel(const uint64_t* __restrict__ part, int Hm, Pattern pat, uint64_t* __restrict__ out) {
-    __shared__ uint64_t red[CB_WAVES * 4 * NS], tot[4 * NS];
-    const int f = blockIdx.x;
-    const uint64_t* p = part + (size_t)f * Hm * 2 * NS;
-    uint64_t v[4 * NS];                                        // [2*py + px][s]
-#pragma unroll
-    for (int k = 0; k < 4 * NS; ++k) v[k] = 0;
-    for (int y = threadIdx.x; y < Hm; y += CB_THREADS) {
-        const int py = y & 1;
-#pragma unroll
-        for (int px = 0; px < 2; ++px)
-#pragma unroll
-            for (int s = 0; s < NS; ++s) {
-                const uint64_t a = p[((size_t)y * 2 + px) * NS + s];
-                v[(2 * 0 + px) * NS + s] += py ? 0 : a;
-                v[(2 * 1 + px) * NS + s] += py ? a : 0;
-            }
-    }
-    block_sum_u64<4 * NS>(v, red, tot);
-    if (threadIdx.x < 4 * NS) {
-        const int q = threadIdx.x / NS, s = threadIdx.x % NS;
-        out[((size_t)f * 4 + pat.c[q]) * NS + s] = tot[threadIdx.x];
-    }
-}
-
-// ---- flat statistics, pass 1: one block per (row, pair).  part[(p*Hm + y)*2 + px][4] = sum(a+b), sum(a-b), sum((a-b)^2), #(a or b >= white)
-template <bool VEC>
-__global__ __launch_bounds__(CB_THREADS) void flat_row_kernel(const uint16_t* __restrict__ ab, int Hm, int Wm, uint32_t white,
-                                                               uint64_t* __restrict__ part) {
-    __shared__ uint64_t red[CB_WAVES * 8], tot[8];
-    const int y = blockIdx.x, pr = blockIdx.y;
-    const size_t frame = (size_t)Hm * Wm;
-    const uint16_t* a = ab + (size_t)pr * 2 * frame + (size_t)y * Wm;
-    const uint32_t* ra = reinterpret_cast<const uint32_t*>(a);
-    const uint32_t* rb = reinterpret_cast<const uint32_t*>(a + frame);
-    const int nw = Wm / 2, nk = VEC ? nw / 4 : nw;
-    uint64_t v[8] = {0, 0, 0, 0, 0, 0, 0, 0};                  // [px][s]
-    for (int k = threadIdx.x; k < nk; k += CB_THREADS) {
-        uint32_t wa[4], wb[4];
-        const int m = row_words<VEC>(ra, k, wa);
-        row_words<VEC>(rb, k, wb);
-        for (int j = 0; j < m; ++j)
-#pragma unroll
-            for (int px = 0; px < 2; ++px) {
-                const uint32_t x = (wa[j] >> (16 * px)) & 0xFFFFu, z = (wb[j] >> (16 * px)) & 0xFFFFu;
-                const int32_t d = (int32_t)x - (int32_t)z;
-                v[px * 4 + 0] += x + z;
-                v[px * 4 + 1] += (uint64_t)(int64_t)d;
-                v[px * 4 + 2] += (uint64_t)((uint32_t)d * (uint32_t)d);   // d^2 < 2^32: exact modulo 2^32
-                v[px * 4 + 3] += (x >= white || z >= white) ? 1u : 0u;
-            }
-    }
-    block_sum_u64<8>(v, red, tot);
-    if (threadIdx.x < 8) part[((size_t)pr * Hm + y) * 8 + threadIdx.x] = tot[threadIdx.x];
-}
-
-// ---- bias residual: t = float32(((u - black_c) - cb[f][c]) - rho[f][y]) in float64.  One block per (row, frame). ----
-struct Black {
-    double b[4];
-};
-
-__global__ __launch_bounds__(CB_THREADS) void bias_residual_kernel(const uint16_t* __restrict__ u, int Hm, int Wm, Pattern pat, Black blk,
-                                                                   const double* __restrict__ cb, const double* __restrict__ rho,
-                                                                   float* __restrict__ t) {
-    const int y = blockIdx.x, f = blockIdx.y;
-    const size_t ro = (size_t)f * Hm + y;
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(u + ro * Wm);
-    float2* out = reinterpret_cast<float2*>(t + ro * Wm);
-    const int c0 = pat.c[2 * (y & 1)], c1 = pat.c[2 * (y & 1) + 1];
-    const double b0 = blk.b[c0], b1 = blk.b[c1], cb0 = cb[f * 4 + c0], cb1 = cb[f * 4 + c1], r = rho[ro];
-    for (int k = threadIdx.x; k < Wm / 2; k += CB_THREADS) {
-        const uint32_t w = row[k];
-        const double e = (((double)(w & 0xFFFFu) - b0) - cb0) - r;
-        const double o = (((double)(w >> 16) - b1) - cb1) - r;
-        out[k] = make_float2((float)e, (float)o);
-    }
 }
 
 // ---- PPCC over a Tukey-lambda grid -----------------------------------------------------------------------------------------
@@ -304,35 +187,41 @@ __global__ __launch_bounds__(256) void ppcc_final_kernel(const float* __restrict
 // ---- cell statistics of a pattern of period PP = 2 * P2 (2: Bayer, 6: X-Trans) ----------------------------------------------
 // Word k of a row holds columns 2k, 2k+1: column classes 2 (k % P2) and 2 (k % P2) + 1.  A lane takes G consecutive words per step (G a
 // multiple of P2, starting at a multiple of G), so word j of the step has class j % P2 at compile time; the last nw % G words of the row
-// (fewer than G, starting at a multiple of P2) go to lanes 0.. one word each.  fn(q, k, w, take) adds word k to class q where `take`.
+// (fewer than G, starting at a multiple of P2) go to lanes 0.. one word each.  NR rows of one alignment (a bias row; the a and b rows of
+// a flat pair) are walked together: fn(q, w, take) adds the rows' words w[0..NR) at one word index to class q where `take`.
+// VEC: 16-byte loads (4 words) when Wm % 8 == 0 and the base is 16-byte aligned (rows and frames then start 16-byte aligned too).
 // Accumulators v[(q*2 + px)*NS + s]: word class q, column parity px (column class 2q + px), statistic s.
-template <int P2, bool VEC>
+template <int P2, bool VEC, int NR>
 struct CellWalk {
     static constexpr int G = VEC ? 4 * P2 : P2;
     template <typename Fn>
-    __device__ __forceinline__ static void run(const uint32_t* __restrict__ row, int nw, Fn fn) {
+    __device__ __forceinline__ static void run(const uint32_t* const (&row)[NR], int nw, Fn fn) {
         const int ng = nw / G;
         for (int kk = threadIdx.x; kk < ng; kk += CB_THREADS) {
-            uint32_t w[G];
-            if (VEC) {
+            uint32_t w[G][NR];
 #pragma unroll
-                for (int i = 0; i < G / 4; ++i) {
-                    const uint4 q = reinterpret_cast<const uint4*>(row)[kk * (G / 4) + i];
-                    w[4 * i] = q.x; w[4 * i + 1] = q.y; w[4 * i + 2] = q.z; w[4 * i + 3] = q.w;
+            for (int r = 0; r < NR; ++r) {
+                if (VEC) {
+#pragma unroll
+                    for (int i = 0; i < G / 4; ++i) {
+                        const uint4 q = reinterpret_cast<const uint4*>(row[r])[kk * (G / 4) + i];
+                        w[4 * i][r] = q.x; w[4 * i + 1][r] = q.y; w[4 * i + 2][r] = q.z; w[4 * i + 3][r] = q.w;
+                    }
+                } else {
+#pragma unroll
+                    for (int j = 0; j < G; ++j) w[j][r] = row[r][kk * G + j];
                 }
-            } else {
-#pragma unroll
-                for (int j = 0; j < G; ++j) w[j] = row[kk * G + j];
             }
 #pragma unroll
-            for (int j = 0; j < G; ++j) fn(j % P2, (size_t)kk * G + j, w[j], true);
+            for (int j = 0; j < G; ++j) fn(j % P2, w[j], true);
         }
         const int tail = nw - ng * G;
         if ((int)threadIdx.x < tail) {
-            const int k = ng * G + threadIdx.x;
-            const uint32_t wt = row[k];
+            uint32_t wt[NR];
 #pragma unroll
-            for (int q = 0; q < P2; ++q) fn(q, (size_t)k, wt, (int)threadIdx.x % P2 == q);   // every class, masked: no indexed registers
+            for (int r = 0; r < NR; ++r) wt[r] = row[r][ng * G + threadIdx.x];
+#pragma unroll
+            for (int q = 0; q < P2; ++q) fn(q, wt, (int)threadIdx.x % P2 == q);   // every class, masked: no indexed registers
         }
     }
 };
@@ -346,12 +235,12 @@ __global__ __launch_bounds__(CB_THREADS) void cell_row_kernel(const uint16_t* __
     __shared__ uint64_t red[CB_WAVES * NV], tot[NV];
     const int y = blockIdx.x, f = blockIdx.y;
     const size_t ro = (size_t)f * Hm + y;
-    const uint32_t* row = reinterpret_cast<const uint32_t*>(u + ro * Wm);
+    const uint32_t* const row[1] = {reinterpret_cast<const uint32_t*>(u + ro * Wm)};
     uint64_t v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = 0;
-    CellWalk<P2, VEC>::run(row, Wm / 2, [&](int q, size_t, uint32_t w, bool take) __attribute__((always_inline)) {
-        const uint32_t e = take ? w & 0xFFFFu : 0u, o = take ? w >> 16 : 0u;
+    CellWalk<P2, VEC, 1>::run(row, Wm / 2, [&](int q, const uint32_t (&w)[1], bool take) __attribute__((always_inline)) {
+        const uint32_t e = take ? w[0] & 0xFFFFu : 0u, o = take ? w[0] >> 16 : 0u;
         v[(2 * q) * 2] += e; v[(2 * q + 1) * 2] += o;
         v[(2 * q) * 2 + 1] += (uint64_t)(e * e); v[(2 * q + 1) * 2 + 1] += (uint64_t)(o * o);   // < 2^32: exact in uint32
     });
@@ -369,16 +258,14 @@ __global__ __launch_bounds__(CB_THREADS) void cell_flat_row_kernel(const uint16_
     const int y = blockIdx.x, pr = blockIdx.y;
     const size_t frame = (size_t)Hm * Wm;
     const uint16_t* a = ab + (size_t)pr * 2 * frame + (size_t)y * Wm;
-    const uint32_t* rb = reinterpret_cast<const uint32_t*>(a + frame);
+    const uint32_t* const row[2] = {reinterpret_cast<const uint32_t*>(a), reinterpret_cast<const uint32_t*>(a + frame)};
     uint64_t v[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) v[k] = 0;
-    // the b row is read word for word at the a row's word index (same alignment: the frame size is a multiple of 2 words when VEC)
-    CellWalk<P2, VEC>::run(reinterpret_cast<const uint32_t*>(a), Wm / 2, [&](int q, size_t k, uint32_t wa, bool take) __attribute__((always_inline)) {
-        const uint32_t wb = rb[k];
+    CellWalk<P2, VEC, 2>::run(row, Wm / 2, [&](int q, const uint32_t (&w)[2], bool take) __attribute__((always_inline)) {
 #pragma unroll
         for (int px = 0; px < 2; ++px) {
-            const uint32_t x = take ? (wa >> (16 * px)) & 0xFFFFu : 0u, z = take ? (wb >> (16 * px)) & 0xFFFFu : 0u;
+            const uint32_t x = take ? (w[0] >> (16 * px)) & 0xFFFFu : 0u, z = take ? (w[1] >> (16 * px)) & 0xFFFFu : 0u;
             const int32_t d = (int32_t)x - (int32_t)z;
             uint64_t* vv = v + (2 * q + px) * 4;
             vv[0] += x + z;
@@ -391,41 +278,52 @@ __global__ __launch_bounds__(CB_THREADS) void cell_flat_row_kernel(const uint16_
     if (threadIdx.x < NV) part[((size_t)pr * Hm + y) * NV + threadIdx.x] = tot[threadIdx.x];
 }
 
-// pass 2 (bias and flat): one block per frame / pair folds the per-row partials part[F][Hm][PP][NS] into out[F][PP][PP][NS] (row class
-// y % PP).  Lanes take rows y = tid, tid + RS, ... with RS a multiple of PP, so a lane's rows share one class; the lanes of one class
-// are then summed in lane order.
+// pass 2 (bias and flat): one block per frame / pair folds the per-row partials part[F][Hm][PP][NS] into out[F][PP*PP][NS] (row class
+// y % PP; cell (rc, c) goes to slot.s[rc*PP + c]).  Lanes take rows y = tid, tid + RS, ... with RS a multiple of PP, so a lane's rows
+// share one class.  The upper half of the lanes is then folded onto the lower while both halves hold the same classes (RS = 256 -> 2 at
+// PP = 2, 252 -> 126 at PP = 6), and one lane per output sums what is left of its class.
 template <int PP, int NS>
-__global__ __launch_bounds__(CB_THREADS) void cell_reduce_kernel(const uint64_t* __restrict__ part, int Hm, uint64_t* __restrict__ out) {
+__global__ __launch_bounds__(CB_THREADS) void cell_reduce_kernel(const uint64_t* __restrict__ part, int Hm, CellSlots slot, uint64_t* __restrict__ out) {
     constexpr int RS = CB_THREADS - CB_THREADS % PP, NV = PP * NS;
+    static_assert(PP * NV <= CB_THREADS, "one lane per output");
     __shared__ uint64_t red[RS * NV];
     const int f = blockIdx.x, tid = threadIdx.x;
+    const int rc = tid / NV, k = tid - rc * NV;                      // output tid = rc * NV + (c * NS + s), for tid < PP * NV
+    const int cell = tid < PP * NV ? slot.s[rc * PP + k / NS] : 0;
     const uint64_t* p = part + (size_t)f * Hm * NV;
     if (tid < RS) {
         uint64_t v[NV];
 #pragma unroll
-        for (int k = 0; k < NV; ++k) v[k] = 0;
+        for (int i = 0; i < NV; ++i) v[i] = 0;
         for (int y = tid; y < Hm; y += RS)
 #pragma unroll
-            for (int k = 0; k < NV; ++k) v[k] += p[(size_t)y * NV + k];
+            for (int i = 0; i < NV; ++i) v[i] += p[(size_t)y * NV + i];
 #pragma unroll
-        for (int k = 0; k < NV; ++k) red[tid * NV + k] = v[k];
+        for (int i = 0; i < NV; ++i) red[tid * NV + i] = v[i];
     }
     __syncthreads();
-    for (int o = tid; o < PP * NV; o += CB_THREADS) {             // o = rc * NV + (c * NS + s)
-        const int rc = o / NV, k = o - rc * NV;
+    int h = RS;
+    while (h % (2 * PP) == 0) {
+        h /= 2;
+        if (tid < h)
+#pragma unroll
+            for (int i = 0; i < NV; ++i) red[tid * NV + i] += red[(tid + h) * NV + i];
+        __syncthreads();
+    }
+    if (tid < PP * NV) {
         uint64_t s = 0;
-        for (int l = rc; l < RS; l += PP) s += red[l * NV + k];
-        out[(size_t)f * PP * NV + o] = s;
+        for (int l = rc; l < h; l += PP) s += red[l * NV + k];
+        out[((size_t)f * PP * PP + cell) * NS + k % NS] = s;
     }
 }
 
-// residual: t = float32(((u - black[k]) - cb[f][k]) - rho[f][y]), k = (y % PP) * PP + x % PP, in float64.  One block per (row, frame).
+// residual: t = float32(((u - black[k]) - cb[f][slot.s[k]]) - rho[f][y]), k = (y % PP) * PP + x % PP, in float64.  One block per (row, frame).
 struct CellBlack {
     double b[36];
 };
 
 template <int P2>
-__global__ __launch_bounds__(CB_THREADS) void cell_residual_kernel(const uint16_t* __restrict__ u, int Hm, int Wm, CellBlack blk,
+__global__ __launch_bounds__(CB_THREADS) void cell_residual_kernel(const uint16_t* __restrict__ u, int Hm, int Wm, CellBlack blk, CellSlots slot,
                                                                    const double* __restrict__ cb, const double* __restrict__ rho,
                                                                    float* __restrict__ t) {
     constexpr int PP = 2 * P2;
@@ -435,7 +333,7 @@ __global__ __launch_bounds__(CB_THREADS) void cell_residual_kernel(const uint16_
     const int rc = y % PP;
     if (threadIdx.x < PP) {
         s_b[threadIdx.x] = blk.b[rc * PP + threadIdx.x];
-        s_cb[threadIdx.x] = cb[(size_t)f * PP * PP + rc * PP + threadIdx.x];
+        s_cb[threadIdx.x] = cb[(size_t)f * PP * PP + slot.s[rc * PP + threadIdx.x]];
     }
     __syncthreads();
     const uint32_t* row = reinterpret_cast<const uint32_t*>(u + ro * Wm);
@@ -450,21 +348,62 @@ __global__ __launch_bounds__(CB_THREADS) void cell_residual_kernel(const uint16_
     }
 }
 
-int parse_pattern(const int* raw_pattern, Pattern& p) {
+// a 2x2 raw_pattern (a permutation of the channels 0..3) as the slots of the period-2 cells
+int parse_pattern(const int* raw_pattern, CellSlots& p) {
     if (!raw_pattern) return ELD_EINVAL;
     bool seen[4] = {false, false, false, false};
     for (int i = 0; i < 4; ++i) {
         const int k = raw_pattern[i];
         if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
         seen[k] = true;
-        p.c[i] = k;
+        p.s[i] = (unsigned char)k;
     }
     return 0;
 }
 
+CellSlots cells_in_order() {
+    CellSlots p;
+    for (int k = 0; k < 36; ++k) p.s[k] = (unsigned char)k;
+    return p;
+}
+
 bool mosaic_ok(int F, int Hm, int Wm) { return F >= 0 && Hm >= 0 && Wm >= 0 && Hm % 2 == 0 && Wm % 2 == 0 && F <= 65535; }
+bool cell_ok(int F, int Hm, int Wm, int p) { return (p == 2 || p == 6) && F >= 0 && Hm >= 0 && Wm >= 0 && Wm % 2 == 0 && F <= 65535; }
 bool vec_ok(const void* p, int Wm) { return Wm % 8 == 0 && ((uintptr_t)p & 15u) == 0; }
 bool word_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0; }   // rows are read as 32-bit words (two pixels)
+
+// The launches behind the entry points (arguments checked by the caller, nothing empty): the statistics' two passes and the residual.
+template <int P2>
+int launch_cell_stats(const uint16_t* u, int F, int Hm, int Wm, const CellSlots& slot, uint64_t* cell_sums, uint64_t* row_sums, uint64_t* part,
+                      hipStream_t s) {
+    const dim3 g(Hm, F), b(CB_THREADS);
+    if (vec_ok(u, Wm)) ELD_LAUNCH((cell_row_kernel<P2, true>), g, b, 0, s, u, Hm, Wm, row_sums, part);
+    else ELD_LAUNCH((cell_row_kernel<P2, false>), g, b, 0, s, u, Hm, Wm, row_sums, part);
+    ELD_LAUNCH_CHECK();
+    ELD_LAUNCH((cell_reduce_kernel<2 * P2, 2>), dim3(F), b, 0, s, part, Hm, slot, cell_sums);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int P2>
+int launch_cell_flat_stats(const uint16_t* ab, int P, int Hm, int Wm, const CellSlots& slot, uint32_t white, uint64_t* out, uint64_t* part,
+                           hipStream_t s) {
+    const dim3 g(Hm, P), b(CB_THREADS);
+    if (vec_ok(ab, Wm)) ELD_LAUNCH((cell_flat_row_kernel<P2, true>), g, b, 0, s, ab, Hm, Wm, white, part);
+    else ELD_LAUNCH((cell_flat_row_kernel<P2, false>), g, b, 0, s, ab, Hm, Wm, white, part);
+    ELD_LAUNCH_CHECK();
+    ELD_LAUNCH((cell_reduce_kernel<2 * P2, 4>), dim3(P), b, 0, s, part, Hm, slot, out);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+template <int P2>
+int launch_cell_residual(const uint16_t* u, int F, int Hm, int Wm, const CellBlack& blk, const CellSlots& slot, const double* cb,
+                         const double* rho, float* t, hipStream_t s) {
+    ELD_LAUNCH(cell_residual_kernel<P2>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, blk, slot, cb, rho, t);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
 
 }  // namespace
 
@@ -474,32 +413,23 @@ extern "C" size_t eld_calib_bias_stats_workspace_bytes(int F, int Hm) {
 
 extern "C" int eld_calib_bias_stats(const uint16_t* u, int F, int Hm, int Wm, const int* raw_pattern, uint64_t* chan_sums, uint64_t* row_sums,
                                     void* ws, size_t ws_bytes, void* stream) {
-    Pattern pat;
+    CellSlots pat = {};
     if (!mosaic_ok(F, Hm, Wm) || parse_pattern(raw_pattern, pat)) return ELD_EINVAL;
     if (F == 0 || Hm == 0 || Wm == 0) return 0;
     if (!u || !chan_sums || !row_sums || !ws || !word_aligned(u)) return ELD_EINVAL;
     if (ws_bytes < eld_calib_bias_stats_workspace_bytes(F, Hm)) return ELD_EWS;
-    uint64_t* part = static_cast<uint64_t*>(ws);
-    hipStream_t s = as_stream(stream);
-    if (vec_ok(u, Wm)) ELD_LAUNCH(bias_row_kernel<true>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, row_sums, part);
-    else ELD_LAUNCH(bias_row_kernel<false>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, row_sums, part);
-    ELD_LAUNCH_CHECK();
-    ELD_LAUNCH(chan_reduce_kernel<2>, dim3(F), dim3(CB_THREADS), 0, s, part, Hm, pat, chan_sums);
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return launch_cell_stats<1>(u, F, Hm, Wm, pat, chan_sums, row_sums, static_cast<uint64_t*>(ws), as_stream(stream));
 }
 
 extern "C" int eld_calib_bias_residual(const uint16_t* u, int F, int Hm, int Wm, const int* raw_pattern, const double* black_level,
                                        const double* color_bias, const double* row_offset, float* t, void* stream) {
-    Pattern pat;
+    CellSlots pat = {};
     if (!mosaic_ok(F, Hm, Wm) || parse_pattern(raw_pattern, pat) || !black_level) return ELD_EINVAL;
     if (F == 0 || Hm == 0 || Wm == 0) return 0;
     if (!u || !color_bias || !row_offset || !t || !word_aligned(u) || ((uintptr_t)t & 7u)) return ELD_EINVAL;
-    Black blk;
-    for (int k = 0; k < 4; ++k) blk.b[k] = black_level[k];
-    ELD_LAUNCH(bias_residual_kernel, dim3(Hm, F), dim3(CB_THREADS), 0, as_stream(stream), u, Hm, Wm, pat, blk, color_bias, row_offset, t);
-    ELD_LAUNCH_CHECK();
-    return 0;
+    CellBlack blk = {};
+    for (int k = 0; k < 4; ++k) blk.b[k] = black_level[pat.s[k]];
+    return launch_cell_residual<1>(u, F, Hm, Wm, blk, pat, color_bias, row_offset, t, as_stream(stream));
 }
 
 extern "C" size_t eld_calib_flat_stats_workspace_bytes(int P, int Hm) {
@@ -508,19 +438,13 @@ extern "C" size_t eld_calib_flat_stats_workspace_bytes(int P, int Hm) {
 
 extern "C" int eld_calib_flat_stats(const uint16_t* ab, int P, int Hm, int Wm, const int* raw_pattern, int white_level, int64_t* out,
                                     void* ws, size_t ws_bytes, void* stream) {
-    Pattern pat;
+    CellSlots pat = {};
     if (!mosaic_ok(P, Hm, Wm) || parse_pattern(raw_pattern, pat) || white_level < 0) return ELD_EINVAL;
     if (P == 0 || Hm == 0 || Wm == 0) return 0;
     if (!ab || !out || !ws || !word_aligned(ab)) return ELD_EINVAL;
     if (ws_bytes < eld_calib_flat_stats_workspace_bytes(P, Hm)) return ELD_EWS;
-    uint64_t* part = static_cast<uint64_t*>(ws);
-    hipStream_t s = as_stream(stream);
-    if (vec_ok(ab, Wm)) ELD_LAUNCH(flat_row_kernel<true>, dim3(Hm, P), dim3(CB_THREADS), 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
-    else ELD_LAUNCH(flat_row_kernel<false>, dim3(Hm, P), dim3(CB_THREADS), 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
-    ELD_LAUNCH_CHECK();
-    ELD_LAUNCH(chan_reduce_kernel<4>, dim3(P), dim3(CB_THREADS), 0, s, part, Hm, pat, reinterpret_cast<uint64_t*>(out));
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return launch_cell_flat_stats<1>(ab, P, Hm, Wm, pat, (uint32_t)white_level, reinterpret_cast<uint64_t*>(out), static_cast<uint64_t*>(ws),
+                                     as_stream(stream));
 }
 
 extern "C" size_t eld_calib_ppcc_workspace_bytes(int F, size_t n, int L) {
@@ -548,10 +472,6 @@ extern "C" int eld_calib_ppcc(const float* t_sorted, int F, size_t n, const floa
 }
 
 // ---- cell statistics (any CFA of period 2 or 6) ----------------------------------------------------------------------------------
-namespace {
-bool cell_ok(int F, int Hm, int Wm, int p) { return (p == 2 || p == 6) && F >= 0 && Hm >= 0 && Wm >= 0 && Wm % 2 == 0 && F <= 65535; }
-}  // namespace
-
 extern "C" size_t eld_calib_cell_stats_workspace_bytes(int F, int Hm, int p) {
     return F <= 0 || Hm <= 0 || (p != 2 && p != 6) ? 0 : (size_t)F * Hm * p * 2 * sizeof(uint64_t);
 }
@@ -563,22 +483,8 @@ extern "C" int eld_calib_cell_stats(const uint16_t* u, int F, int Hm, int Wm, in
     if (!u || !cell_sums || !row_sums || !ws || !word_aligned(u)) return ELD_EINVAL;
     if (ws_bytes < eld_calib_cell_stats_workspace_bytes(F, Hm, p)) return ELD_EWS;
     uint64_t* part = static_cast<uint64_t*>(ws);
-    hipStream_t s = as_stream(stream);
-    const dim3 g(Hm, F), b(CB_THREADS);
-    const bool v = vec_ok(u, Wm);
-    if (p == 2) {
-        if (v) ELD_LAUNCH((cell_row_kernel<1, true>), g, b, 0, s, u, Hm, Wm, row_sums, part);
-        else ELD_LAUNCH((cell_row_kernel<1, false>), g, b, 0, s, u, Hm, Wm, row_sums, part);
-        ELD_LAUNCH_CHECK();
-        ELD_LAUNCH((cell_reduce_kernel<2, 2>), dim3(F), b, 0, s, part, Hm, cell_sums);
-    } else {
-        if (v) ELD_LAUNCH((cell_row_kernel<3, true>), g, b, 0, s, u, Hm, Wm, row_sums, part);
-        else ELD_LAUNCH((cell_row_kernel<3, false>), g, b, 0, s, u, Hm, Wm, row_sums, part);
-        ELD_LAUNCH_CHECK();
-        ELD_LAUNCH((cell_reduce_kernel<6, 2>), dim3(F), b, 0, s, part, Hm, cell_sums);
-    }
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return p == 2 ? launch_cell_stats<1>(u, F, Hm, Wm, cells_in_order(), cell_sums, row_sums, part, as_stream(stream))
+                  : launch_cell_stats<3>(u, F, Hm, Wm, cells_in_order(), cell_sums, row_sums, part, as_stream(stream));
 }
 
 extern "C" int eld_calib_cell_residual(const uint16_t* u, int F, int Hm, int Wm, int p, const double* black, const double* cell_bias,
@@ -588,11 +494,8 @@ extern "C" int eld_calib_cell_residual(const uint16_t* u, int F, int Hm, int Wm,
     if (!u || !cell_bias || !row_offset || !t || !word_aligned(u) || ((uintptr_t)t & 7u)) return ELD_EINVAL;
     CellBlack blk;
     for (int k = 0; k < 36; ++k) blk.b[k] = k < p * p ? black[k] : 0.0;
-    hipStream_t s = as_stream(stream);
-    if (p == 2) ELD_LAUNCH(cell_residual_kernel<1>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, blk, cell_bias, row_offset, t);
-    else ELD_LAUNCH(cell_residual_kernel<3>, dim3(Hm, F), dim3(CB_THREADS), 0, s, u, Hm, Wm, blk, cell_bias, row_offset, t);
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return p == 2 ? launch_cell_residual<1>(u, F, Hm, Wm, blk, cells_in_order(), cell_bias, row_offset, t, as_stream(stream))
+                  : launch_cell_residual<3>(u, F, Hm, Wm, blk, cells_in_order(), cell_bias, row_offset, t, as_stream(stream));
 }
 
 extern "C" size_t eld_calib_cell_flat_stats_workspace_bytes(int P, int Hm, int p) {
@@ -607,20 +510,6 @@ extern "C" int eld_calib_cell_flat_stats(const uint16_t* ab, int P, int Hm, int 
     if (ws_bytes < eld_calib_cell_flat_stats_workspace_bytes(P, Hm, p)) return ELD_EWS;
     uint64_t* part = static_cast<uint64_t*>(ws);
     uint64_t* o = reinterpret_cast<uint64_t*>(out);
-    hipStream_t s = as_stream(stream);
-    const dim3 g(Hm, P), b(CB_THREADS);
-    const bool v = vec_ok(ab, Wm);
-    if (p == 2) {
-        if (v) ELD_LAUNCH((cell_flat_row_kernel<1, true>), g, b, 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
-        else ELD_LAUNCH((cell_flat_row_kernel<1, false>), g, b, 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
-        ELD_LAUNCH_CHECK();
-        ELD_LAUNCH((cell_reduce_kernel<2, 4>), dim3(P), b, 0, s, part, Hm, o);
-    } else {
-        if (v) ELD_LAUNCH((cell_flat_row_kernel<3, true>), g, b, 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
-        else ELD_LAUNCH((cell_flat_row_kernel<3, false>), g, b, 0, s, ab, Hm, Wm, (uint32_t)white_level, part);
-        ELD_LAUNCH_CHECK();
-        ELD_LAUNCH((cell_reduce_kernel<6, 4>), dim3(P), b, 0, s, part, Hm, o);
-    }
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return p == 2 ? launch_cell_flat_stats<1>(ab, P, Hm, Wm, cells_in_order(), (uint32_t)white_level, o, part, as_stream(stream))
+                  : launch_cell_flat_stats<3>(ab, P, Hm, Wm, cells_in_order(), (uint32_t)white_level, o, part, as_stream(stream));
 }

@@ -29,7 +29,7 @@ import sys
 import numpy as np
 
 from . import _lib as L
-from .calibrate import CODE_COLOUR, XT_PERIOD, _cfa, _check_mosaics, _device_u16, _pattern, _shape, _ws, _xpattern
+from .mosaic import CODE_COLOUR, XT_PERIOD, bayer_pattern, check_cfa, check_mosaics, device_u16, shape_of, workspace, xtrans_pattern
 from .denoise import DEFAULT_PATTERN, _as_u16
 
 MAX_FRAMES = 4096                    # the stack sum stays exact in uint32
@@ -50,13 +50,13 @@ def xtrans_tables():
 def _class_pattern(cfa, raw_pattern):
     """-> (raw_pattern as int64 (p,p), class table int64 (p,p)).  Bayer: the channel codes themselves; X-Trans: colours R 0, G 1, B 2, which
     must be the cell the library packs (its tap lists are compiled for it).  raw_pattern None: RGGB / the library's cell."""
-    if _cfa(cfa) == 'bayer':
-        pat = _pattern(DEFAULT_PATTERN if raw_pattern is None else raw_pattern)
+    if check_cfa(cfa) == 'bayer':
+        pat = bayer_pattern(DEFAULT_PATTERN if raw_pattern is None else raw_pattern)
         return pat, pat
     cell = xtrans_tables()['colour']
     if raw_pattern is None:
         return cell.copy(), cell
-    pat = _xpattern(raw_pattern)
+    pat = xtrans_pattern(raw_pattern)
     if not np.array_equal(CODE_COLOUR[pat], cell):
         raise ValueError('this X-Trans raw_pattern is not the 6x6 cell the library packs (row 0 = R B G B R G): crop the mosaic so that it '
                          'starts on that phase; got %r' % (pat.tolist(),))
@@ -134,7 +134,7 @@ class DefectMap:
     bitmap       the same on the device (uploaded on first use; None without a GPU)"""
 
     def __init__(self, shape, cfa, raw_pattern, mask):
-        self.cfa = _cfa(cfa)
+        self.cfa = check_cfa(cfa)
         self.shape = _check_shape(shape, cfa)
         self.raw_pattern, self._cls = _class_pattern(cfa, raw_pattern)
         mask = np.asarray(mask, bool)
@@ -152,7 +152,7 @@ class DefectMap:
     @classmethod
     def from_sites(cls, sites, shape, cfa='bayer', raw_pattern=None):
         """sites: (K,2) integer (y, x) pairs inside `shape`, in any order, without duplicates."""
-        cfa = _cfa(cfa)
+        cfa = check_cfa(cfa)
         Hm, Wm = _check_shape(shape, cfa)
         s = np.asarray(sites)
         if s.size == 0:
@@ -225,6 +225,23 @@ class DefectMap:
             return cls.from_sites(z['sites'], tuple(int(v) for v in z['shape']), str(z['cfa']), z['raw_pattern'])
 
 
+def check_defects(defects, cfa, shape=None, raw_pattern=None):
+    """The map must be for this CFA, these sides and -- X-Trans -- this pattern: its neighbourhoods are those of the colours of the 6x6
+    cell it was built for.  A Bayer map's neighbourhoods are the sites at offsets of +-2 whatever the 2x2 permutation, so a Bayer map
+    made under another raw_pattern flags and repairs the same sites: its raw_pattern is not compared."""
+    if defects is None or (isinstance(defects, str) and defects == 'auto'):
+        return defects
+    if not isinstance(defects, DefectMap):
+        raise ValueError("defects must be a DefectMap, 'auto' or None, got %r" % (type(defects).__name__,))
+    if cfa == 'xtrans' and defects.cfa == 'xtrans' and raw_pattern is not None and not np.array_equal(CODE_COLOUR[xtrans_pattern(raw_pattern)], defects.classes):
+        raise ValueError('calibration: the defect map was built for another X-Trans raw_pattern (the colours of its 6x6 cell differ)')
+    if shape is not None:
+        defects.check_frames(shape, cfa, 'calibration')
+    elif defects.cfa != cfa:
+        raise ValueError('calibration: the defect map is for cfa=%r, the frames are %r' % (defects.cfa, cfa))
+    return defects
+
+
 def as_defect_map(defects, what='defects'):
     """A DefectMap, or a path to a saved one -> DefectMap; anything else is a ValueError."""
     if isinstance(defects, DefectMap):
@@ -238,10 +255,10 @@ def as_defect_map(defects, what='defects'):
 
 # ---- device passes -------------------------------------------------------------------------------------------------------------------------
 def _check_stack(frames, cfa):
-    _cfa(cfa)
-    if len(_shape(frames)) == 2:
+    check_cfa(cfa)
+    if len(shape_of(frames)) == 2:
         frames = frames[None]
-    F, Hm, Wm = _check_mosaics(frames, 3, 'frames', cfa)
+    F, Hm, Wm = check_mosaics(frames, 3, 'frames', cfa)
     if F < 1 or F > MAX_FRAMES:
         raise ValueError('a stack holds 1 to %d frames, got %d' % (MAX_FRAMES, F))
     return frames, F, Hm, Wm
@@ -253,9 +270,9 @@ def deviation(frames, cfa='bayer', raw_pattern=None):
     import torch
     frames, F, Hm, Wm = _check_stack(frames, cfa)
     _, cls = _class_pattern(cfa, raw_pattern)
-    u = _device_u16(frames)
+    u = device_u16(frames)
     D = torch.empty((Hm, Wm), dtype=torch.int32, device=u.device)
-    ws = _ws(L.lib().eld_defect_deviation_workspace_bytes(Hm, Wm), u.device)
+    ws = workspace(L.lib().eld_defect_deviation_workspace_bytes(Hm, Wm), u.device)
     flat = [int(v) for v in cls.reshape(-1)]
     with torch.cuda.device(u.device):
         L.check(L.lib().eld_defect_deviation(L.dptr(u), F, Hm, Wm, cls.shape[0], (ctypes.c_int * len(flat))(*flat), L.dptr(D), L.dptr(ws),
@@ -374,7 +391,7 @@ def manifest_bias(path, session=None):
     if not 0 <= int(session) < len(ss):
         raise ValueError('--session %r: the manifest has sessions 0..%d' % (session, len(ss) - 1))
     bias = np.stack([np.load(os.path.join(base, p)) for p in ss[int(session)]['bias']])
-    return bias, _cfa(m.get('cfa', 'bayer')), m['raw_pattern'], int(session)
+    return bias, check_cfa(m.get('cfa', 'bayer')), m['raw_pattern'], int(session)
 
 
 def main(argv=None):

@@ -28,6 +28,7 @@ import sys
 import numpy as np
 
 from . import _lib as L
+from . import mosaic as M
 
 NB = L.PAIRSTATS_BINS
 STATS = ('n', 'sum_s', 'sum_e', 'sum_e2')
@@ -51,7 +52,6 @@ def bin_lower_edges():
 # ---- the kernel's wrapper ---------------------------------------------------------------------------------------------------------------
 def _cells(cfa, raw_pattern, black_level):
     """-> (period, group per cell, G, black per cell): the groups of validate.group_map_u16, the integer black level of every cell."""
-    from . import calibrate as CAL
     from .denoise import DEFAULT_BLACK, DEFAULT_PATTERN, _check_cfa
     from .validate import group_map_u16
     _check_cfa(cfa)
@@ -67,11 +67,11 @@ def _cells(cfa, raw_pattern, black_level):
             from .defects import xtrans_tables
             raw_pattern = xtrans_tables()['colour']                # the cell the library packs (R 0, G 1, B 2 are valid colour codes)
         p, group, G = group_map_u16('xtrans', raw_pattern)
-        codes = CAL._xpattern(raw_pattern).reshape(-1)
+        codes = M.xtrans_pattern(raw_pattern).reshape(-1)
     else:
         raw_pattern = DEFAULT_PATTERN if raw_pattern is None else raw_pattern
         p, group, G = group_map_u16('bayer', raw_pattern)
-        codes = CAL._pattern(raw_pattern).reshape(-1)
+        codes = M.bayer_pattern(raw_pattern).reshape(-1)
     return p, group, G, [int(b[c]) for c in codes]
 
 
@@ -114,7 +114,6 @@ def pair_level_stats(est_u16, ref_u16, cfa, raw_pattern, black_level, white_poin
     B, G2; X-Trans R, G, B) and signal bin (NB = 61, the last bin holds ref >= white_point) the sums STATS =
     (n, sum s, sum e, sum e^2) with s = ref - black and e = est - ref.  X-Trans counts the whole 6x6 cells only (the borders beyond them
     pass through the write-back untouched); defects: a DefectMap whose flagged sites are not counted."""
-    from . import calibrate as CAL
     p, group, G, black = _cells(cfa, raw_pattern, black_level)
     white = _white(white_point)
     se, sr = _stack(est_u16, 'est_u16'), _stack(ref_u16, 'ref_u16')
@@ -128,8 +127,8 @@ def pair_level_stats(est_u16, ref_u16, cfa, raw_pattern, black_level, white_poin
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'pair_level_stats')
     Hc, Wc = (Hm // p * p, Wm // p * p) if cfa == 'xtrans' else (Hm, Wm)
-    est = CAL._device_u16(est_u16).reshape(F, Hm, Wm)
-    ref = CAL._device_u16(ref_u16).reshape(F, Hm, Wm)
+    est = M.device_u16(est_u16).reshape(F, Hm, Wm)
+    ref = M.device_u16(ref_u16).reshape(F, Hm, Wm)
     if ref.device != est.device:
         raise ValueError('est_u16 is on %s, ref_u16 on %s' % (est.device, ref.device))
     return _level_sums(est, ref, p, group, G, black, white, Hc, Wc, None if defects is None else defects.bitmap_on(ref.device))

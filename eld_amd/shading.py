@@ -32,6 +32,7 @@ import numpy as np
 
 from . import _lib as L
 from . import calibrate as CAL
+from . import mosaic as M
 from .denoise import DEFAULT_BLACK, DEFAULT_PATTERN, _as_u16
 
 MAX_SESSIONS = 16
@@ -70,13 +71,13 @@ def fit_coefficients(isos, weights):
 # ---- argument checks (host only) ----------------------------------------------------------------------------------------------------------
 def _pattern_and_black(cfa, raw_pattern, black_level):
     """-> (raw_pattern as structure.cell_centres takes it, 4 black levels: per packed channel (Bayer) / colour code (X-Trans))."""
-    cfa = CAL._cfa(cfa)
+    cfa = M.check_cfa(cfa)
     if cfa == 'bayer':
-        pat = CAL._pattern(DEFAULT_PATTERN if raw_pattern is None else raw_pattern)
+        pat = M.bayer_pattern(DEFAULT_PATTERN if raw_pattern is None else raw_pattern)
     else:
         from .defects import _class_pattern
         pat = _class_pattern(cfa, raw_pattern)[0]
-        CAL._xpattern(pat)
+        M.xtrans_pattern(pat)
     b = np.asarray(DEFAULT_BLACK[cfa] if black_level is None else black_level, dtype=np.float64).reshape(-1)
     if b.size == 1:
         b = np.repeat(b, 4)
@@ -160,7 +161,7 @@ class DarkShading:
     counts, isos       per session: bias frames and ISO"""
 
     def __init__(self, a, b, x0, iso_min, iso_max, cfa='bayer', raw_pattern=None, centred=False, counts=(), isos=()):
-        self.cfa = CAL._cfa(cfa)
+        self.cfa = M.check_cfa(cfa)
         a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
         if a.ndim != 2 or a.shape != b.shape or a.size == 0:
             raise ValueError('a and b are two float32 planes of one shape (Hm, Wm), got %s and %s' % (a.shape, b.shape))
@@ -180,7 +181,7 @@ class DarkShading:
 
     @property
     def period(self):
-        return 2 if self.cfa == 'bayer' else CAL.XT_PERIOD
+        return 2 if self.cfa == 'bayer' else M.XT_PERIOD
 
     def t(self, iso, extrapolate=False):
         """float32(iso - x0): the abscissa the kernels take.  ValueError for an ISO outside [iso_min, iso_max] unless extrapolate=True
@@ -211,7 +212,7 @@ class DarkShading:
 
     def check_pattern(self, raw_pattern, what='frames'):
         """ValueError when a Bayer raw_pattern is given that is not the map's (None: not compared)."""
-        if raw_pattern is not None and self.cfa == 'bayer' and not np.array_equal(CAL._pattern(raw_pattern), self.raw_pattern):
+        if raw_pattern is not None and self.cfa == 'bayer' and not np.array_equal(M.bayer_pattern(raw_pattern), self.raw_pattern):
             raise ValueError('%s: the dark-shading map was fitted under raw_pattern %r, got %r'
                              % (what, self.raw_pattern.tolist(), np.asarray(raw_pattern).tolist()))
 
@@ -253,7 +254,7 @@ class DarkShading:
             if not hasattr(out, 'is_cuda') or not out.is_cuda or out.dtype != mosaics.dtype or tuple(out.shape) != shape or not out.is_contiguous() \
                     or out.device != mosaics.device:
                 raise ValueError('out must be a contiguous CUDA tensor of the shape, type and device of the mosaics')
-        t = CAL._device_u16(mosaics)
+        t = M.device_u16(mosaics)
         if out is not None and out.data_ptr() == mosaics.data_ptr() and t.data_ptr() != mosaics.data_ptr():
             raise ValueError('in-place correction needs contiguous, 4-byte aligned mosaics')
         o = self.apply_device(t.reshape((-1,) + self.shape), tval, defects, None if out is None else out.reshape((-1,) + self.shape))
@@ -319,7 +320,7 @@ def fit_dark_shading(sessions, cfa='bayer', raw_pattern=None, black_level=None, 
     weights      one positive weight per session (default: its frame count, which makes the fit the least-squares line over all frames).
     centred      take the mean over the unflagged sites of every cell of the CFA pattern out of both planes (see the module text).
     Bad arguments raise ValueError before any device work; the fit itself needs a GPU."""
-    cfa = CAL._cfa(cfa)
+    cfa = M.check_cfa(cfa)
     pat, black = _pattern_and_black(cfa, raw_pattern, black_level)
     frames, ranges, isos = _sessions(sessions)
     w = _weights(weights, ranges)

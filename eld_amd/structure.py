@@ -13,7 +13,8 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
-from . import calibrate as CAL
+from . import mosaic as M
+from .defects import check_defects
 
 
 def _groups(cfa, raw_pattern):
@@ -26,11 +27,11 @@ def _groups(cfa, raw_pattern):
 def cell_centres(cfa, raw_pattern, black_level):
     """The integer centre of every cell of the pattern, (p,p) int64: rint(black) of the cell's packed channel (Bayer) or colour code
     (X-Trans), clipped to the code range."""
-    b = np.rint(CAL._black(black_level)).astype(np.int64)
-    if CAL._cfa(cfa) == 'xtrans':
-        cells = b[CAL._xpattern(raw_pattern)]
+    b = np.rint(M.black_levels(black_level)).astype(np.int64)
+    if M.check_cfa(cfa) == 'xtrans':
+        cells = b[M.xtrans_pattern(raw_pattern)]
     else:
-        cells = b[CAL._pattern(raw_pattern)]
+        cells = b[M.bayer_pattern(raw_pattern)]
     return np.clip(cells, 0, 65535)
 
 
@@ -65,11 +66,11 @@ def structure_sums(frames, cfa, raw_pattern, centre, defects=None, pairs=None):
     cen = (ctypes.c_int32 * (p * p))(*_centre(centre, p))
     q = _pairs(pairs, F)
     if defects is not None:
-        defects = CAL._check_defects(defects, cfa, (Hm, Wm), raw_pattern if cfa == 'xtrans' else None)
+        defects = check_defects(defects, cfa, (Hm, Wm), raw_pattern if cfa == 'xtrans' else None)
         if isinstance(defects, str):
             raise ValueError("structure_sums takes a DefectMap, not 'auto'")
     import torch
-    u = CAL._device_u16(frames)
+    u = M.device_u16(frames)
     bm = None if defects is None else defects.bitmap_on(u.device)
     row = torch.empty((F, Hm, p, 2), dtype=torch.int64, device=u.device)
     col = torch.empty((F, Wm, p, 2), dtype=torch.int64, device=u.device)

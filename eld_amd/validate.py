@@ -25,6 +25,8 @@ import numpy as np
 
 from . import _lib as L
 from . import calibrate as CAL
+from . import mosaic as M
+from .defects import check_defects
 from .noise import NoiseParams, model_flags, table_cfa
 
 MODEL_LETTERS = 'PpgGRUBD'
@@ -61,14 +63,14 @@ def _models(models):
 def group_map_u16(cfa, raw_pattern):
     """-> (period, groups: p*p ints, G).  Bayer: cell (r, c) -> the packed channel raw_pattern[r][c] (R, G1, B, G2), G = 4;
     X-Trans: cell -> the colour (R 0, G 1, B 2) of its colour code, G = 3."""
-    if CAL._cfa(cfa) == 'xtrans':
-        return CAL.XT_PERIOD, [int(v) for v in CAL.CODE_COLOUR[CAL._xpattern(raw_pattern)].reshape(-1)], 3
-    return 2, [int(v) for v in CAL._pattern(raw_pattern).reshape(-1)], 4
+    if M.check_cfa(cfa) == 'xtrans':
+        return M.XT_PERIOD, [int(v) for v in M.CODE_COLOUR[M.xtrans_pattern(raw_pattern)].reshape(-1)], 3
+    return 2, [int(v) for v in M.bayer_pattern(raw_pattern).reshape(-1)], 4
 
 
 def group_map_f32(cfa):
     """-> (C, groups: C ints, G).  Bayer: plane c -> group c; X-Trans: planes 0, 3 -> R, 1, 5-8 -> G, 2, 4 -> B."""
-    if CAL._cfa(cfa) == 'xtrans':
+    if M.check_cfa(cfa) == 'xtrans':
         return 9, list(XT_PLANE_COLOUR), 3
     return 4, [0, 1, 2, 3], 4
 
@@ -76,7 +78,7 @@ def group_map_f32(cfa):
 def group_black(cfa, black_level):
     """The integer centre of each histogram group: rint(black) of the packed channel (Bayer) or of the colour (X-Trans, whose two green
     codes must share one rounded black level: a group has one centre)."""
-    b = np.rint(CAL._black(black_level)).astype(np.int64)
+    b = np.rint(M.black_levels(black_level)).astype(np.int64)
     if cfa == 'xtrans':
         if b[1] != b[3]:
             raise ValueError('X-Trans: the two green colour codes have black levels %d and %d; a histogram group has one centre' % (b[1], b[3]))
@@ -123,7 +125,7 @@ def kl_divergence(p_counts, q_counts, alpha=1.0):
 
 # ---- histograms (device) ---------------------------------------------------------------------------------------------------------------
 def _check_frames(x, what):
-    s = CAL._shape(x)
+    s = M.shape_of(x)
     if len(s) != 3:
         raise ValueError('%s: expected (F, Hm, Wm), got shape %s' % (what, s))
     if s[2] % 2:
@@ -149,7 +151,7 @@ def histogram_u16(frames, cfa, raw_pattern, centre, radius, subtract=None, defec
     F, Hm, Wm = _check_frames(frames, 'frames')
     if subtract is not None:
         if _check_frames(subtract, 'subtract') != (F, Hm, Wm):
-            raise ValueError('subtract has shape %s, the frames %s' % (CAL._shape(subtract), (F, Hm, Wm)))
+            raise ValueError('subtract has shape %s, the frames %s' % (M.shape_of(subtract), (F, Hm, Wm)))
         cen = None
     else:
         c = np.asarray(centre if centre is not None else [], dtype=np.float64).reshape(-1)
@@ -157,12 +159,12 @@ def histogram_u16(frames, cfa, raw_pattern, centre, radius, subtract=None, defec
             raise ValueError('centre must hold %d integers (one per group), got %r' % (G, centre))
         cen = (ctypes.c_int32 * G)(*[int(v) for v in c])
     if defects is not None:
-        defects = CAL._check_defects(defects, cfa, (Hm, Wm), raw_pattern if cfa == 'xtrans' else None)
+        defects = check_defects(defects, cfa, (Hm, Wm), raw_pattern if cfa == 'xtrans' else None)
         if isinstance(defects, str):
             raise ValueError("histogram_u16 takes a DefectMap, not 'auto'")
     import torch
-    u = CAL._device_u16(frames)
-    v = None if subtract is None else CAL._device_u16(subtract)
+    u = M.device_u16(frames)
+    v = None if subtract is None else M.device_u16(subtract)
     counts = torch.empty((F, G, 2 * R + 1), dtype=torch.int64, device=u.device)
     bm = None if defects is None else defects.bitmap_on(u.device)
     L.check(L.lib().eld_hist_u16(L.dptr(u), L.dptr(v), F, Hm, Wm, p, (ctypes.c_int * (p * p))(*groups), G, cen, R, L.dptr(bm), L.dptr(counts),
@@ -244,10 +246,10 @@ def synthesize_codes(clean, params, model, cfa, seed, sample_id, white, black, s
     params: a NoiseParams / dict (K, g_scale, tl_lambda, tl_scale, row_scale, color_bias, in DN); the sampler runs with ratio = 1,
     saturation = white - max(black) and q_step = 1.  black: per packed channel (Bayer) or per colour code (X-Trans)."""
     import torch
-    CAL._cfa(cfa)
+    M.check_cfa(cfa)
     _models([model])
-    b = np.rint(CAL._black(black))
-    sat = float(white) - float(np.max(CAL._black(black)))
+    b = np.rint(M.black_levels(black))
+    sat = float(white) - float(np.max(M.black_levels(black)))
     if not sat > 0:
         raise ValueError('white level %r does not exceed the black level' % (white,))
     C = group_map_f32(cfa)[0]
@@ -283,13 +285,13 @@ def clean_from_flat_pair(a, b, cfa, raw_pattern, black_level, color_bias, sat):
     import torch
     from .noise import RawPacker
     m = ((a.to(torch.int32) & 0xffff).float() + (b.to(torch.int32) & 0xffff).float()) * 0.5
-    blk = CAL._black(black_level)
+    blk = M.black_levels(black_level)
     if cfa == 'xtrans':
         planes = RawPacker('xtrans').pack_raw_xtrans(m)
         col = list(XT_PLANE_COLOUR)
         bl, cb = blk[col], np.asarray(color_bias, np.float64).reshape(-1)[:3][col]
     else:
-        pat = CAL._pattern(raw_pattern)
+        pat = M.bayer_pattern(raw_pattern)
         pos = [np.argwhere(pat == c)[0] for c in range(4)]
         planes = torch.stack([m[int(r)::2, int(q)::2] for r, q in pos]).contiguous()
         bl, cb = blk, np.asarray(color_bias, np.float64).reshape(-1)[:4]
@@ -331,10 +333,10 @@ def _check_session_shapes(sessions, cfa):
         for k in ('bias', 'flats'):
             if k not in s:
                 raise ValueError('session %d has no %r' % (i, k))
-        F, Hm, Wm = CAL._check_mosaics(s['bias'], 3, 'session %d bias' % i, cfa)
-        P = CAL._check_mosaics(s['flats'], 4, 'session %d flats' % i, cfa)[0]
+        F, Hm, Wm = M.check_mosaics(s['bias'], 3, 'session %d bias' % i, cfa)
+        P = M.check_mosaics(s['flats'], 4, 'session %d flats' % i, cfa)[0]
         shape = shape or (Hm, Wm)
-        if (Hm, Wm) != shape or CAL._shape(s['flats'])[-2:] != shape:
+        if (Hm, Wm) != shape or M.shape_of(s['flats'])[-2:] != shape:
             raise ValueError('session %d: mosaic shapes differ' % i)
         if F == 0 or P == 0:
             raise ValueError('session %d: needs at least one bias frame and one flat pair' % i)
@@ -372,7 +374,7 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     draws from are corrected the same way, so the report shows the fixed components with the correction applied, next to the models.  The
     flats, and the calibration that runs here without a diag, see the frames as they are.  Every session then needs an 'iso' inside the
     map's range (ValueError).  report['shading'] records x0 and the ISO range."""
-    cfa = CAL._cfa(cfa)
+    cfa = M.check_cfa(cfa)
     models = _models(models)
     R, RF = _radius(radius), _radius(flat_radius, 'flat_radius')
     if source not in ('frames', 'table'):
@@ -384,11 +386,11 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         lags = ST._lags(lags)
     if table is not None and any('B' in m for m in models) and table_cfa(table) != cfa:
         raise ValueError('the table is for cfa=%r, the frames are %r: its colour bias does not apply (model with B)' % (table_cfa(table), cfa))
-    CAL._xpattern(raw_pattern) if cfa == 'xtrans' else CAL._pattern(raw_pattern)
-    black = CAL._black(black_level)
-    CAL._check_defects(defects, cfa, raw_pattern=raw_pattern)
+    M.xtrans_pattern(raw_pattern) if cfa == 'xtrans' else M.bayer_pattern(raw_pattern)
+    black = M.black_levels(black_level)
+    check_defects(defects, cfa, raw_pattern=raw_pattern)
     if diag is None:
-        CAL._check_sessions(sessions, cfa)                 # a calibration runs here: its session and frame counts apply
+        M.check_sessions(sessions, cfa)                 # a calibration runs here: its session and frame counts apply
     else:
         _check_session_shapes(sessions, cfa)
     if len(sessions) >= 1 << 20:
@@ -396,20 +398,20 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     with_dark = any('D' in m for m in models)
     if with_dark:
         for i, s in enumerate(sessions):
-            if CAL._shape(s['bias'])[0] < 2:
+            if M.shape_of(s['bias'])[0] < 2:
                 raise ValueError('session %d has a single bias frame: a model with D draws from the OTHER bias frames of the session' % i)
     centre = group_black(cfa, black)
     sat = float(white_level) - float(black.max())
     if not sat > 0:
         raise ValueError('white level %r does not exceed the black level' % (white_level,))
     if defects is not None and not isinstance(defects, str):
-        defects.check_frames(CAL._shape(sessions[0]['bias']), cfa, 'validation')
+        defects.check_frames(M.shape_of(sessions[0]['bias']), cfa, 'validation')
     if shading is not None:
         from .shading import as_dark_shading
         shading = as_dark_shading(shading)
         shading.check_pattern(None if cfa == 'xtrans' else raw_pattern, 'validation')
         for i, s in enumerate(sessions):
-            shading.check_frames(CAL._shape(s['bias']), cfa, 'session %d bias' % i)
+            shading.check_frames(M.shape_of(s['bias']), cfa, 'session %d bias' % i)
             if s.get('iso') is None:
                 raise ValueError("session %d has no 'iso': the dark-shading map is subtracted at the session's ISO" % i)
             shading.t(s['iso'])
@@ -432,7 +434,7 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         if len(diag['K']) != len(sessions):
             raise ValueError("diag['K'] holds %d gains for %d sessions" % (len(diag['K']), len(sessions)))
     else:
-        nb = sum(CAL._shape(s['bias'])[0] for s in sessions)
+        nb = sum(M.shape_of(s['bias'])[0] for s in sessions)
         if 'frames' not in diag or len(diag['frames']) != nb:
             raise ValueError("source='frames' needs diag['frames'] with one record per bias frame (%d)" % nb)
 
@@ -452,12 +454,12 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         bl = np.rint(black)
     j0 = 0
     for si, s in enumerate(sessions):
-        bias = CAL._device_u16(s['bias'])
+        bias = M.device_u16(s['bias'])
         if shading is not None:
             bias = shading.apply_device(bias, shading.t(s['iso']), None if isinstance(defects, str) else defects)
-        flats = CAL._device_u16(s['flats'])
-        F, Hm, Wm = CAL._shape(bias)
-        P = CAL._shape(flats)[0]
+        flats = M.device_u16(s['flats'])
+        F, Hm, Wm = M.shape_of(bias)
+        P = M.shape_of(flats)[0]
         h, w = (2 * (Hm // 6), 2 * (Wm // 6)) if cfa == 'xtrans' else (Hm // 2, Wm // 2)
         if source == 'table':
             fparams = [_table_params(table, float(diag['K'][si]), ncb)] * F

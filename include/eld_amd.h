@@ -288,8 +288,9 @@ size_t eld_calib_ppcc_workspace_bytes(int F, size_t n, int L);
 int eld_calib_ppcc(const float* t_sorted, int F, size_t n, const float* lambdas, int L, double* sums, double* tsums, void* ws, size_t ws_bytes, void* stream);
 /* Cell statistics of a mosaic pattern of period p (2 or 6; anything else is ELD_EINVAL), for any CFA (X-Trans: p = 6).  They know
  * nothing about colours: cell (r, c) is the set of pixels (y, x) with y % p == r, x % p == c, and the host folds cells into colours.
- * Same rules as the Bayer passes above: exact integer sums, fixed reduction order, 4-byte aligned `u` / `ab`, Wm even; Hm and Wm
- * need not be multiples of p.
+ * The Bayer entry points above are these passes at p = 2, with the cells stored in the channel order of raw_pattern (and the Bayer
+ * argument rules: even Hm, a permutation pattern).  Same rules here: exact integer sums, fixed reduction order, 4-byte aligned `u` /
+ * `ab`, Wm even; Hm and Wm need not be multiples of p.
  *
  * cell_sums[F][p][p][2] = (sum u, sum u^2) per frame and cell; row_sums[F][Hm][p] = sum u over the columns x % p == c of each row.
  * Workspace: eld_calib_cell_stats_workspace_bytes(F, Hm, p). */

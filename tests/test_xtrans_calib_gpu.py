@@ -9,6 +9,7 @@ import pytest
 from eld_amd import _lib as L
 from eld_amd import calibrate as CAL
 
+from test_calib_cpu import PATTERNS, flat_sums_ref, sums_ref
 from xtrans_ref import CODE_COLOUR, cell_flat_sums_ref, cell_sums_ref, colour_map, fold_bayer, xtrans_pattern
 
 pytestmark = pytest.mark.gpu
@@ -90,19 +91,58 @@ def test_odd_element_view_gives_the_same_sums(eld_lib):
                           cell_flat_sums_ref(ab, 6, 16383))
 
 
-@pytest.mark.parametrize('shape', [(130, 98), (64, 96), (2, 2)])
-def test_period_two_folds_to_the_bayer_passes(eld_lib, shape):
-    rng = np.random.default_rng(shape[0])
+def bayer_abi(u, pattern, white=None, residual=None):
+    """The Bayer entry points, raw, on a CUDA int16 tensor: (F,Hm,Wm) bias -> (chan_sums, row_sums), or with residual=(black, cb, rho)
+    the float32 residuals; (P,2,Hm,Wm) flats with white -> sums."""
+    torch = _torch()
+    lib, pat = L.lib(), (ctypes.c_int * 4)(*[int(v) for v in np.asarray(pattern).reshape(-1)])
+    if white is not None:
+        P, _, Hm, Wm = u.shape
+        out = torch.empty((P, 4, 4), dtype=torch.int64, device='cuda')
+        ws = torch.empty(max(1, lib.eld_calib_flat_stats_workspace_bytes(P, Hm)), dtype=torch.uint8, device='cuda')
+        L.check(lib.eld_calib_flat_stats(L.dptr(u), P, Hm, Wm, pat, int(white), L.dptr(out), L.dptr(ws), ws.numel(), L.cur_stream()))
+        return out.cpu().numpy()
+    F, Hm, Wm = u.shape
+    if residual is not None:
+        black, cb, rho = residual
+        t = torch.empty((F, Hm * Wm), dtype=torch.float32, device='cuda')
+        cbd, rhod = torch.from_numpy(cb).cuda(), torch.from_numpy(rho).cuda()
+        L.check(lib.eld_calib_bias_residual(L.dptr(u), F, Hm, Wm, pat, (ctypes.c_double * 4)(*black.tolist()), L.dptr(cbd), L.dptr(rhod),
+                                            L.dptr(t), L.cur_stream()))
+        return t.cpu().numpy()
+    cs = torch.empty((F, 4, 2), dtype=torch.int64, device='cuda')
+    rs = torch.empty((F, Hm, 2), dtype=torch.int64, device='cuda')
+    ws = torch.empty(max(1, lib.eld_calib_bias_stats_workspace_bytes(F, Hm)), dtype=torch.uint8, device='cuda')
+    L.check(lib.eld_calib_bias_stats(L.dptr(u), F, Hm, Wm, pat, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), L.cur_stream()))
+    return cs.cpu().numpy(), rs.cpu().numpy()
+
+
+@pytest.mark.parametrize('shape', [(2, 2), (130, 2), (66, 98), (64, 96), (130, 98)])
+@pytest.mark.parametrize('pattern', PATTERNS)
+def test_period_two_folds_to_the_bayer_passes(eld_lib, shape, pattern):
+    # (2, 2): one word, tail lanes only; (66, 98) and (130, 98): the scalar path (Wm % 8 != 0); (64, 96): the 16-byte path, 12 groups.
+    # Two frames / two pairs: the frame stride counts.  The Bayer entry points are called raw: the module no longer enters them.
+    rng = np.random.default_rng(shape[0] + 1000 * PATTERNS.index(pattern))
     Hm, Wm = shape
-    pattern = [[0, 1], [3, 2]]
     u = rng.integers(0, 65536, (2, Hm, Wm), dtype=np.uint16)
     cs, rs = cell_abi(_dev(u), 2)
     assert np.array_equal(cs, cell_sums_ref(u, 2)[0]) and np.array_equal(rs, cell_sums_ref(u, 2)[1])
     bs = CAL.bias_frame_stats(u, pattern, [0.0] * 4)
     assert np.array_equal(fold_bayer(cs, pattern), bs['chan_sums']) and np.array_equal(rs, bs['row_sums'])
+    bcs, brs = bayer_abi(_dev(u), pattern)
+    assert np.array_equal(bcs, sums_ref(u, pattern)[0]) and np.array_equal(brs, sums_ref(u, pattern)[1])
+    white = 16383
     ab = rng.integers(0, 65536, (2, 2, Hm, Wm), dtype=np.uint16)
-    fl = cell_abi(_dev(ab), 2, white=16383)
-    assert np.array_equal(fold_bayer(fl, pattern), CAL.flat_pair_stats(ab, pattern, [0.0] * 4, 16383, [0.0] * 4)['sums'])
+    ab[1] = np.clip(rng.normal(3000, 50, (2, Hm, Wm)), 0, 65535).astype(np.uint16)
+    ab[1, 0, 0, 0], ab[1, 1, -1, -1] = 16383, 65535             # a saturated pixel; the largest code in the last pixel of the second frame
+    fl = cell_abi(_dev(ab), 2, white=white)
+    assert np.array_equal(fold_bayer(fl, pattern), CAL.flat_pair_stats(ab, pattern, [0.0] * 4, white, [0.0] * 4)['sums'])
+    assert np.array_equal(bayer_abi(_dev(ab), pattern, white=white), flat_sums_ref(ab, pattern, white))
+    black = np.array([512.0, 511.0, 513.5, 509.0])
+    cb, rho = rng.normal(0.0, 2.0, (2, 4)), rng.normal(0.0, 1.0, (2, Hm))
+    ch = np.asarray(pattern)[np.arange(Hm)[:, None] & 1, np.arange(Wm)[None, :] & 1]
+    t_np = (((u.astype(np.float64) - black[ch][None]) - cb[:, ch]) - rho[:, :, None]).astype(np.float32)
+    assert np.array_equal(bayer_abi(_dev(u), pattern, residual=(black, cb, rho)), t_np.reshape(2, -1))
 
 
 # ---- 5. closed loop on the sampler -------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 bound (ppcc_bound) and torch.sort's time.  One JSON line at the end (profiles/calib_bench.json is one such run).
 
     python tools/calib_bench.py [--reps 5] [--isos 9] [--out FILE]
+    python tools/calib_bench.py --cfa xtrans | --cfa bayer2      (the cell passes against the Bayer entry points)
 """
 import argparse
 import ctypes
@@ -144,16 +145,70 @@ def bench_cells(F, Hm, Wm, reps):
     return res
 
 
+BAYER_ENTRIES = ('eld_calib_bias_stats', 'eld_calib_bias_residual', 'eld_calib_flat_stats')
+
+
+def bench_bayer2(F, Hm, Wm, P, reps, rounds=5, bayer=BAYER_ENTRIES):
+    """--cfa bayer2: each pixel pass through its Bayer entry point and through the period-2 cell entry point on the same mosaics, `rounds`
+    alternations of the median of `reps`.  Per pass: both medians, cell / bayer, and the spread (max / min) of the Bayer entry's own
+    medians -- the margin inside which the two count as equal.  `bayer` names the three Bayer entries (a build that keeps other kernels
+    under other names for an A/B passes them here; _lib's argument table must know them)."""
+    lib = L.lib()
+    f_stats, f_res, f_flat = (getattr(lib, n) for n in bayer)
+    u = frames(F, Hm, Wm, 7)
+    ab = frames(2 * P, Hm, Wm, 8).view(P, 2, Hm, Wm)
+    pat = (ctypes.c_int * 4)(0, 1, 3, 2)
+    blk4 = (ctypes.c_double * 4)(512.0, 511.0, 513.0, 510.0)
+    blkc = (ctypes.c_double * 4)(512.0, 511.0, 510.0, 513.0)             # black_level[pattern[k]]
+    i64 = lambda *shape: torch.empty(shape, dtype=torch.int64, device='cuda')   # noqa: E731
+    cs, rs, fo = i64(F, 4, 2), i64(F, Hm, 2), i64(P, 4, 4)
+    ws = torch.empty(lib.eld_calib_bias_stats_workspace_bytes(F, Hm), dtype=torch.uint8, device='cuda')
+    fws = torch.empty(lib.eld_calib_flat_stats_workspace_bytes(P, Hm), dtype=torch.uint8, device='cuda')
+    cb = torch.rand((F, 4), dtype=torch.float64, device='cuda')
+    rho = torch.rand((F, Hm), dtype=torch.float64, device='cuda')
+    t = torch.empty((F, Hm * Wm), dtype=torch.float32, device='cuda')
+    st = L.cur_stream()
+    calls = {
+        'bias_stats': (lambda: L.check(f_stats(L.dptr(u), F, Hm, Wm, pat, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), st)),
+                       lambda: L.check(lib.eld_calib_cell_stats(L.dptr(u), F, Hm, Wm, 2, L.dptr(cs), L.dptr(rs), L.dptr(ws), ws.numel(), st)),
+                       2.0 * F * Hm * Wm),
+        'residual': (lambda: L.check(f_res(L.dptr(u), F, Hm, Wm, pat, blk4, L.dptr(cb), L.dptr(rho), L.dptr(t), st)),
+                     lambda: L.check(lib.eld_calib_cell_residual(L.dptr(u), F, Hm, Wm, 2, blkc, L.dptr(cb), L.dptr(rho), L.dptr(t), st)),
+                     6.0 * F * Hm * Wm),
+        'flat_stats': (lambda: L.check(f_flat(L.dptr(ab), P, Hm, Wm, pat, 16383, L.dptr(fo), L.dptr(fws), fws.numel(), st)),
+                       lambda: L.check(lib.eld_calib_cell_flat_stats(L.dptr(ab), P, Hm, Wm, 2, 16383, L.dptr(fo), L.dptr(fws), fws.numel(), st)),
+                       4.0 * P * Hm * Wm),
+    }
+    res = {'mosaic': [F, Hm, Wm], 'pairs': P, 'reps': reps, 'rounds': rounds, 'bayer_entries': list(bayer)}
+    for name, (fa, fb, byt) in calls.items():
+        fa(), fb()                                           # warm-up: code objects loaded
+        ta, tb = [], []
+        for _ in range(rounds):                              # interleaved A/B
+            ta.append(timed(fa, reps))
+            tb.append(timed(fb, reps))
+        ma, mb = float(np.median(ta)), float(np.median(tb))
+        res[name] = {'bayer_ms': ma * 1e3, 'cell2_ms': mb * 1e3, 'cell2_over_bayer': mb / ma, 'bayer_spread': max(ta) / min(ta),
+                     'bayer_GBps': byt / ma / 1e9, 'cell2_GBps': byt / mb / 1e9,
+                     'bayer_medians_ms': [1e3 * v for v in ta], 'cell2_medians_ms': [1e3 * v for v in tb]}
+    print(json.dumps(res))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--cfa', choices=['bayer', 'xtrans'], default='bayer',
-                    help='xtrans: time the cell statistics (p = 6) against the Bayer bias statistics on 4 frames of 4158 x 6240')
+    ap.add_argument('--cfa', choices=['bayer', 'xtrans', 'bayer2'], default='bayer',
+                    help='xtrans: time the cell statistics (p = 6) against the Bayer bias statistics on 4 frames of 4158 x 6240; '
+                         'bayer2: time each pass through its Bayer entry point against the period-2 cell entry point')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--isos', type=int, default=9)
     ap.add_argument('--out', help='also write the JSON result here')
     a = ap.parse_args()
     if a.cfa == 'xtrans':
         bench_cells(4, 4158, 6240, a.reps)
+        return
+    if a.cfa == 'bayer2':
+        bench_bayer2(2, 2848, 4256, 8, a.reps)
+        bench_bayer2(2, 5520, 8288, 2, a.reps)
         return
     L.load_library()
     lam = CAL.DEFAULT_LAMBDAS
