@@ -13,12 +13,15 @@ SHOT_POISSON, SHOT_GAUSS, READ_GAUSS, READ_TL, ROW, QUANT, CBIAS, CLIP = 1, 2, 4
 AUG_NOTRANSPOSE = 256
 CFA_XTRANS = 512
 DARK = 1024             # 'D': signal-independent noise read from a pool of dark frames (eld_noise_forward_dark only)
+COL = 2048              # 'C': per-sensor-column Gaussian; its scale travels as the float bits of EldNoiseParams.reserved[0]
 IN_F32, IN_U16 = 0, 1
 ROUND_TRUNC, ROUND_NEAREST, ROUND_TRUNC_F32 = 0, 1, 2      # write-back rounding (eld_unpack_raw_*_u16)
 RENDER_SRGB8, RENDER_LINEAR_F32 = 0, 1                      # out_mode of eld_render_bayer / eld_render_xtrans
 NPLANES = 6
 PAIRSTATS_BINS = 61                                           # ELD_PAIRSTATS_BINS
 PLANE = {'counts': 0, 'n_shot': 1, 'n_read': 2, 't_tl': 3, 'n_row': 4, 'u_q': 5}
+PLANE_NCOL = 6          # ELD_PLANE_NCOL: the column normal; the inject / dump buffers hold NPLANES_COL planes when COL is in the flags
+NPLANES_COL = 7
 
 # numpy mirror of struct EldNoiseParams (64 bytes)
 NOISE_PARAMS_DTYPE = np.dtype([

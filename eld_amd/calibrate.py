@@ -14,7 +14,10 @@ can synthesise its noise.  The estimators are the contract of DESIGN.md, "Calibr
 X-Trans (cfa='xtrans'): raw_pattern is rawpy's 6x6 raw_pattern, the pixel passes return per-cell sums (eld_calib_cell_*) that the host
 folds into the colours R, G, B; the table gains 'cfa': 'xtrans' and a (m, 3) color_bias in (R, G, B) order.
 
-Command line: python -m eld_amd.calibrate manifest.json --camera NAME --out DIR (the manifest format is in INTEGRATION.md).
+column=True (--column) adds the law of the per-sensor-column term, model letter C: per bias frame C_scale = sqrt(col_var_sensor) of
+eld_amd.structure, regressed over log K like the other scales into 'Profile-1'['C_scale'].
+
+Command line: python -m eld_amd.calibrate manifest.json --camera NAME --out DIR [--column] (the manifest format is in INTEGRATION.md).
 """
 import argparse
 import ctypes
@@ -32,6 +35,7 @@ from .mosaic import (CODE_COLOUR, XT_PERIOD, bayer_pattern, black_levels, cell_c
 DEFAULT_LAMBDAS = np.linspace(-1.0, 1.0, 141)     # scipy.stats.ppcc_plot(x, -1, 1, N=141): every shipped G_shape lies on it
 PROFILE = 'Profile-1'
 SIGMA_KEYS = ('G_scale', 'R_scale', 'g_scale')
+COLUMN_KEY = 'C_scale'                            # the optional fourth regression (calibrate_camera(column=True)): no release table has it
 
 
 # ---- host derivations from the exact sums ------------------------------------------------------------------------------------
@@ -288,20 +292,26 @@ def ptc_gain(mu, var, usable, what='session'):
 
 def params_from_samples(frames, Ks):
     """Per-frame samples (dicts with K, lambda, G_scale, R_scale, g_scale, color_bias) and the session gains -> the release-schema
-    table."""
+    table.  Where every sample also has 'C_scale' (calibrate_camera(column=True)) 'Profile-1' gains the 'C_scale' regression."""
     if len(frames) < 3:
         raise ValueError('at least 3 bias frames are needed for the log-linear fits, got %d' % len(frames))
     for j, fr in enumerate(frames):
         if not fr['R_scale'] > 0:
             raise ValueError('bias frame %d (iso %s): the row-noise sample is 0 (no log): the row offsets do not exceed the read noise '
                              'averaged into them' % (j, fr.get('iso')))
+    keys = SIGMA_KEYS + ((COLUMN_KEY,) if frames and all(COLUMN_KEY in fr for fr in frames) else ())
+    if COLUMN_KEY in keys:
+        for j, fr in enumerate(frames):
+            if not fr[COLUMN_KEY] > 0:
+                raise ValueError('bias frame %d (iso %s): the column-noise sample is not positive (no log): the two row phases of the sensor '
+                                 'columns share no offset beyond chance; drop --column (column=True) for this camera' % (j, fr.get('iso')))
     if len(set(float(k) for k in Ks)) < 2:
         raise ValueError('the sessions give fewer than 2 distinct K: the log-linear fits need a range of gains')
     Kf = np.array([fr['K'] for fr in frames], np.float64)
     return {'Kmin': np.float64(min(Ks)), 'Kmax': np.float64(max(Ks)),
             'G_shape': np.array([fr['lambda'] for fr in frames], dtype=np.float64),
             'color_bias': np.array([fr['color_bias'] for fr in frames], dtype=np.float32).reshape(len(frames), -1),
-            PROFILE: {k: fit_log_linear(Kf, [fr[k] for fr in frames]) for k in SIGMA_KEYS}}
+            PROFILE: {k: fit_log_linear(Kf, [fr[k] for fr in frames]) for k in keys}}
 
 
 def _ols(x, y):
@@ -440,7 +450,34 @@ def fit_log_linear(K, sigma):
     return {'slope': np.float64(slope), 'bias': np.float64(bias), 'sigma': np.float64(np.sqrt(np.sum(res * res) / (x.size - 2)))}
 
 
-def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None, cfa='bayer', defects=None):
+def column_samples(bias, cfa, raw_pattern, black_level, defects=None):
+    """The column term of one session's bias frames (F,Hm,Wm), from the exact sums of eld_amd.structure (centre = the rounded black level of
+    each cell; the flagged sites of `defects` contribute nothing) -> (samples, fixed): samples (F,) = col_var_sensor per frame, the
+    covariance over the sensor columns of the column means of two row phases (white noise and the row term cancel: what is left is what the
+    rows of a column share, the variance C_scale^2 models); fixed = None for a single frame, else {'col_var', 'col_fixed_var',
+    'fixed_share'}: the session's mean column variance, the part of it that two frames share (mean over all frame pairs) and their ratio --
+    near 1 a dark-shading map would remove the term, near 0 it is temporal and only the model letter C describes it."""
+    from . import structure as ST
+    F = shape_of(bias)[0]
+    pairs = [(a, b) for a in range(F) for b in range(a + 1, F)]
+    sums = ST.structure_sums(bias, cfa, raw_pattern, ST.cell_centres(cfa, raw_pattern, black_level), defects=defects, pairs=pairs)
+    return column_samples_from_sums(sums, cfa, raw_pattern)
+
+
+def column_samples_from_sums(sums, cfa, raw_pattern):
+    """Host half of column_samples: the sums of structure_sums (or their restatement) -> (samples, fixed)."""
+    from . import structure as ST
+    st = ST.structure_stats(sums, cfa, raw_pattern, lags=1)
+    samples = np.array([fr['col_var_sensor'] for fr in st['frames']], np.float64)
+    fixed = None
+    if st['pairs']:
+        sm = ST.summarise(st)
+        cv, cf = sm['col_var'], sm['col_fixed_var']
+        fixed = {'col_var': cv, 'col_fixed_var': cf, 'fixed_share': float(cf / cv) if cv is not None and cf is not None and cv > 0 else None}
+    return samples, fixed
+
+
+def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=None, cfa='bayer', defects=None, column=False):
     """Sessions of bias frames and flat pairs (or, in a session without 'flats', 'bursts': stacks (N,Hm,Wm) of a static scene whose gain is
     eld_amd.burst.burst_gain over the session's bursts; bursts next to flats are reported as diag['ptc'][i]['burst']) -> (params, diagnostics).  params has exactly the release schema
     (Kmin, Kmax, G_shape (m,), color_bias (m,4) float32, 'Profile-1': {G_scale, R_scale, g_scale: {slope, bias, sigma}}), one G_shape /
@@ -451,7 +488,11 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
     offsets, g_scale, R_scale, the residuals of the PPCC, the flat-pair sums and their saturation count); 'auto' finds the map first from
     the bias frames of the lowest-ISO session (find_defects with its defaults) and returns it as diag['defects'].  X-Trans maps exist for
     the pattern phase the library packs only (row 0 = R B G B R G): another 6x6 raw_pattern with defects set is a ValueError.  None (default): every
-    site counts, as before."""
+    site counts, as before.
+    column=True: every frame sample gains 'C_scale' = sqrt(col_var_sensor) (column_samples), the table 'Profile-1'['C_scale'] by the same
+    regression, and diag 'column': per session {'iso', 'col_var', 'col_fixed_var', 'fixed_share'} (the last three None for a session of one
+    bias frame).  A frame whose sample is not positive is a ValueError that says to drop the flag.  False (default): table and diag are what
+    they were, keys and bits."""
     xt = check_cfa(cfa) == 'xtrans'
     xtrans_pattern(raw_pattern) if xt else bayer_pattern(raw_pattern)
     black_levels(black_level)
@@ -465,10 +506,13 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
         defects = find_defects(sessions[low]['bias'], cfa, raw_pattern)[0]
     bias_stats = xtrans_bias_frame_stats if xt else bias_frame_stats
     flat_stats = xtrans_flat_pair_stats if xt else flat_pair_stats
-    frames, r_all, ptc, Ks = [], [], [], []
+    frames, r_all, ptc, Ks, colrep = [], [], [], [], []
     lam = None
     for i, s in enumerate(sessions):
         st = bias_stats(s['bias'], raw_pattern, black_level, residual=True, defects=defects)
+        if column:
+            cvar, cfix = column_samples(s['bias'], cfa, raw_pattern, black_level, defects=defects)
+            colrep.append(dict({'iso': s.get('iso')}, **(cfix or {'col_var': None, 'col_fixed_var': None, 'fixed_share': None})))
         pp = tukey_lambda_ppcc(st.pop('t'), lambdas)
         lam = pp['lambdas']
         what = 'session %d (iso %s)' % (i, s.get('iso'))
@@ -492,6 +536,11 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
         for f in range(st['color_bias'].shape[0]):
             frames.append({'session': i, 'iso': s.get('iso'), 'K': K, 'lambda': float(pp['lam_hat'][f]), 'G_scale': float(pp['scale'][f]),
                            'R_scale': float(st['R_scale'][f]), 'g_scale': float(st['g_scale'][f]), 'color_bias': st['color_bias'][f]})
+            if column:
+                if not cvar[f] > 0:
+                    raise ValueError('session %d (iso %s), bias frame %d: the column-noise sample col_var_sensor is %r, not positive: the sensor '
+                                     'shows no column term beyond chance; drop --column (column=True) for this camera' % (i, s.get('iso'), f, cvar[f]))
+                frames[-1][COLUMN_KEY] = float(np.sqrt(cvar[f]))
             r_all.append(pp['r'][f])
     params = params_from_samples(frames, Ks)
     if xt:
@@ -499,6 +548,8 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
     diag = {'frames': frames, 'lambdas': lam, 'r': np.array(r_all), 'K': np.array(Ks), 'ptc': ptc}
     if defects is not None:
         diag['defects'] = defects
+    if column:
+        diag['column'] = colrep
     return params, diag
 
 
@@ -552,12 +603,14 @@ def main(argv=None):
     ap.add_argument('--out', default=os.path.join('camera_params', 'release'))
     ap.add_argument('--defects', help="a defect map written by eld_amd.defects (.npz), or 'auto' to find one from the bias frames of the lowest-ISO "
                                       "session and write <out>/<camera>_defects.npz; overrides the manifest's \"defects\"")
+    ap.add_argument('--column', action='store_true', help="also estimate the per-sensor-column term (model letter C): adds 'C_scale' to the table's "
+                                                          "'Profile-1' and prints, per session of 2+ bias frames, the share of the column variance that is fixed")
     a = ap.parse_args(argv)
     sessions, pattern, black, white, cfa = load_manifest(a.manifest, with_cfa=True)
     defects = a.defects if a.defects is not None else manifest_defects(a.manifest)
     if defects is not None and defects != 'auto':
         defects = as_defect_map(defects, '--defects')
-    params, diag = calibrate_camera(sessions, pattern, black, white, cfa=cfa, defects=defects)
+    params, diag = calibrate_camera(sessions, pattern, black, white, cfa=cfa, defects=defects, column=a.column)
     path = save_camera_params(params, a.camera, a.out)
     if defects is not None:
         print('%d defective sites kept out of every statistic' % diag['defects'].count)
@@ -565,9 +618,14 @@ def main(argv=None):
             print('wrote', diag['defects'].save(os.path.join(a.out, a.camera + '_defects.npz')))
     for fr in diag['frames']:
         print('iso %-6s K %.5g  lambda %+.4f  G_scale %.4g  R_scale %.4g  g_scale %.4g' % (fr['iso'], fr['K'], fr['lambda'], fr['G_scale'],
-                                                                                          fr['R_scale'], fr['g_scale']))
+                                                                                          fr['R_scale'], fr['g_scale'])
+              + ('  C_scale %.4g' % fr[COLUMN_KEY] if a.column else ''))
+    for c in diag.get('column', []):
+        if c['fixed_share'] is not None:
+            print('iso %-6s column variance %.4g DN^2, fixed share %.3f (near 1: a dark-shading map removes it; near 0: temporal, model letter C)'
+                  % (c['iso'], c['col_var'], c['fixed_share']))
     print('Kmin %.5g Kmax %.5g' % (params['Kmin'], params['Kmax']))
-    for k in SIGMA_KEYS:
+    for k in SIGMA_KEYS + ((COLUMN_KEY,) if a.column else ()):
         r = params[PROFILE][k]
         print('%-8s slope %.5f bias %.5f sigma %.5f' % (k, r['slope'], r['bias'], r['sigma']))
     print('wrote', path)

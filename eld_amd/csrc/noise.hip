@@ -11,6 +11,7 @@
 //   * one Philox4x32-7 counter stream per lane (philox.h: why 7 rounds): counters are (group|element|row index, global
 //     sample id, stream), so the result is independent of grid shape, wave mapping and GPU count;
 //   * row noise: the block's rows' normals are drawn once into LDS and broadcast to the pixels;
+//   * column noise (ELD_COL, model letter 'C'): the same per SENSOR COLUMN -- the block's columns' normals are drawn once into LDS;
 //   * the float32 op sequence is exactly the reference's (one rounding per op, FMA contraction
 //     OFF for this translation unit), so with injected variates the output is bit-identical to
 //     the reference's NumPy evaluation.
@@ -34,6 +35,7 @@
 #define GROUPS_PER_BLOCK (NOISE_THREADS * NOISE_ITERS)
 #define ELEMS_PER_BLOCK (GROUPS_PER_BLOCK * 4)
 #define MAX_LDS_ROWS 256
+#define MAX_LDS_COLS 512        // staged column normals per block (2 KiB: the full model stays below 40 KiB of LDS, 4 workgroups per CU)
 #define RUNTIME_FLAGS 0xFFFFFFFFu
 #define POIS_TABLE_LAM 32.0f   // below: alias table of Poisson(floor(lam)) + inversion at the fractional rate; at or above: PTRS
 #define RES_STEPS 5            // branch-free inversion steps of the fractional-rate draw (P(more) < 6e-4 at a rate below 1)
@@ -219,6 +221,19 @@ __device__ __forceinline__ float row_normal(uint32_t srow, const SamplerRng& rng
     return box_muller(w.x, w.y).x;
 }
 
+// ELD_COL: the sensor column of packed element (c, h, x), patch-local as the row index is.  Bayer (noise.py:16-19): planes 0 and 3 sit on
+// the even mosaic columns 2x, planes 1 and 2 on the odd ones 2x + 1.  X-Trans: packed column x holds sensor columns 3x..3x+2; element
+// (c, i, j) reads 3j + d(c, (i ^ j) & 1), d = 2 bits at 4c + 2((i ^ j) & 1) of XT_DCOL (plane 0: 0,1; 2: 1,0; 1, 3, 4: 2; 5, 7: 0; 6, 8: 1
+// -- eld_pack_xtrans's XT_RC / XT_RC3 columns minus 3 (j & 1) resp. 3j).
+constexpr uint64_t XT_DCOL = 0x5050aa1a4ull;
+__device__ __forceinline__ uint32_t xt_dcol(uint32_t c, uint32_t parity) { return (uint32_t)(XT_DCOL >> (4u * c + 2u * parity)) & 3u; }
+__device__ __forceinline__ uint32_t bayer_colpar(uint32_t c) { return (c ^ (c >> 1)) & 1u; }
+
+__device__ __forceinline__ float col_normal(uint32_t scol, const SamplerRng& rng) {
+    const uint4 w = rng.words(scol, STREAM_COL);
+    return box_muller(w.x, w.y).x;
+}
+
 // ---- ELD_DARK ---------------------------------------------------------------------------------------------------------------------------
 // The crop of image n: w = Philox(index 0, sample id, STREAM_DARK); frame = first + umulhi(w.x, count) of the record's range; offsets uniform
 // over the valid ones (X-Trans: the even ones).  Every operand is uniform over the block; readfirstlane tells the compiler so (the table
@@ -330,7 +345,9 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
     constexpr bool MAYBE_P = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_SHOT_POISSON);
     constexpr bool MAYBE_X = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_CFA_XTRANS);
     constexpr bool MAYBE_D = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_DARK);
+    constexpr bool MAYBE_C = (TFLAGS == RUNTIME_FLAGS) || (TFLAGS & ELD_COL);
     __shared__ float s_row[MAX_LDS_ROWS];
+    __shared__ float s_col[MAYBE_C ? MAX_LDS_COLS : 1];
     __shared__ uint32_t s_cnt[MAYBE_P ? ELEMS_PER_BLOCK : 1];     // (count << 9) | low 9 bits of the pixel's POIS_V word (free: u01 takes w >> 9)
     __shared__ uint4 s_qp[MAYBE_P ? QP_CAP : 1];
     __shared__ uint32_t s_tab[MAYBE_P ? POIS_TAB_N * POIS_TAB_ENT : 1];
@@ -371,12 +388,14 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
     }
 
     // ---- row normals of this block's rows -> LDS ------------------------------------------------
-    uint32_t r_first = 0;
+    uint32_t r_first = 0, r_last = 0;
     bool lds_rows = false;
-    if ((flags & ELD_ROW) && !inject) {
+    if ((flags & (ELD_ROW | (MAYBE_C ? ELD_COL : 0u))) && !inject) {
         const uint32_t e_first = g_begin * 4u, e_last = min(g_end * 4u, a.chw) - 1u;
         r_first = VEC ? fdiv_u32(g_begin, a.divW) : fdiv_u32(e_first, a.divW);
-        const uint32_t r_last = VEC ? fdiv_u32(g_end - 1u, a.divW) : fdiv_u32(e_last, a.divW);
+        r_last = VEC ? fdiv_u32(g_end - 1u, a.divW) : fdiv_u32(e_last, a.divW);
+    }
+    if ((flags & ELD_ROW) && !inject) {
         const uint32_t nrows = r_last - r_first + 1u;
         lds_rows = nrows * rows_per <= MAX_LDS_ROWS;
         if (lds_rows) {
@@ -385,6 +404,40 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
                 const uint32_t r = r_first + q;
                 const uint32_t c = fdiv_u32(r, a.divH), h = r - c * a.H;
                 s_row[t] = row_normal(xt ? 3u * h + (t - 3u * q) : 2u * h + (c >> 1), rng);
+            }
+        }
+    }
+
+    // ---- column normals of this block's sensor columns -> LDS (ELD_COL) ---------------------------
+    // The block's elements lie in packed columns x_first .. x_last (one row: its segment; more rows: the whole width).  Slot of a sensor
+    // column: X-Trans scol - 3 x_first; Bayer, planes of one column parity only (col_single: any block inside a plane, or across planes
+    // 1 | 2): x - x_first; Bayer, both parities: scol - 2 x_first.  Each staged column is drawn once; more than MAX_LDS_COLS -> every
+    // element draws its own (the same function of the column).
+    float col_scale = 0.f;
+    uint32_t x_first = 0, col_base = 0;
+    bool lds_cols = false, col_single = false;
+    if constexpr (MAYBE_C) {
+        if (flags & ELD_COL) col_scale = __uint_as_float(P.reserved[0]);
+        if ((flags & ELD_COL) && !inject) {
+            uint32_t x_last = a.W - 1u;
+            if (r_first == r_last) {
+                x_first = VEC ? 4u * (g_begin - r_first * a.divW.d) : g_begin * 4u - r_first * a.W;
+                x_last = VEC ? 4u * (g_end - 1u - r_last * a.divW.d) + 3u : min(g_end * 4u, a.chw) - 1u - r_last * a.W;
+            }
+            const uint32_t nx = x_last - x_first + 1u;
+            uint32_t parmask = 3u;
+            if (!xt) {
+                const uint32_t c_first = fdiv_u32(r_first, a.divH), c_last = fdiv_u32(r_last, a.divH);
+                parmask = 0u;
+                for (uint32_t c = c_first; c <= c_last; ++c) parmask |= 1u << bayer_colpar(c);
+            }
+            col_single = !xt && parmask != 3u;
+            const uint32_t cmul = xt ? 3u : col_single ? 1u : 2u, ncols = nx * cmul;
+            col_base = (xt ? 3u : 2u) * x_first;
+            lds_cols = ncols <= MAX_LDS_COLS;
+            if (lds_cols) {
+                for (uint32_t t = tid; t < ncols; t += NOISE_THREADS)
+                    s_col[t] = col_normal(col_single ? 2u * (x_first + t) + (parmask >> 1) : col_base + t, rng);
             }
         }
     }
@@ -561,7 +614,7 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
         }
 
         uint32_t r_vec = 0;
-        if (VEC && ((flags & (ELD_ROW | ELD_CBIAS)) || do_dark)) r_vec = fdiv_u32(g, a.divW);
+        if (VEC && ((flags & (ELD_ROW | ELD_CBIAS | (MAYBE_C ? ELD_COL : 0u))) || do_dark)) r_vec = fdiv_u32(g, a.divW);
 
         float v_dark[4] = {0.f, 0.f, 0.f, 0.f};     // float(code) - black_c of the lane's four elements
         if (do_dark) dark_load<VEC>(a, dk, xt, e0, nvalid, g, r_vec, v_dark);
@@ -573,9 +626,9 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
             const uint32_t e = e0 + j;
             const size_t ge = img_off + e;
             uint32_t r = r_vec;
-            if (!VEC && (flags & (ELD_ROW | ELD_CBIAS))) r = fdiv_u32(e, a.divW);
+            if (!VEC && (flags & (ELD_ROW | ELD_CBIAS | (MAYBE_C ? ELD_COL : 0u)))) r = fdiv_u32(e, a.divW);
 
-            float v_cnt = 0.f, v_nshot = 0.f, v_nread = 0.f, v_tl = 0.f, v_nrow = 0.f, v_uq = 0.f;
+            float v_cnt = 0.f, v_nshot = 0.f, v_nread = 0.f, v_tl = 0.f, v_nrow = 0.f, v_uq = 0.f, v_ncol = 0.f;
             float zz;
             if (flags & ELD_SHOT_POISSON) {       // noise.py:158-159
                 v_cnt = inject ? a.inject[ELD_PLANE_COUNT * a.total + ge] : (j == 0 ? cnt4.x : j == 1 ? cnt4.y : j == 2 ? cnt4.z : cnt4.w);
@@ -615,6 +668,19 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
                 }
                 zz = zz + v_nrow * P.row_scale;
             }
+            if constexpr (MAYBE_C) {
+                if (flags & ELD_COL) {
+                    if (inject) {
+                        v_ncol = a.inject[ELD_PLANE_NCOL * a.total + ge];
+                    } else {
+                        const uint32_t c = fdiv_u32(r, a.divH);
+                        const uint32_t x = VEC ? 4u * (g - r * a.divW.d) + (uint32_t)j : e - r * a.W;
+                        const uint32_t scol = xt ? 3u * x + xt_dcol(c, ((r - c * a.H) ^ x) & 1u) : 2u * x + bayer_colpar(c);
+                        v_ncol = lds_cols ? s_col[col_single ? x - x_first : scol - col_base] : col_normal(scol, rng);
+                    }
+                    zz = zz + v_ncol * col_scale;
+                }
+            }
             if (do_dark) zz = zz + v_dark[j];
             if (flags & ELD_QUANT) {
                 if (inject) v_uq = a.inject[ELD_PLANE_UQ * a.total + ge];
@@ -638,6 +704,9 @@ __global__ __launch_bounds__(NOISE_THREADS) void noise_kernel(const NoiseArgs a)
                 a.dump[ELD_PLANE_TL * a.total + ge] = v_tl;
                 a.dump[ELD_PLANE_NROW * a.total + ge] = v_nrow;
                 a.dump[ELD_PLANE_UQ * a.total + ge] = v_uq;
+                if constexpr (MAYBE_C) {
+                    if (flags & ELD_COL) a.dump[ELD_PLANE_NCOL * a.total + ge] = v_ncol;     // the buffers hold ELD_NPLANES_COL planes then
+                }
             }
         }
 
@@ -718,7 +787,8 @@ static int noise_forward(const void* in, int in_dtype, size_t in_image_stride, f
     if (in_dtype != ELD_IN_F32 && in_dtype != ELD_IN_U16) return ELD_EINVAL;
     if ((flags & ELD_SHOT_POISSON) && (flags & ELD_SHOT_GAUSS)) return ELD_EINVAL;   // 'P' wins in the parser (noise.py:158-160)
     if ((flags & ELD_CFA_XTRANS) && C != 9) return ELD_EINVAL;
-    if ((flags & (ELD_ROW | ELD_CBIAS)) && !(C == 4 || ((flags & ELD_CFA_XTRANS) && C == 9))) return ELD_EINVAL;
+    if ((flags & (ELD_ROW | ELD_CBIAS | ELD_COL)) && !(C == 4 || ((flags & ELD_CFA_XTRANS) && C == 9))) return ELD_EINVAL;
+    if ((flags & ELD_COL) && (flags & ELD_DARK)) return ELD_EINVAL;                 // the dark frame holds the column term already; both read reserved[0]
     NoiseArgs a;
     a.pool = nullptr; a.pool_elems = 0; a.frames = nullptr; a.F = 0; a.dark_pos = 0;
     for (int k = 0; k < 4; ++k) a.dark_black[k] = 0.f;
@@ -747,7 +817,7 @@ static int noise_forward(const void* in, int in_dtype, size_t in_image_stride, f
         }
         a.pool = dark->pool; a.pool_elems = dark->pool_elems; a.frames = dark->frames; a.F = dark->F;
     }
-    if (!(flags & (ELD_ROW | ELD_CBIAS | ELD_DARK))) flags &= ~ELD_CFA_XTRANS;   // the per-pixel terms do not depend on the layout: same kernels as without
+    if (!(flags & (ELD_ROW | ELD_CBIAS | ELD_DARK | ELD_COL))) flags &= ~ELD_CFA_XTRANS;   // the per-pixel terms do not depend on the layout: same kernels as without
     const size_t chw = (size_t)C * H * W;
     if (N == 0 || chw == 0) return 0;               // empty input: nothing to do (reference returns an empty array)
     if (!in || !out || !params) return ELD_EINVAL;
@@ -779,7 +849,12 @@ static int noise_forward(const void* in, int in_dtype, size_t in_image_stride, f
     constexpr uint32_t FULL = ELD_SHOT_POISSON | ELD_READ_TL | ELD_ROW | ELD_QUANT;   // 'PGRU' -- BASELINE.json config 2
     constexpr uint32_t PG = ELD_SHOT_POISSON | ELD_READ_GAUSS;                        // 'Pg'   -- config 1
     constexpr uint32_t PDU = ELD_SHOT_POISSON | ELD_DARK | ELD_QUANT;                 // 'PDU'  -- shot noise + the sensor's own dark frames
+    constexpr uint32_t FULLC = FULL | ELD_COL;                                        // 'PGRCU' -- the full model with the column term
     switch (flags) {
+        case FULLC: return launch_noise<true, FULLC, false>(a, N, st);
+        case FULLC | ELD_CLIP: return launch_noise<true, FULLC | ELD_CLIP, false>(a, N, st);
+        case FULLC | ELD_CFA_XTRANS: return launch_noise<true, FULLC | ELD_CFA_XTRANS, false>(a, N, st);
+        case FULLC | ELD_CFA_XTRANS | ELD_CLIP: return launch_noise<true, FULLC | ELD_CFA_XTRANS | ELD_CLIP, false>(a, N, st);
         case PDU: return launch_noise<true, PDU, false>(a, N, st);
         case PDU | ELD_CLIP: return launch_noise<true, PDU | ELD_CLIP, false>(a, N, st);
         case PDU | ELD_CFA_XTRANS: return launch_noise<true, PDU | ELD_CFA_XTRANS, false>(a, N, st);

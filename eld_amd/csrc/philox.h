@@ -20,6 +20,7 @@ enum : uint32_t {
     STREAM_POIS_V = 6,  // index = group              -> word j    -> Poisson attempt-0 V
     STREAM_POIS_R = 7,  // index = element, iter      -> (U,V),(U,V) retries
     STREAM_DARK = 8,    // index = 0                  -> words 0,1,2 -> dark frame, y0, x0 of the image's crop (ELD_DARK)
+    STREAM_COL = 9,     // index = sensor column      -> words 0,1 -> one normal (ELD_COL)
 };
 
 struct PhiloxKey {

@@ -14,7 +14,9 @@ Differences a user can observe, all documented in DESIGN.md:
   * model letters G / R / U / B select the withheld ELD terms (Tukey-lambda read, row,
     quantisation, colour bias) -- the reference ignores unknown letters (noise.py:158-166);
   * model letter D takes every signal-independent term from the sensor's own dark frames instead
-    (NoiseModel(model='PDU', dark=DarkPool(...)), eld_amd/darkpool.py): it excludes g / G / R / B.
+    (NoiseModel(model='PDU', dark=DarkPool(...)), eld_amd/darkpool.py): it excludes g / G / R / B / C;
+  * model letter C adds a per-sensor-column Gaussian (a fresh column pattern per sample); its scale is the 'C_scale' regression that
+    `python -m eld_amd.calibrate --column` writes into a camera table (no release table has it).
 There is no CPU path: calling the plugin without a GPU / built library raises.
 """
 import json
@@ -48,6 +50,8 @@ def model_flags(model, cfa='bayer'):
         f |= L.CBIAS
     if 'D' in model:
         f |= L.DARK
+    if 'C' in model:
+        f |= L.COL
     return f
 
 
@@ -65,9 +69,10 @@ class NoiseParams(tuple):
     """(K, g_scale, saturation_level, ratio) exactly as noise.py:225 returns it; the withheld-model
     terms ride along as attributes so burst call sites (sid_dataset.py:269-272) keep working."""
     def __new__(cls, K, g_scale, saturation_level, ratio, tl_lambda=0.0, tl_scale=0.0, row_scale=0.0,
-                q_step=1.0, color_bias=(0.0, 0.0, 0.0, 0.0), dark=None):
+                q_step=1.0, color_bias=(0.0, 0.0, 0.0, 0.0), dark=None, col_scale=0.0):
         self = super().__new__(cls, (K, g_scale, saturation_level, ratio))
         self.tl_lambda, self.tl_scale, self.row_scale, self.q_step = tl_lambda, tl_scale, row_scale, q_step
+        self.col_scale = col_scale                  # model 'C': column-noise std (ADU)
         self.color_bias = tuple(color_bias)
         self.dark = None if dark is None else (int(dark[0]), int(dark[1]))      # model 'D': (first, count) of the session's frames in the DarkPool's table
         return self
@@ -79,7 +84,7 @@ class NoiseParams(tuple):
         if isinstance(p, dict):
             return cls(p['K'], p['g_scale'], p.get('saturation', 16383 - 800), p['ratio'], p.get('tl_lambda', 0.0),
                        p.get('tl_scale', 0.0), p.get('row_scale', 0.0), p.get('q_step', 1.0),
-                       p.get('color_bias', (0.0,) * 4), p.get('dark'))
+                       p.get('color_bias', (0.0,) * 4), p.get('dark'), p.get('col_scale', 0.0))
         K, g, s, r = p
         return cls(K, g, s, r)
 
@@ -90,7 +95,8 @@ class NoiseParams(tuple):
             self.tl_lambda, self.tl_scale, self.row_scale, self.q_step
         rec['color_bias'] = self.color_bias
         rec['sample_id_lo'], rec['sample_id_hi'] = sample_id & 0xFFFFFFFF, (sample_id >> 32) & 0xFFFFFFFF
-        rec['reserved'] = self.dark if self.dark is not None else (0, 0)
+        # one field, two users that exclude each other: the frame range of 'D', else the float bits of the column scale of 'C' (0.0 -> 0)
+        rec['reserved'] = self.dark if self.dark is not None else (int(np.float32(self.col_scale).view(np.uint32)), 0)
         return rec
 
 
@@ -184,6 +190,10 @@ def sample_noise_records(y, recs, flags, seed, in_u16=False, inject=None, dump=N
             raise ValueError('the DarkPool holds %s frames, the flags say %s' % (dark.cfa, 'xtrans' if int(flags) & L.CFA_XTRANS else 'bayer'))
         dark.check_patch(H, W)
         dark_args = dark.launch_args(dark_table)
+    nplanes = L.NPLANES_COL if int(flags) & L.COL else L.NPLANES      # the kernel reads / writes that many planes of N*C*H*W floats
+    for name, buf in (('inject', inject), ('dump', dump)):
+        if buf is not None and buf.numel() < nplanes * y.numel():
+            raise ValueError('%s holds %d floats, these flags need %d planes of %d' % (name, buf.numel(), nplanes, y.numel()))
     prm = _upload(np.ascontiguousarray(recs).view(np.uint8).reshape(-1), y.device)
     if out is None:
         out = torch.empty((N, burst * C, H, W), dtype=torch.float32, device=y.device)
@@ -398,6 +408,8 @@ class NoiseModel(NoiseModelBase):
         super().__init__()
         assert cfa in ['bayer', 'xtrans']                   # noise.py:177
         assert include is None or exclude is None           # noise.py:178
+        if 'C' in model and 'D' in model:
+            raise ValueError("NoiseModel(model=%r): 'D' excludes C (the dark frames contain the sensor's column pattern)" % (model,))
         if 'D' in model:          # the dark frames hold every signal-independent term of the sensor: a parametric one next to them counts it twice
             if dark is None:
                 raise ValueError("NoiseModel(model=%r): 'D' samples the sensor's dark frames and needs dark=DarkPool(...)" % (model,))
@@ -426,6 +438,11 @@ class NoiseModel(NoiseModelBase):
                 if table_cfa(self.camera_params[camera]) != cfa:
                     raise ValueError("NoiseModel(model=%r, cfa=%r): camera %s has a %s table; its colour bias does not apply to %s input"
                                      % (model, cfa, camera, table_cfa(self.camera_params[camera]), cfa))
+        if 'C' in model:          # no release table has the column law: it comes from calibrate --column
+            for camera in self.cameras:
+                if 'C_scale' not in self.camera_params[camera]['Profile-1']:
+                    raise ValueError("NoiseModel(model=%r): the table of camera %s has no 'C_scale' in 'Profile-1'; calibrate the camera with "
+                                     "`python -m eld_amd.calibrate --column` (calibrate_camera(..., column=True))" % (model, camera))
         self._counter = 0
         # noise.py:209-210 reads the calibrated Kmin/Kmax and then samples log K from the hard-coded [0.1, 30] (:215); the
         # calibrated range is the paper's.  Default = the reference's behaviour; ELD_AMD_CALIBRATED_K=1 or this attribute opts in.
@@ -435,7 +452,8 @@ class NoiseModel(NoiseModelBase):
     def _sample_params(self):
         """noise.py:201-225, same five draws from the global NumPy RandomState in the same order.
         When the model string asks for withheld terms (G/R/U/B) their parameters are drawn AFTER the
-        reference's five, so the reference's tuple is unchanged for a given np.random.seed."""
+        reference's five, so the reference's tuple is unchanged for a given np.random.seed.  'C' adds one draw (C_scale) after all of
+        those: every field of 'PGRU' equals the same field of 'PGRCU' for one seed."""
         camera = np.random.choice(self.cameras)
         saturation_level = 16383 - 800
         profiles = ['Profile-1']
@@ -456,7 +474,7 @@ class NoiseModel(NoiseModelBase):
                 raise ValueError("the DarkPool has no session gains: DarkPool(..., K=diag['K'])")
             si = int(np.random.randint(self.dark.sessions))
             return NoiseParams(float(self.dark.K[si]), g_scale, self.dark.saturation, ratio, q_step=1.0, dark=self.dark.ranges[si])
-        if not any(ch in self.model for ch in 'GRUB'):
+        if not any(ch in self.model for ch in 'GRUBC'):
             return NoiseParams(K, g_scale, saturation_level, ratio)
 
         def reg(name):        # log sigma | log K ~ N(slope*logK + bias, sigma)   [ELD paper eq. for joint sampling]
@@ -465,6 +483,7 @@ class NoiseModel(NoiseModelBase):
         tl_scale, row_scale = reg('G_scale'), reg('R_scale')
         i = np.random.randint(len(camera_params['G_shape']))
         cb = [float(b) for b in np.asarray(camera_params['color_bias'])[i]]
+        col_scale = reg('C_scale') if 'C' in self.model else 0.0             # the last draw: the ones before it do not move
         return NoiseParams(K, g_scale, saturation_level, ratio, tl_lambda=float(camera_params['G_shape'][i]),
                            tl_scale=tl_scale, row_scale=row_scale, q_step=1.0,
-                           color_bias=tuple(cb + [0.0] * (4 - len(cb))))      # X-Trans tables: (R, G, B) -> (R, G, B, 0)
+                           color_bias=tuple(cb + [0.0] * (4 - len(cb))), col_scale=col_scale)      # X-Trans tables: (R, G, B) -> (R, G, B, 0)

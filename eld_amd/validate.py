@@ -29,8 +29,8 @@ from . import mosaic as M
 from .defects import check_defects
 from .noise import NoiseParams, model_flags, table_cfa
 
-MODEL_LETTERS = 'PpgGRUBD'
-DARK_EXCLUDES = 'gGRB'                            # the terms a dark frame already holds: not next to D
+MODEL_LETTERS = 'PpgGRUBDC'
+DARK_EXCLUDES = 'gGRBC'                           # the terms a dark frame already holds: not next to D
 MAX_RADIUS = 32767
 XT_PLANE_COLOUR = (0, 1, 2, 0, 2, 1, 1, 1, 1)     # packed X-Trans plane -> colour (R 0, G 1, B 2): planes 0, 3 R; 1, 5-8 G; 2, 4 B
 ID_BASE = 1 << 62                                 # validation streams lie far from the sample ids a training run counts up from 0
@@ -206,10 +206,11 @@ def _noise_params(p, sat):
     """Any parameter record -> the one validation samples with: ratio = 1, saturation = sat, q_step = 1."""
     if isinstance(p, dict):
         p = NoiseParams(p.get('K', 1.0), p.get('g_scale', 0.0), sat, 1.0, p.get('tl_lambda', 0.0), p.get('tl_scale', 0.0), p.get('row_scale', 0.0),
-                        1.0, tuple(p.get('color_bias', (0.0,) * 4)))
+                        1.0, tuple(p.get('color_bias', (0.0,) * 4)), col_scale=p.get('col_scale', 0.0))
     p = NoiseParams.coerce(p)
     cb = tuple(float(v) for v in p.color_bias) + (0.0,) * (4 - len(p.color_bias))
-    return NoiseParams(float(p[0]), float(p[1]), float(sat), 1.0, float(p.tl_lambda), float(p.tl_scale), float(p.row_scale), 1.0, cb)
+    return NoiseParams(float(p[0]), float(p[1]), float(sat), 1.0, float(p.tl_lambda), float(p.tl_scale), float(p.row_scale), 1.0, cb,
+                       col_scale=float(p.col_scale))
 
 
 def _sample(clean, params, model, cfa, seed, ids, dark=None, dark_table=None):
@@ -243,7 +244,7 @@ def synthesize_codes(clean, params, model, cfa, seed, sample_id, white, black, s
     clip(rint(x * sat) + rint(black_c), 0, 65535), unpacked (CUDA uint16 (Hm, Wm); Bayer planes land in the layout [[0, 1], [3, 2]] of
     RawPacker.unpack_raw_bayer).  x * sat is one float32 multiply and rint rounds half to even: eld_hist_f32's q.
     clean: packed float32 (C,h,w) [ndarray or CUDA tensor], or None for a dark frame -- zeros of the packed `shape` (C,h,w).
-    params: a NoiseParams / dict (K, g_scale, tl_lambda, tl_scale, row_scale, color_bias, in DN); the sampler runs with ratio = 1,
+    params: a NoiseParams / dict (K, g_scale, tl_lambda, tl_scale, row_scale, col_scale, color_bias, in DN); the sampler runs with ratio = 1,
     saturation = white - max(black) and q_step = 1.  black: per packed channel (Bayer) or per colour code (X-Trans)."""
     import torch
     M.check_cfa(cfa)
@@ -308,17 +309,25 @@ def _table_params(table, K, ncb):
     lk = float(np.log(K))
     reg = {k: float(np.exp(float(prof[k]['slope']) * lk + float(prof[k]['bias']))) for k in CAL.SIGMA_KEYS}
     cb = np.asarray(table['color_bias'], np.float64).reshape(len(table['G_shape']), -1).mean(axis=0)
-    return {'K': float(K), 'g_scale': reg['g_scale'], 'tl_scale': reg['G_scale'], 'row_scale': reg['R_scale'],
-            'tl_lambda': float(np.median(np.asarray(table['G_shape'], np.float64))), 'color_bias': [float(v) for v in cb[:ncb]]}
+    out = {'K': float(K), 'g_scale': reg['g_scale'], 'tl_scale': reg['G_scale'], 'row_scale': reg['R_scale'],
+           'tl_lambda': float(np.median(np.asarray(table['G_shape'], np.float64))), 'color_bias': [float(v) for v in cb[:ncb]]}
+    if CAL.COLUMN_KEY in prof:                       # a table of calibrate --column
+        out['col_scale'] = float(np.exp(float(prof[CAL.COLUMN_KEY]['slope']) * lk + float(prof[CAL.COLUMN_KEY]['bias'])))
+    return out
 
 
 def _frame_params(fr, ncb):
-    return {'K': float(fr['K']), 'g_scale': float(fr['g_scale']), 'tl_scale': float(fr['G_scale']), 'row_scale': float(fr['R_scale']),
-            'tl_lambda': float(fr['lambda']), 'color_bias': [float(v) for v in np.asarray(fr['color_bias']).reshape(-1)[:ncb]]}
+    out = {'K': float(fr['K']), 'g_scale': float(fr['g_scale']), 'tl_scale': float(fr['G_scale']), 'row_scale': float(fr['R_scale']),
+           'tl_lambda': float(fr['lambda']), 'color_bias': [float(v) for v in np.asarray(fr['color_bias']).reshape(-1)[:ncb]]}
+    if CAL.COLUMN_KEY in fr:                         # a diag of calibrate_camera(column=True): the frame's own column-noise sample
+        out['col_scale'] = float(fr[CAL.COLUMN_KEY])
+    return out
 
 
 def _mean_params(ps):
     out = {k: float(np.mean([p[k] for p in ps])) for k in ('K', 'g_scale', 'tl_scale', 'row_scale')}
+    if all('col_scale' in p for p in ps):
+        out['col_scale'] = float(np.mean([p['col_scale'] for p in ps]))
     out['tl_lambda'] = float(np.median([p['tl_lambda'] for p in ps]))
     out['color_bias'] = [float(v) for v in np.mean([p['color_bias'] for p in ps], axis=0)]
     return out
@@ -357,7 +366,9 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     A model with the letter D (e.g. 'PD', 'PDU') takes its signal-independent noise from the sensor's own frames: for bias frame f the draws
     read the session's OTHER bias frames (leave-one-out: the frame table handed to the sampler omits f; with defects the pooled frames are
     repaired), the clean image is zero and K the frame's.  Such rows carry 'dark': 'leave-one-out'; they apply to bias frames only (kl_flat
-    is None) and every session needs at least two bias frames (ValueError).  kl of 'PD' against its floor is how close two real frames of
+    is None) and every session needs at least two bias frames (ValueError).  A model with the letter C (e.g. 'PGRC') adds the
+    per-sensor-column term: its scale is the frame's 'C_scale' of a diag of calibrate_camera(column=True) (the calibration that runs here
+    without a diag is run that way) or, with source='table', the table's 'C_scale' law; a diag or table without it is a ValueError.  kl of 'PD' against its floor is how close two real frames of
     the sensor are to each other: the yardstick the parametric rows are read against.  best = the model of lowest mean bias-frame kl, lowest index on a tie.
     This is a check of marginal distributions per colour group; the spatial structure of the noise is a separate report:
     structure=True adds report['structure'] (eld_amd/structure.py).  Per session: 'real' -- the components of the bias
@@ -396,6 +407,7 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     if len(sessions) >= 1 << 20:
         raise ValueError('too many sessions')
     with_dark = any('D' in m for m in models)
+    with_col = any('C' in m for m in models)
     if with_dark:
         for i, s in enumerate(sessions):
             if M.shape_of(s['bias'])[0] < 2:
@@ -418,7 +430,7 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
 
     import torch
     if diag is None:
-        table_c, diag = CAL.calibrate_camera(sessions, raw_pattern, black_level, white_level, cfa=cfa, defects=defects)
+        table_c, diag = CAL.calibrate_camera(sessions, raw_pattern, black_level, white_level, cfa=cfa, defects=defects, column=with_col)
         if table is None:
             table = table_c
     if defects == 'auto':
@@ -466,6 +478,9 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
         else:
             fparams = [_frame_params(fr, ncb) for fr in diag['frames'][j0:j0 + F]]
         j0 += F
+        if with_col and not all('col_scale' in p for p in fparams):
+            raise ValueError("a model with C needs the column-noise scale: %s has no 'C_scale'; calibrate with `python -m eld_amd.calibrate --column` "
+                             "(calibrate_camera(..., column=True))" % ("the table's 'Profile-1'" if source == 'table' else "diag['frames']"))
         sparams = _mean_params(fparams)
         real = histogram_u16(bias, cfa, raw_pattern, centre, R, defects=defects)
         dark = torch.zeros((2, C, h, w), dtype=torch.float32, device=bias.device)

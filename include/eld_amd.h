@@ -56,7 +56,12 @@ extern "C" {
  * a static scene): two new symbols, no existing call changed.
  * Still 8: eld_burst_luma_pyramid_elems, eld_burst_luma_pyramid_u16, eld_burst_align_workspace_bytes, eld_burst_align_u16,
  * eld_burst_stack_aligned_workspace_bytes and eld_burst_stack_aligned_u16 were added the same way (registration of a hand-held burst and the
- * stack through its displacement field): six new symbols, no existing call changed. */
+ * stack through its displacement field): six new symbols, no existing call changed.
+ * Still 8: ELD_COL (model letter 'C', a per-sensor-column Gaussian), ELD_PLANE_NCOL and ELD_NPLANES_COL were added without a new number and
+ * without a new symbol: no existing call, record layout or result changes.  The 64-byte EldNoiseParams keeps its layout; with ELD_COL in the
+ * flags reserved[0] is read as the float bits of the column scale (ELD_COL and ELD_DARK, the field's other user, exclude each other), and the
+ * inject / dump buffers then hold ELD_NPLANES_COL planes.  Without ELD_COL the field is ignored and the buffers hold ELD_NPLANES planes, as
+ * before.  The one difference: bit 2048 in the flags of the sampler entries was ignored and now selects the term. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -78,6 +83,8 @@ extern "C" {
                                   ELD_CBIAS follow the X-Trans mosaic; without ELD_ROW / ELD_CBIAS / ELD_DARK it changes nothing */
 #define ELD_DARK       1024u   /* 'D'  z += code - black: the signal-independent noise is a random crop of a real dark frame
                                   (eld_noise_forward_dark only; SFRN, Zhang et al., ICCV 2021) */
+#define ELD_COL        2048u   /* 'C'  per-sensor-column Gaussian: z += N(column) * col_scale, directly after the row term.  col_scale is
+                                  the float whose bits are EldNoiseParams.reserved[0].  Not with ELD_DARK; C == 4, or 9 with ELD_CFA_XTRANS */
 
 /* input element types */
 #define ELD_IN_F32  0   /* float32 in [0,1]                                                      */
@@ -96,7 +103,8 @@ typedef struct EldNoiseParams {
     float ratio;        /* exposure ratio                              noise.py:223           */
     float color_bias[4];/* per packed channel (ADU)  ('color_bias'); ELD_CFA_XTRANS: (R, G, B) per CFA colour, [3] unused */
     uint32_t sample_id_lo, sample_id_hi;  /* GLOBAL sample index -> Philox counter words 1,2  */
-    uint32_t reserved[2];                 /* ELD_DARK: first index and count of the frame-table range this image draws from; else 0 */
+    uint32_t reserved[2];                 /* ELD_DARK: first index and count of the frame-table range this image draws from; ELD_COL: [0] =
+                                             the bits of the float32 column-noise std (ADU) ('C_scale' regression); else ignored */
 } EldNoiseParams;
 
 /* Variate planes of the debug/inject buffers: float[ELD_NPLANES][N*C*H*W]. */
@@ -107,6 +115,8 @@ typedef struct EldNoiseParams {
 #define ELD_PLANE_NROW    4   /* row normal, broadcast per pixel */
 #define ELD_PLANE_UQ      5   /* quantisation uniform in [0,1)   */
 #define ELD_NPLANES       6
+#define ELD_PLANE_NCOL    6   /* column normal, broadcast per pixel: present only with ELD_COL in the flags */
+#define ELD_NPLANES_COL   7   /* planes of the inject / dump buffers when ELD_COL is set (ELD_NPLANES otherwise) */
 
 int eld_abi_version(void);
 const char* eld_build_info(void);               /* "gfx950 hipcc <ver> ..." */
@@ -125,7 +135,13 @@ const char* eld_error_string(int code);
  * ELD_CFA_XTRANS.  X-Trans: packed row i holds sensor rows 3i..3i+2; element (c, i, j) reads sensor row 3i + d, d = 0 for planes
  * 0-2, 1 for 5-6, 2 for 7-8, and for planes 3 / 4 d = 1 / 2 where i + j is even, 2 / 1 where it is odd.  Its row normal is
  * the one of that sensor row (same Philox counter layout as Bayer's, indexed by the sensor row).  The colour bias of plane c
- * is color_bias[colour of c]: planes 0, 3 R; 2, 4 B; 1, 5-8 G.  ELD_CFA_XTRANS with C != 9 is ELD_EINVAL. */
+ * is color_bias[colour of c]: planes 0, 3 R; 2, 4 B; 1, 5-8 G.  ELD_CFA_XTRANS with C != 9 is ELD_EINVAL.
+ * ELD_COL has the same shape requirement.  Its index is the patch-local sensor column: Bayer element (c, h, w) sits on column
+ * 2w + ((c ^ (c >> 1)) & 1) (planes 0 and 3 even, 1 and 2 odd); X-Trans element (c, i, j) on the mosaic column eld_pack_xtrans reads for
+ * it, 3j + d with d = 2 for planes 1, 3, 4; 0 for 5, 7; 1 for 6, 8; and for planes 0 / 2 d = 0 / 1 where i + j is even, 1 / 0 where it is
+ * odd.  The normal of a column is a function of (seed, sample id, column) only (Philox stream 9, words 0 and 1, the row transform); planes
+ * that share a sensor column share it.  zz = zz + n_col * col_scale follows the row term directly (float32, one rounding per operation).
+ * ELD_COL with ELD_DARK is ELD_EINVAL. */
 int eld_noise_forward(const void* in, int in_dtype, float* out, const EldNoiseParams* params,
                       int N, int C, int H, int W, uint32_t flags, uint64_t seed,
                       const float* inject, float* dump, void* stream);
