@@ -147,6 +147,13 @@ SIGNATURES = {
     'eld_debug_last_conv_kernel': (C.c_char_p, []),
     'eld_debug_conv_kernel_count': (C.c_uint, [C.c_char_p]),
     'eld_debug_unet_region': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i)]),
+    'eld_flat_sums_u16': (_i, [_vp, _sz, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'eld_flat_box_workspace_bytes': (_sz, [_i, _i]),
+    'eld_flat_box_tile': (_i, [_i, C.POINTER(_i), C.POINTER(_i)]),
+    'eld_flat_box_u32': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'eld_flat_apply_u16': (_i, [_vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_float), _i, _i, _vp, _vp]),
+    'eld_pack_raw_bayer_u16_flat': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp, _vp, _vp, _f, _vp, _vp]),
+    'eld_pack_raw_xtrans_u16_flat': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _vp, _vp]),
 }
 
 

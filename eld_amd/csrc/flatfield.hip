@@ -1,0 +1,504 @@
+// flatfield.hip -- flat-field maps: what multiplies the signal (pixel response non-uniformity and lens shading), measured from the flat pairs of
+// a calibration manifest and divided out (eld_amd/flatfield.py).
+//
+//   eld_flat_sums_u16                  flat frames in a frame pool -> per site S = sum of codes, D = sum over pairs of (a - b)^2, a bad flag
+//   eld_flat_box_u32                   S and the flag -> per site the sum and the count of the good sites of its window, in its position plane
+//   eld_flat_apply_u16                 uint16 codes [N,Hm,Wm] -> clamp(rint((u - black) * gain + black), 0, 65535)
+//   eld_pack_raw_bayer_u16_flat        eld_pack_raw_bayer_u16_shaded with ((u - black) - (a + b t)) * gain / denom; a, b and ratios optional
+//   eld_pack_raw_xtrans_u16_flat       eld_pack_raw_xtrans_u16_shaded likewise
+// The first two are integer arithmetic throughout: their outputs do not depend on the launch geometry, and tests/flatfield_ref.py restates them
+// (and the float32 operation order of the other three) in NumPy.  The library is built with -ffp-contract=off; the pragma says so for this file.
+//
+// Sums and apply: a lane owns 8 consecutive columns of one row, as in shading.hip (one 16-byte load of codes where the row pitch and the frame's
+// start allow it, else one word per column pair).  The flag bitmap has pack_bitmap's layout (bit x & 31 of word [y][x >> 5]); a lane's 8 bits are
+// one BYTE of it, written with one byte store: no atomics, and the pad bytes of a row are written (zero) by the row's last lane.
+//
+// Box: the window of a site is (2R + 1)^2 sites at steps of the period p around it, clipped at the frame.  Two separable passes over one packed
+// 64-bit word per site, (S << 16) | 1 at a good site and 0 at a bad one: the low 16 bits count (at most 129^2 = 16641 < 2^16), the rest sums
+// (S < 2^32, so a window stays below 2^47 and the packed word below 2^63).  Integer adds in any order are exact, so both passes are running
+// sums: a lane starts its segment with the 2R + 1 taps of its first window and then slides (one tap in, one out).
+//   rows     a workgroup stages FF_TW<P> columns of one row plus p R on either side in LDS (coalesced reads), each lane slides along FF_SEG
+//            plane columns of one column phase, results go back through LDS for coalesced 8-byte stores into the workspace
+//   columns  a lane owns one mosaic column (coalesced across the wave) and slides down FF_VSEG plane rows of each of the p row phases
+// The cost per site is 2 + (2R + 1) / FF_SEG LDS reads and 2 + (2R + 1) / FF_VSEG global reads: linear in R with a small slope, not R^2.
+#include "common.h"
+#include "xtrans.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int FF_T = 256;                        // threads per workgroup
+constexpr int FF_NPX = 8;                        // columns per lane (sums, apply)
+constexpr int FF_U = 4;                          // frames in flight per lane: two pairs
+constexpr int FF_MAX_FRAMES = 65536;             // 65536 * 65535 < 2^32 keeps S exact in uint32
+constexpr int FF_MAX_RADIUS = 64;
+constexpr int FF_SEG = 9;                        // plane columns per lane of the row pass (odd: lanes of a wave spread over the LDS banks)
+constexpr int FF_VSEG = 16;                      // plane rows per lane and row phase of the column pass
+
+template <int P> struct BoxTile {
+    static constexpr int NSEG = FF_T / P;                        // segments per workgroup and column phase
+    static constexpr int TW = NSEG * FF_SEG * P;                 // mosaic columns per workgroup of the row pass: 2304 (p = 2), 2268 (p = 6)
+    static constexpr int LW = TW + 2 * P * FF_MAX_RADIUS;        // with the halo of the largest radius
+    static constexpr int TH = P * FF_VSEG;                       // mosaic rows per workgroup of the column pass: 32, 96
+};
+
+struct SumsArgs {
+    const uint16_t* pool;
+    size_t pool_elems;
+    const EldPoolFrame* frames;
+    const uint32_t* bitmap;
+    uint32_t* S;
+    uint64_t* D;
+    uint32_t* bad;
+    int Hm, Wm, wpr, lpr, F, white, vec_in, vec_out;   // lpr = lanes per row = ceil(Wm / 8)
+};
+
+struct ApplyArgs {
+    const uint16_t* in;
+    uint16_t* out;
+    const float* gain;
+    const uint32_t* bitmap;
+    int N, Hm, Wm, wpr, lpr, white;
+    float black[36];
+};
+
+// the per-cell values a lane needs: row phase r, columns x0 % P + j (x0 % P is 0 when P == 2 and 0, 2 or 4 when P == 6, so 12 entries per row phase)
+template <int P>
+__device__ __forceinline__ void fill_cells(float* s_cell, const float* cell) {
+    if (threadIdx.x < P * 12) s_cell[threadIdx.x] = cell[(threadIdx.x / 12) * P + (threadIdx.x % 12) % P];
+}
+
+// 8 codes as 4 words.  VEC: one 16-byte load; otherwise one word per column pair that lies inside the row (the others read as 0)
+template <bool VEC>
+__device__ __forceinline__ void load_codes(const uint16_t* p, int x0, int Wm, uint32_t (&w)[4]) {
+    if (VEC) {
+        const uint4 q = *reinterpret_cast<const uint4*>(p);
+        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) w[k] = x0 + 2 * k < Wm ? *reinterpret_cast<const uint32_t*>(p + 2 * k) : 0u;
+    }
+}
+
+__device__ __forceinline__ uint32_t code_of(const uint32_t (&w)[4], int j) { return (w[j / 2] >> (16 * (j & 1))) & 0xFFFFu; }
+
+// ---- pass 1: one read of every flat code ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FF_T) void flat_sums_kernel(SumsArgs a) {
+    const uint32_t units = (uint32_t)a.Hm * (uint32_t)a.lpr;             // Hm * Wm < 2^31
+    const size_t fsz = (size_t)a.Hm * a.Wm;
+    for (uint32_t i = blockIdx.x * FF_T + threadIdx.x; i < units; i += gridDim.x * FF_T) {
+        const int y = (int)(i / (uint32_t)a.lpr), l = (int)(i - (uint32_t)y * (uint32_t)a.lpr), x0 = l * FF_NPX;
+        const size_t site = (size_t)y * a.Wm + x0;
+        uint32_t T[FF_NPX], sat = 0u;
+        uint64_t Q[FF_NPX];
+#pragma unroll
+        for (int j = 0; j < FF_NPX; ++j) { T[j] = 0u; Q[j] = 0ull; }
+        for (int f0 = 0; f0 < a.F; f0 += FF_U) {                         // F is even: a group of four holds whole pairs
+            const uint16_t* src[FF_U];
+            bool ok[FF_U], wide = a.vec_in;
+#pragma unroll
+            for (int u = 0; u < FF_U; ++u) {                             // launch-uniform: the table entry decides, not the lane
+                ok[u] = f0 + u < a.F;
+                src[u] = a.pool;
+                if (ok[u]) {
+                    const EldPoolFrame e = a.frames[f0 + u];
+                    // an entry that is not an Hm x Wm frame inside the pool contributes no codes: nothing outside the pool is read
+                    ok[u] = e.Hm == a.Hm && e.Wm == a.Wm && !(e.offset & 1u) && e.offset <= a.pool_elems && fsz <= a.pool_elems - e.offset;
+                    if (ok[u]) {
+                        src[u] = a.pool + e.offset + site;
+                        wide = wide && e.offset % FF_NPX == 0;
+                    }
+                }
+            }
+            uint32_t w[FF_U][4];
+            if (wide) {
+#pragma unroll
+                for (int u = 0; u < FF_U; ++u) {
+                    if (ok[u]) load_codes<true>(src[u], x0, a.Wm, w[u]);
+                    else w[u][0] = w[u][1] = w[u][2] = w[u][3] = 0u;
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < FF_U; ++u) {
+                    if (ok[u]) load_codes<false>(src[u], x0, a.Wm, w[u]);
+                    else w[u][0] = w[u][1] = w[u][2] = w[u][3] = 0u;
+                }
+            }
+#pragma unroll
+            for (int h = 0; h < FF_U / 2; ++h)
+#pragma unroll
+                for (int j = 0; j < FF_NPX; ++j) {
+                    const uint32_t ca = code_of(w[2 * h], j), cb = code_of(w[2 * h + 1], j);
+                    const uint32_t d = ca > cb ? ca - cb : cb - ca;
+                    T[j] += ca + cb;
+                    Q[j] += (uint64_t)(d * d);                           // d <= 65535: the square fits 32 bits
+                    sat |= (uint32_t)(((int)ca >= a.white) | ((int)cb >= a.white)) << j;
+                }
+        }
+        uint32_t flag = sat | (a.bitmap ? (a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31)) : 0u);
+        const int inside = a.Wm - x0 < FF_NPX ? a.Wm - x0 : FF_NPX;      // columns of this lane that lie in the row: no bits beyond it
+        flag &= (1u << inside) - 1u;
+        uint8_t* bytes = reinterpret_cast<uint8_t*>(a.bad) + (size_t)y * a.wpr * 4;
+        bytes[l] = (uint8_t)flag;
+        if (l == a.lpr - 1)
+            for (int k = a.lpr; k < a.wpr * 4; ++k) bytes[k] = 0;        // the pad bytes of the row's last word
+        if (a.vec_out) {
+            uint4* ps = reinterpret_cast<uint4*>(a.S + site);
+            ps[0] = make_uint4(T[0], T[1], T[2], T[3]); ps[1] = make_uint4(T[4], T[5], T[6], T[7]);
+            ulonglong2* pd = reinterpret_cast<ulonglong2*>(a.D + site);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pd[k] = make_ulonglong2(Q[2 * k], Q[2 * k + 1]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < FF_NPX; ++j)
+                if (x0 + j < a.Wm) { a.S[site + j] = T[j]; a.D[site + j] = Q[j]; }
+        }
+    }
+}
+
+// ---- pass 2: the window sums ---------------------------------------------------------------------------------------------------------------------
+// rows: ws[y][x] = sum over |d| <= R, 0 <= x + p d < Wm of the packed word of site (y, x + p d)
+template <int P>
+__global__ __launch_bounds__(FF_T) void flat_box_rows_kernel(const uint32_t* __restrict__ S, const uint32_t* __restrict__ bad, uint64_t* __restrict__ ws,
+                                                             int Hm, int Wm, int wpr, int R, int tiles_x) {
+    using BT = BoxTile<P>;
+    __shared__ uint64_t g[BT::LW];
+    __shared__ uint64_t res[BT::TW];
+    const int y = (int)(blockIdx.x / (unsigned)tiles_x), xt = (int)(blockIdx.x % (unsigned)tiles_x) * BT::TW;
+    const int halo = P * R, n = BT::TW + 2 * halo;                       // n <= LW because R <= FF_MAX_RADIUS
+    const int t = threadIdx.x;
+    for (int k = t; k < n; k += FF_T) {
+        const int x = xt - halo + k;
+        uint64_t v = 0ull;
+        if (x >= 0 && x < Wm && !((bad[(size_t)y * wpr + (x >> 5)] >> (x & 31)) & 1u)) v = ((uint64_t)S[(size_t)y * Wm + x] << 16) | 1ull;
+        g[k] = v;
+    }
+    __syncthreads();
+    if (t < BT::NSEG * P) {
+        const int c = t % P, s = t / P;
+        int base = P * (s * FF_SEG) + c;                                 // LDS index of the leftmost tap of the segment's first window
+        if (xt + base < Wm) {
+            uint64_t acc = 0ull;
+            for (int d = 0; d <= 2 * R; ++d) acc += g[base + P * d];
+            for (int k = 0;; ++k) {
+                res[base] = acc;                                         // base < TW
+                if (k + 1 == FF_SEG) break;
+                acc += g[base + P * (2 * R + 1)] - g[base];              // base <= TW - 2 P + c here: the tap in lies below TW + 2 halo = n
+                base += P;
+            }
+        }
+    }
+    __syncthreads();
+    uint64_t* o = ws + (size_t)y * Wm;
+    for (int k = t; k < BT::TW; k += FF_T)
+        if (xt + k < Wm) o[xt + k] = res[k];
+}
+
+// columns: the same sum down the rows of ws, then unpacked
+template <int P>
+__global__ __launch_bounds__(FF_T) void flat_box_cols_kernel(const uint64_t* __restrict__ ws, uint64_t* __restrict__ Bsum, uint32_t* __restrict__ Bcnt,
+                                                             int Hm, int Wm, int R, int tiles_x) {
+    const int x = (int)(blockIdx.x % (unsigned)tiles_x) * FF_T + threadIdx.x;
+    const int y0 = (int)(blockIdx.x / (unsigned)tiles_x) * BoxTile<P>::TH;
+    if (x >= Wm) return;
+    for (int r = 0; r < P; ++r) {
+        int y = y0 + r;
+        if (y >= Hm) break;
+        uint64_t acc = 0ull;
+        for (int d = -R; d <= R; ++d) {
+            const int yy = y + P * d;                                    // |P d| <= 384, y < 2^30
+            if (yy >= 0 && yy < Hm) acc += ws[(size_t)yy * Wm + x];
+        }
+        for (int k = 0; k < FF_VSEG && y < Hm; ++k) {
+            Bsum[(size_t)y * Wm + x] = acc >> 16;
+            Bcnt[(size_t)y * Wm + x] = (uint32_t)(acc & 0xFFFFull);
+            const int yin = y + P * (R + 1), yout = y - P * R;
+            if (yin < Hm) acc += ws[(size_t)yin * Wm + x];
+            if (yout >= 0) acc -= ws[(size_t)yout * Wm + x];
+            y += P;
+        }
+    }
+}
+
+// ---- the integer path ----------------------------------------------------------------------------------------------------------------------------
+// in and out may be the same buffer: a lane reads its own 8 codes of a frame before it writes them, and touches no others
+template <int P, bool VEC>
+__global__ __launch_bounds__(FF_T) void flat_apply_kernel(ApplyArgs a) {
+    __shared__ float s_blk[P * 12];
+    fill_cells<P>(s_blk, a.black);
+    __syncthreads();
+    const uint32_t units = (uint32_t)a.Hm * (uint32_t)a.lpr;
+    const size_t fsz = (size_t)a.Hm * a.Wm;
+    for (uint32_t i = blockIdx.x * FF_T + threadIdx.x; i < units; i += gridDim.x * FF_T) {
+        const int y = (int)(i / (uint32_t)a.lpr), x0 = (int)(i - (uint32_t)y * (uint32_t)a.lpr) * FF_NPX;
+        const size_t site = (size_t)y * a.Wm + x0;
+        const float* blk = s_blk + (y % P) * 12 + (P == 2 ? 0 : x0 % P);
+        float fg[FF_NPX];
+        if (VEC) {
+            const float4 g0 = reinterpret_cast<const float4*>(a.gain + site)[0], g1 = reinterpret_cast<const float4*>(a.gain + site)[1];
+            fg[0] = g0.x; fg[1] = g0.y; fg[2] = g0.z; fg[3] = g0.w; fg[4] = g1.x; fg[5] = g1.y; fg[6] = g1.z; fg[7] = g1.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < FF_NPX; ++j) fg[j] = x0 + j < a.Wm ? a.gain[site + j] : 1.f;
+        }
+        const uint32_t bad = a.bitmap ? a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31) : 0u;
+        for (int n = 0; n < a.N; ++n) {
+            uint32_t w[4], o[4];
+            load_codes<VEC>(a.in + (size_t)n * fsz + site, x0, a.Wm, w);
+            int q[FF_NPX];
+#pragma unroll
+            for (int j = 0; j < FF_NPX; ++j) {
+                const int u = (int)code_of(w, j);
+                const float v = (float)u - blk[j];
+                const float m = v * fg[j];
+                const float r = fminf(fmaxf(rintf(m + blk[j]), 0.f), 65535.f);           // ties to even; clamped before the conversion
+                q[j] = (((bad >> j) & 1u) || u >= a.white) ? u : (int)r;                 // a flagged or saturated site passes through
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k] = (uint32_t)q[2 * k] | ((uint32_t)q[2 * k + 1] << 16);
+            uint16_t* dst = a.out + (size_t)n * fsz + site;
+            if (VEC) {
+                *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x0 + 2 * k < a.Wm) *reinterpret_cast<uint32_t*>(dst + 2 * k) = o[k];
+            }
+        }
+    }
+}
+
+// ---- the inference input stage with the gain fused: pack_raw_shaded_kernel / pack_raw_xtrans_shaded_kernel of shading.hip with one more plane.
+// SHADE = false skips the subtraction (the operation order of pack_raw_kernel of noise.hip); ratios == nullptr skips the ratio (GAIN = false there).
+// v * 1.0f = v for every v, so a gain plane of ones gives the bits of those kernels.
+struct PackRawArgs { int oy[4], ox[4]; float black[4], denom[4]; };
+
+__device__ __forceinline__ float apply_ratio(float v, float ratio) { return fmaxf(fminf(v * ratio, 1.f), 0.f); }
+
+template <bool VMAP, bool SHADE>
+__global__ __launch_bounds__(256) void pack_raw_flat_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, PackRawArgs p,
+                                                            const float* __restrict__ ratios, const float* __restrict__ ma,
+                                                            const float* __restrict__ mb, float t, const float* __restrict__ gain) {
+    const int n = blockIdx.y;
+    const bool scaled = ratios != nullptr;
+    const float ratio = scaled ? ratios[n] : 1.f;
+    const size_t hw = (size_t)h * w, W2 = 2 * (size_t)w;
+    const uint16_t* src = im + (size_t)n * 4 * hw;
+    float* dst = out + (size_t)n * 4 * hw;
+    const int wp = (w + 1) / 2;                                     // position pairs per packed row
+    const size_t total = (size_t)h * wp;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const int y = (int)(i / wp), x = 2 * (int)(i - (size_t)y * wp);
+        const bool two = x + 1 < w;
+        uint16_t q[2][4];                                           // q[row][col] of the 2 x 4 mosaic block
+        float ds[2][4], gn[2][4];                                   // a + b t and the gain of the same sites
+        const size_t m0 = (size_t)(2 * y) * W2 + 2 * x;
+        const uint16_t* r0 = src + m0;
+        if (two && ((W2 & 3) == 0)) {
+            const ushort4 a = *reinterpret_cast<const ushort4*>(r0), b = *reinterpret_cast<const ushort4*>(r0 + W2);
+            q[0][0] = a.x; q[0][1] = a.y; q[0][2] = a.z; q[0][3] = a.w; q[1][0] = b.x; q[1][1] = b.y; q[1][2] = b.z; q[1][3] = b.w;
+        } else {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { const bool ok = c < 2 || two; q[0][c] = ok ? r0[c] : 0; q[1][c] = ok ? r0[W2 + c] : 0; }
+        }
+        if (VMAP && two) {
+#pragma unroll
+            for (int r = 0; r < 2; ++r) {
+                const float4 vg = *reinterpret_cast<const float4*>(gain + m0 + r * W2);
+                gn[r][0] = vg.x; gn[r][1] = vg.y; gn[r][2] = vg.z; gn[r][3] = vg.w;
+                if (SHADE) {
+                    const float4 va = *reinterpret_cast<const float4*>(ma + m0 + r * W2), vb = *reinterpret_cast<const float4*>(mb + m0 + r * W2);
+                    ds[r][0] = va.x + vb.x * t; ds[r][1] = va.y + vb.y * t; ds[r][2] = va.z + vb.z * t; ds[r][3] = va.w + vb.w * t;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const bool ok = c < 2 || two;
+                    gn[r][c] = ok ? gain[m0 + r * W2 + c] : 1.f;
+                    if (SHADE) ds[r][c] = ok ? ma[m0 + r * W2 + c] + mb[m0 + r * W2 + c] * t : 0.f;
+                }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float b0 = (float)q[p.oy[k]][p.ox[k]] - p.black[k], b1 = (float)q[p.oy[k]][2 + p.ox[k]] - p.black[k];
+            if (SHADE) { b0 = b0 - ds[p.oy[k]][p.ox[k]]; b1 = b1 - ds[p.oy[k]][2 + p.ox[k]]; }
+            const float v0 = (b0 * gn[p.oy[k]][p.ox[k]]) / p.denom[k];
+            const float v1 = (b1 * gn[p.oy[k]][2 + p.ox[k]]) / p.denom[k];
+            float* o = dst + (size_t)k * hw + (size_t)y * w + x;
+            float o0 = fminf(fmaxf(v0, 0.f), 1.f), o1 = fminf(fmaxf(v1, 0.f), 1.f);
+            if (scaled) { o0 = apply_ratio(o0, ratio); o1 = apply_ratio(o1, ratio); }
+            o[0] = o0;
+            if (two) o[1] = o1;
+        }
+    }
+}
+
+// one thread per packed element, as pack_raw_xtrans_kernel
+template <bool SHADE>
+__global__ __launch_bounds__(256) void pack_raw_xtrans_flat_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, int Hm, int Wm,
+                                                                   float black, float denom, const float* __restrict__ ratios,
+                                                                   const float* __restrict__ ma, const float* __restrict__ mb, float t,
+                                                                   const float* __restrict__ gain) {
+    const int n = blockIdx.y;
+    const bool scaled = ratios != nullptr;
+    const float ratio = scaled ? ratios[n] : 1.f;
+    const size_t hw = (size_t)h * w, total = 9 * hw;
+    const uint16_t* s = im + (size_t)n * Hm * Wm;
+    float* d = out + (size_t)n * total;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
+        const int c = (int)(e / hw);
+        const int r = (int)(e - (size_t)c * hw);
+        const int i = r / w, j = r - i * w;
+        int row, col;
+        if (c < 5) { row = 6 * (i >> 1) + XT_RC[c][i & 1][j & 1][0]; col = 6 * (j >> 1) + XT_RC[c][i & 1][j & 1][1]; }
+        else { row = 3 * i + XT_RC3[c - 5][0]; col = 3 * j + XT_RC3[c - 5][1]; }
+        const size_t m = (size_t)row * Wm + col;
+        float b = (float)s[m] - black;
+        if (SHADE) b = b - (ma[m] + mb[m] * t);
+        const float v = (b * gain[m]) / denom;
+        const float o = fminf(fmaxf(v, 0.f), 1.f);
+        d[e] = scaled ? apply_ratio(o, ratio) : o;
+    }
+}
+
+// workgroups of a grid-stride pass over `units` lanes' worth of work: at most 8 per compute unit
+unsigned stride_grid(uint32_t units) {
+    const long long nb = ((long long)units + FF_T - 1) / FF_T, cap = 8ll * eld_num_cus();
+    return (unsigned)(nb < cap ? nb : cap);
+}
+
+bool bad_shape(int Hm, int Wm) { return Hm < 0 || Wm < 0 || Wm % 2 || (uint64_t)Hm * (uint64_t)Wm >= (1ull << 31); }
+
+template <int P>
+int box_launch(const uint32_t* S, const uint32_t* bad, int Hm, int Wm, int radius, uint64_t* Bsum, uint32_t* Bcnt, uint64_t* ws, hipStream_t st) {
+    const int wpr = (Wm + 31) / 32;
+    const long long tx = (Wm + BoxTile<P>::TW - 1) / BoxTile<P>::TW, nb1 = tx * Hm;
+    const long long cx = (Wm + FF_T - 1) / FF_T, nb2 = cx * ((Hm + BoxTile<P>::TH - 1) / BoxTile<P>::TH);
+    if (nb1 > 0x7FFFFFFFll || nb2 > 0x7FFFFFFFll) return ELD_EINVAL;
+    ELD_LAUNCH(flat_box_rows_kernel<P>, dim3((unsigned)nb1), dim3(FF_T), 0, st, S, bad, ws, Hm, Wm, wpr, radius, (int)tx);
+    ELD_LAUNCH_CHECK();
+    ELD_LAUNCH(flat_box_cols_kernel<P>, dim3((unsigned)nb2), dim3(FF_T), 0, st, ws, Bsum, Bcnt, Hm, Wm, radius, (int)cx);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int eld_flat_sums_u16(const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int Hm, int Wm, int white_level,
+                                 const uint32_t* bitmap, uint32_t* S, uint64_t* D, uint32_t* bad, void* stream) {
+    if (bad_shape(Hm, Wm) || F < 2 || F % 2 || F > FF_MAX_FRAMES || white_level < 1 || white_level > 65536) return ELD_EINVAL;
+    if (((uintptr_t)pool & 3u) || ((uintptr_t)bitmap & 3u) || ((uintptr_t)frames & 7u) || ((uintptr_t)S & 3u) || ((uintptr_t)D & 7u) || ((uintptr_t)bad & 3u))
+        return ELD_EINVAL;
+    if (Hm == 0 || Wm == 0) return 0;
+    if (!pool || !frames || !S || !D || !bad) return ELD_EINVAL;
+    SumsArgs a;
+    a.pool = pool; a.pool_elems = pool_elems; a.frames = frames; a.bitmap = bitmap; a.S = S; a.D = D; a.bad = bad;
+    a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32; a.lpr = (Wm + FF_NPX - 1) / FF_NPX; a.F = F; a.white = white_level;
+    a.vec_in = Wm % FF_NPX == 0 && !((uintptr_t)pool & 15u);
+    a.vec_out = Wm % FF_NPX == 0 && !(((uintptr_t)S | (uintptr_t)D) & 15u);
+    ELD_LAUNCH(flat_sums_kernel, dim3(stride_grid((uint32_t)Hm * (uint32_t)a.lpr)), dim3(FF_T), 0, as_stream(stream), a);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" size_t eld_flat_box_workspace_bytes(int Hm, int Wm) {
+    if (bad_shape(Hm, Wm)) return 0;
+    return (size_t)Hm * (size_t)Wm * sizeof(uint64_t);
+}
+
+extern "C" int eld_flat_box_tile(int period, int* row_pass_columns, int* column_pass_rows) {
+    if ((period != 2 && period != 6) || !row_pass_columns || !column_pass_rows) return ELD_EINVAL;
+    *row_pass_columns = period == 2 ? BoxTile<2>::TW : BoxTile<6>::TW;
+    *column_pass_rows = period == 2 ? BoxTile<2>::TH : BoxTile<6>::TH;
+    return 0;
+}
+
+extern "C" int eld_flat_box_u32(const uint32_t* S, const uint32_t* bad, int Hm, int Wm, int period, int radius, uint64_t* Bsum, uint32_t* Bcnt,
+                                void* ws, size_t ws_bytes, void* stream) {
+    if ((period != 2 && period != 6) || bad_shape(Hm, Wm) || radius < 0 || radius > FF_MAX_RADIUS) return ELD_EINVAL;
+    if (((uintptr_t)S & 3u) || ((uintptr_t)bad & 3u) || ((uintptr_t)Bsum & 7u) || ((uintptr_t)Bcnt & 3u) || ((uintptr_t)ws & 7u)) return ELD_EINVAL;
+    if (Hm == 0 || Wm == 0) return 0;
+    if (!S || !bad || !Bsum || !Bcnt || !ws) return ELD_EINVAL;
+    if (ws_bytes < eld_flat_box_workspace_bytes(Hm, Wm)) return ELD_EWS;
+    if (period == 2) return box_launch<2>(S, bad, Hm, Wm, radius, Bsum, Bcnt, (uint64_t*)ws, as_stream(stream));
+    return box_launch<6>(S, bad, Hm, Wm, radius, Bsum, Bcnt, (uint64_t*)ws, as_stream(stream));
+}
+
+extern "C" int eld_flat_apply_u16(const uint16_t* in, uint16_t* out, int N, int Hm, int Wm, const float* gain, const float* black, int period,
+                                  int white_level, const uint32_t* bitmap, void* stream) {
+    if ((period != 2 && period != 6) || bad_shape(Hm, Wm) || N < 0 || white_level < 1 || white_level > 65536 || !black) return ELD_EINVAL;
+    for (int k = 0; k < period * period; ++k)
+        if (!(black[k] >= 0.f && black[k] <= 65535.f)) return ELD_EINVAL;
+    if (((uintptr_t)in & 3u) || ((uintptr_t)out & 3u) || ((uintptr_t)bitmap & 3u) || ((uintptr_t)gain & 3u)) return ELD_EINVAL;
+    if (N == 0 || Hm == 0 || Wm == 0) return 0;
+    if (!in || !out || !gain) return ELD_EINVAL;
+    ApplyArgs a;
+    a.in = in; a.out = out; a.gain = gain; a.bitmap = bitmap;
+    a.N = N; a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32; a.lpr = (Wm + FF_NPX - 1) / FF_NPX; a.white = white_level;
+    for (int k = 0; k < 36; ++k) a.black[k] = k < period * period ? black[k] : 0.f;
+    // Wm % 8 == 0 makes a frame a multiple of 16 bytes: every frame of an aligned stack is aligned
+    const bool vec = Wm % FF_NPX == 0 && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)gain) & 15u);
+    const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr));
+    if (period == 2) {
+        if (vec) ELD_LAUNCH((flat_apply_kernel<2, true>), grid, dim3(FF_T), 0, as_stream(stream), a);
+        else ELD_LAUNCH((flat_apply_kernel<2, false>), grid, dim3(FF_T), 0, as_stream(stream), a);
+    } else {
+        if (vec) ELD_LAUNCH((flat_apply_kernel<6, true>), grid, dim3(FF_T), 0, as_stream(stream), a);
+        else ELD_LAUNCH((flat_apply_kernel<6, false>), grid, dim3(FF_T), 0, as_stream(stream), a);
+    }
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int eld_pack_raw_bayer_u16_flat(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern,
+                                           const float* black_level, float white_point, const float* ratios, const float* ma, const float* mb,
+                                           float t, const float* gain, void* stream) {
+    if (N < 0 || h < 0 || w < 0 || !raw_pattern || !black_level) return ELD_EINVAL;
+    if (((uintptr_t)ma & 3u) || ((uintptr_t)mb & 3u) || ((uintptr_t)gain & 3u) || (ma == nullptr) != (mb == nullptr)) return ELD_EINVAL;
+    if (N == 0 || h == 0 || w == 0) return 0;
+    if (!mosaic || !packed || !gain) return ELD_EINVAL;
+    PackRawArgs p;
+    bool seen[4] = {false, false, false, false};
+    for (int i = 0; i < 4; ++i) {                                    // position of colour code k in the 2x2 cell, as eld_pack_raw_bayer_u16
+        const int k = raw_pattern[i];
+        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
+        seen[k] = true; p.oy[k] = i >> 1; p.ox[k] = i & 1;
+    }
+    for (int k = 0; k < 4; ++k) { p.black[k] = black_level[k]; p.denom[k] = white_point - black_level[k]; }
+    const size_t total = (size_t)h * ((w + 1) / 2);
+    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
+    // a lane's first site of a row is (2 y') * 2w + 4 x': a multiple of 4 sites when 2w is; N frames share the planes
+    const bool vmap = (2 * (size_t)w) % 4 == 0 && !(((uintptr_t)ma | (uintptr_t)mb | (uintptr_t)gain) & 15u);
+    const hipStream_t st = as_stream(stream);
+    if (ma) {
+        if (vmap) ELD_LAUNCH((pack_raw_flat_kernel<true, true>), grid, dim3(256), 0, st, mosaic, packed, h, w, p, ratios, ma, mb, t, gain);
+        else ELD_LAUNCH((pack_raw_flat_kernel<false, true>), grid, dim3(256), 0, st, mosaic, packed, h, w, p, ratios, ma, mb, t, gain);
+    } else {
+        if (vmap) ELD_LAUNCH((pack_raw_flat_kernel<true, false>), grid, dim3(256), 0, st, mosaic, packed, h, w, p, ratios, ma, mb, t, gain);
+        else ELD_LAUNCH((pack_raw_flat_kernel<false, false>), grid, dim3(256), 0, st, mosaic, packed, h, w, p, ratios, ma, mb, t, gain);
+    }
+    ELD_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int eld_pack_raw_xtrans_u16_flat(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
+                                            const float* ratios, const float* ma, const float* mb, float t, const float* gain, void* stream) {
+    if (N < 0 || Hm < 0 || Wm < 0 || !(white_point > black_level)) return ELD_EINVAL;
+    if (((uintptr_t)ma & 3u) || ((uintptr_t)mb & 3u) || ((uintptr_t)gain & 3u) || (ma == nullptr) != (mb == nullptr)) return ELD_EINVAL;
+    const int h = 2 * (Hm / 6), w = 2 * (Wm / 6);
+    const size_t total = (size_t)9 * h * w;
+    if (N == 0 || total == 0) return 0;
+    if (!mosaic || !packed || !gain) return ELD_EINVAL;
+    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
+    const hipStream_t st = as_stream(stream);
+    if (ma) ELD_LAUNCH(pack_raw_xtrans_flat_kernel<true>, grid, dim3(256), 0, st, mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level,
+                       ratios, ma, mb, t, gain);
+    else ELD_LAUNCH(pack_raw_xtrans_flat_kernel<false>, grid, dim3(256), 0, st, mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level,
+                    ratios, ma, mb, t, gain);
+    ELD_LAUNCH_CHECK();
+    return 0;
+}

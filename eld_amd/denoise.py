@@ -37,6 +37,7 @@ from . import _lib as L
 PLANES = {'bayer': 4, 'xtrans': 9}
 ROUNDING = ('nearest', 'reference')
 SRGB_SIZES = ('packed', 'full')
+LENS_MODES = ('off', 'srgb', 'all')                  # where the lens plane of a flat-field map applies (eld_amd.flatfield)
 DEFAULT_BLACK = {'bayer': 512, 'xtrans': 1024}      # SID Sony (rawpy black_level_per_channel) / the reference's X-Trans constant
 DEFAULT_PATTERN = ((0, 1), (3, 2))                   # RGGB as rawpy codes (R 0, G1 1, B 2, G2 3)
 
@@ -197,13 +198,28 @@ def _colour(cfa, wb, ccm, N):
 
 
 # ---- the device stages ------------------------------------------------------------------------------------------------------------
-def pack_input(t, cfa, raw_pattern, black_level, white_point, ratios, shading=None, tval=None):
+def pack_input(t, cfa, raw_pattern, black_level, white_point, ratios, shading=None, tval=None, flatfield=None):
     """CUDA int16-view codes (N,Hm,Wm) -> the network input (N,C,h,w) float32: pack, x ratio[n], clip -- one kernel.  shading (a
     DarkShading) with tval = shading.t(iso): the same kernel shape with the map a + b * tval subtracted in float32 between the black level
-    and the division (eld_pack_raw_*_u16_shaded)."""
+    and the division (eld_pack_raw_*_u16_shaded).  flatfield (a FlatField): the black- and shading-corrected value is multiplied by the
+    map's PRNU plane before the division (eld_pack_raw_*_u16_flat), with or without a shading map."""
     import torch
     N, Hm, Wm = t.shape
     r = torch.as_tensor(np.asarray(ratios, np.float32), device=t.device)
+    if flatfield is not None:
+        ma, mb = shading.on(t.device) if shading is not None else (None, None)
+        tv = float(tval) if shading is not None else 0.0
+        gain = flatfield.on(t.device, 'prnu')
+        if cfa == 'bayer':
+            out = torch.empty((N, 4, Hm // 2, Wm // 2), dtype=torch.float32, device=t.device)
+            L.check(L.lib().eld_pack_raw_bayer_u16_flat(L.dptr(t), L.dptr(out), N, Hm // 2, Wm // 2, (ctypes.c_int * 4)(*raw_pattern),
+                                                        (ctypes.c_float * 4)(*black_level), float(white_point), L.dptr(r), L.dptr(ma), L.dptr(mb), tv,
+                                                        L.dptr(gain), L.cur_stream()), 'eld_pack_raw_bayer_u16_flat')
+        else:
+            out = torch.empty((N, 9, 2 * (Hm // 6), 2 * (Wm // 6)), dtype=torch.float32, device=t.device)
+            L.check(L.lib().eld_pack_raw_xtrans_u16_flat(L.dptr(t), L.dptr(out), N, Hm, Wm, float(black_level[0]), float(white_point), L.dptr(r),
+                                                         L.dptr(ma), L.dptr(mb), tv, L.dptr(gain), L.cur_stream()), 'eld_pack_raw_xtrans_u16_flat')
+        return out
     if shading is not None:
         ma, mb = shading.on(t.device)
         if cfa == 'bayer':
@@ -258,7 +274,8 @@ def run_network(denoiser, x, chop=None):
 
 
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
-                chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None, shading=None, iso=None):
+                chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None, shading=None, iso=None, flatfield=None,
+                lens='srgb'):
     """Denoise uint16 sensor mosaics with a trained U-Net.
 
     mosaic_u16  NumPy uint16 array or CUDA uint16 / int16-view tensor, (Hm, Wm) or (N, Hm, Wm) -- rawpy's raw_image_visible.
@@ -281,6 +298,11 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                 (eld_pack_raw_*_u16_shaded) -- the ratio would otherwise multiply it into visible columns and blotches.  The write-back is
                 unchanged: the network's output estimates the clean signal above the nominal black level.  shading without iso, a map
                 of another shape, CFA or Bayer pattern, or an ISO outside the map's range is a ValueError.
+    flatfield, lens  a FlatField (eld_amd.flatfield) or the path of a saved one.  The network input is multiplied by its PRNU plane only,
+                fused into the input stage (eld_pack_raw_*_u16_flat): lens gain in front of the network would raise the corners' noise
+                above what the noise model trained it on.  The lens plane multiplies the network's OUTPUT, before the clip the output
+                stages apply: lens='srgb' (default) in the sRGB rendering only -- the mosaic written back stays a raw frame a converter
+                may still lens-correct; 'all' in the write-back too; 'off' nowhere.  'packed' is the network's own output in every mode.
 
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
@@ -326,6 +348,13 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         tval = shading.t(iso)
     elif iso is not None:
         raise ValueError('iso is the abscissa of a dark-shading map: pass shading= with it')
+    if not isinstance(lens, str) or lens not in LENS_MODES:
+        raise ValueError('lens must be one of %r, got %r' % (LENS_MODES, lens))
+    if flatfield is not None:
+        from .flatfield import as_flat_field
+        flatfield = as_flat_field(flatfield)
+        flatfield.check_frames((Hm, Wm), cfa, 'denoise_raw')
+        flatfield.check_pattern(None if cfa == 'xtrans' else np.asarray(pat).reshape(2, 2), 'denoise_raw')
     if srgb_size == 'full' and cfa == 'bayer' and (pat[0] & 1) != (pat[3] & 1):
         raise ValueError('the full-size render needs a Bayer raw_pattern with its greens on a diagonal, got %r' % (raw_pattern,))
 
@@ -342,10 +371,17 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     t3 = t if batched else t.unsqueeze(0)
     if defects is not None:
         t3 = repair_device(t3, defects)
-    x = pack_input(t3, cfa, pat, blk, white, ratios, shading, tval)
-    out = run_network(denoiser, x, chop)
+    if flatfield is None:
+        x = pack_input(t3, cfa, pat, blk, white, ratios, shading, tval)
+    else:
+        x = pack_input(t3, cfa, pat, blk, white, ratios, shading, tval, flatfield)
+    net_out = out = run_network(denoiser, x, chop)
     mosaic = t3.clone()                   # X-Trans: the borders outside whole cells keep the input's codes
-    write_back(out, mosaic, cfa, pat, blk, white, rounding)
+    if flatfield is not None and lens != 'off':
+        out = net_out * flatfield.packed_lens(dev)             # what the sRGB stages below render; they and the write-back clip after it
+        write_back(out if lens == 'all' else net_out, mosaic, cfa, pat, blk, white, rounding)
+    else:
+        write_back(out, mosaic, cfa, pat, blk, white, rounding)
     srgb = lin = None
     if wbs is not None and srgb_size == 'full':
         from .isp import render_bayer, render_xtrans
@@ -364,12 +400,12 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     if not batched:
         mosaic = mosaic[0]
     if kind == 'numpy':
-        res = {'packed': out.cpu().numpy(), 'mosaic': mosaic.cpu().numpy().view(np.uint16),
+        res = {'packed': net_out.cpu().numpy(), 'mosaic': mosaic.cpu().numpy().view(np.uint16),
                'srgb': None if srgb is None else srgb.cpu().numpy()}
         if lin is not None:
             res['linear'] = lin.cpu().numpy()
         return res
-    res = {'packed': out, 'mosaic': mosaic, 'srgb': srgb}
+    res = {'packed': net_out, 'mosaic': mosaic, 'srgb': srgb}
     if lin is not None:
         res['linear'] = lin
     return res
@@ -379,7 +415,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
 SIDECAR_ALIASES = {'black_level_per_channel': 'black_level', 'white_level': 'white_point', 'camera_whitebalance': 'wb',
                    'rgb_camera_matrix': 'ccm', 'black': 'black_level', 'white': 'white_point'}
 SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size', 'defects',
-                'shading', 'iso')
+                'shading', 'iso', 'flatfield', 'lens')
 
 
 def read_sidecar(path):
@@ -397,7 +433,7 @@ def sidecar_from_dict(d, path):
     out = {}
     for k, v in d.items():
         k = SIDECAR_ALIASES.get(k, k)
-        if k in ('defects', 'shading') and isinstance(v, str):             # a saved defect / dark-shading map, relative to the sidecar
+        if k in ('defects', 'shading', 'flatfield') and isinstance(v, str):  # a saved defect / dark-shading / flat-field map, relative to the sidecar
             v = os.path.join(os.path.dirname(os.path.abspath(path)), v)
         if k not in SIDECAR_KEYS:
             raise ValueError('%s: unknown key %r (known: %s)' % (path, k, ', '.join(SIDECAR_KEYS + tuple(SIDECAR_ALIASES))))
@@ -429,6 +465,8 @@ def build_parser():
     p.add_argument('--defects', metavar='PATH', help='a defect map written by eld_amd.defects (.npz): its sites are repaired before the network')
     p.add_argument('--shading', metavar='FILE', help='a dark-shading map written by eld_amd.shading (.npz): subtracted in the input stage; needs --iso')
     p.add_argument('--iso', type=float, help='the ISO the frames were shot at (the abscissa of --shading)')
+    p.add_argument('--flatfield', metavar='FILE', help='a flat-field map written by eld_amd.flatfield (.npz): PRNU in the input stage, lens gain on the output')
+    p.add_argument('--lens', choices=LENS_MODES, help="where the lens plane of --flatfield applies: the sRGB rendering ('srgb', the default), the written-back mosaic too ('all'), nowhere ('off')")
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
     return p
 
@@ -438,7 +476,7 @@ def parse_args(argv):
     a = build_parser().parse_args(argv)
     o = read_sidecar(a.meta) if a.meta else {}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
-           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'precision': 'bf16' if a.bf16 else None,
+           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'precision': 'bf16' if a.bf16 else None,
            'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
     o.update({k: v for k, v in cli.items() if v is not None})
     o.setdefault('cfa', 'bayer')
@@ -465,6 +503,10 @@ def parse_args(argv):
         raise ValueError('--srgb-size full needs --wb and --ccm')
     if o.get('shading') is not None and o.get('iso') is None:
         raise ValueError('--shading needs --iso')
+    if o.get('lens') is not None and o['lens'] not in LENS_MODES:
+        raise ValueError('lens must be one of %r, got %r' % (LENS_MODES, o['lens']))
+    if o.get('lens') is not None and o.get('flatfield') is None:
+        raise ValueError('--lens needs --flatfield')
     return a.inputs, a.out, a.ckpt, o
 
 
@@ -488,6 +530,9 @@ def main(argv=None):
     if o.get('shading') is not None:
         from .shading import as_dark_shading
         kw['shading'], kw['iso'] = as_dark_shading(o['shading'], '--shading'), o['iso']
+    if o.get('flatfield') is not None:
+        from .flatfield import as_flat_field
+        kw['flatfield'], kw['lens'] = as_flat_field(o['flatfield'], '--flatfield'), o.get('lens') or 'srgb'
     for path in inputs:
         raw = np.load(path)
         res = denoise_raw(den, raw, o['cfa'], **kw)

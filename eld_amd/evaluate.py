@@ -299,7 +299,7 @@ def table_by_iso_ratio(rows):
 
 
 def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, white_point=16383, correct=True, crop=None, chop=None, defects=None,
-                   shading=None, levels=True, on_pair=None):
+                   shading=None, levels=True, on_pair=None, flatfield=None):
     """Evaluate `denoiser` (denoise.load_denoiser) on captured pairs, as the reference's test scripts do.
 
     pairs     a list of dicts: 'short' and 'long' (uint16 mosaics (Hm,Wm): NumPy, or CUDA uint16 / int16-view tensors) and either 'ratio' or
@@ -309,6 +309,8 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
     crop      None, or N: the centre crop of N x N packed pixels the reference's evaluation takes (512), input and target alike.
     chop      as denoise_raw: None = whole frame when the packed sides are multiples of 16, else forward_chop.
     defects, shading   as denoise_raw: both mosaics are repaired with the map; the dark shading is subtracted from the short exposure only.
+    flatfield a FlatField (eld_amd.flatfield) or the path of a saved one: its PRNU plane multiplies the short exposure in the input stage
+              (as denoise_raw) and the long exposure through the integer path (FlatField.apply(part='prnu')), after the repair.
     levels    also the error-versus-signal sums (pair_level_stats) of the corrected output and of the clipped input, both written back to
               codes with rounding='nearest', against the long exposure's codes.
     on_pair   called as on_pair(index, row, {'input', 'output', 'target'}) with the packed CUDA tensors of each pair (the command line's --save).
@@ -336,8 +338,14 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
     if defects is not None:
         from .defects import as_defect_map
         defects = as_defect_map(defects)
+    if flatfield is not None:
+        from .flatfield import as_flat_field
+        flatfield = as_flat_field(flatfield)
+        flatfield.check_pattern(None if cfa == 'xtrans' else np.asarray(pat).reshape(2, 2), 'evaluate_pairs')
     info = _check_pairs(pairs, cfa, crop, shading)
     for i, (_, shape, _, iso) in enumerate(info):
+        if flatfield is not None:
+            flatfield.check_frames(shape, cfa, 'pair %d' % i)
         if defects is not None:
             defects.check_frames(shape, cfa, 'pair %d' % i)
         if shading is not None:
@@ -359,7 +367,11 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
             if defects is not None:
                 from .defects import repair_device
                 short, long_ = repair_device(short, defects), repair_device(long_, defects)
-            x = pack_input(short, cfa, pat, blk, white, [ratio], shading, None if shading is None else shading.t(iso))
+            if flatfield is not None:
+                x = pack_input(short, cfa, pat, blk, white, [ratio], shading, None if shading is None else shading.t(iso), flatfield)
+                long_ = flatfield.apply(long_, part='prnu', black_level=blk, defects=defects)
+            else:
+                x = pack_input(short, cfa, pat, blk, white, [ratio], shading, None if shading is None else shading.t(iso))
             target = pack_input(long_, cfa, pat, blk, white, [1.0])
             y0 = x0 = 0
             if crop is not None:
@@ -419,7 +431,7 @@ def curve_lines(pooled, groups):
 
 # ---- command line -----------------------------------------------------------------------------------------------------------------------
 PAIR_KEYS = ('short', 'long', 'ratio', 'iso', 'exposure', 'long_iso', 'long_exposure', 'name')
-OPTION_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'wb', 'ccm', 'precision', 'chop', 'defects', 'shading')
+OPTION_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'wb', 'ccm', 'precision', 'chop', 'defects', 'shading', 'flatfield')
 
 
 def read_manifest(path):
@@ -479,6 +491,7 @@ def build_parser():
     p.add_argument('--crop', type=int, help='centre crop of N x N packed pixels (the reference evaluates 512)')
     p.add_argument('--defects', metavar='F', help='a defect map written by eld_amd.defects (.npz)')
     p.add_argument('--shading', metavar='F', help='a dark-shading map written by eld_amd.shading (.npz); every pair then needs iso')
+    p.add_argument('--flatfield', metavar='F', help='a flat-field map written by eld_amd.flatfield (.npz): its PRNU plane corrects both exposures')
     p.add_argument('--json', metavar='OUT', help='write the whole report as JSON')
     p.add_argument('--save', metavar='DIR', help='write sRGB PNGs of input, output and target at packed resolution (needs wb and ccm)')
     return p
@@ -492,7 +505,7 @@ def parse_args(argv):
     if a.meta:
         side = read_sidecar(a.meta)
         o.update({k: v for k, v in side.items() if k in OPTION_KEYS})
-    cli = {'defects': a.defects, 'shading': a.shading, 'precision': 'bf16' if a.bf16 else None}
+    cli = {'defects': a.defects, 'shading': a.shading, 'flatfield': a.flatfield, 'precision': 'bf16' if a.bf16 else None}
     o.update({k: v for k, v in cli.items() if v is not None})
     o = {k: v for k, v in o.items() if k in OPTION_KEYS}
     o.setdefault('cfa', 'bayer')
@@ -532,7 +545,7 @@ def main(argv=None):
     den = load_denoiser(a.ckpt, cfa=o['cfa'], precision=o['precision'])
     rep = evaluate_pairs(den, load_pairs(pairs), o['cfa'], raw_pattern=o.get('raw_pattern'), black_level=o.get('black_level'),
                          white_point=o['white_point'], correct=not a.no_correct, crop=a.crop, chop=o.get('chop'), defects=o.get('defects'),
-                         shading=o.get('shading'), on_pair=_saver(a.save, o['cfa'], o['wb'], o['ccm']) if a.save else None)
+                         shading=o.get('shading'), flatfield=o.get('flatfield'), on_pair=_saver(a.save, o['cfa'], o['wb'], o['ccm']) if a.save else None)
     for line in table_lines(rep['table']):
         print(line)
     print('mean over %d pairs: PSNR %.3f SSIM %.4f (input: %.3f %.4f)' % (len(rep['pairs']), rep['mean']['psnr'], rep['mean']['ssim'],

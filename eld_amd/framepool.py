@@ -57,11 +57,14 @@ class FramePool:
     cfa, raw_pattern, black_level, white_point   as eld_amd.denoise.denoise_raw (same checks, same defaults).
     defects      a DefectMap (eld_amd.defects) or the path of a saved one: every frame is repaired once, at upload (no per-step cost);
                  every frame must then have the map's shape.  Paired mode takes the same map for both pools.
+    flatfield    a FlatField (eld_amd.flatfield) or the path of a saved one: after the repair every frame is multiplied by the map's PRNU
+                 plane through the integer path (FlatField.apply(part='prnu'), in place, once, at upload): averaging the exposures of a
+                 clean target does not remove a fixed pattern.  Every frame must have the map's shape.
     device       the CUDA device of the pool (default: the current one).  Without a GPU the pool keeps its geometry only: grid() and the
                  loader's draws work, patches() does not.
     Bad arguments raise ValueError before any device work; a missing libeld_amd raises LibraryMissing."""
 
-    def __init__(self, mosaics, cfa='bayer', raw_pattern=None, black_level=None, white_point=16383, device=None, defects=None):
+    def __init__(self, mosaics, cfa='bayer', raw_pattern=None, black_level=None, white_point=16383, device=None, defects=None, flatfield=None):
         _check_cfa(cfa)
         if isinstance(mosaics, np.ndarray) or hasattr(mosaics, 'is_cuda'):
             mosaics = [mosaics]
@@ -81,6 +84,13 @@ class FramePool:
         self.defects = defects
         self.cfa, self.C = cfa, PLANES[cfa]
         self.raw_pattern, self.black_level, self.white_point = _levels(cfa, raw_pattern, black_level, white_point)
+        if flatfield is not None:
+            from .flatfield import as_flat_field
+            flatfield = as_flat_field(flatfield)
+            for i, m in enumerate(frames):
+                flatfield.check_frames(m.shape, cfa, 'frame %d' % i)
+            flatfield.check_pattern(None if cfa == 'xtrans' else np.asarray(self.raw_pattern).reshape(2, 2), 'FramePool')
+        self.flatfield = flatfield
         table = np.zeros(len(frames), L.POOL_FRAME_DTYPE)
         off = 0
         for i, m in enumerate(frames):
@@ -112,6 +122,10 @@ class FramePool:
             for f in self.frames:                             # in place, frame by frame (the frames start 16-byte aligned, not back to back)
                 v = buf[int(f['offset']):int(f['offset']) + int(f['Hm']) * int(f['Wm'])].view(1, int(f['Hm']), int(f['Wm']))
                 repair_device(v, self.defects, v)
+        if self.flatfield is not None:
+            for f in self.frames:
+                v = buf[int(f['offset']):int(f['offset']) + int(f['Hm']) * int(f['Wm'])].view(1, int(f['Hm']), int(f['Wm']))
+                self.flatfield.apply(v, part='prnu', black_level=self.black_level, defects=self.defects, out=v)
         self.buffer, self.device = buf, dev
         self._table_dev = torch.from_numpy(self.frames.view(np.uint8).copy()).to(dev)
 

@@ -32,6 +32,8 @@ def build_parser():
     p.add_argument('--black', type=float, nargs='+', help='black level(s): 1 or 4 (Bayer), 1 (X-Trans)')
     p.add_argument('--white', type=float, help='white point (default 16383)')
     p.add_argument('--defects', metavar='PATH', help='a defect map written by eld_amd.defects (.npz): the frames are repaired once, at upload')
+    p.add_argument('--flatfield', metavar='FILE', help="a flat-field map written by eld_amd.flatfield (.npz): the clean frames are multiplied by its "
+                                                       'PRNU plane once, at upload (the dark frames carry no signal and are left alone)')
     p.add_argument('--camera', default='SonyA7S2', help='a table written by eld_amd.calibrate (<dir>/<name>_params.npy) or a release camera name')
     p.add_argument('--noise', default='PGRU', help="noise model letters of NoiseModel(model=...) (default 'PGRU')")
     p.add_argument('--dark', metavar='MANIFEST', help="calibrate's manifest JSON: its bias frames become the dark-frame pool of noise letter D (--noise PDU)")
@@ -116,6 +118,8 @@ def main(argv=None):
     from .framepool import FramePool, FramePoolLoader
     np.random.seed(a.seed)
     torch.manual_seed(a.seed)
+    if a.flatfield is not None:
+        o['flatfield'] = a.flatfield
     pool = FramePool(mosaics, cfa=cfa, defects=a.defects if a.defects is not None else side.get('defects'), **o)
     if pool.buffer is None:
         raise RuntimeError('eld_amd.train_frames needs a GPU: there is no CPU fallback')

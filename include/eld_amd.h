@@ -791,6 +791,48 @@ enum { ELD_REGION_EA = 0, ELD_REGION_EB = 1, ELD_REGION_POOL = 2, ELD_REGION_UP 
 int eld_debug_unet_region(int N, int H, int W, int in_ch, int out_ch, int precision, int region, int level, size_t* offset, int* channels,
                           int* dtype);
 
+/* ---- flat-field maps: what multiplies the signal, from the flat frames (csrc/flatfield.hip, eld_amd/flatfield.py) -----------
+ * Appended without a change of ELD_ABI_VERSION (no existing signature changed), as eld_debug_conv_kernel_count above.  tests/flatfield_ref.py
+ * restates every line below in NumPy; the first two passes are integer arithmetic and defined bit for bit whatever the launch geometry.
+ *
+ * eld_flat_sums_u16: pool, pool_elems, frames as eld_shading_fit_u16 takes them (a frame pool and its EldPoolFrame table); the F table entries
+ * are the flat frames, entries 2k and 2k + 1 a pair; F even, 2 <= F <= 65536; Hm * Wm < 2^31, Wm even.  Per site, over the F codes u_f:
+ *   S   [Hm,Wm] uint32 = sum of u_f
+ *   D   [Hm,Wm] uint64 = sum over the pairs of (u_2k - u_2k+1)^2
+ *   bad [Hm,ceil(Wm/32)] uint32, bit x & 31 of word [y][x >> 5] (the layout of the defect bitmap), fully written, pad bits zero: set iff the
+ *       site is set in bitmap (may be NULL) or some u_f >= white_level (1..65536; 65536: no code saturates)
+ * A table entry that is not an Hm x Wm frame inside the pool contributes zeros; nothing outside the pool is read.  pool, bitmap, S, bad 4-byte
+ * aligned, frames and D 8-byte; 16-byte loads and stores where the pool, S and D are 16-byte aligned and Wm % 8 == 0.
+ *
+ * eld_flat_box_u32: S and bad as written above; period p = 2 or 6; 0 <= radius <= 64.  The window of site (y, x) is the sites
+ * (y + p dy, x + p dx), |dy|, |dx| <= radius, that lie inside the frame: its position plane (y % p, x % p), clipped at the border.
+ *   Bsum [Hm,Wm] uint64 = sum of S over the window's sites whose bad bit is clear;  Bcnt [Hm,Wm] uint32 = their number
+ * Two separable running-sum passes through a workspace of eld_flat_box_workspace_bytes(Hm, Wm) bytes (8 per site; 0: bad shape), 8-byte
+ * aligned; ELD_EWS when ws_bytes is smaller.  eld_flat_box_tile reports the mosaic columns a workgroup of the row pass covers and the mosaic
+ * rows a workgroup of the column pass covers, for tests that place a shape across both.
+ *
+ * eld_flat_apply_u16: codes [N,Hm,Wm]; gain [Hm,Wm] float32; black: HOST array of p * p float32 in [0, 65535], one per cell (y % p, x % p).
+ * Per site in float32, one rounding per operation, no fused multiply-add:
+ *   v = float(u) - black;  w = v * gain;  out = clamp(rint(w + black), 0, 65535)     (rint: ties to even)
+ * A site set in bitmap (may be NULL) or with u >= white_level passes through unchanged.  in and out may be the same buffer.
+ *
+ * eld_pack_raw_bayer_u16_flat / eld_pack_raw_xtrans_u16_flat: eld_pack_raw_*_u16_shaded with a gain plane [Hm,Wm] (Bayer: [2h,2w]):
+ *   clip((((float(u) - black) - (a + b t)) * gain) / (white - black), 0, 1), then min(max(. * ratio[n], 0), 1)
+ * ma and mb may both be NULL (no subtraction: the operation order of eld_pack_raw_*_u16_gain) and ratios may be NULL (no ratio step: the order
+ * of eld_pack_raw_*_u16).  A gain plane of ones gives the bits of those entry points.  ma, mb and gain 4-byte aligned. */
+int eld_flat_sums_u16(const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int Hm, int Wm, int white_level,
+                      const uint32_t* bitmap, uint32_t* S, uint64_t* D, uint32_t* bad, void* stream);
+size_t eld_flat_box_workspace_bytes(int Hm, int Wm);
+int eld_flat_box_tile(int period, int* row_pass_columns, int* column_pass_rows);
+int eld_flat_box_u32(const uint32_t* S, const uint32_t* bad, int Hm, int Wm, int period, int radius, uint64_t* Bsum, uint32_t* Bcnt, void* ws,
+                     size_t ws_bytes, void* stream);
+int eld_flat_apply_u16(const uint16_t* in, uint16_t* out, int N, int Hm, int Wm, const float* gain, const float* black, int period,
+                       int white_level, const uint32_t* bitmap, void* stream);
+int eld_pack_raw_bayer_u16_flat(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
+                                float white_point, const float* ratios, const float* ma, const float* mb, float t, const float* gain, void* stream);
+int eld_pack_raw_xtrans_u16_flat(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
+                                 const float* ratios, const float* ma, const float* mb, float t, const float* gain, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
