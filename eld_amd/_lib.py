@@ -147,6 +147,10 @@ SIGNATURES = {
     'eld_debug_last_conv_kernel': (C.c_char_p, []),
     'eld_debug_conv_kernel_count': (C.c_uint, [C.c_char_p]),
     'eld_debug_unet_region': (_i, [_i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i)]),
+    'eld_debug_unet_grad_tap': (None, [_vp, _sz]),
+    'eld_debug_unet_grad_tap_layout': (_i, [_i, _i, _i, _i, _i, _i, _i, C.POINTER(_sz), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    'eld_debug_unet_grad_tap_bytes': (_sz, [_i, _i, _i, _i, _i, _i]),
+    'eld_debug_unet_codes': (_i, [_vp]),
     'eld_flat_sums_u16': (_i, [_vp, _sz, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'eld_flat_box_workspace_bytes': (_sz, [_i, _i]),
     'eld_flat_box_tile': (_i, [_i, C.POINTER(_i), C.POINTER(_i)]),

@@ -383,6 +383,9 @@ struct FusedFwd { bool packed = false; const float* x = nullptr; unsigned codes 
 // fp32 scheme, debug mask) -- the backward reads a region only when its bit is set, whatever its own switches say
 enum { CODES_EA0 = 1, CODES_EA1 = 2, CODES_DA0 = 4, CODES_DA1 = 8, CODES_EB0 = 16, CODES_EB1 = 32, CODES_INFER = 256 };      // CODES_EBl: slope codes of eb[l] AND argmax codes of pool[l]      // CODES_INFER: the forward was eld_unet_infer_ex -- nothing for a backward
 
+static_assert(CODES_EA0 == ELD_CODES_EA0 && CODES_EA1 == ELD_CODES_EA1 && CODES_DA0 == ELD_CODES_DA0 && CODES_DA1 == ELD_CODES_DA1 && CODES_EB0 == ELD_CODES_EB0 &&
+              CODES_EB1 == ELD_CODES_EB1 && CODES_INFER == ELD_CODES_INFER, "eld_debug_unet_codes publishes these bits (include/eld_amd.h)");
+
 int unet_forward(const Plan& P, const float* x, const float* prm, float* out, float* ws, hipStream_t st, const HeadLoss* hl = nullptr, unsigned* have_out = nullptr,
                  bool infer = false) {
     const int N = P.N;
@@ -514,7 +517,47 @@ int unet_forward_bf16(const Plan& P, const float* x, const float* prm, float* ou
     return 0;
 }
 
-int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd, float* ws, hipStream_t st, BucketMarks& marks, const FusedFwd& fused) {
+// The debug tap on the backward's activation gradients (include/eld_amd.h eld_debug_unet_grad_tap): the stage numbering, each tensor's place in the
+// tap buffer, and the copy itself.  buf == nullptr (always, outside the tests): one branch per stage on the host, nothing enqueued.
+enum { TAP_G_HEAD = 0, TAP_DEC = 1, TAP_ENC = 17 };       // decoder level l: TAP_DEC + 4l + {d_da, d_up, skip, d_src}; encoder level l: TAP_ENC + 3(4-l) + {d_ea, d_pool, d_eb}
+static_assert(TAP_ENC + 3 * 4 + 1 == ELD_TAP_NSTAGES, "30 tapped tensors");
+// stage -> channels and level of its tensor; false for a stage outside [0, ELD_TAP_NSTAGES)
+bool tap_stage_shape(int stage, int& ch, int& lev) {
+    if (stage < 0 || stage >= ELD_TAP_NSTAGES) return false;
+    if (stage == TAP_G_HEAD) { ch = chan(0); lev = 0; return true; }
+    if (stage < TAP_ENC) {
+        const int l = (stage - TAP_DEC) / 4, k = (stage - TAP_DEC) % 4;
+        lev = k == 3 ? l + 1 : l; ch = chan(lev);
+        return true;
+    }
+    const int l = 4 - (stage - TAP_ENC) / 3, k = (stage - TAP_ENC) % 3;
+    if (k == 0) { lev = l; ch = chan(l); }                  // d_ea[l]
+    else if (k == 1) { lev = l; ch = chan(l - 1); }         // d_pool[l-1]: level l, channels of level l - 1
+    else { lev = l - 1; ch = chan(l - 1); }                 // d_eb[l-1]
+    return true;
+}
+struct GradTap {
+    char* buf = nullptr;
+    size_t off[ELD_TAP_NSTAGES], bytes[ELD_TAP_NSTAGES], total = 0;
+    void plan(const Plan& P, int precision) {
+        size_t o = 0;
+        for (int s = 0; s < ELD_TAP_NSTAGES; ++s) {
+            int ch = 0, lev = 0;
+            tap_stage_shape(s, ch, lev);
+            off[s] = o;
+            bytes[s] = (size_t)P.N * P.Hl[lev] * P.Wl[lev] * ch * (precision == 1 ? 2 : 4);
+            o += align_up(bytes[s], 256);
+        }
+        total = o;
+    }
+    int copy(int stage, const void* src, hipStream_t st) const {
+        if (!buf) return 0;
+        const hipError_t e = hipMemcpyAsync(buf + off[stage], src, bytes[stage], hipMemcpyDeviceToDevice, st);
+        return e == hipSuccess ? 0 : (int)e;
+    }
+};
+
+int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd, float* ws, hipStream_t st, BucketMarks& marks, const FusedFwd& fused, const GradTap& tap) {
     const int N = P.N;
     KPartScope kp(ws + P.part, P.part_floats);
     const bool h2 = g_algo == 2;
@@ -537,6 +580,7 @@ int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd
     else RC(launch_head_train_reduce(ws + P.head_part, grd + Hd.w_off, grd + Hd.b_off, N, P.H, P.W, P.out_ch, 0, st));      // gA and the partials: eld_unet_forward_loss_ex
     RC(marks.done(P, L_HEAD, st));
     if (h2) RC(launch_absmax(gA, (size_t)N * P.H * P.W * 32, am + S_GA, st));
+    RC(tap.copy(TAP_G_HEAD, gA, st));
     float* cur = gA; float* oth = gB;
     for (int l = 0; l <= 3; ++l) {            // decoder levels 0 (conv9) .. 3 (conv6)
         const int iu = L_UP3 + 3 * (3 - l);
@@ -547,6 +591,7 @@ int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd
         RC(marks.done(P, iu + 2, st));
         RC(fresh(gs(oth))); BD(gs(cur), S_W + iu + 2, gs(oth), -1);
         RC(conv_bwd_data(cur, ws + P.wp_bwd[iu + 2], oth, nullptr, C, ws + P.da[l], nullptr, N, H, W, C, C, st, l < 2 ? CD(P.cd_da[l], l ? CODES_DA1 : CODES_DA0) : nullptr));
+        RC(tap.copy(TAP_DEC + 4 * l, oth, st));
         { float* t = cur; cur = oth; oth = t; }
         // conv_1: input cat[up[l], eb[l]] -> d_up (raw) in oth, skip grad (raw) in skip[l]
         WG(gs(cur), S_UP + l, S_EB + l);
@@ -554,6 +599,8 @@ int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd
         RC(marks.done(P, iu + 1, st));
         RC(fresh(gs(oth))); BD(gs(cur), S_W + iu + 1, gs(oth), S_SKIP + l);
         RC(conv_bwd_data(cur, ws + P.wp_bwd[iu + 1], oth, ws + P.skip[l], C, nullptr, nullptr, N, H, W, 2 * C, C, st));
+        RC(tap.copy(TAP_DEC + 4 * l + 1, oth, st));
+        RC(tap.copy(TAP_DEC + 4 * l + 2, ws + P.skip[l], st));
         { float* t = cur; cur = oth; oth = t; }
         // transposed conv: input src (level l+1, 2C channels), output grad = cur (d_up)
         const float* src = l == 3 ? ws + P.eb[4] : ws + P.db[l + 1];
@@ -562,6 +609,7 @@ int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd
         RC(marks.done(P, iu, st));
         RC(fresh(gs(oth))); BD(gs(cur), S_W + iu, gs(oth), -1);
         RC(convt_bwd_data(cur, ws + P.wp_bwd[iu], src, oth, N, P.Hl[l + 1], P.Wl[l + 1], 2 * C, C, st));
+        RC(tap.copy(TAP_DEC + 4 * l + 3, oth, st));
         { float* t = cur; cur = oth; oth = t; }
     }
     // cur = pre-activation grad of conv5_2 (level 4)
@@ -574,6 +622,7 @@ int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd
         RC(fresh(gs(oth))); BD(gs(cur), S_W + ib, gs(oth), -1);
         RC(conv_bwd_data(cur, ws + P.wp_bwd[ib], oth, nullptr, C, ws + P.ea[l], nullptr, N, H, W, C, C, st,
                          l < 2 ? CD(P.cd_ea[l], l ? CODES_EA1 : CODES_EA0) : nullptr));
+        RC(tap.copy(TAP_ENC + 3 * (4 - l), oth, st));
         { float* t = cur; cur = oth; oth = t; }
         if (l == 0) {
             if (P.in_ch <= 4)
@@ -591,12 +640,14 @@ int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd
         RC(marks.done(P, ia, st));
         RC(fresh(gs(oth))); BD(gs(cur), S_W + ia, gs(oth), -1);
         RC(conv_bwd_data(cur, ws + P.wp_bwd[ia], oth, nullptr, Cp, nullptr, nullptr, N, H, W, Cp, C, st));      // d_pool (raw)
+        RC(tap.copy(TAP_ENC + 3 * (4 - l) + 1, oth, st));
         { float* t = cur; cur = oth; oth = t; }
         if (l - 1 < 2 && CD(P.cd_eb[l - 1], l - 1 ? CODES_EB1 : CODES_EB0) != nullptr)
             RC(launch_maxpool_bwd_codes(CD(P.pc[l - 1], l - 1 ? CODES_EB1 : CODES_EB0), CD(P.cd_eb[l - 1], l - 1 ? CODES_EB1 : CODES_EB0), cur, ws + P.skip[l - 1], oth, N, H, W, Cp, st));
         else
             RC(launch_maxpool_bwd(ws + P.eb[l - 1], cur, ws + P.skip[l - 1], oth, N, H, W, Cp, st));
         if (h2) { RC(fresh(gs(oth))); RC(launch_absmax(oth, (size_t)N * 4 * H * W * Cp, am + gs(oth), st)); }
+        RC(tap.copy(TAP_ENC + 3 * (4 - l) + 2, oth, st));
         { float* t = cur; cur = oth; oth = t; }
     }
     return 0;
@@ -625,7 +676,7 @@ int conv_wgrad_bf16(const bf16_t* g, int Cout, const bf16_t* x0, int C0, const b
     return launch_wgrad_reduce(part, a.bpart, dw, db, q.psplit, q.T, q.CA, q.CBp, Cin_real > 0 ? Cin_real : C0 + C1, st);
 }
 
-int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float* grd, float* ws, hipStream_t st, BucketMarks& marks, const FusedFwd& fused) {
+int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float* grd, float* ws, hipStream_t st, BucketMarks& marks, const FusedFwd& fused, const GradTap& tap) {
     const int N = P.N;
     if (!fused.packed) RC(pack_weights(P, prm, ws, PACK_BWD, st, true));
     auto B = [&](size_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
@@ -634,6 +685,7 @@ int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float
     if (dout) RC(launch_head_bwd_bf16(dout, B(P.db[0]), prm + Hd.w_off, cur, grd + Hd.w_off, grd + Hd.b_off, part, N, P.H, P.W, P.out_ch, st));
     else RC(launch_head_train_reduce(ws + P.head_part, grd + Hd.w_off, grd + Hd.b_off, N, P.H, P.W, P.out_ch, 1, st));
     RC(marks.done(P, L_HEAD, st));
+    RC(tap.copy(TAP_G_HEAD, cur, st));
     auto swap = [&]() { bf16_t* t = cur; cur = oth; oth = t; };
     for (int l = 0; l <= 3; ++l) {
         const int iu = L_UP3 + 3 * (3 - l);
@@ -642,10 +694,13 @@ int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float
         RC(marks.done(P, iu + 2, st));
         RC(conv_bwd_data_bf16(cur, B(P.wp_bwd[iu + 2]), oth, nullptr, C, B(P.da[l]), nullptr, N, H, W, C, C, st,
                               l == 0 && (fused.codes & CODES_DA0) ? reinterpret_cast<const unsigned*>(ws + P.cd_da[0]) : nullptr));
+        RC(tap.copy(TAP_DEC + 4 * l, oth, st));
         swap();
         RC(conv_wgrad_bf16(cur, C, B(P.up[l]), C, B(P.eb[l]), C, grd + P.L[iu + 1].w_off, grd + P.L[iu + 1].b_off, part, N, H, W, st));
         RC(marks.done(P, iu + 1, st));
         RC(conv_bwd_data_bf16(cur, B(P.wp_bwd[iu + 1]), oth, B(P.skip[l]), C, nullptr, nullptr, N, H, W, 2 * C, C, st));
+        RC(tap.copy(TAP_DEC + 4 * l + 1, oth, st));
+        RC(tap.copy(TAP_DEC + 4 * l + 2, B(P.skip[l]), st));
         swap();
         const bf16_t* src = l == 3 ? B(P.eb[4]) : B(P.db[l + 1]);
         {   // transposed conv: weight gradient (gather mode), bias gradient (column sums of d_up), backward data
@@ -663,6 +718,7 @@ int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float
             c.epi = EPI_GRAD; c.out0 = oth; c.split = 2 * C; c.act0 = src; c.dtype = DT_BF16;
             RC(launch_conv(c, CONV_GATHER2X2, st));
         }
+        RC(tap.copy(TAP_DEC + 4 * l + 3, oth, st));
         swap();
     }
     for (int l = 4; l >= 0; --l) {
@@ -672,6 +728,7 @@ int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float
         RC(marks.done(P, ib, st));
         RC(conv_bwd_data_bf16(cur, B(P.wp_bwd[ib]), oth, nullptr, C, B(P.ea[l]), nullptr, N, H, W, C, C, st,
                               l == 0 && (fused.codes & CODES_EA0) ? reinterpret_cast<const unsigned*>(ws + P.cd_ea[0]) : nullptr));
+        RC(tap.copy(TAP_ENC + 3 * (4 - l), oth, st));
         swap();
         if (l == 0) {
             if (P.in_ch <= 4)
@@ -685,8 +742,10 @@ int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float
         RC(conv_wgrad_bf16(cur, C, B(P.pool[l - 1]), Cp, nullptr, 0, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, H, W, st));
         RC(marks.done(P, ia, st));
         RC(conv_bwd_data_bf16(cur, B(P.wp_bwd[ia]), oth, nullptr, Cp, nullptr, nullptr, N, H, W, Cp, C, st));
+        RC(tap.copy(TAP_ENC + 3 * (4 - l) + 1, oth, st));
         swap();
         RC(launch_maxpool_bwd_bf16(B(P.eb[l - 1]), cur, B(P.skip[l - 1]), oth, N, H, W, Cp, st));
+        RC(tap.copy(TAP_ENC + 3 * (4 - l) + 2, oth, st));
         swap();
     }
     return 0;
@@ -773,6 +832,8 @@ void head_state_set(const void* ws, const HeadState* st) {
         if (it != g_ws_state.end()) { it->second.has_head = false; ws_state_drop_if_empty(ws); }
     }
 }
+char* g_tap_buf = nullptr;          // eld_debug_unet_grad_tap (under g_head_mu)
+size_t g_tap_bytes = 0;
 bool head_state_is(const void* ws, HeadState& want) {      // fills want.x (the fused forward's input tensor) on a match
     std::lock_guard<std::mutex> lk(g_head_mu);
     const auto it = g_ws_state.find(ws);
@@ -857,9 +918,21 @@ extern "C" int eld_unet_backward_ex(const float* dout, const float* params, floa
         if (!bucket_event[k] || bucket_start[k] < 0 || (k > 0 && bucket_start[k] <= bucket_start[k - 1]) || (size_t)bucket_start[k] >= P.nparams) return ELD_EINVAL;
     BucketMarks marks;
     marks.start = bucket_start; marks.event = bucket_event; marks.n = n_buckets;
+    GradTap tap;
+    {   // the debug tap (eld_debug_unet_grad_tap; unset outside the tests): its refusals come before any launch
+        std::lock_guard<std::mutex> lk(g_head_mu);
+        if (g_tap_buf) {
+            tap.plan(P, precision);
+            if (g_tap_bytes < tap.total) return ELD_EINVAL;
+            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+            if (hipStreamIsCapturing(as_stream(stream), &cs) != hipSuccess) { (void)hipGetLastError(); return ELD_ENOTSUP; }      // (the legacy stream beside a capture: not tappable either)
+            if (cs != hipStreamCaptureStatusNone) return ELD_ENOTSUP;        // a graph must not bake the debug copies in
+            tap.buf = g_tap_buf;
+        }
+    }
     AlgoScope scope(fp32_algo);
-    const int rc = precision == 1 ? unet_backward_bf16(P, dout, params, grads, (float*)ws, as_stream(stream), marks, fused)
-                                  : unet_backward(P, dout, params, grads, (float*)ws, as_stream(stream), marks, fused);
+    const int rc = precision == 1 ? unet_backward_bf16(P, dout, params, grads, (float*)ws, as_stream(stream), marks, fused, tap)
+                                  : unet_backward(P, dout, params, grads, (float*)ws, as_stream(stream), marks, fused, tap);
     if (rc) return rc;
     return marks.next == n_buckets ? 0 : ELD_EINVAL;
 }
@@ -885,6 +958,35 @@ extern "C" int eld_unet_backward_buckets(const float* dout, const float* params,
                                          int in_ch, int out_ch, int precision, const int64_t* bucket_start, void* const* bucket_event,
                                          int n_buckets, void* stream) {
     return eld_unet_backward_ex(dout, params, grads, ws, ws_bytes, N, H, W, in_ch, out_ch, precision, -1, bucket_start, bucket_event, n_buckets, stream);
+}
+
+extern "C" void eld_debug_unet_grad_tap(void* buf, size_t bytes) {
+    std::lock_guard<std::mutex> lk(g_head_mu);
+    g_tap_buf = (char*)buf; g_tap_bytes = buf ? bytes : 0;
+}
+extern "C" int eld_debug_unet_grad_tap_layout(int N, int H, int W, int in_ch, int out_ch, int precision, int stage, size_t* offset, int* channels, int* level,
+                                              int* dtype) {
+    if (!offset || !channels || !level || !dtype || (precision != 0 && precision != 1)) return ELD_EINVAL;
+    Plan P;
+    RC(make_plan(P, N, H, W, in_ch, out_ch));
+    int ch, lev;
+    if (!tap_stage_shape(stage, ch, lev)) return ELD_EINVAL;
+    GradTap t;
+    t.plan(P, precision);
+    *offset = t.off[stage]; *channels = ch; *level = lev; *dtype = precision;
+    return 0;
+}
+extern "C" size_t eld_debug_unet_grad_tap_bytes(int N, int H, int W, int in_ch, int out_ch, int precision) {
+    Plan P;
+    if ((precision != 0 && precision != 1) || make_plan(P, N, H, W, in_ch, out_ch)) return 0;
+    GradTap t;
+    t.plan(P, precision);
+    return t.total;
+}
+extern "C" int eld_debug_unet_codes(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_head_mu);
+    const auto it = g_ws_state.find(ws);
+    return it == g_ws_state.end() || !it->second.has_codes ? -1 : (int)it->second.codes.have;
 }
 
 extern "C" int eld_debug_ws_state_entries(void) { std::lock_guard<std::mutex> lk(g_head_mu); return (int)g_ws_state.size(); }

@@ -790,6 +790,37 @@ enum { ELD_REGION_EA = 0, ELD_REGION_EB = 1, ELD_REGION_POOL = 2, ELD_REGION_UP 
        ELD_REGION_GRAD_CONV1_1 = 7 };
 int eld_debug_unet_region(int N, int H, int W, int in_ch, int out_ch, int precision, int region, int level, size_t* offset, int* channels,
                           int* dtype);
+/* Test hook: a tap on the activation gradients of the U-Net backward (tests/test_backward_layers_gpu.py; DESIGN.md sections 6 / 6a).  Appended
+ * without a change of ELD_ABI_VERSION, as eld_debug_conv_kernel_count above.  Process-global; buf == NULL switches it off (the default).  While
+ * set, eld_unet_backward_ex (both precisions) enqueues one device-to-device hipMemcpyAsync on the call's own stream right after each stage that
+ * writes an activation gradient -- before the gradient buffers swap and the next stage overwrites the other one -- copying that tensor to
+ * buf + offset(stage).  No kernel differs; with the tap unset the backward enqueues exactly what it always did (one host branch per stage).
+ * The ELD_TAP_NSTAGES = 30 stages, numbered in backward order (l = U-Net level, conv(9-l)_x the decoder layers of level l):
+ *   0                 g_head     gradient of conv9_2's pre-activation output, written by the head backward or by the fused training head
+ *   1 + 4l, l = 0..3  d_da[l]    conv(9-l)_2 backward-data times slope(da[l]): gradient of conv(9-l)_1's pre-activation output
+ *   2 + 4l            d_up[l]    first output of conv(9-l)_1's backward-data (raw: the transposed conv has no activation)
+ *   3 + 4l            skip[l]    its second output (raw): the skip connection's share of eb[l]'s gradient
+ *   4 + 4l            d_src[l]   transposed-conv backward-data times slope(db[l+1]) (l = 3: slope(eb[4])), at level l + 1
+ *   17 + 3(4-l), l = 4..0   d_ea[l]      conv(l+1)_2 backward-data times slope(ea[l]); l = 0 (stage 29) is what conv1_1's weight gradient reads
+ *   18 + 3(4-l), l = 4..1   d_pool[l-1]  conv(l+1)_1 backward-data (raw), at level l with the channels of level l - 1
+ *   19 + 3(4-l), l = 4..1   d_eb[l-1]    the pool backward's output (route(d_pool) + skip[l-1]) * slope(eb[l-1]), at level l - 1
+ * eld_debug_unet_grad_tap_layout is a pure query: *offset in bytes into buf (256-byte aligned), *channels, *level (the tensor is NHWC
+ * [N][H >> level][W >> level][channels]) and *dtype = 0 fp32 / 1 bf16 (= precision); ELD_EINVAL for a stage outside [0, 30) or a shape
+ * eld_unet_workspace_bytes rejects.  eld_debug_unet_grad_tap_bytes: the size the buffer needs for that problem (0: bad arguments).
+ * A backward with the tap set returns, before any launch, ELD_EINVAL when the buffer is smaller than that and ELD_ENOTSUP when the stream is
+ * being captured (a graph must not bake the debug copies in). */
+#define ELD_TAP_NSTAGES 30
+void eld_debug_unet_grad_tap(void* buf, size_t bytes);
+int eld_debug_unet_grad_tap_layout(int N, int H, int W, int in_ch, int out_ch, int precision, int stage, size_t* offset, int* channels, int* level,
+                                   int* dtype);
+size_t eld_debug_unet_grad_tap_bytes(int N, int H, int W, int in_ch, int out_ch, int precision);
+/* Test hook: which slope- / pool-code regions the LAST forward on workspace ws filled (what the next backward on it will read instead of the saved
+ * activations): an OR of the bits below.  ELD_CODES_EBl = the slope codes of eb[l] AND the argmax codes of pool[l]; ELD_CODES_INFER = the
+ * forward was eld_unet_infer_ex (nothing kept for a backward).  -1: the library holds no code state for ws -- no forward ran on it, its last
+ * forward filled no region (fp32 scheme other than 1, a problem too small for the 8-wave level-1 kernels, eld_debug_kernel_mask bit 7), or the
+ * bounded host table evicted the entry; a backward then reads the saved activations.  Never 0.  Host bookkeeping only. */
+enum { ELD_CODES_EA0 = 1, ELD_CODES_EA1 = 2, ELD_CODES_DA0 = 4, ELD_CODES_DA1 = 8, ELD_CODES_EB0 = 16, ELD_CODES_EB1 = 32, ELD_CODES_INFER = 256 };
+int eld_debug_unet_codes(const void* ws);
 
 /* ---- flat-field maps: what multiplies the signal, from the flat frames (csrc/flatfield.hip, eld_amd/flatfield.py) -----------
  * Appended without a change of ELD_ABI_VERSION (no existing signature changed), as eld_debug_conv_kernel_count above.  tests/flatfield_ref.py

@@ -688,6 +688,24 @@ def _codes_case(prec, shape, seed=11):
     return net, x, junk, dout
 
 
+# the code regions the last forward of `net` on the workspace of `key` filled (include/eld_amd.h eld_debug_unet_codes; -1: none)
+EA0, EA1, DA0, DA1, EB0, EB1 = 1, 2, 4, 8, 16, 32
+F32_CODES = EA0 | EA1 | DA0 | DA1 | EB0 | EB1
+
+
+def _codes_filled(lib, net, key):
+    from eld_amd import _lib as L
+    return lib.eld_debug_unet_codes(L.dptr(net._ws.bufs[key]))
+
+
+def _codes_expected(bf16):
+    """what a default forward of the codes shapes fills: everything the engine has, less ea[0]'s codes where the process runs the packed-raw first
+    layer on the fp32-MFMA kernel (ELD_FIRST_MMA=0, tests/variant_child.py: that kernel writes none and conv1_2's backward reads the saved tensor)"""
+    import os
+    ea0 = EA0 if os.environ.get('ELD_FIRST_MMA', '1') != '0' else 0
+    return (DA0 | ea0) if bf16 else (F32_CODES & ~EA0) | ea0
+
+
 @pytest.mark.parametrize('prec,shape', [('fp32', (1, 4, 528, 1072)), ('bf16', (1, 4, 256, 512)), ('bf16', (2, 4, 272, 560)), ('bf16', (1, 4, 1424, 2128))])
 def test_slope_codes_give_the_gradients_of_the_saved_activations_bit_for_bit(lib, prec, shape):
     """Round 5: the forward epilogues of levels 0 / 1 (fp32 three-piece scheme) and of conv1_1 / conv9_1 (bf16) also write 2-bit slope codes, and the
@@ -697,10 +715,12 @@ def test_slope_codes_give_the_gradients_of_the_saved_activations_bit_for_bit(lib
     net, x, junk, dout = _codes_case(prec, shape)
     bf16 = prec == 'bf16'
     _, key, _ = net._engine_forward(x, save=True, bf16=bf16)
+    assert _codes_filled(lib, net, key) == _codes_expected(bf16)      # the default run really reads codes: every region the engine has
     g1 = net._engine_backward(dout, key, shape).clone()
     old = lib.eld_debug_kernel_mask(128)
     try:
         _, key, _ = net._engine_forward(x, save=True, bf16=bf16)
+        assert _codes_filled(lib, net, key) == -1             # ... and the masked run none
         g0 = net._engine_backward(dout, key, shape).clone()
     finally:
         lib.eld_debug_kernel_mask(old)
@@ -709,14 +729,16 @@ def test_slope_codes_give_the_gradients_of_the_saved_activations_bit_for_bit(lib
     assert torch.equal(g1, g0), int((g1 != g0).sum())
 
 
-@pytest.mark.parametrize('prec,shape', [('fp32', (1, 4, 528, 1072)), ('fp32', (2, 4, 144, 208)), ('bf16', (1, 4, 256, 512)), ('bf16', (2, 4, 272, 560))])
+@pytest.mark.parametrize('prec,shape', [('fp32', (1, 4, 528, 1072)), ('fp32', (2, 4, 544, 464)), ('bf16', (1, 4, 256, 512)), ('bf16', (2, 4, 272, 560))])
 def test_pool_codes_route_ties_like_the_saved_activations(lib, prec, shape):
     """Round 6: the forward epilogues of conv1_2 / conv2_2 also write the ARGMAX of every 2x2 pooling window (2 bits per pooled element,
     ConvArgs::pool_codes_out) and their own slope codes, and the pools' backward reads those instead of the saved un-pooled tensors.  The
     winner of a window with equal maxima is the FIRST in row-major order (torch's CPU max_pool2d backward; unet_misc.hip POOL_BWD_1), which random
     inputs never exercise -- so this input is piecewise constant on 6 x 10 blocks (offset against the 2 x 2 windows): inside a block all four
     window elements of conv1_2's output are the same bits, across a block edge two of them are.  eld_debug_kernel_mask bit 8 switches the pool
-    codes off (bit 7: all codes): every gradient must agree to the last bit."""
+    codes off (bit 7: all codes): every gradient must agree to the last bit.  eld_debug_unet_codes confirms what each run filled.  The fp32
+    two-image case was (2, 4, 144, 208), where make_plan never enables codes (level 1 has 40 tiles of the 256 it asks for) and all three runs took
+    the same code-free path: (2, 4, 544, 464) is the smallest two-image shape (by pixels, 256 CUs) whose forward reports all six regions."""
     net, x, junk, dout = _codes_case(prec, shape, seed=13)
     N, C, H, W = shape
     g = torch.Generator(device='cuda').manual_seed(21)
@@ -725,12 +747,18 @@ def test_pool_codes_route_ties_like_the_saved_activations(lib, prec, shape):
     assert x.shape == shape
     bf16 = prec == 'bf16'
     _, key, _ = net._engine_forward(x, save=True, bf16=bf16)
+    have = _codes_filled(lib, net, key)
+    # fp32: the default run routes both full-size pools by their argmax codes (EB0 | EB1 are in the mask).  The bf16 engine has slope codes of
+    # ea[0] / da[0] only and its pools read the saved tensors in all three runs: those cases pin that the mask bits change nothing there.
+    assert have == _codes_expected(bf16), have
     g1 = net._engine_backward(dout, key, shape).clone()
     res = []
     for mask in (256, 128):
         old = lib.eld_debug_kernel_mask(mask)
         try:
             _, key, _ = net._engine_forward(x, save=True, bf16=bf16)
+            have = _codes_filled(lib, net, key)
+            assert (have == -1) if mask == 128 else (have > 0 and not have & (EB0 | EB1)), (mask, have)
             res.append(net._engine_backward(dout, key, shape).clone())
         finally:
             lib.eld_debug_kernel_mask(old)
@@ -754,16 +782,20 @@ def test_backward_reads_slope_codes_only_from_the_forward_that_wrote_them(lib, p
         old = lib.eld_debug_kernel_mask(128) if codes_off else None
         try:
             net.fp32_products = 1
-            net._engine_forward(junk, save=True, bf16=bf16)                   # leaves junk's codes in the workspace (unless switched off)
+            _, jkey, _ = net._engine_forward(junk, save=True, bf16=bf16)      # leaves junk's codes in the workspace (unless switched off)
+            assert _codes_filled(lib, net, jkey) == (-1 if codes_off else _codes_expected(bf16))
             if bf16:
                 m = lib.eld_debug_kernel_mask(0)                              # (returns the previous mask)
                 lib.eld_debug_kernel_mask(m | 1)                              # the forward of x: no conv_bfs, so no codes
                 _, key, _ = net._engine_forward(x, save=True, bf16=True)
                 lib.eld_debug_kernel_mask(m)                                  # the backward: conv_bfs again
+                assert key == jkey
             else:
                 net.fp32_products = 2                                         # the forward of x: a scheme that writes no codes
                 _, key, _ = net._engine_forward(x, save=True)
                 net._ws.algo[key] = 1                                         # the backward: the three-piece kernels
+                assert key == jkey
+            assert _codes_filled(lib, net, key) == -1                         # the forward of x filled none: the backward must not read junk's
             return net._engine_backward(dout, key, shape).clone()
         finally:
             if codes_off:
