@@ -158,6 +158,7 @@ SIGNATURES = {
     'eld_flat_apply_u16': (_i, [_vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_float), _i, _i, _vp, _vp]),
     'eld_pack_raw_bayer_u16_flat': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp, _vp, _vp, _f, _vp, _vp]),
     'eld_pack_raw_xtrans_u16_flat': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _vp, _vp]),
+    'eld_nlm_vst_f32': (_i, [_vp, _i, _i, _i, _i, _f, _vp, _i, _i, _i, C.POINTER(C.c_uint16), _i, _vp, _vp]),
 }
 
 

@@ -1,0 +1,272 @@
+"""A classical baseline beside the U-Net: the generalised Anscombe transform, non-local means in the stabilised domain with weights shared
+by the CFA planes, and the closed-form unbiased inverse -- the yardstick row the paper's tables open with (BM3D / A-BM3D there), run with
+the gain K and the read noise the calibration measured.  It needs no checkpoint.
+
+    den = ClassicalDenoiser('bayer', K=2.1, camera='SonyA7S2')          # sigma from the table's g_scale line at log K
+    res = denoise_raw(den, mosaic_u16, 'bayer', black_level=512, white_point=16383, ratio=100, wb=wb, ccm=ccm)
+    rep = evaluate_pairs(net, pairs, 'bayer', ..., baseline=den)        # adds psnr_nlm / ssim_nlm beside psnr / psnr_in
+
+The sensor codes -- not the network's clipped input: the clip at 0 alone biases the mean by the size of the signal once sigma / K > 1 --
+are packed by the existing input stage with black 0, white 65535 and ratio 1 (so shading and flat-field maps still apply in the same
+kernels), turned into stabilised codes of Q = 16 per noise standard deviation by a per-plane table that holds the black level, filtered by
+one HIP kernel in integer arithmetic (csrc/nlm.hip: eld_nlm_vst_f32, restated bit for bit by tests/nlm_ref.py) and inverted in float64.
+Each plane of the result is z * ratio / (white - black): the network's output convention, so the lens gain, the write-back, the ISP and the
+demosaic of denoise_raw follow unchanged.  The contract, the table builders and the measured times are DESIGN.md sec. 24.
+
+Command line: python -m eld_amd.classical frames.npy... -o DIR --meta sensor.json --K K [--sigma S | --camera TABLE] [--search 7]
+[--patch 2] [--strength 0.5] and every sensor option of python -m eld_amd.denoise (which keeps its required --ckpt)."""
+import ctypes
+import math
+import os
+import sys
+
+import numpy as np
+
+from . import _lib as L
+
+Q = 16                          # stabilised codes per noise standard deviation
+FRAC = 4                        # fractional bits of the filtered code: 1 / 256 of a standard deviation
+MAX_SEARCH, MAX_PATCH = 10, 3   # the kernel's argument ranges (include/eld_amd.h)
+
+
+# ---- tables (host, float64, fixed order) --------------------------------------------------------------------------------------------------
+def _check_noise(K, sigma):
+    K, sigma = float(K), float(sigma)
+    if not (math.isfinite(K) and K > 0):
+        raise ValueError('K (DN per electron) must be finite and > 0, got %r' % (K,))
+    if not (math.isfinite(sigma) and sigma >= 0):
+        raise ValueError('sigma (read noise in DN) must be finite and >= 0, got %r' % (sigma,))
+    return K, sigma
+
+
+def vst_tables(K, sigma, black_per_plane):
+    """The forward transform of every plane as a table over the sensor codes, uint16 (C, 65536):
+    fwd[c][i] = min(rint(Q * (2 / K) * sqrt(max(K * (i - black_c) + 3/8 K^2 + sigma^2, 0))), 32767)."""
+    K, sigma = _check_noise(K, sigma)
+    blk = [float(b) for b in np.asarray(black_per_plane, dtype=np.float64).reshape(-1)]
+    if not blk or len(blk) > 16:
+        raise ValueError('black_per_plane takes 1 to 16 values, got %d' % len(blk))
+    i = np.arange(65536, dtype=np.float64)
+    out = np.empty((len(blk), 65536), np.uint16)
+    for c, b in enumerate(blk):
+        arg = np.maximum(K * (i - b) + 0.375 * K * K + sigma * sigma, 0.0)
+        out[c] = np.minimum(np.rint(Q * (2.0 / K) * np.sqrt(arg)), 32767.0).astype(np.uint16)
+    return out
+
+
+def nlm_weight_table(C, P, strength):
+    """-> (sh, wtab uint16 (256,)).  With n = C (2P + 1)^2 terms in a patch distance, two patches of one signal differ by 2 Q^2 n on
+    average: that much is subtracted, and the rest decays with strength^2 Q^2 n.  sh is the least shift for which 256 << sh reaches the
+    distance whose weight falls below 1 / 510; bin k takes the weight of its middle: wtab[k] = rint(255 exp(-max((k + 1/2) 2^sh - 2 Q^2 n, 0)
+    / (strength^2 Q^2 n))), wtab[0] at least 1."""
+    C, P, strength = int(C), int(P), float(strength)
+    if not (1 <= C <= 16) or not (0 <= P <= MAX_PATCH):
+        raise ValueError('C must be in [1, 16] and P in [0, %d], got %d and %d' % (MAX_PATCH, C, P))
+    if not (math.isfinite(strength) and strength > 0):
+        raise ValueError('strength must be finite and > 0, got %r' % (strength,))
+    n = C * (2 * P + 1) ** 2
+    h2 = strength ** 2 * Q * Q * n
+    bias = 2.0 * Q * Q * n
+    top = bias + h2 * math.log(510.0)
+    sh = 0
+    while (256 << sh) < top:
+        sh += 1
+    if sh > 24:
+        raise ValueError('strength %g puts the weight table beyond the kernel\'s largest shift' % strength)
+    k = np.arange(256, dtype=np.float64)
+    wt = np.rint(255.0 * np.exp(-np.maximum((k + 0.5) * float(1 << sh) - bias, 0.0) / h2)).astype(np.uint16)
+    wt[0] = max(int(wt[0]), 1)
+    return sh, wt
+
+
+def unbiased_inverse(out, frac, K, sigma):
+    """The filtered codes (units of 2^-frac of a stabilised code) -> DN above black, float64 on the tensor's device: the closed form of
+    Makitalo and Foi for the generalised Anscombe transform, with D = out / (Q 2^frac), s = sigma / K, Dm = max(D, 2 sqrt(3/8 + s^2)):
+    z = K (Dm^2 / 4 + sqrt(3/2) / (4 Dm) - 11 / (8 Dm^2) + 5 sqrt(3/2) / (8 Dm^3) - 1/8 - s^2)."""
+    import torch
+    K, sigma = _check_noise(K, sigma)
+    D = out.to(torch.float64) / float(Q * (1 << int(frac)))
+    s = sigma / K
+    Dm = torch.clamp(D, min=2.0 * math.sqrt(0.375 + s * s))
+    r = math.sqrt(1.5)
+    return K * (Dm * Dm / 4.0 + r / (4.0 * Dm) - 11.0 / (8.0 * Dm * Dm) + 5.0 * r / (8.0 * Dm * Dm * Dm) - 0.125 - s * s)
+
+
+# ---- the kernel's wrapper -------------------------------------------------------------------------------------------------------------------
+def nlm_vst(x, qscale, fwd, S, P, sh, wtab, frac, out=None):
+    """eld_nlm_vst_f32 on CUDA tensors: x (N,C,h,w) float32 (any 4-byte aligned contiguous view), fwd (C,65536) uint16 codes as an int16 /
+    uint16 tensor on x's device, wtab 256 host weights -> int32 (N,C,h,w).  The library checks the argument ranges (ELD_EINVAL -> EldError)."""
+    import torch
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError('x must be a CUDA float32 tensor (N, C, h, w)')
+    x = x if x.is_contiguous() else x.contiguous()
+    N, C, h, w = (int(v) for v in x.shape)
+    if tuple(fwd.shape) != (C, 65536) or fwd.element_size() != 2 or fwd.device != x.device or not fwd.is_contiguous():
+        raise ValueError('fwd must be a contiguous 16-bit tensor (%d, 65536) on %s' % (C, x.device))
+    wt = np.ascontiguousarray(np.asarray(wtab).reshape(-1), dtype=np.uint16)
+    if wt.size != 256:
+        raise ValueError('wtab takes 256 weights, got %d' % wt.size)
+    if out is None:
+        out = torch.empty((N, C, h, w), dtype=torch.int32, device=x.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (N, C, h, w) or out.device != x.device or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int32 tensor of x\'s shape and device')
+    with torch.cuda.device(x.device):
+        L.check(L.lib().eld_nlm_vst_f32(L.dptr(x), N, C, h, w, float(qscale), L.dptr(fwd), int(S), int(P), int(sh),
+                                        wt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), int(frac), L.dptr(out), L.cur_stream()), 'eld_nlm_vst_f32')
+    return out
+
+
+# ---- the denoiser ---------------------------------------------------------------------------------------------------------------------------
+def _camera_table(camera):
+    """A calibrated table: the dict itself, the name of a table (camera_params/release/<name>_params.npy of the working directory, else the
+    tables shipped with the package) or the path of a <name>_params.npy file."""
+    if isinstance(camera, dict):
+        return camera
+    if isinstance(camera, (str, os.PathLike)):
+        camera = os.fspath(camera)
+        if camera.endswith('.npy'):
+            if not os.path.exists(camera):
+                raise ValueError('no such camera table: %s' % camera)
+            return np.load(camera, allow_pickle=True).item()
+        from .noise import load_camera_params
+        try:
+            return load_camera_params(camera, os.path.join('camera_params', 'release'))
+        except KeyError:
+            raise ValueError('no camera table named %r' % camera)
+    raise ValueError('camera must be a table (dict), a table\'s name or the path of a _params.npy file, got %r' % (type(camera).__name__,))
+
+
+def sigma_from_table(camera, K):
+    """The read noise in DN the table's 'Profile-1' g_scale line gives at log K: exp(slope log K + bias)."""
+    K = _check_noise(K, 0.0)[0]
+    try:
+        line = _camera_table(camera)['Profile-1']['g_scale']
+        slope, bias = float(line['slope']), float(line['bias'])
+    except (KeyError, TypeError):
+        raise ValueError("the camera table has no 'Profile-1' g_scale line")
+    return math.exp(slope * math.log(K) + bias)
+
+
+class ClassicalDenoiser:
+    """The baseline as denoise_raw and evaluate_pairs take it in place of a Denoiser.
+
+    cfa       'bayer' or 'xtrans': in_channels = out_channels = its plane count
+    K, sigma  overall system gain and read noise (Gaussian, signal-independent) in DN; sigma None: from `camera` (sigma_from_table)
+    search, patch   the radii S and P: candidates within |d| <= search, patches of (2 patch + 1)^2 sites in every plane
+    strength  the filter parameter in units of the noise standard deviation per patch term"""
+    is_classical = True
+
+    def __init__(self, cfa, K, sigma=None, camera=None, search=7, patch=2, strength=0.5):
+        from .denoise import PLANES, _check_cfa
+        _check_cfa(cfa)
+        if sigma is None:
+            if camera is None:
+                raise ValueError('ClassicalDenoiser needs sigma, or a camera table to read it from')
+            sigma = sigma_from_table(camera, K)
+            self._camera = camera                                # with_gain reads the line again at another K
+        else:
+            self._camera = None
+        self.K, self.sigma = _check_noise(K, sigma)
+        for name, v, top in (('search', search, MAX_SEARCH), ('patch', patch, MAX_PATCH)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (0 <= v <= top):
+                raise ValueError('%s must be an integer in [0, %d], got %r' % (name, top, v))
+        self.cfa, self.search, self.patch, self.strength = cfa, int(search), int(patch), float(strength)
+        self.planes = PLANES[cfa]
+        self.sh, self.wtab = nlm_weight_table(self.planes, self.patch, self.strength)
+        self._fwd = {}
+        self._others = {}
+
+    def with_gain(self, K):
+        """This baseline at another gain (another ISO): the read noise again from the camera table where it came from one, else kept."""
+        K = float(K)
+        if K == self.K:
+            return self
+        if K not in self._others:
+            self._others[K] = ClassicalDenoiser(self.cfa, K, sigma=None if self._camera is not None else self.sigma, camera=self._camera,
+                                                search=self.search, patch=self.patch, strength=self.strength)
+        return self._others[K]
+
+    @property
+    def in_channels(self):
+        return self.planes
+
+    @property
+    def out_channels(self):
+        return self.planes
+
+    def black_per_plane(self, black_level):
+        """denoise._levels' black levels (4 for Bayer, in colour-code order = plane order; one for X-Trans) -> one per packed plane"""
+        b = [float(v) for v in black_level]
+        return b if self.cfa == 'bayer' else [b[0]] * self.planes
+
+    def fwd_on(self, device, black_level):
+        """The forward tables for these black levels as an int16-view tensor (C, 65536) on `device`, built and uploaded once."""
+        import torch
+        key = (torch.device(device), tuple(self.black_per_plane(black_level)))
+        if key not in self._fwd:
+            self._fwd[key] = torch.from_numpy(vst_tables(self.K, self.sigma, key[1]).view(np.int16)).to(device)
+        return self._fwd[key]
+
+    def pack_codes(self, t3, raw_pattern, black_level, shading=None, tval=None, flatfield=None):
+        """CUDA int16-view codes (N,Hm,Wm) -> the corrected sensor codes of every packed plane over 65535, float32 (N,C,h,w), unclipped at
+        the black level: denoise.pack_input with black 0, white 65535 and ratio 1.  A flat-field gain g must multiply the signal above black
+        only, so what it did to the pedestal is taken back: x - (g - 1) * black / 65535 in float32."""
+        import torch
+        from .denoise import pack_input
+        N = int(t3.shape[0])
+        zero = [0.0] * len(black_level)
+        if flatfield is None:
+            return pack_input(t3, self.cfa, raw_pattern, zero, 65535.0, [1.0] * N, shading, tval)
+        x = pack_input(t3, self.cfa, raw_pattern, zero, 65535.0, [1.0] * N, shading, tval, flatfield)
+        bq = torch.tensor(self.black_per_plane(black_level), dtype=torch.float32, device=x.device).reshape(1, -1, 1, 1) / 65535.0
+        return x - (flatfield.packed(x.device, 'prnu') - 1.0) * bq
+
+    def filter_planes(self, x, black_level, ratios, white_point):
+        """The corrected codes over 65535 (pack_codes) -> float32 (N,C,h,w) in the network's output convention."""
+        import torch
+        fwd = self.fwd_on(x.device, black_level)
+        out = nlm_vst(x, 65535.0, fwd, self.search, self.patch, self.sh, self.wtab, FRAC)
+        z = unbiased_inverse(out, FRAC, self.K, self.sigma)
+        blk = torch.tensor(self.black_per_plane(black_level), dtype=torch.float64, device=x.device).reshape(1, -1, 1, 1)
+        r = torch.as_tensor(np.asarray(ratios, np.float64).reshape(-1), device=x.device).reshape(-1, 1, 1, 1)
+        return (z * r / (float(white_point) - blk)).to(torch.float32)
+
+    def denoise_codes(self, t3, raw_pattern, black_level, white_point, ratios, shading=None, tval=None, flatfield=None):
+        """CUDA int16-view codes (N,Hm,Wm), as denoise.pack_input takes them -> the denoised packed planes (N,C,h,w) float32: plane c is
+        z * ratio[n] / (white - black_c), z the estimate of the clean signal in DN above black."""
+        return self.filter_planes(self.pack_codes(t3, raw_pattern, black_level, shading, tval, flatfield), black_level, ratios, white_point)
+
+
+# ---- command line ---------------------------------------------------------------------------------------------------------------------------
+def build_parser():
+    from . import denoise as D
+    p = D.build_parser()
+    p.prog = 'python -m eld_amd.classical'
+    p.description = 'Denoise uint16 raw mosaics (.npy) without a checkpoint: Anscombe transform + non-local means + unbiased inverse.'
+    for act in p._actions:
+        if act.dest == 'ckpt':
+            act.required = False
+            act.help = 'ignored: the classical baseline loads no checkpoint'
+    p.add_argument('--K', type=float, required=True, help='overall system gain in DN per electron (eld_amd.calibrate, eld_amd.burst)')
+    p.add_argument('--sigma', type=float, help='read noise in DN (default: the g_scale line of --camera at log K)')
+    p.add_argument('--camera', metavar='TABLE', help="a calibrated table: a name (camera_params/release/<name>_params.npy or a shipped one) or a .npy path")
+    p.add_argument('--search', type=int, default=7, help='search radius (default 7, at most %d)' % MAX_SEARCH)
+    p.add_argument('--patch', type=int, default=2, help='patch radius (default 2, at most %d)' % MAX_PATCH)
+    p.add_argument('--strength', type=float, default=0.5, help='filter strength in noise standard deviations (default 0.5)')
+    return p
+
+
+def main(argv=None):
+    from . import denoise as D
+    a = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    if a.sigma is None and a.camera is None:
+        raise ValueError('the baseline needs --sigma or --camera')
+    if a.bf16:
+        raise ValueError('--bf16 is the network\'s precision: the classical baseline runs in integers')
+    inputs, outdir, _, o = D.options_from(a)
+    den = ClassicalDenoiser(o['cfa'], a.K, sigma=a.sigma, camera=a.camera, search=a.search, patch=a.patch, strength=a.strength)
+    return D.run_frames(den, inputs, outdir, o)
+
+
+if __name__ == '__main__':
+    sys.exit(main())

@@ -276,7 +276,9 @@ def run_network(denoiser, x, chop=None):
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
                 chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None, shading=None, iso=None, flatfield=None,
                 lens='srgb'):
-    """Denoise uint16 sensor mosaics with a trained U-Net.
+    """Denoise uint16 sensor mosaics with a trained U-Net -- or, given an eld_amd.classical.ClassicalDenoiser in place of a Denoiser, with the
+    classical baseline (Anscombe transform, non-local means, unbiased inverse on the sensor's codes instead of the input stage and the
+    network; `chop` is then ignored, and 'packed' is the baseline's output in the network's convention).
 
     mosaic_u16  NumPy uint16 array or CUDA uint16 / int16-view tensor, (Hm, Wm) or (N, Hm, Wm) -- rawpy's raw_image_visible.
     cfa         'bayer' (4 planes; raw_pattern: rawpy's 2x2 raw_pattern, default RGGB; black_level: 1 or 4 values, default 512) or
@@ -359,7 +361,11 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         raise ValueError('the full-size render needs a Bayer raw_pattern with its greens on a diagonal, got %r' % (raw_pattern,))
 
     import torch
-    dev = next(denoiser.net.parameters()).device
+    classical = getattr(denoiser, 'is_classical', False)          # eld_amd.classical.ClassicalDenoiser: no network, so no device of its own
+    if classical:
+        dev = mosaic_u16.device if kind == 'torch' else torch.device('cuda', torch.cuda.current_device())
+    else:
+        dev = next(denoiser.net.parameters()).device
     if dev.type != 'cuda':
         raise ValueError('the denoiser must live on a CUDA device (load_denoiser(..., device=...)), it is on %s' % dev)
     if kind == 'numpy':
@@ -371,11 +377,15 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     t3 = t if batched else t.unsqueeze(0)
     if defects is not None:
         t3 = repair_device(t3, defects)
-    if flatfield is None:
-        x = pack_input(t3, cfa, pat, blk, white, ratios, shading, tval)
+    if classical:                                                 # the sensor's codes, not the clipped input; chop has no meaning here
+        with torch.cuda.device(dev):
+            net_out = out = denoiser.denoise_codes(t3, pat, blk, white, ratios, shading, tval, flatfield)
     else:
-        x = pack_input(t3, cfa, pat, blk, white, ratios, shading, tval, flatfield)
-    net_out = out = run_network(denoiser, x, chop)
+        if flatfield is None:
+            x = pack_input(t3, cfa, pat, blk, white, ratios, shading, tval)
+        else:
+            x = pack_input(t3, cfa, pat, blk, white, ratios, shading, tval, flatfield)
+        net_out = out = run_network(denoiser, x, chop)
     mosaic = t3.clone()                   # X-Trans: the borders outside whole cells keep the input's codes
     if flatfield is not None and lens != 'off':
         out = net_out * flatfield.packed_lens(dev)             # what the sRGB stages below render; they and the write-back clip after it
@@ -473,7 +483,11 @@ def build_parser():
 
 def parse_args(argv):
     """-> (inputs, outdir, ckpt, options for load_denoiser / denoise_raw).  Command-line values override the sidecar's."""
-    a = build_parser().parse_args(argv)
+    return options_from(build_parser().parse_args(argv))
+
+
+def options_from(a):
+    """parse_args on a namespace already parsed by build_parser() or a parser that extends it (eld_amd.classical)."""
     o = read_sidecar(a.meta) if a.meta else {}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
            'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'precision': 'bf16' if a.bf16 else None,
@@ -522,6 +536,11 @@ def _save_png(path, hwc):
 def main(argv=None):
     inputs, outdir, ckpt, o = parse_args(sys.argv[1:] if argv is None else argv)
     den = load_denoiser(ckpt, cfa=o['cfa'], precision=o['precision'])
+    return run_frames(den, inputs, outdir, o)
+
+
+def run_frames(den, inputs, outdir, o):
+    """The command line's loop: denoise every input with `den` (a Denoiser or a ClassicalDenoiser) under the options `o`, write the outputs."""
     os.makedirs(outdir, exist_ok=True)
     kw = {k: o.get(k) for k in ('raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'chop', 'rounding', 'srgb_size')}
     if o.get('defects') is not None:

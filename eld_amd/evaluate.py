@@ -16,7 +16,7 @@ bias and RMSE curves on the host in float64 (level_curves).  The contract, the b
 sec. 19.
 
 Command line: python -m eld_amd.evaluate pairs.json --ckpt net.pt [--meta sensor.json] [--bf16] [--no-correct] [--crop N] [--defects F]
-[--shading F] [--json OUT] [--save DIR]
+[--shading F] [--json OUT] [--save DIR] [--baseline-K K (--baseline-sigma S | --baseline-camera TABLE)]
 """
 import argparse
 import ctypes
@@ -34,6 +34,7 @@ NB = L.PAIRSTATS_BINS
 STATS = ('n', 'sum_s', 'sum_e', 'sum_e2')
 GROUP_NAMES = {'bayer': ('R', 'G1', 'B', 'G2'), 'xtrans': ('R', 'G', 'B')}
 METRICS = ('psnr', 'ssim', 'psnr_in', 'ssim_in')
+BASELINE_METRICS = ('psnr_nlm', 'ssim_nlm')                # added by evaluate_pairs(..., baseline=ClassicalDenoiser)
 
 
 # ---- the bins (host) --------------------------------------------------------------------------------------------------------------------
@@ -285,21 +286,21 @@ def _cut_bitmap(defects, phase, shape, dev):
     return torch.from_numpy(pack_bitmap(m).view(np.int32).copy()).to(dev)
 
 
-def table_by_iso_ratio(rows):
+def table_by_iso_ratio(rows, metrics=METRICS):
     """Means of the metrics over the rows that share (iso, ratio), sorted by iso (rows without one last) then ratio: the paper's layout."""
     keys = sorted({(r['iso'], r['ratio']) for r in rows}, key=lambda k: (k[0] is None, k[0] or 0.0, k[1]))
     table = []
     for iso, ratio in keys:
         sel = [r for r in rows if r['iso'] == iso and r['ratio'] == ratio]
         row = {'iso': iso, 'ratio': ratio, 'count': len(sel)}
-        for k in METRICS:
+        for k in metrics:
             row[k] = float(np.mean([r[k] for r in sel]))
         table.append(row)
     return table
 
 
 def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, white_point=16383, correct=True, crop=None, chop=None, defects=None,
-                   shading=None, levels=True, on_pair=None, flatfield=None):
+                   shading=None, levels=True, on_pair=None, flatfield=None, baseline=None):
     """Evaluate `denoiser` (denoise.load_denoiser) on captured pairs, as the reference's test scripts do.
 
     pairs     a list of dicts: 'short' and 'long' (uint16 mosaics (Hm,Wm): NumPy, or CUDA uint16 / int16-view tensors) and either 'ratio' or
@@ -314,6 +315,11 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
     levels    also the error-versus-signal sums (pair_level_stats) of the corrected output and of the clipped input, both written back to
               codes with rounding='nearest', against the long exposure's codes.
     on_pair   called as on_pair(index, row, {'input', 'output', 'target'}) with the packed CUDA tensors of each pair (the command line's --save).
+    baseline  None, or a ClassicalDenoiser (eld_amd.classical): the short exposure's codes also go through the classical baseline (the same
+              repair, shading and flat-field maps, the same crop and illuminance correction), and every row gains psnr_nlm and ssim_nlm, the
+              table and the mean their means, and with levels 'sums', 'curves' and 'pooled' a third set 'baseline'; the tensors handed to
+              on_pair gain 'baseline'.  A pair's 'K' (its gain in DN per electron: ISO changes it) replaces the baseline's for that pair
+              (ClassicalDenoiser.with_gain).  With None every key and number of the report is what it was without this argument.
 
     Returns {'pairs': rows, 'table': means per (iso, ratio), 'mean': the means over all pairs, 'groups': the colour groups' names,
     'pooled': {'output', 'input'} curves over all pairs (None without levels)}.  A row holds psnr, ssim (output against target), psnr_in,
@@ -343,6 +349,13 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
         flatfield = as_flat_field(flatfield)
         flatfield.check_pattern(None if cfa == 'xtrans' else np.asarray(pat).reshape(2, 2), 'evaluate_pairs')
     info = _check_pairs(pairs, cfa, crop, shading)
+    if baseline is not None:
+        if not getattr(baseline, 'is_classical', False):
+            raise ValueError('baseline must be a ClassicalDenoiser (eld_amd.classical) or None, got %r' % (type(baseline).__name__,))
+        if baseline.cfa != cfa:
+            raise ValueError('the baseline was made for cfa=%r, called with %r' % (baseline.cfa, cfa))
+        baselines = [baseline if pr.get('K') is None else baseline.with_gain(pr['K']) for pr in pairs]
+    metrics = METRICS + (BASELINE_METRICS if baseline is not None else ())
     for i, (_, shape, _, iso) in enumerate(info):
         if flatfield is not None:
             flatfield.check_frames(shape, cfa, 'pair %d' % i)
@@ -361,6 +374,8 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
     span = [white - b for b in blk] if cfa == 'bayer' else white - blk[0]
     rows = []
     pooled = {'output': 0, 'input': 0}
+    if baseline is not None:
+        pooled['baseline'] = 0
     with torch.cuda.device(dev):
         for i, (pr, (_, shape, ratio, iso)) in enumerate(zip(pairs, info)):
             short, long_ = _to_device(pr['short'], dev), _to_device(pr['long'], dev)
@@ -384,9 +399,19 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
             q = quality_assess_frames(out, target)[0].tolist()
             qi = quality_assess_frames(x, target)[0].tolist()
             row = {'name': pr.get('name'), 'ratio': ratio, 'iso': iso, 'psnr': q[0], 'ssim': q[1], 'psnr_in': qi[0], 'ssim_in': qi[1]}
+            sets = (('output', out), ('input', x))
+            if baseline is not None:
+                nlm = baselines[i].denoise_codes(short, pat, blk, white, [ratio], shading, None if shading is None else shading.t(iso), flatfield)
+                if crop is not None:
+                    nlm = nlm[:, :, y0:y0 + crop, x0:x0 + crop].contiguous()
+                if correct:
+                    nlm = illuminance_correct(nlm, target)
+                qn = quality_assess_frames(nlm, target)[0].tolist()
+                row['psnr_nlm'], row['ssim_nlm'] = qn[0], qn[1]
+                sets += (('baseline', nlm),)
             if levels:
                 sums = {}
-                for k, t in (('output', out), ('input', x)):
+                for k, t in sets:
                     est, ref, phase = _codes(t, y0, x0, long_, cfa, pat, blk, white)
                     p, group, G, black = _cells(cfa, _rolled_pattern(cfa, raw_pattern, phase), blk)
                     cut = tuple(int(v) for v in est.shape[1:])
@@ -397,18 +422,26 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
                 row['psnr_codes'] = row['curves']['output']['psnr_codes']
             rows.append(row)
             if on_pair is not None:
-                on_pair(i, row, {'input': x, 'output': out, 'target': target})
-    mean = {k: float(np.mean([r[k] for r in rows])) for k in METRICS}
-    return {'pairs': rows, 'table': table_by_iso_ratio(rows), 'mean': mean, 'groups': list(GROUP_NAMES[cfa]), 'bin_lower_edges': bin_lower_edges(),
+                tensors = {'input': x, 'output': out, 'target': target}
+                if baseline is not None:
+                    tensors['baseline'] = nlm
+                on_pair(i, row, tensors)
+    mean = {k: float(np.mean([r[k] for r in rows])) for k in metrics}
+    return {'pairs': rows, 'table': table_by_iso_ratio(rows, metrics), 'mean': mean, 'groups': list(GROUP_NAMES[cfa]), 'bin_lower_edges': bin_lower_edges(),
             'pooled': {k: level_curves(v, span) for k, v in pooled.items()} if levels else None}
 
 
 # ---- reports ----------------------------------------------------------------------------------------------------------------------------
 def table_lines(table):
     lines = ['%8s %8s %5s %9s %8s %9s %8s' % ('iso', 'ratio', 'n', 'PSNR', 'SSIM', 'PSNR in', 'SSIM in')]
+    nlm = bool(table) and 'psnr_nlm' in table[0]                   # evaluate_pairs(..., baseline=...): two more columns
+    if nlm:
+        lines[0] += ' %9s %8s' % ('PSNR nlm', 'SSIM nlm')
     for r in table:
         lines.append('%8s %8.4g %5d %9.3f %8.4f %9.3f %8.4f' % ('-' if r['iso'] is None else '%g' % r['iso'], r['ratio'], r['count'], r['psnr'], r['ssim'],
                                                                r['psnr_in'], r['ssim_in']))
+        if nlm:
+            lines[-1] += ' %9.3f %8.4f' % (r['psnr_nlm'], r['ssim_nlm'])
     return lines
 
 
@@ -417,8 +450,11 @@ def curve_lines(pooled, groups):
     next to the input's."""
     edges = bin_lower_edges()
     lines = []
+    b_ = pooled.get('baseline')                                   # evaluate_pairs(..., baseline=...): the baseline's bias and RMSE, appended
     for g, name in enumerate(groups):
         lines.append('%s: %8s %10s %10s | %10s %10s | %10s %10s' % (name, 's >=', 'sites', 'signal', 'bias out', 'bias in', 'rmse out', 'rmse in'))
+        if b_ is not None:
+            lines[-1] += ' | %10s %10s' % ('bias nlm', 'rmse nlm')
         o, i = pooled['output'], pooled['input']
         for b in range(NB):
             if o['n'][g, b] == 0:
@@ -426,11 +462,13 @@ def curve_lines(pooled, groups):
             lines.append('%s  %8s %10d %10.2f | %+10.3f %+10.3f | %10.3f %10.3f' % (' ' * len(name), 'sat' if b == NB - 1 else '%d' % edges[b], o['n'][g, b],
                                                                                   o['signal'][g, b], o['bias'][g, b], i['bias'][g, b], o['rmse'][g, b],
                                                                                   i['rmse'][g, b]))
+            if b_ is not None:
+                lines[-1] += ' | %+10.3f %10.3f' % (b_['bias'][g, b], b_['rmse'][g, b])
     return lines
 
 
 # ---- command line -----------------------------------------------------------------------------------------------------------------------
-PAIR_KEYS = ('short', 'long', 'ratio', 'iso', 'exposure', 'long_iso', 'long_exposure', 'name')
+PAIR_KEYS = ('short', 'long', 'ratio', 'iso', 'exposure', 'long_iso', 'long_exposure', 'name', 'K')
 OPTION_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'wb', 'ccm', 'precision', 'chop', 'defects', 'shading', 'flatfield')
 
 
@@ -494,6 +532,13 @@ def build_parser():
     p.add_argument('--flatfield', metavar='F', help='a flat-field map written by eld_amd.flatfield (.npz): its PRNU plane corrects both exposures')
     p.add_argument('--json', metavar='OUT', help='write the whole report as JSON')
     p.add_argument('--save', metavar='DIR', help='write sRGB PNGs of input, output and target at packed resolution (needs wb and ccm)')
+    p.add_argument('--baseline-K', type=float, metavar='K', help="also evaluate the classical baseline (eld_amd.classical) with this gain in DN per "
+                                                                 "electron; a pair's own 'K' in the manifest replaces it for that pair")
+    p.add_argument('--baseline-sigma', type=float, metavar='S', help='read noise of the baseline in DN (default: the g_scale line of --baseline-camera)')
+    p.add_argument('--baseline-camera', metavar='TABLE', help='a calibrated table (a name or a _params.npy path) the baseline reads its read noise from')
+    p.add_argument('--baseline-search', type=int, default=7, metavar='S', help='search radius of the baseline (default 7)')
+    p.add_argument('--baseline-patch', type=int, default=2, metavar='P', help='patch radius of the baseline (default 2)')
+    p.add_argument('--baseline-strength', type=float, default=0.5, metavar='H', help='filter strength of the baseline (default 0.5)')
     return p
 
 
@@ -519,6 +564,10 @@ def parse_args(argv):
         raise ValueError('--save renders sRGB: the manifest or --meta must hold wb and ccm')
     if o.get('shading') is not None and any(pr.get('iso') is None for pr in pairs):
         raise ValueError('--shading needs iso in every pair')
+    if a.baseline_K is None and (a.baseline_sigma is not None or a.baseline_camera is not None):
+        raise ValueError('--baseline-sigma and --baseline-camera belong to --baseline-K')
+    if a.baseline_K is not None and a.baseline_sigma is None and a.baseline_camera is None:
+        raise ValueError('--baseline-K needs --baseline-sigma or --baseline-camera')
     return a, o, pairs
 
 
@@ -543,13 +592,22 @@ def main(argv=None):
     from .validate import to_jsonable
     a, o, pairs = parse_args(sys.argv[1:] if argv is None else argv)
     den = load_denoiser(a.ckpt, cfa=o['cfa'], precision=o['precision'])
+    base = None
+    if a.baseline_K is not None:
+        from .classical import ClassicalDenoiser
+        base = ClassicalDenoiser(o['cfa'], a.baseline_K, sigma=a.baseline_sigma, camera=a.baseline_camera, search=a.baseline_search,
+                                 patch=a.baseline_patch, strength=a.baseline_strength)
     rep = evaluate_pairs(den, load_pairs(pairs), o['cfa'], raw_pattern=o.get('raw_pattern'), black_level=o.get('black_level'),
                          white_point=o['white_point'], correct=not a.no_correct, crop=a.crop, chop=o.get('chop'), defects=o.get('defects'),
-                         shading=o.get('shading'), flatfield=o.get('flatfield'), on_pair=_saver(a.save, o['cfa'], o['wb'], o['ccm']) if a.save else None)
+                         shading=o.get('shading'), flatfield=o.get('flatfield'), on_pair=_saver(a.save, o['cfa'], o['wb'], o['ccm']) if a.save else None,
+                         baseline=base)
     for line in table_lines(rep['table']):
         print(line)
     print('mean over %d pairs: PSNR %.3f SSIM %.4f (input: %.3f %.4f)' % (len(rep['pairs']), rep['mean']['psnr'], rep['mean']['ssim'],
                                                                           rep['mean']['psnr_in'], rep['mean']['ssim_in']))
+    if base is not None:
+        print('classical baseline (search %d, patch %d, strength %g): PSNR %.3f SSIM %.4f' % (base.search, base.patch, base.strength,
+                                                                                              rep['mean']['psnr_nlm'], rep['mean']['ssim_nlm']))
     for line in curve_lines(rep['pooled'], rep['groups']):
         print(line)
     if a.json:

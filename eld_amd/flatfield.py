@@ -186,13 +186,18 @@ class FlatField:
 
     def packed_lens(self, device):
         """The lens plane in the network's packed layout (1,C,h,w) on `device`: packed once with the existing packing routine, then cached."""
+        return self.packed(device, 'lens')
+
+    def packed(self, device, part='lens'):
+        """The gain plane of `part` in the network's packed layout (1,C,h,w) on `device`, packed once per device and part."""
         import torch
         device = torch.device(device)
         if device.type == 'cuda' and device.index is None:
             device = torch.device('cuda', torch.cuda.current_device())
-        if device not in self._packed:
+        key = (device, check_part(part))
+        if key not in self._packed:
             Hm, Wm = self.shape
-            src = self.on(device, 'lens')
+            src = self.on(device, part)
             with torch.cuda.device(device):
                 if self.cfa == 'bayer':
                     # eld_pack_bayer's planes are the cell positions (0,0), (0,1), (1,1), (1,0); the network's plane k is the position of code k
@@ -204,8 +209,8 @@ class FlatField:
                 else:
                     out = torch.empty((1, 9, 2 * (Hm // 6), 2 * (Wm // 6)), dtype=torch.float32, device=device)
                     L.check(L.lib().eld_pack_xtrans(L.dptr(src), L.dptr(out), 1, Hm, Wm, L.cur_stream()), 'eld_pack_xtrans')
-            self._packed[device] = out
-        return self._packed[device]
+            self._packed[key] = out
+        return self._packed[key]
 
     def check_frames(self, shape, cfa, what='frames'):
         """ValueError unless mosaics of `shape` ((..., Hm, Wm)) and `cfa` are what this map was made for."""

@@ -864,6 +864,28 @@ int eld_pack_raw_bayer_u16_flat(const uint16_t* mosaic, float* packed, int N, in
 int eld_pack_raw_xtrans_u16_flat(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
                                  const float* ratios, const float* ma, const float* mb, float t, const float* gain, void* stream);
 
+/* ---- a classical baseline: non-local means on variance-stabilised codes (csrc/nlm.hip, eld_amd/classical.py) ----------------
+ * Appended without a change of ELD_ABI_VERSION (no existing signature changed).  Integer arithmetic from the table lookup on: the result is
+ * defined bit for bit whatever the launch geometry, and tests/nlm_ref.py restates every line below in NumPy.
+ *
+ * eld_nlm_vst_f32: x [N][C][h][w] float32 (device; 4-byte aligned, nothing more), fwd [C][65536] uint16 (device): the forward transform of
+ * plane c as a table over the sensor codes; wtab: HOST array of 256 uint16 weights; out [N][C][h][w] int32 (device).
+ *   codes     i = clamp(rintf(x * qscale), 0, 65535): one float32 multiply, round half to even, NaN -> 0;  v_c = min(fwd[c][i], 32767)
+ *   extension V_c = v_c extended beyond the plane by edge replication
+ *   distance  for an offset d = (dy, dx), |dy|, |dx| <= S:
+ *               D_d(q) = sum over c, sum over |u|_inf <= P of clamp(V_c(q + u) - V_c(q + u + d), -1023, 1023)^2
+ *             a candidate counts only when q + d lies inside the plane (d = 0 always does)
+ *   weight    wt = wtab[min(D_d(q) >> sh, 255)]
+ *   output    num_c = sum of wt * v_c(q + d), den = sum of wt over the counted offsets;
+ *             out_c(q) = (2 * (num_c << frac) + den) / (2 * den), floor division: the weighted mean in units of 2^-frac of a code
+ * Ranges: 1 <= N; 1 <= C <= 16; 1 <= h, w; 0 <= S <= 10; 0 <= P <= 3; 0 <= sh <= 24; 0 <= frac <= 8; wtab[k] <= 255; wtab[0] >= 1; no null
+ * pointer; fwd 2-byte, x and out 4-byte aligned.  Anything else is ELD_EINVAL before any device work.  They make every width provable:
+ * D <= 1023^2 * 16 * 49 < 2^31, num <= 255 * 32767 * 441 < 2^32; only the last shift needs more than 32 bits.
+ * The distance is a box sum of the per-position squared difference (row sums, then running column sums): the work per site and offset does not
+ * grow with the patch area. */
+int eld_nlm_vst_f32(const float* x, int N, int C, int h, int w, float qscale, const uint16_t* fwd, int S, int P, int sh, const uint16_t* wtab,
+                    int frac, int32_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
