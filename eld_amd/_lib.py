@@ -159,6 +159,9 @@ SIGNATURES = {
     'eld_pack_raw_bayer_u16_flat': (_i, [_vp, _vp, _i, _i, _i, C.POINTER(C.c_int), C.POINTER(C.c_float), _f, _vp, _vp, _vp, _f, _vp, _vp]),
     'eld_pack_raw_xtrans_u16_flat': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _vp, _vp]),
     'eld_nlm_vst_f32': (_i, [_vp, _i, _i, _i, _i, _f, _vp, _i, _i, _i, C.POINTER(C.c_uint16), _i, _vp, _vp]),
+    'eld_bm3d_vst_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'eld_bm3d_vst_f32': (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _i, _i, _i, _u32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), _i, _vp, _vp,
+                              _sz, _vp]),
 }
 
 

@@ -13,8 +13,14 @@ one HIP kernel in integer arithmetic (csrc/nlm.hip: eld_nlm_vst_f32, restated bi
 Each plane of the result is z * ratio / (white - black): the network's output convention, so the lens gain, the write-back, the ISP and the
 demosaic of denoise_raw follow unchanged.  The contract, the table builders and the measured times are DESIGN.md sec. 24.
 
+With method='bm3d' the filter is BM3D instead (csrc/bm3d.hip: eld_bm3d_vst_f32, restated by tests/bm3d_ref.py): 8 x 8 blocks matched with
+distances shared by the planes, a Walsh-Hadamard transform over [planes][group][8][8] -- across the four Bayer planes as well, where every
+plane has unit noise variance -- hard thresholding, then an empirical Wiener filter guided by the first estimate; the tables and the inverse
+around it are the same.  DESIGN.md sec. 25.
+
 Command line: python -m eld_amd.classical frames.npy... -o DIR --meta sensor.json --K K [--sigma S | --camera TABLE] [--search 7]
-[--patch 2] [--strength 0.5] and every sensor option of python -m eld_amd.denoise (which keeps its required --ckpt)."""
+[--patch 2] [--strength 0.5] [--method bm3d [--step 3] [--group 16] [--no-mix]] and every sensor option of python -m eld_amd.denoise (which
+keeps its required --ckpt)."""
 import ctypes
 import math
 import os
@@ -27,6 +33,11 @@ from . import _lib as L
 Q = 16                          # stabilised codes per noise standard deviation
 FRAC = 4                        # fractional bits of the filtered code: 1 / 256 of a standard deviation
 MAX_SEARCH, MAX_PATCH = 10, 3   # the kernel's argument ranges (include/eld_amd.h)
+BM3D_MAX_SEARCH, BM3D_MAX_STEP, BM3D_GROUPS, BM3D_BLOCK = 16, 8, (1, 2, 4, 8, 16), 8
+METHODS = ('nlm', 'bm3d')
+# rint(16 kaiser(8, 2) x kaiser(8, 2)), written out: no Bessel routine is part of the contract
+BM3D_WINDOW = ((3, 5, 6, 7, 7, 6, 5, 3), (5, 7, 10, 11, 11, 10, 7, 5), (6, 10, 12, 14, 14, 12, 10, 6), (7, 11, 14, 16, 16, 14, 11, 7),
+               (7, 11, 14, 16, 16, 14, 11, 7), (6, 10, 12, 14, 14, 12, 10, 6), (5, 7, 10, 11, 11, 10, 7, 5), (3, 5, 6, 7, 7, 6, 5, 3))
 
 
 # ---- tables (host, float64, fixed order) --------------------------------------------------------------------------------------------------
@@ -79,6 +90,31 @@ def nlm_weight_table(C, P, strength):
     return sh, wt
 
 
+def bm3d_tables(C, mix, strength=1.0, lam=2.7):
+    """-> (tau1, thr uint32 (5,), tau2, s2 uint32 (5,), win uint8 (64,)): the match thresholds of the two steps, the hard threshold and the
+    Wiener noise energy per group size 2^lg, and the aggregation window.  With Q codes per noise standard deviation a block distance has
+    n = 64 C terms of expectation 2 Q^2 each, and an unnormalised Walsh-Hadamard coefficient over M 2^lg blocks of 64 sites has the standard
+    deviation 8 Q sqrt(M 2^lg) (M = C planes per transformed set with mix, else 1):
+      tau1 = 4 Q^2 n strength^2            thr[lg] = rint(lam 8 Q strength sqrt(M 2^lg))
+      tau2 = rint(0.64 Q^2 n strength^2)   s2[lg]  = rint((8 Q strength)^2 M 2^lg)"""
+    C, mix, strength, lam = int(C), bool(mix), float(strength), float(lam)
+    if not (1 <= C <= 16):
+        raise ValueError('C must be in [1, 16], got %d' % C)
+    if mix and C & (C - 1):
+        raise ValueError('grouping across the planes needs a power-of-two number of them, got %d' % C)
+    if not (math.isfinite(strength) and strength > 0) or not (math.isfinite(lam) and lam > 0):
+        raise ValueError('strength and lam must be finite and > 0, got %r and %r' % (strength, lam))
+    n = 64 * C
+    M = C if mix else 1
+    tau1 = int(np.rint(4.0 * Q * Q * n * strength * strength))
+    tau2 = int(np.rint(0.64 * Q * Q * n * strength * strength))
+    thr = [float(np.rint(lam * 8.0 * Q * strength * np.sqrt(float(M << lg)))) for lg in range(5)]
+    s2 = [float(np.rint((8.0 * Q * strength) ** 2 * float(M << lg))) for lg in range(5)]
+    if tau1 >= 1 << 30 or max(thr + s2) >= float(1 << 32) or min(s2) < 1.0:
+        raise ValueError('strength %g puts the BM3D tables outside the kernel\'s ranges' % strength)
+    return tau1, np.array(thr).astype(np.uint32), tau2, np.array(s2).astype(np.uint32), np.array(BM3D_WINDOW, np.uint8).reshape(-1)
+
+
 def unbiased_inverse(out, frac, K, sigma):
     """The filtered codes (units of 2^-frac of a stabilised code) -> DN above black, float64 on the tensor's device: the closed form of
     Makitalo and Foi for the generalised Anscombe transform, with D = out / (Q 2^frac), s = sigma / K, Dm = max(D, 2 sqrt(3/8 + s^2)):
@@ -113,6 +149,39 @@ def nlm_vst(x, qscale, fwd, S, P, sh, wtab, frac, out=None):
     with torch.cuda.device(x.device):
         L.check(L.lib().eld_nlm_vst_f32(L.dptr(x), N, C, h, w, float(qscale), L.dptr(fwd), int(S), int(P), int(sh),
                                         wt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)), int(frac), L.dptr(out), L.cur_stream()), 'eld_nlm_vst_f32')
+    return out
+
+
+def bm3d_vst(x, qscale, fwd, guide, S, step, Gmax, mix, tau, par, win, frac, out=None):
+    """eld_bm3d_vst_f32 on CUDA tensors: x and fwd as for nlm_vst; guide None (step 1: hard threshold, par the thresholds) or step 1's int32
+    output (step 2: Wiener, par the noise energies); par 5 and win 64 host values -> int32 (N,C,h,w) in units of 2^-frac of a stabilised code.
+    The workspace is allocated here; the library checks the argument ranges (ELD_EINVAL -> EldError)."""
+    import torch
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_cuda:
+        raise ValueError('x must be a CUDA float32 tensor (N, C, h, w)')
+    x = x if x.is_contiguous() else x.contiguous()
+    N, C, h, w = (int(v) for v in x.shape)
+    if tuple(fwd.shape) != (C, 65536) or fwd.element_size() != 2 or fwd.device != x.device or not fwd.is_contiguous():
+        raise ValueError('fwd must be a contiguous 16-bit tensor (%d, 65536) on %s' % (C, x.device))
+    if guide is not None and (guide.dtype != torch.int32 or tuple(guide.shape) != (N, C, h, w) or guide.device != x.device or not guide.is_contiguous()):
+        raise ValueError('guide must be a contiguous int32 tensor of x\'s shape and device')
+    pr = np.ascontiguousarray(np.asarray(par).reshape(-1), dtype=np.uint32)
+    wn = np.ascontiguousarray(np.asarray(win).reshape(-1), dtype=np.uint8)
+    if pr.size != 5 or wn.size != 64:
+        raise ValueError('par takes 5 values and win 64, got %d and %d' % (pr.size, wn.size))
+    if not (0 <= int(tau) < 1 << 32):
+        raise ValueError('tau must fit 32 bits, got %r' % (tau,))
+    if out is None:
+        out = torch.empty((N, C, h, w), dtype=torch.int32, device=x.device)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (N, C, h, w) or out.device != x.device or not out.is_contiguous():
+        raise ValueError('out must be a contiguous int32 tensor of x\'s shape and device')
+    need = int(L.lib().eld_bm3d_vst_workspace_bytes(N, C, h, w))
+    ws = torch.empty(max(need, 8), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().eld_bm3d_vst_f32(L.dptr(x), N, C, h, w, float(qscale), L.dptr(fwd), None if guide is None else L.dptr(guide), int(S), int(step),
+                                         int(Gmax), int(mix), int(tau), pr.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                         wn.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), int(frac), L.dptr(out), L.dptr(ws), need, L.cur_stream()),
+                'eld_bm3d_vst_f32')
     return out
 
 
@@ -153,12 +222,23 @@ class ClassicalDenoiser:
     cfa       'bayer' or 'xtrans': in_channels = out_channels = its plane count
     K, sigma  overall system gain and read noise (Gaussian, signal-independent) in DN; sigma None: from `camera` (sigma_from_table)
     search, patch   the radii S and P: candidates within |d| <= search, patches of (2 patch + 1)^2 sites in every plane
-    strength  the filter parameter in units of the noise standard deviation per patch term"""
+    strength  the filter parameter in units of the noise standard deviation per patch term
+    method    'nlm' (search 7, patch 2, strength 0.5 by default) or 'bm3d' (search 12 at most 16, strength 1.0; blocks are 8 x 8, so a
+              patch other than the default is refused): the filter in the stabilised domain; `label` holds the same word
+    step, group, mix   BM3D only: the stride of the reference blocks (1 to 8), the largest group (1, 2, 4, 8 or 16 blocks) and whether the
+              transform also runs across the planes (None: when their number is a power of two -- Bayer yes, X-Trans no)"""
     is_classical = True
 
-    def __init__(self, cfa, K, sigma=None, camera=None, search=7, patch=2, strength=0.5):
+    def __init__(self, cfa, K, sigma=None, camera=None, search=None, patch=2, strength=None, method='nlm', step=3, group=16, mix=None):
         from .denoise import PLANES, _check_cfa
         _check_cfa(cfa)
+        if method not in METHODS:
+            raise ValueError('method must be one of %r, got %r' % (METHODS, method))
+        bm3d = method == 'bm3d'
+        if search is None:
+            search = 12 if bm3d else 7
+        if strength is None:
+            strength = 1.0 if bm3d else 0.5
         if sigma is None:
             if camera is None:
                 raise ValueError('ClassicalDenoiser needs sigma, or a camera table to read it from')
@@ -167,12 +247,30 @@ class ClassicalDenoiser:
         else:
             self._camera = None
         self.K, self.sigma = _check_noise(K, sigma)
-        for name, v, top in (('search', search, MAX_SEARCH), ('patch', patch, MAX_PATCH)):
+        for name, v, top in (('search', search, BM3D_MAX_SEARCH if bm3d else MAX_SEARCH), ('patch', patch, MAX_PATCH)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not (0 <= v <= top):
                 raise ValueError('%s must be an integer in [0, %d], got %r' % (name, top, v))
         self.cfa, self.search, self.patch, self.strength = cfa, int(search), int(patch), float(strength)
         self.planes = PLANES[cfa]
-        self.sh, self.wtab = nlm_weight_table(self.planes, self.patch, self.strength)
+        self.method = self.label = method
+        if bm3d:
+            if self.patch != 2:
+                raise ValueError('BM3D blocks are %d x %d: patch takes no value but its default, got %r' % (BM3D_BLOCK, BM3D_BLOCK, patch))
+            if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not (1 <= step <= BM3D_MAX_STEP):
+                raise ValueError('step must be an integer in [1, %d], got %r' % (BM3D_MAX_STEP, step))
+            if isinstance(group, bool) or group not in BM3D_GROUPS:
+                raise ValueError('group must be one of %r, got %r' % (BM3D_GROUPS, group))
+            pow2 = self.planes & (self.planes - 1) == 0
+            if mix is None:
+                mix = pow2
+            if mix not in (False, True, 0, 1):
+                raise ValueError('mix must be None, False or True, got %r' % (mix,))
+            if mix and not pow2:
+                raise ValueError('grouping across the planes needs a power-of-two number of them: %s has %d' % (cfa, self.planes))
+            self.step, self.group, self.mix = int(step), int(group), bool(mix)
+            self.tables = bm3d_tables(self.planes, self.mix, self.strength)
+        else:
+            self.sh, self.wtab = nlm_weight_table(self.planes, self.patch, self.strength)
         self._fwd = {}
         self._others = {}
 
@@ -183,8 +281,11 @@ class ClassicalDenoiser:
             return self
         if K not in self._others:
             self._others[K] = ClassicalDenoiser(self.cfa, K, sigma=None if self._camera is not None else self.sigma, camera=self._camera,
-                                                search=self.search, patch=self.patch, strength=self.strength)
+                                                search=self.search, patch=self.patch, strength=self.strength, **self._method_args())
         return self._others[K]
+
+    def _method_args(self):
+        return dict(method='bm3d', step=self.step, group=self.group, mix=self.mix) if self.method == 'bm3d' else {}
 
     @property
     def in_channels(self):
@@ -225,7 +326,15 @@ class ClassicalDenoiser:
         """The corrected codes over 65535 (pack_codes) -> float32 (N,C,h,w) in the network's output convention."""
         import torch
         fwd = self.fwd_on(x.device, black_level)
-        out = nlm_vst(x, 65535.0, fwd, self.search, self.patch, self.sh, self.wtab, FRAC)
+        if self.method == 'bm3d':
+            h, w = int(x.shape[2]), int(x.shape[3])
+            if h < BM3D_BLOCK or w < BM3D_BLOCK:
+                raise ValueError('BM3D needs packed planes of at least %d x %d sites, this frame packs to %d x %d' % (BM3D_BLOCK, BM3D_BLOCK, h, w))
+            tau1, thr, tau2, s2, win = self.tables
+            first = bm3d_vst(x, 65535.0, fwd, None, self.search, self.step, self.group, self.mix, tau1, thr, win, FRAC)
+            out = bm3d_vst(x, 65535.0, fwd, first, self.search, self.step, self.group, self.mix, tau2, s2, win, FRAC)
+        else:
+            out = nlm_vst(x, 65535.0, fwd, self.search, self.patch, self.sh, self.wtab, FRAC)
         z = unbiased_inverse(out, FRAC, self.K, self.sigma)
         blk = torch.tensor(self.black_per_plane(black_level), dtype=torch.float64, device=x.device).reshape(1, -1, 1, 1)
         r = torch.as_tensor(np.asarray(ratios, np.float64).reshape(-1), device=x.device).reshape(-1, 1, 1, 1)
@@ -250,21 +359,36 @@ def build_parser():
     p.add_argument('--K', type=float, required=True, help='overall system gain in DN per electron (eld_amd.calibrate, eld_amd.burst)')
     p.add_argument('--sigma', type=float, help='read noise in DN (default: the g_scale line of --camera at log K)')
     p.add_argument('--camera', metavar='TABLE', help="a calibrated table: a name (camera_params/release/<name>_params.npy or a shipped one) or a .npy path")
-    p.add_argument('--search', type=int, default=7, help='search radius (default 7, at most %d)' % MAX_SEARCH)
-    p.add_argument('--patch', type=int, default=2, help='patch radius (default 2, at most %d)' % MAX_PATCH)
-    p.add_argument('--strength', type=float, default=0.5, help='filter strength in noise standard deviations (default 0.5)')
+    p.add_argument('--search', type=int, default=7, help='search radius (default 7, at most %d; with --method bm3d 12, at most %d)'
+                                                          % (MAX_SEARCH, BM3D_MAX_SEARCH))
+    p.add_argument('--patch', type=int, default=2, help='patch radius (default 2, at most %d; --method bm3d takes no other)' % MAX_PATCH)
+    p.add_argument('--strength', type=float, default=0.5, help='filter strength in noise standard deviations (default 0.5; with --method bm3d 1.0)')
+    p.add_argument('--method', choices=METHODS, default='nlm', help='the filter in the stabilised domain (default nlm)')
+    p.add_argument('--step', type=int, default=3, help='bm3d: stride of the reference blocks (default 3, at most %d)' % BM3D_MAX_STEP)
+    p.add_argument('--group', type=int, default=16, help='bm3d: the largest group, 1, 2, 4, 8 or 16 blocks (default 16)')
+    p.add_argument('--no-mix', action='store_true', help='bm3d: transform every plane alone (default: across the planes when their number is a power of two)')
     return p
+
+
+def parse_method_args(parser, argv, method_dest='method', prefix=''):
+    """Parse, and where the method is bm3d parse again with that method's defaults for the search radius and the strength."""
+    a = parser.parse_args(argv)
+    if getattr(a, method_dest) == 'bm3d':
+        parser.set_defaults(**{prefix + 'search': 12, prefix + 'strength': 1.0})
+        a = parser.parse_args(argv)
+    return a
 
 
 def main(argv=None):
     from . import denoise as D
-    a = build_parser().parse_args(sys.argv[1:] if argv is None else argv)
+    a = parse_method_args(build_parser(), sys.argv[1:] if argv is None else argv)
     if a.sigma is None and a.camera is None:
         raise ValueError('the baseline needs --sigma or --camera')
     if a.bf16:
         raise ValueError('--bf16 is the network\'s precision: the classical baseline runs in integers')
     inputs, outdir, _, o = D.options_from(a)
-    den = ClassicalDenoiser(o['cfa'], a.K, sigma=a.sigma, camera=a.camera, search=a.search, patch=a.patch, strength=a.strength)
+    den = ClassicalDenoiser(o['cfa'], a.K, sigma=a.sigma, camera=a.camera, search=a.search, patch=a.patch, strength=a.strength, method=a.method,
+                            step=a.step, group=a.group, mix=False if a.no_mix else None)
     return D.run_frames(den, inputs, outdir, o)
 
 

@@ -16,7 +16,7 @@ bias and RMSE curves on the host in float64 (level_curves).  The contract, the b
 sec. 19.
 
 Command line: python -m eld_amd.evaluate pairs.json --ckpt net.pt [--meta sensor.json] [--bf16] [--no-correct] [--crop N] [--defects F]
-[--shading F] [--json OUT] [--save DIR] [--baseline-K K (--baseline-sigma S | --baseline-camera TABLE)]
+[--shading F] [--json OUT] [--save DIR] [--baseline-K K (--baseline-sigma S | --baseline-camera TABLE) [--baseline-method bm3d]]
 """
 import argparse
 import ctypes
@@ -34,7 +34,7 @@ NB = L.PAIRSTATS_BINS
 STATS = ('n', 'sum_s', 'sum_e', 'sum_e2')
 GROUP_NAMES = {'bayer': ('R', 'G1', 'B', 'G2'), 'xtrans': ('R', 'G', 'B')}
 METRICS = ('psnr', 'ssim', 'psnr_in', 'ssim_in')
-BASELINE_METRICS = ('psnr_nlm', 'ssim_nlm')                # added by evaluate_pairs(..., baseline=ClassicalDenoiser)
+BASELINE_METRICS = ('psnr_nlm', 'ssim_nlm')                # added by evaluate_pairs(..., baseline=ClassicalDenoiser); '_bm3d' with method='bm3d'
 
 
 # ---- the bins (host) --------------------------------------------------------------------------------------------------------------------
@@ -316,8 +316,8 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
               codes with rounding='nearest', against the long exposure's codes.
     on_pair   called as on_pair(index, row, {'input', 'output', 'target'}) with the packed CUDA tensors of each pair (the command line's --save).
     baseline  None, or a ClassicalDenoiser (eld_amd.classical): the short exposure's codes also go through the classical baseline (the same
-              repair, shading and flat-field maps, the same crop and illuminance correction), and every row gains psnr_nlm and ssim_nlm, the
-              table and the mean their means, and with levels 'sums', 'curves' and 'pooled' a third set 'baseline'; the tensors handed to
+              repair, shading and flat-field maps, the same crop and illuminance correction), and every row gains psnr_nlm and ssim_nlm
+              (psnr_bm3d and ssim_bm3d with a method='bm3d' baseline: the keys take its `label`), the table and the mean their means, and with levels 'sums', 'curves' and 'pooled' a third set 'baseline'; the tensors handed to
               on_pair gain 'baseline'.  A pair's 'K' (its gain in DN per electron: ISO changes it) replaces the baseline's for that pair
               (ClassicalDenoiser.with_gain).  With None every key and number of the report is what it was without this argument.
 
@@ -355,7 +355,9 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
         if baseline.cfa != cfa:
             raise ValueError('the baseline was made for cfa=%r, called with %r' % (baseline.cfa, cfa))
         baselines = [baseline if pr.get('K') is None else baseline.with_gain(pr['K']) for pr in pairs]
-    metrics = METRICS + (BASELINE_METRICS if baseline is not None else ())
+    label = getattr(baseline, 'label', 'nlm')                  # the denoiser's method names its keys and columns
+    bkeys = ('psnr_' + label, 'ssim_' + label)
+    metrics = METRICS + (bkeys if baseline is not None else ())
     for i, (_, shape, _, iso) in enumerate(info):
         if flatfield is not None:
             flatfield.check_frames(shape, cfa, 'pair %d' % i)
@@ -407,7 +409,7 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
                 if correct:
                     nlm = illuminance_correct(nlm, target)
                 qn = quality_assess_frames(nlm, target)[0].tolist()
-                row['psnr_nlm'], row['ssim_nlm'] = qn[0], qn[1]
+                row[bkeys[0]], row[bkeys[1]] = qn[0], qn[1]
                 sets += (('baseline', nlm),)
             if levels:
                 sums = {}
@@ -432,29 +434,37 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
 
 
 # ---- reports ----------------------------------------------------------------------------------------------------------------------------
+def baseline_label(row):
+    """The label of the baseline whose columns a table row or a pair's row carries ('nlm', 'bm3d'), or None."""
+    for label in ('nlm', 'bm3d'):
+        if 'psnr_' + label in row:
+            return label
+    return None
+
+
 def table_lines(table):
     lines = ['%8s %8s %5s %9s %8s %9s %8s' % ('iso', 'ratio', 'n', 'PSNR', 'SSIM', 'PSNR in', 'SSIM in')]
-    nlm = bool(table) and 'psnr_nlm' in table[0]                   # evaluate_pairs(..., baseline=...): two more columns
+    nlm = baseline_label(table[0]) if table else None              # evaluate_pairs(..., baseline=...): two more columns
     if nlm:
-        lines[0] += ' %9s %8s' % ('PSNR nlm', 'SSIM nlm')
+        lines[0] += ' %9s %8s' % ('PSNR ' + nlm, 'SSIM ' + nlm)
     for r in table:
         lines.append('%8s %8.4g %5d %9.3f %8.4f %9.3f %8.4f' % ('-' if r['iso'] is None else '%g' % r['iso'], r['ratio'], r['count'], r['psnr'], r['ssim'],
                                                                r['psnr_in'], r['ssim_in']))
         if nlm:
-            lines[-1] += ' %9.3f %8.4f' % (r['psnr_nlm'], r['ssim_nlm'])
+            lines[-1] += ' %9.3f %8.4f' % (r['psnr_' + nlm], r['ssim_' + nlm])
     return lines
 
 
-def curve_lines(pooled, groups):
+def curve_lines(pooled, groups, label='nlm'):
     """Per colour group the populated bins: lower edge of the bin (DN above black), sites, mean signal, then bias and RMSE of the output
-    next to the input's."""
+    next to the input's; label: the baseline's, for the headings of its two columns."""
     edges = bin_lower_edges()
     lines = []
     b_ = pooled.get('baseline')                                   # evaluate_pairs(..., baseline=...): the baseline's bias and RMSE, appended
     for g, name in enumerate(groups):
         lines.append('%s: %8s %10s %10s | %10s %10s | %10s %10s' % (name, 's >=', 'sites', 'signal', 'bias out', 'bias in', 'rmse out', 'rmse in'))
         if b_ is not None:
-            lines[-1] += ' | %10s %10s' % ('bias nlm', 'rmse nlm')
+            lines[-1] += ' | %10s %10s' % ('bias ' + label, 'rmse ' + label)
         o, i = pooled['output'], pooled['input']
         for b in range(NB):
             if o['n'][g, b] == 0:
@@ -536,16 +546,22 @@ def build_parser():
                                                                  "electron; a pair's own 'K' in the manifest replaces it for that pair")
     p.add_argument('--baseline-sigma', type=float, metavar='S', help='read noise of the baseline in DN (default: the g_scale line of --baseline-camera)')
     p.add_argument('--baseline-camera', metavar='TABLE', help='a calibrated table (a name or a _params.npy path) the baseline reads its read noise from')
-    p.add_argument('--baseline-search', type=int, default=7, metavar='S', help='search radius of the baseline (default 7)')
+    p.add_argument('--baseline-search', type=int, default=7, metavar='S', help='search radius of the baseline (default 7; bm3d: 12)')
     p.add_argument('--baseline-patch', type=int, default=2, metavar='P', help='patch radius of the baseline (default 2)')
-    p.add_argument('--baseline-strength', type=float, default=0.5, metavar='H', help='filter strength of the baseline (default 0.5)')
+    p.add_argument('--baseline-strength', type=float, default=0.5, metavar='H', help='filter strength of the baseline (default 0.5; bm3d: 1.0)')
+    p.add_argument('--baseline-method', choices=('nlm', 'bm3d'), default='nlm', help='the baseline\'s filter (default nlm); it names the added '
+                                                                                      'columns and keys: psnr_nlm or psnr_bm3d')
+    p.add_argument('--baseline-step', type=int, default=3, metavar='N', help='bm3d: stride of the reference blocks (default 3)')
+    p.add_argument('--baseline-group', type=int, default=16, metavar='G', help='bm3d: the largest group (default 16)')
+    p.add_argument('--baseline-no-mix', action='store_true', help='bm3d: transform every plane alone')
     return p
 
 
 def parse_args(argv):
     """-> (argparse namespace, options, pairs).  Precedence: the manifest's fields, then --meta's, then the command line's."""
+    from .classical import parse_method_args
     from .denoise import read_sidecar
-    a = build_parser().parse_args(argv)
+    a = parse_method_args(build_parser(), argv, 'baseline_method', 'baseline_')
     o, pairs = read_manifest(a.manifest)
     if a.meta:
         side = read_sidecar(a.meta)
@@ -596,7 +612,8 @@ def main(argv=None):
     if a.baseline_K is not None:
         from .classical import ClassicalDenoiser
         base = ClassicalDenoiser(o['cfa'], a.baseline_K, sigma=a.baseline_sigma, camera=a.baseline_camera, search=a.baseline_search,
-                                 patch=a.baseline_patch, strength=a.baseline_strength)
+                                 patch=a.baseline_patch, strength=a.baseline_strength, method=a.baseline_method, step=a.baseline_step,
+                                 group=a.baseline_group, mix=False if a.baseline_no_mix else None)
     rep = evaluate_pairs(den, load_pairs(pairs), o['cfa'], raw_pattern=o.get('raw_pattern'), black_level=o.get('black_level'),
                          white_point=o['white_point'], correct=not a.no_correct, crop=a.crop, chop=o.get('chop'), defects=o.get('defects'),
                          shading=o.get('shading'), flatfield=o.get('flatfield'), on_pair=_saver(a.save, o['cfa'], o['wb'], o['ccm']) if a.save else None,
@@ -605,10 +622,14 @@ def main(argv=None):
         print(line)
     print('mean over %d pairs: PSNR %.3f SSIM %.4f (input: %.3f %.4f)' % (len(rep['pairs']), rep['mean']['psnr'], rep['mean']['ssim'],
                                                                           rep['mean']['psnr_in'], rep['mean']['ssim_in']))
-    if base is not None:
+    if base is not None and base.label == 'nlm':
         print('classical baseline (search %d, patch %d, strength %g): PSNR %.3f SSIM %.4f' % (base.search, base.patch, base.strength,
                                                                                               rep['mean']['psnr_nlm'], rep['mean']['ssim_nlm']))
-    for line in curve_lines(rep['pooled'], rep['groups']):
+    elif base is not None:
+        print('classical baseline bm3d (search %d, step %d, group %d, %s, strength %g): PSNR %.3f SSIM %.4f' % (
+            base.search, base.step, base.group, 'across the planes' if base.mix else 'every plane alone', base.strength,
+            rep['mean']['psnr_bm3d'], rep['mean']['ssim_bm3d']))
+    for line in curve_lines(rep['pooled'], rep['groups'], 'nlm' if base is None else base.label):
         print(line)
     if a.json:
         with open(a.json, 'w') as fh:

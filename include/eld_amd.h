@@ -886,6 +886,44 @@ int eld_pack_raw_xtrans_u16_flat(const uint16_t* mosaic, float* packed, int N, i
 int eld_nlm_vst_f32(const float* x, int N, int C, int h, int w, float qscale, const uint16_t* fwd, int S, int P, int sh, const uint16_t* wtab,
                     int frac, int32_t* out, void* stream);
 
+/* ---- BM3D on variance-stabilised codes, grouped across the CFA planes (csrc/bm3d.hip, eld_amd/classical.py) -------------------
+ * Appended without a change of ELD_ABI_VERSION.  Integers from the table lookup on, and the aggregation is integer addition: the result is
+ * defined bit for bit whatever the launch geometry and the order of the adds; tests/bm3d_ref.py restates every line below in NumPy.
+ *
+ * eld_bm3d_vst_f32: x, fwd, qscale and out as for eld_nlm_vst_f32; guide NULL (step 1: hard threshold) or [N][C][h][w] int32 (device), the output
+ * of step 1 in units of 2^-frac (step 2: Wiener); par: HOST, 5 uint32, one per group size 1, 2, 4, 8, 16; win: HOST, 64 uint8, the 8 x 8
+ * aggregation window; ws: device workspace of eld_bm3d_vst_workspace_bytes(N, C, h, w) bytes (0 for a shape out of range), 8-byte aligned, any
+ * contents.
+ *   codes      i = clamp(rintf(x * qscale), 0, 65535), NaN -> 0;  v_c = min(fwd[c][i], 32767)
+ *   guide      g_c = v_c without a guide, else clamp((guide + ((1 << frac) >> 1)) >> frac, 0, 32767)
+ *   blocks     8 x 8; reference corners y in {0, step, 2 step, ... <= h - 8} and h - 8, likewise x: every site is covered
+ *   matching   shared by the planes.  A candidate is an offset d = (dy, dx), |dy|, |dx| <= S, whose whole block lies inside the plane (no
+ *              replication).  D_d = sum over c, sum over u in 8 x 8 of clamp(g_c(p + u) - g_c(p + d + u), -1023, 1023)^2; it counts when
+ *              D_d <= tau.  Order: the key (D_d << 11) | r with r = 0 for d = 0 and 1 + (dy + S)(2S + 1) + (dx + S) otherwise: unique, and d = 0
+ *              is first even where other blocks are exact duplicates (a saturated region), so a reference block is always in its own group
+ *              and every site has a denominator.  With n counted the group is the first G = 2^lg, lg = floor(log2(min(n, Gmax))).
+ *   sets       mix = 1: one set of all C planes; mix = 0: every plane its own set.  M planes per set, lm = log2 M.
+ *   transform  per set, [M][G][8][8] of v at the group's blocks through the unnormalised Walsh-Hadamard transform (Sylvester, natural order)
+ *              along all four axes: T.
+ *   step 1     T' = T if |T| > par[lg] else 0; nnz kept coefficients in the set; W = 2^20 / max(nnz, 1)
+ *   step 2     Tb the same transform of the g blocks, E = Tb^2; R = floor(4096 E / (E + par[lg])); T' = (T R + 2048) >> 12 (arithmetic: floor);
+ *              W = 2^44 / max(sum of R^2 over the set, 2^24)
+ *   inverse    I the same transform of T'; sh = 6 + lg + lm - frac; est = clamp((I + (1 << (sh - 1))) >> sh, 0, 32767 << frac)
+ *   aggregate  for every member block at p', plane c of the set and u: num_c(p' + u) += W win[u] est, den(p' + u) += W win[u], one den per set
+ *   output     out_c(q) = (2 num_c + den) / (2 den), floor
+ * Ranges: 1 <= N; 1 <= C <= 16; 8 <= h, w; 0 <= S <= 16; 1 <= step <= 8; Gmax in {1, 2, 4, 8, 16}; mix in {0, 1}, 1 only with C a power of two;
+ * 0 <= frac <= 4; tau < 2^30; par[k] >= 1 in step 2; 1 <= win[u] <= 16; no null pointer but guide; fwd 2-byte, x, guide and out 4-byte, ws 8-byte
+ * aligned.  Anything else is ELD_EINVAL before any device work; then ws_bytes below the size function is ELD_EWS.
+ * Widths: D <= 1023^2 * 16 * 64 < 2^30, so a key has 41 bits.  A set holds L = 64 M G <= 2^14 codes: |T|, |Tb| <= 32767 L < 2^29, as is every
+ * partial sum on the way.  E < 2^58: the ratio is formed as 4096 - ceil(4096 par / (E + par)), 44 bits over 59, never as the 70-bit E << 12.
+ * T R + 2048 < 2^43.  |T'| <= |T|, but I and its partial sums are bounded by sum |T'| only, up to 2^36 for constructed inputs: I is the exact
+ * integer (the kernel sums in 32 bits when sum |T'| < 2^31 and in 64 bits otherwise).  W <= 2^20, win <= 16, est < 2^19: a contribution is
+ * below 2^43, and at most ((2S + 8) / step + 2)^2 * 16 < 2^15 of them reach a site: num < 2^58, den < 2^39, 64-bit accumulators, and
+ * 2 num + den < 2^60.  W >= 2^20 / 2^14 resp. 2^44 / 2^38 = 64 and win >= 1, so den >= 64 at every site. */
+size_t eld_bm3d_vst_workspace_bytes(int N, int C, int h, int w);
+int eld_bm3d_vst_f32(const float* x, int N, int C, int h, int w, float qscale, const uint16_t* fwd, const int32_t* guide, int S, int step, int Gmax,
+                     int mix, uint32_t tau, const uint32_t* par, const uint8_t* win, int frac, int32_t* out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
