@@ -109,6 +109,8 @@ SIGNATURES = {
     'eld_pack_raw_xtrans_u16_shaded': (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _f, _vp]),
     'eld_pair_level_stats_workspace_bytes': (_sz, [_i, _i, _i]),
     'eld_pair_level_stats_u16': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _sz, _vp]),
+    'eld_tile_noise_workspace_bytes': (_sz, [_i, _i, _i]),
+    'eld_tile_noise_sums_u16': (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _vp, _vp, _sz, _vp]),
     'eld_burst_stack_workspace_bytes': (_sz, [_i, _i, _i]),
     'eld_burst_stack_u16': (_i, [_vp, _i, _i, _i, _i, C.POINTER(C.c_int), _i, C.POINTER(C.c_int32), _i, _vp, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'eld_burst_luma_pyramid_elems': (_sz, [_i, _i, _i, _i, _i]),

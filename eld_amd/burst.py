@@ -345,7 +345,16 @@ def burst_gain(stacks, min_sites=64, what='burst'):
     if mu.size < 2 or np.ptp(mu) <= 0:
         raise ValueError('%s: fewer than two usable photon-transfer points (%d): the burst is saturated, too dark, too small or all one level'
                          % (what, mu.size))
-    w = n / (var * var)
+    K, sigma0_sq = weighted_line(n, mu, var, var, what)
+    return {'K': K, 'sigma0_sq': sigma0_sq, 'mu': mu, 'var': var, 'n': n.astype(np.int64)}
+
+
+def weighted_line(n, mu, var, line, what='burst'):
+    """The weighted least-squares line var = K mu + sigma0^2 through float64 points with weights n / line^2 (line: the variance each point
+    is believed to have; the variance of a variance estimate goes as line^2 / n), in a fixed order of operations.  -> (K, sigma0_sq).
+    ValueError when the points share one signal level or the slope is not a positive gain.  Shared by burst_gain (line = var, one pass)
+    and eld_amd.noiselevel.estimate_noise (which iterates on the fitted line)."""
+    w = n / (line * line)
     sw = float(np.sum(w))
     mw, vw = float(np.sum(w * mu) / sw), float(np.sum(w * var) / sw)
     sxx = float(np.sum(w * (mu - mw) ** 2))
@@ -354,7 +363,7 @@ def burst_gain(stacks, min_sites=64, what='burst'):
     K = float(np.sum(w * (mu - mw) * (var - vw)) / sxx)
     if not K * float(np.ptp(mu)) > 1e-9 * abs(vw):                 # a rise below rounding error over the whole range is a flat line
         raise ValueError('%s: the photon-transfer slope is %r, not a positive gain' % (what, K))
-    return {'K': K, 'sigma0_sq': vw - K * mw, 'mu': mu, 'var': var, 'n': n.astype(np.int64)}
+    return K, vw - K * mw
 
 
 # ---- flicker -------------------------------------------------------------------------------------------------------------------------------

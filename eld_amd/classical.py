@@ -18,7 +18,10 @@ distances shared by the planes, a Walsh-Hadamard transform over [planes][group][
 plane has unit noise variance -- hard thresholding, then an empirical Wiener filter guided by the first estimate; the tables and the inverse
 around it are the same.  DESIGN.md sec. 25.
 
-Command line: python -m eld_amd.classical frames.npy... -o DIR --meta sensor.json --K K [--sigma S | --camera TABLE] [--search 7]
+Without a calibration, ClassicalDenoiser.from_frames(frames, cfa, ...) and --K auto take K and the read noise from the frames themselves
+(eld_amd.noiselevel).
+
+Command line: python -m eld_amd.classical frames.npy... -o DIR --meta sensor.json --K K|auto [--sigma S | --camera TABLE] [--search 7]
 [--patch 2] [--strength 0.5] [--method bm3d [--step 3] [--group 16] [--no-mix]] and every sensor option of python -m eld_amd.denoise (which
 keeps its required --ckpt)."""
 import ctypes
@@ -274,6 +277,17 @@ class ClassicalDenoiser:
         self._fwd = {}
         self._others = {}
 
+    @classmethod
+    def from_frames(cls, frames, cfa, raw_pattern=None, black_level=None, white_level=16383, defects=None, sigma=None, camera=None, **kw):
+        """The baseline with K estimated from the frames themselves (eld_amd.noiselevel.estimate_noise: uint16 frames of one ISO, NumPy or
+        CUDA), and the read noise too unless `sigma` or `camera` gives one; **kw as the constructor's.  The estimate is kept as
+        `.estimate`."""
+        from .noiselevel import estimate_noise
+        est = estimate_noise(frames, cfa, raw_pattern, black_level, white_level, defects)
+        den = cls(cfa, est.K, sigma=est.sigma if sigma is None and camera is None else sigma, camera=camera, **kw)
+        den.estimate = est
+        return den
+
     def with_gain(self, K):
         """This baseline at another gain (another ISO): the read noise again from the camera table where it came from one, else kept."""
         K = float(K)
@@ -347,6 +361,11 @@ class ClassicalDenoiser:
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------------------
+def _gain_arg(text):
+    """--K: a float, or the word 'auto' (anything else is the parser's error)."""
+    return 'auto' if text == 'auto' else float(text)
+
+
 def build_parser():
     from . import denoise as D
     p = D.build_parser()
@@ -356,7 +375,9 @@ def build_parser():
         if act.dest == 'ckpt':
             act.required = False
             act.help = 'ignored: the classical baseline loads no checkpoint'
-    p.add_argument('--K', type=float, required=True, help='overall system gain in DN per electron (eld_amd.calibrate, eld_amd.burst)')
+    p.add_argument('--K', type=_gain_arg, required=True, metavar='K|auto',
+                   help="overall system gain in DN per electron (eld_amd.calibrate, eld_amd.burst), or 'auto': estimated from the input frames "
+                        '(eld_amd.noiselevel), and with it the read noise unless --sigma or --camera gives one')
     p.add_argument('--sigma', type=float, help='read noise in DN (default: the g_scale line of --camera at log K)')
     p.add_argument('--camera', metavar='TABLE', help="a calibrated table: a name (camera_params/release/<name>_params.npy or a shipped one) or a .npy path")
     p.add_argument('--search', type=int, default=7, help='search radius (default 7, at most %d; with --method bm3d 12, at most %d)'
@@ -382,13 +403,26 @@ def parse_method_args(parser, argv, method_dest='method', prefix=''):
 def main(argv=None):
     from . import denoise as D
     a = parse_method_args(build_parser(), sys.argv[1:] if argv is None else argv)
-    if a.sigma is None and a.camera is None:
-        raise ValueError('the baseline needs --sigma or --camera')
+    auto = a.K == 'auto'
+    if a.sigma is None and a.camera is None and not auto:
+        raise ValueError('the baseline needs --sigma or --camera (or --K auto, which estimates both)')
     if a.bf16:
         raise ValueError('--bf16 is the network\'s precision: the classical baseline runs in integers')
     inputs, outdir, _, o = D.options_from(a)
-    den = ClassicalDenoiser(o['cfa'], a.K, sigma=a.sigma, camera=a.camera, search=a.search, patch=a.patch, strength=a.strength, method=a.method,
+    K, sigma = a.K, a.sigma
+    if auto:
+        from .burst import load_burst
+        from .noiselevel import estimate_from_options
+        est = estimate_from_options(load_burst(inputs), o)
+        K = est.K
+        if a.sigma is None and a.camera is None:
+            sigma = est.sigma
+        print('estimated from the input frames: K %.5g DN/e-, sigma %.4g DN (%.0f %% of the tiles kept, %d points)'
+              % (est.K, est.sigma, 100 * est.kept_share, len(est.points['bin'])))
+    den = ClassicalDenoiser(o['cfa'], K, sigma=sigma, camera=a.camera, search=a.search, patch=a.patch, strength=a.strength, method=a.method,
                             step=a.step, group=a.group, mix=False if a.no_mix else None)
+    if auto:
+        print('using K %.5g DN/e-, sigma %.4g DN' % (den.K, den.sigma))
     return D.run_frames(den, inputs, outdir, o)
 
 

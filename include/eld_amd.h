@@ -61,7 +61,9 @@ extern "C" {
  * without a new symbol: no existing call, record layout or result changes.  The 64-byte EldNoiseParams keeps its layout; with ELD_COL in the
  * flags reserved[0] is read as the float bits of the column scale (ELD_COL and ELD_DARK, the field's other user, exclude each other), and the
  * inject / dump buffers then hold ELD_NPLANES_COL planes.  Without ELD_COL the field is ignored and the buffers hold ELD_NPLANES planes, as
- * before.  The one difference: bit 2048 in the flags of the sampler entries was ignored and now selects the term. */
+ * before.  The one difference: bit 2048 in the flags of the sampler entries was ignored and now selects the term.
+ * Still 8: eld_tile_noise_sums_u16 and eld_tile_noise_workspace_bytes were added the same way (exact per-tile second- and first-difference
+ * sums of a single frame, for its gain and read noise): two new symbols, no existing call changed. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -635,6 +637,31 @@ int eld_pack_raw_xtrans_u16_shaded(const uint16_t* mosaic, float* packed, int N,
 size_t eld_pair_level_stats_workspace_bytes(int F, int Hm, int Wm);
 int eld_pair_level_stats_u16(const uint16_t* est, const uint16_t* ref, int F, int Hm, int Wm, int Hc, int Wc, int p, const int* group, int G,
                              const int32_t* black, int white, const uint32_t* bitmap, int64_t* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- noise level from a single frame: per-tile difference sums (csrc/noiselevel.hip, eld_amd/noiselevel.py) ---------------
+ * frames [F,Hm,Wm] uint16 codes (any width, odd ones included), F <= 65535, Hm * Wm < 2^31; Hc, Wc, p, group, G, black, white and bitmap as
+ * eld_pair_level_stats_u16 (group and black: HOST arrays of p*p values per cell (y % p, x % p), group -1 = not counted, 1 <= G <= 4).
+ * stride = s, the distance to the same-colour neighbours: 1 <= s <= p and p % s == 0 (Bayer: p = 2, s = 2; the X-Trans greens have period
+ * 3: p = 6, s = 3 with every other cell in group -1; p = 6, s = 6 serves all colours).
+ *   Per site (y, x) with s <= y < Hc - s and s <= x < Wc - s, let v[a][b] = the code at (y + (a - 1) s, x + (b - 1) s), a, b in 0..2.  The
+ *   site is ELIGIBLE iff g = group[cell(y, x)] >= 0, all nine sites have group g, none of the nine is flagged in bitmap and all nine codes
+ *   are > 0 and < white.  Then
+ *       r  = v00 - 2 v01 + v02 - 2 v10 + 4 v11 - 2 v12 + v20 - 2 v21 + v22     (E r^2 = 36 sigma^2 for white noise of variance sigma^2)
+ *       dx = v12 - v10,  dy = v21 - v01                                         (E (dx^2 + dy^2) = 4 sigma^2)
+ *       S9 = the sum over the nine of (v - black[cell of that site])
+ *   Tile (ty, tx) owns the sites with (y - s) / (16 s) == ty and (x - s) / (16 s) == tx; nty = Hc > 2 s ? ceil((Hc - 2 s) / (16 s)) : 0 and
+ *   ntx the same from Wc.  out[F][nty][ntx][G][4] int64, every entry written by the call:  out[f][ty][tx][g] += (1, S9, r^2, dx^2 + dy^2)
+ *   for every eligible site.  |r| <= 8 * 65535 < 2^20, so r^2 < 2^38; dx^2 + dy^2 < 2^33; |S9| < 2^20; a tile holds (16 s)^2 <= 9216 < 2^14
+ *   sites: every sum stays below 2^52 in magnitude.  Integer adds only, so the result is defined bit for bit whatever the launch geometry
+ *   (tests/noiselevel_ref.py restates it in NumPy).
+ * One pass; a tile and its halo of s are read once, 16 bytes at a time when frames is 16-byte aligned (any width), 2-byte loads otherwise.
+ * frames 2-byte aligned, bitmap 4-byte, out 8-byte.  Workspace: eld_tile_noise_workspace_bytes(F, Hm, Wm) bytes (0 in this implementation:
+ * ws may then be NULL); ELD_EWS when ws_bytes is smaller.  ELD_EINVAL before any launch for everything the host can see: p, stride, G, sizes,
+ * Hc > Hm, Wc > Wm, a group outside [-1, G), a black level outside [0, 65535], white outside [1, 65536], null or misaligned pointers.
+ * F == 0 or an empty tile grid (nty * ntx == 0): 0, nothing is read or written. */
+size_t eld_tile_noise_workspace_bytes(int F, int Hm, int Wm);
+int eld_tile_noise_sums_u16(const uint16_t* frames, int F, int Hm, int Wm, int Hc, int Wc, int p, int stride, const int* group, int G,
+                            const int32_t* black, int white, const uint32_t* bitmap, int64_t* out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- a burst of a static scene: robust mean and photon-transfer sums (csrc/burst.hip, eld_amd/burst.py) --------------------
  * frames [N,Hm,Wm] uint16 codes of one scene shot N times from a tripod, 2 <= N <= 256, Hm * Wm < 2^31, any width; p, group, G, black, white
