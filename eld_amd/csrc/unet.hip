@@ -27,6 +27,8 @@ enum {
     L_E0A = 0, L_E0B, L_E1A, L_E1B, L_E2A, L_E2B, L_E3A, L_E3B, L_E4A, L_E4B,
     L_UP3, L_D3A, L_D3B, L_UP2, L_D2A, L_D2B, L_UP1, L_D1A, L_D1B, L_UP0, L_D0A, L_D0B, L_HEAD, NLAYERS
 };
+// resolution level of layer i's OUTPUT (a transposed conv reads level + 1)
+inline int layer_level(int i) { return i <= L_E4B ? i / 2 : (i < L_HEAD ? 3 - (i - L_UP3) / 3 : 0); }
 
 size_t build_layers(int in_ch, int out_ch, LayerDef* L) {
     int k = 0;
@@ -100,6 +102,13 @@ WgradGeom wgrad_geom(int mode, int CA, int CB, int N, int H, int W, int algo) {
     return g;
 }
 
+// partials of one weight gradient, whichever scheme the call turns out to run (0, 1: fp32; 3: bf16, which re-blocks 3x3 layers only)
+size_t wgrad_floats_max(int mode, int CA, int CB, int N, int H, int W) {
+    size_t f = 0;
+    for (int algo : {0, 1, 3}) { const size_t q = wgrad_geom(mode, CA, CB, N, H, W, algo).floats; f = q > f ? q : f; }
+    return f;
+}
+
 // ------------------------------------------------------------------------------------------------
 // layer helpers on packed weights
 // ------------------------------------------------------------------------------------------------
@@ -117,36 +126,60 @@ struct AlgoScope { int prev; explicit AlgoScope(int a) : prev(g_algo) { g_algo =
 inline void take_amax(ConvArgs& a) { a.algo = g_algo; a.amax_in0 = g_am.in0; a.amax_in1 = g_am.in1; a.amax_w = g_am.w; a.amax_out0 = g_am.out0; a.amax_out1 = g_am.out1; g_am = Amax(); }
 inline void take_amax(WgradArgs& a) { a.algo = g_algo; a.amax_g = g_am.in0; a.amax_x0 = g_am.w; a.amax_x1 = g_am.in1; g_am = Amax(); }      // wgrad: in0 = G, w = X0, in1 = X1
 enum { S_W = 0, S_X = 23, S_EA = 24, S_EB = 29, S_UP = 34, S_DA = 38, S_DB = 42, S_GA = 46, S_GB = 47, S_SKIP = 48, S_COUNT = 64 };
-int conv_fwd(const float* in0, int C0, const float* in1, int C1, const float* wp, const float* bias, float* out, int N, int H, int W,
-             int Cout, int lrelu, hipStream_t st, float* pool_out = nullptr, unsigned* codes_out = nullptr, unsigned* pool_codes_out = nullptr) {
+// The element type T of activations and packed weights (float / bf16_t) decides ConvArgs::dtype and the weight-gradient scheme wgrad_geom sizes for;
+// the bf16 launchers never look at algo, kpart or the operand bounds (launch_conv / launch_wgrad branch on dtype first).
+template <typename T> struct Elem;
+template <> struct Elem<float> {
+    static constexpr int dtype = DT_F32, bf16 = 0;
+    static constexpr int x_pad = 16;                     // channels of the converted NHWC input of conv1_1 (more than 4 planes): one K granule
+    static int wgrad_scheme() { return g_algo; }
+    static int gather_scheme() { return g_algo == 1 ? 1 : 0; }
+    static bool conv_pools(int, int, int, int) { return g_algo == 1; }      // the three-piece 3x3 kernels also write the 2x2 max-pool of their output
+    static bool reads_codes() { return g_algo == 1; }                      // only the three-piece backward-data epilogues and their pool backward read codes
+};
+template <> struct Elem<bf16_t> {
+    static constexpr int dtype = DT_BF16, bf16 = 1;
+    static constexpr int x_pad = 32;
+    static int wgrad_scheme() { return 3; }
+    static int gather_scheme() { return 0; }
+    static bool conv_pools(int C, int N, int H, int W) { return bfd_slab_bn(C, C, N, H, W) != 0; }      // C -> C layers on the DMA kernel (conv_bfd.hip) do
+    static bool reads_codes() { return true; }
+};
+
+template <typename T>
+int conv_fwd(const T* in0, int C0, const T* in1, int C1, const T* wp, const float* bias, T* out, int N, int H, int W,
+             int Cout, int lrelu, hipStream_t st, T* pool_out = nullptr, unsigned* codes_out = nullptr, unsigned* pool_codes_out = nullptr) {
     ConvArgs a = {};
     a.pool_out = pool_out;
     a.codes_out = codes_out;
     a.pool_codes_out = pool_codes_out;
     a.in0 = in0; a.in1 = in1; a.C0 = C0; a.C1 = C1; a.wp = wp; a.N = N; a.H = H; a.W = W; a.Nout = Cout;
-    a.epi = EPI_FWD; a.bias = bias; a.lrelu = lrelu; a.out0 = out;
+    a.epi = EPI_FWD; a.bias = bias; a.lrelu = lrelu; a.out0 = out; a.dtype = Elem<T>::dtype;
     a.kpart = g_kp.p; a.kpart_floats = g_kp.floats;
     take_amax(a);
     return launch_conv(a, CONV_3X3, st);
 }
 
 // g: [N,H,W,Cout] -> din (Cin channels, split over out0/out1), wb packed [9][Cin][Cout]
-int conv_bwd_data(const float* g, const float* wb, float* out0, float* out1, int split, const float* act0, const float* act1, int N, int H,
+template <typename T>
+int conv_bwd_data(const T* g, const T* wb, T* out0, T* out1, int split, const T* act0, const T* act1, int N, int H,
                   int W, int Cin, int Cout, hipStream_t st, const unsigned* codes0 = nullptr) {
     ConvArgs a = {};
     a.codes0 = codes0;
     a.in0 = g; a.C0 = Cout; a.wp = wb; a.N = N; a.H = H; a.W = W; a.Nout = Cin;
-    a.epi = EPI_GRAD; a.out0 = out0; a.out1 = out1; a.split = split; a.act0 = act0; a.act1 = act1;
+    a.epi = EPI_GRAD; a.out0 = out0; a.out1 = out1; a.split = split; a.act0 = act0; a.act1 = act1; a.dtype = Elem<T>::dtype;
     a.kpart = g_kp.p; a.kpart_floats = g_kp.floats;
     take_amax(a);
     return launch_conv(a, CONV_3X3, st);
 }
 
-int conv_wgrad(const float* g, int Cout, const float* x0, int C0, const float* x1, int C1, int Cin_real, float* dw, float* db, float* part,
+// Cin_real: the weight tensor's input channels (less than C0 + C1 where x0 is zero padded beyond them: conv1_1 with more than 4 planes)
+template <typename T>
+int conv_wgrad(const T* g, int Cout, const T* x0, int C0, const T* x1, int C1, int Cin_real, float* dw, float* db, float* part,
                int N, int H, int W, hipStream_t st) {
-    const WgradGeom q = wgrad_geom(CONV_3X3, Cout, C0 + C1, N, H, W, (C0 % 32 || C1 % 32) ? 0 : g_algo);
+    const WgradGeom q = wgrad_geom(CONV_3X3, Cout, C0 + C1, N, H, W, (C0 % 32 || C1 % 32) ? 0 : Elem<T>::wgrad_scheme());
     WgradArgs a = {};
-    a.g = g; a.CA = Cout; a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.N = N; a.H = H; a.W = W;
+    a.g = g; a.CA = Cout; a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.N = N; a.H = H; a.W = W; a.dtype = Elem<T>::dtype;
     a.part = part; a.bpart = db ? part + (size_t)q.psplit * q.T * q.CA * q.CBp : nullptr; a.CBp = q.CBp; a.psplit = q.psplit;
     take_amax(a);
     a.wgrad8 = q.w8;
@@ -156,31 +189,35 @@ int conv_wgrad(const float* g, int Cout, const float* x0, int C0, const float* x
 }
 
 // in [N,H,W,Cin] -> out [N,2H,2W,Cout]; wf packed [4*Cout][Cin]
-int convt_fwd(const float* in, const float* wf, const float* bias, float* out, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
+template <typename T>
+int convt_fwd(const T* in, const T* wf, const float* bias, T* out, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
     ConvArgs a = {};
     a.in0 = in; a.C0 = Cin; a.wp = wf; a.N = N; a.H = H; a.W = W; a.Nout = 4 * Cout;
-    a.epi = EPI_CONVT_FWD; a.bias = bias; a.out0 = out; a.Cout_t = Cout;
+    a.epi = EPI_CONVT_FWD; a.bias = bias; a.out0 = out; a.Cout_t = Cout; a.dtype = Elem<T>::dtype;
     take_amax(a);
     return launch_conv(a, CONV_1X1, st);
 }
 
 // dout [N,2H,2W,Cout] -> din [N,H,W,Cin] (times slope(act) if act); wb packed [4][Cin][Cout]
-int convt_bwd_data(const float* dout, const float* wb, const float* act, float* din, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
+template <typename T>
+int convt_bwd_data(const T* dout, const T* wb, const T* act, T* din, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
     ConvArgs a = {};
     a.in0 = dout; a.C0 = Cout; a.wp = wb; a.N = N; a.H = H; a.W = W; a.Nout = Cin;
-    a.epi = EPI_GRAD; a.out0 = din; a.split = Cin; a.act0 = act;
+    a.epi = EPI_GRAD; a.out0 = din; a.split = Cin; a.act0 = act; a.dtype = Elem<T>::dtype;
     take_amax(a);
     return launch_conv(a, CONV_GATHER2X2, st);
 }
 
 // dw[ci][co][tap] = sum in[p][ci] * dout[gather(p,tap)][co];  db[co] = column sums of dout
-int convt_wgrad(const float* in, const float* dout, float* dw, float* db, float* part, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
-    const WgradGeom q = wgrad_geom(CONV_GATHER2X2, Cin, Cout, N, H, W, g_algo == 1 ? 1 : 0);
+template <typename T>
+int convt_wgrad(const T* in, const T* dout, float* dw, float* db, float* part, int N, int H, int W, int Cin, int Cout, hipStream_t st) {
+    const WgradGeom q = wgrad_geom(CONV_GATHER2X2, Cin, Cout, N, H, W, Elem<T>::gather_scheme());
     WgradArgs a = {};
-    a.g = in; a.CA = Cin; a.x0 = dout; a.C0 = Cout; a.N = N; a.H = H; a.W = W;
+    a.g = in; a.CA = Cin; a.x0 = dout; a.C0 = Cout; a.N = N; a.H = H; a.W = W; a.dtype = Elem<T>::dtype;
     a.part = part; a.bpart = nullptr; a.CBp = q.CBp; a.psplit = q.psplit; a.wgrad8 = q.w8;
     // bias gradient = column sums of dout: accumulated by the weight-gradient kernel from its staging registers (every dout pixel
-    // passes through exactly once per block column); the partials take the plan's bias slot (psplit * CA floats >= psplit * CBp)
+    // passes through exactly once per block column); the partials take the plan's bias slot (psplit * CA floats >= psplit * CBp).
+    // Every transposed conv of the network qualifies (CBp = C <= CA = 2C, C % 32 == 0); other shapes reach this through the single-layer entry points
     const bool fused_bias = db != nullptr && q.CBp <= q.CA && Cout == q.CBp;
     a.xbpart = fused_bias ? part + (size_t)q.psplit * q.T * q.CA * q.CBp : nullptr;
     take_amax(a);
@@ -207,7 +244,7 @@ struct Plan {
     size_t head_part; // partials of the fused training head (eld_unet_forward_loss_ex -> the backward)
     // slope codes (conv.h ConvArgs::codes_out) of the activations the 32- / 64-channel backward-data epilogues multiply by: ea[0], ea[1], da[0], da[1]
     // (2 bits per element); written by the fp32 three-piece forward where `codes` is set (see make_plan) and, for ea[0] / da[0], by the bf16 forward
-    // (unet_forward_bf16); read by the backward for the regions the last forward reports (FusedFwd::codes)
+    // (fwd_code_mask); read by the backward for the regions the last forward reports (FusedFwd::codes)
     size_t cd_ea[2], cd_da[2];
     // round 6: slope codes of eb[0], eb[1] and argmax codes of pool[0], pool[1] (ConvArgs::pool_codes_out): what maxpool_bwd_codes_kernel reads instead of eb
     size_t cd_eb[2], pc[2];
@@ -254,28 +291,17 @@ int make_plan(Plan& P, int N, int H, int W, int in_ch, int out_ch) {
     pmax = pmax > colsum_ws_floats(256) ? pmax : colsum_ws_floats(256);
     for (int i = 0; i < NLAYERS; ++i) {
         const LayerDef& d = P.L[i];
-        int lev;
-        if (i <= L_E4B) lev = i / 2; else if (i < L_HEAD) lev = 3 - (i - L_UP3) / 3; else lev = 0;
+        const int lev = layer_level(i);
         size_t f = 0;
-        if (d.kind == 0) {
-            f = wgrad_geom(CONV_3X3, d.cout, i == L_E0A ? 16 : d.cin, N, P.Hl[lev], P.Wl[lev], 0).floats;
-            const size_t f1 = wgrad_geom(CONV_3X3, d.cout, i == L_E0A ? 16 : d.cin, N, P.Hl[lev], P.Wl[lev], 1).floats;
-            f = f1 > f ? f1 : f;
-            const size_t f3 = wgrad_geom(CONV_3X3, d.cout, i == L_E0A ? 16 : d.cin, N, P.Hl[lev], P.Wl[lev], 3).floats;
-            f = f3 > f ? f3 : f;
-        } else if (d.kind == 1) {
-            f = wgrad_geom(CONV_GATHER2X2, d.cin, d.cout, N, P.Hl[lev + 1], P.Wl[lev + 1], 0).floats;
-            const size_t f1 = wgrad_geom(CONV_GATHER2X2, d.cin, d.cout, N, P.Hl[lev + 1], P.Wl[lev + 1], 1).floats;
-            f = f1 > f ? f1 : f;
-        }
+        if (d.kind == 0) f = wgrad_floats_max(CONV_3X3, d.cout, i == L_E0A ? 16 : d.cin, N, P.Hl[lev], P.Wl[lev]);
+        else if (d.kind == 1) f = wgrad_floats_max(CONV_GATHER2X2, d.cin, d.cout, N, P.Hl[lev + 1], P.Wl[lev + 1]);
         pmax = f > pmax ? f : pmax;
     }
     // split-K partial sums of small problems share this region: up to 16 parts of the largest 3x3 output that can take the split
     for (int i = 0; i < NLAYERS; ++i) {
         const LayerDef& d = P.L[i];
         if (d.kind != 0) continue;
-        int lev;
-        if (i <= L_E4B) lev = i / 2; else lev = 3 - (i - L_UP3) / 3;
+        const int lev = layer_level(i);
         const long long px8 = (long long)((P.Wl[lev] + 31) / 32) * ((P.Hl[lev] + 7) / 8) * N;
         for (int dir = 0; dir < 2; ++dir) {
             const int nout = dir ? d.cin : d.cout, k = dir ? d.cout : d.cin;
@@ -337,8 +363,7 @@ int pack_weights(const Plan& P, const float* params, float* ws, int dir, hipStre
         J.bf16 = bf16 ? 1 : 0;
         J.amax_slot = S_W + i;
         // three-piece scheme: 3x3 layers with GEMM N % 64 == 0 get pre-split slabs (N = Cout forward, Cin backward-data)
-        int lev;                                   // resolution level the layer runs at (its tile domain decides the slab's channel-block width)
-        if (i <= L_E4B) lev = i / 2; else if (i < L_HEAD) lev = 3 - (i - L_UP3) / 3; else lev = 0;
+        const int lev = layer_level(i);            // (the layer's tile domain decides the slab's channel-block width)
         J.x3bn = (!bf16 && g_algo == 1 && d.kind == 0) ? x3_slab_bn(for_backward ? d.cin : d.cout, P.N, P.Hl[lev], P.Wl[lev]) : 0;
         // bf16: 3x3 layers the DMA kernel takes get its slab layout (GEMM N = Cout forward / Cin backward-data, K the other one)
         J.bfdbn = (bf16 && d.kind == 0) ? (for_backward ? bfd_slab_bn(d.cin, d.cout, P.N, P.Hl[lev], P.Wl[lev]) : bfd_slab_bn(d.cout, J.Cinp, P.N, P.Hl[lev], P.Wl[lev])) : 0;
@@ -386,135 +411,118 @@ enum { CODES_EA0 = 1, CODES_EA1 = 2, CODES_DA0 = 4, CODES_DA1 = 8, CODES_EB0 = 1
 static_assert(CODES_EA0 == ELD_CODES_EA0 && CODES_EA1 == ELD_CODES_EA1 && CODES_DA0 == ELD_CODES_DA0 && CODES_DA1 == ELD_CODES_DA1 && CODES_EB0 == ELD_CODES_EB0 &&
               CODES_EB1 == ELD_CODES_EB1 && CODES_INFER == ELD_CODES_INFER, "eld_debug_unet_codes publishes these bits (include/eld_amd.h)");
 
-int unet_forward(const Plan& P, const float* x, const float* prm, float* out, float* ws, hipStream_t st, const HeadLoss* hl = nullptr, unsigned* have_out = nullptr,
-                 bool infer = false) {
-    const int N = P.N;
-    KPartScope kp(ws + P.part, P.part_floats);
-    const bool h2 = g_algo == 2;                                 // operand bounds ride along in the workspace
-    float* am = ws + P.amax;
-    auto AM = [&](int in0, int in1, int w, int out0) {
-        if (!h2) return;
-        g_am.in0 = am + in0; g_am.in1 = in1 >= 0 ? am + in1 : nullptr; g_am.w = am + w; g_am.out0 = am + out0;
-    };
-    if (h2 && hipMemsetAsync(am, 0, S_COUNT * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
-    RC(pack_weights(P, prm, ws, hl ? PACK_BOTH : PACK_FWD, st, false, h2 ? am : nullptr));
-    const bool first_direct = P.in_ch <= 4;        // conv1_1 straight from the NCHW planes (conv_first.hip)
-    const bool use_codes = !infer && P.codes && g_algo == 1 && !(debug_kernel_mask(-1) & 128);   // slope codes for the backward-data epilogues of levels 0 / 1 (Plan::codes)
-    auto CD = [&](size_t off) -> unsigned* { return use_codes ? reinterpret_cast<unsigned*>(ws + off) : nullptr; };
-    const bool use_pcodes = use_codes && !(debug_kernel_mask(-1) & 256);      // argmax codes of the two full-size pools (bit 8 of the mask: A/B and bit-identity switch)
-    if (have_out) *have_out = !use_codes ? 0u : ((!first_direct || conv_first_writes_codes(P.in_ch)) ? CODES_EA0 : 0u) | CODES_EA1 | CODES_DA0 | CODES_DA1 | (use_pcodes ? (x3w_enabled() ? CODES_EB0 : 0u) | CODES_EB1 : 0u);
-    if (first_direct && (hl || infer)) {
-        // fused training forward: the backward reads the caller's x (include/eld_amd.h: it must stay valid and unchanged until that call);
-        // inference (eld_unet_infer_ex): no backward follows
-    } else if (first_direct) {
-        // keep the input for the backward's weight gradient (the backward entry point does not receive x)
-        hipError_t e = hipMemcpyAsync(ws + P.x16, x, (size_t)N * P.in_ch * P.H * P.W * sizeof(float), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return (int)e;
-    } else {
-        RC(launch_nchw_to_nhwc16(x, ws + P.x16, N, P.in_ch, P.H, P.W, st));
+static_assert(CODES_EA1 == CODES_EA0 << 1 && CODES_DA1 == CODES_DA0 << 1 && CODES_EB1 == CODES_EB0 << 1, "code_regions shifts the level-0 bit by the level");
+
+// Where the regions named by a CODES_* mask lie (null: not in the mask).  The forward passes them to the launches that fill them, the backward to
+// the ones that read them instead of the saved activation; the walkers themselves never look at the mask.
+struct CodeRegions { unsigned *ea[NLEV] = {}, *da[NLEV] = {}, *eb[NLEV] = {}, *pc[NLEV] = {}; };
+CodeRegions code_regions(const Plan& P, float* ws, unsigned mask) {
+    CodeRegions r;
+    auto at = [&](size_t off, unsigned bit) { return (mask & bit) ? reinterpret_cast<unsigned*>(ws + off) : nullptr; };
+    for (int l = 0; l < 2; ++l) {
+        r.ea[l] = at(P.cd_ea[l], CODES_EA0 << l);
+        r.da[l] = at(P.cd_da[l], CODES_DA0 << l);
+        r.eb[l] = at(P.cd_eb[l], CODES_EB0 << l);
+        r.pc[l] = at(P.pc[l], CODES_EB0 << l);
     }
-    for (int l = 0; l < NLEV; ++l) {
-        const LayerDef& A = P.L[2 * l]; const LayerDef& B = P.L[2 * l + 1];
-        const float* src = l == 0 ? ws + P.x16 : ws + P.pool[l - 1];
-        const int cin = l == 0 ? 16 : chan(l - 1);
-        if (l == 0 && first_direct) {
-            RC(launch_conv_first_fwd(x, prm + A.w_off, prm + A.b_off, ws + P.ea[0], N, P.in_ch, P.H, P.W, 1, st, CD(P.cd_ea[0])));
-            if (h2) RC(launch_absmax(ws + P.ea[0], (size_t)N * P.H * P.W * chan(0), am + S_EA, st));
-        } else {
-            if (h2 && l == 0) RC(launch_absmax(ws + P.x16, (size_t)N * P.H * P.W * 16, am + S_X, st));
-            AM(l == 0 ? S_X : S_EB + l - 1, -1, S_W + 2 * l, S_EA + l);          // pooled input is bounded by its source's bound
-            RC(conv_fwd(src, cin, nullptr, 0, ws + P.wp_fwd[2 * l], prm + A.b_off, ws + P.ea[l], N, P.Hl[l], P.Wl[l], chan(l), 1, st, nullptr,
-                        l < 2 ? CD(P.cd_ea[l]) : nullptr));
-        }
-        AM(S_EA + l, -1, S_W + 2 * l + 1, S_EB + l);
-        // three-piece scheme: the conv's epilogue also writes the pooled tensor (no second pass over eb[l])
-        const bool fuse_pool = g_algo == 1 && l < NLEV - 1;
-        const bool pcodes = fuse_pool && l < 2 && use_pcodes && (l == 1 || x3w_enabled());      // level 0: conv_x3w_kernel writes them, conv_x3_kernel<32, 4> does not       // levels 0 / 1: the pool's backward then reads codes instead of eb[l]
-        RC(conv_fwd(ws + P.ea[l], chan(l), nullptr, 0, ws + P.wp_fwd[2 * l + 1], prm + B.b_off, ws + P.eb[l], N, P.Hl[l], P.Wl[l], chan(l), 1, st,
-                    fuse_pool ? ws + P.pool[l] : nullptr, pcodes ? CD(P.cd_eb[l]) : nullptr, pcodes ? CD(P.pc[l]) : nullptr));
-        if (l < NLEV - 1 && !fuse_pool) RC(launch_maxpool_fwd(ws + P.eb[l], ws + P.pool[l], N, P.Hl[l + 1], P.Wl[l + 1], chan(l), st));
-    }
-    for (int l = 3; l >= 0; --l) {
-        const int iu = L_UP3 + 3 * (3 - l);
-        const float* src = l == 3 ? ws + P.eb[4] : ws + P.db[l + 1];
-        AM(l == 3 ? S_EB + 4 : S_DB + l + 1, -1, S_W + iu, S_UP + l);
-        RC(convt_fwd(src, ws + P.wp_fwd[iu], prm + P.L[iu].b_off, ws + P.up[l], N, P.Hl[l + 1], P.Wl[l + 1], chan(l + 1), chan(l), st));
-        AM(S_UP + l, S_EB + l, S_W + iu + 1, S_DA + l);
-        RC(conv_fwd(ws + P.up[l], chan(l), ws + P.eb[l], chan(l), ws + P.wp_fwd[iu + 1], prm + P.L[iu + 1].b_off, ws + P.da[l], N, P.Hl[l], P.Wl[l], chan(l), 1, st, nullptr,
-                    l < 2 ? CD(P.cd_da[l]) : nullptr));
-        AM(S_DA + l, -1, S_W + iu + 2, S_DB + l);
-        RC(conv_fwd(ws + P.da[l], chan(l), nullptr, 0, ws + P.wp_fwd[iu + 2], prm + P.L[iu + 2].b_off, ws + P.db[l], N, P.Hl[l], P.Wl[l], chan(l), 1, st));
-    }
-    const LayerDef& Hd = P.L[L_HEAD];
-    if (hl)      // training step: output, loss, the head's backward and the gradient of conv9_2's output (-> gA) in one pass
-        return launch_head_train(ws + P.db[0], 0, prm + Hd.w_off, prm + Hd.b_off, hl->target, out, ws + P.gA, ws + P.head_part, hl->loss, N, P.H, P.W, P.out_ch,
-                                 hl->mse, hl->grad_scale, st);
-    RC(launch_head_fwd(ws + P.db[0], prm + Hd.w_off, prm + Hd.b_off, out, N, P.H, P.W, P.out_ch, st));
-    return 0;
+    return r;
 }
 
-// bf16 forward (inference): bf16 activations and packed weights, fp32 accumulation / bias; the first layer reads the
-// fp32 NCHW planes and the head writes fp32 NCHW.  Buffers of the fp32 plan are reused (half filled).
-int conv_fwd_bf16(const bf16_t* in0, int C0, const bf16_t* in1, int C1, const bf16_t* wp, const float* bias, bf16_t* out, int N, int H, int W,
-                  int Cout, int lrelu, hipStream_t st, bf16_t* pool_out = nullptr, unsigned* codes_out = nullptr) {
-    ConvArgs a = {};
-    a.pool_out = pool_out;
-    a.codes_out = codes_out;
-    a.in0 = in0; a.in1 = in1; a.C0 = C0; a.C1 = C1; a.wp = wp; a.N = N; a.H = H; a.W = W; a.Nout = Cout;
-    a.epi = EPI_FWD; a.bias = bias; a.lrelu = lrelu; a.out0 = out; a.dtype = DT_BF16;
-    return launch_conv(a, CONV_3X3, st);
+// Which regions a forward fills: a per-call choice of each precision's kernels
+template <typename T> unsigned fwd_code_mask(const Plan& P, bool infer);
+template <> unsigned fwd_code_mask<float>(const Plan& P, bool infer) {
+    // slope codes for the backward-data epilogues of levels 0 / 1 (Plan::codes), written by the three-piece kernels
+    if (infer || !P.codes || g_algo != 1 || (debug_kernel_mask(-1) & 128)) return 0;
+    unsigned m = CODES_EA1 | CODES_DA0 | CODES_DA1;
+    if (P.in_ch > 4 || conv_first_writes_codes(P.in_ch)) m |= CODES_EA0;
+    // argmax codes of the two full-size pools (bit 8 of the mask: A/B and bit-identity switch): the pool's backward then reads codes instead of eb[l].
+    // Level 0: conv_x3w_kernel writes them, conv_x3_kernel<32, 4> does not
+    if (!(debug_kernel_mask(-1) & 256)) m |= CODES_EB1 | (x3w_enabled() ? CODES_EB0 : 0u);
+    return m;
 }
-
-int unet_forward_bf16(const Plan& P, const float* x, const float* prm, float* out, float* ws, hipStream_t st, const HeadLoss* hl = nullptr, unsigned* have_out = nullptr,
-                      bool infer = false) {
-    const int N = P.N;
-    const bool first_direct = P.in_ch <= 4;       // conv1_1 straight from the NCHW planes (conv_first.hip); more planes: NHWC32 bf16 in ws + P.x16
-    RC(pack_weights(P, prm, ws, hl ? PACK_BOTH : PACK_FWD, st, true));
-    if (!first_direct) {   // (64 B per pixel: the size of the fp32 plan's NHWC16 region; the backward's weight gradient reads it there)
-        RC(launch_nchw_to_nhwc32_bf16(x, reinterpret_cast<bf16_t*>(ws + P.x16), N, P.in_ch, P.H, P.W, st));
-    } else if (!hl && !infer) {   // keep the fp32 input for the first layer's weight gradient (the fused training forward leaves it with the caller: see FusedFwd)
-        hipError_t e = hipMemcpyAsync(ws + P.x16, x, (size_t)N * P.in_ch * P.H * P.W * sizeof(float), hipMemcpyDeviceToDevice, st);
-        if (e != hipSuccess) return (int)e;
-    }
-    auto B = [&](size_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
+template <> unsigned fwd_code_mask<bf16_t>(const Plan& P, bool infer) {
     // Slope codes of the two full-resolution activations whose backward-data epilogues run on conv_bfs_kernel (conv9_2's and conv1_2's: HBM-bound
     // launches that would otherwise re-read the saved 32-channel tensor): written by conv1_1's and conv9_1's epilogues where those kernels are the
     // ones that run (conv_first's MFMA kernel; conv_bfs for the 64 -> 32 layer) -- 8 bytes per pixel instead of 64 in the backward
-    const bool bfs0 = !infer && bfs_takes(32, 32, N, P.H, P.W) && !(debug_kernel_mask(-1) & 128);
-    const bool c_ea0 = bfs0 && first_direct && conv_first_writes_codes(P.in_ch), c_da0 = bfs0 && bfs_takes(32, 64, N, P.H, P.W);
-    if (have_out) *have_out = (c_ea0 ? CODES_EA0 : 0u) | (c_da0 ? CODES_DA0 : 0u);
+    if (infer || !bfs_takes(32, 32, P.N, P.H, P.W) || (debug_kernel_mask(-1) & 128)) return 0;
+    return (P.in_ch <= 4 && conv_first_writes_codes(P.in_ch) ? CODES_EA0 : 0u) | (bfs_takes(32, 64, P.N, P.H, P.W) ? CODES_DA0 : 0u);
+}
+
+// Operand bounds of the two-piece fp16 scheme along the network (Amax above): one device float per tensor (S_*) in the workspace.
+// am == nullptr unless the pass is fp32 with g_algo == 2: every member then does nothing.
+struct Bounds {
+    float* am;
+    hipStream_t st;
+    void conv(int in0, int in1, int w, int out0) const {
+        if (am) { g_am.in0 = am + in0; g_am.in1 = in1 >= 0 ? am + in1 : nullptr; g_am.w = am + w; g_am.out0 = am + out0; }
+    }
+    void wgrad(int g, int x0, int x1) const { if (am) { g_am.in0 = am + g; g_am.w = am + x0; g_am.in1 = x1 >= 0 ? am + x1 : nullptr; } }
+    void bwd_data(int g, int w, int o0, int o1) const { if (am) { g_am.in0 = am + g; g_am.w = am + w; g_am.out0 = am + o0; g_am.out1 = o1 >= 0 ? am + o1 : nullptr; } }
+    int clear(int slot, int n = 1) const {                           // zero slots before their tensors are (re)written
+        return !am || hipMemsetAsync(am + slot, 0, n * sizeof(float), st) == hipSuccess ? 0 : (int)hipGetLastError();
+    }
+    int measure(const float* t, size_t n, int slot) const { return am ? launch_absmax(t, n, am + slot, st) : 0; }
+    int measure(const bf16_t*, size_t, int) const { return 0; }
+};
+template <typename T> Bounds bounds(const Plan& P, float* ws, hipStream_t st) { return {!Elem<T>::bf16 && g_algo == 2 ? ws + P.amax : nullptr, st}; }
+
+// T = bf16_t: bf16 activations and packed weights, fp32 accumulation / bias; the first layer reads the fp32 NCHW planes and the head writes fp32
+// NCHW.  The plan's buffers are then half filled.
+template <typename T>
+int unet_forward(const Plan& P, const float* x, const float* prm, float* out, float* ws, hipStream_t st, const HeadLoss* hl = nullptr, unsigned* have_out = nullptr,
+                 bool infer = false) {
+    using E = Elem<T>;
+    const int N = P.N;
+    KPartScope kp(ws + P.part, P.part_floats);
+    const Bounds bd = bounds<T>(P, ws, st);
+    auto B = [&](size_t off) { return reinterpret_cast<T*>(ws + off); };
+    RC(bd.clear(0, S_COUNT));
+    RC(pack_weights(P, prm, ws, hl ? PACK_BOTH : PACK_FWD, st, E::bf16, bd.am));
+    const bool first_direct = P.in_ch <= 4;        // conv1_1 straight from the NCHW planes (conv_first.hip); more planes: zero-padded NHWC in ws + P.x16
+    const unsigned have = fwd_code_mask<T>(P, infer);
+    const CodeRegions cd = code_regions(P, ws, have);
+    if (have_out) *have_out = have;
+    if (!first_direct) {      // (64 B per pixel in either precision; the backward's weight gradient reads it there)
+        RC(launch_nchw_to_nhwc_pad(x, B(P.x16), N, P.in_ch, P.H, P.W, st));
+    } else if (!hl && !infer) {
+        // keep the input for the backward's weight gradient (the backward entry point does not receive x).  The fused training forward leaves it
+        // with the caller (include/eld_amd.h: it must stay valid and unchanged until that call); inference: no backward follows
+        hipError_t e = hipMemcpyAsync(ws + P.x16, x, (size_t)N * P.in_ch * P.H * P.W * sizeof(float), hipMemcpyDeviceToDevice, st);
+        if (e != hipSuccess) return (int)e;
+    }
     for (int l = 0; l < NLEV; ++l) {
         const LayerDef& A = P.L[2 * l]; const LayerDef& Bd = P.L[2 * l + 1];
-        if (l == 0 && first_direct)
-            RC(launch_conv_first_fwd_bf16(x, prm + A.w_off, prm + A.b_off, B(P.ea[0]), N, P.in_ch, P.H, P.W, 1, st,
-                                          c_ea0 ? reinterpret_cast<unsigned*>(ws + P.cd_ea[0]) : nullptr));
-        else if (l == 0)
-            RC(conv_fwd_bf16(B(P.x16), 32, nullptr, 0, B(P.wp_fwd[0]), prm + A.b_off, B(P.ea[0]), N, P.H, P.W, chan(0), 1, st));
-        else
-            RC(conv_fwd_bf16(B(P.pool[l - 1]), chan(l - 1), nullptr, 0, B(P.wp_fwd[2 * l]), prm + A.b_off, B(P.ea[l]), N, P.Hl[l], P.Wl[l], chan(l), 1, st));
-        // layers on the DMA kernel (conv_bfd.hip) write the pooled tensor from their epilogue
-        const bool fuse_pool = l < NLEV - 1 && bfd_slab_bn(chan(l), chan(l), N, P.Hl[l], P.Wl[l]) != 0;
-        RC(conv_fwd_bf16(B(P.ea[l]), chan(l), nullptr, 0, B(P.wp_fwd[2 * l + 1]), prm + Bd.b_off, B(P.eb[l]), N, P.Hl[l], P.Wl[l], chan(l), 1, st,
-                         fuse_pool ? B(P.pool[l]) : nullptr));
-        if (l < NLEV - 1 && !fuse_pool) RC(launch_maxpool_fwd_bf16(B(P.eb[l]), B(P.pool[l]), N, P.Hl[l + 1], P.Wl[l + 1], chan(l), st));
+        if (l == 0 && first_direct) {
+            RC(launch_conv_first_fwd(x, prm + A.w_off, prm + A.b_off, B(P.ea[0]), N, P.in_ch, P.H, P.W, 1, st, cd.ea[0]));
+            RC(bd.measure(B(P.ea[0]), (size_t)N * P.H * P.W * chan(0), S_EA));
+        } else {
+            if (l == 0) RC(bd.measure(B(P.x16), (size_t)N * P.H * P.W * E::x_pad, S_X));
+            bd.conv(l == 0 ? S_X : S_EB + l - 1, -1, S_W + 2 * l, S_EA + l);          // pooled input is bounded by its source's bound
+            RC(conv_fwd<T>(l == 0 ? B(P.x16) : B(P.pool[l - 1]), l == 0 ? E::x_pad : chan(l - 1), nullptr, 0, B(P.wp_fwd[2 * l]), prm + A.b_off, B(P.ea[l]),
+                           N, P.Hl[l], P.Wl[l], chan(l), 1, st, nullptr, cd.ea[l]));
+        }
+        bd.conv(S_EA + l, -1, S_W + 2 * l + 1, S_EB + l);
+        const bool fuse_pool = l < NLEV - 1 && E::conv_pools(chan(l), N, P.Hl[l], P.Wl[l]);      // no second pass over eb[l]
+        RC(conv_fwd<T>(B(P.ea[l]), chan(l), nullptr, 0, B(P.wp_fwd[2 * l + 1]), prm + Bd.b_off, B(P.eb[l]), N, P.Hl[l], P.Wl[l], chan(l), 1, st,
+                       fuse_pool ? B(P.pool[l]) : nullptr, cd.eb[l], cd.pc[l]));
+        if (l < NLEV - 1 && !fuse_pool) RC(launch_maxpool_fwd(B(P.eb[l]), B(P.pool[l]), N, P.Hl[l + 1], P.Wl[l + 1], chan(l), st));
     }
     for (int l = 3; l >= 0; --l) {
         const int iu = L_UP3 + 3 * (3 - l);
-        const bf16_t* src = l == 3 ? B(P.eb[4]) : B(P.db[l + 1]);
-        ConvArgs a = {};
-        a.in0 = src; a.C0 = chan(l + 1); a.wp = B(P.wp_fwd[iu]); a.N = N; a.H = P.Hl[l + 1]; a.W = P.Wl[l + 1]; a.Nout = 4 * chan(l);
-        a.epi = EPI_CONVT_FWD; a.bias = prm + P.L[iu].b_off; a.out0 = B(P.up[l]); a.Cout_t = chan(l); a.dtype = DT_BF16;
-        RC(launch_conv(a, CONV_1X1, st));
-        RC(conv_fwd_bf16(B(P.up[l]), chan(l), B(P.eb[l]), chan(l), B(P.wp_fwd[iu + 1]), prm + P.L[iu + 1].b_off, B(P.da[l]), N, P.Hl[l], P.Wl[l], chan(l), 1, st, nullptr,
-                         l == 0 && c_da0 ? reinterpret_cast<unsigned*>(ws + P.cd_da[0]) : nullptr));
-        RC(conv_fwd_bf16(B(P.da[l]), chan(l), nullptr, 0, B(P.wp_fwd[iu + 2]), prm + P.L[iu + 2].b_off, B(P.db[l]), N, P.Hl[l], P.Wl[l], chan(l), 1, st));
+        const T* src = l == 3 ? B(P.eb[4]) : B(P.db[l + 1]);
+        bd.conv(l == 3 ? S_EB + 4 : S_DB + l + 1, -1, S_W + iu, S_UP + l);
+        RC(convt_fwd<T>(src, B(P.wp_fwd[iu]), prm + P.L[iu].b_off, B(P.up[l]), N, P.Hl[l + 1], P.Wl[l + 1], chan(l + 1), chan(l), st));
+        bd.conv(S_UP + l, S_EB + l, S_W + iu + 1, S_DA + l);
+        RC(conv_fwd<T>(B(P.up[l]), chan(l), B(P.eb[l]), chan(l), B(P.wp_fwd[iu + 1]), prm + P.L[iu + 1].b_off, B(P.da[l]), N, P.Hl[l], P.Wl[l], chan(l), 1, st, nullptr,
+                       cd.da[l]));
+        bd.conv(S_DA + l, -1, S_W + iu + 2, S_DB + l);
+        RC(conv_fwd<T>(B(P.da[l]), chan(l), nullptr, 0, B(P.wp_fwd[iu + 2]), prm + P.L[iu + 2].b_off, B(P.db[l]), N, P.Hl[l], P.Wl[l], chan(l), 1, st));
     }
     const LayerDef& Hd = P.L[L_HEAD];
-    if (hl)
-        return launch_head_train(B(P.db[0]), 1, prm + Hd.w_off, prm + Hd.b_off, hl->target, out, B(P.gA), ws + P.head_part, hl->loss, N, P.H, P.W, P.out_ch,
+    if (hl)      // training step: output, loss, the head's backward and the gradient of conv9_2's output (-> gA) in one pass
+        return launch_head_train(B(P.db[0]), E::bf16, prm + Hd.w_off, prm + Hd.b_off, hl->target, out, B(P.gA), ws + P.head_part, hl->loss, N, P.H, P.W, P.out_ch,
                                  hl->mse, hl->grad_scale, st);
-    RC(launch_head_fwd_bf16(B(P.db[0]), prm + Hd.w_off, prm + Hd.b_off, out, N, P.H, P.W, P.out_ch, st));
-    return 0;
+    return launch_head_fwd(B(P.db[0]), prm + Hd.w_off, prm + Hd.b_off, out, N, P.H, P.W, P.out_ch, st);
 }
 
 // The debug tap on the backward's activation gradients (include/eld_amd.h eld_debug_unet_grad_tap): the stage numbering, each tensor's place in the
@@ -557,194 +565,97 @@ struct GradTap {
     }
 };
 
+// The ping-pong buffer the backward ends in: conv1_1's weight gradient reads it, eld_debug_unet_region publishes it, unet_backward checks it at that read
+constexpr size_t Plan::* GRAD_CONV1_1 = &Plan::gB;
+
+// T = bf16_t: activation gradients bf16 (igemm on v_mfma_f32_32x32x16_bf16), weight gradients accumulated and written in fp32 (the wgrad kernels
+// convert the bf16 operands while staging).
+template <typename T>
 int unet_backward(const Plan& P, const float* dout, const float* prm, float* grd, float* ws, hipStream_t st, BucketMarks& marks, const FusedFwd& fused, const GradTap& tap) {
+    using E = Elem<T>;
     const int N = P.N;
     KPartScope kp(ws + P.part, P.part_floats);
-    const bool h2 = g_algo == 2;
-    float* am = ws + P.amax;
-    if (h2 && hipMemsetAsync(am + S_GA, 0, (S_COUNT - S_GA) * sizeof(float), st) != hipSuccess) return (int)hipGetLastError();
-    if (!fused.packed) RC(pack_weights(P, prm, ws, PACK_BWD, st, false, h2 ? am : nullptr));
-    float* gA = ws + P.gA; float* gB = ws + P.gB; float* part = ws + P.part;
+    const Bounds bd = bounds<T>(P, ws, st);
+    auto B = [&](size_t off) { return reinterpret_cast<T*>(ws + off); };
+    RC(bd.clear(S_GA, S_COUNT - S_GA));
+    if (!fused.packed) RC(pack_weights(P, prm, ws, PACK_BWD, st, E::bf16, bd.am));
+    T* cur = B(P.gA); T* oth = B(P.gB); float* part = ws + P.part;
+    auto swap = [&]() { T* t = cur; cur = oth; oth = t; };
+    auto gs = [&](const T* buf) { return buf == B(P.gA) ? (int)S_GA : (int)S_GB; };               // bound slot of a ping-pong gradient buffer
     // slope codes the forward left for levels 0 / 1 (FusedFwd::codes names the regions it filled)
-    auto CD = [&](size_t off, unsigned bit) -> const unsigned* { return g_algo == 1 && (fused.codes & bit) ? reinterpret_cast<const unsigned*>(ws + off) : nullptr; };
-    auto gs = [&](const float* buf) { return buf == gA ? (int)S_GA : (int)S_GB; };                 // slot of a ping-pong gradient buffer
-    auto fresh = [&](int slot) -> int {                                                               // zero a slot before its tensor is rewritten
-        if (!h2) return 0;
-        return hipMemsetAsync(am + slot, 0, sizeof(float), st) == hipSuccess ? 0 : (int)hipGetLastError();
-    };
-    auto WG = [&](int g, int x0, int x1) { if (h2) { g_am.in0 = am + g; g_am.w = am + x0; g_am.in1 = x1 >= 0 ? am + x1 : nullptr; } };
-    auto BD = [&](int g, int w, int o0, int o1) { if (h2) { g_am.in0 = am + g; g_am.w = am + w; g_am.out0 = am + o0; g_am.out1 = o1 >= 0 ? am + o1 : nullptr; } };
+    const CodeRegions cd = code_regions(P, ws, E::reads_codes() ? fused.codes : 0u);
     const LayerDef& Hd = P.L[L_HEAD];
     // head: g (pre-activation grad of conv9_2) -> gA
-    if (dout) RC(launch_head_bwd(dout, ws + P.db[0], prm + Hd.w_off, gA, grd + Hd.w_off, grd + Hd.b_off, part, N, P.H, P.W, P.out_ch, st));
-    else RC(launch_head_train_reduce(ws + P.head_part, grd + Hd.w_off, grd + Hd.b_off, N, P.H, P.W, P.out_ch, 0, st));      // gA and the partials: eld_unet_forward_loss_ex
+    if (dout) RC(launch_head_bwd(dout, B(P.db[0]), prm + Hd.w_off, cur, grd + Hd.w_off, grd + Hd.b_off, part, N, P.H, P.W, P.out_ch, st));
+    else RC(launch_head_train_reduce(ws + P.head_part, grd + Hd.w_off, grd + Hd.b_off, N, P.H, P.W, P.out_ch, E::bf16, st));      // gA and the partials: eld_unet_forward_loss_ex
     RC(marks.done(P, L_HEAD, st));
-    if (h2) RC(launch_absmax(gA, (size_t)N * P.H * P.W * 32, am + S_GA, st));
-    RC(tap.copy(TAP_G_HEAD, gA, st));
-    float* cur = gA; float* oth = gB;
+    RC(bd.measure(cur, (size_t)N * P.H * P.W * 32, S_GA));
+    RC(tap.copy(TAP_G_HEAD, cur, st));
     for (int l = 0; l <= 3; ++l) {            // decoder levels 0 (conv9) .. 3 (conv6)
         const int iu = L_UP3 + 3 * (3 - l);
         const int H = P.Hl[l], W = P.Wl[l], C = chan(l);
         // conv_2 of the level: input da[l]
-        WG(gs(cur), S_DA + l, -1);
-        RC(conv_wgrad(cur, C, ws + P.da[l], C, nullptr, 0, C, grd + P.L[iu + 2].w_off, grd + P.L[iu + 2].b_off, part, N, H, W, st));
+        bd.wgrad(gs(cur), S_DA + l, -1);
+        RC(conv_wgrad<T>(cur, C, B(P.da[l]), C, nullptr, 0, C, grd + P.L[iu + 2].w_off, grd + P.L[iu + 2].b_off, part, N, H, W, st));
         RC(marks.done(P, iu + 2, st));
-        RC(fresh(gs(oth))); BD(gs(cur), S_W + iu + 2, gs(oth), -1);
-        RC(conv_bwd_data(cur, ws + P.wp_bwd[iu + 2], oth, nullptr, C, ws + P.da[l], nullptr, N, H, W, C, C, st, l < 2 ? CD(P.cd_da[l], l ? CODES_DA1 : CODES_DA0) : nullptr));
+        RC(bd.clear(gs(oth))); bd.bwd_data(gs(cur), S_W + iu + 2, gs(oth), -1);
+        RC(conv_bwd_data<T>(cur, B(P.wp_bwd[iu + 2]), oth, nullptr, C, B(P.da[l]), nullptr, N, H, W, C, C, st, cd.da[l]));
         RC(tap.copy(TAP_DEC + 4 * l, oth, st));
-        { float* t = cur; cur = oth; oth = t; }
+        swap();
         // conv_1: input cat[up[l], eb[l]] -> d_up (raw) in oth, skip grad (raw) in skip[l]
-        WG(gs(cur), S_UP + l, S_EB + l);
-        RC(conv_wgrad(cur, C, ws + P.up[l], C, ws + P.eb[l], C, 2 * C, grd + P.L[iu + 1].w_off, grd + P.L[iu + 1].b_off, part, N, H, W, st));
+        bd.wgrad(gs(cur), S_UP + l, S_EB + l);
+        RC(conv_wgrad<T>(cur, C, B(P.up[l]), C, B(P.eb[l]), C, 2 * C, grd + P.L[iu + 1].w_off, grd + P.L[iu + 1].b_off, part, N, H, W, st));
         RC(marks.done(P, iu + 1, st));
-        RC(fresh(gs(oth))); BD(gs(cur), S_W + iu + 1, gs(oth), S_SKIP + l);
-        RC(conv_bwd_data(cur, ws + P.wp_bwd[iu + 1], oth, ws + P.skip[l], C, nullptr, nullptr, N, H, W, 2 * C, C, st));
+        RC(bd.clear(gs(oth))); bd.bwd_data(gs(cur), S_W + iu + 1, gs(oth), S_SKIP + l);
+        RC(conv_bwd_data<T>(cur, B(P.wp_bwd[iu + 1]), oth, B(P.skip[l]), C, nullptr, nullptr, N, H, W, 2 * C, C, st));
         RC(tap.copy(TAP_DEC + 4 * l + 1, oth, st));
-        RC(tap.copy(TAP_DEC + 4 * l + 2, ws + P.skip[l], st));
-        { float* t = cur; cur = oth; oth = t; }
+        RC(tap.copy(TAP_DEC + 4 * l + 2, B(P.skip[l]), st));
+        swap();
         // transposed conv: input src (level l+1, 2C channels), output grad = cur (d_up)
-        const float* src = l == 3 ? ws + P.eb[4] : ws + P.db[l + 1];
-        WG(l == 3 ? S_EB + 4 : S_DB + l + 1, gs(cur), -1);
-        RC(convt_wgrad(src, cur, grd + P.L[iu].w_off, grd + P.L[iu].b_off, part, N, P.Hl[l + 1], P.Wl[l + 1], 2 * C, C, st));
+        const T* src = l == 3 ? B(P.eb[4]) : B(P.db[l + 1]);
+        bd.wgrad(l == 3 ? S_EB + 4 : S_DB + l + 1, gs(cur), -1);
+        RC(convt_wgrad<T>(src, cur, grd + P.L[iu].w_off, grd + P.L[iu].b_off, part, N, P.Hl[l + 1], P.Wl[l + 1], 2 * C, C, st));
         RC(marks.done(P, iu, st));
-        RC(fresh(gs(oth))); BD(gs(cur), S_W + iu, gs(oth), -1);
-        RC(convt_bwd_data(cur, ws + P.wp_bwd[iu], src, oth, N, P.Hl[l + 1], P.Wl[l + 1], 2 * C, C, st));
+        RC(bd.clear(gs(oth))); bd.bwd_data(gs(cur), S_W + iu, gs(oth), -1);
+        RC(convt_bwd_data<T>(cur, B(P.wp_bwd[iu]), src, oth, N, P.Hl[l + 1], P.Wl[l + 1], 2 * C, C, st));
         RC(tap.copy(TAP_DEC + 4 * l + 3, oth, st));
-        { float* t = cur; cur = oth; oth = t; }
+        swap();
     }
     // cur = pre-activation grad of conv5_2 (level 4)
     for (int l = 4; l >= 0; --l) {
         const int H = P.Hl[l], W = P.Wl[l], C = chan(l);
         const int ia = 2 * l, ib = 2 * l + 1;
-        WG(gs(cur), S_EA + l, -1);
-        RC(conv_wgrad(cur, C, ws + P.ea[l], C, nullptr, 0, C, grd + P.L[ib].w_off, grd + P.L[ib].b_off, part, N, H, W, st));
+        bd.wgrad(gs(cur), S_EA + l, -1);
+        RC(conv_wgrad<T>(cur, C, B(P.ea[l]), C, nullptr, 0, C, grd + P.L[ib].w_off, grd + P.L[ib].b_off, part, N, H, W, st));
         RC(marks.done(P, ib, st));
-        RC(fresh(gs(oth))); BD(gs(cur), S_W + ib, gs(oth), -1);
-        RC(conv_bwd_data(cur, ws + P.wp_bwd[ib], oth, nullptr, C, ws + P.ea[l], nullptr, N, H, W, C, C, st,
-                         l < 2 ? CD(P.cd_ea[l], l ? CODES_EA1 : CODES_EA0) : nullptr));
+        RC(bd.clear(gs(oth))); bd.bwd_data(gs(cur), S_W + ib, gs(oth), -1);
+        RC(conv_bwd_data<T>(cur, B(P.wp_bwd[ib]), oth, nullptr, C, B(P.ea[l]), nullptr, N, H, W, C, C, st, cd.ea[l]));
         RC(tap.copy(TAP_ENC + 3 * (4 - l), oth, st));
-        { float* t = cur; cur = oth; oth = t; }
+        swap();
         if (l == 0) {
+            if (cur != B(P.*GRAD_CONV1_1)) return ELD_EINVAL;      // one swap more or less above: GRAD_CONV1_1 moves with it
             if (P.in_ch <= 4)
                 RC(launch_conv_first_wgrad(cur, fused.x ? fused.x : ws + P.x16, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, P.in_ch, H, W, st, g_algo == 1));
-            else {
-                WG(gs(cur), S_X, -1);
-                RC(conv_wgrad(cur, C, ws + P.x16, 16, nullptr, 0, P.in_ch, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, H, W, st));
+            else {      // the zero-padded NHWC input the forward left in ws + P.x16; only the in_ch real channels are written to dw
+                bd.wgrad(gs(cur), S_X, -1);
+                RC(conv_wgrad<T>(cur, C, B(P.x16), E::x_pad, nullptr, 0, P.in_ch, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, H, W, st));
             }
             RC(marks.done(P, ia, st));
             break;
         }
         const int Cp = chan(l - 1);
-        WG(gs(cur), S_EB + l - 1, -1);                 // pooled activations are bounded by their source's bound
-        RC(conv_wgrad(cur, C, ws + P.pool[l - 1], Cp, nullptr, 0, Cp, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, H, W, st));
+        bd.wgrad(gs(cur), S_EB + l - 1, -1);                 // pooled activations are bounded by their source's bound
+        RC(conv_wgrad<T>(cur, C, B(P.pool[l - 1]), Cp, nullptr, 0, Cp, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, H, W, st));
         RC(marks.done(P, ia, st));
-        RC(fresh(gs(oth))); BD(gs(cur), S_W + ia, gs(oth), -1);
-        RC(conv_bwd_data(cur, ws + P.wp_bwd[ia], oth, nullptr, Cp, nullptr, nullptr, N, H, W, Cp, C, st));      // d_pool (raw)
+        RC(bd.clear(gs(oth))); bd.bwd_data(gs(cur), S_W + ia, gs(oth), -1);
+        RC(conv_bwd_data<T>(cur, B(P.wp_bwd[ia]), oth, nullptr, Cp, nullptr, nullptr, N, H, W, Cp, C, st));      // d_pool (raw)
         RC(tap.copy(TAP_ENC + 3 * (4 - l) + 1, oth, st));
-        { float* t = cur; cur = oth; oth = t; }
-        if (l - 1 < 2 && CD(P.cd_eb[l - 1], l - 1 ? CODES_EB1 : CODES_EB0) != nullptr)
-            RC(launch_maxpool_bwd_codes(CD(P.pc[l - 1], l - 1 ? CODES_EB1 : CODES_EB0), CD(P.cd_eb[l - 1], l - 1 ? CODES_EB1 : CODES_EB0), cur, ws + P.skip[l - 1], oth, N, H, W, Cp, st));
+        swap();
+        if (cd.eb[l - 1])
+            RC(launch_maxpool_bwd_codes(cd.pc[l - 1], cd.eb[l - 1], cur, B(P.skip[l - 1]), oth, N, H, W, Cp, st));
         else
-            RC(launch_maxpool_bwd(ws + P.eb[l - 1], cur, ws + P.skip[l - 1], oth, N, H, W, Cp, st));
-        if (h2) { RC(fresh(gs(oth))); RC(launch_absmax(oth, (size_t)N * 4 * H * W * Cp, am + gs(oth), st)); }
-        RC(tap.copy(TAP_ENC + 3 * (4 - l) + 2, oth, st));
-        { float* t = cur; cur = oth; oth = t; }
-    }
-    return 0;
-}
-
-// bf16 backward: activation gradients bf16 (igemm on v_mfma_f32_32x32x16_bf16), weight gradients accumulated and written
-// in fp32 (the wgrad kernels convert the bf16 operands while staging; fp32 MFMA).  Mirrors unet_backward step for step.
-int conv_bwd_data_bf16(const bf16_t* g, const bf16_t* wb, bf16_t* out0, bf16_t* out1, int split, const bf16_t* act0, const bf16_t* act1, int N, int H,
-                       int W, int Cin, int Cout, hipStream_t st, const unsigned* codes0 = nullptr) {
-    ConvArgs a = {};
-    a.codes0 = codes0;
-    a.in0 = g; a.C0 = Cout; a.wp = wb; a.N = N; a.H = H; a.W = W; a.Nout = Cin;
-    a.epi = EPI_GRAD; a.out0 = out0; a.out1 = out1; a.split = split; a.act0 = act0; a.act1 = act1; a.dtype = DT_BF16;
-    return launch_conv(a, CONV_3X3, st);
-}
-
-// Cin_real > 0: the weight tensor's input channels when x0 is zero padded beyond them (conv1_1 with more than 4 planes)
-int conv_wgrad_bf16(const bf16_t* g, int Cout, const bf16_t* x0, int C0, const bf16_t* x1, int C1, float* dw, float* db, float* part,
-                    int N, int H, int W, hipStream_t st, int Cin_real = 0) {
-    const WgradGeom q = wgrad_geom(CONV_3X3, Cout, C0 + C1, N, H, W, (C0 % 32 || C1 % 32) ? 0 : 3);
-    WgradArgs a = {};
-    a.g = g; a.CA = Cout; a.x0 = x0; a.x1 = x1; a.C0 = C0; a.C1 = C1; a.N = N; a.H = H; a.W = W; a.dtype = DT_BF16;
-    a.part = part; a.bpart = db ? part + (size_t)q.psplit * q.T * q.CA * q.CBp : nullptr; a.CBp = q.CBp; a.psplit = q.psplit;
-    a.wgrad8 = q.w8;
-    RC(launch_wgrad(a, CONV_3X3, st));
-    return launch_wgrad_reduce(part, a.bpart, dw, db, q.psplit, q.T, q.CA, q.CBp, Cin_real > 0 ? Cin_real : C0 + C1, st);
-}
-
-int unet_backward_bf16(const Plan& P, const float* dout, const float* prm, float* grd, float* ws, hipStream_t st, BucketMarks& marks, const FusedFwd& fused, const GradTap& tap) {
-    const int N = P.N;
-    if (!fused.packed) RC(pack_weights(P, prm, ws, PACK_BWD, st, true));
-    auto B = [&](size_t off) { return reinterpret_cast<bf16_t*>(ws + off); };
-    bf16_t* cur = B(P.gA); bf16_t* oth = B(P.gB); float* part = ws + P.part;
-    const LayerDef& Hd = P.L[L_HEAD];
-    if (dout) RC(launch_head_bwd_bf16(dout, B(P.db[0]), prm + Hd.w_off, cur, grd + Hd.w_off, grd + Hd.b_off, part, N, P.H, P.W, P.out_ch, st));
-    else RC(launch_head_train_reduce(ws + P.head_part, grd + Hd.w_off, grd + Hd.b_off, N, P.H, P.W, P.out_ch, 1, st));
-    RC(marks.done(P, L_HEAD, st));
-    RC(tap.copy(TAP_G_HEAD, cur, st));
-    auto swap = [&]() { bf16_t* t = cur; cur = oth; oth = t; };
-    for (int l = 0; l <= 3; ++l) {
-        const int iu = L_UP3 + 3 * (3 - l);
-        const int H = P.Hl[l], W = P.Wl[l], C = chan(l);
-        RC(conv_wgrad_bf16(cur, C, B(P.da[l]), C, nullptr, 0, grd + P.L[iu + 2].w_off, grd + P.L[iu + 2].b_off, part, N, H, W, st));
-        RC(marks.done(P, iu + 2, st));
-        RC(conv_bwd_data_bf16(cur, B(P.wp_bwd[iu + 2]), oth, nullptr, C, B(P.da[l]), nullptr, N, H, W, C, C, st,
-                              l == 0 && (fused.codes & CODES_DA0) ? reinterpret_cast<const unsigned*>(ws + P.cd_da[0]) : nullptr));
-        RC(tap.copy(TAP_DEC + 4 * l, oth, st));
-        swap();
-        RC(conv_wgrad_bf16(cur, C, B(P.up[l]), C, B(P.eb[l]), C, grd + P.L[iu + 1].w_off, grd + P.L[iu + 1].b_off, part, N, H, W, st));
-        RC(marks.done(P, iu + 1, st));
-        RC(conv_bwd_data_bf16(cur, B(P.wp_bwd[iu + 1]), oth, B(P.skip[l]), C, nullptr, nullptr, N, H, W, 2 * C, C, st));
-        RC(tap.copy(TAP_DEC + 4 * l + 1, oth, st));
-        RC(tap.copy(TAP_DEC + 4 * l + 2, B(P.skip[l]), st));
-        swap();
-        const bf16_t* src = l == 3 ? B(P.eb[4]) : B(P.db[l + 1]);
-        {   // transposed conv: weight gradient (gather mode), bias gradient (column sums of d_up), backward data
-            const int Hi = P.Hl[l + 1], Wi = P.Wl[l + 1];
-            const WgradGeom q = wgrad_geom(CONV_GATHER2X2, 2 * C, C, N, Hi, Wi, 0);
-            WgradArgs a = {};
-            a.g = src; a.CA = 2 * C; a.x0 = cur; a.C0 = C; a.N = N; a.H = Hi; a.W = Wi; a.dtype = DT_BF16;
-            a.part = part; a.bpart = nullptr; a.CBp = q.CBp; a.psplit = q.psplit;
-            a.xbpart = part + (size_t)q.psplit * q.T * q.CA * q.CBp;          // bias gradient = column sums of d_up, from the staging registers
-            RC(launch_wgrad(a, CONV_GATHER2X2, st));
-            RC(launch_wgrad_reduce(part, a.xbpart, grd + P.L[iu].w_off, grd + P.L[iu].b_off, q.psplit, q.T, q.CA, q.CBp, C, st, q.CBp));
-            RC(marks.done(P, iu, st));
-            ConvArgs c = {};
-            c.in0 = cur; c.C0 = C; c.wp = B(P.wp_bwd[iu]); c.N = N; c.H = Hi; c.W = Wi; c.Nout = 2 * C;
-            c.epi = EPI_GRAD; c.out0 = oth; c.split = 2 * C; c.act0 = src; c.dtype = DT_BF16;
-            RC(launch_conv(c, CONV_GATHER2X2, st));
-        }
-        RC(tap.copy(TAP_DEC + 4 * l + 3, oth, st));
-        swap();
-    }
-    for (int l = 4; l >= 0; --l) {
-        const int H = P.Hl[l], W = P.Wl[l], C = chan(l);
-        const int ia = 2 * l, ib = 2 * l + 1;
-        RC(conv_wgrad_bf16(cur, C, B(P.ea[l]), C, nullptr, 0, grd + P.L[ib].w_off, grd + P.L[ib].b_off, part, N, H, W, st));
-        RC(marks.done(P, ib, st));
-        RC(conv_bwd_data_bf16(cur, B(P.wp_bwd[ib]), oth, nullptr, C, B(P.ea[l]), nullptr, N, H, W, C, C, st,
-                              l == 0 && (fused.codes & CODES_EA0) ? reinterpret_cast<const unsigned*>(ws + P.cd_ea[0]) : nullptr));
-        RC(tap.copy(TAP_ENC + 3 * (4 - l), oth, st));
-        swap();
-        if (l == 0) {
-            if (P.in_ch <= 4)
-                RC(launch_conv_first_wgrad_bf16(cur, fused.x ? fused.x : ws + P.x16, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, P.in_ch, H, W, st));
-            else      // the zero-padded NHWC32 bf16 input the forward left in ws + P.x16; only the in_ch real channels are written to dw
-                RC(conv_wgrad_bf16(cur, C, B(P.x16), 32, nullptr, 0, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, H, W, st, P.in_ch));
-            RC(marks.done(P, ia, st));
-            break;
-        }
-        const int Cp = chan(l - 1);
-        RC(conv_wgrad_bf16(cur, C, B(P.pool[l - 1]), Cp, nullptr, 0, grd + P.L[ia].w_off, grd + P.L[ia].b_off, part, N, H, W, st));
-        RC(marks.done(P, ia, st));
-        RC(conv_bwd_data_bf16(cur, B(P.wp_bwd[ia]), oth, nullptr, Cp, nullptr, nullptr, N, H, W, Cp, C, st));
-        RC(tap.copy(TAP_ENC + 3 * (4 - l) + 1, oth, st));
-        swap();
-        RC(launch_maxpool_bwd_bf16(B(P.eb[l - 1]), cur, B(P.skip[l - 1]), oth, N, H, W, Cp, st));
+            RC(launch_maxpool_bwd(B(P.eb[l - 1]), cur, B(P.skip[l - 1]), oth, N, H, W, Cp, st));
+        RC(bd.clear(gs(oth))); RC(bd.measure(oth, (size_t)N * 4 * H * W * Cp, gs(oth)));
         RC(tap.copy(TAP_ENC + 3 * (4 - l) + 2, oth, st));
         swap();
     }
@@ -862,8 +773,8 @@ static int unet_forward_entry(const float* x, const float* params, float* out, v
     AlgoScope scope(fp32_algo);
     head_state_set(ws, nullptr);      // whatever fused head state the workspace held is overwritten
     unsigned have = 0;
-    const int rc = precision == 1 ? unet_forward_bf16(P, x, params, out, (float*)ws, as_stream(stream), nullptr, &have, infer)
-                                  : unet_forward(P, x, params, out, (float*)ws, as_stream(stream), nullptr, &have, infer);
+    const int rc = precision == 1 ? unet_forward<bf16_t>(P, x, params, out, (float*)ws, as_stream(stream), nullptr, &have, infer)
+                                  : unet_forward<float>(P, x, params, out, (float*)ws, as_stream(stream), nullptr, &have, infer);
     codes_state_set(ws, CodesState{N, H, W, in_ch, out_ch, precision, rc == 0 ? (infer ? (unsigned)CODES_INFER : have) : 0u});
     return rc;
 }
@@ -886,8 +797,8 @@ extern "C" int eld_unet_forward_loss_ex(const float* x, const float* params, con
     const HeadLoss hl = {target, loss, loss_kind, grad_scale};
     head_state_set(ws, nullptr);
     unsigned have = 0;
-    const int rc = precision == 1 ? unet_forward_bf16(P, x, params, out, (float*)ws, as_stream(stream), &hl, &have)
-                                  : unet_forward(P, x, params, out, (float*)ws, as_stream(stream), &hl, &have);
+    const int rc = precision == 1 ? unet_forward<bf16_t>(P, x, params, out, (float*)ws, as_stream(stream), &hl, &have)
+                                  : unet_forward<float>(P, x, params, out, (float*)ws, as_stream(stream), &hl, &have);
     codes_state_set(ws, CodesState{N, H, W, in_ch, out_ch, precision, rc == 0 ? have : 0u});
     if (rc == 0) { const HeadState hs = {N, H, W, in_ch, out_ch, precision, x}; head_state_set(ws, &hs); }
     return rc;
@@ -931,8 +842,8 @@ extern "C" int eld_unet_backward_ex(const float* dout, const float* params, floa
         }
     }
     AlgoScope scope(fp32_algo);
-    const int rc = precision == 1 ? unet_backward_bf16(P, dout, params, grads, (float*)ws, as_stream(stream), marks, fused, tap)
-                                  : unet_backward(P, dout, params, grads, (float*)ws, as_stream(stream), marks, fused, tap);
+    const int rc = precision == 1 ? unet_backward<bf16_t>(P, dout, params, grads, (float*)ws, as_stream(stream), marks, fused, tap)
+                                  : unet_backward<float>(P, dout, params, grads, (float*)ws, as_stream(stream), marks, fused, tap);
     if (rc) return rc;
     return marks.next == n_buckets ? 0 : ELD_EINVAL;
 }
@@ -1020,9 +931,8 @@ extern "C" size_t eld_layer_workspace_bytes(int N, int H, int W, int Cin, int Co
     const int cinp = (Cin + 15) / 16 * 16;
     size_t f = (size_t)9 * Cout * cinp * 2 + 64;                            // one packed weight set (fp32 or pre-split slabs)
     size_t p = 0, q;
-    if (Cout % 32 == 0) { q = wgrad_geom(CONV_3X3, Cout, Cin, N, H, W, 0).floats; p = q > p ? q : p; q = wgrad_geom(CONV_3X3, Cout, Cin, N, H, W, 1).floats; p = q > p ? q : p;
-                          q = wgrad_geom(CONV_3X3, Cout, Cin, N, H, W, 3).floats; p = q > p ? q : p; }      // (3: the bf16 entry points below)
-    if (Cin % 32 == 0) { q = wgrad_geom(CONV_GATHER2X2, Cin, Cout, N, H, W, 0).floats; p = q > p ? q : p; q = wgrad_geom(CONV_GATHER2X2, Cin, Cout, N, H, W, 1).floats; p = q > p ? q : p; }
+    if (Cout % 32 == 0) { q = wgrad_floats_max(CONV_3X3, Cout, Cin, N, H, W); p = q > p ? q : p; }
+    if (Cin % 32 == 0) { q = wgrad_floats_max(CONV_GATHER2X2, Cin, Cout, N, H, W); p = q > p ? q : p; }
     q = colsum_ws_floats(Cout > Cin ? Cout : Cin); p = q > p ? q : p;
     return (align_up(f, 64) + align_up(p, 64) + 64) * sizeof(float);      // + 64 operand-bound slots (conv_fp32_algo 2)
 }
@@ -1168,7 +1078,7 @@ extern "C" int eld_conv3x3_forward_bf16(const uint16_t* in0, int C0, const uint1
     RC(layer_ws(ws, ws_bytes, N, H, W, C0 + C1, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
     RC(pack_one_bf16(w, pack, PACK_CONV_FWD, Cout, C0 + C1, 9, bfd_slab_bn(Cout, C0 + C1, N, H, W), 0, st));
-    return conv_fwd_bf16(in0, C0, in1, C1, reinterpret_cast<const bf16_t*>(pack), bias, out, N, H, W, Cout, lrelu, st, pool_out);
+    return conv_fwd<bf16_t>(in0, C0, in1, C1, reinterpret_cast<const bf16_t*>(pack), bias, out, N, H, W, Cout, lrelu, st, pool_out);
 }
 
 extern "C" int eld_conv3x3_backward_data_bf16(const uint16_t* g, const float* w, uint16_t* din0, uint16_t* din1, int split, const uint16_t* act0,
@@ -1179,7 +1089,7 @@ extern "C" int eld_conv3x3_backward_data_bf16(const uint16_t* g, const float* w,
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
     RC(pack_one_bf16(w, pack, PACK_CONV_BWD, Cout, Cin, 9, bfd_slab_bn(Cin, Cout, N, H, W), 0, st));
-    return conv_bwd_data_bf16(g, reinterpret_cast<const bf16_t*>(pack), din0, din1, split, act0, act1, N, H, W, Cin, Cout, st);
+    return conv_bwd_data<bf16_t>(g, reinterpret_cast<const bf16_t*>(pack), din0, din1, split, act0, act1, N, H, W, Cin, Cout, st);
 }
 
 extern "C" int eld_conv3x3_backward_weight_bf16(const uint16_t* g, const uint16_t* x0, int C0, const uint16_t* x1, int C1, float* dw, float* db, int N,
@@ -1188,7 +1098,7 @@ extern "C" int eld_conv3x3_backward_weight_bf16(const uint16_t* g, const uint16_
     if (!g || !x0 || !dw || Cout % 32 || C0 % 8 || C1 % 8 || (C1 && (!x1 || C0 % 32))) return ELD_EINVAL;
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, C0 + C1, Cout, &pack, &part));
-    return conv_wgrad_bf16(g, Cout, x0, C0, x1, C1, dw, db, part, N, H, W, as_stream(stream));
+    return conv_wgrad<bf16_t>(g, Cout, x0, C0, x1, C1, C0 + C1, dw, db, part, N, H, W, as_stream(stream));
 }
 
 extern "C" int eld_convt2x2_forward_bf16(const uint16_t* in, const float* w, const float* bias, uint16_t* out, int N, int H, int W, int Cin, int Cout,
@@ -1199,10 +1109,7 @@ extern "C" int eld_convt2x2_forward_bf16(const uint16_t* in, const float* w, con
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
     RC(pack_one_bf16(w, pack, PACK_CONVT_FWD, Cout, Cin, 4, 0, bfg_slab_bn(false, 4 * Cout, Cin, Cout, N, H, W), st));
-    ConvArgs a = {};      // as unet_forward_bf16
-    a.in0 = in; a.C0 = Cin; a.wp = pack; a.N = N; a.H = H; a.W = W; a.Nout = 4 * Cout;
-    a.epi = EPI_CONVT_FWD; a.bias = bias; a.out0 = out; a.Cout_t = Cout; a.dtype = DT_BF16;
-    return launch_conv(a, CONV_1X1, st);
+    return convt_fwd<bf16_t>(in, reinterpret_cast<const bf16_t*>(pack), bias, out, N, H, W, Cin, Cout, st);
 }
 
 extern "C" int eld_convt2x2_backward_data_bf16(const uint16_t* dout, const float* w, const uint16_t* act, uint16_t* din, int N, int H, int W, int Cin,
@@ -1213,10 +1120,7 @@ extern "C" int eld_convt2x2_backward_data_bf16(const uint16_t* dout, const float
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
     RC(pack_one_bf16(w, pack, PACK_CONVT_BWD, Cout, Cin, 4, 0, bfg_slab_bn(true, Cin, Cout, 0, N, H, W), st));
-    ConvArgs c = {};      // as unet_backward_bf16
-    c.in0 = dout; c.C0 = Cout; c.wp = pack; c.N = N; c.H = H; c.W = W; c.Nout = Cin;
-    c.epi = EPI_GRAD; c.out0 = din; c.split = Cin; c.act0 = act; c.dtype = DT_BF16;
-    return launch_conv(c, CONV_GATHER2X2, st);
+    return convt_bwd_data<bf16_t>(dout, reinterpret_cast<const bf16_t*>(pack), act, din, N, H, W, Cin, Cout, st);
 }
 
 extern "C" int eld_convt2x2_backward_weight_bf16(const uint16_t* in, const uint16_t* dout, float* dw, float* db, int N, int H, int W, int Cin, int Cout,
@@ -1225,17 +1129,7 @@ extern "C" int eld_convt2x2_backward_weight_bf16(const uint16_t* in, const uint1
     if (!in || !dout || !dw || Cin % 32 || Cout % 8) return ELD_EINVAL;
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
-    hipStream_t st = as_stream(stream);
-    const WgradGeom q = wgrad_geom(CONV_GATHER2X2, Cin, Cout, N, H, W, 0);      // as unet_backward_bf16
-    WgradArgs a = {};
-    a.g = in; a.CA = Cin; a.x0 = dout; a.C0 = Cout; a.N = N; a.H = H; a.W = W; a.dtype = DT_BF16;
-    a.part = part; a.bpart = nullptr; a.CBp = q.CBp; a.psplit = q.psplit;
-    const bool fused_bias = db != nullptr && q.CBp <= q.CA && Cout == q.CBp;
-    a.xbpart = fused_bias ? part + (size_t)q.psplit * q.T * q.CA * q.CBp : nullptr;
-    RC(launch_wgrad(a, CONV_GATHER2X2, st));
-    RC(launch_wgrad_reduce(part, a.xbpart, dw, fused_bias ? db : nullptr, q.psplit, q.T, q.CA, q.CBp, Cout, st, q.CBp));
-    if (!db || fused_bias) return 0;
-    return launch_colsum_bf16(dout, db, part, (size_t)N * 4 * H * W, Cout, st);
+    return convt_wgrad<bf16_t>(in, dout, dw, db, part, N, H, W, Cin, Cout, as_stream(stream));
 }
 
 extern "C" int eld_maxpool2x2_forward_bf16(const uint16_t* in, uint16_t* out, int N, int Ho, int Wo, int C, void* stream) {
@@ -1251,8 +1145,6 @@ extern "C" int eld_maxpool2x2_backward_bf16(const uint16_t* act, const uint16_t*
     return launch_maxpool_bwd_bf16(act, dp, skip, g, N, Ho, Wo, C, as_stream(stream));
 }
 
-// The gradient buffer conv1_1's weight gradient reads in unet_backward_bf16: the head writes gA, every later stage writes the other buffer and
-// swaps -- three swaps per decoder level and per encoder level 4 .. 1 (24, even), one more after conv1_2's backward-data: gB.
 extern "C" int eld_debug_unet_region(int N, int H, int W, int in_ch, int out_ch, int precision, int region, int level, size_t* offset, int* channels,
                                      int* dtype) {
     if (!offset || !channels || !dtype || (precision != 0 && precision != 1)) return ELD_EINVAL;
@@ -1276,7 +1168,7 @@ extern "C" int eld_debug_unet_region(int N, int H, int W, int in_ch, int out_ch,
             break;
         case ELD_REGION_GRAD_CONV1_1:
             if (precision != 1) return ELD_ENOTSUP;
-            off = P.gB; ch = 32;
+            off = P.*GRAD_CONV1_1; ch = 32;
             break;
         default: return ELD_EINVAL;
     }

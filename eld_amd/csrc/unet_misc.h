@@ -59,3 +59,27 @@ int launch_head_wide_train(const void* act, int bf16, const float* w, const floa
                            int N, int H, int W, int OC, int mse, float grad_scale, hipStream_t st);
 int launch_head_wide_train_reduce(const float* part, float* dw, float* db, int N, int H, int W, int OC, hipStream_t st);
 int launch_nchw_to_nhwc32_bf16(const float* x, bf16_t* y, int N, int C, int H, int W, hipStream_t st);
+
+// One name per step for code that is typed on the activation element (unet.hip): the bf16 launchers above as overloads of the fp32 ones
+inline int launch_nchw_to_nhwc_pad(const float* x, float* y, int N, int C, int H, int W, hipStream_t st) { return launch_nchw_to_nhwc16(x, y, N, C, H, W, st); }
+inline int launch_nchw_to_nhwc_pad(const float* x, bf16_t* y, int N, int C, int H, int W, hipStream_t st) { return launch_nchw_to_nhwc32_bf16(x, y, N, C, H, W, st); }
+inline int launch_maxpool_fwd(const bf16_t* in, bf16_t* out, int N, int Ho, int Wo, int C, hipStream_t st) { return launch_maxpool_fwd_bf16(in, out, N, Ho, Wo, C, st); }
+inline int launch_maxpool_bwd(const bf16_t* act, const bf16_t* dp, const bf16_t* skip, bf16_t* g, int N, int Ho, int Wo, int C, hipStream_t st) {
+    return launch_maxpool_bwd_bf16(act, dp, skip, g, N, Ho, Wo, C, st);
+}
+inline int launch_maxpool_bwd_codes(const unsigned*, const unsigned*, const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, hipStream_t) {
+    return ELD_ENOTSUP;      // no bf16 kernel writes or reads pool codes
+}
+inline int launch_head_fwd(const bf16_t* in, const float* w, const float* b, float* out, int N, int H, int W, int OC, hipStream_t st) {
+    return launch_head_fwd_bf16(in, w, b, out, N, H, W, OC, st);
+}
+inline int launch_head_bwd(const float* dout, const bf16_t* act, const float* w, bf16_t* g, float* dw, float* db, float* part, int N, int H, int W, int OC, hipStream_t st) {
+    return launch_head_bwd_bf16(dout, act, w, g, dw, db, part, N, H, W, OC, st);
+}
+inline int launch_colsum(const bf16_t* x, float* out, float* part, size_t P, int C, hipStream_t st) { return launch_colsum_bf16(x, out, part, P, C, st); }
+inline int launch_conv_first_fwd(const float* x, const float* w, const float* bias, bf16_t* out, int N, int Cin, int H, int W, int lrelu, hipStream_t st, unsigned* codes = nullptr) {
+    return launch_conv_first_fwd_bf16(x, w, bias, out, N, Cin, H, W, lrelu, st, codes);
+}
+inline int launch_conv_first_wgrad(const bf16_t* g, const float* x, float* dw, float* db, float* part, int N, int Cin, int H, int W, hipStream_t st, bool /*x3: an fp32 product scheme*/) {
+    return launch_conv_first_wgrad_bf16(g, x, dw, db, part, N, Cin, H, W, st);
+}

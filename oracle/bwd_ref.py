@@ -1,6 +1,6 @@
 """float64 stage references of the U-Net backward (checker only; DESIGN.md sections 6 / 6a).
 
-unet_backward / unet_backward_bf16 (csrc/unet.hip) are 30 stages that write an activation gradient and 23 that write a layer's dW / db.
+unet_backward<T> (csrc/unet.hip: one schedule for fp32 and bf16 tensors) is 30 stages that write an activation gradient and 23 that write a layer's dW / db.
 stages() restates every one of them as the float64 layer functions of oracle/bf16_ref.py applied to
   * the forward's saved regions (`fwd`: x, ea[l], eb[l], pool[l], up[l], da[l], db[l], NHWC float64),
   * the weights as the kernels read them (`W`: reference layouts, float64 -- fp32 values, or their bf16 roundings for the bf16 engine),

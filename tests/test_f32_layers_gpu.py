@@ -12,7 +12,7 @@ saved input (eld_debug_unet_region), pools bit for bit, and the families chosen 
 
 The modes read once per process from the environment (ELD_X3W other than the default, ELD_X3D_32 -> "conv_x3d<32,8>", ELD_X3_BSLAB, ELD_WG8_*, ...)
 run these same checks in one fresh interpreter per setting: tests/test_env_variants_gpu.py.  Out of scope: the other fp32 schemes
-(tests/test_unet_gpu.py runs them).  The backward's call sites -- every gradient stage of unet_backward, teacher-forced through the gradient
+(tests/test_unet_gpu.py runs them).  The backward's call sites -- every gradient stage of unet_backward<float>, teacher-forced through the gradient
 tap, slope and pool codes live and masked -- are in tests/test_backward_layers_gpu.py.
 
 F32_MEASURED: worst error as a fraction of its bound per family, one MI355X (this file)."""
