@@ -350,14 +350,8 @@ __global__ __launch_bounds__(CB_THREADS) void cell_residual_kernel(const uint16_
 
 // a 2x2 raw_pattern (a permutation of the channels 0..3) as the slots of the period-2 cells
 int parse_pattern(const int* raw_pattern, CellSlots& p) {
-    if (!raw_pattern) return ELD_EINVAL;
-    bool seen[4] = {false, false, false, false};
-    for (int i = 0; i < 4; ++i) {
-        const int k = raw_pattern[i];
-        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
-        seen[k] = true;
-        p.s[i] = (unsigned char)k;
-    }
+    if (!raw_pattern || !bayer_permutation(raw_pattern)) return ELD_EINVAL;
+    for (int i = 0; i < 4; ++i) p.s[i] = (unsigned char)raw_pattern[i];
     return 0;
 }
 

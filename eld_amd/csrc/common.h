@@ -73,6 +73,25 @@ static inline int eld_num_cus() {
     return cus[dev];
 }
 
+// workgroups of a grid-stride pass over `units` lanes' worth of work: at most 8 per compute unit
+static inline unsigned stride_grid(uint32_t units, int threads) {
+    const long long nb = ((long long)units + threads - 1) / threads, cap = 8ll * eld_num_cus();
+    return (unsigned)(nb < cap ? nb : cap);
+}
+
+// a mosaic the 8-columns-per-lane passes (shading.hip, flatfield.hip) refuse: odd width, or more sites than a 32-bit unit count holds
+static inline bool bad_shape(int Hm, int Wm) { return Hm < 0 || Wm < 0 || Wm % 2 || (uint64_t)Hm * (uint64_t)Wm >= (1ull << 31); }
+
+// a Bayer raw_pattern (4 ints, not null): a permutation of the colour codes 0..3.  Each caller builds its own table from it.
+static inline bool bayer_permutation(const int* raw_pattern) {
+    unsigned seen = 0u;
+    for (int i = 0; i < 4; ++i) {
+        if (raw_pattern[i] < 0 || raw_pattern[i] > 3) return false;
+        seen |= 1u << raw_pattern[i];
+    }
+    return seen == 15u;
+}
+
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is per device: remember which devices a kernel has been prepared on
 struct EldAttrOnce {
     bool done[64] = {false};

@@ -355,13 +355,8 @@ bool class_table(int period, const int* pattern, ClassTable* t) {
     if (!pattern || (period != 2 && period != 6)) return false;
     t->lo = t->hi = 0; t->p = period;
     if (period == 2) {
-        bool seen[4] = {false, false, false, false};
-        for (int i = 0; i < 4; ++i) {
-            const int k = pattern[i];
-            if (k < 0 || k > 3 || seen[k]) return false;
-            seen[k] = true;
-            t->lo |= (uint64_t)k << (2 * i);
-        }
+        if (!bayer_permutation(pattern)) return false;
+        for (int i = 0; i < 4; ++i) t->lo |= (uint64_t)pattern[i] << (2 * i);
         t->R = 2; t->step = 2;
         return true;
     }

@@ -4,8 +4,7 @@
 //   eld_flat_sums_u16                  flat frames in a frame pool -> per site S = sum of codes, D = sum over pairs of (a - b)^2, a bad flag
 //   eld_flat_box_u32                   S and the flag -> per site the sum and the count of the good sites of its window, in its position plane
 //   eld_flat_apply_u16                 uint16 codes [N,Hm,Wm] -> clamp(rint((u - black) * gain + black), 0, 65535)
-//   eld_pack_raw_bayer_u16_flat        eld_pack_raw_bayer_u16_shaded with ((u - black) - (a + b t)) * gain / denom; a, b and ratios optional
-//   eld_pack_raw_xtrans_u16_flat       eld_pack_raw_xtrans_u16_shaded likewise
+// The input stage that multiplies by the gain plane in float32 (eld_pack_raw_*_u16_flat) is in pack_raw.hip.
 // The first two are integer arithmetic throughout: their outputs do not depend on the launch geometry, and tests/flatfield_ref.py restates them
 // (and the float32 operation order of the other three) in NumPy.  The library is built with -ffp-contract=off; the pragma says so for this file.
 //
@@ -22,7 +21,6 @@
 //   columns  a lane owns one mosaic column (coalesced across the wave) and slides down FF_VSEG plane rows of each of the p row phases
 // The cost per site is 2 + (2R + 1) / FF_SEG LDS reads and 2 + (2R + 1) / FF_VSEG global reads: linear in R with a small slope, not R^2.
 #include "common.h"
-#include "xtrans.h"
 
 #pragma clang fp contract(off)
 
@@ -269,110 +267,6 @@ __global__ __launch_bounds__(FF_T) void flat_apply_kernel(ApplyArgs a) {
     }
 }
 
-// ---- the inference input stage with the gain fused: pack_raw_shaded_kernel / pack_raw_xtrans_shaded_kernel of shading.hip with one more plane.
-// SHADE = false skips the subtraction (the operation order of pack_raw_kernel of noise.hip); ratios == nullptr skips the ratio (GAIN = false there).
-// v * 1.0f = v for every v, so a gain plane of ones gives the bits of those kernels.
-struct PackRawArgs { int oy[4], ox[4]; float black[4], denom[4]; };
-
-__device__ __forceinline__ float apply_ratio(float v, float ratio) { return fmaxf(fminf(v * ratio, 1.f), 0.f); }
-
-template <bool VMAP, bool SHADE>
-__global__ __launch_bounds__(256) void pack_raw_flat_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, PackRawArgs p,
-                                                            const float* __restrict__ ratios, const float* __restrict__ ma,
-                                                            const float* __restrict__ mb, float t, const float* __restrict__ gain) {
-    const int n = blockIdx.y;
-    const bool scaled = ratios != nullptr;
-    const float ratio = scaled ? ratios[n] : 1.f;
-    const size_t hw = (size_t)h * w, W2 = 2 * (size_t)w;
-    const uint16_t* src = im + (size_t)n * 4 * hw;
-    float* dst = out + (size_t)n * 4 * hw;
-    const int wp = (w + 1) / 2;                                     // position pairs per packed row
-    const size_t total = (size_t)h * wp;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int y = (int)(i / wp), x = 2 * (int)(i - (size_t)y * wp);
-        const bool two = x + 1 < w;
-        uint16_t q[2][4];                                           // q[row][col] of the 2 x 4 mosaic block
-        float ds[2][4], gn[2][4];                                   // a + b t and the gain of the same sites
-        const size_t m0 = (size_t)(2 * y) * W2 + 2 * x;
-        const uint16_t* r0 = src + m0;
-        if (two && ((W2 & 3) == 0)) {
-            const ushort4 a = *reinterpret_cast<const ushort4*>(r0), b = *reinterpret_cast<const ushort4*>(r0 + W2);
-            q[0][0] = a.x; q[0][1] = a.y; q[0][2] = a.z; q[0][3] = a.w; q[1][0] = b.x; q[1][1] = b.y; q[1][2] = b.z; q[1][3] = b.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { const bool ok = c < 2 || two; q[0][c] = ok ? r0[c] : 0; q[1][c] = ok ? r0[W2 + c] : 0; }
-        }
-        if (VMAP && two) {
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const float4 vg = *reinterpret_cast<const float4*>(gain + m0 + r * W2);
-                gn[r][0] = vg.x; gn[r][1] = vg.y; gn[r][2] = vg.z; gn[r][3] = vg.w;
-                if (SHADE) {
-                    const float4 va = *reinterpret_cast<const float4*>(ma + m0 + r * W2), vb = *reinterpret_cast<const float4*>(mb + m0 + r * W2);
-                    ds[r][0] = va.x + vb.x * t; ds[r][1] = va.y + vb.y * t; ds[r][2] = va.z + vb.z * t; ds[r][3] = va.w + vb.w * t;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const bool ok = c < 2 || two;
-                    gn[r][c] = ok ? gain[m0 + r * W2 + c] : 1.f;
-                    if (SHADE) ds[r][c] = ok ? ma[m0 + r * W2 + c] + mb[m0 + r * W2 + c] * t : 0.f;
-                }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            float b0 = (float)q[p.oy[k]][p.ox[k]] - p.black[k], b1 = (float)q[p.oy[k]][2 + p.ox[k]] - p.black[k];
-            if (SHADE) { b0 = b0 - ds[p.oy[k]][p.ox[k]]; b1 = b1 - ds[p.oy[k]][2 + p.ox[k]]; }
-            const float v0 = (b0 * gn[p.oy[k]][p.ox[k]]) / p.denom[k];
-            const float v1 = (b1 * gn[p.oy[k]][2 + p.ox[k]]) / p.denom[k];
-            float* o = dst + (size_t)k * hw + (size_t)y * w + x;
-            float o0 = fminf(fmaxf(v0, 0.f), 1.f), o1 = fminf(fmaxf(v1, 0.f), 1.f);
-            if (scaled) { o0 = apply_ratio(o0, ratio); o1 = apply_ratio(o1, ratio); }
-            o[0] = o0;
-            if (two) o[1] = o1;
-        }
-    }
-}
-
-// one thread per packed element, as pack_raw_xtrans_kernel
-template <bool SHADE>
-__global__ __launch_bounds__(256) void pack_raw_xtrans_flat_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, int Hm, int Wm,
-                                                                   float black, float denom, const float* __restrict__ ratios,
-                                                                   const float* __restrict__ ma, const float* __restrict__ mb, float t,
-                                                                   const float* __restrict__ gain) {
-    const int n = blockIdx.y;
-    const bool scaled = ratios != nullptr;
-    const float ratio = scaled ? ratios[n] : 1.f;
-    const size_t hw = (size_t)h * w, total = 9 * hw;
-    const uint16_t* s = im + (size_t)n * Hm * Wm;
-    float* d = out + (size_t)n * total;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e / hw);
-        const int r = (int)(e - (size_t)c * hw);
-        const int i = r / w, j = r - i * w;
-        int row, col;
-        if (c < 5) { row = 6 * (i >> 1) + XT_RC[c][i & 1][j & 1][0]; col = 6 * (j >> 1) + XT_RC[c][i & 1][j & 1][1]; }
-        else { row = 3 * i + XT_RC3[c - 5][0]; col = 3 * j + XT_RC3[c - 5][1]; }
-        const size_t m = (size_t)row * Wm + col;
-        float b = (float)s[m] - black;
-        if (SHADE) b = b - (ma[m] + mb[m] * t);
-        const float v = (b * gain[m]) / denom;
-        const float o = fminf(fmaxf(v, 0.f), 1.f);
-        d[e] = scaled ? apply_ratio(o, ratio) : o;
-    }
-}
-
-// workgroups of a grid-stride pass over `units` lanes' worth of work: at most 8 per compute unit
-unsigned stride_grid(uint32_t units) {
-    const long long nb = ((long long)units + FF_T - 1) / FF_T, cap = 8ll * eld_num_cus();
-    return (unsigned)(nb < cap ? nb : cap);
-}
-
-bool bad_shape(int Hm, int Wm) { return Hm < 0 || Wm < 0 || Wm % 2 || (uint64_t)Hm * (uint64_t)Wm >= (1ull << 31); }
-
 template <int P>
 int box_launch(const uint32_t* S, const uint32_t* bad, int Hm, int Wm, int radius, uint64_t* Bsum, uint32_t* Bcnt, uint64_t* ws, hipStream_t st) {
     const int wpr = (Wm + 31) / 32;
@@ -400,7 +294,7 @@ extern "C" int eld_flat_sums_u16(const uint16_t* pool, size_t pool_elems, const 
     a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32; a.lpr = (Wm + FF_NPX - 1) / FF_NPX; a.F = F; a.white = white_level;
     a.vec_in = Wm % FF_NPX == 0 && !((uintptr_t)pool & 15u);
     a.vec_out = Wm % FF_NPX == 0 && !(((uintptr_t)S | (uintptr_t)D) & 15u);
-    ELD_LAUNCH(flat_sums_kernel, dim3(stride_grid((uint32_t)Hm * (uint32_t)a.lpr)), dim3(FF_T), 0, as_stream(stream), a);
+    ELD_LAUNCH(flat_sums_kernel, dim3(stride_grid((uint32_t)Hm * (uint32_t)a.lpr, FF_T)), dim3(FF_T), 0, as_stream(stream), a);
     ELD_LAUNCH_CHECK();
     return 0;
 }
@@ -442,7 +336,7 @@ extern "C" int eld_flat_apply_u16(const uint16_t* in, uint16_t* out, int N, int 
     for (int k = 0; k < 36; ++k) a.black[k] = k < period * period ? black[k] : 0.f;
     // Wm % 8 == 0 makes a frame a multiple of 16 bytes: every frame of an aligned stack is aligned
     const bool vec = Wm % FF_NPX == 0 && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)gain) & 15u);
-    const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr));
+    const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr, FF_T));
     if (period == 2) {
         if (vec) ELD_LAUNCH((flat_apply_kernel<2, true>), grid, dim3(FF_T), 0, as_stream(stream), a);
         else ELD_LAUNCH((flat_apply_kernel<2, false>), grid, dim3(FF_T), 0, as_stream(stream), a);
@@ -450,55 +344,6 @@ extern "C" int eld_flat_apply_u16(const uint16_t* in, uint16_t* out, int N, int 
         if (vec) ELD_LAUNCH((flat_apply_kernel<6, true>), grid, dim3(FF_T), 0, as_stream(stream), a);
         else ELD_LAUNCH((flat_apply_kernel<6, false>), grid, dim3(FF_T), 0, as_stream(stream), a);
     }
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int eld_pack_raw_bayer_u16_flat(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern,
-                                           const float* black_level, float white_point, const float* ratios, const float* ma, const float* mb,
-                                           float t, const float* gain, void* stream) {
-    if (N < 0 || h < 0 || w < 0 || !raw_pattern || !black_level) return ELD_EINVAL;
-    if (((uintptr_t)ma & 3u) || ((uintptr_t)mb & 3u) || ((uintptr_t)gain & 3u) || (ma == nullptr) != (mb == nullptr)) return ELD_EINVAL;
-    if (N == 0 || h == 0 || w == 0) return 0;
-    if (!mosaic || !packed || !gain) return ELD_EINVAL;
-    PackRawArgs p;
-    bool seen[4] = {false, false, false, false};
-    for (int i = 0; i < 4; ++i) {                                    // position of colour code k in the 2x2 cell, as eld_pack_raw_bayer_u16
-        const int k = raw_pattern[i];
-        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
-        seen[k] = true; p.oy[k] = i >> 1; p.ox[k] = i & 1;
-    }
-    for (int k = 0; k < 4; ++k) { p.black[k] = black_level[k]; p.denom[k] = white_point - black_level[k]; }
-    const size_t total = (size_t)h * ((w + 1) / 2);
-    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
-    // a lane's first site of a row is (2 y') * 2w + 4 x': a multiple of 4 sites when 2w is; N frames share the planes
-    const bool vmap = (2 * (size_t)w) % 4 == 0 && !(((uintptr_t)ma | (uintptr_t)mb | (uintptr_t)gain) & 15u);
-    const hipStream_t st = as_stream(stream);
-    if (ma) {
-        if (vmap) ELD_LAUNCH((pack_raw_flat_kernel<true, true>), grid, dim3(256), 0, st, mosaic, packed, h, w, p, ratios, ma, mb, t, gain);
-        else ELD_LAUNCH((pack_raw_flat_kernel<false, true>), grid, dim3(256), 0, st, mosaic, packed, h, w, p, ratios, ma, mb, t, gain);
-    } else {
-        if (vmap) ELD_LAUNCH((pack_raw_flat_kernel<true, false>), grid, dim3(256), 0, st, mosaic, packed, h, w, p, ratios, ma, mb, t, gain);
-        else ELD_LAUNCH((pack_raw_flat_kernel<false, false>), grid, dim3(256), 0, st, mosaic, packed, h, w, p, ratios, ma, mb, t, gain);
-    }
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int eld_pack_raw_xtrans_u16_flat(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
-                                            const float* ratios, const float* ma, const float* mb, float t, const float* gain, void* stream) {
-    if (N < 0 || Hm < 0 || Wm < 0 || !(white_point > black_level)) return ELD_EINVAL;
-    if (((uintptr_t)ma & 3u) || ((uintptr_t)mb & 3u) || ((uintptr_t)gain & 3u) || (ma == nullptr) != (mb == nullptr)) return ELD_EINVAL;
-    const int h = 2 * (Hm / 6), w = 2 * (Wm / 6);
-    const size_t total = (size_t)9 * h * w;
-    if (N == 0 || total == 0) return 0;
-    if (!mosaic || !packed || !gain) return ELD_EINVAL;
-    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
-    const hipStream_t st = as_stream(stream);
-    if (ma) ELD_LAUNCH(pack_raw_xtrans_flat_kernel<true>, grid, dim3(256), 0, st, mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level,
-                       ratios, ma, mb, t, gain);
-    else ELD_LAUNCH(pack_raw_xtrans_flat_kernel<false>, grid, dim3(256), 0, st, mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level,
-                    ratios, ma, mb, t, gain);
     ELD_LAUNCH_CHECK();
     return 0;
 }

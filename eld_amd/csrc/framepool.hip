@@ -206,12 +206,10 @@ extern "C" int eld_crop_pack_raw_bayer_u16(const uint16_t* pool, size_t pool_ele
                                            const EldCropRecord* recs, int B, int ph, int pw, const int* raw_pattern, const float* black_level,
                                            float white_point, uint16_t* out, void* stream) {
     if (!raw_pattern || !black_level || !crop_args_ok(pool, pool_elems, frames, F, max_h, max_w, recs, B, ph, pw, out)) return ELD_EINVAL;
+    if (!bayer_permutation(raw_pattern)) return ELD_EINVAL;
     CropBayerArgs a;
-    bool seen[4] = {false, false, false, false};
-    for (int i = 0; i < 4; ++i) {                                            // a permutation of 0..3, as eld_pack_raw_bayer_u16
+    for (int i = 0; i < 4; ++i) {
         const int k = raw_pattern[i];
-        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
-        seen[k] = true;
         if (!(black_level[k] >= 0.f) || !(white_point > black_level[k]) || !(white_point <= 65535.f)) return ELD_EINVAL;
         a.plane[i] = k; a.black[i] = black_level[k]; a.denom[i] = white_point - black_level[k];
     }

@@ -804,12 +804,9 @@ static int noise_forward(const void* in, int in_dtype, size_t in_image_stride, f
             if (!(dark->black_level[0] >= 0.f)) return ELD_EINVAL;
             a.dark_black[0] = dark->black_level[0];
         } else {
-            if (!dark->raw_pattern) return ELD_EINVAL;
-            bool seen[4] = {false, false, false, false};
-            for (int i = 0; i < 4; ++i) {                    // a permutation of 0..3, as eld_pack_raw_bayer_u16: cell position i holds plane k
+            if (!dark->raw_pattern || !bayer_permutation(dark->raw_pattern)) return ELD_EINVAL;
+            for (int i = 0; i < 4; ++i) {                    // cell position i holds plane k
                 const int k = dark->raw_pattern[i];
-                if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
-                seen[k] = true;
                 if (!(dark->black_level[k] >= 0.f)) return ELD_EINVAL;
                 a.dark_pos |= (uint32_t)i << (2 * k);
                 a.dark_black[k] = dark->black_level[k];
@@ -1008,135 +1005,7 @@ extern "C" int eld_unpack_xtrans(const float* packed, float* mosaic, int N, int 
     return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Sensor mosaic -> packed, normalised raw (pack_raw_bayer, dataset/sid_dataset.py:172-196), one pass:
-//   out[k][y][x] = clip((float(im[2y+oy_k][2x+ox_k]) - black[k]) / (white - black[k]), 0, 1),  k = R, G1, B, G2 = raw_pattern codes 0..3
-// float32 throughout as NumPy evaluates it (uint16 -> float32 exact, one rounding per op, true division).  2 B read + 4 B written
-// per sensor pixel.  A lane handles two horizontally adjacent packed positions of all four channels: one 8-byte read per mosaic row.
-// ---------------------------------------------------------------------------------------------
-// GAIN (eld_pack_raw_bayer_u16_gain, the evaluation input stage of dataset/sid_dataset.py:398-409): then min(max(v * ratio[n], 0), 1)
-// -- NumPy's np.maximum(np.minimum(v * np.float32(ratio), 1), 0), one float32 rounding for the product.
-struct PackRawArgs { int oy[4], ox[4]; float black[4], denom[4]; };
-
-__device__ __forceinline__ float apply_gain(float v, float ratio) { return fmaxf(fminf(v * ratio, 1.f), 0.f); }
-
-template <bool GAIN>
-__global__ __launch_bounds__(256) void pack_raw_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, PackRawArgs p,
-                                                       const float* __restrict__ ratios) {
-    const int n = blockIdx.y;
-    const float ratio = GAIN ? ratios[n] : 1.f;
-    const size_t hw = (size_t)h * w, W2 = 2 * (size_t)w;
-    const uint16_t* src = im + (size_t)n * 4 * hw;
-    float* dst = out + (size_t)n * 4 * hw;
-    const int wp = (w + 1) / 2;                                     // position pairs per packed row
-    const size_t total = (size_t)h * wp;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int y = (int)(i / wp), x = 2 * (int)(i - (size_t)y * wp);
-        const bool two = x + 1 < w;
-        uint16_t q[2][4];                                           // q[row][col] of the 2 x 4 mosaic block
-        const uint16_t* r0 = src + (size_t)(2 * y) * W2 + 2 * x;
-        if (two && ((W2 & 3) == 0)) {
-            const ushort4 a = *reinterpret_cast<const ushort4*>(r0), b = *reinterpret_cast<const ushort4*>(r0 + W2);
-            q[0][0] = a.x; q[0][1] = a.y; q[0][2] = a.z; q[0][3] = a.w; q[1][0] = b.x; q[1][1] = b.y; q[1][2] = b.z; q[1][3] = b.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { const bool ok = c < 2 || two; q[0][c] = ok ? r0[c] : 0; q[1][c] = ok ? r0[W2 + c] : 0; }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float v0 = ((float)q[p.oy[k]][p.ox[k]] - p.black[k]) / p.denom[k];
-            const float v1 = ((float)q[p.oy[k]][2 + p.ox[k]] - p.black[k]) / p.denom[k];
-            float* o = dst + (size_t)k * hw + (size_t)y * w + x;
-            float o0 = fminf(fmaxf(v0, 0.f), 1.f), o1 = fminf(fmaxf(v1, 0.f), 1.f);
-            if (GAIN) { o0 = apply_gain(o0, ratio); o1 = apply_gain(o1, ratio); }
-            o[0] = o0;
-            if (two) o[1] = o1;
-        }
-    }
-}
-
-static int pack_raw_bayer_launch(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
-                                 float white_point, const float* ratios, void* stream) {
-    if (N < 0 || h < 0 || w < 0 || !raw_pattern || !black_level) return ELD_EINVAL;
-    if (N == 0 || h == 0 || w == 0) return 0;
-    if (!mosaic || !packed) return ELD_EINVAL;
-    PackRawArgs p;
-    bool seen[4] = {false, false, false, false};
-    for (int i = 0; i < 4; ++i) {                                    // np.where(raw_pattern == k): position of colour code k in the 2x2 cell
-        const int k = raw_pattern[i];
-        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
-        seen[k] = true; p.oy[k] = i >> 1; p.ox[k] = i & 1;
-    }
-    for (int k = 0; k < 4; ++k) { p.black[k] = black_level[k]; p.denom[k] = white_point - black_level[k]; }
-    const size_t total = (size_t)h * ((w + 1) / 2);
-    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
-    if (ratios) ELD_LAUNCH(pack_raw_kernel<true>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, p, ratios);
-    else ELD_LAUNCH(pack_raw_kernel<false>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, p, ratios);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int eld_pack_raw_bayer_u16(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
-                                      float white_point, void* stream) {
-    return pack_raw_bayer_launch(mosaic, packed, N, h, w, raw_pattern, black_level, white_point, nullptr, stream);
-}
-
-extern "C" int eld_pack_raw_bayer_u16_gain(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern, const float* black_level,
-                                           float white_point, const float* ratios, void* stream) {
-    if (N > 0 && h > 0 && w > 0 && !ratios) return ELD_EINVAL;
-    return pack_raw_bayer_launch(mosaic, packed, N, h, w, raw_pattern, black_level, white_point, ratios, stream);
-}
-
-// ---------------------------------------------------------------------------------------------
-// X-Trans sensor mosaic -> packed, normalised raw (the X-Trans branch of the dataset pack, dataset/sid_dataset.py:199-239), one pass:
-//   out[c][i][j] = clip((float(im[row][col]) - black) / (white - black), 0, 1),  (row, col) = xtrans_kernel's index map of (c, i, j)
-// float32 as NumPy evaluates it (uint16 -> float32 exact, one rounding per op, true division): bit-exact.  One thread per packed element.
-// ---------------------------------------------------------------------------------------------
-template <bool GAIN>
-__global__ __launch_bounds__(256) void pack_raw_xtrans_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, int Hm, int Wm,
-                                                              float black, float denom, const float* __restrict__ ratios) {
-    const int n = blockIdx.y;
-    const float ratio = GAIN ? ratios[n] : 1.f;
-    const size_t hw = (size_t)h * w, total = 9 * hw;
-    const uint16_t* s = im + (size_t)n * Hm * Wm;
-    float* d = out + (size_t)n * total;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e / hw);
-        const int r = (int)(e - (size_t)c * hw);
-        const int i = r / w, j = r - i * w;
-        int row, col;
-        if (c < 5) { row = 6 * (i >> 1) + XT_RC[c][i & 1][j & 1][0]; col = 6 * (j >> 1) + XT_RC[c][i & 1][j & 1][1]; }
-        else { row = 3 * i + XT_RC3[c - 5][0]; col = 3 * j + XT_RC3[c - 5][1]; }
-        const float v = ((float)s[(size_t)row * Wm + col] - black) / denom;
-        const float o = fminf(fmaxf(v, 0.f), 1.f);
-        d[e] = GAIN ? apply_gain(o, ratio) : o;
-    }
-}
-
-static int pack_raw_xtrans_launch(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
-                                  const float* ratios, void* stream) {
-    if (N < 0 || Hm < 0 || Wm < 0 || !(white_point > black_level)) return ELD_EINVAL;
-    const int h = 2 * (Hm / 6), w = 2 * (Wm / 6);
-    const size_t total = (size_t)9 * h * w;
-    if (N == 0 || total == 0) return 0;
-    if (!mosaic || !packed) return ELD_EINVAL;
-    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
-    if (ratios) ELD_LAUNCH(pack_raw_xtrans_kernel<true>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level, ratios);
-    else ELD_LAUNCH(pack_raw_xtrans_kernel<false>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level, ratios);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-// uint16 mosaic [N, Hm, Wm] -> packed float32 [N, 9, 2*(Hm/6), 2*(Wm/6)] (sides truncated to whole 6x6 cells, as eld_pack_xtrans)
-extern "C" int eld_pack_raw_xtrans_u16(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point, void* stream) {
-    return pack_raw_xtrans_launch(mosaic, packed, N, Hm, Wm, black_level, white_point, nullptr, stream);
-}
-
-extern "C" int eld_pack_raw_xtrans_u16_gain(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
-                                            const float* ratios, void* stream) {
-    if (N > 0 && Hm >= 6 && Wm >= 6 && !ratios) return ELD_EINVAL;
-    return pack_raw_xtrans_launch(mosaic, packed, N, Hm, Wm, black_level, white_point, ratios, stream);
-}
+// Sensor mosaic -> packed, normalised raw (eld_pack_raw_{bayer,xtrans}_u16 and _gain): pack_raw.hip.
 
 // ---------------------------------------------------------------------------------------------
 // Write-back: packed network output -> uint16 sensor codes (the mosaic half of postprocess_bayer / postprocess_xtrans,
@@ -1220,13 +1089,7 @@ static void unpack_raw_bayer_dispatch(bool vec, dim3 grid, hipStream_t st, const
 
 extern "C" int eld_unpack_raw_bayer_u16(const float* packed, uint16_t* mosaic, int N, int h, int w, const int* raw_pattern, const float* black_level,
                                         float white_point, int rounding, void* stream) {
-    if (N < 0 || h < 0 || w < 0 || !raw_pattern || !black_level) return ELD_EINVAL;
-    bool seen[4] = {false, false, false, false};
-    for (int i = 0; i < 4; ++i) {                                    // a permutation of 0..3, as eld_pack_raw_bayer_u16
-        const int k = raw_pattern[i];
-        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
-        seen[k] = true;
-    }
+    if (N < 0 || h < 0 || w < 0 || !raw_pattern || !black_level || !bayer_permutation(raw_pattern)) return ELD_EINVAL;
     WriteBackArgs a;
     if (!writeback_args(a, black_level, raw_pattern, white_point, rounding)) return ELD_EINVAL;
     if (N == 0 || h == 0 || w == 0) return 0;

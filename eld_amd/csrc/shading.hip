@@ -3,8 +3,7 @@
 //
 //   eld_shading_fit_u16                bias frames of S sessions in a frame pool -> two float32 planes a, b [Hm,Wm]
 //   eld_shading_apply_u16              uint16 codes [N,Hm,Wm] -> clamp(u - rint(a + b t), 0, 65535)
-//   eld_pack_raw_bayer_u16_shaded      eld_pack_raw_bayer_u16_gain with ((u - black) - (a + b t)) / denom
-//   eld_pack_raw_xtrans_u16_shaded     eld_pack_raw_xtrans_u16_gain likewise
+// The input stage that subtracts the maps in float32 (eld_pack_raw_*_u16_shaded) is in pack_raw.hip.
 // Every output is a function of its own site: no atomics, no cross-lane sums, and the order of the floating-point operations is the one the
 // header states, so two calls give the same bits and tests/shading_ref.py restates them operation for operation.  The library is built
 // with -ffp-contract=off; the pragma below says so for this file whatever the flags.
@@ -14,7 +13,6 @@
 // bitmap lie in one word.  The fit walks the frames of a session four at a time (four loads in flight per lane), keeps eight uint32 sums
 // for the session in turn and folds them into the float64 pair (A, B) before the next session starts.  Grids are sized from eld_num_cus().
 #include "common.h"
-#include "xtrans.h"
 
 #pragma clang fp contract(off)
 
@@ -207,97 +205,6 @@ __global__ __launch_bounds__(SH_T) void shading_apply_kernel(ApplyArgs a) {
     }
 }
 
-// ---- the inference input stage with the subtraction fused: pack_raw_kernel<GAIN = true> / pack_raw_xtrans_kernel<GAIN = true> of noise.hip
-// with the map subtracted between the black level and the division.  a = b = +0.0 gives their bits: v - 0.0 = v.
-struct PackRawArgs { int oy[4], ox[4]; float black[4], denom[4]; };
-
-__device__ __forceinline__ float apply_gain(float v, float ratio) { return fmaxf(fminf(v * ratio, 1.f), 0.f); }
-
-// A lane handles two horizontally adjacent packed positions of all four planes: per mosaic row one 8-byte read of codes and one 16-byte
-// read of each map plane (VMAP: the planes are 16-byte aligned and the row pitch is a multiple of 4 sites).
-template <bool VMAP>
-__global__ __launch_bounds__(256) void pack_raw_shaded_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, PackRawArgs p,
-                                                              const float* __restrict__ ratios, const float* __restrict__ ma,
-                                                              const float* __restrict__ mb, float t) {
-    const int n = blockIdx.y;
-    const float ratio = ratios[n];
-    const size_t hw = (size_t)h * w, W2 = 2 * (size_t)w;
-    const uint16_t* src = im + (size_t)n * 4 * hw;
-    float* dst = out + (size_t)n * 4 * hw;
-    const int wp = (w + 1) / 2;                                     // position pairs per packed row
-    const size_t total = (size_t)h * wp;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-        const int y = (int)(i / wp), x = 2 * (int)(i - (size_t)y * wp);
-        const bool two = x + 1 < w;
-        uint16_t q[2][4];                                           // q[row][col] of the 2 x 4 mosaic block
-        float ds[2][4];                                             // a + b t of the same sites
-        const size_t m0 = (size_t)(2 * y) * W2 + 2 * x;
-        const uint16_t* r0 = src + m0;
-        if (two && ((W2 & 3) == 0)) {
-            const ushort4 a = *reinterpret_cast<const ushort4*>(r0), b = *reinterpret_cast<const ushort4*>(r0 + W2);
-            q[0][0] = a.x; q[0][1] = a.y; q[0][2] = a.z; q[0][3] = a.w; q[1][0] = b.x; q[1][1] = b.y; q[1][2] = b.z; q[1][3] = b.w;
-        } else {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) { const bool ok = c < 2 || two; q[0][c] = ok ? r0[c] : 0; q[1][c] = ok ? r0[W2 + c] : 0; }
-        }
-        if (VMAP && two) {
-#pragma unroll
-            for (int r = 0; r < 2; ++r) {
-                const float4 va = *reinterpret_cast<const float4*>(ma + m0 + r * W2), vb = *reinterpret_cast<const float4*>(mb + m0 + r * W2);
-                ds[r][0] = va.x + vb.x * t; ds[r][1] = va.y + vb.y * t; ds[r][2] = va.z + vb.z * t; ds[r][3] = va.w + vb.w * t;
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 2; ++r)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const bool ok = c < 2 || two;
-                    ds[r][c] = ok ? ma[m0 + r * W2 + c] + mb[m0 + r * W2 + c] * t : 0.f;
-                }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const float v0 = (((float)q[p.oy[k]][p.ox[k]] - p.black[k]) - ds[p.oy[k]][p.ox[k]]) / p.denom[k];
-            const float v1 = (((float)q[p.oy[k]][2 + p.ox[k]] - p.black[k]) - ds[p.oy[k]][2 + p.ox[k]]) / p.denom[k];
-            float* o = dst + (size_t)k * hw + (size_t)y * w + x;
-            const float o0 = apply_gain(fminf(fmaxf(v0, 0.f), 1.f), ratio), o1 = apply_gain(fminf(fmaxf(v1, 0.f), 1.f), ratio);
-            o[0] = o0;
-            if (two) o[1] = o1;
-        }
-    }
-}
-
-// one thread per packed element, as pack_raw_xtrans_kernel
-__global__ __launch_bounds__(256) void pack_raw_xtrans_shaded_kernel(const uint16_t* __restrict__ im, float* __restrict__ out, int h, int w, int Hm, int Wm,
-                                                                     float black, float denom, const float* __restrict__ ratios,
-                                                                     const float* __restrict__ ma, const float* __restrict__ mb, float t) {
-    const int n = blockIdx.y;
-    const float ratio = ratios[n];
-    const size_t hw = (size_t)h * w, total = 9 * hw;
-    const uint16_t* s = im + (size_t)n * Hm * Wm;
-    float* d = out + (size_t)n * total;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (size_t)gridDim.x * 256) {
-        const int c = (int)(e / hw);
-        const int r = (int)(e - (size_t)c * hw);
-        const int i = r / w, j = r - i * w;
-        int row, col;
-        if (c < 5) { row = 6 * (i >> 1) + XT_RC[c][i & 1][j & 1][0]; col = 6 * (j >> 1) + XT_RC[c][i & 1][j & 1][1]; }
-        else { row = 3 * i + XT_RC3[c - 5][0]; col = 3 * j + XT_RC3[c - 5][1]; }
-        const size_t m = (size_t)row * Wm + col;
-        const float ds = ma[m] + mb[m] * t;
-        const float v = (((float)s[m] - black) - ds) / denom;
-        d[e] = apply_gain(fminf(fmaxf(v, 0.f), 1.f), ratio);
-    }
-}
-
-// workgroups of a grid-stride pass over `units` lanes' worth of work: at most 8 per compute unit
-unsigned stride_grid(uint32_t units) {
-    const long long nb = ((long long)units + SH_T - 1) / SH_T, cap = 8ll * eld_num_cus();
-    return (unsigned)(nb < cap ? nb : cap);
-}
-
-bool bad_shape(int Hm, int Wm) { return Hm < 0 || Wm < 0 || Wm % 2 || (uint64_t)Hm * (uint64_t)Wm >= (1ull << 31); }
-
 }  // namespace
 
 extern "C" int eld_shading_fit_u16(const uint16_t* pool, size_t pool_elems, const EldPoolFrame* frames, int F, int Hm, int Wm, const int32_t* sessions,
@@ -324,7 +231,7 @@ extern "C" int eld_shading_fit_u16(const uint16_t* pool, size_t pool_elems, cons
         a.alpha[s] = s < S ? alpha[s] : 0.0; a.beta[s] = s < S ? beta[s] : 0.0;
     }
     for (int k = 0; k < 36; ++k) a.cen[k] = k < period * period ? centre[k] : 0;
-    const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr));
+    const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr, SH_T));
     if (period == 2) ELD_LAUNCH(shading_fit_kernel<2>, grid, dim3(SH_T), 0, as_stream(stream), a);
     else ELD_LAUNCH(shading_fit_kernel<6>, grid, dim3(SH_T), 0, as_stream(stream), a);
     ELD_LAUNCH_CHECK();
@@ -342,49 +249,9 @@ extern "C" int eld_shading_apply_u16(const uint16_t* in, uint16_t* out, int N, i
     a.N = N; a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32; a.lpr = (Wm + SH_NPX - 1) / SH_NPX;
     // Wm % 8 == 0 makes a frame a multiple of 16 bytes: every frame of an aligned stack is aligned
     const bool vec = Wm % SH_NPX == 0 && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)ma | (uintptr_t)mb) & 15u);
-    const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr));
+    const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr, SH_T));
     if (vec) ELD_LAUNCH(shading_apply_kernel<true>, grid, dim3(SH_T), 0, as_stream(stream), a);
     else ELD_LAUNCH(shading_apply_kernel<false>, grid, dim3(SH_T), 0, as_stream(stream), a);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int eld_pack_raw_bayer_u16_shaded(const uint16_t* mosaic, float* packed, int N, int h, int w, const int* raw_pattern,
-                                             const float* black_level, float white_point, const float* ratios, const float* ma, const float* mb,
-                                             float t, void* stream) {
-    if (N < 0 || h < 0 || w < 0 || !raw_pattern || !black_level) return ELD_EINVAL;
-    if (((uintptr_t)ma & 3u) || ((uintptr_t)mb & 3u)) return ELD_EINVAL;
-    if (N == 0 || h == 0 || w == 0) return 0;
-    if (!mosaic || !packed || !ratios || !ma || !mb) return ELD_EINVAL;
-    PackRawArgs p;
-    bool seen[4] = {false, false, false, false};
-    for (int i = 0; i < 4; ++i) {                                    // position of colour code k in the 2x2 cell, as eld_pack_raw_bayer_u16
-        const int k = raw_pattern[i];
-        if (k < 0 || k > 3 || seen[k]) return ELD_EINVAL;
-        seen[k] = true; p.oy[k] = i >> 1; p.ox[k] = i & 1;
-    }
-    for (int k = 0; k < 4; ++k) { p.black[k] = black_level[k]; p.denom[k] = white_point - black_level[k]; }
-    const size_t total = (size_t)h * ((w + 1) / 2);
-    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
-    // a lane's first site of a row is (2 y') * 2w + 4 x': a multiple of 4 sites when 2w is; N frames share the one map
-    const bool vmap = (2 * (size_t)w) % 4 == 0 && !(((uintptr_t)ma | (uintptr_t)mb) & 15u);
-    if (vmap) ELD_LAUNCH(pack_raw_shaded_kernel<true>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, p, ratios, ma, mb, t);
-    else ELD_LAUNCH(pack_raw_shaded_kernel<false>, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, p, ratios, ma, mb, t);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int eld_pack_raw_xtrans_u16_shaded(const uint16_t* mosaic, float* packed, int N, int Hm, int Wm, float black_level, float white_point,
-                                              const float* ratios, const float* ma, const float* mb, float t, void* stream) {
-    if (N < 0 || Hm < 0 || Wm < 0 || !(white_point > black_level)) return ELD_EINVAL;
-    if (((uintptr_t)ma & 3u) || ((uintptr_t)mb & 3u)) return ELD_EINVAL;
-    const int h = 2 * (Hm / 6), w = 2 * (Wm / 6);
-    const size_t total = (size_t)9 * h * w;
-    if (N == 0 || total == 0) return 0;
-    if (!mosaic || !packed || !ratios || !ma || !mb) return ELD_EINVAL;
-    dim3 grid((unsigned)min((total + 255) / 256, (size_t)4096), N);
-    ELD_LAUNCH(pack_raw_xtrans_shaded_kernel, grid, dim3(256), 0, as_stream(stream), mosaic, packed, h, w, Hm, Wm, black_level, white_point - black_level,
-               ratios, ma, mb, t);
     ELD_LAUNCH_CHECK();
     return 0;
 }

@@ -206,42 +206,24 @@ def pack_input(t, cfa, raw_pattern, black_level, white_point, ratios, shading=No
     import torch
     N, Hm, Wm = t.shape
     r = torch.as_tensor(np.asarray(ratios, np.float32), device=t.device)
-    if flatfield is not None:
-        ma, mb = shading.on(t.device) if shading is not None else (None, None)
-        tv = float(tval) if shading is not None else 0.0
-        gain = flatfield.on(t.device, 'prnu')
-        if cfa == 'bayer':
-            out = torch.empty((N, 4, Hm // 2, Wm // 2), dtype=torch.float32, device=t.device)
-            L.check(L.lib().eld_pack_raw_bayer_u16_flat(L.dptr(t), L.dptr(out), N, Hm // 2, Wm // 2, (ctypes.c_int * 4)(*raw_pattern),
-                                                        (ctypes.c_float * 4)(*black_level), float(white_point), L.dptr(r), L.dptr(ma), L.dptr(mb), tv,
-                                                        L.dptr(gain), L.cur_stream()), 'eld_pack_raw_bayer_u16_flat')
-        else:
-            out = torch.empty((N, 9, 2 * (Hm // 6), 2 * (Wm // 6)), dtype=torch.float32, device=t.device)
-            L.check(L.lib().eld_pack_raw_xtrans_u16_flat(L.dptr(t), L.dptr(out), N, Hm, Wm, float(black_level[0]), float(white_point), L.dptr(r),
-                                                         L.dptr(ma), L.dptr(mb), tv, L.dptr(gain), L.cur_stream()), 'eld_pack_raw_xtrans_u16_flat')
-        return out
-    if shading is not None:
-        ma, mb = shading.on(t.device)
-        if cfa == 'bayer':
-            out = torch.empty((N, 4, Hm // 2, Wm // 2), dtype=torch.float32, device=t.device)
-            L.check(L.lib().eld_pack_raw_bayer_u16_shaded(L.dptr(t), L.dptr(out), N, Hm // 2, Wm // 2, (ctypes.c_int * 4)(*raw_pattern),
-                                                          (ctypes.c_float * 4)(*black_level), float(white_point), L.dptr(r), L.dptr(ma), L.dptr(mb),
-                                                          float(tval), L.cur_stream()), 'eld_pack_raw_bayer_u16_shaded')
-        else:
-            out = torch.empty((N, 9, 2 * (Hm // 6), 2 * (Wm // 6)), dtype=torch.float32, device=t.device)
-            L.check(L.lib().eld_pack_raw_xtrans_u16_shaded(L.dptr(t), L.dptr(out), N, Hm, Wm, float(black_level[0]), float(white_point), L.dptr(r),
-                                                           L.dptr(ma), L.dptr(mb), float(tval), L.cur_stream()), 'eld_pack_raw_xtrans_u16_shaded')
-        return out
     if cfa == 'bayer':
         out = torch.empty((N, 4, Hm // 2, Wm // 2), dtype=torch.float32, device=t.device)
-        pat = (ctypes.c_int * 4)(*raw_pattern)
-        blk = (ctypes.c_float * 4)(*black_level)
-        L.check(L.lib().eld_pack_raw_bayer_u16_gain(L.dptr(t), L.dptr(out), N, Hm // 2, Wm // 2, pat, blk, float(white_point), L.dptr(r),
-                                                    L.cur_stream()), 'eld_pack_raw_bayer_u16_gain')
+        stem = 'eld_pack_raw_bayer_u16'
+        head = (L.dptr(t), L.dptr(out), N, Hm // 2, Wm // 2, (ctypes.c_int * 4)(*raw_pattern), (ctypes.c_float * 4)(*black_level),
+                float(white_point), L.dptr(r))
     else:
         out = torch.empty((N, 9, 2 * (Hm // 6), 2 * (Wm // 6)), dtype=torch.float32, device=t.device)
-        L.check(L.lib().eld_pack_raw_xtrans_u16_gain(L.dptr(t), L.dptr(out), N, Hm, Wm, float(black_level[0]), float(white_point), L.dptr(r),
-                                                     L.cur_stream()), 'eld_pack_raw_xtrans_u16_gain')
+        stem = 'eld_pack_raw_xtrans_u16'
+        head = (L.dptr(t), L.dptr(out), N, Hm, Wm, float(black_level[0]), float(white_point), L.dptr(r))
+    ma, mb = shading.on(t.device) if shading is not None else (None, None)
+    if flatfield is not None:
+        gain = flatfield.on(t.device, 'prnu')
+        name, planes = stem + '_flat', (L.dptr(ma), L.dptr(mb), float(tval) if shading is not None else 0.0, L.dptr(gain))
+    elif shading is not None:
+        name, planes = stem + '_shaded', (L.dptr(ma), L.dptr(mb), float(tval))
+    else:
+        name, planes = stem + '_gain', ()
+    L.check(getattr(L.lib(), name)(*head, *planes, L.cur_stream()), name)
     return out
 
 

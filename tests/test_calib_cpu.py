@@ -286,3 +286,11 @@ def test_misaligned_mosaics_are_refused_by_the_abi(eld_lib):
         assert eld_lib.eld_calib_bias_residual(p, 1, 2, 4, pat, blk, out, out, out, None) == rc
     assert eld_lib.eld_calib_bias_residual(ctypes.c_void_p(0x30000), 1, 2, 4, pat, blk, out, out, ctypes.c_void_p(0x20004), None) == -1
     assert eld_lib.eld_calib_bias_stats(ctypes.c_void_p(0x30000), 1, 2, 4, pat, out, out, ws, 8, None) == -3   # aligned: on to ELD_EWS
+    # a raw_pattern that is no permutation of 0..3 (a repeated code, a code out of range, none at all): refused, aligned or not, empty or not
+    u = ctypes.c_void_p(0x30000)
+    for bad in ((ctypes.c_int * 4)(0, 1, 1, 2), (ctypes.c_int * 4)(0, 1, 4, 2), (ctypes.c_int * 4)(0, -1, 3, 2), None):
+        for F in (1, 0):
+            assert eld_lib.eld_calib_bias_stats(u, F, 2, 4, bad, out, out, ws, 1 << 20, None) == -1
+            assert eld_lib.eld_calib_flat_stats(u, F, 2, 4, bad, 16383, out, ws, 1 << 20, None) == -1
+            assert eld_lib.eld_calib_bias_residual(u, F, 2, 4, bad, blk, out, out, out, None) == -1
+    assert eld_lib.eld_calib_bias_stats(u, 0, 2, 4, pat, out, out, ws, 1 << 20, None) == 0

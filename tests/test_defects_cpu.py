@@ -153,6 +153,13 @@ def test_find_defects_and_repair_argument_errors(eld_lib):
         DF.repair(u, 'map.npz')
     with pytest.raises(ValueError, match='out='):
         DF.repair(u, m, out=u.copy())
+    # the raw binding refuses a Bayer pattern that is no permutation of 0..3 before any launch: every other argument is in order, and the
+    # pointers are never dereferenced
+    import ctypes
+    p = ctypes.c_void_p(0x10000)
+    for bad in ((ctypes.c_int * 4)(0, 1, 1, 2), (ctypes.c_int * 4)(0, 1, 4, 2), (ctypes.c_int * 4)(0, -1, 3, 2), None):
+        assert eld_lib.eld_defect_deviation(p, 2, 8, 12, 2, bad, p, p, 1 << 20, None) == -1
+        assert eld_lib.eld_defect_repair_u16(p, p, 2, 8, 12, 2, bad, p, None) == -1
 
 
 def test_pipeline_argument_errors(eld_lib, tmp_path):

@@ -149,6 +149,17 @@ def test_argument_errors(kw, msg):
         denoise_raw(d, m, cfa, **kw)
 
 
+def test_write_back_refuses_a_bad_pattern_before_any_launch(eld_lib):
+    """eld_unpack_raw_bayer_u16 through the raw binding: a raw_pattern that is no permutation of 0..3 is ELD_EINVAL, decided on the host (the
+    pointers are never dereferenced), even for an empty call; with a good pattern the empty call returns 0."""
+    import ctypes
+    p, blk = ctypes.c_void_p(0x10000), (ctypes.c_float * 4)(512, 512, 512, 512)
+    for bad in ((ctypes.c_int * 4)(0, 1, 1, 2), (ctypes.c_int * 4)(0, 1, 4, 2), (ctypes.c_int * 4)(0, -1, 3, 2), None):
+        for N in (1, 0):
+            assert eld_lib.eld_unpack_raw_bayer_u16(p, p, N, 2, 4, bad, blk, 16383.0, 1, None) == -1
+    assert eld_lib.eld_unpack_raw_bayer_u16(p, p, 0, 2, 4, (ctypes.c_int * 4)(0, 1, 3, 2), blk, 16383.0, 1, None) == 0
+
+
 def test_wb_normalisation():
     from eld_amd.denoise import _colour
     w, m = _colour('bayer', [2000.0, 1000.0, 1500.0, 1000.0], np.eye(3), 2)        # rawpy camera_whitebalance: wb /= wb[1]

@@ -313,3 +313,12 @@ def test_entry_points_refuse_bad_arguments_without_a_device(eld_lib):
     assert lib.eld_pack_raw_xtrans_u16_shaded(ok, ok, 1, 6, 6, 1024.0, 16383.0, ok, ok, None, 1.0, None) == -1
     assert lib.eld_pack_raw_xtrans_u16_shaded(ok, ok, 1, 6, 6, 1024.0, 1024.0, ok, ok, ok, 1.0, None) == -1
     assert lib.eld_pack_raw_xtrans_u16_shaded(None, None, 1, 5, 6, 1024.0, 16383.0, None, None, None, 1.0, None) == 0
+    # the four Bayer entry points of the input stage share one pattern check: a repeated code, a code out of range and no pattern at all are
+    # refused; the first two only where there is work (an empty call returns 0 before the pattern is read), the last always
+    for bad in ((ctypes.c_int * 4)(0, 1, 1, 2), (ctypes.c_int * 4)(0, 1, 4, 2), (ctypes.c_int * 4)(0, -1, 3, 2), None):
+        for N in (1, 0):
+            want = 0 if (N == 0 and bad is not None) else -1
+            assert lib.eld_pack_raw_bayer_u16(ok, ok, N, 2, 4, bad, blk, 16383.0, None) == want
+            assert lib.eld_pack_raw_bayer_u16_gain(ok, ok, N, 2, 4, bad, blk, 16383.0, ok, None) == want
+            assert lib.eld_pack_raw_bayer_u16_shaded(ok, ok, N, 2, 4, bad, blk, 16383.0, ok, ok, ok, 1.0, None) == want
+            assert lib.eld_pack_raw_bayer_u16_flat(ok, ok, N, 2, 4, bad, blk, 16383.0, ok, ok, ok, 1.0, ok, None) == want

@@ -223,6 +223,46 @@ def test_shaded_bayer_pack(eld_lib, dev, pattern, hw, N):
     assert _same_bits(shaded(z, z), plain.cpu().numpy())
 
 
+def _off_by_a_float(arr, dev):
+    """`arr` on the device, 4 bytes past a 16-byte boundary."""
+    import torch
+    store = torch.zeros(arr.size + 1, dtype=torch.float32, device=dev)
+    store[1:] = torch.from_numpy(arr.reshape(-1)).to(dev)
+    t = store[1:].view(arr.shape)
+    assert t.data_ptr() % 16 == 4
+    return t
+
+
+@pytest.mark.parametrize('pattern', PATTERNS)
+def test_shaded_bayer_pack_with_planes_off_the_16_byte_grid(eld_lib, dev, pattern):
+    """A row pitch that allows the 8-byte code reads (2w % 4 == 0) with map planes that forbid the 16-byte plane reads: the same bits as
+    the restatement and as the call on aligned planes."""
+    import torch
+    from eld_amd import _lib as L
+    h, w, N = 3, 4, 2
+    rng = np.random.default_rng(23)
+    u = _codes(rng, (N, 2 * h, 2 * w), 400, 3000)
+    a = (3 * rng.standard_normal((2 * h, 2 * w))).astype(np.float32)
+    b = (rng.standard_normal((2 * h, 2 * w)) / 500).astype(np.float32)
+    black, white, ratios, t = [512.0, 510.0, 515.0, 512.0], 16383.0, np.array([100.0, 250.0], np.float32), np.float32(-733.5)
+    ut, rt = torch.from_numpy(u.view(np.int16)).to(dev), torch.from_numpy(ratios).to(dev)
+    pat, blk = (ctypes.c_int * 4)(*np.asarray(pattern).reshape(-1).tolist()), (ctypes.c_float * 4)(*black)
+
+    def shaded(at, bt):
+        out = torch.full((N, 4, h, w), float('nan'), dtype=torch.float32, device=dev)
+        assert eld_lib.eld_pack_raw_bayer_u16_shaded(L.dptr(ut), L.dptr(out), N, h, w, pat, blk, white, L.dptr(rt), L.dptr(at), L.dptr(bt), float(t),
+                                                     L.cur_stream()) == 0
+        return out.cpu().numpy()
+    at, bt = torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev)
+    assert at.data_ptr() % 16 == 0 and bt.data_ptr() % 16 == 0
+    want = R.pack_bayer_shaded(u, pattern, black, white, ratios, a, b, t)
+    aligned = shaded(at, bt)
+    assert _same_bits(aligned, want)
+    for planes in ((_off_by_a_float(a, dev), _off_by_a_float(b, dev)), (_off_by_a_float(a, dev), bt), (at, _off_by_a_float(b, dev))):
+        got = shaded(*planes)
+        assert _same_bits(got, want) and _same_bits(got, aligned)
+
+
 @pytest.mark.parametrize('shape', [(6, 6), (12, 18), (14, 20)])
 @pytest.mark.parametrize('N', [1, 2])
 def test_shaded_xtrans_pack(eld_lib, dev, shape, N):
@@ -300,7 +340,7 @@ def test_einval_before_any_launch(eld_lib, dev):
         return eld_lib.eld_pack_raw_bayer_u16_shaded(m, o, N, 2, 4, pat_, blk_, 16383.0, r_, a_, b_, 1.0, s)
     assert pb() == 0 and pb(N=0) == 0
     for kw in (dict(m=None), dict(o=None), dict(r_=None), dict(a_=None), dict(b_=None), dict(pat_=None), dict(blk_=None), dict(N=-1),
-               dict(pat_=(ctypes.c_int * 4)(0, 1, 1, 2))):
+               dict(pat_=(ctypes.c_int * 4)(0, 1, 1, 2)), dict(pat_=(ctypes.c_int * 4)(0, 1, 4, 2))):
         assert pb(**kw) == EINVAL, kw
     x = torch.zeros((1, 6, 6), dtype=torch.int16, device=dev)
     xa = torch.zeros((6, 6), dtype=torch.float32, device=dev)
