@@ -33,6 +33,16 @@ assert NOISE_PARAMS_DTYPE.itemsize == 64
 POOL_FRAME_DTYPE = np.dtype([('offset', '<u8'), ('Hm', '<i4'), ('Wm', '<i4')])
 CROP_RECORD_DTYPE = np.dtype([('frame', '<i4'), ('y0', '<i4'), ('x0', '<i4'), ('ratio', '<f4')])
 assert POOL_FRAME_DTYPE.itemsize == 16 and CROP_RECORD_DTYPE.itemsize == 16
+# numpy mirrors of struct EldDngStream (64 bytes) and struct EldDngHuff (1196 bytes); the status words of the two DNG decoders
+DNG_STREAM_DTYPE = np.dtype([('data_off', '<u4'), ('data_len', '<u4'), ('x0', '<i4'), ('y0', '<i4'), ('tw', '<i4'), ('th', '<i4'), ('P', '<i4'),
+                             ('X', '<i4'), ('Y', '<i4'), ('Nf', '<i4'), ('pred', '<i4'), ('table', '<u2', (4,)), ('ws_off', '<u4'),
+                             ('reserved', '<u4', (2,))])
+DNG_FAST_BITS = 9
+DNG_HUFF_DTYPE = np.dtype([('fast', '<u2', (1 << DNG_FAST_BITS,)), ('maxcode', '<i4', (17,)), ('valoff', '<i4', (17,)), ('vals', 'u1', (32,)),
+                           ('nvals', '<i4')])
+assert DNG_STREAM_DTYPE.itemsize == 64 and DNG_HUFF_DTYPE.itemsize == 1196
+DNG_STATUS = {0: 'ok', 1: 'truncated: the data ended before the last sample', 2: 'invalid code: bits that are no code of the Huffman table',
+              3: 'too many samples: the stream holds more samples than its tile', 4: 'bad record: a field out of range'}
 
 _vp, _i, _u32, _u64, _f, _d, _sz = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_float, C.c_double, C.c_size_t
 
@@ -164,6 +174,8 @@ SIGNATURES = {
     'eld_bm3d_vst_workspace_bytes': (_sz, [_i, _i, _i, _i]),
     'eld_bm3d_vst_f32': (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _i, _i, _i, _u32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), _i, _vp, _vp,
                               _sz, _vp]),
+    'eld_dng_unpack_u16': (_i, [_vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
+    'eld_dng_ljpeg_u16': (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _i, _vp, _vp, _vp]),
 }
 
 

@@ -429,9 +429,10 @@ def load_burst(patterns):
         if not hit:
             raise ValueError('no such file: %s' % pat)
         names.extend(hit)
+    from .dng import load_frame
     frames = []
     for nme in names:
-        a = np.load(nme)
+        a = load_frame(nme)
         if a.dtype != np.uint16 or a.ndim not in (2, 3):
             raise ValueError('%s: a uint16 mosaic (Hm, Wm) or stack (n, Hm, Wm) expected, got %s %s' % (nme, a.dtype, a.shape))
         frames.extend(list(a) if a.ndim == 3 else [a])
@@ -472,6 +473,8 @@ def main(argv=None):
     o = read_sidecar(a.meta) if a.meta else {}
     if a.defects is not None:
         o['defects'] = a.defects
+    from .dng import fill_from_tags
+    fill_from_tags(o, [n for pat in a.inputs for n in sorted(glob.glob(pat))])        # below the sidecar, above the defaults
     if (a.disp or a.ref) and not a.align:
         raise SystemExit('--ref and --disp go with --align')
     stack, res = run(load_burst(a.inputs), o, a.k, a.min_dev, a.align, a.ref)

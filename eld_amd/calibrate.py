@@ -579,8 +579,12 @@ def load_manifest(path, with_cfa=False):
         m = json.load(f)
     base = os.path.dirname(os.path.abspath(path))
 
+    from .dng import common_meta, load_frame
+    paths = []
+
     def load(p):
-        return np.load(os.path.join(base, p))
+        paths.append(os.path.join(base, p))
+        return load_frame(paths[-1])
     sessions = []
     for s in m['sessions']:
         bias = np.stack([load(p) for p in s['bias']])
@@ -592,6 +596,10 @@ def load_manifest(path, with_cfa=False):
         if 'bursts' in s:
             session['bursts'] = [np.stack([load(p) for p in b]) for b in s['bursts']]
         sessions.append(session)
+    # what the manifest omits comes from the tags of its first DNG (every DNG of the manifest must agree with it); a manifest that names a value keeps it
+    tags = common_meta(paths) if any(k not in m for k in ('raw_pattern', 'black_level', 'white_level', 'cfa')) else None
+    if tags is not None:
+        m = dict({'cfa': tags['cfa'], 'raw_pattern': tags['raw_pattern'], 'black_level': tags['black_level'], 'white_level': tags['white_point']}, **m)
     out = (sessions, m['raw_pattern'], m['black_level'], m['white_level'])
     return out + (check_cfa(m.get('cfa', 'bayer')),) if with_cfa else out
 

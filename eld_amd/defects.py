@@ -390,7 +390,13 @@ def manifest_bias(path, session=None):
         session = int(np.argmin([float(i) for i in isos])) if all(isinstance(i, (int, float)) for i in isos) else 0
     if not 0 <= int(session) < len(ss):
         raise ValueError('--session %r: the manifest has sessions 0..%d' % (session, len(ss) - 1))
-    bias = np.stack([np.load(os.path.join(base, p)) for p in ss[int(session)]['bias']])
+    from .dng import common_meta, load_frame
+    paths = [os.path.join(base, p) for p in ss[int(session)]['bias']]
+    bias = np.stack([load_frame(p) for p in paths])
+    if 'raw_pattern' not in m or 'cfa' not in m:                   # as calibrate.load_manifest: the first DNG's tags fill what the manifest omits
+        tags = common_meta(paths)
+        if tags is not None:
+            m = dict({'cfa': tags['cfa'], 'raw_pattern': tags['raw_pattern']}, **m)
     return bias, check_cfa(m.get('cfa', 'bayer')), m['raw_pattern'], int(session)
 
 

@@ -16,8 +16,9 @@ float32, and so does this mode).  Under that truncation pack followed by write-b
 [512, 16383], 7893 come back one DN low (7676 of 15360 for black 1024).  rounding='nearest' (the default) rounds half to even, and then
 every code in [black, white] round-trips, for (black, white) = (512, 16383), (1024, 16383), (2048, 16383) and (0, 65535).
 
-Raw files are not decoded here (no rawpy): mosaics arrive as arrays (`raw.raw_image_visible`), and the values rawpy reports
-(raw_pattern, black_level_per_channel, camera_whitebalance, rgb_camera_matrix[:3, :3]) as arguments or a JSON sidecar.
+Raw files: a DNG input (.dng) is decoded on the device by eld_amd.dng (no rawpy) and its tags fill what the command line and the
+sidecar leave open; every other format converts to DNG.  Mosaics also arrive as arrays (.npy, `raw.raw_image_visible`), with the values
+rawpy reports (raw_pattern, black_level_per_channel, camera_whitebalance, rgb_camera_matrix[:3, :3]) as arguments or a JSON sidecar.
 The sRGB output is the reference's `process`: at packed resolution by default, at mosaic resolution with --srgb-size full.
 
     python -m eld_amd.denoise --ckpt model.pt --cfa xtrans --black 1024 --white 16383 --ratio 100 [--wb R G B] [--ccm 9 values] [--bf16] \\
@@ -440,7 +441,7 @@ def sidecar_from_dict(d, path):
 
 def build_parser():
     p = argparse.ArgumentParser(prog='python -m eld_amd.denoise', description='Denoise uint16 raw mosaics (.npy) with a trained ELD U-Net.')
-    p.add_argument('inputs', nargs='+', help='uint16 mosaics (.npy, raw_image_visible)')
+    p.add_argument('inputs', nargs='+', help='uint16 mosaics (.npy, raw_image_visible) or DNG files (.dng; their tags fill what is not given)')
     p.add_argument('-o', '--out', required=True, help='output directory')
     p.add_argument('--ckpt', required=True, help='checkpoint (.pt): the reference dict {"netG": ...} or a U-Net state_dict')
     p.add_argument('--meta', help='JSON sidecar: cfa, raw_pattern, black_level, white_point, ratio, wb, ccm (or rawpy names)')
@@ -459,6 +460,7 @@ def build_parser():
     p.add_argument('--iso', type=float, help='the ISO the frames were shot at (the abscissa of --shading)')
     p.add_argument('--flatfield', metavar='FILE', help='a flat-field map written by eld_amd.flatfield (.npz): PRNU in the input stage, lens gain on the output')
     p.add_argument('--lens', choices=LENS_MODES, help="where the lens plane of --flatfield applies: the sRGB rendering ('srgb', the default), the written-back mosaic too ('all'), nowhere ('off')")
+    p.add_argument('--dng', action='store_true', help='also write <name>_denoised.dng (uncompressed 16-bit; the tags of a .dng input are copied)')
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
     return p
 
@@ -475,6 +477,16 @@ def options_from(a):
            'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'precision': 'bf16' if a.bf16 else None,
            'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
     o.update({k: v for k, v in cli.items() if v is not None})
+    # below the command line and the sidecar, above the defaults: the tags of the first .dng input (all .dng inputs must agree on the sensor keys)
+    from .dng import fill_from_tags
+    tags = fill_from_tags(o, getattr(a, 'inputs', None) or [])
+    if tags is not None:
+        if o.get('wb') is None and o.get('ccm') is None and tags.get('wb') is not None and tags.get('ccm') is not None:
+            o['wb'], o['ccm'] = tags['wb'], tags['ccm']
+        if o.get('shading') is not None and o.get('iso') is None and tags.get('iso') is not None:
+            o['iso'] = tags['iso']
+    if getattr(a, 'dng', False):
+        o['dng'] = True
     o.setdefault('cfa', 'bayer')
     o.setdefault('white_point', 16383)
     o.setdefault('ratio', 1.0)
@@ -534,12 +546,22 @@ def run_frames(den, inputs, outdir, o):
     if o.get('flatfield') is not None:
         from .flatfield import as_flat_field
         kw['flatfield'], kw['lens'] = as_flat_field(o['flatfield'], '--flatfield'), o.get('lens') or 'srgb'
+    from .dng import is_dng, load_frame, write_dng
     for path in inputs:
-        raw = np.load(path)
+        raw = load_frame(path)
         res = denoise_raw(den, raw, o['cfa'], **kw)
         name = os.path.splitext(os.path.basename(path))[0]
         np.save(os.path.join(outdir, name + '_denoised.npy'), res['mosaic'])
         line = '%s -> %s_denoised.npy' % (path, name)
+        if o.get('dng'):
+            if raw.ndim != 2:
+                raise ValueError('%s: --dng writes one frame per file, the input holds a stack of %d' % (path, raw.shape[0]))
+            if is_dng(path):
+                write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'], like=path)
+            else:
+                write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'],
+                          meta={k: o.get(k) for k in ('cfa', 'raw_pattern', 'black_level', 'white_point', 'wb', 'ccm', 'iso')})
+            line += ', %s_denoised.dng' % name
         if res['srgb'] is not None:
             hwc = np.ascontiguousarray(np.moveaxis(res['srgb'], 1, -1))          # (N,h,w,3); one frame: (h,w,3)
             hwc = hwc if raw.ndim == 3 else hwc[0]

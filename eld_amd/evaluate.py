@@ -517,14 +517,15 @@ def read_manifest(path):
 
 
 def load_pairs(pairs):
-    """The manifest's pairs with their mosaics loaded (np.load)."""
+    """The manifest's pairs with their mosaics loaded (.npy: np.load; .dng: eld_amd.dng.read_dng)."""
+    from .dng import load_frame
     out = []
     for pr in pairs:
         q = dict(pr)
         for k in ('short', 'long'):
             if not os.path.exists(pr[k]):
                 raise ValueError('no such file: %s' % pr[k])
-            q[k] = np.load(pr[k])
+            q[k] = load_frame(pr[k])
         out.append(q)
     return out
 
@@ -569,6 +570,8 @@ def parse_args(argv):
     cli = {'defects': a.defects, 'shading': a.shading, 'flatfield': a.flatfield, 'precision': 'bf16' if a.bf16 else None}
     o.update({k: v for k, v in cli.items() if v is not None})
     o = {k: v for k, v in o.items() if k in OPTION_KEYS}
+    from .dng import fill_from_tags
+    fill_from_tags(o, [pr[k] for pr in pairs for k in ('short', 'long') if os.path.exists(pr[k])])   # below the manifest and --meta, above the defaults
     o.setdefault('cfa', 'bayer')
     o.setdefault('white_point', 16383)
     o.setdefault('precision', 'fp32')

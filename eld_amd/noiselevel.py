@@ -290,6 +290,9 @@ def main(argv=None):
     o = read_sidecar(a.meta) if a.meta else {}
     if a.defects is not None:
         o['defects'] = a.defects
+    import glob
+    from .dng import fill_from_tags
+    fill_from_tags(o, [n for pat in a.inputs for n in sorted(glob.glob(pat))])        # below the sidecar, above the defaults
     est = estimate_from_options(load_burst(a.inputs), o, a.stride, False if a.all_colours else None)
     res = est.as_dict()
     if a.camera:

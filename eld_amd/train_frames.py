@@ -108,10 +108,12 @@ def main(argv=None):
     o = {k: v for k, v in side.items() if k in ('cfa', 'raw_pattern', 'black_level', 'white_point')}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white}
     o.update({k: v for k, v in cli.items() if v is not None})
-    cfa = o.pop('cfa', 'bayer')
-    o.setdefault('white_point', 16383)
     paths = [p for pat in a.frames for p in (sorted(glob.glob(pat)) or [pat])]
-    mosaics = [np.load(p) for p in paths]
+    from .dng import fill_from_tags, load_frame
+    fill_from_tags(o, paths)                                         # command line, then sidecar, then the first DNG's tags, then the defaults
+    cfa = o.pop('cfa', None) or 'bayer'
+    o.setdefault('white_point', 16383)
+    mosaics = [load_frame(p) for p in paths]
 
     import torch
     from .engine import Engine

@@ -951,6 +951,56 @@ size_t eld_bm3d_vst_workspace_bytes(int N, int C, int h, int w);
 int eld_bm3d_vst_f32(const float* x, int N, int C, int h, int w, float qscale, const uint16_t* fwd, const int32_t* guide, int S, int step, int Gmax,
                      int mix, uint32_t tau, const uint32_t* par, const uint8_t* win, int frac, int32_t* out, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- DNG raw decode: packed bits and lossless JPEG (csrc/dng.hip, csrc/dng_dev.h, eld_amd/dng.py) ------------------------------
+ * Appended without a change of ELD_ABI_VERSION: two new symbols, no existing call changed.  The host (eld_amd/dng.py) parses the TIFF container
+ * and every JPEG marker segment; the device sees one contiguous byte range of the file (blob), one record per strip or tile (a stream) and, for
+ * lossless JPEG, the canonical Huffman decode tables.  Both entry points write the visible mosaic out[Hm][Wm]: the site (y, x) of the full
+ * H x W image goes to out[y - top][x - left] when it lies inside the active area [top, top + Hm) x [left, left + Wm); tile samples beyond
+ * the image are dropped; with lin, the value written is lin[min(v, lin_len - 1)].
+ *
+ * A record the kernel cannot trust is never followed: every read is checked against the stream's byte range (and that against blob_bytes),
+ * every write against the tile and the image, every table index against the table.  A stream stops at its first violation and reports it
+ * in status[stream] (ELD_DNG_*); streams are independent, the others decode. */
+#define ELD_DNG_OK 0
+#define ELD_DNG_TRUNCATED 1        /* the data ended before the last sample */
+#define ELD_DNG_BADCODE 2          /* bits that are no code of the table, or a symbol above 16 */
+#define ELD_DNG_TOOMANY 3          /* the stream holds more samples than its tile */
+#define ELD_DNG_BADRECORD 4        /* a field of the record out of range (data beyond the blob, table index, geometry, row buffer) */
+#define ELD_DNG_FAST_BITS 9
+
+typedef struct EldDngStream {      /* 64 bytes */
+    uint32_t data_off, data_len;   /* the byte range in blob: entropy-coded data (after the SOS header) / the packed rows */
+    int32_t x0, y0, tw, th;        /* the tile's origin in the full image, its stored width and length (a last strip: the rows it has) */
+    int32_t P, X, Y, Nf, pred;     /* lossless JPEG only: precision 2..16, samples per line, lines, components 1..4, predictor 1..7 */
+    uint16_t table[4];             /* lossless JPEG only: the decode table of each component */
+    uint32_t ws_off;               /* lossless JPEG, predictors 2..7: where this stream's row of X * Nf samples starts in ws (elements) */
+    uint32_t reserved[2];
+} EldDngStream;
+
+typedef struct EldDngHuff {        /* 1196 bytes: one canonical Huffman table, symbols 0..16, codes of 1..16 bits */
+    uint16_t fast[1 << ELD_DNG_FAST_BITS];  /* indexed by the next 9 bits: (length << 8) | symbol for a code of <= 9 bits, else 0 */
+    int32_t maxcode[17];           /* [l]: the largest code of l bits, -1 where there is none */
+    int32_t valoff[17];            /* [l]: the code c of l bits has the symbol vals[c + valoff[l]] */
+    uint8_t vals[32];              /* the symbols in code order */
+    int32_t nvals;
+} EldDngHuff;
+
+/* eld_dng_unpack_u16: compression 1.  bits in {8, 10, 12, 14, 16}, samples MSB-first, every row of a stream starts on a byte boundary (a row
+ * takes ceil(tw * bits / 8) bytes); 16-bit samples are little-endian unless big_endian.  One lane per four samples.
+ * eld_dng_ljpeg_u16: compression 7 (ITU-T T.81 process 14).  One lane per stream; `lanes` streams share a wave (1..64; 0: chosen from nstreams
+ * and the device's size).  The decoded samples are laid into the tile linearly (sample i -> row i / tw, column i % tw) while prediction runs
+ * in the JPEG's own X x Y x Nf geometry; SSSS = 16 is the difference 32768 without extra bits; sums are modulo 65536.  ws: ws_elems uint16
+ * of scratch (the previous line of the streams whose predictor looks up), may be NULL when ws_elems is 0.
+ * ELD_EINVAL before any device work: a null blob / streams / tables / out / status with nstreams > 0; nstreams or ntables < 0 (ntables < 1
+ * with streams); bits outside the set; H, W, Hm, Wm < 1, top or left < 0, top + Hm > H, left + Wm > W, H * W >= 2^31; lin_len outside
+ * [0, 65536] or lin null with lin_len > 0; lanes outside [0, 64]; ws null with ws_elems > 0; out, lin or ws not 2-byte, streams, tables or
+ * status not 4-byte aligned.  nstreams == 0 is a successful no-op. */
+int eld_dng_unpack_u16(const uint8_t* blob, size_t blob_bytes, const EldDngStream* streams, int nstreams, int bits, int big_endian, int H, int W,
+                       int top, int left, int Hm, int Wm, const uint16_t* lin, int lin_len, uint16_t* out, int32_t* status, void* stream);
+int eld_dng_ljpeg_u16(const uint8_t* blob, size_t blob_bytes, const EldDngStream* streams, int nstreams, const EldDngHuff* tables, int ntables,
+                      int H, int W, int top, int left, int Hm, int Wm, const uint16_t* lin, int lin_len, uint16_t* ws, size_t ws_elems, int lanes,
+                      uint16_t* out, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
