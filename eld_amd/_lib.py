@@ -41,6 +41,10 @@ DNG_FAST_BITS = 9
 DNG_HUFF_DTYPE = np.dtype([('fast', '<u2', (1 << DNG_FAST_BITS,)), ('maxcode', '<i4', (17,)), ('valoff', '<i4', (17,)), ('vals', 'u1', (32,)),
                            ('nvals', '<i4')])
 assert DNG_STREAM_DTYPE.itemsize == 64 and DNG_HUFF_DTYPE.itemsize == 1196
+# struct EldDngEncChunk (16 bytes) and the segment / chunk lengths of the lossless-JPEG encoder (samples resp. bytes)
+DNG_ENC_CHUNK_DTYPE = np.dtype([('src', '<u4'), ('nbytes', '<u4'), ('dst', '<u4'), ('reserved', '<u4')])
+DNG_ENC_SEGMENT, DNG_ENC_MIN_SEGMENT, DNG_ENC_MAX_SEGMENT = 2048, 64, 8192
+DNG_ENC_CHUNK, DNG_ENC_MIN_CHUNK, DNG_ENC_MAX_CHUNK = 4096, 16, 4096
 DNG_STATUS = {0: 'ok', 1: 'truncated: the data ended before the last sample', 2: 'invalid code: bits that are no code of the Huffman table',
               3: 'too many samples: the stream holds more samples than its tile', 4: 'bad record: a field out of range'}
 
@@ -176,6 +180,10 @@ SIGNATURES = {
                               _sz, _vp]),
     'eld_dng_unpack_u16': (_i, [_vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp]),
     'eld_dng_ljpeg_u16': (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _i, _vp, _vp, _vp]),
+    'eld_dng_enc_hist_u16': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    'eld_dng_enc_pack_u16': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'eld_dng_enc_ffcount_u8': (_i, [_vp, _sz, _vp, _i, _i, _vp, _vp]),
+    'eld_dng_enc_stuff_u8': (_i, [_vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 

@@ -26,6 +26,8 @@ tripod: misalignment below one CFA period adds variance wherever the scene has g
 
 Command line: python -m eld_amd.burst 'burst/*.npy' --meta sensor.json -o clean.npy [--kept kept.npy] [--ptc ptc.json] [--defects map.npz]
 [--k 5] [--min-dev 2] [--align [--ref N] [--disp field.npy]]
+An -o that ends in .dng writes the stack from the device tensor as lossless-JPEG tiles (eld_amd.dng.write_dng, compression 7) with the tags of
+the first .dng input, else of the sidecar.
 """
 import argparse
 import ctypes
@@ -409,7 +411,8 @@ def build_parser():
     p = argparse.ArgumentParser(prog='python -m eld_amd.burst', description='Stack a tripod burst of uint16 raw mosaics (.npy): clean frame and gain.')
     p.add_argument('inputs', nargs='+', help="the burst's frames: .npy files or quoted globs, each (Hm, Wm) or (n, Hm, Wm) uint16")
     p.add_argument('--meta', help='JSON sidecar (eld_amd.denoise): cfa, raw_pattern, black_level, white_point (or rawpy names), defects')
-    p.add_argument('-o', '--out', required=True, help='the stacked frame (.npy, uint16): what train_frames reads as a clean frame')
+    p.add_argument('-o', '--out', required=True, help='the stacked frame: .npy (uint16), or .dng (lossless-JPEG tiles written from the device, with the tags of the first '
+                                                        '.dng input, else of the sidecar); train_frames reads either as a clean frame')
     p.add_argument('--kept', metavar='OUT', help='write the samples kept per site (.npy, uint8; 0 stands for 256)')
     p.add_argument('--ptc', metavar='OUT', help='write the photon-transfer sums and the fitted line as JSON')
     p.add_argument('--defects', metavar='F', help='a defect map written by eld_amd.defects (.npz)')
@@ -474,11 +477,18 @@ def main(argv=None):
     if a.defects is not None:
         o['defects'] = a.defects
     from .dng import fill_from_tags
-    fill_from_tags(o, [n for pat in a.inputs for n in sorted(glob.glob(pat))])        # below the sidecar, above the defaults
+    names = [n for pat in a.inputs for n in sorted(glob.glob(pat))]
+    fill_from_tags(o, names)                                                          # below the sidecar, above the defaults
     if (a.disp or a.ref) and not a.align:
         raise SystemExit('--ref and --disp go with --align')
     stack, res = run(load_burst(a.inputs), o, a.k, a.min_dev, a.align, a.ref)
-    np.save(a.out, stack.mean.cpu().numpy())
+    from .dng import is_dng, write_dng
+    if is_dng(a.out):                                                                 # straight from the device tensor
+        like = next((n for n in names if is_dng(n)), None)
+        meta = None if like is not None else {k: o.get(k) for k in ('cfa', 'raw_pattern', 'black_level', 'white_point', 'wb', 'ccm', 'iso')}
+        write_dng(a.out, stack.mean, meta=meta, like=like, compression=7)
+    else:
+        np.save(a.out, stack.mean.cpu().numpy())
     print('stacked %d frames -> %s' % (res['N'], a.out))
     print('sites with a rejected sample: %.4f %%' % (100.0 * res['rejected_share']))
     if a.align:

@@ -460,7 +460,8 @@ def build_parser():
     p.add_argument('--iso', type=float, help='the ISO the frames were shot at (the abscissa of --shading)')
     p.add_argument('--flatfield', metavar='FILE', help='a flat-field map written by eld_amd.flatfield (.npz): PRNU in the input stage, lens gain on the output')
     p.add_argument('--lens', choices=LENS_MODES, help="where the lens plane of --flatfield applies: the sRGB rendering ('srgb', the default), the written-back mosaic too ('all'), nowhere ('off')")
-    p.add_argument('--dng', action='store_true', help='also write <name>_denoised.dng (uncompressed 16-bit; the tags of a .dng input are copied)')
+    p.add_argument('--dng', action='store_true', help='also write <name>_denoised.dng (uncompressed 16-bit unless --dng-compression says otherwise; the tags of a .dng input are copied)')
+    p.add_argument('--dng-compression', choices=('none', 'ljpeg'), default='none', help="of --dng: 'none' (uncompressed strips, the default) or 'ljpeg' (lossless-JPEG tiles, encoded on the device)")
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
     return p
 
@@ -487,6 +488,10 @@ def options_from(a):
             o['iso'] = tags['iso']
     if getattr(a, 'dng', False):
         o['dng'] = True
+    if getattr(a, 'dng_compression', 'none') != 'none':
+        if not o.get('dng'):
+            raise ValueError('--dng-compression goes with --dng')
+        o['dng_compression'] = a.dng_compression
     o.setdefault('cfa', 'bayer')
     o.setdefault('white_point', 16383)
     o.setdefault('ratio', 1.0)
@@ -546,7 +551,8 @@ def run_frames(den, inputs, outdir, o):
     if o.get('flatfield') is not None:
         from .flatfield import as_flat_field
         kw['flatfield'], kw['lens'] = as_flat_field(o['flatfield'], '--flatfield'), o.get('lens') or 'srgb'
-    from .dng import is_dng, load_frame, write_dng
+    from .dng import COMPRESSION_CHOICES, is_dng, load_frame, write_dng
+    dng_kw = {'compression': COMPRESSION_CHOICES[o.get('dng_compression') or 'none']}
     for path in inputs:
         raw = load_frame(path)
         res = denoise_raw(den, raw, o['cfa'], **kw)
@@ -557,10 +563,10 @@ def run_frames(den, inputs, outdir, o):
             if raw.ndim != 2:
                 raise ValueError('%s: --dng writes one frame per file, the input holds a stack of %d' % (path, raw.shape[0]))
             if is_dng(path):
-                write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'], like=path)
+                write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'], like=path, **dng_kw)
             else:
                 write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'],
-                          meta={k: o.get(k) for k in ('cfa', 'raw_pattern', 'black_level', 'white_point', 'wb', 'ccm', 'iso')})
+                          meta={k: o.get(k) for k in ('cfa', 'raw_pattern', 'black_level', 'white_point', 'wb', 'ccm', 'iso')}, **dng_kw)
             line += ', %s_denoised.dng' % name
         if res['srgb'] is not None:
             hwc = np.ascontiguousarray(np.moveaxis(res['srgb'], 1, -1))          # (N,h,w,3); one frame: (h,w,3)

@@ -5,8 +5,10 @@ ITU-T T.81): there is no rawpy here.
     read_dng(path, device=None) -> (mosaic, meta)   the visible mosaic as rawpy's raw_image_visible would give it
     dng_meta(path)                                  the tags only, in the sidecar's keys (eld_amd.denoise.SIDECAR_KEYS)
     load_frame(path)                                .npy -> np.load(path); .dng -> read_dng(path)[0]
-    write_dng(path, mosaic, meta=None, like=None)   an uncompressed 16-bit little-endian DNG, one IFD, strips
-    python -m eld_amd.dng in.dng [-o frame.npy] [--meta-out sensor.json]
+    write_dng(path, mosaic, meta=None, like=None)   an uncompressed 16-bit little-endian DNG, one IFD, strips; compression=7: lossless-JPEG
+                                                    tiles, encoded on the device (eld_dng_enc_*)
+    encode_ljpeg(mosaic, tile, bits)                the JPEG streams of the tiles alone, for callers with a container of their own
+    python -m eld_amd.dng in.dng [-o frame.npy | -o out.dng [--compression ljpeg] [--tile TH TW] [--bits N]] [--meta-out sensor.json]
 
 Container.  Classic TIFF in both byte orders.  The raw image is the IFD with NewSubFileType = 0 and PhotometricInterpretation = 32803
 (CFA), looked for in IFD0 and in its SubIFDs (tag 330); SamplesPerPixel = 1; strips or tiles; Compression 1 (8, 10, 12, 14 or 16 bits, rows
@@ -644,19 +646,274 @@ def _pack_entry(e):
     return e.type, len(vals), struct.pack('<%d%s' % (len(vals), TYPE_FMT[e.type]), *vals)
 
 
-def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None):
-    """Write `mosaic` ((H, W) uint16 codes, NumPy or a CUDA int16-view tensor) as an uncompressed 16-bit little-endian DNG: one IFD, the CFA
-    image in strips.  like: a source DNG whose CFA, level, colour, neutral, make / model, ISO and exposure tags are copied with their original
+# ---- lossless-JPEG encoder: tables and markers on the host, the bits on the device (csrc/dng_enc.hip) ------------------
+DEFAULT_TILE = (256, 256)
+COMPRESSION_CHOICES = {'none': 1, 'ljpeg': 7}                        # the command lines' names of write_dng's compression
+_EXTRA_BITS = np.array(list(range(16)) + [0], dtype=np.int64)        # SSSS extra bits behind the code; SSSS = 16 carries none
+
+
+def huffman_lengths(hist):
+    """The 17-bin SSSS histogram of a stream -> (counts of the code lengths 1..16, the symbols in code order), as a DHT segment stores them:
+    ITU-T T.81 Annex K.2.  Figure K.1 with an 18th symbol of frequency 1 that keeps the all-ones code point free (it ends up with the longest
+    code and is dropped); the least frequency goes to V1, the next to V2, ties to the larger index; Figure K.3 limits the lengths to 16."""
+    freq = [int(v) for v in hist] + [1]
+    if len(freq) != 18 or min(freq) < 0:
+        raise ValueError('a histogram of 17 non-negative counts, got %r' % (list(hist),))
+    n = len(freq)
+    size, chain = [0] * n, [-1] * n
+
+    def least(skip):
+        best = -1
+        for i in range(n):
+            if freq[i] > 0 and i != skip and (best < 0 or freq[i] <= freq[best]):
+                best = i
+        return best
+    while True:
+        v1 = least(-1)
+        v2 = least(v1)
+        if v2 < 0:
+            break
+        freq[v1] += freq[v2]
+        freq[v2] = 0
+        size[v1] += 1                                                # every symbol of both subtrees is one bit longer
+        while chain[v1] >= 0:
+            v1 = chain[v1]
+            size[v1] += 1
+        chain[v1] = v2                                               # V2's subtree hangs behind the end of V1's chain
+        size[v2] += 1
+        while chain[v2] >= 0:
+            v2 = chain[v2]
+            size[v2] += 1
+    counts = [0] * 33
+    for s in size:
+        if s:
+            counts[s] += 1
+    for l in range(32, 16, -1):                                      # Figure K.3: a pair of the longest codes moves up under a shorter one
+        while counts[l] > 0:
+            j = l - 2
+            while counts[j] == 0:
+                j -= 1
+            counts[l] -= 2
+            counts[l - 1] += 1
+            counts[j + 1] += 2
+            counts[j] -= 1
+    l = 16
+    while counts[l] == 0:
+        l -= 1
+    counts[l] -= 1                                                   # the reserved code point
+    symbols = [s for l in range(1, 33) for s in range(n - 1) if size[s] == l]
+    return counts[1:17], symbols
+
+
+def encoder_table(counts, symbols):
+    """-> 17 uint32, [ssss] = (code length << 16) | canonical code (Annex C), 0 for a symbol the table lacks"""
+    tab = np.zeros(17, dtype=np.uint32)
+    code, k = 0, 0
+    for l in range(1, 17):
+        for _ in range(counts[l - 1]):
+            tab[symbols[k]] = (l << 16) | code
+            code += 1
+            k += 1
+        code <<= 1
+    return tab
+
+
+def ljpeg_header(P, X, Y, counts, symbols):
+    """SOI, SOF3 (two components, ids 1 and 2, 1 x 1 sampling), DHT (class 0, id 0), SOS (both components on table 0, predictor 1)"""
+    sof = struct.pack('>BHHB', P, Y, X, 2) + bytes([1, 0x11, 0, 2, 0x11, 0])
+    dht = bytes([0]) + bytes(counts) + bytes(symbols)
+    sos = bytes([2, 1, 0, 2, 0, 1, 0, 0])
+    return (b'\xff\xd8\xff\xc3' + struct.pack('>H', 2 + len(sof)) + sof + b'\xff\xc4' + struct.pack('>H', 2 + len(dht)) + dht +
+            b'\xff\xda' + struct.pack('>H', 2 + len(sos)) + sos)
+
+
+def _check_encode_args(tile, bits, segment=0, chunk=0):
+    try:
+        th, tw = (int(v) for v in tile)
+    except (TypeError, ValueError):
+        raise ValueError('tile takes (TileLength, TileWidth), got %r' % (tile,))
+    if tw % 2:
+        raise ValueError('tile %r: an odd TileWidth does not split into the two components of the JPEG' % (tile,))
+    if th < 16 or tw < 16 or th % 16 or tw % 16:
+        raise ValueError('tile %r: TileLength and TileWidth must be multiples of 16 (TIFF 6.0, section 15)' % (tile,))
+    if th * tw > 1 << 24:
+        raise ValueError('tile %r: more than 2^24 samples' % (tile,))
+    bits = int(bits)
+    if not 8 <= bits <= 16:
+        raise ValueError('bits = %d: the lossless-JPEG writer takes 8..16' % bits)
+    segment, chunk = int(segment), int(chunk)
+    if segment and (segment % L.DNG_ENC_MIN_SEGMENT or not L.DNG_ENC_MIN_SEGMENT <= segment <= L.DNG_ENC_MAX_SEGMENT):
+        raise ValueError('segment = %d samples: a multiple of %d up to %d, or 0 for the default' % (segment, L.DNG_ENC_MIN_SEGMENT, L.DNG_ENC_MAX_SEGMENT))
+    if chunk and (chunk % L.DNG_ENC_MIN_CHUNK or not L.DNG_ENC_MIN_CHUNK <= chunk <= L.DNG_ENC_MAX_CHUNK):
+        raise ValueError('chunk = %d bytes: a multiple of %d up to %d, or 0 for the default' % (chunk, L.DNG_ENC_MIN_CHUNK, L.DNG_ENC_MAX_CHUNK))
+    return (th, tw), bits, segment or L.DNG_ENC_SEGMENT, chunk or L.DNG_ENC_CHUNK
+
+
+def _mosaic_shape(mosaic, who):
+    """(H, W) of a NumPy uint16 / int16 array or a torch int16 / uint16 tensor; anything else is a ValueError"""
+    if isinstance(mosaic, np.ndarray):
+        ok = mosaic.dtype in (np.uint16, np.int16)
+    else:
+        ok = str(getattr(mosaic, 'dtype', None)) in ('torch.int16', 'torch.uint16')
+    if not ok or len(mosaic.shape) != 2 or mosaic.shape[0] < 1 or mosaic.shape[1] < 1:
+        raise ValueError('%s takes one (H, W) uint16 mosaic, got %s %s' % (who, getattr(mosaic, 'dtype', type(mosaic)), tuple(getattr(mosaic, 'shape', ()))))
+    return int(mosaic.shape[0]), int(mosaic.shape[1])
+
+
+class Encoder:
+    """One encode, step by step (encode_ljpeg runs the steps in order; tools/dng_enc_time.py times them one by one):
+    hist() -> plan() -> pack() -> ffcount() -> sizes() -> stuff() -> streams().  The mosaic stays on its device; the host sees the
+    histograms, the stuffed sizes and the compressed bytes."""
+    def __init__(self, mosaic, tile=DEFAULT_TILE, bits=16, segment=0, chunk=0):
+        (self.th, self.tw), self.bits, self.segment, self.chunk = _check_encode_args(tile, bits, segment, chunk)
+        self.H, self.W = _mosaic_shape(mosaic, 'encode_ljpeg')
+        self.ny, self.nx = -(-self.H // self.th), -(-self.W // self.tw)
+        self.ns = self.ny * self.nx
+        if self.ns > 65535:
+            raise ValueError('%d x %d in tiles of %d x %d: %d tiles, more than 65535' % (self.H, self.W, self.th, self.tw, self.ns))
+        if self.H * self.W >= 1 << 31:
+            raise ValueError('a mosaic of %d x %d: more than 2^31 sites' % (self.H, self.W))
+        self.nseg = -(-(self.th * self.tw) // self.segment)
+        import torch
+        self.torch = torch
+        self.lib = L.lib()
+        if isinstance(mosaic, np.ndarray):
+            mosaic = torch.from_numpy(np.ascontiguousarray(mosaic).view(np.int16)).to(torch.device('cuda', torch.cuda.current_device()))
+        if mosaic.device.type != 'cuda':
+            raise ValueError('encode_ljpeg encodes on a CUDA device, got a tensor on %s' % mosaic.device)
+        self.mosaic = mosaic.detach().contiguous()
+        self.dev = self.mosaic.device
+
+    def _up(self, a):
+        return self.torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1)).to(self.dev)
+
+    def _geom(self):
+        return (L.dptr(self.mosaic), self.H, self.W, self.th, self.tw, self.bits, self.segment)
+
+    def hist(self):
+        torch = self.torch
+        with torch.cuda.device(self.dev):
+            self.d_hist = torch.empty(self.ns * self.nseg * 17, dtype=torch.int32, device=self.dev)
+            self.d_max = torch.empty(self.ns, dtype=torch.int32, device=self.dev)
+            L.check(self.lib.eld_dng_enc_hist_u16(*self._geom(), L.dptr(self.d_hist), L.dptr(self.d_max), L.cur_stream()), 'eld_dng_enc_hist_u16')
+
+    def plan(self):
+        """The histograms -> every stream's table and markers, every segment's first bit, the layout of the unstuffed bytes and its chunks."""
+        h = self.d_hist.cpu().numpy().view(np.uint32).reshape(self.ns, self.nseg, 17).astype(np.int64)
+        mx = self.d_max.cpu().numpy().view(np.uint32)
+        bad = np.flatnonzero(mx >= (1 << self.bits))
+        if bad.size:
+            s = int(bad[0])
+            raise ValueError('the mosaic holds the code %d in tile %d (rows from %d, columns from %d): it does not fit bits = %d'
+                             % (int(mx[s]), s, (s // self.nx) * self.th, (s % self.nx) * self.tw, self.bits))
+        tot = h.sum(axis=1)
+        tables, lens, self.headers, seen = np.zeros((self.ns, 17), dtype=np.uint32), np.zeros((self.ns, 17), dtype=np.int64), [], {}
+        for s in range(self.ns):
+            key = tot[s].tobytes()
+            if key not in seen:
+                counts, symbols = huffman_lengths(tot[s])
+                seen[key] = (encoder_table(counts, symbols), ljpeg_header(self.bits, self.tw // 2, self.th, counts, symbols))
+            tables[s], hd = seen[key]
+            self.headers.append(hd)
+            lens[s] = tables[s] >> 16
+        seg_bit = np.zeros((self.ns, self.nseg + 1), dtype=np.int64)
+        seg_bit[:, 1:] = np.cumsum((h * (lens + _EXTRA_BITS)[:, None, :]).sum(axis=2), axis=1)
+        self.nraw = (seg_bit[:, -1] + 7) // 8                        # unstuffed bytes per stream; th * tw * 31 bits at most: below 2^29
+        room = (self.nraw + 15) // 16 * 16                           # every stream starts on 16 bytes of the unstuffed buffer
+        raw_off = np.concatenate([[0], np.cumsum(room)[:-1]])
+        self.raw_bytes = int(room.sum())
+        if self.raw_bytes >= 1 << 31:
+            raise ValueError('the entropy-coded data takes %d bytes: more than 2^31' % self.raw_bytes)
+        nch = -(-self.nraw // self.chunk)
+        self.first_chunk = np.concatenate([[0], np.cumsum(nch)])
+        sid = np.repeat(np.arange(self.ns), nch)
+        j = np.arange(int(nch.sum())) - self.first_chunk[sid]
+        ch = np.zeros(sid.size, dtype=L.DNG_ENC_CHUNK_DTYPE)
+        ch['src'] = raw_off[sid] + j * self.chunk
+        ch['nbytes'] = np.minimum(self.chunk, self.nraw[sid] - j * self.chunk)
+        ch['dst'] = np.concatenate([[0], np.cumsum(self.nraw)[:-1]])[sid] + j * self.chunk
+        self.nchunks = int(sid.size)
+        self.d_tables, self.d_seg_bit = self._up(tables), self._up(seg_bit.astype(np.uint32))
+        self.d_raw_dword, self.d_chunks = self._up((raw_off // 4).astype(np.uint32)), self._up(ch)
+        self.d_last = self.torch.from_numpy(self.first_chunk[1:] - 1).to(self.dev)
+        self.d_raw = self.torch.empty(self.raw_bytes // 4, dtype=self.torch.int32, device=self.dev)
+        self.d_count = self.torch.empty(self.nchunks, dtype=self.torch.int32, device=self.dev)
+
+    def pack(self):
+        with self.torch.cuda.device(self.dev):
+            L.check(self.lib.eld_dng_enc_pack_u16(*self._geom(), L.dptr(self.d_tables), L.dptr(self.d_seg_bit), L.dptr(self.d_raw_dword),
+                                                  L.dptr(self.d_raw), self.raw_bytes // 4, L.cur_stream()), 'eld_dng_enc_pack_u16')
+
+    def ffcount(self):
+        with self.torch.cuda.device(self.dev):
+            L.check(self.lib.eld_dng_enc_ffcount_u8(L.dptr(self.d_raw), self.raw_bytes, L.dptr(self.d_chunks), self.nchunks, self.chunk,
+                                                    L.dptr(self.d_count), L.cur_stream()), 'eld_dng_enc_ffcount_u8')
+
+    def sizes(self):
+        """The running sum of the FF counts (device), then the one synchronisation: the stuffed size of every stream."""
+        torch = self.torch
+        cum = torch.cumsum(self.d_count, 0, dtype=torch.int32)
+        self.d_before = (cum - self.d_count).contiguous()
+        ends = cum[self.d_last].cpu().numpy().astype(np.int64)
+        self.sizes_ = self.nraw + np.diff(np.concatenate([[0], ends]))
+        self.out_bytes = int(self.sizes_.sum())
+        if self.out_bytes >= 1 << 32:
+            raise ValueError('the stuffed data takes %d bytes: more than 2^32' % self.out_bytes)
+        self.d_out = torch.empty((self.out_bytes + 3) // 4 * 4, dtype=torch.uint8, device=self.dev)
+
+    def stuff(self):
+        with self.torch.cuda.device(self.dev):
+            L.check(self.lib.eld_dng_enc_stuff_u8(L.dptr(self.d_raw), self.raw_bytes, L.dptr(self.d_chunks), self.nchunks, self.chunk,
+                                                  L.dptr(self.d_before), L.dptr(self.d_out), self.out_bytes, L.cur_stream()), 'eld_dng_enc_stuff_u8')
+
+    def streams(self):
+        """The one copy of the compressed bytes to the host -> the complete JPEG streams in TileOffsets order."""
+        data = self.d_out.cpu().numpy()
+        offs = np.concatenate([[0], np.cumsum(self.sizes_)])
+        return [self.headers[s] + data[offs[s]:offs[s + 1]].tobytes() + b'\xff\xd9' for s in range(self.ns)]
+
+
+def encode_ljpeg(mosaic, tile=DEFAULT_TILE, bits=16, segment=0, chunk=0):
+    """`mosaic` ((H, W) uint16 codes: NumPy, uploaded; or a CUDA int16-view tensor, used in place) -> the complete lossless-JPEG streams of
+    its tiles (list of bytes, rows of tiles, left to right): process 14, two components of TileWidth / 2 samples (Adobe's layout), precision
+    `bits`, predictor 1, one Huffman table from the stream's own histogram.  Edge tiles are stored whole, padded by edge replication.
+    segment (samples) and chunk (bytes) cut the work of the kernels, 0: the defaults; the bytes do not depend on them.  A code >= 2^bits is a
+    ValueError that names the value and the tile."""
+    e = Encoder(mosaic, tile, bits, segment, chunk)
+    e.hist()
+    e.plan()
+    e.pack()
+    e.ffcount()
+    e.sizes()
+    e.stuff()
+    return e.streams()
+
+
+def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compression=1, tile=None, bits=None):
+    """Write `mosaic` ((H, W) uint16 codes, NumPy or a CUDA int16-view tensor) as a little-endian DNG with one IFD.  compression 1 (the
+    default): uncompressed 16-bit strips.  compression 7: lossless-JPEG tiles of `tile` (TileLength, TileWidth; default 256 x 256) at `bits`
+    (8..16, default 16) precision, encoded on the device (encode_ljpeg): a NumPy mosaic is uploaded, a device tensor is used where it is.
+    like: a source DNG whose CFA, level, colour, neutral, make / model, ISO and exposure tags are copied with their original
     values (rationals stay the rationals they were; the mosaic is taken to be the source's visible mosaic, so no ActiveArea and no
     LinearizationTable are written).  meta: sidecar keys (cfa, raw_pattern, black_level, white_point, wb, ccm, iso, exposure_time, make, model);
     its tags are written from those values (ColorMatrix1 with CalibrationIlluminant1 = 21) and override what `like` gave."""
-    if not isinstance(mosaic, np.ndarray):
-        mosaic = mosaic.detach().cpu().numpy()
-    if mosaic.dtype == np.int16:
-        mosaic = mosaic.view(np.uint16)
-    if mosaic.dtype != np.uint16 or mosaic.ndim != 2 or mosaic.size == 0:
-        raise ValueError('write_dng takes one (H, W) uint16 mosaic, got %s %s' % (mosaic.dtype, mosaic.shape))
-    H, W = mosaic.shape
+    if compression not in (1, 7):
+        raise ValueError('compression = %r: write_dng writes 1 (uncompressed) and 7 (lossless JPEG)' % (compression,))
+    if compression == 7:
+        if rows_per_strip:
+            raise ValueError('rows_per_strip with compression = 7: lossless JPEG is written in tiles')
+        tile, bits, _, _ = _check_encode_args(DEFAULT_TILE if tile is None else tile, 16 if bits is None else bits)
+        _mosaic_shape(mosaic, 'write_dng')
+    else:
+        if tile is not None or bits is not None:
+            raise ValueError('tile and bits belong to compression = 7; compression = 1 writes 16-bit strips')
+        if not isinstance(mosaic, np.ndarray):
+            mosaic = mosaic.detach().cpu().numpy()
+        if mosaic.dtype == np.int16:
+            mosaic = mosaic.view(np.uint16)
+        if mosaic.dtype != np.uint16 or mosaic.ndim != 2 or mosaic.size == 0:
+            raise ValueError('write_dng takes one (H, W) uint16 mosaic, got %s %s' % (mosaic.dtype, mosaic.shape))
+    H, W = (int(v) for v in mosaic.shape)
     tags = {}
 
     def put(tag, typ, vals):
@@ -733,18 +990,29 @@ def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None):
             tags[tag] = Entry(tag, ASCII, 0, str(m[key]))
     if T_CFADIM not in tags:
         raise ValueError('write_dng needs a CFA pattern: meta with cfa / raw_pattern, or like= a DNG')
-    rps = int(rows_per_strip) if rows_per_strip else max(1, min(H, (1 << 20) // (2 * W)))
-    ns = -(-H // rps)
     put(T_NEWSUBFILETYPE, LONG, (0,))
     put(T_WIDTH, LONG, (W,))
     put(T_LENGTH, LONG, (H,))
-    put(T_BITS, SHORT, (16,))
-    put(T_COMPRESSION, SHORT, (1,))
     put(T_PHOTOMETRIC, SHORT, (CFA_PHOTOMETRIC,))
     put(T_SPP, SHORT, (1,))
-    put(T_ROWSPERSTRIP, LONG, (rps,))
-    put(T_STRIPBYTECOUNTS, LONG, tuple(2 * W * min(rps, H - i * rps) for i in range(ns)))
-    put(T_STRIPOFFSETS, LONG, (0,) * ns)                            # patched below
+    if compression == 7:                                            # every argument and tag has been checked: now the device
+        streams = encode_ljpeg(mosaic, tile, bits)
+        ns, T_OFFSETS = len(streams), T_TILEOFFSETS
+        sizes = tuple(len(s) for s in streams)
+        put(T_BITS, SHORT, (bits,))
+        put(T_COMPRESSION, SHORT, (7,))
+        put(T_TILEWIDTH, LONG, (tile[1],))
+        put(T_TILELENGTH, LONG, (tile[0],))
+        put(T_TILEBYTECOUNTS, LONG, sizes)
+    else:
+        rps = int(rows_per_strip) if rows_per_strip else max(1, min(H, (1 << 20) // (2 * W)))
+        ns, T_OFFSETS = -(-H // rps), T_STRIPOFFSETS
+        sizes = tuple(2 * W * min(rps, H - i * rps) for i in range(ns))
+        put(T_BITS, SHORT, (16,))
+        put(T_COMPRESSION, SHORT, (1,))
+        put(T_ROWSPERSTRIP, LONG, (rps,))
+        put(T_STRIPBYTECOUNTS, LONG, sizes)
+    put(T_OFFSETS, LONG, (0,) * ns)                                 # patched below
     put(T_DNGVERSION, BYTE, (1, 4, 0, 0))
     put(T_DNGBACKWARD, BYTE, (1, 1, 0, 0))
     put(T_CFALAYOUT, SHORT, (1,))
@@ -765,11 +1033,16 @@ def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None):
     if len(extra) % 2:
         extra += b'\0'
     pix_off = data_off + len(extra)
-    offs = tuple(pix_off + 2 * W * rps * i for i in range(ns))
-    packed[T_STRIPOFFSETS] = (LONG, ns, struct.pack('<%dI' % ns, *offs))
+    offs, pos = [], pix_off
+    for n in sizes:                                                 # a compressed stream of odd length is followed by one byte of padding
+        offs.append(pos)
+        pos += n + n % 2
+    if pos >= 1 << 32:
+        raise ValueError('%s: %d bytes do not fit a classic TIFF' % (path, pos))
+    packed[T_OFFSETS] = (LONG, ns, struct.pack('<%dI' % ns, *offs))
     if ns > 1:                                                      # the payload sits in `extra`: patch it in place
-        a = where[T_STRIPOFFSETS] - data_off
-        extra = extra[:a] + packed[T_STRIPOFFSETS][2] + extra[a + 4 * ns:]
+        a = where[T_OFFSETS] - data_off
+        extra = extra[:a] + packed[T_OFFSETS][2] + extra[a + 4 * ns:]
     out = bytearray(b'II' + struct.pack('<HI', 42, ifd_off) + struct.pack('<H', len(order)))
     for tag in order:
         typ, cnt, payload = packed[tag]
@@ -778,19 +1051,37 @@ def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None):
     out += struct.pack('<I', 0) + extra
     with open(path, 'wb') as fh:
         fh.write(out)
-        fh.write(np.ascontiguousarray(mosaic).astype('<u2', copy=False).tobytes())
+        if compression == 7:
+            for s in streams:
+                fh.write(s + b'\0' * (len(s) % 2))
+        else:
+            fh.write(np.ascontiguousarray(mosaic).astype('<u2', copy=False).tobytes())
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m eld_amd.dng', description='Convert a DNG to a uint16 mosaic (.npy) and a JSON sidecar.')
     ap.add_argument('input', help='a DNG file')
-    ap.add_argument('-o', '--out', help='the mosaic (.npy); default: the input name with .npy')
+    ap.add_argument('-o', '--out', help='the mosaic (.npy), or a .dng: the visible mosaic re-written with the source\'s tags; default: the input '
+                                        'name with .npy')
     ap.add_argument('--meta-out', help='the sidecar (.json) with the keys eld_amd.denoise --meta reads')
+    ap.add_argument('--compression', choices=sorted(COMPRESSION_CHOICES), default='none', help='of a .dng output: uncompressed strips or '
+                                                                                               'lossless-JPEG tiles (default: none)')
+    ap.add_argument('--tile', type=int, nargs=2, metavar=('TH', 'TW'), help='TileLength TileWidth of --compression ljpeg (default 256 256)')
+    ap.add_argument('--bits', type=int, help='the precision of --compression ljpeg, 8..16 (default 16)')
     a = ap.parse_args(sys.argv[1:] if argv is None else argv)
-    mosaic, meta = read_dng(a.input)
+    if (a.tile or a.bits) and a.compression != 'ljpeg':
+        ap.error('--tile and --bits belong to --compression ljpeg')
+    if a.compression == 'ljpeg' and not is_dng(a.out):
+        ap.error('--compression ljpeg needs an -o that ends in .dng')
     out = a.out or os.path.splitext(a.input)[0] + '.npy'
-    np.save(out, mosaic)
+    if is_dng(out):
+        mosaic, meta = read_dng(a.input, device='cuda')
+        kw = dict(compression=7, tile=a.tile and tuple(a.tile), bits=a.bits) if a.compression == 'ljpeg' else {}
+        write_dng(out, mosaic, like=a.input, **kw)
+    else:
+        mosaic, meta = read_dng(a.input)
+        np.save(out, mosaic)
     print('%s -> %s (%d x %d, %s, %d bits, compression %d)' % (a.input, out, mosaic.shape[0], mosaic.shape[1], meta['cfa'], meta['bits'], meta['compression']))
     if meta['opcodes']:
         print('%s: %s present and not applied (gain maps, defect lists and warps stay with the raw converter)' % (a.input, ', '.join(meta['opcodes'])))

@@ -1001,6 +1001,51 @@ int eld_dng_ljpeg_u16(const uint8_t* blob, size_t blob_bytes, const EldDngStream
                       int H, int W, int top, int left, int Hm, int Wm, const uint16_t* lin, int lin_len, uint16_t* ws, size_t ws_elems, int lanes,
                       uint16_t* out, int32_t* status, void* stream);
 
+/* ---- DNG raw encode: lossless-JPEG tiles (csrc/dng_enc.hip, csrc/dng_enc_dev.h, eld_amd/dng.py) --------------------------------
+ * Appended without a change of ELD_ABI_VERSION: four new symbols, no existing call changed.  The mosaic[H][W] is cut into tiles of th x tw,
+ * th and tw multiples of 16; stream s = ty * ceil(W / tw) + tx is the tile at (ty * th, tx * tw), stored whole: its sample (r, c) is
+ * mosaic[min(y0 + r, H - 1)][min(x0 + c, W - 1)].  A stream is ITU-T T.81 process 14 with two components of tw / 2 samples per line (the sample
+ * sequence is the tile's raster), predictor 1, no point transform: sample (r, c) is predicted by (r, c - 2), the first two of a row by
+ * (r - 1, c), the first two of the tile by 2^(bits - 1); differences are modulo 65536 and SSSS = 16 carries no extra bits.
+ *
+ * Units.  `segment` is in SAMPLES: a stream's th * tw samples are cut into ceil(th * tw / segment) segments, one workgroup each; a multiple of
+ * 64 in [64, ELD_DNG_ENC_MAX_SEGMENT], 0: ELD_DNG_ENC_SEGMENT.  `chunk` is in BYTES of a stream's unstuffed entropy data, one workgroup each; a
+ * multiple of 16 in [16, ELD_DNG_ENC_MAX_CHUNK], 0: ELD_DNG_ENC_CHUNK.  With nstreams = ceil(H / th) * ceil(W / tw) and nseg = segments per
+ * stream:
+ *   eld_dng_enc_hist_u16    hist[(s * nseg + g) * 17 + ssss]: how many samples of segment g of stream s fall into each category; maxcode[s]:
+ *                           the largest code of the stream (bits is not looked at here beyond its range: the caller compares).
+ *   eld_dng_enc_pack_u16    tables[s * 17 + ssss] = (code length << 16) | code, length 0 for a category the stream does not hold;
+ *                           seg_bit[s * (nseg + 1) + g]: the first bit of segment g inside stream s, [.. + nseg]: the stream's bit count;
+ *                           raw_dword[s]: the dword of `raw` at which stream s starts.  raw (raw_dwords dwords) is zeroed here, then every
+ *                           segment writes its bits MSB-first; the last one pads the stream's last byte with 1-bits.  A segment whose bit count
+ *                           differs from seg_bit's writes nothing.  The first and last dword of a segment go out as atomic ORs, so the result
+ *                           does not depend on the order of execution.
+ *   eld_dng_enc_ffcount_u8  count[k]: the FF bytes among the nbytes (<= chunk) bytes of raw at chunks[k].src.
+ *   eld_dng_enc_stuff_u8    byte i of chunk k goes to out[chunks[k].dst + ffbefore[k] + i + (the FF bytes of the chunk before i)], a 00 behind
+ *                           every FF; with ffbefore the exclusive running sum of count, the streams come out stuffed and back to back.
+ * Every write is compared with raw_dwords resp. out_bytes, every read with raw_bytes and the mosaic.
+ * ELD_EINVAL before any device work: a null pointer; H or W < 1, H * W >= 2^31; th or tw < 16 or no multiple of 16 (so tw is even), th * tw > 2^24;
+ * more than 65535 tiles; bits outside [8, 16]; segment resp. chunk outside its set; nchunks < 0; mosaic not 2-byte, the uint32 arrays, raw and out not 4-byte aligned.
+ * nchunks == 0 is a successful no-op. */
+#define ELD_DNG_ENC_SEGMENT 2048
+#define ELD_DNG_ENC_MAX_SEGMENT 8192
+#define ELD_DNG_ENC_CHUNK 4096
+#define ELD_DNG_ENC_MAX_CHUNK 4096
+
+typedef struct EldDngEncChunk {    /* 16 bytes */
+    uint32_t src;                  /* byte offset of the chunk in raw (a multiple of 16 reads fastest) */
+    uint32_t nbytes;               /* 1 .. chunk */
+    uint32_t dst;                  /* byte offset in out of the chunk's first byte were no FF in front of it */
+    uint32_t reserved;
+} EldDngEncChunk;
+
+int eld_dng_enc_hist_u16(const uint16_t* mosaic, int H, int W, int th, int tw, int bits, int segment, uint32_t* hist, uint32_t* maxcode, void* stream);
+int eld_dng_enc_pack_u16(const uint16_t* mosaic, int H, int W, int th, int tw, int bits, int segment, const uint32_t* tables, const uint32_t* seg_bit,
+                         const uint32_t* raw_dword, uint32_t* raw, size_t raw_dwords, void* stream);
+int eld_dng_enc_ffcount_u8(const uint8_t* raw, size_t raw_bytes, const EldDngEncChunk* chunks, int nchunks, int chunk, uint32_t* count, void* stream);
+int eld_dng_enc_stuff_u8(const uint8_t* raw, size_t raw_bytes, const EldDngEncChunk* chunks, int nchunks, int chunk, const uint32_t* ffbefore,
+                         uint8_t* out, size_t out_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
