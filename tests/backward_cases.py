@@ -84,7 +84,8 @@ def forward_regions(Ws, Bs, x):
 
 
 def f32_rejects(got, y, bound):
-    return bool(((got.double() - y).abs() > bound).any())
+    """an element is accepted only if err <= bound is true (NaN is rejected)"""
+    return not bool(((got.double() - y).abs() <= bound).all())
 
 
 def negative_controls(fwd, W, dout):

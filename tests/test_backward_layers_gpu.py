@@ -30,6 +30,7 @@ from oracle import bf16_ref as R     # noqa: E402  (checker only)
 from oracle import bwd_ref as B      # noqa: E402
 
 import backward_cases as BC          # noqa: E402
+from guarded import Guards           # noqa: E402
 from test_bf16_layers_gpu import FLIP_MAX      # noqa: E402  (the bf16 layer file's cap on near-tie flips of one tensor)
 
 MEASURED = {'fp32 g': 0.970, 'fp32 dw': 0.413, 'fp32 db': 0.240, 'fp32 head_g': 0.357, 'fp32 head_dw': 0.016, 'fp32 head_db': 0.010,
@@ -150,13 +151,16 @@ class Net:
             assert b0 - w0 == self.Ws[i].numel() and e - b0 == self.Bs[i].numel()
             prm[w0:b0] = self.Ws[i].reshape(-1)
             prm[b0:e] = self.Bs[i]
-        self.prm = prm.cuda()
-        self.x = BC.tied_input(N, Cin, H, W, g).cuda()
-        self.dout = BC.sprinkle(torch.randn(N, Cin, H, W, generator=g)).cuda()
+        # every buffer the library writes lies between guard bands and starts as 0xFF bytes (the workspace at exactly the size the library asks
+        # for); what it only reads is a guarded copy whose bits are compared after every call (check)
+        self.gd = Guards()
+        self.prm = self.gd.ro(prm.cuda(), 'prm')
+        self.x = self.gd.ro(BC.tied_input(N, Cin, H, W, g).cuda(), 'x')
+        self.dout = self.gd.ro(BC.sprinkle(torch.randn(N, Cin, H, W, generator=g)).cuda(), 'dout')
         self.noise = torch.randn(N, Cin, H, W, generator=g).cuda()
         self.nbytes = lib.eld_unet_workspace_bytes(N, H, W, Cin, Cin)
-        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device='cuda')
-        self.out = torch.empty(N, Cin, H, W, device='cuda')
+        self.ws = self.gd.new((self.nbytes,), torch.uint8, 'workspace')
+        self.out = self.gd.new((N, Cin, H, W), name='out')
         self.tap_bytes = lib.eld_debug_unet_grad_tap_bytes(N, H, W, Cin, Cin, self.p)
         assert self.tap_bytes > 0
         self.algo = -1 if self.p else 1
@@ -164,15 +168,20 @@ class Net:
     def dims(self):
         return self.N, self.H, self.W, self.Cin, self.Cout
 
+    def check(self):
+        torch.cuda.synchronize()
+        self.gd.check()
+
     def forward(self, target=None, grad_scale=0.0):
         st = Lb().cur_stream()
         if target is None:
             Lb().check(self.lib.eld_unet_forward_ex(dp(self.x), dp(self.prm), dp(self.out), dp(self.ws), self.nbytes, *self.dims(), self.p, self.algo, st))
         else:
-            loss = torch.empty(1, device='cuda')
+            loss = self.gd.new((1,), name='loss')
             Lb().check(self.lib.eld_unet_forward_loss_ex(dp(self.x), dp(self.prm), dp(target), dp(self.out), dp(loss), dp(self.ws), self.nbytes, *self.dims(),
                                                          self.p, self.algo, 0, grad_scale, st))
-        torch.cuda.synchronize()
+        self.check()
+        assert target is None or not bool(torch.isnan(loss).any())
         return self.lib.eld_debug_unet_codes(dp(self.ws))
 
     def backward(self, dout, grads):
@@ -245,6 +254,7 @@ def test_unet_backward_teacher_forced(lib, prec, shape, mask, codes, fused):
             # target: the output itself at every 7th element (dout exactly 0 there), else off by noise of either sign; grad_scale = n: dout = +-1
             target = net.out + 0.1 * net.noise
             target.view(-1)[::7] = net.out.view(-1)[::7]
+            target = net.gd.ro(target, 'target')
             n = net.out.numel()
             have = net.forward(target, float(n))
             gs = float(np.float32(n) / np.float32(n))
@@ -256,14 +266,14 @@ def test_unet_backward_teacher_forced(lib, prec, shape, mask, codes, fused):
         fwd = net.regions(fused)
         before = {n_: lib.eld_debug_conv_kernel_count(n_.encode()) for n_ in NAMES[prec]}
         assert 0xFFFFFFFF not in before.values()
-        tap = torch.full((net.tap_bytes,), 0xFF, dtype=torch.uint8, device='cuda')         # NaN in fp32 and in bf16
+        tap = net.gd.new((net.tap_bytes,), torch.uint8, 'tap')                             # 0xFF bytes: NaN in fp32 and in bf16
         res = []
         lib.eld_debug_unet_grad_tap(dp(tap), tap.numel())
         try:
             for rep in range(2):
-                grads = torch.full((net.offs[46],), float('nan'), device='cuda')
+                grads = net.gd.new((net.offs[46],), name='grads')
                 Lb().check(net.backward(None if fused else net.dout, grads))
-                torch.cuda.synchronize()
+                net.check()
                 res.append(grads)
                 if rep == 0:
                     ran = {n_ for n_ in NAMES[prec] if lib.eld_debug_conv_kernel_count(n_.encode()) > before[n_]}
@@ -349,7 +359,7 @@ def test_tap_argument_checks(lib):
     finally:
         lib.eld_debug_unet_grad_tap(None, 0)
     Lb().check(net.backward(net.dout, grads))                 # unset: the plain backward
-    torch.cuda.synchronize()
+    net.check()
     assert bool(grads.any()) and not bool(tap.any())
 
 

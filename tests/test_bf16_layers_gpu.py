@@ -8,6 +8,9 @@ float64 values computed from the very bf16 operands the kernel read:
 Pools are bit-exact.  The whole network is checked teacher-forced: every layer against the reference applied to the kernel's own saved
 inputs (eld_debug_unet_region), so errors cannot compound across layers.  Negative controls (host-side tensors only) show that the rule
 rejects truncation, a dropped border / seam row, a bf16-rounded bias, a one-ulp change and a weight gradient without one border row.
+Every buffer of a call lies between guard bands (tests/guarded.py): outputs, gradients and the workspace (exactly the bytes the library asks
+for) start as 0xFF bytes -- 0xFFFF is a bf16 NaN, which the rounding rule rejects, so an element no kernel wrote fails --, operands are guarded
+copies; after each call the bands must be intact and the operands the same bits (done()).
 
 FLIP_MAX bounds the fraction of near-tie flips (accepted elements that are not rne_bf16(y64)) of any one tensor at 3x the largest rate
 measured on one MI355X; the measured figures are in FLIP_MEASURED / F32_MEASURED (worst fp32 error as a fraction of its bound)."""
@@ -20,6 +23,8 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip('torch')
 
 from oracle import bf16_ref as R     # noqa: E402  (checker only)
+
+from guarded import Guards           # noqa: E402
 
 FLIP_MEASURED = 3.9e-4               # largest near-tie flip rate of one tensor, one MI355X (this file)
 F32_MEASURED = 0.29                  # worst fp32 error as a fraction of its bound, same run
@@ -61,10 +66,17 @@ def rand_bf16(shape, g, scale=1.0):
     return R.rne_bf16(t).cuda()
 
 
-def ws_for(lib, N, H, W, Cin, Cout):
+def ws_for(lib, gd, N, H, W, Cin, Cout):
+    """the layer workspace at exactly the size the library asks for, between guard bands, every byte 0xFF"""
     n = lib.eld_layer_workspace_bytes(N, H, W, Cin, Cout)
     assert n > 0
-    return torch.empty(n, dtype=torch.uint8, device='cuda')
+    return gd.new((n,), torch.uint8, 'layer workspace')
+
+
+def done(gd):
+    """after a call, before the numeric check: nothing outside any buffer was written, no operand the kernels only read has changed"""
+    torch.cuda.synchronize()
+    gd.check()
 
 
 def family(lib):
@@ -128,20 +140,23 @@ FWD = [  # family, N, H, W, C0, C1, Cout    (one MI355X: 256 CUs decide which la
 @pytest.mark.parametrize('act', [1, 0])
 def test_conv3x3_forward_bf16(lib, fam, N, H, W, C0, C1, Cout, act):
     g = torch.Generator().manual_seed(N * H * W + C0 + 7 * C1 + Cout + act)
+    gd = Guards()
     x = rand_bf16((N, H, W, C0 + C1), g)
-    w = (torch.randn(Cout, C0 + C1, 3, 3, generator=g) / np.sqrt(9 * (C0 + C1))).cuda()
-    b = (0.5 * torch.randn(Cout, generator=g)).cuda()
-    x0 = i16(R.bits_of(x[..., :C0]))
-    x1 = i16(R.bits_of(x[..., C0:])) if C1 else None
-    out = torch.empty(N, H, W, Cout, dtype=torch.int16, device='cuda')
+    w = gd.ro((torch.randn(Cout, C0 + C1, 3, 3, generator=g) / np.sqrt(9 * (C0 + C1))).cuda(), 'w')
+    b = gd.ro((0.5 * torch.randn(Cout, generator=g)).cuda(), 'b')
+    x0 = gd.ro(i16(R.bits_of(x[..., :C0])), 'x0')
+    x1 = gd.ro(i16(R.bits_of(x[..., C0:])), 'x1') if C1 else None
+    out = gd.new((N, H, W, Cout), torch.int16, 'out')           # (0xFFFF everywhere, a bf16 NaN: an element the kernel does not write fails the rule)
     fuse = act and fam != 'conv_igemm<bf16>'
-    pool = torch.empty(N, H // 2, W // 2, Cout, dtype=torch.int16, device='cuda') if fuse else None
-    ws = ws_for(lib, N, H, W, C0 + C1, Cout)
+    pool = gd.new((N, H // 2, W // 2, Cout), torch.int16, 'pool') if fuse else None
+    ws = ws_for(lib, gd, N, H, W, C0 + C1, Cout)
     st = Lb().cur_stream()
     if act and not fuse:       # the generic kernel has no pooled epilogue
         assert lib.eld_conv3x3_forward_bf16(dp(x0), C0, dp(x1), C1, dp(w), dp(b), dp(out), dp(out), N, H, W, Cout, act, dp(ws), ws.numel(), st) == ELD_ENOTSUP
+        torch.cuda.synchronize()
+        assert bool((out == -1).all())                         # the refused call wrote no output (the workspace is scratch: the weights may be packed by then)
     Lb().check(lib.eld_conv3x3_forward_bf16(dp(x0), C0, dp(x1), C1, dp(w), dp(b), dp(out), dp(pool), N, H, W, Cout, act, dp(ws), ws.numel(), st))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == fam
     y, m = conv_ref(x, w, b, act)
     accept(out, y, m, fam)
@@ -161,14 +176,15 @@ def test_conv3x3_rounds_exact_ties_to_even(lib, fam, N, H, W, C, Cout):
          * torch.exp2(torch.randint(-1, 2, shape, generator=g).double())).double()
     x.view(-1)[::11] = 0.0
     x = x.cuda()
-    w = (torch.randint(-2, 3, (Cout, C, 3, 3), generator=g) / 2.0).float().cuda()
-    b = torch.zeros(Cout, device='cuda')
-    out = torch.empty(N, H, W, Cout, dtype=torch.int16, device='cuda')
-    ws = ws_for(lib, N, H, W, C, Cout)
-    x16 = i16(R.bits_of(x))
+    gd = Guards()
+    w = gd.ro((torch.randint(-2, 3, (Cout, C, 3, 3), generator=g) / 2.0).float().cuda(), 'w')
+    b = gd.ro(torch.zeros(Cout, device='cuda'), 'b')
+    out = gd.new((N, H, W, Cout), torch.int16, 'out')
+    ws = ws_for(lib, gd, N, H, W, C, Cout)
+    x16 = gd.ro(i16(R.bits_of(x)), 'x')
     Lb().check(lib.eld_conv3x3_forward_bf16(dp(x16), C, None, 0, dp(w), dp(b), dp(out), None, N, H, W, Cout, 0, dp(ws), ws.numel(),
                                             Lb().cur_stream()))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == fam
     y = R.conv3x3(x, w.double())
     assert bool((R.f64_of_bits(bits(out)) == R.rne_bf16(y)).all())
@@ -192,17 +208,18 @@ BWD = [  # family, N, H, W, Cin, Cout, split, slopes
 @pytest.mark.parametrize('fam,N,H,W,Cin,Cout,split,slopes', BWD)
 def test_conv3x3_backward_data_bf16(lib, fam, N, H, W, Cin, Cout, split, slopes):
     g = torch.Generator().manual_seed(3 * N * H * W + Cin + Cout + split)
+    gd = Guards()
     gy = rand_bf16((N, H, W, Cout), g)
-    w = (torch.randn(Cout, Cin, 3, 3, generator=g) / np.sqrt(9 * Cout)).cuda()
+    w = gd.ro((torch.randn(Cout, Cin, 3, 3, generator=g) / np.sqrt(9 * Cout)).cuda(), 'w')
     act = rand_bf16((N, H, W, Cin), g)
-    d0 = torch.empty(N, H, W, split, dtype=torch.int16, device='cuda')
-    d1 = torch.empty(N, H, W, Cin - split, dtype=torch.int16, device='cuda') if split < Cin else None
-    a0 = i16(R.bits_of(act[..., :split])) if slopes else None
-    ws = ws_for(lib, N, H, W, Cin, Cout)
-    g16 = i16(R.bits_of(gy))
+    d0 = gd.new((N, H, W, split), torch.int16, 'd0')
+    d1 = gd.new((N, H, W, Cin - split), torch.int16, 'd1') if split < Cin else None
+    a0 = gd.ro(i16(R.bits_of(act[..., :split])), 'act') if slopes else None
+    ws = ws_for(lib, gd, N, H, W, Cin, Cout)
+    g16 = gd.ro(i16(R.bits_of(gy)), 'gy')
     Lb().check(lib.eld_conv3x3_backward_data_bf16(dp(g16), dp(w), dp(d0), dp(d1), split, dp(a0), None, N, H, W, Cin, Cout,
                                                   dp(ws), ws.numel(), Lb().cur_stream()))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == fam
     wb = R.rne_bf16(w.double())
     y = R.conv3x3_bwd_data(gy, wb)
@@ -228,14 +245,15 @@ def test_conv3x3_backward_weight_bf16(lib, fam, N, H, W, C0, C1, Cout):
     g = torch.Generator().manual_seed(5 * N * H * W + C0 + C1 + Cout)
     gy = rand_bf16((N, H, W, Cout), g)
     x = rand_bf16((N, H, W, C0 + C1), g)
-    dw = torch.full((Cout, C0 + C1, 3, 3), float('nan'), device='cuda')
-    db = torch.full((Cout,), float('nan'), device='cuda')
-    ws = ws_for(lib, N, H, W, C0 + C1, Cout)
-    g16, x0 = i16(R.bits_of(gy)), i16(R.bits_of(x[..., :C0]))          # (named: a temporary's memory could be reused by the next one)
-    x1 = i16(R.bits_of(x[..., C0:])) if C1 else None
+    gd = Guards()
+    dw = gd.new((Cout, C0 + C1, 3, 3), name='dw')
+    db = gd.new((Cout,), name='db')
+    ws = ws_for(lib, gd, N, H, W, C0 + C1, Cout)
+    g16, x0 = gd.ro(i16(R.bits_of(gy)), 'gy'), gd.ro(i16(R.bits_of(x[..., :C0])), 'x0')
+    x1 = gd.ro(i16(R.bits_of(x[..., C0:])), 'x1') if C1 else None
     Lb().check(lib.eld_conv3x3_backward_weight_bf16(dp(g16), dp(x0), C0, dp(x1), C1, dp(dw), dp(db),
                                                     N, H, W, Cout, dp(ws), ws.numel(), Lb().cur_stream()))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == fam
     y, bound = wgrad_ref(gy, x)
     f32_check(dw, y, bound, fam + ' dW')
@@ -254,30 +272,31 @@ CT = [  # forward family, backward-data family, N, H, W (input resolution), Cin,
 @pytest.mark.parametrize('ffam,bfam,N,H,W,Cin,Cout', CT)
 def test_convt2x2_bf16(lib, ffam, bfam, N, H, W, Cin, Cout, wfam='wgrad<bf16,gather>'):      # wfam: tests/variant_child.py passes a variant's name
     g = torch.Generator().manual_seed(7 * N * H * W + Cin)
+    gd = Guards()
     x = rand_bf16((N, H, W, Cin), g)
-    w = (torch.randn(Cin, Cout, 2, 2, generator=g) / np.sqrt(Cin)).cuda()
-    b = (0.5 * torch.randn(Cout, generator=g)).cuda()
+    w = gd.ro((torch.randn(Cin, Cout, 2, 2, generator=g) / np.sqrt(Cin)).cuda(), 'w')
+    b = gd.ro((0.5 * torch.randn(Cout, generator=g)).cuda(), 'b')
     wb = R.rne_bf16(w.double())
-    ws = ws_for(lib, N, H, W, Cin, Cout)
+    ws = ws_for(lib, gd, N, H, W, Cin, Cout)
     st = Lb().cur_stream()
-    xb = i16(R.bits_of(x))
-    out = torch.empty(N, 2 * H, 2 * W, Cout, dtype=torch.int16, device='cuda')
+    xb = gd.ro(i16(R.bits_of(x)), 'x')
+    out = gd.new((N, 2 * H, 2 * W, Cout), torch.int16, 'out')
     Lb().check(lib.eld_convt2x2_forward_bf16(dp(xb), dp(w), dp(b), dp(out), N, H, W, Cin, Cout, dp(ws), ws.numel(), st))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == ffam
     accept(out, R.convt_fwd(x, wb) + b.double(), R.margin(R.convt_fwd(x * x, wb * wb), Cin, b), ffam)
     d = rand_bf16((N, 2 * H, 2 * W, Cout), g)
-    db16 = i16(R.bits_of(d))
-    din = torch.empty(N, H, W, Cin, dtype=torch.int16, device='cuda')
+    db16 = gd.ro(i16(R.bits_of(d)), 'd')
+    din = gd.new((N, H, W, Cin), torch.int16, 'din')
     Lb().check(lib.eld_convt2x2_backward_data_bf16(dp(db16), dp(w), dp(xb), dp(din), N, H, W, Cin, Cout, dp(ws), ws.numel(), st))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == bfam
     y, m = R.scale_ref(R.convt_bwd_data(d, wb), R.margin(R.convt_bwd_data(d * d, wb * wb), 4 * Cout), R.slope(x))
     accept(din, y, m, bfam)
-    dw = torch.full((Cin, Cout, 2, 2), float('nan'), device='cuda')
-    dbias = torch.full((Cout,), float('nan'), device='cuda')
+    dw = gd.new((Cin, Cout, 2, 2), name='dw')
+    dbias = gd.new((Cout,), name='dbias')
     Lb().check(lib.eld_convt2x2_backward_weight_bf16(dp(xb), dp(db16), dp(dw), dp(dbias), N, H, W, Cin, Cout, dp(ws), ws.numel(), st))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == wfam
     f32_check(dw, R.convt_wgrad(x, d), R.f32_bound(R.convt_wgrad(x * x, d * d), N * H * W, R.convt_wgrad(x.abs(), d.abs())), 'convT dW')
     yb, bb = colsum_ref(d)
@@ -292,18 +311,19 @@ def test_maxpool2x2_bf16_bit_exact(lib, N, Ho, Wo, C):
     x[:, ::3, 1, :, 1, :] = x[:, ::3, 0, :, 0, :]           # tied maxima: the first in row-major order takes the gradient
     x[:, 1::4, 1, :, 0, :] = x[:, 1::4, 0, :, 1, :]
     x = x.reshape(N, 2 * Ho, 2 * Wo, C).contiguous()
-    xb = i16(R.bits_of(x))
-    out = torch.empty(N, Ho, Wo, C, dtype=torch.int16, device='cuda')
+    gd = Guards()
+    xb = gd.ro(i16(R.bits_of(x)), 'x')
+    out = gd.new((N, Ho, Wo, C), torch.int16, 'out')
     st = Lb().cur_stream()
     Lb().check(lib.eld_maxpool2x2_forward_bf16(dp(xb), dp(out), N, Ho, Wo, C, st))
     dpool = rand_bf16((N, Ho, Wo, C), g)
     skip = rand_bf16((N, 2 * Ho, 2 * Wo, C), g)
-    gs = torch.empty(N, 2 * Ho, 2 * Wo, C, dtype=torch.int16, device='cuda')
-    gn = torch.empty_like(gs)
-    p16, s16 = i16(R.bits_of(dpool)), i16(R.bits_of(skip))
+    gs = gd.new((N, 2 * Ho, 2 * Wo, C), torch.int16, 'gs')
+    gn = gd.new((N, 2 * Ho, 2 * Wo, C), torch.int16, 'gn')
+    p16, s16 = gd.ro(i16(R.bits_of(dpool)), 'dpool'), gd.ro(i16(R.bits_of(skip)), 'skip')
     Lb().check(lib.eld_maxpool2x2_backward_bf16(dp(xb), dp(p16), dp(s16), dp(gs), N, Ho, Wo, C, st))
     Lb().check(lib.eld_maxpool2x2_backward_bf16(dp(xb), dp(p16), None, dp(gn), N, Ho, Wo, C, st))
-    torch.cuda.synchronize()
+    done(gd)
     assert bool((R.f64_of_bits(bits(out)) == R.maxpool_fwd(x)).all())
     assert bool((R.f64_of_bits(bits(gs)) == R.rne_bf16(R.maxpool_bwd_f32(x, dpool, skip))).all())
     assert bool((R.f64_of_bits(bits(gn)) == R.rne_bf16(R.maxpool_bwd_f32(x, dpool, None))).all())
@@ -317,12 +337,14 @@ def test_negative_controls_are_rejected(lib):
     x = rand_bf16((N, H, W, C), g)
     w = (torch.randn(Cout, C, 3, 3, generator=g) / np.sqrt(9 * C)).cuda()
     b = (0.5 * torch.randn(Cout, generator=g)).cuda()
-    out = torch.empty(N, H, W, Cout, dtype=torch.int16, device='cuda')
-    ws = ws_for(lib, N, H, W, C, Cout)
-    x16 = i16(R.bits_of(x))
+    gd = Guards()
+    w, b = gd.ro(w, 'w'), gd.ro(b, 'b')
+    out = gd.new((N, H, W, Cout), torch.int16, 'out')
+    ws = ws_for(lib, gd, N, H, W, C, Cout)
+    x16 = gd.ro(i16(R.bits_of(x)), 'x')
     Lb().check(lib.eld_conv3x3_forward_bf16(dp(x16), C, None, 0, dp(w), dp(b), dp(out), None, N, H, W, Cout, 1, dp(ws), ws.numel(),
                                             Lb().cur_stream()))
-    torch.cuda.synchronize()
+    done(gd)
     got = bits(out)
     y, m = conv_ref(x, w, b, 1)
     assert not rejects(got, y, m)
@@ -332,6 +354,9 @@ def test_negative_controls_are_rejected(lib):
         xd[n, r] = 0.0
         assert rejects(got, *conv_ref(xd, w, b, 1)), (n, r)
     assert rejects(got, *conv_ref(x, w, R.rne_bf16(b.double()).float(), 1))  # bias rounded to bf16
+    unwritten = got.clone()
+    unwritten[1, H - 1, W - 1, Cout - 1] = 0xFFFF                            # one element the kernel did not write (the buffers start as 0xFF bytes)
+    assert rejects(unwritten, y, m)
     r = R.rne_bf16(y)
     far = ((y - r).abs() < 0.1 * R.ulp_bf16(y)) & (got & 0x7FFF < 0x7F00) & (y.abs() > 1e-3)
     idx = int(far.reshape(-1).nonzero()[0])
@@ -340,11 +365,11 @@ def test_negative_controls_are_rejected(lib):
     assert rejects(one.reshape(got.shape), y, m)
     # the weight gradient: a reference that leaves one border pixel row out of the contraction
     gy = rand_bf16((N, H, W, Cout), g)
-    dw = torch.empty(Cout, C, 3, 3, device='cuda')
-    g16 = i16(R.bits_of(gy))
+    dw = gd.new((Cout, C, 3, 3), name='dw')
+    g16 = gd.ro(i16(R.bits_of(gy)), 'gy')
     Lb().check(lib.eld_conv3x3_backward_weight_bf16(dp(g16), dp(x16), C, None, 0, dp(dw), None, N, H, W, Cout,
                                                     dp(ws), ws.numel(), Lb().cur_stream()))
-    torch.cuda.synchronize()
+    done(gd)
     yw, bound = wgrad_ref(gy, x)
     assert bool(((dw.double() - yw).abs() <= bound).all())
     gd = gy.clone()
@@ -372,16 +397,17 @@ def test_unet_bf16_teacher_forced(lib, N, Cin, H, W):
         fan = (b0 - w0) // (e - b0)
         prm[w0:b0] = torch.randn(b0 - w0, generator=g) * np.sqrt(2.0 / fan)
         prm[b0:e] = 0.1 * torch.randn(e - b0, generator=g)
-    prm = prm.cuda()
+    gd = Guards()
+    prm = gd.ro(prm.cuda(), 'prm')
     x = torch.rand(N, Cin, H, W, generator=g)
     x.view(-1)[::17] = 0.0
-    x = x.cuda()
+    x = gd.ro(x.cuda(), 'x')
     nbytes = lib.eld_unet_workspace_bytes(N, H, W, Cin, Cout)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
-    out = torch.empty(N, Cout, H, W, device='cuda')
+    ws = gd.new((nbytes,), torch.uint8, 'workspace')           # exactly the bytes the library asks for, every one 0xFF
+    out = gd.new((N, Cout, H, W), name='out')
     st = Lb().cur_stream()
     Lb().check(lib.eld_unet_forward_ex(dp(x), dp(prm), dp(out), dp(ws), nbytes, N, H, W, Cin, Cout, 1, -1, st))
-    torch.cuda.synchronize()
+    done(gd)
 
     def Wt(i, shape):
         return prm[offs[2 * i]:offs[2 * i + 1]].reshape(shape)
@@ -444,10 +470,10 @@ def test_unet_bf16_teacher_forced(lib, N, Cin, H, W):
     bo = R.f32_bound(torch.einsum('nyxc,oc->noyx', db0 * db0, wh_ * wh_), 32) + R.C_ACC * R.U32 * (yo.abs() + Bs(22).double().abs()[None, :, None, None])
     f32_check(out, yo, bo, 'head output')
     # backward
-    dout = torch.randn(N, Cout, H, W, generator=g).cuda()
-    grads = torch.full((offs[46],), float('nan'), device='cuda')
+    dout = gd.ro(torch.randn(N, Cout, H, W, generator=g).cuda(), 'dout')
+    grads = gd.new((offs[46],), name='grads')
     Lb().check(lib.eld_unet_backward_ex(dp(dout), dp(prm), dp(grads), dp(ws), nbytes, N, H, W, Cin, Cout, 1, -1, None, None, 0, st))
-    torch.cuda.synchronize()
+    done(gd)
     d64 = dout.double()
     K = N * H * W
     yw = torch.einsum('noyx,nyxc->oc', d64, db0)

@@ -15,6 +15,10 @@ run these same checks in one fresh interpreter per setting: tests/test_env_varia
 (tests/test_unet_gpu.py runs them).  The backward's call sites -- every gradient stage of unet_backward<float>, teacher-forced through the gradient
 tap, slope and pool codes live and masked -- are in tests/test_backward_layers_gpu.py.
 
+Every buffer of a call lies between guard bands (tests/guarded.py): outputs, gradients and the workspace (exactly the bytes the library asks
+for) start as 0xFF bytes -- NaN, which check() rejects, so an element no kernel wrote fails --, operands are guarded copies; after each call
+the bands must be intact and the operands the same bits (done()).
+
 F32_MEASURED: worst error as a fraction of its bound per family, one MI355X (this file)."""
 import ctypes as C
 
@@ -26,6 +30,8 @@ torch = pytest.importorskip('torch')
 
 from oracle import bf16_ref as R     # noqa: E402  (checker only)
 from oracle import f32_ref as F3     # noqa: E402
+
+from guarded import Guards           # noqa: E402
 
 F32_MEASURED = {'conv_x3w': 0.688, 'conv_x3<32>': 0.461, 'conv_x3d<64,8>': 0.824, 'conv_x3d<128,8>': 0.767, 'conv_x3d<64,4>': 0.539,
                 'conv_x3_gemm<1x1>': 0.548, 'conv_x3_gemm<gather>': 0.492, 'conv_igemm<f32>': 0.440, 'wgrad8<f32,128x64>': 0.129,
@@ -55,10 +61,17 @@ def dp(t):
     return Lb().dptr(t)
 
 
-def ws_for(lib, N, H, W, Cin, Cout):
+def ws_for(lib, gd, N, H, W, Cin, Cout):
+    """the layer workspace at exactly the size the library asks for, between guard bands, every byte 0xFF"""
     n = lib.eld_layer_workspace_bytes(N, H, W, Cin, Cout)
     assert n > 0
-    return torch.empty(n, dtype=torch.uint8, device='cuda')
+    return gd.new((n,), torch.uint8, 'layer workspace')
+
+
+def done(gd):
+    """after a call, before the numeric check: nothing outside any buffer was written, no operand the kernels only read has changed"""
+    torch.cuda.synchronize()
+    gd.check()
 
 
 def family(lib):
@@ -66,13 +79,17 @@ def family(lib):
 
 
 def check(got, y, bound, fam, what=''):
+    """an element passes only if err <= bound is true: a NaN in got (an element no kernel wrote: the outputs start as NaN) fails, and so does a
+    worst ratio that is NaN (recorded as inf: max() would drop it)"""
     err = (got.double() - y).abs()
     r = float((err / bound.clamp_min(1e-300)).max())
+    r = r if r == r else float('inf')
     STATS[fam] = max(STATS.get(fam, 0.0), r)
     print('%s %s: worst error / bound %.3f' % (fam, what, r))
-    bad = err > bound
-    assert not bool(bad.any()), '%s %s: %d of %d elements outside the bound, worst %.3f of it, first at %s' % (
-        fam, what, int(bad.sum()), bad.numel(), r, tuple(bad.nonzero()[0].tolist()))
+    bad = ~(err <= bound)
+    assert not bool(bad.any()), '%s %s: %d of %d elements outside the bound (%d of them NaN), worst %.3f of it, first at %s' % (
+        fam, what, int(bad.sum()), bad.numel(), int(torch.isnan(got).sum()), r, tuple(bad.nonzero()[0].tolist()))
+    assert r != float('inf'), '%s %s: the worst error / bound is not a number' % (fam, what)
 
 
 def sprinkle(t):
@@ -124,13 +141,14 @@ def test_conv3x3_forward_f32(lib, fam, N, H, W, C0, C1, Cout, act, kind):
     g = torch.Generator().manual_seed(N * H * W + C0 + 7 * C1 + Cout + act)
     Cin = C0 + C1
     x, w = operands(kind, (N, H, W, Cin), (Cout, Cin, 3, 3), 9 * Cin, g)
-    b = (0.5 * torch.randn(Cout, generator=g)).cuda()
-    x0 = x[..., :C0].contiguous()
-    x1 = x[..., C0:].contiguous() if C1 else None
-    out = torch.full((N, H, W, Cout), float('nan'), device='cuda')
-    ws = ws_for(lib, N, H, W, Cin, Cout)
+    gd = Guards()
+    w, b = gd.ro(w, 'w'), gd.ro((0.5 * torch.randn(Cout, generator=g)).cuda(), 'b')
+    x0 = gd.ro(x[..., :C0].contiguous(), 'x0')
+    x1 = gd.ro(x[..., C0:].contiguous(), 'x1') if C1 else None
+    out = gd.new((N, H, W, Cout), name='out')                   # (NaN everywhere: an element the kernel does not write fails the check)
+    ws = ws_for(lib, gd, N, H, W, Cin, Cout)
     Lb().check(lib.eld_conv3x3_forward(dp(x0), C0, dp(x1), C1, dp(w), dp(b), dp(out), N, H, W, Cout, act, dp(ws), ws.numel(), Lb().cur_stream()))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == fam
     s, m = bound_of(R.conv3x3, x.double(), w.double(), 9 * Cin, kind, b)
     y = s + b.double()
@@ -155,13 +173,15 @@ BWD = [  # family, N, H, W, Cin, Cout, split
 def test_conv3x3_backward_data_f32(lib, fam, N, H, W, Cin, Cout, split, kind):
     g = torch.Generator().manual_seed(3 * N * H * W + Cin + Cout + split)
     gy, w = operands(kind, (N, H, W, Cout), (Cout, Cin, 3, 3), 9 * Cout, g)
-    act = sprinkle(torch.randn(N, H, W, split, generator=g)).cuda()
-    d0 = torch.full((N, H, W, split), float('nan'), device='cuda')
-    d1 = torch.full((N, H, W, Cin - split), float('nan'), device='cuda') if split < Cin else None
-    ws = ws_for(lib, N, H, W, Cin, Cout)
+    gd = Guards()
+    gy, w = gd.ro(gy, 'gy'), gd.ro(w, 'w')
+    act = gd.ro(sprinkle(torch.randn(N, H, W, split, generator=g)).cuda(), 'act')
+    d0 = gd.new((N, H, W, split), name='d0')
+    d1 = gd.new((N, H, W, Cin - split), name='d1') if split < Cin else None
+    ws = ws_for(lib, gd, N, H, W, Cin, Cout)
     Lb().check(lib.eld_conv3x3_backward_data(dp(gy), dp(w), dp(d0), dp(d1), split, dp(act), None, N, H, W, Cin, Cout,
                                              dp(ws), ws.numel(), Lb().cur_stream()))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == fam
     y, m = bound_of(R.conv3x3_bwd_data, gy.double(), w.double(), 9 * Cout, kind)
     y0, m0 = R.scale_ref(y[..., :split], m[..., :split], R.slope(act.double()))
@@ -210,16 +230,18 @@ def test_conv3x3_backward_weight_f32(lib, fam, N, H, W, C0, C1, Cout, kind):
     else:
         gy = sprinkle(torch.randn(N, H, W, Cout, generator=g)).cuda()
         x = sprinkle(torch.randn(N, H, W, Cin, generator=g)).cuda()
-    x0 = x[..., :C0].contiguous()
-    x1 = x[..., C0:].contiguous() if C1 else None
-    ws = ws_for(lib, N, H, W, Cin, Cout)
+    gd = Guards()
+    gy = gd.ro(gy, 'gy')
+    x0 = gd.ro(x[..., :C0].contiguous(), 'x0')
+    x1 = gd.ro(x[..., C0:].contiguous(), 'x1') if C1 else None
+    ws = ws_for(lib, gd, N, H, W, Cin, Cout)
     res = []
-    for _ in range(2):                  # fixed reduction order, no atomics: the same bits twice
-        dw = torch.full((Cout, Cin, 3, 3), float('nan'), device='cuda')
-        db = torch.full((Cout,), float('nan'), device='cuda')
+    for _ in range(2):                  # fixed reduction order, no atomics: the same bits twice (the second time from a used workspace)
+        dw = gd.new((Cout, Cin, 3, 3), name='dw')
+        db = gd.new((Cout,), name='db')
         Lb().check(lib.eld_conv3x3_backward_weight(dp(gy), dp(x0), C0, dp(x1), C1, dp(dw), dp(db), N, H, W, Cout, dp(ws), ws.numel(),
                                                    Lb().cur_stream()))
-        torch.cuda.synchronize()
+        done(gd)
         assert family(lib) == fam
         res.append((dw, db))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
@@ -247,21 +269,23 @@ CT = [  # forward, backward-data and weight-gradient family (None: the entry poi
 def test_convt2x2_f32(lib, ffam, bfam, wfam, N, H, W, Cin, Cout, kind):
     g = torch.Generator().manual_seed(7 * N * H * W + Cin)
     x, w = operands(kind, (N, H, W, Cin), (Cin, Cout, 2, 2), Cin, g)
-    b = (0.5 * torch.randn(Cout, generator=g)).cuda()
-    ws = ws_for(lib, N, H, W, Cin, Cout)
+    gd = Guards()
+    x, w, b = gd.ro(x, 'x'), gd.ro(w, 'w'), gd.ro((0.5 * torch.randn(Cout, generator=g)).cuda(), 'b')
+    ws = ws_for(lib, gd, N, H, W, Cin, Cout)
     st = Lb().cur_stream()
-    out = torch.full((N, 2 * H, 2 * W, Cout), float('nan'), device='cuda')
+    out = gd.new((N, 2 * H, 2 * W, Cout), name='out')
     Lb().check(lib.eld_convt2x2_forward(dp(x), dp(w), dp(b), dp(out), N, H, W, Cin, Cout, dp(ws), ws.numel(), st))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == ffam
     s, m = bound_of(R.convt_fwd, x.double(), w.double(), Cin, kind, b)
     check(out, s + b.double(), m, ffam, 'convT forward %s' % kind)
     if bfam is None:
         return
     d, w2 = operands(kind, (N, 2 * H, 2 * W, Cout), (Cin, Cout, 2, 2), 4 * Cout, g)
-    din = torch.full((N, H, W, Cin), float('nan'), device='cuda')
+    d, w2 = gd.ro(d, 'd'), gd.ro(w2, 'w2')
+    din = gd.new((N, H, W, Cin), name='din')
     Lb().check(lib.eld_convt2x2_backward_data(dp(d), dp(w2), dp(x), dp(din), N, H, W, Cin, Cout, dp(ws), ws.numel(), st))
-    torch.cuda.synchronize()
+    done(gd)
     assert family(lib) == bfam
     y, m = bound_of(R.convt_bwd_data, d.double(), w2.double(), 4 * Cout, kind)
     check(din, *R.scale_ref(y, m, R.slope(x.double())), bfam, 'convT backward-data %s' % kind)
@@ -269,13 +293,13 @@ def test_convt2x2_f32(lib, ffam, bfam, wfam, N, H, W, Cin, Cout, kind):
     if kind == 'exposure':
         if K > F3.EXPOSURE_MAX_K:                     # (2, 45, 67): the exposure operands no longer separate the piece products; zero-mean data only
             return
-        d = F3.exposure_operands((N, 2 * H, 2 * W, Cout), g, 2.0 ** -K.bit_length()).cuda()
+        d = gd.ro(F3.exposure_operands((N, 2 * H, 2 * W, Cout), g, 2.0 ** -K.bit_length()).cuda(), 'd (exposure)')
     res = []
     for _ in range(2):
-        dw = torch.full((Cin, Cout, 2, 2), float('nan'), device='cuda')
-        dbias = torch.full((Cout,), float('nan'), device='cuda')
+        dw = gd.new((Cin, Cout, 2, 2), name='dw')
+        dbias = gd.new((Cout,), name='dbias')
         Lb().check(lib.eld_convt2x2_backward_weight(dp(x), dp(d), dp(dw), dp(dbias), N, H, W, Cin, Cout, dp(ws), ws.numel(), st))
-        torch.cuda.synchronize()
+        done(gd)
         assert family(lib) == wfam
         res.append((dw, dbias))
     assert torch.equal(res[0][0], res[1][0]) and torch.equal(res[0][1], res[1][1])
@@ -320,17 +344,18 @@ def test_unet_fp32_teacher_forced(lib, N, Cin, H, W):
         fan = (b0 - w0) // (e - b0)
         prm[w0:b0] = torch.randn(b0 - w0, generator=g) * np.sqrt(2.0 / fan)
         prm[b0:e] = 0.1 * torch.randn(e - b0, generator=g)
-    prm = prm.cuda()
+    gd = Guards()
+    prm = gd.ro(prm.cuda(), 'prm')
     x = torch.rand(N, Cin, H, W, generator=g)
     x.view(-1)[::17] = 0.0
-    x = x.cuda()
+    x = gd.ro(x.cuda(), 'x')
     nbytes = lib.eld_unet_workspace_bytes(N, H, W, Cin, Cout)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device='cuda')
-    out = torch.empty(N, Cout, H, W, device='cuda')
+    ws = gd.new((nbytes,), torch.uint8, 'workspace')           # exactly the bytes the library asks for, every one 0xFF
+    out = gd.new((N, Cout, H, W), name='out')
     before = {n: lib.eld_debug_conv_kernel_count(n.encode()) for n in NAMES}
     assert 0xFFFFFFFF not in before.values()           # (the counter's table of names is full: its answers are unknown)
     Lb().check(lib.eld_unet_forward_ex(dp(x), dp(prm), dp(out), dp(ws), nbytes, N, H, W, Cin, Cout, 0, 1, Lb().cur_stream()))
-    torch.cuda.synchronize()
+    done(gd)
     ran = {n for n in NAMES if lib.eld_debug_conv_kernel_count(n.encode()) > before[n]}
     print('families in the forward of', (N, Cin, H, W), sorted(ran))
     assert ran == RAN[(N, Cin, H, W)]

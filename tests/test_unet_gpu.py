@@ -13,6 +13,8 @@ import torch.nn.functional as F      # noqa: E402
 
 from oracle import unet_ref as U     # noqa: E402  (checker only)
 
+from guarded import Guards           # noqa: E402
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -44,13 +46,30 @@ def ws_for(lib, N, H, W, Cin, Cout):
     return torch.empty(n, dtype=torch.uint8, device='cuda')
 
 
+def gws_for(lib, gd, N, H, W, Cin, Cout):
+    """the layer workspace at exactly the size the library asks for, between guard bands (tests/guarded.py), every byte 0xFF"""
+    n = lib.eld_layer_workspace_bytes(N, H, W, Cin, Cout)
+    assert n > 0
+    return gd.new((n,), torch.uint8, 'layer workspace')
+
+
+def done(gd):
+    """after a call, before the numeric check: nothing outside any buffer was written, no operand the kernels only read has changed"""
+    torch.cuda.synchronize()
+    gd.check()
+
+
 def close(got, ref64, tol=1e-5, scale=None):
-    """|got - ref| <= tol * (1 + scale) elementwise; scale = magnitude of the accumulated terms (fp64)."""
+    """|got - ref| <= tol * (1 + scale) elementwise; scale = magnitude of the accumulated terms (fp64).  An element passes only if the
+    comparison is true: NaN or inf in got fails."""
     got = got.detach().cpu().double()
     err = (got - ref64).abs()
     bound = tol * (1.0 + (scale if scale is not None else ref64.abs()))
-    bad = (err > bound)
-    assert not bad.any(), 'max err %.3e (bound %.3e) at %d elements' % (float(err.max()), float(bound.max() if torch.is_tensor(bound) else bound), int(bad.sum()))
+    bad = ~(err <= bound)
+    worst = float(err.max())
+    assert not bad.any(), 'max err %.3e (bound %.3e) at %d elements (%d NaN)' % (worst, float(bound.max() if torch.is_tensor(bound) else bound), int(bad.sum()),
+                                                                                  int(torch.isnan(got).sum()))
+    assert worst == worst, 'the worst error is not a number'
 
 
 CASES = [  # N, H, W, C0, C1, Cout
@@ -72,13 +91,15 @@ def test_conv3x3_forward(lib, N, H, W, C0, C1, Cout, act, algo):
     mag = F.conv2d(x.double().abs(), w.double().abs(), b.double().abs(), padding=1)
     if act:
         ref = torch.max(0.2 * ref, ref)
-    x0 = nhwc(x[:, :C0]).cuda()
-    x1 = nhwc(x[:, C0:]).cuda() if C1 else None
-    out = torch.empty(N, H, W, Cout, device='cuda')
-    ws = ws_for(lib, N, H, W, C0 + C1, Cout)
-    wd_, bd_ = w.cuda(), b.cuda()           # keep device operands alive across the async call
+    gd = Guards()
+    x0 = gd.ro(nhwc(x[:, :C0]).cuda(), 'x0')
+    x1 = gd.ro(nhwc(x[:, C0:]).cuda(), 'x1') if C1 else None
+    out = gd.new((N, H, W, Cout), name='out')
+    ws = gws_for(lib, gd, N, H, W, C0 + C1, Cout)
+    wd_, bd_ = gd.ro(w.cuda(), 'w'), gd.ro(b.cuda(), 'b')
     L.check(lib.eld_conv3x3_forward(L.dptr(x0), C0, L.dptr(x1), C1, L.dptr(wd_), L.dptr(bd_), L.dptr(out), N, H, W, Cout, act,
                                     L.dptr(ws), ws.numel(), L.cur_stream()))
+    done(gd)
     close(nchw(out), ref, tol=2e-6, scale=mag)
     ref32 = F.conv2d(x, w, b, padding=1)
     if act:
@@ -98,13 +119,15 @@ def test_conv3x3_backward_data(lib, N, H, W, Cin, Cout, split, algo):
     ref = torch.nn.grad.conv2d_input((N, Cin, H, W), w.double(), gy.double(), padding=1)
     mag = torch.nn.grad.conv2d_input((N, Cin, H, W), w.double().abs(), gy.double().abs(), padding=1)
     slope = torch.where(act > 0, 1.0, torch.where(act < 0, 0.2, 0.6)).double()
-    d0 = torch.empty(N, H, W, split, device='cuda')
-    d1 = torch.empty(N, H, W, Cin - split, device='cuda') if split < Cin else None
-    a0 = nhwc(act[:, :split]).cuda()
-    ws = ws_for(lib, N, H, W, Cin, Cout)
-    gyd_, wd_ = nhwc(gy).cuda(), w.cuda()
+    gd = Guards()
+    d0 = gd.new((N, H, W, split), name='d0')
+    d1 = gd.new((N, H, W, Cin - split), name='d1') if split < Cin else None
+    a0 = gd.ro(nhwc(act[:, :split]).cuda(), 'act')
+    ws = gws_for(lib, gd, N, H, W, Cin, Cout)
+    gyd_, wd_ = gd.ro(nhwc(gy).cuda(), 'gy'), gd.ro(w.cuda(), 'w')
     L.check(lib.eld_conv3x3_backward_data(L.dptr(gyd_), L.dptr(wd_), L.dptr(d0), L.dptr(d1), split, L.dptr(a0), None,
                                           N, H, W, Cin, Cout, L.dptr(ws), ws.numel(), L.cur_stream()))
+    done(gd)
     close(nchw(d0), ref[:, :split] * slope[:, :split], tol=2e-6, scale=mag[:, :split])
     if d1 is not None:
         close(nchw(d1), ref[:, split:], tol=2e-6, scale=mag[:, split:])      # second half: no activation in front
@@ -118,15 +141,19 @@ def test_conv3x3_backward_weight(lib, N, H, W, C0, C1, Cout, algo):
     gy = torch.randn(N, Cout, H, W, generator=g)
     ref = torch.nn.grad.conv2d_weight(x.double(), (Cout, C0 + C1, 3, 3), gy.double(), padding=1)
     mag = torch.nn.grad.conv2d_weight(x.double().abs(), (Cout, C0 + C1, 3, 3), gy.double().abs(), padding=1)
-    x0 = nhwc(x[:, :C0]).cuda()
-    x1 = nhwc(x[:, C0:]).cuda() if C1 else None
-    dw = torch.full((Cout, C0 + C1, 3, 3), float('nan'), device='cuda')
-    db = torch.full((Cout,), float('nan'), device='cuda')
-    ws = ws_for(lib, N, H, W, C0 + C1, Cout)
-    gyd_ = nhwc(gy).cuda()
+    gd = Guards()
+    x0 = gd.ro(nhwc(x[:, :C0]).cuda(), 'x0')
+    x1 = gd.ro(nhwc(x[:, C0:]).cuda(), 'x1') if C1 else None
+    dw = gd.new((Cout, C0 + C1, 3, 3), name='dw')
+    db = gd.new((Cout,), name='db')
+    ws = gws_for(lib, gd, N, H, W, C0 + C1, Cout)
+    gyd_ = gd.ro(nhwc(gy).cuda(), 'gy')
     for _ in range(2):      # run twice: bit-stable (fixed reduction order, no atomics)
+        dw.guard.fill(0xFF)
+        db.guard.fill(0xFF)
         L.check(lib.eld_conv3x3_backward_weight(L.dptr(gyd_), L.dptr(x0), C0, L.dptr(x1), C1, L.dptr(dw), L.dptr(db), N, H, W, Cout,
                                                 L.dptr(ws), ws.numel(), L.cur_stream()))
+        done(gd)
         cur = (dw.clone(), db.clone())
         if _:
             assert torch.equal(cur[0], prev[0]) and torch.equal(cur[1], prev[1])
@@ -196,29 +223,33 @@ def test_conv_transpose2x2(lib, N, H, W, Cin, Cout, algo):
     w = torch.randn(Cin, Cout, 2, 2, generator=g) / np.sqrt(Cin)
     b = torch.randn(Cout, generator=g)
     gy = torch.randn(N, Cout, 2 * H, 2 * W, generator=g)
-    ws = ws_for(lib, N, H, W, Cin, Cout)
+    gd = Guards()
+    ws = gws_for(lib, gd, N, H, W, Cin, Cout)
     xd = x.double().requires_grad_(True)
     wd = w.double().requires_grad_(True)
     bd = b.double().requires_grad_(True)
     ref = F.conv_transpose2d(xd, wd, bd, stride=2)
     ref.backward(gy.double())
-    out = torch.empty(N, 2 * H, 2 * W, Cout, device='cuda')
-    xd_, wd_, bd_ = nhwc(x).cuda(), w.cuda(), b.cuda()
+    out = gd.new((N, 2 * H, 2 * W, Cout), name='out')
+    xd_, wd_, bd_ = gd.ro(nhwc(x).cuda(), 'x'), gd.ro(w.cuda(), 'w'), gd.ro(b.cuda(), 'b')
     L.check(lib.eld_convt2x2_forward(L.dptr(xd_), L.dptr(wd_), L.dptr(bd_), L.dptr(out), N, H, W, Cin, Cout,
                                      L.dptr(ws), ws.numel(), L.cur_stream()))
+    done(gd)
     mag = F.conv_transpose2d(x.double().abs(), w.double().abs(), b.double().abs(), stride=2)
     close(nchw(out), ref.detach(), tol=2e-6, scale=mag)
-    din = torch.empty(N, H, W, Cin, device='cuda')
-    gyd = nhwc(gy).cuda()
+    din = gd.new((N, H, W, Cin), name='din')
+    gyd = gd.ro(nhwc(gy).cuda(), 'gy')
     L.check(lib.eld_convt2x2_backward_data(L.dptr(gyd), L.dptr(wd_), L.dptr(xd_), L.dptr(din), N, H, W, Cin, Cout,
                                            L.dptr(ws), ws.numel(), L.cur_stream()))
+    done(gd)
     slope = torch.where(x > 0, 1.0, torch.where(x < 0, 0.2, 0.6)).double()
     magd = F.conv2d(gy.double().abs(), w.double().abs().permute(0, 1, 2, 3), stride=2)       # |gy| * |w| summed: conv with (Cin,Cout,2,2)
     close(nchw(din), xd.grad * slope, tol=2e-6, scale=magd)
-    dw = torch.empty(Cin, Cout, 2, 2, device='cuda')
-    db = torch.empty(Cout, device='cuda')
+    dw = gd.new((Cin, Cout, 2, 2), name='dw')
+    db = gd.new((Cout,), name='db')
     L.check(lib.eld_convt2x2_backward_weight(L.dptr(xd_), L.dptr(gyd), L.dptr(dw), L.dptr(db), N, H, W, Cin, Cout,
                                              L.dptr(ws), ws.numel(), L.cur_stream()))
+    done(gd)
     close(dw, wd.grad, tol=2e-6, scale=wd.grad.abs() + float(np.sqrt(N * H * W)) * 3)
     close(db, bd.grad, tol=2e-6, scale=gy.double().abs().sum(dim=(0, 2, 3)))
 
@@ -232,17 +263,20 @@ def test_maxpool(lib):
     x[:, :, 4:6, 4:6] = 0.0                                                      # tie + zero activation
     dp = torch.randn(N, C, Ho, Wo, generator=g)
     skip = torch.randn(N, C, 2 * Ho, 2 * Wo, generator=g)
-    out = torch.empty(N, Ho, Wo, C, device='cuda')
-    xd_, dpd_, skd_ = nhwc(x).cuda(), nhwc(dp).cuda(), nhwc(skip).cuda()
+    gd = Guards()
+    out = gd.new((N, Ho, Wo, C), name='out')
+    xd_, dpd_, skd_ = gd.ro(nhwc(x).cuda(), 'x'), gd.ro(nhwc(dp).cuda(), 'dpool'), gd.ro(nhwc(skip).cuda(), 'skip')
     L.check(lib.eld_maxpool2x2_forward(L.dptr(xd_), L.dptr(out), N, Ho, Wo, C, L.cur_stream()))
+    done(gd)
     assert torch.equal(nchw(out).cpu(), F.max_pool2d(x, 2))
     xr = x.clone().requires_grad_(True)
     F.max_pool2d(xr, 2).backward(dp)
     slope = torch.where(x > 0, 1.0, torch.where(x < 0, 0.2, 0.6))
     for sk in (skip, None):
-        gout = torch.empty(N, 2 * Ho, 2 * Wo, C, device='cuda')
+        gout = gd.new((N, 2 * Ho, 2 * Wo, C), name='gout')
         L.check(lib.eld_maxpool2x2_backward(L.dptr(xd_), L.dptr(dpd_), L.dptr(skd_) if sk is not None else None,
                                             L.dptr(gout), N, Ho, Wo, C, L.cur_stream()))
+        done(gd)
         ref = (xr.grad + (sk if sk is not None else 0)) * slope
         assert torch.equal(nchw(gout).cpu(), ref)
 
@@ -254,18 +288,23 @@ def test_l1_and_adam(lib):
     out = torch.randn(n, generator=g)
     tgt = torch.randn(n, generator=g)
     tgt[:10] = out[:10]
-    dout = torch.empty(n, device='cuda')
-    loss = torch.zeros(1, device='cuda')
-    ws = torch.empty(lib.eld_l1_workspace_bytes(), dtype=torch.uint8, device='cuda')
-    od_, td_ = out.cuda(), tgt.cuda()
+    gd = Guards()
+    dout = gd.new((n,), name='dout')
+    loss = gd.new((1,), name='loss')
+    ws = gd.new((lib.eld_l1_workspace_bytes(),), torch.uint8, 'loss workspace')
+    od_, td_ = gd.ro(out.cuda(), 'out'), gd.ro(tgt.cuda(), 'target')
     L.check(lib.eld_l1_loss(L.dptr(od_), L.dptr(td_), L.dptr(dout), L.dptr(loss), L.dptr(ws), n, 1.0, L.cur_stream()))
+    done(gd)
     o = out.clone().requires_grad_(True)
     lref = F.l1_loss(o, tgt)
     lref.backward()
     assert abs(float(loss) - float(lref)) < 1e-6
     assert torch.equal(dout.cpu(), o.grad)
     # --loss l2 (models/losses.py:34): nn.MSELoss and its gradient
+    dout.guard.fill(0xFF)
+    loss.guard.fill(0xFF)
     L.check(lib.eld_mse_loss(L.dptr(od_), L.dptr(td_), L.dptr(dout), L.dptr(loss), L.dptr(ws), n, 1.0, L.cur_stream()))
+    done(gd)
     o2 = out.clone().requires_grad_(True)
     lref2 = F.mse_loss(o2, tgt)
     lref2.backward()
@@ -275,15 +314,121 @@ def test_l1_and_adam(lib):
     p = torch.randn(10007, generator=g)
     pr = p.clone().requires_grad_(True)
     opt = torch.optim.Adam([pr], lr=1e-4, betas=(0.9, 0.999))
-    pd, m, v = p.cuda(), torch.zeros(10007, device='cuda'), torch.zeros(10007, device='cuda')
+    pd, m, v = gd.new((10007,), name='p', src=p), gd.new((10007,), name='m', src=torch.zeros(10007)), gd.new((10007,), name='v', src=torch.zeros(10007))
     for step in range(1, 6):
         gr = torch.randn(10007, generator=g) * 0.01
         pr.grad = gr.clone()
         opt.step()
-        grd_ = gr.cuda()
+        grd_ = gd.ro(gr.cuda(), 'grad %d' % step)
         L.check(lib.eld_adam_step(L.dptr(pd), L.dptr(grd_), L.dptr(m), L.dptr(v), 10007, 1e-4, 0.9, 0.999, 1e-8, 0.0, step, 1.0, L.cur_stream()))
-        torch.cuda.synchronize()
+        done(gd)
     assert (pd.cpu() - pr.detach()).abs().max() < 5e-7      # a few ulp at |p| ~ 1
+
+
+ADAM = dict(lr=1e-4, b1=0.9, b2=0.999, eps=1e-8)
+ADAM_PHASES = [range(1, 6), range(100000, 100005)]
+ADAM_TORCH_F32_VS_F64 = [4.68e-7, 6.12e-7]                  # see test_adam_weight_decay_and_grad_scale
+
+
+def _adam_inputs(n):
+    g = torch.Generator().manual_seed(2024)
+    p = torch.randn(n, generator=g)
+    return p, [[torch.randn(n, generator=g) * 0.01 for _ in ph] for ph in ADAM_PHASES]
+
+
+def _adam_f64(p, grads, wd, gs):
+    """the comment above adam_kernel (csrc/unet_misc.hip), restated in float64: g' = g gs + wd p; m = b1 m + (1 - b1) g'; v = b2 v + (1 - b2) g'^2;
+    p -= (lr / (1 - b1^t)) m / (sqrt(v) / sqrt(1 - b2^t) + eps).  Returns (p, m, v) after each phase; m and v carry over."""
+    lr, b1, b2, eps = ADAM['lr'], ADAM['b1'], ADAM['b2'], ADAM['eps']
+    p, m, v = p.double().clone(), torch.zeros_like(p, dtype=torch.float64), torch.zeros_like(p, dtype=torch.float64)
+    out = []
+    for ph, gl in zip(ADAM_PHASES, grads):
+        for t, g in zip(ph, gl):
+            gi = g.double() * gs + wd * p
+            m = b1 * m + (1 - b1) * gi
+            v = b2 * v + (1 - b2) * gi * gi
+            p = p - (lr / (1 - b1 ** t)) * m / (v.sqrt() / np.sqrt(1 - b2 ** t) + eps)
+        out.append((p.clone(), m.clone(), v.clone()))
+    return out
+
+
+def _adam_torch_f32(p, grads, wd, gs):
+    """float32 torch.optim.Adam(weight_decay=wd) on the CPU, fed g * gs (gs a power of two: exact), its step counter set for the second phase"""
+    pr = p.clone().requires_grad_(True)
+    opt = torch.optim.Adam([pr], lr=ADAM['lr'], betas=(ADAM['b1'], ADAM['b2']), eps=ADAM['eps'], weight_decay=wd)
+    out = []
+    for ph, gl in zip(ADAM_PHASES, grads):
+        if ph[0] != 1:
+            opt.state[pr]['step'] = torch.tensor(float(ph[0] - 1))
+        for t, g in zip(ph, gl):
+            pr.grad = g * gs
+            opt.step()
+            assert float(opt.state[pr]['step']) == t
+        out.append(pr.detach().clone())
+    return out
+
+
+def _adam_kernel_f32(p, m, v, g, t):
+    """adam_kernel's own float32 operation sequence for wd = 0, grad_scale = 1 (one rounding per operation: the library is built without
+    contraction and with correctly rounded division and square root), scalars formed in double and rounded as launch_adam does.  Square root
+    and quotient are taken in float64 and rounded once more: for float32 operands that is the correctly rounded float32 result (53 >= 2 x 24 + 2
+    bits), which torch's own float32 sqrt on the CPU is not (65 of these 10007 inputs differ in the last bit)."""
+    f = lambda x: torch.full_like(p, float(np.float32(x)))              # noqa: E731
+    sqrt = lambda a: a.double().sqrt().float()                          # noqa: E731
+    div = lambda a, b: (a.double() / b.double()).float()                # noqa: E731
+    lr, b1, b2, eps = ADAM['lr'], ADAM['b1'], ADAM['b2'], ADAM['eps']
+    step_size, bc2_sqrt = f(lr / (1.0 - b1 ** t)), f(np.sqrt(1.0 - b2 ** t))
+    mi = f(b1) * m + (f(1.0) - f(b1)) * g
+    vi = f(b2) * v + (f(1.0) - f(b2)) * g * g
+    return p - step_size * div(mi, div(sqrt(vi), bc2_sqrt) + f(eps)), mi, vi
+
+
+def test_adam_weight_decay_and_grad_scale(lib):
+    """eld_adam_step with the two arguments no other test sets: weight_decay = 1e-2 and grad_scale = 0.25, n = 10007 (40 blocks, the last one
+    ragged), steps 1-5 and then 100000-100004 with m and v carried over (both bias corrections ~1: a step counter that is not used, or used as a
+    float of too few bits, is off by far more than the bound), against the float64 restatement of the formula in the comment above adam_kernel.
+
+    Tolerance: float32 torch.optim.Adam(weight_decay=1e-2) on the CPU, fed g * 0.25, lies max |p32 - p64| = 4.68e-7 from that float64 restatement
+    after step 5 and 6.12e-7 after step 100004 on these inputs (measured: ADAM_TORCH_F32_VS_F64; |p| up to 4, one ulp there 2.4e-7).  The kernel
+    is another float32 evaluation of the same formula in another operation order and gets 4 x that distance; the parameters move by 5e-4 and
+    3.2e-3 over the two phases, and a step without the decay term (it is 4 x the scaled gradient here) misses the bound by orders of magnitude.
+    Measured on one MI355X: the kernel lies 4.68e-7 and 6.12e-7 from the float64 restatement, 0.25 of its bound.
+
+    weight_decay = 0 with grad_scale = 1 is the call every training step makes: it must give the bits of the kernel's own float32 operation
+    sequence (_adam_kernel_f32) -- the new arguments change nothing when they are neutral."""
+    from eld_amd import _lib as L
+    n = 10007
+    wd, gs = 1e-2, 0.25
+    p0, grads = _adam_inputs(n)
+    ref = _adam_f64(p0, grads, wd, gs)
+    t32 = _adam_torch_f32(p0, grads, wd, gs)
+    dist = [float((a.double() - r[0]).abs().max()) for a, r in zip(t32, ref)]
+    print('adam: float32 torch.optim.Adam against the float64 formula, max |dp| after each phase', dist)
+    gd = Guards()
+    pd, m, v = gd.new((n,), name='p', src=p0), gd.new((n,), name='m', src=torch.zeros(n)), gd.new((n,), name='v', src=torch.zeros(n))
+    for k, (ph, gl) in enumerate(zip(ADAM_PHASES, grads)):
+        for t, g in zip(ph, gl):
+            gdev = gd.ro(g.cuda(), 'grad %d' % t)
+            L.check(lib.eld_adam_step(L.dptr(pd), L.dptr(gdev), L.dptr(m), L.dptr(v), n, ADAM['lr'], ADAM['b1'], ADAM['b2'], ADAM['eps'], wd, t, gs,
+                                      L.cur_stream()))
+            done(gd)
+        err = float((pd.cpu().double() - ref[k][0]).abs().max())
+        print('adam: phase %d kernel max |dp| %.3e (bound %.3e), |dm| %.3e, |dv| %.3e' % (
+            k, err, 4 * ADAM_TORCH_F32_VS_F64[k], float((m.cpu().double() - ref[k][1]).abs().max()), float((v.cpu().double() - ref[k][2]).abs().max())))
+        assert bool(torch.isfinite(m).all()) and bool(torch.isfinite(v).all()) and bool((v >= 0).all())
+        assert bool(((pd.cpu().double() - ref[k][0]).abs() <= 4 * ADAM_TORCH_F32_VS_F64[k]).all()), (k, err)
+    # the neutral arguments: the kernel's own float32 sequence, bit for bit
+    gd = Guards()
+    pd, m, v = gd.new((n,), name='p', src=p0), gd.new((n,), name='m', src=torch.zeros(n)), gd.new((n,), name='v', src=torch.zeros(n))
+    pe, me, ve = p0.clone(), torch.zeros(n), torch.zeros(n)
+    for t, g in zip(ADAM_PHASES[0], grads[0]):
+        gdev = gd.ro(g.cuda(), 'grad %d' % t)
+        L.check(lib.eld_adam_step(L.dptr(pd), L.dptr(gdev), L.dptr(m), L.dptr(v), n, ADAM['lr'], ADAM['b1'], ADAM['b2'], ADAM['eps'], 0.0, t, 1.0,
+                                  L.cur_stream()))
+        done(gd)
+        pe, me, ve = _adam_kernel_f32(pe, me, ve, g, t)
+        off = {name: int((got.cpu() != want).sum()) for name, got, want in (('p', pd, pe), ('m', m, me), ('v', v, ve))}
+        assert not any(off.values()), 'step %d: elements that differ from the float32 sequence: %s' % (t, off)
 
 
 # ------------------------------------------------------------------------------------------------ whole network
