@@ -350,7 +350,7 @@ int x3_slab_bn(int Nout, int N, int H, int W, int* waves = nullptr);      // (N,
 __host__ __device__ inline size_t x3_slab_stride(int BN) { return (size_t)(3 * BN * 112 + 1023) / 1024 * 1024; }      // bytes of one (ky, chunk, channel-block) slab
 void conv_x3_set_prof(unsigned long long* buf);      // dev tool: 8 workgroups x 4 waves x 128 stages x 6 stamps
 int launch_conv_x3_gemm(const ConvArgs& a, int mode, hipStream_t st);
-// conv_x3w.hip (round 6): the 32-output-channel full-resolution layers on a workgroup of specialised waves (4 MFMA + 4 load / cut waves); weights in the
+// conv_x3w.hip (round 6): the 32-output-channel full-resolution layers on a workgroup of specialised waves (8 MFMA + 7 load / cut waves + 1 slab wave); weights in the
 // BN = 32 slab layout.  x3w_enabled(): the process-wide switch (ELD_X3W, default on) -- it decides the pack layout of every 32-output-channel layer.
 bool x3w_enabled();
 bool x3w_takes(const ConvArgs& a);

@@ -485,14 +485,14 @@ void conv_tile_shape(int N, int H, int W, int TH, bool pooled, int& th, int& tw)
     th = TH; tw = 32;
     const TileMode& tm = tile_mode();
     const int mode = tm.mode, marg = tm.marg;
-    if (pooled || mode == 1 || N <= 0 || H <= 0 || W <= 0 || (TH != 8 && TH != 16 && TH != 32)) return;
-    const int ti = TH == 8 ? 0 : (TH == 16 ? 1 : 2);
+    if (pooled || mode == 1 || N <= 0 || H <= 0 || W <= 0 || (TH != 8 && TH != 16)) return;
+    const int ti = TH == 8 ? 0 : 1;
     const int slots = TH * 32, halo = (TH + 2) * 34;
     auto height = [&](int w) { int h = slots / w; while (h > 1 && (h + 2) * (w + 2) > halo) --h; return h > 128 ? 128 : h; };
-    struct ConflictTable { float v[3][65]; };                // conflict factor per width, per TH in {8, 16, 32}; filled once (shape-independent)
+    struct ConflictTable { float v[2][65]; };                // conflict factor per width, per TH in {8, 16}; filled once (shape-independent)
     static const ConflictTable cft = [] {
         ConflictTable c = {};
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < 2; ++k) {
             const int THk = 8 << k, sl = THk * 32, hl = (THk + 2) * 34;
             for (int w = 8; w <= 64; ++w) {
                 int h = sl / w;
@@ -502,7 +502,7 @@ void conv_tile_shape(int N, int H, int W, int TH, bool pooled, int& th, int& tw)
         }
         return c;
     }();
-    const float (&cf)[3][65] = cft.v;
+    const float (&cf)[2][65] = cft.v;
     double best = (double)tile_count(N, H, W, th, tw);       // the standard shape is conflict-free
     for (int w = 8; w <= 64; ++w) {                          // narrower than 8 pixels: a halo row is no longer a few whole 64-byte DMA units
         if (mode == 2 && (w & (w - 1))) continue;

@@ -34,8 +34,9 @@ namespace {
 // BSLAB (round 6): the weights arrive PRE-SPLIT in conv_x3d_kernel's slab layout (x3_store, unet_misc.hip: the exact LDS image of a stage's slab, rows of
 // 3 pieces x 16 bf16 + pad) and a stage's slab is copied global -> registers -> LDS as it is (three 16-byte units per thread): no weight cut per
 // stage and tile (a fifth of this kernel's VALU work and a third of its ds_write instructions); the register staging and the two 4-wave workgroups
-// per CU stay (the LDS-DMA variants of this layer shape, conv_x3d_kernel<32, ...>, need a second slab buffer and lose the second workgroup).
-template <int BN, int RPW, bool DB, bool BFIRST = false, bool BSLAB = false, bool STREAM = false>
+// per CU stay (the LDS-DMA variants of this layer shape needed a second slab buffer and lost the second workgroup: retired, see x3_slab_bn).
+// BSLAB = false: fp32 packed weights [tap][Nout][Cin], cut into pieces per stage like the halo tile.
+template <int BN, int RPW, bool BSLAB>
 __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const ConvArgs a) {
     constexpr int CK = 16;
     constexpr int TH = 4 * RPW, NT = BN / 32, A_PIX = (TH + 2) * (TW + 2);
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const ConvArgs a) {
 
         for (int c0 = 0; c0 < Cin; c0 += CK) {
             const bool last_chunk = c0 + CK >= Cin;
-#pragma unroll BFIRST ? 3 : 1            // (BFIRST: three explicit stages, so that every wait sees a static queue -- see the issue order below)
+#pragma unroll 3                         // (three explicit stages, so that every wait sees a static queue -- see the issue order below)
             for (int ky = 0; ky < 3; ++ky) {
                 __builtin_amdgcn_s_setprio(3);   // the short staging section goes ahead of the co-resident workgroup's MFMA stream
                 if (!(ELD_DBG(a) & 512)) __syncthreads();                 // every wave is done with the previous stage's operands  (dev probe 512: no barriers)
@@ -166,87 +167,30 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const ConvArgs a) {
                     // Order matters: vmcnt retires in order, so the loads the NEXT stage needs (its weight slab) go first and the halo tile -- needed
                     // three stages from now -- behind them: the compiler's wait for the slab registers then leaves the halo loads in flight (round 5;
                     // with the halo first, the next stage's wait for the slab drained the halo as well: one stage of latency instead of two)
-                    auto issue_B = [&]() {
+                    auto issue_B = [&]() {       // (a lambda on purpose: written out in place, hipcc numbers two scalar registers of the slab-fed kernel the other way round)
                         if (ky < 2) load_B(nb, c0, ky + 1);
                         else if (!last_chunk) load_B(nb, c0 + CK, 0);
                         else if (t_next < total_tiles) load_B(t_next % NB, 0, 0);
                     };
-                    if constexpr (BFIRST) issue_B();          // (a compile-time choice: the compiler's wait counts follow the issue order)
+                    issue_B();
                     if (ky == 0) {               // the halo tile of the next chunk / next tile has three stages to arrive
                         if (!last_chunk) load_A(c0 + CK);
                         else if (t_next < total_tiles) { setup_load(t_next); load_A(0); }
                     }
-                    if constexpr (!BFIRST) issue_B();
                 }
                 __builtin_amdgcn_s_setprio(0);
                 if (ELD_DBG(a) & 2) continue;    // (dev ablation: no fragment reads, no MFMAs)
-                if constexpr (STREAM) {
-                    x3_stage_blocks<RPW, NT>(acc,
-                        [&](int kx, int r, uint4 (&X)[3]) {
-                            const float* p = ldsA + ((wave * RPW + r + ky) * (TW + 2) + m + kx) * PX + hi * 4;
-#pragma unroll
-                            for (int pc = 0; pc < 3; ++pc) X[pc] = *reinterpret_cast<const uint4*>(p + pc * 8);
-                        },
-                        [&](int kx, int tt, uint4 (&Wt)[3]) {
-                            const float* p = ldsB + (kx * BN + tt * 32 + m) * PX + hi * 4;
-#pragma unroll
-                            for (int pc = 0; pc < 3; ++pc) Wt[pc] = *reinterpret_cast<const uint4*>(p + pc * 8);
-                        });
-                    continue;
-                }
-                uint4 fx[DB ? 2 : 1][3][RPW], fw[DB ? 2 : 1][3][NT];
-                auto read_tap = [&](int kx, uint4 (&X)[3][RPW], uint4 (&Wt)[3][NT]) {
-#pragma unroll
-                    for (int r = 0; r < RPW; ++r) {
+                x3_stage_blocks<RPW, NT>(acc,
+                    [&](int kx, int r, uint4 (&X)[3]) {
                         const float* p = ldsA + ((wave * RPW + r + ky) * (TW + 2) + m + kx) * PX + hi * 4;
 #pragma unroll
-                        for (int pc = 0; pc < 3; ++pc) X[pc][r] = *reinterpret_cast<const uint4*>(p + pc * 8);
-                    }
-#pragma unroll
-                    for (int tt = 0; tt < NT; ++tt) {
+                        for (int pc = 0; pc < 3; ++pc) X[pc] = *reinterpret_cast<const uint4*>(p + pc * 8);
+                    },
+                    [&](int kx, int tt, uint4 (&Wt)[3]) {
                         const float* p = ldsB + (kx * BN + tt * 32 + m) * PX + hi * 4;
 #pragma unroll
-                        for (int pc = 0; pc < 3; ++pc) Wt[pc][tt] = *reinterpret_cast<const uint4*>(p + pc * 8);
-                    }
-                };
-                constexpr int WI[6] = {0, 1, 2, 0, 1, 0};
-                constexpr int XI[6] = {2, 1, 0, 1, 0, 0};
-                if constexpr (DB) {
-                    read_tap(0, fx[0], fw[0]);
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        const int cur = kx & 1;
-                        if (kx + 1 < 3) read_tap(kx + 1, fx[cur ^ 1], fw[cur ^ 1]);
-                        __builtin_amdgcn_sched_barrier(0);
-                        // six piece products per (row, channel block), smallest first.  The pixel operand is held for up to six
-                        // consecutive MFMAs (fewer operand-bus toggles: these kernels run at the power limit) while the two
-                        // accumulators of the row alternate.
-#pragma unroll
-                        for (int r = 0; r < RPW; ++r)
-#pragma unroll
-                            for (int j = 2; j >= 0; --j)
-#pragma unroll
-                                for (int i = 0; i + j <= 2; ++i)
-#pragma unroll
-                                    for (int tt = 0; tt < NT; ++tt)
-                                        acc[r][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[cur][i][tt]),
-                                                                                             __builtin_bit_cast(bf16x8, fx[cur][j][r]), acc[r][tt], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else {                         // register budget: one fragment set, the compiler interleaves reads and MFMAs
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        read_tap(kx, fx[0], fw[0]);
-#pragma unroll
-                        for (int q = 0; q < 6; ++q)
-#pragma unroll
-                            for (int r = 0; r < RPW; ++r)
-#pragma unroll
-                                for (int tt = 0; tt < NT; ++tt)
-                                    acc[r][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[0][WI[q]][tt]),
-                                                                                         __builtin_bit_cast(bf16x8, fx[0][XI[q]][r]), acc[r][tt], 0, 0, 0);
-                    }
-                }
+                        for (int pc = 0; pc < 3; ++pc) Wt[pc] = *reinterpret_cast<const uint4*>(p + pc * 8);
+                    });
             }
         }
 
@@ -371,8 +315,8 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const ConvArgs a) {
 // knows about (s_waitcnt vmcnt(0) in front of the stage's first fragment read, which would serialise the prefetch and drain the halo
 // loads with it).  The kernel waits for its own pieces explicitly (dma_wait) before the barrier that publishes the slab.
 // s_nop 4: SALU-written soffset / descriptor -> VMEM read wait states; s_nop 0: M0 write -> LDS-DMA; M0 is saved and restored.
-template <int BN, int RPW, int WAVES, bool DB, int STREAM = 0>       // STREAM: 0 = the round-5 loops, 1 = streamed blocks, 2 = streamed blocks in the weight-reuse order (conv_x3_dev.h)
-__global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && BN <= 64) ? 2 : (WAVES == 8 ? 2 : 1)) void conv_x3d_kernel(const ConvArgs a) {
+template <int BN, int RPW, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, 2) void conv_x3d_kernel(const ConvArgs a) {
     constexpr int CK = 16, THREADS = 64 * WAVES;
     constexpr int TH = WAVES * RPW, NT = BN / 32, A_PIX = (TH + 2) * (TW + 2);
     constexpr int B_ROWS = 3 * BN;
@@ -536,8 +480,8 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && BN <= 64) ? 2 : (WAVES =
                 __builtin_amdgcn_s_setprio(0);
                 if (ELD_DBG(a) & 2) { buf ^= 1; continue; }      // (dev ablation: no fragment reads, no MFMAs)
                 const float* lb = ldsB + buf * B_WORDS;
-                if constexpr (STREAM) {
-                    x3_stage_blocks<RPW, NT, STREAM == 2>(acc,
+                if constexpr (WAVES == 8) {      // streamed fragment blocks in the weight-reuse order (conv_x3_dev.h)
+                    x3_stage_blocks<RPW, NT>(acc,
                         [&](int kx, int r, uint4 (&X)[3]) {
                             const float* p = ldsA + pb[r] + (ky * HWL + kx) * PX;
 #pragma unroll
@@ -548,57 +492,35 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && BN <= 64) ? 2 : (WAVES =
 #pragma unroll
                             for (int pc = 0; pc < 3; ++pc) Wt[pc] = *reinterpret_cast<const uint4*>(p + pc * 8);
                         });
-                    buf ^= 1;
-                    continue;
-                }
-                uint4 fx[DB ? 2 : 1][3][RPW], fw[DB ? 2 : 1][3][NT];
-                auto read_tap = [&](int kx, uint4 (&X)[3][RPW], uint4 (&Wt)[3][NT]) {
+                } else {                         // the 4-wave kernel (small problems): one fragment set per tap, the compiler interleaves reads and MFMAs
+                    uint4 fx[3][RPW], fw[3][NT];
+                    auto read_tap = [&](int kx, uint4 (&X)[3][RPW], uint4 (&Wt)[3][NT]) {
 #pragma unroll
-                    for (int r = 0; r < RPW; ++r) {
-                        const float* p = ldsA + pb[r] + (ky * HWL + kx) * PX;
+                        for (int r = 0; r < RPW; ++r) {
+                            const float* p = ldsA + pb[r] + (ky * HWL + kx) * PX;
 #pragma unroll
-                        for (int pc = 0; pc < 3; ++pc) X[pc][r] = *reinterpret_cast<const uint4*>(p + pc * 8);
-                    }
+                            for (int pc = 0; pc < 3; ++pc) X[pc][r] = *reinterpret_cast<const uint4*>(p + pc * 8);
+                        }
 #pragma unroll
-                    for (int tt = 0; tt < NT; ++tt) {
-                        const float* p = lb + (kx * BN + tt * 32 + m) * PX + hi * 4;
+                        for (int tt = 0; tt < NT; ++tt) {
+                            const float* p = lb + (kx * BN + tt * 32 + m) * PX + hi * 4;
 #pragma unroll
-                        for (int pc = 0; pc < 3; ++pc) Wt[pc][tt] = *reinterpret_cast<const uint4*>(p + pc * 8);
-                    }
-                };
-                constexpr int WI[6] = {0, 1, 2, 0, 1, 0};
-                constexpr int XI[6] = {2, 1, 0, 1, 0, 0};
-                if constexpr (DB) {
-                    read_tap(0, fx[0], fw[0]);
+                            for (int pc = 0; pc < 3; ++pc) Wt[pc][tt] = *reinterpret_cast<const uint4*>(p + pc * 8);
+                        }
+                    };
+                    constexpr int WI[6] = {0, 1, 2, 0, 1, 0};      // six piece products per (row, channel block), smallest first
+                    constexpr int XI[6] = {2, 1, 0, 1, 0, 0};
 #pragma unroll
                     for (int kx = 0; kx < 3; ++kx) {
-                        const int cur = kx & 1;
-                        if (kx + 1 < 3) read_tap(kx + 1, fx[cur ^ 1], fw[cur ^ 1]);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int r = 0; r < RPW; ++r)
-#pragma unroll
-                            for (int j = 2; j >= 0; --j)
-#pragma unroll
-                                for (int i = 0; i + j <= 2; ++i)
-#pragma unroll
-                                    for (int tt = 0; tt < NT; ++tt)
-                                        acc[r][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[cur][i][tt]),
-                                                                                             __builtin_bit_cast(bf16x8, fx[cur][j][r]), acc[r][tt], 0, 0, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else {
-#pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        read_tap(kx, fx[0], fw[0]);
+                        read_tap(kx, fx, fw);
 #pragma unroll
                         for (int q = 0; q < 6; ++q)
 #pragma unroll
                             for (int r = 0; r < RPW; ++r)
 #pragma unroll
                                 for (int tt = 0; tt < NT; ++tt)
-                                    acc[r][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[0][WI[q]][tt]),
-                                                                                         __builtin_bit_cast(bf16x8, fx[0][XI[q]][r]), acc[r][tt], 0, 0, 0);
+                                    acc[r][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, fw[WI[q]][tt]),
+                                                                                         __builtin_bit_cast(bf16x8, fx[XI[q]][r]), acc[r][tt], 0, 0, 0);
                     }
                 }
                 buf ^= 1;
@@ -982,7 +904,7 @@ int launch_x3_splitk_finish(const ConvArgs& a, hipStream_t st) {
     return 0;
 }
 
-template <int BN, int RPW, bool DB, bool BFIRST = false, bool BSLAB = false, bool STREAM = false>
+template <int BN, int RPW, bool BSLAB>
 int launch_x3(ConvArgs a, hipStream_t st) {
     a.xcd = eld_xcd_mask() & XCD_X3W;
     constexpr int TH = 4 * RPW;
@@ -992,10 +914,9 @@ int launch_x3(ConvArgs a, hipStream_t st) {
     const long long tiles = (long long)a.tiles_x * a.tiles_y * a.N * (a.Nout / BN);
     if (tiles <= 0) return 0;
     if (tiles > 0x7fffffffLL) return ELD_ENOTSUP;
-    // (every instantiation has BN == 32)  The default is the round-6 loop: BFIRST, BSLAB, STREAM; what an instantiation lacks is in its name
-    // (cut = fp32 packed weights cut per stage instead of pre-split slabs: ELD_X3W=0 without ELD_X3_BSLAB=1)
-    eld_note_conv_variant("conv_x3<32>", BSLAB ? nullptr : "cut", BFIRST ? nullptr : "bfirst0", STREAM ? nullptr : "stream0");
-    auto kern = conv_x3_kernel<BN, RPW, DB, BFIRST, BSLAB, STREAM>;
+    // (every instantiation has BN == 32)  cut = fp32 packed weights cut per stage instead of pre-split slabs
+    eld_note_conv_variant("conv_x3<32>", BSLAB ? nullptr : "cut");
+    auto kern = conv_x3_kernel<BN, RPW, BSLAB>;
     static EldAttrOnce once;
     { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
     int per_cu = (int)((160 * 1024) / lds_bytes);
@@ -1008,7 +929,7 @@ int launch_x3(ConvArgs a, hipStream_t st) {
     return 0;
 }
 
-template <int BN, int RPW, int WAVES, bool DB, int STREAM = 0>
+template <int BN, int RPW, int WAVES>
 int launch_x3d(ConvArgs a, hipStream_t st) {
     a.xcd = eld_xcd_mask() & XCD_X3D;
     constexpr int TH = WAVES * RPW;
@@ -1033,11 +954,9 @@ int launch_x3d(ConvArgs a, hipStream_t st) {
         if (ks >= 2) { a.ksplit = ks; tiles *= ks; }
     }
     if (tiles > 0x7fffffffLL) return ELD_ENOTSUP;
-    // the 8-wave kernels of 64 / 128 channels default to the streamed weight-reuse loop (STREAM == 2); the others have the one loop (STREAM == 0)
-    eld_note_conv_variant(BN == 128 ? "conv_x3d<128,8>" : (BN == 32 ? "conv_x3d<32,8>" : (WAVES == 8 ? "conv_x3d<64,8>" : (a.ksplit > 1 ? "conv_x3d<64,4,splitk>" : "conv_x3d<64,4>"))),
-                          (WAVES == 8 && BN >= 64) ? (STREAM == 0 ? "stream0" : (STREAM == 1 ? "wreuse0" : nullptr)) : nullptr,
+    eld_note_conv_variant(BN == 128 ? "conv_x3d<128,8>" : (WAVES == 8 ? "conv_x3d<64,8>" : (a.ksplit > 1 ? "conv_x3d<64,4,splitk>" : "conv_x3d<64,4>")),
                           a.pool_out ? nullptr : conv_tile_variant());
-    auto kern = conv_x3d_kernel<BN, RPW, WAVES, DB, STREAM>;
+    auto kern = conv_x3d_kernel<BN, RPW, WAVES>;
     static EldAttrOnce once;
     { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
     int per_cu = (int)((160 * 1024) / lds_bytes);
@@ -1082,41 +1001,26 @@ int launch_x3_gemm(ConvArgs a, hipStream_t st) {
 }  // namespace
 
 
-static bool x3_32_slabs() {
-    static const int on = [] { const char* e = getenv("ELD_X3_BSLAB"); return e ? atoi(e) : 0; }();      // measured 0.0 ... +0.3 % against the per-stage cut (profiles/r06_ab_notes.md): opt-in
-    return on != 0 || x3w_enabled();             // conv_x3w_kernel takes slabs: then every 32-output-channel layer is packed that way (small problems: the BSLAB variant)
-}
-static bool x3d_32_kernel(int N, int H, int W) {      // opt-in ELD_X3D_32=1: the 32-channel layers on the LDS-DMA kernel (measured slower, see x3_slab_bn)
-    static const int on = [] { const char* e = getenv("ELD_X3D_32"); return e ? atoi(e) : 0; }();
-    return on && x3_32_slabs() && conv_tile_count(N, H, W, 32, false) >= 2 * eld_num_cus();
-}
-
 // Tile shapes of the LDS-DMA kernel (measured, profiles/r02_*): 16-row tiles with ONE 8-wave workgroup per CU; 128 output channels per
-// tile where the layer has them (half the halo cuts per MFMA), else 64.  Layers with 32 output channels stay on the register-staged
-// conv_x3_kernel<32, 4> with two workgroups per CU: their K loop is 2-4 chunks long and a lone workgroup cannot hide its epilogue
-// (DMA variants with 32-channel slabs measured 0-2 % slower).
+// tile where the layer has them (half the halo cuts per MFMA), else 64.  Layers with 32 output channels run conv_x3w_kernel (conv_x3w.hip) or the
+// register-staged conv_x3_kernel<32, 4> with two workgroups per CU: their K loop is 2-4 chunks long and a lone workgroup cannot hide its epilogue.
+// They take pre-split slabs at BN = 32 wherever conv_x3w is enabled (conv_x3w_kernel consumes them by LDS-DMA, conv_x3_kernel<32, 4, BSLAB> through
+// registers), else fp32 packed weights.
 // Small problems (the reference trains on single 512 x 512 patches, train_syn.py defaults): when the big tiles do not give every CU a
 // workgroup the layer drops to 64-channel tiles, and then to 8-row tiles with 4-wave workgroups -- 4x the workgroups of the 16 x 128 tile
 // (conv5_x of a 512 x 512 patch: 8 -> 32 workgroups).  The pack kernel lays the slabs out for the same choice (same function, same arguments).
+// Retired experiments (their A/B figures stay in profiles/):
+//   conv_x3d_kernel<32, 4, 8> on the 32-channel layers, +6 %, and <32, 2, 4>, +10.7 %: r05_ab_notes.md "fp32 laggard layers"
+//   slabs for the 32-channel layers without conv_x3w, 0.0 ... +0.3 %: r06_ab_notes.md section 2
+//   the 4-wave kernel for the 64-channel layers of big problems, -0.2 %: r05_ab_notes.md "fp32 laggard layers"
 int x3_slab_bn(int Nout, int N, int H, int W, int* waves) {
     if (waves) *waves = 8;
-    // 32 output channels (round 4, opt-in ELD_X3D_32=1): conv_x3d_kernel<32, 4, 8> -- 32-row x 32-pixel tiles, the layer's pre-split weight slabs by
-    // LDS-DMA instead of a cut of the fp32 weights per stage and tile (a third of conv_x3_kernel<32, 4>'s staging work).  Measured 6 % SLOWER than
-    // conv_x3_kernel<32, 4> (3087 vs 2917 us per launch, same box): one 8-wave workgroup per CU loses more to its barriers than the two 4-wave
-    // workgroups of the register-staged kernel lose to the weight cut.  Off by default.
-    if (Nout == 32) {
-        // (round 5: conv_x3d_kernel<32, 2, 4> -- the same slabs, 8-row tiles, two 4-wave workgroups per CU -- measured +10.7 %: not kept either)
-        // Round 6 (opt-in ELD_X3_BSLAB=1): the 32-channel layers take pre-split slabs too -- consumed through registers by conv_x3_kernel<32, 4, ..., BSLAB>:
-        // a fifth of the kernel's VALU instructions gone and no change in its time (2848-2862 vs 2842-2854 us per launch, same box, interleaved): the
-        // kernel is not bound by VALU issue.  Default: fp32 packed weights cut per stage, the round-5 kernel.
-        return x3_32_slabs() ? 32 : 0;
-    }
+    if (Nout == 32) return x3w_enabled() ? 32 : 0;
     if (Nout % 64) return 0;
     const long long px_tiles = conv_tile_count(N, H, W, 16, false);
     const int cus = eld_num_cus();
     if (Nout % 128 == 0 && px_tiles * (Nout / 128) >= cus) return 128;
     if (waves && px_tiles * (Nout / 64) < cus) *waves = 4;
-    // (round 5: the 4-wave kernel for the 64-channel layers of big problems too -- 8-row tiles, two 81 KB workgroups per CU -- measured -0.2 %: not kept)
     return 64;
 }
 
@@ -1132,38 +1036,26 @@ int eld_tile_band() {
 }
 
 // a: fp32 CONV_3X3 arguments already validated by launch_conv
+//   Nout 128-multiples / 64-multiples: conv_x3d_kernel (slabs by LDS-DMA; x3_slab_bn picks the tile)
+//   Nout == 32, slabs (conv_x3w enabled): conv_x3w_kernel where it takes the layer, else the slab-fed conv_x3_kernel<32, 4, true> (small problems, other K)
+//   everything else on the cut-fed conv_x3_kernel<32, 4, false> (fp32 packed weights, cut per stage): the 32-channel layers under ELD_X3W=0, and every
+//   Nout that is a multiple of 32 but neither 32 nor a multiple of 64 (x3_slab_bn returns 0 for them).  Both BSLAB values are reached with no switch set.
+// Retired main loops (A/B figures in profiles/): halo loads ahead of the slab loads, r05_ab_notes.md "fp32 laggard layers"; hipcc's own
+// schedule of the per-tap loops, r06_ab_notes.md sections 2-3; streamed blocks without the weight-reuse order,
+// r06_ab_notes.md section 6.
 int launch_conv_x3(const ConvArgs& a_in, hipStream_t st) {
     ConvArgs a = a_in;
     a.prof = nullptr;
     if ((size_t)a.H * a.W * a.C0 * 4 >= 0xFFFFFFF0ull) return ELD_ENOTSUP;
     if (a.pool_out && (a.epi != EPI_FWD || (a.H & 1) || (a.W & 1))) return ELD_EINVAL;
     int waves = 8;
-    const int bn0 = x3_slab_bn(a.Nout, a.N, a.H, a.W, nullptr);
-    // conv_x3d_kernel addresses a two-image window (virtual rows)
-    if ((bn0 >= 64 || (bn0 == 32 && x3d_32_kernel(a.N, a.H, a.W))) && a.N > 1 && (size_t)a.H * a.W * a.C0 * 8 >= 0xFFFFFFF0ull) return ELD_ENOTSUP;
     const int bn = x3_slab_bn(a.Nout, a.N, a.H, a.W, &waves);
-    // round 6: streamed fragment blocks (x3_stage_blocks) in the main loops; ELD_X3_STREAM=0 restores hipcc's own schedule of the round-5 loops (A/B runs),
-    // a bit mask selects per family: 1 = the 32-channel kernel, 2 = conv_x3d_kernel<64>, 4 = conv_x3d_kernel<128>
-    static const int stream = [] { const char* e = getenv("ELD_X3_STREAM"); return e ? atoi(e) : 7; }();
+    // conv_x3d_kernel addresses a two-image window (virtual rows)
+    if (bn >= 64 && a.N > 1 && (size_t)a.H * a.W * a.C0 * 8 >= 0xFFFFFFF0ull) return ELD_ENOTSUP;
     if (bn == 32 && x3w_takes(a)) return launch_conv_x3w(a, st);      // specialised waves (conv_x3w.hip)
-    if (bn == 32 && x3d_32_kernel(a.N, a.H, a.W)) return launch_x3d<32, 4, 8, false>(a, st);
-    if (bn == 32) return (stream & 1) ? launch_x3<32, 4, false, true, true, true>(a, st) : launch_x3<32, 4, false, true, true>(a, st);      // pre-split slabs through registers (round 6)
-    // ELD_X3_WREUSE (bit mask: 2 = conv_x3d_kernel<64>, 4 = conv_x3d_kernel<128>; default both): the streamed blocks in the weight-reuse order (conv_x3_dev.h
-    // x3_stage_blocks) -- a third fewer LDS fragment reads; same box, interleaved: 2168 -> 2126 us (-1.9 %) / 2580 -> 2538 us (-1.6 %) per launch, step -0.9 %
-    static const int wreuse = [] { const char* e = getenv("ELD_X3_WREUSE"); return e ? atoi(e) : 6; }();
-    if (bn == 128) {                                                  // weights pre-split in slab layout: LDS-DMA kernel
-        if ((stream & 4) && (wreuse & 4)) return launch_x3d<128, 2, 8, false, 2>(a, st);
-        return (stream & 4) ? launch_x3d<128, 2, 8, false, 1>(a, st) : launch_x3d<128, 2, 8, false>(a, st);
-    }
-    if (bn == 64) {
-        if (waves != 8) return launch_x3d<64, 2, 4, false>(a, st);
-        if ((stream & 2) && (wreuse & 2)) return launch_x3d<64, 2, 8, false, 2>(a, st);
-        return (stream & 2) ? launch_x3d<64, 2, 8, false, 1>(a, st) : launch_x3d<64, 2, 8, false>(a, st);
-    }
-    // round 5: the next stage's slab loads are issued AHEAD of the halo loads (template BFIRST; -2.7 % per launch, same box); ELD_X3_BFIRST=0 restores the
-    // round-4 order for A/B runs
-    static const int bfirst = [] { const char* e = getenv("ELD_X3_BFIRST"); return e ? atoi(e) : 1; }();
-    if (bfirst) return (stream & 1) ? launch_x3<32, 4, false, true, false, true>(a, st) : launch_x3<32, 4, false, true>(a, st);
+    if (bn == 32) return launch_x3<32, 4, true>(a, st);
+    if (bn == 128) return launch_x3d<128, 2, 8>(a, st);
+    if (bn == 64) return waves == 8 ? launch_x3d<64, 2, 8>(a, st) : launch_x3d<64, 2, 4>(a, st);
     return launch_x3<32, 4, false>(a, st);
 }
 

@@ -105,17 +105,18 @@ __device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" :
 // small double buffers while the predecessor's six MFMAs run, and __builtin_amdgcn_sched_barrier pins that order: 2 x (12 + 12) fragment registers
 // instead of 60 ... 72, no LDS latency in front of any MFMA but a stage's first.
 //   readX(kx, r, X[3]) / readW(kx, tt, W[3]): the three piece fragments of pixel row r / channel block tt at tap kx.
-// WREUSE (NT > 1 only): the blocks of a tap run (channel block tt, pixel row r) with r fastest, every pixel row's fragments resident (one buffer per row)
+// NT > 1 (the weight-reuse order): the blocks of a tap run (channel block tt, pixel row r) with r fastest, every pixel row's fragments resident (one buffer per row)
 // and the weight fragments of a channel block used for all RPW rows before the next block's replace them: a stage then reads every pixel fragment once
-// per tap (as before) and every weight fragment once per tap instead of RPW times -- 3 (RPW + NT) fragment triples instead of 3 RPW (1 + NT): -33 % of a
-// 64-channel tile's LDS reads, -40 % of a 128-channel tile's, in the same 2 x (12 + 12) fragment registers at RPW = 2.  An accumulator still receives its
-// taps in the order 0, 1, 2 and its six products smallest first: the same bits.
-template <int RPW, int NT, bool WREUSE = false, typename RX, typename RW>
+// per tap and every weight fragment once per tap instead of RPW times -- 3 (RPW + NT) fragment triples instead of 3 RPW (1 + NT): -33 % of a
+// 64-channel tile's LDS reads, -40 % of a 128-channel tile's, in the same 2 x (12 + 12) fragment registers at RPW = 2.
+// NT == 1: the blocks run (tap kx, pixel row r); the pixel fragments change every block, the one channel block's weight fragments every tap.
+// Either way an accumulator receives its taps in the order 0, 1, 2 and its six products smallest first.
+template <int RPW, int NT, typename RX, typename RW>
 __device__ __forceinline__ void x3_stage_blocks(f32x16 (&acc)[RPW][NT], RX&& readX, RW&& readW) {
     constexpr int NBLK = 3 * RPW * NT;
     constexpr int WI[6] = {0, 1, 2, 0, 1, 0};
     constexpr int XI[6] = {2, 1, 0, 1, 0, 0};
-    if constexpr (WREUSE && NT > 1) {
+    if constexpr (NT > 1) {
         uint4 X[RPW][3], Wf[2][3];
         readX(0, 0, X[0]);
         readW(0, 0, Wf[0]);
@@ -134,26 +135,26 @@ __device__ __forceinline__ void x3_stage_blocks(f32x16 (&acc)[RPW][NT], RX&& rea
                 acc[r][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Wf[wi][WI[q]]), __builtin_bit_cast(bf16x8, X[r][XI[q]]), acc[r][tt], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
-        return;
-    }
-    uint4 X[2][3], Wf[2][3];
-    readX(0, 0, X[0]);
-    readW(0, 0, Wf[0]);
+    } else {
+        static_assert(RPW > 1, "the pixel fragments change with every block");
+        uint4 X[2][3], Wf[2][3];
+        readX(0, 0, X[0]);
+        readW(0, 0, Wf[0]);
 #pragma unroll
-    for (int b = 0; b < NBLK; ++b) {
-        const int kx = b / (RPW * NT), r = (b / NT) % RPW, tt = b % NT;
-        const int xi = (b / NT) & 1;                                   // the pixel fragments change every NT blocks,
-        const int wi = NT > 1 ? (b & 1) : ((b / RPW) & 1);            // the weight fragments every block (NT > 1) or every tap (NT == 1)
-        if (b + 1 < NBLK) {
-            const int kx1 = (b + 1) / (RPW * NT), r1 = ((b + 1) / NT) % RPW, tt1 = (b + 1) % NT;
-            if (kx1 != kx || r1 != r) readX(kx1, r1, X[xi ^ 1]);
-            if (kx1 != kx || tt1 != tt) readW(kx1, tt1, Wf[wi ^ 1]);
+        for (int b = 0; b < NBLK; ++b) {
+            const int kx = b / RPW, r = b % RPW;
+            const int xi = b & 1, wi = kx & 1;
+            if (b + 1 < NBLK) {
+                const int kx1 = (b + 1) / RPW, r1 = (b + 1) % RPW;
+                readX(kx1, r1, X[xi ^ 1]);
+                if (kx1 != kx) readW(kx1, 0, Wf[wi ^ 1]);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+                acc[r][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Wf[wi][WI[q]]), __builtin_bit_cast(bf16x8, X[xi][XI[q]]), acc[r][0], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
         }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < 6; ++q)
-            acc[r][tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, Wf[wi][WI[q]]), __builtin_bit_cast(bf16x8, X[xi][XI[q]]), acc[r][tt], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(0);
     }
 }
 

@@ -5,8 +5,8 @@
 // Why (profiles/r06_ab_notes.md): in conv_x3_kernel<32, 4> every wave does everything in turn -- wait for its halo loads, cut them into bf16 pieces, store
 // them to LDS, barrier, 72 MFMAs, ... epilogue -- and a tile's memory side (78 KB in, 64-80 KB out) takes about as long as its matrix side (13.8 K pipe
 // cycles per wave); with two such workgroups per CU the two sides ran almost back to back (matrix pipe 50 % busy), because a workgroup can hold only ONE
-// 16-channel chunk of loads in flight (40 staging VGPRs at a full register file).  Here ONE 16-wave workgroup owns the CU (the shipped configuration; the template
-// also builds 4 + 4 and 8 + 4 waves, profiles/r06_ab_notes.md):
+// 16-channel chunk of loads in flight (40 staging VGPRs at a full register file).  Here ONE 16-wave workgroup owns the CU (4 + 4 and 8 + 4 waves, producers that
+// also move the slabs, producers at raised priority and paired halo loads were measured and retired: profiles/r06_ab_notes.md sections 5 and 7):
 //   * waves 0-7 (two per SIMD, two pixel rows each) are CONSUMERS: fragment reads + MFMAs (x3_stage_blocks) and the tile's epilogue, nothing else;
 //   * waves 8-15 (two more per SIMD; 122 VGPRs per wave) are PRODUCERS: they run the chunk sequence of the workgroup's tiles AHEAD of the consumers -- halo loads of chunk g+3
 //     into one of two register sets (two chunks in flight per CU instead of one: the producers have the registers the consumers' accumulators do not
@@ -24,9 +24,6 @@
 
 namespace {
 
-template <int N>
-__device__ __forceinline__ void w_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
 // dev tool (ELD_DEV_TOOLS builds, eld_debug_conv_prof): (tag, s_memtime) pairs of the first consumer / halo / slab wave of the first 8 workgroups, 1024 per wave
 struct WProf {
     unsigned long long* p; int n;
@@ -35,7 +32,9 @@ struct WProf {
     }
 };
 
-constexpr int W_BN = 32, W_TH = 16, W_CK = 16;          // (consumer waves x rows per consumer wave = W_TH: 4 x 4 or 8 x 2, template parameters)
+constexpr int W_BN = 32, W_TH = 16, W_CK = 16;
+constexpr int W_CW = 8, W_RPW = 2, W_PW = 8;            // consumer waves x pixel rows per consumer wave = W_TH; producer waves
+static_assert(W_CW * W_RPW == W_TH, "tile rows");
 constexpr int W_APIX = (W_TH + 2) * (TW + 2);                       // 612 halo pixels
 constexpr int W_AWORDS = W_APIX * PX;                               // 17,136 words = 68,544 B
 constexpr int W_BROWS = 3 * W_BN;
@@ -43,16 +42,12 @@ constexpr int W_BWORDS = (W_BROWS * PX * 4 + 1023) / 1024 * 256;    // 2,816 wor
 constexpr int W_BPIECES = W_BWORDS * 4 / 1024;                      // 11
 constexpr int W_AUNITS = W_APIX * 4;
 
-// SLABW: the last producer wave moves the weight slabs and the other three stage the halo (13 units per thread and chunk: 216 VGPRs, so only with two waves per
-// SIMD = 4 consumer waves); else all four producer waves stage the halo (10 units) AND move the slabs, with a counted wait for their pieces.
-template <int W_CW, int W_RPW, bool SLABW, bool PRIO, int W_PW = 4, bool PAIR = false>
+constexpr int W_HW = W_PW - 1;                                     // producer waves that stage the halo; the last one moves the weight slabs
+constexpr int W_PTHREADS = 64 * W_HW;
+constexpr int W_AIT = (W_AUNITS + W_PTHREADS - 1) / W_PTHREADS;   // sixteen-byte units per halo thread and chunk: 6
+constexpr int W_T0 = (W_AIT + 2) / 3, W_T1 = W_T0 + (W_AIT - W_T0 + 1) / 2;      // a chunk's units are cut in three parts, one per stage: 6 -> 2 2 2
+
 __global__ __launch_bounds__(64 * (W_CW + W_PW), (W_CW + W_PW) / 4) void conv_x3w_kernel(const ConvArgs a) {
-    static_assert(W_CW * W_RPW == W_TH, "tile rows");
-    static_assert(!PAIR || SLABW, "paired halo loads: the halo waves wait for nothing but their own loads");
-    constexpr int W_HW = SLABW ? W_PW - 1 : W_PW;                     // producer waves that stage the halo
-    constexpr int W_PTHREADS = 64 * W_HW;
-    constexpr int W_AIT = (W_AUNITS + W_PTHREADS - 1) / W_PTHREADS;   // sixteen-byte units per halo thread and chunk: 13 / 10
-    constexpr int W_T0 = (W_AIT + 2) / 3, W_T1 = W_T0 + (W_AIT - W_T0 + 1) / 2;      // a chunk's units are cut in three parts, one per stage: 13 -> 5 4 4, 10 -> 4 3 3, 5 -> 2 2 1
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* ldsB = lds;                                                // [2][W_BWORDS]: the DMA destinations stay at low LDS addresses
     float* ldsA = lds + 2 * W_BWORDS;                                 // [2][W_AWORDS]
@@ -94,22 +89,17 @@ __global__ __launch_bounds__(64 * (W_CW + W_PW), (W_CW + W_PW) / 4) void conv_x3
     // else in flight.
     auto dma_slab = [&](int buf, int c, int ky) {
         const unsigned soff = (unsigned)((ky * NCH + c) * (W_BWORDS * 4));
-        constexpr int MOVERS = SLABW ? 1 : W_PW;
-        const int first_piece = SLABW ? 0 : wave - W_CW;
 #pragma unroll
-        for (int it = 0; it < (W_BPIECES + MOVERS - 1) / MOVERS; ++it) {
-            const int piece = first_piece + it * MOVERS;              // wave-uniform
-            if (piece < W_BPIECES) bdma16(rsrc_w, (unsigned)lane * 16u, soff + (unsigned)(piece * 1024), ldsB_addr + (unsigned)(buf * W_BWORDS * 4 + piece * 1024));
-        }
+        for (int piece = 0; piece < W_BPIECES; ++piece)
+            bdma16(rsrc_w, (unsigned)lane * 16u, soff + (unsigned)(piece * 1024), ldsB_addr + (unsigned)(buf * W_BWORDS * 4 + piece * 1024));
     };
 
     // The two roles are two separate loops over the same stage sequence (prologue barrier, then one barrier per (tile, chunk, kernel row)): their registers
     // -- the producers' two staging sets, the consumers' accumulators and fragments -- never compete for one allocation.
-    if (SLABW && wave == W_CW + W_HW) {
+    if (wave == W_CW + W_HW) {
         // ======================================================================================================================================
         // SLAB wave: the next stage's weight slab, one stage ahead
         // ======================================================================================================================================
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
         dma_slab(0, 0, 0);
         dma_wait();
         __syncthreads();
@@ -135,15 +125,12 @@ __global__ __launch_bounds__(64 * (W_CW + W_PW), (W_CW + W_PW) / 4) void conv_x3
         // ======================================================================================================================================
         // HALO waves: halo loads two chunks ahead, the three-piece cut one chunk ahead
         // ======================================================================================================================================
-        // The producers share their SIMDs with the consumers' MFMA / ds_read streams and are the YOUNGER waves: VALU issue goes to the older wave first
-        // (MI355X_MICROARCH.md, two waves per SIMD), so without a priority their short cut / store bursts queue behind it and every stage ends late.
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
-        const int ptid = tid - 64 * W_CW;                             // 0 .. 255
+        const int ptid = tid - 64 * W_CW;                             // 0 .. W_PTHREADS - 1
         constexpr unsigned OOB = 0xFFFFFFF0u;
         float4 ra[2][W_AIT];                                          // register set s holds the halo of the chunks g with (g & 1) == s (NCH is even: s = chunk & 1)
         unsigned a_voff[2][W_AIT];
         int s_img[2] = {0, 0}, s_tile[2] = {-1, -1};
-        // addresses of set s for tile t (a chunk's units: unit u = ptid + it * 256 -> halo pixel stage_row(u >> 2), 16-byte part u & 3)
+        // addresses of set s for tile t (a chunk's units: unit u = ptid + it * W_PTHREADS -> halo pixel stage_row(u >> 2), 16-byte part u & 3)
         auto setup_set = [&](auto S, int t) {
             constexpr int s = decltype(S)::value;
             int y0, x0;
@@ -183,67 +170,34 @@ __global__ __launch_bounds__(64 * (W_CW + W_PW), (W_CW + W_PW) / 4) void conv_x3
                 if (u < W_AUNITS) split_store(ldsA + s * W_AWORDS + stage_row(u >> 2, W_APIX) * PX + (u & 3) * 2, ra[s][it]);
             }
         };
-        // prologue: (the first slab,) chunk 0 cut into half 0; chunks 1 and 2 in flight
-        if constexpr (!SLABW) dma_slab(0, 0, 0);                      // (older than every load below: landed when chunk 0's registers are)
+        // prologue: chunk 0 cut into half 0; chunks 1 and 2 in flight
         load_part(I0_{}, I0_{}, IE_{}, 0);
         load_part(I1_{}, I0_{}, IE_{}, 1);
         cut_part(I0_{}, I0_{}, IE_{});
-        if constexpr (!PAIR) load_part(I0_{}, I0_{}, IE_{}, 2);
+        load_part(I0_{}, I0_{}, IE_{}, 2);
         __syncthreads();
-        int g = 0, sb = 0;
+        int g = 0;
         for (int k = 0; k < my_tiles; ++k) {
             for (int cp = 0; cp < NCH; cp += 2) {
                 // two chunks per trip so that register-set / LDS-half indices are compile-time constants: chunk g (even) is consumed from half 0, g + 1 from half 1
-                auto chunk = [&](auto SN, int c) {                     // SN: the set / half PRODUCED while the other half is consumed; c: the chunk being consumed
+                auto chunk = [&](auto SN) {                            // SN: the set / half PRODUCED while the other half is consumed
 #pragma unroll
                     for (int ky = 0; ky < 3; ++ky) {
-                        if constexpr (!SLABW) {
-                            // the next stage's slab first: its pieces are then OLDER than this stage's halo loads, which the counted wait below leaves in flight
-                            int c1 = c, ky1 = ky + 1;
-                            if (ky1 == 3) { ky1 = 0; c1 = c + 1 < NCH ? c + 1 : 0; }
-                            if (g + 1 < n_chunks || ky < 2) dma_slab(sb ^ 1, c1, ky1);      // (the other ring buffer: everybody finished reading it at the last barrier)
-                        }
                         // chunk g + 1: this stage's third of its units into LDS, then the same third of chunk g + 3 into the freed registers
                         prof(10);
-                        if constexpr (PAIR) {
-                            // Paired loads: chunks 2j and 2j + 1 of a tile are the two 64-byte halves of the same 128-byte pixel records (32 channels x 4 B), and
-                            // the L2 fetches whole lines.  Issued a chunk period apart (the schedule below), the second half finds its line evicted again
-                            // (FETCH_SIZE: 5.72 GB read per launch against 4.07 GB of halo tiles).  Here BOTH halves of a third's pixels are
-                            // requested back to back, in the stages of the EVEN chunk: the odd chunk g + 3 into the registers the cut of chunk g + 1 has just
-                            // freed, the even chunk g + 2 into the other set (free since chunk g was cut); the odd chunk's stages only cut.  An even chunk's
-                            // units are cut three stages after their loads were issued, an odd chunk's six.  Measured (profiles/r06_ab_notes.md): 4.09 GB per launch,
-                            // but the launch takes 2.7 % longer (all of a pair's loads in three stages instead of six) and the step is unchanged: opt-in (ELD_X3W=7).
-                            constexpr bool even = decltype(SN)::value == 1;          // (the set being cut holds an odd chunk <=> the chunk being consumed is even)
-                            using SO = std::integral_constant<int, 1 - decltype(SN)::value>;
-                            if (g + 1 < n_chunks) {
-                                if (ky == 0) cut_part(SN, I0_{}, IA_{}); else if (ky == 1) cut_part(SN, IA_{}, IB_{}); else cut_part(SN, IB_{}, IE_{});
-                            }
-                            prof(11);
-                            if constexpr (even) {
-                                if (ky == 0) { load_part(SO{}, I0_{}, IA_{}, g + 2); load_part(SN, I0_{}, IA_{}, g + 3); }
-                                else if (ky == 1) { load_part(SO{}, IA_{}, IB_{}, g + 2); load_part(SN, IA_{}, IB_{}, g + 3); }
-                                else { load_part(SO{}, IB_{}, IE_{}, g + 2); load_part(SN, IB_{}, IE_{}, g + 3); }
-                            }
-                        } else
                         if (g + 1 < n_chunks) {
                             if (ky == 0) { cut_part(SN, I0_{}, IA_{}); prof(11); load_part(SN, I0_{}, IA_{}, g + 3); }
                             else if (ky == 1) { cut_part(SN, IA_{}, IB_{}); prof(11); load_part(SN, IA_{}, IB_{}, g + 3); }
                             else { cut_part(SN, IB_{}, IE_{}); prof(11); load_part(SN, IB_{}, IE_{}, g + 3); }
                         }
                         prof(12);
-                        if constexpr (!SLABW) {
-                            if (g + 3 < n_chunks) {                    // this wave's slab pieces have landed (and, vmcnt being in order, every older load); the loads just issued may fly
-                                if (ky == 0) w_wait_vm<W_T0>(); else if (ky == 1) w_wait_vm<W_T1 - W_T0>(); else w_wait_vm<W_AIT - W_T1>();
-                            } else dma_wait();
-                        }
                         prof(13);
-                        __syncthreads();                              // this third of half SN (/ the next slab) is in LDS (all three thirds by the chunk's last stage)
-                        sb ^= 1;
+                        __syncthreads();                              // this third of half SN is in LDS (all three thirds by the chunk's last stage)
                     }
                     ++g;
                 };
-                chunk(I1_{}, cp);
-                chunk(I0_{}, cp + 1);
+                chunk(I1_{});
+                chunk(I0_{});
             }
         }
         return;
@@ -370,14 +324,12 @@ __global__ __launch_bounds__(64 * (W_CW + W_PW), (W_CW + W_PW) / 4) void conv_x3
 
 // Layers this kernel takes: fp32 three-piece 3x3 with exactly 32 output channels (GEMM N) and 32 or 64 input channels (one tensor, or the virtual concat of two
 // 32-channel tensors), a single 32-channel output tensor, on a tile domain that gives every CU a tile; weights in conv_x3d_kernel's slab layout at BN = 32.
-// ELD_X3W=0 keeps these layers on conv_x3_kernel<32, 4>.
-// ELD_X3W: 0 = off (conv_x3_kernel<32, 4>), 1 = 4 consumer waves x 4 rows + 3 halo waves + 1 slab wave, 2 = 8 consumer waves x 2 rows + 4 producer waves (two MFMA
-// waves per SIMD cover each other's fragment-read latency), 3 = as 2 with the producers at s_setprio 3, 4 = 8 consumer + 8 producer waves (four waves per SIMD), 5 = as 4 with one of the producer waves moving the slabs and nothing else (the default), 7 = as 5 with the halo loads of a chunk pair issued together (opt-in: -28 % of the launch's HBM reads, +2.7 % of its time)
-static int x3w_mode() {
-    static const int on = [] { const char* e = getenv("ELD_X3W"); return e ? atoi(e) : 5; }();
-    return on;
+// ELD_X3W=0 keeps these layers on conv_x3_kernel<32, 4> with fp32 packed weights (the old <-> new A/B switch of the family); any other value, and no value,
+// runs this kernel.
+bool x3w_enabled() {
+    static const int on = [] { const char* e = getenv("ELD_X3W"); return e ? atoi(e) : 1; }();
+    return on != 0;
 }
-bool x3w_enabled() { return x3w_mode() != 0; }
 bool x3w_takes(const ConvArgs& a) {
     if (!x3w_enabled() || a.Nout != 32 || a.dtype != DT_F32) return false;
     const int Cin = a.C0 + a.C1;
@@ -404,33 +356,10 @@ int launch_conv_x3w(const ConvArgs& a_in, hipStream_t st) {
     constexpr size_t lds_bytes = (size_t)(2 * W_BWORDS + 2 * W_AWORDS) * sizeof(float);
     long long grid = (long long)eld_num_cus();
     if (grid > tiles) grid = tiles;
-    const int mode = x3w_mode();
-    eld_note_conv_variant("conv_x3w", mode == 5 ? nullptr : (mode == 7 ? "m7" : (mode == 4 ? "m4" : (mode == 1 ? "m1" : (mode == 3 ? "m3" : "m2")))));      // (any other value runs mode 2)
-    if (mode == 7) {
-        static EldAttrOnce once;
-        { const int rc = once.ensure(conv_x3w_kernel<8, 2, true, false, 8, true>, lds_bytes); if (rc) return rc; }
-        ELD_LAUNCH((conv_x3w_kernel<8, 2, true, false, 8, true>), dim3((unsigned)grid), dim3(1024), lds_bytes, st, a);
-    } else if (mode == 5) {
-        static EldAttrOnce once;
-        { const int rc = once.ensure(conv_x3w_kernel<8, 2, true, false, 8>, lds_bytes); if (rc) return rc; }
-        ELD_LAUNCH((conv_x3w_kernel<8, 2, true, false, 8>), dim3((unsigned)grid), dim3(1024), lds_bytes, st, a);
-    } else if (mode == 4) {
-        static EldAttrOnce once;
-        { const int rc = once.ensure(conv_x3w_kernel<8, 2, false, false, 8>, lds_bytes); if (rc) return rc; }
-        ELD_LAUNCH((conv_x3w_kernel<8, 2, false, false, 8>), dim3((unsigned)grid), dim3(1024), lds_bytes, st, a);
-    } else if (mode == 1) {
-        static EldAttrOnce once;
-        { const int rc = once.ensure(conv_x3w_kernel<4, 4, true, false>, lds_bytes); if (rc) return rc; }
-        ELD_LAUNCH((conv_x3w_kernel<4, 4, true, false>), dim3((unsigned)grid), dim3(512), lds_bytes, st, a);
-    } else if (mode == 3) {
-        static EldAttrOnce once;
-        { const int rc = once.ensure(conv_x3w_kernel<8, 2, false, true>, lds_bytes); if (rc) return rc; }
-        ELD_LAUNCH((conv_x3w_kernel<8, 2, false, true>), dim3((unsigned)grid), dim3(768), lds_bytes, st, a);
-    } else {
-        static EldAttrOnce once;
-        { const int rc = once.ensure(conv_x3w_kernel<8, 2, false, false>, lds_bytes); if (rc) return rc; }
-        ELD_LAUNCH((conv_x3w_kernel<8, 2, false, false>), dim3((unsigned)grid), dim3(768), lds_bytes, st, a);
-    }
+    eld_note_conv_kernel("conv_x3w");
+    static EldAttrOnce once;
+    { const int rc = once.ensure(conv_x3w_kernel, lds_bytes); if (rc) return rc; }
+    ELD_LAUNCH(conv_x3w_kernel, dim3((unsigned)grid), dim3(64 * (W_CW + W_PW)), lds_bytes, st, a);
     ELD_LAUNCH_CHECK();
     return 0;
 }

@@ -794,12 +794,13 @@ int eld_maxpool2x2_backward_bf16(const uint16_t* act, const uint16_t* dp, const 
  *   bf16: "conv_bfs", "conv_bfw", "conv_bfd<128>", "conv_bfd<64>", "conv_bfg<128>", "conv_bfg<64,gather>", "conv_bfg<128,gather>", "conv_igemm<bf16>",
  *         "conv_igemm<bf16,1x1>", "conv_igemm<bf16,gather>", "wgrad8d", "wgrad8<bf16>", "wgrad<bf16>", "wgrad<bf16,gather>";
  *   fp32, three-piece scheme (tile width in output channels, waves per workgroup): "conv_x3w", "conv_x3<32>", "conv_x3d<128,8>", "conv_x3d<64,8>",
- *         "conv_x3d<64,4>", "conv_x3d<64,4,splitk>" (K split over workgroups, inside a U-Net entry point only), "conv_x3d<32,8>" (opt-in),
+ *         "conv_x3d<64,4>", "conv_x3d<64,4,splitk>" (K split over workgroups, inside a U-Net entry point only),
  *         "conv_x3_gemm<1x1>", "conv_x3_gemm<gather>" (transposed convs), "wgrad8<f32,128x64>", "wgrad8<f32,64x64>", "wgrad8<f32,64x32>",
  *         "wgrad8<f32,32x64>", "wgrad8<f32,32x32>" (block = output x input channels), "wgradt8";
  *   fp32, other schemes and shapes: "conv_igemm<f32>", "conv_igemm<f32,h2>", "wgrad<f32>", "wgrad<f32,gather>".
  * A launch of a non-default variant of a family -- one that an ELD_* switch of the process environment selected (DESIGN.md section 6a lists them) --
- * answers "family/suffix[,suffix]" instead, e.g. "conv_x3d<64,8>/stream0", "conv_x3w/m2", "conv_x3<32>/cut", "conv_bfd<64>/tiles-f"; with
+ * answers "family/suffix[,suffix]" instead: "conv_x3<32>/cut" (ELD_X3W=0: fp32 packed weights cut per stage; also what layers of 96, 160, ... output
+ * channels record), "conv_x3d<...>/tiles-f" and "conv_bfd<...>/tiles-f" (-p, -m, -q, -t: ELD_CONV_TILES), "wgrad<bf16,gather>/f32mma" (ELD_WGRAD_BF16_MMA=0); with
  * ELD_FIRST_MMA=0 the first layer of 4 planes records "conv_first/mma0" (it records nothing otherwise).  With no switch set the names are the ones above. */
 const char* eld_debug_last_conv_kernel(void);
 /* Test hook: how many launches this process has recorded under a family name (0 for a name never seen): what a test of a whole-network entry

@@ -43,7 +43,7 @@ ELD_EINVAL, ELD_ENOTSUP = -1, -2
 EA0, EA1, DA0, DA1, EB0, EB1 = 1, 2, 4, 8, 16, 32
 RG = {'ea': 0, 'eb': 1, 'pool': 2, 'up': 3, 'da': 4, 'db': 5, 'x16': 6}
 NAMES = {
-    'fp32': ['conv_x3w', 'conv_x3<32>', 'conv_x3d<128,8>', 'conv_x3d<64,8>', 'conv_x3d<64,4>', 'conv_x3d<64,4,splitk>', 'conv_x3d<32,8>', 'conv_x3_gemm<1x1>',
+    'fp32': ['conv_x3w', 'conv_x3<32>', 'conv_x3d<128,8>', 'conv_x3d<64,8>', 'conv_x3d<64,4>', 'conv_x3d<64,4,splitk>', 'conv_x3_gemm<1x1>',
              'conv_x3_gemm<gather>', 'conv_igemm<f32>', 'conv_igemm<f32,h2>', 'wgrad8<f32,128x64>', 'wgrad8<f32,64x64>', 'wgrad8<f32,64x32>',
              'wgrad8<f32,32x64>', 'wgrad8<f32,32x32>', 'wgradt8', 'wgrad<f32>', 'wgrad<f32,gather>'],
     'bf16': ['conv_bfs', 'conv_bfw', 'conv_bfd<128>', 'conv_bfd<64>', 'conv_bfg<128>', 'conv_bfg<64,gather>', 'conv_bfg<128,gather>', 'conv_igemm<bf16>',

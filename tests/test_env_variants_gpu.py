@@ -4,8 +4,8 @@ eld_amd/csrc reads its ELD_* switches once per process, so each setting runs in 
 case's environment the way tests/test_placement_gpu.py starts its children.  The child calls the per-layer checks of tests/test_f32_layers_gpu.py and
 tests/test_bf16_layers_gpu.py with the rows of their tables that the switch affects: the same operands, the same float64 layer, the same derived bound
 (oracle/f32_ref.py x3_bound, oracle/bf16_ref.py margin / f32_bound) as the default family has to meet.  Nothing is compared with a tolerance of this
-file's own.  A variant also has to prove that it ran: the launchers record "family/suffix" for every non-default instantiation (csrc/common.h
-eld_note_conv_variant) and the checks assert that name.  The table of cases is variant_child.CASES; tests/test_env_variants_cpu.py keeps it complete.
+file's own.  A variant also has to prove that it ran: the launchers record "family/suffix" for every non-default instantiation or tile setting
+(csrc/common.h eld_note_conv_variant) and the checks assert that name.  The table of cases is variant_child.CASES; tests/test_env_variants_cpu.py keeps it complete.
 
 ELD_CONV_TILES: a tile's result does not depend on the tile's shape, so every convolution output under f / p / m16 / m36 / q8 / t must also equal the
 default's bit for bit (SHA-256 of the output tensors, exchanged through the children's RESULT lines).
@@ -36,9 +36,7 @@ VARIANT_MEASURED = {
     ('first-mma0', 'unet'): 0.557,
     ('first-mma0', 'unet<bf16>'): 0.286,
     ('first-mma0', 'unet<bf16>', 'flip'): 0.445,
-    ('stream0', 'conv_x3<32>/stream0'): 0.461,
-    ('stream0', 'conv_x3d<128,8>/stream0'): 0.767,
-    ('stream0', 'conv_x3d<64,8>/stream0'): 0.824,
+    ('nosplitk', 'unet'): 0.907,
     ('tiles-default', 'conv_bfd<128>', 'flip'): 0.121,
     ('tiles-default', 'conv_bfd<64>', 'flip'): 0.128,
     ('tiles-default', 'conv_x3d<128,8>'): 0.767,
@@ -86,32 +84,14 @@ VARIANT_MEASURED = {
     ('tiles-t', 'conv_x3d<128,8>/tiles-t'): 0.767,
     ('tiles-t', 'conv_x3d<64,4>/tiles-t'): 0.539,
     ('tiles-t', 'conv_x3d<64,8>/tiles-t'): 0.824,
-    ('wg8-rowshare', 'wgrad8<f32,128x64>/rowshare'): 0.142,
     ('wgrad', 'conv_bfg<128>', 'flip'): 0.058,
     ('wgrad', 'conv_igemm<bf16,1x1>', 'flip'): 0.196,
     ('wgrad', 'conv_x3_gemm<1x1>'): 0.548,
     ('wgrad', 'conv_x3_gemm<gather>'): 0.492,
     ('wgrad', 'wgrad8<bf16>'): 0.066,
-    ('wgrad', 'wgrad8<f32,128x64>/stream'): 0.129,
-    ('wgrad', 'wgrad8<f32,32x32>/stream'): 0.094,
-    ('wgrad', 'wgrad8<f32,32x64>/stream'): 0.123,
-    ('wgrad', 'wgrad8<f32,64x32>/stream'): 0.101,
-    ('wgrad', 'wgrad8<f32,64x64>/stream'): 0.091,
     ('wgrad', 'wgrad<bf16,gather>/f32mma'): 0.143,
     ('wgrad', 'wgrad<f32,gather>'): 0.126,
-    ('wreuse0+nosplitk', 'conv_x3d<128,8>/wreuse0'): 0.767,
-    ('wreuse0+nosplitk', 'conv_x3d<64,8>/wreuse0'): 0.824,
-    ('wreuse0+nosplitk', 'unet'): 0.907,
-    ('x3d32', 'conv_x3d<32,8>'): 0.676,
     ('x3w0', 'conv_x3<32>/cut'): 0.688,
-    ('x3w0-bfirst0', 'conv_x3<32>/cut,bfirst0,stream0'): 0.688,
-    ('x3w0-bslab', 'conv_x3<32>'): 0.688,
-    ('x3w0-stream0', 'conv_x3<32>/cut,stream0'): 0.688,
-    ('x3w1', 'conv_x3w/m1'): 0.688,
-    ('x3w2', 'conv_x3w/m2'): 0.688,
-    ('x3w3', 'conv_x3w/m3'): 0.688,
-    ('x3w4', 'conv_x3w/m4'): 0.688,
-    ('x3w7', 'conv_x3w/m7'): 0.688,
 }
 
 _RESULTS = {}

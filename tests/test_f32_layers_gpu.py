@@ -10,7 +10,7 @@ proof in tests/test_f32_ref_cpu.py), both with exact +0 / -0 sprinkled into the 
 bit for bit.  The whole fp32 forward is checked teacher-forced: each of the 23 layers against the reference applied to the kernel's own
 saved input (eld_debug_unet_region), pools bit for bit, and the families chosen inside it (split-K among them) by launch counts.
 
-The modes read once per process from the environment (ELD_X3W other than the default, ELD_X3D_32 -> "conv_x3d<32,8>", ELD_X3_BSLAB, ELD_WG8_*, ...)
+The modes read once per process from the environment (ELD_X3W=0 -> "conv_x3<32>/cut", ELD_CONV_TILES -> ".../tiles-f" etc., ELD_NO_SPLITK, ELD_WGRADT8=0, ...)
 run these same checks in one fresh interpreter per setting: tests/test_env_variants_gpu.py.  Out of scope: the other fp32 schemes
 (tests/test_unet_gpu.py runs them).  The backward's call sites -- every gradient stage of unet_backward<float>, teacher-forced through the gradient
 tap, slope and pool codes live and masked -- are in tests/test_backward_layers_gpu.py.
@@ -313,7 +313,7 @@ def test_convt2x2_f32(lib, ffam, bfam, wfam, N, H, W, Cin, Cout, kind):
 # ---- the whole network, teacher-forced ------------------------------------------------------------------------------------
 NET = [(2, 4, 272, 560), (3, 4, 48, 80), (2, 9, 272, 560), (1, 4, 512, 512)]
 RG = {'ea': 0, 'eb': 1, 'pool': 2, 'up': 3, 'da': 4, 'db': 5, 'x16': 6}
-NAMES = ['conv_x3w', 'conv_x3<32>', 'conv_x3d<128,8>', 'conv_x3d<64,8>', 'conv_x3d<64,4>', 'conv_x3d<64,4,splitk>', 'conv_x3d<32,8>', 'conv_x3_gemm<1x1>',
+NAMES = ['conv_x3w', 'conv_x3<32>', 'conv_x3d<128,8>', 'conv_x3d<64,8>', 'conv_x3d<64,4>', 'conv_x3d<64,4,splitk>', 'conv_x3_gemm<1x1>',
          'conv_x3_gemm<gather>', 'conv_igemm<f32>', 'conv_igemm<f32,h2>']
 # The families a 256-CU dispatcher chooses inside each forward, from its own conditions (conv_x3.hip x3_slab_bn, launch_x3d; conv_x3w.hip x3w_takes):
 #   level 0 (32 channels): conv_x3w from 256 tiles of 16 x 32 on (272 x 560 x 2: 612, 512 x 512: 512), else conv_x3<32> (48 x 80 x 3: 27); conv1_1 of

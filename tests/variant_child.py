@@ -31,13 +31,10 @@ for p in (HERE, ROOT):
 
 # ---- the settings: case -> environment.  Plain data, readable without torch (tests/test_env_variants_cpu.py reads it) -------------------------------
 ENV = {
-    'x3w0': {'ELD_X3W': '0'}, 'x3w1': {'ELD_X3W': '1'}, 'x3w2': {'ELD_X3W': '2'}, 'x3w3': {'ELD_X3W': '3'}, 'x3w4': {'ELD_X3W': '4'}, 'x3w7': {'ELD_X3W': '7'},
-    'x3w0-bslab': {'ELD_X3W': '0', 'ELD_X3_BSLAB': '1'}, 'x3w0-bfirst0': {'ELD_X3W': '0', 'ELD_X3_BFIRST': '0'},
-    'x3w0-stream0': {'ELD_X3W': '0', 'ELD_X3_STREAM': '0'}, 'stream0': {'ELD_X3_STREAM': '0'},
-    'wreuse0+nosplitk': {'ELD_X3_WREUSE': '0', 'ELD_NO_SPLITK': '1'}, 'x3d32': {'ELD_X3W': '0', 'ELD_X3_BSLAB': '1', 'ELD_X3D_32': '1'},
+    'x3w0': {'ELD_X3W': '0'}, 'nosplitk': {'ELD_NO_SPLITK': '1'},
     'tiles-default': {}, 'tiles-f': {'ELD_CONV_TILES': 'f'}, 'tiles-p': {'ELD_CONV_TILES': 'p'}, 'tiles-m16': {'ELD_CONV_TILES': 'm16'},
     'tiles-m36': {'ELD_CONV_TILES': 'm36'}, 'tiles-q8': {'ELD_CONV_TILES': 'q8'}, 'tiles-t': {'ELD_CONV_TILES': 't'},
-    'wgrad': {'ELD_WG8_STREAM': '3', 'ELD_WGRADT8': '0', 'ELD_WGRAD_DMA': '0', 'ELD_WGRAD_BF16_MMA': '0'}, 'wg8-rowshare': {'ELD_WG8_ROWSHARE': '1'},
+    'wgrad': {'ELD_WGRADT8': '0', 'ELD_WGRAD_DMA': '0', 'ELD_WGRAD_BF16_MMA': '0'},
     'first-mma0': {'ELD_FIRST_MMA': '0'}, 'fp32conv-unset': {}, 'fp32conv-m': {'ELD_FP32_CONV': 'm'}, 'fp32conv-h': {'ELD_FP32_CONV': 'h'},
 }
 SWITCHES = sorted({k for e in ENV.values() for k in e})
@@ -70,35 +67,16 @@ def _tiles(sfx):
     return runs
 
 
-# conv_x3d<32,8> needs 2 x 256 tiles of its 32-row tile domain (conv_x3.hip x3d_32_kernel): 2 x 545 x 470 is 518 tiles of 30 x 34, odd height, ragged
-# last tile row and column, the seam between the images.  With ELD_X3W at its default conv_x3w takes every 32 / 64 -> 32 layer first, so the switch
-# is run with ELD_X3W=0 ELD_X3_BSLAB=1 (the slabs the kernel reads), where every 32-output-channel layer of that size reaches it.
-X3D32 = [('f32_fwd', ('conv_x3d<32,8>', 2, 545, 470, 32, 0, 32)), ('f32_fwd', ('conv_x3d<32,8>', 2, 545, 470, 32, 32, 32)),
-         ('f32_bwd', ('conv_x3d<32,8>', 2, 545, 470, 32, 64, 32))]
-WG8 = [r[0] for r in F.WG if r[0].startswith('wgrad8<f32')]
 NET_SMALL = (3, 4, 48, 80)
 NOSPLIT = {'conv_x3d<64,4>', 'conv_x3_gemm<1x1>'}
 
 CASES = {
-    # conv_x3w.hip: every mode is its own instantiation; 0 hands the layers to conv_x3_kernel<32, 4> on fp32 packed weights cut per stage
+    # conv_x3w.hip: 0 hands the layers to conv_x3_kernel<32, 4> on fp32 packed weights cut per stage (the cut-fed instantiation's coverage)
     'x3w0': {'env': {'ELD_X3W': '0'}, 'runs': _x3({X3W: X32 + '/cut', X32: X32 + '/cut'})},
-    'x3w1': {'env': {'ELD_X3W': '1'}, 'runs': _x3({X3W: X3W + '/m1'})},
-    'x3w2': {'env': {'ELD_X3W': '2'}, 'runs': _x3({X3W: X3W + '/m2'})},
-    'x3w3': {'env': {'ELD_X3W': '3'}, 'runs': _x3({X3W: X3W + '/m3'})},
-    'x3w4': {'env': {'ELD_X3W': '4'}, 'runs': _x3({X3W: X3W + '/m4'})},
-    'x3w7': {'env': {'ELD_X3W': '7'}, 'runs': _x3({X3W: X3W + '/m7'})},
-    # conv_x3.hip launch_x3<32, 4, ...>: its five instantiations (the default's, BFIRST + BSLAB + STREAM, at the former conv_x3w rows too)
-    'x3w0-bslab': {'env': {'ELD_X3W': '0', 'ELD_X3_BSLAB': '1'}, 'runs': _x3({X3W: X32, X32: X32})},
-    'x3w0-bfirst0': {'env': {'ELD_X3W': '0', 'ELD_X3_BFIRST': '0'}, 'runs': _x3({X3W: X32 + '/cut,bfirst0,stream0', X32: X32 + '/cut,bfirst0,stream0'})},
-    'x3w0-stream0': {'env': {'ELD_X3W': '0', 'ELD_X3_STREAM': '0'}, 'runs': _x3({X3W: X32 + '/cut,stream0', X32: X32 + '/cut,stream0'})},
-    # the main loops of the 8-wave LDS-DMA kernels (STREAM 0 / 1 against the default 2) and of the slab-fed 32-channel kernel
-    'stream0': {'env': {'ELD_X3_STREAM': '0'}, 'runs': _x3({X32: X32 + '/stream0', D64: D64 + '/stream0', D128: D128 + '/stream0'})},
-    # (disjoint families in one child: the 8-wave kernels' loop, and the 4-wave kernel with and without the K split)
-    'wreuse0+nosplitk': {'env': {'ELD_X3_WREUSE': '0', 'ELD_NO_SPLITK': '1'},
-                         'runs': _x3({D64: D64 + '/wreuse0', D128: D128 + '/wreuse0'})
-                         + [('f32_net', NET_SMALL + (NOSPLIT | {X32},)), ('f32_net', (1, 4, 512, 512, NOSPLIT | {X3W})),      # every shape of F.RAN records the split by default
-                                    ('f32_net', (2, 4, 272, 560, NOSPLIT | {X3W})), ('f32_net', (2, 9, 272, 560, NOSPLIT | {X3W, X32}))]},
-    'x3d32': {'env': {'ELD_X3W': '0', 'ELD_X3_BSLAB': '1', 'ELD_X3D_32': '1'}, 'runs': X3D32},
+    # conv_x3.hip launch_x3d: the 4-wave kernel without the K split
+    'nosplitk': {'env': {'ELD_NO_SPLITK': '1'},
+                 'runs': [('f32_net', NET_SMALL + (NOSPLIT | {X32},)), ('f32_net', (1, 4, 512, 512, NOSPLIT | {X3W})),      # every shape of F.RAN records the split by default
+                          ('f32_net', (2, 4, 272, 560, NOSPLIT | {X3W})), ('f32_net', (2, 9, 272, 560, NOSPLIT | {X3W, X32}))]},
     # conv_igemm.hip conv_tile_shape: the default's outputs are hashed too (tests/test_env_variants_gpu.py compares them bit for bit)
     'tiles-default': {'env': {}, 'runs': _tiles(''), 'hash': True},
     'tiles-f': {'env': {'ELD_CONV_TILES': 'f'}, 'runs': _tiles('/tiles-f'), 'hash': True},
@@ -107,14 +85,12 @@ CASES = {
     'tiles-m36': {'env': {'ELD_CONV_TILES': 'm36'}, 'runs': _tiles('/tiles-m'), 'hash': True},
     'tiles-q8': {'env': {'ELD_CONV_TILES': 'q8'}, 'runs': _tiles('/tiles-q'), 'hash': True},
     'tiles-t': {'env': {'ELD_CONV_TILES': 't'}, 'runs': _tiles('/tiles-t'), 'hash': True},
-    # conv_wgrad.hip, four disjoint families in one child: the streamed loop of every wgrad8<f32> block shape; the transposed convs' gradient back on
-    # wgrad_kernel; the bf16 128 x 64 blocks on the register-staged kernel; the bf16 gather gradient on the fp32 MFMA
-    'wgrad': {'env': {'ELD_WG8_STREAM': '3', 'ELD_WGRADT8': '0', 'ELD_WGRAD_DMA': '0', 'ELD_WGRAD_BF16_MMA': '0'},
-              'runs': _f32(F.WG, 'f32_wg', {k: k + '/stream' for k in WG8})
-              + [('f32_ct', tuple(r[:2]) + ('wgrad<f32,gather>',) + tuple(r[3:])) for r in F.CT if r[2] == 'wgradt8']
+    # conv_wgrad.hip, three disjoint families in one child: the transposed convs' gradient back on wgrad_kernel; the bf16 128 x 64 blocks on the
+    # register-staged kernel; the bf16 gather gradient on the fp32 MFMA
+    'wgrad': {'env': {'ELD_WGRADT8': '0', 'ELD_WGRAD_DMA': '0', 'ELD_WGRAD_BF16_MMA': '0'},
+              'runs': [('f32_ct', tuple(r[:2]) + ('wgrad<f32,gather>',) + tuple(r[3:])) for r in F.CT if r[2] == 'wgradt8']
               + _f32(B.WG, 'bf16_wg', {'wgrad8d': 'wgrad8<bf16>'})
               + [('bf16_ct', tuple(r) + ('wgrad<bf16,gather>/f32mma',)) for r in B.CT]},
-    'wg8-rowshare': {'env': {'ELD_WG8_ROWSHARE': '1'}, 'runs': _f32(F.WG, 'f32_wg', {'wgrad8<f32,128x64>': 'wgrad8<f32,128x64>/rowshare'})},
     # conv_first.hip: the packed-raw first layer back on the fp32-MFMA kernel, which writes no slope codes (the backward of conv1_2 reads the saved tensor)
     'first-mma0': {'env': {'ELD_FIRST_MMA': '0'},
                    'runs': [('f32_net', NET_SMALL + ({'conv_x3d<64,4>', 'conv_x3d<64,4,splitk>', 'conv_x3_gemm<1x1>', X32},)), ('bf16_net_uncut', NET_SMALL),
