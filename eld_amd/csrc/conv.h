@@ -11,6 +11,9 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_hw __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));      // an MFMA operand fragment
+typedef int i32x4 __attribute__((ext_vector_type(4)));          // a raw buffer descriptor
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));     // native vector type: one 128-bit register tuple per asm operand
 
 enum ConvMode { CONV_3X3 = 0, CONV_1X1 = 1, CONV_GATHER2X2 = 2 };
 enum ConvEpi { EPI_FWD = 0, EPI_CONVT_FWD = 1, EPI_GRAD = 2 };
@@ -243,6 +246,19 @@ __device__ __forceinline__ void eld_wait_vmcnt_dyn(int n) {
 #undef ELD_W
         default: eld_wait_vmcnt<0>(); break;
     }
+}
+
+// One 1 KiB LDS-DMA piece: lane l copies the 16 bytes at buffer offset voff (per lane) + soff (wave-uniform) to LDS byte address
+// lds_dst + 16 l (lds_dst wave-uniform).  Issued through inline asm ON PURPOSE: hipcc orders every later ds_read behind an LDS-DMA it
+// knows about (s_waitcnt vmcnt(0) in front of the stage's first fragment read, which would serialise the prefetch and drain the loads in
+// flight with it).  The kernels wait for their own pieces explicitly (eld_wait_vmcnt) before the barrier that publishes them.
+// s_nop 4: SALU-written soffset / descriptor -> VMEM read wait states; s_nop 0: M0 write -> LDS-DMA; M0 is saved and restored.
+// soff and lds_dst must be wave-uniform; a caller whose value the compiler cannot prove uniform passes it through readfirstlane (the "s"
+// constraint alone does not force an SGPR).
+__device__ __forceinline__ void lds_dma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
 }
 
 // fp32 counterpart of the full-line store.  Lane (m, hi) holds, for q = 0..3, channels 8q + 4hi .. +3 of pixel m of a 32-channel block: float4 v[q] is the

@@ -31,25 +31,9 @@
 // conv_tile_shape() picks (15 x 34, 17 x 30, 18 x 28 on the strip) it is 1.04x / 1.03x / 1.02x.  Launches that fuse the 2x2 max-pool keep 16 x 32
 // (the pool wants a lane's two rows to be a vertical pair); they still take the strip.
 #include <stdlib.h>
-#include "conv.h"
-
-#define TW 32
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+#include "conv_bf_dev.h"
 
 namespace {
-
-// One 1 KiB LDS-DMA piece (see conv_x3.hip::bdma16 for the inline-asm rationale: the compiler would order every later ds_read behind
-// a DMA it knows about; the kernel waits for its own pieces explicitly).
-__device__ __forceinline__ void bfd_dma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
-// wait until at most N of this wave's vector-memory operations are outstanding (they retire in issue order): everything older than the
-// N youngest has landed
-template <int N>
-__device__ __forceinline__ void bfd_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 template <int BN, int RPW, int WAVES>
 __global__ __launch_bounds__(64 * WAVES) void conv_bfd_kernel(const ConvArgs a) {
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfd_kernel(const ConvArgs a) 
 #pragma unroll
         for (int it = 0; it < A_IT; ++it) {
             const int piece = (wave + it * WAVES) % A_PIECES;            // wave-uniform
-            bfd_dma16(rsrc_a, a_voff[it], (unsigned)(cs * 64), ldsA_addr + (unsigned)(buf * A_BYTES + piece * 1024));
+            lds_dma16(rsrc_a, a_voff[it], (unsigned)(cs * 64), ldsA_addr + (unsigned)(buf * A_BYTES + piece * 1024));
         }
     };
     auto dma_B = [&](int buf, int nb, int chunk, int ky) {
@@ -142,7 +126,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfd_kernel(const ConvArgs a) 
 #pragma unroll
         for (int it = 0; it < B_IT; ++it) {
             const int piece = (wave + it * WAVES) % B_PIECES;
-            bfd_dma16(rsrc_w, dma_voff, soff + (unsigned)(piece * 1024), ldsB_addr + (unsigned)(buf * B_BYTES + piece * 1024));
+            lds_dma16(rsrc_w, dma_voff, soff + (unsigned)(piece * 1024), ldsB_addr + (unsigned)(buf * B_BYTES + piece * 1024));
         }
     };
 
@@ -175,7 +159,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfd_kernel(const ConvArgs a) 
             ep_rc[r][h] = p < NPX ? (unsigned)((tr << 8) | tc) : 0xFFFFu;
         }
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) fw_off[kb] = (unsigned)(m * 64 + (((kb * 2 + hi) ^ ((m >> 2) & 3)) * 16));
+    for (int kb = 0; kb < 2; ++kb) fw_off[kb] = bf_frag_off(m, kb, hi);
     const char* ldsA = lds + NBB * B_BYTES;
     const char* ldsB = lds;
 
@@ -223,8 +207,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfd_kernel(const ConvArgs a) 
             for (int ky = 0; ky < 3; ++ky) {
                 __builtin_amdgcn_s_setprio(3);
                 // this wave's pieces of THIS stage's operands have landed (the younger ones, for later stages, may still fly)
-                if (young == B_IT) bfd_wait_vm<B_IT>();
-                else if (young == B_IT + A_IT) bfd_wait_vm<B_IT + A_IT>();
+                if (young == B_IT) eld_wait_vmcnt<B_IT>();
+                else if (young == B_IT + A_IT) eld_wait_vmcnt<B_IT + A_IT>();
                 else eld_wait_vmcnt_dyn(young);
                 __syncthreads();                 // ... and everybody else's; the previous stage's fragment reads are done
                 // This stage's DMA pieces (the slab two stages ahead; at ky = 0 the halo tile three stages ahead).  A piece costs its wave 100-200
@@ -361,16 +345,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfd_kernel(const ConvArgs a) 
                         const bool over = row >= VP;
                         const int y = over ? row - VP : row, img = img0 + (over ? 1 : 0);
                         if (y >= a.H || img >= a.N) continue;
-                        uint2 pk[4];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            float u[4];
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) u[j] = fmax_lane_xor1(fmax_raw(acc[2 * rp][tt][4 * q + j], acc[2 * rp + 1][tt][4 * q + j]));
-                            pk[q] = pack_bf4(make_float4(u[0], u[1], u[2], u[3]));
-                        }
-                        // (every lane takes part in the exchanges; even pixels inside the image store)
-                        const uint4 w0 = bf16_pair_swap(pk[0], pk[1]), w1 = bf16_pair_swap(pk[2], pk[3]);
+                        uint4 w0, w1;
+                        bf_pool_block(acc[2 * rp][tt], acc[2 * rp + 1][tt], w0, w1);      // (every lane takes part in the exchanges; even pixels inside the image store)
                         if (xok && !(x & 1)) {
                             bf16_t* dp = static_cast<bf16_t*>(a.pool_out) + ((size_t)(img * Hp + (y >> 1)) * Wp + (x >> 1)) * a.Nout + nb * BN + tt * 32 + 8 * hi;
                             *reinterpret_cast<uint4*>(dp) = w0;
@@ -392,7 +368,6 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfd_kernel(const ConvArgs a) 
 
 template <int BN, int RPW, int WAVES>
 int launch_bfd(ConvArgs a, hipStream_t st) {
-    a.xcd = eld_xcd_mask() & XCD_BF16;
     constexpr int TH = WAVES * RPW;
     conv_tile_shape(a.N, a.H, a.W, TH, a.pool_out != nullptr, a.tile_h, a.tile_w);
     a.vp = vrow_pitch(a.N, a.H, a.tile_h);
@@ -402,16 +377,7 @@ int launch_bfd(ConvArgs a, hipStream_t st) {
     if (a.Nout > 1024) return ELD_ENOTSUP;
     const size_t lds_bytes = 2 * A_BYTES + 3 * B_BYTES + 4096;      // + bias (up to 1024 floats)
     const long long tiles = (long long)a.tiles_x * a.tiles_y * (a.Nout / BN);
-    if (tiles <= 0) return 0;
-    if (tiles > 0x7fffffffLL) return ELD_ENOTSUP;
-    auto kern = conv_bfd_kernel<BN, RPW, WAVES>;
-    static EldAttrOnce once;
-    { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
-    long long grid = (long long)eld_num_cus();
-    if (grid > tiles) grid = tiles;
-    ELD_LAUNCH(kern, dim3((unsigned)grid), dim3(64 * WAVES), lds_bytes, st, a);
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return launch_persistent<conv_bfd_kernel<BN, RPW, WAVES>>(a, tiles, 0x7fffffffLL, 64 * WAVES, lds_bytes, lds_bytes, st);
 }
 
 }  // namespace

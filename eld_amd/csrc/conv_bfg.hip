@@ -15,19 +15,9 @@
 //     instructions per wave -- past the end of the work, out-of-range dummies -- so the count is one immediate);
 //   * bias lives in LDS; outputs leave as full 64-byte runs per pixel (conv.h bf16_line_swap), forward scattered to the four taps' pixels.
 #include <stdlib.h>
-#include "conv.h"
-
-#define TW 32
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
+#include "conv_bf_dev.h"
 
 namespace {
-
-__device__ __forceinline__ void bfg_dma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {      // as conv_bfd.hip::bfd_dma16
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
 
 constexpr int BFG_NAB = 3, BFG_WAVES = 8, BFG_RPW = 2, BFG_TH = BFG_WAVES * BFG_RPW;
 constexpr int BFG_A_BYTES = BFG_TH * TW * 64;            // 32 KB: 512 pixels x one 32-channel chunk
@@ -116,19 +106,19 @@ __global__ __launch_bounds__(64 * BFG_WAVES) void conv_bfg_kernel(const ConvArgs
 #pragma unroll
         for (int it = 0; it < A_IT; ++it) {
             const unsigned voff = (live && a_pix[it] != OOB) ? (a_pix[it] + tapoff) * (unsigned)(Cs * 2) + a_oct[it] : OOB;
-            bfg_dma16(rsrc_a, voff, (unsigned)(chunk * 64), lds_base + (unsigned)(buf * A_BYTES + (wave + it * WAVES) * 1024));
+            lds_dma16(rsrc_a, voff, (unsigned)(chunk * 64), lds_base + (unsigned)(buf * A_BYTES + (wave + it * WAVES) * 1024));
         }
         {
             const int piece = wave % B_PIECES;
             const unsigned soff = live ? (unsigned)(((kslab << lNB) + nb) * B_BYTES + piece * 1024) : 0u;
-            bfg_dma16(rsrc_w, live ? (unsigned)lane * 16u : OOB, soff, ldsB_addr + (unsigned)(buf * B_BYTES + piece * 1024));
+            lds_dma16(rsrc_w, live ? (unsigned)lane * 16u : OOB, soff, ldsB_addr + (unsigned)(buf * B_BYTES + piece * 1024));
         }
     };
 
     // ---- fragment addresses ------------------------------------------------------------------------------------------------------------
     unsigned f_off[2];
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) f_off[kb] = (unsigned)(m * 64 + (((kb * 2 + hi) ^ ((m >> 2) & 3)) * 16));
+    for (int kb = 0; kb < 2; ++kb) f_off[kb] = bf_frag_off(m, kb, hi);
 
     issue(0);
     issue(1);
@@ -225,21 +215,11 @@ __global__ __launch_bounds__(64 * BFG_WAVES) void conv_bfg_kernel(const ConvArgs
 
 template <int BN, bool GATHER>
 int launch_bfg(ConvArgs a, hipStream_t st) {
-    a.xcd = eld_xcd_mask() & XCD_BF16;
     a.tiles_x = (a.W + TW - 1) / TW;
     a.tiles_y = (a.H + BFG_TH - 1) / BFG_TH;
     const size_t lds_bytes = (size_t)BFG_NAB * (BFG_A_BYTES + BN * 64) + BFG_BIAS_BYTES;
     const long long tiles = (long long)a.tiles_x * a.tiles_y * a.N;
-    if (tiles <= 0) return 0;
-    if (tiles > 0x00ffffffLL) return ELD_ENOTSUP;
-    auto kern = conv_bfg_kernel<BN, GATHER>;
-    static EldAttrOnce once;
-    { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
-    long long grid = (long long)eld_num_cus();
-    if (grid > tiles) grid = tiles;
-    ELD_LAUNCH(kern, dim3((unsigned)grid), dim3(64 * BFG_WAVES), lds_bytes, st, a);
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return launch_persistent<conv_bfg_kernel<BN, GATHER>>(a, tiles, 0x00ffffffLL, 64 * BFG_WAVES, lds_bytes, lds_bytes, st);
 }
 
 inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }

@@ -19,22 +19,9 @@
 //     sit between two tiles' pieces in the queue) -- "at most A_IT operations outstanding" implies "at most A_IT loads outstanding" either way.
 #include <stdlib.h>
 #include <atomic>
-#include "conv.h"
-
-#define TW 32
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "conv_bf_dev.h"
 
 namespace {
-
-__device__ __forceinline__ void bfs_dma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {      // as conv_bfd.hip::bfd_dma16
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void bfs_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 constexpr int BFS_NAB = 3;                               // activation ring depth
 constexpr int BFS_WCHUNK = 9 * 32 * 64;                  // packed weights of one 32-channel chunk: 18 DMA pieces
@@ -44,9 +31,9 @@ constexpr int BFS_WCHUNK = 9 * 32 * 64;                  // packed weights of on
 // pass through a phi (cdna_hip_programming.md 5.7 item 1: the compiler may copy them before the data has landed)
 template <int RPW, int WAVES, int ACT>
 __global__ __launch_bounds__(64 * WAVES) void conv_bfs_kernel(const ConvArgs a) {
-    constexpr int TH = WAVES * RPW, HW2 = TW + 2, A_PIX = (TH + 2) * HW2;
-    constexpr int A_UNITS = A_PIX * 4, A_PIECES = (A_UNITS + 63) / 64, A_BYTES = A_PIECES * 1024;
-    constexpr int A_IT = (A_PIECES + WAVES - 1) / WAVES;
+    constexpr int TH = WAVES * RPW;
+    using Halo = BfHalo<4, TH, WAVES>;                                   // a 32-channel chunk per pixel; f = (halo column >> 2) & 3 (conv_bfd.hip, header)
+    constexpr int HW2 = Halo::HW2, A_UNITS = Halo::UNITS, A_PIECES = Halo::PIECES, A_BYTES = Halo::BYTES, A_IT = Halo::IT;
     extern __shared__ __attribute__((aligned(16))) char lds[];           // [A0][A1][A2][W chunk 0][W chunk 1]
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -59,7 +46,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfs_kernel(const ConvArgs a) 
 
     const unsigned lds_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(size_t)(__attribute__((address_space(3))) char*)lds);
     const unsigned ldsW_addr = lds_base + BFS_NAB * A_BYTES;
-    constexpr unsigned OOB = 0xFFFFFFF0u;
+    constexpr unsigned OOB = Halo::OOB;
 
     // ---- the layer's weights: 18 * NCH linear 1 KiB pieces, dealt round-robin (a duplicate piece rewrites identical bytes) -------------------
     {
@@ -69,7 +56,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfs_kernel(const ConvArgs a) 
 #pragma unroll
         for (int it = 0; it < 5; ++it) {                                  // ceil(36 / 8) = 5; with NCH = 1 the later ones repeat earlier pieces
             const int piece = (wave + it * WAVES) % wpieces;
-            bfs_dma16(rsrc_w, (unsigned)lane * 16u, (unsigned)(piece * 1024), ldsW_addr + (unsigned)(piece * 1024));
+            lds_dma16(rsrc_w, (unsigned)lane * 16u, (unsigned)(piece * 1024), ldsW_addr + (unsigned)(piece * 1024));
         }
     }
 
@@ -130,7 +117,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfs_kernel(const ConvArgs a) 
 #pragma unroll
         for (int it = 0; it < A_IT; ++it) {
             const int piece = (wave + it * WAVES) % A_PIECES;
-            bfs_dma16(rsrc_a, a_voff[it], (unsigned)(cs * 64), lds_base + (unsigned)(buf * A_BYTES + piece * 1024));
+            lds_dma16(rsrc_a, a_voff[it], (unsigned)(cs * 64), lds_base + (unsigned)(buf * A_BYTES + piece * 1024));
         }
     };
 
@@ -141,10 +128,10 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfs_kernel(const ConvArgs a) 
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             const int hc = m + kx;
-            fx_off[kx][kb] = (unsigned)(hc * 64 + (((kb * 2 + hi) ^ ((hc >> 2) & 3)) * 16));
+            fx_off[kx][kb] = bf_frag_off(hc, kb, hi);
         }
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) fw_off[kb] = (unsigned)(m * 64 + (((kb * 2 + hi) ^ ((m >> 2) & 3)) * 16));
+    for (int kb = 0; kb < 2; ++kb) fw_off[kb] = bf_frag_off(m, kb, hi);
     const char* ldsW = lds + BFS_NAB * A_BYTES;
 
     // bias of this lane's 16 channels, loaded once (a load inside the loop's epilogue would drain the DMA queue ahead of it: vmcnt is in order)
@@ -167,7 +154,7 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfs_kernel(const ConvArgs a) 
         const int k = NCH == 2 ? (j >> 1) : j, chunk = NCH == 2 ? (j & 1) : 0;
         const int t = first + k * stride;
         // this wave's pieces of item j (and, the first time, of the weights) have landed; item j+1's may still fly
-        bfs_wait_vm<A_IT>();
+        eld_wait_vmcnt<A_IT>();
         __syncthreads();                         // ... and everybody else's; everybody is done reading ring slot (j - 1) % 3 = (j + 2) % 3
         if constexpr (ACT == 2) {                 // slope codes of this tile's output pixels: word (pixel x0 + m, hi) -- the MFMA result layout itself
             int img, y0, x0;
@@ -291,15 +278,8 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfs_kernel(const ConvArgs a) 
             for (int rp = 0; rp < RPW / 2; ++rp) {
                 const int y = y0 + wave * RPW + 2 * rp;
                 if (y >= a.H) continue;
-                uint2 pk[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    float u[4];
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) u[jj] = fmax_lane_xor1(fmax_raw(acc[2 * rp][4 * q + jj], acc[2 * rp + 1][4 * q + jj]));
-                    pk[q] = pack_bf4(make_float4(u[0], u[1], u[2], u[3]));
-                }
-                const uint4 w0 = bf16_pair_swap(pk[0], pk[1]), w1 = bf16_pair_swap(pk[2], pk[3]);
+                uint4 w0, w1;
+                bf_pool_block(acc[2 * rp], acc[2 * rp + 1], w0, w1);
                 if (!(x & 1)) {
                     bf16_t* dp = static_cast<bf16_t*>(a.pool_out) + ((size_t)(img * Hp + (y >> 1)) * Wp + (x >> 1)) * 32 + 8 * hi;
                     *reinterpret_cast<uint4*>(dp) = w0;
@@ -312,25 +292,15 @@ __global__ __launch_bounds__(64 * WAVES) void conv_bfs_kernel(const ConvArgs a) 
 
 template <int RPW, int WAVES, int ACT>
 int launch_bfs(ConvArgs a, hipStream_t st) {
-    a.xcd = eld_xcd_mask() & XCD_BF16;
     a.band = eld_tile_band();
     constexpr int TH = WAVES * RPW;
     a.tiles_x = (a.W + TW - 1) / TW;
     a.tiles_y = (a.H + TH - 1) / TH;
-    constexpr size_t A_BYTES = (size_t)(((TH + 2) * (TW + 2) * 4 + 63) / 64) * 1024;
+    constexpr size_t A_BYTES = BfHalo<4, TH, WAVES>::BYTES;
     const int NCH = (a.C0 + a.C1) >> 5;
     const size_t lds_bytes = BFS_NAB * A_BYTES + (size_t)NCH * BFS_WCHUNK;
     const long long tiles = (long long)a.tiles_x * a.tiles_y * a.N;
-    if (tiles <= 0) return 0;
-    if (tiles > 0x3fffffffLL) return ELD_ENOTSUP;
-    auto kern = conv_bfs_kernel<RPW, WAVES, ACT>;
-    static EldAttrOnce once;
-    { const int rc = once.ensure(kern, BFS_NAB * A_BYTES + 2 * (size_t)BFS_WCHUNK); if (rc) return rc; }
-    long long grid = (long long)eld_num_cus();
-    if (grid > tiles) grid = tiles;
-    ELD_LAUNCH(kern, dim3((unsigned)grid), dim3(64 * WAVES), lds_bytes, st, a);
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return launch_persistent<conv_bfs_kernel<RPW, WAVES, ACT>>(a, tiles, 0x3fffffffLL, 64 * WAVES, BFS_NAB * A_BYTES + 2 * (size_t)BFS_WCHUNK, lds_bytes, st);
 }
 
 }  // namespace

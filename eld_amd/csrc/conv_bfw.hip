@@ -16,21 +16,14 @@
 // The K order of the accumulation is (32-channel chunk, 16-channel half, ky, kx) instead of conv_igemm / conv_bfd's (chunk, ky, kx, half): results
 // equal theirs up to the fp32 summation order (tests compare with a bf16-rounding tolerance; the other DMA kernels are bit-identical to conv_igemm).
 #include <stdlib.h>
-#include "conv.h"
-
-#define TW 32
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+#include "conv_bf_dev.h"
 
 namespace {
 
-__device__ __forceinline__ void bfw_dma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {      // as conv_bfd.hip::bfd_dma16
-    unsigned keep;
-    soff = (unsigned)__builtin_amdgcn_readfirstlane((int)soff);        // wave-uniform by construction; the "s" constraint alone does not force an SGPR
-    lds_dst = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_dst);
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
+// conv.h lds_dma16 with soff and lds_dst forced into SGPRs: both are wave-uniform by construction here, but the compiler does not prove it for
+// this kernel, and the "s" constraint alone does not force an SGPR
+__device__ __forceinline__ void bfw_dma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {
+    lds_dma16(rsrc, voff, (unsigned)__builtin_amdgcn_readfirstlane((int)soff), (unsigned)__builtin_amdgcn_readfirstlane((int)lds_dst));
 }
 
 constexpr int BFW_NAB = 4;                               // activation ring depth
@@ -41,9 +34,9 @@ constexpr int BFW_WCHUNK = 9 * 64 * 64;                  // packed weights of on
 template <bool ACT>
 __global__ __launch_bounds__(512) void conv_bfw_kernel(const ConvArgs a) {
     constexpr int RPW = 2, WAVES = 8, NT = 2;
-    constexpr int TH = WAVES * RPW, HW2 = TW + 2, A_PIX = (TH + 2) * HW2;
-    constexpr int A_UNITS = A_PIX * 2, A_PIECES = (A_UNITS + 63) / 64, A_BYTES = A_PIECES * 1024;      // 1224 units -> 20 pieces
-    constexpr int A_IT = (A_PIECES + WAVES - 1) / WAVES;                                                 // 3
+    constexpr int TH = WAVES * RPW;
+    using Halo = BfHalo<2, TH, WAVES>;                                   // a 16-channel half chunk per pixel: 1224 units -> 20 pieces, 3 per wave
+    constexpr int HW2 = Halo::HW2, A_UNITS = Halo::UNITS, A_PIECES = Halo::PIECES, A_BYTES = Halo::BYTES, A_IT = Halo::IT;
     constexpr int ROWB = HW2 * 32;                                                                       // bytes of a halo row
     extern __shared__ __attribute__((aligned(16))) char lds[];           // [A0][A1][A2][A3][W chunk 0][W chunk 1]
 
@@ -58,7 +51,7 @@ __global__ __launch_bounds__(512) void conv_bfw_kernel(const ConvArgs a) {
 
     const unsigned lds_base = (unsigned)__builtin_amdgcn_readfirstlane((int)(size_t)(__attribute__((address_space(3))) char*)lds);
     const unsigned ldsW_addr = lds_base + BFW_NAB * A_BYTES;
-    constexpr unsigned OOB = 0xFFFFFFF0u;
+    constexpr unsigned OOB = Halo::OOB;
 
     // ---- the layer's weights: 36 * NCH linear 1 KiB pieces, dealt round-robin (a duplicate piece rewrites identical bytes) -------------------
     {
@@ -142,7 +135,7 @@ __global__ __launch_bounds__(512) void conv_bfw_kernel(const ConvArgs a) {
     for (int kx = 0; kx < 3; ++kx) fx_off[kx] = (unsigned)((m + kx) * 32 + ((hi ^ (((m + kx) >> 3) & 1)) * 16));
     unsigned fw_off[2];                                                   // slab rows of 64 B, units XOR-swizzled (conv_bfd.hip): half = k-block
 #pragma unroll
-    for (int kb = 0; kb < 2; ++kb) fw_off[kb] = (unsigned)(m * 64 + (((kb * 2 + hi) ^ ((m >> 2) & 3)) * 16));
+    for (int kb = 0; kb < 2; ++kb) fw_off[kb] = bf_frag_off(m, kb, hi);
     const char* ldsW = lds + BFW_NAB * A_BYTES;
 
     // bias -> LDS once per workgroup (a global load inside the loop would be waited for with a vmcnt that drains the DMA queue ahead of it).  The
@@ -249,15 +242,8 @@ __global__ __launch_bounds__(512) void conv_bfw_kernel(const ConvArgs a) {
             if (y < a.H) {
 #pragma unroll
                 for (int tt = 0; tt < NT; ++tt) {
-                    uint2 pk[4];
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        float u[4];
-#pragma unroll
-                        for (int jj = 0; jj < 4; ++jj) u[jj] = fmax_lane_xor1(fmax_raw(R[0][tt][4 * q + jj], R[1][tt][4 * q + jj]));
-                        pk[q] = pack_bf4(make_float4(u[0], u[1], u[2], u[3]));
-                    }
-                    const uint4 w0 = bf16_pair_swap(pk[0], pk[1]), w1 = bf16_pair_swap(pk[2], pk[3]);       // (every lane takes part)
+                    uint4 w0, w1;
+                    bf_pool_block(R[0][tt], R[1][tt], w0, w1);
                     if (x < a.W && !(x & 1)) {
                         bf16_t* dp = static_cast<bf16_t*>(a.pool_out) + ((size_t)(img * Hp + (y >> 1)) * Wp + (x >> 1)) * 64 + tt * 32 + 8 * hi;
                         *reinterpret_cast<uint4*>(dp) = w0;
@@ -338,23 +324,13 @@ __global__ __launch_bounds__(512) void conv_bfw_kernel(const ConvArgs a) {
 
 template <bool ACT>
 int launch_bfw(ConvArgs a, hipStream_t st) {
-    a.xcd = eld_xcd_mask() & XCD_BF16;
     constexpr int TH = 16;
     a.tiles_x = (a.W + TW - 1) / TW;
     a.tiles_y = (a.H + TH - 1) / TH;
-    constexpr size_t A_BYTES = (size_t)(((TH + 2) * (TW + 2) * 2 + 63) / 64) * 1024;
+    constexpr size_t A_BYTES = BfHalo<2, TH, 8>::BYTES;
     const size_t lds_bytes = BFW_NAB * A_BYTES + 2 * (size_t)BFW_WCHUNK + 256;      // + bias (the second weight chunk's space stays unused at K = 32)
     const long long tiles = (long long)a.tiles_x * a.tiles_y * a.N;
-    if (tiles <= 0) return 0;
-    if (tiles > 0x1fffffffLL) return ELD_ENOTSUP;
-    auto kern = conv_bfw_kernel<ACT>;
-    static EldAttrOnce once;
-    { const int rc = once.ensure(kern, lds_bytes); if (rc) return rc; }
-    long long grid = (long long)eld_num_cus();
-    if (grid > tiles) grid = tiles;
-    ELD_LAUNCH(kern, dim3((unsigned)grid), dim3(512), lds_bytes, st, a);
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return launch_persistent<conv_bfw_kernel<ACT>>(a, tiles, 0x1fffffffLL, 512, lds_bytes, lds_bytes, st);
 }
 
 }  // namespace

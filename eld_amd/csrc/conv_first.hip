@@ -414,10 +414,9 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_kernel(const TG* __restr
 // ------------------------------------------------------------------------------------------------------------------
 typedef __bf16 fw_bf16x8 __attribute__((ext_vector_type(8)));
 typedef short fw_s16x4 __attribute__((ext_vector_type(4)));
-typedef int fw_i32x4 __attribute__((ext_vector_type(4)));
 #define FXW 40                                   // padded row of a shifted halo copy (bf16 elements; 80 B keeps 16-byte alignment)
 
-__device__ __forceinline__ void fw_dma16(fw_i32x4 rsrc, unsigned voff, unsigned lds_dst) {
+__device__ __forceinline__ void fw_dma16(i32x4 rsrc, unsigned voff, unsigned lds_dst) {
     unsigned keep;
     asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory");
@@ -447,7 +446,7 @@ __global__ __launch_bounds__(256) void conv_first_wgrad_bf16_kernel(const bf16_t
     const unsigned lds_gl = (unsigned)__builtin_amdgcn_readfirstlane((int)(size_t)(__attribute__((address_space(3))) bf16_t*)&gl[0][0]);
     const unsigned long long gbase = (unsigned long long)g;
     const size_t gbytes = (size_t)N * H * W * 64;
-    const fw_i32x4 rsrc_g = {(int)(unsigned)gbase, (int)((unsigned)(gbase >> 32) & 0xFFFFu), (int)(gbytes < 0xFFFFFFF0ull ? gbytes : 0xFFFFFFF0ull), 0x00020000};
+    const i32x4 rsrc_g = {(int)(unsigned)gbase, (int)((unsigned)(gbase >> 32) & 0xFFFFu), (int)(gbytes < 0xFFFFFFF0ull ? gbytes : 0xFFFFFFF0ull), 0x00020000};
     f32x16 acc[2];
 #pragma unroll
     for (int jt = 0; jt < 2; ++jt)

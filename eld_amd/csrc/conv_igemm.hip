@@ -35,7 +35,6 @@
 
 #define ELD_FP32_CONV_DEFAULT 1
 #define PS 20           // LDS pixel stride in 4-byte words: one 64-byte K chunk (16 fp32 / 32 bf16 channels) + 16 bytes pad
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 #define TW 32
 

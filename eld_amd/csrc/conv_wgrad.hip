@@ -22,9 +22,7 @@
 #define TW 32
 #define JB 32     // j (shifted-operand channel) tile
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4_t __attribute__((ext_vector_type(4)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // BFM = true (bf16 inputs only): the tiles stay bf16 in LDS, untransposed [pixel][channel], and the contraction runs on
@@ -669,7 +667,7 @@ __global__ __launch_bounds__(512, 2) void wgrad8_kernel(const WgradArgs a) {
 // out-of-range buffer offsets.  The bias gradient (column sums of G) is read back from the landed G tile by the jb == 0 blocks.
 // Tiles: TH x TWT pixels over the virtual-row strip, as wgrad8_kernel; a block of X is padded to whole 1 KiB pieces so that a DMA instruction
 // never straddles two source tensors (virtual concat [x0, x1]).
-__device__ __forceinline__ void wg_dma16(i32x4_t rsrc, unsigned voff, unsigned lds_dst) {
+__device__ __forceinline__ void wg_dma16(i32x4 rsrc, unsigned voff, unsigned lds_dst) {
     unsigned keep;
     asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(lds_dst) : "memory");
@@ -767,7 +765,7 @@ __global__ __launch_bounds__(512, 2) void wgrad8d_kernel(const WgradArgs a) {
         const unsigned dst0 = lds_base + (unsigned)(buf * BUF_BYTES);
         {
             const unsigned long long gb = (unsigned long long)(static_cast<const char*>(a.g) + (size_t)img0 * g_img);
-            const i32x4_t rs = {(int)(unsigned)gb, (int)((unsigned)(gb >> 32) & 0xFFFFu), (int)(unsigned)(g_img * (size_t)nimg), 0x00020000};
+            const i32x4 rs = {(int)(unsigned)gb, (int)((unsigned)(gb >> 32) & 0xFFFFu), (int)(unsigned)(g_img * (size_t)nimg), 0x00020000};
             const unsigned b0 = (unsigned)((vrel * a.W + x0) * a.CA) * 2u, b1 = (unsigned)((row1 * a.W + x0) * a.CA) * 2u;
 #pragma unroll
             for (int it = 0; it < G_IT; ++it) {
@@ -787,7 +785,7 @@ __global__ __launch_bounds__(512, 2) void wgrad8d_kernel(const WgradArgs a) {
             for (int cb = 1; cb < WCI; ++cb) if (blk == cb) { src = xs[cb]; C = xC[cb]; }
             const size_t x_img = (size_t)a.H * a.W * C * 2;
             const unsigned long long xb = (unsigned long long)(src ? src + (size_t)img0 * x_img : nullptr);
-            const i32x4_t rs = {(int)(unsigned)xb, (int)((unsigned)(xb >> 32) & 0xFFFFu), src ? (int)(unsigned)(x_img * (size_t)nimg) : 0, 0x00020000};
+            const i32x4 rs = {(int)(unsigned)xb, (int)((unsigned)(xb >> 32) & 0xFFFFu), src ? (int)(unsigned)(x_img * (size_t)nimg) : 0, 0x00020000};
             const unsigned b0 = (unsigned)((vrel * a.W + x0) * C) * 2u, b1 = (unsigned)((row1 * a.W + x0) * C) * 2u;
             const int r = (x_rc[it] >> 8) - 1, gx = x0 - 1 + (x_rc[it] & 255);
             const bool second = r >= nxt;

@@ -310,11 +310,8 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const ConvArgs a) {
 //                    issue DMA of slab s+1 into the other buffer; ky == 0: issue the next chunk's halo loads into registers
 //                    3 taps x 6 piece products x RPW x NT MFMAs out of LDS
 // Barriers per chunk: 4 (was 6); VALU per MFMA: the activation cut only.  WAVES = 4 (two workgroups per CU) or 8 (one).
-// One 1 KiB LDS-DMA piece: lane l copies the 16 bytes at buffer offset voff (per lane) + soff (wave-uniform) to LDS byte address
-// lds_dst + 16 l (lds_dst wave-uniform).  Issued through inline asm ON PURPOSE: hipcc orders every later ds_read behind an LDS-DMA it
-// knows about (s_waitcnt vmcnt(0) in front of the stage's first fragment read, which would serialise the prefetch and drain the halo
-// loads with it).  The kernel waits for its own pieces explicitly (dma_wait) before the barrier that publishes the slab.
-// s_nop 4: SALU-written soffset / descriptor -> VMEM read wait states; s_nop 0: M0 write -> LDS-DMA; M0 is saved and restored.
+// The slab travels in 1 KiB LDS-DMA pieces (conv.h lds_dma16, where the inline-asm rationale lives); the kernel waits for its own pieces
+// explicitly (eld_wait_vmcnt<0>) before the barrier that publishes the slab.
 template <int BN, int RPW, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, 2) void conv_x3d_kernel(const ConvArgs a) {
     constexpr int CK = 16, THREADS = 64 * WAVES;
@@ -417,7 +414,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_x3d_kernel(const ConvArgs 
 #pragma unroll
         for (int it = 0; it < DMA_IT; ++it) {
             const int piece = wave + it * WAVES;             // wave-uniform
-            if (piece < B_PIECES) bdma16(rsrc_w, dma_voff, soff + (unsigned)(piece * 1024), ldsB_addr + (unsigned)(buf * B_WORDS * 4 + piece * 1024));
+            if (piece < B_PIECES) lds_dma16(rsrc_w, dma_voff, soff + (unsigned)(piece * 1024), ldsB_addr + (unsigned)(buf * B_WORDS * 4 + piece * 1024));
         }
     };
 
@@ -463,7 +460,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void conv_x3d_kernel(const ConvArgs 
                 __builtin_amdgcn_s_setprio(3);   // the short staging section goes ahead of co-resident waves' MFMA streams
                 if ((ELD_DBG(a) & 2048) && after_epi) after_epi = false;      // (dev probe 2048: no drain of the epilogue's stores -- timing only, the slab is not waited for)
                 else
-                dma_wait();                      // this wave's pieces of the stage's slab (issued one stage ago) have landed (round 5: a counted wait that
+                eld_wait_vmcnt<0>();                      // this wave's pieces of the stage's slab (issued one stage ago) have landed (round 5: a counted wait that
                                                  // leaves the halo loads of the chunk's first stage in flight here measured 0.0 %: profiles/r05_ab_notes.md)
                 __syncthreads();                 // ... and so have everybody else's; the previous stage's fragment reads are done
                 if (ky == 0) {

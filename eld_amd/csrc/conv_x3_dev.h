@@ -1,5 +1,5 @@
 // conv_x3_dev.h -- device helpers shared by the three-piece fp32 3x3 kernels (conv_x3.hip, conv_x3w.hip): the exact three-piece cut of four fp32 values
-// into an LDS row, the staging-row permutation, the fused 2x2 max-pool epilogue, the LDS-DMA piece, the streamed fragment blocks of a stage.
+// into an LDS row, the staging-row permutation, the fused 2x2 max-pool epilogue, the streamed fragment blocks of a stage.
 #pragma once
 #include "conv.h"
 
@@ -7,8 +7,6 @@ namespace {
 
 #define PX 28
 #define TW 32
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 
 __device__ __forceinline__ unsigned hi_pair(unsigned lo_src, unsigned hi_src) {        // (hi_src & 0xFFFF0000) | (lo_src >> 16)
     return __builtin_amdgcn_perm(hi_src, lo_src, 0x07060302u);
@@ -88,14 +86,6 @@ __device__ __forceinline__ void pool_epilogue(const ConvArgs& a, const f32x16 (&
         }
     }
 }
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void bdma16(i32x4 rsrc, unsigned voff, unsigned soff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(rsrc), "s"(soff), "s"(lds_dst) : "memory");
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // Streamed fragment blocks (round 6).  A stage's MFMA work is a sequence of blocks b = (tap kx, pixel row r, channel block tt), six piece products on ONE
 // accumulator each (smallest first: the per-accumulator summation order of the round-5 loops, so results are the same bits).  hipcc's own schedule of the

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(64 * (W_CW + W_PW), (W_CW + W_PW) / 4) void conv_x3
         const unsigned soff = (unsigned)((ky * NCH + c) * (W_BWORDS * 4));
 #pragma unroll
         for (int piece = 0; piece < W_BPIECES; ++piece)
-            bdma16(rsrc_w, (unsigned)lane * 16u, soff + (unsigned)(piece * 1024), ldsB_addr + (unsigned)(buf * W_BWORDS * 4 + piece * 1024));
+            lds_dma16(rsrc_w, (unsigned)lane * 16u, soff + (unsigned)(piece * 1024), ldsB_addr + (unsigned)(buf * W_BWORDS * 4 + piece * 1024));
     };
 
     // The two roles are two separate loops over the same stage sequence (prologue barrier, then one barrier per (tile, chunk, kernel row)): their registers
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(64 * (W_CW + W_PW), (W_CW + W_PW) / 4) void conv_x3
         // SLAB wave: the next stage's weight slab, one stage ahead
         // ======================================================================================================================================
         dma_slab(0, 0, 0);
-        dma_wait();
+        eld_wait_vmcnt<0>();
         __syncthreads();
         int g = 0, sb = 0;
         for (int k = 0; k < my_tiles; ++k)
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(64 * (W_CW + W_PW), (W_CW + W_PW) / 4) void conv_x3
                     prof(20);
                     if (g + 1 < n_chunks || ky < 2) dma_slab(sb ^ 1, c1, ky1);      // (the other ring buffer: everybody finished reading it at the last barrier)
                     prof(21);
-                    dma_wait();
+                    eld_wait_vmcnt<0>();
                     prof(22);
                     __syncthreads();
                     sb ^= 1;
