@@ -30,7 +30,6 @@ An -o that ends in .dng writes the stack from the device tensor as lossless-JPEG
 the first .dng input, else of the sidecar.
 """
 import argparse
-import ctypes
 import glob
 import json
 import sys
@@ -39,6 +38,7 @@ import numpy as np
 
 from . import _lib as L
 from . import mosaic as M
+from .defects import as_defect_map
 
 NB = L.PAIRSTATS_BINS
 MAX_FRAMES = 256
@@ -148,26 +148,14 @@ def _min_dev(min_dev):
 
 
 def _check_burst(frames, cfa, what='frames'):
-    from .denoise import _as_u16, _check_sides
-    try:
-        _, batched = _as_u16(frames)
-    except ValueError as e:
-        raise ValueError('%s: %s' % (what, e))
-    if not batched:
+    N, Hm, Wm = M.check_stack(frames, what)
+    if len(frames.shape) != 3:
         raise ValueError('%s: a burst is a stack (N, Hm, Wm), got shape %s' % (what, tuple(frames.shape)))
-    N, Hm, Wm = (int(v) for v in frames.shape)
     if N < 2 or N > MAX_FRAMES:
         raise ValueError('%s: a burst holds 2 to %d frames, got %d' % (what, MAX_FRAMES, N))
-    _check_sides(Hm, Wm, cfa)
-    if Hm * Wm >= 1 << 31:
-        raise ValueError('%s: a frame of %d x %d has 2^31 sites or more' % (what, Hm, Wm))
+    M.check_sides(Hm, Wm, cfa)
+    M.check_site_count(Hm, Wm, what)
     return N, Hm, Wm
-
-
-def _period(cfa):
-    if cfa not in ('bayer', 'xtrans'):
-        raise ValueError("cfa must be 'bayer' or 'xtrans', got %r" % (cfa,))
-    return 2 if cfa == 'bayer' else 6
 
 
 def align_levels(Hm, Wm, p, levels=None):
@@ -206,7 +194,7 @@ def align_burst(frames, cfa='bayer', ref=0, levels=None):
     (default: as many as the frame allows, at most 4; each level doubles the reach: 4, 12, 28, 60 CFA periods).  -> BurstAlignment.
     Translation per tile in whole CFA periods; no rotation model, no exposure compensation.  Bad arguments raise ValueError before any
     device work."""
-    p = _period(cfa)
+    p = M.period_of(cfa)
     N, Hm, Wm = _check_burst(frames, cfa)
     ref = _check_ref(ref, N)
     levels = align_levels(Hm, Wm, p, levels)
@@ -245,13 +233,12 @@ def stack_burst(frames, cfa='bayer', raw_pattern=None, black_level=None, white_l
     as given.  An aligned stack takes each site's samples through the field, reports in `present` how many lay inside the frame, applies
     the rule over those, and counts only sites with all N present in the photon-transfer sums.
     Bad arguments raise ValueError before any device work."""
-    from .evaluate import _cells, _white
-    p, group, G, black = _cells(cfa, raw_pattern, black_level)
-    white = _white(white_level)
+    lay = M.CfaLayout.for_codes(cfa, raw_pattern, black_level)
+    p, group, G, black = lay.period, lay.group, lay.G, lay.black_ints
+    white = M.check_white(white_level)
     k2q, min_dev = _k2q(k), _min_dev(min_dev)
     N, Hm, Wm = _check_burst(frames, cfa)
     if defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'stack_burst')
     if align is not None and align is not False and align is not True:
@@ -274,8 +261,7 @@ def stack_burst(frames, cfa='bayer', raw_pattern=None, black_level=None, white_l
             need = lib.eld_burst_stack_aligned_workspace_bytes(N, Hm, Wm)
             ws = torch.empty(max(need, 4), dtype=torch.uint8, device=u.device)
             bm = None if defects is None else defects.bitmap_on(u.device)
-            L.check(lib.eld_burst_stack_aligned_u16(L.dptr(u), N, Hm, Wm, p, (ctypes.c_int * (p * p))(*group), G, (ctypes.c_int32 * (p * p))(*black),
-                                                    white, L.dptr(bm), k2q, min_dev, L.dptr(disp), TY, TX, L.dptr(mean), L.dptr(kept),
+            L.check(lib.eld_burst_stack_aligned_u16(L.dptr(u), N, Hm, Wm, p, lay.c_group(), G, lay.c_black(), white, L.dptr(bm), k2q, min_dev, L.dptr(disp), TY, TX, L.dptr(mean), L.dptr(kept),
                                                     L.dptr(present), L.dptr(ptc), L.dptr(ws), need, L.cur_stream()),
                     'eld_burst_stack_aligned_u16')
         return BurstStack(mean.view(torch.uint16), kept, ptc.cpu().numpy(), N, cfa, p, group, G, black, white, k2q, min_dev, present, align)
@@ -284,10 +270,9 @@ def stack_burst(frames, cfa='bayer', raw_pattern=None, black_level=None, white_l
         kept = torch.empty((Hm, Wm), dtype=torch.uint8, device=u.device)
         ptc = torch.empty((G, NB, 4), dtype=torch.int64, device=u.device)
         need = lib.eld_burst_stack_workspace_bytes(N, Hm, Wm)
-        ws = torch.empty(need, dtype=torch.uint8, device=u.device) if need else None
+        ws = M.workspace(need, u.device)
         bm = None if defects is None else defects.bitmap_on(u.device)
-        L.check(lib.eld_burst_stack_u16(L.dptr(u), N, Hm, Wm, p, (ctypes.c_int * (p * p))(*group), G, (ctypes.c_int32 * (p * p))(*black), white,
-                                        L.dptr(bm), k2q, min_dev, L.dptr(mean), L.dptr(kept), L.dptr(ptc), L.dptr(ws), need, L.cur_stream()),
+        L.check(lib.eld_burst_stack_u16(L.dptr(u), N, Hm, Wm, p, lay.c_group(), G, lay.c_black(), white, L.dptr(bm), k2q, min_dev, L.dptr(mean), L.dptr(kept), L.dptr(ptc), L.dptr(ws), need, L.cur_stream()),
                 'eld_burst_stack_u16')
     return BurstStack(mean.view(torch.uint16), kept, ptc.cpu().numpy(), N, cfa, p, group, G, black, white, k2q, min_dev)
 
@@ -371,16 +356,9 @@ def weighted_line(n, mu, var, line, what='burst'):
 # ---- flicker -------------------------------------------------------------------------------------------------------------------------------
 def frame_levels(frames, cfa='bayer', raw_pattern=None, black_level=None, defects=None):
     """The mean level of every frame in DN above black, float64 (N,), and the sites behind it: eld_struct_sums_u16's exact cell sums."""
-    from .evaluate import _cells
     from .structure import structure_sums
-    p, _, _, black = _cells(cfa, raw_pattern, black_level)
-    if cfa == 'xtrans' and raw_pattern is None:
-        from .defects import xtrans_tables
-        raw_pattern = xtrans_tables()['colour']
-    elif raw_pattern is None:
-        from .denoise import DEFAULT_PATTERN
-        raw_pattern = DEFAULT_PATTERN
-    cell = structure_sums(frames, cfa, raw_pattern, black, defects=defects)['cell']          # (N, p*p, 3) = (n, sum d, sum d^2)
+    lay = M.CfaLayout.for_codes(cfa, raw_pattern, black_level)
+    cell = structure_sums(frames, cfa, M.default_pattern(cfa, raw_pattern), lay.black_ints, defects=defects)['cell']          # (N, p*p, 3) = (n, sum d, sum d^2)
     n = cell[..., 0].sum(axis=1)
     return cell[..., 1].sum(axis=1) / np.maximum(n, 1), int(n[0])
 
@@ -450,7 +428,6 @@ def run(frames, o, k=5.0, min_dev=2, align=False, ref=0):
     kw = dict(cfa=o.get('cfa', 'bayer'), raw_pattern=o.get('raw_pattern'), black_level=o.get('black_level'))
     defects = o.get('defects')
     if defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects)
     field = align_burst(frames, kw['cfa'], ref) if align else None
     stack = stack_burst(frames, white_level=o.get('white_point', 16383), k=k, min_dev=min_dev, defects=defects, align=field, **kw)

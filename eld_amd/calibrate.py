@@ -29,8 +29,7 @@ import numpy as np
 
 from . import _lib as L
 from .defects import as_defect_map, check_defects, find_defects
-from .mosaic import (CODE_COLOUR, XT_PERIOD, bayer_pattern, black_levels, cell_counts, check_cfa, check_mosaics,  # noqa: F401 (re-exported)
-                     check_sessions as _check_sessions, device_u16, shape_of, workspace, xtrans_pattern)
+from .mosaic import XT_PERIOD, CfaLayout, black_levels, cell_counts, check_cfa, check_mosaics, check_sessions as _check_sessions, device_u16, shape_of, workspace
 
 DEFAULT_LAMBDAS = np.linspace(-1.0, 1.0, 141)     # scipy.stats.ppcc_plot(x, -1, 1, N=141): every shipped G_shape lies on it
 PROFILE = 'Profile-1'
@@ -72,7 +71,8 @@ def bias_stats_from_sums_masked(chan_sums, row_sums, raw_pattern, black_level, H
     """bias_stats_from_sums over the unflagged sites only: chan_sums / row_sums are the sums over those sites, chan_counts (4,) and
     row_counts (Hm,2) (even / odd columns) their numbers.  Without counts (or with every site counted) it IS bias_stats_from_sums: the
     same expressions, hence the same bits."""
-    pat, black = bayer_pattern(raw_pattern), black_levels(black_level)
+    lay = CfaLayout('bayer', raw_pattern, black_level)
+    pat, black = lay.codes, lay.black
     full = chan_counts is None or (np.all(np.asarray(chan_counts) == Hm * Wm // 4) and np.all(np.asarray(row_counts) == Wm // 2))
     chan_sums, row_sums = np.asarray(chan_sums), np.asarray(row_sums)
     nc = np.full(4, Hm * Wm // 4, np.int64) if full else np.asarray(chan_counts, np.int64).reshape(4)
@@ -106,13 +106,13 @@ def xtrans_bias_stats_from_cell_sums(cell_sums, row_sums, raw_pattern, black_lev
 def xtrans_bias_stats_from_cell_sums_masked(cell_sums, row_sums, raw_pattern, black_level, Hm, Wm, cell_n=None, row_n=None):
     """xtrans_bias_stats_from_cell_sums over the unflagged sites only: cell_n (6,6) and row_n (Hm,6) count them per cell and per row and
     column class.  Without counts (or with every site counted) it IS xtrans_bias_stats_from_cell_sums."""
-    pat, black = xtrans_pattern(raw_pattern), black_levels(black_level)
+    lay = CfaLayout('xtrans', raw_pattern, black_level)
     ncol = cell_counts(1, Wm)[0]                                          # pixels per column class in one row
     full = cell_n is None or (np.array_equal(cell_n, cell_counts(Hm, Wm)) and np.array_equal(row_n, np.broadcast_to(ncol, (Hm, XT_PERIOD))))
     cs, rs = np.asarray(cell_sums).reshape(-1, XT_PERIOD, XT_PERIOD, 2), np.asarray(row_sums)
     ncell = cell_counts(Hm, Wm) if full else np.asarray(cell_n, np.int64).reshape(XT_PERIOD, XT_PERIOD)
     F = cs.shape[0]
-    bcell, col = black[pat], CODE_COLOUR[pat]                             # (6,6) black level and colour of each cell
+    bcell, col = lay.black_cells, lay.colour                              # (6,6) black level and colour of each cell
     for k in range(3):
         if ncell[col == k].sum() == 0:
             raise ValueError('colour %d has no unflagged site' % k)
@@ -165,12 +165,12 @@ def xtrans_flat_stats_from_cell_sums(sums, raw_pattern, black_level, white_level
 
 def xtrans_flat_stats_from_cell_sums_masked(sums, raw_pattern, black_level, white_level, color_bias, Hm, Wm, cell_n=None):
     """xtrans_flat_stats_from_cell_sums over the unflagged sites only (cell_n (6,6) of them per cell; default: every site)."""
-    pat, black = xtrans_pattern(raw_pattern), black_levels(black_level)
+    lay = CfaLayout('xtrans', raw_pattern, black_level)
     sums = np.asarray(sums).reshape(-1, XT_PERIOD, XT_PERIOD, 4)
     P = sums.shape[0]
     cbm = np.asarray(color_bias, np.float64).reshape(3)
     ncell = cell_counts(Hm, Wm) if cell_n is None else np.asarray(cell_n, np.int64).reshape(XT_PERIOD, XT_PERIOD)
-    bcell, col = black[pat], CODE_COLOUR[pat]
+    bcell, col = lay.black_cells, lay.colour
     mu, var, usable = np.zeros((P, 3)), np.zeros((P, 3)), np.zeros((P, 3), bool)
     for k in range(3):
         m = col == k
@@ -333,7 +333,8 @@ def bias_frame_stats(bias, raw_pattern, black_level, residual=False, defects=Non
     defects (a DefectMap): every statistic is over its unflagged sites only -- the sums have the flagged sites' contributions taken out
     (exactly, on the host), 'chan_counts' (4,) and 'row_counts' (Hm,2) count what is left, and 't' is (F, Hm*Wm - K): the flagged
     entries are dropped."""
-    pat, black = bayer_pattern(raw_pattern), black_levels(black_level)
+    lay = CfaLayout('bayer', raw_pattern, black_level)
+    pat, black = lay.codes, lay.black
     F, Hm, Wm = check_mosaics(bias, 3, 'bias')
     defects = check_defects(defects, 'bayer', (Hm, Wm))
     u = device_u16(bias)
@@ -343,7 +344,7 @@ def bias_frame_stats(bias, raw_pattern, black_level, residual=False, defects=Non
         out['row_counts'], out['chan_counts'] = row_n, _to_channels(cell_n, pat, axis=0)
     out.update(bias_stats_from_sums_masked(out['chan_sums'], rs, pat, black, Hm, Wm, out.get('chan_counts'), row_n))
     if residual:
-        out['t'] = _cell_residual(u, 2, black[pat], out['color_bias'][:, pat.reshape(-1)], out['row_offset'], defects)
+        out['t'] = _cell_residual(u, 2, lay.black_cells, out['color_bias'][:, pat.reshape(-1)], out['row_offset'], defects)
     return out
 
 
@@ -393,7 +394,8 @@ def flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias, de
     """Flat pairs (P,2,Hm,Wm) uint16 -> dict: sums int64 (P,4,4) = per channel (sum(a+b), sum(a-b), sum((a-b)^2), saturated pixels),
     mu (P,4) = mean((a+b)/2) - black_c - color_bias_c, var (P,4) = var(a-b)/2, usable (P,4) bool (no saturated pixel and
     0 < mu <= 0.8 (white - black_c)).  color_bias: the session's mean colour bias (4,)."""
-    pat, black = bayer_pattern(raw_pattern), black_levels(black_level)
+    lay = CfaLayout('bayer', raw_pattern, black_level)
+    pat, black = lay.codes, lay.black
     P, _, Hm, Wm = check_mosaics(flats, 4, 'flats')
     defects = check_defects(defects, 'bayer', (Hm, Wm))
     cbm = np.asarray(color_bias, np.float64).reshape(4)
@@ -409,7 +411,7 @@ def xtrans_bias_frame_stats(bias, raw_pattern, black_level, residual=False, defe
     """X-Trans bias frames (F,Hm,Wm) uint16 -> dict: cell_sums int64 (F,6,6,2), row_sums int64 (F,Hm,6), color_bias (F,3), row_offset
     (F,Hm), g_scale, R_scale (F,); with residual=True also 't' (CUDA float32 (F,Hm*Wm)) = float32(((u - black_code) - cb) - rho_y).
     defects: as bias_frame_stats, with 'cell_counts' (6,6) and 'row_counts' (Hm,6)."""
-    pat, black = xtrans_pattern(raw_pattern), black_levels(black_level)
+    lay = CfaLayout('xtrans', raw_pattern, black_level)
     F, Hm, Wm = check_mosaics(bias, 3, 'bias', 'xtrans')
     defects = check_defects(defects, 'xtrans', (Hm, Wm), raw_pattern)
     u = device_u16(bias)
@@ -417,23 +419,23 @@ def xtrans_bias_frame_stats(bias, raw_pattern, black_level, residual=False, defe
     out = {'cell_sums': cs, 'row_sums': rs}
     if cell_n is not None:
         out['cell_counts'], out['row_counts'] = cell_n, row_n
-    out.update(xtrans_bias_stats_from_cell_sums_masked(cs, rs, pat, black, Hm, Wm, cell_n, row_n))
+    out.update(xtrans_bias_stats_from_cell_sums_masked(cs, rs, lay.codes, lay.black, Hm, Wm, cell_n, row_n))
     if residual:                                              # the colour bias of each cell's colour, (F,36)
-        out['t'] = _cell_residual(u, XT_PERIOD, black[pat], out['color_bias'][:, CODE_COLOUR[pat].reshape(-1)], out['row_offset'], defects)
+        out['t'] = _cell_residual(u, XT_PERIOD, lay.black_cells, out['color_bias'][:, lay.colour.reshape(-1)], out['row_offset'], defects)
     return out
 
 
 def xtrans_flat_pair_stats(flats, raw_pattern, black_level, white_level, color_bias, defects=None):
     """X-Trans flat pairs (P,2,Hm,Wm) uint16 -> dict: sums int64 (P,6,6,4) per cell, mu, var (P,3), usable (P,3) per colour.
     color_bias: the session's mean (R, G, B) bias."""
-    pat, black = xtrans_pattern(raw_pattern), black_levels(black_level)
+    lay = CfaLayout('xtrans', raw_pattern, black_level)
     P, _, Hm, Wm = check_mosaics(flats, 4, 'flats', 'xtrans')
     defects = check_defects(defects, 'xtrans', (Hm, Wm), raw_pattern)
     sums, cell_n = _cell_flat_sums(device_u16(flats), XT_PERIOD, white_level, defects)
     res = {'sums': sums}
     if cell_n is not None:
         res['cell_counts'] = cell_n
-    res.update(xtrans_flat_stats_from_cell_sums_masked(res['sums'], pat, black, white_level, color_bias, Hm, Wm, res.get('cell_counts')))
+    res.update(xtrans_flat_stats_from_cell_sums_masked(res['sums'], lay.codes, lay.black, white_level, color_bias, Hm, Wm, res.get('cell_counts')))
     return res
 
 
@@ -493,9 +495,7 @@ def calibrate_camera(sessions, raw_pattern, black_level, white_level, lambdas=No
     regression, and diag 'column': per session {'iso', 'col_var', 'col_fixed_var', 'fixed_share'} (the last three None for a session of one
     bias frame).  A frame whose sample is not positive is a ValueError that says to drop the flag.  False (default): table and diag are what
     they were, keys and bits."""
-    xt = check_cfa(cfa) == 'xtrans'
-    xtrans_pattern(raw_pattern) if xt else bayer_pattern(raw_pattern)
-    black_levels(black_level)
+    xt = CfaLayout(cfa, raw_pattern, black_level).cfa == 'xtrans'
     check_defects(defects, cfa, raw_pattern=raw_pattern)
     _check_sessions(sessions, cfa)
     if defects is not None and not isinstance(defects, str):

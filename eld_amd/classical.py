@@ -189,7 +189,7 @@ def bm3d_vst(x, qscale, fwd, guide, S, step, Gmax, mix, tau, par, win, frac, out
 
 
 # ---- the denoiser ---------------------------------------------------------------------------------------------------------------------------
-def _camera_table(camera):
+def camera_table(camera):
     """A calibrated table: the dict itself, the name of a table (camera_params/release/<name>_params.npy of the working directory, else the
     tables shipped with the package) or the path of a <name>_params.npy file."""
     if isinstance(camera, dict):
@@ -212,7 +212,7 @@ def sigma_from_table(camera, K):
     """The read noise in DN the table's 'Profile-1' g_scale line gives at log K: exp(slope log K + bias)."""
     K = _check_noise(K, 0.0)[0]
     try:
-        line = _camera_table(camera)['Profile-1']['g_scale']
+        line = camera_table(camera)['Profile-1']['g_scale']
         slope, bias = float(line['slope']), float(line['bias'])
     except (KeyError, TypeError):
         raise ValueError("the camera table has no 'Profile-1' g_scale line")
@@ -233,8 +233,8 @@ class ClassicalDenoiser:
     is_classical = True
 
     def __init__(self, cfa, K, sigma=None, camera=None, search=None, patch=2, strength=None, method='nlm', step=3, group=16, mix=None):
-        from .denoise import PLANES, _check_cfa
-        _check_cfa(cfa)
+        from .mosaic import PLANES, check_cfa
+        check_cfa(cfa)
         if method not in METHODS:
             raise ValueError('method must be one of %r, got %r' % (METHODS, method))
         bm3d = method == 'bm3d'
@@ -310,7 +310,7 @@ class ClassicalDenoiser:
         return self.planes
 
     def black_per_plane(self, black_level):
-        """denoise._levels' black levels (4 for Bayer, in colour-code order = plane order; one for X-Trans) -> one per packed plane"""
+        """mosaic.levels' black levels (4 for Bayer, in colour-code order = plane order; one for X-Trans) -> one per packed plane"""
         b = [float(v) for v in black_level]
         return b if self.cfa == 'bayer' else [b[0]] * self.planes
 

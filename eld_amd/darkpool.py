@@ -18,8 +18,11 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
-from .denoise import _as_u16, _check_cfa
+from . import calibrate as CAL
+from .defects import find_defects
 from .framepool import FramePool
+from .mosaic import as_u16, check_cfa
+from .shading import as_dark_shading
 
 
 class DarkPool:
@@ -39,7 +42,7 @@ class DarkPool:
     Bad arguments raise ValueError before any device work."""
 
     def __init__(self, sessions, cfa='bayer', raw_pattern=None, black_level=None, white_level=16383, K=None, defects=None, device=None, shading=None):
-        _check_cfa(cfa)
+        check_cfa(cfa)
         if not isinstance(sessions, (list, tuple)) or len(sessions) == 0:
             raise ValueError('sessions must be a non-empty list of {"bias": frames[, "iso"]}')
         frames, ranges, isos = [], [], []
@@ -50,7 +53,7 @@ class DarkPool:
             items = [b] if (isinstance(b, np.ndarray) or hasattr(b, 'is_cuda')) else list(b)
             mine = []
             for m in items:
-                _, batched = _as_u16(m)
+                _, batched = as_u16(m)
                 mine.extend(list(m) if batched else [m])
             if not mine:
                 raise ValueError('session %d has no bias frames' % i)
@@ -63,7 +66,6 @@ class DarkPool:
                 raise ValueError('K holds one finite gain > 0 per session (%d), got %r' % (len(sessions), K.tolist()))
         tvals = None
         if shading is not None:
-            from .shading import as_dark_shading
             shading = as_dark_shading(shading)
             for i, m in enumerate(frames):
                 shading.check_frames(m.shape, cfa, 'frame %d' % i)
@@ -99,7 +101,6 @@ class DarkPool:
         gains, one per session; or the path of a table eld_amd.calibrate wrote.  A table keeps only the range [Kmin, Kmax] of the gains, not
         the gain of each session, so with a path the calibration runs as well and the gains it finds must lie in the table's range
         (ValueError otherwise: the table belongs to other frames)."""
-        from . import calibrate as CAL
         sessions, pattern, black, white, cfa = CAL.load_manifest(path, with_cfa=True)
         if defects is None:
             defects = CAL.manifest_defects(path)
@@ -114,7 +115,6 @@ class DarkPool:
             if table is not None and not (float(table['Kmin']) * (1 - 1e-6) <= min(K) and max(K) <= float(table['Kmax']) * (1 + 1e-6)):
                 raise ValueError('the table covers K in [%g, %g]; the manifest calibrates to %r' % (float(table['Kmin']), float(table['Kmax']), K))
         if defects == 'auto':
-            from .defects import find_defects
             defects = find_defects(sessions[0]['bias'], cfa, pattern)[0]
         if cfa == 'xtrans':
             b = np.asarray(black, dtype=np.float64).reshape(-1)

@@ -29,47 +29,22 @@ import sys
 import numpy as np
 
 from . import _lib as L
-from .mosaic import CODE_COLOUR, XT_PERIOD, bayer_pattern, check_cfa, check_mosaics, device_u16, shape_of, workspace, xtrans_pattern
-from .denoise import DEFAULT_PATTERN, _as_u16
+from .mosaic import (XT_PERIOD, CfaLayout, SensorMap, as_u16, check_cfa, check_mosaics, device_u16, shape_of, tile_cells, workspace,
+                     xtrans_tables)              # xtrans_tables: the library lookup lives in mosaic and stays importable from here
 
 MAX_FRAMES = 4096                    # the stack sum stays exact in uint32
 INT32_MAX = 2 ** 31 - 1
 
 
 # ---- geometry (host) --------------------------------------------------------------------------------------------------------------------
-def xtrans_tables():
-    """The library's X-Trans tables (host call, no device work): {'R': window radius, 'colour' (6,6) R 0 / G 1 / B 2, 'count' (6,6)
-    same-colour taps of the (2R + 1)^2 window, 'mask' (6,6) uint64 (bit = raster index of the tap in the window)}."""
-    buf = (ctypes.c_int * 145)()
-    L.check(L.lib().eld_debug_xtrans_defect_tables(buf, 145), 'eld_debug_xtrans_defect_tables')
-    a = np.array(buf[1:], np.int64).reshape(6, 6, 4)
-    mask = (a[..., 2] & 0xffffffff).astype(np.uint64) | ((a[..., 3] & 0xffffffff).astype(np.uint64) << np.uint64(32))
-    return {'R': int(buf[0]), 'colour': a[..., 0].copy(), 'count': a[..., 1].copy(), 'mask': mask}
-
-
 def _class_pattern(cfa, raw_pattern):
-    """-> (raw_pattern as int64 (p,p), class table int64 (p,p)).  Bayer: the channel codes themselves; X-Trans: colours R 0, G 1, B 2, which
-    must be the cell the library packs (its tap lists are compiled for it).  raw_pattern None: RGGB / the library's cell."""
-    if check_cfa(cfa) == 'bayer':
-        pat = bayer_pattern(DEFAULT_PATTERN if raw_pattern is None else raw_pattern)
-        return pat, pat
-    cell = xtrans_tables()['colour']
-    if raw_pattern is None:
-        return cell.copy(), cell
-    pat = xtrans_pattern(raw_pattern)
-    if not np.array_equal(CODE_COLOUR[pat], cell):
-        raise ValueError('this X-Trans raw_pattern is not the 6x6 cell the library packs (row 0 = R B G B R G): crop the mosaic so that it '
-                         'starts on that phase; got %r' % (pat.tolist(),))
-    return pat, cell
+    """-> (raw_pattern as int64 (p,p), class table int64 (p,p): Bayer channel codes, X-Trans colours) by CfaLayout.for_map."""
+    lay = CfaLayout.for_map(cfa, raw_pattern)
+    return lay.codes, lay.group_table
 
 
 def _radius(cfa):
     return 2 if cfa == 'bayer' else xtrans_tables()['R']
-
-
-def _class_map(cls, Hm, Wm):
-    p = cls.shape[0]
-    return cls[np.arange(Hm)[:, None] % p, np.arange(Wm)[None, :] % p]
 
 
 def _check_shape(shape, cfa):
@@ -108,7 +83,7 @@ def stranded_sites(mask, cls, R):
     ys, xs = np.nonzero(mask)
     if ys.size == 0:
         return np.zeros((0, 2), np.int32)
-    cm = _class_map(cls, Hm, Wm)
+    cm = tile_cells(cls, Hm, Wm)
     ok = np.zeros(ys.size, bool)
     for dy in range(-R, R + 1):
         for dx in range(-R, R + 1):
@@ -122,7 +97,7 @@ def stranded_sites(mask, cls, R):
 
 
 # ---- the map -------------------------------------------------------------------------------------------------------------------------------
-class DefectMap:
+class DefectMap(SensorMap):
     """The defective sites of one sensor.
 
     shape        (Hm, Wm) of the mosaics it applies to
@@ -132,6 +107,7 @@ class DefectMap:
     count        K
     words        host uint32 (Hm, ceil(Wm/32)): the bitmap
     bitmap       the same on the device (uploaded on first use; None without a GPU)"""
+    NOUN = 'defect map'
 
     def __init__(self, shape, cfa, raw_pattern, mask):
         self.cfa = check_cfa(cfa)
@@ -173,10 +149,6 @@ class DefectMap:
         return unpack_bitmap(self.words, self.shape[1])
 
     @property
-    def period(self):
-        return 2 if self.cfa == 'bayer' else XT_PERIOD
-
-    @property
     def classes(self):
         """(p,p) int64 class table: Bayer channel codes, X-Trans colours."""
         return self._cls
@@ -198,13 +170,6 @@ class DefectMap:
         if device not in self._dev:
             self._dev[device] = torch.from_numpy(self.words.view(np.int32).copy()).to(device)
         return self._dev[device]
-
-    def check_frames(self, shape, cfa, what='frames'):
-        """ValueError unless mosaics of `shape` ((..., Hm, Wm)) and `cfa` are what this map was made for."""
-        if cfa != self.cfa:
-            raise ValueError('%s: the defect map is for cfa=%r, the frames are %r' % (what, self.cfa, cfa))
-        if tuple(int(v) for v in shape[-2:]) != self.shape:
-            raise ValueError('%s: the defect map is for %d x %d mosaics, got %d x %d' % ((what,) + self.shape + tuple(int(v) for v in shape[-2:])))
 
     def save(self, path):
         """Write an .npz (no pickle): shape, cfa, raw_pattern, sites.  Returns the path written: '.npz' is appended when it is missing
@@ -233,7 +198,7 @@ def check_defects(defects, cfa, shape=None, raw_pattern=None):
         return defects
     if not isinstance(defects, DefectMap):
         raise ValueError("defects must be a DefectMap, 'auto' or None, got %r" % (type(defects).__name__,))
-    if cfa == 'xtrans' and defects.cfa == 'xtrans' and raw_pattern is not None and not np.array_equal(CODE_COLOUR[xtrans_pattern(raw_pattern)], defects.classes):
+    if cfa == 'xtrans' and defects.cfa == 'xtrans' and raw_pattern is not None and not np.array_equal(CfaLayout('xtrans', raw_pattern).colour, defects.classes):
         raise ValueError('calibration: the defect map was built for another X-Trans raw_pattern (the colours of its 6x6 cell differ)')
     if shape is not None:
         defects.check_frames(shape, cfa, 'calibration')
@@ -354,7 +319,7 @@ def repair(mosaics, dmap, out=None):
     place, with the same bits.  A shape or CFA mismatch with the map raises ValueError before any device work."""
     if not isinstance(dmap, DefectMap):
         raise ValueError('dmap must be a DefectMap, got %r' % (type(dmap).__name__,))
-    kind, batched = _as_u16(mosaics)
+    kind, batched = as_u16(mosaics)
     shape = tuple(int(v) for v in mosaics.shape)
     dmap.check_frames(shape, dmap.cfa, 'repair')
     if batched and shape[0] < 1:

@@ -27,20 +27,21 @@ The sRGB output is the reference's `process`: at packed resolution by default, a
 import argparse
 import ctypes
 import json
-import math
 import os
 import sys
 
 import numpy as np
 
 from . import _lib as L
+from .defects import as_defect_map, repair_device
+from .flatfield import LENS_MODES, as_flat_field
+from .isp import process, process_xtrans, render_bayer, render_xtrans
+from .mosaic import (DEFAULT_BLACK, DEFAULT_PATTERN, PLANES, as_u16 as _as_u16, check_cfa as _check_cfa,  # noqa: F401 (the names this module always had)
+                     check_sides as _check_sides, levels as _levels)
+from .shading import as_dark_shading
 
-PLANES = {'bayer': 4, 'xtrans': 9}
 ROUNDING = ('nearest', 'reference')
 SRGB_SIZES = ('packed', 'full')
-LENS_MODES = ('off', 'srgb', 'all')                  # where the lens plane of a flat-field map applies (eld_amd.flatfield)
-DEFAULT_BLACK = {'bayer': 512, 'xtrans': 1024}      # SID Sony (rawpy black_level_per_channel) / the reference's X-Trans constant
-DEFAULT_PATTERN = ((0, 1), (3, 2))                   # RGGB as rawpy codes (R 0, G1 1, B 2, G2 3)
 
 
 # ---- the denoiser ---------------------------------------------------------------------------------------------------------------
@@ -56,11 +57,6 @@ class Denoiser:
     @property
     def out_channels(self):
         return self.net.out_channels
-
-
-def _check_cfa(cfa):
-    if cfa not in PLANES:
-        raise ValueError("cfa must be 'bayer' or 'xtrans', got %r" % (cfa,))
 
 
 def load_denoiser(ckpt_or_model, cfa='bayer', precision='fp32', device=None):
@@ -94,69 +90,7 @@ def load_denoiser(ckpt_or_model, cfa='bayer', precision='fp32', device=None):
     return Denoiser(net, cfa, precision)
 
 
-# ---- argument checks (all before any device work) ---------------------------------------------------------------------------------
-def _as_u16(mosaic):
-    """-> (kind, array-or-tensor, batched).  kind: 'numpy' or 'torch'.  Refuses anything that is not uint16 codes."""
-    if isinstance(mosaic, np.ndarray):
-        if mosaic.dtype != np.uint16:
-            raise ValueError('mosaic must be a uint16 array, got %s' % mosaic.dtype)
-        kind = 'numpy'
-    else:
-        try:
-            import torch
-        except ImportError:                                     # pragma: no cover
-            torch = None
-        if torch is None or not isinstance(mosaic, torch.Tensor):
-            raise ValueError('mosaic must be a NumPy uint16 array or a CUDA uint16 / int16 tensor, got %r' % (type(mosaic).__name__,))
-        if mosaic.dtype not in (torch.uint16, torch.int16):
-            raise ValueError('mosaic must hold uint16 codes (torch.uint16, or its int16 view), got %s' % mosaic.dtype)
-        if not mosaic.is_cuda:
-            raise ValueError('a mosaic tensor must be on a CUDA device (NumPy arrays are uploaded)')
-        kind = 'torch'
-    if mosaic.ndim not in (2, 3):
-        raise ValueError('mosaic must be (Hm, Wm) or (N, Hm, Wm), got shape %s' % (tuple(mosaic.shape),))
-    return kind, mosaic.ndim == 3
-
-
-def _check_sides(Hm, Wm, cfa):
-    if Hm % 2 or Wm % 2:
-        raise ValueError('mosaic sides must be even, got %d x %d' % (Hm, Wm))
-    if cfa == 'xtrans' and (Hm < 6 or Wm < 6):
-        raise ValueError('an X-Trans mosaic needs sides of at least 6 (one 6x6 cell), got %d x %d' % (Hm, Wm))
-    if Hm < 2 or Wm < 2:
-        raise ValueError('empty mosaic: %d x %d' % (Hm, Wm))
-
-
-def _levels(cfa, raw_pattern, black_level, white_point):
-    """-> (pattern as 4 ints or None, black levels: 4 float32 for Bayer / one for X-Trans, white)"""
-    white = float(white_point)
-    if not (0 < white <= 65535) or white != math.floor(white):
-        raise ValueError('white_point must be an integer in (0, 65535], got %r' % (white_point,))
-    if black_level is None:
-        black_level = DEFAULT_BLACK[cfa]
-    blk = np.asarray(black_level, dtype=np.float64).reshape(-1)
-    if cfa == 'bayer':
-        pat = np.asarray(DEFAULT_PATTERN if raw_pattern is None else raw_pattern).reshape(-1)
-        if pat.size != 4 or sorted(int(v) for v in pat) != [0, 1, 2, 3]:
-            raise ValueError('raw_pattern must be a 2x2 permutation of the codes 0..3, got %r' % (raw_pattern,))
-        pat = [int(v) for v in pat]
-        if blk.size == 1:
-            blk = np.repeat(blk, 4)
-        if blk.size != 4:
-            raise ValueError('Bayer black_level takes 1 or 4 values (black_level_per_channel), got %d' % blk.size)
-    else:
-        pat = None
-        if blk.size > 1:
-            if not np.all(blk == blk[0]):
-                raise ValueError('X-Trans takes one black level for all planes (as the reference), got %r' % (blk.tolist(),))
-            blk = blk[:1]
-    if np.any(blk < 0) or np.any(blk != np.floor(blk)):
-        raise ValueError('black levels must be non-negative integers, got %r' % (blk.tolist(),))
-    if np.any(white <= blk):
-        raise ValueError('white_point (%g) must exceed every black level %r' % (white, blk.tolist()))
-    return pat, [float(v) for v in blk], white
-
-
+# ---- argument checks (all before any device work; the mosaic's own are eld_amd.mosaic's) -----------------------------------------------
 def _ratios(ratio, N):
     r = np.asarray(ratio, dtype=np.float64).reshape(-1)
     if r.size == 1:
@@ -196,6 +130,9 @@ def _colour(cfa, wb, ccm, N):
     if not (np.all(np.isfinite(w)) and np.all(np.isfinite(m))):
         raise ValueError('wb and ccm must be finite')
     return np.ascontiguousarray(w, dtype=np.float32), np.ascontiguousarray(m, dtype=np.float32)
+
+
+colour_args = _colour                                 # the public name (eld_amd.evaluate renders with it)
 
 
 # ---- the device stages ------------------------------------------------------------------------------------------------------------
@@ -319,12 +256,10 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         raise ValueError('the network writes %d planes, the %s write-back needs %d' % (denoiser.out_channels, cfa, PLANES[cfa]))
     wbs, ccms = _colour(cfa, wb, ccm, N)
     if defects is not None:
-        from .defects import as_defect_map, repair_device
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'denoise_raw')
     tval = None
     if shading is not None:
-        from .shading import as_dark_shading
         shading = as_dark_shading(shading)
         if iso is None:
             raise ValueError('shading needs iso: the ISO the frames were shot at')
@@ -336,7 +271,6 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     if not isinstance(lens, str) or lens not in LENS_MODES:
         raise ValueError('lens must be one of %r, got %r' % (LENS_MODES, lens))
     if flatfield is not None:
-        from .flatfield import as_flat_field
         flatfield = as_flat_field(flatfield)
         flatfield.check_frames((Hm, Wm), cfa, 'denoise_raw')
         flatfield.check_pattern(None if cfa == 'xtrans' else np.asarray(pat).reshape(2, 2), 'denoise_raw')
@@ -377,7 +311,6 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         write_back(out, mosaic, cfa, pat, blk, white, rounding)
     srgb = lin = None
     if wbs is not None and srgb_size == 'full':
-        from .isp import render_bayer, render_xtrans
         wt, ct = torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev)
         if cfa == 'bayer':
             srgb = render_bayer(out, pat, wt, ct, CRF=CRF)
@@ -386,7 +319,6 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
             srgb = render_xtrans(out, wt, ct, CRF=CRF)
             lin = render_xtrans(out, wt, ct, linear=True) if linear else None
     elif wbs is not None:
-        from .isp import process, process_xtrans
         fn = process if cfa == 'bayer' else process_xtrans
         rgb = fn(out, torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev), CRF=CRF)
         srgb = torch.round(rgb * 255.0).to(torch.uint8)          # k/255 -> k exactly
@@ -523,7 +455,7 @@ def options_from(a):
     return a.inputs, a.out, a.ckpt, o
 
 
-def _save_png(path, hwc):
+def save_png(path, hwc):
     try:
         from PIL import Image
     except ImportError:
@@ -543,13 +475,10 @@ def run_frames(den, inputs, outdir, o):
     os.makedirs(outdir, exist_ok=True)
     kw = {k: o.get(k) for k in ('raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'chop', 'rounding', 'srgb_size')}
     if o.get('defects') is not None:
-        from .defects import as_defect_map
         kw['defects'] = as_defect_map(o['defects'], '--defects')
     if o.get('shading') is not None:
-        from .shading import as_dark_shading
         kw['shading'], kw['iso'] = as_dark_shading(o['shading'], '--shading'), o['iso']
     if o.get('flatfield') is not None:
-        from .flatfield import as_flat_field
         kw['flatfield'], kw['lens'] = as_flat_field(o['flatfield'], '--flatfield'), o.get('lens') or 'srgb'
     from .dng import COMPRESSION_CHOICES, is_dng, load_frame, write_dng
     dng_kw = {'compression': COMPRESSION_CHOICES[o.get('dng_compression') or 'none']}
@@ -573,7 +502,7 @@ def run_frames(den, inputs, outdir, o):
             hwc = hwc if raw.ndim == 3 else hwc[0]
             np.save(os.path.join(outdir, name + '_srgb.npy'), hwc)
             line += ', %s_srgb.npy' % name
-            if hwc.ndim == 3 and _save_png(os.path.join(outdir, name + '_srgb.png'), hwc):
+            if hwc.ndim == 3 and save_png(os.path.join(outdir, name + '_srgb.png'), hwc):
                 line += ', %s_srgb.png' % name
         print(line)
     return 0

@@ -19,7 +19,6 @@ Command line: python -m eld_amd.evaluate pairs.json --ckpt net.pt [--meta sensor
 [--shading F] [--json OUT] [--save DIR] [--baseline-K K (--baseline-sigma S | --baseline-camera TABLE) [--baseline-method bm3d]]
 """
 import argparse
-import ctypes
 import json
 import math
 import os
@@ -29,6 +28,7 @@ import numpy as np
 
 from . import _lib as L
 from . import mosaic as M
+from .defects import as_defect_map, pack_bitmap, repair_device
 
 NB = L.PAIRSTATS_BINS
 STATS = ('n', 'sum_s', 'sum_e', 'sum_e2')
@@ -51,61 +51,18 @@ def bin_lower_edges():
 
 
 # ---- the kernel's wrapper ---------------------------------------------------------------------------------------------------------------
-def _cells(cfa, raw_pattern, black_level):
-    """-> (period, group per cell, G, black per cell): the groups of validate.group_map_u16, the integer black level of every cell."""
-    from .denoise import DEFAULT_BLACK, DEFAULT_PATTERN, _check_cfa
-    from .validate import group_map_u16
-    _check_cfa(cfa)
-    if black_level is None:
-        black_level = DEFAULT_BLACK[cfa]
-    b = np.asarray(black_level, dtype=np.float64).reshape(-1)
-    if b.size not in (1, 4) or np.any(b != np.rint(b)) or np.any(b < 0) or np.any(b > 65535):
-        raise ValueError('black_level takes 1 or 4 integers in [0, 65535], got %r' % (black_level,))
-    if b.size == 1:
-        b = np.repeat(b, 4)
-    if cfa == 'xtrans':
-        if raw_pattern is None:
-            from .defects import xtrans_tables
-            raw_pattern = xtrans_tables()['colour']                # the cell the library packs (R 0, G 1, B 2 are valid colour codes)
-        p, group, G = group_map_u16('xtrans', raw_pattern)
-        codes = M.xtrans_pattern(raw_pattern).reshape(-1)
-    else:
-        raw_pattern = DEFAULT_PATTERN if raw_pattern is None else raw_pattern
-        p, group, G = group_map_u16('bayer', raw_pattern)
-        codes = M.bayer_pattern(raw_pattern).reshape(-1)
-    return p, group, G, [int(b[c]) for c in codes]
-
-
-def _white(white_point):
-    w = float(white_point)
-    if w != math.floor(w) or not (1 <= w <= 65536):
-        raise ValueError('white_point must be an integer in [1, 65536], got %r' % (white_point,))
-    return int(w)
-
-
-def _stack(x, what):
-    """uint16 ndarray or CUDA int16/uint16 tensor, (Hm,Wm) or (F,Hm,Wm) -> shape (F,Hm,Wm) as a tuple"""
-    from .denoise import _as_u16
-    try:
-        _, batched = _as_u16(x)
-    except ValueError as e:
-        raise ValueError('%s: %s' % (what, e))
-    s = tuple(int(v) for v in x.shape)
-    return s if batched else (1,) + s
-
-
-def _level_sums(est, ref, p, group, G, black, white, Hc, Wc, bitmap=None):
-    """eld_pair_level_stats_u16 on CUDA code tensors (F,Hm,Wm) -> int64 ndarray (F, G, NB, 4); bitmap: the device words of a defect map."""
+def _level_sums(est, ref, lay, white, Hc, Wc, bitmap=None):
+    """eld_pair_level_stats_u16 on CUDA code tensors (F,Hm,Wm) -> int64 ndarray (F, G, NB, 4); lay: the CfaLayout of the cut; bitmap: the
+    device words of a defect map."""
     import torch
     F, Hm, Wm = (int(v) for v in ref.shape)
     lib = L.lib()
     with torch.cuda.device(ref.device):
-        out = torch.empty((F, G, NB, 4), dtype=torch.int64, device=ref.device)
+        out = torch.empty((F, lay.G, NB, 4), dtype=torch.int64, device=ref.device)
         need = lib.eld_pair_level_stats_workspace_bytes(F, Hm, Wm)
-        ws = torch.empty(need, dtype=torch.uint8, device=ref.device) if need else None
-        L.check(lib.eld_pair_level_stats_u16(L.dptr(est), L.dptr(ref), F, Hm, Wm, Hc, Wc, p, (ctypes.c_int * (p * p))(*group), G,
-                                             (ctypes.c_int32 * (p * p))(*black), white, L.dptr(bitmap), L.dptr(out), L.dptr(ws), need, L.cur_stream()),
-                'eld_pair_level_stats_u16')
+        ws = M.workspace(need, ref.device)
+        L.check(lib.eld_pair_level_stats_u16(L.dptr(est), L.dptr(ref), F, Hm, Wm, Hc, Wc, lay.period, lay.c_group(), lay.G, lay.c_black(), white,
+                                             L.dptr(bitmap), L.dptr(out), L.dptr(ws), need, L.cur_stream()), 'eld_pair_level_stats_u16')
     return out.cpu().numpy()
 
 
@@ -115,24 +72,22 @@ def pair_level_stats(est_u16, ref_u16, cfa, raw_pattern, black_level, white_poin
     B, G2; X-Trans R, G, B) and signal bin (NB = 61, the last bin holds ref >= white_point) the sums STATS =
     (n, sum s, sum e, sum e^2) with s = ref - black and e = est - ref.  X-Trans counts the whole 6x6 cells only (the borders beyond them
     pass through the write-back untouched); defects: a DefectMap whose flagged sites are not counted."""
-    p, group, G, black = _cells(cfa, raw_pattern, black_level)
-    white = _white(white_point)
-    se, sr = _stack(est_u16, 'est_u16'), _stack(ref_u16, 'ref_u16')
+    lay = M.CfaLayout.for_codes(cfa, raw_pattern, black_level)
+    white = M.check_white(white_point)
+    se, sr = M.check_stack(est_u16, 'est_u16'), M.check_stack(ref_u16, 'ref_u16')
     if se != sr:
         raise ValueError('est_u16 has shape %s, ref_u16 %s' % (se, sr))
     F, Hm, Wm = sr
-    if Hm * Wm >= 1 << 31:
-        raise ValueError('a frame of %d x %d has 2^31 sites or more' % (Hm, Wm))
+    M.check_site_count(Hm, Wm)
     if defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'pair_level_stats')
-    Hc, Wc = (Hm // p * p, Wm // p * p) if cfa == 'xtrans' else (Hm, Wm)
+    Hc, Wc = lay.whole_cells(Hm, Wm)
     est = M.device_u16(est_u16).reshape(F, Hm, Wm)
     ref = M.device_u16(ref_u16).reshape(F, Hm, Wm)
     if ref.device != est.device:
         raise ValueError('est_u16 is on %s, ref_u16 on %s' % (est.device, ref.device))
-    return _level_sums(est, ref, p, group, G, black, white, Hc, Wc, None if defects is None else defects.bitmap_on(ref.device))
+    return _level_sums(est, ref, lay, white, Hc, Wc, None if defects is None else defects.bitmap_on(ref.device))
 
 
 # ---- curves (host, float64) -------------------------------------------------------------------------------------------------------------
@@ -201,7 +156,6 @@ def _crop_box(h, w, crop):
 
 def _check_pairs(pairs, cfa, crop, shading):
     """Everything the host can see -> [(kind, (Hm, Wm), ratio, iso)]"""
-    from .denoise import PLANES, _as_u16, _check_sides
     if not isinstance(pairs, (list, tuple)) or not pairs:
         raise ValueError('pairs must be a non-empty list of dicts')
     info = []
@@ -212,7 +166,7 @@ def _check_pairs(pairs, cfa, crop, shading):
         kinds = []
         for k in ('short', 'long'):
             try:
-                kind, batched = _as_u16(pr[k])
+                kind, batched = M.as_u16(pr[k])
             except ValueError as e:
                 raise ValueError('%s: %s: %s' % (what, k, e))
             if batched:
@@ -221,14 +175,14 @@ def _check_pairs(pairs, cfa, crop, shading):
         ss, sl = tuple(int(v) for v in pr['short'].shape), tuple(int(v) for v in pr['long'].shape)
         if ss != sl:
             raise ValueError('%s: short is %d x %d, long %d x %d' % ((what,) + ss + sl))
-        _check_sides(ss[0], ss[1], cfa)
+        M.check_sides(ss[0], ss[1], cfa)
         ratio = pair_ratio(pr, what)
         iso = pr.get('iso')
         if iso is not None and not (math.isfinite(float(iso)) and float(iso) > 0):
             raise ValueError('%s: iso must be finite and > 0, got %r' % (what, iso))
         if shading is not None and iso is None:
             raise ValueError('%s: shading needs iso: the ISO the short exposure was shot at' % what)
-        h, w = (ss[0] // 2, ss[1] // 2) if PLANES[cfa] == 4 else (2 * (ss[0] // 6), 2 * (ss[1] // 6))
+        h, w = (ss[0] // 2, ss[1] // 2) if M.PLANES[cfa] == 4 else (2 * (ss[0] // 6), 2 * (ss[1] // 6))
         if crop is not None and (crop > h or crop > w):
             raise ValueError('%s: crop %d exceeds the packed frame %d x %d' % (what, crop, h, w))
         info.append((kinds, ss, ratio, None if iso is None else float(iso)))
@@ -265,13 +219,10 @@ def _codes(packed, y0, x0, long3, cfa, pat, blk, white):
 
 def _rolled_pattern(cfa, raw_pattern, phase):
     """The CFA cell as seen from a cut that starts at mosaic site `phase`."""
-    from .denoise import DEFAULT_PATTERN
+    pat = np.asarray(M.default_pattern(cfa, raw_pattern))
     if cfa == 'xtrans':
-        if raw_pattern is None:
-            from .defects import xtrans_tables
-            raw_pattern = xtrans_tables()['colour']
-        return np.roll(np.asarray(raw_pattern), (-(phase[0] % 6), -(phase[1] % 6)), axis=(0, 1))
-    return np.asarray(DEFAULT_PATTERN if raw_pattern is None else raw_pattern).reshape(2, 2)      # a Bayer cut starts on an even site
+        return np.roll(pat, (-(phase[0] % 6), -(phase[1] % 6)), axis=(0, 1))
+    return pat.reshape(2, 2)                                       # a Bayer cut starts on an even site
 
 
 def _cut_bitmap(defects, phase, shape, dev):
@@ -281,7 +232,6 @@ def _cut_bitmap(defects, phase, shape, dev):
     if tuple(shape) == defects.shape:
         return defects.bitmap_on(dev)
     import torch
-    from .defects import pack_bitmap
     m = defects.mask[phase[0]:phase[0] + shape[0], phase[1]:phase[1] + shape[1]]
     return torch.from_numpy(pack_bitmap(m).view(np.int32).copy()).to(dev)
 
@@ -325,8 +275,8 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
     'pooled': {'output', 'input'} curves over all pairs (None without levels)}.  A row holds psnr, ssim (output against target), psnr_in,
     ssim_in (input against target), ratio, iso, name and with levels 'sums' {'output', 'input'} (int64 (G, NB, 4)), 'curves' (level_curves
     of them) and psnr_codes (the output's, per group).  Bad arguments raise ValueError before any device work."""
-    from .denoise import PLANES, _check_cfa, _levels, pack_input, run_network
-    _check_cfa(cfa)
+    from .denoise import pack_input, run_network
+    M.check_cfa(cfa)
     if getattr(denoiser, 'cfa', cfa) != cfa:
         raise ValueError('the denoiser was loaded for cfa=%r, called with %r' % (denoiser.cfa, cfa))
     if chop not in (None, True, False):
@@ -335,14 +285,13 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
         raise ValueError('crop must be None or a positive integer (packed pixels), got %r' % (crop,))
     if crop is not None and cfa == 'xtrans' and crop % 2:
         raise ValueError('an X-Trans crop must be even (two packed pixels span one 6x6 cell), got %d' % crop)
-    pat, blk, white = _levels(cfa, raw_pattern, black_level, white_point)
-    if denoiser.in_channels != PLANES[cfa] or denoiser.out_channels != PLANES[cfa]:
-        raise ValueError('the network maps %d to %d planes, a %s frame packs to %d' % (denoiser.in_channels, denoiser.out_channels, cfa, PLANES[cfa]))
+    pat, blk, white = M.levels(cfa, raw_pattern, black_level, white_point)
+    if denoiser.in_channels != M.PLANES[cfa] or denoiser.out_channels != M.PLANES[cfa]:
+        raise ValueError('the network maps %d to %d planes, a %s frame packs to %d' % (denoiser.in_channels, denoiser.out_channels, cfa, M.PLANES[cfa]))
     if shading is not None:
         from .shading import as_dark_shading
         shading = as_dark_shading(shading)
     if defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects)
     if flatfield is not None:
         from .flatfield import as_flat_field
@@ -382,7 +331,6 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
         for i, (pr, (_, shape, ratio, iso)) in enumerate(zip(pairs, info)):
             short, long_ = _to_device(pr['short'], dev), _to_device(pr['long'], dev)
             if defects is not None:
-                from .defects import repair_device
                 short, long_ = repair_device(short, defects), repair_device(long_, defects)
             if flatfield is not None:
                 x = pack_input(short, cfa, pat, blk, white, [ratio], shading, None if shading is None else shading.t(iso), flatfield)
@@ -415,9 +363,9 @@ def evaluate_pairs(denoiser, pairs, cfa, raw_pattern=None, black_level=None, whi
                 sums = {}
                 for k, t in sets:
                     est, ref, phase = _codes(t, y0, x0, long_, cfa, pat, blk, white)
-                    p, group, G, black = _cells(cfa, _rolled_pattern(cfa, raw_pattern, phase), blk)
+                    lay = M.CfaLayout.for_codes(cfa, _rolled_pattern(cfa, raw_pattern, phase), blk)
                     cut = tuple(int(v) for v in est.shape[1:])
-                    sums[k] = _level_sums(est, ref, p, group, G, black, int(white), cut[0], cut[1], _cut_bitmap(defects, phase, cut, dev))[0]
+                    sums[k] = _level_sums(est, ref, lay, int(white), cut[0], cut[1], _cut_bitmap(defects, phase, cut, dev))[0]
                     pooled[k] = pooled[k] + sums[k]
                 row['sums'] = sums
                 row['curves'] = {k: level_curves(v, span) for k, v in sums.items()}
@@ -593,16 +541,16 @@ def parse_args(argv):
 def _saver(outdir, cfa, wb, ccm):
     """on_pair callback: packed-resolution sRGB PNGs through the ISP (util/process.py `process`)."""
     import torch
-    from .denoise import _colour, _save_png
+    from .denoise import colour_args, save_png
     from .isp import process, process_xtrans
     os.makedirs(outdir, exist_ok=True)
-    wbs, ccms = _colour(cfa, wb, ccm, 1)
+    wbs, ccms = colour_args(cfa, wb, ccm, 1)
 
     def save(i, row, tensors):
         for k, t in tensors.items():
             rgb = (process if cfa == 'bayer' else process_xtrans)(t, torch.from_numpy(wbs).to(t.device), torch.from_numpy(ccms).to(t.device))
             hwc = torch.round(rgb * 255.0).to(torch.uint8)[0].permute(1, 2, 0).contiguous().cpu().numpy()
-            _save_png(os.path.join(outdir, '%s_%s.png' % (row['name'] or 'pair%03d' % i, k)), hwc)
+            save_png(os.path.join(outdir, '%s_%s.png' % (row['name'] or 'pair%03d' % i, k)), hwc)
     return save
 
 

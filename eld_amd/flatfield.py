@@ -35,12 +35,12 @@ import numpy as np
 from . import _lib as L
 from . import calibrate as CAL
 from . import mosaic as M
-from .denoise import LENS_MODES, _as_u16
-from .shading import _pattern_and_black
+from .defects import as_defect_map, find_defects
 
 MAX_FRAMES = 65536                   # the sum of a site over all flats stays exact in uint32
 MAX_RADIUS = 64
 PARTS = ('prnu', 'lens', 'both')
+LENS_MODES = ('off', 'srgb', 'all')                  # where the lens plane applies in denoise_raw (eld_amd.denoise)
 COLOURS = ('R', 'G', 'B')
 REPORT_KEYS = ('rho_var', 'noise_var', 'prnu_sigma', 'snr', 'falloff', 'sites')
 
@@ -53,10 +53,7 @@ def check_radius(radius):
 
 
 def check_white(white_level):
-    w = float(white_level)
-    if not (1 <= w <= 65535) or w != np.floor(w):
-        raise ValueError('white_level must be an integer in [1, 65535], got %r' % (white_level,))
-    return int(w)
+    return M.check_white(white_level, 65535, 'white_level')
 
 
 def check_part(part):
@@ -105,11 +102,7 @@ def colour_table(cfa, pat):
     return M.CODE_COLOUR[np.asarray(pat)].astype(np.int64)
 
 
-def cell_map(values, Hm, Wm):
-    """(p,p) table -> (Hm,Wm): the value of cell (y % p, x % p) at every site."""
-    v = np.asarray(values)
-    p = v.shape[0]
-    return v[np.arange(Hm)[:, None] % p, np.arange(Wm)[None, :] % p]
+cell_map = M.tile_cells                              # (p,p) table -> (Hm,Wm): the value of cell (y % p, x % p) at every site
 
 
 def black_cells(cfa, pat, black):
@@ -135,12 +128,13 @@ def make_report(rho, nvar, V, ok, cmap):
 
 
 # ---- the map ------------------------------------------------------------------------------------------------------------------------------
-class FlatField:
+class FlatField(M.FittedMap):
     """The flat-field map of one sensor and lens setting.
 
     lens, prnu   host float32 (Hm,Wm) gains (multiply the black-corrected signal); exactly 1.0 where nothing could be measured
     cfa, raw_pattern, shape, radius (cells), frames (flat frames of the fit), white_level, invalid (sites left at 1.0)
     report       {'R' | 'G' | 'B': {rho_var, noise_var, prnu_sigma, snr, falloff, sites}}"""
+    NOUN = 'flat-field map'
 
     def __init__(self, lens, prnu, cfa='bayer', raw_pattern=None, radius=0, frames=0, white_level=16383, invalid=0, report=None):
         self.cfa = M.check_cfa(cfa)
@@ -153,16 +147,12 @@ class FlatField:
             if not np.all(np.isfinite(g)) or np.any(g <= 0):
                 raise ValueError('the %s plane must be finite and > 0' % name)
         self.lens, self.prnu, self.shape = lens, prnu, tuple(int(v) for v in lens.shape)
-        self.raw_pattern = _pattern_and_black(self.cfa, raw_pattern, None)[0]
+        self.raw_pattern = M.CfaLayout.for_map(self.cfa, raw_pattern).codes
         self.radius, self.frames, self.white_level, self.invalid = check_radius(int(radius)), int(frames), check_white(white_level), int(invalid)
         self.report = {} if report is None else {c: {k: (int(v[k]) if k == 'sites' else float(v[k])) for k in REPORT_KEYS} for c, v in report.items()}
         self._both = None
         self._dev = {}
         self._packed = {}
-
-    @property
-    def period(self):
-        return 2 if self.cfa == 'bayer' else M.XT_PERIOD
 
     def plane(self, part):
         """The host gain plane of a part; 'both' is the float32 product of the two, formed once."""
@@ -212,22 +202,9 @@ class FlatField:
             self._packed[key] = out
         return self._packed[key]
 
-    def check_frames(self, shape, cfa, what='frames'):
-        """ValueError unless mosaics of `shape` ((..., Hm, Wm)) and `cfa` are what this map was made for."""
-        if cfa != self.cfa:
-            raise ValueError('%s: the flat-field map is for cfa=%r, the frames are %r' % (what, self.cfa, cfa))
-        if tuple(int(v) for v in shape[-2:]) != self.shape:
-            raise ValueError('%s: the flat-field map is for %d x %d mosaics, got %d x %d' % ((what,) + self.shape + tuple(int(v) for v in shape[-2:])))
-
-    def check_pattern(self, raw_pattern, what='frames'):
-        """ValueError when a Bayer raw_pattern is given that is not the map's (None: not compared)."""
-        if raw_pattern is not None and self.cfa == 'bayer' and not np.array_equal(M.bayer_pattern(raw_pattern), self.raw_pattern):
-            raise ValueError('%s: the flat-field map was fitted under raw_pattern %r, got %r'
-                             % (what, self.raw_pattern.tolist(), np.asarray(raw_pattern).tolist()))
-
     def apply_device(self, t3, part, black, defects=None, out=None):
         """CUDA int16/uint16 codes (N,Hm,Wm), contiguous -> corrected codes in `out` (default: a new tensor; `t3` itself: in place).
-        black: 4 black levels as _pattern_and_black returns them."""
+        black: 4 black levels, per packed channel (Bayer) / colour code (X-Trans)."""
         import torch
         N, Hm, Wm = (int(v) for v in t3.shape)
         if out is None:
@@ -248,14 +225,13 @@ class FlatField:
         tensor in -> tensor out (out=: a contiguous CUDA tensor of the same shape and type, or `mosaics` itself for an in-place run with the
         same bits).  black_level: 1 or 4 values as fit_flat_field takes them.  Bad arguments raise ValueError before any device work."""
         part = check_part(part)
-        kind, batched = _as_u16(mosaics)
+        kind, batched = M.as_u16(mosaics)
         shape = tuple(int(v) for v in mosaics.shape)
         self.check_frames(shape, self.cfa, 'apply')
         if batched and shape[0] < 1:
             raise ValueError('empty batch')
-        black = _pattern_and_black(self.cfa, self.raw_pattern, black_level)[1]
+        black = M.CfaLayout.for_map(self.cfa, self.raw_pattern, black_level).black
         if defects is not None:
-            from .defects import as_defect_map
             defects = as_defect_map(defects)
             defects.check_frames(shape, self.cfa, 'apply')
         if kind == 'numpy':
@@ -388,17 +364,15 @@ def fit_flat_field(sessions, cfa='bayer', raw_pattern=None, black_level=None, wh
     defects      a DefectMap or its path: flagged sites are bad likewise.
     Bad arguments raise ValueError before any device work; the fit itself needs a GPU."""
     cfa = M.check_cfa(cfa)
-    pat, black = _pattern_and_black(cfa, raw_pattern, black_level)
+    lay = M.CfaLayout.for_map(cfa, raw_pattern, black_level)
+    pat, centre, colours = lay.codes, lay.centres, lay.colour
     radius, white_level = check_radius(radius), check_white(white_level)
     frames = flat_frames(sessions, cfa)
     Hm, Wm = (int(v) for v in frames[0].shape)
     if defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'fit_flat_field')
     from .framepool import FramePool
-    from .structure import cell_centres
-    centre = cell_centres(cfa, pat, black)
     # the pool is the existing upload (one flat buffer, frames 16-byte aligned, an EldPoolFrame table); its levels are not used here
     pool = FramePool(frames, cfa=cfa, raw_pattern=pat if cfa == 'bayer' else None, white_point=65535, device=device)
     if pool.buffer is None:
@@ -406,7 +380,6 @@ def fit_flat_field(sessions, cfa='bayer', raw_pattern=None, black_level=None, wh
     p, F = centre.shape[0], len(frames)
     S, D, bad = flat_sums(pool, white_level, defects)
     Bsum, Bcnt = flat_box(S, bad, p, radius)
-    colours = colour_table(cfa, pat)
     lens, prnu, invalid, rho, nvar, V, ok = flat_maps(S, D, unpack_bad(bad, Wm), Bsum, Bcnt, F, centre, colours)
     report = make_report(rho, nvar, V, ok, cell_map(colours, Hm, Wm))
     out = FlatField(lens.cpu().numpy(), prnu.cpu().numpy(), cfa, pat, radius, F, white_level, invalid, report)
@@ -445,10 +418,8 @@ def main(argv=None):
     sessions, pattern, black, white, cfa = CAL.load_manifest(a.manifest, with_cfa=True)
     defects = a.defects if a.defects is not None else CAL.manifest_defects(a.manifest)
     if defects == 'auto':
-        from .defects import find_defects
         defects = find_defects(sessions[0]['bias'], cfa, pattern)[0]
     elif defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects, '--defects')
     ff = fit_flat_field(sessions, cfa, pattern, black, white_level=white, radius=a.radius, defects=defects)
     out = ff.save(a.out)

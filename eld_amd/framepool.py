@@ -19,7 +19,8 @@ import ctypes
 import numpy as np
 
 from . import _lib as L
-from .denoise import PLANES, _as_u16, _check_cfa, _check_sides, _levels
+from .defects import as_defect_map, repair_device
+from .mosaic import PLANES, as_u16, check_cfa, check_sides, levels
 
 MAX_LAUNCH = 65528          # patches per launch (a patch is a blockIdx.y slice, at most 65535; a multiple of 8 keeps every chunk's output 16-byte aligned)
 
@@ -65,25 +66,24 @@ class FramePool:
     Bad arguments raise ValueError before any device work; a missing libeld_amd raises LibraryMissing."""
 
     def __init__(self, mosaics, cfa='bayer', raw_pattern=None, black_level=None, white_point=16383, device=None, defects=None, flatfield=None):
-        _check_cfa(cfa)
+        check_cfa(cfa)
         if isinstance(mosaics, np.ndarray) or hasattr(mosaics, 'is_cuda'):
             mosaics = [mosaics]
         frames = []
         for m in mosaics:
-            _, batched = _as_u16(m)
+            _, batched = as_u16(m)
             frames.extend(list(m) if batched else [m])
         if not frames:
             raise ValueError('FramePool needs at least one mosaic')
         for m in frames:
-            _check_sides(int(m.shape[0]), int(m.shape[1]), cfa)
+            check_sides(int(m.shape[0]), int(m.shape[1]), cfa)
         if defects is not None:
-            from .defects import as_defect_map
             defects = as_defect_map(defects)
             for i, m in enumerate(frames):
                 defects.check_frames(m.shape, cfa, 'frame %d' % i)
         self.defects = defects
         self.cfa, self.C = cfa, PLANES[cfa]
-        self.raw_pattern, self.black_level, self.white_point = _levels(cfa, raw_pattern, black_level, white_point)
+        self.raw_pattern, self.black_level, self.white_point = levels(cfa, raw_pattern, black_level, white_point)
         if flatfield is not None:
             from .flatfield import as_flat_field
             flatfield = as_flat_field(flatfield)
@@ -118,7 +118,6 @@ class FramePool:
             src = torch.from_numpy(np.ascontiguousarray(m).view(np.int16)) if isinstance(m, np.ndarray) else m.contiguous().view(torch.int16)
             buf[int(f['offset']):int(f['offset']) + n].copy_(src.reshape(-1))
         if self.defects is not None and self.defects.count:
-            from .defects import repair_device
             for f in self.frames:                             # in place, frame by frame (the frames start 16-byte aligned, not back to back)
                 v = buf[int(f['offset']):int(f['offset']) + int(f['Hm']) * int(f['Wm'])].view(1, int(f['Hm']), int(f['Wm']))
                 repair_device(v, self.defects, v)

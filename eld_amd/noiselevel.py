@@ -19,7 +19,6 @@ frame must span a range of signal levels; sigma0^2 includes the quantisation ste
 Command line: python -m eld_amd.noiselevel frame.npy [more.npy] --meta sensor.json [--defects F] [--stride S] [--camera TABLE] [--json]
 """
 import argparse
-import ctypes
 import json
 import math
 import sys
@@ -28,6 +27,7 @@ import numpy as np
 
 from . import _lib as L
 from . import mosaic as M
+from .defects import as_defect_map
 
 NB = L.PAIRSTATS_BINS
 TILE = 16                       # csrc/noiselevel.hip NL_TS: a tile is TILE * stride sites on a side
@@ -107,10 +107,9 @@ class NoiseEstimate:
 
 # ---- the kernel's wrapper ---------------------------------------------------------------------------------------------------------------
 def _layout(cfa, raw_pattern, black_level, stride, green_only):
-    """-> (period, group per cell, G, black per cell, stride): evaluate._cells, then the defaults of the single-frame statistic."""
-    from .evaluate import _cells
-    p, group, G, black = _cells(cfa, raw_pattern, black_level)
-    xt = cfa == 'xtrans'
+    """-> (CfaLayout.for_codes, the groups that count, stride): the layout, then the defaults of the single-frame statistic."""
+    lay = M.CfaLayout.for_codes(cfa, raw_pattern, black_level)
+    p, group, xt = lay.period, lay.group, cfa == 'xtrans'
     if stride is None:
         stride = 3 if xt else 2
     if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not (1 <= stride <= p) or p % stride:
@@ -121,7 +120,7 @@ def _layout(cfa, raw_pattern, black_level, stride, green_only):
         if not xt:
             raise ValueError('green_only is the X-Trans layout (its greens have period 3); a Bayer frame counts all four positions')
         group = [g if g == 1 else -1 for g in group]
-    return p, list(group), G, list(black), int(stride)
+    return lay, list(group), int(stride)
 
 
 def tile_sums(frames, cfa='bayer', raw_pattern=None, black_level=None, white_level=16383, defects=None, stride=None, green_only=None):
@@ -130,19 +129,16 @@ def tile_sums(frames, cfa='bayer', raw_pattern=None, black_level=None, white_lev
     path) whose sites make every neighbourhood they lie in ineligible.  stride: the distance to the same-colour neighbours (default 2 for
     Bayer, 3 for X-Trans); green_only (X-Trans, default True): count the greens only, whose period is 3.  X-Trans looks at the whole 6 x 6
     cells.  Bad arguments raise ValueError before any device work."""
-    from .evaluate import _stack, _white
-    p, group, G, black, stride = _layout(cfa, raw_pattern, black_level, stride, green_only)
-    white = _white(white_level)
-    F, Hm, Wm = _stack(frames, 'frames')
-    if Hm * Wm >= 1 << 31:
-        raise ValueError('a frame of %d x %d has 2^31 sites or more' % (Hm, Wm))
+    lay, group, stride = _layout(cfa, raw_pattern, black_level, stride, green_only)
+    p, G = lay.period, lay.G
+    white = M.check_white(white_level)
+    F, Hm, Wm = M.check_stack(frames, 'frames', limit=True)
     if F > 65535:
         raise ValueError('at most 65535 frames per call, got %d' % F)
     if defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'tile_sums')
-    Hc, Wc = (Hm // p * p, Wm // p * p) if cfa == 'xtrans' else (Hm, Wm)
+    Hc, Wc = lay.whole_cells(Hm, Wm)
     import torch
     u = M.device_u16(frames).reshape(F, Hm, Wm)
     nty, ntx = tiles_along(Hc, stride), tiles_along(Wc, stride)
@@ -150,11 +146,10 @@ def tile_sums(frames, cfa='bayer', raw_pattern=None, black_level=None, white_lev
     with torch.cuda.device(u.device):
         out = torch.zeros((F, nty, ntx, G, 4), dtype=torch.int64, device=u.device)
         need = lib.eld_tile_noise_workspace_bytes(F, Hm, Wm)
-        ws = torch.empty(need, dtype=torch.uint8, device=u.device) if need else None
+        ws = M.workspace(need, u.device)
         bm = None if defects is None else defects.bitmap_on(u.device)
-        L.check(lib.eld_tile_noise_sums_u16(L.dptr(u), F, Hm, Wm, Hc, Wc, p, stride, (ctypes.c_int * (p * p))(*group), G,
-                                            (ctypes.c_int32 * (p * p))(*black), white, L.dptr(bm), L.dptr(out), L.dptr(ws), need, L.cur_stream()),
-                'eld_tile_noise_sums_u16')
+        L.check(lib.eld_tile_noise_sums_u16(L.dptr(u), F, Hm, Wm, Hc, Wc, p, stride, lay.c_group(group), G, lay.c_black(), white, L.dptr(bm),
+                                            L.dptr(out), L.dptr(ws), need, L.cur_stream()), 'eld_tile_noise_sums_u16')
     return TileSums(out.cpu().numpy(), p, stride, group, G, (Hc, Wc))
 
 
@@ -272,8 +267,8 @@ def estimate_from_options(frames, o, stride=None, green_only=None):
 
 def table_check(camera, K):
     """The 'does this table fit this capture' numbers: the table's K range and the read noise of its g_scale line at log K."""
-    from .classical import _camera_table, sigma_from_table
-    t = _camera_table(camera)
+    from .classical import camera_table, sigma_from_table
+    t = camera_table(camera)
     out = {'sigma_table': sigma_from_table(t, K), 'K_min': None, 'K_max': None, 'K_inside': None}
     try:
         out['K_min'], out['K_max'] = float(t['Kmin']), float(t['Kmax'])

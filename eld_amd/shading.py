@@ -33,7 +33,7 @@ import numpy as np
 from . import _lib as L
 from . import calibrate as CAL
 from . import mosaic as M
-from .denoise import DEFAULT_BLACK, DEFAULT_PATTERN, _as_u16
+from .defects import as_defect_map, find_defects
 
 MAX_SESSIONS = 16
 MAX_FRAMES = 65536                   # per session: the sum of a site over a session stays exact in uint32
@@ -69,23 +69,6 @@ def fit_coefficients(isos, weights):
 
 
 # ---- argument checks (host only) ----------------------------------------------------------------------------------------------------------
-def _pattern_and_black(cfa, raw_pattern, black_level):
-    """-> (raw_pattern as structure.cell_centres takes it, 4 black levels: per packed channel (Bayer) / colour code (X-Trans))."""
-    cfa = M.check_cfa(cfa)
-    if cfa == 'bayer':
-        pat = M.bayer_pattern(DEFAULT_PATTERN if raw_pattern is None else raw_pattern)
-    else:
-        from .defects import _class_pattern
-        pat = _class_pattern(cfa, raw_pattern)[0]
-        M.xtrans_pattern(pat)
-    b = np.asarray(DEFAULT_BLACK[cfa] if black_level is None else black_level, dtype=np.float64).reshape(-1)
-    if b.size == 1:
-        b = np.repeat(b, 4)
-    if b.size != 4 or not np.all(np.isfinite(b)) or np.any(b < 0) or np.any(b > 65535):
-        raise ValueError('black_level takes 1 or 4 values in [0, 65535], got %r' % (black_level,))
-    return pat, b
-
-
 def _sessions(sessions):
     """-> (frames: list of (Hm,Wm) arrays / tensors, ranges [(first, count)], isos [float])."""
     if not isinstance(sessions, (list, tuple)) or len(sessions) == 0:
@@ -103,7 +86,7 @@ def _sessions(sessions):
         items = [b] if (isinstance(b, np.ndarray) or hasattr(b, 'is_cuda')) else list(b)
         mine = []
         for m in items:
-            _, batched = _as_u16(m)
+            _, batched = M.as_u16(m)
             mine.extend(list(m) if batched else [m])
         if not 1 <= len(mine) <= MAX_FRAMES:
             raise ValueError('session %d: 1 to %d bias frames, got %d' % (i, MAX_FRAMES, len(mine)))
@@ -151,7 +134,7 @@ def centre_planes(a, b, period, flagged=None):
 
 
 # ---- the map ------------------------------------------------------------------------------------------------------------------------------
-class DarkShading:
+class DarkShading(M.FittedMap):
     """The dark-shading map of one sensor.
 
     a, b         host float32 (Hm,Wm): offset(iso) = a + b * (iso - x0), in DN above the nominal black level
@@ -159,6 +142,7 @@ class DarkShading:
     iso_min, iso_max   the ISO range of the fit's sessions: t() refuses an ISO outside it unless extrapolate=True
     cfa, raw_pattern, shape, centred
     counts, isos       per session: bias frames and ISO"""
+    NOUN = 'dark-shading map'
 
     def __init__(self, a, b, x0, iso_min, iso_max, cfa='bayer', raw_pattern=None, centred=False, counts=(), isos=()):
         self.cfa = M.check_cfa(cfa)
@@ -173,15 +157,11 @@ class DarkShading:
         self.x0, self.iso_min, self.iso_max = float(x0), float(iso_min), float(iso_max)
         if not (np.isfinite(self.x0) and self.iso_min <= self.iso_max):
             raise ValueError('x0 must be finite and iso_min <= iso_max, got %r, %r, %r' % (x0, iso_min, iso_max))
-        self.raw_pattern = _pattern_and_black(self.cfa, raw_pattern, None)[0]
+        self.raw_pattern = M.CfaLayout.for_map(self.cfa, raw_pattern).codes
         self.centred = bool(centred)
         self.counts = [int(v) for v in counts]
         self.isos = [float(v) for v in isos]
         self._dev = {}
-
-    @property
-    def period(self):
-        return 2 if self.cfa == 'bayer' else M.XT_PERIOD
 
     def t(self, iso, extrapolate=False):
         """float32(iso - x0): the abscissa the kernels take.  ValueError for an ISO outside [iso_min, iso_max] unless extrapolate=True
@@ -203,19 +183,6 @@ class DarkShading:
             self._dev[device] = (torch.from_numpy(self.a).to(device), torch.from_numpy(self.b).to(device))
         return self._dev[device]
 
-    def check_frames(self, shape, cfa, what='frames'):
-        """ValueError unless mosaics of `shape` ((..., Hm, Wm)) and `cfa` are what this map was made for."""
-        if cfa != self.cfa:
-            raise ValueError('%s: the dark-shading map is for cfa=%r, the frames are %r' % (what, self.cfa, cfa))
-        if tuple(int(v) for v in shape[-2:]) != self.shape:
-            raise ValueError('%s: the dark-shading map is for %d x %d mosaics, got %d x %d' % ((what,) + self.shape + tuple(int(v) for v in shape[-2:])))
-
-    def check_pattern(self, raw_pattern, what='frames'):
-        """ValueError when a Bayer raw_pattern is given that is not the map's (None: not compared)."""
-        if raw_pattern is not None and self.cfa == 'bayer' and not np.array_equal(M.bayer_pattern(raw_pattern), self.raw_pattern):
-            raise ValueError('%s: the dark-shading map was fitted under raw_pattern %r, got %r'
-                             % (what, self.raw_pattern.tolist(), np.asarray(raw_pattern).tolist()))
-
     def apply_device(self, t3, tval, defects=None, out=None):
         """CUDA int16/uint16 codes (N,Hm,Wm), contiguous -> corrected codes in `out` (default: a new tensor; `t3` itself: in place)."""
         import torch
@@ -234,14 +201,13 @@ class DarkShading:
         -> NumPy out; CUDA uint16 / int16-view tensor in -> tensor out (out=: a contiguous CUDA tensor of the same shape and type, or
         `mosaics` itself for an in-place run with the same bits).  defects: a DefectMap whose flagged sites pass through unchanged (they
         are repaired elsewhere).  Bad arguments raise ValueError before any device work."""
-        kind, batched = _as_u16(mosaics)
+        kind, batched = M.as_u16(mosaics)
         shape = tuple(int(v) for v in mosaics.shape)
         self.check_frames(shape, self.cfa, 'apply')
         if batched and shape[0] < 1:
             raise ValueError('empty batch')
         tval = self.t(iso, extrapolate)
         if defects is not None:
-            from .defects import as_defect_map
             defects = as_defect_map(defects)
             defects.check_frames(shape, self.cfa, 'apply')
         if kind == 'numpy':
@@ -321,17 +287,15 @@ def fit_dark_shading(sessions, cfa='bayer', raw_pattern=None, black_level=None, 
     centred      take the mean over the unflagged sites of every cell of the CFA pattern out of both planes (see the module text).
     Bad arguments raise ValueError before any device work; the fit itself needs a GPU."""
     cfa = M.check_cfa(cfa)
-    pat, black = _pattern_and_black(cfa, raw_pattern, black_level)
+    lay = M.CfaLayout.for_map(cfa, raw_pattern, black_level)
+    pat, centre = lay.codes, lay.centres
     frames, ranges, isos = _sessions(sessions)
     w = _weights(weights, ranges)
     Hm, Wm = (int(v) for v in frames[0].shape)
     if defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects)
         defects.check_frames((Hm, Wm), cfa, 'fit_dark_shading')
     from .framepool import FramePool
-    from .structure import cell_centres
-    centre = cell_centres(cfa, pat, black)
     x0, alpha, beta = fit_coefficients(isos, w)
     # the pool is the existing upload (one flat buffer, frames 16-byte aligned, an EldPoolFrame table); its levels are not used here
     pool = FramePool(frames, cfa=cfa, raw_pattern=pat if cfa == 'bayer' else None, white_point=65535, device=device)
@@ -350,13 +314,12 @@ def fit_dark_shading(sessions, cfa='bayer', raw_pattern=None, black_level=None, 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------------------
 def group_rms(shading, iso, defects=None):
-    """r.m.s. of the map at `iso` per colour group (validate.group_map_u16), over the unflagged sites, float64."""
-    from .validate import group_map_u16
-    p, groups, G = group_map_u16(shading.cfa, shading.raw_pattern)
-    groups = np.asarray(groups).reshape(p, p)
+    """r.m.s. of the map at `iso` per colour group (CfaLayout.group), over the unflagged sites, float64."""
+    lay = M.CfaLayout(shading.cfa, shading.raw_pattern)
+    G = lay.G
     ds = shading.a + shading.b * shading.t(iso, extrapolate=True)
     Hm, Wm = shading.shape
-    gm = groups[np.arange(Hm)[:, None] % p, np.arange(Wm)[None, :] % p]
+    gm = lay.tile(lay.group, Hm, Wm)
     good = np.ones((Hm, Wm), bool) if defects is None else ~defects.mask
     return [float(np.sqrt(np.mean(ds[(gm == g) & good].astype(np.float64) ** 2))) if np.any((gm == g) & good) else float('nan') for g in range(G)]
 
@@ -375,10 +338,8 @@ def main(argv=None):
     sessions, pattern, black, white, cfa = CAL.load_manifest(a.manifest, with_cfa=True)
     defects = a.defects if a.defects is not None else CAL.manifest_defects(a.manifest)
     if defects == 'auto':
-        from .defects import find_defects
         defects = find_defects(sessions[0]['bias'], cfa, pattern)[0]
     elif defects is not None:
-        from .defects import as_defect_map
         defects = as_defect_map(defects, '--defects')
     sh = fit_dark_shading(sessions, cfa, pattern, black, defects=defects, centred=a.centred)
     out = sh.save(a.out)

@@ -17,22 +17,10 @@ from . import mosaic as M
 from .defects import check_defects
 
 
-def _groups(cfa, raw_pattern):
-    """-> (period, (p,p) int array cell -> colour group, G): validate.group_map_u16."""
-    from .validate import group_map_u16
-    p, groups, G = group_map_u16(cfa, raw_pattern)
-    return p, np.asarray(groups, np.int64).reshape(p, p), G
-
-
 def cell_centres(cfa, raw_pattern, black_level):
     """The integer centre of every cell of the pattern, (p,p) int64: rint(black) of the cell's packed channel (Bayer) or colour code
-    (X-Trans), clipped to the code range."""
-    b = np.rint(M.black_levels(black_level)).astype(np.int64)
-    if M.check_cfa(cfa) == 'xtrans':
-        cells = b[M.xtrans_pattern(raw_pattern)]
-    else:
-        cells = b[M.bayer_pattern(raw_pattern)]
-    return np.clip(cells, 0, 65535)
+    (X-Trans), clipped to the code range (CfaLayout.centres; the black levels are checked first, as they always were)."""
+    return M.CfaLayout(cfa, raw_pattern, M.black_levels(black_level)).centres
 
 
 def _centre(centre, p):
@@ -60,9 +48,8 @@ def structure_sums(frames, cfa, raw_pattern, centre, defects=None, pairs=None):
         'row' (F,Hm,p,2) (n, sum d) per row and column phase     'col' (F,Wm,p,2) (n, sum d) per column and row phase
         'cell' (F,p*p,3) (n, sum d, sum d^2)                     'cross' (Q,p*p) sum d_a d_b (None without pairs)
     and 'pairs' (Q,2), 'period' p."""
-    from .validate import _check_frames
-    p, _, _ = _groups(cfa, raw_pattern)
-    F, Hm, Wm = _check_frames(frames, 'frames')
+    p = M.CfaLayout(cfa, raw_pattern).period
+    F, Hm, Wm = M.check_mosaics(frames, 3, 'frames', None)
     cen = (ctypes.c_int32 * (p * p))(*_centre(centre, p))
     q = _pairs(pairs, F)
     if defects is not None:
@@ -87,7 +74,7 @@ def structure_sums(frames, cfa, raw_pattern, centre, defects=None, pairs=None):
 
 
 # ---- the estimators (host, float64) ----------------------------------------------------------------------------------------------------
-def _lags(lags):
+def check_lags(lags):
     if isinstance(lags, bool) or not isinstance(lags, (int, np.integer)) or lags < 1 or lags > 4096:
         raise ValueError('lags must be an integer in [1, 4096], got %r' % (lags,))
     return int(lags)
@@ -212,8 +199,9 @@ def structure_stats(sums, cfa, raw_pattern, lags=8):
     row_fixed_var, col_fixed_var (the covariance of the two frames' line means, minus the share of the fixed pixel part, solved the same way) and the temporal
     remainders pix_temporal_var, row_temporal_var, col_temporal_var = mean of the two frames' totals - the fixed part.
     Entries with n == 0 (fully masked) are dropped from every moment; a moment without data is nan."""
-    lags = _lags(lags)
-    p, groups, G = _groups(cfa, raw_pattern)
+    lags = check_lags(lags)
+    lay = M.CfaLayout(cfa, raw_pattern)
+    p, groups, G = lay.period, lay.group_table, lay.G
     if int(sums['period']) != p:
         raise ValueError('the sums were taken with period %d, the pattern has period %d' % (int(sums['period']), p))
     row, col, cell = (np.asarray(sums[k]) for k in ('row', 'col', 'cell'))

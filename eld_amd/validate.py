@@ -26,7 +26,8 @@ import numpy as np
 from . import _lib as L
 from . import calibrate as CAL
 from . import mosaic as M
-from .defects import check_defects
+from . import structure as ST
+from .defects import as_defect_map, check_defects, find_defects
 from .noise import NoiseParams, model_flags, table_cfa
 
 MODEL_LETTERS = 'PpgGRUBDC'
@@ -63,9 +64,8 @@ def _models(models):
 def group_map_u16(cfa, raw_pattern):
     """-> (period, groups: p*p ints, G).  Bayer: cell (r, c) -> the packed channel raw_pattern[r][c] (R, G1, B, G2), G = 4;
     X-Trans: cell -> the colour (R 0, G 1, B 2) of its colour code, G = 3."""
-    if M.check_cfa(cfa) == 'xtrans':
-        return M.XT_PERIOD, [int(v) for v in M.CODE_COLOUR[M.xtrans_pattern(raw_pattern)].reshape(-1)], 3
-    return 2, [int(v) for v in M.bayer_pattern(raw_pattern).reshape(-1)], 4
+    lay = M.CfaLayout(cfa, raw_pattern)
+    return lay.period, list(lay.group), lay.G
 
 
 def group_map_f32(cfa):
@@ -124,33 +124,16 @@ def kl_divergence(p_counts, q_counts, alpha=1.0):
 
 
 # ---- histograms (device) ---------------------------------------------------------------------------------------------------------------
-def _check_frames(x, what):
-    s = M.shape_of(x)
-    if len(s) != 3:
-        raise ValueError('%s: expected (F, Hm, Wm), got shape %s' % (what, s))
-    if s[2] % 2:
-        raise ValueError('%s: the mosaic width must be even (rows are read as 32-bit words), got %d' % (what, s[2]))
-    if s[1] * s[2] >= 1 << 31:
-        raise ValueError('%s: a frame of %d x %d has 2^31 pixels or more' % (what, s[1], s[2]))
-    if isinstance(x, np.ndarray):
-        if x.dtype != np.uint16:
-            raise ValueError('%s: uint16 mosaics expected, got %s' % (what, x.dtype))
-    else:
-        import torch
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype in (torch.int16, torch.uint16)):
-            raise ValueError('%s: a tensor must be CUDA int16/uint16 codes' % what)
-    return s
-
-
 def histogram_u16(frames, cfa, raw_pattern, centre, radius, subtract=None, defects=None):
     """Exact histograms of sensor codes.  frames (F,Hm,Wm) uint16 [ndarray or CUDA int16/uint16 tensor] -> int64 ndarray (F, G, 2R+1):
     per colour group (group_map_u16) the counts of clamp(u - centre[g] + R, 0, 2R), or of clamp(u - v + R, 0, 2R) with subtract=v (same
     shape; centre is then ignored and may be None).  defects: a DefectMap whose flagged sites are not counted."""
     R = _radius(radius)
-    p, groups, G = group_map_u16(cfa, raw_pattern)
-    F, Hm, Wm = _check_frames(frames, 'frames')
+    lay = M.CfaLayout(cfa, raw_pattern)
+    p, G = lay.period, lay.G
+    F, Hm, Wm = M.check_mosaics(frames, 3, 'frames', None)
     if subtract is not None:
-        if _check_frames(subtract, 'subtract') != (F, Hm, Wm):
+        if M.check_mosaics(subtract, 3, 'subtract', None) != (F, Hm, Wm):
             raise ValueError('subtract has shape %s, the frames %s' % (M.shape_of(subtract), (F, Hm, Wm)))
         cen = None
     else:
@@ -167,7 +150,7 @@ def histogram_u16(frames, cfa, raw_pattern, centre, radius, subtract=None, defec
     v = None if subtract is None else M.device_u16(subtract)
     counts = torch.empty((F, G, 2 * R + 1), dtype=torch.int64, device=u.device)
     bm = None if defects is None else defects.bitmap_on(u.device)
-    L.check(L.lib().eld_hist_u16(L.dptr(u), L.dptr(v), F, Hm, Wm, p, (ctypes.c_int * (p * p))(*groups), G, cen, R, L.dptr(bm), L.dptr(counts),
+    L.check(L.lib().eld_hist_u16(L.dptr(u), L.dptr(v), F, Hm, Wm, p, lay.c_group(), G, cen, R, L.dptr(bm), L.dptr(counts),
                                  L.cur_stream()), 'eld_hist_u16')
     return counts.cpu().numpy()
 
@@ -393,8 +376,7 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     if not (alpha >= 0):
         raise ValueError('alpha must be >= 0, got %r' % (alpha,))
     if structure:
-        from . import structure as ST
-        lags = ST._lags(lags)
+        lags = ST.check_lags(lags)
     if table is not None and any('B' in m for m in models) and table_cfa(table) != cfa:
         raise ValueError('the table is for cfa=%r, the frames are %r: its colour bias does not apply (model with B)' % (table_cfa(table), cfa))
     M.xtrans_pattern(raw_pattern) if cfa == 'xtrans' else M.bayer_pattern(raw_pattern)
@@ -436,7 +418,6 @@ def validate_camera(sessions, raw_pattern, black_level, white_level, table=None,
     if defects == 'auto':
         defects = diag.get('defects')
         if defects is None:
-            from .defects import find_defects
             defects = find_defects(sessions[0]['bias'], cfa, raw_pattern)[0]
     C, _, G = group_map_f32(cfa)
     ncb = 3 if cfa == 'xtrans' else 4
@@ -633,9 +614,8 @@ def parser():
 
 
 def _lags_arg(s):
-    from .structure import _lags
     try:
-        return _lags(int(s))
+        return ST.check_lags(int(s))
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
 
@@ -659,7 +639,6 @@ def main(argv=None):
     sessions, pattern, black, white, cfa = CAL.load_manifest(a.manifest, with_cfa=True)
     defects = a.defects if a.defects is not None else CAL.manifest_defects(a.manifest)
     if defects is not None and defects != 'auto':
-        from .defects import as_defect_map
         defects = as_defect_map(defects, '--defects')
     table = None if a.camera is None else np.load(a.camera, allow_pickle=True).item()
     rep = validate_camera(sessions, pattern, black, white, table=table, models=a.models, source=a.source, cfa=cfa, defects=defects,
