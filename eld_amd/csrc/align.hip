@@ -283,13 +283,13 @@ __global__ __launch_bounds__(256) void disp_check_kernel(const int16_t* __restri
 template <int P, int CW>
 __global__ __launch_bounds__(BT) void stack_aligned_kernel(AlignedArgs a) {
     static_assert(CW == 1 || CW == 2, "one site or one 32-bit word");
-    __shared__ int32_t s_tab[P * 12];                            // row phase r, 12 columns: cell (r, k % P)
+    __shared__ int32_t s_tab[P * CELL_ROW];
     __shared__ unsigned long long s_lds[BS_COPIES * BS_STRIDE / 2];
     uint32_t* lds = reinterpret_cast<uint32_t*>(s_lds);
     const bool want_ptc = a.ptc != nullptr;
     if (want_ptc)
         for (int i = threadIdx.x; i < BS_COPIES * BS_STRIDE; i += BT) lds[i] = 0;
-    if (threadIdx.x < P * 12) s_tab[threadIdx.x] = a.tab[(threadIdx.x / 12) * P + (threadIdx.x % 12) % P];
+    fill_cell_rows<P>(s_tab, a.tab);
     __syncthreads();
     uint32_t* tab = lds + (threadIdx.x & (BS_COPIES - 1)) * BS_STRIDE;
     const int N = a.N, white = a.white;
@@ -372,9 +372,9 @@ __global__ __launch_bounds__(BT) void stack_aligned_kernel(AlignedArgs a) {
             }
         }
 
-        const int32_t* trow = s_tab + (P == 2 ? (y & 1u) : mod6(y)) * 12 + (P == 2 ? (x0 & 1u) : mod6(x0));   // x0 % P + CW - 1 <= 6
+        const int32_t* trow = cell_row<P>(s_tab, y, x0);
         uint32_t bad = 0;
-        if (a.bitmap) bad = a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31u);   // CW = 2: x0 is even, both bits lie in one word
+        if (a.bitmap) bad = a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31u);   // defect_bits, written out: the call changes the CW = 1 kernels
         uint32_t m[CW];
 #pragma unroll
         for (int j = 0; j < CW; ++j) {
@@ -485,9 +485,7 @@ extern "C" int eld_burst_stack_aligned_u16(const uint16_t* frames, int N, int Hm
     size_t lum = 0, dsp = 0;
     if (!al_geometry(N, Hm, Wm, p, 1, lv, &lum, &dsp) || G < 1 || G > 4) return ELD_EINVAL;
     if (TY0 != lv[0].ty || TX0 != lv[0].tx) return ELD_EINVAL;
-    if (!group || !black || white < 1 || white > 65536) return ELD_EINVAL;
-    for (int k = 0; k < p * p; ++k)
-        if (group[k] < -1 || group[k] >= G || black[k] < 0 || black[k] > 65535) return ELD_EINVAL;
+    if (!cell_groups_ok(p, group, G, black, white)) return ELD_EINVAL;
     if (k2q < 0 || k2q > 256 || min_dev < 0 || min_dev > 65535) return ELD_EINVAL;
     if (!ws || ((uintptr_t)ws & 3u)) return ELD_EINVAL;
     if (ws_bytes < eld_burst_stack_aligned_workspace_bytes(N, Hm, Wm)) return ELD_EWS;
@@ -504,15 +502,13 @@ extern "C" int eld_burst_stack_aligned_u16(const uint16_t* frames, int N, int Hm
     ELD_LAUNCH_CHECK();
     if (hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return ELD_EINVAL;
     if (bad) return ELD_EINVAL;
-    if (ptc) {
-        ELD_LAUNCH(burst_zero_kernel, dim3((G * PS_NB * 4 + 255) / 256), dim3(256), 0, s, (unsigned long long*)ptc, G * PS_NB * 4);
-        ELD_LAUNCH_CHECK();
-    }
+    if (ptc)
+        if (int rc = zero_u64(ptc, (size_t)G * PS_NB * 4, s)) return rc;
     AlignedArgs a;
     a.frames = frames; a.bitmap = bitmap; a.disp = disp; a.mean = mean; a.kept = kept; a.present = present; a.ptc = (unsigned long long*)ptc;
-    a.N = N; a.Hm = Hm; a.Wm = Wm; a.G = G; a.white = white; a.wpr = (Wm + 31) / 32; a.k2q = k2q; a.min_dev = min_dev; a.ty = TY0; a.tx = TX0;
+    a.N = N; a.Hm = Hm; a.Wm = Wm; a.G = G; a.white = white; a.wpr = bitmap_pitch(Wm); a.k2q = k2q; a.min_dev = min_dev; a.ty = TY0; a.tx = TX0;
     a.hw = (uint32_t)Hm * (uint32_t)Wm;
-    for (int k = 0; k < 36; ++k) a.tab[k] = k < p * p ? (black[k] | ((group[k] + 1) << 16)) : 0;
+    pack_cell_tab(a.tab, p, group, black);
     const uintptr_t fm = (uintptr_t)frames | (uintptr_t)mean;
     const int cw = (!(fm & 3u) && !(((uintptr_t)kept | (uintptr_t)present) & 1u) && Wm % 2 == 0) ? 2 : 1;
     a.upr = (uint32_t)(Wm / cw);

@@ -39,7 +39,7 @@
 // The ratio R: E < 2^58, so E << 12 needs 70 bits; floor(4096 E / (E + p)) = 4096 - ceil(4096 p / (E + p)) needs 44 over 59.
 // T R + 2048 < 2^43.  W <= 2^20, win <= 16, est < 2^19: one contribution < 2^43; the header's count of contributions gives num < 2^58, den < 2^39.
 // W >= 2^20 / 2^14 (step 1) and 2^44 / (2^24 2^14) (step 2): at least 64, and every site lies under a reference block, so den >= 64.
-#include "common.h"
+#include "mosaic_dev.h"
 
 namespace {
 
@@ -76,12 +76,6 @@ __host__ __device__ inline Bm3dLds bm3d_lds(int C, int S, int M, int Gmax, bool 
     l.grp = l.rb + (wiener ? L * 2 : 0);
     l.total = l.grp + 16 * sizeof(int) + BM_WAVES * sizeof(unsigned long long) + 64;      // the group, the partial sums, the window table
     return l;
-}
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 __device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {

@@ -58,30 +58,16 @@ struct BurstArgs {
     int32_t tab[36];                             // cell -> black | (group + 1) << 16
 };
 
-template <int CW>
-__device__ __forceinline__ void load_codes(const uint16_t* __restrict__ p, uint32_t (&w)[(CW + 1) / 2]) {
-    if constexpr (CW == 8) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    } else if constexpr (CW == 2) {
-        w[0] = *reinterpret_cast<const uint32_t*>(p);
-    } else {
-        w[0] = *p;
-    }
-}
-
-__device__ __forceinline__ uint32_t code_of(const uint32_t* w, int j) { return (w[j / 2] >> (16 * (j & 1))) & 0xFFFFu; }
-
 template <int P, int CW>
 __global__ __launch_bounds__(BT) void burst_stack_kernel(BurstArgs a) {
     constexpr int NW = (CW + 1) / 2;
-    __shared__ int32_t s_tab[P * 12];                            // row phase r, 12 columns: cell (r, k % P)
+    __shared__ int32_t s_tab[P * CELL_ROW];
     __shared__ unsigned long long s_lds[BS_COPIES * BS_STRIDE / 2];
     uint32_t* lds = reinterpret_cast<uint32_t*>(s_lds);
     const bool want_ptc = a.ptc != nullptr;
     if (want_ptc)
         for (int i = threadIdx.x; i < BS_COPIES * BS_STRIDE; i += BT) lds[i] = 0;
-    if (threadIdx.x < P * 12) s_tab[threadIdx.x] = a.tab[(threadIdx.x / 12) * P + (threadIdx.x % 12) % P];
+    fill_cell_rows<P>(s_tab, a.tab);
     __syncthreads();
     uint32_t* tab = lds + (threadIdx.x & (BS_COPIES - 1)) * BS_STRIDE;
     const int N = a.N, white = a.white;
@@ -166,9 +152,9 @@ __global__ __launch_bounds__(BT) void burst_stack_kernel(BurstArgs a) {
 
         const uint32_t y = fdiv_u32(u, a.dupr);
         const uint32_t x0 = (u - y * a.upr) * (uint32_t)CW;
-        const int32_t* trow = s_tab + (P == 2 ? (y & 1u) : mod6(y)) * 12 + (P == 2 ? (x0 & 1u) : mod6(x0));   // x0 % P + CW - 1 <= 11
+        const int32_t* trow = cell_row<P>(s_tab, y, x0);
         uint32_t bad = 0;
-        if (a.bitmap) bad = a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31u);   // x0 is a multiple of CW, CW divides 32: the bits lie in one word
+        if (a.bitmap) bad = a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31u);   // defect_bits, written out: the call changes the CW = 1 kernels
         uint32_t m[CW];
 #pragma unroll
         for (int j = 0; j < CW; ++j) {
@@ -224,10 +210,7 @@ extern "C" int eld_burst_stack_u16(const uint16_t* frames, int N, int Hm, int Wm
                                    const uint32_t* bitmap, int k2q, int min_dev, uint16_t* mean, uint8_t* kept, int64_t* ptc, void* ws,
                                    size_t ws_bytes, void* stream) {
     if ((p != 2 && p != 6) || Hm < 0 || Wm < 0 || G < 1 || G > 4) return ELD_EINVAL;
-    if (!group || !black || white < 1 || white > 65536) return ELD_EINVAL;
-    if ((uint64_t)Hm * (uint64_t)Wm >= (1ull << 31)) return ELD_EINVAL;
-    for (int k = 0; k < p * p; ++k)
-        if (group[k] < -1 || group[k] >= G || black[k] < 0 || black[k] > 65535) return ELD_EINVAL;
+    if ((uint64_t)Hm * (uint64_t)Wm >= (1ull << 31) || !cell_groups_ok(p, group, G, black, white)) return ELD_EINVAL;
     if (N < 2 || N > 256 || k2q < 0 || k2q > 256 || min_dev < 0 || min_dev > 65535) return ELD_EINVAL;
     (void)ws;
     if (ws_bytes < eld_burst_stack_workspace_bytes(N, Hm, Wm)) return ELD_EWS;
@@ -235,21 +218,19 @@ extern "C" int eld_burst_stack_u16(const uint16_t* frames, int N, int Hm, int Wm
     const bool empty = Hm == 0 || Wm == 0;
     if (!empty && (!frames || !mean || ((uintptr_t)frames & 1u) || ((uintptr_t)mean & 1u) || ((uintptr_t)bitmap & 3u))) return ELD_EINVAL;
     hipStream_t s = as_stream(stream);
-    if (ptc) {
-        ELD_LAUNCH(burst_zero_kernel, dim3((G * PS_NB * 4 + 255) / 256), dim3(256), 0, s, (unsigned long long*)ptc, G * PS_NB * 4);
-        ELD_LAUNCH_CHECK();
-    }
+    if (ptc)
+        if (int rc = zero_u64(ptc, (size_t)G * PS_NB * 4, s)) return rc;
     if (empty) return 0;
     BurstArgs a;
     a.frames = frames; a.bitmap = bitmap; a.mean = mean; a.kept = kept; a.ptc = (unsigned long long*)ptc;
-    a.N = N; a.Wm = Wm; a.G = G; a.white = white; a.wpr = (Wm + 31) / 32; a.k2q = k2q; a.min_dev = min_dev;
+    a.N = N; a.Wm = Wm; a.G = G; a.white = white; a.wpr = bitmap_pitch(Wm); a.k2q = k2q; a.min_dev = min_dev;
     a.hw = (uint32_t)Hm * (uint32_t)Wm;
     // the per-site test: the smallest shift at which neither ((d^2 >> shift) + 1) A nor (V >> shift) B can exceed 64 bits for this N
     const uint64_t pre_a = 4ull * N * (N - 2) + (uint64_t)k2q * (N - 1), pre_b = (uint64_t)k2q * (N - 1) * (N - 1);
     const uint64_t d2max = (uint64_t)(N - 1) * 65535u * ((uint64_t)(N - 1) * 65535u), vmax = (uint64_t)N * N * 65535u * 65535u / 4;
     a.pre_a = (uint32_t)pre_a; a.pre_b = (uint32_t)pre_b; a.shift = 0;
     while ((pre_a && (d2max >> a.shift) + 1 > UINT64_MAX / pre_a) || (pre_b && (vmax >> a.shift) > UINT64_MAX / pre_b)) ++a.shift;
-    for (int k = 0; k < 36; ++k) a.tab[k] = k < p * p ? (black[k] | ((group[k] + 1) << 16)) : 0;
+    pack_cell_tab(a.tab, p, group, black);
     const uintptr_t fm = (uintptr_t)frames | (uintptr_t)mean;
     const int cw = (!(fm & 15u) && !((uintptr_t)kept & 7u) && Wm % 8 == 0) ? 8 : (!(fm & 3u) && !((uintptr_t)kept & 1u) && Wm % 2 == 0) ? 2 : 1;
     a.upr = (uint32_t)(Wm / cw);

@@ -2,8 +2,8 @@
 // leave-one-out rule for one sample and the photon-transfer accumulation (per-lane runs -> copies of the table in LDS -> 64-bit integer
 // atomics into ptc[]).  Widths and the reasoning behind both are at the head of burst.hip; DESIGN.md sec. 20.
 #pragma once
-#include "common.h"
 #include "levelbins.h"
+#include "mosaic_dev.h"
 
 namespace {
 
@@ -19,10 +19,6 @@ static_assert(BS_COPIES * BS_STRIDE * 4 <= 65536, "static LDS");
 static_assert(256ll * 65535 < (1ll << 24) && 256ll * 65535 * 65535 < (1ll << 40), "S1, |d| < 2^24 and S2 < 2^40");
 static_assert(255ull * 255 * 65535 * 65535 / 4 < (1ull << 46) && 256ull * 256 * 65535 * 65535 / 4 < (1ull << 46), "V1, V < 2^46");
 static_assert(4ull * 254 * (255ull * 65535) * (255ull * 65535) < (1ull << 58), "4 (N - 2) d^2 < 2^58");
-
-__global__ __launch_bounds__(256) void burst_zero_kernel(unsigned long long* __restrict__ p, int n) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) p[i] = 0;
-}
 
 // The rule for one sample x of a site with sums s1, s2 over its n samples (n >= 4, k2q > 0: the caller decides whether the rule is on).
 struct BurstRule {

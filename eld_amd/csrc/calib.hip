@@ -10,7 +10,7 @@
 //   PPCC              sorted residuals -> per Tukey-lambda shape: sum t*M, sum M^2 (and sum t, sum t^2), float64, fixed order
 // Cell of mosaic pixel (y, x): (y % p, x % p); its Bayer channel is raw_pattern[y&1][x&1] (R, G1, B, G2 = 0..3), as eld_pack_raw_bayer_u16.
 // No atomics anywhere: every sum is reduced in an order fixed by the shape alone, so two launches give identical bits.
-#include "common.h"
+#include "mosaic_dev.h"
 
 namespace {
 
@@ -23,22 +23,13 @@ struct CellSlots {
     unsigned char s[36];
 };
 
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // Sum NV uint64 values over the block (256 threads); the block's totals land in tot[] (LDS, valid after the call).  Integer sums:
 // exact, order-independent.
 template <int NV>
 __device__ __forceinline__ void block_sum_u64(uint64_t (&v)[NV], uint64_t* red /* LDS [CB_WAVES][NV] */, uint64_t* tot /* LDS [NV] */) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = wave_sum_u64(v[k]);
+    for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
     if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < NV; ++k) red[wv * NV + k] = v[k];
@@ -125,10 +116,10 @@ __global__ __launch_bounds__(PP_THREADS) void ppcc_partial_kernel(const float* _
     // block reduction in a fixed order: wave butterflies, then waves 0..3 in order
 #pragma unroll
     for (int q = 0; q < PP_LG; ++q) {
-        const double s1 = wave_sum_f64(stm[q]), s2 = wave_sum_f64(smm[q]);
+        const double s1 = wave_sum(stm[q]), s2 = wave_sum(smm[q]);
         if (lane == 0) { red[wv][2 * q] = s1; red[wv][2 * q + 1] = 2.0 * s2; }
     }
-    const double a1 = wave_sum_f64(st), a2 = wave_sum_f64(stt);
+    const double a1 = wave_sum(st), a2 = wave_sum(stt);
     __syncthreads();
     if (threadIdx.x < 2 * PP_LG) {
         double s = 0.0;
@@ -162,8 +153,8 @@ __global__ __launch_bounds__(256) void ppcc_final_kernel(const float* __restrict
         s1 += p[0];
         s2 += p[1];
     }
-    s1 = wave_sum_f64(s1);
-    s2 = wave_sum_f64(s2);
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
     if (lane == 0) { red[wv][0] = s1; red[wv][1] = s2; }
     __syncthreads();
     if (threadIdx.x == 0) {

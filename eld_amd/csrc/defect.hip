@@ -14,7 +14,7 @@
 // unflagged neighbour keeps its code (the Python layer refuses such a map before it reaches the device).
 //
 // No atomics, no LDS, no scratch; every site is computed by one lane from the same operands in the same order whatever the launch shape.
-#include "common.h"
+#include "mosaic_dev.h"
 #include "xtrans.h"
 
 namespace {
@@ -262,9 +262,6 @@ __device__ __forceinline__ int class_of(const ClassTable& t, int y, int x) {
     const int k = (y % t.p) * t.p + x % t.p;
     return (int)((k < 32 ? t.lo >> (2 * k) : t.hi >> (2 * (k - 32))) & 3u);
 }
-__device__ __forceinline__ bool flagged(const uint32_t* __restrict__ bitmap, int pitch, int y, int x) {
-    return (bitmap[(size_t)y * pitch + (x >> 5)] >> (x & 31)) & 1u;
-}
 
 // the rare path: lower median of the unflagged same-class sites of the window, by rank counting over at most |N| candidates
 __device__ __noinline__ uint32_t repair_gather(const uint16_t* f, const uint32_t* __restrict__ bitmap, int pitch, int Hm, int Wm, ClassTable t,
@@ -275,7 +272,7 @@ __device__ __noinline__ uint32_t repair_gather(const uint16_t* f, const uint32_t
         for (int dx = -t.R; dx <= t.R; dx += t.step) {
             const int yy = y + dy, xx = x + dx;
             if ((!dy && !dx) || (unsigned)yy >= (unsigned)Hm || (unsigned)xx >= (unsigned)Wm) continue;
-            if (class_of(t, yy, xx) != cls || flagged(bitmap, pitch, yy, xx)) continue;
+            if (class_of(t, yy, xx) != cls || defect_bit(bitmap, pitch, yy, xx)) continue;
             cand |= 1ull << ((dy + t.R) * W + dx + t.R);
         }
     const uint32_t own = f[(size_t)y * Wm + x];
@@ -408,7 +405,7 @@ extern "C" int eld_defect_deviation(const uint16_t* stack, int F, int Hm, int Wm
 
 extern "C" int eld_defect_flags(const int32_t* D, int Hm, int Wm, int32_t T_hi, int32_t T_lo, uint32_t* bitmap, void* stream) {
     if (!D || !bitmap || !sides_ok(Hm, Wm, 2) || ((uintptr_t)D & 3) || ((uintptr_t)bitmap & 3)) return ELD_EINVAL;
-    const int pitch = (Wm + 31) / 32;
+    const int pitch = bitmap_pitch(Wm);
     ELD_LAUNCH(defect_flags_kernel, dim3((unsigned)min((Wm + 255) / 256, 64), rows_grid(Hm)), dim3(256), 0, as_stream(stream), D, Hm, Wm, T_hi, T_lo,
                pitch, bitmap);
     ELD_LAUNCH_CHECK();
@@ -425,7 +422,7 @@ extern "C" int eld_defect_repair_u16(const uint16_t* in, uint16_t* out, int N, i
         const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out, n = (uintptr_t)N * Hm * Wm * 2;
         if (a < b + n && b < a + n) return ELD_EINVAL;
     }
-    const int groups = (Wm + 7) / 8, pitch = (Wm + 31) / 32;
+    const int groups = (Wm + 7) / 8, pitch = bitmap_pitch(Wm);
     ELD_LAUNCH(defect_repair_kernel, dim3((unsigned)min((groups + 255) / 256, 64), rows_grid(N * Hm)), dim3(256), 0, as_stream(stream), in, out, N, Hm,
                Wm, t, bitmap, pitch);
     ELD_LAUNCH_CHECK();

@@ -6,7 +6,7 @@
 //   * illuminance_correct: models/ELD_model.py:138-169, out = <p,s>/<p,p> * p over the elements with s != 1, p clamped
 //     to [0,1], one scale per image.
 // Sums are accumulated in double and reduced in a fixed order (run-to-run bit-stable, no atomics).
-#include "common.h"
+#include "mosaic_dev.h"
 #include "xtrans.h"
 
 int debug_kernel_mask(int set);      // conv_bfs.hip (eld_debug_kernel_mask): set < 0 only queries
@@ -140,12 +140,6 @@ __global__ __launch_bounds__(256) void qa_final_kernel(const double* __restrict_
 constexpr int QA_RH = 106, QA_ROWS = QA_RH + HALO;                  // 112 input rows per item = 8 x 14
 static_assert(QA_ROWS % 14 == 0, "row loop unrolled by 14");
 
-__device__ __forceinline__ double wave_sum_fixed(double v) {        // butterfly over the 64 lanes: the same order on every run
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // EDGE = false: every column this wave reads exists (uniform row base + per-lane column + immediate k: no address arithmetic per load);
 // EDGE = true (the last strip of a row of strips): column indices clamped to W - 1
 template <int NC, bool EDGE>
@@ -225,7 +219,7 @@ __device__ __forceinline__ void qa_item(const float* __restrict__ px, const floa
             }
         }
     }
-    const double Sw = wave_sum_fixed(S_acc), Qw = wave_sum_fixed(sq);
+    const double Sw = wave_sum(S_acc), Qw = wave_sum(sq);
     if (lane == 0) { *ss_out = Sw; *sq_out = Qw; }
 }
 

@@ -20,15 +20,13 @@
 //            plane columns of one column phase, results go back through LDS for coalesced 8-byte stores into the workspace
 //   columns  a lane owns one mosaic column (coalesced across the wave) and slides down FF_VSEG plane rows of each of the p row phases
 // The cost per site is 2 + (2R + 1) / FF_SEG LDS reads and 2 + (2R + 1) / FF_VSEG global reads: linear in R with a small slope, not R^2.
-#include "common.h"
+#include "mosaic_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int FF_T = 256;                        // threads per workgroup
-constexpr int FF_NPX = 8;                        // columns per lane (sums, apply)
-constexpr int FF_U = 4;                          // frames in flight per lane: two pairs
 constexpr int FF_MAX_FRAMES = 65536;             // 65536 * 65535 < 2^32 keeps S exact in uint32
 constexpr int FF_MAX_RADIUS = 64;
 constexpr int FF_SEG = 9;                        // plane columns per lane of the row pass (odd: lanes of a wave spread over the LDS banks)
@@ -61,42 +59,22 @@ struct ApplyArgs {
     float black[36];
 };
 
-// the per-cell values a lane needs: row phase r, columns x0 % P + j (x0 % P is 0 when P == 2 and 0, 2 or 4 when P == 6, so 12 entries per row phase)
-template <int P>
-__device__ __forceinline__ void fill_cells(float* s_cell, const float* cell) {
-    if (threadIdx.x < P * 12) s_cell[threadIdx.x] = cell[(threadIdx.x / 12) * P + (threadIdx.x % 12) % P];
-}
-
-// 8 codes as 4 words.  VEC: one 16-byte load; otherwise one word per column pair that lies inside the row (the others read as 0)
-template <bool VEC>
-__device__ __forceinline__ void load_codes(const uint16_t* p, int x0, int Wm, uint32_t (&w)[4]) {
-    if (VEC) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = x0 + 2 * k < Wm ? *reinterpret_cast<const uint32_t*>(p + 2 * k) : 0u;
-    }
-}
-
-__device__ __forceinline__ uint32_t code_of(const uint32_t (&w)[4], int j) { return (w[j / 2] >> (16 * (j & 1))) & 0xFFFFu; }
-
 // ---- pass 1: one read of every flat code ------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(FF_T) void flat_sums_kernel(SumsArgs a) {
     const uint32_t units = (uint32_t)a.Hm * (uint32_t)a.lpr;             // Hm * Wm < 2^31
     const size_t fsz = (size_t)a.Hm * a.Wm;
     for (uint32_t i = blockIdx.x * FF_T + threadIdx.x; i < units; i += gridDim.x * FF_T) {
-        const int y = (int)(i / (uint32_t)a.lpr), l = (int)(i - (uint32_t)y * (uint32_t)a.lpr), x0 = l * FF_NPX;
+        const int y = (int)(i / (uint32_t)a.lpr), l = (int)(i - (uint32_t)y * (uint32_t)a.lpr), x0 = l * ROW_NPX;
         const size_t site = (size_t)y * a.Wm + x0;
-        uint32_t T[FF_NPX], sat = 0u;
-        uint64_t Q[FF_NPX];
+        uint32_t T[ROW_NPX], sat = 0u;
+        uint64_t Q[ROW_NPX];
 #pragma unroll
-        for (int j = 0; j < FF_NPX; ++j) { T[j] = 0u; Q[j] = 0ull; }
-        for (int f0 = 0; f0 < a.F; f0 += FF_U) {                         // F is even: a group of four holds whole pairs
-            const uint16_t* src[FF_U];
-            bool ok[FF_U], wide = a.vec_in;
+        for (int j = 0; j < ROW_NPX; ++j) { T[j] = 0u; Q[j] = 0ull; }
+        for (int f0 = 0; f0 < a.F; f0 += POOL_U) {                       // F is even: a group of four holds whole pairs
+            const uint16_t* src[POOL_U];
+            bool ok[POOL_U], wide = a.vec_in;
 #pragma unroll
-            for (int u = 0; u < FF_U; ++u) {                             // launch-uniform: the table entry decides, not the lane
+            for (int u = 0; u < POOL_U; ++u) {                           // launch-uniform: the table entry decides, not the lane
                 ok[u] = f0 + u < a.F;
                 src[u] = a.pool;
                 if (ok[u]) {
@@ -105,28 +83,28 @@ __global__ __launch_bounds__(FF_T) void flat_sums_kernel(SumsArgs a) {
                     ok[u] = e.Hm == a.Hm && e.Wm == a.Wm && !(e.offset & 1u) && e.offset <= a.pool_elems && fsz <= a.pool_elems - e.offset;
                     if (ok[u]) {
                         src[u] = a.pool + e.offset + site;
-                        wide = wide && e.offset % FF_NPX == 0;
+                        wide = wide && e.offset % ROW_NPX == 0;
                     }
                 }
             }
-            uint32_t w[FF_U][4];
+            uint32_t w[POOL_U][4];
             if (wide) {
 #pragma unroll
-                for (int u = 0; u < FF_U; ++u) {
-                    if (ok[u]) load_codes<true>(src[u], x0, a.Wm, w[u]);
+                for (int u = 0; u < POOL_U; ++u) {
+                    if (ok[u]) load_codes8<true>(src[u], x0, a.Wm, w[u]);
                     else w[u][0] = w[u][1] = w[u][2] = w[u][3] = 0u;
                 }
             } else {
 #pragma unroll
-                for (int u = 0; u < FF_U; ++u) {
-                    if (ok[u]) load_codes<false>(src[u], x0, a.Wm, w[u]);
+                for (int u = 0; u < POOL_U; ++u) {
+                    if (ok[u]) load_codes8<false>(src[u], x0, a.Wm, w[u]);
                     else w[u][0] = w[u][1] = w[u][2] = w[u][3] = 0u;
                 }
             }
 #pragma unroll
-            for (int h = 0; h < FF_U / 2; ++h)
+            for (int h = 0; h < POOL_U / 2; ++h)
 #pragma unroll
-                for (int j = 0; j < FF_NPX; ++j) {
+                for (int j = 0; j < ROW_NPX; ++j) {
                     const uint32_t ca = code_of(w[2 * h], j), cb = code_of(w[2 * h + 1], j);
                     const uint32_t d = ca > cb ? ca - cb : cb - ca;
                     T[j] += ca + cb;
@@ -134,8 +112,8 @@ __global__ __launch_bounds__(FF_T) void flat_sums_kernel(SumsArgs a) {
                     sat |= (uint32_t)(((int)ca >= a.white) | ((int)cb >= a.white)) << j;
                 }
         }
-        uint32_t flag = sat | (a.bitmap ? (a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31)) : 0u);
-        const int inside = a.Wm - x0 < FF_NPX ? a.Wm - x0 : FF_NPX;      // columns of this lane that lie in the row: no bits beyond it
+        uint32_t flag = sat | (a.bitmap ? defect_bits(a.bitmap, a.wpr, y, x0) : 0u);
+        const int inside = a.Wm - x0 < ROW_NPX ? a.Wm - x0 : ROW_NPX;    // columns of this lane that lie in the row: no bits beyond it
         flag &= (1u << inside) - 1u;
         uint8_t* bytes = reinterpret_cast<uint8_t*>(a.bad) + (size_t)y * a.wpr * 4;
         bytes[l] = (uint8_t)flag;
@@ -149,7 +127,7 @@ __global__ __launch_bounds__(FF_T) void flat_sums_kernel(SumsArgs a) {
             for (int k = 0; k < 4; ++k) pd[k] = make_ulonglong2(Q[2 * k], Q[2 * k + 1]);
         } else {
 #pragma unroll
-            for (int j = 0; j < FF_NPX; ++j)
+            for (int j = 0; j < ROW_NPX; ++j)
                 if (x0 + j < a.Wm) { a.S[site + j] = T[j]; a.D[site + j] = Q[j]; }
         }
     }
@@ -169,7 +147,7 @@ __global__ __launch_bounds__(FF_T) void flat_box_rows_kernel(const uint32_t* __r
     for (int k = t; k < n; k += FF_T) {
         const int x = xt - halo + k;
         uint64_t v = 0ull;
-        if (x >= 0 && x < Wm && !((bad[(size_t)y * wpr + (x >> 5)] >> (x & 31)) & 1u)) v = ((uint64_t)S[(size_t)y * Wm + x] << 16) | 1ull;
+        if (x >= 0 && x < Wm && !defect_bit(bad, wpr, y, x)) v = ((uint64_t)S[(size_t)y * Wm + x] << 16) | 1ull;
         g[k] = v;
     }
     __syncthreads();
@@ -223,30 +201,30 @@ __global__ __launch_bounds__(FF_T) void flat_box_cols_kernel(const uint64_t* __r
 // in and out may be the same buffer: a lane reads its own 8 codes of a frame before it writes them, and touches no others
 template <int P, bool VEC>
 __global__ __launch_bounds__(FF_T) void flat_apply_kernel(ApplyArgs a) {
-    __shared__ float s_blk[P * 12];
-    fill_cells<P>(s_blk, a.black);
+    __shared__ float s_blk[P * CELL_ROW];
+    fill_cell_rows<P>(s_blk, a.black);
     __syncthreads();
     const uint32_t units = (uint32_t)a.Hm * (uint32_t)a.lpr;
     const size_t fsz = (size_t)a.Hm * a.Wm;
     for (uint32_t i = blockIdx.x * FF_T + threadIdx.x; i < units; i += gridDim.x * FF_T) {
-        const int y = (int)(i / (uint32_t)a.lpr), x0 = (int)(i - (uint32_t)y * (uint32_t)a.lpr) * FF_NPX;
+        const int y = (int)(i / (uint32_t)a.lpr), x0 = (int)(i - (uint32_t)y * (uint32_t)a.lpr) * ROW_NPX;
         const size_t site = (size_t)y * a.Wm + x0;
-        const float* blk = s_blk + (y % P) * 12 + (P == 2 ? 0 : x0 % P);
-        float fg[FF_NPX];
+        const float* blk = s_blk + (y % P) * CELL_ROW + (P == 2 ? 0 : x0 % P);
+        float fg[ROW_NPX];
         if (VEC) {
             const float4 g0 = reinterpret_cast<const float4*>(a.gain + site)[0], g1 = reinterpret_cast<const float4*>(a.gain + site)[1];
             fg[0] = g0.x; fg[1] = g0.y; fg[2] = g0.z; fg[3] = g0.w; fg[4] = g1.x; fg[5] = g1.y; fg[6] = g1.z; fg[7] = g1.w;
         } else {
 #pragma unroll
-            for (int j = 0; j < FF_NPX; ++j) fg[j] = x0 + j < a.Wm ? a.gain[site + j] : 1.f;
+            for (int j = 0; j < ROW_NPX; ++j) fg[j] = x0 + j < a.Wm ? a.gain[site + j] : 1.f;
         }
-        const uint32_t bad = a.bitmap ? a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31) : 0u;
+        const uint32_t bad = a.bitmap ? defect_bits(a.bitmap, a.wpr, y, x0) : 0u;
         for (int n = 0; n < a.N; ++n) {
             uint32_t w[4], o[4];
-            load_codes<VEC>(a.in + (size_t)n * fsz + site, x0, a.Wm, w);
-            int q[FF_NPX];
+            load_codes8<VEC>(a.in + (size_t)n * fsz + site, x0, a.Wm, w);
+            int q[ROW_NPX];
 #pragma unroll
-            for (int j = 0; j < FF_NPX; ++j) {
+            for (int j = 0; j < ROW_NPX; ++j) {
                 const int u = (int)code_of(w, j);
                 const float v = (float)u - blk[j];
                 const float m = v * fg[j];
@@ -269,7 +247,7 @@ __global__ __launch_bounds__(FF_T) void flat_apply_kernel(ApplyArgs a) {
 
 template <int P>
 int box_launch(const uint32_t* S, const uint32_t* bad, int Hm, int Wm, int radius, uint64_t* Bsum, uint32_t* Bcnt, uint64_t* ws, hipStream_t st) {
-    const int wpr = (Wm + 31) / 32;
+    const int wpr = bitmap_pitch(Wm);
     const long long tx = (Wm + BoxTile<P>::TW - 1) / BoxTile<P>::TW, nb1 = tx * Hm;
     const long long cx = (Wm + FF_T - 1) / FF_T, nb2 = cx * ((Hm + BoxTile<P>::TH - 1) / BoxTile<P>::TH);
     if (nb1 > 0x7FFFFFFFll || nb2 > 0x7FFFFFFFll) return ELD_EINVAL;
@@ -291,9 +269,9 @@ extern "C" int eld_flat_sums_u16(const uint16_t* pool, size_t pool_elems, const 
     if (!pool || !frames || !S || !D || !bad) return ELD_EINVAL;
     SumsArgs a;
     a.pool = pool; a.pool_elems = pool_elems; a.frames = frames; a.bitmap = bitmap; a.S = S; a.D = D; a.bad = bad;
-    a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32; a.lpr = (Wm + FF_NPX - 1) / FF_NPX; a.F = F; a.white = white_level;
-    a.vec_in = Wm % FF_NPX == 0 && !((uintptr_t)pool & 15u);
-    a.vec_out = Wm % FF_NPX == 0 && !(((uintptr_t)S | (uintptr_t)D) & 15u);
+    a.Hm = Hm; a.Wm = Wm; a.wpr = bitmap_pitch(Wm); a.lpr = (Wm + ROW_NPX - 1) / ROW_NPX; a.F = F; a.white = white_level;
+    a.vec_in = Wm % ROW_NPX == 0 && !((uintptr_t)pool & 15u);
+    a.vec_out = Wm % ROW_NPX == 0 && !(((uintptr_t)S | (uintptr_t)D) & 15u);
     ELD_LAUNCH(flat_sums_kernel, dim3(stride_grid((uint32_t)Hm * (uint32_t)a.lpr, FF_T)), dim3(FF_T), 0, as_stream(stream), a);
     ELD_LAUNCH_CHECK();
     return 0;
@@ -332,10 +310,10 @@ extern "C" int eld_flat_apply_u16(const uint16_t* in, uint16_t* out, int N, int 
     if (!in || !out || !gain) return ELD_EINVAL;
     ApplyArgs a;
     a.in = in; a.out = out; a.gain = gain; a.bitmap = bitmap;
-    a.N = N; a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32; a.lpr = (Wm + FF_NPX - 1) / FF_NPX; a.white = white_level;
+    a.N = N; a.Hm = Hm; a.Wm = Wm; a.wpr = bitmap_pitch(Wm); a.lpr = (Wm + ROW_NPX - 1) / ROW_NPX; a.white = white_level;
     for (int k = 0; k < 36; ++k) a.black[k] = k < period * period ? black[k] : 0.f;
     // Wm % 8 == 0 makes a frame a multiple of 16 bytes: every frame of an aligned stack is aligned
-    const bool vec = Wm % FF_NPX == 0 && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)gain) & 15u);
+    const bool vec = Wm % ROW_NPX == 0 && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)gain) & 15u);
     const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr, FF_T));
     if (period == 2) {
         if (vec) ELD_LAUNCH((flat_apply_kernel<2, true>), grid, dim3(FF_T), 0, as_stream(stream), a);

@@ -14,7 +14,7 @@
 // LDS counters cannot wrap: a workgroup adds one per pixel it reads, all of one frame (plane), and the host refuses Hm * Wm >= 2^31 (H * W).
 // The group of a pixel comes from a per-row 64-bit word of 4-bit codes (group + 1, 0 = not counted) shifted by the column phase, the defect
 // bit from one 32-bit word of the bitmap per 16-byte load: neither needs a pass of its own.
-#include "common.h"
+#include "mosaic_dev.h"
 
 namespace {
 
@@ -47,10 +47,6 @@ struct HistF32Args {
     int nc, stride;
     signed char grp[64];
 };
-
-__global__ __launch_bounds__(256) void hist_zero_kernel(uint64_t* __restrict__ p, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0;
-}
 
 extern __shared__ uint32_t h_lds[];
 
@@ -104,18 +100,18 @@ __global__ __launch_bounds__(HT) void hist_u16_kernel(HistU16Args a) {
     auto bin_chunk = [&](uint32_t i, const uint32_t (&wu)[NW], const uint32_t (&wv)[NW]) __attribute__((always_inline)) {
         const uint32_t y = fdiv_u32(i, a.dcpr);
         const uint32_t x0 = (i - y * a.cpr) * NPX;
-        const uint32_t rm = P == 2 ? (y & 1u) : y - 6u * (__umulhi(y, 0xAAAAAAABu) >> 2);
-        const uint32_t cm = P == 2 ? 0u : x0 - 6u * (__umulhi(x0, 0xAAAAAAABu) >> 2);
+        const uint32_t rm = cell_phase<P>(y);
+        const uint32_t cm = P == 2 ? 0u : mod6(x0);
         const uint64_t rw = s_roww[rm] >> (4u * cm);
         uint32_t bad = 0;
-        if (a.bitmap) bad = a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31u);   // x0 is a multiple of NPX: the NPX bits lie in one word
+        if (a.bitmap) bad = defect_bits(a.bitmap, a.wpr, y, x0);
 #pragma unroll
         for (int j = 0; j < NPX; ++j) {
-            const int code = (int)((wu[j / 2] >> (16 * (j & 1))) & 0xFFFFu);
+            const int code = (int)code_of(wu, j);
             const int nib = (int)((uint32_t)(rw >> (4 * j)) & 15u);
             if (nib != 0 && !((bad >> j) & 1u)) {
                 const int g = nib - 1;
-                const int sub = vw ? (int)((wv[j / 2] >> (16 * (j & 1))) & 0xFFFFu) : (g == 0 ? c0 : g == 1 ? c1 : g == 2 ? c2 : c3);
+                const int sub = vw ? (int)code_of(wv, j) : (g == 0 ? c0 : g == 1 ? c1 : g == 2 ? c2 : c3);
                 const int b = min(max(code - sub + R, 0), 2 * R);
                 hist_add<GLOBAL>(tab, out, g * B + b);
             }
@@ -198,13 +194,6 @@ void lds_layout(size_t tw, int& nc, int& stride, size_t& bytes) {
     bytes = (size_t)nc * st * 4;
 }
 
-int zero_counts(uint64_t* counts, size_t n, hipStream_t s) {
-    const size_t nb = (n + 255) / 256;
-    ELD_LAUNCH(hist_zero_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, s, counts, n);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
 unsigned grid_x(uint32_t nchunks, int per_thread, size_t lds_bytes, int others) {
     const unsigned want = (unsigned)((nchunks + (uint32_t)(HT * per_thread) - 1) / (uint32_t)(HT * per_thread));
     const int wg_per_cu = lds_bytes > (size_t)H_LDS_SHARED ? 1 : 2;
@@ -257,14 +246,14 @@ extern "C" int eld_hist_u16(const uint16_t* u, const uint16_t* v, int F, int Hm,
     if (!empty && (!u || ((uintptr_t)u & 3u) || ((uintptr_t)v & 3u) || ((uintptr_t)bitmap & 3u))) return ELD_EINVAL;
     HistU16Args a;
     a.u = u; a.v = v; a.bitmap = bitmap; a.counts = counts;
-    a.Hm = Hm; a.Wm = Wm; a.G = G; a.R = R; a.B = 2 * R + 1; a.wpr = (Wm + 31) / 32;
+    a.Hm = Hm; a.Wm = Wm; a.G = G; a.R = R; a.B = 2 * R + 1; a.wpr = bitmap_pitch(Wm);
     for (int k = 0; k < 4; ++k) a.centre[k] = (!v && k < G) ? centre[k] : 0;
     for (int r = 0; r < 6; ++r) {
         a.roww[r] = 0;
         for (int k = 0; k < 12 && r < p; ++k) a.roww[r] |= (uint64_t)(group[r * p + k % p] + 1) << (4 * k);
     }
     hipStream_t s = as_stream(stream);
-    const int rc = zero_counts(counts, (size_t)F * G * a.B, s);
+    const int rc = zero_u64(counts, (size_t)F * G * a.B, s);
     if (rc || empty) return rc;
     const bool vec = Wm % 8 == 0 && !((uintptr_t)u & 15u) && !((uintptr_t)v & 15u);
     const int npx = vec ? 8 : 2;
@@ -293,7 +282,7 @@ extern "C" int eld_hist_f32(const float* x, const float* x2, int N, int C, int H
     a.C = C; a.G = G; a.R = R; a.B = 2 * R + 1; a.hw = (uint32_t)H * (uint32_t)W;
     for (int k = 0; k < 64; ++k) a.grp[k] = (signed char)(k < C ? group[k] : -1);
     hipStream_t s = as_stream(stream);
-    const int rc = zero_counts(counts, (size_t)N * G * a.B, s);
+    const int rc = zero_u64(counts, (size_t)N * G * a.B, s);
     if (rc || empty) return rc;
     const bool vec = a.hw % 4 == 0 && !((uintptr_t)x & 15u) && !((uintptr_t)x2 & 15u);
     size_t lds_bytes;

@@ -13,5 +13,3 @@ __device__ __forceinline__ int bin_of(int code, int s, int white) {
     const int o = 31 - __clz(s);
     return 8 + 4 * (o - 3) + ((s >> (o - 2)) & 3);
 }
-
-__device__ __forceinline__ uint32_t mod6(uint32_t v) { return v - 6u * (__umulhi(v, 0xAAAAAAABu) >> 2); }

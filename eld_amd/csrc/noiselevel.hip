@@ -20,8 +20,7 @@
 //   * store   after a barrier thread j < 4 G adds the four waves' rows and stores out[..][j].
 // Bounds: |r| <= 8 * 65535 < 2^20, r^2 < 2^38; dx^2 + dy^2 < 2^33; S9 < 2^20; a tile has at most (16 * 6)^2 = 9216 < 2^14 sites: every
 // sum stays below 2^52.
-#include "common.h"
-#include "levelbins.h"
+#include "mosaic_dev.h"
 
 namespace {
 
@@ -40,8 +39,6 @@ struct NoiseTileArgs {
     FastDiv dntx;
     int32_t tab[36];                             // cell -> sum of the nine black levels | (the nine's common group + 1) << 24, 0 in the top byte: not eligible
 };
-
-__device__ __forceinline__ uint32_t modp(uint32_t v, int p) { return p == 2 ? (v & 1u) : mod6(v); }
 
 template <int P, int S, bool VEC>
 __global__ __launch_bounds__(NL_T) void noise_tile_kernel(NoiseTileArgs a) {
@@ -72,7 +69,7 @@ __global__ __launch_bounds__(NL_T) void noise_tile_kernel(NoiseTileArgs a) {
     const unsigned long long fo = (unsigned long long)f * a.hw;
     const int white = a.white;
     auto keep = [&](int code, uint32_t ym, int x, bool flagged) __attribute__((always_inline)) -> uint16_t {
-        const uint32_t c = ym * P + modp((uint32_t)x, P);
+        const uint32_t c = ym * P + cell_phase<P>((uint32_t)x);
         const bool ok = code < white && !flagged && ((a.counted >> c) & 1ull);
         return ok ? (uint16_t)code : (uint16_t)0;
     };
@@ -94,7 +91,7 @@ __global__ __launch_bounds__(NL_T) void noise_tile_kernel(NoiseTileArgs a) {
                 if ((xf >> 5) + 1 < a.wpr) bad |= (unsigned long long)bw[1] << 32;
                 bad >>= (xf & 31);
             }
-            const uint32_t ym = modp((uint32_t)y, P);
+            const uint32_t ym = cell_phase<P>((uint32_t)y);
             const int lx0 = (int)((long long)cb - (long long)i0);                         // the chunk's code j goes to column lx0 + j of the staged row
             uint16_t* row = s_v + ly * PITCH;
             if (cb + 8 > a.total) {                                                       // the stack's last, partial chunk: code by code
@@ -105,15 +102,15 @@ __global__ __launch_bounds__(NL_T) void noise_tile_kernel(NoiseTileArgs a) {
             const uint32_t w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                if (j >= j0 && j < j1) row[lx0 + j] = keep((int)((w[j / 2] >> (16 * (j & 1))) & 0xFFFFu), ym, xb + j, (bad >> (j - j0)) & 1ull);
+                if (j >= j0 && j < j1) row[lx0 + j] = keep((int)code_of(w, j), ym, xb + j, (bad >> (j - j0)) & 1ull);
         }
     } else {
         for (int t = tid; t < rows * RS; t += NL_T) {
             const int ly = t / RS, lx = t - ly * RS;
             if (lx >= cols) continue;
             const int y = ys + ly, x = xs + lx;
-            const bool flagged = a.bitmap && ((a.bitmap[(size_t)y * a.wpr + (x >> 5)] >> (x & 31)) & 1u);
-            s_v[ly * PITCH + lx] = keep((int)a.frames[fo + (unsigned long long)y * a.Wm + x], modp((uint32_t)y, P), x, flagged);
+            const bool flagged = a.bitmap && defect_bit(a.bitmap, a.wpr, y, x);
+            s_v[ly * PITCH + lx] = keep((int)a.frames[fo + (unsigned long long)y * a.Wm + x], cell_phase<P>((uint32_t)y), x, flagged);
         }
     }
     __syncthreads();
@@ -121,13 +118,13 @@ __global__ __launch_bounds__(NL_T) void noise_tile_kernel(NoiseTileArgs a) {
     // ---- sums: wave w takes the cells w, w + 4, ...
     const int lane = tid & (ELD_WAVE - 1), wave = tid / ELD_WAVE;
     const int y0 = ys + S, x0 = xs + S;                                                   // the tile's first site
-    const int py = (int)modp((uint32_t)y0, P), px = (int)modp((uint32_t)x0, P);
+    const int py = (int)cell_phase<P>((uint32_t)y0), px = (int)cell_phase<P>((uint32_t)x0);
     int cur = -1;
     unsigned long long an = 0, as = 0, ar = 0, ad = 0;
     auto flush = [&]() __attribute__((always_inline)) {
         if (cur >= 0) {
 #pragma unroll
-            for (int m = ELD_WAVE / 2; m >= 1; m >>= 1) {
+            for (int m = ELD_WAVE / 2; m >= 1; m >>= 1) {         // four sums per step: wave_sum four times is another instruction stream
                 an += __shfl_xor(an, m, ELD_WAVE);
                 as += __shfl_xor(as, m, ELD_WAVE);
                 ar += __shfl_xor(ar, m, ELD_WAVE);
@@ -205,10 +202,7 @@ extern "C" int eld_tile_noise_sums_u16(const uint16_t* frames, int F, int Hm, in
                                        void* stream) {
     if ((p != 2 && p != 6) || F < 0 || F > 65535 || Hm < 0 || Wm < 0 || Hc < 0 || Hc > Hm || Wc < 0 || Wc > Wm || G < 1 || G > 4) return ELD_EINVAL;
     if (stride < 1 || stride > p || p % stride != 0) return ELD_EINVAL;
-    if (!group || !black || white < 1 || white > 65536) return ELD_EINVAL;
-    if ((uint64_t)Hm * (uint64_t)Wm >= (1ull << 31)) return ELD_EINVAL;
-    for (int k = 0; k < p * p; ++k)
-        if (group[k] < -1 || group[k] >= G || black[k] < 0 || black[k] > 65535) return ELD_EINVAL;
+    if ((uint64_t)Hm * (uint64_t)Wm >= (1ull << 31) || !cell_groups_ok(p, group, G, black, white)) return ELD_EINVAL;
     (void)ws;
     if (ws_bytes < eld_tile_noise_workspace_bytes(F, Hm, Wm)) return ELD_EWS;
     const int nty = tiles_along(Hc, stride), ntx = tiles_along(Wc, stride);
@@ -216,7 +210,7 @@ extern "C" int eld_tile_noise_sums_u16(const uint16_t* frames, int F, int Hm, in
     if (!frames || ((uintptr_t)frames & 1u) || !out || ((uintptr_t)out & 7u) || ((uintptr_t)bitmap & 3u)) return ELD_EINVAL;
     NoiseTileArgs a;
     a.frames = frames; a.bitmap = bitmap; a.out = (long long*)out;
-    a.Hm = Hm; a.Wm = Wm; a.Hc = Hc; a.Wc = Wc; a.G = G; a.white = white; a.wpr = (Wm + 31) / 32; a.ntx = ntx; a.nty = nty;
+    a.Hm = Hm; a.Wm = Wm; a.Hc = Hc; a.Wc = Wc; a.G = G; a.white = white; a.wpr = bitmap_pitch(Wm); a.ntx = ntx; a.nty = nty;
     a.hw = (uint32_t)Hm * (uint32_t)Wm;
     a.total = (unsigned long long)F * a.hw;
     a.dntx = make_fastdiv((uint32_t)ntx);

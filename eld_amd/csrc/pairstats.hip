@@ -23,8 +23,8 @@
 //     instead of 64-way.  16 copies are 80000 bytes: two workgroups (16 waves) per CU.
 // At its end a workgroup folds the copies and adds every non-zero sum to out[] with a 64-bit global integer atomic (at most 976 per 32768
 // sites); out[] is zeroed by a kernel of this call first.  No floating point anywhere, no environment switch, no workspace.
-#include "common.h"
 #include "levelbins.h"
+#include "mosaic_dev.h"
 
 namespace {
 
@@ -53,10 +53,6 @@ struct PairStatArgs {
     int32_t tab[36];                             // cell -> black | (group + 1) << 16
 };
 
-__global__ __launch_bounds__(256) void pairstats_zero_kernel(long long* __restrict__ p, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0;
-}
-
 extern __shared__ unsigned long long ps_lds[];
 
 // the pending run of one column parity
@@ -66,6 +62,8 @@ struct Run {
     int32_t s, e;
     unsigned long long q;
 };
+
+__device__ __forceinline__ void run_clear(Run& r) { r.key = -1; r.n = 0; r.s = 0; r.e = 0; r.q = 0; }
 
 __device__ __forceinline__ void run_flush(uint32_t* __restrict__ tab, const Run& r) {
     if (r.key >= 0) {
@@ -94,10 +92,10 @@ __device__ __forceinline__ void run_add(uint32_t* __restrict__ tab, Run& r, int 
 
 template <int P, int MODE>
 __global__ __launch_bounds__(PT) void pairstats_kernel(PairStatArgs a) {
-    __shared__ int32_t s_tab[P * 12];                            // row phase r, 12 columns: cell (r, k % P)
+    __shared__ int32_t s_tab[P * CELL_ROW];
     uint32_t* lds = reinterpret_cast<uint32_t*>(ps_lds);
     for (int i = threadIdx.x; i < PS_COPIES * PS_STRIDE; i += PT) lds[i] = 0;
-    if (threadIdx.x < P * 12) s_tab[threadIdx.x] = a.tab[(threadIdx.x / 12) * P + (threadIdx.x % 12) % P];
+    fill_cell_rows<P>(s_tab, a.tab);
     __syncthreads();
     uint32_t* tab = lds + (threadIdx.x & (PS_COPIES - 1)) * PS_STRIDE;
     const int f = blockIdx.y;
@@ -106,17 +104,17 @@ __global__ __launch_bounds__(PT) void pairstats_kernel(PairStatArgs a) {
     const uint16_t* fr = a.ref + fo;
     const int white = a.white;
     Run run[2];
-    run[0].key = run[1].key = -1;
-    run[0].n = run[1].n = 0; run[0].s = run[1].s = 0; run[0].e = run[1].e = 0; run[0].q = run[1].q = 0;
+    run_clear(run[0]);
+    run_clear(run[1]);
 
     // a site by its index in the frame: everything derived per site
     auto site = [&](uint32_t i, int est, int ref, Run& r) __attribute__((always_inline)) {
         const uint32_t y = fdiv_u32(i, a.dwm);
         const uint32_t x = i - y * (uint32_t)a.Wm;
-        const uint32_t ym = P == 2 ? (y & 1u) : mod6(y), xm = P == 2 ? (x & 1u) : mod6(x);
+        const uint32_t ym = cell_phase<P>(y), xm = cell_phase<P>(x);
         bool ok = (int)y < a.Hc && (int)x < a.Wc;
-        if (a.bitmap) ok = ok && !((a.bitmap[(size_t)y * a.wpr + (x >> 5)] >> (x & 31u)) & 1u);
-        run_add(tab, r, est, ref, s_tab[ym * 12 + xm], ok, white);
+        if (a.bitmap) ok = ok && !defect_bit(a.bitmap, a.wpr, y, x);
+        run_add(tab, r, est, ref, s_tab[ym * CELL_ROW + xm], ok, white);
     };
 
     if constexpr (MODE == PS_SCALAR) {
@@ -140,20 +138,20 @@ __global__ __launch_bounds__(PT) void pairstats_kernel(PairStatArgs a) {
             if constexpr (MODE == PS_ROWS) {
                 const uint32_t y = fdiv_u32(ci, a.dcpr);
                 const uint32_t x0 = (ci - y * a.cpr) * 8u;
-                const int32_t* trow = s_tab + (P == 2 ? (y & 1u) : mod6(y)) * 12 + (P == 2 ? 0u : mod6(x0));
+                const int32_t* trow = cell_row<P>(s_tab, y, x0);
                 uint32_t bad = 0;
-                if (a.bitmap) bad = a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31u);   // x0 is a multiple of 8: the bits lie in one word
+                if (a.bitmap) bad = defect_bits(a.bitmap, a.wpr, y, x0);
                 const bool rowin = (int)y < a.Hc;
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int est = (int)((we[j / 2] >> (16 * (j & 1))) & 0xFFFFu), ref = (int)((wr[j / 2] >> (16 * (j & 1))) & 0xFFFFu);
+                    const int est = (int)code_of(we, j), ref = (int)code_of(wr, j);
                     const bool ok = rowin && (int)x0 + j < a.Wc && !((bad >> j) & 1u);
                     run_add(tab, run[j & 1], est, ref, trow[j], ok, white);
                 }
             } else {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const int est = (int)((we[j / 2] >> (16 * (j & 1))) & 0xFFFFu), ref = (int)((wr[j / 2] >> (16 * (j & 1))) & 0xFFFFu);
+                    const int est = (int)code_of(we, j), ref = (int)code_of(wr, j);
                     site(i + j, est, ref, run[j & 1]);
                 }
             }
@@ -209,10 +207,7 @@ extern "C" int eld_pair_level_stats_u16(const uint16_t* est, const uint16_t* ref
                                         int G, const int32_t* black, int white, const uint32_t* bitmap, int64_t* out, void* ws, size_t ws_bytes,
                                         void* stream) {
     if ((p != 2 && p != 6) || F < 0 || F > 65535 || Hm < 0 || Wm < 0 || Hc < 0 || Hc > Hm || Wc < 0 || Wc > Wm || G < 1 || G > 4) return ELD_EINVAL;
-    if (!group || !black || white < 1 || white > 65536) return ELD_EINVAL;
-    if ((uint64_t)Hm * (uint64_t)Wm >= (1ull << 31)) return ELD_EINVAL;
-    for (int k = 0; k < p * p; ++k)
-        if (group[k] < -1 || group[k] >= G || black[k] < 0 || black[k] > 65535) return ELD_EINVAL;
+    if ((uint64_t)Hm * (uint64_t)Wm >= (1ull << 31) || !cell_groups_ok(p, group, G, black, white)) return ELD_EINVAL;
     (void)ws;
     if (ws_bytes < eld_pair_level_stats_workspace_bytes(F, Hm, Wm)) return ELD_EWS;
     if (F == 0) return 0;
@@ -220,15 +215,13 @@ extern "C" int eld_pair_level_stats_u16(const uint16_t* est, const uint16_t* ref
     const bool empty = Hm == 0 || Wm == 0;
     if (!empty && (!est || !ref || ((uintptr_t)est & 1u) || ((uintptr_t)ref & 1u) || ((uintptr_t)bitmap & 3u))) return ELD_EINVAL;
     hipStream_t s = as_stream(stream);
-    const size_t nout = (size_t)F * G * PS_NB * 4;
-    ELD_LAUNCH(pairstats_zero_kernel, dim3((unsigned)((nout + 255) / 256 < 4096 ? (nout + 255) / 256 : 4096)), dim3(256), 0, s, (long long*)out, nout);
-    ELD_LAUNCH_CHECK();
+    if (int rc = zero_u64(out, (size_t)F * G * PS_NB * 4, s)) return rc;
     if (empty || Hc == 0 || Wc == 0) return 0;
     PairStatArgs a;
     a.est = est; a.ref = ref; a.bitmap = bitmap; a.out = (long long*)out;
-    a.Hm = Hm; a.Wm = Wm; a.Hc = Hc; a.Wc = Wc; a.G = G; a.white = white; a.wpr = (Wm + 31) / 32;
+    a.Hm = Hm; a.Wm = Wm; a.Hc = Hc; a.Wc = Wc; a.G = G; a.white = white; a.wpr = bitmap_pitch(Wm);
     a.hw = (uint32_t)Hm * (uint32_t)Wm;
-    for (int k = 0; k < 36; ++k) a.tab[k] = k < p * p ? (black[k] | ((group[k] + 1) << 16)) : 0;
+    pack_cell_tab(a.tab, p, group, black);
     const bool al16 = !(((uintptr_t)est | (uintptr_t)ref) & 15u);
     const int mode = !al16 ? PS_SCALAR : (Wm % 8 == 0 ? PS_ROWS : PS_FLAT);
     a.cpr = mode == PS_ROWS ? (uint32_t)(Wm / 8) : 1u;

@@ -12,15 +12,13 @@
 // the frame's start allow it, else one 32-bit word per column pair (Wm is even, frames start at even elements).  The 8 bits of the defect
 // bitmap lie in one word.  The fit walks the frames of a session four at a time (four loads in flight per lane), keeps eight uint32 sums
 // for the session in turn and folds them into the float64 pair (A, B) before the next session starts.  Grids are sized from eld_num_cus().
-#include "common.h"
+#include "mosaic_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int SH_T = 256;                        // threads per workgroup
-constexpr int SH_NPX = 8;                        // columns per lane
-constexpr int SH_U = 4;                          // frames in flight per lane
 constexpr int SH_MAX_S = 16;                     // sessions per call (they travel as kernel arguments)
 constexpr int SH_MAX_COUNT = 65536;              // frames per session: 65536 * 65535 < 2^32 keeps the uint32 sums exact
 
@@ -47,50 +45,30 @@ struct ApplyArgs {
     int N, Hm, Wm, wpr, lpr;
 };
 
-// the centres a lane needs: row phase r, columns x0 % P + j (x0 % P is 0 when P == 2 and 0, 2 or 4 when P == 6, so 12 entries per row phase)
-template <int P>
-__device__ __forceinline__ void fill_centres(int32_t* s_cen, const int32_t* cen) {
-    if (threadIdx.x < P * 12) s_cen[threadIdx.x] = cen[(threadIdx.x / 12) * P + (threadIdx.x % 12) % P];
-}
-
-// 8 codes as 4 words.  VEC: one 16-byte load; otherwise one word per column pair that lies inside the row (the others read as 0)
-template <bool VEC>
-__device__ __forceinline__ void load_codes(const uint16_t* p, int x0, int Wm, uint32_t (&w)[4]) {
-    if (VEC) {
-        const uint4 q = *reinterpret_cast<const uint4*>(p);
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) w[k] = x0 + 2 * k < Wm ? *reinterpret_cast<const uint32_t*>(p + 2 * k) : 0u;
-    }
-}
-
-__device__ __forceinline__ uint32_t code_of(const uint32_t (&w)[4], int j) { return (w[j / 2] >> (16 * (j & 1))) & 0xFFFFu; }
-
 template <int P>
 __global__ __launch_bounds__(SH_T) void shading_fit_kernel(FitArgs a) {
-    __shared__ int32_t s_cen[P * 12];
-    fill_centres<P>(s_cen, a.cen);
+    __shared__ int32_t s_cen[P * CELL_ROW];
+    fill_cell_rows<P>(s_cen, a.cen);
     __syncthreads();
     const uint32_t units = (uint32_t)a.Hm * (uint32_t)a.lpr;             // Hm * Wm < 2^31
     const size_t fsz = (size_t)a.Hm * a.Wm;
     for (uint32_t i = blockIdx.x * SH_T + threadIdx.x; i < units; i += gridDim.x * SH_T) {
-        const int y = (int)(i / (uint32_t)a.lpr), x0 = (int)(i - (uint32_t)y * (uint32_t)a.lpr) * SH_NPX;
+        const int y = (int)(i / (uint32_t)a.lpr), x0 = (int)(i - (uint32_t)y * (uint32_t)a.lpr) * ROW_NPX;
         const size_t site = (size_t)y * a.Wm + x0;
-        const int32_t* cenl = s_cen + (y % P) * 12 + (P == 2 ? 0 : x0 % P);
-        double A[SH_NPX], B[SH_NPX];
+        const int32_t* cenl = s_cen + (y % P) * CELL_ROW + (P == 2 ? 0 : x0 % P);
+        double A[ROW_NPX], B[ROW_NPX];
 #pragma unroll
-        for (int j = 0; j < SH_NPX; ++j) A[j] = B[j] = 0.0;
+        for (int j = 0; j < ROW_NPX; ++j) A[j] = B[j] = 0.0;
         for (int s = 0; s < a.S; ++s) {
             const int first = a.first[s], cnt = a.count[s];
-            uint32_t T[SH_NPX];
+            uint32_t T[ROW_NPX];
 #pragma unroll
-            for (int j = 0; j < SH_NPX; ++j) T[j] = 0u;
-            for (int f0 = 0; f0 < cnt; f0 += SH_U) {
-                const uint16_t* src[SH_U];
-                bool ok[SH_U], wide = a.vec_in;
+            for (int j = 0; j < ROW_NPX; ++j) T[j] = 0u;
+            for (int f0 = 0; f0 < cnt; f0 += POOL_U) {
+                const uint16_t* src[POOL_U];
+                bool ok[POOL_U], wide = a.vec_in;
 #pragma unroll
-                for (int u = 0; u < SH_U; ++u) {                         // launch-uniform: the table entry decides, not the lane
+                for (int u = 0; u < POOL_U; ++u) {                       // launch-uniform: the table entry decides, not the lane
                     ok[u] = f0 + u < cnt;
                     src[u] = a.pool;
                     if (ok[u]) {
@@ -99,41 +77,41 @@ __global__ __launch_bounds__(SH_T) void shading_fit_kernel(FitArgs a) {
                         ok[u] = e.Hm == a.Hm && e.Wm == a.Wm && !(e.offset & 1u) && e.offset <= a.pool_elems && fsz <= a.pool_elems - e.offset;
                         if (ok[u]) {
                             src[u] = a.pool + e.offset + site;
-                            wide = wide && e.offset % SH_NPX == 0;
+                            wide = wide && e.offset % ROW_NPX == 0;
                         }
                     }
                 }
-                uint32_t w[SH_U][4];
+                uint32_t w[POOL_U][4];
                 if (wide) {
 #pragma unroll
-                    for (int u = 0; u < SH_U; ++u) {
-                        if (ok[u]) load_codes<true>(src[u], x0, a.Wm, w[u]);
+                    for (int u = 0; u < POOL_U; ++u) {
+                        if (ok[u]) load_codes8<true>(src[u], x0, a.Wm, w[u]);
                         else w[u][0] = w[u][1] = w[u][2] = w[u][3] = 0u;
                     }
                 } else {
 #pragma unroll
-                    for (int u = 0; u < SH_U; ++u) {
-                        if (ok[u]) load_codes<false>(src[u], x0, a.Wm, w[u]);
+                    for (int u = 0; u < POOL_U; ++u) {
+                        if (ok[u]) load_codes8<false>(src[u], x0, a.Wm, w[u]);
                         else w[u][0] = w[u][1] = w[u][2] = w[u][3] = 0u;
                     }
                 }
 #pragma unroll
-                for (int u = 0; u < SH_U; ++u)
+                for (int u = 0; u < POOL_U; ++u)
 #pragma unroll
-                    for (int j = 0; j < SH_NPX; ++j) T[j] += code_of(w[u], j);
+                    for (int j = 0; j < ROW_NPX; ++j) T[j] += code_of(w[u], j);
             }
             const double c = (double)cnt, al = a.alpha[s], be = a.beta[s];
 #pragma unroll
-            for (int j = 0; j < SH_NPX; ++j) {
+            for (int j = 0; j < ROW_NPX; ++j) {
                 const double ys = ((double)T[j] - c * (double)cenl[j]) / c;      // product and difference exact: one rounding
                 A[j] = A[j] + al * ys;
                 B[j] = B[j] + be * ys;
             }
         }
-        const uint32_t bad = a.bitmap ? a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31) : 0u;
-        float oa[SH_NPX], ob[SH_NPX];
+        const uint32_t bad = a.bitmap ? defect_bits(a.bitmap, a.wpr, y, x0) : 0u;
+        float oa[ROW_NPX], ob[ROW_NPX];
 #pragma unroll
-        for (int j = 0; j < SH_NPX; ++j) {
+        for (int j = 0; j < ROW_NPX; ++j) {
             const bool flagged = (bad >> j) & 1u;
             oa[j] = flagged ? 0.f : (float)A[j];
             ob[j] = flagged ? 0.f : (float)B[j];
@@ -145,7 +123,7 @@ __global__ __launch_bounds__(SH_T) void shading_fit_kernel(FitArgs a) {
             pb[0] = make_float4(ob[0], ob[1], ob[2], ob[3]); pb[1] = make_float4(ob[4], ob[5], ob[6], ob[7]);
         } else {
 #pragma unroll
-            for (int j = 0; j < SH_NPX; ++j)
+            for (int j = 0; j < ROW_NPX; ++j)
                 if (x0 + j < a.Wm) { a.out_a[site + j] = oa[j]; a.out_b[site + j] = ob[j]; }
         }
     }
@@ -164,9 +142,9 @@ __global__ __launch_bounds__(SH_T) void shading_apply_kernel(ApplyArgs a) {
     const uint32_t units = (uint32_t)a.Hm * (uint32_t)a.lpr;
     const size_t fsz = (size_t)a.Hm * a.Wm;
     for (uint32_t i = blockIdx.x * SH_T + threadIdx.x; i < units; i += gridDim.x * SH_T) {
-        const int y = (int)(i / (uint32_t)a.lpr), x0 = (int)(i - (uint32_t)y * (uint32_t)a.lpr) * SH_NPX;
+        const int y = (int)(i / (uint32_t)a.lpr), x0 = (int)(i - (uint32_t)y * (uint32_t)a.lpr) * ROW_NPX;
         const size_t site = (size_t)y * a.Wm + x0;
-        float fa[SH_NPX], fb[SH_NPX];
+        float fa[ROW_NPX], fb[ROW_NPX];
         if (VEC) {
             const float4 a0 = reinterpret_cast<const float4*>(a.a + site)[0], a1 = reinterpret_cast<const float4*>(a.a + site)[1];
             const float4 b0 = reinterpret_cast<const float4*>(a.b + site)[0], b1 = reinterpret_cast<const float4*>(a.b + site)[1];
@@ -174,19 +152,19 @@ __global__ __launch_bounds__(SH_T) void shading_apply_kernel(ApplyArgs a) {
             fb[0] = b0.x; fb[1] = b0.y; fb[2] = b0.z; fb[3] = b0.w; fb[4] = b1.x; fb[5] = b1.y; fb[6] = b1.z; fb[7] = b1.w;
         } else {
 #pragma unroll
-            for (int j = 0; j < SH_NPX; ++j) {
+            for (int j = 0; j < ROW_NPX; ++j) {
                 const bool in = x0 + j < a.Wm;
                 fa[j] = in ? a.a[site + j] : 0.f;
                 fb[j] = in ? a.b[site + j] : 0.f;
             }
         }
-        const uint32_t bad = a.bitmap ? a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31) : 0u;
-        int r[SH_NPX];
+        const uint32_t bad = a.bitmap ? defect_bits(a.bitmap, a.wpr, y, x0) : 0u;
+        int r[ROW_NPX];
 #pragma unroll
-        for (int j = 0; j < SH_NPX; ++j) r[j] = ((bad >> j) & 1u) ? 0 : shading_step(fa[j], fb[j], a.t);   // a flagged site passes through
+        for (int j = 0; j < ROW_NPX; ++j) r[j] = ((bad >> j) & 1u) ? 0 : shading_step(fa[j], fb[j], a.t);   // a flagged site passes through
         for (int n = 0; n < a.N; ++n) {
             uint32_t w[4], o[4];
-            load_codes<VEC>(a.in + (size_t)n * fsz + site, x0, a.Wm, w);
+            load_codes8<VEC>(a.in + (size_t)n * fsz + site, x0, a.Wm, w);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int lo = min(max((int)code_of(w, 2 * k) - r[2 * k], 0), 65535);
@@ -223,9 +201,9 @@ extern "C" int eld_shading_fit_u16(const uint16_t* pool, size_t pool_elems, cons
     if (!pool || !frames || !out_a || !out_b) return ELD_EINVAL;
     FitArgs a;
     a.pool = pool; a.pool_elems = pool_elems; a.frames = frames; a.bitmap = bitmap; a.out_a = out_a; a.out_b = out_b;
-    a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32; a.lpr = (Wm + SH_NPX - 1) / SH_NPX; a.S = S;
-    a.vec_in = Wm % SH_NPX == 0 && !((uintptr_t)pool & 15u);
-    a.vec_out = Wm % SH_NPX == 0 && !(((uintptr_t)out_a | (uintptr_t)out_b) & 15u);
+    a.Hm = Hm; a.Wm = Wm; a.wpr = bitmap_pitch(Wm); a.lpr = (Wm + ROW_NPX - 1) / ROW_NPX; a.S = S;
+    a.vec_in = Wm % ROW_NPX == 0 && !((uintptr_t)pool & 15u);
+    a.vec_out = Wm % ROW_NPX == 0 && !(((uintptr_t)out_a | (uintptr_t)out_b) & 15u);
     for (int s = 0; s < SH_MAX_S; ++s) {
         a.first[s] = s < S ? sessions[2 * s] : 0; a.count[s] = s < S ? sessions[2 * s + 1] : 0;
         a.alpha[s] = s < S ? alpha[s] : 0.0; a.beta[s] = s < S ? beta[s] : 0.0;
@@ -246,9 +224,9 @@ extern "C" int eld_shading_apply_u16(const uint16_t* in, uint16_t* out, int N, i
     if (!in || !out || !ma || !mb) return ELD_EINVAL;
     ApplyArgs a;
     a.in = in; a.out = out; a.a = ma; a.b = mb; a.bitmap = bitmap; a.t = t;
-    a.N = N; a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32; a.lpr = (Wm + SH_NPX - 1) / SH_NPX;
+    a.N = N; a.Hm = Hm; a.Wm = Wm; a.wpr = bitmap_pitch(Wm); a.lpr = (Wm + ROW_NPX - 1) / ROW_NPX;
     // Wm % 8 == 0 makes a frame a multiple of 16 bytes: every frame of an aligned stack is aligned
-    const bool vec = Wm % SH_NPX == 0 && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)ma | (uintptr_t)mb) & 15u);
+    const bool vec = Wm % ROW_NPX == 0 && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)ma | (uintptr_t)mb) & 15u);
     const dim3 grid(stride_grid((uint32_t)Hm * (uint32_t)a.lpr, SH_T));
     if (vec) ELD_LAUNCH(shading_apply_kernel<true>, grid, dim3(SH_T), 0, as_stream(stream), a);
     else ELD_LAUNCH(shading_apply_kernel<false>, grid, dim3(SH_T), 0, as_stream(stream), a);

@@ -20,7 +20,7 @@
 // phases with two selects each.  The cell centres come from a small LDS table (row phase x 12 entries, read at x0 % 6 + j).
 // Grid: blockIdx.x = band * spans + span, blockIdx.y = frame (pair).  The band height starts at 32 (p = 2) or 48 (p = 6) rows per wave and
 // doubles while the call would still start more than 8 workgroups per CU (eld_num_cus()): larger bands mean fewer atomics per pixel.
-#include "common.h"
+#include "mosaic_dev.h"
 
 namespace {
 
@@ -42,17 +42,6 @@ struct StructArgs {
 struct PairArgs {
     int32_t ab[S_PAIRS][2];
 };
-
-__global__ __launch_bounds__(256) void struct_zero_kernel(long long* __restrict__ p, size_t n) {
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int m = ELD_WAVE / 2; m > 0; m >>= 1) v += __shfl_xor(v, m, ELD_WAVE);
-    return v;
-}
 
 __device__ __forceinline__ void add64(long long* p, long long v) {
     atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
@@ -77,21 +66,6 @@ __device__ __forceinline__ void rotate_phases(const T (&rel)[KC], int cm, T (&ab
     }
 }
 
-template <int NPX>
-__device__ __forceinline__ void load_row(const uint16_t* __restrict__ rowp, int x0, uint32_t (&w)[NPX / 2]) {
-    if constexpr (NPX == 8) {
-        const uint4 q = *reinterpret_cast<const uint4*>(rowp + x0);
-        w[0] = q.x; w[1] = q.y; w[2] = q.z; w[3] = q.w;
-    } else {
-        w[0] = *reinterpret_cast<const uint32_t*>(rowp + x0);
-    }
-}
-
-template <int P>
-__device__ __forceinline__ void fill_centres(int32_t* s_cen, const int32_t* cen) {
-    if (threadIdx.x < P * 12) s_cen[threadIdx.x] = cen[(threadIdx.x / 12) * P + (threadIdx.x % 12) % P];
-}
-
 template <int P, int NPX>
 __global__ __launch_bounds__(ST) void struct_sums_kernel(StructArgs a) {
     constexpr int NW = NPX / 2;
@@ -100,12 +74,12 @@ __global__ __launch_bounds__(ST) void struct_sums_kernel(StructArgs a) {
     constexpr int E = ELD_WAVE * NPX * P * 2;                    // column partials of the span: [lane][j][row phase][n, sum]
     constexpr int NPK = (P + 2) / 3;                             // packed count words: three 10-bit fields each
     __shared__ uint32_t s_col[E + E / 32];                       // entry e lies at e + e / 32: a lane stride of 32 (96) words becomes 33 (99)
-    __shared__ int32_t s_cen[P * 12];
+    __shared__ int32_t s_cen[P * CELL_ROW];
     const int lane = threadIdx.x & (ELD_WAVE - 1), wave = threadIdx.x / ELD_WAVE;
     const int f = blockIdx.y;
     const int span = blockIdx.x % a.nspans, band = blockIdx.x / a.nspans;
     for (int i = threadIdx.x; i < E + E / 32; i += ST) s_col[i] = 0;
-    fill_centres<P>(s_cen, a.cen);
+    fill_cell_rows<P>(s_cen, a.cen);
     __syncthreads();
 
     const int x0 = (span * ELD_WAVE + lane) * NPX;
@@ -128,8 +102,8 @@ __global__ __launch_bounds__(ST) void struct_sums_kernel(StructArgs a) {
             for (int k = 0; k < NW; ++k) w[i][k] = 0;
             bad[i] = ~0u;
             if (in) {
-                load_row<NPX>(fb + (size_t)y * a.Wm, x0, w[i]);
-                bad[i] = a.bitmap ? a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31) : 0u;   // NPX divides 32: the bits lie in one word
+                load_codes<NPX>(fb + (size_t)y * a.Wm + x0, w[i]);
+                bad[i] = a.bitmap ? defect_bits(a.bitmap, a.wpr, y, x0) : 0u;
             }
         }
 #pragma unroll
@@ -141,9 +115,9 @@ __global__ __launch_bounds__(ST) void struct_sums_kernel(StructArgs a) {
                 int srel[KC] = {}, nrel[KC] = {};
 #pragma unroll
                 for (int j = 0; j < NPX; ++j) {
-                    const int code = (int)((w[i][j / 2] >> (16 * (j & 1))) & 0xFFFFu);
+                    const int code = (int)((w[i][j / 2] >> (16 * (j & 1))) & 0xFFFFu);   // written out, here and below: code_of changes the NPX = 2 kernels
                     const int good = (int)(~(bad[i] >> j) & 1u);
-                    const int d = good ? code - cenl[r * 12 + j] : 0;
+                    const int d = good ? code - cenl[r * CELL_ROW + j] : 0;
                     cn[r][j] += good;
                     cs[r][j] += d;
                     nrel[j % PP] += good;
@@ -224,10 +198,10 @@ __global__ __launch_bounds__(ST) void struct_cross_kernel(StructArgs a, PairArgs
     constexpr int NW = NPX / 2;
     constexpr int KC = P < NPX ? P : NPX;
     constexpr int U = P == 2 ? 2 : 3;                            // rows in flight per wave and frame (P == 6: two turns make a period)
-    __shared__ int32_t s_cen[P * 12];
+    __shared__ int32_t s_cen[P * CELL_ROW];
     const int lane = threadIdx.x & (ELD_WAVE - 1), wave = threadIdx.x / ELD_WAVE;
     const int span = blockIdx.x % a.nspans, band = blockIdx.x / a.nspans;
-    fill_centres<P>(s_cen, a.cen);
+    fill_cell_rows<P>(s_cen, a.cen);
     __syncthreads();
 
     const int x0 = (span * ELD_WAVE + lane) * NPX;
@@ -250,9 +224,9 @@ __global__ __launch_bounds__(ST) void struct_cross_kernel(StructArgs a, PairArgs
                 for (int k = 0; k < NW; ++k) wa[i][k] = wb[i][k] = 0;
                 bad[i] = ~0u;
                 if (act && y < y1) {
-                    load_row<NPX>(fa + (size_t)y * a.Wm, x0, wa[i]);
-                    load_row<NPX>(fb + (size_t)y * a.Wm, x0, wb[i]);
-                    bad[i] = a.bitmap ? a.bitmap[(size_t)y * a.wpr + (x0 >> 5)] >> (x0 & 31) : 0u;
+                    load_codes<NPX>(fa + (size_t)y * a.Wm + x0, wa[i]);
+                    load_codes<NPX>(fb + (size_t)y * a.Wm + x0, wb[i]);
+                    bad[i] = a.bitmap ? defect_bits(a.bitmap, a.wpr, y, x0) : 0u;
                 }
             }
 #pragma unroll
@@ -261,7 +235,7 @@ __global__ __launch_bounds__(ST) void struct_cross_kernel(StructArgs a, PairArgs
 #pragma unroll
                 for (int j = 0; j < NPX; ++j) {
                     const int good = (int)(~(bad[i] >> j) & 1u);
-                    const int c = cenl[r * 12 + j];
+                    const int c = cenl[r * CELL_ROW + j];
                     const int da = good ? (int)((wa[i][j / 2] >> (16 * (j & 1))) & 0xFFFFu) - c : 0;
                     const int db = (int)((wb[i][j / 2] >> (16 * (j & 1))) & 0xFFFFu) - c;
                     acc[r][j % P] += (long long)da * db;         // |da db| < 2^32, at most Hm * Wm < 2^31 terms
@@ -279,14 +253,6 @@ __global__ __launch_bounds__(ST) void struct_cross_kernel(StructArgs a, PairArgs
             if (lane == 0 && s) add64(a.cell + (size_t)blockIdx.y * (P * P) + r * P + c, s);
         }
     }
-}
-
-int zero_i64(long long* p, size_t n, hipStream_t s) {
-    if (n == 0) return 0;
-    const size_t nb = (n + 255) / 256;
-    ELD_LAUNCH(struct_zero_kernel, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(256), 0, s, p, n);
-    ELD_LAUNCH_CHECK();
-    return 0;
 }
 
 // rows per band: a multiple of `unit` (the rows the four waves take per turn); doubled while the call would start more than 8 workgroups per CU
@@ -312,7 +278,7 @@ bool bad_out(const void* p, size_t n) { return ((uintptr_t)p & 7u) || (n && !p);
 
 void fill_args(StructArgs& a, const uint16_t* u, int Hm, int Wm, int p, const int32_t* centre, const uint32_t* bitmap, bool vec, int others) {
     a.u = u; a.bitmap = bitmap;
-    a.Hm = Hm; a.Wm = Wm; a.wpr = (Wm + 31) / 32;
+    a.Hm = Hm; a.Wm = Wm; a.wpr = bitmap_pitch(Wm);
     const int lane_cols = ELD_WAVE * (vec ? 8 : 2);
     a.nspans = (Wm + lane_cols - 1) / lane_cols;
     a.bh = band_height(Hm, a.nspans, others, SWAVES * (p == 2 ? 4 : 6));
@@ -329,7 +295,7 @@ extern "C" int eld_struct_sums_u16(const uint16_t* u, int F, int Hm, int Wm, int
     if (bad_out(row, nrow) || bad_out(col, ncol) || bad_out(cell, ncell)) return ELD_EINVAL;
     if (F == 0) return 0;
     hipStream_t s = as_stream(stream);
-    if ((rc = zero_i64((long long*)row, nrow, s)) || (rc = zero_i64((long long*)col, ncol, s)) || (rc = zero_i64((long long*)cell, ncell, s))) return rc;
+    if ((rc = zero_u64(row, nrow, s)) || (rc = zero_u64(col, ncol, s)) || (rc = zero_u64(cell, ncell, s))) return rc;
     if (Hm == 0 || Wm == 0) return 0;
     const bool vec = Wm % 8 == 0 && !((uintptr_t)u & 15u);
     StructArgs a;
@@ -358,7 +324,7 @@ extern "C" int eld_struct_cross_u16(const uint16_t* u, int F, int Hm, int Wm, in
     if (bad_out(cross, ncross)) return ELD_EINVAL;
     if (Q == 0) return 0;
     hipStream_t s = as_stream(stream);
-    if ((rc = zero_i64((long long*)cross, ncross, s))) return rc;
+    if ((rc = zero_u64(cross, ncross, s))) return rc;
     if (Hm == 0 || Wm == 0) return 0;
     const bool vec = Wm % 8 == 0 && !((uintptr_t)u & 15u);
     StructArgs a;

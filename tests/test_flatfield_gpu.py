@@ -347,7 +347,7 @@ def _gain_case(rng, shape, p):
     return u, g, black, n
 
 
-@pytest.mark.parametrize('cfa,shape', SHAPES)
+@pytest.mark.parametrize('cfa,shape', SHAPES + [('xtrans', (12, 24))])     # (12, 24): X-Trans on the 16-byte path
 @pytest.mark.parametrize('N', [1, 3])
 def test_apply_equals_the_restatement(eld_lib, dev, cfa, shape, N):
     import torch

@@ -112,8 +112,11 @@ def test_groups(eld_lib, p, s, G, group):
     rng = np.random.default_rng(p * 100 + s * 10 + G)
     Hm, Wm = (70, 100) if p == 2 else (120, 114)
     fr = _frames(rng, 1, Hm, Wm, 4000)
-    want = _check(eld_lib, fr, Hm, Wm, p, s, group, G, rng.integers(0, 600, size=p * p), 4000)
+    black = rng.integers(0, 600, size=p * p)
+    want = _check(eld_lib, fr, Hm, Wm, p, s, group, G, black, 4000)
     assert want[..., 0].sum() > 0
+    if (p, s) == (2, 1):                                                              # the only Bayer case at stride 1: also on the 2-byte path
+        _check(eld_lib, fr, Hm, Wm, p, s, group, G, black, 4000, offset=1)
 
 
 @pytest.mark.parametrize('p,s,group,G,Hm,Wm', [(2, 2, RGGB, 4, 70, 100), (6, 3, XT_GREEN, 3, 114, 126)])

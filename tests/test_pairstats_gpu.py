@@ -92,6 +92,12 @@ def test_misaligned_views_take_the_scalar_path(eld_lib):
         rc, out = _call(eld_lib, ve, vr, 2, [0, 1, 3, 2], 4, [512] * 4, 16383)
         assert rc == 0
         assert np.array_equal(out, R.pair_level_sums(est, ref, 2, [0, 1, 3, 2], 4, [512] * 4, 16383))
+    est, ref = _frames(rng, 2, 12, 18, 1024, 16383)            # the same path under the X-Trans cell
+    ve, vr = torch.zeros(est.size + 1, dtype=torch.int16, device='cuda')[1:].view(est.shape), torch.zeros(ref.size + 1, dtype=torch.int16, device='cuda')[1:].view(ref.shape)
+    ve.copy_(_dev(est)); vr.copy_(_dev(ref))
+    rc, out = _call(eld_lib, ve, vr, 6, XT_COLOUR.reshape(-1), 3, [1024] * 36, 16383)
+    assert rc == 0 and ve.data_ptr() % 16 == 2
+    assert np.array_equal(out, R.pair_level_sums(est, ref, 6, XT_COLOUR.reshape(-1), 3, [1024] * 36, 16383))
 
 
 def test_every_bin_populated(eld_lib):

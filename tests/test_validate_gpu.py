@@ -114,6 +114,11 @@ def test_hist_u16_every_radius_works(eld_lib):
     u = rng.integers(0, 65536, (2, 40, 264)).astype(np.uint16)
     for R in (32767, 4859, 4860):
         assert np.array_equal(hist_abi(_dev(u), 2, [0, 1, 3, 2], 4, [32768, 512, 0, 65535], R), hist_u16_ref(u, 2, [0, 1, 3, 2], 4, [32768, 512, 0, 65535], R))
+    # counting in global memory on the other three load paths: Bayer 32-bit words, X-Trans 32-bit words, X-Trans 16-byte loads
+    g6 = groups_u16('xtrans', XPAT)[1].reshape(-1).tolist()
+    for p, group, centre, shape in ((2, [0, 1, 3, 2], [32768, 512, 0, 65535], (6, 130)), (6, g6, [32768, 512, 0], (12, 18)), (6, g6, [32768, 512, 0], (12, 24))):
+        u = rng.integers(0, 65536, (2,) + shape).astype(np.uint16)
+        assert np.array_equal(hist_abi(_dev(u), p, group, len(centre), centre, 32767), hist_u16_ref(u, p, group, len(centre), centre, 32767))
 
 
 @pytest.mark.parametrize('shape,cfa', [((34, 50), 'bayer'), ((34, 64), 'bayer'), ((45, 264), 'xtrans'), ((13, 70), 'xtrans')])
