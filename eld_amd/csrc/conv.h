@@ -385,7 +385,7 @@ int launch_conv_bfs(const ConvArgs& a, hipStream_t st);
 // same BN = 64 slab layout as conv_bfd_kernel<64>, chosen per launch inside launch_conv_bfd
 bool bfw_takes(const ConvArgs& a);
 int launch_conv_bfw(const ConvArgs& a, hipStream_t st);
-// bf16 transposed convolutions (conv_bfg.hip: both operands by LDS-DMA): column-block width of the packed slabs (bfg_store), 0 = stays on conv_igemm_kernel
+// bf16 transposed convolutions (conv_bfg.hip: both operands by LDS-DMA): column-block width of the packed slabs (bfg_store8), 0 = stays on conv_igemm_kernel
 int bfg_slab_bn(bool gather, int Nout, int Cs, int Cout_t, int N, int H, int W);
 __host__ __device__ inline size_t bfg_slab_bytes(int BN) { return (size_t)BN * 64; }
 int launch_conv_bfg(const ConvArgs& a, int mode, hipStream_t st);

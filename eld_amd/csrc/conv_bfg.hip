@@ -9,7 +9,7 @@
 // the register-staged kernel spent its time in two barriers per 8 MFMAs and 8-byte scattered stores (2.1 TB/s).  Here:
 //   * work item = (16 x 32 pixel tile, BN-wide column block, 32-channel k chunk): one 32 KB activation tile + one BN x 64 B weight slab, both
 //     copied HBM/L2 -> LDS by linear 1 KiB LDS-DMA pieces in conv_bfd's XOR-swizzled landing order (conflict-free ds_read_b128 fragments);
-//     the weights are packed once per step as the exact LDS image of every slab (bfg_store, unet_misc.hip);
+//     the weights are packed once per step as the exact LDS image of every slab (bfg_store8, unet_misc.hip);
 //   * a ring of three (tile, slab) buffers: items j+1 and j+2 are in flight while item j is multiplied; the ring runs across column blocks and
 //     tiles, so the queue never drains inside a launch; one barrier per item; waits are counted (every item has exactly A_IT + B_IT DMA
 //     instructions per wave -- past the end of the work, out-of-range dummies -- so the count is one immediate);

@@ -296,7 +296,7 @@ static int launch_first_t(const float* x, const float* w, const float* bias, TO*
 int launch_conv_first_fwd(const float* x, const float* w, const float* bias, float* out, int N, int Cin, int H, int W, int lrelu, hipStream_t st, unsigned* codes) {
     return launch_first_t<float>(x, w, bias, out, N, Cin, H, W, lrelu, st, codes);
 }
-int launch_conv_first_fwd_bf16(const float* x, const float* w, const float* bias, bf16_t* out, int N, int Cin, int H, int W, int lrelu, hipStream_t st, unsigned* codes) {
+int launch_conv_first_fwd(const float* x, const float* w, const float* bias, bf16_t* out, int N, int Cin, int H, int W, int lrelu, hipStream_t st, unsigned* codes) {
     return launch_first_t<bf16_t>(x, w, bias, out, N, Cin, H, W, lrelu, st, codes);
 }
 
@@ -779,7 +779,7 @@ int launch_conv_first_wgrad(const float* g, const float* x, float* dw, float* db
     ELD_LAUNCH_CHECK();
     return 0;
 }
-int launch_conv_first_wgrad_bf16(const bf16_t* g, const float* x, float* dw, float* db, float* part, int N, int Cin, int H, int W, hipStream_t st) {
+int launch_conv_first_wgrad(const bf16_t* g, const float* x, float* dw, float* db, float* part, int N, int Cin, int H, int W, hipStream_t st, bool /*x3: an fp32 product scheme*/) {
     const int tiles = ((W + FTW - 1) / FTW) * ((H + FTH - 1) / FTH) * N;
     if (tiles <= 0) return 0;
     if (Cin != 4 || (size_t)N * H * W * 64 >= 0xFFFFFFF0ull) return launch_first_wgrad_t<bf16_t>(g, x, dw, db, part, N, Cin, H, W, st);      // generic fp32-MFMA kernel

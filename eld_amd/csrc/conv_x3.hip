@@ -31,7 +31,7 @@
 
 namespace {
 
-// BSLAB (round 6): the weights arrive PRE-SPLIT in conv_x3d_kernel's slab layout (x3_store, unet_misc.hip: the exact LDS image of a stage's slab, rows of
+// BSLAB (round 6): the weights arrive PRE-SPLIT in conv_x3d_kernel's slab layout (x3_store8, unet_misc.hip: the exact LDS image of a stage's slab, rows of
 // 3 pieces x 16 bf16 + pad) and a stage's slab is copied global -> registers -> LDS as it is (three 16-byte units per thread): no weight cut per
 // stage and tile (a fifth of this kernel's VALU work and a third of its ds_write instructions); the register staging and the two 4-wave workgroups
 // per CU stay (the LDS-DMA variants of this layer shape needed a second slab buffer and lost the second workgroup: retired, see x3_slab_bn).
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256, 2) void conv_x3_kernel(const ConvArgs a) {
 // once per 16-channel chunk = once per three stages.
 //
 //   packed weights:  slab(ky, chunk, nb) = [kx 0..2][n 0..BN)[3 pieces][16 bf16] + 16 B pad per row  (3*BN rows x 112 B, 1 KiB-multiple)
-//                    at byte offset ((ky * (K/16) + chunk) * (Nout/BN) + nb) * 3*BN*112          (x3_store in unet_misc.hip)
+//                    at byte offset ((ky * (K/16) + chunk) * (Nout/BN) + nb) * 3*BN*112          (x3_store8 in unet_misc.hip)
 //   stage s:         barrier [slab s landed (each wave drained its own DMA pieces before arriving) / everybody done with stage s-1]
 //                    ky == 0:  cut the halo registers into LDS, barrier
 //                    issue DMA of slab s+1 into the other buffer; ky == 0: issue the next chunk's halo loads into registers

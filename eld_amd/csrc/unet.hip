@@ -960,6 +960,18 @@ static int layer_ws(void* ws, size_t ws_bytes, int N, int H, int W, int Cin, int
     return 0;
 }
 
+// one layer's reference-layout fp32 weights -> the packed layout its kernel family reads, as pack_weights does for the same launch: a one-job pack_all launch.
+// bf16: round to nearest even (bfdbn / bfgbn: the DMA kernels' slab width from bfd_slab_bn / bfg_slab_bn); fp32: plain, or the pre-split slabs of width x3bn.
+// The channel rules of the callers give the groups of eight k-channels pack_all_kernel works in.
+static int pack_one(const float* w, float* pack, int kind, int Cout, int Cin, int T, int bf16, int x3bn, int bfdbn, int bfgbn, hipStream_t st) {
+    PackJobs jobs;
+    jobs.n = 1;
+    PackJob J = {};
+    J.kind = kind; J.Cout = Cout; J.Cin = Cin; J.Cinp = Cin; J.T = T; J.bf16 = bf16; J.x3bn = x3bn; J.bfdbn = bfdbn; J.bfgbn = bfgbn;
+    jobs.job[0] = J;
+    return launch_pack_all(jobs, w, pack, st);
+}
+
 extern "C" int eld_conv3x3_forward(const float* in0, int C0, const float* in1, int C1, const float* w, const float* bias, float* out, int N,
                                    int H, int W, int Cout, int lrelu, void* ws, size_t ws_bytes, void* stream) {
     if (N == 0) return 0;
@@ -968,7 +980,7 @@ extern "C" int eld_conv3x3_forward(const float* in0, int C0, const float* in1, i
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, C0 + C1, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
-    RC(launch_pack(w, pack, PACK_CONV_FWD, Cout, C0 + C1, C0 + C1, 9, st, g_algo == 1 ? x3_slab_bn(Cout, N, H, W) : 0));
+    RC(pack_one(w, pack, PACK_CONV_FWD, Cout, C0 + C1, 9, 0, g_algo == 1 ? x3_slab_bn(Cout, N, H, W) : 0, 0, 0, st));
     float* am;
     RC(layer_amax(ws, eld_layer_workspace_bytes(N, H, W, C0 + C1, Cout), st, in0, (size_t)N * H * W * C0, in1, (size_t)N * H * W * C1, pack, (size_t)9 * Cout * (C0 + C1), &am));
     if (am) { g_am.in0 = am; g_am.in1 = in1 ? am + 1 : nullptr; g_am.w = am + 2; g_am.out0 = am + 3; }
@@ -983,7 +995,7 @@ extern "C" int eld_conv3x3_backward_data(const float* g, const float* w, float* 
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
-    RC(launch_pack(w, pack, PACK_CONV_BWD, Cout, Cin, Cin, 9, st, g_algo == 1 ? x3_slab_bn(Cin, N, H, W) : 0));
+    RC(pack_one(w, pack, PACK_CONV_BWD, Cout, Cin, 9, 0, g_algo == 1 ? x3_slab_bn(Cin, N, H, W) : 0, 0, 0, st));
     float* am;
     RC(layer_amax(ws, eld_layer_workspace_bytes(N, H, W, Cin, Cout), st, g, (size_t)N * H * W * Cout, nullptr, 0, pack, (size_t)9 * Cout * Cin, &am));
     if (am) { g_am.in0 = am; g_am.w = am + 2; g_am.out0 = am + 3; g_am.out1 = am + 4; }
@@ -1011,7 +1023,7 @@ extern "C" int eld_convt2x2_forward(const float* in, const float* w, const float
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
-    RC(launch_pack(w, pack, PACK_CONVT_FWD, Cout, Cin, Cin, 4, st));
+    RC(pack_one(w, pack, PACK_CONVT_FWD, Cout, Cin, 4, 0, 0, 0, 0, st));
     float* am;
     RC(layer_amax(ws, eld_layer_workspace_bytes(N, H, W, Cin, Cout), st, in, (size_t)N * H * W * Cin, nullptr, 0, pack, (size_t)4 * Cout * Cin, &am));
     if (am) { g_am.in0 = am; g_am.w = am + 2; g_am.out0 = am + 3; }
@@ -1026,7 +1038,7 @@ extern "C" int eld_convt2x2_backward_data(const float* dout, const float* w, con
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
-    RC(launch_pack(w, pack, PACK_CONVT_BWD, Cout, Cin, Cin, 4, st));
+    RC(pack_one(w, pack, PACK_CONVT_BWD, Cout, Cin, 4, 0, 0, 0, 0, st));
     float* am;
     RC(layer_amax(ws, eld_layer_workspace_bytes(N, H, W, Cin, Cout), st, dout, (size_t)N * 4 * H * W * Cout, nullptr, 0, pack, (size_t)4 * Cout * Cin, &am));
     if (am) { g_am.in0 = am; g_am.w = am + 2; g_am.out0 = am + 3; }
@@ -1061,15 +1073,6 @@ extern "C" int eld_maxpool2x2_backward(const float* act, const float* dp, const 
 // ---- single layers on NHWC bf16 tensors (test hooks of the bf16 network's dispatchers) -------------------------------------------------
 // Each call packs the reference-layout fp32 weights as pack_weights does for the same launch (bf16, round to nearest even; the DMA kernels' slab
 // width from bfd_slab_bn / bfg_slab_bn) and calls the dispatcher the bf16 U-Net calls, so the launch runs on the kernel family the network would use.
-static int pack_one_bf16(const float* w, float* pack, int kind, int Cout, int Cin, int T, int bfdbn, int bfgbn, hipStream_t st) {
-    PackJobs jobs;
-    jobs.n = 1;
-    PackJob J = {};
-    J.kind = kind; J.Cout = Cout; J.Cin = Cin; J.Cinp = Cin; J.T = T; J.bf16 = 1; J.bfdbn = bfdbn; J.bfgbn = bfgbn;
-    jobs.job[0] = J;
-    return launch_pack_all(jobs, w, pack, st);
-}
-
 extern "C" int eld_conv3x3_forward_bf16(const uint16_t* in0, int C0, const uint16_t* in1, int C1, const float* w, const float* bias, uint16_t* out,
                                         uint16_t* pool_out, int N, int H, int W, int Cout, int lrelu, void* ws, size_t ws_bytes, void* stream) {
     if (N == 0) return 0;
@@ -1077,7 +1080,7 @@ extern "C" int eld_conv3x3_forward_bf16(const uint16_t* in0, int C0, const uint1
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, C0 + C1, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
-    RC(pack_one_bf16(w, pack, PACK_CONV_FWD, Cout, C0 + C1, 9, bfd_slab_bn(Cout, C0 + C1, N, H, W), 0, st));
+    RC(pack_one(w, pack, PACK_CONV_FWD, Cout, C0 + C1, 9, 1, 0, bfd_slab_bn(Cout, C0 + C1, N, H, W), 0, st));
     return conv_fwd<bf16_t>(in0, C0, in1, C1, reinterpret_cast<const bf16_t*>(pack), bias, out, N, H, W, Cout, lrelu, st, pool_out);
 }
 
@@ -1088,7 +1091,7 @@ extern "C" int eld_conv3x3_backward_data_bf16(const uint16_t* g, const float* w,
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
-    RC(pack_one_bf16(w, pack, PACK_CONV_BWD, Cout, Cin, 9, bfd_slab_bn(Cin, Cout, N, H, W), 0, st));
+    RC(pack_one(w, pack, PACK_CONV_BWD, Cout, Cin, 9, 1, 0, bfd_slab_bn(Cin, Cout, N, H, W), 0, st));
     return conv_bwd_data<bf16_t>(g, reinterpret_cast<const bf16_t*>(pack), din0, din1, split, act0, act1, N, H, W, Cin, Cout, st);
 }
 
@@ -1108,7 +1111,7 @@ extern "C" int eld_convt2x2_forward_bf16(const uint16_t* in, const float* w, con
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
-    RC(pack_one_bf16(w, pack, PACK_CONVT_FWD, Cout, Cin, 4, 0, bfg_slab_bn(false, 4 * Cout, Cin, Cout, N, H, W), st));
+    RC(pack_one(w, pack, PACK_CONVT_FWD, Cout, Cin, 4, 1, 0, 0, bfg_slab_bn(false, 4 * Cout, Cin, Cout, N, H, W), st));
     return convt_fwd<bf16_t>(in, reinterpret_cast<const bf16_t*>(pack), bias, out, N, H, W, Cin, Cout, st);
 }
 
@@ -1119,7 +1122,7 @@ extern "C" int eld_convt2x2_backward_data_bf16(const uint16_t* dout, const float
     float *pack, *part;
     RC(layer_ws(ws, ws_bytes, N, H, W, Cin, Cout, &pack, &part));
     hipStream_t st = as_stream(stream);
-    RC(pack_one_bf16(w, pack, PACK_CONVT_BWD, Cout, Cin, 4, 0, bfg_slab_bn(true, Cin, Cout, 0, N, H, W), st));
+    RC(pack_one(w, pack, PACK_CONVT_BWD, Cout, Cin, 4, 1, 0, 0, bfg_slab_bn(true, Cin, Cout, 0, N, H, W), st));
     return convt_bwd_data<bf16_t>(dout, reinterpret_cast<const bf16_t*>(pack), act, din, N, H, W, Cin, Cout, st);
 }
 
@@ -1135,14 +1138,14 @@ extern "C" int eld_convt2x2_backward_weight_bf16(const uint16_t* in, const uint1
 extern "C" int eld_maxpool2x2_forward_bf16(const uint16_t* in, uint16_t* out, int N, int Ho, int Wo, int C, void* stream) {
     if (N == 0) return 0;
     if (!in || !out || C % 4) return ELD_EINVAL;
-    return launch_maxpool_fwd_bf16(in, out, N, Ho, Wo, C, as_stream(stream));
+    return launch_maxpool_fwd(in, out, N, Ho, Wo, C, as_stream(stream));
 }
 
 extern "C" int eld_maxpool2x2_backward_bf16(const uint16_t* act, const uint16_t* dp, const uint16_t* skip, uint16_t* g, int N, int Ho, int Wo, int C,
                                             void* stream) {
     if (N == 0) return 0;
     if (!act || !dp || !g || C % 4) return ELD_EINVAL;
-    return launch_maxpool_bwd_bf16(act, dp, skip, g, N, Ho, Wo, C, as_stream(stream));
+    return launch_maxpool_bwd(act, dp, skip, g, N, Ho, Wo, C, as_stream(stream));
 }
 
 extern "C" int eld_debug_unet_region(int N, int H, int W, int in_ch, int out_ch, int precision, int region, int level, size_t* offset, int* channels,

@@ -30,9 +30,28 @@ int launch_nchw_to_nhwc16(const float* x, float* y, int N, int C, int H, int W, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// 2x2 max pool, NHWC.  One thread = one output pixel x 4 channels (float4).
+// Four channels of an activation tensor as one lane access: a float4 (16 bytes) or four bf16 in a uint2 (8 bytes).  The streaming kernels below are
+// written once over this; the math is fp32 for either element type.
 // ------------------------------------------------------------------------------------------------
-__global__ void maxpool_fwd_kernel(const float* __restrict__ in, float* __restrict__ out, int N, int Ho, int Wo, int C) {
+template <typename T> struct Act4;
+template <> struct Act4<float> {
+    typedef float4 vec;
+    static __device__ __forceinline__ float4 load4(vec v) { return v; }
+    static __device__ __forceinline__ vec store4(float4 v) { return v; }
+};
+template <> struct Act4<bf16_t> {
+    typedef uint2 vec;
+    static __device__ __forceinline__ float4 load4(vec v) { return unpack_bf4(v); }
+    static __device__ __forceinline__ vec store4(float4 v) { return pack_bf4(v); }
+};
+
+// ------------------------------------------------------------------------------------------------
+// 2x2 max pool, NHWC.  One thread = one output pixel x 4 channels.
+// ------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void maxpool_fwd_kernel(const T* __restrict__ in, T* __restrict__ out, int N, int Ho, int Wo, int C) {
+    typedef Act4<T> E;
+    typedef typename E::vec V;
     const int C4 = C / 4;
     const size_t total = (size_t)N * Ho * Wo * C4;
     const int Wi = 2 * Wo;
@@ -42,24 +61,27 @@ __global__ void maxpool_fwd_kernel(const float* __restrict__ in, float* __restri
         const int xo = (int)(p % Wo); p /= Wo;
         const int yo = (int)(p % Ho);
         const int n = (int)(p / Ho);
-        const float4* src = reinterpret_cast<const float4*>(in + (((size_t)n * 2 * Ho + 2 * yo) * Wi + 2 * xo) * C) + c4;
-        const float4 a = src[0], b = src[C4], c = src[(size_t)Wi * C4], d = src[(size_t)Wi * C4 + C4];
+        const V* src = reinterpret_cast<const V*>(in + (((size_t)n * 2 * Ho + 2 * yo) * Wi + 2 * xo) * C) + c4;
+        const float4 a = E::load4(src[0]), b = E::load4(src[C4]), c = E::load4(src[(size_t)Wi * C4]), d = E::load4(src[(size_t)Wi * C4 + C4]);
         float4 r;
         r.x = fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x));
         r.y = fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y));
         r.z = fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z));
         r.w = fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w));
-        reinterpret_cast<float4*>(out)[i] = r;
+        reinterpret_cast<V*>(out)[i] = E::store4(r);
     }
 }
 
-int launch_maxpool_fwd(const float* in, float* out, int N, int Ho, int Wo, int C, hipStream_t st) {
+template <typename T>
+int launch_maxpool_fwd(const T* in, T* out, int N, int Ho, int Wo, int C, hipStream_t st) {
     const size_t total = (size_t)N * Ho * Wo * (C / 4);
     if (!total) return 0;
-    ELD_LAUNCH(maxpool_fwd_kernel, dim3((unsigned)min((total + 255) / 256, (size_t)32768)), dim3(256), 0, st, in, out, N, Ho, Wo, C);
+    ELD_LAUNCH(maxpool_fwd_kernel<T>, dim3((unsigned)min((total + 255) / 256, (size_t)32768)), dim3(256), 0, st, in, out, N, Ho, Wo, C);
     ELD_LAUNCH_CHECK();
     return 0;
 }
+template int launch_maxpool_fwd<float>(const float*, float*, int, int, int, int, hipStream_t);
+template int launch_maxpool_fwd<bf16_t>(const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);
 
 // Backward of pool fused with the skip-connection add and the LeakyReLU slope of the pooled tensor:
 //   g[pos] = (route(dp)[pos] + skip[pos]) * slope(act[pos])
@@ -76,8 +98,11 @@ int launch_maxpool_fwd(const float* in, float* out, int N, int Ho, int Wo, int C
         gd.F = ((sel == 3 ? gp.F : 0.f) + sd.F) * lrelu_slope(d.F);                            \
     }
 
-__global__ void maxpool_bwd_kernel(const float* __restrict__ act, const float* __restrict__ dp, const float* __restrict__ skip,
-                                   float* __restrict__ g, int N, int Ho, int Wo, int C) {
+template <typename T>
+__global__ void maxpool_bwd_kernel(const T* __restrict__ act, const T* __restrict__ dp, const T* __restrict__ skip, T* __restrict__ g, int N, int Ho, int Wo,
+                                   int C) {
+    typedef Act4<T> E;
+    typedef typename E::vec V;
     const int C4 = C / 4;
     const size_t total = (size_t)N * Ho * Wo * C4;
     const int Wi = 2 * Wo;
@@ -89,18 +114,18 @@ __global__ void maxpool_bwd_kernel(const float* __restrict__ act, const float* _
         const int n = (int)(p / Ho);
         const size_t base = ((((size_t)n * 2 * Ho + 2 * yo) * Wi + 2 * xo) * C) / 4 + c4;
         const size_t o1 = C4, o2 = (size_t)Wi * C4, o3 = o2 + C4;
-        const float4* A = reinterpret_cast<const float4*>(act);
-        const float4 a = A[base], b = A[base + o1], c = A[base + o2], d = A[base + o3];
-        const float4 gp = reinterpret_cast<const float4*>(dp)[i];
+        const V* A = reinterpret_cast<const V*>(act);
+        const float4 a = E::load4(A[base]), b = E::load4(A[base + o1]), c = E::load4(A[base + o2]), d = E::load4(A[base + o3]);
+        const float4 gp = E::load4(reinterpret_cast<const V*>(dp)[i]);
         float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = sa, sc = sa, sd = sa;
         if (skip) {
-            const float4* S = reinterpret_cast<const float4*>(skip);
-            sa = S[base]; sb = S[base + o1]; sc = S[base + o2]; sd = S[base + o3];
+            const V* S = reinterpret_cast<const V*>(skip);
+            sa = E::load4(S[base]); sb = E::load4(S[base + o1]); sc = E::load4(S[base + o2]); sd = E::load4(S[base + o3]);
         }
         float4 ga, gb, gc, gd;
         POOL_BWD_1(x) POOL_BWD_1(y) POOL_BWD_1(z) POOL_BWD_1(w)
-        float4* G = reinterpret_cast<float4*>(g);
-        G[base] = ga; G[base + o1] = gb; G[base + o2] = gc; G[base + o3] = gd;
+        V* G = reinterpret_cast<V*>(g);
+        G[base] = E::store4(ga); G[base + o1] = E::store4(gb); G[base + o2] = E::store4(gc); G[base + o3] = E::store4(gd);
     }
 }
 
@@ -154,13 +179,16 @@ int launch_maxpool_bwd_codes(const unsigned* pool_codes, const unsigned* slope_c
     return 0;
 }
 
-int launch_maxpool_bwd(const float* act, const float* dp, const float* skip, float* g, int N, int Ho, int Wo, int C, hipStream_t st) {
+template <typename T>
+int launch_maxpool_bwd(const T* act, const T* dp, const T* skip, T* g, int N, int Ho, int Wo, int C, hipStream_t st) {
     const size_t total = (size_t)N * Ho * Wo * (C / 4);
     if (!total) return 0;
-    ELD_LAUNCH(maxpool_bwd_kernel, dim3((unsigned)min((total + 255) / 256, (size_t)32768)), dim3(256), 0, st, act, dp, skip, g, N, Ho, Wo, C);
+    ELD_LAUNCH(maxpool_bwd_kernel<T>, dim3((unsigned)min((total + 255) / 256, (size_t)32768)), dim3(256), 0, st, act, dp, skip, g, N, Ho, Wo, C);
     ELD_LAUNCH_CHECK();
     return 0;
 }
+template int launch_maxpool_bwd<float>(const float*, const float*, const float*, float*, int, int, int, int, hipStream_t);
+template int launch_maxpool_bwd<bf16_t>(const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int, int, int, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------
 // conv10_1: 1x1, 32 -> OC (<= 4; 5..16: unet_wide.hip), no activation; NHWC in, NCHW out (Unet.py:46,88)
@@ -198,10 +226,16 @@ __device__ __forceinline__ void head_load(const T* act, size_t pc, int cq, float
     }
 }
 
+// lane geometry of the head kernels for activation element T: channels per lane, lanes per pixel, pixels per block pass (256 lanes)
+template <typename T> struct HeadGeom { static constexpr int CPL = sizeof(T) == 4 ? 4 : 8, LPP = 32 / CPL, PPB = 256 / LPP; };
+template <typename T> static int head_blocks(size_t total, size_t cap) { return (int)min((total + HeadGeom<T>::PPB - 1) / HeadGeom<T>::PPB, cap); }
+
+// Each head kernel opens with the same four lines, wq[o][j] = W[o][CPL cq + j] (zero for the planes beyond OC).  They stay written out: behind a call
+// (array by reference, or a struct by value) the compiler merges the conditional weight loads and every head kernel's code changes.
 template <typename T>
 __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ in, const float* __restrict__ w, const float* __restrict__ b,
                                                        float* __restrict__ out, int N, size_t HW, int OC) {
-    constexpr int CPL = sizeof(T) == 4 ? 4 : 8, LPP = 32 / CPL, PPB = 256 / LPP;
+    constexpr int CPL = HeadGeom<T>::CPL, LPP = HeadGeom<T>::LPP, PPB = HeadGeom<T>::PPB;
     const int tid = threadIdx.x, cq = tid & (LPP - 1), o_ld = tid & 3;
     float wq[4][CPL];
 #pragma unroll
@@ -225,21 +259,28 @@ __global__ __launch_bounds__(256) void head_fwd_kernel(const T* __restrict__ in,
     }
 }
 
-int launch_head_fwd(const float* in, const float* w, const float* b, float* out, int N, int H, int W, int OC, hipStream_t st) {
-    if (OC > 4) return launch_head_wide_fwd(in, 0, w, b, out, N, H, W, OC, st);
+template <typename T>
+int launch_head_fwd(const T* in, const float* w, const float* b, float* out, int N, int H, int W, int OC, hipStream_t st) {
+    if (OC > 4) return launch_head_wide_fwd(in, sizeof(T) != 4, w, b, out, N, H, W, OC, st);
     const size_t total = (size_t)N * H * W;
     if (!total) return 0;
-    ELD_LAUNCH(head_fwd_kernel<float>, dim3((unsigned)min((total + 31) / 32, (size_t)16384)), dim3(256), 0, st, in, w, b, out, N, (size_t)H * W, OC);
+    ELD_LAUNCH(head_fwd_kernel<T>, dim3(head_blocks<T>(total, 16384)), dim3(256), 0, st, in, w, b, out, N, (size_t)H * W, OC);
     ELD_LAUNCH_CHECK();
     return 0;
 }
+template int launch_head_fwd<float>(const float*, const float*, const float*, float*, int, int, int, int, hipStream_t);
+template int launch_head_fwd<bf16_t>(const bf16_t*, const float*, const float*, float*, int, int, int, int, hipStream_t);
 
 // backward: g[p][c] = (sum_o W[o][c] d[o][p]) * slope(act[p][c]);  dW[o][c] = sum_p d[o][p] act[p][c];  db[o] = sum_p d[o][p]
 // per-block partials [nblocks][132] -> reduced by head_bwd_reduce_kernel in fixed order.
 #define HEAD_BLOCKS 1024
-// Eight lanes per pixel, one channel quad each: a wave reads / writes 8 whole pixels = 1 KiB contiguous per instruction (the one-thread-per-
-// pixel layout touched 64 cache lines per load).  The pixel's four output gradients are read once (lane o of each quad of lanes reads plane o)
-// and handed round with quad-permute DPP moves.  A lane keeps dW[o][its 4 channels] (16 sums) and, in quad 0, db[o].
+// LPP lanes per pixel, one group of CPL channels = 16 bytes each: a wave reads / writes whole pixels, 1 KiB contiguous per instruction (the
+// one-thread-per-pixel layout touched 64 cache lines per load).
+//   fp32: EIGHT lanes per pixel, a channel quad each (8 whole pixels per wave instruction); a lane keeps dW[o][its 4 channels] (16 sums);
+//   bf16: FOUR lanes per pixel, eight channels each (16 whole pixels per wave instruction; the eight-lane layout at 8 bytes per lane measured slower
+//         than one thread per pixel); a lane keeps dW[o][its 8 channels] (32 sums).
+// The pixel's four output gradients are read once (lane o of each quad of lanes reads plane o) and handed round with quad-permute DPP moves.
+// Lanes with cq < 4 (the pixel's first quad; every lane in bf16) also keep db[their plane].
 __device__ __forceinline__ float quad_bcast(float v, int src) {
     const int i = __float_as_int(v);
     switch (src) {
@@ -249,26 +290,44 @@ __device__ __forceinline__ float quad_bcast(float v, int src) {
         default: return __int_as_float(__builtin_amdgcn_update_dpp(0, i, 0xFF, 0xF, 0xF, true));
     }
 }
+// one channel of one pixel's backward (j: index among this lane's CPL channels, c = CPL cq + j, a = act[c]):
+//   returns g[c] = (sum_o W[o][c] d[o]) * slope(a)  and adds  dW[o][c] += d[o] a
+template <int CPL>
+__device__ __forceinline__ float head_bwd_ch(const float (&d)[4], float a, const float (&wq)[4][CPL], float (&dw)[4][CPL], int j) {
+    float sacc = 0.f;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) { sacc = fmaf(wq[o][j], d[o], sacc); dw[o][j] = fmaf(d[o], a, dw[o][j]); }
+    return sacc * lrelu_slope(a);
+}
+// this lane's CPL gradient channels as the 16 bytes it stores: four floats, or eight bf16
+__device__ __forceinline__ float4 head_pack_g(const float (&gv)[4]) { return make_float4(gv[0], gv[1], gv[2], gv[3]); }
+__device__ __forceinline__ uint4 head_pack_g(const float (&gv)[8]) {
+    const uint2 g0 = pack_bf4(make_float4(gv[0], gv[1], gv[2], gv[3])), g1 = pack_bf4(make_float4(gv[4], gv[5], gv[6], gv[7]));
+    return make_uint4(g0.x, g0.y, g1.x, g1.y);
+}
+template <typename T, typename V>
+__device__ __forceinline__ void head_store_g(T* g, size_t pc, int cq, V v) { reinterpret_cast<V*>(g + pc * 32)[cq] = v; }
 
 template <typename T>       // T = float or bf16_t: element type of the saved activation and of the gradient written (math in fp32 either way)
 __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dout, const T* __restrict__ act, const float* __restrict__ w,
                                                        T* __restrict__ g, float* __restrict__ part, int N, size_t HW, int OC) {
+    constexpr int CPL = HeadGeom<T>::CPL, LPP = HeadGeom<T>::LPP, PPB = HeadGeom<T>::PPB;
     __shared__ float red[4][132];
-    const int tid = threadIdx.x, cq = tid & 7, o_ld = tid & 3;
-    float wq[4][4];                                   // w[o][4cq + j]
+    const int tid = threadIdx.x, cq = tid & (LPP - 1), o_ld = tid & 3;
+    float wq[4][CPL];                                 // w[o][CPL cq + j]
 #pragma unroll
     for (int o = 0; o < 4; ++o)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) wq[o][j] = o < OC ? w[o * 32 + 4 * cq + j] : 0.f;
-    float dw[4][4];
+        for (int j = 0; j < CPL; ++j) wq[o][j] = o < OC ? w[o * 32 + CPL * cq + j] : 0.f;
+    float dw[4][CPL];
     float db = 0.f;                                   // lanes with cq < 4 sum plane o_ld = cq
 #pragma unroll
     for (int o = 0; o < 4; ++o)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) dw[o][j] = 0.f;
+        for (int j = 0; j < CPL; ++j) dw[o][j] = 0.f;
     const size_t total = (size_t)N * HW;
-    const size_t stride = (size_t)gridDim.x * 32;
-    size_t p = (size_t)blockIdx.x * 32 + (tid >> 3);
+    const size_t stride = (size_t)gridDim.x * PPB;
+    size_t p = (size_t)blockIdx.x * PPB + (tid / LPP);
     const size_t iters = (total + stride - 1) / stride;               // every lane of a quad runs the same trip count (DPP needs its quad mates)
     for (size_t itn = 0; itn < iters; ++itn, p += stride) {
         const bool ok = p < total;
@@ -281,39 +340,29 @@ __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__
 #pragma unroll
         for (int o = 0; o < 4; ++o) d[o] = quad_bcast(dl, o);
         if (!ok) continue;
-        float4 a;
-        if constexpr (sizeof(T) == 4) a = reinterpret_cast<const float4*>(act + pc * 32)[cq];
-        else a = unpack_bf4(reinterpret_cast<const uint2*>(act + pc * 32)[cq]);
-        const float av[4] = {a.x, a.y, a.z, a.w};
-        float gv[4];
+        float av[CPL], gv[CPL];
+        head_load<T, CPL>(act, pc, cq, av);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float s = 0.f;
-#pragma unroll
-            for (int o = 0; o < 4; ++o) { s = fmaf(wq[o][j], d[o], s); dw[o][j] = fmaf(d[o], av[j], dw[o][j]); }
-            gv[j] = s * lrelu_slope(av[j]);
-        }
-        if constexpr (sizeof(T) == 4) reinterpret_cast<float4*>(g + pc * 32)[cq] = make_float4(gv[0], gv[1], gv[2], gv[3]);
-        else reinterpret_cast<uint2*>(g + pc * 32)[cq] = pack_bf4(make_float4(gv[0], gv[1], gv[2], gv[3]));
+        for (int j = 0; j < CPL; ++j) gv[j] = head_bwd_ch<CPL>(d, av[j], wq, dw, j);
+        head_store_g(g, pc, cq, head_pack_g(gv));
     }
-    // block reduction in a fixed order: lanes sharing a channel quad (cq, cq+8, ...) by xor-shuffles, then the 4 waves through LDS
+    // block reduction in a fixed order: lanes sharing a channel group (cq, cq + LPP, ...) by xor-shuffles, then the 4 waves through LDS
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int o = 0; o < 4; ++o)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
+        for (int j = 0; j < CPL; ++j) {
             float v = dw[o][j];
-            for (int off = 8; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-            if (lane < 8) red[wave][o * 32 + 4 * lane + j] = v;
+            for (int off = LPP; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+            if (lane < LPP) red[wave][o * 32 + CPL * lane + j] = v;
         }
     {
         float v = db;
-        for (int off = 8; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
+        for (int off = LPP; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
         if (lane < 4) red[wave][128 + lane] = v;
     }
     __syncthreads();
-    if (tid < 132)
-        part[(size_t)blockIdx.x * 132 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+    if (tid < 132) part[(size_t)blockIdx.x * 132 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
 }
 
 // 132 outputs, 16 lanes each over the per-block partials; fixed shuffle tree
@@ -331,24 +380,29 @@ __global__ __launch_bounds__(256) void head_bwd_reduce_kernel(const float* __res
 
 size_t head_bwd_ws_floats(int OC) { return OC > 4 ? head_wide_bwd_ws_floats(OC) : (size_t)HEAD_BLOCKS * 132; }
 
-int launch_head_bwd(const float* dout, const float* act, const float* w, float* g, float* dw, float* db, float* part,
-                    int N, int H, int W, int OC, hipStream_t st) {
-    if (OC > 4) return launch_head_wide_bwd(dout, act, 0, w, g, dw, db, part, N, H, W, OC, st);
+template <typename T>
+int launch_head_bwd(const float* dout, const T* act, const float* w, T* g, float* dw, float* db, float* part, int N, int H, int W, int OC, hipStream_t st) {
+    if (OC > 4) return launch_head_wide_bwd(dout, act, sizeof(T) != 4, w, g, dw, db, part, N, H, W, OC, st);
     const size_t total = (size_t)N * H * W;
     if (!total) return 0;
-    const int nb = (int)min((total + 31) / 32, (size_t)HEAD_BLOCKS);
-    ELD_LAUNCH(head_bwd_kernel<float>, dim3(nb), dim3(256), 0, st, dout, act, w, g, part, N, (size_t)H * W, OC);
+    const int nb = head_blocks<T>(total, HEAD_BLOCKS);
+    ELD_LAUNCH(head_bwd_kernel<T>, dim3(nb), dim3(256), 0, st, dout, act, w, g, part, N, (size_t)H * W, OC);
     ELD_LAUNCH_CHECK();
     ELD_LAUNCH(head_bwd_reduce_kernel, dim3((132 + 15) / 16), dim3(256), 0, st, part, dw, db, nb, OC);
     ELD_LAUNCH_CHECK();
     return 0;
 }
+template int launch_head_bwd<float>(const float*, const float*, const float*, float*, float*, float*, float*, int, int, int, int, hipStream_t);
+template int launch_head_bwd<bf16_t>(const float*, const bf16_t*, const float*, bf16_t*, float*, float*, float*, int, int, int, int, hipStream_t);
 
 // ------------------------------------------------------------------------------------------------
 // column sums of an NHWC matrix [P][C] -> [C]  (bias gradient of the transposed convs)
 // ------------------------------------------------------------------------------------------------
 #define COLSUM_BLOCKS 2048
-__global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x, float* __restrict__ part, size_t P, int C) {
+template <typename T>
+__global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ x, float* __restrict__ part, size_t P, int C) {
+    typedef Act4<T> E;
+    typedef typename E::vec V;
     // thread t handles channel (t % C4)*4.. of pixels t / C4 + k*(256/C4 * gridDim)
     const int C4 = C / 4;
     const int ppb = 256 / C4;                  // pixels per block-iteration (C4 <= 128 -> ppb >= 2); threads beyond ppb*C4 idle
@@ -357,14 +411,14 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ x
     if (pl < ppb) {
         const size_t step = (size_t)gridDim.x * ppb;
         size_t p = (size_t)blockIdx.x * ppb + pl;
-        for (; p + 3 * step < P; p += 4 * step) {            // four independent 16-byte loads in flight per lane
-            const float4 v0 = reinterpret_cast<const float4*>(x + p * C)[c4], v1 = reinterpret_cast<const float4*>(x + (p + step) * C)[c4];
-            const float4 v2 = reinterpret_cast<const float4*>(x + (p + 2 * step) * C)[c4], v3 = reinterpret_cast<const float4*>(x + (p + 3 * step) * C)[c4];
+        for (; p + 3 * step < P; p += 4 * step) {            // four independent 16-byte (bf16: 8-byte) loads in flight per lane
+            const float4 v0 = E::load4(reinterpret_cast<const V*>(x + p * C)[c4]), v1 = E::load4(reinterpret_cast<const V*>(x + (p + step) * C)[c4]);
+            const float4 v2 = E::load4(reinterpret_cast<const V*>(x + (p + 2 * step) * C)[c4]), v3 = E::load4(reinterpret_cast<const V*>(x + (p + 3 * step) * C)[c4]);
             s.x += (v0.x + v1.x) + (v2.x + v3.x); s.y += (v0.y + v1.y) + (v2.y + v3.y);
             s.z += (v0.z + v1.z) + (v2.z + v3.z); s.w += (v0.w + v1.w) + (v2.w + v3.w);
         }
         for (; p < P; p += step) {
-            const float4 v = reinterpret_cast<const float4*>(x + p * C)[c4];
+            const float4 v = E::load4(reinterpret_cast<const V*>(x + p * C)[c4]);
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
         }
     }
@@ -408,89 +462,20 @@ int launch_colsum_reduce(const float* part, float* out, int nblocks, int C, hipS
     return 0;
 }
 
-int launch_colsum(const float* x, float* out, float* part, size_t P, int C, hipStream_t st) {
+template <typename T>
+int launch_colsum(const T* x, float* out, float* part, size_t P, int C, hipStream_t st) {
     if (C % 4 || C > 512) return ELD_EINVAL;
     const int ppb = 256 / (C / 4);
     const int nb = (int)min((P + ppb - 1) / ppb, (size_t)COLSUM_BLOCKS);
     if (nb == 0) return 0;
-    ELD_LAUNCH(colsum_kernel, dim3(nb), dim3(256), 0, st, x, part, P, C);
+    ELD_LAUNCH(colsum_kernel<T>, dim3(nb), dim3(256), 0, st, x, part, P, C);
     ELD_LAUNCH_CHECK();
     ELD_LAUNCH(colsum_reduce_kernel, dim3((C + 63) / 64), dim3(1024), 0, st, part, out, nb, C);
     ELD_LAUNCH_CHECK();
     return 0;
 }
-
-// ------------------------------------------------------------------------------------------------
-// weight packing (tiny: 7.76 M parameters in total)
-//   PACK_CONV_FWD : dst[t][co][ci_p] = src[co][ci][t]        (zero for ci >= Cin)       src OIHW
-//   PACK_CONV_BWD : dst[t][ci][co]   = src[co][ci][T-1-t]    (flipped taps, transposed)
-//   PACK_CONVT_FWD: dst[tap*Cout+co][ci] = src[ci][co][tap]                              src (Cin,Cout,2,2)
-//   PACK_CONVT_BWD: dst[tap][ci][co]     = src[ci][co][tap]
-// ------------------------------------------------------------------------------------------------
-// Pre-split slab layout of conv_x3d_kernel (conv_x3.hip): element (tap t, GEMM column n of N, k-channel c of K) of the logical packed
-// weight B[t][n][c] is cut EXACTLY into its three bf16 pieces (top 16 bits, top 16 bits of the exact remainder, exact rest -- the same
-// cut split_store makes) and stored at   slab(ky, c/16, n/BN) + row(kx, n%BN) * 112 B + piece * 32 B + (c%16) * 2 B.
-__device__ __forceinline__ void x3_store(float* dst, int t, int n, int c, int N, int K, int BN, float v) {
-    const int NCH = K >> 4, NB = N / BN;
-    const int ky = t / 3, kx = t - 3 * ky;
-    const size_t slab = (size_t)(ky * NCH + (c >> 4)) * NB + n / BN;
-    bf16_t* d = reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(dst) + slab * x3_slab_stride(BN)) + (size_t)(kx * BN + (n % BN)) * 56 + (c & 15);
-    const unsigned x = __float_as_uint(v);
-    const float r = v - __uint_as_float(x & 0xFFFF0000u);
-    const unsigned y = __float_as_uint(r);
-    const float q = r - __uint_as_float(y & 0xFFFF0000u);
-    d[0] = (bf16_t)(x >> 16); d[16] = (bf16_t)(y >> 16); d[32] = (bf16_t)(__float_as_uint(q) >> 16);
-}
-
-// Slab layout of conv_bfd_kernel (conv_bfd.hip): element (tap t, GEMM column n of N, k-channel c of K) of the logical packed weight
-// B[t][n][c] as bf16 at   slab(ky, c/32, n/BN) + slot * 16 B + (c%8) * 2 B,   slot = 4 P + (octet ^ ((P >> 2) & 3)),  P = kx*BN + n%BN,
-// octet = (c%32)/8: the exact (XOR-swizzled) LDS image of a stage's slab, so it travels by linear 1 KiB LDS-DMA pieces.
-__device__ __forceinline__ void bfd_store(float* dst, int t, int n, int c, int N, int K, int BN, float v) {
-    const int NCH = K >> 5, NB = N / BN;
-    const int ky = t / 3, kx = t - 3 * ky;
-    const size_t slab = (size_t)(ky * NCH + (c >> 5)) * NB + n / BN;
-    const int P = kx * BN + (n % BN), o = (c & 31) >> 3;
-    const int slot = 4 * P + (o ^ ((P >> 2) & 3));
-    reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(dst) + slab * bfd_slab_bytes(BN))[slot * 8 + (c & 7)] = f2bf(v);
-}
-
-// Slab layout of conv_bfg_kernel (conv_bfg.hip): element (GEMM column n of N, k index c of K) of the logical packed weight B[n][c] as bf16 at
-//   slab(c/32, n/BN) + slot * 16 B + (c%8) * 2 B,   slot = 4 n' + (octet ^ ((n' >> 2) & 3)),  n' = n % BN, octet = (c%32)/8
-__device__ __forceinline__ void bfg_store(float* dst, int n, int c, int N, int K, int BN, float v) {
-    const int NB = N / BN, np = n % BN;
-    const size_t slab = (size_t)(c >> 5) * NB + n / BN;
-    const int slot = 4 * np + (((c & 31) >> 3) ^ ((np >> 2) & 3));
-    reinterpret_cast<bf16_t*>(reinterpret_cast<char*>(dst) + slab * bfg_slab_bytes(BN))[slot * 8 + (c & 7)] = f2bf(v);
-}
-
-__global__ void pack_kernel(const float* __restrict__ src, float* __restrict__ dst, int kind, int Cout, int Cin, int Cinp, int T, int x3bn) {
-    size_t total;
-    if (kind == PACK_CONV_FWD) total = (size_t)T * Cout * Cinp; else total = (size_t)T * Cout * Cin;
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    if (kind == PACK_CONV_FWD) {
-        const int ci = (int)(i % Cinp); const int co = (int)((i / Cinp) % Cout); const int t = (int)(i / ((size_t)Cinp * Cout));
-        const float v = ci < Cin ? src[((size_t)co * Cin + ci) * T + t] : 0.f;
-        if (x3bn) x3_store(dst, t, co, ci, Cout, Cinp, x3bn, v); else dst[i] = v;
-    } else if (kind == PACK_CONV_BWD) {
-        const int co = (int)(i % Cout); const int ci = (int)((i / Cout) % Cin); const int t = (int)(i / ((size_t)Cout * Cin));
-        const float v = src[((size_t)co * Cin + ci) * T + (T - 1 - t)];
-        if (x3bn) x3_store(dst, t, ci, co, Cin, Cout, x3bn, v); else dst[i] = v;
-    } else if (kind == PACK_CONVT_FWD) {
-        const int ci = (int)(i % Cin); const int co = (int)((i / Cin) % Cout); const int t = (int)(i / ((size_t)Cin * Cout));
-        dst[i] = src[((size_t)ci * Cout + co) * T + t];
-    } else {
-        const int co = (int)(i % Cout); const int ci = (int)((i / Cout) % Cin); const int t = (int)(i / ((size_t)Cout * Cin));
-        dst[i] = src[((size_t)ci * Cout + co) * T + t];
-    }
-}
-
-int launch_pack(const float* src, float* dst, int kind, int Cout, int Cin, int Cinp, int T, hipStream_t st, int x3bn) {
-    const size_t total = (size_t)T * Cout * (kind == PACK_CONV_FWD ? Cinp : Cin);
-    ELD_LAUNCH(pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, dst, kind, Cout, Cin, Cinp, T, x3bn);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
+template int launch_colsum<float>(const float*, float*, float*, size_t, int, hipStream_t);
+template int launch_colsum<bf16_t>(const bf16_t*, float*, float*, size_t, int, hipStream_t);
 
 // max |x| of a tensor into *slot (atomic max on the bit pattern; slot zeroed by the caller) -- operand bound of the two-piece
 // fp16 product scheme for tensors whose producer does not report it
@@ -513,10 +498,20 @@ int launch_absmax(const float* x, size_t n, float* slot, hipStream_t st) {
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// weight packing (tiny: 7.76 M parameters in total)
+//   PACK_CONV_FWD : dst[t][co][ci_p] = src[co][ci][t]        (zero for ci >= Cin)       src OIHW
+//   PACK_CONV_BWD : dst[t][ci][co]   = src[co][ci][T-1-t]    (flipped taps, transposed)
+//   PACK_CONVT_FWD: dst[tap*Cout+co][ci] = src[ci][co][tap]                              src (Cin,Cout,2,2)
+//   PACK_CONVT_BWD: dst[tap][ci][co]     = src[ci][co][tap]
+// ------------------------------------------------------------------------------------------------
 // ---- eight consecutive k-channels (c0 .. c0 + 7, c0 % 8 == 0) of one (tap, column) per thread: in every packed layout these are 16 contiguous bytes ----
 __device__ __forceinline__ uint4 bf8(const float (&v)[8]) { return make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7])); }
 __device__ __forceinline__ unsigned hi16_pair(float lo, float hi) { return (__float_as_uint(hi) & 0xFFFF0000u) | (__float_as_uint(lo) >> 16); }
-// x3_store for the eight values: the three pieces as three 16-byte stores
+// Pre-split slab layout of conv_x3d_kernel (conv_x3.hip): element (tap t, GEMM column n of N, k-channel c of K) of the logical packed
+// weight B[t][n][c] is cut EXACTLY into its three bf16 pieces (top 16 bits, top 16 bits of the exact remainder, exact rest -- the same
+// cut split_store makes) and stored at   slab(ky, c/16, n/BN) + row(kx, n%BN) * 112 B + piece * 32 B + (c%16) * 2 B.
+// The eight values' three pieces go out as three 16-byte stores.
 __device__ __forceinline__ void x3_store8(float* dst, int t, int n, int c0, int N, int K, int BN, const float (&v)[8]) {
     const int NCH = K >> 4, NB = N / BN;
     const int ky = t / 3, kx = t - 3 * ky;
@@ -532,6 +527,9 @@ __device__ __forceinline__ void x3_store8(float* dst, int t, int n, int c0, int 
     *reinterpret_cast<uint4*>(d + 16) = make_uint4(hi16_pair(r[0], r[1]), hi16_pair(r[2], r[3]), hi16_pair(r[4], r[5]), hi16_pair(r[6], r[7]));
     *reinterpret_cast<uint4*>(d + 32) = make_uint4(hi16_pair(q[0], q[1]), hi16_pair(q[2], q[3]), hi16_pair(q[4], q[5]), hi16_pair(q[6], q[7]));
 }
+// Slab layout of conv_bfd_kernel (conv_bfd.hip): element (tap t, GEMM column n of N, k-channel c of K) of the logical packed weight
+// B[t][n][c] as bf16 at   slab(ky, c/32, n/BN) + slot * 16 B + (c%8) * 2 B,   slot = 4 P + (octet ^ ((P >> 2) & 3)),  P = kx*BN + n%BN,
+// octet = (c%32)/8: the exact (XOR-swizzled) LDS image of a stage's slab, so it travels by linear 1 KiB LDS-DMA pieces.
 __device__ __forceinline__ void bfd_store8(float* dst, int t, int n, int c0, int N, int K, int BN, const float (&v)[8]) {
     const int NCH = K >> 5, NB = N / BN;
     const int ky = t / 3, kx = t - 3 * ky;
@@ -540,6 +538,8 @@ __device__ __forceinline__ void bfd_store8(float* dst, int t, int n, int c0, int
     const int slot = 4 * P + (o ^ ((P >> 2) & 3));
     reinterpret_cast<uint4*>(reinterpret_cast<char*>(dst) + slab * bfd_slab_bytes(BN))[slot] = bf8(v);
 }
+// Slab layout of conv_bfg_kernel (conv_bfg.hip): element (GEMM column n of N, k index c of K) of the logical packed weight B[n][c] as bf16 at
+//   slab(c/32, n/BN) + slot * 16 B + (c%8) * 2 B,   slot = 4 n' + (octet ^ ((n' >> 2) & 3)),  n' = n % BN, octet = (c%32)/8
 __device__ __forceinline__ void bfg_store8(float* dst, int n, int c0, int N, int K, int BN, const float (&v)[8]) {
     const int NB = N / BN, np = n % BN;
     const size_t slab = (size_t)(c0 >> 5) * NB + n / BN;
@@ -735,208 +735,6 @@ int launch_adam(float* p, const float* g, float* m, float* v, size_t n, double l
 }
 
 // ------------------------------------------------------------------------------------------------
-// bf16 activation variants of the streaming kernels (forward path): 4 channels = 8 bytes per lane access
-// ------------------------------------------------------------------------------------------------
-__global__ void maxpool_fwd_bf16_kernel(const bf16_t* __restrict__ in, bf16_t* __restrict__ out, int N, int Ho, int Wo, int C) {
-    const int C4 = C / 4;
-    const size_t total = (size_t)N * Ho * Wo * C4;
-    const int Wi = 2 * Wo;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c4 = (int)(i % C4);
-        size_t p = i / C4;
-        const int xo = (int)(p % Wo); p /= Wo;
-        const int yo = (int)(p % Ho);
-        const int n = (int)(p / Ho);
-        const uint2* src = reinterpret_cast<const uint2*>(in + (((size_t)n * 2 * Ho + 2 * yo) * Wi + 2 * xo) * C) + c4;
-        const float4 a = unpack_bf4(src[0]), b = unpack_bf4(src[C4]), c = unpack_bf4(src[(size_t)Wi * C4]), d = unpack_bf4(src[(size_t)Wi * C4 + C4]);
-        float4 r;
-        r.x = fmaxf(fmaxf(a.x, b.x), fmaxf(c.x, d.x));
-        r.y = fmaxf(fmaxf(a.y, b.y), fmaxf(c.y, d.y));
-        r.z = fmaxf(fmaxf(a.z, b.z), fmaxf(c.z, d.z));
-        r.w = fmaxf(fmaxf(a.w, b.w), fmaxf(c.w, d.w));
-        reinterpret_cast<uint2*>(out)[i] = pack_bf4(r);
-    }
-}
-
-int launch_maxpool_fwd_bf16(const bf16_t* in, bf16_t* out, int N, int Ho, int Wo, int C, hipStream_t st) {
-    const size_t total = (size_t)N * Ho * Wo * (C / 4);
-    if (!total) return 0;
-    ELD_LAUNCH(maxpool_fwd_bf16_kernel, dim3((unsigned)min((total + 255) / 256, (size_t)32768)), dim3(256), 0, st, in, out, N, Ho, Wo, C);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-int launch_head_fwd_bf16(const bf16_t* in, const float* w, const float* b, float* out, int N, int H, int W, int OC, hipStream_t st) {
-    if (OC > 4) return launch_head_wide_fwd(in, 1, w, b, out, N, H, W, OC, st);
-    const size_t total = (size_t)N * H * W;
-    if (!total) return 0;
-    ELD_LAUNCH(head_fwd_kernel<bf16_t>, dim3((unsigned)min((total + 63) / 64, (size_t)16384)), dim3(256), 0, st, in, w, b, out, N, (size_t)H * W, OC);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-// ---- backward pieces with bf16 activations / gradients (fp32 math, fp32 weight-gradient outputs) -----------------------
-__global__ void maxpool_bwd_bf16_kernel(const bf16_t* __restrict__ act, const bf16_t* __restrict__ dp, const bf16_t* __restrict__ skip,
-                                        bf16_t* __restrict__ g, int N, int Ho, int Wo, int C) {
-    const int C4 = C / 4;
-    const size_t total = (size_t)N * Ho * Wo * C4;
-    const int Wi = 2 * Wo;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c4 = (int)(i % C4);
-        size_t p = i / C4;
-        const int xo = (int)(p % Wo); p /= Wo;
-        const int yo = (int)(p % Ho);
-        const int n = (int)(p / Ho);
-        const size_t base = ((((size_t)n * 2 * Ho + 2 * yo) * Wi + 2 * xo) * C) / 4 + c4;
-        const size_t o1 = C4, o2 = (size_t)Wi * C4, o3 = o2 + C4;
-        const uint2* A = reinterpret_cast<const uint2*>(act);
-        const float4 a = unpack_bf4(A[base]), b = unpack_bf4(A[base + o1]), c = unpack_bf4(A[base + o2]), d = unpack_bf4(A[base + o3]);
-        const float4 gp = unpack_bf4(reinterpret_cast<const uint2*>(dp)[i]);
-        float4 sa = make_float4(0.f, 0.f, 0.f, 0.f), sb = sa, sc = sa, sd = sa;
-        if (skip) {
-            const uint2* S = reinterpret_cast<const uint2*>(skip);
-            sa = unpack_bf4(S[base]); sb = unpack_bf4(S[base + o1]); sc = unpack_bf4(S[base + o2]); sd = unpack_bf4(S[base + o3]);
-        }
-        float4 ga, gb, gc, gd;
-        POOL_BWD_1(x) POOL_BWD_1(y) POOL_BWD_1(z) POOL_BWD_1(w)
-        uint2* G = reinterpret_cast<uint2*>(g);
-        G[base] = pack_bf4(ga); G[base + o1] = pack_bf4(gb); G[base + o2] = pack_bf4(gc); G[base + o3] = pack_bf4(gd);
-    }
-}
-
-int launch_maxpool_bwd_bf16(const bf16_t* act, const bf16_t* dp, const bf16_t* skip, bf16_t* g, int N, int Ho, int Wo, int C, hipStream_t st) {
-    const size_t total = (size_t)N * Ho * Wo * (C / 4);
-    if (!total) return 0;
-    ELD_LAUNCH(maxpool_bwd_bf16_kernel, dim3((unsigned)min((total + 255) / 256, (size_t)32768)), dim3(256), 0, st, act, dp, skip, g, N, Ho, Wo, C);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-// bf16 head backward: FOUR lanes per pixel, eight channels (16 bytes) each -- a wave reads / writes 16 whole pixels = 1 KiB contiguous per
-// instruction (head_bwd_kernel<float>'s eight-lane layout at 8 bytes per lane measured slower than one thread per pixel).  The pixel's four
-// output gradients are read once (lane o of the quad reads plane o) and handed round with quad-permute DPP moves; a lane keeps
-// dW[o][its 8 channels] (32 sums) and db[its plane].
-__global__ __launch_bounds__(256) void head_bwd_bf16_kernel(const float* __restrict__ dout, const bf16_t* __restrict__ act, const float* __restrict__ w,
-                                                            bf16_t* __restrict__ g, float* __restrict__ part, int N, size_t HW, int OC) {
-    __shared__ float red[4][132];
-    const int tid = threadIdx.x, cq = tid & 3;
-    float wq[4][8];                                   // w[o][8cq + j]
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) wq[o][j] = o < OC ? w[o * 32 + 8 * cq + j] : 0.f;
-    float dw[4][8];
-    float db = 0.f;                                   // lane cq sums plane cq
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) dw[o][j] = 0.f;
-    const size_t total = (size_t)N * HW;
-    const size_t stride = (size_t)gridDim.x * 64;
-    size_t p = (size_t)blockIdx.x * 64 + (tid >> 2);
-    const size_t iters = (total + stride - 1) / stride;               // every lane of a quad runs the same trip count (DPP needs its quad mates)
-    for (size_t itn = 0; itn < iters; ++itn, p += stride) {
-        const bool ok = p < total;
-        const size_t pc = ok ? p : total - 1;
-        const size_t n = pc / HW, q = pc - n * HW;
-        float dl = 0.f;
-        if (ok && cq < OC) dl = dout[(n * OC + cq) * HW + q];
-        db += dl;
-        float d[4];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) d[o] = quad_bcast(dl, o);
-        if (!ok) continue;
-        const uint4 av4 = reinterpret_cast<const uint4*>(act + pc * 32)[cq];
-        const float4 alo = unpack_bf4(make_uint2(av4.x, av4.y)), ahi = unpack_bf4(make_uint2(av4.z, av4.w));
-        const float av[8] = {alo.x, alo.y, alo.z, alo.w, ahi.x, ahi.y, ahi.z, ahi.w};
-        float gv[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float sacc = 0.f;
-#pragma unroll
-            for (int o = 0; o < 4; ++o) { sacc = fmaf(wq[o][j], d[o], sacc); dw[o][j] = fmaf(d[o], av[j], dw[o][j]); }
-            gv[j] = sacc * lrelu_slope(av[j]);
-        }
-        const uint2 g0 = pack_bf4(make_float4(gv[0], gv[1], gv[2], gv[3])), g1 = pack_bf4(make_float4(gv[4], gv[5], gv[6], gv[7]));
-        reinterpret_cast<uint4*>(g + pc * 32)[cq] = make_uint4(g0.x, g0.y, g1.x, g1.y);
-    }
-    // block reduction in a fixed order: lanes sharing a channel octet (cq, cq+4, ...) by xor-shuffles, then the 4 waves through LDS
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int o = 0; o < 4; ++o)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v = dw[o][j];
-            for (int off = 4; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-            if (lane < 4) red[wave][o * 32 + 8 * lane + j] = v;
-        }
-    {
-        float v = db;
-        for (int off = 4; off < 64; off <<= 1) v += __shfl_xor(v, off, 64);
-        if (lane < 4) red[wave][128 + lane] = v;
-    }
-    __syncthreads();
-    if (tid < 132)
-        part[(size_t)blockIdx.x * 132 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
-}
-
-int launch_head_bwd_bf16(const float* dout, const bf16_t* act, const float* w, bf16_t* g, float* dw, float* db, float* part,
-                         int N, int H, int W, int OC, hipStream_t st) {
-    if (OC > 4) return launch_head_wide_bwd(dout, act, 1, w, g, dw, db, part, N, H, W, OC, st);
-    const size_t total = (size_t)N * H * W;
-    if (!total) return 0;
-    const int nb = (int)min((total + 63) / 64, (size_t)HEAD_BLOCKS);
-    ELD_LAUNCH(head_bwd_bf16_kernel, dim3(nb), dim3(256), 0, st, dout, act, w, g, part, N, (size_t)H * W, OC);
-    ELD_LAUNCH_CHECK();
-    ELD_LAUNCH(head_bwd_reduce_kernel, dim3((132 + 15) / 16), dim3(256), 0, st, part, dw, db, nb, OC);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-__global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restrict__ x, float* __restrict__ part, size_t P, int C) {
-    const int C4 = C / 4;
-    const int ppb = 256 / C4;
-    const int c4 = threadIdx.x % C4, pl = threadIdx.x / C4;
-    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (pl < ppb) {
-        const size_t step = (size_t)gridDim.x * ppb;
-        size_t p = (size_t)blockIdx.x * ppb + pl;
-        for (; p + 3 * step < P; p += 4 * step) {
-            const uint2 q0 = reinterpret_cast<const uint2*>(x + p * C)[c4], q1 = reinterpret_cast<const uint2*>(x + (p + step) * C)[c4];
-            const uint2 q2 = reinterpret_cast<const uint2*>(x + (p + 2 * step) * C)[c4], q3 = reinterpret_cast<const uint2*>(x + (p + 3 * step) * C)[c4];
-            const float4 v0 = unpack_bf4(q0), v1 = unpack_bf4(q1), v2 = unpack_bf4(q2), v3 = unpack_bf4(q3);
-            s.x += (v0.x + v1.x) + (v2.x + v3.x); s.y += (v0.y + v1.y) + (v2.y + v3.y);
-            s.z += (v0.z + v1.z) + (v2.z + v3.z); s.w += (v0.w + v1.w) + (v2.w + v3.w);
-        }
-        for (; p < P; p += step) {
-            const float4 v = unpack_bf4(reinterpret_cast<const uint2*>(x + p * C)[c4]);
-            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
-        }
-    }
-    __shared__ float4 sh[256];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x < C4) {
-        float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int k = 0; k < ppb; ++k) { const float4 v = sh[k * C4 + threadIdx.x]; t.x += v.x; t.y += v.y; t.z += v.z; t.w += v.w; }
-        reinterpret_cast<float4*>(part + (size_t)blockIdx.x * C)[threadIdx.x] = t;
-    }
-}
-
-int launch_colsum_bf16(const bf16_t* x, float* out, float* part, size_t P, int C, hipStream_t st) {
-    if (C % 4 || C > 512) return ELD_EINVAL;
-    const int ppb = 256 / (C / 4);
-    const int nb = (int)min((P + ppb - 1) / ppb, (size_t)COLSUM_BLOCKS);
-    if (nb == 0) return 0;
-    ELD_LAUNCH(colsum_bf16_kernel, dim3(nb), dim3(256), 0, st, x, part, P, C);
-    ELD_LAUNCH_CHECK();
-    ELD_LAUNCH(colsum_reduce_kernel, dim3((C + 63) / 64), dim3(1024), 0, st, part, out, nb, C);
-    ELD_LAUNCH_CHECK();
-    return 0;
-}
-
-
-// ------------------------------------------------------------------------------------------------
 // Fused training head: conv10_1 forward (Unet.py:46,88) + nn.L1Loss / nn.MSELoss (models/losses.py:30-34) + the head's backward in ONE pass over
 // conv9_2's output.  The three separate kernels read that 32-channel full-resolution tensor twice and move the output gradient through HBM
 // (head_fwd, l1_kernel, head_bwd: 1.34 ms per 8-frame bf16 step); here every pixel is read once:
@@ -952,7 +750,7 @@ template <typename T, int MSE>
 __global__ __launch_bounds__(256) void head_train_kernel(const T* __restrict__ act, const float* __restrict__ w, const float* __restrict__ b,
                                                          const float* __restrict__ tgt, float* __restrict__ out, T* __restrict__ g, float* __restrict__ part,
                                                          float* __restrict__ lpart, int N, size_t HW, int OC, float gscale) {
-    constexpr int CPL = sizeof(T) == 4 ? 4 : 8, LPP = 32 / CPL, PPB = 256 / LPP;      // channels per lane, lanes per pixel, pixels per block pass
+    constexpr int CPL = HeadGeom<T>::CPL, LPP = HeadGeom<T>::LPP, PPB = HeadGeom<T>::PPB;
     __shared__ float red[4][133];
     const int tid = threadIdx.x, cq = tid & (LPP - 1), o_ld = tid & 3;
     float wq[4][CPL];                                 // w[o][CPL cq + j]
@@ -992,22 +790,12 @@ __global__ __launch_bounds__(256) void head_train_kernel(const T* __restrict__ a
 #pragma unroll
         for (int o = 0; o < 4; ++o) d[o] = quad_bcast(dl, o);
         if (!ok) continue;
-        // backward
         float gv[CPL];
 #pragma unroll
-        for (int j = 0; j < CPL; ++j) {
-            float sacc = 0.f;
-#pragma unroll
-            for (int o = 0; o < 4; ++o) { sacc = fmaf(wq[o][j], d[o], sacc); dw[o][j] = fmaf(d[o], av[j], dw[o][j]); }
-            gv[j] = sacc * lrelu_slope(av[j]);
-        }
-        if constexpr (sizeof(T) == 4) reinterpret_cast<float4*>(g + pc * 32)[cq] = make_float4(gv[0], gv[1], gv[2], gv[3]);
-        else {
-            const uint2 g0 = pack_bf4(make_float4(gv[0], gv[1], gv[2], gv[3])), g1 = pack_bf4(make_float4(gv[4], gv[5], gv[6], gv[7]));
-            reinterpret_cast<uint4*>(g + pc * 32)[cq] = make_uint4(g0.x, g0.y, g1.x, g1.y);
-        }
+        for (int j = 0; j < CPL; ++j) gv[j] = head_bwd_ch<CPL>(d, av[j], wq, dw, j);
+        head_store_g(g, pc, cq, head_pack_g(gv));
     }
-    // block reduction in a fixed order: lanes sharing a channel group by xor-shuffles, then the 4 waves through LDS
+    // block reduction as in head_bwd_kernel, plus the loss sum of all lanes in slot 132 (written out in both: as a shared routine it reorders the db store)
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int o = 0; o < 4; ++o)
@@ -1031,7 +819,7 @@ __global__ __launch_bounds__(256) void head_train_kernel(const T* __restrict__ a
 }
 
 size_t head_train_ws_floats(int OC) { return OC > 4 ? head_wide_train_ws_floats(OC) : (size_t)HEAD_BLOCKS * 133; }
-static int head_train_blocks(size_t total, int bf16) { return (int)min((total + (bf16 ? 63 : 31)) / (bf16 ? 64 : 32), (size_t)HEAD_BLOCKS); }
+static int head_train_blocks(size_t total, int bf16) { return bf16 ? head_blocks<bf16_t>(total, HEAD_BLOCKS) : head_blocks<float>(total, HEAD_BLOCKS); }
 
 // part: head_train_ws_floats(OC) floats that must survive until launch_head_train_reduce (the backward) has run
 int launch_head_train(const void* act, int bf16, const float* w, const float* b, const float* tgt, float* out, void* g, float* part, float* loss,

@@ -303,6 +303,25 @@ def test_convt2x2_bf16(lib, ffam, bfam, N, H, W, Cin, Cout, wfam='wgrad<bf16,gat
     f32_check(dbias, yb, bb, 'convT db')
 
 
+def test_convt2x2_bias_gradient_by_column_sums_bf16(lib):
+    """Cout = 8 is below the weight-gradient kernel's 32-channel block, so the bias gradient is not formed inside that launch: it is the column-sum
+    kernel's own output (colsum_kernel<bf16>), which no case above reaches.  The gradients are multiples of 1/16 in [-1, 1] (exact in bf16) and
+    there are 64 pixels: every fp32 partial sum is exact in any order, so the result must be the float64 sum, bit for bit."""
+    N, H, W, Cin, Cout = 1, 4, 4, 32, 8
+    g = torch.Generator().manual_seed(7 * N * H * W + Cin)
+    gd = Guards()
+    x = rand_bf16((N, H, W, Cin), g)
+    d = (torch.randint(-16, 17, (N, 2 * H, 2 * W, Cout), generator=g).double() / 16).cuda()
+    assert bool((R.rne_bf16(d) == d).all())
+    xb, db16 = gd.ro(i16(R.bits_of(x)), 'x'), gd.ro(i16(R.bits_of(d)), 'd')
+    ws = ws_for(lib, gd, N, H, W, Cin, Cout)
+    dw = gd.new((Cin, Cout, 2, 2), name='dw')
+    dbias = gd.new((Cout,), name='dbias')
+    Lb().check(lib.eld_convt2x2_backward_weight_bf16(dp(xb), dp(db16), dp(dw), dp(dbias), N, H, W, Cin, Cout, dp(ws), ws.numel(), Lb().cur_stream()))
+    done(gd)
+    assert torch.equal(dbias.double(), d.sum((0, 1, 2)))
+
+
 # ---- pools ---------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize('N,Ho,Wo,C', [(2, 45, 77, 32), (3, 8, 13, 64), (1, 20, 33, 256)])
 def test_maxpool2x2_bf16_bit_exact(lib, N, Ho, Wo, C):

@@ -2,7 +2,10 @@
 """Compare the gfx950 device assembly of two builds of one .hip file, kernel by kernel (dev tool; the method of profiles/r07_prune_notes.md section 2).
 
     hipcc <the build's flags> --cuda-device-only -S old/conv_bfd.hip -o old.s      (same for new.s)
-    tools/asm_compare.py old.s new.s [--md] [--diff]
+    tools/asm_compare.py old.s new.s [--md] [--diff] [--rename OLD=NEW ...]
+
+--rename pairs a kernel of the old file with one of another name in the new file, both as the table prints them (demangled, without "void " and the
+parameter list), e.g.  --rename 'colsum_bf16_kernel=colsum_kernel<unsigned short>'  after a kernel became a template instantiation.
 
 Per kernel: the lines between the kernel's label and its .Lfunc_end, comments and .loc-style directives dropped, .LBBn_m -> .LBB_m, mangled names -> one
 token; compared as text.  Registers, spills, scratch and static LDS come from the amdhsa.kernels metadata.  It compares two texts and knows no instruction.
@@ -45,7 +48,7 @@ def kernels(path):
             if ln.startswith('.Lfunc_end'):
                 break
             ln = re.sub(r'\s*;.*$', '', ln).strip()
-            if not ln or re.match(r'\.(loc|file|cfi_|p2align|section|type|size)\b', ln):
+            if not ln or re.match(r'\.(loc|file|cfi_|p2align|section|type|size)\b|\.text$', ln):
                 continue
             ln = re.sub(r'\.LBB\d+_(\d+)', r'.LBB_\1', ln)
             ln = re.sub(r'_Z[A-Za-z0-9_]+', 'SYM', ln)
@@ -54,16 +57,39 @@ def kernels(path):
     return out
 
 
+def by_pretty(ks):
+    """The kernels of one file keyed by the name the table prints; overloads that would share it keep their parameter lists."""
+    full = demangle(sorted(ks))
+    short = {n: re.sub(r'^void |\([^()]*\)$', '', full[n].replace('(anonymous namespace)::', '')) for n in ks}
+    twice = {v for v in short.values() if list(short.values()).count(v) > 1}
+    return {(full[n] if short[n] in twice else short[n]): ks[n] for n in ks}
+
+
 def main():
-    args = [a for a in sys.argv[1:] if not a.startswith('--')]
-    md, show = '--md' in sys.argv, '--diff' in sys.argv
+    argv, renames = [], {}
+    it = iter(sys.argv[1:])
+    for a in it:
+        if a == '--rename' or a.startswith('--rename='):
+            o, _, n = (next(it, '') if a == '--rename' else a[9:]).partition('=')
+            if not o or not n:
+                sys.exit(__doc__)
+            renames[o] = n
+        else:
+            argv.append(a)
+    args = [a for a in argv if not a.startswith('--')]
+    md, show = '--md' in argv, '--diff' in argv
     if len(args) != 2:
         sys.exit(__doc__)
-    old, new = kernels(args[0]), kernels(args[1])
-    names = demangle(sorted(set(old) | set(new)))
+    old, new = by_pretty(kernels(args[0])), by_pretty(kernels(args[1]))
+    missing = [o for o in renames if o not in old]
+    if missing:
+        sys.exit('--rename: not in %s: %s' % (args[0], ', '.join(missing)))
+    old = {renames.get(k, k): v for k, v in old.items()}
+    was = {v: k for k, v in renames.items()}
+    names = sorted(set(old) | set(new))
     bad = 0
-    for n in sorted(names, key=lambda k: names[k]):
-        pretty = re.sub(r'^void |\([^()]*\)$', '', names[n].replace('(anonymous namespace)::', ''))
+    for n in names:
+        pretty = n + (' (was %s)' % was[n] if n in was else '')
         if n not in old or n not in new:
             print('%s: only in %s' % (pretty, 'new' if n in new else 'old'))
             bad += 1

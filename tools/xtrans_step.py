@@ -63,7 +63,7 @@ def head_kind(name):
     import re
     if 'reduce' in name or 'loss' in name:
         return None, None
-    bf16 = 'unsigned short' in name or 'ItL' in name or 'IDF16' in name or 'bf16' in name
+    bf16 = 'unsigned short' in name or 'ItL' in name or 'ItE' in name or 'IDF16' in name      # every head kernel is a template on the element: <unsigned short> / It..E
     m = re.search(r'head_wide_kernel<[^,]+, *\d+, *(\d)>', name) or re.search(r'head_wide_kernel\w*?Li\d+ELi(\d)E', name)
     if m:
         return (2 if bf16 else 4), {'0': 'fwd', '3': 'bwd'}.get(m.group(1), 'train')
