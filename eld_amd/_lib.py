@@ -45,6 +45,11 @@ assert DNG_STREAM_DTYPE.itemsize == 64 and DNG_HUFF_DTYPE.itemsize == 1196
 DNG_ENC_CHUNK_DTYPE = np.dtype([('src', '<u4'), ('nbytes', '<u4'), ('dst', '<u4'), ('reserved', '<u4')])
 DNG_ENC_SEGMENT, DNG_ENC_MIN_SEGMENT, DNG_ENC_MAX_SEGMENT = 2048, 64, 8192
 DNG_ENC_CHUNK, DNG_ENC_MIN_CHUNK, DNG_ENC_MAX_CHUNK = 4096, 16, 4096
+# struct EldDngOp (104 bytes): one operation record of a compiled opcode program (eld_amd/dng_opcodes.py); the limits of a program
+DNG_OP_DTYPE = np.dtype([('kind', '<i4'), ('top', '<i4'), ('left', '<i4'), ('bottom', '<i4'), ('right', '<i4'), ('row_pitch', '<i4'),
+                         ('col_pitch', '<i4'), ('n0', '<i4'), ('n1', '<i4'), ('data_off', '<u4'), ('reserved', '<u4', (2,)), ('p', '<f8', (7,))])
+assert DNG_OP_DTYPE.itemsize == 104
+DNG_MAX_OPS, DNG_MAX_BLOB = 32, 64 << 20
 DNG_STATUS = {0: 'ok', 1: 'truncated: the data ended before the last sample', 2: 'invalid code: bits that are no code of the Huffman table',
               3: 'too many samples: the stream holds more samples than its tile', 4: 'bad record: a field out of range'}
 
@@ -184,6 +189,8 @@ SIGNATURES = {
     'eld_dng_enc_pack_u16': (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     'eld_dng_enc_ffcount_u8': (_i, [_vp, _sz, _vp, _i, _i, _vp, _vp]),
     'eld_dng_enc_stuff_u8': (_i, [_vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    'eld_dng_opcodes_apply_f32': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
+    'eld_dng_opcodes_gain_f32': (_i, [_vp, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
 }
 
 

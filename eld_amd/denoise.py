@@ -392,6 +392,9 @@ def build_parser():
     p.add_argument('--iso', type=float, help='the ISO the frames were shot at (the abscissa of --shading)')
     p.add_argument('--flatfield', metavar='FILE', help='a flat-field map written by eld_amd.flatfield (.npz): PRNU in the input stage, lens gain on the output')
     p.add_argument('--lens', choices=LENS_MODES, help="where the lens plane of --flatfield applies: the sRGB rendering ('srgb', the default), the written-back mosaic too ('all'), nowhere ('off')")
+    p.add_argument('--opcodes', choices=('ignore', 'apply'), default='ignore',
+                   help="the OpcodeList tags of .dng inputs: 'ignore' (the default), or 'apply': list 1's bad pixels join --defects, the gain "
+                        'opcodes of lists 2 and 3 become the lens plane --lens places (not together with --flatfield)')
     p.add_argument('--dng', action='store_true', help='also write <name>_denoised.dng (uncompressed 16-bit unless --dng-compression says otherwise; the tags of a .dng input are copied)')
     p.add_argument('--dng-compression', choices=('none', 'ljpeg'), default='none', help="of --dng: 'none' (uncompressed strips, the default) or 'ljpeg' (lossless-JPEG tiles, encoded on the device)")
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
@@ -450,7 +453,11 @@ def options_from(a):
         raise ValueError('--shading needs --iso')
     if o.get('lens') is not None and o['lens'] not in LENS_MODES:
         raise ValueError('lens must be one of %r, got %r' % (LENS_MODES, o['lens']))
-    if o.get('lens') is not None and o.get('flatfield') is None:
+    if getattr(a, 'opcodes', 'ignore') == 'apply':
+        o['opcodes'] = 'apply'
+        if o.get('flatfield') is not None:
+            raise ValueError('--opcodes apply together with --flatfield would correct the lens twice: give one of them')
+    if o.get('lens') is not None and o.get('flatfield') is None and o.get('opcodes') != 'apply':
         raise ValueError('--lens needs --flatfield')
     return a.inputs, a.out, a.ckpt, o
 
@@ -470,6 +477,48 @@ def main(argv=None):
     return run_frames(den, inputs, outdir, o)
 
 
+def opcode_options(path, raw, kw, o):
+    """--opcodes apply for one .dng input: denoise_raw's keywords with the file's own corrections in them, and the opcode tags --dng carries
+    into the written file.  List 1's bad pixels are OR-ed into the --defects map; the gain opcodes of lists 2 and 3 become a FlatField whose
+    lens plane goes where --flatfield's would, under --lens (default 'srgb').  A list-2 opcode that is no gain (MapTable, MapPolynomial,
+    DeltaPerRow, DeltaPerColumn) would change the network's input and is not applied there: mandatory, it is a ValueError that names it.
+    Carried: lists 2 and 3 as the source has them -- with lens='all', where the gains are already in the written mosaic, without their gain
+    opcodes; never list 1 (its pixels are repaired, and the written mosaic is the active area only)."""
+    from . import dng_opcodes as O
+    from .dng import dng_meta, is_dng
+    if not is_dng(path):
+        raise ValueError('%s: --opcodes apply reads the opcode lists of .dng inputs' % path)
+    lists, meta = O.read_opcodes(path), dng_meta(path)
+    Hm, Wm = (int(v) for v in raw.shape[-2:])
+    kw = dict(kw)
+    dmap = O.defects_from_opcodes(lists[0], raw, meta, lists.linearization)
+    if dmap.count:
+        kw['defects'] = O.merge_defects(kw.get('defects'), dmap)
+    for i, op in enumerate(lists[1]):
+        if O.disposition(op, 2) == 'apply' and op.id in O.NOT_GAIN_IDS_2:
+            if not op.optional:
+                raise ValueError('%s: OpcodeList2[%d] %s is mandatory and changes the pixel values in front of the network: it is not applied '
+                                 'there (python -m eld_amd.dng --opcodes apply --linear-out applies it)' % (path, i, op.name))
+            print('%s: OpcodeList2[%d] %s skipped because optional' % (path, i, op.name))
+    lens = o.get('lens') or 'srgb'
+    prog = O.gain_program(lists[1], lists[2], Hm, Wm)
+    if len(prog):
+        pattern = o.get('raw_pattern') if o['cfa'] == 'bayer' else meta['raw_pattern']
+        kw['flatfield'] = O.lens_from_opcodes(lists[1], lists[2], Hm, Wm, o['cfa'], pattern, min(int(o['white_point']), 65535))
+        kw['lens'] = lens
+    carried = {}
+    for no, name in ((2, 'OpcodeList2'), (3, 'OpcodeList3')):
+        if name not in lists.raw:
+            continue
+        if lens == 'all':
+            rest = O.without_gains(lists[no - 1], no)
+            if rest:
+                carried[name] = O.pack_opcode_list(rest)
+        else:
+            carried[name] = lists.raw[name]
+    return kw, carried
+
+
 def run_frames(den, inputs, outdir, o):
     """The command line's loop: denoise every input with `den` (a Denoiser or a ClassicalDenoiser) under the options `o`, write the outputs."""
     os.makedirs(outdir, exist_ok=True)
@@ -484,7 +533,10 @@ def run_frames(den, inputs, outdir, o):
     dng_kw = {'compression': COMPRESSION_CHOICES[o.get('dng_compression') or 'none']}
     for path in inputs:
         raw = load_frame(path)
-        res = denoise_raw(den, raw, o['cfa'], **kw)
+        fkw, carried = kw, None
+        if o.get('opcodes') == 'apply':
+            fkw, carried = opcode_options(path, raw, kw, o)
+        res = denoise_raw(den, raw, o['cfa'], **fkw)
         name = os.path.splitext(os.path.basename(path))[0]
         np.save(os.path.join(outdir, name + '_denoised.npy'), res['mosaic'])
         line = '%s -> %s_denoised.npy' % (path, name)
@@ -492,7 +544,7 @@ def run_frames(den, inputs, outdir, o):
             if raw.ndim != 2:
                 raise ValueError('%s: --dng writes one frame per file, the input holds a stack of %d' % (path, raw.shape[0]))
             if is_dng(path):
-                write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'], like=path, **dng_kw)
+                write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'], like=path, opcodes=carried, **dng_kw)
             else:
                 write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'],
                           meta={k: o.get(k) for k in ('cfa', 'raw_pattern', 'black_level', 'white_point', 'wb', 'ccm', 'iso')}, **dng_kw)

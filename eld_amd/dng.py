@@ -5,10 +5,11 @@ ITU-T T.81): there is no rawpy here.
     read_dng(path, device=None) -> (mosaic, meta)   the visible mosaic as rawpy's raw_image_visible would give it
     dng_meta(path)                                  the tags only, in the sidecar's keys (eld_amd.denoise.SIDECAR_KEYS)
     load_frame(path)                                .npy -> np.load(path); .dng -> read_dng(path)[0]
-    write_dng(path, mosaic, meta=None, like=None)   an uncompressed 16-bit little-endian DNG, one IFD, strips; compression=7: lossless-JPEG
+    write_dng(path, mosaic, meta=None, like=None, opcodes=None)   an uncompressed 16-bit little-endian DNG, one IFD, strips; compression=7: lossless-JPEG
                                                     tiles, encoded on the device (eld_dng_enc_*)
     encode_ljpeg(mosaic, tile, bits)                the JPEG streams of the tiles alone, for callers with a container of their own
     python -m eld_amd.dng in.dng [-o frame.npy | -o out.dng [--compression ljpeg] [--tile TH TW] [--bits N]] [--meta-out sensor.json]
+                          [--opcodes apply [--flatfield-out lens.npz] [--defects-out defects.npz] [--linear-out stage2.npy]]
 
 Container.  Classic TIFF in both byte orders.  The raw image is the IFD with NewSubFileType = 0 and PhotometricInterpretation = 32803
 (CFA), looked for in IFD0 and in its SubIFDs (tag 330); SamplesPerPixel = 1; strips or tiles; Compression 1 (8, 10, 12, 14 or 16 bits, rows
@@ -34,7 +35,8 @@ Metadata mapping (tag -> key):
     ISOSpeedRatings,      iso, exposure_time: from the Exif IFD (tag 34665), or from IFD0 where they sit there
     ExposureTime
     Make, Model           make, model
-    OpcodeList1/2/3       not applied; the lists present are named in meta['opcodes']
+    OpcodeList1/2/3       not applied by read_dng; the lists present are named in meta['opcodes'].  eld_amd.dng_opcodes parses them and turns
+                          them into a DefectMap and a lens FlatField (--opcodes apply here and in eld_amd.denoise / eld_amd.classical)
 and bits (BitsPerSample), compression, active_area.
 
 Nothing touches a device before the arguments and the file have been validated."""
@@ -889,14 +891,21 @@ def encode_ljpeg(mosaic, tile=DEFAULT_TILE, bits=16, segment=0, chunk=0):
     return e.streams()
 
 
-def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compression=1, tile=None, bits=None):
+def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compression=1, tile=None, bits=None, opcodes=None):
     """Write `mosaic` ((H, W) uint16 codes, NumPy or a CUDA int16-view tensor) as a little-endian DNG with one IFD.  compression 1 (the
     default): uncompressed 16-bit strips.  compression 7: lossless-JPEG tiles of `tile` (TileLength, TileWidth; default 256 x 256) at `bits`
     (8..16, default 16) precision, encoded on the device (encode_ljpeg): a NumPy mosaic is uploaded, a device tensor is used where it is.
     like: a source DNG whose CFA, level, colour, neutral, make / model, ISO and exposure tags are copied with their original
     values (rationals stay the rationals they were; the mosaic is taken to be the source's visible mosaic, so no ActiveArea and no
     LinearizationTable are written).  meta: sidecar keys (cfa, raw_pattern, black_level, white_point, wb, ccm, iso, exposure_time, make, model);
-    its tags are written from those values (ColorMatrix1 with CalibrationIlluminant1 = 21) and override what `like` gave."""
+    its tags are written from those values (ColorMatrix1 with CalibrationIlluminant1 = 21) and override what `like` gave.
+    opcodes: {'OpcodeList1' | 'OpcodeList2' | 'OpcodeList3': bytes}, written as given (like= copies no opcode tag)."""
+    op_tags = {}
+    for name, data in (opcodes or {}).items():
+        tag = {n: t for t, n in OPCODE_TAGS}.get(name)
+        if tag is None or not isinstance(data, (bytes, bytearray)) or len(data) < 4:
+            raise ValueError('opcodes takes {tag name: bytes} with the names %s, got %r' % (', '.join(n for _, n in OPCODE_TAGS), name))
+        op_tags[tag] = bytes(data)
     if compression not in (1, 7):
         raise ValueError('compression = %r: write_dng writes 1 (uncompressed) and 7 (lossless JPEG)' % (compression,))
     if compression == 7:
@@ -990,6 +999,8 @@ def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compressi
             tags[tag] = Entry(tag, ASCII, 0, str(m[key]))
     if T_CFADIM not in tags:
         raise ValueError('write_dng needs a CFA pattern: meta with cfa / raw_pattern, or like= a DNG')
+    for tag, data in op_tags.items():
+        tags[tag] = Entry(tag, UNDEFINED, len(data), data)
     put(T_NEWSUBFILETYPE, LONG, (0,))
     put(T_WIDTH, LONG, (W,))
     put(T_LENGTH, LONG, (H,))
@@ -1059,6 +1070,43 @@ def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compressi
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
+def _apply_opcodes(a, mosaic, meta):
+    """--opcodes apply: list 1's bad pixels repaired in `mosaic` (the project's own repair), the maps and the stage-2 image written where asked.
+    -> (the repaired mosaic, one line per opcode, the tags of lists 2 and 3 for a .dng output: list 1 is applied, they are still to do)"""
+    from . import dng_opcodes as O
+    from .defects import repair
+    lists = O.read_opcodes(a.input)
+    Hm, Wm = (int(v) for v in mosaic.shape)
+    dmap = O.defects_from_opcodes(lists[0], mosaic, meta, lists.linearization)
+    if dmap.count:
+        mosaic = repair(mosaic, dmap)
+    lines = []
+    for no, ops in enumerate(lists, 1):
+        for i, op in enumerate(ops):
+            d = O.disposition(op, no, lists.linearization)
+            if d == 'never':
+                what = 'never applied (warps and TrimBounds stay with the raw converter)'
+            elif d == 'skip':
+                what = 'skipped because optional (not supported in this list)'
+            elif no == 1:
+                what = 'applied: its sites are repaired (%d sites in all)' % dmap.count
+            elif no == 3 or op.id in O.GAIN_IDS_2:
+                what = 'folded into the lens plane' + ('' if a.flatfield_out else ' (--flatfield-out writes it)')
+            else:
+                what = 'applied in --linear-out' if a.linear_out else 'not applied: it changes the pixel values in front of the network (--linear-out applies it)'
+            lines.append('%s: OpcodeList%d[%d] %s: %s' % (a.input, no, i, op.name, what))
+    if a.defects_out:
+        lines.append('%s -> %s (%d defective sites)' % (a.input, dmap.save(a.defects_out), dmap.count))
+    if a.flatfield_out:
+        ff = O.lens_from_opcodes(lists[1], lists[2], Hm, Wm, meta['cfa'], meta['raw_pattern'], min(int(meta['white_point']), 65535))
+        lines.append('%s -> %s (lens gain %.4g .. %.4g)' % (a.input, ff.save(a.flatfield_out), float(ff.lens.min()), float(ff.lens.max())))
+    if a.linear_out:
+        lin = O.apply_list2(O.normalise(mosaic, meta), O.OpcodeProgram(lists[1], Hm, Wm))
+        np.save(a.linear_out, lin.cpu().numpy())
+        lines.append('%s -> %s (float32 stage 2)' % (a.input, a.linear_out))
+    return mosaic, lines, {k: v for k, v in lists.raw.items() if k != 'OpcodeList1'}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog='python -m eld_amd.dng', description='Convert a DNG to a uint16 mosaic (.npy) and a JSON sidecar.')
     ap.add_argument('input', help='a DNG file')
@@ -1069,21 +1117,38 @@ def main(argv=None):
                                                                                                'lossless-JPEG tiles (default: none)')
     ap.add_argument('--tile', type=int, nargs=2, metavar=('TH', 'TW'), help='TileLength TileWidth of --compression ljpeg (default 256 256)')
     ap.add_argument('--bits', type=int, help='the precision of --compression ljpeg, 8..16 (default 16)')
+    ap.add_argument('--opcodes', choices=('report', 'apply'), default='report',
+                    help="OpcodeList1/2/3: 'report' names the lists present (the default); 'apply' repairs list 1's bad pixels in the -o output and "
+                         'says what becomes of every opcode')
+    ap.add_argument('--flatfield-out', metavar='FILE', help='with --opcodes apply: the gain opcodes of lists 2 and 3 as a flat-field map (.npz) whose '
+                                                            'lens plane they fill, for --flatfield')
+    ap.add_argument('--defects-out', metavar='FILE', help="with --opcodes apply: list 1's bad pixels as a defect map (.npz), for --defects")
+    ap.add_argument('--linear-out', metavar='FILE', help='with --opcodes apply: the float32 stage-2 image (.npy): black / white normalisation, then '
+                                                         'every list-2 opcode')
     a = ap.parse_args(sys.argv[1:] if argv is None else argv)
+    if (a.flatfield_out or a.defects_out or a.linear_out) and a.opcodes != 'apply':
+        ap.error('--flatfield-out, --defects-out and --linear-out belong to --opcodes apply')
     if (a.tile or a.bits) and a.compression != 'ljpeg':
         ap.error('--tile and --bits belong to --compression ljpeg')
     if a.compression == 'ljpeg' and not is_dng(a.out):
         ap.error('--compression ljpeg needs an -o that ends in .dng')
     out = a.out or os.path.splitext(a.input)[0] + '.npy'
+    lines, carried = [], None
     if is_dng(out):
         mosaic, meta = read_dng(a.input, device='cuda')
+        if a.opcodes == 'apply':
+            mosaic, lines, carried = _apply_opcodes(a, mosaic, meta)
         kw = dict(compression=7, tile=a.tile and tuple(a.tile), bits=a.bits) if a.compression == 'ljpeg' else {}
-        write_dng(out, mosaic, like=a.input, **kw)
+        write_dng(out, mosaic, like=a.input, opcodes=carried, **kw)
     else:
         mosaic, meta = read_dng(a.input)
+        if a.opcodes == 'apply':
+            mosaic, lines, _ = _apply_opcodes(a, mosaic, meta)
         np.save(out, mosaic)
     print('%s -> %s (%d x %d, %s, %d bits, compression %d)' % (a.input, out, mosaic.shape[0], mosaic.shape[1], meta['cfa'], meta['bits'], meta['compression']))
-    if meta['opcodes']:
+    for line in lines:
+        print(line)
+    if meta['opcodes'] and a.opcodes == 'report':
         print('%s: %s present and not applied (gain maps, defect lists and warps stay with the raw converter)' % (a.input, ', '.join(meta['opcodes'])))
     if a.meta_out:
         from .denoise import SIDECAR_KEYS

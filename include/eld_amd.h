@@ -1047,6 +1047,56 @@ int eld_dng_enc_ffcount_u8(const uint8_t* raw, size_t raw_bytes, const EldDngEnc
 int eld_dng_enc_stuff_u8(const uint8_t* raw, size_t raw_bytes, const EldDngEncChunk* chunks, int nchunks, int chunk, const uint32_t* ffbefore,
                          uint8_t* out, size_t out_bytes, void* stream);
 
+/* ---- DNG opcode lists: the mosaic-domain opcodes per site (csrc/dng_opcodes.hip, csrc/dng_opcodes_dev.h, eld_amd/dng_opcodes.py) ----
+ * Appended without a change of ELD_ABI_VERSION: two new symbols, no existing call changed.  A program is at most ELD_DNG_MAX_OPS operation
+ * records in HOST memory (they are validated here and travel as kernel arguments) and one parameter blob of at most ELD_DNG_MAX_BLOB bytes in
+ * DEVICE memory, 8-byte aligned.  A record's area is already clipped to the Hm x Wm image (0 <= top < bottom <= Hm, 0 <= left < right <= Wm),
+ * its pitches are >= 1, and data_off (a multiple of 4) is where its parameters start in the blob:
+ *   MAPTABLE     n0 = table size 1..65536; n0 uint16.               out = float32(table[min(rint(v * 65535), n0 - 1)]) / 65535
+ *   MAPPOLY      n0 = degree 0..8; n0 + 1 float32 c0..cn.           out = clip(Horner from cn, product and sum rounded apart)
+ *   GAINMAP      n0 x n1 map points (plane 0 of the file's map), n0 * n1 <= 2^24; n0 * n1 float32, row-major.  p[0..3] = MapSpacingV,
+ *                MapSpacingH, MapOriginV, MapOriginH.             out = clip(v * bilinear gain)
+ *   DELTAPERROW / DELTAPERCOL / SCALEPERROW / SCALEPERCOL   n0 = entries; n0 float32; the area's last addressed line must index below n0.
+ *                                                                  out = clip(v + d[k]) resp. clip(v * s[k]), k = (y - top) / row_pitch
+ *   VIGNETTE     (gain entry point only) p[0..4] = k0..k4, p[5], p[6] = the centre cx, cy in relative coordinates; no blob data.
+ * A site (y, x) is addressed when top <= y < bottom, (y - top) % row_pitch == 0, and likewise in x.  clip is to [0, 1].  The arithmetic -- the
+ * float64 map coordinate at pixel centres, the order and rounding of every float32 operation -- is the contract of DESIGN.md sec. 29, restated
+ * by tests/dng_opcodes_ref.py bit for bit.
+ *   eld_dng_opcodes_apply_f32   out[n][y][x] = the program run in record order on in[n][y][x]; one pass, 4 B read and 4 B written per site.
+ *                               in == out (in place) or no overlap.  A NaN site passes through unchanged.  VIGNETTE is ELD_EINVAL here.
+ *   eld_dng_opcodes_gain_f32    out[y][x] = the float32 product, in record order from 1, of the factors of the GAINMAP, SCALEPERROW,
+ *                               SCALEPERCOL and VIGNETTE records that address the site; unclipped; any other kind is ELD_EINVAL.
+ * map_lds_bytes: how many bytes of GAINMAP gains the kernel may copy into LDS (taken in record order while they fit; the rest is read from
+ * the blob); < 0: the default, 32 KiB; at most 64 KiB.  The result does not depend on it.
+ * ELD_EINVAL before any device work: a null or misaligned pointer (float32 arrays 4-byte, the blob 8-byte); N < 0 or > 65535; Hm, Wm < 1 or
+ * Hm * Wm >= 2^31; nops outside [0, ELD_DNG_MAX_OPS]; blob_bytes > ELD_DNG_MAX_BLOB; in and out overlapping without being equal; any record
+ * that fails the checks above or points beyond the blob.  N == 0 is a successful no-op; nops == 0 copies resp. writes 1. */
+#define ELD_DNG_MAX_OPS 32
+#define ELD_DNG_MAX_BLOB (64u << 20)
+#define ELD_DNG_OP_VIGNETTE 3
+#define ELD_DNG_OP_MAPTABLE 7
+#define ELD_DNG_OP_MAPPOLY 8
+#define ELD_DNG_OP_GAINMAP 9
+#define ELD_DNG_OP_DELTAPERROW 10
+#define ELD_DNG_OP_DELTAPERCOL 11
+#define ELD_DNG_OP_SCALEPERROW 12
+#define ELD_DNG_OP_SCALEPERCOL 13
+
+typedef struct EldDngOp {          /* 104 bytes */
+    int32_t kind;                  /* ELD_DNG_OP_*: the DNG opcode id */
+    int32_t top, left, bottom, right;  /* the area, clipped to the image */
+    int32_t row_pitch, col_pitch;
+    int32_t n0, n1;                /* see above; n1: GAINMAP only */
+    uint32_t data_off;             /* byte offset of the parameters in the blob, a multiple of 4 */
+    uint32_t reserved[2];
+    double p[7];                   /* GAINMAP: spacing V, H, origin V, H; VIGNETTE: k0..k4, cx, cy */
+} EldDngOp;
+
+int eld_dng_opcodes_apply_f32(const float* in, float* out, int N, int Hm, int Wm, const EldDngOp* ops, int nops, const uint8_t* blob,
+                              size_t blob_bytes, int map_lds_bytes, void* stream);
+int eld_dng_opcodes_gain_f32(float* out, int Hm, int Wm, const EldDngOp* ops, int nops, const uint8_t* blob, size_t blob_bytes,
+                             int map_lds_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
