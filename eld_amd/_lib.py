@@ -50,6 +50,10 @@ DNG_OP_DTYPE = np.dtype([('kind', '<i4'), ('top', '<i4'), ('left', '<i4'), ('bot
                          ('col_pitch', '<i4'), ('n0', '<i4'), ('n1', '<i4'), ('data_off', '<u4'), ('reserved', '<u4', (2,)), ('p', '<f8', (7,))])
 assert DNG_OP_DTYPE.itemsize == 104
 DNG_MAX_OPS, DNG_MAX_BLOB = 32, 64 << 20
+# struct EldWarp (184 bytes): DNG WarpRectilinear for eld_warp_rgb_f32 (eld_amd/dng_opcodes.py Warp.record); k holds kr0 - 1 in place of kr0
+WARP_DTYPE = np.dtype([('nsets', '<i4'), ('reserved', '<i4'), ('k', '<f8', (3, 6)), ('cxp', '<f8'), ('cyp', '<f8'), ('m', '<f8'), ('m2', '<f8')])
+assert WARP_DTYPE.itemsize == 184
+WARP_MAX_LDS = 64 << 10
 DNG_STATUS = {0: 'ok', 1: 'truncated: the data ended before the last sample', 2: 'invalid code: bits that are no code of the Huffman table',
               3: 'too many samples: the stream holds more samples than its tile', 4: 'bad record: a field out of range'}
 
@@ -191,6 +195,7 @@ SIGNATURES = {
     'eld_dng_enc_stuff_u8': (_i, [_vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     'eld_dng_opcodes_apply_f32': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
     'eld_dng_opcodes_gain_f32': (_i, [_vp, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
+    'eld_warp_rgb_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp]),
 }
 
 

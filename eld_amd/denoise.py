@@ -35,7 +35,7 @@ import numpy as np
 from . import _lib as L
 from .defects import as_defect_map, repair_device
 from .flatfield import LENS_MODES, as_flat_field
-from .isp import process, process_xtrans, render_bayer, render_xtrans
+from .isp import process, process_xtrans, render_bayer, render_xtrans, warp_rgb
 from .mosaic import (DEFAULT_BLACK, DEFAULT_PATTERN, PLANES, as_u16 as _as_u16, check_cfa as _check_cfa,  # noqa: F401 (the names this module always had)
                      check_sides as _check_sides, levels as _levels)
 from .shading import as_dark_shading
@@ -195,7 +195,7 @@ def run_network(denoiser, x, chop=None):
 
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
                 chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None, shading=None, iso=None, flatfield=None,
-                lens='srgb'):
+                lens='srgb', warp=None):
     """Denoise uint16 sensor mosaics with a trained U-Net -- or, given an eld_amd.classical.ClassicalDenoiser in place of a Denoiser, with the
     classical baseline (Anscombe transform, non-local means, unbiased inverse on the sensor's codes instead of the input stage and the
     network; `chop` is then ignored, and 'packed' is the baseline's output in the network's convention).
@@ -226,6 +226,10 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                 stages apply: lens='srgb' (default) in the sRGB rendering only -- the mosaic written back stays a raw frame a converter
                 may still lens-correct; 'all' in the write-back too; 'off' nowhere.  'packed' is the network's own output in every mode.
 
+    warp        an eld_amd.dng_opcodes.Warp (a DNG WarpRectilinear: lens distortion and lateral chromatic aberration), with srgb_size='full'
+                only: the demosaiced camera RGB is resampled by it before the colour matrix and the tone curve (eld_amd.isp.warp_rgb), in
+                'srgb' and in 'linear'.  The mosaic written back is not warped: it stays a raw frame.
+
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
     _check_cfa(cfa)
@@ -241,6 +245,12 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         raise ValueError("srgb_size='full' renders sRGB: it needs both wb and ccm")
     if linear and srgb_size != 'full':
         raise ValueError("linear=True needs srgb_size='full'")
+    if warp is not None:
+        from .dng_opcodes import Warp
+        if not isinstance(warp, Warp):
+            raise ValueError('warp must be an eld_amd.dng_opcodes.Warp, got %r' % (type(warp).__name__,))
+        if srgb_size != 'full':
+            raise ValueError("warp resamples the full-resolution render: it needs srgb_size='full'")
     kind, batched = _as_u16(mosaic_u16)
     shape = tuple(mosaic_u16.shape)
     N = shape[0] if batched else 1
@@ -313,11 +323,16 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     if wbs is not None and srgb_size == 'full':
         wt, ct = torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev)
         if cfa == 'bayer':
-            srgb = render_bayer(out, pat, wt, ct, CRF=CRF)
-            lin = render_bayer(out, pat, wt, ct, linear=True) if linear else None
+            render = lambda c, **kw: render_bayer(out, pat, wt, c, **kw)
         else:
-            srgb = render_xtrans(out, wt, ct, CRF=CRF)
-            lin = render_xtrans(out, wt, ct, linear=True) if linear else None
+            render = lambda c, **kw: render_xtrans(out, wt, c, **kw)
+        if warp is None:
+            srgb = render(ct, CRF=CRF)
+            lin = render(ct, linear=True) if linear else None
+        else:                                                     # one demosaic to camera RGB, resampled once per output
+            cam = render(None, linear=True)
+            srgb = warp_rgb(cam, warp, ct, CRF=CRF)
+            lin = warp_rgb(cam, warp, ct, linear=True) if linear else None
     elif wbs is not None:
         fn = process if cfa == 'bayer' else process_xtrans
         rgb = fn(out, torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev), CRF=CRF)
@@ -340,7 +355,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
 SIDECAR_ALIASES = {'black_level_per_channel': 'black_level', 'white_level': 'white_point', 'camera_whitebalance': 'wb',
                    'rgb_camera_matrix': 'ccm', 'black': 'black_level', 'white': 'white_point'}
 SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size', 'defects',
-                'shading', 'iso', 'flatfield', 'lens')
+                'shading', 'iso', 'flatfield', 'lens', 'warp')
 
 
 def read_sidecar(path):
@@ -358,8 +373,8 @@ def sidecar_from_dict(d, path):
     out = {}
     for k, v in d.items():
         k = SIDECAR_ALIASES.get(k, k)
-        if k in ('defects', 'shading', 'flatfield') and isinstance(v, str):  # a saved defect / dark-shading / flat-field map, relative to the sidecar
-            v = os.path.join(os.path.dirname(os.path.abspath(path)), v)
+        if (k in ('defects', 'shading', 'flatfield') or (k == 'warp' and v != 'opcodes')) and isinstance(v, str):
+            v = os.path.join(os.path.dirname(os.path.abspath(path)), v)      # a saved defect / dark-shading / flat-field map or a warp file, relative to the sidecar
         if k not in SIDECAR_KEYS:
             raise ValueError('%s: unknown key %r (known: %s)' % (path, k, ', '.join(SIDECAR_KEYS + tuple(SIDECAR_ALIASES))))
         if k == 'ccm':
@@ -395,6 +410,10 @@ def build_parser():
     p.add_argument('--opcodes', choices=('ignore', 'apply'), default='ignore',
                    help="the OpcodeList tags of .dng inputs: 'ignore' (the default), or 'apply': list 1's bad pixels join --defects, the gain "
                         'opcodes of lists 2 and 3 become the lens plane --lens places (not together with --flatfield)')
+    p.add_argument('--warp', metavar='opcodes|FILE.json',
+                   help="with --srgb-size full: resample the demosaiced picture by a DNG WarpRectilinear (lens distortion, lateral CA) before the colour "
+                        "matrix: 'opcodes' takes the one in OpcodeList3 of each .dng input, FILE.json holds {\"sets\": [[kr0, kr1, kr2, kr3, kt0, kt1], ...], "
+                        '"cx": ..., "cy": ...} with one set or three (R, G, B).  The written-back mosaic and --dng stay unwarped raw frames')
     p.add_argument('--dng', action='store_true', help='also write <name>_denoised.dng (uncompressed 16-bit unless --dng-compression says otherwise; the tags of a .dng input are copied)')
     p.add_argument('--dng-compression', choices=('none', 'ljpeg'), default='none', help="of --dng: 'none' (uncompressed strips, the default) or 'ljpeg' (lossless-JPEG tiles, encoded on the device)")
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
@@ -410,7 +429,7 @@ def options_from(a):
     """parse_args on a namespace already parsed by build_parser() or a parser that extends it (eld_amd.classical)."""
     o = read_sidecar(a.meta) if a.meta else {}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
-           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'precision': 'bf16' if a.bf16 else None,
+           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'warp': getattr(a, 'warp', None), 'precision': 'bf16' if a.bf16 else None,
            'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
     o.update({k: v for k, v in cli.items() if v is not None})
     # below the command line and the sidecar, above the defaults: the tags of the first .dng input (all .dng inputs must agree on the sensor keys)
@@ -459,6 +478,16 @@ def options_from(a):
             raise ValueError('--opcodes apply together with --flatfield would correct the lens twice: give one of them')
     if o.get('lens') is not None and o.get('flatfield') is None and o.get('opcodes') != 'apply':
         raise ValueError('--lens needs --flatfield')
+    if o.get('warp') is not None:
+        if o['srgb_size'] != 'full':
+            raise ValueError('--warp resamples the full-resolution render: it needs --srgb-size full')
+        if o['warp'] == 'opcodes':
+            from .dng import is_dng
+            for path in getattr(a, 'inputs', None) or []:
+                if not is_dng(path):
+                    raise ValueError("%s: --warp opcodes reads OpcodeList3 of .dng inputs (a .json file gives a warp to any input)" % path)
+        elif not isinstance(o['warp'], str):
+            raise ValueError("warp must be 'opcodes' or the path of a .json file, got %r" % (o['warp'],))
     return a.inputs, a.out, a.ckpt, o
 
 
@@ -519,6 +548,36 @@ def opcode_options(path, raw, kw, o):
     return kw, carried
 
 
+def read_warp(path):
+    """A warp file: JSON {"sets": [[kr0, kr1, kr2, kr3, kt0, kt1], ...] (one set or three: R, G, B), "cx": ..., "cy": ...} -> Warp."""
+    from .dng_opcodes import Warp
+    with open(path) as fh:
+        d = json.load(fh)
+    if not isinstance(d, dict) or set(d) != {'sets', 'cx', 'cy'}:
+        raise ValueError('%s: a warp file is a JSON object with the keys sets, cx, cy' % path)
+    try:
+        return Warp(d['sets'], d['cx'], d['cy'])
+    except (TypeError, ValueError) as e:
+        raise ValueError('%s: %s' % (path, e))
+
+
+def warp_option(path, raw, o, carried):
+    """--warp for one input -> (Warp or None, the opcode tags --dng carries).  'opcodes': list 3's WarpRectilinear of the .dng input (None, with a
+    line saying so, when the list has none); the written mosaic is not warped, so --dng carries the source's lists 2 and 3 -- as --opcodes apply
+    already decided them when it is given too."""
+    if o['warp'] != 'opcodes':
+        return read_warp(o['warp']), carried
+    from . import dng_opcodes as O
+    lists = O.read_opcodes(path)
+    Hm, Wm = (int(v) for v in raw.shape[-2:])
+    warp = O.warp_from_opcodes(lists[2], Hm, Wm, '%s: OpcodeList3' % path)
+    if warp is None:
+        print('%s: OpcodeList3 holds no WarpRectilinear: --warp opcodes changes nothing for this file' % path)
+    if carried is None:
+        carried = {name: lists.raw[name] for name in ('OpcodeList2', 'OpcodeList3') if name in lists.raw}
+    return warp, carried
+
+
 def run_frames(den, inputs, outdir, o):
     """The command line's loop: denoise every input with `den` (a Denoiser or a ClassicalDenoiser) under the options `o`, write the outputs."""
     os.makedirs(outdir, exist_ok=True)
@@ -536,6 +595,9 @@ def run_frames(den, inputs, outdir, o):
         fkw, carried = kw, None
         if o.get('opcodes') == 'apply':
             fkw, carried = opcode_options(path, raw, kw, o)
+        if o.get('warp') is not None:
+            warp, carried = warp_option(path, raw, o, carried)
+            fkw = dict(fkw, warp=warp)
         res = denoise_raw(den, raw, o['cfa'], **fkw)
         name = os.path.splitext(os.path.basename(path))[0]
         np.save(os.path.join(outdir, name + '_denoised.npy'), res['mosaic'])

@@ -10,12 +10,15 @@ eld_dng_opcodes_gain_f32; csrc/dng_opcodes.hip).
     gain_plane(ops2, ops3, Hm, Wm, device)            float32 (Hm,Wm): the per-site product of the multiplicative opcodes
     lens_from_opcodes(ops2, ops3, Hm, Wm, ...)        -> FlatField (lens = that plane, prnu = 1)
     defects_from_opcodes(ops1, mosaic, meta)          -> DefectMap (FixBadPixelsList, FixBadPixelsConstant)
+    warp_from_opcodes(ops3, Hm, Wm)                   -> Warp (list 3's WarpRectilinear) or None; warp_params / pack_warp: its bytes <-> fields
 
 The list is big-endian whatever the file's byte order: uint32 count, then per opcode uint32 id, DNG version, flags (bit 0: optional, bit 1:
 skip for preview), byte count of the parameters, and the parameters.  Parsing checks every offset and count against the bytes; a failure is a
 ValueError that names the list, the opcode's index and the field.  An id this module does not apply (unknown, or in a list where it has no
 meaning here) is skipped when its optional bit is set and a ValueError otherwise -- raised when the list is APPLIED, not when it is parsed
-or reported.  Warps (1, 2) and TrimBounds (6) are known by name and never applied.
+or reported.  Warps (1, 2) and TrimBounds (6) are known by name and never applied by the lists' own machinery: parse_opcode_list keeps their
+bytes and disposition answers 'never'.  WarpRectilinear is decoded on request (warp_params, warp_from_opcodes) for the full-resolution render,
+which resamples the demosaiced camera RGB with it (eld_amd.isp.warp_rgb, eld_warp_rgb_f32; denoise --warp).
 
 Where a list applies: list 1 to the stored image (its coordinates are relative to the full stored image: the ActiveArea origin is subtracted
 and what falls outside the visible mosaic is dropped); lists 2 and 3 to the active area, which is the mosaic read_dng returns.  A mosaic has
@@ -457,6 +460,100 @@ def defects_from_opcodes(ops1, mosaic, meta, linearization=False):
             if t < b and l < r:
                 mask[t:b, l:r] = True
     return DefectMap((Hm, Wm), meta.get('cfa', 'bayer'), meta.get('raw_pattern'), mask)
+
+
+# ---- WarpRectilinear (opcode 1, list 3) ----------------------------------------------------------------------------------------------------------
+IDENTITY_SET = (1.0, 0.0, 0.0, 0.0, 0.0, 0.0)
+
+
+def warp_params(op, where='WarpRectilinear'):
+    """The parameter bytes of an opcode-1 Opcode (`.data`, as parse_opcode_list keeps them) -> {'sets': float64 (N,6) rows kr0, kr1, kr2, kr3,
+    kt0, kt1, 'cx', 'cy'}.  Big-endian: uint32 N, N x six float64, two float64; exactly 4 + 48 N + 16 bytes; N is 1 (one set for the three
+    planes) or 3 (R, G, B).  A wrong length, another N or a value that is not finite is a ValueError that starts with `where`."""
+    if op.id != 1:
+        raise ValueError('%s: opcode id %d (%s) is no WarpRectilinear' % (where, op.id, op.name))
+    p = op.data
+    if len(p) < 4:
+        raise ValueError('%s: N needs 4 parameter bytes, the opcode has %d' % (where, len(p)))
+    n, = struct.unpack('>I', p[:4])
+    if n not in (1, 3):
+        raise ValueError('%s: N (the number of coefficient sets) is %d: 1 or 3' % (where, n))
+    if len(p) != 4 + 48 * n + 16:
+        raise ValueError('%s: byte count: N = %d takes %d parameter bytes, the opcode has %d' % (where, n, 4 + 48 * n + 16, len(p)))
+    v = np.frombuffer(p, '>f8', 6 * n + 2, 4).astype(np.float64)
+    names = ('kr0', 'kr1', 'kr2', 'kr3', 'kt0', 'kt1')
+    for i, x in enumerate(v):
+        if not np.isfinite(x):
+            field = 'set %d %s' % (i // 6, names[i % 6]) if i < 6 * n else ('cx', 'cy')[i - 6 * n]
+            raise ValueError('%s: %s is %r: not finite' % (where, field, float(x)))
+    return {'sets': v[:6 * n].reshape(n, 6).copy(), 'cx': float(v[6 * n]), 'cy': float(v[6 * n + 1])}
+
+
+def pack_warp(sets, cx, cy, flags=0):
+    """-> the opcode-1 Opcode of these coefficient sets ((6,), (1,6) or (3,6)) and centre; warp_params is its inverse."""
+    sets = np.asarray(sets, np.float64).reshape(-1, 6)
+    if len(sets) not in (1, 3):
+        raise ValueError('a WarpRectilinear holds 1 or 3 coefficient sets, got %d' % len(sets))
+    return Opcode(1, None, struct.pack('>I', len(sets)) + sets.astype('>f8').tobytes() + struct.pack('>2d', float(cx), float(cy)), flags)
+
+
+class Warp:
+    """A WarpRectilinear: sets float64 (1,6) or (3,6) rows kr0, kr1, kr2, kr3, kt0, kt1 (three rows: planes R, G, B); cx, cy the centre in
+    relative coordinates.  record(Hm, Wm): the EldWarp record eld_warp_rgb_f32 takes for an image of that size; identity: every set is
+    (1, 0, 0, 0, 0, 0), so the map returns every pixel's own centre whatever cx, cy are."""
+    def __init__(self, sets, cx=0.5, cy=0.5):
+        sets = np.array(sets, np.float64).reshape(-1, 6)
+        if len(sets) not in (1, 3):
+            raise ValueError('a warp holds 1 or 3 coefficient sets, got %d' % len(sets))
+        self.sets, self.cx, self.cy = sets, float(cx), float(cy)
+        if not (np.all(np.isfinite(sets)) and np.isfinite(self.cx) and np.isfinite(self.cy)):
+            raise ValueError('a warp needs finite coefficients and a finite centre, got %r, (%r, %r)' % (sets.tolist(), self.cx, self.cy))
+
+    @property
+    def identity(self):
+        return bool(np.all(self.sets == np.asarray(IDENTITY_SET)))
+
+    def record(self, Hm, Wm):
+        """numpy WARP_DTYPE scalar array: k = the sets with kr0 - 1 in place of kr0; cxp = cx Wm, cyp = cy Hm; m2 = mx mx + my my with
+        mx = max(|cxp|, |Wm - cxp|), my likewise; m = sqrt(m2) -- float64, every operation rounded on its own."""
+        Hm, Wm = int(Hm), int(Wm)
+        if Hm < 1 or Wm < 1 or Hm * Wm >= 1 << 31:
+            raise ValueError('an image of %d x %d' % (Hm, Wm))
+        r = np.zeros(1, L.WARP_DTYPE)
+        r['nsets'] = len(self.sets)
+        k = self.sets.copy()
+        k[:, 0] = k[:, 0] - 1.0
+        r['k'][0, :len(k)] = k
+        cxp, cyp = np.float64(self.cx) * np.float64(Wm), np.float64(self.cy) * np.float64(Hm)
+        mx, my = max(abs(cxp), abs(np.float64(Wm) - cxp)), max(abs(cyp), abs(np.float64(Hm) - cyp))
+        m2 = mx * mx + my * my
+        r['cxp'], r['cyp'], r['m2'], r['m'] = cxp, cyp, m2, np.sqrt(m2)
+        return r
+
+    def __repr__(self):
+        return 'Warp(%d set%s, centre (%g, %g)%s)' % (len(self.sets), '' if len(self.sets) == 1 else 's', self.cx, self.cy,
+                                                    ', identity' if self.identity else '')
+
+
+def warp_from_opcodes(ops3, Hm=None, Wm=None, name='OpcodeList3'):
+    """List 3's WarpRectilinear -> Warp, or None when the list holds none.  More than one is a ValueError that says so.  A WarpFisheye (id 2)
+    goes by its optional bit: skipped when optional, else a ValueError that names it (it is not implemented).  Every other opcode is not this
+    function's business.  Hm, Wm: when given, the image the warp is for is checked as Warp.record checks it."""
+    found = None
+    for i, op in enumerate(ops3 or ()):
+        if op.id == 2 and not op.optional:
+            raise ValueError('%s: opcode %d (WarpFisheye) is not supported and not marked optional' % (name, i))
+        if op.id != 1:
+            continue
+        if found is not None:
+            raise ValueError('%s: opcode %d is a second WarpRectilinear (the first is opcode %d): a list holds at most one' % (name, i, found[0]))
+        f = warp_params(op, '%s: opcode %d (WarpRectilinear)' % (name, i))
+        found = (i, Warp(f['sets'], f['cx'], f['cy']))
+    if found is None:
+        return None
+    if Hm is not None and Wm is not None:
+        found[1].record(Hm, Wm)
+    return found[1]
 
 
 def merge_defects(a, b):

@@ -1,7 +1,8 @@
 """Raw -> sRGB ISP on the device: the reference's util/process.py:52-68 `process` (gains, binning, CCM, gamma / camera
 response, 8-bit quantisation) as one HBM-bound HIP kernel (csrc/eval.hip eld_isp_process).  Used by the sRGB training /
 evaluation stages (train_syn.py:55-58, models/ELD_model.py:230-233), and its X-Trans counterpart (process_xtrans) for eld_amd.denoise.
-render_bayer / render_xtrans are the same pipeline at MOSAIC resolution: a demosaic (csrc/demosaic.hip) in place of the binning."""
+render_bayer / render_xtrans are the same pipeline at MOSAIC resolution: a demosaic (csrc/demosaic.hip) in place of the binning; with
+`warp=` the demosaiced camera RGB is resampled by a DNG WarpRectilinear before the matrix and the tone curve (warp_rgb, csrc/warp.hip)."""
 import ctypes
 
 import numpy as np
@@ -72,11 +73,50 @@ def _render_out(x, planes, wbs, cam2rgbs, linear, gains):
     return x, wbs, ccm, out, L.RENDER_LINEAR_F32 if linear else L.RENDER_SRGB8
 
 
-def render_bayer(bayer_images, raw_pattern, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False):
+WARP_LDS_BYTES = -1                      # LDS a workgroup of eld_warp_rgb_f32 may stage source boxes in (< 0: the library's default, 0: none); tests set 65536
+
+
+def warp_rgb(rgb, warp, cam2rgbs=None, gamma=2.2, CRF=None, linear=False):
+    """DNG WarpRectilinear on demosaiced camera RGB, then the tail of the renders (csrc/warp.hip eld_warp_rgb_f32).
+    rgb: CUDA (N,3,Hm,Wm) float32 camera RGB, as render_bayer / render_xtrans return it with linear=True and cam2rgbs=None.  warp: an
+    eld_amd.dng_opcodes.Warp.  Every output pixel of every plane is a Catmull-Rom sample of its plane at the coordinate the warp's polynomial
+    gives (the edge replicated); the three samples then take cam2rgbs (N,3,3; None: no matrix) and, unless linear, the gamma or CRF and the
+    8-bit quantiser.  Returns CUDA (N,3,Hm,Wm): uint8 codes, or with linear=True float32."""
+    import torch
+    from .dng_opcodes import Warp
+    if not isinstance(warp, Warp):
+        raise ValueError('warp must be an eld_amd.dng_opcodes.Warp, got %r' % (type(warp).__name__,))
+    if not (hasattr(rgb, 'is_cuda') and rgb.is_cuda and rgb.dim() == 4 and rgb.shape[1] == 3):
+        raise ValueError('rgb must be a CUDA (N,3,Hm,Wm) tensor, got %s' % (tuple(rgb.shape) if hasattr(rgb, 'shape') else type(rgb).__name__,))
+    dev = rgb.device
+    x = rgb.contiguous().float()
+    N, _, Hm, Wm = x.shape
+    rec = warp.record(Hm, Wm)
+    ccm = None if cam2rgbs is None else torch.as_tensor(cam2rgbs, dtype=torch.float32, device=dev).reshape(N, 9).contiguous()
+    out = torch.empty((N, 3, Hm, Wm), dtype=torch.float32 if linear else torch.uint8, device=dev)
+    E, fs, n = _crf(CRF, dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().eld_warp_rgb_f32(L.dptr(x), L.dptr(out), L.RENDER_LINEAR_F32 if linear else L.RENDER_SRGB8, N, Hm, Wm,
+                                         ctypes.c_void_p(rec.ctypes.data), L.dptr(ccm), float(gamma), L.dptr(E), L.dptr(fs), n,
+                                         int(WARP_LDS_BYTES), L.cur_stream()), 'eld_warp_rgb_f32')
+    return out
+
+
+def _warped(render, warp, cam2rgbs, gamma, CRF, linear):
+    """the render with a warp: camera RGB (linear, no matrix) from `render`, then warp_rgb with the caller's matrix and tone curve"""
+    if cam2rgbs is None and not linear:
+        raise ValueError('the sRGB render needs cam2rgbs (only linear=True renders camera RGB)')
+    return warp_rgb(render(), warp, cam2rgbs, gamma, CRF, linear)
+
+
+def render_bayer(bayer_images, raw_pattern, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False, warp=None):
     """`process` at mosaic resolution (csrc/demosaic.hip eld_render_bayer): gains and clamp, Malvar-He-Cutler demosaic with mirrored
     borders, then the CCM / gamma or CRF / quantiser of `process`.  bayer_images CUDA (N,4,h,w) float32 in the planes of raw_pattern (2x2
     rawpy codes, R 0, G1 1, B 2, G2 3, as the write-back takes it); wbs (N,4) by plane; cam2rgbs (N,3,3), or None with linear=True.
-    Returns CUDA (N,3,2h,2w): uint8 codes, or with linear=True float32 linear RGB after the CCM (no clamp, no gamma)."""
+    Returns CUDA (N,3,2h,2w): uint8 codes, or with linear=True float32 linear RGB after the CCM (no clamp, no gamma).
+    warp: None, or an eld_amd.dng_opcodes.Warp: the demosaiced camera RGB is resampled by it (warp_rgb) before the matrix and the tone curve."""
+    if warp is not None:
+        return _warped(lambda: render_bayer(bayer_images, raw_pattern, wbs, None, linear=True), warp, cam2rgbs, gamma, CRF, linear)
     x, wbs, ccm, out, mode = _render_out(bayer_images, 4, wbs, cam2rgbs, linear, 4)
     pat = [int(v) for v in np.asarray(raw_pattern).reshape(-1)]
     if len(pat) != 4:
@@ -88,11 +128,13 @@ def render_bayer(bayer_images, raw_pattern, wbs, cam2rgbs, gamma=2.2, CRF=None, 
     return out
 
 
-def render_xtrans(packed, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False):
+def render_xtrans(packed, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False, warp=None):
     """`process_xtrans` at mosaic resolution (csrc/demosaic.hip eld_render_xtrans): gains by plane colour and clamp, a two-stage normalised
     convolution on colour differences (G from the 3x3, R - G and B - G from the 5x5 neighbourhood, windows clipped to the image), then
     the tail of `process`.  packed CUDA (N,9,h,w) float32 with even h and w (whole 6x6 cells); wbs (N,3); cam2rgbs (N,3,3), or None with
-    linear=True.  Returns CUDA (N,3,3h,3w): uint8 codes, or with linear=True float32 linear RGB after the CCM."""
+    linear=True.  Returns CUDA (N,3,3h,3w): uint8 codes, or with linear=True float32 linear RGB after the CCM.  warp: as render_bayer's."""
+    if warp is not None:
+        return _warped(lambda: render_xtrans(packed, wbs, None, linear=True), warp, cam2rgbs, gamma, CRF, linear)
     x, wbs, ccm, out, mode = _render_out(packed, 9, wbs, cam2rgbs, linear, 3)
     E, fs, n = _crf(CRF, x.device)
     N, _, h, w = x.shape

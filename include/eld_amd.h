@@ -63,7 +63,9 @@ extern "C" {
  * inject / dump buffers then hold ELD_NPLANES_COL planes.  Without ELD_COL the field is ignored and the buffers hold ELD_NPLANES planes, as
  * before.  The one difference: bit 2048 in the flags of the sampler entries was ignored and now selects the term.
  * Still 8: eld_tile_noise_sums_u16 and eld_tile_noise_workspace_bytes were added the same way (exact per-tile second- and first-difference
- * sums of a single frame, for its gain and read noise): two new symbols, no existing call changed. */
+ * sums of a single frame, for its gain and read noise): two new symbols, no existing call changed.
+ * Still 8: eld_warp_rgb_f32 and EldWarp were added the same way (DNG WarpRectilinear on demosaiced camera RGB, followed by the renders' tail):
+ * one new symbol, no existing call changed. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -1096,6 +1098,41 @@ int eld_dng_opcodes_apply_f32(const float* in, float* out, int N, int Hm, int Wm
                               size_t blob_bytes, int map_lds_bytes, void* stream);
 int eld_dng_opcodes_gain_f32(float* out, int Hm, int Wm, const EldDngOp* ops, int nops, const uint8_t* blob, size_t blob_bytes,
                              int map_lds_bytes, void* stream);
+
+/* ---- DNG WarpRectilinear: lens distortion and lateral CA on demosaiced camera RGB (csrc/warp.hip, csrc/warp_dev.h) ----
+ * Appended without a change of ELD_ABI_VERSION: one new symbol, no existing call changed.
+ *   rgb   (N,3,Hm,Wm) float32 camera RGB in DEVICE memory, as eld_render_* write it with ELD_RENDER_LINEAR_F32 and ccms NULL; 16-byte aligned.
+ *   out   (N,3,Hm,Wm) uint8 (ELD_RENDER_SRGB8) or float32 (ELD_RENDER_LINEAR_F32), as the renders write it; it must not overlap rgb.
+ *   warp  one EldWarp record in HOST memory (it is validated here and travels by value as a kernel argument).
+ *   ccms, gamma, crf_E, crf_f, crf_n: the tail of eld_render_*, unchanged, applied to the three resampled values of a pixel.
+ * The map (float64, every operation rounded on its own, no FMA), for destination pixel (x, y), set s = plane (nsets 3) or 0 (nsets 1),
+ * k = warp->k[s] = kr0 - 1, kr1, kr2, kr3, kt0, kt1:
+ *   dx = (x + 0.5) - cxp   dy = (y + 0.5) - cyp   r2 = (dx*dx + dy*dy) / m2   g = k[0] + r2*(k[1] + r2*(k[2] + r2*k[3]))
+ *   nx = dx / m   ny = dy / m   tx = k[4]*(2*nx*ny) + k[5]*(r2 + 2*nx*nx)   ty = k[5]*(2*nx*ny) + k[4]*(r2 + 2*ny*ny)
+ *   u = ((x + 0.5) + (g*dx + m*tx)) - 0.5        v = ((y + 0.5) + (g*dy + m*ty)) - 0.5
+ * u is clamped to [-1, Wm] and v to [-1, Hm], NaN becoming -1; j0 = floor(u), t = float32(u - j0), likewise i0 from v; the taps j0-1 .. j0+2 and
+ * i0-1 .. i0+2 are each clamped to the image (the edge is replicated).  No address is formed from a coordinate before these clamps.
+ * Catmull-Rom in float32, every product and sum rounded on its own:
+ *   w0 = t*(t*(-0.5*t + 1) - 0.5)   w1 = t*t*(1.5*t - 2.5) + 1   w2 = t*(t*(-1.5*t + 2) + 0.5)   w3 = t*t*(0.5*t - 0.5)
+ *   h_i = ((w0x*p[i][0] + w1x*p[i][1]) + w2x*p[i][2]) + w3x*p[i][3]      val = ((w0y*h_0 + w1y*h_1) + w2y*h_2) + w3y*h_3      (unclamped)
+ * With k = 0 the map is u = x, v = y exactly and the output is the tail of the input.  tests/warp_ref.py restates all of it bit for bit.
+ * lds_bytes: the LDS a workgroup may use to stage the source boxes of its 32 x 64 tile (all three planes, halo included); a tile whose boxes
+ * do not fit reads its taps from global memory.  < 0: the default, which is 0 (reading from global memory measured faster: DESIGN.md sec. 30);
+ * 0: always from global memory; at most 65536.  The result does not depend on it.
+ * ELD_EINVAL before any device work: rgb, out or warp NULL; rgb not 16-byte aligned, a float32 out not 4-byte aligned; N < 0 or > 65535;
+ * Hm, Wm < 1, Hm * Wm >= 2^31 or more than 65535 * 32 rows; nsets not 1 or 3; a field of a used set, cxp, cyp, m or m2 not finite; m2 <= 0;
+ * an unknown out_mode; the tail's rules (ccms 4-byte aligned, gamma > 0, crf_n 0 or >= 2 with both tables); lds_bytes > 65536; rgb and out
+ * overlapping.  N == 0 is a successful no-op. */
+typedef struct EldWarp {           /* 184 bytes */
+    int32_t nsets;                 /* 1: one coefficient set for the three planes; 3: one per plane, R, G, B */
+    int32_t reserved;
+    double k[3][6];                /* per set kr0 - 1, kr1, kr2, kr3, kt0, kt1; sets beyond nsets are not read */
+    double cxp, cyp;               /* the centre in pixels: cx * Wm, cy * Hm */
+    double m, m2;                  /* m2 = mx*mx + my*my with mx = max(|cxp|, |Wm - cxp|), my = max(|cyp|, |Hm - cyp|); m = sqrt(m2) */
+} EldWarp;
+
+int eld_warp_rgb_f32(const float* rgb, void* out, int out_mode, int N, int Hm, int Wm, const EldWarp* warp, const float* ccms, float gamma,
+                     const float* crf_E, const float* crf_f, int crf_n, int lds_bytes, void* stream);
 
 #ifdef __cplusplus
 }
