@@ -54,6 +54,10 @@ DNG_MAX_OPS, DNG_MAX_BLOB = 32, 64 << 20
 WARP_DTYPE = np.dtype([('nsets', '<i4'), ('reserved', '<i4'), ('k', '<f8', (3, 6)), ('cxp', '<f8'), ('cyp', '<f8'), ('m', '<f8'), ('m2', '<f8')])
 assert WARP_DTYPE.itemsize == 184
 WARP_MAX_LDS = 64 << 10
+# the baseline-JPEG encoder: subsampling codes, segment lengths in blocks, the bins of a histogram and the entries of the code tables
+JPEG_444, JPEG_420 = 0, 2
+JPEG_SEGMENT, JPEG_MIN_SEGMENT, JPEG_MAX_SEGMENT = 1024, 8, 2048
+JPEG_HIST, JPEG_TABLE, JPEG_MAX_LDS = 536, 546, 60 << 10
 DNG_STATUS = {0: 'ok', 1: 'truncated: the data ended before the last sample', 2: 'invalid code: bits that are no code of the Huffman table',
               3: 'too many samples: the stream holds more samples than its tile', 4: 'bad record: a field out of range'}
 
@@ -196,6 +200,9 @@ SIGNATURES = {
     'eld_dng_opcodes_apply_f32': (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
     'eld_dng_opcodes_gain_f32': (_i, [_vp, _i, _i, _vp, _i, _vp, _sz, _i, _vp]),
     'eld_warp_rgb_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _i, _vp]),
+    'eld_jpeg_coef_u8': (_i, [_vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    'eld_jpeg_hist_i16': (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _sz, _vp]),
+    'eld_jpeg_pack_i16': (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]),
 }
 
 

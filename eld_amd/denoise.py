@@ -195,7 +195,7 @@ def run_network(denoiser, x, chop=None):
 
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
                 chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None, shading=None, iso=None, flatfield=None,
-                lens='srgb', warp=None):
+                lens='srgb', warp=None, jpeg=None):
     """Denoise uint16 sensor mosaics with a trained U-Net -- or, given an eld_amd.classical.ClassicalDenoiser in place of a Denoiser, with the
     classical baseline (Anscombe transform, non-local means, unbiased inverse on the sensor's codes instead of the input stage and the
     network; `chop` is then ignored, and 'packed' is the baseline's output in the network's convention).
@@ -230,6 +230,10 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                 only: the demosaiced camera RGB is resampled by it before the colour matrix and the tone curve (eld_amd.isp.warp_rgb), in
                 'srgb' and in 'linear'.  The mosaic written back is not warped: it stays a raw frame.
 
+    jpeg        None (default), or a dict with any of quality (1..100, default 90) and subsampling ('444' / '420', default '420'): the sRGB
+                rendering is also encoded as baseline JPEG on the device, before its copy to the host (eld_amd.jpeg.encode_jpeg), and the
+                result gains 'jpeg': a list of bytes, one file per frame.  It needs the sRGB output (wb and ccm) and not linear=True.
+
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
     _check_cfa(cfa)
@@ -251,6 +255,15 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
             raise ValueError('warp must be an eld_amd.dng_opcodes.Warp, got %r' % (type(warp).__name__,))
         if srgb_size != 'full':
             raise ValueError("warp resamples the full-resolution render: it needs srgb_size='full'")
+    if jpeg is not None:
+        from .jpeg import _check_args as check_jpeg_args
+        if not isinstance(jpeg, dict) or set(jpeg) - {'quality', 'subsampling'}:
+            raise ValueError('jpeg must be None or a dict with the keys quality and subsampling, got %r' % (jpeg,))
+        check_jpeg_args(jpeg.get('quality', 90), jpeg.get('subsampling', '420'), 0, 0)
+        if wb is None or ccm is None:
+            raise ValueError('jpeg encodes the sRGB rendering: it needs both wb and ccm')
+        if linear:
+            raise ValueError('jpeg encodes the uint8 sRGB rendering: it does not go with linear=True')
     kind, batched = _as_u16(mosaic_u16)
     shape = tuple(mosaic_u16.shape)
     N = shape[0] if batched else 1
@@ -337,6 +350,11 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         fn = process if cfa == 'bayer' else process_xtrans
         rgb = fn(out, torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev), CRF=CRF)
         srgb = torch.round(rgb * 255.0).to(torch.uint8)          # k/255 -> k exactly
+    files = None
+    if jpeg is not None:                                          # on the device, before the rendering's copy to the host
+        from .jpeg import encode_jpeg
+        with torch.cuda.device(dev):
+            files = encode_jpeg(srgb, **jpeg)
     if not batched:
         mosaic = mosaic[0]
     if kind == 'numpy':
@@ -344,10 +362,12 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                'srgb': None if srgb is None else srgb.cpu().numpy()}
         if lin is not None:
             res['linear'] = lin.cpu().numpy()
-        return res
-    res = {'packed': net_out, 'mosaic': mosaic, 'srgb': srgb}
-    if lin is not None:
-        res['linear'] = lin
+    else:
+        res = {'packed': net_out, 'mosaic': mosaic, 'srgb': srgb}
+        if lin is not None:
+            res['linear'] = lin
+    if files is not None:
+        res['jpeg'] = files
     return res
 
 
@@ -416,6 +436,9 @@ def build_parser():
                         '"cx": ..., "cy": ...} with one set or three (R, G, B).  The written-back mosaic and --dng stay unwarped raw frames')
     p.add_argument('--dng', action='store_true', help='also write <name>_denoised.dng (uncompressed 16-bit unless --dng-compression says otherwise; the tags of a .dng input are copied)')
     p.add_argument('--dng-compression', choices=('none', 'ljpeg'), default='none', help="of --dng: 'none' (uncompressed strips, the default) or 'ljpeg' (lossless-JPEG tiles, encoded on the device)")
+    p.add_argument('--dng-preview', action='store_true', help='of --dng: the sRGB rendering, encoded as JPEG on the device (the settings of --jpeg, or its defaults), becomes the preview in IFD0 and the mosaic moves to a SubIFD')
+    p.add_argument('--jpeg', type=int, nargs='?', const=90, metavar='Q', help='also write <name>_srgb.jpg: the sRGB rendering as baseline JPEG of quality Q (1..100, default 90), encoded on the device')
+    p.add_argument('--jpeg-subsampling', choices=('444', '420'), help="chroma subsampling of --jpeg and --dng-preview (default '420')")
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
     return p
 
@@ -446,6 +469,20 @@ def options_from(a):
         if not o.get('dng'):
             raise ValueError('--dng-compression goes with --dng')
         o['dng_compression'] = a.dng_compression
+    if getattr(a, 'dng_preview', False):
+        if not o.get('dng'):
+            raise ValueError('--dng-preview goes with --dng')
+        o['dng_preview'] = True
+    if getattr(a, 'jpeg', None) is not None:
+        o['jpeg_out'] = True
+    if o.get('jpeg_out') or o.get('dng_preview'):
+        from .jpeg import _check_args as check_jpeg_args
+        o['jpeg'] = {'quality': 90 if getattr(a, 'jpeg', None) is None else a.jpeg, 'subsampling': getattr(a, 'jpeg_subsampling', None) or '420'}
+        check_jpeg_args(o['jpeg']['quality'], o['jpeg']['subsampling'], 0, 0)
+        if o.get('wb') is None or o.get('ccm') is None:
+            raise ValueError('--jpeg and --dng-preview encode the sRGB rendering: they need --wb and --ccm')
+    elif getattr(a, 'jpeg_subsampling', None) is not None:
+        raise ValueError('--jpeg-subsampling goes with --jpeg or --dng-preview')
     o.setdefault('cfa', 'bayer')
     o.setdefault('white_point', 16383)
     o.setdefault('ratio', 1.0)
@@ -588,6 +625,8 @@ def run_frames(den, inputs, outdir, o):
         kw['shading'], kw['iso'] = as_dark_shading(o['shading'], '--shading'), o['iso']
     if o.get('flatfield') is not None:
         kw['flatfield'], kw['lens'] = as_flat_field(o['flatfield'], '--flatfield'), o.get('lens') or 'srgb'
+    if o.get('jpeg') is not None:
+        kw['jpeg'] = dict(o['jpeg'])
     from .dng import COMPRESSION_CHOICES, is_dng, load_frame, write_dng
     dng_kw = {'compression': COMPRESSION_CHOICES[o.get('dng_compression') or 'none']}
     for path in inputs:
@@ -605,6 +644,8 @@ def run_frames(den, inputs, outdir, o):
         if o.get('dng'):
             if raw.ndim != 2:
                 raise ValueError('%s: --dng writes one frame per file, the input holds a stack of %d' % (path, raw.shape[0]))
+            if o.get('dng_preview'):
+                dng_kw = dict(dng_kw, preview=res['jpeg'][0])
             if is_dng(path):
                 write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'], like=path, opcodes=carried, **dng_kw)
             else:
@@ -618,6 +659,12 @@ def run_frames(den, inputs, outdir, o):
             line += ', %s_srgb.npy' % name
             if hwc.ndim == 3 and save_png(os.path.join(outdir, name + '_srgb.png'), hwc):
                 line += ', %s_srgb.png' % name
+            if o.get('jpeg_out'):
+                for i, data in enumerate(res['jpeg']):
+                    jname = name + ('_srgb.jpg' if raw.ndim == 2 else '_srgb_%d.jpg' % i)
+                    with open(os.path.join(outdir, jname), 'wb') as fh:
+                        fh.write(data)
+                    line += ', %s' % jname
         print(line)
     return 0
 

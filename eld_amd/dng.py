@@ -7,8 +7,9 @@ ITU-T T.81): there is no rawpy here.
     load_frame(path)                                .npy -> np.load(path); .dng -> read_dng(path)[0]
     write_dng(path, mosaic, meta=None, like=None, opcodes=None)   an uncompressed 16-bit little-endian DNG, one IFD, strips; compression=7: lossless-JPEG
                                                     tiles, encoded on the device (eld_dng_enc_*)
+                                                    preview=bytes: a baseline JPEG (eld_amd.jpeg) as IFD0, the mosaic in a SubIFD
     encode_ljpeg(mosaic, tile, bits)                the JPEG streams of the tiles alone, for callers with a container of their own
-    python -m eld_amd.dng in.dng [-o frame.npy | -o out.dng [--compression ljpeg] [--tile TH TW] [--bits N]] [--meta-out sensor.json]
+    python -m eld_amd.dng in.dng [-o frame.npy | -o out.dng [--compression ljpeg] [--tile TH TW] [--bits N] [--preview FILE.jpg]] [--meta-out sensor.json]
                           [--opcodes apply [--flatfield-out lens.npz] [--defects-out defects.npz] [--linear-out stage2.npy]]
 
 Container.  Classic TIFF in both byte orders.  The raw image is the IFD with NewSubFileType = 0 and PhotometricInterpretation = 32803
@@ -59,6 +60,7 @@ BYTE, ASCII, SHORT, LONG, RATIONAL, UNDEFINED, SRATIONAL = 1, 2, 3, 4, 5, 7, 10
 T_NEWSUBFILETYPE, T_WIDTH, T_LENGTH, T_BITS, T_COMPRESSION, T_PHOTOMETRIC, T_FILLORDER = 254, 256, 257, 258, 259, 262, 266
 T_MAKE, T_MODEL, T_STRIPOFFSETS, T_ORIENTATION, T_SPP, T_ROWSPERSTRIP, T_STRIPBYTECOUNTS = 271, 272, 273, 274, 277, 278, 279
 T_TILEWIDTH, T_TILELENGTH, T_TILEOFFSETS, T_TILEBYTECOUNTS, T_SUBIFDS, T_SAMPLEFORMAT = 322, 323, 324, 325, 330, 339
+T_YCBCRSUBSAMPLING, YCBCR_PHOTOMETRIC = 530, 6
 T_CFADIM, T_CFAPATTERN, T_EXPOSURETIME, T_EXIFIFD, T_ISO = 33421, 33422, 33434, 34665, 34855
 T_DNGVERSION, T_DNGBACKWARD, T_UNIQUEMODEL, T_CFAPLANECOLOR, T_CFALAYOUT, T_LINTABLE = 50706, 50707, 50708, 50710, 50711, 50712
 T_BLACKDIM, T_BLACK, T_BLACKDH, T_BLACKDV, T_WHITE = 50713, 50714, 50715, 50716, 50717
@@ -654,13 +656,14 @@ COMPRESSION_CHOICES = {'none': 1, 'ljpeg': 7}                        # the comma
 _EXTRA_BITS = np.array(list(range(16)) + [0], dtype=np.int64)        # SSSS extra bits behind the code; SSSS = 16 carries none
 
 
-def huffman_lengths(hist):
+def huffman_lengths(hist, bins=17):
     """The 17-bin SSSS histogram of a stream -> (counts of the code lengths 1..16, the symbols in code order), as a DHT segment stores them:
     ITU-T T.81 Annex K.2.  Figure K.1 with an 18th symbol of frequency 1 that keeps the all-ones code point free (it ends up with the longest
-    code and is dropped); the least frequency goes to V1, the next to V2, ties to the larger index; Figure K.3 limits the lengths to 16."""
+    code and is dropped); the least frequency goes to V1, the next to V2, ties to the larger index; Figure K.3 limits the lengths to 16.
+    bins: the size of the alphabet (eld_amd.jpeg: 12 DC sizes, 256 AC run/size bytes)."""
     freq = [int(v) for v in hist] + [1]
-    if len(freq) != 18 or min(freq) < 0:
-        raise ValueError('a histogram of 17 non-negative counts, got %r' % (list(hist),))
+    if len(freq) != bins + 1 or min(freq) < 0:
+        raise ValueError('a histogram of %d non-negative counts, got %r' % (bins, list(hist)))
     n = len(freq)
     size, chain = [0] * n, [-1] * n
 
@@ -686,11 +689,12 @@ def huffman_lengths(hist):
         while chain[v2] >= 0:
             v2 = chain[v2]
             size[v2] += 1
-    counts = [0] * 33
+    top = max(32, bins)                                              # no code is longer than the alphabet
+    counts = [0] * (top + 1)
     for s in size:
         if s:
             counts[s] += 1
-    for l in range(32, 16, -1):                                      # Figure K.3: a pair of the longest codes moves up under a shorter one
+    for l in range(top, 16, -1):                                      # Figure K.3: a pair of the longest codes moves up under a shorter one
         while counts[l] > 0:
             j = l - 2
             while counts[j] == 0:
@@ -703,13 +707,13 @@ def huffman_lengths(hist):
     while counts[l] == 0:
         l -= 1
     counts[l] -= 1                                                   # the reserved code point
-    symbols = [s for l in range(1, 33) for s in range(n - 1) if size[s] == l]
-    return counts[1:17], symbols
+    by_length = sorted((size[s], s) for s in range(n - 1) if size[s])
+    return counts[1:17], [s for _, s in by_length]
 
 
-def encoder_table(counts, symbols):
-    """-> 17 uint32, [ssss] = (code length << 16) | canonical code (Annex C), 0 for a symbol the table lacks"""
-    tab = np.zeros(17, dtype=np.uint32)
+def encoder_table(counts, symbols, bins=17):
+    """-> `bins` uint32, [ssss] = (code length << 16) | canonical code (Annex C), 0 for a symbol the table lacks"""
+    tab = np.zeros(bins, dtype=np.uint32)
     code, k = 0, 0
     for l in range(1, 17):
         for _ in range(counts[l - 1]):
@@ -891,7 +895,29 @@ def encode_ljpeg(mosaic, tile=DEFAULT_TILE, bits=16, segment=0, chunk=0):
     return e.streams()
 
 
-def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compression=1, tile=None, bits=None, opcodes=None):
+def _serialise_ifd(tags, ifd_off):
+    """One IFD at the even offset ifd_off, its out-of-line values behind it -> bytes of an even length"""
+    order = sorted(tags)
+    packed = {tag: _pack_entry(tags[tag]) for tag in order}
+    data_off = ifd_off + 2 + 12 * len(order) + 4
+    out, extra = bytearray(struct.pack('<H', len(order))), b''
+    for tag in order:
+        typ, cnt, payload = packed[tag]
+        out += struct.pack('<HHI', tag, typ, cnt)
+        if len(payload) <= 4:
+            out += payload.ljust(4, b'\0')
+        else:
+            out += struct.pack('<I', data_off + len(extra))
+            extra += payload + b'\0' * (len(payload) % 2)
+    return bytes(out) + struct.pack('<I', 0) + extra
+
+
+# with a preview these stay in IFD0; every other tag of the mosaic moves to the raw SubIFD
+IFD0_LEVEL = (T_MAKE, T_MODEL, T_UNIQUEMODEL, T_COLORMATRIX1, T_COLORMATRIX2, T_ILLUMINANT1, T_ILLUMINANT2, T_ANALOGBALANCE, T_ASSHOTNEUTRAL,
+              T_ISO, T_EXPOSURETIME, T_DNGVERSION, T_DNGBACKWARD)
+
+
+def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compression=1, tile=None, bits=None, opcodes=None, preview=None):
     """Write `mosaic` ((H, W) uint16 codes, NumPy or a CUDA int16-view tensor) as a little-endian DNG with one IFD.  compression 1 (the
     default): uncompressed 16-bit strips.  compression 7: lossless-JPEG tiles of `tile` (TileLength, TileWidth; default 256 x 256) at `bits`
     (8..16, default 16) precision, encoded on the device (encode_ljpeg): a NumPy mosaic is uploaded, a device tensor is used where it is.
@@ -899,7 +925,18 @@ def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compressi
     values (rationals stay the rationals they were; the mosaic is taken to be the source's visible mosaic, so no ActiveArea and no
     LinearizationTable are written).  meta: sidecar keys (cfa, raw_pattern, black_level, white_point, wb, ccm, iso, exposure_time, make, model);
     its tags are written from those values (ColorMatrix1 with CalibrationIlluminant1 = 21) and override what `like` gave.
-    opcodes: {'OpcodeList1' | 'OpcodeList2' | 'OpcodeList3': bytes}, written as given (like= copies no opcode tag)."""
+    opcodes: {'OpcodeList1' | 'OpcodeList2' | 'OpcodeList3': bytes}, written as given (like= copies no opcode tag).
+    preview: the bytes of a baseline YCbCr JPEG (eld_amd.jpeg.encode_jpeg of the render).  IFD0 then describes the preview (NewSubFileType 1,
+    Compression 7, PhotometricInterpretation 6, one strip, its size and YCbCrSubSampling read from the stream's SOF0) and keeps the DNG
+    version, camera and colour tags; the mosaic with its CFA, level and opcode tags moves to a SubIFD (NewSubFileType 0).  None: one IFD, the
+    bytes of before."""
+    if preview is not None:
+        from .jpeg import jpeg_info
+        try:
+            pinfo = jpeg_info(preview)
+        except ValueError as e:
+            raise ValueError('preview: %s' % e)
+        preview = bytes(preview)
     op_tags = {}
     for name, data in (opcodes or {}).items():
         tag = {n: t for t, n in OPCODE_TAGS}.get(name)
@@ -1029,6 +1066,30 @@ def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compressi
     put(T_CFALAYOUT, SHORT, (1,))
     if T_UNIQUEMODEL not in tags:
         tags[T_UNIQUEMODEL] = Entry(T_UNIQUEMODEL, ASCII, 0, tags[T_MODEL].values if T_MODEL in tags else 'eld_amd')
+    if preview is not None:
+        top = {tag: tags.pop(tag) for tag in IFD0_LEVEL if tag in tags}
+        for tag, typ, vals in ((T_NEWSUBFILETYPE, LONG, (1,)), (T_WIDTH, LONG, (pinfo['width'],)), (T_LENGTH, LONG, (pinfo['height'],)),
+                               (T_BITS, SHORT, (8, 8, 8)), (T_COMPRESSION, SHORT, (7,)), (T_PHOTOMETRIC, SHORT, (YCBCR_PHOTOMETRIC,)),
+                               (T_STRIPOFFSETS, LONG, (0,)), (T_SPP, SHORT, (3,)), (T_ROWSPERSTRIP, LONG, (pinfo['height'],)),
+                               (T_STRIPBYTECOUNTS, LONG, (len(preview),)), (T_SUBIFDS, LONG, (0,)), (T_YCBCRSUBSAMPLING, SHORT, pinfo['subsampling'])):
+            top[tag] = Entry(tag, typ, len(vals), vals)
+        raw_off = 8 + len(_serialise_ifd(top, 8))                   # the offsets are LONGs: the sizes do not depend on their values
+        prev_off = raw_off + len(_serialise_ifd(tags, raw_off))
+        offs, pos = [], prev_off + len(preview) + len(preview) % 2
+        for n in sizes:
+            offs.append(pos)
+            pos += n + n % 2
+        if pos >= 1 << 32:
+            raise ValueError('%s: %d bytes do not fit a classic TIFF' % (path, pos))
+        top[T_SUBIFDS].values, top[T_STRIPOFFSETS].values, tags[T_OFFSETS].values = (raw_off,), (prev_off,), tuple(offs)
+        with open(path, 'wb') as fh:
+            fh.write(b'II' + struct.pack('<HI', 42, 8) + _serialise_ifd(top, 8) + _serialise_ifd(tags, raw_off) + preview + b'\0' * (len(preview) % 2))
+            if compression == 7:
+                for s in streams:
+                    fh.write(s + b'\0' * (len(s) % 2))
+            else:
+                fh.write(np.ascontiguousarray(mosaic).astype('<u2', copy=False).tobytes())
+        return
     order = sorted(tags)
     packed = {tag: _pack_entry(tags[tag]) for tag in order}
     ifd_off = 8
@@ -1117,6 +1178,8 @@ def main(argv=None):
                                                                                                'lossless-JPEG tiles (default: none)')
     ap.add_argument('--tile', type=int, nargs=2, metavar=('TH', 'TW'), help='TileLength TileWidth of --compression ljpeg (default 256 256)')
     ap.add_argument('--bits', type=int, help='the precision of --compression ljpeg, 8..16 (default 16)')
+    ap.add_argument('--preview', metavar='FILE.jpg', help='of a .dng output: a baseline JPEG (python -m eld_amd.jpeg writes one) stored as the preview '
+                                                          'in IFD0; the mosaic moves to a SubIFD')
     ap.add_argument('--opcodes', choices=('report', 'apply'), default='report',
                     help="OpcodeList1/2/3: 'report' names the lists present (the default); 'apply' repairs list 1's bad pixels in the -o output and "
                          'says what becomes of every opcode')
@@ -1132,6 +1195,8 @@ def main(argv=None):
         ap.error('--tile and --bits belong to --compression ljpeg')
     if a.compression == 'ljpeg' and not is_dng(a.out):
         ap.error('--compression ljpeg needs an -o that ends in .dng')
+    if a.preview and not is_dng(a.out):
+        ap.error('--preview needs an -o that ends in .dng')
     out = a.out or os.path.splitext(a.input)[0] + '.npy'
     lines, carried = [], None
     if is_dng(out):
@@ -1139,6 +1204,9 @@ def main(argv=None):
         if a.opcodes == 'apply':
             mosaic, lines, carried = _apply_opcodes(a, mosaic, meta)
         kw = dict(compression=7, tile=a.tile and tuple(a.tile), bits=a.bits) if a.compression == 'ljpeg' else {}
+        if a.preview:
+            with open(a.preview, 'rb') as fh:
+                kw['preview'] = fh.read()
         write_dng(out, mosaic, like=a.input, opcodes=carried, **kw)
     else:
         mosaic, meta = read_dng(a.input)

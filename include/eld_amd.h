@@ -65,7 +65,9 @@ extern "C" {
  * Still 8: eld_tile_noise_sums_u16 and eld_tile_noise_workspace_bytes were added the same way (exact per-tile second- and first-difference
  * sums of a single frame, for its gain and read noise): two new symbols, no existing call changed.
  * Still 8: eld_warp_rgb_f32 and EldWarp were added the same way (DNG WarpRectilinear on demosaiced camera RGB, followed by the renders' tail):
- * one new symbol, no existing call changed. */
+ * one new symbol, no existing call changed.
+ * Still 8: eld_jpeg_coef_u8, eld_jpeg_hist_i16 and eld_jpeg_pack_i16 were added the same way (baseline JPEG of the uint8 sRGB render, encoded
+ * on the device): three new symbols, no existing call changed. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -1133,6 +1135,49 @@ typedef struct EldWarp {           /* 184 bytes */
 
 int eld_warp_rgb_f32(const float* rgb, void* out, int out_mode, int N, int Hm, int Wm, const EldWarp* warp, const float* ccms, float gamma,
                      const float* crf_E, const float* crf_f, int crf_n, int lds_bytes, void* stream);
+
+/* ---- Baseline JPEG encode of an sRGB render (csrc/jpeg.hip, csrc/jpeg_dev.h, eld_amd/jpeg.py) -------------------------------
+ * Appended without a change of ELD_ABI_VERSION: three new symbols, no existing call changed.  rgb is planar uint8 (3, H, W) in DEVICE memory.
+ * The picture is ITU-T T.81 process 1 (baseline sequential DCT, 8 bits), components Y, Cb, Cr in one interleaved scan; subsampling is
+ * ELD_JPEG_444 (every component 1 x 1, MCU 8 x 8, 3 blocks) or ELD_JPEG_420 (Y 2 x 2, MCU 16 x 16, 6 blocks: Y00 Y01 Y10 Y11 Cb Cr).  With
+ * mcux = ceil(W / MCU width), mcuy likewise, nblocks = mcux * mcuy * blocks per MCU; block b = MCU (b / blocks per MCU, row-major) and its
+ * k-th block.  The arithmetic is libjpeg's, integer throughout (DESIGN.md sec. 31 states it; tests/jpeg_ref.py restates it bit for bit): colour
+ * conversion with 16 fraction bits, edges by replication, the h2v2 downsampler with its alternating bias, the "slow integer" forward DCT,
+ * the quantiser sign(c) * ((|c| + 4q) / 8q), and libjpeg's dummy blocks: a Y block of a 4:2:0 MCU wholly outside ceil(W / 8) x ceil(H / 8) has no
+ * AC terms and the DC of the block in front of it in the MCU (both blocks of a dummy bottom row: the DC of the MCU's top-right block).
+ *   eld_jpeg_coef_u8    coef[b * 64 + k]: quantised coefficient k (zigzag order) of block b.  qtables: 2 x 64 divisors in natural (row-major)
+ *                       order in HOST memory, luma then chroma, each 1..255.  coef_elems must be nblocks * 64.
+ *   eld_jpeg_hist_i16   `segment` is in BLOCKS: the nblocks are cut into nseg = ceil(nblocks / segment) segments, one workgroup each; a multiple of
+ *                       ELD_JPEG_MIN_SEGMENT up to ELD_JPEG_MAX_SEGMENT, 0: ELD_JPEG_SEGMENT.  hist[g * ELD_JPEG_HIST + i]: how often segment g uses
+ *                       symbol i of the four alphabets laid end to end: luma DC sizes (12), chroma DC sizes (12), luma AC run/size bytes (256),
+ *                       chroma AC (256).  A DC difference takes the previous block of the same component in scan order (0 for the first); sizes
+ *                       beyond 11 (DC) or 10 (AC) do not arise from eld_jpeg_coef_u8 and are counted as the largest size.  hist_elems must be
+ *                       nseg * ELD_JPEG_HIST.
+ *   eld_jpeg_pack_i16   tables[ELD_JPEG_TABLE]: (code length << 16) | code per symbol, 0 for a symbol without a code, laid out as luma DC (17
+ *                       entries, 12 used), chroma DC (17), luma AC (256), chroma AC (256).  seg_bit[g]: the first bit of segment g, [nseg]: the bit
+ *                       count of the scan (uint64).  raw (raw_dwords dwords) is zeroed here, then every segment writes its bits MSB-first; the last one
+ *                       pads the last byte with 1-bits.  A segment whose bit count differs from seg_bit's writes nothing.  A segment's bits are
+ *                       assembled in an LDS image when they fit lds_bytes (< 0: the default, 32 KiB; at most 61440) and leave as whole dwords, the
+ *                       first and last one by atomic OR; a segment that does not fit ORs every dword into raw directly.  Either way the result does
+ *                       not depend on lds_bytes or on the order of execution.  The bytes still lack their FF stuffing: eld_dng_enc_ffcount_u8 and
+ *                       eld_dng_enc_stuff_u8 do that for any byte buffer.
+ * Every read is compared with coef_elems resp. the picture, every write with coef_elems, hist_elems resp. raw_dwords.
+ * ELD_EINVAL before any device work: a null pointer; rgb is any address, coef must be 16-byte, hist, tables and raw 4-byte, seg_bit 8-byte
+ * aligned; H or W outside [1, 65535]; H * W >= 2^31; a subsampling other than the two; a segment outside its set; a quantisation divisor outside
+ * [1, 255]; coef_elems or hist_elems other than stated; raw_dwords < 1; lds_bytes > 61440. */
+#define ELD_JPEG_444 0
+#define ELD_JPEG_420 2
+#define ELD_JPEG_SEGMENT 1024
+#define ELD_JPEG_MIN_SEGMENT 8
+#define ELD_JPEG_MAX_SEGMENT 2048
+#define ELD_JPEG_HIST 536
+#define ELD_JPEG_TABLE 546
+
+int eld_jpeg_coef_u8(const uint8_t* rgb, int H, int W, int subsampling, const uint16_t* qtables, int16_t* coef, size_t coef_elems, void* stream);
+int eld_jpeg_hist_i16(const int16_t* coef, size_t coef_elems, int H, int W, int subsampling, int segment, uint32_t* hist, size_t hist_elems,
+                      void* stream);
+int eld_jpeg_pack_i16(const int16_t* coef, size_t coef_elems, int H, int W, int subsampling, int segment, const uint32_t* tables,
+                      const uint64_t* seg_bit, uint32_t* raw, size_t raw_dwords, int lds_bytes, void* stream);
 
 #ifdef __cplusplus
 }
