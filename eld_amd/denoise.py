@@ -8,7 +8,8 @@ denoiser for it (train_syn.py through the plugins).  Every device stage is a HIP
                   models/ELD_model.py:41-129)
     sRGB          util/process.py `process` (eld_isp_process; X-Trans: eld_isp_process_xtrans, the same pipeline on X-Trans binning) at
                   packed resolution, or with srgb_size='full' the same pipeline behind a demosaic at mosaic resolution
-                  (eld_render_bayer: Malvar-He-Cutler; eld_render_xtrans: normalised convolution on colour differences)
+                  (eld_render_bayer: Malvar-He-Cutler, or with demosaic='edge' eld_render_bayer_edge: edge-directed; eld_render_xtrans:
+                  normalised convolution on colour differences)
 
 Write-back rounding.  Per element v = float64(clip(x, 0, 1)) * (white - black) + black (exact).  rounding='reference' truncates as the
 reference's assignment into the uint16 raw_image_visible does (Bayer: the float64 expression; X-Trans: the reference evaluates it in
@@ -19,7 +20,8 @@ every code in [black, white] round-trips, for (black, white) = (512, 16383), (10
 Raw files: a DNG input (.dng) is decoded on the device by eld_amd.dng (no rawpy) and its tags fill what the command line and the
 sidecar leave open; every other format converts to DNG.  Mosaics also arrive as arrays (.npy, `raw.raw_image_visible`), with the values
 rawpy reports (raw_pattern, black_level_per_channel, camera_whitebalance, rgb_camera_matrix[:3, :3]) as arguments or a JSON sidecar.
-The sRGB output is the reference's `process`: at packed resolution by default, at mosaic resolution with --srgb-size full.
+The sRGB output is the reference's `process`: at packed resolution by default, at mosaic resolution with --srgb-size full
+(Bayer: Malvar-He-Cutler, or with --demosaic edge the edge-directed demosaic).
 
     python -m eld_amd.denoise --ckpt model.pt --cfa xtrans --black 1024 --white 16383 --ratio 100 [--wb R G B] [--ccm 9 values] [--bf16] \\
         [--srgb-size full] in.npy [more.npy] -o outdir
@@ -35,7 +37,7 @@ import numpy as np
 from . import _lib as L
 from .defects import as_defect_map, repair_device
 from .flatfield import LENS_MODES, as_flat_field
-from .isp import process, process_xtrans, render_bayer, render_xtrans, warp_rgb
+from .isp import DEMOSAICS, check_demosaic, process, process_xtrans, render_bayer, render_xtrans, warp_rgb
 from .mosaic import (DEFAULT_BLACK, DEFAULT_PATTERN, PLANES, as_u16 as _as_u16, check_cfa as _check_cfa,  # noqa: F401 (the names this module always had)
                      check_sides as _check_sides, levels as _levels)
 from .shading import as_dark_shading
@@ -195,7 +197,7 @@ def run_network(denoiser, x, chop=None):
 
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
                 chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None, shading=None, iso=None, flatfield=None,
-                lens='srgb', warp=None, jpeg=None):
+                lens='srgb', warp=None, jpeg=None, demosaic='mhc'):
     """Denoise uint16 sensor mosaics with a trained U-Net -- or, given an eld_amd.classical.ClassicalDenoiser in place of a Denoiser, with the
     classical baseline (Anscombe transform, non-local means, unbiased inverse on the sensor's codes instead of the input stage and the
     network; `chop` is then ignored, and 'packed' is the baseline's output in the network's convention).
@@ -234,6 +236,10 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                 rendering is also encoded as baseline JPEG on the device, before its copy to the host (eld_amd.jpeg.encode_jpeg), and the
                 result gains 'jpeg': a list of bytes, one file per frame.  It needs the sRGB output (wb and ccm) and not linear=True.
 
+    demosaic    'mhc' (default): the full-resolution Bayer render demosaics with Malvar-He-Cutler.  'edge': with the edge-directed demosaic
+                (eld_amd.isp.render_bayer(..., demosaic='edge')), which keeps fine oriented detail free of zipper; Bayer and
+                srgb_size='full' only.  warp, linear and jpeg take its output as they take the default's.
+
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
     _check_cfa(cfa)
@@ -249,6 +255,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         raise ValueError("srgb_size='full' renders sRGB: it needs both wb and ccm")
     if linear and srgb_size != 'full':
         raise ValueError("linear=True needs srgb_size='full'")
+    check_demosaic(demosaic, cfa, srgb_size)
     if warp is not None:
         from .dng_opcodes import Warp
         if not isinstance(warp, Warp):
@@ -336,7 +343,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     if wbs is not None and srgb_size == 'full':
         wt, ct = torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev)
         if cfa == 'bayer':
-            render = lambda c, **kw: render_bayer(out, pat, wt, c, **kw)
+            render = lambda c, **kw: render_bayer(out, pat, wt, c, demosaic=demosaic, **kw)
         else:
             render = lambda c, **kw: render_xtrans(out, wt, c, **kw)
         if warp is None:
@@ -375,7 +382,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
 SIDECAR_ALIASES = {'black_level_per_channel': 'black_level', 'white_level': 'white_point', 'camera_whitebalance': 'wb',
                    'rgb_camera_matrix': 'ccm', 'black': 'black_level', 'white': 'white_point'}
 SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size', 'defects',
-                'shading', 'iso', 'flatfield', 'lens', 'warp')
+                'shading', 'iso', 'flatfield', 'lens', 'warp', 'demosaic')
 
 
 def read_sidecar(path):
@@ -440,6 +447,7 @@ def build_parser():
     p.add_argument('--jpeg', type=int, nargs='?', const=90, metavar='Q', help='also write <name>_srgb.jpg: the sRGB rendering as baseline JPEG of quality Q (1..100, default 90), encoded on the device')
     p.add_argument('--jpeg-subsampling', choices=('444', '420'), help="chroma subsampling of --jpeg and --dng-preview (default '420')")
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
+    p.add_argument('--demosaic', choices=DEMOSAICS, help="of --srgb-size full on Bayer frames: Malvar-He-Cutler ('mhc', the default) or the edge-directed demosaic ('edge')")
     return p
 
 
@@ -452,7 +460,7 @@ def options_from(a):
     """parse_args on a namespace already parsed by build_parser() or a parser that extends it (eld_amd.classical)."""
     o = read_sidecar(a.meta) if a.meta else {}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
-           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'warp': getattr(a, 'warp', None), 'precision': 'bf16' if a.bf16 else None,
+           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'warp': getattr(a, 'warp', None), 'demosaic': getattr(a, 'demosaic', None), 'precision': 'bf16' if a.bf16 else None,
            'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
     o.update({k: v for k, v in cli.items() if v is not None})
     # below the command line and the sidecar, above the defaults: the tags of the first .dng input (all .dng inputs must agree on the sensor keys)
@@ -494,6 +502,8 @@ def options_from(a):
     if o.get('chop') == 'auto':
         o['chop'] = None
     _check_cfa(o['cfa'])
+    if o.get('demosaic') is not None:
+        check_demosaic(o['demosaic'], o['cfa'], o['srgb_size'])
     if o.get('raw_pattern') is not None:
         o['raw_pattern'] = np.asarray(o['raw_pattern']).reshape(2, 2).tolist()
     if o.get('black_level') is not None:
@@ -627,6 +637,8 @@ def run_frames(den, inputs, outdir, o):
         kw['flatfield'], kw['lens'] = as_flat_field(o['flatfield'], '--flatfield'), o.get('lens') or 'srgb'
     if o.get('jpeg') is not None:
         kw['jpeg'] = dict(o['jpeg'])
+    if o.get('demosaic') is not None:
+        kw['demosaic'] = o['demosaic']
     from .dng import COMPRESSION_CHOICES, is_dng, load_frame, write_dng
     dng_kw = {'compression': COMPRESSION_CHOICES[o.get('dng_compression') or 'none']}
     for path in inputs:

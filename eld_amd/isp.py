@@ -1,7 +1,8 @@
 """Raw -> sRGB ISP on the device: the reference's util/process.py:52-68 `process` (gains, binning, CCM, gamma / camera
 response, 8-bit quantisation) as one HBM-bound HIP kernel (csrc/eval.hip eld_isp_process).  Used by the sRGB training /
 evaluation stages (train_syn.py:55-58, models/ELD_model.py:230-233), and its X-Trans counterpart (process_xtrans) for eld_amd.denoise.
-render_bayer / render_xtrans are the same pipeline at MOSAIC resolution: a demosaic (csrc/demosaic.hip) in place of the binning; with
+render_bayer / render_xtrans are the same pipeline at MOSAIC resolution: a demosaic (csrc/demosaic.hip; for Bayer with demosaic='edge'
+csrc/demosaic_edge.hip) in place of the binning; with
 `warp=` the demosaiced camera RGB is resampled by a DNG WarpRectilinear before the matrix and the tone curve (warp_rgb, csrc/warp.hip)."""
 import ctypes
 
@@ -109,22 +110,46 @@ def _warped(render, warp, cam2rgbs, gamma, CRF, linear):
     return warp_rgb(render(), warp, cam2rgbs, gamma, CRF, linear)
 
 
-def render_bayer(bayer_images, raw_pattern, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False, warp=None):
+DEMOSAICS = ('mhc', 'edge')             # render_bayer's demosaic: Malvar-He-Cutler (the default) or the edge-directed one (csrc/demosaic_edge.hip)
+
+
+def check_demosaic(demosaic, cfa='bayer', srgb_size='full'):
+    """what every caller with a demosaic argument refuses before any device work"""
+    if not isinstance(demosaic, str) or demosaic not in DEMOSAICS:
+        raise ValueError('demosaic must be one of %r, got %r' % (DEMOSAICS, demosaic))
+    if demosaic == 'edge' and cfa != 'bayer':
+        raise ValueError("demosaic='edge' is a Bayer demosaic: cfa=%r renders with its own" % (cfa,))
+    if demosaic == 'edge' and srgb_size != 'full':
+        raise ValueError("demosaic='edge' belongs to the full-resolution render: it needs srgb_size='full', got %r" % (srgb_size,))
+
+
+def edge_tile():
+    """(rows, columns) of PACKED pixels in the tile one workgroup of eld_render_bayer_edge owns"""
+    th, tw = ctypes.c_int(), ctypes.c_int()
+    L.check(L.lib().eld_render_bayer_edge_tile(ctypes.byref(th), ctypes.byref(tw), None), 'eld_render_bayer_edge_tile')
+    return th.value // 2, tw.value // 2
+
+
+def render_bayer(bayer_images, raw_pattern, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False, warp=None, demosaic='mhc'):
     """`process` at mosaic resolution (csrc/demosaic.hip eld_render_bayer): gains and clamp, Malvar-He-Cutler demosaic with mirrored
     borders, then the CCM / gamma or CRF / quantiser of `process`.  bayer_images CUDA (N,4,h,w) float32 in the planes of raw_pattern (2x2
     rawpy codes, R 0, G1 1, B 2, G2 3, as the write-back takes it); wbs (N,4) by plane; cam2rgbs (N,3,3), or None with linear=True.
     Returns CUDA (N,3,2h,2w): uint8 codes, or with linear=True float32 linear RGB after the CCM (no clamp, no gamma).
-    warp: None, or an eld_amd.dng_opcodes.Warp: the demosaiced camera RGB is resampled by it (warp_rgb) before the matrix and the tone curve."""
+    warp: None, or an eld_amd.dng_opcodes.Warp: the demosaiced camera RGB is resampled by it (warp_rgb) before the matrix and the tone curve.
+    demosaic: 'mhc' (default), or 'edge': the edge-directed demosaic of csrc/demosaic_edge.hip eld_render_bayer_edge in
+    place of Malvar-He-Cutler; everything around it is the same, and packed sides of 1 are allowed."""
+    check_demosaic(demosaic)
     if warp is not None:
-        return _warped(lambda: render_bayer(bayer_images, raw_pattern, wbs, None, linear=True), warp, cam2rgbs, gamma, CRF, linear)
+        return _warped(lambda: render_bayer(bayer_images, raw_pattern, wbs, None, linear=True, demosaic=demosaic), warp, cam2rgbs, gamma, CRF, linear)
     x, wbs, ccm, out, mode = _render_out(bayer_images, 4, wbs, cam2rgbs, linear, 4)
     pat = [int(v) for v in np.asarray(raw_pattern).reshape(-1)]
     if len(pat) != 4:
         raise ValueError('raw_pattern must hold 2x2 codes, got %r' % (raw_pattern,))
     E, fs, n = _crf(CRF, x.device)
     N, _, h, w = x.shape
-    L.check(L.lib().eld_render_bayer(L.dptr(x), (ctypes.c_int * 4)(*pat), L.dptr(wbs), L.dptr(ccm), L.dptr(out), mode, N, h, w, float(gamma),
-                                     L.dptr(E), L.dptr(fs), n, L.cur_stream()), 'eld_render_bayer')
+    name = 'eld_render_bayer_edge' if demosaic == 'edge' else 'eld_render_bayer'
+    L.check(getattr(L.lib(), name)(L.dptr(x), (ctypes.c_int * 4)(*pat), L.dptr(wbs), L.dptr(ccm), L.dptr(out), mode, N, h, w, float(gamma),
+                                   L.dptr(E), L.dptr(fs), n, L.cur_stream()), name)
     return out
 
 

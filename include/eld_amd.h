@@ -67,7 +67,9 @@ extern "C" {
  * Still 8: eld_warp_rgb_f32 and EldWarp were added the same way (DNG WarpRectilinear on demosaiced camera RGB, followed by the renders' tail):
  * one new symbol, no existing call changed.
  * Still 8: eld_jpeg_coef_u8, eld_jpeg_hist_i16 and eld_jpeg_pack_i16 were added the same way (baseline JPEG of the uint8 sRGB render, encoded
- * on the device): three new symbols, no existing call changed. */
+ * on the device): three new symbols, no existing call changed.
+ * Still 8: eld_render_bayer_edge and eld_render_bayer_edge_tile were added the same way (the full-resolution Bayer render behind an
+ * edge-directed demosaic): two new symbols, no existing call changed. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -1178,6 +1180,36 @@ int eld_jpeg_hist_i16(const int16_t* coef, size_t coef_elems, int H, int W, int 
                       void* stream);
 int eld_jpeg_pack_i16(const int16_t* coef, size_t coef_elems, int H, int W, int subsampling, int segment, const uint32_t* tables,
                       const uint64_t* seg_bit, uint32_t* raw, size_t raw_dwords, int lds_bytes, void* stream);
+
+/* ---- Edge-directed Bayer demosaic for the full-resolution render (csrc/demosaic_edge.hip, csrc/demosaic_edge_dev.h) --------
+ * Appended without a change of ELD_ABI_VERSION: two new symbols, no existing call changed.  eld_render_bayer_edge is eld_render_bayer with
+ * another step 2: the same arguments, output modes, step 1 (v = min(max(p * gain, 0), 1)) and step 3 (the matrix, then for ELD_RENDER_SRGB8 the
+ * clamp, the gamma table / pow / CRF and the quantiser of eld_isp_process; camera RGB when ccms is NULL with ELD_RENDER_LINEAR_F32).
+ * Step 2, per mosaic site, float32, one rounding per operation, evaluated exactly as written (no FMA; the division is correctly rounded).
+ * Every stage is evaluated on v extended by mirroring without repeating the edge (index -1 -> 1, H -> H - 2, period 2 (H - 1), as NumPy's
+ * pad mode 'reflect'), which preserves CFA parity for any h, w >= 1; the stages address the extension up to 4 sites.  c is the site's own
+ * value, W E N S its 4-neighbours, WW EE NN SS those at distance 2:
+ *   A, every site:     a_h = (2*c - WW) - EE             a_v = (2*c - NN) - SS
+ *                      d_h = |W - E| + |a_h|             d_v = |N - S| + |a_v|
+ *   B, every site:     S_h, S_v = the sums of d_h, d_v over the 3x3 window; the nine terms are added to a zero in raster order (rows top to
+ *                      bottom, left to right)
+ *   C:                 G^ = c at G sites; at R and B sites
+ *                      g_h = (W + E)*0.5 + a_h*0.25      g_v = (N + S)*0.5 + a_v*0.25
+ *                      w_h = S_v*S_v + 1e-6f             w_v = S_h*S_h + 1e-6f
+ *                      G^  = g_h + (g_v - g_h) * (w_v / (w_h + w_v))
+ *   D:                 delta = c - G^ at R and B sites; for k in {R, B}:
+ *                      at a k site                                  c
+ *                      at the other colour's site                   G^ + ((delta_NW + delta_NE) + (delta_SW + delta_SE))*0.25
+ *                      at a G site with k to its left and right     G^ + (delta_W + delta_E)*0.5
+ *                      at a G site with k above and below           G^ + (delta_N + delta_S)*0.5
+ * Sampled values pass through unchanged; a frame of one colour on a dyadic grid comes back exact (equal gradients make the weight exactly
+ * 0.5, and it multiplies a zero); the output is finite for p * gain of any finite value (w_h + w_v >= 2e-6).
+ * ELD_EINVAL before any launch: as eld_render_bayer, except that h and w may be 1 (mosaic sides from 2) and must not exceed 2^28.
+ * eld_render_bayer_edge_tile (HOST, no device work): the tile of mosaic sites one workgroup owns and, when lds_bytes is not NULL, the LDS the
+ * kernel declares; ELD_EINVAL for a null tile_h or tile_w. */
+int eld_render_bayer_edge(const float* packed, const int* raw_pattern, const float* wbs, const float* ccms, void* out, int out_mode,
+                          int N, int h, int w, float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream);
+int eld_render_bayer_edge_tile(int* tile_h, int* tile_w, int* lds_bytes);
 
 #ifdef __cplusplus
 }
