@@ -205,6 +205,8 @@ SIGNATURES = {
     'eld_jpeg_pack_i16': (_i, [_vp, _sz, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _i, _vp]),
     'eld_render_bayer_edge': (_i, [_vp, C.POINTER(C.c_int), _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     'eld_render_bayer_edge_tile': (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'eld_render_xtrans_dir': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
+    'eld_render_xtrans_dir_tile': (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 

@@ -9,7 +9,7 @@ denoiser for it (train_syn.py through the plugins).  Every device stage is a HIP
     sRGB          util/process.py `process` (eld_isp_process; X-Trans: eld_isp_process_xtrans, the same pipeline on X-Trans binning) at
                   packed resolution, or with srgb_size='full' the same pipeline behind a demosaic at mosaic resolution
                   (eld_render_bayer: Malvar-He-Cutler, or with demosaic='edge' eld_render_bayer_edge: edge-directed; eld_render_xtrans:
-                  normalised convolution on colour differences)
+                  normalised convolution on colour differences, or with demosaic='directional' eld_render_xtrans_dir: directional)
 
 Write-back rounding.  Per element v = float64(clip(x, 0, 1)) * (white - black) + black (exact).  rounding='reference' truncates as the
 reference's assignment into the uint16 raw_image_visible does (Bayer: the float64 expression; X-Trans: the reference evaluates it in
@@ -21,7 +21,8 @@ Raw files: a DNG input (.dng) is decoded on the device by eld_amd.dng (no rawpy)
 sidecar leave open; every other format converts to DNG.  Mosaics also arrive as arrays (.npy, `raw.raw_image_visible`), with the values
 rawpy reports (raw_pattern, black_level_per_channel, camera_whitebalance, rgb_camera_matrix[:3, :3]) as arguments or a JSON sidecar.
 The sRGB output is the reference's `process`: at packed resolution by default, at mosaic resolution with --srgb-size full
-(Bayer: Malvar-He-Cutler, or with --demosaic edge the edge-directed demosaic).
+(Bayer: Malvar-He-Cutler, or with --demosaic edge the edge-directed demosaic; X-Trans: normalised convolution, or with
+--demosaic directional the directional demosaic).
 
     python -m eld_amd.denoise --ckpt model.pt --cfa xtrans --black 1024 --white 16383 --ratio 100 [--wb R G B] [--ccm 9 values] [--bf16] \\
         [--srgb-size full] in.npy [more.npy] -o outdir
@@ -236,9 +237,11 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                 rendering is also encoded as baseline JPEG on the device, before its copy to the host (eld_amd.jpeg.encode_jpeg), and the
                 result gains 'jpeg': a list of bytes, one file per frame.  It needs the sRGB output (wb and ccm) and not linear=True.
 
-    demosaic    'mhc' (default): the full-resolution Bayer render demosaics with Malvar-He-Cutler.  'edge': with the edge-directed demosaic
+    demosaic    'mhc' (default): the full-resolution render demosaics with its CFA's default (Bayer: Malvar-He-Cutler).  'edge': with the edge-directed demosaic
                 (eld_amd.isp.render_bayer(..., demosaic='edge')), which keeps fine oriented detail free of zipper; Bayer and
-                srgb_size='full' only.  warp, linear and jpeg take its output as they take the default's.
+                srgb_size='full' only.  'directional': the full-resolution X-Trans render demosaics with the directional demosaic
+                (eld_amd.isp.render_xtrans(..., demosaic='directional'); DESIGN.md sec. 33) in place of the isotropic normalised convolution;
+                X-Trans and srgb_size='full' only.  warp, linear and jpeg take either's output as they take the default's.
 
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
@@ -345,7 +348,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         if cfa == 'bayer':
             render = lambda c, **kw: render_bayer(out, pat, wt, c, demosaic=demosaic, **kw)
         else:
-            render = lambda c, **kw: render_xtrans(out, wt, c, **kw)
+            render = lambda c, **kw: render_xtrans(out, wt, c, demosaic=demosaic, **kw)
         if warp is None:
             srgb = render(ct, CRF=CRF)
             lin = render(ct, linear=True) if linear else None
@@ -447,7 +450,7 @@ def build_parser():
     p.add_argument('--jpeg', type=int, nargs='?', const=90, metavar='Q', help='also write <name>_srgb.jpg: the sRGB rendering as baseline JPEG of quality Q (1..100, default 90), encoded on the device')
     p.add_argument('--jpeg-subsampling', choices=('444', '420'), help="chroma subsampling of --jpeg and --dng-preview (default '420')")
     p.add_argument('--srgb-size', choices=SRGB_SIZES, help="sRGB at packed resolution (default) or demosaiced at mosaic resolution ('full')")
-    p.add_argument('--demosaic', choices=DEMOSAICS, help="of --srgb-size full on Bayer frames: Malvar-He-Cutler ('mhc', the default) or the edge-directed demosaic ('edge')")
+    p.add_argument('--demosaic', choices=DEMOSAICS, help="of --srgb-size full: the CFA's default ('mhc': Bayer Malvar-He-Cutler, X-Trans normalised convolution), the edge-directed demosaic ('edge', Bayer only) or the directional one ('directional', X-Trans only)")
     return p
 
 

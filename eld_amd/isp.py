@@ -2,7 +2,7 @@
 response, 8-bit quantisation) as one HBM-bound HIP kernel (csrc/eval.hip eld_isp_process).  Used by the sRGB training /
 evaluation stages (train_syn.py:55-58, models/ELD_model.py:230-233), and its X-Trans counterpart (process_xtrans) for eld_amd.denoise.
 render_bayer / render_xtrans are the same pipeline at MOSAIC resolution: a demosaic (csrc/demosaic.hip; for Bayer with demosaic='edge'
-csrc/demosaic_edge.hip) in place of the binning; with
+csrc/demosaic_edge.hip, for X-Trans with demosaic='directional' csrc/demosaic_xdir.hip) in place of the binning; with
 `warp=` the demosaiced camera RGB is resampled by a DNG WarpRectilinear before the matrix and the tone curve (warp_rgb, csrc/warp.hip)."""
 import ctypes
 
@@ -110,7 +110,9 @@ def _warped(render, warp, cam2rgbs, gamma, CRF, linear):
     return warp_rgb(render(), warp, cam2rgbs, gamma, CRF, linear)
 
 
-DEMOSAICS = ('mhc', 'edge')             # render_bayer's demosaic: Malvar-He-Cutler (the default) or the edge-directed one (csrc/demosaic_edge.hip)
+# the renders' demosaic: 'mhc', the CFA's default (Bayer: Malvar-He-Cutler; X-Trans: the normalised convolution); 'edge', the edge-directed
+# Bayer one (csrc/demosaic_edge.hip); 'directional', the directional X-Trans one (csrc/demosaic_xdir.hip)
+DEMOSAICS = ('mhc', 'edge', 'directional')
 
 
 def check_demosaic(demosaic, cfa='bayer', srgb_size='full'):
@@ -121,6 +123,10 @@ def check_demosaic(demosaic, cfa='bayer', srgb_size='full'):
         raise ValueError("demosaic='edge' is a Bayer demosaic: cfa=%r renders with its own" % (cfa,))
     if demosaic == 'edge' and srgb_size != 'full':
         raise ValueError("demosaic='edge' belongs to the full-resolution render: it needs srgb_size='full', got %r" % (srgb_size,))
+    if demosaic == 'directional' and cfa != 'xtrans':
+        raise ValueError("demosaic='directional' is an X-Trans demosaic: cfa=%r renders with its own" % (cfa,))
+    if demosaic == 'directional' and srgb_size != 'full':
+        raise ValueError("demosaic='directional' belongs to the full-resolution render: it needs srgb_size='full', got %r" % (srgb_size,))
 
 
 def edge_tile():
@@ -153,16 +159,27 @@ def render_bayer(bayer_images, raw_pattern, wbs, cam2rgbs, gamma=2.2, CRF=None, 
     return out
 
 
-def render_xtrans(packed, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False, warp=None):
+def xdir_tile():
+    """(rows, columns) of PACKED pixels in the tile one workgroup of eld_render_xtrans_dir owns"""
+    th, tw = ctypes.c_int(), ctypes.c_int()
+    L.check(L.lib().eld_render_xtrans_dir_tile(ctypes.byref(th), ctypes.byref(tw), None), 'eld_render_xtrans_dir_tile')
+    return th.value // 3, tw.value // 3
+
+
+def render_xtrans(packed, wbs, cam2rgbs, gamma=2.2, CRF=None, linear=False, warp=None, demosaic='mhc'):
     """`process_xtrans` at mosaic resolution (csrc/demosaic.hip eld_render_xtrans): gains by plane colour and clamp, a two-stage normalised
     convolution on colour differences (G from the 3x3, R - G and B - G from the 5x5 neighbourhood, windows clipped to the image), then
     the tail of `process`.  packed CUDA (N,9,h,w) float32 with even h and w (whole 6x6 cells); wbs (N,3); cam2rgbs (N,3,3), or None with
-    linear=True.  Returns CUDA (N,3,3h,3w): uint8 codes, or with linear=True float32 linear RGB after the CCM.  warp: as render_bayer's."""
+    linear=True.  Returns CUDA (N,3,3h,3w): uint8 codes, or with linear=True float32 linear RGB after the CCM.  warp: as render_bayer's.
+    demosaic: 'mhc' (default: the render above), or 'directional': the directional demosaic of csrc/demosaic_xdir.hip eld_render_xtrans_dir
+     in place of the normalised convolution of green; everything around it is the same."""
+    check_demosaic(demosaic, 'xtrans')
     if warp is not None:
-        return _warped(lambda: render_xtrans(packed, wbs, None, linear=True), warp, cam2rgbs, gamma, CRF, linear)
+        return _warped(lambda: render_xtrans(packed, wbs, None, linear=True, demosaic=demosaic), warp, cam2rgbs, gamma, CRF, linear)
     x, wbs, ccm, out, mode = _render_out(packed, 9, wbs, cam2rgbs, linear, 3)
     E, fs, n = _crf(CRF, x.device)
     N, _, h, w = x.shape
-    L.check(L.lib().eld_render_xtrans(L.dptr(x), L.dptr(wbs), L.dptr(ccm), L.dptr(out), mode, N, h, w, float(gamma), L.dptr(E), L.dptr(fs), n,
-                                      L.cur_stream()), 'eld_render_xtrans')
+    name = 'eld_render_xtrans_dir' if demosaic == 'directional' else 'eld_render_xtrans'
+    L.check(getattr(L.lib(), name)(L.dptr(x), L.dptr(wbs), L.dptr(ccm), L.dptr(out), mode, N, h, w, float(gamma), L.dptr(E), L.dptr(fs), n,
+                                   L.cur_stream()), name)
     return out

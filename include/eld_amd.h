@@ -1211,6 +1211,38 @@ int eld_render_bayer_edge(const float* packed, const int* raw_pattern, const flo
                           int N, int h, int w, float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream);
 int eld_render_bayer_edge_tile(int* tile_h, int* tile_w, int* lds_bytes);
 
+/* ---- Directional X-Trans demosaic for the full-resolution render (csrc/demosaic_xdir.hip, csrc/demosaic_xdir_dev.h) -------
+ * Appended without a change of ELD_ABI_VERSION: two new symbols, no existing call changed.  eld_render_xtrans_dir is eld_render_xtrans with
+ * another step 2: the same arguments, output modes, step 1 (v = min(max(p * gain, 0), 1), the gain by plane colour) and step 3 (the matrix,
+ * then for ELD_RENDER_SRGB8 the clamp, the gamma table / pow / CRF and the quantiser of eld_isp_process; camera RGB when ccms is NULL with
+ * ELD_RENDER_LINEAR_F32).
+ * Step 2, per mosaic site, float32, one rounding per operation, evaluated exactly as written (no FMA; the division is correctly rounded).
+ * Every stage is evaluated with full windows on v extended by 6 sites (one cell) with the mirror that keeps every site's colour: the 6x6 cell
+ * (row 0 = R B G B R G) is symmetric about the rows = 0 (mod 3) and the columns = 2 (mod 3) only, so
+ *     y < 0 -> -y      y >= H -> 2*(H - 3) - y      x < 0 -> 4 - x      x >= W -> 2*(W - 1) - x,
+ * repeated until the index is inside (a 6-site side needs two rounds).  v(k) is the value k sites along an axis from the site:
+ *   A, every site:     G0 = v at G sites; elsewhere sum(wt * v) / sum(wt) over the G sites of the 3x3 window, wt = [1 2 1] x [1 2 1]: the
+ *                      products are added to a zero in raster order (rows top to bottom, left to right), then one division
+ *   B, every site:     d_h = |G0_W - G0_E| + |(2*G0 - G0_WW) - G0_EE|          d_v likewise with N, S
+ *                      S_h, S_v = the sums of d_h, d_v over the 3x3 window, the nine terms added to a zero in raster order
+ *   C:                 G^ = v at G sites.  An R or B site has one solitary axis (both neighbours and both second neighbours are G) and one
+ *                      paired axis (one neighbour, a = -1 or +1, is G; the site at 2a has the site's colour, the one at -2a is G):
+ *                      solitary:  s1 = v(-1) + v(1)    s2 = v(-2) + v(2)    g = s1*0.5f + (s1 - s2)*(46/256)
+ *                      paired:    g = (v(a) + (v(-2a) - v(a))*(33/256)) + (v(0) - v(2a))*(92/256)
+ *                      with g_h along the row and g_v along the column:
+ *                      w_h = S_v*S_v + 1e-6f             w_v = S_h*S_h + 1e-6f
+ *                      G^  = g_h + (g_v - g_h) * (w_v / (w_h + w_v))
+ *   D:                 delta = v - G^ at R and B sites; for k in {R, B}: v at a k site, elsewhere
+ *                      G^ + sum(wt * delta) / sum(wt) over the k sites of the 5x5 window, wt = [1 2 3 2 1] x [1 2 3 2 1], added as in A
+ * Sampled values pass through unchanged; a frame of one colour comes back exact where the sums of stages A and D are (dyadic values: the
+ * axis estimates are a mean plus differences that vanish); the output is finite for p * gain of any finite value (w_h + w_v >= 2e-6).
+ * ELD_EINVAL before any launch: as eld_render_xtrans; h and w must not exceed 2^28.
+ * eld_render_xtrans_dir_tile (HOST, no device work): the tile of mosaic sites one workgroup owns (whole cells) and, when lds_bytes is not
+ * NULL, the LDS the kernel declares; ELD_EINVAL for a null tile_h or tile_w. */
+int eld_render_xtrans_dir(const float* packed, const float* wbs, const float* ccms, void* out, int out_mode, int N, int h, int w, float gamma,
+                          const float* crf_E, const float* crf_f, int crf_n, void* stream);
+int eld_render_xtrans_dir_tile(int* tile_h, int* tile_w, int* lds_bytes);
+
 #ifdef __cplusplus
 }
 #endif
