@@ -21,40 +21,15 @@ namespace {
 
 constexpr uint32_t PAD = 0xffffffffu;          // sorts after every stack sum (S <= 4096 * 65535 < 2^28) and every code
 
-// ---- X-Trans tables, derived from the index map of xtrans.h ----------------------------------------------------------------------------
+// ---- X-Trans tables, derived from the colour map of the cell (xtrans.h: XT.colour[6 * row + col]) ---------------------------------------------------
 constexpr int XT_MAXR = 3;                     // a (2R + 1)^2 window mask fits 64 bits up to R = 3
-
-struct XtCell { int colour[6][6]; };
-constexpr XtCell make_xt_cell() {
-    XtCell t{};
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) t.colour[r][c] = -1;
-    for (int c = 0; c < 5; ++c)
-        for (int pi = 0; pi < 2; ++pi)
-            for (int pj = 0; pj < 2; ++pj) t.colour[XT_RC[c][pi][pj][0]][XT_RC[c][pi][pj][1]] = (int)xt_colour(c);
-    for (int c = 5; c < 9; ++c)
-        for (int i = 0; i < 2; ++i)
-            for (int j = 0; j < 2; ++j) t.colour[3 * i + XT_RC3[c - 5][0]][3 * j + XT_RC3[c - 5][1]] = (int)xt_colour(c);
-    return t;
-}
-constexpr XtCell XT_CELL = make_xt_cell();
-constexpr bool xt_cell_complete() {
-    int n[3] = {0, 0, 0};
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) {
-            if (XT_CELL.colour[r][c] < 0 || XT_CELL.colour[r][c] > 2) return false;
-            ++n[XT_CELL.colour[r][c]];
-        }
-    return n[0] == 8 && n[1] == 20 && n[2] == 8;
-}
-static_assert(xt_cell_complete(), "xtrans.h must colour every site of the 6x6 cell: 8 R, 20 G, 8 B");
 
 // same-class taps of phase (py, px) in the (2R + 1)^2 window, centre excluded: bit = raster index (dy + R) * (2R + 1) + dx + R
 constexpr uint64_t xt_same_mask(int py, int px, int R) {
     uint64_t m = 0;
     for (int dy = -R; dy <= R; ++dy)
         for (int dx = -R; dx <= R; ++dx)
-            if ((dy || dx) && XT_CELL.colour[(py + dy + 12) % 6][(px + dx + 12) % 6] == XT_CELL.colour[py][px])
+            if ((dy || dx) && XT.colour[6 * ((py + dy + 12) % 6) + (px + dx + 12) % 6] == XT.colour[6 * py + px])
                 m |= 1ull << ((dy + R) * (2 * R + 1) + dx + R);
     return m;
 }
@@ -361,7 +336,7 @@ bool class_table(int period, const int* pattern, ClassTable* t) {
         const int k = pattern[i];
         if (k < 0 || k > 3) return false;
         const int col = k == 3 ? 1 : k;
-        if (col != XT_CELL.colour[i / 6][i % 6]) return false;
+        if (col != XT.colour[i]) return false;
         (i < 32 ? t->lo : t->hi) |= (uint64_t)col << (2 * (i < 32 ? i : i - 32));
     }
     t->R = XT_DR; t->step = 1;
@@ -435,7 +410,7 @@ extern "C" int eld_debug_xtrans_defect_tables(int* out, int n) {
     for (int py = 0; py < 6; ++py)
         for (int px = 0; px < 6; ++px) {
             int* o = out + 1 + 4 * (6 * py + px);
-            o[0] = XT_CELL.colour[py][px];
+            o[0] = XT.colour[6 * py + px];
             o[1] = XT_TAPS.count[py][px];
             o[2] = (int)(uint32_t)XT_TAPS.mask[py][px];
             o[3] = (int)(uint32_t)(XT_TAPS.mask[py][px] >> 32);

@@ -9,23 +9,7 @@
 #include "xtrans.h"
 
 namespace {
-#include "render_tail.h"                   // site_out, load_ccm, TAIL_*, render_tail: shared with warp.hip
-
-struct RenderArgs {
-    const float* packed;
-    const float* wbs;
-    const float* ccms;                 // NULL: no matrix (linear mode: the demosaiced camera RGB; sRGB mode: the identity)
-    void* out;
-    int mode, h, w;                    // packed sides
-    float inv_gamma;
-    const float* crf_E;
-    const float* crf_f;
-    int crf_n;
-    int pos[4];                        // Bayer: colour code (R 0, G1 1, B 2, G2 3) at cell position (0,0), (0,1), (1,0), (1,1)
-    int r_row;                         // Bayer: row parity of the R site
-};
-
-__device__ __forceinline__ float gain_clamp(float p, float gain) { return fminf(fmaxf(p * gain, 0.f), 1.f); }
+#include "render_args.h"                   // RenderArgs, BayerCell, gain_clamp, store_sites; with render_tail.h: site_out, load_ccm, TAIL_*, with_tail
 
 // ---- Bayer ---------------------------------------------------------------------------------------------------------------------------
 // A lane owns BAY_RUN consecutive packed columns of one packed row = a 2 x 8 block of mosaic sites, and reads the 3 x 6 packed
@@ -40,9 +24,11 @@ __device__ __forceinline__ int mirror(int x, int L) {           // -1 -> 1, -2 -
 }
 
 template <bool G00, bool VEC, int TAIL>
-__global__ __launch_bounds__(256) void render_bayer_kernel(RenderArgs a, int groups) {
+__global__ __launch_bounds__(256) void render_bayer_kernel(BayerArgs ba, int groups) {
+    const RenderArgs& a = ba.r;
+    const BayerCell& cell = ba.cell;
     __shared__ unsigned s_t[256];
-    if (TAIL == TAIL_TABLE) s_t[threadIdx.x] = ELD_GAMMA22_T[threadIdx.x];
+    stage_gamma_table<TAIL, 256>(s_t);
     __syncthreads();
     const int n = blockIdx.y, h = a.h, w = a.w;
     const unsigned idx = blockIdx.x * 256u + threadIdx.x;
@@ -52,10 +38,10 @@ __global__ __launch_bounds__(256) void render_bayer_kernel(RenderArgs a, int gro
     const float* src = a.packed + (size_t)n * 4 * hw;
     float gains[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) gains[k] = a.wbs[4 * n + a.pos[k]];
+    for (int k = 0; k < 4; ++k) gains[k] = a.wbs[4 * n + cell.pos[k]];
     float m[9];
-    load_ccm(a.ccms, n, m);
-    const double ig = (double)a.inv_gamma;
+    load_ccm(a.t.ccms, n, m);
+    const double ig = (double)a.t.inv_gamma;
 
     // p[dj][sy][sx][q]: the packed value at packed row j - 1 + dj, cell position (sy, sx), packed column 4i - 1 + q (mirrored at the borders),
     // after gain and clamp.  Mosaic site (2j - 2 + y, 8i - 2 + x) of the 6 x 12 window is p[y >> 1][y & 1][x & 1][x >> 1].
@@ -66,7 +52,7 @@ __global__ __launch_bounds__(256) void render_bayer_kernel(RenderArgs a, int gro
         for (int dj = 0; dj < 3; ++dj)
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
-                const float* row = src + (size_t)a.pos[s] * hw + (size_t)(j - 1 + dj) * w + c0;
+                const float* row = src + (size_t)cell.pos[s] * hw + (size_t)(j - 1 + dj) * w + c0;
                 const float4 v = *reinterpret_cast<const float4*>(row);
                 const float g = gains[s];
                 p[dj][s >> 1][s & 1][0] = gain_clamp(row[-1], g);
@@ -84,7 +70,7 @@ __global__ __launch_bounds__(256) void render_bayer_kernel(RenderArgs a, int gro
                 const int pr = mirror(2 * (j - 1 + dj) + sy, 2 * h) >> 1;
 #pragma unroll
                 for (int sx = 0; sx < 2; ++sx) {
-                    const float* row = src + (size_t)a.pos[2 * sy + sx] * hw + (size_t)pr * w;
+                    const float* row = src + (size_t)cell.pos[2 * sy + sx] * hw + (size_t)pr * w;
 #pragma unroll
                     for (int q = 0; q < BAY_RUN + 2; ++q) {
                         const int pc = mirror(2 * (c0 - 1 + q) + sx, 2 * w) >> 1;
@@ -106,7 +92,7 @@ __global__ __launch_bounds__(256) void render_bayer_kernel(RenderArgs a, int gro
             const float nn_ss = M(y - 2, x) + M(y + 2, x), ww_ee = M(y, x - 2) + M(y, x + 2);
             const float D = (M(y - 1, x - 1) + M(y - 1, x + 1)) + (M(y + 1, x - 1) + M(y + 1, x + 1));
             float r, g, b;
-            const bool r_in_row = a.r_row == oy;                   // launch-uniform
+            const bool r_in_row = cell.r_row == oy;                   // launch-uniform
             if ((((oy ^ ox) & 1) == 0) == G00) {                   // G site: R and B from the horizontal / vertical formula
                 const float hor = (((5.f * c + 4.f * w_e) + 0.5f * nn_ss) - (D + ww_ee)) * 0.125f;
                 const float ver = (((5.f * c + 4.f * n_s) + 0.5f * ww_ee) - (D + nn_ss)) * 0.125f;
@@ -121,7 +107,7 @@ __global__ __launch_bounds__(256) void render_bayer_kernel(RenderArgs a, int gro
                 b = r_in_row ? diag : c;
             }
             float t[3];
-            site_out<TAIL>(r, g, b, m, a.ccms != nullptr, a, ig, s_t, t);
+            site_out<TAIL>(r, g, b, m, a.t, ig, s_t, t);
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) o[ch][oy][ox] = t[ch];
         }
@@ -135,107 +121,18 @@ __global__ __launch_bounds__(256) void render_bayer_kernel(RenderArgs a, int gro
         for (int oy = 0; oy < 2; ++oy) {
             const size_t e = ((size_t)n * 3 + ch) * plane + (size_t)(2 * j + oy) * Wm + 2 * c0;
             const float(&v)[2 * BAY_RUN] = o[ch][oy];
-            if (TAIL == TAIL_LINEAR) {
-                float* d = (float*)a.out + e;
-                if (VEC) {
-                    reinterpret_cast<float4*>(d)[0] = make_float4(v[0], v[1], v[2], v[3]);
-                    reinterpret_cast<float4*>(d)[1] = make_float4(v[4], v[5], v[6], v[7]);
-                } else {
-#pragma unroll
-                    for (int q = 0; q < BAY_RUN; ++q)
-                        if (q < nv) reinterpret_cast<float2*>(d)[q] = make_float2(v[2 * q], v[2 * q + 1]);
-                }
+            if (VEC) {
+                store_sites<TAIL, 2 * BAY_RUN>(a.out, e, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
             } else {
-                unsigned char* d = (unsigned char*)a.out + e;
-                unsigned b2[BAY_RUN];
 #pragma unroll
-                for (int q = 0; q < BAY_RUN; ++q) b2[q] = (unsigned)v[2 * q] | ((unsigned)v[2 * q + 1] << 8);
-                if (VEC) {
-                    *reinterpret_cast<uint2*>(d) = make_uint2(b2[0] | (b2[1] << 16), b2[2] | (b2[3] << 16));
-                } else {
-#pragma unroll
-                    for (int q = 0; q < BAY_RUN; ++q)
-                        if (q < nv) reinterpret_cast<unsigned short*>(d)[q] = (unsigned short)b2[q];
-                }
+                for (int q = 0; q < BAY_RUN; ++q)
+                    if (q < nv) store_sites<TAIL, 2>(a.out, e + 2 * q, v[2 * q], v[2 * q + 1]);
             }
         }
 }
 
 // ---- X-Trans ---------------------------------------------------------------------------------------------------------------------------
-// Per-phase tables of the 6 x 6 cell, derived from xtrans.h at compile time (phase = 6 * row + col): the site's colour and packed plane,
-// the taps of its 3x3 window that are G sites and of its 5x5 window that are R / B sites (bit = raster index of the tap) and the sums of
-// their weights ([1 2 1] x [1 2 1], [1 2 3 2 1] x [1 2 3 2 1]) in the interior.  eld_debug_xtrans_demosaic_tables exports them.
-struct XtTables {
-    unsigned char colour[36], plane[36];
-    unsigned gmask[36], gsum[36];
-    unsigned cmask[2][36], csum[2][36];          // [0] R, [1] B
-};
-constexpr int W3K[3] = {1, 2, 1}, W5K[5] = {1, 2, 3, 2, 1};
-
-constexpr XtTables make_xt_tables() {
-    XtTables t{};
-    for (int i = 0; i < 36; ++i) t.plane[i] = 255;
-    for (int k = 0; k < 5; ++k)
-        for (int pi = 0; pi < 2; ++pi)
-            for (int pj = 0; pj < 2; ++pj) t.plane[6 * XT_RC[k][pi][pj][0] + XT_RC[k][pi][pj][1]] = (unsigned char)k;
-    for (int k = 5; k < 9; ++k)
-        for (int bi = 0; bi < 2; ++bi)
-            for (int bj = 0; bj < 2; ++bj) t.plane[6 * (3 * bi + XT_RC3[k - 5][0]) + 3 * bj + XT_RC3[k - 5][1]] = (unsigned char)k;
-    for (int i = 0; i < 36; ++i) t.colour[i] = (unsigned char)xt_colour(t.plane[i]);
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) {
-            const int ph = 6 * r + c;
-            for (int dy = -2; dy <= 2; ++dy)
-                for (int dx = -2; dx <= 2; ++dx) {
-                    const int col = t.colour[6 * ((r + dy + 6) % 6) + (c + dx + 6) % 6];
-                    if (col == 1) {
-                        if (dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1) {
-                            t.gmask[ph] |= 1u << (3 * (dy + 1) + dx + 1);
-                            t.gsum[ph] += W3K[dy + 1] * W3K[dx + 1];
-                        }
-                    } else {
-                        t.cmask[col >> 1][ph] |= 1u << (5 * (dy + 2) + dx + 2);
-                        t.csum[col >> 1][ph] += W5K[dy + 2] * W5K[dx + 2];
-                    }
-                }
-        }
-    return t;
-}
-constexpr XtTables XT = make_xt_tables();
-
-// every plane fills its places, and a mosaic site (Y, X) is packed pixel (Y / 3, X / 3) of plane XT.plane[phase]: the block parity of
-// XT_RC's [pi][pj] is the 3x3 block the position lies in
-constexpr bool xt_map_ok() {
-    for (int i = 0; i < 36; ++i)
-        if (XT.plane[i] > 8) return false;
-    for (int k = 0; k < 5; ++k)
-        for (int pi = 0; pi < 2; ++pi)
-            for (int pj = 0; pj < 2; ++pj)
-                if (XT_RC[k][pi][pj][0] / 3 != pi || XT_RC[k][pi][pj][1] / 3 != pj) return false;
-    return true;
-}
-static_assert(xt_map_ok(), "X-Trans index map: site (Y, X) must be packed pixel (Y / 3, X / 3)");
-
-// window coverage on frames of ch x cw whole cells: every clipped 3x3 window holds a G site, every clipped 5x5 window an R and a B site
-constexpr bool xt_covered(int ch, int cw) {
-    const int H = 6 * ch, W = 6 * cw;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            bool g = false, r = false, b = false;
-            for (int dy = -2; dy <= 2; ++dy)
-                for (int dx = -2; dx <= 2; ++dx) {
-                    const int yy = y + dy, xx = x + dx;
-                    if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
-                    const int col = XT.colour[6 * (yy % 6) + xx % 6];
-                    if (col == 1) g = g || (dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1);
-                    else if (col == 0) r = true;
-                    else b = true;
-                }
-            if (!g || !r || !b) return false;
-        }
-    return true;
-}
-static_assert(xt_covered(1, 1) && xt_covered(1, 3) && xt_covered(3, 1) && xt_covered(3, 3), "X-Trans window coverage");
+// The per-phase tables of the 6 x 6 cell are xtrans.h's XT, with the checks of the index map and of the window coverage the kernel stands on.
 
 // A workgroup of 128 threads owns a tile of XT_CH x XT_CW whole cells.  LDS holds v (after gain and clamp) of tile + halo 3 (= one
 // packed pixel on every side; zero outside the image) and d = v - G^ at the R / B sites of tile + halo 2 (zero outside the image).
@@ -271,7 +168,7 @@ __device__ __forceinline__ float xt_green(const float* s, int r, int c, int edge
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx)
             if ((XT.gmask[6 * r + c] >> (3 * (dy + 1) + dx + 1)) & 1u) {
-                const int wt = W3K[dy + 1] * W3K[dx + 1];
+                const int wt = XT_W3[dy + 1] * XT_W3[dx + 1];
                 acc = acc + (float)wt * s[dy * XT_LW + dx];
                 ws += tap_weight(r, c, dy, dx, wt, edge);
             }
@@ -316,28 +213,21 @@ __device__ __forceinline__ void xt_stage2_row(const float* sv, const float* sd, 
 #pragma unroll
                 for (int dx = -2; dx <= 2; ++dx)
                     if ((XT.cmask[k][ph] >> (5 * (dy + 2) + dx + 2)) & 1u) {
-                        const int wt = W5K[dy + 2] * W5K[dx + 2];
+                        const int wt = XT_W5[dy + 2] * XT_W5[dx + 2];
                         acc = acc + (float)wt * sd[l + dy * XT_LW + dx];
                         ws += tap_weight(r, c, dy, dx, wt, edge);
                     }
             rb[k] = g + acc / (float)ws;
         }
         float t[3];
-        site_out<TAIL>(rb[0], g, rb[1], m, a.ccms != nullptr, a, ig, s_t, t);
+        site_out<TAIL>(rb[0], g, rb[1], m, a.t, ig, s_t, t);
         o[0][c] = t[0]; o[1][c] = t[1]; o[2][c] = t[2];
     }
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
         const size_t e = e0 + ch * plane + (size_t)R * Wm;
-        if (TAIL == TAIL_LINEAR) {
-            float2* d = reinterpret_cast<float2*>((float*)a.out + e);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) d[q] = make_float2(o[ch][2 * q], o[ch][2 * q + 1]);
-        } else {
-            unsigned short* d = reinterpret_cast<unsigned short*>((unsigned char*)a.out + e);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) d[q] = (unsigned short)((unsigned)o[ch][2 * q] | ((unsigned)o[ch][2 * q + 1] << 8));
-        }
+        for (int q = 0; q < 3; ++q) store_sites<TAIL, 2>(a.out, e + 2 * q, o[ch][2 * q], o[ch][2 * q + 1]);
     }
 }
 
@@ -347,8 +237,7 @@ __global__ __launch_bounds__(XT_THREADS) void render_xtrans_kernel(RenderArgs a,
     __shared__ float sd[XT_LH * XT_LW];
     __shared__ unsigned s_t[256];
     const int tid = threadIdx.x;
-    if (TAIL == TAIL_TABLE)
-        for (int i = tid; i < 256; i += XT_THREADS) s_t[i] = ELD_GAMMA22_T[i];
+    stage_gamma_table<TAIL, XT_THREADS>(s_t);
     const int n = blockIdx.z, h = a.h, w = a.w;
     const int cy0 = blockIdx.y * XT_CH, cx0 = blockIdx.x * XT_CW;        // first cell of the tile
     const size_t hw = (size_t)h * w;
@@ -392,8 +281,8 @@ __global__ __launch_bounds__(XT_THREADS) void render_xtrans_kernel(RenderArgs a,
     if (cy >= cells_y || cx >= cells_x) return;
     const int edge = (cy == 0 ? 1 : 0) | (cy == cells_y - 1 ? 2 : 0) | (cx == 0 ? 4 : 0) | (cx == cells_x - 1 ? 8 : 0);
     float m[9];
-    load_ccm(a.ccms, n, m);
-    const double ig = (double)a.inv_gamma;
+    load_ccm(a.t.ccms, n, m);
+    const double ig = (double)a.t.inv_gamma;
     const int Wm = 3 * w;
     const size_t plane = (size_t)9 * hw;
     const int l0 = (6 * cr + 3) * XT_LW + 6 * cc + 3;                     // the cell's first site in LDS
@@ -403,68 +292,42 @@ __global__ __launch_bounds__(XT_THREADS) void render_xtrans_kernel(RenderArgs a,
     xt_stage2_row<TAIL, 4>(sv, sd, s_t, a, m, ig, l0, e0, plane, Wm, edge); xt_stage2_row<TAIL, 5>(sv, sd, s_t, a, m, ig, l0, e0, plane, Wm, edge);
 }
 
-// what both entry points refuse before any launch
-int render_args_bad(const void* packed, const void* wbs, const void* ccms, const void* out, int out_mode, int N, int h, int w, float gamma,
-                    const float* crf_E, const float* crf_f, int crf_n) {
-    if (!packed || !wbs || !out) return 1;
-    if (((uintptr_t)packed & 15) || ((uintptr_t)out & 15) || ((uintptr_t)wbs & 3)) return 1;
-    if (N < 1 || N > 65535 || h < 2 || w < 2) return 1;
-    return tail_args_bad(ccms, out_mode, gamma, crf_E, crf_f, crf_n);
-}
 }  // namespace
 
 extern "C" int eld_render_bayer(const float* packed, const int* raw_pattern, const float* wbs, const float* ccms, void* out, int out_mode,
                                 int N, int h, int w, float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream) {
-    if (render_args_bad(packed, wbs, ccms, out, out_mode, N, h, w, gamma, crf_E, crf_f, crf_n) || !raw_pattern) return ELD_EINVAL;
-    int seen = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (raw_pattern[k] < 0 || raw_pattern[k] > 3) return ELD_EINVAL;
-        seen |= 1 << raw_pattern[k];
-    }
-    if (seen != 15) return ELD_EINVAL;
-    // a Bayer cell has its two greens on a diagonal
-    if ((raw_pattern[0] & 1) != (raw_pattern[3] & 1) || (raw_pattern[1] & 1) != (raw_pattern[2] & 1)) return ELD_EINVAL;
+    BayerArgs a{{packed, wbs, tail_args(ccms, gamma, crf_E, crf_f, crf_n), out, h, w}, {}};
+    if (render_args_bad(packed, wbs, ccms, out, out_mode, N, gamma, crf_E, crf_f, crf_n) || h < 2 || w < 2) return ELD_EINVAL;
+    if (!bayer_cell(raw_pattern, &a.cell)) return ELD_EINVAL;
     const int groups = (w + BAY_RUN - 1) / BAY_RUN;
     if ((long long)h * groups > 0x7fffffffLL - 256) return ELD_EINVAL;
-    RenderArgs a{};
-    a.packed = packed; a.wbs = wbs; a.ccms = ccms; a.out = out; a.mode = out_mode; a.h = h; a.w = w;
-    a.inv_gamma = (float)(1.0 / (double)gamma); a.crf_E = crf_E; a.crf_f = crf_f; a.crf_n = crf_n;
-    for (int k = 0; k < 4; ++k) {
-        a.pos[k] = raw_pattern[k];
-        if (raw_pattern[k] == 0) a.r_row = k >> 1;
-    }
-    const bool g00 = (raw_pattern[0] & 1) != 0;
     const bool vec = w % BAY_RUN == 0;                                     // then every run is whole and every row of every plane 16-byte aligned
     const dim3 grid((unsigned)(((long long)h * groups + 255) / 256), N), block(256);
     hipStream_t st = as_stream(stream);
-    const int tail = render_tail(out_mode, gamma, crf_n);
-#define BAYER_CASE(G, V, T) \
-    if (g00 == G && vec == V && tail == T) { ELD_LAUNCH((render_bayer_kernel<G, V, T>), grid, block, 0, st, a, groups); }
-#define BAYER_TAILS(G, V) BAYER_CASE(G, V, TAIL_LINEAR) BAYER_CASE(G, V, TAIL_TABLE) BAYER_CASE(G, V, TAIL_GENERAL)
-    BAYER_TAILS(true, true) BAYER_TAILS(true, false) BAYER_TAILS(false, true) BAYER_TAILS(false, false)
-#undef BAYER_TAILS
-#undef BAYER_CASE
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return with_tail(render_tail(out_mode, gamma, crf_n), [&](auto T) {
+        constexpr int TAIL = decltype(T)::value;
+        auto kern = a.cell.g00 ? (vec ? render_bayer_kernel<true, true, TAIL> : render_bayer_kernel<true, false, TAIL>)
+                        : (vec ? render_bayer_kernel<false, true, TAIL> : render_bayer_kernel<false, false, TAIL>);
+        ELD_LAUNCH(kern, grid, block, 0, st, a, groups);
+        ELD_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 extern "C" int eld_render_xtrans(const float* packed, const float* wbs, const float* ccms, void* out, int out_mode, int N, int h, int w,
                                  float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream) {
-    if (render_args_bad(packed, wbs, ccms, out, out_mode, N, h, w, gamma, crf_E, crf_f, crf_n) || (h & 1) || (w & 1)) return ELD_EINVAL;
+    if (render_args_bad(packed, wbs, ccms, out, out_mode, N, gamma, crf_E, crf_f, crf_n) || h < 2 || w < 2 || (h & 1) || (w & 1)) return ELD_EINVAL;
     const int cells_y = h / 2, cells_x = w / 2;
     const unsigned gy = (unsigned)((cells_y + XT_CH - 1) / XT_CH);
     if (gy > 65535u) return ELD_EINVAL;
-    RenderArgs a{};
-    a.packed = packed; a.wbs = wbs; a.ccms = ccms; a.out = out; a.mode = out_mode; a.h = h; a.w = w;
-    a.inv_gamma = (float)(1.0 / (double)gamma); a.crf_E = crf_E; a.crf_f = crf_f; a.crf_n = crf_n;
+    const RenderArgs a{packed, wbs, tail_args(ccms, gamma, crf_E, crf_f, crf_n), out, h, w};
     const dim3 grid((unsigned)((cells_x + XT_CW - 1) / XT_CW), gy, N), block(XT_THREADS);
     hipStream_t st = as_stream(stream);
-    const int tail = render_tail(out_mode, gamma, crf_n);
-    if (tail == TAIL_LINEAR) { ELD_LAUNCH(render_xtrans_kernel<TAIL_LINEAR>, grid, block, 0, st, a, cells_y, cells_x); }
-    else if (tail == TAIL_TABLE) { ELD_LAUNCH(render_xtrans_kernel<TAIL_TABLE>, grid, block, 0, st, a, cells_y, cells_x); }
-    else { ELD_LAUNCH(render_xtrans_kernel<TAIL_GENERAL>, grid, block, 0, st, a, cells_y, cells_x); }
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return with_tail(render_tail(out_mode, gamma, crf_n), [&](auto T) {
+        ELD_LAUNCH(render_xtrans_kernel<decltype(T)::value>, grid, block, 0, st, a, cells_y, cells_x);
+        ELD_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // HOST, no device work: the 36 x 8 per-phase table rows (colour, plane, G mask, G weight sum, R mask, R weight sum, B mask, B weight sum)

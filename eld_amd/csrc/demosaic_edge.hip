@@ -19,22 +19,7 @@
 #include "demosaic_edge_dev.h"
 
 namespace {
-#include "render_tail.h"                   // site_out, load_ccm, TAIL_*, render_tail, tail_args_bad: shared with demosaic.hip and warp.hip
-
-struct EdgeArgs {
-    const float* packed;
-    const float* wbs;
-    const float* ccms;                 // NULL: no matrix (linear mode: the demosaiced camera RGB; sRGB mode: the identity)
-    void* out;
-    int h, w;                          // packed sides
-    float inv_gamma;
-    const float* crf_E;
-    const float* crf_f;
-    int crf_n;
-    int pos[4];                        // colour code (R 0, G1 1, B 2, G2 3) = packed plane at cell position (0,0), (0,1), (1,0), (1,1)
-    int r_row;                         // row parity of the R site
-    int wide;                          // Wm % 4 == 0: every lane's 4 sites exist and start 16-byte (float32) / 4-byte (codes) aligned
-};
+#include "render_args.h"                   // RenderArgs, BayerCell, gain_clamp, store_sites; with render_tail.h: site_out, load_ccm, TAIL_*, with_tail
 
 constexpr int EDGE_TH = 16, EDGE_TW = 64, EDGE_THREADS = 256;
 constexpr int EV_H = EDGE_TH + 2 * EDGE_HALO, EV_W = EDGE_TW + 2 * EDGE_HALO, EV_P = EV_W + 1;        // v: tile + 4
@@ -46,13 +31,11 @@ static_assert(EDGE_THREADS / ELD_WAVE == 4 && EDGE_TW / 4 == 16 && EDGE_TH == 16
 static_assert(EV_P % 2 == 1 && ED_P % 2 == 1 && EG_P % 2 == 1, "odd pitches");
 static_assert(2 * EDGE_LDS_BYTES <= 160 * 1024, "at least two workgroups per CU");
 
-__device__ __forceinline__ float gain_clamp(float p, float gain) { return fminf(fmaxf(p * gain, 0.f), 1.f); }
-
 // stage D and the tail of the lane's 4 sites (row ty of the tile, columns tx .. tx + 3, tx % 4 == 0); OY: the row's parity
 template <bool G00, int TAIL, int OY>
-__device__ __forceinline__ void edge_row_out(const float* sv, const float* sg, const unsigned* s_t, const EdgeArgs& a, const float (&m)[9], double ig,
-                                             int ty, int tx, float (&o)[3][4]) {
-    const bool r_in_row = a.r_row == OY;                           // launch-uniform
+__device__ __forceinline__ void edge_row_out(const float* sv, const float* sg, const unsigned* s_t, const TailArgs& a, int r_row, const float (&m)[9],
+                                             double ig, int ty, int tx, float (&o)[3][4]) {
+    const bool r_in_row = r_row == OY;                           // launch-uniform
 #pragma unroll
     for (int ox = 0; ox < 4; ++ox) {
         const float* c = sv + (ty + EDGE_HALO) * EV_P + tx + ox + EDGE_HALO;
@@ -71,21 +54,23 @@ __device__ __forceinline__ void edge_row_out(const float* sv, const float* sg, c
             b = r_in_row ? other : c[0];
         }
         float t[3];
-        site_out<TAIL>(r, gg, b, m, a.ccms != nullptr, a, ig, s_t, t);
+        site_out<TAIL>(r, gg, b, m, a, ig, s_t, t);
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) o[ch][ox] = t[ch];
     }
 }
 
 template <bool G00, int TAIL>
-__global__ __launch_bounds__(EDGE_THREADS) void render_bayer_edge_kernel(EdgeArgs a) {
+__global__ __launch_bounds__(EDGE_THREADS) void render_bayer_edge_kernel(BayerArgs ba, int wide) {
+    const RenderArgs& a = ba.r;
+    const BayerCell& cell = ba.cell;
     __shared__ float sv[EV_H * EV_P];
     __shared__ float sdh[ED_H * ED_P];
     __shared__ float sdv[ED_H * ED_P];
     __shared__ float sg[EG_H * EG_P];
     __shared__ unsigned s_t[256];
     const int tid = threadIdx.x;
-    if (TAIL == TAIL_TABLE) s_t[tid] = ELD_GAMMA22_T[tid];
+    stage_gamma_table<TAIL, EDGE_THREADS>(s_t);
     const int n = blockIdx.z, h = a.h, w = a.w, Hm = 2 * h, Wm = 2 * w;
     const int y0 = blockIdx.y * EDGE_TH, x0 = blockIdx.x * EDGE_TW;           // the tile's first site; both even
     const size_t hw = (size_t)h * w;
@@ -95,8 +80,8 @@ __global__ __launch_bounds__(EDGE_THREADS) void render_bayer_edge_kernel(EdgeArg
     // parity, so the site at cell position (sy, sx) of the extended tile is packed pixel (Y >> 1, X >> 1) of that position's plane.
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        const float* plane = src + (size_t)a.pos[s] * hw;
-        const float gain = a.wbs[4 * n + a.pos[s]];
+        const float* plane = src + (size_t)cell.pos[s] * hw;
+        const float gain = a.wbs[4 * n + cell.pos[s]];
         for (int it = tid; it < (EV_H / 2) * (EV_W / 2); it += EDGE_THREADS) {
             const int pr = it / (EV_W / 2), pc = it - pr * (EV_W / 2);
             const int ly = 2 * pr + (s >> 1), lx = 2 * pc + (s & 1);
@@ -131,11 +116,11 @@ __global__ __launch_bounds__(EDGE_THREADS) void render_bayer_edge_kernel(EdgeArg
     const int Y = y0 + ty, X = x0 + tx;
     if (Y >= Hm || X >= Wm) return;
     float m[9];
-    load_ccm(a.ccms, n, m);
-    const double ig = (double)a.inv_gamma;
+    load_ccm(a.t.ccms, n, m);
+    const double ig = (double)a.t.inv_gamma;
     float o[3][4];
-    if (wv & 1) edge_row_out<G00, TAIL, 1>(sv, sg, s_t, a, m, ig, ty, tx, o);
-    else edge_row_out<G00, TAIL, 0>(sv, sg, s_t, a, m, ig, ty, tx, o);
+    if (wv & 1) edge_row_out<G00, TAIL, 1>(sv, sg, s_t, a.t, cell.r_row, m, ig, ty, tx, o);
+    else edge_row_out<G00, TAIL, 0>(sv, sg, s_t, a.t, cell.r_row, m, ig, ty, tx, o);
 
     // Wm is even and X a multiple of 4: a lane's sites are 4, or the 2 in front of the right edge of a frame with Wm % 4 == 2
     const size_t plane = (size_t)4 * hw;                           // Hm * Wm, a multiple of 4
@@ -144,23 +129,11 @@ __global__ __launch_bounds__(EDGE_THREADS) void render_bayer_edge_kernel(EdgeArg
     for (int ch = 0; ch < 3; ++ch) {
         const size_t e = ((size_t)n * 3 + ch) * plane + (size_t)Y * Wm + X;
         const float(&v)[4] = o[ch];
-        if (TAIL == TAIL_LINEAR) {
-            float* d = (float*)a.out + e;
-            if (a.wide) {
-                *reinterpret_cast<float4*>(d) = make_float4(v[0], v[1], v[2], v[3]);
-            } else {                                               // 8-byte aligned: e is even
-                reinterpret_cast<float2*>(d)[0] = make_float2(v[0], v[1]);
-                if (pair2) reinterpret_cast<float2*>(d)[1] = make_float2(v[2], v[3]);
-            }
+        if (wide) {
+            store_sites<TAIL, 4>(a.out, e, v[0], v[1], v[2], v[3]);
         } else {
-            unsigned char* d = (unsigned char*)a.out + e;
-            const unsigned lo = (unsigned)v[0] | ((unsigned)v[1] << 8), hi = (unsigned)v[2] | ((unsigned)v[3] << 8);
-            if (a.wide) {
-                *reinterpret_cast<unsigned*>(d) = lo | (hi << 16);
-            } else {
-                reinterpret_cast<unsigned short*>(d)[0] = (unsigned short)lo;
-                if (pair2) reinterpret_cast<unsigned short*>(d)[1] = (unsigned short)hi;
-            }
+            store_sites<TAIL, 2>(a.out, e, v[0], v[1]);
+            if (pair2) store_sites<TAIL, 2>(a.out, e + 2, v[2], v[3]);
         }
     }
 }
@@ -168,39 +141,22 @@ __global__ __launch_bounds__(EDGE_THREADS) void render_bayer_edge_kernel(EdgeArg
 
 extern "C" int eld_render_bayer_edge(const float* packed, const int* raw_pattern, const float* wbs, const float* ccms, void* out, int out_mode,
                                      int N, int h, int w, float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream) {
-    if (!packed || !wbs || !out || !raw_pattern) return ELD_EINVAL;
-    if (((uintptr_t)packed & 15) || ((uintptr_t)out & 15) || ((uintptr_t)wbs & 3)) return ELD_EINVAL;
-    if (N < 1 || N > 65535 || h < 1 || w < 1 || h > (1 << 28) || w > (1 << 28)) return ELD_EINVAL;      // edge_reflect's period 2 (2h - 1) is an int
-    if (tail_args_bad(ccms, out_mode, gamma, crf_E, crf_f, crf_n)) return ELD_EINVAL;
-    int seen = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (raw_pattern[k] < 0 || raw_pattern[k] > 3) return ELD_EINVAL;
-        seen |= 1 << raw_pattern[k];
-    }
-    if (seen != 15) return ELD_EINVAL;
-    // a Bayer cell has its two greens on a diagonal
-    if ((raw_pattern[0] & 1) != (raw_pattern[3] & 1) || (raw_pattern[1] & 1) != (raw_pattern[2] & 1)) return ELD_EINVAL;
+    BayerArgs a{{packed, wbs, tail_args(ccms, gamma, crf_E, crf_f, crf_n), out, h, w}, {}};
+    if (render_args_bad(packed, wbs, ccms, out, out_mode, N, gamma, crf_E, crf_f, crf_n) || h < 1 || w < 1) return ELD_EINVAL;
+    if (h > (1 << 28) || w > (1 << 28)) return ELD_EINVAL;                 // edge_reflect's period 2 (2h - 1) is an int
+    if (!bayer_cell(raw_pattern, &a.cell)) return ELD_EINVAL;
     const long long gx = (2LL * w + EDGE_TW - 1) / EDGE_TW, gy = (2LL * h + EDGE_TH - 1) / EDGE_TH;
     if (gy > 65535 || gx > 0x7fffffffLL) return ELD_EINVAL;
-    EdgeArgs a{};
-    a.packed = packed; a.wbs = wbs; a.ccms = ccms; a.out = out; a.h = h; a.w = w;
-    a.inv_gamma = (float)(1.0 / (double)gamma); a.crf_E = crf_E; a.crf_f = crf_f; a.crf_n = crf_n;
-    for (int k = 0; k < 4; ++k) {
-        a.pos[k] = raw_pattern[k];
-        if (raw_pattern[k] == 0) a.r_row = k >> 1;
-    }
-    a.wide = w % 2 == 0;
-    const bool g00 = (raw_pattern[0] & 1) != 0;
+    const int wide = w % 2 == 0;           // Wm % 4 == 0: every lane's 4 sites exist and start 16-byte (float32) / 4-byte (codes) aligned
     const dim3 grid((unsigned)gx, (unsigned)gy, N), block(EDGE_THREADS);
     hipStream_t st = as_stream(stream);
-    const int tail = render_tail(out_mode, gamma, crf_n);
-#define EDGE_CASE(G, T) \
-    if (g00 == G && tail == T) { ELD_LAUNCH((render_bayer_edge_kernel<G, T>), grid, block, 0, st, a); }
-    EDGE_CASE(true, TAIL_LINEAR) EDGE_CASE(true, TAIL_TABLE) EDGE_CASE(true, TAIL_GENERAL)
-    EDGE_CASE(false, TAIL_LINEAR) EDGE_CASE(false, TAIL_TABLE) EDGE_CASE(false, TAIL_GENERAL)
-#undef EDGE_CASE
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return with_tail(render_tail(out_mode, gamma, crf_n), [&](auto T) {
+        constexpr int TAIL = decltype(T)::value;
+        auto kern = a.cell.g00 ? render_bayer_edge_kernel<true, TAIL> : render_bayer_edge_kernel<false, TAIL>;
+        ELD_LAUNCH(kern, grid, block, 0, st, a, wide);
+        ELD_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // HOST, no device work: the tile of one workgroup in mosaic sites and the LDS it declares

@@ -19,19 +19,7 @@
 #include "demosaic_xdir_dev.h"
 
 namespace {
-#include "render_tail.h"                   // site_out, load_ccm, TAIL_*, render_tail, tail_args_bad: shared with demosaic.hip and warp.hip
-
-struct XdirArgs {
-    const float* packed;
-    const float* wbs;
-    const float* ccms;                 // NULL: no matrix (linear mode: the demosaiced camera RGB; sRGB mode: the identity)
-    void* out;
-    int h, w;                          // packed sides
-    float inv_gamma;
-    const float* crf_E;
-    const float* crf_f;
-    int crf_n;
-};
+#include "render_args.h"                   // RenderArgs, gain_clamp, store_sites; with render_tail.h: site_out, load_ccm, TAIL_*, with_tail
 
 constexpr int XD_CH = 4, XD_CW = 16, XD_THREADS = 384;
 constexpr int XD_TH = 6 * XD_CH, XD_TW = 6 * XD_CW;
@@ -44,8 +32,6 @@ static_assert(XD_THREADS == 6 * ELD_WAVE && XD_CH * XD_CW == ELD_WAVE, "a wave p
 static_assert(XV_H == 6 * XE_CH && XV_W == 6 * XE_CW, "v is whole cells");
 static_assert(XDIR_LDS_BYTES <= 64 * 1024 && 2 * XDIR_LDS_BYTES <= 160 * 1024, "static LDS; two workgroups per CU");
 
-__device__ __forceinline__ float gain_clamp(float p, float gain) { return fminf(fmaxf(p * gain, 0.f), 1.f); }
-
 // stage A, row R of the cell whose first site is (ly0, lx0) of v: G0 at its sites that lie in tile + 5
 template <int R>
 __device__ __forceinline__ void xd_stage_a(const float* sv, float* sg, int ly0, int lx0) {
@@ -56,7 +42,7 @@ __device__ __forceinline__ void xd_stage_a(const float* sv, float* sg, int ly0, 
         const int lx = lx0 + c;
         if (lx < 1 || lx >= XV_W - 1) continue;
         const float* s = sv + ly * XV_W + lx;
-        sg[(ly - 1) * XG_W + lx - 1] = XDIR.colour[6 * R + c] == 1 ? s[0] : xdir_green0(s, XV_W, 6 * R + c);
+        sg[(ly - 1) * XG_W + lx - 1] = XT.colour[6 * R + c] == 1 ? s[0] : xdir_green0(s, XV_W, 6 * R + c);
     }
 }
 
@@ -67,7 +53,7 @@ __device__ __forceinline__ void xd_stage_c(const float* sv, const float* sdh, co
     if (ly < 4 || ly >= XV_H - 4) return;
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-        if (XDIR.colour[6 * R + c] == 1) continue;
+        if (XT.colour[6 * R + c] == 1) continue;
         const int lx = lx0 + c;
         if (lx < 4 || lx >= XV_W - 4) continue;
         const int d = (ly - 3) * XB_W + lx - 3;
@@ -84,7 +70,7 @@ __device__ __forceinline__ void xd_stage_d(const float* sv, const float* sg, int
         const int ph = 6 * r + c;
         const float* s = sv + (ly0 + r) * XV_W + lx0 + c;
         const float* gp = sg + (ly0 + r - 1) * XG_W + lx0 + c - 1;
-        const int col = XDIR.colour[ph];
+        const int col = XT.colour[ph];
         const float g = col == 1 ? s[0] : gp[0];
         cam[0][c] = col == 0 ? s[0] : g + xdir_chroma(s, XV_W, gp, XG_W, ph, 0);
         cam[1][c] = g;
@@ -95,29 +81,19 @@ __device__ __forceinline__ void xd_stage_d(const float* sv, const float* sg, int
 // the tail of those six sites, stored as three 2-site vectors per colour plane.  Outside the switch over the cell's rows: the six waves share
 // one copy of the matrix and the tone curve instead of running six.
 template <int TAIL>
-__device__ __forceinline__ void xd_row_out(const float (&cam)[3][6], const unsigned* s_t, const XdirArgs& a, const float (&m)[9], double ig, size_t e0,
+__device__ __forceinline__ void xd_row_out(const float (&cam)[3][6], const unsigned* s_t, const RenderArgs& a, const float (&m)[9], double ig, size_t e0,
                                            size_t plane) {
     float o[3][6];
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
         float t[3];
-        site_out<TAIL>(cam[0][c], cam[1][c], cam[2][c], m, a.ccms != nullptr, a, ig, s_t, t);
+        site_out<TAIL>(cam[0][c], cam[1][c], cam[2][c], m, a.t, ig, s_t, t);
         o[0][c] = t[0]; o[1][c] = t[1]; o[2][c] = t[2];
     }
-    // Wm, the site's column and the plane size are even: every pair is 8-byte (float32) / 2-byte (codes) aligned
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-        const size_t e = e0 + ch * plane;
-        if (TAIL == TAIL_LINEAR) {
-            float2* d = reinterpret_cast<float2*>((float*)a.out + e);
+    for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
-            for (int q = 0; q < 3; ++q) d[q] = make_float2(o[ch][2 * q], o[ch][2 * q + 1]);
-        } else {
-            unsigned short* d = reinterpret_cast<unsigned short*>((unsigned char*)a.out + e);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) d[q] = (unsigned short)((unsigned)o[ch][2 * q] | ((unsigned)o[ch][2 * q + 1] << 8));
-        }
-    }
+        for (int q = 0; q < 3; ++q) store_sites<TAIL, 2>(a.out, e0 + ch * plane + 2 * q, o[ch][2 * q], o[ch][2 * q + 1]);
 }
 
 // the wave's row of the cell as a template argument: wv is wave-uniform
@@ -132,15 +108,14 @@ __device__ __forceinline__ void xd_row_out(const float (&cam)[3][6], const unsig
     }
 
 template <int TAIL>
-__global__ __launch_bounds__(XD_THREADS) void render_xtrans_dir_kernel(XdirArgs a, int cells_y, int cells_x) {
+__global__ __launch_bounds__(XD_THREADS) void render_xtrans_dir_kernel(RenderArgs a, int cells_y, int cells_x) {
     __shared__ float sv[XV_H * XV_W];
     __shared__ float sg[XG_H * XG_W];
     __shared__ float sdh[XB_H * XB_W];
     __shared__ float sdv[XB_H * XB_W];
     __shared__ unsigned s_t[256];
     const int tid = threadIdx.x;
-    if (TAIL == TAIL_TABLE)
-        if (tid < 256) s_t[tid] = ELD_GAMMA22_T[tid];
+    stage_gamma_table<TAIL, XD_THREADS>(s_t);
     const int n = blockIdx.z, h = a.h, w = a.w, Hm = 3 * h, Wm = 3 * w;
     const int y0 = 6 * XD_CH * blockIdx.y, x0 = 6 * XD_CW * blockIdx.x;              // the tile's first site
     const size_t hw = (size_t)h * w;
@@ -156,8 +131,8 @@ __global__ __launch_bounds__(XD_THREADS) void render_xtrans_dir_kernel(XdirArgs 
         if (fy < Hm + XDIR_HALO && fx < Wm + XDIR_HALO) {
             const int Y = xdir_ext_row(fy, Hm), X = xdir_ext_col(fx, Wm);
             const int ph = 6 * (Y % 6) + X % 6;
-            const int col = XDIR.colour[ph];
-            v = gain_clamp(src[XDIR.plane[ph] * hw + (size_t)(Y / 3) * w + X / 3], col == 0 ? wr : col == 1 ? wg : wb);
+            const int col = XT.colour[ph];
+            v = gain_clamp(src[XT.plane[ph] * hw + (size_t)(Y / 3) * w + X / 3], col == 0 ? wr : col == 1 ? wg : wb);
         }
         sv[it] = v;
     }
@@ -194,8 +169,8 @@ __global__ __launch_bounds__(XD_THREADS) void render_xtrans_dir_kernel(XdirArgs 
     const int cy = XD_CH * blockIdx.y + cr, cx = XD_CW * blockIdx.x + cc;
     if (cy >= cells_y || cx >= cells_x) return;
     float m[9];
-    load_ccm(a.ccms, n, m);
-    const double ig = (double)a.inv_gamma;
+    load_ccm(a.t.ccms, n, m);
+    const double ig = (double)a.t.inv_gamma;
     const size_t plane = (size_t)9 * hw;
     const size_t e0 = (size_t)n * 3 * plane + (size_t)(6 * cy + wv) * Wm + 6 * cx;
     float cam[3][6];
@@ -207,24 +182,19 @@ __global__ __launch_bounds__(XD_THREADS) void render_xtrans_dir_kernel(XdirArgs 
 
 extern "C" int eld_render_xtrans_dir(const float* packed, const float* wbs, const float* ccms, void* out, int out_mode, int N, int h, int w,
                                      float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream) {
-    if (!packed || !wbs || !out) return ELD_EINVAL;
-    if (((uintptr_t)packed & 15) || ((uintptr_t)out & 15) || ((uintptr_t)wbs & 3)) return ELD_EINVAL;
-    if (N < 1 || N > 65535 || h < 2 || w < 2 || (h & 1) || (w & 1) || h > (1 << 28) || w > (1 << 28)) return ELD_EINVAL;      // 2 (3h - 1) is an int
-    if (tail_args_bad(ccms, out_mode, gamma, crf_E, crf_f, crf_n)) return ELD_EINVAL;
+    if (render_args_bad(packed, wbs, ccms, out, out_mode, N, gamma, crf_E, crf_f, crf_n) || h < 2 || w < 2 || (h & 1) || (w & 1)) return ELD_EINVAL;
+    if (h > (1 << 28) || w > (1 << 28)) return ELD_EINVAL;                 // xdir_ext_row's 2 (3h - 1) is an int
     const int cells_y = h / 2, cells_x = w / 2;
     const unsigned gy = (unsigned)((cells_y + XD_CH - 1) / XD_CH);
     if (gy > 65535u) return ELD_EINVAL;
-    XdirArgs a{};
-    a.packed = packed; a.wbs = wbs; a.ccms = ccms; a.out = out; a.h = h; a.w = w;
-    a.inv_gamma = (float)(1.0 / (double)gamma); a.crf_E = crf_E; a.crf_f = crf_f; a.crf_n = crf_n;
+    const RenderArgs a{packed, wbs, tail_args(ccms, gamma, crf_E, crf_f, crf_n), out, h, w};
     const dim3 grid((unsigned)((cells_x + XD_CW - 1) / XD_CW), gy, N), block(XD_THREADS);
     hipStream_t st = as_stream(stream);
-    const int tail = render_tail(out_mode, gamma, crf_n);
-    if (tail == TAIL_LINEAR) { ELD_LAUNCH(render_xtrans_dir_kernel<TAIL_LINEAR>, grid, block, 0, st, a, cells_y, cells_x); }
-    else if (tail == TAIL_TABLE) { ELD_LAUNCH(render_xtrans_dir_kernel<TAIL_TABLE>, grid, block, 0, st, a, cells_y, cells_x); }
-    else { ELD_LAUNCH(render_xtrans_dir_kernel<TAIL_GENERAL>, grid, block, 0, st, a, cells_y, cells_x); }
-    ELD_LAUNCH_CHECK();
-    return 0;
+    return with_tail(render_tail(out_mode, gamma, crf_n), [&](auto T) {
+        ELD_LAUNCH(render_xtrans_dir_kernel<decltype(T)::value>, grid, block, 0, st, a, cells_y, cells_x);
+        ELD_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // HOST, no device work: the tile of one workgroup in mosaic sites and the LDS it declares

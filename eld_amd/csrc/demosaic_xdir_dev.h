@@ -1,7 +1,7 @@
 // demosaic_xdir_dev.h -- the per-site arithmetic of the directional X-Trans demosaic (demosaic_xdir.hip eld_render_xtrans_dir):
-// the colour-preserving extension index, the per-phase tables of the 6 x 6 cell and the four stages, as functions a plain host compiler accepts
-// too: tools/demosaic_xdir_hostcheck.cpp runs them under AddressSanitizer over small frames, borders included.  Nothing here is HIP-only; under
-// hipcc the functions are __host__ __device__.
+// the colour-preserving extension index and the four stages over the per-phase tables of the 6 x 6 cell (xtrans.h), as functions a plain host
+// compiler accepts too: tools/demosaic_xdir_hostcheck.cpp runs them under AddressSanitizer over small frames, borders included.  Nothing here is
+// HIP-only; under hipcc the functions are __host__ __device__.
 //
 // Every stage function takes a pointer AT its site into a row-major image of float32 with the given pitch and reads a fixed neighbourhood of it
 // (stated per function); the caller owns that neighbourhood.  `ph` is the site's phase, 6 * (row % 6) + col % 6: where it is a compile-time
@@ -19,12 +19,8 @@
 #define XDIR_HD __host__ __device__ __forceinline__
 #else
 #define XDIR_HD inline
-#ifndef __host__
-#define __host__
-#define __device__
 #endif
-#endif
-#include "xtrans.h"
+#include "xtrans.h"                      // the per-phase tables XT, and the pattern facts stage C and the extension stand on (xdir_pattern_ok)
 
 constexpr int XDIR_HALO = 6;             // sites of the extension the four stages reach: A 1, B 2 + 1, C 2 (with B's sums), D 2 -- one cell
 
@@ -40,80 +36,6 @@ XDIR_HD int xdir_ext_col(int x, int W) {
     return x;
 }
 
-// Per-phase tables, derived from xtrans.h at compile time: the site's colour (R 0, G 1, B 2) and packed plane; the G taps of its 3x3 window and
-// the R / B taps of its 5x5 window (bit = raster index of the tap) with the sums of their weights ([1 2 1] x [1 2 1],
-// [1 2 3 2 1] x [1 2 3 2 1]); and, for a non-G site, its two axes: 0 = solitary (both neighbours and both second neighbours are G), -1 / +1 =
-// paired, the side a of the G neighbour (then 2a has the site's colour, -a the other colour, -2a is G).
-struct XdirTables {
-    unsigned char colour[36], plane[36];
-    unsigned gmask[36], gsum[36];
-    unsigned cmask[2][36], csum[2][36];          // [0] R, [1] B
-    signed char ah[36], av[36];
-};
-constexpr int XDIR_W3[3] = {1, 2, 1}, XDIR_W5[5] = {1, 2, 3, 2, 1};
-
-constexpr XdirTables make_xdir_tables() {
-    XdirTables t{};
-    for (int i = 0; i < 36; ++i) t.plane[i] = 255;
-    for (int k = 0; k < 5; ++k)
-        for (int pi = 0; pi < 2; ++pi)
-            for (int pj = 0; pj < 2; ++pj) t.plane[6 * XT_RC[k][pi][pj][0] + XT_RC[k][pi][pj][1]] = (unsigned char)k;
-    for (int k = 5; k < 9; ++k)
-        for (int bi = 0; bi < 2; ++bi)
-            for (int bj = 0; bj < 2; ++bj) t.plane[6 * (3 * bi + XT_RC3[k - 5][0]) + 3 * bj + XT_RC3[k - 5][1]] = (unsigned char)k;
-    for (int i = 0; i < 36; ++i) t.colour[i] = (unsigned char)((XT_COLOUR >> (2u * t.plane[i])) & 3u);
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) {
-            const int ph = 6 * r + c;
-            for (int dy = -2; dy <= 2; ++dy)
-                for (int dx = -2; dx <= 2; ++dx) {
-                    const int col = t.colour[6 * ((r + dy + 6) % 6) + (c + dx + 6) % 6];
-                    if (col == 1) {
-                        if (dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1) {
-                            t.gmask[ph] |= 1u << (3 * (dy + 1) + dx + 1);
-                            t.gsum[ph] += XDIR_W3[dy + 1] * XDIR_W3[dx + 1];
-                        }
-                    } else {
-                        t.cmask[col >> 1][ph] |= 1u << (5 * (dy + 2) + dx + 2);
-                        t.csum[col >> 1][ph] += XDIR_W5[dy + 2] * XDIR_W5[dx + 2];
-                    }
-                }
-            if (t.colour[ph] != 1) {
-                const bool gw = t.colour[6 * r + (c + 5) % 6] == 1, ge = t.colour[6 * r + (c + 1) % 6] == 1;
-                const bool gn = t.colour[6 * ((r + 5) % 6) + c] == 1, gs = t.colour[6 * ((r + 1) % 6) + c] == 1;
-                t.ah[ph] = (signed char)(gw && ge ? 0 : gw ? -1 : 1);
-                t.av[ph] = (signed char)(gn && gs ? 0 : gn ? -1 : 1);
-            }
-        }
-    return t;
-}
-constexpr XdirTables XDIR = make_xdir_tables();
-
-// the pattern facts stage C stands on, for every non-G phase, and the two mirrors of the extension
-constexpr bool xdir_pattern_ok() {
-    for (int r = 0; r < 6; ++r)
-        for (int c = 0; c < 6; ++c) {
-            const int ph = 6 * r + c, own = XDIR.colour[ph];
-            if (XDIR.plane[ph] > 8) return false;
-            // row y and row -y, column x and column 4 - x have one colour; with the period 6 so have the mirrors about row 3 and column 5
-            if (XDIR.colour[6 * ((6 - r) % 6) + c] != own || XDIR.colour[6 * r + (10 - c) % 6] != own) return false;
-            if (own == 1) continue;
-            if ((XDIR.ah[ph] == 0) == (XDIR.av[ph] == 0)) return false;          // exactly one solitary axis
-            for (int axis = 0; axis < 2; ++axis) {
-                const int a = axis ? XDIR.av[ph] : XDIR.ah[ph];
-                int col[5] = {};
-                for (int k = -2; k <= 2; ++k) col[k + 2] = axis ? XDIR.colour[6 * ((r + k + 6) % 6) + c] : XDIR.colour[6 * r + (c + k + 6) % 6];
-                if (a == 0) {
-                    if (col[0] != 1 || col[1] != 1 || col[3] != 1 || col[4] != 1) return false;
-                } else {
-                    if (col[2 + a] != 1 || col[2 + 2 * a] != own || col[2 - a] != 2 - own || col[2 - 2 * a] != 1) return false;
-                }
-            }
-        }
-    return true;
-}
-static_assert(xdir_pattern_ok(), "X-Trans pattern facts: one solitary and one paired axis at every R and B site; the cell's mirrors");
-
 // stage A at a non-G site: the provisional green.  s into v (pitch vp); reads the G sites of the 3x3 window
 XDIR_HD float xdir_green0(const float* s, int vp, int ph) {
     float acc = 0.f;
@@ -121,8 +43,8 @@ XDIR_HD float xdir_green0(const float* s, int vp, int ph) {
     for (int dy = -1; dy <= 1; ++dy)
 #pragma unroll
         for (int dx = -1; dx <= 1; ++dx)
-            if ((XDIR.gmask[ph] >> (3 * (dy + 1) + dx + 1)) & 1u) acc = acc + (float)(XDIR_W3[dy + 1] * XDIR_W3[dx + 1]) * s[dy * vp + dx];
-    return acc / (float)XDIR.gsum[ph];
+            if ((XT.gmask[ph] >> (3 * (dy + 1) + dx + 1)) & 1u) acc = acc + (float)(XT_W3[dy + 1] * XT_W3[dx + 1]) * s[dy * vp + dx];
+    return acc / (float)XT.gsum[ph];
 }
 
 // stage B at any site: d_h = |W - E| + |(2c - WW) - EE| on G0, d_v likewise.  g into G0 (pitch p); reads g[-2 .. 2] and g[-2p .. 2p]
@@ -155,7 +77,7 @@ XDIR_HD float xdir_axis(const float* c, int step, int a) {
 // stage C at an R or B site: G^.  c into v (pitch vp; reads c[-2 .. 2], c[-2vp .. 2vp]), d_h and d_v into the stage B images (pitch dp; 3x3)
 XDIR_HD float xdir_green(const float* c, int vp, const float* d_h, const float* d_v, int dp, int ph) {
     const float S_h = xdir_sum9(d_h, dp), S_v = xdir_sum9(d_v, dp);
-    const float g_h = xdir_axis(c, 1, XDIR.ah[ph]), g_v = xdir_axis(c, vp, XDIR.av[ph]);
+    const float g_h = xdir_axis(c, 1, XT.ah[ph]), g_v = xdir_axis(c, vp, XT.av[ph]);
     const float w_h = S_v * S_v + 1e-6f, w_v = S_h * S_h + 1e-6f;
     return g_h + (g_v - g_h) * (w_v / (w_h + w_v));
 }
@@ -168,7 +90,7 @@ XDIR_HD float xdir_chroma(const float* c, int vp, const float* g, int gp, int ph
     for (int dy = -2; dy <= 2; ++dy)
 #pragma unroll
         for (int dx = -2; dx <= 2; ++dx)
-            if ((XDIR.cmask[k][ph] >> (5 * (dy + 2) + dx + 2)) & 1u)
-                acc = acc + (float)(XDIR_W5[dy + 2] * XDIR_W5[dx + 2]) * (c[dy * vp + dx] - g[dy * gp + dx]);
-    return acc / (float)XDIR.csum[k][ph];
+            if ((XT.cmask[k][ph] >> (5 * (dy + 2) + dx + 2)) & 1u)
+                acc = acc + (float)(XT_W5[dy + 2] * XT_W5[dx + 2]) * (c[dy * vp + dx] - g[dy * gp + dx]);
+    return acc / (float)XT.csum[k][ph];
 }

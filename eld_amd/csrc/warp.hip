@@ -31,13 +31,9 @@ static_assert(WTX == ELD_WAVE, "a wave spans the tile's columns: a row of a wave
 struct WarpArgs {
     const float* rgb;
     void* out;
-    const float* ccms;
+    TailArgs t;
     int Hm, Wm;
     int lds_floats;                              // the staging budget in floats (0: the direct path everywhere)
-    float inv_gamma;
-    const float* crf_E;
-    const float* crf_f;
-    int crf_n;
     EldWarp w;
 };
 
@@ -50,7 +46,7 @@ __global__ __launch_bounds__(WT) void warp_kernel(WarpArgs a) {
     __shared__ int s_box[WWAVES][NSETS][4];          // per wave and set: min i0, max i0, min j0, max j0 of its pixels inside the image
     __shared__ unsigned s_t[256];
     const int tid = threadIdx.x, lane = tid & (ELD_WAVE - 1), wave = tid / ELD_WAVE;
-    if (TAIL == TAIL_TABLE && tid < 256) s_t[tid] = ELD_GAMMA22_T[tid];
+    stage_gamma_table<TAIL, WT>(s_t);
     const int n = blockIdx.z, Hm = a.Hm, Wm = a.Wm;
     const int x = blockIdx.x * WTX + lane, y0 = blockIdx.y * WTY + wave * WROWS;
     const bool x_in = x < Wm;
@@ -127,8 +123,8 @@ __global__ __launch_bounds__(WT) void warp_kernel(WarpArgs a) {
     if (STAGE) __syncthreads();
 
     float m[9];
-    load_ccm(a.ccms, n, m);
-    const double ig = (double)a.inv_gamma;
+    load_ccm(a.t.ccms, n, m);
+    const double ig = (double)a.t.inv_gamma;
     if (!x_in) return;
 #pragma unroll
     for (int r = 0; r < WROWS; ++r) {
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(WT) void warp_kernel(WarpArgs a) {
             val[c] = warp_sum16(p, wx[s], wy[s]);
         }
         float o[3];
-        site_out<TAIL>(val[0], val[1], val[2], m, a.ccms != nullptr, a, ig, s_t, o);
+        site_out<TAIL>(val[0], val[1], val[2], m, a.t, ig, s_t, o);
         const size_t e = (size_t)n * 3 * plane + (size_t)y * (size_t)Wm + (size_t)x;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -207,17 +203,15 @@ extern "C" int eld_warp_rgb_f32(const float* rgb, void* out, int out_mode, int N
     }
     if (N == 0) return 0;
     WarpArgs a = {};
-    a.rgb = rgb; a.out = out; a.ccms = ccms; a.Hm = Hm; a.Wm = Wm;
+    a.rgb = rgb; a.out = out; a.Hm = Hm; a.Wm = Wm;
     const size_t lds = (size_t)(lds_bytes < 0 ? WARP_DEFAULT_LDS : lds_bytes) & ~(size_t)3;
     a.lds_floats = (int)(lds / sizeof(float));
-    a.inv_gamma = (float)(1.0 / (double)gamma); a.crf_E = crf_E; a.crf_f = crf_f; a.crf_n = crf_n;
+    a.t = tail_args(ccms, gamma, crf_E, crf_f, crf_n);
     a.w = *warp;
     hipStream_t st = as_stream(stream);
-    const int tail = render_tail(out_mode, gamma, crf_n);
-#define WARP_CASE(T)                                                                                                          \
-    if (tail == T && lds > 0) return a.w.nsets == 1 ? warp_launch<T, 1, true>(a, grid, lds, st) : warp_launch<T, 3, true>(a, grid, lds, st); \
-    if (tail == T) return a.w.nsets == 1 ? warp_launch<T, 1, false>(a, grid, 0, st) : warp_launch<T, 3, false>(a, grid, 0, st);
-    WARP_CASE(TAIL_LINEAR) WARP_CASE(TAIL_TABLE) WARP_CASE(TAIL_GENERAL)
-#undef WARP_CASE
-    return ELD_EINVAL;
+    return with_tail(render_tail(out_mode, gamma, crf_n), [&](auto T) {
+        constexpr int TAIL = decltype(T)::value;
+        if (lds > 0) return a.w.nsets == 1 ? warp_launch<TAIL, 1, true>(a, grid, lds, st) : warp_launch<TAIL, 3, true>(a, grid, lds, st);
+        return a.w.nsets == 1 ? warp_launch<TAIL, 1, false>(a, grid, 0, st) : warp_launch<TAIL, 3, false>(a, grid, 0, st);
+    });
 }

@@ -1,6 +1,6 @@
 """GPU tests of the full-resolution renders (csrc/demosaic.hip eld_render_bayer / eld_render_xtrans, eld_amd.isp.render_*, denoise_raw's
-srgb_size='full'): the linear output bit for bit against the NumPy float32 restatement (tests/demosaic_ref.py), the 8-bit codes, agreement
-with the packed-resolution ISP kernels on frames of constant colour, denoise_raw end to end, and the argument refusals."""
+srgb_size='full'): the linear output bit for bit against the NumPy float32 restatement (tests/demosaic_ref.py), the 8-bit codes, guarded
+buffers, agreement with the packed-resolution ISP kernels on frames of constant colour, denoise_raw end to end, and the argument refusals."""
 import ctypes
 import os
 import subprocess
@@ -94,6 +94,43 @@ def test_xtrans_srgb8(lib, h, w):
     p, wbs, ccms = inputs(2, 9, h, w, 40, 3)
     x = dev(p)
     check_codes(lambda **kw: render_xtrans(x, wbs, ccms, **kw), D.linear_xtrans(p, wbs, ccms))
+
+
+# ---- 7b. guarded, poisoned buffers -----------------------------------------------------------------------------------------------------------
+# Packed shapes, the smallest at which each store path and its edge can go wrong.  Bayer: 2 x 2 (one run of two columns), 3 x 5 (the non-vector
+# path, the last run holds one column), 5 x 8 (the vector path, every lane at a border: the mirrored gather), 9 x 12 (the vector path with
+# interior lanes).  X-Trans: 2 x 2 (one cell), 6 x 10, 10 x 66 (5 x 33 cells: two tiles of 4 x 32 cells down and two across, ragged both ways).
+GUARDED = [('bayer', 2, 2), ('bayer', 3, 5), ('bayer', 5, 8), ('bayer', 9, 12), ('xtrans', 2, 2), ('xtrans', 6, 10), ('xtrans', 10, 66)]
+
+
+@pytest.mark.parametrize('cfa,h,w', GUARDED)
+def test_guarded_buffers(lib, cfa, h, w):
+    """every operand between guard bands of NaN, the outputs poisoned with 0xFF (NaN), two frames (the batch stride): nothing outside is written,
+    every element inside is, no NaN (a read outside an input) reaches the result, and the linear output has the restatement's bits"""
+    from eld_amd import _lib as L
+    from guarded import Guards
+    bayer = cfa == 'bayer'
+    pat = PATTERNS[(h + w) % 4]
+    p, wbs, ccms = inputs(2, 4 if bayer else 9, h, w, 90 + 3 * h + w, 4 if bayer else 3)
+    lin = D.linear_bayer(p, pat, wbs, ccms) if bayer else D.linear_xtrans(p, wbs, ccms)
+    s = 2 if bayer else 3
+    g = Guards()
+    x, wb, cm = g.ro(dev(p), 'packed'), g.ro(dev(wbs), 'wbs'), g.ro(dev(ccms.reshape(2, 9)), 'ccms')
+    o32 = g.new((2, 3, s * h, s * w), torch.float32, 'linear out')
+    o8 = g.new((2, 3, s * h, s * w), torch.uint8, 'srgb out')
+    cpat = (ctypes.c_int * 4)(*np.asarray(pat).reshape(-1).tolist())
+    for out, mode in ((o32, L.RENDER_LINEAR_F32), (o8, L.RENDER_SRGB8)):
+        tail = (L.dptr(wb), L.dptr(cm), L.dptr(out), mode, 2, h, w, 2.2, None, None, 0, L.cur_stream())
+        if bayer:
+            L.check(lib.eld_render_bayer(L.dptr(x), cpat, *tail), 'eld_render_bayer')
+        else:
+            L.check(lib.eld_render_xtrans(L.dptr(x), *tail), 'eld_render_xtrans')
+    torch.cuda.synchronize()
+    g.check()
+    got = o32.cpu().numpy()
+    assert not np.isnan(got).any()
+    assert got.shape == lin.shape and got.dtype == lin.dtype == np.float32 and np.array_equal(got.view(np.uint32), lin.view(np.uint32))
+    assert np.array_equal(o8.cpu().numpy(), D.srgb8(lin))
 
 
 # ---- 8. consistency with the packed-resolution render ----------------------------------------------------------------------------------------

@@ -59,14 +59,14 @@ void demosaic(const Case& c, std::vector<float>& out) {
         for (int x = -5; x < W + 5; ++x) {
             const float* s = V + (y + 6) * vp + x + 6;
             const int ph = phase(y, x);
-            G[(y + 5) * gp + x + 5] = XDIR.colour[ph] == 1 ? s[0] : xdir_green0(s, vp, ph);
+            G[(y + 5) * gp + x + 5] = XT.colour[ph] == 1 ? s[0] : xdir_green0(s, vp, ph);
         }
     for (int y = -3; y < H + 3; ++y)
         for (int x = -3; x < W + 3; ++x) xdir_grad(G + (y + 5) * gp + x + 5, gp, DH[(y + 3) * dp + x + 3], DV[(y + 3) * dp + x + 3]);
     for (int y = -2; y < H + 2; ++y)
         for (int x = -2; x < W + 2; ++x) {
             const int ph = phase(y, x);
-            if (XDIR.colour[ph] != 1)
+            if (XT.colour[ph] != 1)
                 G[(y + 5) * gp + x + 5] = xdir_green(V + (y + 6) * vp + x + 6, vp, DH + (y + 3) * dp + x + 3, DV + (y + 3) * dp + x + 3, dp, ph);
         }
     out.assign((size_t)3 * H * W, nan);
@@ -75,7 +75,7 @@ void demosaic(const Case& c, std::vector<float>& out) {
         for (int x = 0; x < W; ++x) {
             const float* s = V + (y + 6) * vp + x + 6;
             const float* g = G + (y + 5) * gp + x + 5;
-            const int ph = phase(y, x), col = XDIR.colour[ph];
+            const int ph = phase(y, x), col = XT.colour[ph];
             const float gg = col == 1 ? s[0] : g[0];
             out[(size_t)y * W + x] = col == 0 ? s[0] : gg + xdir_chroma(s, vp, g, gp, ph, 0);
             out[hw + (size_t)y * W + x] = gg;
@@ -118,7 +118,7 @@ int main(int argc, char** argv) {
                 return 1;
             }
             for (int k = 0; k < 6; ++k)
-                if (XDIR.colour[phase(y, k)] != XDIR.colour[phase(i, k)] || XDIR.colour[phase(k, x)] != XDIR.colour[phase(k, i)]) {
+                if (XT.colour[phase(y, k)] != XT.colour[phase(i, k)] || XT.colour[phase(k, x)] != XT.colour[phase(k, i)]) {
                     printf("extension of index %d of %d sites changes the colour: row %d, column %d\n", i, L, y, x);
                     return 1;
                 }
