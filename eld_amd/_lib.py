@@ -207,6 +207,9 @@ SIGNATURES = {
     'eld_render_bayer_edge_tile': (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'eld_render_xtrans_dir': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp]),
     'eld_render_xtrans_dir_tile': (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    'eld_frame_rgb_f32': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _f, _vp, _vp, _i,
+                               _vp]),
+    'eld_frame_rgb_tile': (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
 }
 
 

@@ -38,7 +38,7 @@ import numpy as np
 from . import _lib as L
 from .defects import as_defect_map, repair_device
 from .flatfield import LENS_MODES, as_flat_field
-from .isp import DEMOSAICS, check_demosaic, process, process_xtrans, render_bayer, render_xtrans, warp_rgb
+from .isp import DEMOSAICS, FRAME_FILTERS, Frame, check_demosaic, frame_rgb, process, process_xtrans, render_bayer, render_xtrans, warp_rgb
 from .mosaic import (DEFAULT_BLACK, DEFAULT_PATTERN, PLANES, as_u16 as _as_u16, check_cfa as _check_cfa,  # noqa: F401 (the names this module always had)
                      check_sides as _check_sides, levels as _levels)
 from .shading import as_dark_shading
@@ -198,7 +198,7 @@ def run_network(denoiser, x, chop=None):
 
 def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, white_point=16383, ratio=1.0, wb=None, ccm=None, CRF=None,
                 chop=None, rounding='nearest', srgb_size='packed', linear=False, defects=None, shading=None, iso=None, flatfield=None,
-                lens='srgb', warp=None, jpeg=None, demosaic='mhc'):
+                lens='srgb', warp=None, jpeg=None, demosaic='mhc', frame=None, preview_frame=None):
     """Denoise uint16 sensor mosaics with a trained U-Net -- or, given an eld_amd.classical.ClassicalDenoiser in place of a Denoiser, with the
     classical baseline (Anscombe transform, non-local means, unbiased inverse on the sensor's codes instead of the input stage and the
     network; `chop` is then ignored, and 'packed' is the baseline's output in the network's convention).
@@ -243,6 +243,14 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
                 (eld_amd.isp.render_xtrans(..., demosaic='directional'); DESIGN.md sec. 33) in place of the isotropic normalised convolution;
                 X-Trans and srgb_size='full' only.  warp, linear and jpeg take either's output as they take the default's.
 
+    frame       an eld_amd.isp.Frame (crop, upright size, TIFF orientation, resampling filter), with srgb_size='full' only: the demosaiced
+                camera RGB (after the warp, when there is one) is cropped, resampled in linear light and turned by it before the colour
+                matrix and the tone curve (eld_amd.isp.frame_rgb).  It applies to 'srgb', to 'linear' and to what jpeg
+                encodes, which then have the frame's upright shape.  The mosaic written back and 'packed' are untouched.
+    preview_frame  a second Frame, with jpeg only: the result gains 'preview', a list of JPEG files of the sRGB rendering framed by it
+                instead (a small preview beside the full picture, or an unturned one for a DNG whose Orientation tag does the turning),
+                encoded with jpeg's quality and subsampling.
+
     Returns {'packed': (N,C,h,w) float32 network output, 'mosaic': codes of the input's shape, type and device, 'srgb': (N,3,h,w)
     uint8 or None}; NumPy in -> NumPy out, CUDA tensor in -> CUDA tensors out.  Bad arguments raise ValueError before any device work."""
     _check_cfa(cfa)
@@ -274,6 +282,15 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
             raise ValueError('jpeg encodes the sRGB rendering: it needs both wb and ccm')
         if linear:
             raise ValueError('jpeg encodes the uint8 sRGB rendering: it does not go with linear=True')
+    for name, f in (('frame', frame), ('preview_frame', preview_frame)):
+        if f is None:
+            continue
+        if not isinstance(f, Frame):
+            raise ValueError('%s must be an eld_amd.isp.Frame, got %r' % (name, type(f).__name__))
+        if srgb_size != 'full':
+            raise ValueError("%s frames the full-resolution render: it needs srgb_size='full'" % name)
+    if preview_frame is not None and jpeg is None:
+        raise ValueError('preview_frame makes a second JPEG: it needs jpeg (a dict, possibly empty)')
     kind, batched = _as_u16(mosaic_u16)
     shape = tuple(mosaic_u16.shape)
     N = shape[0] if batched else 1
@@ -281,6 +298,9 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
     if N < 1:
         raise ValueError('empty batch')
     _check_sides(Hm, Wm, cfa)
+    for f in (frame, preview_frame):                                  # the render's rectangle: X-Trans renders whole 6 x 6 cells
+        if f is not None:
+            f.taps(*((Hm // 6 * 6, Wm // 6 * 6) if cfa == 'xtrans' else (Hm, Wm)))
     pat, blk, white = _levels(cfa, raw_pattern, black_level, white_point)
     ratios = _ratios(ratio, N)
     if denoiser.in_channels != PLANES[cfa]:
@@ -342,29 +362,41 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
         write_back(out if lens == 'all' else net_out, mosaic, cfa, pat, blk, white, rounding)
     else:
         write_back(out, mosaic, cfa, pat, blk, white, rounding)
-    srgb = lin = None
+    srgb = lin = preview = None
     if wbs is not None and srgb_size == 'full':
         wt, ct = torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev)
         if cfa == 'bayer':
             render = lambda c, **kw: render_bayer(out, pat, wt, c, demosaic=demosaic, **kw)
         else:
             render = lambda c, **kw: render_xtrans(out, wt, c, demosaic=demosaic, **kw)
-        if warp is None:
+        if warp is None and frame is None and preview_frame is None:
             srgb = render(ct, CRF=CRF)
             lin = render(ct, linear=True) if linear else None
         else:                                                     # one demosaic to camera RGB, resampled once per output
             cam = render(None, linear=True)
-            srgb = warp_rgb(cam, warp, ct, CRF=CRF)
-            lin = warp_rgb(cam, warp, ct, linear=True) if linear else None
+            if frame is not None or preview_frame is not None:    # the frames take the warped camera RGB
+                warped = cam if warp is None else warp_rgb(cam, warp, None, linear=True)
+            if frame is not None:
+                srgb = frame_rgb(warped, frame, ct, CRF=CRF)
+                lin = frame_rgb(warped, frame, ct, linear=True) if linear else None
+            elif warp is not None:
+                srgb = warp_rgb(cam, warp, ct, CRF=CRF)
+                lin = warp_rgb(cam, warp, ct, linear=True) if linear else None
+            else:                                                 # only the preview is framed
+                srgb = render(ct, CRF=CRF)
+                lin = render(ct, linear=True) if linear else None
+            if preview_frame is not None:
+                preview = frame_rgb(warped, preview_frame, ct, CRF=CRF)
     elif wbs is not None:
         fn = process if cfa == 'bayer' else process_xtrans
         rgb = fn(out, torch.from_numpy(wbs).to(dev), torch.from_numpy(ccms).to(dev), CRF=CRF)
         srgb = torch.round(rgb * 255.0).to(torch.uint8)          # k/255 -> k exactly
-    files = None
+    files = previews = None
     if jpeg is not None:                                          # on the device, before the rendering's copy to the host
         from .jpeg import encode_jpeg
         with torch.cuda.device(dev):
             files = encode_jpeg(srgb, **jpeg)
+            previews = None if preview is None else encode_jpeg(preview, **jpeg)
     if not batched:
         mosaic = mosaic[0]
     if kind == 'numpy':
@@ -378,6 +410,8 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
             res['linear'] = lin
     if files is not None:
         res['jpeg'] = files
+        if previews is not None:
+            res['preview'] = previews
     return res
 
 
@@ -385,7 +419,7 @@ def denoise_raw(denoiser, mosaic_u16, cfa, raw_pattern=None, black_level=None, w
 SIDECAR_ALIASES = {'black_level_per_channel': 'black_level', 'white_level': 'white_point', 'camera_whitebalance': 'wb',
                    'rgb_camera_matrix': 'ccm', 'black': 'black_level', 'white': 'white_point'}
 SIDECAR_KEYS = ('cfa', 'raw_pattern', 'black_level', 'white_point', 'ratio', 'wb', 'ccm', 'precision', 'rounding', 'chop', 'srgb_size', 'defects',
-                'shading', 'iso', 'flatfield', 'lens', 'warp', 'demosaic')
+                'shading', 'iso', 'flatfield', 'lens', 'warp', 'demosaic', 'crop', 'orient', 'size', 'resample', 'dng_preview_size')
 
 
 def read_sidecar(path):
@@ -444,6 +478,14 @@ def build_parser():
                    help="with --srgb-size full: resample the demosaiced picture by a DNG WarpRectilinear (lens distortion, lateral CA) before the colour "
                         "matrix: 'opcodes' takes the one in OpcodeList3 of each .dng input, FILE.json holds {\"sets\": [[kr0, kr1, kr2, kr3, kt0, kt1], ...], "
                         '"cx": ..., "cy": ...} with one set or three (R, G, B).  The written-back mosaic and --dng stay unwarped raw frames')
+    p.add_argument('--crop', metavar='default|Y0,X0,H,W',
+                   help="with --srgb-size full: render this rectangle of the demosaiced picture only (pixel-edge coordinates, fractions allowed); "
+                        "'default' takes DefaultCropOrigin / DefaultCropSize of each .dng input.  The written-back mosaic and --dng keep the whole frame")
+    p.add_argument('--orient', metavar='auto|1..8',
+                   help="with --srgb-size full: turn the rendered picture upright by this TIFF Orientation; 'auto' takes the Orientation tag of each .dng input")
+    p.add_argument('--size', metavar='N|HxW', help='with --srgb-size full: resample the rendered picture to a long edge of N pixels (aspect kept) or to H x W, in linear light')
+    p.add_argument('--resample', choices=FRAME_FILTERS, help="the filter of --size and of a fractional --crop: 'area' (default) or 'lanczos'")
+    p.add_argument('--dng-preview-size', type=int, metavar='N', help='of --dng-preview: the long edge of the preview (default: the size of the cropped picture)')
     p.add_argument('--dng', action='store_true', help='also write <name>_denoised.dng (uncompressed 16-bit unless --dng-compression says otherwise; the tags of a .dng input are copied)')
     p.add_argument('--dng-compression', choices=('none', 'ljpeg'), default='none', help="of --dng: 'none' (uncompressed strips, the default) or 'ljpeg' (lossless-JPEG tiles, encoded on the device)")
     p.add_argument('--dng-preview', action='store_true', help='of --dng: the sRGB rendering, encoded as JPEG on the device (the settings of --jpeg, or its defaults), becomes the preview in IFD0 and the mosaic moves to a SubIFD')
@@ -463,7 +505,7 @@ def options_from(a):
     """parse_args on a namespace already parsed by build_parser() or a parser that extends it (eld_amd.classical)."""
     o = read_sidecar(a.meta) if a.meta else {}
     cli = {'cfa': a.cfa, 'raw_pattern': a.raw_pattern, 'black_level': a.black, 'white_point': a.white, 'ratio': a.ratio, 'wb': a.wb,
-           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'warp': getattr(a, 'warp', None), 'demosaic': getattr(a, 'demosaic', None), 'precision': 'bf16' if a.bf16 else None,
+           'ccm': a.ccm, 'rounding': a.rounding, 'srgb_size': a.srgb_size, 'defects': a.defects, 'shading': a.shading, 'iso': a.iso, 'flatfield': a.flatfield, 'lens': a.lens, 'warp': getattr(a, 'warp', None), 'demosaic': getattr(a, 'demosaic', None), 'crop': getattr(a, 'crop', None), 'orient': getattr(a, 'orient', None), 'size': getattr(a, 'size', None), 'resample': getattr(a, 'resample', None), 'dng_preview_size': getattr(a, 'dng_preview_size', None), 'precision': 'bf16' if a.bf16 else None,
            'chop': None if a.chop is None else {'auto': 'auto', 'on': True, 'off': False}[a.chop]}
     o.update({k: v for k, v in cli.items() if v is not None})
     # below the command line and the sidecar, above the defaults: the tags of the first .dng input (all .dng inputs must agree on the sensor keys)
@@ -538,7 +580,96 @@ def options_from(a):
                     raise ValueError("%s: --warp opcodes reads OpcodeList3 of .dng inputs (a .json file gives a warp to any input)" % path)
         elif not isinstance(o['warp'], str):
             raise ValueError("warp must be 'opcodes' or the path of a .json file, got %r" % (o['warp'],))
+    check_frame_options(o, getattr(a, 'inputs', None) or [])
     return a.inputs, a.out, a.ckpt, o
+
+
+FRAME_OPTIONS = (('crop', '--crop'), ('orient', '--orient'), ('size', '--size'), ('resample', '--resample'), ('dng_preview_size', '--dng-preview-size'))
+
+
+def check_frame_options(o, inputs):
+    """The frame's options (command line or sidecar) parsed in place: crop -> 'default' or (y0, x0, h, w) floats; orient -> 'auto' or 1 .. 8; size ->
+    an int or (H, W); every ValueError they can raise without reading a pixel."""
+    from .dng import is_dng
+    for key, flag in FRAME_OPTIONS:
+        if o.get(key) is not None and o['srgb_size'] != 'full':
+            raise ValueError('%s frames the full-resolution render: it needs --srgb-size full' % flag)
+    v = o.get('crop')
+    if v is not None and v != 'default':
+        try:
+            v = tuple(float(x) for x in (v.split(',') if isinstance(v, str) else v))
+            Frame(crop=v)
+        except (TypeError, ValueError):
+            raise ValueError("--crop takes 'default' or Y0,X0,H,W with Y0, X0 >= 0 and H, W > 0, got %r" % (o['crop'],))
+        o['crop'] = v
+    v = o.get('orient')
+    if v is not None and v != 'auto':
+        try:
+            v = int(v)
+            Frame(orientation=v)
+        except (TypeError, ValueError):
+            raise ValueError("--orient takes 'auto' or a TIFF Orientation 1 .. 8, got %r" % (o['orient'],))
+        o['orient'] = v
+    v = o.get('size')
+    if v is not None:
+        try:
+            if isinstance(v, str):
+                v = tuple(int(x) for x in v.lower().split('x')) if 'x' in v.lower() else int(v)
+            elif not isinstance(v, int):
+                v = tuple(int(x) for x in v)
+            Frame(size=v)
+        except (TypeError, ValueError):
+            raise ValueError('--size takes a long edge N >= 1 or HxW, got %r' % (o['size'],))
+        o['size'] = v
+    if o.get('resample') is not None and o['resample'] not in FRAME_FILTERS:
+        raise ValueError('resample must be one of %r, got %r' % (FRAME_FILTERS, o['resample']))
+    v = o.get('dng_preview_size')
+    if v is not None:
+        if not o.get('dng_preview'):
+            raise ValueError('--dng-preview-size goes with --dng-preview')
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError('--dng-preview-size takes a long edge N >= 1, got %r' % (v,))
+    for key, word, flag in (('crop', 'default', '--crop default reads DefaultCropOrigin / DefaultCropSize'), ('orient', 'auto', '--orient auto reads the Orientation tag')):
+        if o.get(key) == word:
+            for path in inputs:
+                if not is_dng(path):
+                    raise ValueError('%s: %s of .dng inputs' % (path, flag))
+
+
+def frame_option(path, raw, o):
+    """The frame's options for one input -> (Frame or None for the sRGB outputs, Frame or None for the DNG preview).  The render's rectangle is the
+    visible mosaic (X-Trans: its whole 6 x 6 cells); a crop is intersected with it, with a line when that clips it, and an empty
+    intersection is a ValueError.  The DNG preview takes the same crop, --dng-preview-size and orientation 1: the DNG's Orientation tag turns
+    the preview as it turns the raw image."""
+    if all(o.get(k) is None for k, _ in FRAME_OPTIONS):
+        return None, None
+    Hm, Wm = (int(v) for v in raw.shape[-2:])
+    if o['cfa'] == 'xtrans':
+        Hm, Wm = Hm // 6 * 6, Wm // 6 * 6
+    crop, orient = o.get('crop'), o.get('orient') or 1
+    if crop == 'default' or orient == 'auto':
+        from .dng import dng_meta
+        meta = dng_meta(path)
+        if crop == 'default':
+            crop = meta.get('default_crop')
+            if crop is None:
+                print('%s: no DefaultCropSize: --crop default changes nothing for this file' % path)
+        if orient == 'auto':
+            orient = meta.get('orientation', 1)
+    if crop is not None:
+        y0, x0, ch, cw = (float(v) for v in crop)
+        y1, x1 = min(y0 + ch, float(Hm)), min(x0 + cw, float(Wm))
+        if y1 <= y0 or x1 <= x0:
+            raise ValueError('%s: the crop (y0, x0, h, w) = %r lies outside the %d x %d picture' % (path, tuple(crop), Hm, Wm))
+        if (y1 - y0, x1 - x0) != (ch, cw):
+            print('%s: the crop %r is clipped to the %d x %d picture: (%g, %g, %g, %g)' % (path, tuple(crop), Hm, Wm, y0, x0, y1 - y0, x1 - x0))
+        crop = (y0, x0, y1 - y0, x1 - x0)
+    flt = o.get('resample') or 'area'
+    frame = Frame(crop, orient, o.get('size'), flt)
+    preview = None
+    if o.get('dng_preview') and (orient != 1 or o.get('size') is not None or o.get('dng_preview_size') is not None):
+        preview = Frame(crop, 1, o.get('dng_preview_size'), flt)
+    return (None if frame.identity else frame), preview
 
 
 def save_png(path, hwc):
@@ -652,6 +783,9 @@ def run_frames(den, inputs, outdir, o):
         if o.get('warp') is not None:
             warp, carried = warp_option(path, raw, o, carried)
             fkw = dict(fkw, warp=warp)
+        frame, preview_frame = frame_option(path, raw, o)
+        if frame is not None or preview_frame is not None:
+            fkw = dict(fkw, frame=frame, preview_frame=preview_frame)
         res = denoise_raw(den, raw, o['cfa'], **fkw)
         name = os.path.splitext(os.path.basename(path))[0]
         np.save(os.path.join(outdir, name + '_denoised.npy'), res['mosaic'])
@@ -660,7 +794,7 @@ def run_frames(den, inputs, outdir, o):
             if raw.ndim != 2:
                 raise ValueError('%s: --dng writes one frame per file, the input holds a stack of %d' % (path, raw.shape[0]))
             if o.get('dng_preview'):
-                dng_kw = dict(dng_kw, preview=res['jpeg'][0])
+                dng_kw = dict(dng_kw, preview=(res['preview'] if preview_frame is not None else res['jpeg'])[0])
             if is_dng(path):
                 write_dng(os.path.join(outdir, name + '_denoised.dng'), res['mosaic'], like=path, opcodes=carried, **dng_kw)
             else:

@@ -24,7 +24,9 @@ Metadata mapping (tag -> key):
                           ((0, 1), (3, 2)), the project's default); X-Trans: every green is 1.  The pattern is relative to the top-left
                           corner of ActiveArea.
     ActiveArea            (top, left, bottom, right): the mosaic is full[top:bottom, left:right].  DefaultCropOrigin / DefaultCropSize and
-                          Orientation are ignored (rawpy's raw_image_visible ignores them too).
+                          Orientation do not change the mosaic (rawpy's raw_image_visible ignores them too); dng_meta reports them as
+                          default_crop (y0, x0, h, w) and orientation when the file carries them, write_dng(like=) copies them, and
+                          eld_amd.denoise --crop default / --orient auto frame the rendered picture by them.
     BlackLevelRepeatDim,  black_level: four values indexed by rawpy code (Bayer), one value (X-Trans; unequal values are an error).  A
     BlackLevel            non-zero BlackLevelDeltaH / BlackLevelDeltaV is an error.
     WhiteLevel            white_point
@@ -66,6 +68,7 @@ T_DNGVERSION, T_DNGBACKWARD, T_UNIQUEMODEL, T_CFAPLANECOLOR, T_CFALAYOUT, T_LINT
 T_BLACKDIM, T_BLACK, T_BLACKDH, T_BLACKDV, T_WHITE = 50713, 50714, 50715, 50716, 50717
 T_COLORMATRIX1, T_COLORMATRIX2, T_ANALOGBALANCE, T_ASSHOTNEUTRAL, T_ILLUMINANT1, T_ILLUMINANT2 = 50721, 50722, 50727, 50728, 50778, 50779
 T_ACTIVEAREA, T_OPCODE1, T_OPCODE2, T_OPCODE3 = 50829, 51008, 51009, 51022
+T_DEFAULTCROPORIGIN, T_DEFAULTCROPSIZE = 50719, 50720
 OPCODE_TAGS = ((T_OPCODE1, 'OpcodeList1'), (T_OPCODE2, 'OpcodeList2'), (T_OPCODE3, 'OpcodeList3'))
 CFA_PHOTOMETRIC, LINEARRAW_PHOTOMETRIC = 32803, 34892
 COMPRESSION_NAMES = {6: 'old-style JPEG', 8: 'deflate', 32946: 'deflate', 34892: 'lossy JPEG', 52546: 'JPEG XL'}
@@ -356,6 +359,20 @@ def _meta(t, ifd):
     m['bits'] = bits
     m['compression'] = int(_get1(ifd, T_COMPRESSION, 1))
     m['opcodes'] = [name for tag, name in OPCODE_TAGS if tag in ifd or tag in t.ifd0]
+    # the frame of the picture, only where the file carries it: Orientation (IFD0) and the default crop (raw IFD; SHORT, LONG or RATIONAL,
+    # origin as (x, y) and size as (width, height), relative to the visible mosaic) as (y0, x0, h, w).  This is also read_dng's path, which
+    # uses neither: a tag with values nobody can use (some writers store Orientation 0) gives no key and never an error, so such a file
+    # reads as it always did, and --orient auto / --crop default treat it as a file without the tag.
+    if T_ORIENTATION in t.ifd0 and t.ifd0[T_ORIENTATION].type in (SHORT, LONG) and 1 <= int(_get1(t.ifd0, T_ORIENTATION)) <= 8:
+        m['orientation'] = int(_get1(t.ifd0, T_ORIENTATION))
+    if T_DEFAULTCROPSIZE in ifd:
+        try:
+            size = _numbers(ifd[T_DEFAULTCROPSIZE], 'DefaultCropSize', p)
+            origin = _numbers(ifd[T_DEFAULTCROPORIGIN], 'DefaultCropOrigin', p) if T_DEFAULTCROPORIGIN in ifd else [Fraction(0), Fraction(0)]
+        except (ValueError, TypeError):                             # a rational with denominator 0, a type that holds no numbers
+            size = origin = []
+        if len(size) == 2 and len(origin) == 2 and min(size) > 0 and min(origin) >= 0:
+            m['default_crop'] = [num(origin[1]), num(origin[0]), num(size[1]), num(size[0])]
     return m
 
 
@@ -630,9 +647,9 @@ def color_matrix_from_ccm(ccm):
     return [(int(round(v * 10000)), 10000) for v in cm.reshape(-1)]
 
 
-COPIED_RAW = (T_CFADIM, T_CFAPATTERN, T_CFAPLANECOLOR, T_BLACKDIM, T_BLACK, T_WHITE)
+COPIED_RAW = (T_CFADIM, T_CFAPATTERN, T_CFAPLANECOLOR, T_BLACKDIM, T_BLACK, T_WHITE, T_DEFAULTCROPORIGIN, T_DEFAULTCROPSIZE)
 COPIED_IFD0 = (T_MAKE, T_MODEL, T_UNIQUEMODEL, T_COLORMATRIX1, T_COLORMATRIX2, T_ILLUMINANT1, T_ILLUMINANT2, T_ANALOGBALANCE, T_ASSHOTNEUTRAL,
-               T_ISO, T_EXPOSURETIME)
+               T_ISO, T_EXPOSURETIME, T_ORIENTATION)
 COPIED_EXIF = (T_ISO, T_EXPOSURETIME)
 
 
@@ -914,7 +931,7 @@ def _serialise_ifd(tags, ifd_off):
 
 # with a preview these stay in IFD0; every other tag of the mosaic moves to the raw SubIFD
 IFD0_LEVEL = (T_MAKE, T_MODEL, T_UNIQUEMODEL, T_COLORMATRIX1, T_COLORMATRIX2, T_ILLUMINANT1, T_ILLUMINANT2, T_ANALOGBALANCE, T_ASSHOTNEUTRAL,
-              T_ISO, T_EXPOSURETIME, T_DNGVERSION, T_DNGBACKWARD)
+              T_ISO, T_EXPOSURETIME, T_DNGVERSION, T_DNGBACKWARD, T_ORIENTATION)
 
 
 def write_dng(path, mosaic, meta=None, like=None, rows_per_strip=None, compression=1, tile=None, bits=None, opcodes=None, preview=None):

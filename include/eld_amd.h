@@ -69,7 +69,9 @@ extern "C" {
  * Still 8: eld_jpeg_coef_u8, eld_jpeg_hist_i16 and eld_jpeg_pack_i16 were added the same way (baseline JPEG of the uint8 sRGB render, encoded
  * on the device): three new symbols, no existing call changed.
  * Still 8: eld_render_bayer_edge and eld_render_bayer_edge_tile were added the same way (the full-resolution Bayer render behind an
- * edge-directed demosaic): two new symbols, no existing call changed. */
+ * edge-directed demosaic): two new symbols, no existing call changed.
+ * Still 8: eld_frame_rgb_f32 and eld_frame_rgb_tile were added the same way (crop, antialiased resize and orientation of the full-resolution
+ * render, followed by the renders' tail): two new symbols, no existing call changed. */
 #define ELD_ABI_VERSION 8
 
 /* negative = argument errors (hipError_t values are >= 0) */
@@ -1242,6 +1244,43 @@ int eld_render_bayer_edge_tile(int* tile_h, int* tile_w, int* lds_bytes);
 int eld_render_xtrans_dir(const float* packed, const float* wbs, const float* ccms, void* out, int out_mode, int N, int h, int w, float gamma,
                           const float* crf_E, const float* crf_f, int crf_n, void* stream);
 int eld_render_xtrans_dir_tile(int* tile_h, int* tile_w, int* lds_bytes);
+
+/* ---- The frame of the full-resolution render: crop, antialiased resize, orientation (csrc/frame.hip, csrc/frame_dev.h) ----
+ * Appended without a change of ELD_ABI_VERSION: two new symbols, no existing call changed.
+ *   rgb   (N,3,Hs,Ws) float32 camera RGB in DEVICE memory, as eld_render_* write it with ELD_RENDER_LINEAR_F32 and ccms NULL, or
+ *         eld_warp_rgb_f32 with the same; 4-byte aligned.
+ *   out   (N,3,Ho,Wo) uint8 (ELD_RENDER_SRGB8) or float32 (ELD_RENDER_LINEAR_F32): the UPRIGHT picture.  orientation (TIFF / Exif, 1 .. 8)
+ *         says how it is turned: the unoriented grid is Hc x Wc = Ho x Wo for orientation <= 4 and Wo x Ho for orientation >= 5, and upright
+ *         pixel (Y, X) is unoriented pixel (i, j) =
+ *           1 (Y, X)             2 (Y, Wc-1-X)        3 (Hc-1-Y, Wc-1-X)   4 (Hc-1-Y, X)
+ *           5 (X, Y)             6 (Hc-1-X, Y)        7 (Hc-1-X, Wc-1-Y)   8 (X, Wc-1-Y)
+ *   ystart, ycount (Hc int32), yw (Hc x Ty float32), xstart, xcount (Wc int32), xw (Tx x Wc float32): the tap tables, in DEVICE memory,
+ *         4-byte aligned.  Unoriented row i is the weighted sum of the source rows ystart[i] .. ystart[i] + ycount[i] - 1 with the weights
+ *         yw[i * Ty + 0 ..]; unoriented column j likewise from xstart[j], xcount[j] and the weights xw[0 * Wc + j], xw[1 * Wc + j], ...
+ *         (tap-major: the row pass reads one tap of 64 neighbouring columns at a time).  The crop and the filter are in the tables alone (eld_amd.isp.Frame.taps builds them: 'area'
+ *         and 'lanczos').  Every count is clamped to [1, T] and every tap index to the plane before an address is formed from it, so no
+ *         table content reads or writes outside the buffers; padding behind a row's count is never read.
+ *   row0, rows: the source rows the vertical tables use, row0 .. row0 + rows - 1 (the caller takes min(ystart) and max(ystart + ycount));
+ *         a vertical tap outside them is clamped into them.
+ *   workspace: float32 (N,3,rows,Wc) in DEVICE memory, workspace_bytes of it; it holds the horizontal sums between the two kernels and
+ *         overlaps neither rgb nor out.
+ *   ccms, gamma, crf_E, crf_f, crf_n: the tail of eld_render_*, unchanged, applied to the three resampled values of a pixel.
+ * The sums, float32, strictly ascending tap order, every product and sum rounded on its own (no FMA), no initial zero:
+ *   h[r][j] = ((xw0*p[r][s] + xw1*p[r][s+1]) + xw2*p[r][s+2]) + ...      s = xstart[j]
+ *   v[i][j] = ((yw0*h[t][j] + yw1*h[t+1][j]) + yw2*h[t+2][j]) + ...      t = ystart[i]
+ * A single tap of weight 1.0 on both axes hands the source value to the tail unchanged (-0.0 and NaN included): with the full rectangle at
+ * its own size and orientation 1 the output is the render's own.  tests/frame_ref.py restates all of it bit for bit.
+ * ELD_EINVAL before any device work: a NULL or misaligned pointer; N < 0 or > 21845; Hs, Ws, Ho, Wo < 1; Hs * Ws, Ho * Wo or rows * Wc
+ * >= 2^31; orientation outside 1 .. 8; Ty or Tx outside 1 .. 4096; row0 < 0, rows < 1 or row0 + rows > Hs; rows > 262140; an unknown
+ * out_mode; the tail's rules; rgb, out and workspace overlapping.  ELD_EWS: workspace_bytes < N * 3 * rows * Wc * 4.  N == 0 is a
+ * successful no-op.
+ * eld_frame_rgb_tile (HOST, no device work): the tile of unoriented outputs one workgroup of the column pass owns and, when lds_bytes is not
+ * NULL, the most LDS an instantiation declares; ELD_EINVAL for a null tile_h or tile_w. */
+int eld_frame_rgb_f32(const float* rgb, void* out, int out_mode, int N, int Hs, int Ws, int Ho, int Wo, int orientation,
+                      const int* ystart, const int* ycount, const float* yw, int Ty, const int* xstart, const int* xcount,
+                      const float* xw, int Tx, int row0, int rows, float* workspace, size_t workspace_bytes, const float* ccms,
+                      float gamma, const float* crf_E, const float* crf_f, int crf_n, void* stream);
+int eld_frame_rgb_tile(int* tile_h, int* tile_w, int* lds_bytes);
 
 #ifdef __cplusplus
 }
